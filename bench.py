@@ -1,6 +1,6 @@
 """bench.py -- denoising steps/sec of the MagCache hot path on MI355X (the driver's contract).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workload (BASELINE.json configs[1]): Wan2.1-T2V-1.3B, 480p, 81 frames -> latent 16x21x60x104,
@@ -9,8 +9,11 @@ thresh 0.12, K 4, retention 0.2 (the README command, MagCache4Wan2.1/README.md:1
 T2V-1.3B resampled to the step count exactly as the reference does (:915-919).  Synthetic latents,
 synthetic contexts, random-init weights of the real architecture (no checkpoint offline).
 `value` = K / wall time of the timed MagCache region (whole job; N>1 = the same video with the token
-sequence sharded over N GPUs, i.e. strong scaling).  A second timed region runs the same K steps
-with the cache off for `speedup_vs_nocache`.
+sequence sharded over N GPUs, i.e. strong scaling); `ms_per_step` = its wall time / K.  A plain run
+does only that.  With --full, a second timed region runs the same K steps with the cache off for
+`speedup_vs_nocache` and PSNR, followed by the live per-class kernel times, the back-to-back
+per-kernel table, the live PMC pass and the CPU baseline.  --dump-outputs DIR writes the final
+latent of the timed region (DIR/latent.npy, fp32, 8.4 MB).
 """
 import argparse
 import json
@@ -492,6 +495,12 @@ def build_parser():
     ap.add_argument("--retention_ratio", type=float, default=0.2)
     ap.add_argument("--guide_scale", type=float, default=5.0)
     ap.add_argument("--shift", type=float, default=5.0)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the second (cache off) timed region (speed-up, PSNR), "
+                         "the live per-class kernel times, the back-to-back per-kernel table, the live PMC pass and the CPU "
+                         "baseline; the --no_* flags below drop single parts of it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the final latent of the timed MagCache region (what sample() returns) as DIR/latent.npy, fp32")
     ap.add_argument("--no_cpu_baseline", action="store_true")
     ap.add_argument("--no_kernels", action="store_true")
     ap.add_argument("--no_nocache", action="store_true", help="skip the second (cache off) timed region")
@@ -512,6 +521,9 @@ def bench_main():
     args = build_parser().parse_args()
     if args.no_cfg_parallel:
         args.layout = "sp"
+    if not args.full:
+        # a plain run is repeated for every change: set-up, warm-up, the timed MagCache region, the line
+        args.no_nocache = args.no_kernels = args.no_table = args.no_cpu_baseline = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -688,6 +700,11 @@ def bench_main():
         cnt = torch.tensor([skipped if first else 0], device=device, dtype=torch.int64)
         dist.all_reduce(cnt)
         skipped = int(cnt[0])
+    if args.dump_outputs and rank == 0:
+        # every rank holds the same replica of the latent; fixed seeds make it comparable between two builds
+        stage("dump outputs")
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "latent.npy"), lat_mc.float().cpu().numpy())
     # ---- timed region 2: the same K steps with the cache off
     t_nc, psnr, attn_live = None, None, None
     stage("timed region 2 (no cache)")

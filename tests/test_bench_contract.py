@@ -53,6 +53,10 @@ def test_contract_line_fields_from_bench_own_assembly_with_stubbed_timings():
     B = _bench()
     args = B.build_parser().parse_args(["--steps", "50", "--warmup", "5"])
     assert args.gpus == 1 and args.magcache_K == 4 and args.magcache_thresh == 0.12 and args.retention_ratio == 0.2
+    # a plain run times the headline only; the rest of the measurements and the output dump are asked for
+    assert args.full is False and args.dump_outputs is None
+    af = B.build_parser().parse_args(["--steps", "3", "--full", "--dump-outputs", "out"])
+    assert af.full is True and af.dump_outputs == "out" and af.steps == 3
     from magcache_amd.engine import WAN_T2V_1_3B
     fl = B.flops_forward(WAN_T2V_1_3B, B.SEQ, ctx_cached=True)
     sched = _schedule(4)

@@ -454,7 +454,8 @@ def test_bench_two_ranks_one_gpu(nproc, extra, par, steps):
     log-sum-exp over 4 rounds; cfg2 x sp4 = 8190 of 8192 rows.  Two steps keep the gloo traffic (1.4 GB per layer through host
     memory) inside a test; whatever the rule skips in step 1, the check is the FINAL LATENT itself against the single-process run."""
     env = dict(os.environ, PYTHONPATH=ROOT, MC_BENCH_BACKEND="gloo", MC_BENCH_ABLATION_STEPS="1")
-    base = [os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "0", "--no_cpu_baseline", "--no_table"]
+    base = [os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "0", "--full", "--no_cpu_baseline",
+            "--no_table"]
     if nproc >= 4:
         base.append("--no_kernels")
     if steps <= 4:
@@ -516,6 +517,28 @@ def test_bench_two_ranks_one_gpu(nproc, extra, par, steps):
     if got["layout"] == "sp" or nproc > 2 or par is None:
         # overlapped (local-shard attention beside the K/V all-gather) vs serialised sequence-parallel forward
         assert got["sp_selfcheck_rel"] <= 3e-3 and got["sp_overlap"] is True
+
+
+def test_bench_plain_run_times_the_headline_only_and_dumps_its_latent(tmp_path):
+    """bench.py without --full (the run repeated for every change): the timed MagCache region and its line, none of the
+    cache-off region, kernel tables or CPU baseline; --dump-outputs writes the final latent that region returned."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], env=dict(os.environ, PYTHONPATH=ROOT), capture_output=True,
+                       text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 5 and d["warmup"] == 1 and d["forwards_total"] == 10 and d["dtype"] == "bf16"
+    assert d["value"] > 0 and d["value"] == pytest.approx(1e3 / d["ms_per_step"], rel=1e-9)
+    assert d["nocache_steps_per_s"] is None and d["final_latent_probe"]["nocache"] is None
+    assert not {"roofline", "kernels", "kernels_live", "cpu_baseline"} & set(d)
+    lat = np.load(tmp_path / "latent.npy")
+    assert lat.dtype == np.float32 and lat.shape == (16, 21, 60, 104) and np.isfinite(lat).all()
+    p = d["final_latent_probe"]["magcache"]
+    flat = lat.reshape(-1)
+    assert abs(float(np.linalg.norm(flat.astype(np.float64))) - p["l2"]) < 1e-4 * p["l2"]
+    assert p["samples"][0] == float(flat[0]) and p["samples"][-1] == float(flat[-1])
 
 
 def test_wan22_two_experts_i2v_vs_oracle():

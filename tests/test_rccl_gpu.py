@@ -40,7 +40,7 @@ def test_bench_line_through_rccl_at_world_one():
     between the timed regions, teardown) runs on RCCL with one rank; the line reports rccl_world = 1."""
     env = dict(_env(29583), MC_BENCH_FORCE_DIST="1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "0",
-                        "--no_cpu_baseline", "--no_kernels"], env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--no_cpu_baseline", "--no_kernels"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["rccl_world"] == 1 and line["comm_backend"] == "nccl" and line["n_gpus"] == 1
@@ -53,8 +53,8 @@ def test_bench_whole_multi_gpu_flow_on_one_gpu_through_the_library_side_rccl():
     forwards, the library-side RCCL communicator with ONE mc_forward_sp_rccl per forward, the N > 1 report (sp_collective,
     sp_gather_wait, rank 0's launch classes, per-GPU roofline) -- on the one GPU there is, with the real collective library.
     The final latents equal the plain single-GPU run's."""
-    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "0", "--no_cpu_baseline",
-            "--no_table"]
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "0", "--full",
+            "--no_cpu_baseline", "--no_table"]
     r = subprocess.run(base, env=dict(_env(29585), MC_BENCH_FORCE_DIST="1", MC_BENCH_FORCE_SP="1"), capture_output=True, text=True,
                        timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]

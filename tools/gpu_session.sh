@@ -9,7 +9,7 @@
 #   pytest[:expr]      pytest -m gpu (optionally -k expr)
 #   pytest_slow        the slow-marked full-size parity runs
 #   smoke              __graft_entry__.smoke()
-#   bench[:args]       python bench.py <args, ':'-separated>  (default: --steps 20 --warmup 5)
+#   bench[:args]       python bench.py <args, ':'-separated>  (default: --steps 20 --warmup 5 --full)
 #   stats[:steps]      rocprofv3 --kernel-trace --stats over a short bench run WITHOUT the back-to-back table (its 1 s pre-heats would swamp the summary); summary csv kept
 #   py:<script>[:args] python <script> args (tools/*.py probes)
 set -u
@@ -89,13 +89,13 @@ for step in "$@"; do
       timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > "$out/smoke.log" 2>&1; echo "smoke exit: $?" >> "$out/smoke.log"; tail -5 "$out/smoke.log"
       ;;
     bench)
-      args="${a[@]:1}"; [ -z "$args" ] && args="--steps 20 --warmup 5"
+      args="${a[@]:1}"; [ -z "$args" ] && args="--steps 20 --warmup 5 --full"
       name=$(echo "bench_$args" | tr -c 'A-Za-z0-9_\n' '_')
       timeout 900 python bench.py $args > "$out/$name.log" 2>&1; echo "bench exit: $?" >> "$out/$name.log"; tail -3 "$out/$name.log"
       ;;
     stats)
       steps=${a[1]:-6}
-      (cd /tmp && export TMPDIR=/tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/stats_$tag -o s -- python "$R/bench.py" --steps $steps --warmup 1 --no_cpu_baseline --no_table > "$out/stats_run.log" 2>&1; echo "rocprof exit: $?" >> "$out/stats_run.log")
+      (cd /tmp && export TMPDIR=/tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/stats_$tag -o s -- python "$R/bench.py" --steps $steps --warmup 1 --full --no_cpu_baseline --no_table > "$out/stats_run.log" 2>&1; echo "rocprof exit: $?" >> "$out/stats_run.log")
       f=$(find /tmp/stats_$tag -name "*kernel_stats.csv" | head -1)
       [ -n "$f" ] && cp "$f" "$out/kernel_stats_bench_steps$steps.csv" && head -25 "$out/kernel_stats_bench_steps$steps.csv"
       tail -2 "$out/stats_run.log"

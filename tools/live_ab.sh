@@ -7,7 +7,7 @@ for n in "$@"; do
   if [ "$n" = shipped ]; then cp /tmp/shipped.so magcache_amd/libmagcache_hip.so
   elif [ -d build_variants/$n ]; then cp build_variants/$n/libmagcache_hip.so magcache_amd/libmagcache_hip.so
   else cp build_variants/v5_$n/libmagcache_hip.so magcache_amd/libmagcache_hip.so; fi
-  i=$((i+1)); MC_BENCH_PMC=0 timeout 600 python bench.py --steps 20 --warmup 5 --no_cpu_baseline --no_table > $out/bench_${i}_$n.log 2>&1
+  i=$((i+1)); MC_BENCH_PMC=0 timeout 600 python bench.py --steps 20 --warmup 5 --full --no_cpu_baseline --no_table > $out/bench_${i}_$n.log 2>&1
   python3 - $out/bench_${i}_$n.log $n <<'PY'
 import json,sys
 for l in open(sys.argv[1]):
