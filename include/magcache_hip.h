@@ -444,6 +444,17 @@ mc_status mc_op_calib_stats(const float* r_dev, long ldr, const float* rp_dev, l
                             mc_stream stream);
 mc_status mc_op_cfg_euler(const float* cond_dev, const float* uncond_dev, float guide, float dt, float* x_dev,
                           float* eps_out_dev, size_t n, mc_stream stream);
+/* Qwen-Image's true-CFG step (QwenImagePipeline norm-preserving combine + FlowMatchEulerDiscreteScheduler.step), one fp32
+ * pass, in place on x: per token row m < n_rows of C (<= 256) channels, comb = u + guide (c - u), v = comb * |c| / |comb|
+ * (norms over the channels of the row), x[m] += dt * v with dt = sigma_next - sigma.  A row whose |comb| is 0 gets v = 0
+ * (upstream: 0 / 0 = NaN).  cond / uncond rows have stride ld_pred and may hold more rows than are updated (Qwen-Image-
+ * Edit: the reference-image tokens after the first n_rows). */
+mc_status mc_op_cfg_norm_euler(const float* cond_dev, const float* uncond_dev, long ld_pred, float guide, float dt,
+                               float* x_dev, long ldx, int n_rows, int C, mc_stream stream);
+/* weighted row RMSNorm to bf16 (Qwen-Image txt_norm, eps 1e-6): out[m] = bf16(x[m] * rsqrt(mean(x[m]^2) + eps) * w) for
+ * m < rows_valid; rows [rows_valid, rows) are written as zeros.  D, ldx, ldo multiples of 4. */
+mc_status mc_op_rmsnorm_rows_bf16(const float* x_dev, long ldx, const float* w_dev, float eps, void* out_bf16_dev, long ldo,
+                                  int rows_valid, int rows, int D, mc_stream stream);
 /* out[i] = sum_j coef[j] * xs[j][i]: xs = HOST array of k (1..6) device pointers, coef = host array of k
  * floats; out may alias an operand.  The sampler's solver updates around the model call -- CFG combine and
  * the UniPC / DPM++ / Euler flow steps of the upstream pipeline (wan_magcache.py:296-310) -- are one launch

@@ -9,6 +9,9 @@
  *                  accumulated_ratio/err/steps, previous_residual; :452-470)
  *   HunyuanVideo  HYVideoDiffusionTransformer.forward = magcache_forward  MagCache4HunyuanVideo/magcache_sample_video.py:29-160
  *                 (cnt, num_steps, ..., residual_cache; :300-330)
+ *   Qwen-Image    QwenImageTransformer2DModel.forward = magcache_forward  MagCache4QwenImage/magcache_generate.py:173-253
+ *   (and -Edit)   (cnt, num_steps, K, magcache_thresh, retention_ratio, accumulated_*[2], residual_cache[2]; :63-83),
+ *                 MagCache4QwenImageEdit/magcache_generate.py (same functions, more image tokens)
  * Everything those functions do between their arguments and their return value is one mc_mmdit_forward call; the
  * decision rule stays on the host (scalar state, `<=`, the FLUX step-11 exclusion: see mc_rule_* in magcache_hip.h
  * and magcache_amd/mmdit.py).  The transformer blocks themselves are upstream code (huggingface/diffusers
@@ -39,22 +42,28 @@ typedef struct mc_mmdit mc_mmdit;
 
 typedef enum {
   MC_FAMILY_FLUX = 0,    /* token order [text ; image], RoPE on every token (ids), packed-latent tokens in and out */
-  MC_FAMILY_HUNYUAN = 1  /* token order [image ; text], RoPE on image tokens, Conv3d (1,2,2) patch embedding,
+  MC_FAMILY_HUNYUAN = 1, /* token order [image ; text], RoPE on image tokens, Conv3d (1,2,2) patch embedding,
                             SingleTokenRefiner on the text states, text attention mask (valid prefix) */
+  MC_FAMILY_QWEN = 2     /* Qwen-Image / Qwen-Image-Edit: token order [text ; image], double-stream blocks only
+                            (n_single == 0), no pooled vector and no guidance embedding (vec_dim == 0), weighted RMSNorm
+                            on the text states before txt_in, a text length that varies per call (txt_valid <= txt_len),
+                            two CFG residual slots (mc_mmdit_forward2), one GPU (sp_size 1) */
 } mc_family;
 
 typedef struct {
   int family;
   int dim, num_heads;       /* head_dim is 128 */
-  int n_double, n_single;   /* 19 / 38 (FLUX.1-dev), 20 / 40 (HunyuanVideo) */
-  int in_channels;          /* FLUX: 64 token features; HunyuanVideo: 16 latent channels */
+  int n_double, n_single;   /* 19 / 38 (FLUX.1-dev), 20 / 40 (HunyuanVideo), 60 / 0 (Qwen-Image) */
+  int in_channels;          /* FLUX, Qwen-Image: 64 token features; HunyuanVideo: 16 latent channels */
   int out_channels;         /* FLUX: 64 token features; HunyuanVideo: 16 */
-  int txt_dim, txt_len;     /* T5 4096 x 512 (FLUX), LLaVA 4096 x 256 (HunyuanVideo) */
-  int vec_dim;              /* pooled CLIP text embedding, 768 */
-  int img_tokens;           /* FLUX: (H/16)*(W/16); HunyuanVideo: F * (H/2) * (W/2) of the latent grid below */
+  int txt_dim, txt_len;     /* T5 4096 x 512 (FLUX), LLaVA 4096 x 256 (HunyuanVideo), Qwen2.5-VL 3584 x the longest
+                               prompt of a sample (Qwen-Image: txt_len is the maximum, txt_valid the length of a call) */
+  int vec_dim;              /* pooled CLIP text embedding, 768; Qwen-Image: 0 */
+  int img_tokens;           /* FLUX: (H/16)*(W/16); HunyuanVideo: F * (H/2) * (W/2) of the latent grid below;
+                               Qwen-Image-Edit: noisy tokens + reference-image tokens */
   int latent_f, latent_h, latent_w; /* HunyuanVideo latent [16, F, H, W]; FLUX: ignored */
   int refiner_depth;        /* HunyuanVideo txt_in blocks (2); FLUX: 0 */
-  int calibration;          /* reserve the second residual slot calibration mode needs */
+  int calibration;          /* reserve the second residual slot calibration mode needs (per CFG branch: Qwen-Image) */
   int sp_rank, sp_size;     /* sequence parallel: this rank owns image tokens [rank, rank+1) * img_tokens / sp_size; the
                                text tokens are replicated.  0, 1 (or 0, 0) for one GPU */
 } mc_mmdit_config;
@@ -71,19 +80,30 @@ int mc_mmdit_weights_missing(const mc_mmdit* e, char* buf, size_t buflen);
 
 /* RoPE table for the joint sequence, rows in the engine's token order: cos_dev / sin_dev are the upstream
  * "use_real" tables [n_rows, 128] (every frequency repeated twice; FluxPosEmbed(ids) / get_nd_rotary_pos_embed).
- * FLUX: n_rows = txt_len + img_tokens (text rows first); HunyuanVideo: n_rows = img_tokens. */
+ * FLUX, Qwen-Image: n_rows = txt_len + img_tokens (text rows first; Qwen-Image: the table of the MAXIMUM text length,
+ * text row j at QwenEmbedRope position max(h/2, w/2) + j, so a shorter call uses its first txt_valid rows);
+ * HunyuanVideo: n_rows = img_tokens. */
 mc_status mc_mmdit_set_rope(mc_mmdit* e, const float* cos_dev, const float* sin_dev, int n_rows, mc_stream stream);
 
 /* One transformer evaluation (the body of the reference's magcache_forward).
  *   img_dev    FLUX: packed latent tokens [img_tokens, in_channels]; HunyuanVideo: latent [16, F, H, W]   (fp32)
  *   timestep   the value the embedding sees: FLUX timestep*1000 (:303), HunyuanVideo t (:54); guidance likewise
  *   txt_dev    text states [txt_len, txt_dim] fp32; txt_valid = number of valid rows (HunyuanVideo text_mask.sum();
- *              FLUX attends all txt_len rows and ignores it)
- *   vec_dev    pooled text embedding [vec_dim] fp32
+ *              FLUX attends all txt_len rows and ignores it).  Qwen-Image: [txt_valid, txt_dim] (only those rows are
+ *              read), 0 < txt_valid <= txt_len: the attention visits exactly txt_valid text keys and all image keys
+ *   vec_dev    pooled text embedding [vec_dim] fp32 (Qwen-Image: none, may be NULL; guidance is ignored)
  *   mode       MC_MODE_FULL / MC_MODE_SKIP / MC_MODE_CALIB with the meaning of magcache_hip.h (one residual slot)
  *   out_dev    FLUX: [img_tokens, out_channels] fp32; HunyuanVideo: [16, F, H, W] fp32 */
 mc_status mc_mmdit_forward(mc_mmdit* e, const float* img_dev, double timestep, double guidance, const float* txt_dev,
                            int txt_valid, const float* vec_dev, mc_mode mode, float* out_dev, mc_stream stream);
+/* The same forward on one of two CFG branches (cond = 0, uncond = 1), each with its own residual cache (and, with
+ * calibration, its own previous residual): MC_MODE_SKIP adds the branch's cached residual, MC_MODE_CALIB compares with
+ * the branch's previous one -- the reference's residual_cache[cnt % 2] (MagCache4QwenImage/magcache_generate.py:224-244).
+ * branch 1 is MC_FAMILY_QWEN only; mc_mmdit_forward is branch 0.  Buffer "residual" (mc_mmdit_buffer_info) is the
+ * cache of the branch of the last forward, "residual_b0" / "residual_b1" the cache of that branch. */
+mc_status mc_mmdit_forward2(mc_mmdit* e, const float* img_dev, double timestep, double guidance, const float* txt_dev,
+                            int txt_valid, const float* vec_dev, mc_mode mode, int branch, float* out_dev,
+                            mc_stream stream);
 /* The same forward in phases, for sequence parallelism: after every mc_mmdit_block_pre the caller all-gathers
  * "kv_gather" ([sp_size][Lr_pad][2*dim] bf16; this rank's image K|V rows were put into slot sp_rank) with its own
  * communicator (torch.distributed / RCCL), then calls mc_mmdit_block_post, which attends the local queries over all

@@ -119,6 +119,8 @@ SIGNATURES = {
     "mc_op_calib_stats": (_i, [_vp, _l, _vp, _l, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "mc_op_cfg_euler": (_i, [_vp, _vp, _f, _f, _vp, _vp, _sz, _vp]),
     "mc_op_cast_bf16": (_i, [_vp, _vp, _sz, _vp]),
+    "mc_op_cfg_norm_euler": (_i, [_vp, _vp, _l, _f, _f, _vp, _l, _i, _i, _vp]),
+    "mc_op_rmsnorm_rows_bf16": (_i, [_vp, _l, _vp, _f, _vp, _l, _i, _i, _i, _vp]),
     "mc_op_lincomb": (_i, [_vp, _vp, _i, _vp, _sz, _vp]),
     "mc_op_rope_table": (_i, [_i, _i, _i, _i, _i, _vp]),
     # include/magcache_mmdit.h
@@ -131,6 +133,7 @@ SIGNATURES = {
     "mc_mmdit_weights_missing": (_i, [_vp, C.c_char_p, _sz]),
     "mc_mmdit_set_rope": (_i, [_vp, _vp, _vp, _i, _vp]),
     "mc_mmdit_forward": (_i, [_vp, _vp, _d, _d, _vp, _i, _vp, _i, _vp, _vp]),
+    "mc_mmdit_forward2": (_i, [_vp, _vp, _d, _d, _vp, _i, _vp, _i, _i, _vp, _vp]),
     "mc_mmdit_begin": (_i, [_vp, _vp, _d, _d, _vp, _i, _vp, _i, _vp]),
     "mc_mmdit_block_pre": (_i, [_vp, _i, _vp]),
     "mc_mmdit_block_attn_local": (_i, [_vp, _i, _vp]),
@@ -148,7 +151,7 @@ class McMmditConfig(C.Structure):
                                        "refiner_depth", "calibration", "sp_rank", "sp_size")]
 
 
-MC_FAMILY_FLUX, MC_FAMILY_HUNYUAN = 0, 1
+MC_FAMILY_FLUX, MC_FAMILY_HUNYUAN, MC_FAMILY_QWEN = 0, 1, 2
 
 _lib = None
 

@@ -535,6 +535,69 @@ __global__ void cfg_euler_kernel(const float* __restrict__ cond, const float* __
   }
 }
 
+// Qwen-Image txt_norm: out[m, :] = bf16(x[m, :] * rsqrt(mean(x[m, :]^2) + eps) * w) for m < rows_valid, zero rows up to
+// `rows` (the padded text rows).  One wave per row, 4 floats per lane per step.  (Upstream RMSNorm multiplies by the weight
+// in fp32 when the weight is fp32; its bf16 mode rounds before the weight -- the fp32 form is the one restated here.)
+__global__ __launch_bounds__(256) void rmsnorm_rows_bf16_kernel(const float* __restrict__ x, long ldx,
+                                                                const float* __restrict__ w, float eps,
+                                                                bf16_t* __restrict__ out, long ldo, int rows_valid,
+                                                                int rows, int D) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  bf16_t* orow = out + (size_t)row * ldo;
+  if (row >= rows_valid) {
+    for (int e = lane * 4; e < D; e += 256) *(u32x2*)(orow + e) = u32x2{0u, 0u};
+    return;
+  }
+  const float* xr = x + (size_t)row * ldx;
+  float ss = 0.f;
+  for (int e = lane * 4; e < D; e += 256) {
+    const f32x4 v = *(const f32x4*)(xr + e);
+    ss += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
+  }
+  const float rstd = rsqrtf(wave_sum(ss) / (float)D + eps);
+  for (int e = lane * 4; e < D; e += 256) {
+    const f32x4 v = *(const f32x4*)(xr + e), wv = *(const f32x4*)(w + e);
+    *(u32x2*)(orow + e) = u32x2{pack_bf16x2(v[0] * rstd * wv[0], v[1] * rstd * wv[1]),
+                                pack_bf16x2(v[2] * rstd * wv[2], v[3] * rstd * wv[3])};
+  }
+}
+
+// Qwen-Image true-CFG step (QwenImagePipeline + FlowMatchEulerDiscreteScheduler.step), one wave per token row of C <= 256
+// channels, fp32 throughout:  comb = u + g (c - u);  v = comb * |c| / |comb|  (norms over the row);  x += dt * v.
+// |comb| == 0 (comb is the zero row): v = 0, where the upstream division gives NaN.  Rows >= n_rows are not touched.
+__global__ __launch_bounds__(256) void cfg_norm_euler_kernel(const float* __restrict__ cond, const float* __restrict__ uncond,
+                                                             long ldp, float g, float dt, float* __restrict__ x, long ldx,
+                                                             int n_rows, int C) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= n_rows) return;
+  const float* cr = cond + (size_t)row * ldp;
+  const float* ur = uncond + (size_t)row * ldp;
+  float comb[4], cc = 0.f, nn = 0.f;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int ch = lane + 64 * j;
+    comb[j] = 0.f;
+    if (ch < C) {
+      const float c = cr[ch], u = ur[ch];
+      comb[j] = u + g * (c - u);
+      cc += c * c;
+      nn += comb[j] * comb[j];
+    }
+  }
+  cc = wave_sum(cc);
+  nn = wave_sum(nn);
+  const float f = nn > 0.f ? sqrtf(cc) / sqrtf(nn) : 0.f;
+  float* xr = x + (size_t)row * ldx;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int ch = lane + 64 * j;
+    if (ch < C) xr[ch] = xr[ch] + dt * (comb[j] * f);
+  }
+}
+
 __global__ void add_bf16_kernel(bf16_t* __restrict__ a, const bf16_t* __restrict__ b, size_t n8) {
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n8; i += (size_t)gridDim.x * blockDim.x) {
     u32x4 x = ((const u32x4*)a)[i], y = ((const u32x4*)b)[i], o;
@@ -791,6 +854,24 @@ hipError_t launch_cfg_euler(const float* cond, const float* uncond, float g, flo
                             size_t n, hipStream_t stream) {
   hipLaunchKernelGGL(cfg_euler_kernel, dim3(grid_for((long)n, 256)), dim3(256), 0, stream, cond, uncond, g, dt, x,
                      eps_out, n);
+  return hipGetLastError();
+}
+
+hipError_t launch_rmsnorm_rows_bf16(const float* x, long ldx, const float* w, float eps, bf16_t* out, long ldo,
+                                    int rows_valid, int rows, int D, hipStream_t stream) {
+  if (D <= 0 || (D % 4) != 0 || (ldx % 4) != 0 || (ldo % 4) != 0 || rows_valid < 0 || rows_valid > rows) return hipErrorInvalidValue;
+  if (rows == 0) return hipSuccess;
+  hipLaunchKernelGGL(rmsnorm_rows_bf16_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, x, ldx, w, eps, out, ldo,
+                     rows_valid, rows, D);
+  return hipGetLastError();
+}
+
+hipError_t launch_cfg_norm_euler(const float* cond, const float* uncond, long ldp, float g, float dt, float* x, long ldx,
+                                 int n_rows, int C, hipStream_t stream) {
+  if (C <= 0 || C > 256 || ldp < C || ldx < C || n_rows < 0) return hipErrorInvalidValue;
+  if (n_rows == 0) return hipSuccess;
+  hipLaunchKernelGGL(cfg_norm_euler_kernel, dim3((n_rows + 3) / 4), dim3(256), 0, stream, cond, uncond, ldp, g, dt, x, ldx,
+                     n_rows, C);
   return hipGetLastError();
 }
 

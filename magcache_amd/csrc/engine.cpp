@@ -1917,6 +1917,24 @@ mc_status mc_op_cfg_euler(const float* cond, const float* uncond, float guide, f
   return MC_OK;
 }
 
+mc_status mc_op_cfg_norm_euler(const float* cond, const float* uncond, long ld_pred, float guide, float dt, float* x, long ldx,
+                               int n_rows, int C, mc_stream s) {
+  if (!cond || !uncond || !x) return fail(MC_EINVAL, "null argument");
+  hipError_t err = mc::launch_cfg_norm_euler(cond, uncond, ld_pred, guide, dt, x, ldx, n_rows, C, (hipStream_t)s);
+  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "cfg_norm_euler: 0 < C <= 256, ld_pred / ldx >= C, n_rows >= 0");
+  HIP_TRY(err);
+  return MC_OK;
+}
+
+mc_status mc_op_rmsnorm_rows_bf16(const float* x, long ldx, const float* w, float eps, void* out, long ldo, int rows_valid,
+                                  int rows, int D, mc_stream s) {
+  if (!x || !w || !out) return fail(MC_EINVAL, "null argument");
+  hipError_t err = mc::launch_rmsnorm_rows_bf16(x, ldx, w, eps, (bf16_t*)out, ldo, rows_valid, rows, D, (hipStream_t)s);
+  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "rmsnorm_rows_bf16: D, ldx, ldo multiples of 4, 0 <= rows_valid <= rows");
+  HIP_TRY(err);
+  return MC_OK;
+}
+
 mc_status mc_op_lincomb(const float* const* xs_dev, const float* coef, int k, float* out_dev, size_t n, mc_stream s) {
   if (!xs_dev || !coef) return fail(MC_EINVAL, "null argument");
   hipError_t err = mc::launch_lincomb(xs_dev, coef, k, out_dev, n, (hipStream_t)s);

@@ -1,9 +1,18 @@
-// MM-DiT engine behind include/magcache_mmdit.h: FLUX.1 (diffusers FluxTransformer2DModel) and HunyuanVideo
-// (hyvideo HYVideoDiffusionTransformer) forward with the MagCache skip path, on the kernels of this library.
+// MM-DiT engine behind include/magcache_mmdit.h: FLUX.1 (diffusers FluxTransformer2DModel), HunyuanVideo
+// (hyvideo HYVideoDiffusionTransformer) and Qwen-Image (diffusers QwenImageTransformer2DModel) forward with the MagCache
+// skip path, on the kernels of this library.
 //
-// Reference boundary: the body of magcache_forward in MagCache4FLUX/magcache_flux.py:301-432 and
-// MagCache4HunyuanVideo/magcache_sample_video.py:40-146; the blocks are upstream code (see oracle/flux_ref.py and
-// oracle/hunyuan_ref.py for the restatement this engine is tested against).
+// Reference boundary: the body of magcache_forward in MagCache4FLUX/magcache_flux.py:301-432,
+// MagCache4HunyuanVideo/magcache_sample_video.py:40-146 and MagCache4QwenImage/magcache_generate.py:186-253; the blocks
+// are upstream code (see oracle/flux_ref.py, oracle/hunyuan_ref.py and tests/qwen_image_ref.py for the restatements this
+// engine is tested against).
+//
+// Qwen-Image (MC_FAMILY_QWEN) is FLUX's double block 60 times with no single blocks: rows [text ; image] like FLUX, the
+// text rows sized for the longest prompt (txt_len) and the call's prompt in the first txt_valid of them.  The padded text
+// rows [txt_valid, txt_len) are zero after txt_in (EPI_EMBED m_valid) and stay finite; they are left out of the key set
+// by attending the image keys and the txt_valid text keys in two launches merged by their log-sum-exp (the sequence-
+// parallel machinery), so the result is that of the unpadded sequence.  The two CFG branches keep their own residual
+// slots (residual_cache[cnt % 2] of the reference).
 //
 // Data layout in HBM (one caller-owned workspace; d = dim, S = txt_len + img_tokens, S_pad = S up to 256):
 //   x    fp32 [S_pad, d]    joint residual stream.  Row order = the family's attention order: FLUX [text ; image],
@@ -16,7 +25,8 @@
 //   am   bf16 [S_pad, 5d]   columns [0,d): attention output; [d,5d): GELU(MLP-in) -- exactly the operand of the
 //                           single block's fused output projection (cat([attn, mlp]) upstream) with K = 5d
 //   emod fp32               every block's modulation vector, produced by ONE bf16-weight GEMV over silu(vec)
-//   residual0/1 fp32 [S_pad, d] MagCache residual cache (+ the previous one in calibration mode), joint row index: the
+//   residual0/1 fp32 [S_pad, d] MagCache residual cache (+ the previous one in calibration mode; Qwen-Image: per CFG
+//                           branch, residual0..3 with calibration), joint row index: the
 //                           capture is the epilogue of the LAST block's output GEMM (R = x_new - x0 per row); the image
 //                           rows are the cache, the text rows are scratch
 // GEMMs over one stream use the exact row count (the 256^2 kernel guards a partial last tile), so neighbouring
@@ -113,6 +123,7 @@ struct mc_mmdit {
   int P = 1, rank = 0, tok0 = 0, Lrp = 0;                    // sequence parallel: image shard [tok0, tok0 + Li)
   mc_mode mode = MC_MODE_FULL;                               // of the forward in progress (begin .. end)
   int txt_valid = 0, dst = 0, local_attn_blk = -1;
+  int branch = 0;                                            // CFG branch of the forward in progress (Qwen-Image: 0 / 1)
   bool begun = false;
   // optional second compute stream: the text stream of a double block next to the image stream (mc_set_option
   // "mmdit_two_streams"); a ring of event pairs so that an event is not re-recorded while an earlier wait on it may
@@ -127,21 +138,27 @@ struct mc_mmdit {
   Mlp2 time_mlp, guid_mlp, vec_mlp, ref_t_mlp, ref_c_mlp;
   bf16_t *w_in = nullptr, *w_ctx = nullptr, *w_mod = nullptr;
   float *b_in = nullptr, *b_ctx = nullptr, *b_mod = nullptr, *w_head = nullptr, *b_head = nullptr;
+  float* w_txt_norm = nullptr;  // Qwen-Image txt_norm (RMSNorm over txt_dim)
   float* cs = nullptr;  // RoPE (cos,sin) [Sp][64][2]
   std::map<std::string, Slot> slots;
   std::vector<void*> owned;
   char* ws = nullptr;
   size_t ws_need = 0;
   std::map<std::string, Buf> bufs;
-  int res_cur = 0;  // slot holding residual_cache / previous_residual
-  bool have_res = false, have_stats = false, pads_clean = false;
+  int res_cur[2] = {0, 0};  // per CFG branch: the slot (of the branch's own) holding residual_cache / previous_residual
+  bool have_res[2] = {false, false}, have_stats = false, pads_clean = false;
 
   template <class T>
   T* buf(const char* name) const {
     return reinterpret_cast<T*>(ws + bufs.find(name)->second.off);
   }
-  float* residual_joint(int i) const { return buf<float>(i ? "residual1" : "residual0"); }
-  float* residual(int i) const { return residual_joint(i) + (size_t)img0 * d; }   // image rows
+  // slot i (0 / 1) of CFG branch b: residual<b * slots_per_branch + i>; branch 0 is residual0 / residual1 as before
+  int res_index(int b, int i) const { return b * (cfg.calibration ? 2 : 1) + i; }
+  float* residual_joint(int i, int b = 0) const {
+    static const char* nm[4] = {"residual0", "residual1", "residual2", "residual3"};
+    return buf<float>(nm[res_index(b, i)]);
+  }
+  float* residual(int i, int b = 0) const { return residual_joint(i, b) + (size_t)img0 * d; }   // image rows
   size_t mod_double(int blk, int stream) const { return ((size_t)blk * 2 + stream) * 6 * d; }
   size_t mod_single(int blk) const { return (size_t)cfg.n_double * 12 * d + (size_t)blk * 3 * d; }
   size_t mod_final() const { return (size_t)cfg.n_double * 12 * d + (size_t)cfg.n_single * 3 * d; }
@@ -217,19 +234,25 @@ mc_status mc_mmdit_create(const mc_mmdit_config* cfg, mc_mmdit** out) {
   if (!cfg || !out) return fail(MC_EINVAL, "null argument");
   const mc_mmdit_config& c = *cfg;
   const bool hy = c.family == MC_FAMILY_HUNYUAN;
-  if (c.family != MC_FAMILY_FLUX && !hy) return fail(MC_EINVAL, "unknown family %d", c.family);
+  const bool qw = c.family == MC_FAMILY_QWEN;
+  if (c.family != MC_FAMILY_FLUX && !hy && !qw) return fail(MC_EINVAL, "unknown family %d", c.family);
   if (c.num_heads <= 0 || c.dim != c.num_heads * 128) return fail(MC_EINVAL, "dim must be num_heads * 128 (head_dim 128)");
   if ((c.dim % 256) != 0) return fail(MC_EINVAL, "dim %d must be a multiple of 256", c.dim);
   if (c.n_double < 0 || c.n_single < 0 || c.n_double + c.n_single == 0) return fail(MC_EINVAL, "no blocks");
-  if (c.txt_len <= 0 || c.txt_dim <= 0 || (c.txt_dim % 64) != 0 || c.vec_dim <= 0 || (c.vec_dim % 8) != 0)
+  if (c.txt_len <= 0 || c.txt_dim <= 0 || (c.txt_dim % 64) != 0 || (!qw && (c.vec_dim <= 0 || (c.vec_dim % 8) != 0)))
     return fail(MC_EINVAL, "bad text geometry");
+  if (qw) {
+    if (c.n_single != 0) return fail(MC_EINVAL, "Qwen-Image has no single-stream blocks (n_single %d)", c.n_single);
+    if (c.vec_dim != 0) return fail(MC_EINVAL, "Qwen-Image has no pooled text vector (vec_dim %d)", c.vec_dim);
+    if (c.sp_size > 1) return fail(MC_EINVAL, "Qwen-Image runs on one GPU (sp_size %d)", c.sp_size);
+  }
   if (c.img_tokens <= 0) return fail(MC_EINVAL, "img_tokens must be positive");
   if (hy) {
     if ((c.latent_h & 1) || (c.latent_w & 1) || c.img_tokens != c.latent_f * (c.latent_h / 2) * (c.latent_w / 2))
       return fail(MC_EINVAL, "img_tokens must equal F*(H/2)*(W/2) of the latent grid");
     if (c.out_channels * 4 > 64) return fail(MC_EINVAL, "out_channels*4 > 64 unsupported by the head kernel");
   } else if (c.out_channels > 64 || c.refiner_depth != 0) {
-    return fail(MC_EINVAL, "FLUX: out_channels <= 64, no refiner");
+    return fail(MC_EINVAL, "FLUX / Qwen-Image: out_channels <= 64, no refiner");
   }
   mc_mmdit* e = new mc_mmdit();
   e->cfg = c;
@@ -250,7 +273,7 @@ mc_status mc_mmdit_create(const mc_mmdit_config* cfg, mc_mmdit** out) {
   e->txt0 = hy ? e->Li : 0;
   e->out_feat = hy ? c.out_channels * 4 : c.out_channels;
   const size_t d = e->d;
-  const bool flux = !hy;
+  const bool flux = c.family == MC_FAMILY_FLUX;
   auto cleanup = [&](mc_status st) { mc_mmdit_destroy(e); return st; };
 #define TRY_C(expr) do { mc_status _s = (expr); if (_s != MC_OK) return cleanup(_s); } while (0)
 #undef ALLOC
@@ -260,10 +283,17 @@ mc_status mc_mmdit_create(const mc_mmdit_config* cfg, mc_mmdit** out) {
   ALLOC(e->w_in, d * e->Kp); ALLOC(e->b_in, d);
   if (hipMemset(e->w_in, 0, d * e->Kp * 2) != hipSuccess) return cleanup(fail(MC_EHIP, "hipMemset failed"));
   ALLOC(e->w_ctx, d * c.txt_dim); ALLOC(e->b_ctx, d);
-  add_slot(e, flux ? "x_embedder.weight" : "img_in.proj.weight", e->w_in, MC_BF16, d * e->Kin);
-  add_slot(e, flux ? "x_embedder.bias" : "img_in.proj.bias", e->b_in, MC_F32, d);
-  linear_slot(e, flux ? "context_embedder" : "txt_in.input_embedder", e->w_ctx, e->b_ctx, d, c.txt_dim);
-  if (flux) {
+  // Qwen-Image slots: diffusers models/transformers/transformer_qwenimage.py (QwenImageTransformer2DModel: img_in,
+  // txt_norm, txt_in, time_text_embed.timestep_embedder, transformer_blocks.{i}.{img_mod.1, txt_mod.1, attn.*,
+  // img_mlp.net.{0.proj,2}, txt_mlp.net.{0.proj,2}}, norm_out.linear, proj_out)
+  add_slot(e, flux ? "x_embedder.weight" : qw ? "img_in.weight" : "img_in.proj.weight", e->w_in, MC_BF16, d * e->Kin);
+  add_slot(e, flux ? "x_embedder.bias" : qw ? "img_in.bias" : "img_in.proj.bias", e->b_in, MC_F32, d);
+  linear_slot(e, flux ? "context_embedder" : qw ? "txt_in" : "txt_in.input_embedder", e->w_ctx, e->b_ctx, d, c.txt_dim);
+  if (qw) {
+    ALLOC(e->w_txt_norm, c.txt_dim);
+    add_slot(e, "txt_norm.weight", e->w_txt_norm, MC_F32, c.txt_dim);
+    TRY_C(alloc_mlp2(e, e->time_mlp, 256, "time_text_embed.timestep_embedder.linear_1", "time_text_embed.timestep_embedder.linear_2"));
+  } else if (flux) {
     TRY_C(alloc_mlp2(e, e->time_mlp, 256, "time_text_embed.timestep_embedder.linear_1", "time_text_embed.timestep_embedder.linear_2"));
     TRY_C(alloc_mlp2(e, e->guid_mlp, 256, "time_text_embed.guidance_embedder.linear_1", "time_text_embed.guidance_embedder.linear_2"));
     TRY_C(alloc_mlp2(e, e->vec_mlp, c.vec_dim, "time_text_embed.text_embedder.linear_1", "time_text_embed.text_embedder.linear_2"));
@@ -299,10 +329,11 @@ mc_status mc_mmdit_create(const mc_mmdit_config* cfg, mc_mmdit** out) {
     Stream &a = e->dimg[i], &t = e->dtxt[i];
     TRY_C(alloc_stream(e, a));
     TRY_C(alloc_stream(e, t));
-    const std::string p = (flux ? "transformer_blocks." : "double_blocks.") + std::to_string(i) + ".";
-    if (flux) {
-      linear_slot(e, p + "norm1.linear", e->w_mod, e->b_mod, 6 * d, d, e->mod_double(i, 0));
-      linear_slot(e, p + "norm1_context.linear", e->w_mod, e->b_mod, 6 * d, d, e->mod_double(i, 1));
+    const std::string p = (hy ? "double_blocks." : "transformer_blocks.") + std::to_string(i) + ".";
+    if (!hy) {
+      // modulation chunk order shift, scale, gate (attention), shift, scale, gate (MLP) in both families
+      linear_slot(e, p + (qw ? "img_mod.1" : "norm1.linear"), e->w_mod, e->b_mod, 6 * d, d, e->mod_double(i, 0));
+      linear_slot(e, p + (qw ? "txt_mod.1" : "norm1_context.linear"), e->w_mod, e->b_mod, 6 * d, d, e->mod_double(i, 1));
       const char* qkv_i[3] = {"attn.to_q", "attn.to_k", "attn.to_v"};
       const char* qkv_t[3] = {"attn.add_q_proj", "attn.add_k_proj", "attn.add_v_proj"};
       for (int j = 0; j < 3; ++j) {
@@ -314,10 +345,11 @@ mc_status mc_mmdit_create(const mc_mmdit_config* cfg, mc_mmdit** out) {
       add_slot(e, p + "attn.norm_added_k.weight", t.kn, MC_F32, 128);
       linear_slot(e, p + "attn.to_out.0", a.wo, a.bo, d, d);
       linear_slot(e, p + "attn.to_add_out", t.wo, t.bo, d, d);
-      linear_slot(e, p + "ff.net.0.proj", a.w1, a.b1, 4 * d, d);
-      linear_slot(e, p + "ff.net.2", a.w2, a.b2, d, 4 * d);
-      linear_slot(e, p + "ff_context.net.0.proj", t.w1, t.b1, 4 * d, d);
-      linear_slot(e, p + "ff_context.net.2", t.w2, t.b2, d, 4 * d);
+      const std::string ffi = qw ? "img_mlp" : "ff", fft = qw ? "txt_mlp" : "ff_context";
+      linear_slot(e, p + ffi + ".net.0.proj", a.w1, a.b1, 4 * d, d);
+      linear_slot(e, p + ffi + ".net.2", a.w2, a.b2, d, 4 * d);
+      linear_slot(e, p + fft + ".net.0.proj", t.w1, t.b1, 4 * d, d);
+      linear_slot(e, p + fft + ".net.2", t.w2, t.b2, d, 4 * d);
     } else {
       const char* nm[2] = {"img", "txt"};
       Stream* st[2] = {&a, &t};
@@ -355,10 +387,11 @@ mc_status mc_mmdit_create(const mc_mmdit_config* cfg, mc_mmdit** out) {
     }
   }
   // ---- final layer
-  linear_slot(e, flux ? "norm_out.linear" : "final_layer.adaLN_modulation.1", e->w_mod, e->b_mod, 2 * d, d, e->mod_final());
+  // (Qwen-Image's head is FLUX's: AdaLayerNormContinuous, chunk order scale, shift)
+  linear_slot(e, !hy ? "norm_out.linear" : "final_layer.adaLN_modulation.1", e->w_mod, e->b_mod, 2 * d, d, e->mod_final());
   ALLOC(e->w_head, (size_t)e->out_feat * d); ALLOC(e->b_head, e->out_feat);
-  add_slot(e, flux ? "proj_out.weight" : "final_layer.linear.weight", e->w_head, MC_F32, (size_t)e->out_feat * d);
-  add_slot(e, flux ? "proj_out.bias" : "final_layer.linear.bias", e->b_head, MC_F32, e->out_feat);
+  add_slot(e, !hy ? "proj_out.weight" : "final_layer.linear.weight", e->w_head, MC_F32, (size_t)e->out_feat * d);
+  add_slot(e, !hy ? "proj_out.bias" : "final_layer.linear.bias", e->b_head, MC_F32, e->out_feat);
   if (hy) {  // upstream token vector is (c, pt, ph, pw) channel-major; launch_unpatchify wants (ph, pw, c)
     e->slots["final_layer.linear.weight"].perm_c = c.out_channels;
     e->slots["final_layer.linear.bias"].perm_c = c.out_channels;
@@ -382,6 +415,8 @@ mc_status mc_mmdit_create(const mc_mmdit_config* cfg, mc_mmdit** out) {
   if (e->P > 1) {
     add_buf(e, cur, "kv_gather", (size_t)e->P * e->Lrp * 2 * d * 2);   // image K|V of every rank
     add_buf(e, cur, "attn_lse", (size_t)e->H * Sp * 4);
+  } else if (qw) {
+    add_buf(e, cur, "attn_lse", (size_t)e->H * Sp * 4);                // image keys, then the valid text keys merged
   }
   add_buf(e, cur, "am", Sp * 5 * d * 2);               // also the fp32 [img, d] head operand after the last block
   add_buf(e, cur, "tokens", align_up(Li, 256) * e->Kp * 2);
@@ -392,6 +427,10 @@ mc_status mc_mmdit_create(const mc_mmdit_config* cfg, mc_mmdit** out) {
   add_buf(e, cur, "head_tokens", Li * 64 * 4);
   add_buf(e, cur, "residual0", Sp * d * 4);
   if (c.calibration) add_buf(e, cur, "residual1", Sp * d * 4);
+  if (qw) {   // the uncond branch's slots (Qwen-Image only: the other families are guidance distilled, one branch)
+    add_buf(e, cur, c.calibration ? "residual2" : "residual1", Sp * d * 4);
+    if (c.calibration) add_buf(e, cur, "residual3", Sp * d * 4);
+  }
   {
     // split-K scratch (gemm_bf16_v2): the largest any GEMM of a block wants, one buffer per stream that may run GEMMs
     size_t need_all = 0, need_txt = 0;
@@ -445,7 +484,7 @@ mc_status mc_mmdit_set_workspace(mc_mmdit* e, void* ws_dev, size_t bytes) {
   if (bytes < e->ws_need) return fail(MC_EINVAL, "workspace too small: %zu < %zu", bytes, e->ws_need);
   if (((uintptr_t)ws_dev) & 255) return fail(MC_EINVAL, "workspace must be 256-byte aligned");
   e->ws = (char*)ws_dev;
-  e->have_res = e->have_stats = e->pads_clean = false;
+  e->have_res[0] = e->have_res[1] = e->have_stats = e->pads_clean = false;
   HIP_TRY(hipMemset(e->buf<double>("calib_partial") + 2048 * 4, 0, 16));   // arrival ticket of calib_stats_kernel
   return MC_OK;
 }
@@ -453,8 +492,13 @@ mc_status mc_mmdit_set_workspace(mc_mmdit* e, void* ws_dev, size_t bytes) {
 mc_status mc_mmdit_buffer_info(const mc_mmdit* e, const char* name, size_t* offset, size_t* bytes) {
   if (!e || !name) return fail(MC_EINVAL, "null argument");
   std::string n(name);
-  const bool res = (n == "residual");      // the image rows of the slot that holds the cache
-  if (res) n = e->res_cur ? "residual1" : "residual0";
+  // "residual": the image rows of the slot that holds the cache of the last forward's branch; "residual_b<k>": branch k's
+  const bool res = (n == "residual" || n == "residual_b0" || n == "residual_b1");
+  if (res) {
+    const int b = n == "residual" ? e->branch : n[10] - '0';
+    if (b == 1 && e->cfg.family != MC_FAMILY_QWEN) return fail(MC_EINVAL, "unknown buffer '%s'", name);
+    n = "residual" + std::to_string(e->res_index(b, e->res_cur[b]));
+  }
   auto it = e->bufs.find(n);
   if (it == e->bufs.end()) return fail(MC_EINVAL, "unknown buffer '%s'", name);
   if (offset) *offset = it->second.off + (res ? (size_t)e->img0 * e->d * 4 : 0);
@@ -538,7 +582,7 @@ mc_status mc_mmdit_set_rope(mc_mmdit* e, const float* cos_dev, const float* sin_
 
 mc_status mc_mmdit_state_reset(mc_mmdit* e) {
   if (!e) return fail(MC_EINVAL, "null engine");
-  e->have_res = e->have_stats = false;
+  e->have_res[0] = e->have_res[1] = e->have_stats = false;
   return MC_OK;
 }
 
@@ -573,6 +617,34 @@ mc_status joint_attention(const mc_mmdit* e, int q_rows_pad, int n_valid, hipStr
   a.Lq_pad = q_rows_pad; a.n_heads = e->H; a.scale = 1.0f / std::sqrt(128.0f);
   a.shard_rows = q_rows_pad; a.shard_valid = n_valid; a.n_shards = 1;
   HIP_TRY(mc::launch_attention(a, s));
+  return MC_OK;
+}
+
+// Qwen-Image with a prompt shorter than txt_len: the queries of every row over the image keys (log-sum-exp kept), then
+// over the txt_valid text keys merged with it -- the padded text rows [txt_valid, txt_len) are never keys.  (At
+// txt_valid == txt_len the engine takes joint_attention over all S keys, as for FLUX.)
+mc_status qwen_attention(const mc_mmdit* e, hipStream_t s) {
+  const int d = e->d;
+  bf16_t* qkv = e->buf<bf16_t>("qkv");
+  mc::AttnParams a;
+  memset(&a, 0, sizeof(a));
+  a.Q = qkv; a.ldq = 3 * d;
+  a.O = e->buf<bf16_t>("am"); a.ldo = 5 * d;
+  a.Lq_pad = e->Sp; a.n_heads = e->H; a.scale = 1.0f / std::sqrt(128.0f);
+  a.n_shards = 1;
+  float* lse = e->buf<float>("attn_lse");
+  mc::AttnParams im = a;   // image keys: rows [img0, img0 + Li); the padding up to 64 rows is the zeroed tail of qkv
+  im.K = qkv + (size_t)e->img0 * 3 * d + d; im.ldk = 3 * d;
+  im.V = qkv + (size_t)e->img0 * 3 * d + 2 * d; im.ldv = 3 * d;
+  im.shard_rows = (int)align_up(e->Li, 64); im.shard_valid = e->Li;
+  im.lse_out = lse;
+  HIP_TRY(mc::launch_attention(im, s));
+  mc::AttnParams tx = a;   // the valid text keys; rows [txt_valid, align64(Lt)) are read (finite: padded text / image rows)
+  tx.K = qkv + (size_t)e->txt0 * 3 * d + d; tx.ldk = 3 * d;
+  tx.V = qkv + (size_t)e->txt0 * 3 * d + 2 * d; tx.ldv = 3 * d;
+  tx.shard_rows = (int)align_up(e->Lt, 64); tx.shard_valid = e->txt_valid;
+  tx.lse_in = lse;
+  HIP_TRY(mc::launch_attention(tx, s));
   return MC_OK;
 }
 
@@ -781,25 +853,34 @@ mc_status run_two(mc_mmdit* e, hipStream_t s, int mode, FI&& img_part, FT&& txt_
 // -> end (final layer).  mc_mmdit_forward runs them back to back on one GPU.
 extern "C" {
 
-mc_status mc_mmdit_begin(mc_mmdit* e, const float* img_dev, double timestep, double guidance, const float* txt_dev,
-                         int txt_valid, const float* vec_dev, mc_mode mode, mc_stream stream_) {
+}  // extern "C"
+
+namespace {
+
+mc_status begin_impl(mc_mmdit* e, const float* img_dev, double timestep, double guidance, const float* txt_dev,
+                     int txt_valid, const float* vec_dev, mc_mode mode, int branch, mc_stream stream_) {
   hipStream_t s = (hipStream_t)stream_;
   if (!e) return fail(MC_EINVAL, "null engine");
   if (!e->ws) return fail(MC_ESTATE, "workspace not set (mc_mmdit_set_workspace)");
   for (auto& kv : e->slots)
     if (!kv.second.loaded) return fail(MC_ESTATE, "weight '%s' was never set", kv.first.c_str());
-  if (!img_dev || !txt_dev || !vec_dev) return fail(MC_EINVAL, "null input");
   const mc_mmdit_config& c = e->cfg;
   const bool hy = c.family == MC_FAMILY_HUNYUAN;
-  if (hy && (txt_valid <= 0 || txt_valid > e->Lt)) return fail(MC_EINVAL, "txt_valid %d out of (0, %d]", txt_valid, e->Lt);
-  if (mode == MC_MODE_SKIP && !e->have_res)
+  const bool qw = c.family == MC_FAMILY_QWEN;
+  if (!img_dev || !txt_dev || (!vec_dev && !qw)) return fail(MC_EINVAL, "null input");
+  if ((hy || qw) && (txt_valid <= 0 || txt_valid > e->Lt))
+    return fail(MC_EINVAL, "txt_valid %d out of (0, %d]", txt_valid, e->Lt);
+  if (branch < 0 || branch > (qw ? 1 : 0))
+    return fail(MC_EINVAL, "CFG branch %d: this family has %s", branch, qw ? "branches 0 and 1" : "branch 0 only");
+  if (mode == MC_MODE_SKIP && !e->have_res[branch])
     return fail(MC_ESTATE, "skip requested but the residual cache is empty");
   if (mode == MC_MODE_CALIB && !c.calibration) return fail(MC_ESTATE, "engine was created without calibration");
   if (mode == MC_MODE_CALIB && e->P > 1) return fail(MC_ESTATE, "calibration runs on one GPU in this engine");
   e->mode = mode;
-  e->txt_valid = hy ? txt_valid : e->Lt;
+  e->branch = branch;
+  e->txt_valid = (hy || qw) ? txt_valid : e->Lt;
   e->begun = true;
-  e->dst = (mode == MC_MODE_CALIB && e->have_res) ? 1 - e->res_cur : e->res_cur;
+  e->dst = (mode == MC_MODE_CALIB && e->have_res[branch]) ? 1 - e->res_cur[branch] : e->res_cur[branch];
   const int d = e->d, Li = e->Li, Lt = e->Lt, S = e->S, Sp = e->Sp;
   float* x = e->buf<float>("x");
   bf16_t* x0 = e->buf<bf16_t>("x0") + (size_t)e->img0 * d;   // image rows of the joint-indexed copy
@@ -815,11 +896,14 @@ mc_status mc_mmdit_begin(mc_mmdit* e, const float* img_dev, double timestep, dou
     e->pads_clean = true;
   }
   // ---- conditioning vector: time + guidance + pooled text   (flux :303-313, hunyuan :53-67)
+  // (Qwen-Image, QwenTimestepProjEmbeddings: the timestep MLP alone, no guidance and no pooled text)
   HIP_TRY(mc::launch_sinusoid(nullptr, timestep, 256, sin_t, s));
-  HIP_TRY(mc::launch_sinusoid(nullptr, guidance, 256, sin_g, s));
   MC_TRY(run_mlp2(e, e->time_mlp, sin_t, hid, vec, 0, s));
-  MC_TRY(run_mlp2(e, e->guid_mlp, sin_g, hid, vec, 1, s));
-  MC_TRY(run_mlp2(e, e->vec_mlp, vec_dev, hid, vec, 1, s));
+  if (!qw) {
+    HIP_TRY(mc::launch_sinusoid(nullptr, guidance, 256, sin_g, s));
+    MC_TRY(run_mlp2(e, e->guid_mlp, sin_g, hid, vec, 1, s));
+    MC_TRY(run_mlp2(e, e->vec_mlp, vec_dev, hid, vec, 1, s));
+  }
   // modulation of every block = Linear(silu(vec)); a skipped step needs the final layer's only
   if (mode == MC_MODE_SKIP) {
     const size_t r0 = e->mod_final();
@@ -843,14 +927,30 @@ mc_status mc_mmdit_begin(mc_mmdit* e, const float* img_dev, double timestep, dou
   }
   if (mode != MC_MODE_SKIP) {
     // ---- text embedding -> text rows of x   (flux :314; hunyuan :72-78 incl. the token refiner); replicated per rank
+    // Qwen-Image (upstream forward, run on every call as the reference does :186-188): txt_norm = weighted RMSNorm
+    // (eps 1e-6) of the txt_valid rows to bf16, the padded rows zero -- and zero after txt_in (m_valid)
     bf16_t* tin = e->buf<bf16_t>("txt_in");
-    HIP_TRY(mc::launch_cast_pad_bf16(txt_dev, c.txt_dim, Lt, Lt, c.txt_dim, tin, c.txt_dim, s));
+    if (qw) {
+      HIP_TRY(mc::launch_rmsnorm_rows_bf16(txt_dev, c.txt_dim, e->w_txt_norm, 1e-6f, tin, c.txt_dim, txt_valid, Lt, c.txt_dim, s));
+    } else {
+      HIP_TRY(mc::launch_cast_pad_bf16(txt_dev, c.txt_dim, Lt, Lt, c.txt_dim, tin, c.txt_dim, s));
+    }
     mc::GemmParams p = gp(tin, c.txt_dim, e->w_ctx, c.txt_dim, e->b_ctx, Lt, d, c.txt_dim);
-    p.X = x + (size_t)e->txt0 * d; p.ldx = d; p.X0out = e->buf<bf16_t>("txt_e"); p.ldx0out = d; p.m_valid = Lt;
+    p.X = x + (size_t)e->txt0 * d; p.ldx = d; p.X0out = e->buf<bf16_t>("txt_e"); p.ldx0out = d;
+    p.m_valid = qw ? txt_valid : Lt;
     HIP_TRY(gemm(e, p, mc::EPI_EMBED, s));
     if (hy) MC_TRY(run_refiner(e, txt_dev, txt_valid, vecs, s));
   }
   return MC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+mc_status mc_mmdit_begin(mc_mmdit* e, const float* img_dev, double timestep, double guidance, const float* txt_dev,
+                         int txt_valid, const float* vec_dev, mc_mode mode, mc_stream stream) {
+  return begin_impl(e, img_dev, timestep, guidance, txt_dev, txt_valid, vec_dev, mode, 0, stream);
 }
 
 // block index: 0 .. n_double-1 double-stream blocks, then the single-stream blocks
@@ -958,7 +1058,9 @@ mc_status mc_mmdit_block_post(mc_mmdit* e, int blk, mc_stream stream_) {
   const float* emod = e->buf<float>("emod");
   bf16_t* qkv = e->buf<bf16_t>("qkv");
   // ---- joint attention of the local queries over [all image tokens ; valid text tokens]
-  if (e->P == 1) {
+  if (e->P == 1 && c.family == MC_FAMILY_QWEN && e->txt_valid < Lt) {
+    MC_TRY(qwen_attention(e, s));
+  } else if (e->P == 1) {
     const bool hy = c.family == MC_FAMILY_HUNYUAN;
     MC_TRY(joint_attention(e, Sp, hy ? Li + e->txt_valid : S, s));
   } else {
@@ -992,13 +1094,13 @@ mc_status mc_mmdit_block_post(mc_mmdit* e, int blk, mc_stream stream_) {
   }
   const bool last = (blk == nb - 1);
   if (blk < c.n_double && double_block_merged(e)) {
-    MC_TRY(double_post_merged(e, blk, emod, s, last ? e->residual_joint(e->dst) : nullptr));
+    MC_TRY(double_post_merged(e, blk, emod, s, last ? e->residual_joint(e->dst, e->branch) : nullptr));
   } else if (blk < c.n_double) {
     MC_TRY(run_two(
         e, s, g_mmdit_two_streams > 2 ? 0 : g_mmdit_two_streams,
         [&](hipStream_t q) {
           return stream_post_attn(e, e->dimg[blk], emod + e->mod_double(blk, 0), e->img0, Li, q,
-                                  last ? e->residual_joint(e->dst) : nullptr);
+                                  last ? e->residual_joint(e->dst, e->branch) : nullptr);
         },
         [&](hipStream_t q) { return stream_post_attn(e, e->dtxt[blk], emod + e->mod_double(blk, 1), e->txt0, Lt, q); }));
   } else {
@@ -1015,14 +1117,15 @@ mc_status mc_mmdit_block_post(mc_mmdit* e, int blk, mc_stream stream_) {
     }
   }
   if (last) {
-    if (e->mode == MC_MODE_CALIB && e->have_res) {
-      HIP_TRY(mc::launch_calib_stats(e->residual(e->dst), d, e->residual(e->res_cur), d, Li, d,
+    const int b = e->branch;   // calibration compares with the previous residual of the SAME branch
+    if (e->mode == MC_MODE_CALIB && e->have_res[b]) {
+      HIP_TRY(mc::launch_calib_stats(e->residual(e->dst, b), d, e->residual(e->res_cur[b], b), d, Li, d,
                                      e->buf<double>("calib_partial"), 2048, e->buf<double>("calib_sums"),
                                      e->buf<float>("calib_stats"), s));
       e->have_stats = true;
     }
-    e->res_cur = e->dst;
-    e->have_res = true;
+    e->res_cur[b] = e->dst;
+    e->have_res[b] = true;
   }
   return MC_OK;
 }
@@ -1045,7 +1148,8 @@ mc_status mc_mmdit_end(mc_mmdit* e, float* out_dev, mc_stream stream_) {
   bf16_t* x0 = e->buf<bf16_t>("x0") + (size_t)e->img0 * d;
   if (e->mode == MC_MODE_SKIP) {
     // hidden_states = ori + cur_residual (flux :348, hunyuan :102) folded into the LayerNorm load
-    HIP_TRY(mc::launch_ln_modulate(e->residual(e->res_cur), d, x0, d, scale, shift, 0, 1e-6f, nullptr, 0, hn, d, Li, d, s));
+    HIP_TRY(mc::launch_ln_modulate(e->residual(e->res_cur[e->branch], e->branch), d, x0, d, scale, shift, 0, 1e-6f, nullptr,
+                                   0, hn, d, Li, d, s));
   } else {
     HIP_TRY(mc::launch_ln_modulate(e->buf<float>("x") + (size_t)e->img0 * d, d, nullptr, 0, scale, shift, 0, 1e-6f,
                                    nullptr, 0, hn, d, Li, d, s));
@@ -1074,10 +1178,16 @@ mc_status mc_mmdit_unpatchify(mc_mmdit* e, const float* tokens_dev, float* out_d
 
 mc_status mc_mmdit_forward(mc_mmdit* e, const float* img_dev, double timestep, double guidance, const float* txt_dev,
                            int txt_valid, const float* vec_dev, mc_mode mode, float* out_dev, mc_stream stream) {
+  return mc_mmdit_forward2(e, img_dev, timestep, guidance, txt_dev, txt_valid, vec_dev, mode, 0, out_dev, stream);
+}
+
+mc_status mc_mmdit_forward2(mc_mmdit* e, const float* img_dev, double timestep, double guidance, const float* txt_dev,
+                            int txt_valid, const float* vec_dev, mc_mode mode, int branch, float* out_dev,
+                            mc_stream stream) {
   if (!e) return fail(MC_EINVAL, "null engine");
   if (e->P != 1) return fail(MC_ESTATE, "mc_mmdit_forward is single-GPU; drive a sharded engine through the phase calls");
   if (!out_dev) return fail(MC_EINVAL, "null output");
-  MC_TRY(mc_mmdit_begin(e, img_dev, timestep, guidance, txt_dev, txt_valid, vec_dev, mode, stream));
+  MC_TRY(begin_impl(e, img_dev, timestep, guidance, txt_dev, txt_valid, vec_dev, mode, branch, stream));
   if (mode != MC_MODE_SKIP) {
     for (int b = 0; b < e->cfg.n_double + e->cfg.n_single; ++b) {
       MC_TRY(mc_mmdit_block_pre(e, b, stream));

@@ -203,6 +203,15 @@ hipError_t launch_head_linear(const float* xn, long ldx, const float* W, const f
 hipError_t launch_cfg_euler(const float* cond, const float* uncond, float g, float dt, float* x, float* eps_out,
                             size_t n, hipStream_t stream);
 
+// Qwen-Image true-CFG + flow-Euler step on token rows (fp32, in place on x): comb = u + g (c - u), v = comb * |c| / |comb|
+// (row norms over the C <= 256 channels; v = 0 where |comb| == 0), x += dt * v, rows [0, n_rows) only
+hipError_t launch_cfg_norm_euler(const float* cond, const float* uncond, long ldp, float g, float dt, float* x, long ldx,
+                                 int n_rows, int C, hipStream_t stream);
+// weighted row RMSNorm fp32 -> bf16: out[m] = bf16(x[m] * rsqrt(mean(x[m]^2) + eps) * w) for m < rows_valid, zero rows
+// [rows_valid, rows)  (Qwen-Image txt_norm)
+hipError_t launch_rmsnorm_rows_bf16(const float* x, long ldx, const float* w, float eps, bf16_t* out, long ldo,
+                                    int rows_valid, int rows, int D, hipStream_t stream);
+
 // out[i] = sum_j coef[j] * xs[j][i], 1 <= k <= 6 fp32 operands (host arrays of k pointers / coefficients);
 // out may alias an operand.  The multistep flow solvers (sampler.py) are built from this.
 hipError_t launch_lincomb(const float* const* xs, const float* coef, int k, float* out, size_t n, hipStream_t stream);

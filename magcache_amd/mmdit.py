@@ -6,6 +6,9 @@ surfaces:
         accumulated_err, accumulated_steps, previous_residual     (:452-470)
     HYVideoDiffusionTransformer.forward = magcache_forward        MagCache4HunyuanVideo/magcache_sample_video.py:325
       + cnt, num_steps, magcache_thresh, K, retention_ratio, mag_ratios, accumulated_*, residual_cache  (:305-328)
+    QwenImageTransformer2DModel.forward = magcache_forward        MagCache4QwenImage/magcache_generate.py:64
+      + cnt, num_steps, magcache_thresh, K, retention_ratio, accumulated_{err,steps,ratio}[2], residual_cache[2],
+        mag_ratios                                                (:63-83; MagCache4QwenImageEdit: the same functions)
 
 `FluxTransformer2DModelHIP` / `HYVideoDiffusionTransformerHIP` stand where the upstream model objects stand (same
 forward signatures and return types), `flux_magcache_forward` / `hunyuan_magcache_forward` and the two
@@ -21,8 +24,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (MC_F32, MC_BF16, MC_FAMILY_FLUX, MC_FAMILY_HUNYUAN, MC_MODE_CALIB, MC_MODE_FULL, MC_MODE_SKIP,
-                   McMmditConfig, check)
+from ._lib import (MC_F32, MC_BF16, MC_FAMILY_FLUX, MC_FAMILY_HUNYUAN, MC_FAMILY_QWEN, MC_MODE_CALIB, MC_MODE_FULL,
+                   MC_MODE_SKIP, McMmditConfig, check)
 from .mag_ratios import TABLES
 from .model import nearest_interp
 from .parallel import SP_OVERLAP
@@ -116,9 +119,11 @@ class MMDiTEngine:
         check(self.lib.mc_mmdit_buffer_info(self.h, name.encode(), C.byref(off), C.byref(nb)))
         return self.ws[off.value:off.value + nb.value].view(dtype)
 
-    def residual(self):
-        """fp32 [img_tokens / sp_size, dim] view of the cached residual (reference previous_residual / residual_cache)."""
-        return self.buffer("residual", torch.float32).view(-1, self.dim)[:self.tokens_per_rank]
+    def residual(self, branch=None):
+        """fp32 [img_tokens / sp_size, dim] view of the cached residual (reference previous_residual / residual_cache);
+        `branch` 0 / 1: that CFG branch's cache (Qwen-Image), None: the branch of the last forward."""
+        name = "residual" if branch is None else f"residual_b{int(branch)}"
+        return self.buffer(name, torch.float32).view(-1, self.dim)[:self.tokens_per_rank]
 
     def set_rope(self, cos, sin):
         """upstream use_real tables [n, 128]; uploaded only when the tensors change (constant over a sample).  The
@@ -134,13 +139,21 @@ class MMDiTEngine:
         torch.cuda.current_stream().synchronize()
         self._rope_key = key
 
-    def forward(self, img, timestep, guidance, txt, txt_valid, vec, mode=MC_MODE_FULL, out=None):
-        img, txt, vec = _f32(img, self.device), _f32(txt, self.device), _f32(vec, self.device)
+    def forward(self, img, timestep, guidance, txt, txt_valid, vec, mode=MC_MODE_FULL, out=None, branch=None):
+        """`branch` (None = the one-slot mc_mmdit_forward): the CFG branch of mc_mmdit_forward2 (Qwen-Image 0 / 1).
+        `vec` None: no pooled vector (Qwen-Image)."""
+        img, txt = _f32(img, self.device), _f32(txt, self.device)
+        vec = _f32(vec, self.device) if vec is not None else None
         if out is None:
             shape = (self.out_channels,) + self.latent_grid if self.family == MC_FAMILY_HUNYUAN else (self.img_tokens, self.out_channels)
             out = torch.empty(shape, dtype=torch.float32, device=self.device)
-        check(self.lib.mc_mmdit_forward(self.h, _ptr(img), float(timestep), float(guidance), _ptr(txt), int(txt_valid),
-                                        _ptr(vec), mode, _ptr(out), _stream()))
+        vp = _ptr(vec) if vec is not None else C.c_void_p(0)
+        if branch is None:
+            check(self.lib.mc_mmdit_forward(self.h, _ptr(img), float(timestep), float(guidance), _ptr(txt), int(txt_valid),
+                                            vp, mode, _ptr(out), _stream()))
+        else:
+            check(self.lib.mc_mmdit_forward2(self.h, _ptr(img), float(timestep), float(guidance), _ptr(txt), int(txt_valid),
+                                             vp, mode, int(branch), _ptr(out), _stream()))
         return out
 
     # ---- the same forward in phases (sequence parallel; see MMDiTSequenceParallel)
@@ -539,5 +552,187 @@ def init_hunyuan_magcache(model, infer_steps=50, magcache_thresh=0.24, K=6, rete
     cls.accumulated_ratio = 1
     cls.accumulated_err = 0
     cls.accumulated_steps = 0
+    model.engine.reset()
+    return model
+
+
+# ============================================================================================== Qwen-Image (-Edit)
+QWEN_IMAGE = dict(patch_size=2, in_channels=64, out_channels=16, num_layers=60, attention_head_dim=128,
+                  num_attention_heads=24, joint_attention_dim=3584, guidance_embeds=False, axes_dims_rope=(16, 56, 56))
+
+
+def qwen_nearest_interp(original, target_length):
+    """MagCache4QwenImage/magcache_generate.py nearest_interp (:14-21): the np.linspace form, per CFG branch."""
+    original = np.asarray(original)
+    if len(original) == target_length:
+        return original.copy()
+    return original[np.round(np.linspace(0, len(original) - 1, target_length)).astype(int)]
+
+
+def qwen_rope(img_shapes, max_txt_len, axes_dim=(16, 56, 56), theta=10000.0):
+    """[UPSTREAM] diffusers QwenEmbedRope(theta=10000, axes_dim=(16, 56, 56), scale_rope=True) as fp32 use_real tables
+    (cos, sin) [max_txt_len + sum(f*h*w), 128], rows [text ; image 0 ; image 1 ...], every frequency twice.
+    Image `idx` (0 = the noisy latent, 1 = Qwen-Image-Edit's reference image) has frame positions idx + f and centred
+    row / column positions y - (h - h//2), x - (w - w//2); text token j sits at max(h//2, w//2) over the images + j on
+    all three axes.  Angles are fp32 products position * theta^(-2i/dim), as upstream's rope_params computes them."""
+    ids, m = [], 0
+    for idx, (f, h, w) in enumerate(img_shapes):
+        fi, yi, xi = np.meshgrid(np.arange(f) + idx, np.arange(h) - (h - h // 2), np.arange(w) - (w - w // 2), indexing="ij")
+        ids.append(np.stack([fi.ravel(), yi.ravel(), xi.ravel()], 1))
+        m = max(m, h // 2, w // 2)
+    t = np.arange(max_txt_len) + m
+    ids = np.concatenate([np.stack([t, t, t], 1)] + ids, 0)
+    cos, sin = [], []
+    for i, dim in enumerate(axes_dim):
+        freqs = (1.0 / torch.pow(torch.tensor(theta), torch.arange(0, dim, 2, dtype=torch.float32) / dim)).float()
+        ang = torch.outer(torch.from_numpy(ids[:, i]).float(), freqs)
+        cos.append(ang.cos().repeat_interleave(2, dim=1))
+        sin.append(ang.sin().repeat_interleave(2, dim=1))
+    return torch.cat(cos, 1).contiguous(), torch.cat(sin, 1).contiguous()
+
+
+class QwenImageTransformer2DModelHIP:
+    """Stands where diffusers' QwenImageTransformer2DModel stands (Qwen-Image and Qwen-Image-Edit: the same transformer;
+    Edit's image tokens are the noisy latent's followed by the reference image's).  One (image tokens, longest prompt)
+    geometry per instance; every call may carry a shorter prompt (cond vs the " " negative prompt, unpadded).  The two
+    CFG branches keep their own residual cache in the engine (mc_mmdit_forward2)."""
+
+    def __init__(self, cfg, img_tokens, txt_len=1024, device="cuda:0", calibration=True, engine=None, sp_size=1):
+        self.config = SimpleNamespace(**cfg)
+        self.cfg = dict(cfg)
+        dim = cfg["attention_head_dim"] * cfg["num_attention_heads"]
+        assert cfg["attention_head_dim"] == 128 and not cfg.get("guidance_embeds", False)
+        out = cfg["patch_size"] ** 2 * cfg["out_channels"]
+        self.inner_dim, self.img_tokens, self.txt_len, self.out_features = dim, img_tokens, txt_len, out
+        self.engine = engine or MMDiTEngine(MC_FAMILY_QWEN, dim, cfg["num_attention_heads"], cfg["num_layers"], 0,
+                                            cfg["in_channels"], out, cfg["joint_attention_dim"], txt_len, 0, img_tokens,
+                                            calibration=calibration, device=device, sp_size=sp_size)
+        self.device = self.engine.device
+        self._shapes_key = None
+
+    def load_state_dict(self, sd):
+        """diffusers state_dict names (img_in, txt_norm, txt_in, time_text_embed.timestep_embedder, transformer_blocks.{i}.*,
+        norm_out.linear, proj_out); a missing name raises KeyError."""
+        self.engine.load_weights(sd)
+        return self
+
+    @staticmethod
+    def _images(img_shapes):
+        # pipeline form: [[(1, h, w)]] per batch entry (Edit: [[(1, h, w), (1, h_ref, w_ref)]]); a bare [(1, h, w)] too
+        shapes = img_shapes[0] if isinstance(img_shapes[0], list) else img_shapes
+        return [tuple(int(v) for v in s) for s in shapes]
+
+    def _run(self, hidden_states, encoder_hidden_states, timestep, img_shapes, txt_seq_lens, mode, branch):
+        assert hidden_states.dim() == 3 and hidden_states.shape[0] == 1, "one sample per call, as the Qwen-Image pipeline does"
+        assert hidden_states.shape[1] == self.img_tokens, (tuple(hidden_states.shape), self.img_tokens)
+        shapes = self._images(img_shapes)
+        assert sum(f * h * w for f, h, w in shapes) == self.img_tokens, ("img_shapes do not cover the image tokens", shapes)
+        n = int(txt_seq_lens[0]) if txt_seq_lens is not None else int(encoder_hidden_states.shape[1])
+        if not 0 < n <= min(self.txt_len, encoder_hidden_states.shape[1]):
+            raise ValueError(f"text length {n} outside (0, {self.txt_len}]")
+        # timestep.to(hidden_states.dtype) (:184); Timesteps(scale=1000) of the upstream embedding: the sinusoid of t * 1000
+        t = float(timestep.to(hidden_states.dtype).reshape(-1)[0]) * 1000.0
+        key = tuple(shapes)
+        if key != self._shapes_key:
+            self.engine.set_rope(*qwen_rope(shapes, self.txt_len, tuple(self.cfg["axes_dims_rope"])))
+            self._shapes_key = key
+        out = self.engine.forward(hidden_states[0], t, 0.0, encoder_hidden_states[0, :n], n, None, mode, branch=branch)
+        return out.unsqueeze(0).to(hidden_states.dtype)
+
+    __call__ = _dispatch
+
+
+def qwen_plain_forward(self, hidden_states, encoder_hidden_states=None, encoder_hidden_states_mask=None, timestep=None,
+                       img_shapes=None, txt_seq_lens=None, guidance=None, attention_kwargs=None, return_dict=True, **_):
+    out = self._run(hidden_states, encoder_hidden_states, timestep, img_shapes, txt_seq_lens, MC_MODE_FULL, 0)
+    return _flux_output(out, return_dict)
+
+
+QwenImageTransformer2DModelHIP.forward = qwen_plain_forward
+
+
+def qwen_magcache_forward(self, hidden_states, encoder_hidden_states=None, encoder_hidden_states_mask=None, timestep=None,
+                          img_shapes=None, txt_seq_lens=None, guidance=None, attention_kwargs=None, return_dict=True):
+    """Drop-in for MagCache4QwenImage/magcache_generate.py magcache_forward (:173-253): calls alternate cond / uncond
+    (branch cnt % 2), strict `<`, and the accumulators are NOT reset when cnt wraps."""
+    cnt = int(self.cnt)
+    b = cnt % 2
+    skip_forward = False
+    if cnt >= int(self.num_steps * self.retention_ratio):                                    # :205
+        cur_mag_ratio = self.mag_ratios[cnt]
+        self.accumulated_ratio[b] *= cur_mag_ratio
+        self.accumulated_steps[b] += 1
+        self.accumulated_err[b] += np.abs(1 - self.accumulated_ratio[b])
+        if self.accumulated_err[b] < self.magcache_thresh and self.accumulated_steps[b] <= self.K:   # :213
+            skip_forward = True
+        else:
+            self.accumulated_err[b] = 0.0
+            self.accumulated_steps[b] = 0
+            self.accumulated_ratio[b] = 1.0
+    if skip_forward and self.residual_cache[b] is None:
+        raise RuntimeError("MagCache asked to skip before any residual was cached")
+    out = self._run(hidden_states, encoder_hidden_states, timestep, img_shapes, txt_seq_lens,
+                    MC_MODE_SKIP if skip_forward else MC_MODE_FULL, b)
+    self.residual_cache[b] = self.engine.residual(b)                                          # :242
+    self.cnt = cnt + 1
+    if self.cnt >= self.num_steps:
+        self.cnt = 0
+    return _flux_output(out, return_dict)
+
+
+def qwen_magcache_calibration(self, hidden_states, encoder_hidden_states=None, encoder_hidden_states_mask=None,
+                              timestep=None, img_shapes=None, txt_seq_lens=None, guidance=None, attention_kwargs=None,
+                              return_dict=True):
+    """Drop-in for magcache_generate.py magcache_calibration (:94-171): statistics against the same branch's previous
+    residual from the third call on."""
+    cnt = int(self.cnt)
+    b = cnt % 2
+    out = self._run(hidden_states, encoder_hidden_states, timestep, img_shapes, txt_seq_lens, MC_MODE_CALIB, b)
+    if cnt >= 2:                                                                              # :140
+        norm_ratio, norm_std, cos_dis = self.engine.calib_stats()
+        self.norm_ratio.append(round(norm_ratio, 5))
+        self.norm_std.append(round(norm_std, 5))
+        self.cos_dis.append(round(cos_dis, 5))
+        print(f"Step {cnt}: norm_ratio={norm_ratio:.5f}, norm_std={norm_std:.5f}, cos_dis={cos_dis:.5f}")
+    self.residual_cache[b] = self.engine.residual(b)
+    self.cnt = cnt + 1
+    if self.cnt >= self.num_steps:                                                            # :156-161
+        self.cnt = 0
+        print("\nCalibration Results:")
+        print("norm_ratio:", self.norm_ratio)
+        print("norm_std:", self.norm_std)
+        print("cos_dis:", self.cos_dis)
+    return _flux_output(out, return_dict)
+
+
+def init_qwen_magcache(model, sample_steps=50, magcache_thresh=0.06, K=2, retention_ratio=0.2, mag_ratios=None,
+                       calibration=False, edit=False):
+    """The reference's patch site on the model's CLASS: init_magcache (:63-83) / init_magcache_calibration (:85-92).
+    `mag_ratios` is the reference's list WITHOUT the two leading 1.0 pads (default: the Qwen-Image or -Edit table)."""
+    cls = model.__class__
+    cls.cnt = 0
+    cls.num_steps = sample_steps * 2
+    cls.residual_cache = [None, None]
+    if calibration:
+        cls.forward = qwen_magcache_calibration
+        cls.norm_ratio, cls.norm_std, cls.cos_dis = [], [], []
+    else:
+        cls.forward = qwen_magcache_forward
+        cls.split_step = None
+        cls.mode = "t2v"
+        cls.magcache_thresh = magcache_thresh
+        cls.K = K
+        cls.accumulated_err = [0.0, 0.0]
+        cls.accumulated_steps = [0, 0]
+        cls.accumulated_ratio = [1.0, 1.0]
+        cls.retention_ratio = retention_ratio
+        if mag_ratios is None:
+            mag_ratios = list(TABLES["qwen_image_edit" if edit else "qwen_image"][2:])
+        table = np.array([1.0] * 2 + list(mag_ratios))
+        if len(table) != sample_steps * 2:                                                  # :77-83
+            con = qwen_nearest_interp(table[0::2], sample_steps)
+            ucon = qwen_nearest_interp(table[1::2], sample_steps)
+            table = np.concatenate([con.reshape(-1, 1), ucon.reshape(-1, 1)], axis=1).flatten()
+        cls.mag_ratios = table
     model.engine.reset()
     return model

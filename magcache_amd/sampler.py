@@ -195,3 +195,71 @@ def sample(model, noise, context, context_null, sampling_steps=50, shift=5.0, gu
         if callback is not None:
             callback(i, latent)
     return latent
+
+
+# ============================================================================================== Qwen-Image (-Edit)
+def qwen_image_sigmas(num_inference_steps, image_seq_len, base_image_seq_len=256, max_image_seq_len=8192, base_shift=0.5,
+                      max_shift=0.9, shift_terminal=0.02, num_train_timesteps=1000):
+    """[UPSTREAM] QwenImagePipeline + diffusers FlowMatchEulerDiscreteScheduler(use_dynamic_shifting=True,
+    time_shift_type="exponential"): sigmas = linspace(1, 1/n, n); mu = calculate_shift(image_seq_len) (linear in the
+    sequence length between (base_image_seq_len, base_shift) and (max_image_seq_len, max_shift)); exponential time shift
+    exp(mu) / (exp(mu) + (1/s - 1)); shift_terminal stretch 1 - (1 - s) / ((1 - s[-1]) / (1 - shift_terminal)); a
+    trailing 0.  Returns (sigmas [n+1] fp32, timesteps [n] fp32 = sigmas * num_train_timesteps).
+    The defaults are the Qwen-Image scheduler config as published; the model files are not on this machine's side of
+    the project, so they could not be checked offline -- pass the values of the scheduler_config.json in use."""
+    n = int(num_inference_steps)
+    s = np.linspace(1.0, 1.0 / n, n).astype(np.float32)
+    m = (max_shift - base_shift) / (max_image_seq_len - base_image_seq_len)
+    mu = image_seq_len * m + (base_shift - m * base_image_seq_len)
+    s = (math.exp(mu) / (math.exp(mu) + (1.0 / s.astype(np.float64) - 1.0) ** 1.0))
+    if shift_terminal:
+        one_minus = 1.0 - s
+        s = 1.0 - one_minus / (one_minus[-1] / (1.0 - shift_terminal))
+    s = s.astype(np.float32)
+    return np.concatenate([s, [0.0]]).astype(np.float32), (s * num_train_timesteps).astype(np.float32)
+
+
+def cfg_norm_euler_(latent, pred_cond, pred_uncond, true_cfg_scale, dt):
+    """Qwen-Image's true-CFG step on the device, in place: comb = u + g (c - u), v = comb * |c| / |comb| (norms per token
+    over the channels; v = 0 where |comb| = 0), latent += dt * v.  latent [N, C]; the predictions [>= N, C] (Qwen-Image-
+    Edit: the reference-image rows after the first N are not read)."""
+    lib = _lib.load()
+    assert latent.dtype == pred_cond.dtype == pred_uncond.dtype == torch.float32
+    assert latent.is_contiguous() and pred_cond.is_contiguous() and pred_uncond.is_contiguous()
+    n, c = latent.shape[-2], latent.shape[-1]
+    assert pred_cond.shape[-1] == c and pred_cond.shape[-2] >= n and pred_uncond.shape == pred_cond.shape
+    check(lib.mc_op_cfg_norm_euler(C.c_void_p(pred_cond.data_ptr()), C.c_void_p(pred_uncond.data_ptr()), c,
+                                   float(true_cfg_scale), float(dt), C.c_void_p(latent.data_ptr()), c, n, c,
+                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return latent
+
+
+def sample_qwen_image(model, latents, prompt_embeds, negative_prompt_embeds, img_shapes, num_inference_steps=50,
+                      true_cfg_scale=4.0, image_latents=None, sigmas=None, callback=None):
+    """The denoising loop of QwenImagePipeline / QwenImageEditPipeline around a QwenImageTransformer2DModelHIP: per step
+    the cond forward, then the uncond forward (negative prompt, its own unpadded length), the norm-preserving true-CFG
+    combine and the flow-Euler update as ONE kernel (cfg_norm_euler_).  latents [1, N, 64] packed; image_latents (Edit)
+    [1, N_ref, 64] is appended to the model input every step and the prediction is sliced to the first N rows (the
+    kernel reads only those).  Returns the final packed latents (the pipeline would unpack and VAE-decode them)."""
+    x = latents.to(torch.float32).contiguous().clone()
+    n = x.shape[1]
+    if sigmas is None:
+        sigmas, _ = qwen_image_sigmas(num_inference_steps, n)
+    pe, ne = prompt_embeds, negative_prompt_embeds
+    lens_c, lens_u = [int(pe.shape[1])], [int(ne.shape[1])]
+    do_cfg = true_cfg_scale > 1 and ne is not None
+    for i in range(num_inference_steps):
+        t = torch.tensor([float(sigmas[i]) * 1000.0], device=x.device)
+        inp = x if image_latents is None else torch.cat([x, image_latents.to(x)], dim=1)
+        cond = model(hidden_states=inp, timestep=t / 1000, encoder_hidden_states=pe, img_shapes=img_shapes,
+                     txt_seq_lens=lens_c, return_dict=False)[0]
+        dt = float(sigmas[i + 1]) - float(sigmas[i])
+        if do_cfg:
+            unc = model(hidden_states=inp, timestep=t / 1000, encoder_hidden_states=ne, img_shapes=img_shapes,
+                        txt_seq_lens=lens_u, return_dict=False)[0]
+            cfg_norm_euler_(x[0], cond[0].contiguous(), unc[0].contiguous(), true_cfg_scale, dt)
+        else:
+            lincomb_hip([1.0, dt], [x[0], cond[0, :n].contiguous()], out=x[0])
+        if callback is not None:
+            callback(i, x)
+    return x
