@@ -23,9 +23,13 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-res
 # dispatcher and mc_set_option compiled with MC_WITH_REF_GEMM so that gemm_kernel = 2 selects it.  It is the independent
 # implementation the parity tests compare gemm_bf16_v2 with bit for bit (tests/hip_ops.py: ref_lib()); the product never
 # loads it.  Lives under tests/ and travels to the GPU box like the shipped library.
+# test_ops.cpp adds the mc_test_* entry points (thin wrappers around the launchers of ops.h that the shipped C ABI has no
+# single-op call for: tests/test_tokenwise_ops_gpu.py).  Only REF_RECOMPILED is compiled a second time: every other object --
+# elementwise.hip.o and gemm_mxfp8.hip.o among them -- is the very file the shipped library links, so a test that calls a
+# launcher through the reference library runs the shipped machine code.
 REF_LIB = os.path.join(HERE, "..", "tests", "_ref", "libmagcache_hip_ref.so")
 REF_RECOMPILED = ["gemm_bf16.hip", "engine.cpp"]     # the two translation units that test MC_WITH_REF_GEMM
-REF_EXTRA = ["gemm_bf16_big.hip"]
+REF_EXTRA = ["gemm_bf16_big.hip", "test_ops.cpp"]
 
 
 def _stale(target, deps):

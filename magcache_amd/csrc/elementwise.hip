@@ -476,7 +476,7 @@ __global__ __launch_bounds__(256) void head_linear_kernel(const float* __restric
   const int m0 = blockIdx.x * 64;
   const int n0 = blockIdx.y * 64;
   Wt += (size_t)n0 * K;
-  b += n0;
+  if (b) b += n0;   // a null bias must stay null for the test at the store (column blocks n0 > 0)
   out += n0;
   N -= n0;
   const int tr = tid >> 4, tc = tid & 15;  // thread -> rows tr*4.., cols tc*4..
@@ -666,6 +666,7 @@ hipError_t launch_ln_modulate(const float* x, long ldx, const bf16_t* x0, long l
                               const float* sh, int mode, float eps, bf16_t* out, long ldo, float* out_f32,
                               long ldof, int M, int D, hipStream_t stream, const float* sc2, const float* sh2,
                               const uint8_t* sel) {
+  if (!out && !out_f32) return hipErrorInvalidValue;   // the kernel stores through one of the two
   return launch_ln_t<0>(x, ldx, x0, ldx0, sc, sh, mode, eps, out, ldo, out_f32, ldof, M, D, stream, sc2, sh2, sel,
                         LnQuantOut{nullptr, 0, nullptr, nullptr, 0});
 }
@@ -740,6 +741,7 @@ hipError_t launch_patchify(const float* lat, int C, int F, int H, int W, int tok
 
 hipError_t launch_unpatchify(const float* tok, long ldt, int C, int F, int H, int W, int tok0, int n_tok,
                              float* out, hipStream_t stream) {
+  if ((H & 1) || (W & 1)) return hipErrorInvalidValue;   // patch (1,2,2), as launch_patchify
   hipLaunchKernelGGL(unpatchify_kernel, dim3(grid_for((long)n_tok * 4 * C, 256)), dim3(256), 0, stream, tok, ldt, C,
                      F, H, W, tok0, n_tok, out);
   return hipGetLastError();

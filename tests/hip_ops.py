@@ -195,3 +195,189 @@ def calib_stats(r, rp, n_blocks=2048):     # 2048 = what both engines launch (32
     check(lib.mc_op_calib_stats(P(r), r.stride(0), P(rp), rp.stride(0), r.shape[0], r.shape[1], P(partial), n_blocks,
                                 P(sums), P(stats), S()))
     return stats.cpu(), sums.cpu()
+
+
+# ----------------------------------------------------------------------------- test-only entry points (mc_test_*)
+# magcache_amd/csrc/test_ops.cpp, linked into the REFERENCE library only: thin wrappers around the launchers of ops.h the
+# shipped C ABI has no single-op call for.  The reference library links the shipped elementwise.hip.o / gemm_mxfp8.hip.o, so
+# these run the shipped machine code.  Each returns the launcher's hipError_t (0 = hipSuccess, 1 = hipErrorInvalidValue).
+HIP_INVALID_VALUE = 1
+_vp, _i, _l, _f, _d, _sz = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_double, C.c_size_t
+TEST_SIGNATURES = {
+    "mc_test_headnorm_rope": [_vp, _l, _l, _vp, _vp, _f, _vp, _i, _i, _i, _vp],
+    "mc_test_gemv_bf16w": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
+    "mc_test_gemv_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "mc_test_head_linear": [_vp, _l, _vp, _vp, _vp, _l, _i, _i, _i, _vp],
+    "mc_test_ln_modulate": [_vp, _l, _vp, _l, _vp, _vp, _i, _f, _vp, _l, _vp, _l, _i, _i, _vp, _vp, _vp, _vp],
+    "mc_test_ln_modulate_fp8": [_vp, _l, _vp, _vp, _i, _f, _vp, _l, _vp, _vp, _l, _i, _i, _vp, _vp, _vp, _vp],
+    "mc_test_gemm_mxfp8_gelu_quant": [_vp, _l, _vp, _l, _vp, _l, _vp, _l, _vp, _i, _i, _i, _vp, _l, _vp, _l, _vp],
+    "mc_test_token_t_prepare": [_vp, _i, _i, _i, _i, _vp, _vp, _vp],
+    "mc_test_patchify": [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _l, _vp],
+    "mc_test_unpatchify": [_vp, _l, _i, _i, _i, _i, _i, _i, _vp, _vp],
+    "mc_test_cast_pad_bf16": [_vp, _l, _i, _i, _i, _vp, _l, _vp],
+    "mc_test_cast_bf16": [_vp, _vp, _sz, _vp],
+    "mc_test_add_bf16": [_vp, _vp, _sz, _vp],
+    "mc_test_add_bcast": [_vp, _i, _vp, _vp, _i, _vp],
+    "mc_test_sinusoid": [_vp, _d, _i, _vp, _vp],
+    "mc_test_colmean": [_vp, _l, _i, _i, _vp, _vp],
+    "mc_test_rope_table_from_cos_sin": [_vp, _vp, _l, _i, _vp, _vp],
+    "mc_test_cfg_euler": [_vp, _vp, _f, _f, _vp, _vp, _sz, _vp],
+    "mc_test_attn_merge": [_vp, _vp, _i, _vp, _l, _i, _i, _i, _vp],
+}
+_test_bound = False
+
+
+class HipStatusError(RuntimeError):
+    def __init__(self, name, status):
+        super().__init__(f"{name}: hipError_t {status}")
+        self.status = status
+
+
+def T(name, *args):
+    """call mc_test_<name> of the reference library; a non-zero hipError_t raises HipStatusError"""
+    global _test_bound
+    lib = ref_lib()
+    if not _test_bound:
+        for n, argtypes in TEST_SIGNATURES.items():
+            fn = getattr(lib, n)
+            fn.restype, fn.argtypes = C.c_int, argtypes
+        _test_bound = True
+    status = getattr(lib, "mc_test_" + name)(*args)
+    if status != 0:
+        raise HipStatusError(name, status)
+
+
+def _ld(t):
+    return t.stride(0) if t is not None else 0
+
+
+def headnorm_rope(x, k_col0, wq, wk, eps, cs, cs_row0, n_heads, M=None):
+    """in place on the q | k columns of x [M, ldx] bf16 (q at column 0, k at column k_col0)"""
+    T("headnorm_rope", P(x), x.stride(0), k_col0, P(wq), P(wk), eps, P(cs), cs_row0, x.shape[0] if M is None else M, n_heads, S())
+
+
+def gemv_bf16w(W, x, b, y, act_in=0, act_out=0, accumulate=0, N=None, K=None):
+    T("gemv_bf16w", P(W), P(x), P(b), P(y), W.shape[0] if N is None else N, W.shape[1] if K is None else K, act_in, act_out,
+      accumulate, S())
+
+
+def gemv_f32(W, x, b, y, act_in=0, act_out=0, N=None, K=None):
+    T("gemv_f32", P(W), P(x), P(b), P(y), W.shape[0] if N is None else N, W.shape[1] if K is None else K, act_in, act_out, S())
+
+
+def head_linear(xn, W, b, out, M, N, K):
+    T("head_linear", P(xn), xn.stride(0), P(W), P(b), P(out), out.stride(0), M, N, K, S())
+
+
+def ln_modulate_sel(x, sc, sh, mode, eps, out_bf16=None, out_f32=None, x0=None, sc2=None, sh2=None, sel=None, M=None, D=None):
+    """launch_ln_modulate with every argument (H.ln_modulate is the shipped mc_op_ln_modulate, which has no sc2 / sh2 / sel)"""
+    T("ln_modulate", P(x), x.stride(0), P(x0), _ld(x0), P(sc), P(sh), mode, eps, P(out_bf16), _ld(out_bf16), P(out_f32),
+      _ld(out_f32), x.shape[0] if M is None else M, x.shape[1] if D is None else D, P(sc2), P(sh2), P(sel), S())
+
+
+def ln_modulate_fp8(x, sc, sh, mode, eps, mx, sc2=None, sh2=None, sel=None):
+    """-> (q uint8 [M, D], per-row scales fp32 [M]) or, mx=True, (q, E8M0 scales uint8 [D/32, rows_pad] as quantize_rows_mx)"""
+    M, D = x.shape
+    q = torch.full((M, D), 0x55, dtype=torch.uint8, device=x.device)
+    if mx:
+        rows_pad = (M + 255) // 256 * 256
+        s = torch.full((D // 32, rows_pad), 127, dtype=torch.uint8, device=x.device)
+        T("ln_modulate_fp8", P(x), x.stride(0), P(sc), P(sh), mode, eps, P(q), q.stride(0), None, P(s), rows_pad, M, D, P(sc2),
+          P(sh2), P(sel), S())
+    else:
+        s = torch.full((M,), -1.0, dtype=torch.float32, device=x.device)
+        T("ln_modulate_fp8", P(x), x.stride(0), P(sc), P(sh), mode, eps, P(q), q.stride(0), P(s), None, 0, M, D, P(sc2), P(sh2),
+          P(sel), S())
+    return q, s
+
+
+def gemm_mxfp8_gelu_quant(Aq, sa, Wq, sw, bias):
+    """EPI_GELU_MXFP8 -> (Cq uint8 [M, N] e4m3, c_mx uint8 [N/32, rows_pad]): the A operand of the next MX GEMM"""
+    M, K = Aq.shape
+    N = Wq.shape[0]
+    rows_pad = (M + 255) // 256 * 256
+    cq = torch.full((M, N), 0x55, dtype=torch.uint8, device=Aq.device)
+    cs = torch.full((N // 32, rows_pad), 127, dtype=torch.uint8, device=Aq.device)
+    T("gemm_mxfp8_gelu_quant", P(Aq), Aq.stride(0), P(sa), sa.shape[1], P(Wq), Wq.stride(0), P(sw), sw.shape[1], P(bias), M, N, K,
+      P(cq), cq.stride(0), P(cs), rows_pad, S())
+    return cq, cs
+
+
+def token_t_prepare(t, n_all, row0, n_rows, n_rows_pad, t2, sel):
+    T("token_t_prepare", P(t), n_all, row0, n_rows, n_rows_pad, P(t2), P(sel), S())
+
+
+def patchify(lat, tok0, n_tok, n_rows, out, dims=None):
+    Cc, F_, Hh, Ww = dims or lat.shape
+    T("patchify", P(lat), Cc, F_, Hh, Ww, tok0, n_tok, n_rows, P(out), out.stride(0), S())
+
+
+def unpatchify(tok, tok0, n_tok, out, dims=None):
+    Cc, F_, Hh, Ww = dims or out.shape
+    T("unpatchify", P(tok), tok.stride(0), Cc, F_, Hh, Ww, tok0, n_tok, P(out), S())
+
+
+def cast_pad_bf16(src, rows_valid, rows, cols, dst):
+    T("cast_pad_bf16", P(src), src.stride(0), rows_valid, rows, cols, P(dst), dst.stride(0), S())
+
+
+def cast_bf16(src, dst, n):
+    T("cast_bf16", P(src), P(dst), n, S())
+
+
+def add_bf16(a, b, n):
+    T("add_bf16", P(a), P(b), n, S())
+
+
+def add_bcast(a, b, out, n):
+    T("add_bcast", P(a), a.numel(), P(b), P(out), n, S())
+
+
+def sinusoid(t_dev, t_host, dim, out):
+    T("sinusoid", P(t_dev), float(t_host), dim, P(out), S())
+
+
+def colmean(x, n_rows, D, out):
+    T("colmean", P(x), x.stride(0), n_rows, D, P(out), S())
+
+
+def rope_table_from_cos_sin(cosv, sinv, n_rows, cs):
+    T("rope_table_from_cos_sin", P(cosv), P(sinv), cosv.stride(0), n_rows, P(cs), S())
+
+
+def cfg_euler(cond, uncond, g, dt, x, eps_out, n):
+    T("cfg_euler", P(cond), P(uncond), g, dt, P(x), P(eps_out), n, S())
+
+
+def attn_merge_raw(o_parts, lse_parts, out, rows, rows_pad, d):
+    """launch_attn_merge with explicit rows / rows_pad / d (H.attn_merge takes them from the tensors)"""
+    n = len(o_parts)
+    op = (C.c_void_p * n)(*[t.data_ptr() for t in o_parts])
+    lp = (C.c_void_p * n)(*[t.data_ptr() for t in lse_parts])
+    T("attn_merge", op, lp, n, P(out), out.stride(0), rows, rows_pad, d, S())
+
+
+# ----------------------------------------------------------------------------- helpers shared by the GPU test files
+def mx_quantize_ref(x):
+    """torch restatement of quantize_rows_mx: per (row, 32 k) block e = ceil(log2(amax / 448)) through frexp of
+    amax * fl32(1/448), elements e4m3fn(x * 2^-e), scale byte e + 127."""
+    M, K = x.shape
+    xb = x.float().view(M, K // 32, 32)
+    amax = xb.abs().amax(dim=-1)
+    f, ex = torch.frexp(amax * torch.tensor(1.0 / 448.0, dtype=torch.float32, device=x.device))
+    e = torch.where(f == 0.5, ex - 1, ex).clamp(-127, 127)
+    e = torch.where(amax > 0, e, torch.full_like(e, -127))
+    q = (xb * torch.exp2(-e.float())[..., None]).to(torch.float8_e4m3fn)
+    return q.view(M, K), (e + 127).to(torch.uint8)
+
+
+def v2_sample_rows(M, device="cuda:0"):
+    """>= 512 rows spread over M tiles of 256 at the start, the middle and the end of the row range (under the grouped,
+    XCD-contiguous tile order these land in the first, middle and last persistent trips of different workgroups), and inside
+    a tile the rows where a wave's strip / range-check arithmetic changes: 0..3, 104..131 (incl. 108-111 and 124-127, where the
+    first lean epilogue addressed rows through the buffer soffset and was wrong: profiles/r04/NOTES.md 1.4), 250..255."""
+    tiles = [0, 1, 2, 3, 31, 32, 37, 63, 64, 65, 95, 100, 125, 126, 127]
+    inside = list(range(0, 4)) + list(range(104, 132)) + list(range(250, 256))
+    rows = torch.tensor([t * 256 + r for t in tiles for r in inside if t * 256 + r < M])
+    assert rows.numel() >= 512
+    return rows.to(device)

@@ -762,6 +762,28 @@ def test_reference_library_is_current():
     assert _lib.load().mc_set_option(b"gemm_kernel", 2) == _lib.MC_EINVAL   # ... the shipped one refuses it
 
 
+def test_test_entry_points_live_in_the_reference_library_only():
+    """magcache_amd/csrc/test_ops.cpp (the mc_test_* wrappers tests/test_tokenwise_ops_gpu.py calls) is linked into the
+    reference library and nowhere else: every name tests/hip_ops.py binds is exported there, and the shipped library's
+    dynamic symbol table holds no mc_test_* name at all."""
+    import subprocess
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import hip_ops as H
+
+    def exported(path):
+        out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+        return {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
+    assert H.TEST_SIGNATURES and all(n.startswith("mc_test_") for n in H.TEST_SIGNATURES)
+    ref = exported(H.REF_PATH)
+    missing = sorted(n for n in H.TEST_SIGNATURES if n not in ref)
+    assert not missing, missing
+    leaked = sorted(n for n in exported(_lib.LIB_PATH) if n.startswith("mc_test_"))
+    assert not leaked, leaked
+    shipped = C.CDLL(_lib.LIB_PATH)
+    assert not any(hasattr(shipped, n) for n in H.TEST_SIGNATURES)
+
+
 def test_headers_are_plain_c(tmp_path):
     """include/*.h are the drop-in boundary: they must compile as C99 (gcc -pedantic), with nothing but <stddef.h> / <stdint.h>
     behind them, and the C host of INTEGRATION.md section 4 must at least parse against them."""
