@@ -5,73 +5,25 @@
 // Nothing here allocates or synchronises during a forward: weights are converted once at
 // mc_set_weight, all scratch + the residual cache are carved from one caller-owned workspace, the
 // MagCache decision is made by the caller on the host (reference :277-292 never touches the GPU).
-#include <hip/hip_runtime.h>
-
 #include <cmath>
 #include <cstddef>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
-#include <map>
-#include <string>
-#include <vector>
+#include <memory>
 
-#include "../../include/magcache_hip.h"
-#include "ops.h"
+#include "host.h"
 
+using mc::align_up;
 using mc::bf16_t;
+using mc::fail;
+using mc::gp;
+using mc::Linear;
 
 namespace {
 
-thread_local char g_err[512] = "";
-
-mc_status fail(mc_status s, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return s;
-}
-
-#define HIP_TRY(expr)                                                                              \
-  do {                                                                                             \
-    hipError_t _e = (expr);                                                                        \
-    if (_e != hipSuccess) return fail(MC_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-  } while (0)
-
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-struct Slot {  // one named parameter
-  void* dst = nullptr;
-  mc_dtype dst_dtype = MC_F32;
-  size_t numel = 0;
-  size_t row_off = 0;  // for fused destinations (q/k/v -> wqkv): element offset
-  bool loaded = false;
-  // fp8 weight path: after the bf16 store the same rows are quantised (per output channel) into q8 / q8_scale
-  uint8_t* q8 = nullptr;
-  float* q8_scale = nullptr;
-  size_t q8_k = 0;  // row length (in_features)
-  // fp8_linear == 2 (MX): E8M0 block scales of the fused destination, block-major with mx_rows rows per k block
-  uint8_t* mx = nullptr;
-  size_t mx_rows = 0;
-};
-
 struct Layer {
-  bf16_t *wqkv, *wo, *wcq, *wckv, *wco, *w1, *w2;
-  float *bqkv, *bo, *bcq, *bckv, *bco, *b1, *b2;
+  Linear qkv, o, cq, ckv, co, ffn1, ffn2;   // self-attention q|k|v and o, cross-attention q, k|v and o, the FFN
   float *nq, *nk, *cnq, *cnk, *n3w, *n3b, *mod;
-  bf16_t* wckv_img = nullptr;  // I2V: [k_img ; v_img]
-  float *bckv_img = nullptr, *cnk_img = nullptr;
-  // fp8_linear: e4m3 copies of the three large Linears + per-output-channel scales
-  uint8_t *q_wqkv = nullptr, *q_w1 = nullptr, *q_w2 = nullptr;
-  float *s_wqkv = nullptr, *s_w1 = nullptr, *s_w2 = nullptr;
-  uint8_t *m_wqkv = nullptr, *m_w1 = nullptr, *m_w2 = nullptr;   // fp8_linear >= 2: MX block scales [K/32][N]
-  // fp8_linear == 3: the d x d Linears too (self-attention O, cross-attention Q and O), MX
-  uint8_t *q_wo = nullptr, *q_wcq = nullptr, *q_wco = nullptr, *m_wo = nullptr, *m_wcq = nullptr, *m_wco = nullptr;
-};
-
-struct Buf {
-  size_t off = 0, bytes = 0;
+  Linear ckv_img;  // I2V: [k_img ; v_img]
+  float* cnk_img = nullptr;
 };
 
 }  // namespace
@@ -129,12 +81,8 @@ struct mc_engine {
   int NV = 0, Kvp = 0;
   bool have_vace = false;
   float* cs_table = nullptr;  // rope (cos,sin) [Lp][64][2]
-  std::map<std::string, Slot> slots;
-  std::vector<void*> owned;
-  // workspace
-  char* ws = nullptr;
-  size_t ws_bytes = 0, ws_need = 0;
-  std::map<std::string, Buf> bufs;
+  mc::WeightStore weights;
+  mc::Workspace work;
   int res_slot[2] = {0, 1};  // residual buffer index held by branch b
   int res_scratch = 2;
   bool have_res[2] = {false, false};
@@ -142,10 +90,7 @@ struct mc_engine {
   bool embedded = false;
 
   template <class T>
-  T* buf(const char* name) const {
-    auto it = bufs.find(name);
-    return reinterpret_cast<T*>(ws + it->second.off);
-  }
+  T* buf(const char* name) const { return work.get<T>(name); }
   float* residual(int idx) const {
     static const char* names[3] = {"residual0", "residual1", "residual2"};
     return buf<float>(names[idx]);
@@ -178,33 +123,6 @@ struct Prof {
   Prof& operator=(const Prof&) = delete;
 };
 
-template <class T>
-mc_status dev_alloc(mc_engine* e, T** p, size_t n) {
-  void* q = nullptr;
-  hipError_t err = hipMalloc(&q, n * sizeof(T) + 256);
-  if (err != hipSuccess) return fail(MC_ENOMEM, "hipMalloc(%zu) failed: %s", n * sizeof(T), hipGetErrorString(err));
-  e->owned.push_back(q);
-  *p = reinterpret_cast<T*>(q);
-  return MC_OK;
-}
-
-void add_slot(mc_engine* e, const std::string& name, void* dst, mc_dtype dt, size_t numel, size_t row_off = 0) {
-  Slot s;
-  s.dst = dst;
-  s.dst_dtype = dt;
-  s.numel = numel;
-  s.row_off = row_off;
-  e->slots[name] = s;
-}
-
-void add_buf(mc_engine* e, size_t& cur, const char* name, size_t bytes) {
-  Buf b;
-  b.off = cur;
-  b.bytes = bytes;
-  e->bufs[name] = b;
-  cur = align_up(cur + bytes, 256);
-}
-
 // upstream rope_params / rope_apply frequency split for head_dim 128 (22 + 21 + 21 complex pairs)
 void rope_table_host(int F, int Hp, int Wp, int tok0, int n_tok, float* cs) {
   const int d = 128, c = d / 2;
@@ -230,48 +148,55 @@ void rope_table_host(int F, int Hp, int Wp, int tok0, int n_tok, float* cs) {
   }
 }
 
-mc_status check_ready(const mc_engine* e) {
-  if (!e) return fail(MC_EINVAL, "null engine");
-  if (!e->ws) return fail(MC_ESTATE, "workspace not set (mc_set_workspace)");
-  for (auto& kv : e->slots)
-    if (!kv.second.loaded) return fail(MC_ESTATE, "weight '%s' was never set", kv.first.c_str());
+// One Linear [n_out, k_in] of a block: the bf16 weight + fp32 bias and, quant != QUANT_NONE, an e4m3 copy of the weight.
+// `parts` names the upstream Linears whose rows are stacked in it in equal shares (q | k | v -> qkv); every part's slot
+// carries the quantised copy, so that setting a part requantises its rows of the fused destination.
+enum Quant { QUANT_NONE, QUANT_ROW, QUANT_MX };   // one scale per output channel | one E8M0 byte per (channel, 32 inputs)
+
+mc_status add_linear(mc_engine* e, Linear& l, const std::string& prefix, std::initializer_list<const char*> parts,
+                     size_t n_out, size_t k_in, Quant quant) {
+  mc::WeightStore& w = e->weights;
+  l.n_out = (int)n_out; l.k_in = (int)k_in;
+  MC_TRY(w.alloc(&l.w, n_out * k_in));
+  MC_TRY(w.alloc(&l.b, n_out));
+  if (quant != QUANT_NONE) MC_TRY(w.alloc(&l.q, n_out * k_in));
+  if (quant == QUANT_ROW) MC_TRY(w.alloc(&l.q_scale, n_out));
+  if (quant == QUANT_MX) MC_TRY(w.alloc(&l.mx, (k_in / 32) * n_out));
+  const size_t rows = n_out / parts.size();
+  size_t row0 = 0;
+  for (const char* part : parts) {
+    mc::Slot& s = w.add_linear(prefix + part, l.w, l.b, rows, k_in, row0);
+    s.q8 = l.q; s.q8_scale = l.q_scale; s.q8_k = k_in; s.mx = l.mx; s.mx_rows = n_out;
+    row0 += rows;
+  }
   return MC_OK;
 }
 
-mc::GemmParams gp(const bf16_t* A, long lda, const bf16_t* W, long ldw, const float* bias, int M, int N, int K) {
-  mc::GemmParams p;
-  memset(&p, 0, sizeof(p));
-  p.A = A; p.lda = lda; p.W = W; p.ldw = ldw; p.bias = bias; p.M = M; p.N = N; p.K = K;
-  return p;
+mc_status check_ready(const mc_engine* e) {
+  if (!e) return fail(MC_EINVAL, "null engine");
+  if (!e->work.ws) return fail(MC_ESTATE, "workspace not set (mc_set_workspace)");
+  const char* name = nullptr;
+  if (!e->weights.all_loaded(&name)) return fail(MC_ESTATE, "weight '%s' was never set", name);
+  return MC_OK;
 }
 
 }  // namespace
 
 namespace mc {
-// error text shared with the other engines of this library (mmdit_engine.cpp): mc_last_error() reports it
-mc_status set_error_v(mc_status s, const char* fmt, va_list ap) {
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  return s;
-}
-}  // namespace mc
-
-// mc_set_option("fp8_fused_quant", 0|1): 1 (default) = with fp8_linear the LayerNorm + modulate kernel (and, MX, the GELU
+// option "fp8_fused_quant" (0 | 1): 1 (default) = with fp8_linear the LayerNorm + modulate kernel (and, MX, the GELU
 // epilogue of FFN-1) write the e4m3 operand of the next GEMM directly; 0 = round 3's separate quantise passes (same bits).
-static int g_fp8_fused_quant = 1;
-// mc_set_option("sp_attn_partials", 0|1|2): mc_blocks_sp runs the launches of a layer's self-attention chain independently on
+int g_fp8_fused_quant = 1;
+// option "sp_attn_partials" (0 | 1 | 2): mc_blocks_sp runs the launches of a layer's self-attention chain independently on
 // two streams into partial buffers + one merge kernel -- 1 (default) when a rank's launch fills less than 90 % of the CU slots
 // of the waves it runs in (query blocks x heads against the CU count: 384 workgroups at sp 4 and 192 at sp 8 are 75 %; sp 2's
 // 768 are 100 % and 14B's 1480 at sp 8 96 %: there the merge only costs -- measured -4 % / -4 % / +2 % / +3 % of the layer loop
 // at 1.3B sp 4 / 8 / 2 and 14B sp 8, profiles/r06/sp_timeline*.log), 2 always, 0 never
 // (one stream, merged in place launch by launch)
-static int g_sp_attn_partials = 1;
+int g_sp_attn_partials = 1;
+}  // namespace mc
 static int g_n_cu = 0;
-extern int g_mmdit_two_streams;   // mmdit_engine.cpp: mc_set_option("mmdit_two_streams", v)
 
 extern "C" {
-
-const char* mc_last_error(void) { return g_err; }
-const char* mc_version(void) { return "magcache_hip 0.5 (gfx950)"; }
 
 // mc_config only ever grows at its END, and a zero in a new field keeps the behaviour older callers had: a caller built
 // against an older header passes ITS sizeof(mc_config) and the tail reads as zeros (instead of being read past the end of
@@ -311,17 +236,14 @@ mc_status mc_create(const mc_config* cfg, mc_engine** out) {
   if (c.vace_layers > 0 && c.sp_size > 1 && (c.vace_layers - 1) * c.vace_stride == c.num_layers - 1)
     return fail(MC_EINVAL, "VACE with a hint on the last layer is single-GPU in this engine");
 
-  mc_engine* e = new mc_engine();
+  std::unique_ptr<mc_engine, void (*)(mc_engine*)> own(new mc_engine(), mc_destroy);   // every early return frees it
+  mc_engine* e = own.get();
   e->cfg = c;
   e->d = c.dim; e->ffn = c.ffn_dim; e->H = c.num_heads; e->NL = c.num_layers;
   e->L = c.latent_f * (c.latent_h / 2) * (c.latent_w / 2);
   e->P = c.sp_size; e->rank = c.sp_rank;
   e->sp = c.sp_size > 1 || c.sp_phases != 0;
-  if (e->L % e->P) {
-    const int seq_len = e->L;
-    delete e;
-    return fail(MC_EINVAL, "seq_len %d not divisible by sp_size %d", seq_len, c.sp_size);
-  }
+  if (e->L % e->P) return fail(MC_EINVAL, "seq_len %d not divisible by sp_size %d", e->L, c.sp_size);
   e->Lr = e->L / e->P;
   e->Lp = (int)align_up(e->Lr, 256);
   e->tok0 = e->rank * e->Lr;
@@ -329,109 +251,57 @@ mc_status mc_create(const mc_config* cfg, mc_engine** out) {
   e->HT = (int)align_up((size_t)c.out_dim * 4, 64);
   e->ctx_rows = (int)align_up(c.text_len, 64);
   const size_t d = e->d, ffn = e->ffn;
+  mc::WeightStore& W = e->weights;
 
-  mc_status st = MC_OK;
-#define ALLOC(ptr, n) do { st = dev_alloc(e, &(ptr), (n)); if (st != MC_OK) { mc_destroy(e); return st; } } while (0)
+#define ALLOC(ptr, n) MC_TRY(W.alloc(&(ptr), (n)))
+  // fp8_linear only decides which Linears keep an e4m3 copy and of which kind: 1 = QKV, FFN-1, FFN-2 with per-row scales,
+  // 2 = the same three with MX block scales, 3 = MX, the d x d Linears (self-attention O, cross-attention Q and O) too
+  const Quant q_big = c.fp8_linear >= 2 ? QUANT_MX : c.fp8_linear == 1 ? QUANT_ROW : QUANT_NONE;
+  const Quant q_dd = c.fp8_linear == 3 ? QUANT_MX : QUANT_NONE;
   e->layers.resize(e->NL);
   e->NV = c.vace_layers;
   e->vlayers.resize(e->NV);
   for (int i = 0; i < e->NL + e->NV; ++i) {
     const bool is_vace = i >= e->NL;
     Layer& l = is_vace ? e->vlayers[i - e->NL] : e->layers[i];
-    ALLOC(l.wqkv, 3 * d * d); ALLOC(l.bqkv, 3 * d); ALLOC(l.nq, d); ALLOC(l.nk, d);
-    ALLOC(l.wo, d * d); ALLOC(l.bo, d);
-    ALLOC(l.n3w, d); ALLOC(l.n3b, d);
-    ALLOC(l.wcq, d * d); ALLOC(l.bcq, d); ALLOC(l.cnq, d);
-    ALLOC(l.wckv, 2 * d * d); ALLOC(l.bckv, 2 * d); ALLOC(l.cnk, d);
-    ALLOC(l.wco, d * d); ALLOC(l.bco, d);
-    ALLOC(l.w1, ffn * d); ALLOC(l.b1, ffn); ALLOC(l.w2, d * ffn); ALLOC(l.b2, d);
-    ALLOC(l.mod, 6 * d);
     const std::string p = (is_vace ? "vace_blocks." + std::to_string(i - e->NL) : "blocks." + std::to_string(i)) + ".";
-    add_slot(e, p + "self_attn.q.weight", l.wqkv, MC_BF16, d * d, 0);
-    add_slot(e, p + "self_attn.k.weight", l.wqkv, MC_BF16, d * d, d * d);
-    add_slot(e, p + "self_attn.v.weight", l.wqkv, MC_BF16, d * d, 2 * d * d);
-    add_slot(e, p + "self_attn.q.bias", l.bqkv, MC_F32, d, 0);
-    add_slot(e, p + "self_attn.k.bias", l.bqkv, MC_F32, d, d);
-    add_slot(e, p + "self_attn.v.bias", l.bqkv, MC_F32, d, 2 * d);
-    add_slot(e, p + "self_attn.norm_q.weight", l.nq, MC_F32, d);
-    add_slot(e, p + "self_attn.norm_k.weight", l.nk, MC_F32, d);
-    add_slot(e, p + "self_attn.o.weight", l.wo, MC_BF16, d * d);
-    add_slot(e, p + "self_attn.o.bias", l.bo, MC_F32, d);
-    add_slot(e, p + "norm3.weight", l.n3w, MC_F32, d);
-    add_slot(e, p + "norm3.bias", l.n3b, MC_F32, d);
-    add_slot(e, p + "cross_attn.q.weight", l.wcq, MC_BF16, d * d);
-    add_slot(e, p + "cross_attn.q.bias", l.bcq, MC_F32, d);
-    add_slot(e, p + "cross_attn.norm_q.weight", l.cnq, MC_F32, d);
-    add_slot(e, p + "cross_attn.k.weight", l.wckv, MC_BF16, d * d, 0);
-    add_slot(e, p + "cross_attn.v.weight", l.wckv, MC_BF16, d * d, d * d);
-    add_slot(e, p + "cross_attn.k.bias", l.bckv, MC_F32, d, 0);
-    add_slot(e, p + "cross_attn.v.bias", l.bckv, MC_F32, d, d);
-    add_slot(e, p + "cross_attn.norm_k.weight", l.cnk, MC_F32, d);
-    add_slot(e, p + "cross_attn.o.weight", l.wco, MC_BF16, d * d);
-    add_slot(e, p + "cross_attn.o.bias", l.bco, MC_F32, d);
-    add_slot(e, p + "ffn.0.weight", l.w1, MC_BF16, ffn * d);
-    add_slot(e, p + "ffn.0.bias", l.b1, MC_F32, ffn);
-    add_slot(e, p + "ffn.2.weight", l.w2, MC_BF16, d * ffn);
-    add_slot(e, p + "ffn.2.bias", l.b2, MC_F32, d);
-    add_slot(e, p + "modulation", l.mod, MC_F32, 6 * d);
-    if (c.fp8_linear) {
-      ALLOC(l.q_wqkv, 3 * d * d); ALLOC(l.s_wqkv, 3 * d);
-      ALLOC(l.q_w1, ffn * d); ALLOC(l.s_w1, ffn);
-      ALLOC(l.q_w2, d * ffn); ALLOC(l.s_w2, d);
-      const char* qkv_names[3] = {"self_attn.q.weight", "self_attn.k.weight", "self_attn.v.weight"};
-      for (int j = 0; j < 3; ++j) {
-        Slot& sl = e->slots[p + qkv_names[j]];
-        sl.q8 = l.q_wqkv; sl.q8_scale = l.s_wqkv; sl.q8_k = d;
-      }
-      Slot& s1 = e->slots[p + "ffn.0.weight"];
-      s1.q8 = l.q_w1; s1.q8_scale = l.s_w1; s1.q8_k = d;
-      Slot& s2 = e->slots[p + "ffn.2.weight"];
-      s2.q8 = l.q_w2; s2.q8_scale = l.s_w2; s2.q8_k = ffn;
-      if (c.fp8_linear >= 2) {   // MX: one E8M0 byte per (output channel, 32 input features), block-major
-        ALLOC(l.m_wqkv, (d / 32) * 3 * d); ALLOC(l.m_w1, (d / 32) * ffn); ALLOC(l.m_w2, (ffn / 32) * d);
-        for (int j = 0; j < 3; ++j) {
-          Slot& sl = e->slots[p + qkv_names[j]];
-          sl.mx = l.m_wqkv; sl.mx_rows = 3 * d;
-        }
-        s1.mx = l.m_w1; s1.mx_rows = ffn;
-        s2.mx = l.m_w2; s2.mx_rows = d;
-      }
-      if (c.fp8_linear == 3) {
-        const struct { const char* name; uint8_t** q; uint8_t** m; } dd[3] = {
-            {"self_attn.o.weight", &l.q_wo, &l.m_wo}, {"cross_attn.q.weight", &l.q_wcq, &l.m_wcq},
-            {"cross_attn.o.weight", &l.q_wco, &l.m_wco}};
-        for (const auto& w : dd) {
-          ALLOC(*w.q, d * d); ALLOC(*w.m, (d / 32) * d);
-          Slot& sl = e->slots[p + w.name];
-          sl.q8 = *w.q; sl.q8_scale = nullptr; sl.q8_k = d; sl.mx = *w.m; sl.mx_rows = d;
-        }
-      }
-    }
+    MC_TRY(add_linear(e, l.qkv, p + "self_attn.", {"q", "k", "v"}, 3 * d, d, q_big));
+    MC_TRY(add_linear(e, l.o, p + "self_attn.", {"o"}, d, d, q_dd));
+    MC_TRY(add_linear(e, l.cq, p + "cross_attn.", {"q"}, d, d, q_dd));
+    MC_TRY(add_linear(e, l.ckv, p + "cross_attn.", {"k", "v"}, 2 * d, d, QUANT_NONE));
+    MC_TRY(add_linear(e, l.co, p + "cross_attn.", {"o"}, d, d, q_dd));
+    MC_TRY(add_linear(e, l.ffn1, p + "ffn.", {"0"}, ffn, d, q_big));
+    MC_TRY(add_linear(e, l.ffn2, p + "ffn.", {"2"}, d, ffn, q_big));
+    ALLOC(l.nq, d); ALLOC(l.nk, d); ALLOC(l.n3w, d); ALLOC(l.n3b, d); ALLOC(l.cnq, d); ALLOC(l.cnk, d); ALLOC(l.mod, 6 * d);
+    W.add(p + "self_attn.norm_q.weight", l.nq, MC_F32, d);
+    W.add(p + "self_attn.norm_k.weight", l.nk, MC_F32, d);
+    W.add(p + "norm3.weight", l.n3w, MC_F32, d);
+    W.add(p + "norm3.bias", l.n3b, MC_F32, d);
+    W.add(p + "cross_attn.norm_q.weight", l.cnq, MC_F32, d);
+    W.add(p + "cross_attn.norm_k.weight", l.cnk, MC_F32, d);
+    W.add(p + "modulation", l.mod, MC_F32, 6 * d);
     if (c.clip_dim > 0) {
-      ALLOC(l.wckv_img, 2 * d * d); ALLOC(l.bckv_img, 2 * d); ALLOC(l.cnk_img, d);
-      add_slot(e, p + "cross_attn.k_img.weight", l.wckv_img, MC_BF16, d * d, 0);
-      add_slot(e, p + "cross_attn.v_img.weight", l.wckv_img, MC_BF16, d * d, d * d);
-      add_slot(e, p + "cross_attn.k_img.bias", l.bckv_img, MC_F32, d, 0);
-      add_slot(e, p + "cross_attn.v_img.bias", l.bckv_img, MC_F32, d, d);
-      add_slot(e, p + "cross_attn.norm_k_img.weight", l.cnk_img, MC_F32, d);
+      MC_TRY(add_linear(e, l.ckv_img, p + "cross_attn.", {"k_img", "v_img"}, 2 * d, d, QUANT_NONE));
+      ALLOC(l.cnk_img, d);
+      W.add(p + "cross_attn.norm_k_img.weight", l.cnk_img, MC_F32, d);
     }
   }
   if (e->NV > 0) {
     e->Kvp = (int)align_up((size_t)c.vace_in_dim * 4, 64);
     const size_t kv = (size_t)c.vace_in_dim * 4;
-    if (kv != (size_t)e->Kvp) { mc_destroy(e); return fail(MC_EINVAL, "vace_in_dim*4 must be a multiple of 64"); }
+    if (kv != (size_t)e->Kvp) { return fail(MC_EINVAL, "vace_in_dim*4 must be a multiple of 64"); }
     ALLOC(e->w_vpatch, d * kv); ALLOC(e->b_vpatch, d); ALLOC(e->w_before, d * d); ALLOC(e->b_before, d);
     ALLOC(e->vscale, d);
-    add_slot(e, "vace_patch_embedding.weight", e->w_vpatch, MC_BF16, d * kv);
-    add_slot(e, "vace_patch_embedding.bias", e->b_vpatch, MC_F32, d);
-    add_slot(e, "vace_blocks.0.before_proj.weight", e->w_before, MC_BF16, d * d);
-    add_slot(e, "vace_blocks.0.before_proj.bias", e->b_before, MC_F32, d);
+    W.add("vace_patch_embedding.weight", e->w_vpatch, MC_BF16, d * kv);
+    W.add("vace_patch_embedding.bias", e->b_vpatch, MC_F32, d);
+    W.add("vace_blocks.0.before_proj.weight", e->w_before, MC_BF16, d * d);
+    W.add("vace_blocks.0.before_proj.bias", e->b_before, MC_F32, d);
     e->w_after.resize(e->NV); e->b_after.resize(e->NV);
     for (int i = 0; i < e->NV; ++i) {
       ALLOC(e->w_after[i], d * d); ALLOC(e->b_after[i], d);
       const std::string p = "vace_blocks." + std::to_string(i) + ".after_proj.";
-      add_slot(e, p + "weight", e->w_after[i], MC_BF16, d * d);
-      add_slot(e, p + "bias", e->b_after[i], MC_F32, d);
+      W.add(p + "weight", e->w_after[i], MC_BF16, d * d);
+      W.add(p + "bias", e->b_after[i], MC_F32, d);
     }
   }
   if (c.clip_dim > 0) {
@@ -439,14 +309,14 @@ mc_status mc_create(const mc_config* cfg, mc_engine** out) {
     e->img_rows = (int)align_up(257, 64);
     ALLOC(e->ln_img0_w, cd); ALLOC(e->ln_img0_b, cd); ALLOC(e->w_img1, cd * cd); ALLOC(e->b_img1, cd);
     ALLOC(e->w_img3, d * cd); ALLOC(e->b_img3, d); ALLOC(e->ln_img4_w, d); ALLOC(e->ln_img4_b, d);
-    add_slot(e, "img_emb.proj.0.weight", e->ln_img0_w, MC_F32, cd);
-    add_slot(e, "img_emb.proj.0.bias", e->ln_img0_b, MC_F32, cd);
-    add_slot(e, "img_emb.proj.1.weight", e->w_img1, MC_BF16, cd * cd);
-    add_slot(e, "img_emb.proj.1.bias", e->b_img1, MC_F32, cd);
-    add_slot(e, "img_emb.proj.3.weight", e->w_img3, MC_BF16, d * cd);
-    add_slot(e, "img_emb.proj.3.bias", e->b_img3, MC_F32, d);
-    add_slot(e, "img_emb.proj.4.weight", e->ln_img4_w, MC_F32, d);
-    add_slot(e, "img_emb.proj.4.bias", e->ln_img4_b, MC_F32, d);
+    W.add("img_emb.proj.0.weight", e->ln_img0_w, MC_F32, cd);
+    W.add("img_emb.proj.0.bias", e->ln_img0_b, MC_F32, cd);
+    W.add("img_emb.proj.1.weight", e->w_img1, MC_BF16, cd * cd);
+    W.add("img_emb.proj.1.bias", e->b_img1, MC_F32, cd);
+    W.add("img_emb.proj.3.weight", e->w_img3, MC_BF16, d * cd);
+    W.add("img_emb.proj.3.bias", e->b_img3, MC_F32, d);
+    W.add("img_emb.proj.4.weight", e->ln_img4_w, MC_F32, d);
+    W.add("img_emb.proj.4.bias", e->ln_img4_b, MC_F32, d);
   }
   const size_t kin = (size_t)c.in_dim * 4;
   ALLOC(e->w_patch, d * e->Kp); ALLOC(e->b_patch, d);
@@ -456,21 +326,22 @@ mc_status mc_create(const mc_config* cfg, mc_engine** out) {
   ALLOC(e->w_tproj, 6 * d * d); ALLOC(e->b_tproj, 6 * d);
   ALLOC(e->w_head, (size_t)c.out_dim * 4 * d); ALLOC(e->b_head, (size_t)c.out_dim * 4); ALLOC(e->head_mod, 2 * d);
   // patch weight [d, in_dim, 1, 2, 2] is stored [d, Kp] (Kp = in_dim*4 padded to a GEMM K step)
-  add_slot(e, "patch_embedding.weight", e->w_patch, MC_BF16, d * kin);
-  add_slot(e, "patch_embedding.bias", e->b_patch, MC_F32, d);
-  add_slot(e, "text_embedding.0.weight", e->w_text0, MC_BF16, d * c.text_dim);
-  add_slot(e, "text_embedding.0.bias", e->b_text0, MC_F32, d);
-  add_slot(e, "text_embedding.2.weight", e->w_text1, MC_BF16, d * d);
-  add_slot(e, "text_embedding.2.bias", e->b_text1, MC_F32, d);
-  add_slot(e, "time_embedding.0.weight", e->w_time0, MC_F32, d * c.freq_dim);
-  add_slot(e, "time_embedding.0.bias", e->b_time0, MC_F32, d);
-  add_slot(e, "time_embedding.2.weight", e->w_time1, MC_F32, d * d);
-  add_slot(e, "time_embedding.2.bias", e->b_time1, MC_F32, d);
-  add_slot(e, "time_projection.1.weight", e->w_tproj, MC_F32, 6 * d * d);
-  add_slot(e, "time_projection.1.bias", e->b_tproj, MC_F32, 6 * d);
-  add_slot(e, "head.head.weight", e->w_head, MC_F32, (size_t)c.out_dim * 4 * d);
-  add_slot(e, "head.head.bias", e->b_head, MC_F32, (size_t)c.out_dim * 4);
-  add_slot(e, "head.modulation", e->head_mod, MC_F32, 2 * d);
+  mc::Slot& patch = W.add("patch_embedding.weight", e->w_patch, MC_BF16, d * kin);
+  if (kin != (size_t)e->Kp) patch.pad = {d, kin, (size_t)e->Kp};
+  W.add("patch_embedding.bias", e->b_patch, MC_F32, d);
+  W.add("text_embedding.0.weight", e->w_text0, MC_BF16, d * c.text_dim);
+  W.add("text_embedding.0.bias", e->b_text0, MC_F32, d);
+  W.add("text_embedding.2.weight", e->w_text1, MC_BF16, d * d);
+  W.add("text_embedding.2.bias", e->b_text1, MC_F32, d);
+  W.add("time_embedding.0.weight", e->w_time0, MC_F32, d * c.freq_dim);
+  W.add("time_embedding.0.bias", e->b_time0, MC_F32, d);
+  W.add("time_embedding.2.weight", e->w_time1, MC_F32, d * d);
+  W.add("time_embedding.2.bias", e->b_time1, MC_F32, d);
+  W.add("time_projection.1.weight", e->w_tproj, MC_F32, 6 * d * d);
+  W.add("time_projection.1.bias", e->b_tproj, MC_F32, 6 * d);
+  W.add("head.head.weight", e->w_head, MC_F32, (size_t)c.out_dim * 4 * d);
+  W.add("head.head.bias", e->b_head, MC_F32, (size_t)c.out_dim * 4);
+  W.add("head.modulation", e->head_mod, MC_F32, 2 * d);
 
   // RoPE table for this rank's rows
   ALLOC(e->cs_table, (size_t)e->Lp * 128);
@@ -485,78 +356,77 @@ mc_status mc_create(const mc_config* cfg, mc_engine** out) {
 #undef ALLOC
 
   // ---- workspace plan
-  size_t cur = 0;
+  mc::Workspace& ws = e->work;
   const size_t Lp = e->Lp;
-  add_buf(e, cur, "x", Lp * d * 4);
-  add_buf(e, cur, "x0", Lp * d * 2);
-  add_buf(e, cur, "xn", Lp * d * 2);
-  add_buf(e, cur, "qkv", Lp * 3 * d * 2);  // P>1: only the first Lp*d (q) is used
-  add_buf(e, cur, "ao", Lp * d * 2);
-  add_buf(e, cur, "h", std::max(Lp * ffn * 2, Lp * d * 4));  // FFN hidden (bf16) / head LN out (fp32)
-  add_buf(e, cur, "tokens", Lp * e->Kp * 2);
-  add_buf(e, cur, "ctx_in", (size_t)e->ctx_rows * c.text_dim * 2);
-  add_buf(e, cur, "ctx_h", (size_t)e->ctx_rows * d * 2);
-  add_buf(e, cur, "ctx", (size_t)e->ctx_rows * d * 2);
-  add_buf(e, cur, "ckv", (size_t)e->ctx_rows * 2 * d * 2);
-  add_buf(e, cur, "ctx_cache", (size_t)2 * e->ctx_rows * d * 2);                              // [2 slots][ctx_rows][d]
+  ws.add("x", Lp * d * 4);
+  ws.add("x0", Lp * d * 2);
+  ws.add("xn", Lp * d * 2);
+  ws.add("qkv", Lp * 3 * d * 2);  // P>1: only the first Lp*d (q) is used
+  ws.add("ao", Lp * d * 2);
+  ws.add("h", std::max(Lp * ffn * 2, Lp * d * 4));  // FFN hidden (bf16) / head LN out (fp32)
+  ws.add("tokens", Lp * e->Kp * 2);
+  ws.add("ctx_in", (size_t)e->ctx_rows * c.text_dim * 2);
+  ws.add("ctx_h", (size_t)e->ctx_rows * d * 2);
+  ws.add("ctx", (size_t)e->ctx_rows * d * 2);
+  ws.add("ckv", (size_t)e->ctx_rows * 2 * d * 2);
+  ws.add("ctx_cache", (size_t)2 * e->ctx_rows * d * 2);                              // [2 slots][ctx_rows][d]
   if (!c.no_context_cache)      // (0.84 GB at 14B that a caller who passes its context every forward never uses)
-    add_buf(e, cur, "ckv_cache", (size_t)2 * (e->NL + e->NV) * e->ctx_rows * 2 * d * 2);      // [2][layers][ctx_rows][2d]
+    ws.add("ckv_cache", (size_t)2 * (e->NL + e->NV) * e->ctx_rows * 2 * d * 2);      // [2][layers][ctx_rows][2d]
   // two sets of everything that depends on t: set 0 for the (maximum) timestep, set 1 for the second value per-token
   // timesteps may carry (Wan2.2 TI2V: the conditioning frame's tokens have t = 0)
   const size_t tsets = c.no_token_timesteps ? 1 : 2;
-  add_buf(e, cur, "temb", tsets * (c.freq_dim + 2 * d + 6 * d) * 4);  // sets x (sinus | h1 | e | e0)
-  add_buf(e, cur, "emod", tsets * (e->NL + e->NV) * 6 * d * 4);
-  add_buf(e, cur, "tok_sel", c.no_token_timesteps ? 256 : (size_t)Lp + 256);
-  add_buf(e, cur, "tok_t2", 64);
+  ws.add("temb", tsets * (c.freq_dim + 2 * d + 6 * d) * 4);  // sets x (sinus | h1 | e | e0)
+  ws.add("emod", tsets * (e->NL + e->NV) * 6 * d * 4);
+  ws.add("tok_sel", c.no_token_timesteps ? 256 : (size_t)Lp + 256);
+  ws.add("tok_t2", 64);
   if (c.fp8_linear) {
-    add_buf(e, cur, "aq", Lp * std::max(d, ffn));            // e4m3 activations of the current fp8 GEMM
-    add_buf(e, cur, "a_scale", Lp * 4);                      // their per-token scales
-    if (c.fp8_linear >= 2) add_buf(e, cur, "a_mx", (std::max(d, ffn) / 32) * Lp);   // MX: per (token, 32 k) block scales
+    ws.add("aq", Lp * std::max(d, ffn));            // e4m3 activations of the current fp8 GEMM
+    ws.add("a_scale", Lp * 4);                      // their per-token scales
+    if (c.fp8_linear >= 2) ws.add("a_mx", (std::max(d, ffn) / 32) * Lp);   // MX: per (token, 32 k) block scales
   }
   if (e->NV > 0) {
-    add_buf(e, cur, "xc", Lp * d * 4);                       // VACE control stream c (fp32 like x)
-    add_buf(e, cur, "c0", Lp * d * 2);                       // vace_patch_embedding(vace_context), constant per video
-    add_buf(e, cur, "vtokens", Lp * (size_t)e->Kvp * 2);
+    ws.add("xc", Lp * d * 4);                       // VACE control stream c (fp32 like x)
+    ws.add("c0", Lp * d * 2);                       // vace_patch_embedding(vace_context), constant per video
+    ws.add("vtokens", Lp * (size_t)e->Kvp * 2);
   }
-  add_buf(e, cur, "ehead", 2 * 2 * d * 4);
-  add_buf(e, cur, "head_tokens", (size_t)Lp * e->HT * 4);
+  ws.add("ehead", 2 * 2 * d * 4);
+  ws.add("head_tokens", (size_t)Lp * e->HT * 4);
   // sequence parallel: "kv_local" [Lp][2d] = this rank's post-norm, post-RoPE K|V rows (the send buffer of the gather);
   // "kv_gather" [C][P][Lp / C][2d] = round c of the gather holds rows [c Lp / C, (c + 1) Lp / C) of EVERY rank's shard
-  add_buf(e, cur, "kv_local", e->sp ? Lp * 2 * d * 2 : 256);
-  add_buf(e, cur, "kv_gather", e->sp ? (size_t)e->P * Lp * 2 * d * 2 : 256);
-  add_buf(e, cur, "residual0", Lp * d * 4);
-  add_buf(e, cur, "residual1", c.n_branches > 1 ? Lp * d * 4 : 256);
-  add_buf(e, cur, "residual2", c.calibration ? Lp * d * 4 : 256);
+  ws.add("kv_local", e->sp ? Lp * 2 * d * 2 : 256);
+  ws.add("kv_gather", e->sp ? (size_t)e->P * Lp * 2 * d * 2 : 256);
+  ws.add("residual0", Lp * d * 4);
+  ws.add("residual1", c.n_branches > 1 ? Lp * d * 4 : 256);
+  ws.add("residual2", c.calibration ? Lp * d * 4 : 256);
   if (c.clip_dim > 0) {
     const size_t ir = e->img_rows, cd = c.clip_dim;
-    add_buf(e, cur, "clip_in", ir * cd * 4);
-    add_buf(e, cur, "clip_n", ir * cd * 2);
-    add_buf(e, cur, "clip_h", ir * cd * 2);
-    add_buf(e, cur, "clip_o", ir * d * 4);
-    add_buf(e, cur, "clip_h2", ir * d * 2);
-    add_buf(e, cur, "ctx_img", ir * d * 2);
-    add_buf(e, cur, "ckv_img", ir * 2 * d * 2);
-    add_buf(e, cur, "ao2", Lp * d * 2);
+    ws.add("clip_in", ir * cd * 4);
+    ws.add("clip_n", ir * cd * 2);
+    ws.add("clip_h", ir * cd * 2);
+    ws.add("clip_o", ir * d * 4);
+    ws.add("clip_h2", ir * d * 2);
+    ws.add("ctx_img", ir * d * 2);
+    ws.add("ckv_img", ir * 2 * d * 2);
+    ws.add("ao2", Lp * d * 2);
   }
-  if (e->sp) add_buf(e, cur, "attn_lse", (size_t)e->H * Lp * 4);
+  if (e->sp) ws.add("attn_lse", (size_t)e->H * Lp * 4);
   // split-K scratch of FFN-2 (K = ffn): a rank of a wide sequence-parallel job has too few 256^2 tiles for the chip (sp 8 at
   // 1.3B: M = 4096 -> 96 tiles), launch_gemm_bf16 then cuts K in slices (policy: gemm_bf16_v2.hip); 0 bytes where it would not
   e->splitk_bytes = e->sp ? mc::gemm_splitk_ws_need((int)Lp, (int)d, (int)ffn, mc::EPI_RESID_GATE) : 0;
-  add_buf(e, cur, "splitk", e->splitk_bytes ? e->splitk_bytes : 256);
+  ws.add("splitk", e->splitk_bytes ? e->splitk_bytes : 256);
   // partial attention results of a layer's chain (local shard + up to 8 gather rounds), merged by attn_merge
-  add_buf(e, cur, "ao_part", e->P > 1 ? (size_t)kSpMaxParts * Lp * d * 2 : 256);
-  add_buf(e, cur, "lse_part", e->P > 1 ? (size_t)kSpMaxParts * e->H * Lp * 4 : 256);
-  add_buf(e, cur, "calib_partial", (2048 * 4 + 2) * 8);   // + the arrival ticket of calib_stats_kernel
-  add_buf(e, cur, "calib_sums", 4 * 8);
-  add_buf(e, cur, "calib_stats", 2 * 3 * 4);
-  e->ws_need = cur;
-  *out = e;
+  ws.add("ao_part", e->P > 1 ? (size_t)kSpMaxParts * Lp * d * 2 : 256);
+  ws.add("lse_part", e->P > 1 ? (size_t)kSpMaxParts * e->H * Lp * 4 : 256);
+  ws.add("calib_partial", (2048 * 4 + 2) * 8);   // + the arrival ticket of calib_stats_kernel
+  ws.add("calib_sums", 4 * 8);
+  ws.add("calib_stats", 2 * 3 * 4);
+  *out = own.release();
   return MC_OK;
 }
 
 void mc_destroy(mc_engine* e) {
   if (!e) return;
-  for (void* p : e->owned) (void)hipFree(p);
+  e->weights.free_all();
   for (hipEvent_t ev : e->prof_ev) (void)hipEventDestroy(ev);
   if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
   if (e->ev_join) (void)hipEventDestroy(e->ev_join);
@@ -564,14 +434,11 @@ void mc_destroy(mc_engine* e) {
   delete e;
 }
 
-size_t mc_workspace_bytes(const mc_engine* e) { return e ? e->ws_need : 0; }
+size_t mc_workspace_bytes(const mc_engine* e) { return e ? e->work.need : 0; }
 
 mc_status mc_set_workspace(mc_engine* e, void* ws_dev, size_t bytes) {
-  if (!e || !ws_dev) return fail(MC_EINVAL, "null argument");
-  if (bytes < e->ws_need) return fail(MC_EINVAL, "workspace too small: %zu < %zu", bytes, e->ws_need);
-  if (((uintptr_t)ws_dev) & 255) return fail(MC_EINVAL, "workspace must be 256-byte aligned");
-  e->ws = (char*)ws_dev;
-  e->ws_bytes = bytes;
+  if (!e) return fail(MC_EINVAL, "null argument");
+  MC_TRY(e->work.bind(ws_dev, bytes));
   e->have_res[0] = e->have_res[1] = false;
   // the arrival ticket of the one-launch calibration reduction starts at zero (the kernel rearms it itself)
   HIP_TRY(hipMemset(e->buf<double>("calib_partial") + 2048 * 4, 0, 16));
@@ -585,78 +452,20 @@ mc_status mc_buffer_info(const mc_engine* e, const char* name, size_t* offset, s
     static const char* names[3] = {"residual0", "residual1", "residual2"};
     n = names[e->res_slot[n.back() - '0']];
   }
-  auto it = e->bufs.find(n);
-  if (it == e->bufs.end()) return fail(MC_EINVAL, "unknown buffer '%s'", name);
-  if (offset) *offset = it->second.off;
-  if (bytes) *bytes = it->second.bytes;
-  return MC_OK;
+  return e->work.info(n, offset, bytes);
 }
 
 mc_status mc_set_weight(mc_engine* e, const char* name, const void* src_dev, mc_dtype dtype, const int64_t* shape,
-                        int ndim, mc_stream stream_) {
+                        int ndim, mc_stream stream) {
   if (e) {  // any cached text context was computed with the old weights
     e->ctx_valid[0] = e->ctx_valid[1] = false;
     e->ctx_active = -1;
   }
-  hipStream_t stream = (hipStream_t)stream_;
   if (!e || !name || !src_dev || !shape) return fail(MC_EINVAL, "null argument");
-  auto it = e->slots.find(name);
-  if (it == e->slots.end()) return fail(MC_EINVAL, "unknown weight '%s'", name);
-  Slot& s = it->second;
-  size_t numel = 1;
-  for (int i = 0; i < ndim; ++i) numel *= (size_t)shape[i];
-  if (numel != s.numel) return fail(MC_EINVAL, "weight '%s': %zu elements given, %zu expected", name, numel, s.numel);
-  const bool is_patch = (std::string(name) == "patch_embedding.weight");
-  if (s.dst_dtype == MC_F32) {
-    if (dtype != MC_F32) return fail(MC_EINVAL, "weight '%s' must be given as fp32", name);
-    HIP_TRY(hipMemcpyAsync((float*)s.dst + s.row_off, src_dev, numel * 4, hipMemcpyDeviceToDevice, stream));
-  } else {
-    bf16_t* dst = (bf16_t*)s.dst + s.row_off;
-    const size_t kin = (size_t)e->cfg.in_dim * 4;
-    if (is_patch && kin != (size_t)e->Kp) {
-      // [d, kin] -> [d, Kp] row pitch (padding columns stay zero)
-      if (dtype == MC_F32) {
-        HIP_TRY(mc::launch_cast_pad_bf16((const float*)src_dev, (long)kin, e->d, e->d, (int)kin, dst, e->Kp, stream));
-      } else {
-        HIP_TRY(hipMemcpy2DAsync(dst, e->Kp * 2, src_dev, kin * 2, kin * 2, e->d, hipMemcpyDeviceToDevice, stream));
-      }
-    } else if (dtype == MC_F32) {
-      HIP_TRY(mc::launch_cast_bf16((const float*)src_dev, dst, numel, stream));
-    } else {
-      HIP_TRY(hipMemcpyAsync(dst, src_dev, numel * 2, hipMemcpyDeviceToDevice, stream));
-    }
-    if (s.q8) {  // fp8 weight path: e4m3 copy of the rows just stored, one scale per output channel
-      const size_t rows = numel / s.q8_k, row0 = s.row_off / s.q8_k;
-      if (s.mx) {  // MX: the e4m3 bytes are relative to the block scales, not to a row scale
-        HIP_TRY(mc::launch_quantize_rows_mx(dst, nullptr, (long)s.q8_k, (int)rows, (int)s.q8_k, s.q8 + s.row_off,
-                                            (long)s.q8_k, s.mx + row0, (long)s.mx_rows, stream));
-      } else {
-        HIP_TRY(mc::launch_quantize_rows_fp8(dst, nullptr, (long)s.q8_k, (int)rows, (int)s.q8_k, s.q8 + s.row_off,
-                                             (long)s.q8_k, s.q8_scale + row0, stream));
-      }
-    }
-  }
-  s.loaded = true;
-  return MC_OK;
+  return e->weights.set(name, src_dev, dtype, shape, ndim, (hipStream_t)stream);
 }
 
-int mc_weights_missing(const mc_engine* e, char* buf, size_t buflen) {
-  if (!e) return -1;
-  int n = 0;
-  size_t pos = 0;
-  if (buf && buflen) buf[0] = 0;
-  for (auto& kv : e->slots) {
-    if (kv.second.loaded) continue;
-    ++n;
-    if (buf && pos + kv.first.size() + 2 < buflen) {
-      memcpy(buf + pos, kv.first.c_str(), kv.first.size());
-      pos += kv.first.size();
-      buf[pos++] = '\n';
-      buf[pos] = 0;
-    }
-  }
-  return n;
-}
+int mc_weights_missing(const mc_engine* e, char* buf, size_t buflen) { return e ? e->weights.missing(buf, buflen) : -1; }
 
 // I2V: context_clip = img_emb(clip_fea)   (reference :264-266; upstream MLPProj: LayerNorm, Linear, GELU(erf),
 // Linear, LayerNorm).  257 tokens; rows up to img_rows are padding (finite, masked in the attention).
@@ -750,7 +559,7 @@ static mc_status embed_context(mc_engine* e, const void* context_dev, mc_dtype c
 // the cross-attention K|V of one block for a context: k = norm_k(k(ctx)), v = v(ctx)  (upstream WanT2VCrossAttention)
 static mc_status context_kv(mc_engine* e, const Layer& l, const bf16_t* ctx, bf16_t* ckv, hipStream_t s) {
   const int d = e->d;
-  mc::GemmParams q = gp(ctx, d, l.wckv, d, l.bckv, e->ctx_rows, 2 * d, d);
+  mc::GemmParams q = gp(ctx, d, l.ckv.w, d, l.ckv.b, e->ctx_rows, 2 * d, d);
   q.Cb = ckv; q.ldc = 2 * d;
   HIP_TRY(mc::launch_gemm_bf16(q, mc::EPI_BF16, s));
   HIP_TRY(mc::launch_rmsnorm_rope(ckv, 2 * d, l.cnk, e->cfg.eps, nullptr, 0, e->ctx_rows, d, s));
@@ -817,48 +626,60 @@ mc_status mc_embed(mc_engine* e, const float* latent_dev, const float* t_dev, do
   return MC_OK;
 }
 
-// LN + modulate -> q,k,v Linear -> RMSNorm(q), RMSNorm(k) -> RoPE(q,k)      (upstream WanSelfAttention)
-// fp8_linear: y = epilogue((quantise_rows(A) . Wq^T) * a_scale * w_scale + bias): per-token activation scales are
-// computed here (one pass over the bf16 rows), the weights were quantised per output channel at load time.
-// fp8_linear == 2 (wm != null): MX block scales instead -- activations per (token, 32 k), weights per (channel, 32 k),
-// multiplied inside the matrix core (gemm_mxfp8.hip).
-// A == nullptr: the producer already left the quantised rows (and their scales) in "aq" / "a_mx" / "a_scale"
-// (ln_for_gemm below) or in aq_pre / amx_pre (the GELU epilogue of the MX FFN-1 GEMM, which writes into "h").
-// mx_rows_w: rows of the block-major MX scale image `wm` points into (0 = p.N: the whole weight; a row RANGE of a fused
-// weight -- the k|v rows of w_qkv -- passes the fused weight's row count and a pointer advanced by the first row)
-static mc_status gemm_fp8_rows(mc_engine* e, const bf16_t* A, long lda, int M, int K, const uint8_t* Wq, const float* ws,
-                               const uint8_t* wm, mc::GemmParams p, int epi, hipStream_t s, uint8_t* aq_pre = nullptr,
-                               uint8_t* amx_pre = nullptr, long mx_rows_w = 0) {
-  uint8_t* aq = aq_pre ? aq_pre : e->buf<uint8_t>("aq");
-  p.A = (const bf16_t*)aq; p.lda = K; p.W = (const bf16_t*)Wq; p.ldw = K; p.K = K;
-  if (wm) {
-    uint8_t* am = amx_pre ? amx_pre : e->buf<uint8_t>("a_mx");
-    if (A) HIP_TRY(mc::launch_quantize_rows_mx(A, nullptr, lda, M, K, aq, K, am, (long)e->Lp, s));
-    p.a_mx = am; p.mx_rows_a = (long)e->Lp; p.w_mx = wm; p.mx_rows_w = mx_rows_w ? mx_rows_w : p.N;
+// ---- the one launch path of a block's Linears
+struct RowRange { int first, count; };   // output channels of a Linear: all of them, or k|v / q of the fused q|k|v
+static RowRange whole(const Linear& l) { return {0, l.n_out}; }
+
+// The activation rows [Lp, k_in] a Linear reads.  A bf16 Linear reads `rows`.  An fp8 Linear reads e4m3 rows + scales:
+// it quantises `rows` into "aq" (+ "a_scale" | "a_mx") first, unless they are `quantised` already -- there by a fused producer
+// or an earlier Linear over the same rows, or, q / mx given, in the caller's buffers (FFN-1's GELU epilogue writes FFN-2's).
+struct ActSrc {
+  const bf16_t* rows = nullptr; long ld = 0;
+  bool quantised = false;
+  uint8_t *q = nullptr, *mx = nullptr;
+};
+
+// y[:, out] = epilogue(a W[out]^T + b[out]): p carries the outputs, gates, capture and split-K operands of the epilogue; the
+// operands, the shape and every pointer advance of a row range come from `l`.
+// fp8: per-token activation scales x per-output-channel weight scales (launch_gemm_fp8), or MX block scales on both sides --
+// activations per (token, 32 k), weights per (channel, 32 k) -- multiplied inside the matrix core (launch_gemm_mxfp8).
+static mc_status linear(mc_engine* e, const Linear& l, RowRange out, ActSrc a, mc::GemmParams p, int epi, hipStream_t s) {
+  const int Lp = e->Lp, K = l.k_in;
+  p.M = Lp; p.N = out.count; p.K = K; p.bias = l.b + out.first;
+  if (!l.q) {
+    p.A = a.rows; p.lda = a.ld; p.W = l.w + (size_t)out.first * K; p.ldw = K;
+    HIP_TRY(mc::launch_gemm_bf16(p, epi, s));
+    return MC_OK;
+  }
+  uint8_t* aq = a.q ? a.q : e->buf<uint8_t>("aq");
+  p.A = (const bf16_t*)aq; p.lda = K; p.W = (const bf16_t*)(l.q + (size_t)out.first * K); p.ldw = K;
+  if (l.mx) {
+    uint8_t* am = a.mx ? a.mx : e->buf<uint8_t>("a_mx");
+    if (!a.quantised) HIP_TRY(mc::launch_quantize_rows_mx(a.rows, nullptr, a.ld, Lp, K, aq, K, am, (long)Lp, s));
+    p.a_mx = am; p.mx_rows_a = (long)Lp; p.w_mx = l.mx + out.first; p.mx_rows_w = l.n_out;   // block-major: [k / 32][n_out]
     HIP_TRY(mc::launch_gemm_mxfp8(p, epi, s));
     return MC_OK;
   }
   float* as = e->buf<float>("a_scale");
-  if (A) HIP_TRY(mc::launch_quantize_rows_fp8(A, nullptr, lda, M, K, aq, K, as, s));
-  p.a_scale = as; p.w_scale = ws;
+  if (!a.quantised) HIP_TRY(mc::launch_quantize_rows_fp8(a.rows, nullptr, a.ld, Lp, K, aq, K, as, s));
+  p.a_scale = as; p.w_scale = l.q_scale + out.first;
   HIP_TRY(mc::launch_gemm_fp8(p, epi, s));
   return MC_OK;
 }
 
-// LayerNorm + modulate whose consumer may be an fp8 GEMM: with fp8_fused_quant the row goes straight to "aq" (+ scales) and
-// *fused is set (the GEMM wrapper is then called with A == nullptr); otherwise the bf16 row goes to "xn" as ever and the
-// GEMM wrapper quantises it.
-static mc_status ln_for_gemm(mc_engine* e, bool fp8_consumer, bool mx, const float* x, const float* sc, const float* sh,
-                             int mode, const float* sc2, const float* sh2, const uint8_t* sel, hipStream_t s, bool* fused) {
+// LayerNorm + modulate of x for the Linear `l`, as that Linear's activation source: with fp8_fused_quant an fp8 Linear's row
+// goes straight to "aq" (+ scales); otherwise the bf16 row goes to "xn" as ever (and an fp8 Linear quantises it).
+static mc_status ln_for_gemm(mc_engine* e, const Linear& l, const float* x, const float* sc, const float* sh, int mode,
+                             const float* sc2, const float* sh2, const uint8_t* sel, hipStream_t s, ActSrc* a) {
   const int d = e->d, Lp = e->Lp;
-  *fused = fp8_consumer && g_fp8_fused_quant;
-  if (*fused) {
+  bf16_t* xn = e->buf<bf16_t>("xn");
+  *a = ActSrc{xn, d, l.q && mc::g_fp8_fused_quant};
+  if (a->quantised) {
     HIP_TRY(mc::launch_ln_modulate_fp8(x, d, sc, sh, mode, e->cfg.eps, e->buf<uint8_t>("aq"), d,
-                                       mx ? nullptr : e->buf<float>("a_scale"), mx ? e->buf<uint8_t>("a_mx") : nullptr,
+                                       l.mx ? nullptr : e->buf<float>("a_scale"), l.mx ? e->buf<uint8_t>("a_mx") : nullptr,
                                        (long)Lp, Lp, d, s, sc2, sh2, sel));
   } else {
-    HIP_TRY(mc::launch_ln_modulate(x, d, nullptr, 0, sc, sh, mode, e->cfg.eps, e->buf<bf16_t>("xn"), d, nullptr, 0, Lp, d,
-                                   s, sc2, sh2, sel));
+    HIP_TRY(mc::launch_ln_modulate(x, d, nullptr, 0, sc, sh, mode, e->cfg.eps, xn, d, nullptr, 0, Lp, d, s, sc2, sh2, sel));
   }
   return MC_OK;
 }
@@ -887,48 +708,31 @@ static int sp_rounds(const mc_engine* e) {               // rounds that carry at
 // the caller can start the all-gather before this rank's q exists (block_pre_q).
 static mc_status block_pre_kv(mc_engine* e, const Layer& l, const float* em, float* x, hipStream_t s) {
   const int d = e->d, Lp = e->Lp;
-  bf16_t* xn = e->buf<bf16_t>("xn");
-  bf16_t* qkv = e->buf<bf16_t>("qkv");
   const float* em2 = second_set(e, em);
-  const uint8_t* sel = tok_sel(e);
-  bool fused = false;
+  ActSrc a;
   {
     Prof pr(e, MC_PROF_LN_MODULATE, s);
-    mc_status st = ln_for_gemm(e, l.q_wqkv != nullptr, l.m_wqkv != nullptr, x, em + d, em, 0, em2 ? em2 + d : nullptr, em2,
-                               sel, s, &fused);
-    if (st != MC_OK) return st;
+    MC_TRY(ln_for_gemm(e, l.qkv, x, em + d, em, 0, em2 ? em2 + d : nullptr, em2, tok_sel(e), s, &a));
   }
+  mc::GemmParams p = {};
   if (!e->sp) {
-    mc::GemmParams p = gp(xn, d, l.wqkv, d, l.bqkv, Lp, 3 * d, d);
+    bf16_t* qkv = e->buf<bf16_t>("qkv");
     p.Cb = qkv; p.ldc = 3 * d;
     {
       Prof pr(e, MC_PROF_GEMM_QKV, s);
-      if (l.q_wqkv) {
-        mc_status st = gemm_fp8_rows(e, fused ? nullptr : xn, d, Lp, d, l.q_wqkv, l.s_wqkv, l.m_wqkv, p, mc::EPI_BF16, s);
-        if (st != MC_OK) return st;
-      } else {
-        HIP_TRY(mc::launch_gemm_bf16(p, mc::EPI_BF16, s));
-      }
+      MC_TRY(linear(e, l.qkv, whole(l.qkv), a, p, mc::EPI_BF16, s));
     }
     Prof pr(e, MC_PROF_RMSNORM_ROPE, s);
     HIP_TRY(mc::launch_rmsnorm_rope(qkv, 3 * d, l.nq, e->cfg.eps, e->cs_table, 0, Lp, d, s));
     HIP_TRY(mc::launch_rmsnorm_rope(qkv + d, 3 * d, l.nk, e->cfg.eps, e->cs_table, 0, Lp, d, s));
   } else {
-    // [k|v] -> "kv_local" (ld 2d): the rows every other rank needs, first
+    // [k|v] -> "kv_local" (ld 2d): the rows every other rank needs, first.  An fp8 Linear quantises the activation rows once
+    // ("aq": the fused LayerNorm, or this launch) and block_pre_q reuses them
     bf16_t* kvl = e->buf<bf16_t>("kv_local");
+    p.Cb = kvl; p.ldc = 2 * d;
     {
       Prof pr(e, MC_PROF_GEMM_QKV, s);
-      mc::GemmParams q = gp(xn, d, l.wqkv + (size_t)d * d, d, l.bqkv + d, Lp, 2 * d, d);
-      q.Cb = kvl; q.ldc = 2 * d;
-      if (l.q_wqkv) {
-        // fp8 Linear modes: rows [d, 3d) of the fused e4m3 weight (+ their per-row / MX scales); the activation rows are
-        // quantised once ("aq": by the fused LayerNorm, or here) and block_pre_q reuses them
-        mc_status st = gemm_fp8_rows(e, fused ? nullptr : xn, d, Lp, d, l.q_wqkv + (size_t)d * d, l.s_wqkv ? l.s_wqkv + d : nullptr,
-                                     l.m_wqkv ? l.m_wqkv + d : nullptr, q, mc::EPI_BF16, s, nullptr, nullptr, 3 * d);
-        if (st != MC_OK) return st;
-      } else {
-        HIP_TRY(mc::launch_gemm_bf16(q, mc::EPI_BF16, s));
-      }
+      MC_TRY(linear(e, l.qkv, RowRange{d, 2 * d}, a, p, mc::EPI_BF16, s));
     }
     Prof pr(e, MC_PROF_RMSNORM_ROPE, s);
     HIP_TRY(mc::launch_rmsnorm_rope(kvl, 2 * d, l.nk, e->cfg.eps, e->cs_table, 0, Lp, d, s));
@@ -937,23 +741,17 @@ static mc_status block_pre_kv(mc_engine* e, const Layer& l, const float* em, flo
   return MC_OK;
 }
 
-// sequence parallel only: q Linear of the rows block_pre_kv normalised ("xn") -> "qkv"[:, :d] (ld d), q norm / RoPE; runs
-// beside the all-gather the caller started in between
+// sequence parallel only: q Linear of the rows block_pre_kv normalised ("xn", or quantised in "aq") -> "qkv"[:, :d] (ld d),
+// q norm / RoPE; runs beside the all-gather the caller started in between
 static mc_status block_pre_q(mc_engine* e, const Layer& l, hipStream_t s) {
   const int d = e->d, Lp = e->Lp;
   if (!e->sp) return MC_OK;
-  bf16_t* xn = e->buf<bf16_t>("xn");
   bf16_t* qkv = e->buf<bf16_t>("qkv");
   {
     Prof pr(e, MC_PROF_GEMM_QKV, s);
-    mc::GemmParams p = gp(xn, d, l.wqkv, d, l.bqkv, Lp, d, d);
+    mc::GemmParams p = {};
     p.Cb = qkv; p.ldc = d;
-    if (l.q_wqkv) {    // rows [0, d) of the fused weight on the activation rows block_pre_kv left quantised in "aq"
-      mc_status st = gemm_fp8_rows(e, nullptr, d, Lp, d, l.q_wqkv, l.s_wqkv, l.m_wqkv, p, mc::EPI_BF16, s, nullptr, nullptr, 3 * d);
-      if (st != MC_OK) return st;
-    } else {
-      HIP_TRY(mc::launch_gemm_bf16(p, mc::EPI_BF16, s));
-    }
+    MC_TRY(linear(e, l.qkv, RowRange{0, d}, ActSrc{e->buf<bf16_t>("xn"), d, true}, p, mc::EPI_BF16, s));
   }
   Prof pr(e, MC_PROF_RMSNORM_ROPE, s);
   HIP_TRY(mc::launch_rmsnorm_rope(qkv, d, l.nq, e->cfg.eps, e->cs_table, 0, Lp, d, s));
@@ -1116,7 +914,7 @@ mc_status mc_sp_geometry(const mc_engine* e, int* num_layers, int* seq_len, int*
   return MC_OK;
 }
 
-void* mc_workspace_base(const mc_engine* e) { return e ? (void*)e->ws : nullptr; }
+void* mc_workspace_base(const mc_engine* e) { return e ? (void*)e->work.ws : nullptr; }
 
 // geometry of round `round` (NULL outputs are skipped): rows per shard chunk, valid keys at the start of each, and the
 // number of rounds that carry valid keys (later rounds hold padding only: neither gathered nor attended)
@@ -1135,7 +933,6 @@ mc_status mc_sp_round_info(const mc_engine* e, int round, int* n_rounds, int* ch
 static mc_status block_post(mc_engine* e, const Layer& l, const float* em, float* x, int layer, bool capture, int branch,
                             mc_mode mode, hipStream_t s) {
   const int d = e->d, Lp = e->Lp, ffn = e->ffn;
-  bf16_t* xn = e->buf<bf16_t>("xn");
   bf16_t* qkv = e->buf<bf16_t>("qkv");
   bf16_t* ao = e->buf<bf16_t>("ao");
   const float scale = 1.0f / std::sqrt(128.0f);
@@ -1164,36 +961,25 @@ static mc_status block_post(mc_engine* e, const Layer& l, const float* em, float
   }
   {  // x = x + o(attn) * e[2]
     Prof pr(e, MC_PROF_GEMM_O, s);
-    mc::GemmParams p = gp(ao, d, l.wo, d, l.bo, Lp, d, d);
+    mc::GemmParams p = {};
     p.X = x; p.ldx = d; p.gate = em + 2 * d;
     if (em2) { p.gate2 = em2 + 2 * d; p.gate_sel = sel; }
-    if (l.q_wo) {
-      mc_status st = gemm_fp8_rows(e, ao, d, Lp, d, l.q_wo, nullptr, l.m_wo, p, mc::EPI_RESID_GATE, s);
-      if (st != MC_OK) return st;
-    } else {
-      HIP_TRY(mc::launch_gemm_bf16(p, mc::EPI_RESID_GATE, s));
-    }
+    MC_TRY(linear(e, l.o, whole(l.o), ActSrc{ao, d}, p, mc::EPI_RESID_GATE, s));
   }
   // ---- cross attention: x = x + o(attn(norm_q(q(norm3(x))), norm_k(k(ctx)), v(ctx)))
-  bool fused_cq = false;
+  ActSrc xn;   // LayerNorm output: the activation rows of cross-attention Q, then of FFN-1
   {
     Prof pr(e, MC_PROF_LN_MODULATE, s);
-    mc_status st = ln_for_gemm(e, l.q_wcq != nullptr, true, x, l.n3w, l.n3b, 1, nullptr, nullptr, nullptr, s, &fused_cq);
-    if (st != MC_OK) return st;
+    MC_TRY(ln_for_gemm(e, l.cq, x, l.n3w, l.n3b, 1, nullptr, nullptr, nullptr, s, &xn));
   }
   bf16_t* cq = qkv;  // the self-attention q/k/v are dead now
   bf16_t* ckv = e->buf<bf16_t>("ckv");
   {
-    mc::GemmParams p = gp(xn, d, l.wcq, d, l.bcq, Lp, d, d);
+    mc::GemmParams p = {};
     p.Cb = cq; p.ldc = d;
     {
       Prof pr(e, MC_PROF_GEMM_CROSS_Q, s);
-      if (l.q_wcq) {
-        mc_status st = gemm_fp8_rows(e, fused_cq ? nullptr : xn, d, Lp, d, l.q_wcq, nullptr, l.m_wcq, p, mc::EPI_BF16, s);
-        if (st != MC_OK) return st;
-      } else {
-        HIP_TRY(mc::launch_gemm_bf16(p, mc::EPI_BF16, s));
-      }
+      MC_TRY(linear(e, l.cq, whole(l.cq), xn, p, mc::EPI_BF16, s));
     }
     {
       Prof pr(e, MC_PROF_RMSNORM_ROPE, s);
@@ -1222,7 +1008,7 @@ static mc_status block_post(mc_engine* e, const Layer& l, const float* em, float
       // I2V (upstream WanI2VCrossAttention): + attention over the 257 CLIP image tokens with their own k/v
       bf16_t* ckvi = e->buf<bf16_t>("ckv_img");
       bf16_t* ao2 = e->buf<bf16_t>("ao2");
-      mc::GemmParams qi = gp(e->buf<bf16_t>("ctx_img"), d, l.wckv_img, d, l.bckv_img, e->img_rows, 2 * d, d);
+      mc::GemmParams qi = gp(e->buf<bf16_t>("ctx_img"), d, l.ckv_img.w, d, l.ckv_img.b, e->img_rows, 2 * d, d);
       qi.Cb = ckvi; qi.ldc = 2 * d;
       HIP_TRY(mc::launch_gemm_bf16(qi, mc::EPI_BF16, s));
       HIP_TRY(mc::launch_rmsnorm_rope(ckvi, 2 * d, l.cnk_img, e->cfg.eps, nullptr, 0, e->img_rows, d, s));
@@ -1233,54 +1019,39 @@ static mc_status block_post(mc_engine* e, const Layer& l, const float* em, float
       HIP_TRY(mc::launch_add_bf16(ao, ao2, (size_t)Lp * d, s));
     }
     Prof pr(e, MC_PROF_GEMM_CROSS_O, s);
-    mc::GemmParams o = gp(ao, d, l.wco, d, l.bco, Lp, d, d);
+    mc::GemmParams o = {};
     o.X = x; o.ldx = d; o.gate = nullptr;
-    if (l.q_wco) {
-      mc_status st = gemm_fp8_rows(e, ao, d, Lp, d, l.q_wco, nullptr, l.m_wco, o, mc::EPI_RESID_GATE, s);
-      if (st != MC_OK) return st;
-    } else {
-      HIP_TRY(mc::launch_gemm_bf16(o, mc::EPI_RESID_GATE, s));
-    }
+    MC_TRY(linear(e, l.co, whole(l.co), ActSrc{ao, d}, o, mc::EPI_RESID_GATE, s));
   }
   // ---- FFN: x = x + ffn(LN(x)*(1+e[4])+e[3]) * e[5]
-  bool fused_ffn = false;
   {
     Prof pr(e, MC_PROF_LN_MODULATE, s);
-    mc_status st = ln_for_gemm(e, l.q_w1 != nullptr, l.m_w1 != nullptr, x, em + 4 * d, em + 3 * d, 0,
-                               em2 ? em2 + 4 * d : nullptr, em2 ? em2 + 3 * d : nullptr, sel, s, &fused_ffn);
-    if (st != MC_OK) return st;
+    MC_TRY(ln_for_gemm(e, l.ffn1, x, em + 4 * d, em + 3 * d, 0, em2 ? em2 + 4 * d : nullptr, em2 ? em2 + 3 * d : nullptr, sel,
+                       s, &xn));
   }
   bf16_t* h = e->buf<bf16_t>("h");
   {
-    mc::GemmParams p = gp(xn, d, l.w1, d, l.b1, Lp, ffn, d);
+    mc::GemmParams p = {};
     p.Cb = h; p.ldc = ffn;
     // MX with fused quantisers: FFN-1's GELU epilogue writes the e4m3 rows + block scales FFN-2 reads (both inside "h":
     // Lp * ffn bytes, then ffn / 32 * Lp scale bytes), the bf16 hidden tensor never exists
-    const bool h_fp8 = l.m_w1 && l.m_w2 && g_fp8_fused_quant;
-    uint8_t* hq = (uint8_t*)h;
-    uint8_t* hmx = hq + (size_t)Lp * ffn;
+    const bool h_fp8 = l.ffn1.mx && l.ffn2.mx && mc::g_fp8_fused_quant;
+    ActSrc hidden{h, ffn};
+    if (h_fp8) {
+      hidden.quantised = true; hidden.q = (uint8_t*)h; hidden.mx = hidden.q + (size_t)Lp * ffn;
+      p.Cq = hidden.q; p.ldcq = ffn; p.c_mx = hidden.mx; p.mx_rows_c = Lp;
+    }
     {
       Prof pr(e, MC_PROF_GEMM_FFN1, s);
-      if (l.q_w1) {
-        if (h_fp8) { p.Cq = hq; p.ldcq = ffn; p.c_mx = hmx; p.mx_rows_c = Lp; }
-        mc_status st = gemm_fp8_rows(e, fused_ffn ? nullptr : xn, d, Lp, d, l.q_w1, l.s_w1, l.m_w1, p,
-                                     h_fp8 ? mc::EPI_GELU_MXFP8 : mc::EPI_GELU_BF16, s);
-        if (st != MC_OK) return st;
-      } else {
-        HIP_TRY(mc::launch_gemm_bf16(p, mc::EPI_GELU_BF16, s));
-      }
+      MC_TRY(linear(e, l.ffn1, whole(l.ffn1), xn, p, h_fp8 ? mc::EPI_GELU_MXFP8 : mc::EPI_GELU_BF16, s));
     }
-    mc::GemmParams q = gp(h, ffn, l.w2, ffn, l.b2, Lp, d, ffn);
+    mc::GemmParams q = {};
     q.X = x; q.ldx = d; q.gate = em + 5 * d;
     if (e->splitk_bytes) { q.splitk_ws = e->buf<float>("splitk"); q.splitk_ws_bytes = e->splitk_bytes; }
     if (em2) { q.gate2 = em2 + 5 * d; q.gate_sel = sel; }
-    const bool f8 = l.q_w2 != nullptr;
     auto ffn2 = [&](int epi) -> mc_status {
       Prof pr(e, MC_PROF_GEMM_FFN2, s);
-      if (f8 && h_fp8) return gemm_fp8_rows(e, nullptr, ffn, Lp, ffn, l.q_w2, l.s_w2, l.m_w2, q, epi, s, hq, hmx);
-      if (f8) return gemm_fp8_rows(e, h, ffn, Lp, ffn, l.q_w2, l.s_w2, l.m_w2, q, epi, s);
-      HIP_TRY(mc::launch_gemm_bf16(q, epi, s));
-      return MC_OK;
+      return linear(e, l.ffn2, whole(l.ffn2), hidden, q, epi, s);
     };
     if (capture) {
       // MagCache residual capture fused into the last epilogue: residual = x_out - ori_x  (:299-301)
@@ -1428,7 +1199,7 @@ mc_status mc_blocks_sp(mc_engine* e, int layer_begin, int layer_end, int branch,
   const long wg = (long)(e->Lp / 256) * e->H, waves = (wg + g_n_cu - 1) / g_n_cu;
   const bool underfilled = wg * 10 < waves * g_n_cu * 9;               // < 90 % of the CU slots it occupies (sp 4 / 8 at 1.3B: 75 %;
                                                                        // 14B at sp 8: 1480 workgroups = 96 %: the merge would only cost)
-  const bool partials = (g_sp_attn_partials == 2 || (g_sp_attn_partials == 1 && underfilled)) && e->P > 1 && 1 + R <= kSpMaxParts;
+  const bool partials = (mc::g_sp_attn_partials == 2 || (mc::g_sp_attn_partials == 1 && underfilled)) && e->P > 1 && 1 + R <= kSpMaxParts;
   if (partials)
     if (mc_status st = sp_side_stream(e); st != MC_OK) return st;
   // one attention chain: starts, [waits], q, local shard, ([wait] round) x R
@@ -1585,7 +1356,7 @@ mc_status mc_calib_ready(const mc_engine* e, int branch, int* has_stats) {
 }
 
 mc_status mc_calib_finalize(mc_engine* e, int branch, mc_stream stream) {
-  if (!e || !e->ws) return fail(MC_ESTATE, "no workspace");
+  if (!e || !e->work.ws) return fail(MC_ESTATE, "no workspace");
   if (branch < 0 || branch > 1) return fail(MC_EINVAL, "branch %d out of range", branch);
   HIP_TRY(mc::launch_calib_finalize(e->buf<double>("calib_sums"), e->buf<float>("calib_stats") + 3 * branch,
                                     (hipStream_t)stream));
@@ -1593,7 +1364,7 @@ mc_status mc_calib_finalize(mc_engine* e, int branch, mc_stream stream) {
 }
 
 mc_status mc_import_residual(mc_engine* e, int branch, const float* src_dev, mc_stream stream) {
-  if (!e || !e->ws || !src_dev) return fail(MC_EINVAL, "null argument / no workspace");
+  if (!e || !e->work.ws || !src_dev) return fail(MC_EINVAL, "null argument / no workspace");
   if (branch < 0 || branch >= e->cfg.n_branches) return fail(MC_EINVAL, "branch %d out of range", branch);
   float* dst = e->residual(e->res_slot[branch]);
   if (dst != src_dev)
@@ -1689,304 +1460,6 @@ mc_status mc_state_reset(mc_engine* e) {
   if (!e) return fail(MC_EINVAL, "null engine");
   e->have_res[0] = e->have_res[1] = false;
   e->have_stats[0] = e->have_stats[1] = false;
-  return MC_OK;
-}
-
-// ------------------------------------------------------------------------------------------------ ops
-// split-K scratch of the single-op entry point (mc_op_set_splitk_workspace): the engines carry their own in their workspace
-static float* g_op_splitk_ws = nullptr;
-static size_t g_op_splitk_bytes = 0;
-
-mc_status mc_op_gemm_bf16(const void* A, long lda, const void* W, long ldw, const float* bias, int M, int N, int K,
-                          int epi, void* Cb, long ldc, float* X, long ldx, const float* gate, const void* X0,
-                          long ldx0, float* R, long ldr, void* X0out, long ldx0out, int m_valid, mc_stream s) {
-  mc::GemmParams p = gp((const bf16_t*)A, lda, (const bf16_t*)W, ldw, bias, M, N, K);
-  p.Cb = (bf16_t*)Cb; p.ldc = ldc; p.X = X; p.ldx = ldx; p.gate = gate;
-  p.X0 = (const bf16_t*)X0; p.ldx0 = ldx0; p.R = R; p.ldr = ldr;
-  p.X0out = (bf16_t*)X0out; p.ldx0out = ldx0out; p.m_valid = m_valid;
-  p.splitk_ws = g_op_splitk_ws; p.splitk_ws_bytes = g_op_splitk_bytes;
-  hipError_t err = mc::launch_gemm_bf16(p, epi, (hipStream_t)s);
-  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "gemm: unsupported shape M=%d N=%d K=%d epi=%d", M, N, K, epi);
-  HIP_TRY(err);
-  return MC_OK;
-}
-
-mc_status mc_op_gemm_bf16_resid_sel(const void* A, long lda, const void* W, long ldw, const float* bias, int M, int N, int K,
-                                    int capture, float* X, long ldx, const float* gate, const float* gate2,
-                                    const unsigned char* gate_sel, const void* X0, long ldx0, float* R, long ldr, mc_stream s) {
-  mc::GemmParams p = gp((const bf16_t*)A, lda, (const bf16_t*)W, ldw, bias, M, N, K);
-  p.X = X; p.ldx = ldx; p.gate = gate; p.gate2 = gate2; p.gate_sel = gate_sel;
-  p.X0 = (const bf16_t*)X0; p.ldx0 = ldx0; p.R = R; p.ldr = ldr;
-  if (!gate || !gate2 || !gate_sel) return fail(MC_EINVAL, "gemm (per-token gates): gate, gate2 and gate_sel are required");
-  hipError_t err = mc::launch_gemm_bf16(p, capture ? mc::EPI_RESID_CAPTURE : mc::EPI_RESID_GATE, (hipStream_t)s);
-  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "gemm (per-token gates): unsupported shape M=%d N=%d K=%d", M, N, K);
-  HIP_TRY(err);
-  return MC_OK;
-}
-
-mc_status mc_op_gemm_bf16_rowsplit(const void* A, long lda, const void* W, const void* W_b, long ldw, const float* bias,
-                                   const float* bias_b, int M, int N, int K, int m_split, int epi, void* Cb, long ldc, float* X,
-                                   long ldx, const float* gate, const float* gate_b, mc_stream s) {
-  mc::GemmParams p = gp((const bf16_t*)A, lda, (const bf16_t*)W, ldw, bias, M, N, K);
-  p.Cb = (bf16_t*)Cb; p.ldc = ldc; p.X = X; p.ldx = ldx; p.gate = gate;
-  p.m_split = m_split; p.W_b = (const bf16_t*)W_b; p.bias_b = bias_b; p.gate_b = gate_b;
-  p.splitk_ws = g_op_splitk_ws; p.splitk_ws_bytes = g_op_splitk_bytes;
-  if (epi != mc::EPI_BF16 && epi != mc::EPI_GELU_BF16 && epi != mc::EPI_RESID_GATE)
-    return fail(MC_EINVAL, "gemm (row split): epi %d (0 bf16, 1 gelu, 2 gated residual)", epi);
-  hipError_t err = mc::launch_gemm_bf16(p, epi, (hipStream_t)s);
-  if (err == hipErrorInvalidValue)
-    return fail(MC_EINVAL, "gemm (row split): unsupported shape M=%d N=%d K=%d m_split=%d epi=%d", M, N, K, m_split, epi);
-  HIP_TRY(err);
-  return MC_OK;
-}
-
-mc_status mc_op_gemm_bf16_gelu_split(const void* A, long lda, const void* W, long ldw, const float* bias, int M, int N, int K,
-                                     int n_split, void* Cb, long ldc, void* Cb2, long ldc2, mc_stream s) {
-  mc::GemmParams p = gp((const bf16_t*)A, lda, (const bf16_t*)W, ldw, bias, M, N, K);
-  p.Cb = (bf16_t*)Cb; p.ldc = ldc; p.n_split = n_split; p.Cb2 = (bf16_t*)Cb2; p.ldc2 = ldc2;
-  hipError_t err = mc::launch_gemm_bf16(p, mc::EPI_BF16_GELU_SPLIT, (hipStream_t)s);
-  if (err == hipErrorInvalidValue)
-    return fail(MC_EINVAL, "gemm (bf16 | gelu split): unsupported shape M=%d N=%d K=%d n_split=%d", M, N, K, n_split);
-  HIP_TRY(err);
-  return MC_OK;
-}
-
-int mc_op_gemm_bf16_kernel(int M, int N, int K, int epi) {
-  mc::GemmParams p = gp(nullptr, K, nullptr, K, nullptr, M, N, K);
-  p.ldc = N; p.ldx = N;
-  if (M <= 0 || N <= 0 || K <= 0 || (K % 64) != 0 || (N % 4) != 0) return 0;
-  // the operands an epilogue form needs, as the engines pass them (never dereferenced here): the dispatch asks whether
-  // gemm_bf16_v2 can run THIS form (gemm_bf16_v2_epi_ok), not only the shape
-  static char dummy[16];
-  if (epi == mc::EPI_RESID_CAPTURE) { p.X0 = (const bf16_t*)dummy; p.ldx0 = N; p.R = (float*)dummy; p.ldr = N; }
-  if (epi == mc::EPI_BF16_GELU_SPLIT) { p.n_split = N > 256 ? (N / 2) / 256 * 256 : 0; p.Cb2 = (bf16_t*)dummy; p.ldc2 = N; }
-  return mc::gemm_bf16_kernel_for(p, epi);
-}
-
-int mc_op_gemm_bf16_splitk(int M, int N, int K, int epi) {
-  mc::GemmParams p = gp(nullptr, K, nullptr, K, nullptr, M, N, K);
-  p.ldc = N; p.ldx = N;
-  p.splitk_ws = g_op_splitk_ws; p.splitk_ws_bytes = g_op_splitk_bytes;
-  if (M <= 0 || N <= 0 || K <= 0 || (mc::g_gemm_kernel != 0 && mc::g_gemm_kernel != 4)) return 1;
-  return mc::gemm_splitk_slices(p, epi);
-}
-
-size_t mc_op_gemm_splitk_need(int M, int N, int K, int epi) { return mc::gemm_splitk_ws_need(M, N, K, epi); }
-
-mc_status mc_op_set_splitk_workspace(void* ws_dev, size_t bytes) {
-  g_op_splitk_ws = (float*)ws_dev;
-  g_op_splitk_bytes = ws_dev ? bytes : 0;
-  return MC_OK;
-}
-
-mc_status mc_op_attention(const void* Q, long ldq, const void* K, long ldk, long kss, const void* V, long ldv,
-                          long vss, void* O, long ldo, int Lq_pad, int n_heads, int shard_rows, int shard_valid,
-                          int n_shards, float scale, mc_stream s) {
-  mc::AttnParams a;
-  memset(&a, 0, sizeof(a));
-  a.Q = (const bf16_t*)Q; a.ldq = ldq; a.K = (const bf16_t*)K; a.ldk = ldk; a.k_shard_stride = kss;
-  a.V = (const bf16_t*)V; a.ldv = ldv; a.v_shard_stride = vss; a.O = (bf16_t*)O; a.ldo = ldo;
-  a.Lq_pad = Lq_pad; a.n_heads = n_heads; a.shard_rows = shard_rows; a.shard_valid = shard_valid;
-  a.n_shards = n_shards; a.scale = scale;
-  hipError_t err = mc::launch_attention(a, (hipStream_t)s);
-  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "attention: unsupported shape");
-  HIP_TRY(err);
-  return MC_OK;
-}
-
-mc_status mc_op_quantize_rows_fp8(const void* x, mc_dtype dtype, long ldx, int M, int K, void* q, long ldq, float* scale,
-                                  mc_stream s) {
-  hipError_t err = mc::launch_quantize_rows_fp8(dtype == MC_BF16 ? (const bf16_t*)x : nullptr,
-                                                dtype == MC_F32 ? (const float*)x : nullptr, ldx, M, K, (uint8_t*)q, ldq,
-                                                scale, (hipStream_t)s);
-  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "quantize_rows_fp8: K, ldx, ldq must be multiples of 4");
-  HIP_TRY(err);
-  return MC_OK;
-}
-
-mc_status mc_op_gemm_fp8(const void* A, long lda, const float* a_scale, const void* W, long ldw, const float* w_scale,
-                         const float* bias, int M, int N, int K, int epi, void* Cb, long ldc, float* X, long ldx,
-                         const float* gate, mc_stream s) {
-  mc::GemmParams p = gp((const bf16_t*)A, lda, (const bf16_t*)W, ldw, bias, M, N, K);
-  p.a_scale = a_scale; p.w_scale = w_scale;
-  p.Cb = (bf16_t*)Cb; p.ldc = ldc; p.X = X; p.ldx = ldx; p.gate = gate;
-  hipError_t err = mc::launch_gemm_fp8(p, epi, (hipStream_t)s);
-  if (err == hipErrorInvalidValue)
-    return fail(MC_EINVAL, "gemm_fp8: needs N %% 256 == 0, K %% 256 == 0, K >= 512, lda/ldw %% 16 == 0, both scale vectors");
-  HIP_TRY(err);
-  return MC_OK;
-}
-
-mc_status mc_op_quantize_rows_mx(const void* x, mc_dtype dtype, long ldx, int M, int K, void* q, long ldq, void* scales,
-                                 long rows_pad, mc_stream s) {
-  hipError_t err = mc::launch_quantize_rows_mx(dtype == MC_BF16 ? (const bf16_t*)x : nullptr,
-                                               dtype == MC_F32 ? (const float*)x : nullptr, ldx, M, K, (uint8_t*)q, ldq,
-                                               (uint8_t*)scales, rows_pad, (hipStream_t)s);
-  if (err == hipErrorInvalidValue)
-    return fail(MC_EINVAL, "quantize_rows_mx: K %% 32 == 0, ldx %% 8 == 0, ldq %% 16 == 0, rows_pad >= M");
-  HIP_TRY(err);
-  return MC_OK;
-}
-
-mc_status mc_op_gemm_mxfp8(const void* A, long lda, const void* a_scales, long rows_pad_a, const void* W, long ldw,
-                           const void* w_scales, long rows_pad_w, const float* bias, int M, int N, int K, int epi, void* Cb,
-                           long ldc, float* X, long ldx, const float* gate, mc_stream s) {
-  mc::GemmParams p = gp((const bf16_t*)A, lda, (const bf16_t*)W, ldw, bias, M, N, K);
-  p.a_mx = (const uint8_t*)a_scales; p.mx_rows_a = rows_pad_a; p.w_mx = (const uint8_t*)w_scales; p.mx_rows_w = rows_pad_w;
-  p.Cb = (bf16_t*)Cb; p.ldc = ldc; p.X = X; p.ldx = ldx; p.gate = gate;
-  hipError_t err = mc::launch_gemm_mxfp8(p, epi, (hipStream_t)s);
-  if (err == hipErrorInvalidValue)
-    return fail(MC_EINVAL, "gemm_mxfp8: needs N %% 256 == 0, K %% 256 == 0, K >= 512, lda/ldw %% 16 == 0, block scales with "
-                           "rows_pad_a >= M rounded up to 256, rows_pad_w >= N, both multiples of 4");
-  HIP_TRY(err);
-  return MC_OK;
-}
-
-mc_status mc_op_attention_partial(const void* Q, long ldq, const void* K, long ldk, long kss, const void* V, long ldv,
-                                  long vss, void* O, long ldo, int Lq_pad, int n_heads, int shard_rows,
-                                  int shard_valid, int n_shards, float scale, int skip_shard, float* lse_out,
-                                  const float* lse_in, mc_stream s) {
-  mc::AttnParams a;
-  memset(&a, 0, sizeof(a));
-  a.Q = (const bf16_t*)Q; a.ldq = ldq; a.K = (const bf16_t*)K; a.ldk = ldk; a.k_shard_stride = kss;
-  a.V = (const bf16_t*)V; a.ldv = ldv; a.v_shard_stride = vss; a.O = (bf16_t*)O; a.ldo = ldo;
-  a.Lq_pad = Lq_pad; a.n_heads = n_heads; a.shard_rows = shard_rows; a.shard_valid = shard_valid;
-  a.n_shards = n_shards; a.scale = scale;
-  a.skip_shard_p1 = skip_shard >= 0 ? skip_shard + 1 : 0; a.lse_out = lse_out; a.lse_in = lse_in;
-  hipError_t err = mc::launch_attention(a, (hipStream_t)s);
-  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "attention: unsupported shape / shard selection");
-  HIP_TRY(err);
-  return MC_OK;
-}
-
-mc_status mc_op_attn_merge(const void* const* o_parts, const float* const* lse_parts, int n, void* out, long ldo, int rows,
-                           int rows_pad, int d, mc_stream s) {
-  if (!o_parts || !lse_parts || !out) return fail(MC_EINVAL, "attn_merge: null argument");
-  hipError_t err = mc::launch_attn_merge((const bf16_t* const*)o_parts, lse_parts, n, (bf16_t*)out, ldo, rows, rows_pad, d,
-                                         (hipStream_t)s);
-  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "attn_merge: 1..9 parts, d a multiple of 128, 16-byte rows");
-  HIP_TRY(err);
-  return MC_OK;
-}
-
-mc_status mc_op_ln_modulate(const float* x, long ldx, const void* x0, long ldx0, const float* sc, const float* sh,
-                            int mode, float eps, void* out, long ldo, float* out_f32, long ldof, int M, int D,
-                            mc_stream s) {
-  hipError_t err = mc::launch_ln_modulate(x, ldx, (const bf16_t*)x0, ldx0, sc, sh, mode, eps, (bf16_t*)out, ldo,
-                                          out_f32, ldof, M, D, (hipStream_t)s);
-  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "ln_modulate: unsupported D=%d", D);
-  HIP_TRY(err);
-  return MC_OK;
-}
-
-mc_status mc_op_rmsnorm_rope(void* x, long ldx, const float* w, float eps, const float* cs, int cs_row0, int M, int D,
-                             mc_stream s) {
-  hipError_t err = mc::launch_rmsnorm_rope((bf16_t*)x, ldx, w, eps, cs, cs_row0, M, D, (hipStream_t)s);
-  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "rmsnorm_rope: unsupported D=%d", D);
-  HIP_TRY(err);
-  return MC_OK;
-}
-
-mc_status mc_op_skip_add(const void* x0, long ldx0, const float* r, long ldr, float* out, long ldo, int M, int D,
-                         mc_stream s) {
-  hipError_t err = mc::launch_skip_add((const bf16_t*)x0, ldx0, r, ldr, out, ldo, M, D, (hipStream_t)s);
-  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "skip_add: unsupported shape");
-  HIP_TRY(err);
-  return MC_OK;
-}
-
-mc_status mc_op_residual_sub(const float* x, long ldx, const void* x0, long ldx0, float* r, long ldr, int M, int D,
-                             mc_stream s) {
-  hipError_t err = mc::launch_residual_sub(x, ldx, (const bf16_t*)x0, ldx0, r, ldr, M, D, (hipStream_t)s);
-  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "residual_sub: unsupported shape");
-  HIP_TRY(err);
-  return MC_OK;
-}
-
-mc_status mc_op_calib_stats(const float* r, long ldr, const float* rp, long ldrp, int M, int D, double* partial,
-                            int n_blocks, double* sums, float* stats, mc_stream s) {
-  hipError_t err = mc::launch_calib_stats(r, ldr, rp, ldrp, M, D, partial, n_blocks, sums, stats, (hipStream_t)s);
-  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "calib_stats: unsupported shape");
-  HIP_TRY(err);
-  return MC_OK;
-}
-
-mc_status mc_op_cfg_euler(const float* cond, const float* uncond, float guide, float dt, float* x, float* eps_out,
-                          size_t n, mc_stream s) {
-  HIP_TRY(mc::launch_cfg_euler(cond, uncond, guide, dt, x, eps_out, n, (hipStream_t)s));
-  return MC_OK;
-}
-
-mc_status mc_op_cfg_norm_euler(const float* cond, const float* uncond, long ld_pred, float guide, float dt, float* x, long ldx,
-                               int n_rows, int C, mc_stream s) {
-  if (!cond || !uncond || !x) return fail(MC_EINVAL, "null argument");
-  hipError_t err = mc::launch_cfg_norm_euler(cond, uncond, ld_pred, guide, dt, x, ldx, n_rows, C, (hipStream_t)s);
-  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "cfg_norm_euler: 0 < C <= 256, ld_pred / ldx >= C, n_rows >= 0");
-  HIP_TRY(err);
-  return MC_OK;
-}
-
-mc_status mc_op_rmsnorm_rows_bf16(const float* x, long ldx, const float* w, float eps, void* out, long ldo, int rows_valid,
-                                  int rows, int D, mc_stream s) {
-  if (!x || !w || !out) return fail(MC_EINVAL, "null argument");
-  hipError_t err = mc::launch_rmsnorm_rows_bf16(x, ldx, w, eps, (bf16_t*)out, ldo, rows_valid, rows, D, (hipStream_t)s);
-  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "rmsnorm_rows_bf16: D, ldx, ldo multiples of 4, 0 <= rows_valid <= rows");
-  HIP_TRY(err);
-  return MC_OK;
-}
-
-mc_status mc_op_lincomb(const float* const* xs_dev, const float* coef, int k, float* out_dev, size_t n, mc_stream s) {
-  if (!xs_dev || !coef) return fail(MC_EINVAL, "null argument");
-  hipError_t err = mc::launch_lincomb(xs_dev, coef, k, out_dev, n, (hipStream_t)s);
-  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "lincomb: 1..6 operands, non-empty output");
-  HIP_TRY(err);
-  return MC_OK;
-}
-
-mc_status mc_op_cast_bf16(const float* src, void* dst, size_t n, mc_stream s) {
-  HIP_TRY(mc::launch_cast_bf16(src, (bf16_t*)dst, n, (hipStream_t)s));
-  return MC_OK;
-}
-
-mc_status mc_set_option(const char* key, int value) {
-  if (!key) return fail(MC_EINVAL, "null key");
-  const std::string k(key);
-  if (k == "gemm_kernel") {
-    if ((value < 0 || value > 2) && value != 4)
-      return fail(MC_EINVAL, "gemm_kernel must be 0 (by shape), 1 (128x128), 2 (256x256, 8 waves) or 4 (256x256, 4 waves, generated stream)");
-#ifndef MC_WITH_REF_GEMM
-    if (value == 2)
-      return fail(MC_EINVAL, "gemm_kernel 2: the 8-wave reference kernel is not in this library (round 6: it lives in the "
-                             "test-only libmagcache_hip_ref.so, magcache_amd.build.build_ref())");
-#endif
-    mc::g_gemm_kernel = value;
-  } else if (k == "sp_attn_partials") {
-    if (value < 0 || value > 2)
-      return fail(MC_EINVAL, "sp_attn_partials must be 0 (chain on one stream), 1 (independent launches on two streams + merge where a launch "
-                             "does not fill the chip in whole waves) or 2 (always)");
-    g_sp_attn_partials = value;
-  } else if (k == "gemm_splitk") {
-    if (value < 0 || value > 16) return fail(MC_EINVAL, "gemm_splitk must be 0 (never), 1 (by shape) or 2..16 (that many K slices wherever valid)");
-    mc::g_gemm_splitk = value;
-  } else if (k == "gemm_v2_max_grid") {
-    if (value < 0 || value > 4096) return fail(MC_EINVAL, "gemm_v2_max_grid must be 0 (= the CUs) or a workgroup count");
-    mc::g_gemm_v2_max_grid = value;
-  } else if (k == "gemm_defer") {
-    if (value != 0 && value != 1) return fail(MC_EINVAL, "gemm_defer must be 0 (residual epilogues in place) or 1 (deferred into the next tile's main loop)");
-    mc::g_gemm_defer = value;
-  } else if (k == "fp8_fused_quant") {
-    if (value != 0 && value != 1) return fail(MC_EINVAL, "fp8_fused_quant must be 0 (separate quantise passes) or 1 (fused into the producers)");
-    g_fp8_fused_quant = value;
-  } else if (k == "attn_kernel") {
-    if (value != 0 && value != 3 && value != 5)
-      return fail(MC_EINVAL, "attn_kernel must be 0 (default), 3 (8 waves x 32 rows) or 5 (4 waves x 64 rows, hand-scheduled)");
-    mc::g_attn_kernel = value;
-  } else if (k == "mmdit_two_streams") {
-    if (value < -1 || value > 6) return fail(MC_EINVAL, "mmdit_two_streams must be -1 (by shape), 0, 1 or a diagnostic mode 2..6");
-    g_mmdit_two_streams = value;
-  } else {
-    return fail(MC_EINVAL, "unknown option '%s'", key);
-  }
   return MC_OK;
 }
 

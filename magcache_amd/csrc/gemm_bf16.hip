@@ -229,6 +229,14 @@ hipError_t launch_gemm_bf16_small(const GemmParams& p, int epi, hipStream_t stre
 // 50.  K < 1024: the 256^2 kernels' prologue / epilogue dominate, keep the small one.
 int g_gemm_kernel = 0;
 
+bool gemm_bf16_big_linked() {
+#ifdef MC_WITH_REF_GEMM
+  return true;
+#else
+  return false;
+#endif
+}
+
 static bool prefer_256(const GemmParams& p) {
   const long tiles256 = (long)((p.M + 255) / 256) * (p.N / 256);
   const long tiles128 = (long)((p.M + 127) / 128) * ((p.N + 127) / 128);

@@ -1,0 +1,117 @@
+// What the host-side engines (engine.cpp, mmdit_engine.cpp) share, internal like ops.h: the error text mc_last_error()
+// reports, the named weight store behind *_set_weight, the workspace plan behind *_set_workspace, the Linear descriptor.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdarg>
+#include <cstring>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "../../include/magcache_hip.h"
+#include "ops.h"
+
+namespace mc {
+
+// ---------------------------------------------------------------- error text (thread local, one per library)
+mc_status fail(mc_status s, const char* fmt, ...);
+const char* last_error();
+
+#define HIP_TRY(expr)                                                                              \
+  do {                                                                                             \
+    hipError_t _e = (expr);                                                                        \
+    if (_e != hipSuccess) return ::mc::fail(MC_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
+  } while (0)
+#define MC_TRY(expr)                 \
+  do {                               \
+    mc_status _s = (expr);           \
+    if (_s != MC_OK) return _s;      \
+  } while (0)
+
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+inline GemmParams gp(const bf16_t* A, long lda, const bf16_t* W, long ldw, const float* bias, int M, int N, int K) {
+  GemmParams p;
+  memset(&p, 0, sizeof(p));
+  p.A = A; p.lda = lda; p.W = W; p.ldw = ldw; p.bias = bias; p.M = M; p.N = N; p.K = K;
+  return p;
+}
+
+// mc_set_option values (ops_capi.cpp sets them), each defined in the file that reads it
+extern int g_fp8_fused_quant;    // engine.cpp
+extern int g_sp_attn_partials;   // engine.cpp
+extern int g_mmdit_two_streams;  // mmdit_engine.cpp
+
+// ---------------------------------------------------------------- weights
+// y = x W^T + b with W [n_out, k_in] bf16 and, optionally, an e4m3 copy of W made when the weight is set: with one scale
+// per output channel (q_scale) or with MX block scales (mx: E8M0, block-major [k_in / 32][n_out]).  q == null: bf16 only.
+struct Linear {
+  bf16_t* w = nullptr;
+  float* b = nullptr;
+  int n_out = 0, k_in = 0;
+  uint8_t* q = nullptr;
+  float* q_scale = nullptr;
+  uint8_t* mx = nullptr;
+};
+
+struct Slot {  // one named parameter
+  void* dst = nullptr;
+  mc_dtype dst_dtype = MC_F32;
+  size_t numel = 0;
+  size_t off = 0;  // element offset inside a fused destination (q/k/v -> wqkv)
+  int perm_c = 0;  // > 0: rows are (c, pq) channel-major upstream and are stored (pq, c) -- HunyuanVideo final linear
+  struct Pad { size_t rows = 0, k_in = 0, k_pitch = 0; } pad;  // rows > 0: given [rows, k_in], stored with row pitch k_pitch
+  bool loaded = false;
+  // quantised copy: after the bf16 store the same rows are quantised into q8 -- per output channel (q8_scale), or, mx != null,
+  // relative to E8M0 block scales of the fused destination, block-major with mx_rows rows per k block
+  uint8_t* q8 = nullptr;
+  float* q8_scale = nullptr;
+  size_t q8_k = 0;  // row length (in_features)
+  uint8_t* mx = nullptr;
+  size_t mx_rows = 0;
+};
+
+struct WeightStore {
+  std::map<std::string, Slot> slots;
+  std::vector<void*> owned;
+
+  template <class T>
+  mc_status alloc(T** p, size_t n) { return alloc_bytes(reinterpret_cast<void**>(p), n * sizeof(T)); }
+  Slot& add(const std::string& name, void* dst, mc_dtype dt, size_t numel, size_t off = 0);
+  // "<prefix>.weight" [n_out, n_in] (bf16) and "<prefix>.bias" [n_out] (fp32) at row row_off of fused destinations; returns
+  // the weight's slot
+  Slot& add_linear(const std::string& prefix, bf16_t* w, float* b, size_t n_out, size_t n_in, size_t row_off = 0);
+  // copy / cast / permute / pad one parameter into place (and requantise its rows) on the caller's stream
+  mc_status set(const char* name, const void* src_dev, mc_dtype dtype, const int64_t* shape, int ndim, hipStream_t stream);
+  int missing(char* buf, size_t buflen) const;  // count; names, one per line, as far as buf holds them
+  bool all_loaded(const char** first_missing) const;
+  void free_all();
+
+ private:
+  mc_status alloc_bytes(void** p, size_t bytes);
+};
+
+// ---------------------------------------------------------------- workspace
+struct Buf {
+  size_t off = 0, bytes = 0;
+};
+
+// the plan of one caller-owned allocation: named buffers at 256-byte aligned offsets
+struct Workspace {
+  std::map<std::string, Buf> bufs;
+  char* ws = nullptr;
+  size_t need = 0;  // bytes planned so far
+
+  void add(const char* name, size_t bytes);
+  mc_status bind(void* ws_dev, size_t bytes);
+  const Buf* find(const std::string& name) const;
+  mc_status info(const std::string& name, size_t* offset, size_t* bytes) const;
+  template <class T>
+  T* get(const char* name) const { return reinterpret_cast<T*>(ptr(name)); }
+
+ private:
+  char* ptr(const char* name) const;  // null (and the error text) for a name that is not in the plan
+};
+
+}  // namespace mc

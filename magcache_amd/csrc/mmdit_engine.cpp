@@ -31,64 +31,26 @@
 //                           rows are the cache, the text rows are scratch
 // GEMMs over one stream use the exact row count (the 256^2 kernel guards a partial last tile), so neighbouring
 // rows of the other stream are never touched.
-#include <hip/hip_runtime.h>
-
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
-#include <map>
-#include <string>
-#include <vector>
 
 #include "../../include/magcache_mmdit.h"
-#include "ops.h"
+#include "host.h"
 
+using mc::align_up;
 using mc::bf16_t;
+using mc::fail;
+using mc::gp;
 
 namespace mc {
-mc_status set_error_v(mc_status s, const char* fmt, va_list ap);  // engine.cpp
-}
-
 // mc_set_option("mmdit_two_streams", v): 0 = off (the DEFAULT since round 3: the packed-fp32 co-execution fault behind
 // round 2's nondeterminism has a measured workaround but no root cause -- ADVICE r02 -- so the overlap is opt-in),
 // -1 = by shape (on when the text half is at least 1/16 of the image half and the engine is not sequence parallel: FLUX),
 // 1 on, 2..6 diagnostic splits (tests/two_stream_bisect.py)
 int g_mmdit_two_streams = 0;
+}  // namespace mc
+using mc::g_mmdit_two_streams;
 
 namespace {
-
-mc_status fail(mc_status s, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  mc_status r = mc::set_error_v(s, fmt, ap);
-  va_end(ap);
-  return r;
-}
-
-#define HIP_TRY(expr)                                                                              \
-  do {                                                                                             \
-    hipError_t _e = (expr);                                                                        \
-    if (_e != hipSuccess) return fail(MC_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-  } while (0)
-#define MC_TRY(expr)                 \
-  do {                               \
-    mc_status _s = (expr);           \
-    if (_s != MC_OK) return _s;      \
-  } while (0)
-
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-struct Slot {
-  void* dst = nullptr;
-  mc_dtype dst_dtype = MC_F32;
-  size_t numel = 0, off = 0;
-  int perm_c = 0;  // > 0: rows are (c, pq) channel-major upstream and are stored (pq, c) -- HunyuanVideo final linear
-  bool loaded = false;
-};
-struct Buf {
-  size_t off = 0, bytes = 0;
-};
 
 struct Stream {  // one stream (image or text) of a double block
   bf16_t *wqkv, *wo, *w1, *w2;
@@ -107,13 +69,6 @@ struct Refiner {
   bf16_t *wqkv, *wo, *w1, *w2, *wada;
   float *bqkv, *bo, *b1, *b2, *bada, *n1w, *n1b, *n2w, *n2b;
 };
-
-mc::GemmParams gp(const bf16_t* A, long lda, const bf16_t* W, long ldw, const float* bias, int M, int N, int K) {
-  mc::GemmParams p;
-  memset(&p, 0, sizeof(p));
-  p.A = A; p.lda = lda; p.W = W; p.ldw = ldw; p.bias = bias; p.M = M; p.N = N; p.K = K;
-  return p;
-}
 
 }  // namespace
 
@@ -140,18 +95,13 @@ struct mc_mmdit {
   float *b_in = nullptr, *b_ctx = nullptr, *b_mod = nullptr, *w_head = nullptr, *b_head = nullptr;
   float* w_txt_norm = nullptr;  // Qwen-Image txt_norm (RMSNorm over txt_dim)
   float* cs = nullptr;  // RoPE (cos,sin) [Sp][64][2]
-  std::map<std::string, Slot> slots;
-  std::vector<void*> owned;
-  char* ws = nullptr;
-  size_t ws_need = 0;
-  std::map<std::string, Buf> bufs;
+  mc::WeightStore weights;
+  mc::Workspace work;
   int res_cur[2] = {0, 0};  // per CFG branch: the slot (of the branch's own) holding residual_cache / previous_residual
   bool have_res[2] = {false, false}, have_stats = false, pads_clean = false;
 
   template <class T>
-  T* buf(const char* name) const {
-    return reinterpret_cast<T*>(ws + bufs.find(name)->second.off);
-  }
+  T* buf(const char* name) const { return work.get<T>(name); }
   // slot i (0 / 1) of CFG branch b: residual<b * slots_per_branch + i>; branch 0 is residual0 / residual1 as before
   int res_index(int b, int i) const { return b * (cfg.calibration ? 2 : 1) + i; }
   float* residual_joint(int i, int b = 0) const {
@@ -169,52 +119,22 @@ namespace {
 // every GEMM of the engine: the split-K scratch of the stream it runs on rides along (launch_gemm_bf16 decides by shape
 // whether to use it: the projections back to d at FLUX sizes do, nothing at HunyuanVideo's 119 k tokens does)
 hipError_t gemm(const mc_mmdit* e, mc::GemmParams p, int epi, hipStream_t s) {
-  auto it = e->bufs.find((e->side && s == e->side) ? "splitk1" : "splitk0");
-  if (it != e->bufs.end() && it->second.bytes > 0 && e->ws) {
-    p.splitk_ws = reinterpret_cast<float*>(e->ws + it->second.off);
-    p.splitk_ws_bytes = it->second.bytes;
+  const mc::Buf* b = e->work.find((e->side && s == e->side) ? "splitk1" : "splitk0");
+  if (b && b->bytes > 0 && e->work.ws) {
+    p.splitk_ws = reinterpret_cast<float*>(e->work.ws + b->off);
+    p.splitk_ws_bytes = b->bytes;
   }
   return mc::launch_gemm_bf16(p, epi, s);
 }
 
-template <class T>
-mc_status dev_alloc(mc_mmdit* e, T** p, size_t n) {
-  void* q = nullptr;
-  hipError_t err = hipMalloc(&q, n * sizeof(T) + 256);
-  if (err != hipSuccess) return fail(MC_ENOMEM, "hipMalloc(%zu) failed: %s", n * sizeof(T), hipGetErrorString(err));
-  e->owned.push_back(q);
-  *p = reinterpret_cast<T*>(q);
-  return MC_OK;
-}
-
-void add_slot(mc_mmdit* e, const std::string& name, void* dst, mc_dtype dt, size_t numel, size_t off = 0) {
-  Slot s;
-  s.dst = dst; s.dst_dtype = dt; s.numel = numel; s.off = off;
-  e->slots[name] = s;
-}
-
-void add_buf(mc_mmdit* e, size_t& cur, const char* name, size_t bytes) {
-  Buf b;
-  b.off = cur; b.bytes = bytes;
-  e->bufs[name] = b;
-  cur = align_up(cur + bytes, 256);
-}
-
-#define ALLOC(ptr, n) MC_TRY(dev_alloc(e, &(ptr), (n)))
-
-// Linear slots "<prefix>.weight" [n_out, n_in] (bf16) and "<prefix>.bias" [n_out] (fp32) inside fused destinations
-void linear_slot(mc_mmdit* e, const std::string& prefix, bf16_t* w, float* b, size_t n_out, size_t n_in,
-                 size_t row_off = 0) {
-  add_slot(e, prefix + ".weight", w, MC_BF16, n_out * n_in, row_off * n_in);
-  add_slot(e, prefix + ".bias", b, MC_F32, n_out, row_off);
-}
+#define ALLOC(ptr, n) MC_TRY(e->weights.alloc(&(ptr), (n)))
 
 mc_status alloc_mlp2(mc_mmdit* e, Mlp2& m, int k_in, const std::string& l1, const std::string& l2) {
   const size_t d = e->d;
   m.k_in = k_in;
   ALLOC(m.w1, d * k_in); ALLOC(m.b1, d); ALLOC(m.w2, d * d); ALLOC(m.b2, d);
-  linear_slot(e, l1, m.w1, m.b1, d, k_in);
-  linear_slot(e, l2, m.w2, m.b2, d, d);
+  e->weights.add_linear(l1, m.w1, m.b1, d, k_in);
+  e->weights.add_linear(l2, m.w2, m.b2, d, d);
   return MC_OK;
 }
 
@@ -277,7 +197,7 @@ mc_status mc_mmdit_create(const mc_mmdit_config* cfg, mc_mmdit** out) {
   auto cleanup = [&](mc_status st) { mc_mmdit_destroy(e); return st; };
 #define TRY_C(expr) do { mc_status _s = (expr); if (_s != MC_OK) return cleanup(_s); } while (0)
 #undef ALLOC
-#define ALLOC(ptr, n) TRY_C(dev_alloc(e, &(ptr), (n)))
+#define ALLOC(ptr, n) TRY_C(e->weights.alloc(&(ptr), (n)))
 
   // ---- embeds
   ALLOC(e->w_in, d * e->Kp); ALLOC(e->b_in, d);
@@ -286,12 +206,13 @@ mc_status mc_mmdit_create(const mc_mmdit_config* cfg, mc_mmdit** out) {
   // Qwen-Image slots: diffusers models/transformers/transformer_qwenimage.py (QwenImageTransformer2DModel: img_in,
   // txt_norm, txt_in, time_text_embed.timestep_embedder, transformer_blocks.{i}.{img_mod.1, txt_mod.1, attn.*,
   // img_mlp.net.{0.proj,2}, txt_mlp.net.{0.proj,2}}, norm_out.linear, proj_out)
-  add_slot(e, flux ? "x_embedder.weight" : qw ? "img_in.weight" : "img_in.proj.weight", e->w_in, MC_BF16, d * e->Kin);
-  add_slot(e, flux ? "x_embedder.bias" : qw ? "img_in.bias" : "img_in.proj.bias", e->b_in, MC_F32, d);
-  linear_slot(e, flux ? "context_embedder" : qw ? "txt_in" : "txt_in.input_embedder", e->w_ctx, e->b_ctx, d, c.txt_dim);
+  mc::Slot& w_in = e->weights.add(flux ? "x_embedder.weight" : qw ? "img_in.weight" : "img_in.proj.weight", e->w_in, MC_BF16, d * e->Kin);
+  if (e->Kin != e->Kp) w_in.pad = {d, (size_t)e->Kin, (size_t)e->Kp};   // stored [d, Kp]: Kin padded to a GEMM K step
+  e->weights.add(flux ? "x_embedder.bias" : qw ? "img_in.bias" : "img_in.proj.bias", e->b_in, MC_F32, d);
+  e->weights.add_linear(flux ? "context_embedder" : qw ? "txt_in" : "txt_in.input_embedder", e->w_ctx, e->b_ctx, d, c.txt_dim);
   if (qw) {
     ALLOC(e->w_txt_norm, c.txt_dim);
-    add_slot(e, "txt_norm.weight", e->w_txt_norm, MC_F32, c.txt_dim);
+    e->weights.add("txt_norm.weight", e->w_txt_norm, MC_F32, c.txt_dim);
     TRY_C(alloc_mlp2(e, e->time_mlp, 256, "time_text_embed.timestep_embedder.linear_1", "time_text_embed.timestep_embedder.linear_2"));
   } else if (flux) {
     TRY_C(alloc_mlp2(e, e->time_mlp, 256, "time_text_embed.timestep_embedder.linear_1", "time_text_embed.timestep_embedder.linear_2"));
@@ -311,13 +232,13 @@ mc_status mc_mmdit_create(const mc_mmdit_config* cfg, mc_mmdit** out) {
       ALLOC(r.w1, 4 * d * d); ALLOC(r.b1, 4 * d); ALLOC(r.w2, 4 * d * d); ALLOC(r.b2, d);
       ALLOC(r.wada, 2 * d * d); ALLOC(r.bada, 2 * d);
       ALLOC(r.n1w, d); ALLOC(r.n1b, d); ALLOC(r.n2w, d); ALLOC(r.n2b, d);
-      linear_slot(e, p + "self_attn_qkv", r.wqkv, r.bqkv, 3 * d, d);
-      linear_slot(e, p + "self_attn_proj", r.wo, r.bo, d, d);
-      linear_slot(e, p + "mlp.fc1", r.w1, r.b1, 4 * d, d);
-      linear_slot(e, p + "mlp.fc2", r.w2, r.b2, d, 4 * d);
-      linear_slot(e, p + "adaLN_modulation.1", r.wada, r.bada, 2 * d, d);
-      add_slot(e, p + "norm1.weight", r.n1w, MC_F32, d); add_slot(e, p + "norm1.bias", r.n1b, MC_F32, d);
-      add_slot(e, p + "norm2.weight", r.n2w, MC_F32, d); add_slot(e, p + "norm2.bias", r.n2b, MC_F32, d);
+      e->weights.add_linear(p + "self_attn_qkv", r.wqkv, r.bqkv, 3 * d, d);
+      e->weights.add_linear(p + "self_attn_proj", r.wo, r.bo, d, d);
+      e->weights.add_linear(p + "mlp.fc1", r.w1, r.b1, 4 * d, d);
+      e->weights.add_linear(p + "mlp.fc2", r.w2, r.b2, d, 4 * d);
+      e->weights.add_linear(p + "adaLN_modulation.1", r.wada, r.bada, 2 * d, d);
+      e->weights.add(p + "norm1.weight", r.n1w, MC_F32, d); e->weights.add(p + "norm1.bias", r.n1b, MC_F32, d);
+      e->weights.add(p + "norm2.weight", r.n2w, MC_F32, d); e->weights.add(p + "norm2.bias", r.n2b, MC_F32, d);
     }
   }
   // ---- fused modulation matrix: every block's AdaLN linear stacked, one GEMV per forward
@@ -332,36 +253,36 @@ mc_status mc_mmdit_create(const mc_mmdit_config* cfg, mc_mmdit** out) {
     const std::string p = (hy ? "double_blocks." : "transformer_blocks.") + std::to_string(i) + ".";
     if (!hy) {
       // modulation chunk order shift, scale, gate (attention), shift, scale, gate (MLP) in both families
-      linear_slot(e, p + (qw ? "img_mod.1" : "norm1.linear"), e->w_mod, e->b_mod, 6 * d, d, e->mod_double(i, 0));
-      linear_slot(e, p + (qw ? "txt_mod.1" : "norm1_context.linear"), e->w_mod, e->b_mod, 6 * d, d, e->mod_double(i, 1));
+      e->weights.add_linear(p + (qw ? "img_mod.1" : "norm1.linear"), e->w_mod, e->b_mod, 6 * d, d, e->mod_double(i, 0));
+      e->weights.add_linear(p + (qw ? "txt_mod.1" : "norm1_context.linear"), e->w_mod, e->b_mod, 6 * d, d, e->mod_double(i, 1));
       const char* qkv_i[3] = {"attn.to_q", "attn.to_k", "attn.to_v"};
       const char* qkv_t[3] = {"attn.add_q_proj", "attn.add_k_proj", "attn.add_v_proj"};
       for (int j = 0; j < 3; ++j) {
-        linear_slot(e, p + qkv_i[j], a.wqkv, a.bqkv, d, d, j * d);
-        linear_slot(e, p + qkv_t[j], t.wqkv, t.bqkv, d, d, j * d);
+        e->weights.add_linear(p + qkv_i[j], a.wqkv, a.bqkv, d, d, j * d);
+        e->weights.add_linear(p + qkv_t[j], t.wqkv, t.bqkv, d, d, j * d);
       }
-      add_slot(e, p + "attn.norm_q.weight", a.qn, MC_F32, 128); add_slot(e, p + "attn.norm_k.weight", a.kn, MC_F32, 128);
-      add_slot(e, p + "attn.norm_added_q.weight", t.qn, MC_F32, 128);
-      add_slot(e, p + "attn.norm_added_k.weight", t.kn, MC_F32, 128);
-      linear_slot(e, p + "attn.to_out.0", a.wo, a.bo, d, d);
-      linear_slot(e, p + "attn.to_add_out", t.wo, t.bo, d, d);
+      e->weights.add(p + "attn.norm_q.weight", a.qn, MC_F32, 128); e->weights.add(p + "attn.norm_k.weight", a.kn, MC_F32, 128);
+      e->weights.add(p + "attn.norm_added_q.weight", t.qn, MC_F32, 128);
+      e->weights.add(p + "attn.norm_added_k.weight", t.kn, MC_F32, 128);
+      e->weights.add_linear(p + "attn.to_out.0", a.wo, a.bo, d, d);
+      e->weights.add_linear(p + "attn.to_add_out", t.wo, t.bo, d, d);
       const std::string ffi = qw ? "img_mlp" : "ff", fft = qw ? "txt_mlp" : "ff_context";
-      linear_slot(e, p + ffi + ".net.0.proj", a.w1, a.b1, 4 * d, d);
-      linear_slot(e, p + ffi + ".net.2", a.w2, a.b2, d, 4 * d);
-      linear_slot(e, p + fft + ".net.0.proj", t.w1, t.b1, 4 * d, d);
-      linear_slot(e, p + fft + ".net.2", t.w2, t.b2, d, 4 * d);
+      e->weights.add_linear(p + ffi + ".net.0.proj", a.w1, a.b1, 4 * d, d);
+      e->weights.add_linear(p + ffi + ".net.2", a.w2, a.b2, d, 4 * d);
+      e->weights.add_linear(p + fft + ".net.0.proj", t.w1, t.b1, 4 * d, d);
+      e->weights.add_linear(p + fft + ".net.2", t.w2, t.b2, d, 4 * d);
     } else {
       const char* nm[2] = {"img", "txt"};
       Stream* st[2] = {&a, &t};
       for (int k = 0; k < 2; ++k) {
         const std::string q = p + nm[k];
-        linear_slot(e, q + "_mod.linear", e->w_mod, e->b_mod, 6 * d, d, e->mod_double(i, k));
-        linear_slot(e, q + "_attn_qkv", st[k]->wqkv, st[k]->bqkv, 3 * d, d);
-        add_slot(e, q + "_attn_q_norm.weight", st[k]->qn, MC_F32, 128);
-        add_slot(e, q + "_attn_k_norm.weight", st[k]->kn, MC_F32, 128);
-        linear_slot(e, q + "_attn_proj", st[k]->wo, st[k]->bo, d, d);
-        linear_slot(e, q + "_mlp.fc1", st[k]->w1, st[k]->b1, 4 * d, d);
-        linear_slot(e, q + "_mlp.fc2", st[k]->w2, st[k]->b2, d, 4 * d);
+        e->weights.add_linear(q + "_mod.linear", e->w_mod, e->b_mod, 6 * d, d, e->mod_double(i, k));
+        e->weights.add_linear(q + "_attn_qkv", st[k]->wqkv, st[k]->bqkv, 3 * d, d);
+        e->weights.add(q + "_attn_q_norm.weight", st[k]->qn, MC_F32, 128);
+        e->weights.add(q + "_attn_k_norm.weight", st[k]->kn, MC_F32, 128);
+        e->weights.add_linear(q + "_attn_proj", st[k]->wo, st[k]->bo, d, d);
+        e->weights.add_linear(q + "_mlp.fc1", st[k]->w1, st[k]->b1, 4 * d, d);
+        e->weights.add_linear(q + "_mlp.fc2", st[k]->w2, st[k]->b2, d, 4 * d);
       }
     }
   }
@@ -372,29 +293,29 @@ mc_status mc_mmdit_create(const mc_mmdit_config* cfg, mc_mmdit** out) {
     ALLOC(g.qn, 128); ALLOC(g.kn, 128);
     const std::string p = (flux ? "single_transformer_blocks." : "single_blocks.") + std::to_string(i) + ".";
     if (flux) {
-      linear_slot(e, p + "norm.linear", e->w_mod, e->b_mod, 3 * d, d, e->mod_single(i));
-      linear_slot(e, p + "attn.to_q", g.w_in, g.b_in, d, d, 0);
-      linear_slot(e, p + "attn.to_k", g.w_in, g.b_in, d, d, d);
-      linear_slot(e, p + "attn.to_v", g.w_in, g.b_in, d, d, 2 * d);
-      linear_slot(e, p + "proj_mlp", g.w_in, g.b_in, 4 * d, d, 3 * d);
-      linear_slot(e, p + "proj_out", g.w_out, g.b_out, d, 5 * d);
-      add_slot(e, p + "attn.norm_q.weight", g.qn, MC_F32, 128); add_slot(e, p + "attn.norm_k.weight", g.kn, MC_F32, 128);
+      e->weights.add_linear(p + "norm.linear", e->w_mod, e->b_mod, 3 * d, d, e->mod_single(i));
+      e->weights.add_linear(p + "attn.to_q", g.w_in, g.b_in, d, d, 0);
+      e->weights.add_linear(p + "attn.to_k", g.w_in, g.b_in, d, d, d);
+      e->weights.add_linear(p + "attn.to_v", g.w_in, g.b_in, d, d, 2 * d);
+      e->weights.add_linear(p + "proj_mlp", g.w_in, g.b_in, 4 * d, d, 3 * d);
+      e->weights.add_linear(p + "proj_out", g.w_out, g.b_out, d, 5 * d);
+      e->weights.add(p + "attn.norm_q.weight", g.qn, MC_F32, 128); e->weights.add(p + "attn.norm_k.weight", g.kn, MC_F32, 128);
     } else {
-      linear_slot(e, p + "modulation.linear", e->w_mod, e->b_mod, 3 * d, d, e->mod_single(i));
-      linear_slot(e, p + "linear1", g.w_in, g.b_in, 7 * d, d);
-      linear_slot(e, p + "linear2", g.w_out, g.b_out, d, 5 * d);
-      add_slot(e, p + "q_norm.weight", g.qn, MC_F32, 128); add_slot(e, p + "k_norm.weight", g.kn, MC_F32, 128);
+      e->weights.add_linear(p + "modulation.linear", e->w_mod, e->b_mod, 3 * d, d, e->mod_single(i));
+      e->weights.add_linear(p + "linear1", g.w_in, g.b_in, 7 * d, d);
+      e->weights.add_linear(p + "linear2", g.w_out, g.b_out, d, 5 * d);
+      e->weights.add(p + "q_norm.weight", g.qn, MC_F32, 128); e->weights.add(p + "k_norm.weight", g.kn, MC_F32, 128);
     }
   }
   // ---- final layer
   // (Qwen-Image's head is FLUX's: AdaLayerNormContinuous, chunk order scale, shift)
-  linear_slot(e, !hy ? "norm_out.linear" : "final_layer.adaLN_modulation.1", e->w_mod, e->b_mod, 2 * d, d, e->mod_final());
+  e->weights.add_linear(!hy ? "norm_out.linear" : "final_layer.adaLN_modulation.1", e->w_mod, e->b_mod, 2 * d, d, e->mod_final());
   ALLOC(e->w_head, (size_t)e->out_feat * d); ALLOC(e->b_head, e->out_feat);
-  add_slot(e, !hy ? "proj_out.weight" : "final_layer.linear.weight", e->w_head, MC_F32, (size_t)e->out_feat * d);
-  add_slot(e, !hy ? "proj_out.bias" : "final_layer.linear.bias", e->b_head, MC_F32, e->out_feat);
+  e->weights.add(!hy ? "proj_out.weight" : "final_layer.linear.weight", e->w_head, MC_F32, (size_t)e->out_feat * d);
+  e->weights.add(!hy ? "proj_out.bias" : "final_layer.linear.bias", e->b_head, MC_F32, e->out_feat);
   if (hy) {  // upstream token vector is (c, pt, ph, pw) channel-major; launch_unpatchify wants (ph, pw, c)
-    e->slots["final_layer.linear.weight"].perm_c = c.out_channels;
-    e->slots["final_layer.linear.bias"].perm_c = c.out_channels;
+    e->weights.slots["final_layer.linear.weight"].perm_c = c.out_channels;
+    e->weights.slots["final_layer.linear.bias"].perm_c = c.out_channels;
   }
   // ---- RoPE table, identity rotation until mc_mmdit_set_rope
   {
@@ -405,31 +326,31 @@ mc_status mc_mmdit_create(const mc_mmdit_config* cfg, mc_mmdit** out) {
       return cleanup(fail(MC_EHIP, "RoPE table upload failed"));
   }
   // ---- workspace plan
-  size_t cur = 0;
+  mc::Workspace& ws = e->work;
   const size_t Sp = e->Sp, Li = e->Li;
   const size_t Ltp = align_up(e->Lt, 256);
-  add_buf(e, cur, "x", Sp * d * 4);
-  add_buf(e, cur, "x0", Sp * d * 2);
-  add_buf(e, cur, "xn", Sp * d * 2);
-  add_buf(e, cur, "qkv", (Sp + 64) * 3 * d * 2);        // + one key tile of slack behind the text rows
+  ws.add("x", Sp * d * 4);
+  ws.add("x0", Sp * d * 2);
+  ws.add("xn", Sp * d * 2);
+  ws.add("qkv", (Sp + 64) * 3 * d * 2);        // + one key tile of slack behind the text rows
   if (e->P > 1) {
-    add_buf(e, cur, "kv_gather", (size_t)e->P * e->Lrp * 2 * d * 2);   // image K|V of every rank
-    add_buf(e, cur, "attn_lse", (size_t)e->H * Sp * 4);
+    ws.add("kv_gather", (size_t)e->P * e->Lrp * 2 * d * 2);   // image K|V of every rank
+    ws.add("attn_lse", (size_t)e->H * Sp * 4);
   } else if (qw) {
-    add_buf(e, cur, "attn_lse", (size_t)e->H * Sp * 4);                // image keys, then the valid text keys merged
+    ws.add("attn_lse", (size_t)e->H * Sp * 4);                // image keys, then the valid text keys merged
   }
-  add_buf(e, cur, "am", Sp * 5 * d * 2);               // also the fp32 [img, d] head operand after the last block
-  add_buf(e, cur, "tokens", align_up(Li, 256) * e->Kp * 2);
-  add_buf(e, cur, "txt_in", Ltp * c.txt_dim * 2);
-  add_buf(e, cur, "txt_e", Ltp * d * 2);
-  add_buf(e, cur, "emod", e->mod_rows * 4);
-  add_buf(e, cur, "vecs", 16 * d * 4 + (size_t)c.txt_dim * 4 + 1024);   // sinusoids, hidden vectors, vec, c, gates
-  add_buf(e, cur, "head_tokens", Li * 64 * 4);
-  add_buf(e, cur, "residual0", Sp * d * 4);
-  if (c.calibration) add_buf(e, cur, "residual1", Sp * d * 4);
+  ws.add("am", Sp * 5 * d * 2);               // also the fp32 [img, d] head operand after the last block
+  ws.add("tokens", align_up(Li, 256) * e->Kp * 2);
+  ws.add("txt_in", Ltp * c.txt_dim * 2);
+  ws.add("txt_e", Ltp * d * 2);
+  ws.add("emod", e->mod_rows * 4);
+  ws.add("vecs", 16 * d * 4 + (size_t)c.txt_dim * 4 + 1024);   // sinusoids, hidden vectors, vec, c, gates
+  ws.add("head_tokens", Li * 64 * 4);
+  ws.add("residual0", Sp * d * 4);
+  if (c.calibration) ws.add("residual1", Sp * d * 4);
   if (qw) {   // the uncond branch's slots (Qwen-Image only: the other families are guidance distilled, one branch)
-    add_buf(e, cur, c.calibration ? "residual2" : "residual1", Sp * d * 4);
-    if (c.calibration) add_buf(e, cur, "residual3", Sp * d * 4);
+    ws.add(c.calibration ? "residual2" : "residual1", Sp * d * 4);
+    if (c.calibration) ws.add("residual3", Sp * d * 4);
   }
   {
     // split-K scratch (gemm_bf16_v2): the largest any GEMM of a block wants, one buffer per stream that may run GEMMs
@@ -444,13 +365,12 @@ mc_status mc_mmdit_create(const mc_mmdit_config* cfg, mc_mmdit** out) {
         upd(*n, M, d, 5 * d, mc::EPI_RESID_GATE);
       }
     }
-    if (need_all) add_buf(e, cur, "splitk0", need_all);
-    if (need_txt) add_buf(e, cur, "splitk1", need_txt);
+    if (need_all) ws.add("splitk0", need_all);
+    if (need_txt) ws.add("splitk1", need_txt);
   }
-  add_buf(e, cur, "calib_partial", (2048 * 4 + 2) * 8);   // + the arrival ticket of calib_stats_kernel
-  add_buf(e, cur, "calib_sums", 64);
-  add_buf(e, cur, "calib_stats", 64);
-  e->ws_need = cur;
+  ws.add("calib_partial", (2048 * 4 + 2) * 8);   // + the arrival ticket of calib_stats_kernel
+  ws.add("calib_sums", 64);
+  ws.add("calib_stats", 64);
   // side stream and fork / join events of the (optional) two-stream double block: created here, never inside a forward
   // (a forward may run under stream capture)
   if (hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking) != hipSuccess) return cleanup(fail(MC_EHIP, "side stream"));
@@ -473,17 +393,15 @@ void mc_mmdit_destroy(mc_mmdit* e) {
       (void)hipEventDestroy(e->ev_join[i]);
     }
   }
-  for (void* p : e->owned) (void)hipFree(p);
+  e->weights.free_all();
   delete e;
 }
 
-size_t mc_mmdit_workspace_bytes(const mc_mmdit* e) { return e ? e->ws_need : 0; }
+size_t mc_mmdit_workspace_bytes(const mc_mmdit* e) { return e ? e->work.need : 0; }
 
 mc_status mc_mmdit_set_workspace(mc_mmdit* e, void* ws_dev, size_t bytes) {
-  if (!e || !ws_dev) return fail(MC_EINVAL, "null argument");
-  if (bytes < e->ws_need) return fail(MC_EINVAL, "workspace too small: %zu < %zu", bytes, e->ws_need);
-  if (((uintptr_t)ws_dev) & 255) return fail(MC_EINVAL, "workspace must be 256-byte aligned");
-  e->ws = (char*)ws_dev;
+  if (!e) return fail(MC_EINVAL, "null argument");
+  MC_TRY(e->work.bind(ws_dev, bytes));
   e->have_res[0] = e->have_res[1] = e->have_stats = e->pads_clean = false;
   HIP_TRY(hipMemset(e->buf<double>("calib_partial") + 2048 * 4, 0, 16));   // arrival ticket of calib_stats_kernel
   return MC_OK;
@@ -499,71 +417,20 @@ mc_status mc_mmdit_buffer_info(const mc_mmdit* e, const char* name, size_t* offs
     if (b == 1 && e->cfg.family != MC_FAMILY_QWEN) return fail(MC_EINVAL, "unknown buffer '%s'", name);
     n = "residual" + std::to_string(e->res_index(b, e->res_cur[b]));
   }
-  auto it = e->bufs.find(n);
-  if (it == e->bufs.end()) return fail(MC_EINVAL, "unknown buffer '%s'", name);
-  if (offset) *offset = it->second.off + (res ? (size_t)e->img0 * e->d * 4 : 0);
-  if (bytes) *bytes = res ? (size_t)e->Li * e->d * 4 : it->second.bytes;
+  MC_TRY(e->work.info(n, offset, bytes));
+  if (res && offset) *offset += (size_t)e->img0 * e->d * 4;
+  if (res && bytes) *bytes = (size_t)e->Li * e->d * 4;
   return MC_OK;
 }
 
 mc_status mc_mmdit_set_weight(mc_mmdit* e, const char* name, const void* src_dev, mc_dtype dtype, const int64_t* shape,
-                              int ndim, mc_stream stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
+                              int ndim, mc_stream stream) {
   if (!e || !name || !src_dev || !shape) return fail(MC_EINVAL, "null argument");
-  auto it = e->slots.find(name);
-  if (it == e->slots.end()) return fail(MC_EINVAL, "unknown weight '%s'", name);
-  Slot& s = it->second;
-  size_t numel = 1;
-  for (int i = 0; i < ndim; ++i) numel *= (size_t)shape[i];
-  if (numel != s.numel) return fail(MC_EINVAL, "weight '%s': %zu elements given, %zu expected", name, numel, s.numel);
-  if (s.dst_dtype == MC_F32) {
-    if (dtype != MC_F32) return fail(MC_EINVAL, "weight '%s' must be given as fp32", name);
-    float* dst = (float*)s.dst + s.off;
-    if (s.perm_c > 0) {  // rows (c, pq) -> (pq, c)
-      const size_t C = s.perm_c, row = numel / (4 * C);
-      for (size_t c = 0; c < C; ++c)
-        for (size_t pq = 0; pq < 4; ++pq)
-          HIP_TRY(hipMemcpyAsync(dst + (pq * C + c) * row, (const float*)src_dev + (c * 4 + pq) * row, row * 4,
-                                 hipMemcpyDeviceToDevice, stream));
-    } else {
-      HIP_TRY(hipMemcpyAsync(dst, src_dev, numel * 4, hipMemcpyDeviceToDevice, stream));
-    }
-  } else {
-    bf16_t* dst = (bf16_t*)s.dst + s.off;
-    const bool is_in = (s.dst == e->w_in);
-    if (is_in && e->Kin != e->Kp) {
-      if (dtype == MC_F32) {
-        HIP_TRY(mc::launch_cast_pad_bf16((const float*)src_dev, e->Kin, e->d, e->d, e->Kin, dst, e->Kp, stream));
-      } else {
-        HIP_TRY(hipMemcpy2DAsync(dst, (size_t)e->Kp * 2, src_dev, (size_t)e->Kin * 2, (size_t)e->Kin * 2, e->d,
-                                 hipMemcpyDeviceToDevice, stream));
-      }
-    } else if (dtype == MC_F32) {
-      HIP_TRY(mc::launch_cast_bf16((const float*)src_dev, dst, numel, stream));
-    } else {
-      HIP_TRY(hipMemcpyAsync(dst, src_dev, numel * 2, hipMemcpyDeviceToDevice, stream));
-    }
-  }
-  s.loaded = true;
-  return MC_OK;
+  return e->weights.set(name, src_dev, dtype, shape, ndim, (hipStream_t)stream);
 }
 
 int mc_mmdit_weights_missing(const mc_mmdit* e, char* buf, size_t buflen) {
-  if (!e) return -1;
-  int n = 0;
-  size_t pos = 0;
-  if (buf && buflen) buf[0] = 0;
-  for (auto& kv : e->slots) {
-    if (kv.second.loaded) continue;
-    ++n;
-    if (buf && pos + kv.first.size() + 2 < buflen) {
-      memcpy(buf + pos, kv.first.c_str(), kv.first.size());
-      pos += kv.first.size();
-      buf[pos++] = '\n';
-      buf[pos] = 0;
-    }
-  }
-  return n;
+  return e ? e->weights.missing(buf, buflen) : -1;
 }
 
 mc_status mc_mmdit_set_rope(mc_mmdit* e, const float* cos_dev, const float* sin_dev, int n_rows, mc_stream stream) {
@@ -851,19 +718,14 @@ mc_status run_two(mc_mmdit* e, hipStream_t s, int mode, FI&& img_part, FT&& txt_
 // ================================================================================================ forward, in phases
 // begin (conditioning, embeds) -> for every block: block_pre, [caller: all-gather of the image K|V shards], block_post
 // -> end (final layer).  mc_mmdit_forward runs them back to back on one GPU.
-extern "C" {
-
-}  // extern "C"
-
 namespace {
 
 mc_status begin_impl(mc_mmdit* e, const float* img_dev, double timestep, double guidance, const float* txt_dev,
                      int txt_valid, const float* vec_dev, mc_mode mode, int branch, mc_stream stream_) {
   hipStream_t s = (hipStream_t)stream_;
   if (!e) return fail(MC_EINVAL, "null engine");
-  if (!e->ws) return fail(MC_ESTATE, "workspace not set (mc_mmdit_set_workspace)");
-  for (auto& kv : e->slots)
-    if (!kv.second.loaded) return fail(MC_ESTATE, "weight '%s' was never set", kv.first.c_str());
+  if (!e->work.ws) return fail(MC_ESTATE, "workspace not set (mc_mmdit_set_workspace)");
+  if (const char* w = nullptr; !e->weights.all_loaded(&w)) return fail(MC_ESTATE, "weight '%s' was never set", w);
   const mc_mmdit_config& c = e->cfg;
   const bool hy = c.family == MC_FAMILY_HUNYUAN;
   const bool qw = c.family == MC_FAMILY_QWEN;
@@ -890,9 +752,9 @@ mc_status begin_impl(mc_mmdit* e, const float* img_dev, double timestep, double 
   float *sin_t = vecs, *sin_g = vecs + d, *hid = vecs + 2 * d, *vec = vecs + 3 * d;
   if (!e->pads_clean) {
     // rows [S, S_pad) are read by the attention kernel (masked keys, ignored queries) and never written by a GEMM
-    HIP_TRY(hipMemsetAsync(qkv, 0, e->bufs["qkv"].bytes, s));
+    HIP_TRY(hipMemsetAsync(qkv, 0, e->work.find("qkv")->bytes, s));
     HIP_TRY(hipMemsetAsync(x + (size_t)S * d, 0, (size_t)(Sp - S) * d * 4, s));
-    if (e->P > 1) HIP_TRY(hipMemsetAsync(e->buf<bf16_t>("kv_gather"), 0, e->bufs["kv_gather"].bytes, s));
+    if (e->P > 1) HIP_TRY(hipMemsetAsync(e->buf<bf16_t>("kv_gather"), 0, e->work.find("kv_gather")->bytes, s));
     e->pads_clean = true;
   }
   // ---- conditioning vector: time + guidance + pooled text   (flux :303-313, hunyuan :53-67)

@@ -76,6 +76,7 @@ hipError_t launch_gemm_bf16_small(const GemmParams& p, int epi, hipStream_t stre
 // implementation gemm_bf16_v2 is compared with bit for bit
 hipError_t launch_gemm_bf16_big(const GemmParams& p, int epi, hipStream_t stream);
 bool gemm_bf16_big_supported(const GemmParams& p);
+bool gemm_bf16_big_linked();   // is this the reference library?  (gemm_bf16.hip is the one file built both ways)
 hipError_t launch_gemm_bf16_v2(const GemmParams& p, int epi, hipStream_t stream);     // 256x256 tiles, 4 waves, generated stream
 bool gemm_bf16_v2_supported(const GemmParams& p);
 bool gemm_bf16_v2_epi_ok(const GemmParams& p, int epi);         // this epilogue on these operands?

@@ -1,0 +1,311 @@
+// The single-op C entry points of include/magcache_hip.h (mc_op_*: one launcher of ops.h each, for callers that bring their
+// own buffers -- the sampler, the parity tests, the A/B tools), mc_set_option, mc_last_error and mc_version.
+#include <string>
+
+#include "host.h"
+
+using mc::bf16_t;
+using mc::fail;
+using mc::gp;
+
+extern "C" {
+
+const char* mc_last_error(void) { return mc::last_error(); }
+const char* mc_version(void) { return "magcache_hip 0.5 (gfx950)"; }
+
+// split-K scratch of the single-op entry point (mc_op_set_splitk_workspace): the engines carry their own in their workspace
+static float* g_op_splitk_ws = nullptr;
+static size_t g_op_splitk_bytes = 0;
+
+mc_status mc_op_gemm_bf16(const void* A, long lda, const void* W, long ldw, const float* bias, int M, int N, int K,
+                          int epi, void* Cb, long ldc, float* X, long ldx, const float* gate, const void* X0,
+                          long ldx0, float* R, long ldr, void* X0out, long ldx0out, int m_valid, mc_stream s) {
+  mc::GemmParams p = gp((const bf16_t*)A, lda, (const bf16_t*)W, ldw, bias, M, N, K);
+  p.Cb = (bf16_t*)Cb; p.ldc = ldc; p.X = X; p.ldx = ldx; p.gate = gate;
+  p.X0 = (const bf16_t*)X0; p.ldx0 = ldx0; p.R = R; p.ldr = ldr;
+  p.X0out = (bf16_t*)X0out; p.ldx0out = ldx0out; p.m_valid = m_valid;
+  p.splitk_ws = g_op_splitk_ws; p.splitk_ws_bytes = g_op_splitk_bytes;
+  hipError_t err = mc::launch_gemm_bf16(p, epi, (hipStream_t)s);
+  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "gemm: unsupported shape M=%d N=%d K=%d epi=%d", M, N, K, epi);
+  HIP_TRY(err);
+  return MC_OK;
+}
+
+mc_status mc_op_gemm_bf16_resid_sel(const void* A, long lda, const void* W, long ldw, const float* bias, int M, int N, int K,
+                                    int capture, float* X, long ldx, const float* gate, const float* gate2,
+                                    const unsigned char* gate_sel, const void* X0, long ldx0, float* R, long ldr, mc_stream s) {
+  mc::GemmParams p = gp((const bf16_t*)A, lda, (const bf16_t*)W, ldw, bias, M, N, K);
+  p.X = X; p.ldx = ldx; p.gate = gate; p.gate2 = gate2; p.gate_sel = gate_sel;
+  p.X0 = (const bf16_t*)X0; p.ldx0 = ldx0; p.R = R; p.ldr = ldr;
+  if (!gate || !gate2 || !gate_sel) return fail(MC_EINVAL, "gemm (per-token gates): gate, gate2 and gate_sel are required");
+  hipError_t err = mc::launch_gemm_bf16(p, capture ? mc::EPI_RESID_CAPTURE : mc::EPI_RESID_GATE, (hipStream_t)s);
+  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "gemm (per-token gates): unsupported shape M=%d N=%d K=%d", M, N, K);
+  HIP_TRY(err);
+  return MC_OK;
+}
+
+mc_status mc_op_gemm_bf16_rowsplit(const void* A, long lda, const void* W, const void* W_b, long ldw, const float* bias,
+                                   const float* bias_b, int M, int N, int K, int m_split, int epi, void* Cb, long ldc, float* X,
+                                   long ldx, const float* gate, const float* gate_b, mc_stream s) {
+  mc::GemmParams p = gp((const bf16_t*)A, lda, (const bf16_t*)W, ldw, bias, M, N, K);
+  p.Cb = (bf16_t*)Cb; p.ldc = ldc; p.X = X; p.ldx = ldx; p.gate = gate;
+  p.m_split = m_split; p.W_b = (const bf16_t*)W_b; p.bias_b = bias_b; p.gate_b = gate_b;
+  p.splitk_ws = g_op_splitk_ws; p.splitk_ws_bytes = g_op_splitk_bytes;
+  if (epi != mc::EPI_BF16 && epi != mc::EPI_GELU_BF16 && epi != mc::EPI_RESID_GATE)
+    return fail(MC_EINVAL, "gemm (row split): epi %d (0 bf16, 1 gelu, 2 gated residual)", epi);
+  hipError_t err = mc::launch_gemm_bf16(p, epi, (hipStream_t)s);
+  if (err == hipErrorInvalidValue)
+    return fail(MC_EINVAL, "gemm (row split): unsupported shape M=%d N=%d K=%d m_split=%d epi=%d", M, N, K, m_split, epi);
+  HIP_TRY(err);
+  return MC_OK;
+}
+
+mc_status mc_op_gemm_bf16_gelu_split(const void* A, long lda, const void* W, long ldw, const float* bias, int M, int N, int K,
+                                     int n_split, void* Cb, long ldc, void* Cb2, long ldc2, mc_stream s) {
+  mc::GemmParams p = gp((const bf16_t*)A, lda, (const bf16_t*)W, ldw, bias, M, N, K);
+  p.Cb = (bf16_t*)Cb; p.ldc = ldc; p.n_split = n_split; p.Cb2 = (bf16_t*)Cb2; p.ldc2 = ldc2;
+  hipError_t err = mc::launch_gemm_bf16(p, mc::EPI_BF16_GELU_SPLIT, (hipStream_t)s);
+  if (err == hipErrorInvalidValue)
+    return fail(MC_EINVAL, "gemm (bf16 | gelu split): unsupported shape M=%d N=%d K=%d n_split=%d", M, N, K, n_split);
+  HIP_TRY(err);
+  return MC_OK;
+}
+
+int mc_op_gemm_bf16_kernel(int M, int N, int K, int epi) {
+  mc::GemmParams p = gp(nullptr, K, nullptr, K, nullptr, M, N, K);
+  p.ldc = N; p.ldx = N;
+  if (M <= 0 || N <= 0 || K <= 0 || (K % 64) != 0 || (N % 4) != 0) return 0;
+  // the operands an epilogue form needs, as the engines pass them (never dereferenced here): the dispatch asks whether
+  // gemm_bf16_v2 can run THIS form (gemm_bf16_v2_epi_ok), not only the shape
+  static char dummy[16];
+  if (epi == mc::EPI_RESID_CAPTURE) { p.X0 = (const bf16_t*)dummy; p.ldx0 = N; p.R = (float*)dummy; p.ldr = N; }
+  if (epi == mc::EPI_BF16_GELU_SPLIT) { p.n_split = N > 256 ? (N / 2) / 256 * 256 : 0; p.Cb2 = (bf16_t*)dummy; p.ldc2 = N; }
+  return mc::gemm_bf16_kernel_for(p, epi);
+}
+
+int mc_op_gemm_bf16_splitk(int M, int N, int K, int epi) {
+  mc::GemmParams p = gp(nullptr, K, nullptr, K, nullptr, M, N, K);
+  p.ldc = N; p.ldx = N;
+  p.splitk_ws = g_op_splitk_ws; p.splitk_ws_bytes = g_op_splitk_bytes;
+  if (M <= 0 || N <= 0 || K <= 0 || (mc::g_gemm_kernel != 0 && mc::g_gemm_kernel != 4)) return 1;
+  return mc::gemm_splitk_slices(p, epi);
+}
+
+size_t mc_op_gemm_splitk_need(int M, int N, int K, int epi) { return mc::gemm_splitk_ws_need(M, N, K, epi); }
+
+mc_status mc_op_set_splitk_workspace(void* ws_dev, size_t bytes) {
+  g_op_splitk_ws = (float*)ws_dev;
+  g_op_splitk_bytes = ws_dev ? bytes : 0;
+  return MC_OK;
+}
+
+mc_status mc_op_attention(const void* Q, long ldq, const void* K, long ldk, long kss, const void* V, long ldv,
+                          long vss, void* O, long ldo, int Lq_pad, int n_heads, int shard_rows, int shard_valid,
+                          int n_shards, float scale, mc_stream s) {
+  mc::AttnParams a;
+  memset(&a, 0, sizeof(a));
+  a.Q = (const bf16_t*)Q; a.ldq = ldq; a.K = (const bf16_t*)K; a.ldk = ldk; a.k_shard_stride = kss;
+  a.V = (const bf16_t*)V; a.ldv = ldv; a.v_shard_stride = vss; a.O = (bf16_t*)O; a.ldo = ldo;
+  a.Lq_pad = Lq_pad; a.n_heads = n_heads; a.shard_rows = shard_rows; a.shard_valid = shard_valid;
+  a.n_shards = n_shards; a.scale = scale;
+  hipError_t err = mc::launch_attention(a, (hipStream_t)s);
+  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "attention: unsupported shape");
+  HIP_TRY(err);
+  return MC_OK;
+}
+
+mc_status mc_op_quantize_rows_fp8(const void* x, mc_dtype dtype, long ldx, int M, int K, void* q, long ldq, float* scale,
+                                  mc_stream s) {
+  hipError_t err = mc::launch_quantize_rows_fp8(dtype == MC_BF16 ? (const bf16_t*)x : nullptr,
+                                                dtype == MC_F32 ? (const float*)x : nullptr, ldx, M, K, (uint8_t*)q, ldq,
+                                                scale, (hipStream_t)s);
+  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "quantize_rows_fp8: K, ldx, ldq must be multiples of 4");
+  HIP_TRY(err);
+  return MC_OK;
+}
+
+mc_status mc_op_gemm_fp8(const void* A, long lda, const float* a_scale, const void* W, long ldw, const float* w_scale,
+                         const float* bias, int M, int N, int K, int epi, void* Cb, long ldc, float* X, long ldx,
+                         const float* gate, mc_stream s) {
+  mc::GemmParams p = gp((const bf16_t*)A, lda, (const bf16_t*)W, ldw, bias, M, N, K);
+  p.a_scale = a_scale; p.w_scale = w_scale;
+  p.Cb = (bf16_t*)Cb; p.ldc = ldc; p.X = X; p.ldx = ldx; p.gate = gate;
+  hipError_t err = mc::launch_gemm_fp8(p, epi, (hipStream_t)s);
+  if (err == hipErrorInvalidValue)
+    return fail(MC_EINVAL, "gemm_fp8: needs N %% 256 == 0, K %% 256 == 0, K >= 512, lda/ldw %% 16 == 0, both scale vectors");
+  HIP_TRY(err);
+  return MC_OK;
+}
+
+mc_status mc_op_quantize_rows_mx(const void* x, mc_dtype dtype, long ldx, int M, int K, void* q, long ldq, void* scales,
+                                 long rows_pad, mc_stream s) {
+  hipError_t err = mc::launch_quantize_rows_mx(dtype == MC_BF16 ? (const bf16_t*)x : nullptr,
+                                               dtype == MC_F32 ? (const float*)x : nullptr, ldx, M, K, (uint8_t*)q, ldq,
+                                               (uint8_t*)scales, rows_pad, (hipStream_t)s);
+  if (err == hipErrorInvalidValue)
+    return fail(MC_EINVAL, "quantize_rows_mx: K %% 32 == 0, ldx %% 8 == 0, ldq %% 16 == 0, rows_pad >= M");
+  HIP_TRY(err);
+  return MC_OK;
+}
+
+mc_status mc_op_gemm_mxfp8(const void* A, long lda, const void* a_scales, long rows_pad_a, const void* W, long ldw,
+                           const void* w_scales, long rows_pad_w, const float* bias, int M, int N, int K, int epi, void* Cb,
+                           long ldc, float* X, long ldx, const float* gate, mc_stream s) {
+  mc::GemmParams p = gp((const bf16_t*)A, lda, (const bf16_t*)W, ldw, bias, M, N, K);
+  p.a_mx = (const uint8_t*)a_scales; p.mx_rows_a = rows_pad_a; p.w_mx = (const uint8_t*)w_scales; p.mx_rows_w = rows_pad_w;
+  p.Cb = (bf16_t*)Cb; p.ldc = ldc; p.X = X; p.ldx = ldx; p.gate = gate;
+  hipError_t err = mc::launch_gemm_mxfp8(p, epi, (hipStream_t)s);
+  if (err == hipErrorInvalidValue)
+    return fail(MC_EINVAL, "gemm_mxfp8: needs N %% 256 == 0, K %% 256 == 0, K >= 512, lda/ldw %% 16 == 0, block scales with "
+                           "rows_pad_a >= M rounded up to 256, rows_pad_w >= N, both multiples of 4");
+  HIP_TRY(err);
+  return MC_OK;
+}
+
+mc_status mc_op_attention_partial(const void* Q, long ldq, const void* K, long ldk, long kss, const void* V, long ldv,
+                                  long vss, void* O, long ldo, int Lq_pad, int n_heads, int shard_rows,
+                                  int shard_valid, int n_shards, float scale, int skip_shard, float* lse_out,
+                                  const float* lse_in, mc_stream s) {
+  mc::AttnParams a;
+  memset(&a, 0, sizeof(a));
+  a.Q = (const bf16_t*)Q; a.ldq = ldq; a.K = (const bf16_t*)K; a.ldk = ldk; a.k_shard_stride = kss;
+  a.V = (const bf16_t*)V; a.ldv = ldv; a.v_shard_stride = vss; a.O = (bf16_t*)O; a.ldo = ldo;
+  a.Lq_pad = Lq_pad; a.n_heads = n_heads; a.shard_rows = shard_rows; a.shard_valid = shard_valid;
+  a.n_shards = n_shards; a.scale = scale;
+  a.skip_shard_p1 = skip_shard >= 0 ? skip_shard + 1 : 0; a.lse_out = lse_out; a.lse_in = lse_in;
+  hipError_t err = mc::launch_attention(a, (hipStream_t)s);
+  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "attention: unsupported shape / shard selection");
+  HIP_TRY(err);
+  return MC_OK;
+}
+
+mc_status mc_op_attn_merge(const void* const* o_parts, const float* const* lse_parts, int n, void* out, long ldo, int rows,
+                           int rows_pad, int d, mc_stream s) {
+  if (!o_parts || !lse_parts || !out) return fail(MC_EINVAL, "attn_merge: null argument");
+  hipError_t err = mc::launch_attn_merge((const bf16_t* const*)o_parts, lse_parts, n, (bf16_t*)out, ldo, rows, rows_pad, d,
+                                         (hipStream_t)s);
+  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "attn_merge: 1..9 parts, d a multiple of 128, 16-byte rows");
+  HIP_TRY(err);
+  return MC_OK;
+}
+
+mc_status mc_op_ln_modulate(const float* x, long ldx, const void* x0, long ldx0, const float* sc, const float* sh,
+                            int mode, float eps, void* out, long ldo, float* out_f32, long ldof, int M, int D,
+                            mc_stream s) {
+  hipError_t err = mc::launch_ln_modulate(x, ldx, (const bf16_t*)x0, ldx0, sc, sh, mode, eps, (bf16_t*)out, ldo,
+                                          out_f32, ldof, M, D, (hipStream_t)s);
+  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "ln_modulate: unsupported D=%d", D);
+  HIP_TRY(err);
+  return MC_OK;
+}
+
+mc_status mc_op_rmsnorm_rope(void* x, long ldx, const float* w, float eps, const float* cs, int cs_row0, int M, int D,
+                             mc_stream s) {
+  hipError_t err = mc::launch_rmsnorm_rope((bf16_t*)x, ldx, w, eps, cs, cs_row0, M, D, (hipStream_t)s);
+  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "rmsnorm_rope: unsupported D=%d", D);
+  HIP_TRY(err);
+  return MC_OK;
+}
+
+mc_status mc_op_skip_add(const void* x0, long ldx0, const float* r, long ldr, float* out, long ldo, int M, int D,
+                         mc_stream s) {
+  hipError_t err = mc::launch_skip_add((const bf16_t*)x0, ldx0, r, ldr, out, ldo, M, D, (hipStream_t)s);
+  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "skip_add: unsupported shape");
+  HIP_TRY(err);
+  return MC_OK;
+}
+
+mc_status mc_op_residual_sub(const float* x, long ldx, const void* x0, long ldx0, float* r, long ldr, int M, int D,
+                             mc_stream s) {
+  hipError_t err = mc::launch_residual_sub(x, ldx, (const bf16_t*)x0, ldx0, r, ldr, M, D, (hipStream_t)s);
+  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "residual_sub: unsupported shape");
+  HIP_TRY(err);
+  return MC_OK;
+}
+
+mc_status mc_op_calib_stats(const float* r, long ldr, const float* rp, long ldrp, int M, int D, double* partial,
+                            int n_blocks, double* sums, float* stats, mc_stream s) {
+  hipError_t err = mc::launch_calib_stats(r, ldr, rp, ldrp, M, D, partial, n_blocks, sums, stats, (hipStream_t)s);
+  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "calib_stats: unsupported shape");
+  HIP_TRY(err);
+  return MC_OK;
+}
+
+mc_status mc_op_cfg_euler(const float* cond, const float* uncond, float guide, float dt, float* x, float* eps_out,
+                          size_t n, mc_stream s) {
+  HIP_TRY(mc::launch_cfg_euler(cond, uncond, guide, dt, x, eps_out, n, (hipStream_t)s));
+  return MC_OK;
+}
+
+mc_status mc_op_cfg_norm_euler(const float* cond, const float* uncond, long ld_pred, float guide, float dt, float* x, long ldx,
+                               int n_rows, int C, mc_stream s) {
+  if (!cond || !uncond || !x) return fail(MC_EINVAL, "null argument");
+  hipError_t err = mc::launch_cfg_norm_euler(cond, uncond, ld_pred, guide, dt, x, ldx, n_rows, C, (hipStream_t)s);
+  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "cfg_norm_euler: 0 < C <= 256, ld_pred / ldx >= C, n_rows >= 0");
+  HIP_TRY(err);
+  return MC_OK;
+}
+
+mc_status mc_op_rmsnorm_rows_bf16(const float* x, long ldx, const float* w, float eps, void* out, long ldo, int rows_valid,
+                                  int rows, int D, mc_stream s) {
+  if (!x || !w || !out) return fail(MC_EINVAL, "null argument");
+  hipError_t err = mc::launch_rmsnorm_rows_bf16(x, ldx, w, eps, (bf16_t*)out, ldo, rows_valid, rows, D, (hipStream_t)s);
+  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "rmsnorm_rows_bf16: D, ldx, ldo multiples of 4, 0 <= rows_valid <= rows");
+  HIP_TRY(err);
+  return MC_OK;
+}
+
+mc_status mc_op_lincomb(const float* const* xs_dev, const float* coef, int k, float* out_dev, size_t n, mc_stream s) {
+  if (!xs_dev || !coef) return fail(MC_EINVAL, "null argument");
+  hipError_t err = mc::launch_lincomb(xs_dev, coef, k, out_dev, n, (hipStream_t)s);
+  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "lincomb: 1..6 operands, non-empty output");
+  HIP_TRY(err);
+  return MC_OK;
+}
+
+mc_status mc_op_cast_bf16(const float* src, void* dst, size_t n, mc_stream s) {
+  HIP_TRY(mc::launch_cast_bf16(src, (bf16_t*)dst, n, (hipStream_t)s));
+  return MC_OK;
+}
+
+mc_status mc_set_option(const char* key, int value) {
+  if (!key) return fail(MC_EINVAL, "null key");
+  const std::string k(key);
+  if (k == "gemm_kernel") {
+    if ((value < 0 || value > 2) && value != 4)
+      return fail(MC_EINVAL, "gemm_kernel must be 0 (by shape), 1 (128x128), 2 (256x256, 8 waves) or 4 (256x256, 4 waves, generated stream)");
+    if (value == 2 && !mc::gemm_bf16_big_linked())
+      return fail(MC_EINVAL, "gemm_kernel 2: the 8-wave reference kernel is not in this library (round 6: it lives in the "
+                             "test-only libmagcache_hip_ref.so, magcache_amd.build.build_ref())");
+    mc::g_gemm_kernel = value;
+  } else if (k == "sp_attn_partials") {
+    if (value < 0 || value > 2)
+      return fail(MC_EINVAL, "sp_attn_partials must be 0 (chain on one stream), 1 (independent launches on two streams + merge where a launch "
+                             "does not fill the chip in whole waves) or 2 (always)");
+    mc::g_sp_attn_partials = value;
+  } else if (k == "gemm_splitk") {
+    if (value < 0 || value > 16) return fail(MC_EINVAL, "gemm_splitk must be 0 (never), 1 (by shape) or 2..16 (that many K slices wherever valid)");
+    mc::g_gemm_splitk = value;
+  } else if (k == "gemm_v2_max_grid") {
+    if (value < 0 || value > 4096) return fail(MC_EINVAL, "gemm_v2_max_grid must be 0 (= the CUs) or a workgroup count");
+    mc::g_gemm_v2_max_grid = value;
+  } else if (k == "gemm_defer") {
+    if (value != 0 && value != 1) return fail(MC_EINVAL, "gemm_defer must be 0 (residual epilogues in place) or 1 (deferred into the next tile's main loop)");
+    mc::g_gemm_defer = value;
+  } else if (k == "fp8_fused_quant") {
+    if (value != 0 && value != 1) return fail(MC_EINVAL, "fp8_fused_quant must be 0 (separate quantise passes) or 1 (fused into the producers)");
+    mc::g_fp8_fused_quant = value;
+  } else if (k == "attn_kernel") {
+    if (value != 0 && value != 3 && value != 5)
+      return fail(MC_EINVAL, "attn_kernel must be 0 (default), 3 (8 waves x 32 rows) or 5 (4 waves x 64 rows, hand-scheduled)");
+    mc::g_attn_kernel = value;
+  } else if (k == "mmdit_two_streams") {
+    if (value < -1 || value > 6) return fail(MC_EINVAL, "mmdit_two_streams must be -1 (by shape), 0, 1 or a diagnostic mode 2..6");
+    mc::g_mmdit_two_streams = value;
+  } else {
+    return fail(MC_EINVAL, "unknown option '%s'", key);
+  }
+  return MC_OK;
+}
+
+}  // extern "C"

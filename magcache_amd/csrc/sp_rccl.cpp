@@ -14,26 +14,15 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <vector>
 
-#include "../../include/magcache_hip.h"
+#include "host.h"
 
-namespace mc {
-mc_status set_error_v(mc_status s, const char* fmt, va_list ap);   // engine.cpp: the text mc_last_error() reports
-}
+using mc::fail;   // the text mc_last_error() reports
 
 namespace {
-
-mc_status failf(mc_status s, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  s = mc::set_error_v(s, fmt, ap);
-  va_end(ap);
-  return s;
-}
 
 struct Rccl {
   void* h = nullptr;
@@ -62,10 +51,10 @@ mc_status load_rccl() {
     for (const char* n : more)
       if (n && (h = dlopen(n, RTLD_NOW | RTLD_GLOBAL))) { snprintf(g_rccl.where, sizeof(g_rccl.where), "%s", n); break; }
   }
-  if (!h) return failf(MC_ESTATE, "librccl not found (dlopen: %s); set MAGCACHE_RCCL_LIB", dlerror());
+  if (!h) return fail(MC_ESTATE, "librccl not found (dlopen: %s); set MAGCACHE_RCCL_LIB", dlerror());
 #define SYM(f)                                                                                  \
   g_rccl.f = (decltype(g_rccl.f))dlsym(h, "nccl" #f);                                           \
-  if (!g_rccl.f) return failf(MC_ESTATE, "librccl (%s) lacks nccl" #f, g_rccl.where)
+  if (!g_rccl.f) return fail(MC_ESTATE, "librccl (%s) lacks nccl" #f, g_rccl.where)
   SYM(GetUniqueId); SYM(CommInitRank); SYM(CommDestroy); SYM(AllGather); SYM(AllReduce); SYM(GetErrorString); SYM(GetVersion);
 #undef SYM
   g_rccl.h = h;
@@ -75,12 +64,7 @@ mc_status load_rccl() {
 #define NCCL_TRY(expr)                                                                                          \
   do {                                                                                                          \
     ncclResult_t _r = (expr);                                                                                   \
-    if (_r != ncclSuccess) return failf(MC_EHIP, "%s failed: %s (%s:%d)", #expr, g_rccl.GetErrorString(_r), __FILE__, __LINE__); \
-  } while (0)
-#define HIP_TRY(expr)                                                                                           \
-  do {                                                                                                          \
-    hipError_t _e = (expr);                                                                                     \
-    if (_e != hipSuccess) return failf(MC_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
+    if (_r != ncclSuccess) return fail(MC_EHIP, "%s failed: %s (%s:%d)", #expr, g_rccl.GetErrorString(_r), __FILE__, __LINE__); \
   } while (0)
 
 }  // namespace
@@ -105,14 +89,14 @@ namespace {
 mc_status bind_engine(mc_sp_comm* c, mc_engine* e) {
   size_t off = 0, bytes = 0, off_g = 0, bytes_g = 0;
   char* base = (char*)mc_workspace_base(e);
-  if (!base) return failf(MC_ESTATE, "mc_set_workspace must run first");
+  if (!base) return fail(MC_ESTATE, "mc_set_workspace must run first");
   if (mc_status st = mc_buffer_info(e, "kv_local", &off, &bytes); st != MC_OK) return st;
   if (mc_status st = mc_buffer_info(e, "kv_gather", &off_g, &bytes_g); st != MC_OK) return st;
   int rows = 0, nr = 0, dim = 0, sp = 0;
   if (mc_status st = mc_sp_round_info(e, 0, &nr, &rows, nullptr); st != MC_OK) return st;
   if (mc_status st = mc_sp_geometry(e, nullptr, nullptr, nullptr, nullptr, &dim, &sp); st != MC_OK) return st;
-  if (nr < 1) return failf(MC_ESTATE, "the engine is not sequence parallel (sp_size 1)");
-  if (sp != c->nranks) return failf(MC_EINVAL, "communicator of %d ranks on an engine with sp_size %d", c->nranks, sp);
+  if (nr < 1) return fail(MC_ESTATE, "the engine is not sequence parallel (sp_size 1)");
+  if (sp != c->nranks) return fail(MC_EINVAL, "communicator of %d ranks on an engine with sp_size %d", c->nranks, sp);
   c->e = e; c->kv_local = base + off; c->kv_gather = base + off_g;
   c->d2 = 2 * dim;
   c->n_rounds = nr; c->chunk_rows = rows;
@@ -149,7 +133,7 @@ extern "C" {
 int mc_sp_rccl_available(void) { return load_rccl() == MC_OK ? 1 : 0; }
 
 mc_status mc_sp_comm_id(void* id_out) {
-  if (!id_out) return failf(MC_EINVAL, "null id");
+  if (!id_out) return fail(MC_EINVAL, "null id");
   if (mc_status st = load_rccl(); st != MC_OK) return st;
   ncclUniqueId id;
   NCCL_TRY(g_rccl.GetUniqueId(&id));
@@ -159,14 +143,14 @@ mc_status mc_sp_comm_id(void* id_out) {
 }
 
 mc_status mc_sp_comm_create(const void* id_in, int nranks, int rank, mc_sp_comm** out) {
-  if (!id_in || !out || nranks < 1 || rank < 0 || rank >= nranks) return failf(MC_EINVAL, "bad communicator arguments");
+  if (!id_in || !out || nranks < 1 || rank < 0 || rank >= nranks) return fail(MC_EINVAL, "bad communicator arguments");
   if (mc_status st = load_rccl(); st != MC_OK) return st;
   ncclUniqueId id;
   memcpy(&id, id_in, sizeof(id));
   mc_sp_comm* c = new mc_sp_comm();
   c->nranks = nranks; c->rank = rank;
   ncclResult_t r = g_rccl.CommInitRank(&c->comm, nranks, id, rank);      // on the calling thread's current device
-  if (r != ncclSuccess) { delete c; return failf(MC_EHIP, "ncclCommInitRank(%d ranks, rank %d): %s", nranks, rank, g_rccl.GetErrorString(r)); }
+  if (r != ncclSuccess) { delete c; return fail(MC_EHIP, "ncclCommInitRank(%d ranks, rank %d): %s", nranks, rank, g_rccl.GetErrorString(r)); }
   int lo = 0, hi = 0;
   (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
   // highest priority: the collective's few workgroups must get their CUs between the attention workgroups queued behind them
@@ -174,7 +158,7 @@ mc_status mc_sp_comm_create(const void* id_in, int nranks, int rank, mc_sp_comm*
   hipError_t e2 = hipEventCreateWithFlags(&c->ready, hipEventDisableTiming);
   if (e1 != hipSuccess || e2 != hipSuccess) {
     mc_sp_comm_destroy(c);
-    return failf(MC_EHIP, "stream / event for the communicator: %s", hipGetErrorString(e1 != hipSuccess ? e1 : e2));
+    return fail(MC_EHIP, "stream / event for the communicator: %s", hipGetErrorString(e1 != hipSuccess ? e1 : e2));
   }
   *out = c;
   return MC_OK;
@@ -200,7 +184,7 @@ const char* mc_sp_comm_info(const mc_sp_comm* c) {
 
 mc_status mc_blocks_sp_rccl(mc_engine* e, mc_sp_comm* c, int layer_begin, int layer_end, int branch, mc_mode mode, int overlap,
                             mc_stream stream) {
-  if (!e || !c) return failf(MC_EINVAL, "null argument");
+  if (!e || !c) return fail(MC_EINVAL, "null argument");
   if (mc_status st = bind_engine(c, e); st != MC_OK) return st;     // cheap; follows mc_sp_set_chunks
   c->rc = 0;
   return mc_blocks_sp(e, layer_begin, layer_end, branch, mode, overlap, gather_cb, c, stream);
@@ -209,7 +193,7 @@ mc_status mc_blocks_sp_rccl(mc_engine* e, mc_sp_comm* c, int layer_begin, int la
 mc_status mc_forward_sp_rccl(mc_engine* e, mc_sp_comm* c, const float* latent_dev, const float* t_dev, double t_host,
                              const void* context_dev, mc_dtype ctx_dtype, int ctx_len, int branch, mc_mode mode, int overlap,
                              float* tokens_full_dev, float* out_dev, mc_stream stream) {
-  if (!e || !c || !tokens_full_dev || !out_dev) return failf(MC_EINVAL, "null argument");
+  if (!e || !c || !tokens_full_dev || !out_dev) return fail(MC_EINVAL, "null argument");
   hipStream_t s = (hipStream_t)stream;
   mc_status st = mc_embed(e, latent_dev, t_dev, t_host, context_dev, ctx_dtype, ctx_len, stream);
   if (st != MC_OK) return st;
