@@ -436,6 +436,12 @@ mc_status mc_op_skip_add(const void* x0_bf16_dev, long ldx0, const float* r_dev,
                          int M, int D, mc_stream stream);
 mc_status mc_op_residual_sub(const float* x_dev, long ldx, const void* x0_bf16_dev, long ldx0, float* r_dev,
                              long ldr, int M, int D, mc_stream stream);
+/* x[m, :] += s[m, :] for m < rows: a ControlNet sample (fp32 or bf16, contiguous [rows, D], widened exactly) added to rows
+ * of an fp32 stream, bitwise x + float(s).  r_dev != NULL is a second destination in the same pass: r += s, or, with
+ * x0_bf16_dev != NULL, r = x_new - x0 (the MagCache residual taken after the add).  MC_EINVAL for D % 8 != 0 or a pointer
+ * that is not 16-byte aligned. */
+mc_status mc_op_add_rows(float* x_dev, long ldx, const void* s_dev, mc_dtype s_dtype, float* r_dev, long ldr,
+                         const void* x0_bf16_dev, long ldx0, int rows, int D, mc_stream stream);
 /* One launch: per-token ratios + the cross-block reduction by the last block to arrive.  partial_dev: 4*n_blocks + 1
  * doubles of scratch whose LAST 8 bytes (the arrival ticket) must be zero before the first call -- the kernel rearms it;
  * sums_dev: 4 doubles (sum rho, sum rho^2, sum 1-cos, count); stats_dev: 3 floats or NULL */

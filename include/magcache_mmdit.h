@@ -14,7 +14,8 @@
  *                 MagCache4QwenImageEdit/magcache_generate.py (same functions, more image tokens)
  * Everything those functions do between their arguments and their return value is one mc_mmdit_forward call; the
  * decision rule stays on the host (scalar state, `<=`, the FLUX step-11 exclusion: see mc_rule_* in magcache_hip.h
- * and magcache_amd/mmdit.py).  The transformer blocks themselves are upstream code (huggingface/diffusers
+ * and magcache_amd/mmdit.py).  FLUX's ControlNet arguments (:374-384, :416-423) are set ahead of the forward with
+ * mc_mmdit_set_controlnet.  The transformer blocks themselves are upstream code (huggingface/diffusers
  * transformer_flux.py, Tencent/HunyuanVideo hyvideo/modules/models.py); the weight names below are the upstream
  * state_dict names.
  *
@@ -84,6 +85,23 @@ int mc_mmdit_weights_missing(const mc_mmdit* e, char* buf, size_t buflen);
  * text row j at QwenEmbedRope position max(h/2, w/2) + j, so a shorter call uses its first txt_valid rows);
  * HunyuanVideo: n_rows = img_tokens. */
 mc_status mc_mmdit_set_rope(mc_mmdit* e, const float* cos_dev, const float* sin_dev, int n_rows, mc_stream stream);
+
+/* FLUX ControlNet residuals (the reference keeps upstream's controlnet_block_samples, controlnet_single_block_samples and
+ * controlnet_blocks_repeat, MagCache4FLUX/magcache_flux.py:374-384 and :416-423; the ControlNet itself is the caller's).
+ * Every sample is a caller-owned device tensor [img_tokens, dim] of `dtype` (16-byte aligned; always the FULL tensor, like
+ * img_dev: a sequence-parallel rank reads its own rows).  The engine keeps the two pointer lists, not the samples: they are
+ * read by every following MC_MODE_FULL / MC_MODE_CALIB forward until the next call; (NULL, 0, NULL, 0, ..) clears them.
+ * With n blocks and m samples, block i adds sample i / ceil(n / m) to its image rows after the block (text rows untouched);
+ * blocks_repeat: double block i adds sample i % m (the single blocks keep the first rule).  m > n is refused.  A sample
+ * on the last block is part of the cached residual and of the calibration statistics (the residual is x_final - x0,
+ * taken after the add); MC_MODE_SKIP runs no block and adds nothing.  One extra launch per block that has a sample, none
+ * otherwise.  MC_FAMILY_FLUX only. */
+mc_status mc_mmdit_set_controlnet(mc_mmdit* e, const void* const* double_samples_dev, int n_double_samples,
+                                  const void* const* single_samples_dev, int n_single_samples, mc_dtype dtype,
+                                  int blocks_repeat);
+/* the index rule alone (host arithmetic): the sample block `block` of n_blocks adds, or -1 where mc_mmdit_set_controlnet
+ * refuses the pair (n_samples > n_blocks, or an index past the list).  blocks_repeat applies to double blocks only. */
+int mc_mmdit_controlnet_index(int n_blocks, int n_samples, int block, int blocks_repeat);
 
 /* One transformer evaluation (the body of the reference's magcache_forward).
  *   img_dev    FLUX: packed latent tokens [img_tokens, in_channels]; HunyuanVideo: latent [16, F, H, W]   (fp32)

@@ -122,6 +122,7 @@ SIGNATURES = {
     "mc_op_cfg_norm_euler": (_i, [_vp, _vp, _l, _f, _f, _vp, _l, _i, _i, _vp]),
     "mc_op_rmsnorm_rows_bf16": (_i, [_vp, _l, _vp, _f, _vp, _l, _i, _i, _i, _vp]),
     "mc_op_lincomb": (_i, [_vp, _vp, _i, _vp, _sz, _vp]),
+    "mc_op_add_rows": (_i, [_vp, _l, _vp, _i, _vp, _l, _vp, _l, _i, _i, _vp]),
     "mc_op_rope_table": (_i, [_i, _i, _i, _i, _i, _vp]),
     # include/magcache_mmdit.h
     "mc_mmdit_create": (_i, [_vp, C.POINTER(_vp)]),
@@ -132,6 +133,8 @@ SIGNATURES = {
     "mc_mmdit_set_weight": (_i, [_vp, C.c_char_p, _vp, _i, C.POINTER(C.c_int64), _i, _vp]),
     "mc_mmdit_weights_missing": (_i, [_vp, C.c_char_p, _sz]),
     "mc_mmdit_set_rope": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "mc_mmdit_set_controlnet": (_i, [_vp, _vp, _i, _vp, _i, _i, _i]),
+    "mc_mmdit_controlnet_index": (_i, [_i, _i, _i, _i]),
     "mc_mmdit_forward": (_i, [_vp, _vp, _d, _d, _vp, _i, _vp, _i, _vp, _vp]),
     "mc_mmdit_forward2": (_i, [_vp, _vp, _d, _d, _vp, _i, _vp, _i, _i, _vp, _vp]),
     "mc_mmdit_begin": (_i, [_vp, _vp, _d, _d, _vp, _i, _vp, _i, _vp]),

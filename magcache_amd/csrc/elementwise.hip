@@ -611,6 +611,48 @@ __global__ void add_bf16_kernel(bf16_t* __restrict__ a, const bf16_t* __restrict
   }
 }
 
+// x[row, :] += s[row, :] over rows [0, rows): a ControlNet sample added to image rows of the fp32 residual stream.
+// s is fp32 or bf16 (widened exactly), contiguous [rows, D]; one fp32 add per element, so x is bitwise x + float(s).
+// r != null is a second destination written in the same pass: r += s, or -- x0 != null -- r = x_new - x0 (x0 bf16),
+// the MagCache residual as the reference takes it AFTER the add.  One thread = 8 columns: 16-byte loads and stores.
+template <bool S_BF16>
+__global__ __launch_bounds__(256) void add_rows_kernel(float* x, long ldx, const void* __restrict__ s_, float* r, long ldr,
+                                                       const bf16_t* __restrict__ x0, long ldx0, uint32_t total,
+                                                       uint32_t per_row) {
+  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
+    const uint32_t row = i / per_row, c = (i - row * per_row) * 8;
+    const size_t so = (size_t)row * per_row * 8 + c;
+    f32x4 a, b;
+    if constexpr (S_BF16) {
+      const u32x4 t = *(const u32x4*)((const bf16_t*)s_ + so);
+      a = f32x4{__uint_as_float(t[0] << 16), __uint_as_float(t[0] & 0xffff0000u), __uint_as_float(t[1] << 16),
+                __uint_as_float(t[1] & 0xffff0000u)};
+      b = f32x4{__uint_as_float(t[2] << 16), __uint_as_float(t[2] & 0xffff0000u), __uint_as_float(t[3] << 16),
+                __uint_as_float(t[3] & 0xffff0000u)};
+    } else {
+      a = *(const f32x4*)((const float*)s_ + so);
+      b = *(const f32x4*)((const float*)s_ + so + 4);
+    }
+    float* xp = x + (size_t)row * ldx + c;
+    const f32x4 xa = *(const f32x4*)xp + a, xb = *(const f32x4*)(xp + 4) + b;
+    *(f32x4*)xp = xa;
+    *(f32x4*)(xp + 4) = xb;
+    if (r) {
+      float* rp = r + (size_t)row * ldr + c;
+      if (x0) {
+        const u32x4 o = *(const u32x4*)(x0 + (size_t)row * ldx0 + c);
+        *(f32x4*)rp = xa - f32x4{__uint_as_float(o[0] << 16), __uint_as_float(o[0] & 0xffff0000u),
+                                 __uint_as_float(o[1] << 16), __uint_as_float(o[1] & 0xffff0000u)};
+        *(f32x4*)(rp + 4) = xb - f32x4{__uint_as_float(o[2] << 16), __uint_as_float(o[2] & 0xffff0000u),
+                                       __uint_as_float(o[3] << 16), __uint_as_float(o[3] & 0xffff0000u)};
+      } else {
+        *(f32x4*)rp = *(const f32x4*)rp + a;
+        *(f32x4*)(rp + 4) = *(const f32x4*)(rp + 4) + b;
+      }
+    }
+  }
+}
+
 // out = sum_i a[i] * x[i] over up to 6 fp32 operands (null operands skipped; out may alias an operand):
 // the multistep solver updates (UniPC / DPM++ predictor and corrector, CFG combine) in one pass
 struct LinComb {
@@ -838,6 +880,24 @@ hipError_t launch_token_t_prepare(const float* t, int n_all, int row0, int n_row
 hipError_t launch_add_bf16(bf16_t* a, const bf16_t* b, size_t n, hipStream_t stream) {
   if (n % 8) return hipErrorInvalidValue;
   hipLaunchKernelGGL(add_bf16_kernel, dim3(grid_for((long)(n / 8), 256)), dim3(256), 0, stream, a, b, n / 8);
+  return hipGetLastError();
+}
+
+hipError_t launch_add_rows(float* x, long ldx, const void* s, int s_bf16, float* r, long ldr, const bf16_t* x0, long ldx0,
+                           int rows, int D, hipStream_t stream) {
+  auto misaligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
+  if (!x || !s || rows < 0 || D <= 0 || (D % 8) != 0 || ldx < D || (ldx % 4) != 0 || misaligned(x) || misaligned(s))
+    return hipErrorInvalidValue;
+  if (r && (ldr < D || (ldr % 4) != 0 || misaligned(r))) return hipErrorInvalidValue;
+  if (x0 && (!r || ldx0 < D || (ldx0 % 8) != 0 || misaligned(x0))) return hipErrorInvalidValue;
+  if ((long)rows * (D / 8) >= (1l << 31)) return hipErrorInvalidValue;
+  if (rows == 0) return hipSuccess;
+  const uint32_t per_row = (uint32_t)(D / 8), total = (uint32_t)rows * per_row;
+  const dim3 grid(grid_for((long)total, 256));
+  if (s_bf16)
+    hipLaunchKernelGGL(add_rows_kernel<true>, grid, dim3(256), 0, stream, x, ldx, s, r, ldr, x0, ldx0, total, per_row);
+  else
+    hipLaunchKernelGGL(add_rows_kernel<false>, grid, dim3(256), 0, stream, x, ldx, s, r, ldr, x0, ldx0, total, per_row);
   return hipGetLastError();
 }
 

@@ -99,6 +99,10 @@ struct mc_mmdit {
   mc::Workspace work;
   int res_cur[2] = {0, 0};  // per CFG branch: the slot (of the branch's own) holding residual_cache / previous_residual
   bool have_res[2] = {false, false}, have_stats = false, pads_clean = false;
+  // ControlNet residuals (mc_mmdit_set_controlnet, FLUX): caller-owned [img_tokens, d] samples; host pointer lists only
+  std::vector<const void*> cn_double, cn_single;
+  mc_dtype cn_dtype = MC_F32;
+  bool cn_repeat = false;
 
   template <class T>
   T* buf(const char* name) const { return work.get<T>(name); }
@@ -806,9 +810,66 @@ mc_status begin_impl(mc_mmdit* e, const float* img_dev, double timestep, double 
   return MC_OK;
 }
 
+// ControlNet (flux :374-384, :416-423): the sample block `blk` adds to its image rows, or null (the lists were checked
+// against mc_mmdit_controlnet_index when they were set; blocks_repeat is a rule of the double blocks only)
+const void* controlnet_sample(const mc_mmdit* e, int blk) {
+  const bool dbl = blk < e->cfg.n_double;
+  const std::vector<const void*>& v = dbl ? e->cn_double : e->cn_single;
+  if (v.empty()) return nullptr;
+  return dbl ? v[mc_mmdit_controlnet_index(e->cfg.n_double, (int)v.size(), blk, e->cn_repeat)]
+             : v[mc_mmdit_controlnet_index(e->cfg.n_single, (int)v.size(), blk - e->cfg.n_double, 0)];
+}
+
+// x_img += sample rows of this rank.  The LAST block's output GEMM then leaves the residual capture to this launch
+// (with_capture): the reference takes hidden_states - ori AFTER the add (:426), and (x + s) - x0 is not (x - x0) + s in
+// fp32, so the kernel writes R = x_new - x0 itself.
+mc_status controlnet_add(const mc_mmdit* e, const void* sample, bool with_capture, hipStream_t s) {
+  const int d = e->d;
+  const size_t elem = e->cn_dtype == MC_BF16 ? 2 : 4;
+  const void* rows = static_cast<const char*>(sample) + (size_t)e->tok0 * d * elem;
+  HIP_TRY(mc::launch_add_rows(e->buf<float>("x") + (size_t)e->img0 * d, d, rows, e->cn_dtype == MC_BF16,
+                              with_capture ? e->residual(e->dst, e->branch) : nullptr, d,
+                              with_capture ? e->buf<bf16_t>("x0") + (size_t)e->img0 * d : nullptr, d, e->Li, d, s));
+  return MC_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int mc_mmdit_controlnet_index(int n_blocks, int n_samples, int block, int blocks_repeat) {
+  if (n_blocks <= 0 || n_samples <= 0 || n_samples > n_blocks || block < 0 || block >= n_blocks) return -1;
+  const int k = blocks_repeat ? block % n_samples : block / ((n_blocks + n_samples - 1) / n_samples);
+  return k < n_samples ? k : -1;   // the reference raises IndexError past the end of its list
+}
+
+mc_status mc_mmdit_set_controlnet(mc_mmdit* e, const void* const* double_samples_dev, int n_double_samples,
+                                  const void* const* single_samples_dev, int n_single_samples, mc_dtype dtype,
+                                  int blocks_repeat) {
+  if (!e) return fail(MC_EINVAL, "null engine");
+  if (e->cfg.family != MC_FAMILY_FLUX) return fail(MC_EINVAL, "ControlNet residuals are a FLUX input; this engine is another family");
+  if (e->begun) return fail(MC_ESTATE, "mc_mmdit_set_controlnet between mc_mmdit_begin and mc_mmdit_end");
+  if (dtype != MC_F32 && dtype != MC_BF16) return fail(MC_EINVAL, "ControlNet samples are fp32 or bf16");
+  const void* const* lists[2] = {double_samples_dev, single_samples_dev};
+  const int counts[2] = {n_double_samples, n_single_samples}, blocks[2] = {e->cfg.n_double, e->cfg.n_single};
+  for (int k = 0; k < 2; ++k) {
+    const int m = counts[k], n = blocks[k];
+    const char* what = k ? "single" : "double";
+    if (m < 0 || (m > 0 && !lists[k])) return fail(MC_EINVAL, "ControlNet: %d %s samples with a null list", m, what);
+    if (m > n) return fail(MC_EINVAL, "ControlNet: %d samples for %d %s blocks", m, n, what);
+    for (int i = 0; i < n && m > 0; ++i)
+      if (mc_mmdit_controlnet_index(n, m, i, k == 0 && blocks_repeat) < 0)
+        return fail(MC_EINVAL, "ControlNet: %d samples leave %s block %d of %d without one", m, what, i, n);
+    for (int i = 0; i < m; ++i)
+      if (!lists[k][i] || (reinterpret_cast<uintptr_t>(lists[k][i]) & 15))
+        return fail(MC_EINVAL, "ControlNet: %s sample %d is null or not 16-byte aligned", what, i);
+  }
+  e->cn_double.assign(double_samples_dev, double_samples_dev + n_double_samples);
+  e->cn_single.assign(single_samples_dev, single_samples_dev + n_single_samples);
+  e->cn_dtype = dtype;
+  e->cn_repeat = blocks_repeat != 0;
+  return MC_OK;
+}
 
 mc_status mc_mmdit_begin(mc_mmdit* e, const float* img_dev, double timestep, double guidance, const float* txt_dev,
                          int txt_valid, const float* vec_dev, mc_mode mode, mc_stream stream) {
@@ -955,14 +1016,16 @@ mc_status mc_mmdit_block_post(mc_mmdit* e, int blk, mc_stream stream_) {
     }
   }
   const bool last = (blk == nb - 1);
+  const void* cn = (e->cn_double.empty() && e->cn_single.empty()) ? nullptr : controlnet_sample(e, blk);
+  const bool capture = last && !cn;   // a sample on the last block: controlnet_add captures after its add
   if (blk < c.n_double && double_block_merged(e)) {
-    MC_TRY(double_post_merged(e, blk, emod, s, last ? e->residual_joint(e->dst, e->branch) : nullptr));
+    MC_TRY(double_post_merged(e, blk, emod, s, capture ? e->residual_joint(e->dst, e->branch) : nullptr));
   } else if (blk < c.n_double) {
     MC_TRY(run_two(
         e, s, g_mmdit_two_streams > 2 ? 0 : g_mmdit_two_streams,
         [&](hipStream_t q) {
           return stream_post_attn(e, e->dimg[blk], emod + e->mod_double(blk, 0), e->img0, Li, q,
-                                  last ? e->residual_joint(e->dst, e->branch) : nullptr);
+                                  capture ? e->residual_joint(e->dst, e->branch) : nullptr);
         },
         [&](hipStream_t q) { return stream_post_attn(e, e->dtxt[blk], emod + e->mod_double(blk, 1), e->txt0, Lt, q); }));
   } else {
@@ -971,13 +1034,14 @@ mc_status mc_mmdit_block_post(mc_mmdit* e, int blk, mc_stream stream_) {
     const float* m = emod + e->mod_single(i);
     mc::GemmParams o = gp(e->buf<bf16_t>("am"), 5 * d, g.w_out, 5 * d, g.b_out, S, d, 5 * d);
     o.X = e->buf<float>("x"); o.ldx = d; o.gate = m + 2 * d;
-    if (last) {   // MagCache residual capture (flux :428, hunyuan :140); the text rows of R are scratch
-      o.X0 = e->buf<bf16_t>("x0"); o.ldx0 = d; o.R = e->residual_joint(e->dst); o.ldr = d;
+    if (capture) {   // MagCache residual capture (flux :428, hunyuan :140); the text rows of R are scratch
+      o.X0 = e->buf<bf16_t>("x0"); o.ldx0 = d; o.R = e->residual_joint(e->dst, e->branch); o.ldr = d;
       HIP_TRY(gemm(e, o, mc::EPI_RESID_CAPTURE, s));
     } else {
       HIP_TRY(gemm(e, o, mc::EPI_RESID_GATE, s));
     }
   }
+  if (cn) MC_TRY(controlnet_add(e, cn, last, s));
   if (last) {
     const int b = e->branch;   // calibration compares with the previous residual of the SAME branch
     if (e->mode == MC_MODE_CALIB && e->have_res[b]) {

@@ -197,6 +197,12 @@ hipError_t launch_attn_merge(const bf16_t* const* o_parts, const float* const* l
                              int rows_pad, int d, hipStream_t stream);
 // a[i] = bf16(float(a[i]) + float(b[i]))   (sum of two attention outputs, Wan I2V cross-attention)
 hipError_t launch_add_bf16(bf16_t* a, const bf16_t* b, size_t n, hipStream_t stream);
+// x[m, :] += s[m, :] for m < rows (x fp32; s fp32 or bf16 -- s_bf16 -- contiguous [rows, D], widened exactly): a ControlNet
+// sample added to rows of the residual stream, bitwise x + float(s).  r != null, a second destination in the same pass:
+// r[m, :] += s[m, :], or with x0 != null r[m, :] = x_new[m, :] - x0[m, :] (x0 bf16): the MagCache residual taken after the
+// add.  hipErrorInvalidValue for D % 8 != 0 or a pointer that is not 16-byte aligned.
+hipError_t launch_add_rows(float* x, long ldx, const void* s, int s_bf16, float* r, long ldr, const bf16_t* x0, long ldx0,
+                           int rows, int D, hipStream_t stream);
 // head: out[m, n] = dot(xn[m,:], W[n,:]) + b[n], fp32, N <= 256 (64 columns per block)
 hipError_t launch_head_linear(const float* xn, long ldx, const float* W, const float* b, float* out, long ldo,
                               int M, int N, int K, hipStream_t stream);

@@ -263,6 +263,16 @@ mc_status mc_op_lincomb(const float* const* xs_dev, const float* coef, int k, fl
   return MC_OK;
 }
 
+mc_status mc_op_add_rows(float* x, long ldx, const void* s, mc_dtype s_dtype, float* r, long ldr, const void* x0, long ldx0,
+                         int rows, int D, mc_stream stream) {
+  if (s_dtype != MC_F32 && s_dtype != MC_BF16) return fail(MC_EINVAL, "add_rows: the sample is fp32 or bf16");
+  hipError_t err = mc::launch_add_rows(x, ldx, s, s_dtype == MC_BF16, r, ldr, (const bf16_t*)x0, ldx0, rows, D, (hipStream_t)stream);
+  if (err == hipErrorInvalidValue)
+    return fail(MC_EINVAL, "add_rows: D a multiple of 8, 16-byte aligned pointers, ldx / ldr >= D multiples of 4, ldx0 of 8, x0 needs r");
+  HIP_TRY(err);
+  return MC_OK;
+}
+
 mc_status mc_op_cast_bf16(const float* src, void* dst, size_t n, mc_stream s) {
   HIP_TRY(mc::launch_cast_bf16(src, (bf16_t*)dst, n, (hipStream_t)s));
   return MC_OK;

@@ -79,6 +79,7 @@ class MMDiTEngine:
         self.ws.zero_()
         check(self.lib.mc_mmdit_set_workspace(self.h, _ptr(self.ws), nbytes))
         self._rope_key = None
+        self._controlnet = None
 
     def __del__(self):
         try:
@@ -138,6 +139,34 @@ class MMDiTEngine:
         check(self.lib.mc_mmdit_set_rope(self.h, _ptr(cos), _ptr(sin), cos.shape[0], _stream()))
         torch.cuda.current_stream().synchronize()
         self._rope_key = key
+
+    def set_controlnet(self, double=None, single=None, blocks_repeat=False):
+        """FLUX ControlNet residuals (upstream controlnet_block_samples / controlnet_single_block_samples /
+        controlnet_blocks_repeat) for every following full or calibration forward; both None clears them.  Each sample is
+        [1, img_tokens, dim] or [img_tokens, dim], all bf16 or all fp32.  The engine reads the tensors in place during the
+        forwards, so they are kept alive here until the next call."""
+        double = list(double) if double is not None else []
+        single = list(single) if single is not None else []
+        if not double and not single:
+            if self._controlnet is not None:
+                check(self.lib.mc_mmdit_set_controlnet(self.h, None, 0, None, 0, MC_F32, 0))
+                self._controlnet = None
+            return
+        dtypes = {t.dtype for t in double + single}
+        if len(dtypes) != 1 or next(iter(dtypes)) not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"ControlNet samples must all be fp32 or all be bf16, got {sorted(map(str, dtypes))}")
+
+        def rows(t):
+            if t.dim() == 3 and t.shape[0] == 1:
+                t = t[0]
+            if tuple(t.shape) != (self.img_tokens, self.dim):
+                raise ValueError(f"ControlNet sample {tuple(t.shape)}: expected [{self.img_tokens}, {self.dim}]")
+            return t.detach().to(self.device).contiguous()
+        keep = ([rows(t) for t in double], [rows(t) for t in single])
+        lists = [(C.c_void_p * len(k))(*[t.data_ptr() for t in k]) for k in keep]
+        check(self.lib.mc_mmdit_set_controlnet(self.h, lists[0], len(keep[0]), lists[1], len(keep[1]),
+                                               MC_F32 if dtypes == {torch.float32} else MC_BF16, int(bool(blocks_repeat))))
+        self._controlnet = keep
 
     def forward(self, img, timestep, guidance, txt, txt_valid, vec, mode=MC_MODE_FULL, out=None, branch=None):
         """`branch` (None = the one-slot mc_mmdit_forward): the CFG branch of mc_mmdit_forward2 (Qwen-Image 0 / 1).
@@ -221,6 +250,9 @@ class MMDiTSequenceParallel:
                 full.view(self.P, -1)[r].copy_(p_.reshape(-1))
 
     def forward(self, img, timestep, guidance, txt, txt_valid, vec, mode):
+        """FLUX ControlNet samples are state of the rank's engine, not an argument: MMDiTEngine.set_controlnet ahead of
+        this call (the FLUX shims do it), with the FULL [img_tokens, dim] tensors on every rank; block_post adds this
+        rank's rows of them."""
         e = self.e
         e.begin(img, timestep, guidance, txt, txt_valid, vec, mode)
         if mode != MC_MODE_SKIP:
@@ -324,12 +356,33 @@ class FluxTransformer2DModelHIP:
     __call__ = _dispatch
 
 
+def controlnet_sample_index(block, n_blocks, n_samples, blocks_repeat=False):
+    """The list index the reference's forward reads for block `block` of n_blocks (magcache_flux.py:376-384, :418-422:
+    block // int(ceil(n_blocks / n_samples)), or block % n_samples under controlnet_blocks_repeat, a rule of the double
+    blocks only), as the engine computes it; ValueError where the engine refuses the pair."""
+    k = _lib.load().mc_mmdit_controlnet_index(int(n_blocks), int(n_samples), int(block), int(bool(blocks_repeat)))
+    if k < 0:
+        raise ValueError(f"{n_samples} ControlNet samples do not fit {n_blocks} blocks (block {block})")
+    return k
+
+
+def _flux_set_controlnet(model, double, single, blocks_repeat):
+    """the forward's ControlNet arguments -> the engine, ahead of the forward; a call without samples clears what an earlier
+    call set (and touches nothing when there is nothing to clear)"""
+    e = model.engine
+    if double is not None or single is not None or getattr(e, "_controlnet", None) is not None:
+        e.set_controlnet(double, single, blocks_repeat)
+
+
 def _flux_output(output, return_dict):
     return SimpleNamespace(sample=output) if return_dict else (output,)
 
 
 def flux_plain_forward(self, hidden_states, encoder_hidden_states=None, pooled_projections=None, timestep=None,
-                       img_ids=None, txt_ids=None, guidance=None, joint_attention_kwargs=None, return_dict=True, **_):
+                       img_ids=None, txt_ids=None, guidance=None, joint_attention_kwargs=None,
+                       controlnet_block_samples=None, controlnet_single_block_samples=None, return_dict=True,
+                       controlnet_blocks_repeat=False, **_):
+    _flux_set_controlnet(self, controlnet_block_samples, controlnet_single_block_samples, controlnet_blocks_repeat)
     out = self._run(hidden_states, encoder_hidden_states, pooled_projections, timestep, img_ids, txt_ids, guidance, MC_MODE_FULL)
     return _flux_output(out, return_dict)
 
@@ -342,7 +395,7 @@ def flux_magcache_forward(self, hidden_states, encoder_hidden_states=None, poole
                           controlnet_block_samples=None, controlnet_single_block_samples=None, return_dict=True,
                           controlnet_blocks_repeat=False):
     """Drop-in for MagCache4FLUX/magcache_flux.py magcache_forward (:234-445)."""
-    assert controlnet_block_samples is None and controlnet_single_block_samples is None, "ControlNet residuals are not supported"
+    _flux_set_controlnet(self, controlnet_block_samples, controlnet_single_block_samples, controlnet_blocks_repeat)
     skip_forward = False
     if self.cnt >= int(self.retention_ratio * self.num_steps + 0.5):                       # :333
         cur_scale = self.mag_ratios[self.cnt]
@@ -375,6 +428,7 @@ def flux_magcache_calibration(self, hidden_states, encoder_hidden_states=None, p
                               controlnet_block_samples=None, controlnet_single_block_samples=None, return_dict=True,
                               controlnet_blocks_repeat=False):
     """Drop-in for magcache_flux.py magcache_calibration (:37-232)."""
+    _flux_set_controlnet(self, controlnet_block_samples, controlnet_single_block_samples, controlnet_blocks_repeat)
     out = self._run(hidden_states, encoder_hidden_states, pooled_projections, timestep, img_ids, txt_ids, guidance, MC_MODE_CALIB)
     if self.cnt >= 1:                                                                       # :199-207
         norm_ratio, norm_std, cos_dis = self.engine.calib_stats()

@@ -5,6 +5,9 @@ headline bench line):
     python tools/bench_mmdit.py flux      FLUX.1-dev 512x512, 28 steps: no-cache vs MagCache (thresh 0.24, K 5, R 0.1)
     python tools/bench_mmdit.py hunyuan   HunyuanVideo 720p 129 frames: full / skipped forward times, model TFLOP/s
     (a trailing `two_streams` runs the text half of every double block on a second HIP stream)
+    python tools/bench_mmdit.py flux --controlnet 5,10
+                                          FLUX.1-dev 1024x1024, one full forward with 5 double + 10 single random bf16
+                                          ControlNet samples vs the same forward without, alternating, ms per forward
 
 Synthetic inputs, seeded random-init weights of the real architecture (no checkpoints offline).  One JSON line each.
 Also checks the size-independent MagCache properties at full size: a skipped forward equals the final layer applied
@@ -153,6 +156,46 @@ def bench_flux():
                       "finite": bool(torch.isfinite(x_mc).all())}))
 
 
+def bench_flux_controlnet(n_double, n_single, rounds=7, per_round=4):
+    """One FULL forward at FLUX.1-dev 1024x1024 (4096 image + 512 text tokens) with ControlNet samples and without, in
+    alternating windows of `per_round` forwards after a warm-up of both; median and spread of the windows, host clock
+    around a device synchronise."""
+    cfg = MM.FLUX_DEV
+    h2 = w2 = 64
+    txt_len, d = 512, 3072
+    cls = type("FluxControlNetBench", (MM.FluxTransformer2DModelHIP,), {})
+    m = cls(cfg, h2 * w2, txt_len=txt_len, device=DEV, calibration=False)
+    synth_load(m, flux_names(cfg))
+    g = torch.Generator(device=DEV).manual_seed(42)
+    lat = torch.randn(1, h2 * w2, 64, generator=g, device=DEV)
+    ids = torch.zeros(h2, w2, 3, device=DEV)
+    ids[..., 1] += torch.arange(h2, device=DEV)[:, None]
+    ids[..., 2] += torch.arange(w2, device=DEV)[None, :]
+    kw = dict(encoder_hidden_states=torch.randn(1, txt_len, 4096, generator=g, device=DEV),
+              pooled_projections=torch.randn(1, 768, generator=g, device=DEV), img_ids=ids.reshape(-1, 3),
+              txt_ids=torch.zeros(txt_len, 3, device=DEV), guidance=torch.tensor([3.5], device=DEV), return_dict=False)
+    t = torch.tensor([0.5], device=DEV)
+    double = [(0.05 * torch.randn(h2 * w2, d, generator=g, device=DEV)).bfloat16() for _ in range(n_double)]
+    single = [(0.05 * torch.randn(h2 * w2, d, generator=g, device=DEV)).bfloat16() for _ in range(n_single)]
+    cn = dict(controlnet_block_samples=double or None, controlnet_single_block_samples=single or None)
+    without = lambda: m(hidden_states=lat, timestep=t, **kw)[0]
+    with_cn = lambda: m(hidden_states=lat, timestep=t, **kw, **cn)[0]
+    for f in (without, with_cn, without, with_cn):
+        timed(f)
+    ms = {"without": [], "with": []}
+    for _ in range(rounds):
+        ms["without"].append(timed(without, per_round)[0] * 1e3)
+        ms["with"].append(timed(with_cn, per_round)[0] * 1e3)
+    o_with, o_without = with_cn(), without()
+    adds = (cfg["num_layers"] if double else 0) + (cfg["num_single_layers"] if single else 0)   # every block has a sample
+    print(json.dumps({"config": f"FLUX.1-dev 1024x1024 full forward, {n_double} double + {n_single} single bf16 ControlNet samples "
+                                f"({adds} add launches), synthetic weights/inputs",
+                      "forward_ms_without": float(np.median(ms["without"])), "forward_ms_with": float(np.median(ms["with"])),
+                      "windows_without_ms": [round(v, 3) for v in ms["without"]], "windows_with_ms": [round(v, 3) for v in ms["with"]],
+                      "forwards_per_window": per_round, "finite": bool(torch.isfinite(o_with).all()),
+                      "output_moved_rel_l2": float((o_with - o_without).norm() / o_without.norm())}))
+
+
 def bench_hunyuan():
     cfg = MM.HUNYUAN_VIDEO
     grid, txt_len, n_valid = (33, 90, 160), 256, 77          # 720x1280, 129 frames -> latent 16 x 33 x 90 x 160
@@ -202,4 +245,10 @@ if __name__ == "__main__":
         from magcache_amd._lib import check
         check(lib.mc_set_option(b"mmdit_two_streams", 1))
         print("mmdit_two_streams = 1")
-    {"flux": bench_flux, "hunyuan": bench_hunyuan}[which]()
+    if "--controlnet" in sys.argv[2:]:
+        if which != "flux":
+            sys.exit(f"--controlnet benches FLUX (ControlNet residuals are a FLUX input), not '{which}'")
+        n_d, n_s = (int(v) for v in sys.argv[sys.argv.index("--controlnet") + 1].split(","))
+        bench_flux_controlnet(n_d, n_s)
+    else:
+        {"flux": bench_flux, "hunyuan": bench_hunyuan}[which]()
