@@ -28,7 +28,7 @@
  * MLP-out run as ONE row-split launch each when the range boundary sits on a 256-row tile boundary (FLUX; HunyuanVideo's does
  * not: two launches); a single block's [q|k|v ; MLP-in] is one launch with two destinations; the projections back to d at small
  * image sizes (<= 128 tiles of 256 x 256) are cut along K into slices summed by a second launch -- their scratch is the
- * workspace's "splitk0" / "splitk1" (mc_mmdit_buffer_info), sized at create time from the geometry (absent at HunyuanVideo's).
+ * workspace's "splitk0" / "splitk1" (mc_mmdit_buffer_info), sized with the plan from the geometry (absent at HunyuanVideo's).
  */
 #ifndef MAGCACHE_MMDIT_H
 #define MAGCACHE_MMDIT_H
@@ -74,6 +74,31 @@ void mc_mmdit_destroy(mc_mmdit* e);
 size_t mc_mmdit_workspace_bytes(const mc_mmdit* e);
 mc_status mc_mmdit_set_workspace(mc_mmdit* e, void* ws_dev, size_t bytes);
 mc_status mc_mmdit_buffer_info(const mc_mmdit* e, const char* name, size_t* offset, size_t* bytes);
+
+/* Token geometry per call.  mc_mmdit_create fixes the family, the widths and the depths for good; the image tokens, the
+ * HunyuanVideo latent grid and the text length it was given are only the FIRST geometry: one engine (one copy of the
+ * weights) serves any resolution and prompt length, as the transformers it stands for do.
+ *
+ * mc_mmdit_geometry_bytes: the workspace a geometry would need, the engine unchanged -- to size ONE workspace for all
+ * the geometries a caller will serve (take the maximum: the plan is not monotone in the token count, the split-K scratch
+ * exists at small geometries only).
+ *
+ * mc_mmdit_set_geometry: between forwards only (MC_ESTATE between mc_mmdit_begin and mc_mmdit_end).  The geometry is
+ * checked as mc_mmdit_create checks it (MC_EINVAL: counts not positive, HunyuanVideo img_tokens != F*(H/2)*(W/2), odd H or
+ * W) and the workspace is planned again: mc_mmdit_workspace_bytes and every mc_mmdit_buffer_info offset are then those of
+ * an engine created at the new geometry, and views into the old plan are void.  A bound workspace is kept when the new
+ * plan fits its bytes; when it does not the call returns MC_EINVAL (the message names both byte counts) and the engine
+ * stays as it was, usable at its old geometry.  With no workspace bound the call only plans.  Afterwards the engine is in
+ * the state mc_mmdit_set_workspace leaves it in: residual caches of both branches and calibration statistics forgotten,
+ * pad rows cleaned again by the next forward; the ControlNet lists are cleared (the samples had the old img_tokens) and
+ * the RoPE table is the identity rotation as after mc_mmdit_create -- set the new geometry's with mc_mmdit_set_rope.
+ * The call may allocate (a longer RoPE table) and synchronises the device: it is no part of a forward and must not be
+ * stream-captured.  Sequence-parallel engines (sp_size > 1) keep their geometry: MC_EINVAL.  latent_f/h/w: HunyuanVideo,
+ * ignored otherwise. */
+mc_status mc_mmdit_geometry_bytes(const mc_mmdit* e, int img_tokens, int latent_f, int latent_h, int latent_w, int txt_len,
+                                  size_t* bytes);
+mc_status mc_mmdit_set_geometry(mc_mmdit* e, int img_tokens, int latent_f, int latent_h, int latent_w, int txt_len);
+
 /* upstream state_dict names (diffusers FluxTransformer2DModel / hyvideo HYVideoDiffusionTransformer), fp32 or bf16 */
 mc_status mc_mmdit_set_weight(mc_mmdit* e, const char* name, const void* src_dev, mc_dtype dtype,
                               const int64_t* shape, int ndim, mc_stream stream);

@@ -130,6 +130,8 @@ SIGNATURES = {
     "mc_mmdit_workspace_bytes": (_sz, [_vp]),
     "mc_mmdit_set_workspace": (_i, [_vp, _vp, _sz]),
     "mc_mmdit_buffer_info": (_i, [_vp, C.c_char_p, C.POINTER(_sz), C.POINTER(_sz)]),
+    "mc_mmdit_geometry_bytes": (_i, [_vp, _i, _i, _i, _i, _i, C.POINTER(_sz)]),
+    "mc_mmdit_set_geometry": (_i, [_vp, _i, _i, _i, _i, _i]),
     "mc_mmdit_set_weight": (_i, [_vp, C.c_char_p, _vp, _i, C.POINTER(C.c_int64), _i, _vp]),
     "mc_mmdit_weights_missing": (_i, [_vp, C.c_char_p, _sz]),
     "mc_mmdit_set_rope": (_i, [_vp, _vp, _vp, _i, _vp]),

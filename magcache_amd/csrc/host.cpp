@@ -115,6 +115,15 @@ bool WeightStore::all_loaded(const char** first_missing) const {
   return true;
 }
 
+void WeightStore::release(void* p) {
+  for (size_t i = 0; i < owned.size(); ++i)
+    if (owned[i] == p) {
+      (void)hipFree(p);
+      owned.erase(owned.begin() + i);
+      return;
+    }
+}
+
 void WeightStore::free_all() {
   for (void* p : owned) (void)hipFree(p);
   owned.clear();
@@ -128,11 +137,20 @@ void Workspace::add(const char* name, size_t bytes) {
   need = align_up(need + bytes, 256);
 }
 
+mc_status Workspace::replan(const Workspace& plan) {
+  if (ws && plan.need > bound)
+    return fail(MC_EINVAL, "the new plan needs a workspace of %zu bytes, %zu bytes are bound", plan.need, bound);
+  bufs = plan.bufs;
+  need = plan.need;
+  return MC_OK;
+}
+
 mc_status Workspace::bind(void* ws_dev, size_t bytes) {
   if (!ws_dev) return fail(MC_EINVAL, "null argument");
   if (bytes < need) return fail(MC_EINVAL, "workspace too small: %zu < %zu", bytes, need);
   if (((uintptr_t)ws_dev) & 255) return fail(MC_EINVAL, "workspace must be 256-byte aligned");
   ws = (char*)ws_dev;
+  bound = bytes;
   return MC_OK;
 }
 

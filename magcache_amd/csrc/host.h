@@ -86,6 +86,7 @@ struct WeightStore {
   mc_status set(const char* name, const void* src_dev, mc_dtype dtype, const int64_t* shape, int ndim, hipStream_t stream);
   int missing(char* buf, size_t buflen) const;  // count; names, one per line, as far as buf holds them
   bool all_loaded(const char** first_missing) const;
+  void release(void* p);  // free one allocation of alloc() (never inside a forward)
   void free_all();
 
  private:
@@ -101,9 +102,13 @@ struct Buf {
 struct Workspace {
   std::map<std::string, Buf> bufs;
   char* ws = nullptr;
-  size_t need = 0;  // bytes planned so far
+  size_t need = 0;   // bytes planned so far
+  size_t bound = 0;  // bytes behind ws
 
   void add(const char* name, size_t bytes);
+  // take over another plan (one made with add() on a Workspace of its own) under the binding of this one: refused, and
+  // nothing changed, when memory is bound and the plan does not fit it
+  mc_status replan(const Workspace& plan);
   mc_status bind(void* ws_dev, size_t bytes);
   const Buf* find(const std::string& name) const;
   mc_status info(const std::string& name, size_t* offset, size_t* bytes) const;

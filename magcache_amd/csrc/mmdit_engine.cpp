@@ -95,6 +95,7 @@ struct mc_mmdit {
   float *b_in = nullptr, *b_ctx = nullptr, *b_mod = nullptr, *w_head = nullptr, *b_head = nullptr;
   float* w_txt_norm = nullptr;  // Qwen-Image txt_norm (RMSNorm over txt_dim)
   float* cs = nullptr;  // RoPE (cos,sin) [Sp][64][2]
+  int cs_rows = 0;      // rows allocated behind cs (>= Sp: mc_mmdit_set_geometry grows it, never shrinks it)
   mc::WeightStore weights;
   mc::Workspace work;
   int res_cur[2] = {0, 0};  // per CFG branch: the slot (of the branch's own) holding residual_cache / previous_residual
@@ -150,6 +151,123 @@ mc_status alloc_stream(mc_mmdit* e, Stream& s) {
   return MC_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- token geometry
+// What a call may change (mc_mmdit_set_geometry): image tokens, the HunyuanVideo latent grid, the text length.  Everything
+// below is a function of it and of what mc_mmdit_create fixed for good (family, widths, depths, the sequence-parallel
+// shard) -- mc_mmdit_create and mc_mmdit_set_geometry share it.
+struct Geometry {
+  int img_tokens, latent_f, latent_h, latent_w, txt_len;
+};
+struct Rows {  // the derived integers of mc_mmdit
+  int Li, Lt, S, Sp, Lrp, tok0, img0, txt0;
+};
+
+mc_status check_geometry(const mc_mmdit_config& c, const Geometry& g, int P, int rank) {
+  if (g.txt_len <= 0) return fail(MC_EINVAL, "bad text geometry");
+  if (g.img_tokens <= 0) return fail(MC_EINVAL, "img_tokens must be positive");
+  if (c.family == MC_FAMILY_HUNYUAN &&
+      (g.latent_f <= 0 || g.latent_h <= 0 || g.latent_w <= 0 || (g.latent_h & 1) || (g.latent_w & 1) ||
+       g.img_tokens != g.latent_f * (g.latent_h / 2) * (g.latent_w / 2)))
+    return fail(MC_EINVAL, "img_tokens must equal F*(H/2)*(W/2) of the latent grid");
+  if (rank < 0 || rank >= P || (g.img_tokens % P) != 0)
+    return fail(MC_EINVAL, "bad sequence-parallel geometry: rank %d of %d, %d image tokens", rank, P, g.img_tokens);
+  return MC_OK;
+}
+
+Rows derive_rows(int family, const Geometry& g, int P, int rank) {
+  const bool hy = family == MC_FAMILY_HUNYUAN;
+  Rows r;
+  r.Li = g.img_tokens / P; r.Lt = g.txt_len;
+  r.tok0 = rank * r.Li;
+  r.Lrp = (int)align_up(r.Li, 256);
+  r.S = r.Li + r.Lt;
+  r.Sp = (int)align_up(r.S, 256);
+  r.img0 = hy ? 0 : r.Lt;
+  r.txt0 = hy ? r.Li : 0;
+  return r;
+}
+
+void apply_geometry(mc_mmdit* e, const Geometry& g, const Rows& r) {
+  e->cfg.img_tokens = g.img_tokens; e->cfg.txt_len = g.txt_len;
+  e->cfg.latent_f = g.latent_f; e->cfg.latent_h = g.latent_h; e->cfg.latent_w = g.latent_w;
+  e->Li = r.Li; e->Lt = r.Lt; e->S = r.S; e->Sp = r.Sp; e->Lrp = r.Lrp;
+  e->tok0 = r.tok0; e->img0 = r.img0; e->txt0 = r.txt0;
+}
+
+// the workspace of a geometry: needs of `e` only what mc_mmdit_create fixed (cfg widths, d, H, P, Kp, mod_rows)
+void plan_workspace(const mc_mmdit* e, const Rows& r, mc::Workspace& ws) {
+  const mc_mmdit_config& c = e->cfg;
+  const bool qw = c.family == MC_FAMILY_QWEN;
+  const size_t d = e->d, Sp = r.Sp, Li = r.Li;
+  const size_t Ltp = align_up(r.Lt, 256);
+  ws.add("x", Sp * d * 4);
+  ws.add("x0", Sp * d * 2);
+  ws.add("xn", Sp * d * 2);
+  ws.add("qkv", (Sp + 64) * 3 * d * 2);        // + one key tile of slack behind the text rows
+  if (e->P > 1) {
+    ws.add("kv_gather", (size_t)e->P * r.Lrp * 2 * d * 2);   // image K|V of every rank
+    ws.add("attn_lse", (size_t)e->H * Sp * 4);
+  } else if (qw) {
+    ws.add("attn_lse", (size_t)e->H * Sp * 4);                // image keys, then the valid text keys merged
+  }
+  ws.add("am", Sp * 5 * d * 2);               // also the fp32 [img, d] head operand after the last block
+  ws.add("tokens", align_up(Li, 256) * e->Kp * 2);
+  ws.add("txt_in", Ltp * c.txt_dim * 2);
+  ws.add("txt_e", Ltp * d * 2);
+  ws.add("emod", e->mod_rows * 4);
+  ws.add("vecs", 16 * d * 4 + (size_t)c.txt_dim * 4 + 1024);   // sinusoids, hidden vectors, vec, c, gates
+  ws.add("head_tokens", Li * 64 * 4);
+  ws.add("residual0", Sp * d * 4);
+  if (c.calibration) ws.add("residual1", Sp * d * 4);
+  if (qw) {   // the uncond branch's slots (Qwen-Image only: the other families are guidance distilled, one branch)
+    ws.add(c.calibration ? "residual2" : "residual1", Sp * d * 4);
+    if (c.calibration) ws.add("residual3", Sp * d * 4);
+  }
+  {
+    // split-K scratch (gemm_bf16_v2): the largest any GEMM of a block wants, one buffer per stream that may run GEMMs
+    // (by shape: present at small geometries only, so the plan is not monotone in the token count)
+    size_t need_all = 0, need_txt = 0;
+    auto upd = [&](size_t& n, int M, int N, int K, int epi) { n = std::max(n, mc::gemm_splitk_ws_need(M, N, K, epi)); };
+    for (int M : {(int)Li, r.Lt, r.S}) {
+      for (size_t* n : {&need_all, M == r.Lt ? &need_txt : &need_all}) {
+        upd(*n, M, 3 * d, d, mc::EPI_BF16);
+        upd(*n, M, d, d, mc::EPI_RESID_GATE);
+        upd(*n, M, 4 * d, d, mc::EPI_GELU_BF16);
+        upd(*n, M, d, 4 * d, mc::EPI_RESID_GATE);
+        upd(*n, M, d, 5 * d, mc::EPI_RESID_GATE);
+      }
+    }
+    if (need_all) ws.add("splitk0", need_all);
+    if (need_txt) ws.add("splitk1", need_txt);
+  }
+  ws.add("calib_partial", (2048 * 4 + 2) * 8);   // + the arrival ticket of calib_stats_kernel
+  ws.add("calib_sums", 64);
+  ws.add("calib_stats", 64);
+}
+
+// (re)allocate the RoPE table for `rows` rows where it is shorter, and set every row to the identity rotation
+mc_status rope_identity(mc_mmdit* e, int rows) {
+  if (rows > e->cs_rows) {
+    float* grown = nullptr;
+    MC_TRY(e->weights.alloc(&grown, (size_t)rows * 128));
+    if (e->cs) e->weights.release(e->cs);
+    e->cs = grown;
+    e->cs_rows = rows;
+  }
+  std::vector<float> ident((size_t)e->cs_rows * 128);
+  for (size_t i = 0; i < ident.size(); i += 2) { ident[i] = 1.f; ident[i + 1] = 0.f; }
+  if (hipMemcpy(e->cs, ident.data(), ident.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+    return fail(MC_EHIP, "RoPE table upload failed");
+  return MC_OK;
+}
+
+// what a (re)bound or re-planned workspace means for the state: nothing cached, pad rows to be cleaned by the next forward
+mc_status forget_workspace_state(mc_mmdit* e) {
+  e->have_res[0] = e->have_res[1] = e->have_stats = e->pads_clean = false;
+  if (e->work.ws) HIP_TRY(hipMemset(e->buf<double>("calib_partial") + 2048 * 4, 0, 16));   // arrival ticket of calib_stats_kernel
+  return MC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -163,38 +281,30 @@ mc_status mc_mmdit_create(const mc_mmdit_config* cfg, mc_mmdit** out) {
   if (c.num_heads <= 0 || c.dim != c.num_heads * 128) return fail(MC_EINVAL, "dim must be num_heads * 128 (head_dim 128)");
   if ((c.dim % 256) != 0) return fail(MC_EINVAL, "dim %d must be a multiple of 256", c.dim);
   if (c.n_double < 0 || c.n_single < 0 || c.n_double + c.n_single == 0) return fail(MC_EINVAL, "no blocks");
-  if (c.txt_len <= 0 || c.txt_dim <= 0 || (c.txt_dim % 64) != 0 || (!qw && (c.vec_dim <= 0 || (c.vec_dim % 8) != 0)))
+  if (c.txt_dim <= 0 || (c.txt_dim % 64) != 0 || (!qw && (c.vec_dim <= 0 || (c.vec_dim % 8) != 0)))
     return fail(MC_EINVAL, "bad text geometry");
   if (qw) {
     if (c.n_single != 0) return fail(MC_EINVAL, "Qwen-Image has no single-stream blocks (n_single %d)", c.n_single);
     if (c.vec_dim != 0) return fail(MC_EINVAL, "Qwen-Image has no pooled text vector (vec_dim %d)", c.vec_dim);
     if (c.sp_size > 1) return fail(MC_EINVAL, "Qwen-Image runs on one GPU (sp_size %d)", c.sp_size);
   }
-  if (c.img_tokens <= 0) return fail(MC_EINVAL, "img_tokens must be positive");
   if (hy) {
-    if ((c.latent_h & 1) || (c.latent_w & 1) || c.img_tokens != c.latent_f * (c.latent_h / 2) * (c.latent_w / 2))
-      return fail(MC_EINVAL, "img_tokens must equal F*(H/2)*(W/2) of the latent grid");
     if (c.out_channels * 4 > 64) return fail(MC_EINVAL, "out_channels*4 > 64 unsupported by the head kernel");
   } else if (c.out_channels > 64 || c.refiner_depth != 0) {
     return fail(MC_EINVAL, "FLUX / Qwen-Image: out_channels <= 64, no refiner");
   }
+  const Geometry geo = {c.img_tokens, c.latent_f, c.latent_h, c.latent_w, c.txt_len};
+  const int P = c.sp_size > 0 ? c.sp_size : 1;
+  MC_TRY(check_geometry(c, geo, P, c.sp_rank));
   mc_mmdit* e = new mc_mmdit();
   e->cfg = c;
-  e->P = c.sp_size > 0 ? c.sp_size : 1;
+  e->P = P;
   e->rank = c.sp_rank;
-  if (e->rank < 0 || e->rank >= e->P || (c.img_tokens % e->P) != 0) {
-    delete e;
-    return fail(MC_EINVAL, "bad sequence-parallel geometry: rank %d of %d, %d image tokens", c.sp_rank, c.sp_size, c.img_tokens);
-  }
-  e->d = c.dim; e->H = c.num_heads; e->Li = c.img_tokens / e->P; e->Lt = c.txt_len;
-  e->tok0 = e->rank * e->Li;
-  e->Lrp = (int)align_up(e->Li, 256);
-  e->S = e->Li + e->Lt;
-  e->Sp = (int)align_up(e->S, 256);
+  e->d = c.dim; e->H = c.num_heads;
+  const Rows rows = derive_rows(c.family, geo, P, c.sp_rank);
+  apply_geometry(e, geo, rows);
   e->Kin = hy ? c.in_channels * 4 : c.in_channels;
   e->Kp = (int)align_up(e->Kin, 64);
-  e->img0 = hy ? 0 : e->Lt;
-  e->txt0 = hy ? e->Li : 0;
   e->out_feat = hy ? c.out_channels * 4 : c.out_channels;
   const size_t d = e->d;
   const bool flux = c.family == MC_FAMILY_FLUX;
@@ -322,59 +432,9 @@ mc_status mc_mmdit_create(const mc_mmdit_config* cfg, mc_mmdit** out) {
     e->weights.slots["final_layer.linear.bias"].perm_c = c.out_channels;
   }
   // ---- RoPE table, identity rotation until mc_mmdit_set_rope
-  {
-    ALLOC(e->cs, (size_t)e->Sp * 128);
-    std::vector<float> ident((size_t)e->Sp * 128);
-    for (size_t i = 0; i < ident.size(); i += 2) { ident[i] = 1.f; ident[i + 1] = 0.f; }
-    if (hipMemcpy(e->cs, ident.data(), ident.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-      return cleanup(fail(MC_EHIP, "RoPE table upload failed"));
-  }
+  TRY_C(rope_identity(e, e->Sp));
   // ---- workspace plan
-  mc::Workspace& ws = e->work;
-  const size_t Sp = e->Sp, Li = e->Li;
-  const size_t Ltp = align_up(e->Lt, 256);
-  ws.add("x", Sp * d * 4);
-  ws.add("x0", Sp * d * 2);
-  ws.add("xn", Sp * d * 2);
-  ws.add("qkv", (Sp + 64) * 3 * d * 2);        // + one key tile of slack behind the text rows
-  if (e->P > 1) {
-    ws.add("kv_gather", (size_t)e->P * e->Lrp * 2 * d * 2);   // image K|V of every rank
-    ws.add("attn_lse", (size_t)e->H * Sp * 4);
-  } else if (qw) {
-    ws.add("attn_lse", (size_t)e->H * Sp * 4);                // image keys, then the valid text keys merged
-  }
-  ws.add("am", Sp * 5 * d * 2);               // also the fp32 [img, d] head operand after the last block
-  ws.add("tokens", align_up(Li, 256) * e->Kp * 2);
-  ws.add("txt_in", Ltp * c.txt_dim * 2);
-  ws.add("txt_e", Ltp * d * 2);
-  ws.add("emod", e->mod_rows * 4);
-  ws.add("vecs", 16 * d * 4 + (size_t)c.txt_dim * 4 + 1024);   // sinusoids, hidden vectors, vec, c, gates
-  ws.add("head_tokens", Li * 64 * 4);
-  ws.add("residual0", Sp * d * 4);
-  if (c.calibration) ws.add("residual1", Sp * d * 4);
-  if (qw) {   // the uncond branch's slots (Qwen-Image only: the other families are guidance distilled, one branch)
-    ws.add(c.calibration ? "residual2" : "residual1", Sp * d * 4);
-    if (c.calibration) ws.add("residual3", Sp * d * 4);
-  }
-  {
-    // split-K scratch (gemm_bf16_v2): the largest any GEMM of a block wants, one buffer per stream that may run GEMMs
-    size_t need_all = 0, need_txt = 0;
-    auto upd = [&](size_t& n, int M, int N, int K, int epi) { n = std::max(n, mc::gemm_splitk_ws_need(M, N, K, epi)); };
-    for (int M : {(int)Li, (int)e->Lt, (int)e->S}) {
-      for (size_t* n : {&need_all, M == e->Lt ? &need_txt : &need_all}) {
-        upd(*n, M, 3 * d, d, mc::EPI_BF16);
-        upd(*n, M, d, d, mc::EPI_RESID_GATE);
-        upd(*n, M, 4 * d, d, mc::EPI_GELU_BF16);
-        upd(*n, M, d, 4 * d, mc::EPI_RESID_GATE);
-        upd(*n, M, d, 5 * d, mc::EPI_RESID_GATE);
-      }
-    }
-    if (need_all) ws.add("splitk0", need_all);
-    if (need_txt) ws.add("splitk1", need_txt);
-  }
-  ws.add("calib_partial", (2048 * 4 + 2) * 8);   // + the arrival ticket of calib_stats_kernel
-  ws.add("calib_sums", 64);
-  ws.add("calib_stats", 64);
+  plan_workspace(e, rows, e->work);
   // side stream and fork / join events of the (optional) two-stream double block: created here, never inside a forward
   // (a forward may run under stream capture)
   if (hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking) != hipSuccess) return cleanup(fail(MC_EHIP, "side stream"));
@@ -406,9 +466,41 @@ size_t mc_mmdit_workspace_bytes(const mc_mmdit* e) { return e ? e->work.need : 0
 mc_status mc_mmdit_set_workspace(mc_mmdit* e, void* ws_dev, size_t bytes) {
   if (!e) return fail(MC_EINVAL, "null argument");
   MC_TRY(e->work.bind(ws_dev, bytes));
-  e->have_res[0] = e->have_res[1] = e->have_stats = e->pads_clean = false;
-  HIP_TRY(hipMemset(e->buf<double>("calib_partial") + 2048 * 4, 0, 16));   // arrival ticket of calib_stats_kernel
+  return forget_workspace_state(e);
+}
+
+mc_status mc_mmdit_geometry_bytes(const mc_mmdit* e, int img_tokens, int latent_f, int latent_h, int latent_w, int txt_len,
+                                  size_t* bytes) {
+  if (!e || !bytes) return fail(MC_EINVAL, "null argument");
+  const Geometry g = {img_tokens, latent_f, latent_h, latent_w, txt_len};
+  MC_TRY(check_geometry(e->cfg, g, e->P, e->rank));
+  mc::Workspace plan;
+  plan_workspace(e, derive_rows(e->cfg.family, g, e->P, e->rank), plan);
+  *bytes = plan.need;
   return MC_OK;
+}
+
+mc_status mc_mmdit_set_geometry(mc_mmdit* e, int img_tokens, int latent_f, int latent_h, int latent_w, int txt_len) {
+  if (!e) return fail(MC_EINVAL, "null engine");
+  if (e->begun) return fail(MC_ESTATE, "mc_mmdit_set_geometry between mc_mmdit_begin and mc_mmdit_end");
+  if (e->P > 1)
+    return fail(MC_EINVAL, "mc_mmdit_set_geometry: a sequence-parallel engine (sp_size %d) keeps the geometry it was created with", e->P);
+  const Geometry g = {img_tokens, latent_f, latent_h, latent_w, txt_len};
+  MC_TRY(check_geometry(e->cfg, g, e->P, e->rank));
+  const Rows r = derive_rows(e->cfg.family, g, e->P, e->rank);
+  mc::Workspace plan;
+  plan_workspace(e, r, plan);
+  if (e->work.ws && plan.need > e->work.bound)
+    return fail(MC_EINVAL, "geometry needs a workspace of %zu bytes, %zu bytes are bound (mc_mmdit_set_workspace)", plan.need,
+                e->work.bound);
+  // earlier forwards may still be reading the RoPE table and the buffers of the old plan
+  HIP_TRY(hipDeviceSynchronize());
+  MC_TRY(rope_identity(e, r.Sp));   // the one step that can fail for lack of memory: before anything changes
+  MC_TRY(e->work.replan(plan));
+  apply_geometry(e, g, r);
+  e->cn_double.clear();   // the samples were [img_tokens, d] of the old geometry
+  e->cn_single.clear();
+  return forget_workspace_state(e);
 }
 
 mc_status mc_mmdit_buffer_info(const mc_mmdit* e, const char* name, size_t* offset, size_t* bytes) {

@@ -72,12 +72,55 @@ class MMDiTEngine:
         h = C.c_void_p()
         check(self.lib.mc_mmdit_create(C.byref(c), C.byref(h)))
         self.h = h
-        nbytes = self.lib.mc_mmdit_workspace_bytes(self.h)
-        self.workspace = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
-        off = (-self.workspace.data_ptr()) % 256
-        self.ws = self.workspace[off:off + nbytes]
-        self.ws.zero_()
-        check(self.lib.mc_mmdit_set_workspace(self.h, _ptr(self.ws), nbytes))
+        self._bind(self.lib.mc_mmdit_workspace_bytes(self.h))
+        self._rope_key = None
+        self._controlnet = None
+
+    def _bind(self, nbytes):
+        """a zeroed workspace of `nbytes` (at least the current plan), bound with mc_mmdit_set_workspace; the tensor it
+        replaces is let go after a device synchronise (forwards in flight may still use it)"""
+        workspace = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
+        off = (-workspace.data_ptr()) % 256
+        ws = workspace[off:off + nbytes]
+        ws.zero_()
+        torch.cuda.synchronize(self.device)
+        check(self.lib.mc_mmdit_set_workspace(self.h, _ptr(ws), nbytes))
+        self.workspace, self.ws = workspace, ws
+
+    def geometry_bytes(self, img_tokens, latent_grid=(0, 0, 0), txt_len=None):
+        """workspace bytes the geometry would need (mc_mmdit_geometry_bytes); the engine is not changed"""
+        n = C.c_size_t()
+        f, h, w = (int(v) for v in latent_grid)
+        check(self.lib.mc_mmdit_geometry_bytes(self.h, int(img_tokens), f, h, w,
+                                               int(self.txt_len if txt_len is None else txt_len), C.byref(n)))
+        return n.value
+
+    def reserve(self, geometries):
+        """Size the workspace once for every geometry of the list -- (img_tokens, latent_grid, txt_len) tuples, or dicts
+        with those keys; latent_grid and txt_len may be left out as in set_geometry -- so that set_geometry among them
+        allocates nothing.  The maximum of their needs, not the need of the largest: the plan is not monotone in the token
+        count.  A workspace that has to grow is rebound, which forgets the residual caches like set_geometry does."""
+        need = self.ws.numel()
+        for g in geometries:
+            need = max(need, self.geometry_bytes(**g) if isinstance(g, dict) else self.geometry_bytes(*g))
+        if need > self.ws.numel():
+            self._bind(need)
+        return need
+
+    def set_geometry(self, img_tokens, latent_grid=(0, 0, 0), txt_len=None):
+        """Change the token geometry of the engine between forwards (mc_mmdit_set_geometry): image tokens, the
+        HunyuanVideo latent grid, the text length (None: unchanged).  The weights stay; the workspace stays too when the new
+        plan fits it (see reserve), else a larger one is allocated.  The residual caches, the calibration statistics, the
+        RoPE table and the ControlNet samples are forgotten, and views handed out earlier by buffer() / residual() are
+        invalid: they point into the old plan."""
+        txt_len = int(self.txt_len if txt_len is None else txt_len)
+        grid = tuple(int(v) for v in latent_grid)
+        need = self.geometry_bytes(img_tokens, grid, txt_len)
+        if need > self.ws.numel():
+            self._bind(need)
+        check(self.lib.mc_mmdit_set_geometry(self.h, int(img_tokens), grid[0], grid[1], grid[2], txt_len))
+        self.img_tokens, self.txt_len, self.latent_grid = int(img_tokens), txt_len, grid
+        self.tokens_per_rank = self.img_tokens // self.sp_size
         self._rope_key = None
         self._controlnet = None
 
@@ -295,6 +338,22 @@ def _dispatch(self, *args, **kwargs):
     return type(self).forward(self, *args, **kwargs)
 
 
+def _shim_set_geometry(model, img_tokens, latent_grid, txt_len, fresh):
+    """dynamic_geometry: a call whose shapes differ from the engine's geometry switches the engine first and starts the
+    MagCache state of a new sample, as init_*_magcache would (`fresh`: the family's attributes).  Only between samples:
+    the reference cannot change shapes in the middle of one either (its cached residual has the old shape)."""
+    cnt = int(getattr(model, "cnt", 0))
+    if cnt != 0:
+        raise ValueError(f"geometry change in the middle of a sample (cnt = {cnt}): {model.img_tokens} image / "
+                         f"{model.txt_len} text tokens -> {img_tokens} / {txt_len}")
+    model.engine.set_geometry(img_tokens, latent_grid, txt_len)
+    model.img_tokens, model.txt_len = img_tokens, txt_len
+    if hasattr(model, "cnt"):
+        for k, v in fresh.items():
+            if hasattr(model, k):
+                setattr(model, k, v)
+
+
 # ============================================================================================== FLUX
 def flux_rope(ids, axes_dim=(16, 56, 56), theta=10000.0):
     """diffusers FluxPosEmbed(ids): host float64 angles -> fp32 (cos, sin) [S, 128], each frequency twice."""
@@ -309,15 +368,18 @@ def flux_rope(ids, axes_dim=(16, 56, 56), theta=10000.0):
 
 
 class FluxTransformer2DModelHIP:
-    """Stands where diffusers' FluxTransformer2DModel stands.  One (image tokens, text length) geometry per instance."""
+    """Stands where diffusers' FluxTransformer2DModel stands.  One (image tokens, text length) geometry per instance, unless
+    dynamic_geometry=True: then every call may bring its own (MMDiTEngine.set_geometry)."""
+    dynamic_geometry = False
 
     def __init__(self, cfg, img_tokens, txt_len=512, device="cuda:0", calibration=True, engine=None, sp_rank=0,
-                 sp_size=1, sp_group=None):
+                 sp_size=1, sp_group=None, dynamic_geometry=False):
         self.config = SimpleNamespace(**cfg)
         self.cfg = dict(cfg)
         dim = cfg["attention_head_dim"] * cfg["num_attention_heads"]
         assert cfg["attention_head_dim"] == 128 and cfg.get("guidance_embeds", True)
         self.inner_dim, self.img_tokens, self.txt_len = dim, img_tokens, txt_len
+        self.dynamic_geometry = dynamic_geometry
         self.engine = engine or MMDiTEngine(MC_FAMILY_FLUX, dim, cfg["num_attention_heads"], cfg["num_layers"],
                                             cfg["num_single_layers"], cfg["in_channels"], cfg["in_channels"],
                                             cfg["joint_attention_dim"], txt_len, cfg["pooled_projection_dim"], img_tokens,
@@ -329,6 +391,16 @@ class FluxTransformer2DModelHIP:
     def load_state_dict(self, sd):
         self.engine.load_weights(sd)
         return self
+
+    def _geometry(self, hidden_states, encoder_hidden_states):
+        """dynamic_geometry: follow the call's image tokens / text length (the RoPE comes from the call's ids as always)"""
+        if not self.dynamic_geometry or hidden_states.dim() != 3:
+            return
+        li, lt = int(hidden_states.shape[1]), int(encoder_hidden_states.shape[1])
+        if (li, lt) != (self.img_tokens, self.txt_len):
+            _shim_set_geometry(self, li, (0, 0, 0), lt, dict(accumulated_ratio=1, accumulated_err=0, accumulated_steps=0,
+                                                              previous_residual=None, norm_ratio=[], norm_std=[], cos_dis=[]))
+            self._ids_key = None
 
     def _run(self, hidden_states, encoder_hidden_states, pooled_projections, timestep, img_ids, txt_ids, guidance, mode):
         assert hidden_states.dim() == 3 and hidden_states.shape[0] == 1, "one sample per call, as the FLUX pipeline does"
@@ -366,9 +438,12 @@ def controlnet_sample_index(block, n_blocks, n_samples, blocks_repeat=False):
     return k
 
 
-def _flux_set_controlnet(model, double, single, blocks_repeat):
+def _flux_set_controlnet(model, double, single, blocks_repeat, hidden_states=None, encoder_hidden_states=None):
     """the forward's ControlNet arguments -> the engine, ahead of the forward; a call without samples clears what an earlier
-    call set (and touches nothing when there is nothing to clear)"""
+    call set (and touches nothing when there is nothing to clear).  The engine takes the call's geometry first
+    (dynamic_geometry): the samples are checked against it."""
+    if hidden_states is not None:
+        model._geometry(hidden_states, encoder_hidden_states)
     e = model.engine
     if double is not None or single is not None or getattr(e, "_controlnet", None) is not None:
         e.set_controlnet(double, single, blocks_repeat)
@@ -382,7 +457,8 @@ def flux_plain_forward(self, hidden_states, encoder_hidden_states=None, pooled_p
                        img_ids=None, txt_ids=None, guidance=None, joint_attention_kwargs=None,
                        controlnet_block_samples=None, controlnet_single_block_samples=None, return_dict=True,
                        controlnet_blocks_repeat=False, **_):
-    _flux_set_controlnet(self, controlnet_block_samples, controlnet_single_block_samples, controlnet_blocks_repeat)
+    _flux_set_controlnet(self, controlnet_block_samples, controlnet_single_block_samples, controlnet_blocks_repeat,
+                         hidden_states, encoder_hidden_states)
     out = self._run(hidden_states, encoder_hidden_states, pooled_projections, timestep, img_ids, txt_ids, guidance, MC_MODE_FULL)
     return _flux_output(out, return_dict)
 
@@ -395,7 +471,8 @@ def flux_magcache_forward(self, hidden_states, encoder_hidden_states=None, poole
                           controlnet_block_samples=None, controlnet_single_block_samples=None, return_dict=True,
                           controlnet_blocks_repeat=False):
     """Drop-in for MagCache4FLUX/magcache_flux.py magcache_forward (:234-445)."""
-    _flux_set_controlnet(self, controlnet_block_samples, controlnet_single_block_samples, controlnet_blocks_repeat)
+    _flux_set_controlnet(self, controlnet_block_samples, controlnet_single_block_samples, controlnet_blocks_repeat,
+                         hidden_states, encoder_hidden_states)
     skip_forward = False
     if self.cnt >= int(self.retention_ratio * self.num_steps + 0.5):                       # :333
         cur_scale = self.mag_ratios[self.cnt]
@@ -428,7 +505,8 @@ def flux_magcache_calibration(self, hidden_states, encoder_hidden_states=None, p
                               controlnet_block_samples=None, controlnet_single_block_samples=None, return_dict=True,
                               controlnet_blocks_repeat=False):
     """Drop-in for magcache_flux.py magcache_calibration (:37-232)."""
-    _flux_set_controlnet(self, controlnet_block_samples, controlnet_single_block_samples, controlnet_blocks_repeat)
+    _flux_set_controlnet(self, controlnet_block_samples, controlnet_single_block_samples, controlnet_blocks_repeat,
+                         hidden_states, encoder_hidden_states)
     out = self._run(hidden_states, encoder_hidden_states, pooled_projections, timestep, img_ids, txt_ids, guidance, MC_MODE_CALIB)
     if self.cnt >= 1:                                                                       # :199-207
         norm_ratio, norm_std, cos_dis = self.engine.calib_stats()
@@ -478,12 +556,15 @@ def init_flux_magcache(model, num_inference_steps=28, magcache_thresh=0.24, K=5,
 
 # ============================================================================================== HunyuanVideo
 class HYVideoDiffusionTransformerHIP:
-    """Stands where hyvideo's HYVideoDiffusionTransformer stands.  One latent grid / text length per instance."""
+    """Stands where hyvideo's HYVideoDiffusionTransformer stands.  One latent grid / text length per instance, unless
+    dynamic_geometry=True: then every call may bring its own (MMDiTEngine.set_geometry)."""
+    dynamic_geometry = False
 
     def __init__(self, cfg, latent_grid, txt_len=256, device="cuda:0", calibration=True, engine=None, sp_rank=0,
-                 sp_size=1, sp_group=None):
+                 sp_size=1, sp_group=None, dynamic_geometry=False):
         self.cfg = dict(cfg)
         self.sp_group = sp_group
+        self.dynamic_geometry = dynamic_geometry
         self.patch_size = tuple(cfg.get("patch_size", (1, 2, 2)))
         assert self.patch_size == (1, 2, 2)
         self.hidden_size, self.heads_num = cfg["hidden_size"], cfg["heads_num"]
@@ -502,6 +583,17 @@ class HYVideoDiffusionTransformerHIP:
     def load_state_dict(self, sd):
         self.engine.load_weights(sd)
         return self
+
+    def _geometry(self, x, text_states):
+        """dynamic_geometry: follow the call's latent grid / text length (the RoPE tables come with every call)"""
+        if not self.dynamic_geometry or x.dim() != 5:
+            return
+        grid, lt = tuple(int(v) for v in x.shape[2:]), int(text_states.shape[1])
+        if (grid, lt) != (self.latent_grid, self.txt_len):
+            _shim_set_geometry(self, grid[0] * (grid[1] // 2) * (grid[2] // 2), grid, lt,
+                               dict(accumulated_ratio=1, accumulated_err=0, accumulated_steps=0, residual_cache=None,
+                                    norm_ratio=[], norm_std=[], cos_dis=[]))
+            self.latent_grid = grid
 
     def _run(self, x, t, text_states, text_mask, text_states_2, freqs_cos, freqs_sin, guidance, mode):
         assert x.dim() == 5 and x.shape[0] == 1, "one sample per call, as the HunyuanVideo sampler does"
@@ -526,6 +618,7 @@ def _hy_output(img, return_dict):
 
 def hunyuan_plain_forward(self, x, t, text_states=None, text_mask=None, text_states_2=None, freqs_cos=None,
                           freqs_sin=None, guidance=None, return_dict=True):
+    self._geometry(x, text_states)
     return _hy_output(self._run(x, t, text_states, text_mask, text_states_2, freqs_cos, freqs_sin, guidance, MC_MODE_FULL),
                       return_dict)
 
@@ -536,6 +629,7 @@ HYVideoDiffusionTransformerHIP.forward = hunyuan_plain_forward
 def hunyuan_magcache_forward(self, x, t, text_states=None, text_mask=None, text_states_2=None, freqs_cos=None,
                              freqs_sin=None, guidance=None, return_dict=True):
     """Drop-in for MagCache4HunyuanVideo/magcache_sample_video.py magcache_forward (:29-160)."""
+    self._geometry(x, text_states)
     skip_forward = False
     if self.cnt >= int(self.retention_ratio * self.num_steps):                               # :91
         cur_mag_ratio = self.mag_ratios[self.cnt]
@@ -566,6 +660,7 @@ def hunyuan_magcache_forward(self, x, t, text_states=None, text_mask=None, text_
 def hunyuan_magcache_calibration(self, x, t, text_states=None, text_mask=None, text_states_2=None, freqs_cos=None,
                                  freqs_sin=None, guidance=None, return_dict=True):
     """Drop-in for magcache_sample_video.py magcache_calibration (:162-281)."""
+    self._geometry(x, text_states)
     img = self._run(x, t, text_states, text_mask, text_states_2, freqs_cos, freqs_sin, guidance, MC_MODE_CALIB)
     if self.cnt >= 1:
         norm_ratio, norm_std, cos_dis = self.engine.calib_stats()
@@ -649,11 +744,15 @@ class QwenImageTransformer2DModelHIP:
     """Stands where diffusers' QwenImageTransformer2DModel stands (Qwen-Image and Qwen-Image-Edit: the same transformer;
     Edit's image tokens are the noisy latent's followed by the reference image's).  One (image tokens, longest prompt)
     geometry per instance; every call may carry a shorter prompt (cond vs the " " negative prompt, unpadded).  The two
-    CFG branches keep their own residual cache in the engine (mc_mmdit_forward2)."""
+    CFG branches keep their own residual cache in the engine (mc_mmdit_forward2).  dynamic_geometry=True: the image
+    tokens follow the call and txt_len grows with the longest prompt seen (MMDiTEngine.set_geometry)."""
+    dynamic_geometry = False
 
-    def __init__(self, cfg, img_tokens, txt_len=1024, device="cuda:0", calibration=True, engine=None, sp_size=1):
+    def __init__(self, cfg, img_tokens, txt_len=1024, device="cuda:0", calibration=True, engine=None, sp_size=1,
+                 dynamic_geometry=False):
         self.config = SimpleNamespace(**cfg)
         self.cfg = dict(cfg)
+        self.dynamic_geometry = dynamic_geometry
         dim = cfg["attention_head_dim"] * cfg["num_attention_heads"]
         assert cfg["attention_head_dim"] == 128 and not cfg.get("guidance_embeds", False)
         out = cfg["patch_size"] ** 2 * cfg["out_channels"]
@@ -675,6 +774,19 @@ class QwenImageTransformer2DModelHIP:
         # pipeline form: [[(1, h, w)]] per batch entry (Edit: [[(1, h, w), (1, h_ref, w_ref)]]); a bare [(1, h, w)] too
         shapes = img_shapes[0] if isinstance(img_shapes[0], list) else img_shapes
         return [tuple(int(v) for v in s) for s in shapes]
+
+    def _geometry(self, hidden_states, encoder_hidden_states, txt_seq_lens):
+        """dynamic_geometry: follow the call's image tokens; txt_len stays the MAXIMUM, so only a prompt longer than it
+        changes the geometry (a shorter one is this call's txt_valid, as always)"""
+        if not self.dynamic_geometry or hidden_states.dim() != 3:
+            return
+        li = int(hidden_states.shape[1])
+        n = int(txt_seq_lens[0]) if txt_seq_lens is not None else int(encoder_hidden_states.shape[1])
+        if li != self.img_tokens or n > self.txt_len:
+            _shim_set_geometry(self, li, (0, 0, 0), max(n, self.txt_len),
+                               dict(accumulated_err=[0.0, 0.0], accumulated_steps=[0, 0], accumulated_ratio=[1.0, 1.0],
+                                    residual_cache=[None, None], norm_ratio=[], norm_std=[], cos_dis=[]))
+            self._shapes_key = None
 
     def _run(self, hidden_states, encoder_hidden_states, timestep, img_shapes, txt_seq_lens, mode, branch):
         assert hidden_states.dim() == 3 and hidden_states.shape[0] == 1, "one sample per call, as the Qwen-Image pipeline does"
@@ -698,6 +810,7 @@ class QwenImageTransformer2DModelHIP:
 
 def qwen_plain_forward(self, hidden_states, encoder_hidden_states=None, encoder_hidden_states_mask=None, timestep=None,
                        img_shapes=None, txt_seq_lens=None, guidance=None, attention_kwargs=None, return_dict=True, **_):
+    self._geometry(hidden_states, encoder_hidden_states, txt_seq_lens)
     out = self._run(hidden_states, encoder_hidden_states, timestep, img_shapes, txt_seq_lens, MC_MODE_FULL, 0)
     return _flux_output(out, return_dict)
 
@@ -709,6 +822,7 @@ def qwen_magcache_forward(self, hidden_states, encoder_hidden_states=None, encod
                           img_shapes=None, txt_seq_lens=None, guidance=None, attention_kwargs=None, return_dict=True):
     """Drop-in for MagCache4QwenImage/magcache_generate.py magcache_forward (:173-253): calls alternate cond / uncond
     (branch cnt % 2), strict `<`, and the accumulators are NOT reset when cnt wraps."""
+    self._geometry(hidden_states, encoder_hidden_states, txt_seq_lens)
     cnt = int(self.cnt)
     b = cnt % 2
     skip_forward = False
@@ -739,6 +853,7 @@ def qwen_magcache_calibration(self, hidden_states, encoder_hidden_states=None, e
                               return_dict=True):
     """Drop-in for magcache_generate.py magcache_calibration (:94-171): statistics against the same branch's previous
     residual from the third call on."""
+    self._geometry(hidden_states, encoder_hidden_states, txt_seq_lens)
     cnt = int(self.cnt)
     b = cnt % 2
     out = self._run(hidden_states, encoder_hidden_states, timestep, img_shapes, txt_seq_lens, MC_MODE_CALIB, b)

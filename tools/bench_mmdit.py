@@ -8,6 +8,12 @@ headline bench line):
     python tools/bench_mmdit.py flux --controlnet 5,10
                                           FLUX.1-dev 1024x1024, one full forward with 5 double + 10 single random bf16
                                           ControlNet samples vs the same forward without, alternating, ms per forward
+    python tools/bench_mmdit.py flux --regeometry 512x512,1024x1024
+    python tools/bench_mmdit.py qwen --regeometry 1664x928,928x1664
+                                          ONE engine (one copy of the weights) switched between the image sizes with
+                                          MMDiTEngine.set_geometry, against a fresh engine per size: per size the full-forward
+                                          time of both (alternating windows), the set_geometry time with and without reserve(),
+                                          the workspace bytes, and the HBM the weights hold once (`--depth D,S`: fewer blocks)
 
 Synthetic inputs, seeded random-init weights of the real architecture (no checkpoints offline).  One JSON line each.
 Also checks the size-independent MagCache properties at full size: a skipped forward equals the final layer applied
@@ -238,6 +244,88 @@ def bench_hunyuan():
                       "workspace_gb": e.workspace.numel() / 2 ** 30}))
 
 
+def bench_regeometry(which, sizes, depth=None, rounds=7, per_round=4):
+    """`sizes`: [(width, height)] in pixels; image tokens (H/16) * (W/16) for both families.  Engine-level forwards (the
+    shims add host work only).  Windows of `per_round` full forwards alternate between a fresh engine created at the size
+    and the one engine that is switched from size to size; host clock around a device synchronise."""
+    from magcache_amd.qwen_bench import random_state_dict
+    flux = which == "flux"
+    cfg = dict(MM.FLUX_DEV if flux else MM.QWEN_IMAGE)
+    if depth:
+        cfg.update(num_layers=depth[0], **({"num_single_layers": depth[1]} if flux else {}))
+    txt_len = 512
+    grids = [(h // 16, w // 16) for w, h in sizes]
+
+    def make(grid):
+        free0 = torch.cuda.mem_get_info()[0]
+        if flux:
+            m = MM.FluxTransformer2DModelHIP(cfg, grid[0] * grid[1], txt_len=txt_len, device=DEV, calibration=False)
+            synth_load(m, flux_names(cfg))
+        else:
+            m = MM.QwenImageTransformer2DModelHIP(cfg, grid[0] * grid[1], txt_len=txt_len, device=DEV, calibration=False)
+            m.engine.load_weights(random_state_dict(cfg, DEV))
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        return m.engine, free0 - torch.cuda.mem_get_info()[0] - m.engine.workspace.numel()
+
+    def inputs(grid):
+        h2, w2 = grid
+        g = torch.Generator(device=DEV).manual_seed(h2 * 1000 + w2)
+        img = torch.randn(h2 * w2, 64, generator=g, device=DEV)
+        txt = torch.randn(txt_len, cfg["joint_attention_dim"], generator=g, device=DEV)
+        if flux:
+            ids = torch.zeros(txt_len + h2 * w2, 3)
+            ids[txt_len:, 1] = torch.arange(h2).repeat_interleave(w2)
+            ids[txt_len:, 2] = torch.arange(w2).repeat(h2)
+            return img, txt, torch.randn(768, generator=g, device=DEV), MM.flux_rope(ids)
+        return img, txt, None, MM.qwen_rope([(1, h2, w2)], txt_len)
+
+    def forward(e, inp):
+        return lambda: e.forward(inp[0], 500.0, 3500.0, inp[1], txt_len, inp[2], branch=None if flux else 0)
+
+    def switch(e, grid, inp):
+        ptr = e.workspace.data_ptr()
+        t_geo, _ = timed(lambda: e.set_geometry(grid[0] * grid[1], (0, 0, 0), txt_len))
+        t_rope, _ = timed(lambda: e.set_rope(*inp[3]))
+        return {"set_geometry_ms": t_geo * 1e3, "set_rope_ms": t_rope * 1e3, "reallocated": e.workspace.data_ptr() != ptr}
+
+    order = sorted(range(len(grids)), key=lambda i: grids[i][0] * grids[i][1])
+    one, weight_bytes = make(grids[order[0]])                  # created at the smallest size: every first switch grows
+    data = {i: inputs(grids[i]) for i in range(len(grids))}
+    no_reserve = {}
+    for i in order[1:]:
+        no_reserve["%dx%d" % sizes[i]] = switch(one, grids[i], data[i])
+    one.reserve([(gr[0] * gr[1], (0, 0, 0), txt_len) for gr in grids])
+    res = []
+    for i in range(len(grids)):
+        fresh, _ = make(grids[i])
+        fresh.set_rope(*data[i][3])
+        sw = switch(one, grids[i], data[i])
+        f_fresh, f_one = forward(fresh, data[i]), forward(one, data[i])
+        same = bool(torch.equal(f_fresh(), f_one()))
+        for f in (f_fresh, f_one):
+            timed(f, 2)
+        ms = {"fresh": [], "switched": []}
+        for _ in range(rounds):
+            ms["fresh"].append(timed(f_fresh, per_round)[0] * 1e3)
+            ms["switched"].append(timed(f_one, per_round)[0] * 1e3)
+        res.append({"size": "%dx%d" % sizes[i], "img_tokens": grids[i][0] * grids[i][1],
+                    "forward_ms_fresh": float(np.median(ms["fresh"])), "forward_ms_switched": float(np.median(ms["switched"])),
+                    "windows_fresh_ms": [round(v, 3) for v in ms["fresh"]], "windows_switched_ms": [round(v, 3) for v in ms["switched"]],
+                    "fresh_window_spread_ms": float(max(ms["fresh"]) - min(ms["fresh"])), "bitwise_equal_to_fresh": same,
+                    "switch_with_reserve": sw, "workspace_bytes": one.geometry_bytes(grids[i][0] * grids[i][1], (0, 0, 0), txt_len),
+                    "workspace_bytes_fresh_engine": fresh.workspace.numel() - 256})
+        del fresh, f_fresh
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+    print(json.dumps({"config": f"{'FLUX.1-dev' if flux else 'Qwen-Image'} {cfg['num_layers']} double"
+                                f"{' + %d single' % cfg['num_single_layers'] if flux else ''} blocks, one engine over "
+                                f"{', '.join('%dx%d' % s for s in sizes)}, {txt_len} text tokens, synthetic weights/inputs",
+                      "forwards_per_window": per_round, "weight_bytes_held_once": weight_bytes,
+                      "weight_bytes_one_engine_per_size": weight_bytes * len(sizes), "reserved_workspace_bytes": one.ws.numel(),
+                      "switch_without_reserve": no_reserve, "per_size": res}))
+
+
 if __name__ == "__main__":
     lib = load()
     which = sys.argv[1] if len(sys.argv) > 1 else "flux"
@@ -245,7 +333,13 @@ if __name__ == "__main__":
         from magcache_amd._lib import check
         check(lib.mc_set_option(b"mmdit_two_streams", 1))
         print("mmdit_two_streams = 1")
-    if "--controlnet" in sys.argv[2:]:
+    if "--regeometry" in sys.argv[2:]:
+        if which not in ("flux", "qwen"):
+            sys.exit(f"--regeometry benches FLUX and Qwen-Image, not '{which}'")
+        sizes = [tuple(int(v) for v in g.split("x")) for g in sys.argv[sys.argv.index("--regeometry") + 1].split(",")]
+        depth = [int(v) for v in sys.argv[sys.argv.index("--depth") + 1].split(",")] if "--depth" in sys.argv else None
+        bench_regeometry(which, sizes, depth)
+    elif "--controlnet" in sys.argv[2:]:
         if which != "flux":
             sys.exit(f"--controlnet benches FLUX (ControlNet residuals are a FLUX input), not '{which}'")
         n_d, n_s = (int(v) for v in sys.argv[sys.argv.index("--controlnet") + 1].split(","))
