@@ -16,6 +16,8 @@ using mc::bf16_t;
 using mc::fail;
 using mc::gp;
 using mc::Linear;
+using mc::RowRange;
+using mc::whole;
 
 namespace {
 
@@ -148,36 +150,9 @@ void rope_table_host(int F, int Hp, int Wp, int tok0, int n_tok, float* cs) {
   }
 }
 
-// One Linear [n_out, k_in] of a block: the bf16 weight + fp32 bias and, quant != QUANT_NONE, an e4m3 copy of the weight.
-// `parts` names the upstream Linears whose rows are stacked in it in equal shares (q | k | v -> qkv); every part's slot
-// carries the quantised copy, so that setting a part requantises its rows of the fused destination.
-enum Quant { QUANT_NONE, QUANT_ROW, QUANT_MX };   // one scale per output channel | one E8M0 byte per (channel, 32 inputs)
-
-mc_status add_linear(mc_engine* e, Linear& l, const std::string& prefix, std::initializer_list<const char*> parts,
-                     size_t n_out, size_t k_in, Quant quant) {
-  mc::WeightStore& w = e->weights;
-  l.n_out = (int)n_out; l.k_in = (int)k_in;
-  MC_TRY(w.alloc(&l.w, n_out * k_in));
-  MC_TRY(w.alloc(&l.b, n_out));
-  if (quant != QUANT_NONE) MC_TRY(w.alloc(&l.q, n_out * k_in));
-  if (quant == QUANT_ROW) MC_TRY(w.alloc(&l.q_scale, n_out));
-  if (quant == QUANT_MX) MC_TRY(w.alloc(&l.mx, (k_in / 32) * n_out));
-  const size_t rows = n_out / parts.size();
-  size_t row0 = 0;
-  for (const char* part : parts) {
-    mc::Slot& s = w.add_linear(prefix + part, l.w, l.b, rows, k_in, row0);
-    s.q8 = l.q; s.q8_scale = l.q_scale; s.q8_k = k_in; s.mx = l.mx; s.mx_rows = n_out;
-    row0 += rows;
-  }
-  return MC_OK;
-}
-
 mc_status check_ready(const mc_engine* e) {
   if (!e) return fail(MC_EINVAL, "null engine");
-  if (!e->work.ws) return fail(MC_ESTATE, "workspace not set (mc_set_workspace)");
-  const char* name = nullptr;
-  if (!e->weights.all_loaded(&name)) return fail(MC_ESTATE, "weight '%s' was never set", name);
-  return MC_OK;
+  return mc::check_ready(e->work, e->weights, "mc_set_workspace");
 }
 
 }  // namespace
@@ -256,8 +231,8 @@ mc_status mc_create(const mc_config* cfg, mc_engine** out) {
 #define ALLOC(ptr, n) MC_TRY(W.alloc(&(ptr), (n)))
   // fp8_linear only decides which Linears keep an e4m3 copy and of which kind: 1 = QKV, FFN-1, FFN-2 with per-row scales,
   // 2 = the same three with MX block scales, 3 = MX, the d x d Linears (self-attention O, cross-attention Q and O) too
-  const Quant q_big = c.fp8_linear >= 2 ? QUANT_MX : c.fp8_linear == 1 ? QUANT_ROW : QUANT_NONE;
-  const Quant q_dd = c.fp8_linear == 3 ? QUANT_MX : QUANT_NONE;
+  const mc::Quant q_big = c.fp8_linear >= 2 ? mc::QUANT_MX : c.fp8_linear == 1 ? mc::QUANT_ROW : mc::QUANT_NONE;
+  const mc::Quant q_dd = c.fp8_linear == 3 ? mc::QUANT_MX : mc::QUANT_NONE;
   e->layers.resize(e->NL);
   e->NV = c.vace_layers;
   e->vlayers.resize(e->NV);
@@ -265,13 +240,13 @@ mc_status mc_create(const mc_config* cfg, mc_engine** out) {
     const bool is_vace = i >= e->NL;
     Layer& l = is_vace ? e->vlayers[i - e->NL] : e->layers[i];
     const std::string p = (is_vace ? "vace_blocks." + std::to_string(i - e->NL) : "blocks." + std::to_string(i)) + ".";
-    MC_TRY(add_linear(e, l.qkv, p + "self_attn.", {"q", "k", "v"}, 3 * d, d, q_big));
-    MC_TRY(add_linear(e, l.o, p + "self_attn.", {"o"}, d, d, q_dd));
-    MC_TRY(add_linear(e, l.cq, p + "cross_attn.", {"q"}, d, d, q_dd));
-    MC_TRY(add_linear(e, l.ckv, p + "cross_attn.", {"k", "v"}, 2 * d, d, QUANT_NONE));
-    MC_TRY(add_linear(e, l.co, p + "cross_attn.", {"o"}, d, d, q_dd));
-    MC_TRY(add_linear(e, l.ffn1, p + "ffn.", {"0"}, ffn, d, q_big));
-    MC_TRY(add_linear(e, l.ffn2, p + "ffn.", {"2"}, d, ffn, q_big));
+    MC_TRY(W.add_linear(l.qkv, p + "self_attn.", {{"q", d}, {"k", d}, {"v", d}}, d, q_big));
+    MC_TRY(W.add_linear(l.o, p + "self_attn.", {{"o", d}}, d, q_dd));
+    MC_TRY(W.add_linear(l.cq, p + "cross_attn.", {{"q", d}}, d, q_dd));
+    MC_TRY(W.add_linear(l.ckv, p + "cross_attn.", {{"k", d}, {"v", d}}, d));
+    MC_TRY(W.add_linear(l.co, p + "cross_attn.", {{"o", d}}, d, q_dd));
+    MC_TRY(W.add_linear(l.ffn1, p + "ffn.", {{"0", ffn}}, d, q_big));
+    MC_TRY(W.add_linear(l.ffn2, p + "ffn.", {{"2", d}}, ffn, q_big));
     ALLOC(l.nq, d); ALLOC(l.nk, d); ALLOC(l.n3w, d); ALLOC(l.n3b, d); ALLOC(l.cnq, d); ALLOC(l.cnk, d); ALLOC(l.mod, 6 * d);
     W.add(p + "self_attn.norm_q.weight", l.nq, MC_F32, d);
     W.add(p + "self_attn.norm_k.weight", l.nk, MC_F32, d);
@@ -281,7 +256,7 @@ mc_status mc_create(const mc_config* cfg, mc_engine** out) {
     W.add(p + "cross_attn.norm_k.weight", l.cnk, MC_F32, d);
     W.add(p + "modulation", l.mod, MC_F32, 6 * d);
     if (c.clip_dim > 0) {
-      MC_TRY(add_linear(e, l.ckv_img, p + "cross_attn.", {"k_img", "v_img"}, 2 * d, d, QUANT_NONE));
+      MC_TRY(W.add_linear(l.ckv_img, p + "cross_attn.", {{"k_img", d}, {"v_img", d}}, d));
       ALLOC(l.cnk_img, d);
       W.add(p + "cross_attn.norm_k_img.weight", l.cnk_img, MC_F32, d);
     }
@@ -627,9 +602,6 @@ mc_status mc_embed(mc_engine* e, const float* latent_dev, const float* t_dev, do
 }
 
 // ---- the one launch path of a block's Linears
-struct RowRange { int first, count; };   // output channels of a Linear: all of them, or k|v / q of the fused q|k|v
-static RowRange whole(const Linear& l) { return {0, l.n_out}; }
-
 // The activation rows [Lp, k_in] a Linear reads.  A bf16 Linear reads `rows`.  An fp8 Linear reads e4m3 rows + scales:
 // it quantises `rows` into "aq" (+ "a_scale" | "a_mx") first, unless they are `quantised` already -- there by a fused producer
 // or an earlier Linear over the same rows, or, q / mx given, in the caller's buffers (FFN-1's GELU epilogue writes FFN-2's).
@@ -645,12 +617,11 @@ struct ActSrc {
 // activations per (token, 32 k), weights per (channel, 32 k) -- multiplied inside the matrix core (launch_gemm_mxfp8).
 static mc_status linear(mc_engine* e, const Linear& l, RowRange out, ActSrc a, mc::GemmParams p, int epi, hipStream_t s) {
   const int Lp = e->Lp, K = l.k_in;
-  p.M = Lp; p.N = out.count; p.K = K; p.bias = l.b + out.first;
   if (!l.q) {
-    p.A = a.rows; p.lda = a.ld; p.W = l.w + (size_t)out.first * K; p.ldw = K;
-    HIP_TRY(mc::launch_gemm_bf16(p, epi, s));
+    HIP_TRY(mc::launch_linear_bf16(l, out, a.rows, a.ld, Lp, p, epi, s));
     return MC_OK;
   }
+  p.M = Lp; p.N = out.count; p.K = K; p.bias = l.b + out.first;
   uint8_t* aq = a.q ? a.q : e->buf<uint8_t>("aq");
   p.A = (const bf16_t*)aq; p.lda = K; p.W = (const bf16_t*)(l.q + (size_t)out.first * K); p.ldw = K;
   if (l.mx) {

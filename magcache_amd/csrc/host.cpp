@@ -35,9 +35,34 @@ Slot& WeightStore::add(const std::string& name, void* dst, mc_dtype dt, size_t n
   return slots[name] = s;
 }
 
-Slot& WeightStore::add_linear(const std::string& prefix, bf16_t* w, float* b, size_t n_out, size_t n_in, size_t row_off) {
-  add(prefix + ".bias", b, MC_F32, n_out, row_off);
-  return add(prefix + ".weight", w, MC_BF16, n_out * n_in, row_off * n_in);
+mc_status WeightStore::alloc_linear(Linear& l, size_t n_out, size_t k_in, Quant quant) {
+  l.n_out = (int)n_out; l.k_in = (int)k_in;
+  MC_TRY(alloc(&l.w, n_out * k_in));
+  MC_TRY(alloc(&l.b, n_out));
+  if (quant != QUANT_NONE) MC_TRY(alloc(&l.q, n_out * k_in));
+  if (quant == QUANT_ROW) MC_TRY(alloc(&l.q_scale, n_out));
+  if (quant == QUANT_MX) MC_TRY(alloc(&l.mx, (k_in / 32) * n_out));
+  return MC_OK;
+}
+
+Slot& WeightStore::add_parts(const Linear& l, const std::string& prefix, const std::vector<Part>& parts, size_t row0) {
+  const size_t k = l.k_in;
+  Slot* last = nullptr;
+  for (const Part& part : parts) {
+    add(prefix + part.name + ".bias", l.b, MC_F32, part.rows, row0);
+    last = &add(prefix + part.name + ".weight", l.w, MC_BF16, part.rows * k, row0 * k);
+    last->q8 = l.q; last->q8_scale = l.q_scale; last->q8_k = k; last->mx = l.mx; last->mx_rows = l.n_out;
+    row0 += part.rows;
+  }
+  return *last;
+}
+
+mc_status WeightStore::add_linear(Linear& l, const std::string& prefix, const std::vector<Part>& parts, size_t k_in, Quant quant) {
+  size_t n_out = 0;
+  for (const Part& part : parts) n_out += part.rows;
+  MC_TRY(alloc_linear(l, n_out, k_in, quant));
+  add_parts(l, prefix, parts);
+  return MC_OK;
 }
 
 mc_status WeightStore::set(const char* name, const void* src_dev, mc_dtype dtype, const int64_t* shape, int ndim,
@@ -174,6 +199,20 @@ char* Workspace::ptr(const char* name) const {
     return nullptr;
   }
   return ws + b->off;
+}
+
+// ------------------------------------------------------------------------------------------------ shared by the engines
+mc_status check_ready(const Workspace& work, const WeightStore& weights, const char* set_workspace) {
+  if (!work.ws) return fail(MC_ESTATE, "workspace not set (%s)", set_workspace);
+  const char* name = nullptr;
+  if (!weights.all_loaded(&name)) return fail(MC_ESTATE, "weight '%s' was never set", name);
+  return MC_OK;
+}
+
+hipError_t launch_linear_bf16(const Linear& l, RowRange out, const bf16_t* A, long lda, int M, GemmParams p, int epi, hipStream_t s) {
+  p.A = A; p.lda = lda; p.M = M; p.N = out.count; p.K = l.k_in;
+  p.W = l.w + (size_t)out.first * l.k_in; p.ldw = l.k_in; p.bias = l.b + out.first;
+  return launch_gemm_bf16(p, epi, s);
 }
 
 }  // namespace mc

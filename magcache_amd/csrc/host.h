@@ -54,6 +54,10 @@ struct Linear {
   float* q_scale = nullptr;
   uint8_t* mx = nullptr;
 };
+enum Quant { QUANT_NONE, QUANT_ROW, QUANT_MX };   // one scale per output channel | one E8M0 byte per (channel, 32 inputs)
+struct Part { std::string name; size_t rows; };   // an upstream Linear whose rows are stacked into a fused one (q | k | v -> qkv)
+struct RowRange { int first, count; };            // output channels of a Linear: all of them, or k|v / q of the fused q|k|v
+inline RowRange whole(const Linear& l) { return {0, l.n_out}; }
 
 struct Slot {  // one named parameter
   void* dst = nullptr;
@@ -79,9 +83,14 @@ struct WeightStore {
   template <class T>
   mc_status alloc(T** p, size_t n) { return alloc_bytes(reinterpret_cast<void**>(p), n * sizeof(T)); }
   Slot& add(const std::string& name, void* dst, mc_dtype dt, size_t numel, size_t off = 0);
-  // "<prefix>.weight" [n_out, n_in] (bf16) and "<prefix>.bias" [n_out] (fp32) at row row_off of fused destinations; returns
-  // the weight's slot
-  Slot& add_linear(const std::string& prefix, bf16_t* w, float* b, size_t n_out, size_t n_in, size_t row_off = 0);
+  // One Linear [sum of the parts' rows, k_in]: allocates the bf16 weight + fp32 bias (and, quant != QUANT_NONE, the e4m3 copy
+  // with its scales) and registers the parts.  alloc_linear / add_parts are its two halves, for a Linear whose parts are
+  // added one by one (the fused modulation matrix) or whose slot the caller adjusts (Slot::pad, Slot::perm_c).
+  mc_status add_linear(Linear& l, const std::string& prefix, const std::vector<Part>& parts, size_t k_in, Quant quant = QUANT_NONE);
+  mc_status alloc_linear(Linear& l, size_t n_out, size_t k_in, Quant quant = QUANT_NONE);
+  // "<prefix><part>.weight" [rows, k_in] (bf16) and "<prefix><part>.bias" [rows] (fp32) of every part, stacked from row row0 of
+  // `l`; every slot carries the quantised copy, so that setting a part requantises its rows.  Returns the last weight's slot.
+  Slot& add_parts(const Linear& l, const std::string& prefix, const std::vector<Part>& parts, size_t row0 = 0);
   // copy / cast / permute / pad one parameter into place (and requantise its rows) on the caller's stream
   mc_status set(const char* name, const void* src_dev, mc_dtype dtype, const int64_t* shape, int ndim, hipStream_t stream);
   int missing(char* buf, size_t buflen) const;  // count; names, one per line, as far as buf holds them
@@ -118,5 +127,13 @@ struct Workspace {
  private:
   char* ptr(const char* name) const;  // null (and the error text) for a name that is not in the plan
 };
+
+// what every entry point that launches needs: a bound workspace and every weight set (`set_workspace` names the call that
+// binds one, for the error text)
+mc_status check_ready(const Workspace& work, const WeightStore& weights, const char* set_workspace);
+
+// y[:, out] = epilogue(A W[out]^T + b[out]) on bf16 operands: p carries what the epilogue needs, the operands, the shape and
+// every pointer advance of a row range come from `l`
+hipError_t launch_linear_bf16(const Linear& l, RowRange out, const bf16_t* A, long lda, int M, GemmParams p, int epi, hipStream_t s);
 
 }  // namespace mc

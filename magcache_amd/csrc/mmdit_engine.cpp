@@ -31,7 +31,14 @@
 //                           rows are the cache, the text rows are scratch
 // GEMMs over one stream use the exact row count (the 256^2 kernel guards a partial last tile), so neighbouring
 // rows of the other stream are never touched.
+//
+// Host structure (the Wan engine's, host.h): every weight matrix is an mc::Linear that WeightStore::add_linear allocates and
+// registers under its upstream names; every GEMM goes through linear(), which takes operands and shape from the descriptor
+// (a second Linear makes it the row-split launch over two row ranges); a double block is double_pre / double_post over one
+// or two row ranges (Range) -- both streams in merged launches by default, one stream per call for the two-stream modes and
+// sequence parallel; every attention launch is attend() over a key set (Keys).
 #include <cmath>
+#include <memory>
 
 #include "../../include/magcache_mmdit.h"
 #include "host.h"
@@ -39,7 +46,7 @@
 using mc::align_up;
 using mc::bf16_t;
 using mc::fail;
-using mc::gp;
+using mc::Linear;
 
 namespace mc {
 // mc_set_option("mmdit_two_streams", v): 0 = off (the DEFAULT since round 3: the packed-fp32 co-execution fault behind
@@ -53,21 +60,19 @@ using mc::g_mmdit_two_streams;
 namespace {
 
 struct Stream {  // one stream (image or text) of a double block
-  bf16_t *wqkv, *wo, *w1, *w2;
-  float *bqkv, *bo, *b1, *b2, *qn, *kn;
+  Linear qkv, o, fc1, fc2;
+  float *qn, *kn;
 };
 struct Single {
-  bf16_t *w_in, *w_out;  // w_in = [q;k;v;mlp] rows [7d, d]; w_out [d, 5d]
-  float *b_in, *b_out, *qn, *kn;
+  Linear in, out;  // in = [q;k;v;mlp] rows [7d, d]; out [d, 5d]
+  float *qn, *kn;
 };
 struct Mlp2 {  // Linear, SiLU, Linear on a vector
-  bf16_t *w1, *w2;
-  float *b1, *b2;
-  int k_in;
+  Linear l1, l2;
 };
 struct Refiner {
-  bf16_t *wqkv, *wo, *w1, *w2, *wada;
-  float *bqkv, *bo, *b1, *b2, *bada, *n1w, *n1b, *n2w, *n2b;
+  Linear qkv, o, fc1, fc2, ada;
+  float *n1w, *n1b, *n2w, *n2b;
 };
 
 }  // namespace
@@ -91,8 +96,8 @@ struct mc_mmdit {
   std::vector<Single> singles;
   std::vector<Refiner> refiners;
   Mlp2 time_mlp, guid_mlp, vec_mlp, ref_t_mlp, ref_c_mlp;
-  bf16_t *w_in = nullptr, *w_ctx = nullptr, *w_mod = nullptr;
-  float *b_in = nullptr, *b_ctx = nullptr, *b_mod = nullptr, *w_head = nullptr, *b_head = nullptr;
+  Linear img_in, txt_in, mod;   // image embedder [d, Kp], text embedder [d, txt_dim], fused modulation matrix [mod_rows, d]
+  float *w_head = nullptr, *b_head = nullptr;
   float* w_txt_norm = nullptr;  // Qwen-Image txt_norm (RMSNorm over txt_dim)
   float* cs = nullptr;  // RoPE (cos,sin) [Sp][64][2]
   int cs_rows = 0;      // rows allocated behind cs (>= Sp: mc_mmdit_set_geometry grows it, never shrinks it)
@@ -121,34 +126,32 @@ struct mc_mmdit {
 
 namespace {
 
-// every GEMM of the engine: the split-K scratch of the stream it runs on rides along (launch_gemm_bf16 decides by shape
-// whether to use it: the projections back to d at FLUX sizes do, nothing at HunyuanVideo's 119 k tokens does)
-hipError_t gemm(const mc_mmdit* e, mc::GemmParams p, int epi, hipStream_t s) {
+// Every GEMM of the engine: y = epilogue(A l.w^T + l.b) over M rows, operands and shape from the descriptor, p carrying what
+// the epilogue needs.  `lb` makes it the row-split launch over two row ranges of the same buffers: rows >= m_split use lb's
+// weight and bias and gate_b.  The split-K scratch of the stream it runs on rides along (launch_gemm_bf16 decides by shape
+// whether to use it: the projections back to d at FLUX sizes do, nothing at HunyuanVideo's 119 k tokens does).
+mc_status linear(const mc_mmdit* e, const Linear& l, int M, const bf16_t* A, long lda, mc::GemmParams p, int epi, hipStream_t s,
+                 const Linear* lb = nullptr, int m_split = 0, const float* gate_b = nullptr) {
+  if (l.q || (lb && lb->q)) return fail(MC_ESTATE, "the MM-DiT engine has no fp8 Linears");
   const mc::Buf* b = e->work.find((e->side && s == e->side) ? "splitk1" : "splitk0");
   if (b && b->bytes > 0 && e->work.ws) {
     p.splitk_ws = reinterpret_cast<float*>(e->work.ws + b->off);
     p.splitk_ws_bytes = b->bytes;
   }
-  return mc::launch_gemm_bf16(p, epi, s);
-}
-
-#define ALLOC(ptr, n) MC_TRY(e->weights.alloc(&(ptr), (n)))
-
-mc_status alloc_mlp2(mc_mmdit* e, Mlp2& m, int k_in, const std::string& l1, const std::string& l2) {
-  const size_t d = e->d;
-  m.k_in = k_in;
-  ALLOC(m.w1, d * k_in); ALLOC(m.b1, d); ALLOC(m.w2, d * d); ALLOC(m.b2, d);
-  e->weights.add_linear(l1, m.w1, m.b1, d, k_in);
-  e->weights.add_linear(l2, m.w2, m.b2, d, d);
+  if (lb) { p.m_split = m_split; p.W_b = lb->w; p.bias_b = lb->b; p.gate_b = gate_b; }
+  HIP_TRY(mc::launch_linear_bf16(l, mc::whole(l), A, lda, M, p, epi, s));
   return MC_OK;
 }
 
-mc_status alloc_stream(mc_mmdit* e, Stream& s) {
-  const size_t d = e->d;
-  ALLOC(s.wqkv, 3 * d * d); ALLOC(s.bqkv, 3 * d); ALLOC(s.wo, d * d); ALLOC(s.bo, d);
-  ALLOC(s.w1, 4 * d * d); ALLOC(s.b1, 4 * d); ALLOC(s.w2, 4 * d * d); ALLOC(s.b2, d);
-  ALLOC(s.qn, 128); ALLOC(s.kn, 128);
-  return MC_OK;
+// the gated residual epilogue on rows [row0, ..) of "x": x += gate * y, and with a capture destination (joint row index, the
+// LAST block's output GEMM) the MagCache residual R = x_new - x0 as well.  Returns the epilogue to launch with.
+int resid_epi(const mc_mmdit* e, mc::GemmParams& p, int row0, const float* gate, float* capture_to) {
+  const size_t off = (size_t)row0 * e->d;
+  p.X = e->buf<float>("x") + off; p.ldx = e->d; p.gate = gate;
+  if (!capture_to) return mc::EPI_RESID_GATE;
+  p.X0 = e->buf<bf16_t>("x0") + off; p.ldx0 = e->d;
+  p.R = capture_to + off; p.ldr = e->d;
+  return mc::EPI_RESID_CAPTURE;
 }
 
 // ---------------------------------------------------------------------------------------------- token geometry
@@ -296,7 +299,8 @@ mc_status mc_mmdit_create(const mc_mmdit_config* cfg, mc_mmdit** out) {
   const Geometry geo = {c.img_tokens, c.latent_f, c.latent_h, c.latent_w, c.txt_len};
   const int P = c.sp_size > 0 ? c.sp_size : 1;
   MC_TRY(check_geometry(c, geo, P, c.sp_rank));
-  mc_mmdit* e = new mc_mmdit();
+  std::unique_ptr<mc_mmdit, void (*)(mc_mmdit*)> own(new mc_mmdit(), mc_mmdit_destroy);   // every early return frees it
+  mc_mmdit* e = own.get();
   e->cfg = c;
   e->P = P;
   e->rank = c.sp_rank;
@@ -308,154 +312,137 @@ mc_status mc_mmdit_create(const mc_mmdit_config* cfg, mc_mmdit** out) {
   e->out_feat = hy ? c.out_channels * 4 : c.out_channels;
   const size_t d = e->d;
   const bool flux = c.family == MC_FAMILY_FLUX;
-  auto cleanup = [&](mc_status st) { mc_mmdit_destroy(e); return st; };
-#define TRY_C(expr) do { mc_status _s = (expr); if (_s != MC_OK) return cleanup(_s); } while (0)
-#undef ALLOC
-#define ALLOC(ptr, n) TRY_C(e->weights.alloc(&(ptr), (n)))
+  mc::WeightStore& W = e->weights;
+  auto vec128 = [&](float*& v, const std::string& name) {   // a per-head norm weight
+    MC_TRY(W.alloc(&v, 128));
+    W.add(name, v, MC_F32, 128);
+    return MC_OK;
+  };
+  auto mlp2 = [&](Mlp2& m, size_t k_in, const std::string& l1, const std::string& l2) {
+    MC_TRY(W.add_linear(m.l1, l1, {{"", d}}, k_in));
+    return W.add_linear(m.l2, l2, {{"", d}}, d);
+  };
 
   // ---- embeds
-  ALLOC(e->w_in, d * e->Kp); ALLOC(e->b_in, d);
-  if (hipMemset(e->w_in, 0, d * e->Kp * 2) != hipSuccess) return cleanup(fail(MC_EHIP, "hipMemset failed"));
-  ALLOC(e->w_ctx, d * c.txt_dim); ALLOC(e->b_ctx, d);
   // Qwen-Image slots: diffusers models/transformers/transformer_qwenimage.py (QwenImageTransformer2DModel: img_in,
   // txt_norm, txt_in, time_text_embed.timestep_embedder, transformer_blocks.{i}.{img_mod.1, txt_mod.1, attn.*,
   // img_mlp.net.{0.proj,2}, txt_mlp.net.{0.proj,2}}, norm_out.linear, proj_out)
-  mc::Slot& w_in = e->weights.add(flux ? "x_embedder.weight" : qw ? "img_in.weight" : "img_in.proj.weight", e->w_in, MC_BF16, d * e->Kin);
-  if (e->Kin != e->Kp) w_in.pad = {d, (size_t)e->Kin, (size_t)e->Kp};   // stored [d, Kp]: Kin padded to a GEMM K step
-  e->weights.add(flux ? "x_embedder.bias" : qw ? "img_in.bias" : "img_in.proj.bias", e->b_in, MC_F32, d);
-  e->weights.add_linear(flux ? "context_embedder" : qw ? "txt_in" : "txt_in.input_embedder", e->w_ctx, e->b_ctx, d, c.txt_dim);
+  MC_TRY(W.alloc_linear(e->img_in, d, e->Kp));
+  HIP_TRY(hipMemset(e->img_in.w, 0, d * e->Kp * 2));
+  mc::Slot& w_in = W.add_parts(e->img_in, "", {{flux ? "x_embedder" : qw ? "img_in" : "img_in.proj", d}});
+  if (e->Kin != e->Kp) {   // given [d, Kin], stored [d, Kp]: Kin padded to a GEMM K step
+    w_in.numel = d * e->Kin;
+    w_in.pad = {d, (size_t)e->Kin, (size_t)e->Kp};
+  }
+  MC_TRY(W.add_linear(e->txt_in, "", {{flux ? "context_embedder" : qw ? "txt_in" : "txt_in.input_embedder", d}}, c.txt_dim));
   if (qw) {
-    ALLOC(e->w_txt_norm, c.txt_dim);
-    e->weights.add("txt_norm.weight", e->w_txt_norm, MC_F32, c.txt_dim);
-    TRY_C(alloc_mlp2(e, e->time_mlp, 256, "time_text_embed.timestep_embedder.linear_1", "time_text_embed.timestep_embedder.linear_2"));
+    MC_TRY(W.alloc(&e->w_txt_norm, c.txt_dim));
+    W.add("txt_norm.weight", e->w_txt_norm, MC_F32, c.txt_dim);
+    MC_TRY(mlp2(e->time_mlp, 256, "time_text_embed.timestep_embedder.linear_1", "time_text_embed.timestep_embedder.linear_2"));
   } else if (flux) {
-    TRY_C(alloc_mlp2(e, e->time_mlp, 256, "time_text_embed.timestep_embedder.linear_1", "time_text_embed.timestep_embedder.linear_2"));
-    TRY_C(alloc_mlp2(e, e->guid_mlp, 256, "time_text_embed.guidance_embedder.linear_1", "time_text_embed.guidance_embedder.linear_2"));
-    TRY_C(alloc_mlp2(e, e->vec_mlp, c.vec_dim, "time_text_embed.text_embedder.linear_1", "time_text_embed.text_embedder.linear_2"));
+    MC_TRY(mlp2(e->time_mlp, 256, "time_text_embed.timestep_embedder.linear_1", "time_text_embed.timestep_embedder.linear_2"));
+    MC_TRY(mlp2(e->guid_mlp, 256, "time_text_embed.guidance_embedder.linear_1", "time_text_embed.guidance_embedder.linear_2"));
+    MC_TRY(mlp2(e->vec_mlp, c.vec_dim, "time_text_embed.text_embedder.linear_1", "time_text_embed.text_embedder.linear_2"));
   } else {
-    TRY_C(alloc_mlp2(e, e->time_mlp, 256, "time_in.mlp.0", "time_in.mlp.2"));
-    TRY_C(alloc_mlp2(e, e->guid_mlp, 256, "guidance_in.mlp.0", "guidance_in.mlp.2"));
-    TRY_C(alloc_mlp2(e, e->vec_mlp, c.vec_dim, "vector_in.in_layer", "vector_in.out_layer"));
-    TRY_C(alloc_mlp2(e, e->ref_t_mlp, 256, "txt_in.t_embedder.mlp.0", "txt_in.t_embedder.mlp.2"));
-    TRY_C(alloc_mlp2(e, e->ref_c_mlp, c.txt_dim, "txt_in.c_embedder.linear_1", "txt_in.c_embedder.linear_2"));
+    MC_TRY(mlp2(e->time_mlp, 256, "time_in.mlp.0", "time_in.mlp.2"));
+    MC_TRY(mlp2(e->guid_mlp, 256, "guidance_in.mlp.0", "guidance_in.mlp.2"));
+    MC_TRY(mlp2(e->vec_mlp, c.vec_dim, "vector_in.in_layer", "vector_in.out_layer"));
+    MC_TRY(mlp2(e->ref_t_mlp, 256, "txt_in.t_embedder.mlp.0", "txt_in.t_embedder.mlp.2"));
+    MC_TRY(mlp2(e->ref_c_mlp, c.txt_dim, "txt_in.c_embedder.linear_1", "txt_in.c_embedder.linear_2"));
     e->refiners.resize(c.refiner_depth);
     for (int i = 0; i < c.refiner_depth; ++i) {
       Refiner& r = e->refiners[i];
       const std::string p = "txt_in.individual_token_refiner.blocks." + std::to_string(i) + ".";
-      ALLOC(r.wqkv, 3 * d * d); ALLOC(r.bqkv, 3 * d); ALLOC(r.wo, d * d); ALLOC(r.bo, d);
-      ALLOC(r.w1, 4 * d * d); ALLOC(r.b1, 4 * d); ALLOC(r.w2, 4 * d * d); ALLOC(r.b2, d);
-      ALLOC(r.wada, 2 * d * d); ALLOC(r.bada, 2 * d);
-      ALLOC(r.n1w, d); ALLOC(r.n1b, d); ALLOC(r.n2w, d); ALLOC(r.n2b, d);
-      e->weights.add_linear(p + "self_attn_qkv", r.wqkv, r.bqkv, 3 * d, d);
-      e->weights.add_linear(p + "self_attn_proj", r.wo, r.bo, d, d);
-      e->weights.add_linear(p + "mlp.fc1", r.w1, r.b1, 4 * d, d);
-      e->weights.add_linear(p + "mlp.fc2", r.w2, r.b2, d, 4 * d);
-      e->weights.add_linear(p + "adaLN_modulation.1", r.wada, r.bada, 2 * d, d);
-      e->weights.add(p + "norm1.weight", r.n1w, MC_F32, d); e->weights.add(p + "norm1.bias", r.n1b, MC_F32, d);
-      e->weights.add(p + "norm2.weight", r.n2w, MC_F32, d); e->weights.add(p + "norm2.bias", r.n2b, MC_F32, d);
+      MC_TRY(W.add_linear(r.qkv, p, {{"self_attn_qkv", 3 * d}}, d));
+      MC_TRY(W.add_linear(r.o, p, {{"self_attn_proj", d}}, d));
+      MC_TRY(W.add_linear(r.fc1, p, {{"mlp.fc1", 4 * d}}, d));
+      MC_TRY(W.add_linear(r.fc2, p, {{"mlp.fc2", d}}, 4 * d));
+      MC_TRY(W.add_linear(r.ada, p, {{"adaLN_modulation.1", 2 * d}}, d));
+      float** norms[4] = {&r.n1w, &r.n1b, &r.n2w, &r.n2b};
+      const char* names[4] = {"norm1.weight", "norm1.bias", "norm2.weight", "norm2.bias"};
+      for (int k = 0; k < 4; ++k) {
+        MC_TRY(W.alloc(norms[k], d));
+        W.add(p + names[k], *norms[k], MC_F32, d);
+      }
     }
   }
-  // ---- fused modulation matrix: every block's AdaLN linear stacked, one GEMV per forward
+  // ---- fused modulation matrix: every block's AdaLN linear stacked, one GEMV per forward; the blocks add their parts
   e->mod_rows = e->mod_final() + 2 * d;
-  ALLOC(e->w_mod, e->mod_rows * d); ALLOC(e->b_mod, e->mod_rows);
+  MC_TRY(W.alloc_linear(e->mod, e->mod_rows, d));
   // ---- blocks
   e->dimg.resize(c.n_double); e->dtxt.resize(c.n_double);
   for (int i = 0; i < c.n_double; ++i) {
-    Stream &a = e->dimg[i], &t = e->dtxt[i];
-    TRY_C(alloc_stream(e, a));
-    TRY_C(alloc_stream(e, t));
     const std::string p = (hy ? "double_blocks." : "transformer_blocks.") + std::to_string(i) + ".";
-    if (!hy) {
-      // modulation chunk order shift, scale, gate (attention), shift, scale, gate (MLP) in both families
-      e->weights.add_linear(p + (qw ? "img_mod.1" : "norm1.linear"), e->w_mod, e->b_mod, 6 * d, d, e->mod_double(i, 0));
-      e->weights.add_linear(p + (qw ? "txt_mod.1" : "norm1_context.linear"), e->w_mod, e->b_mod, 6 * d, d, e->mod_double(i, 1));
-      const char* qkv_i[3] = {"attn.to_q", "attn.to_k", "attn.to_v"};
-      const char* qkv_t[3] = {"attn.add_q_proj", "attn.add_k_proj", "attn.add_v_proj"};
-      for (int j = 0; j < 3; ++j) {
-        e->weights.add_linear(p + qkv_i[j], a.wqkv, a.bqkv, d, d, j * d);
-        e->weights.add_linear(p + qkv_t[j], t.wqkv, t.bqkv, d, d, j * d);
-      }
-      e->weights.add(p + "attn.norm_q.weight", a.qn, MC_F32, 128); e->weights.add(p + "attn.norm_k.weight", a.kn, MC_F32, 128);
-      e->weights.add(p + "attn.norm_added_q.weight", t.qn, MC_F32, 128);
-      e->weights.add(p + "attn.norm_added_k.weight", t.kn, MC_F32, 128);
-      e->weights.add_linear(p + "attn.to_out.0", a.wo, a.bo, d, d);
-      e->weights.add_linear(p + "attn.to_add_out", t.wo, t.bo, d, d);
-      const std::string ffi = qw ? "img_mlp" : "ff", fft = qw ? "txt_mlp" : "ff_context";
-      e->weights.add_linear(p + ffi + ".net.0.proj", a.w1, a.b1, 4 * d, d);
-      e->weights.add_linear(p + ffi + ".net.2", a.w2, a.b2, d, 4 * d);
-      e->weights.add_linear(p + fft + ".net.0.proj", t.w1, t.b1, 4 * d, d);
-      e->weights.add_linear(p + fft + ".net.2", t.w2, t.b2, d, 4 * d);
-    } else {
-      const char* nm[2] = {"img", "txt"};
-      Stream* st[2] = {&a, &t};
-      for (int k = 0; k < 2; ++k) {
-        const std::string q = p + nm[k];
-        e->weights.add_linear(q + "_mod.linear", e->w_mod, e->b_mod, 6 * d, d, e->mod_double(i, k));
-        e->weights.add_linear(q + "_attn_qkv", st[k]->wqkv, st[k]->bqkv, 3 * d, d);
-        e->weights.add(q + "_attn_q_norm.weight", st[k]->qn, MC_F32, 128);
-        e->weights.add(q + "_attn_k_norm.weight", st[k]->kn, MC_F32, 128);
-        e->weights.add_linear(q + "_attn_proj", st[k]->wo, st[k]->bo, d, d);
-        e->weights.add_linear(q + "_mlp.fc1", st[k]->w1, st[k]->b1, 4 * d, d);
-        e->weights.add_linear(q + "_mlp.fc2", st[k]->w2, st[k]->b2, d, 4 * d);
+    for (int k = 0; k < 2; ++k) {   // image stream, text stream
+      Stream& t = k ? e->dtxt[i] : e->dimg[i];
+      if (hy) {
+        const std::string q = p + (k ? "txt" : "img");
+        W.add_parts(e->mod, q, {{"_mod.linear", 6 * d}}, e->mod_double(i, k));
+        MC_TRY(W.add_linear(t.qkv, q, {{"_attn_qkv", 3 * d}}, d));
+        MC_TRY(W.add_linear(t.o, q, {{"_attn_proj", d}}, d));
+        MC_TRY(W.add_linear(t.fc1, q, {{"_mlp.fc1", 4 * d}}, d));
+        MC_TRY(W.add_linear(t.fc2, q, {{"_mlp.fc2", d}}, 4 * d));
+        MC_TRY(vec128(t.qn, q + "_attn_q_norm.weight"));
+        MC_TRY(vec128(t.kn, q + "_attn_k_norm.weight"));
+      } else {
+        // modulation chunk order shift, scale, gate (attention), shift, scale, gate (MLP) in both families
+        const std::string ff = qw ? (k ? "txt_mlp" : "img_mlp") : (k ? "ff_context" : "ff");
+        W.add_parts(e->mod, p, {{qw ? (k ? "txt_mod.1" : "img_mod.1") : (k ? "norm1_context.linear" : "norm1.linear"), 6 * d}},
+                    e->mod_double(i, k));
+        if (k) MC_TRY(W.add_linear(t.qkv, p, {{"attn.add_q_proj", d}, {"attn.add_k_proj", d}, {"attn.add_v_proj", d}}, d));
+        else MC_TRY(W.add_linear(t.qkv, p, {{"attn.to_q", d}, {"attn.to_k", d}, {"attn.to_v", d}}, d));
+        MC_TRY(W.add_linear(t.o, p, {{k ? "attn.to_add_out" : "attn.to_out.0", d}}, d));
+        MC_TRY(W.add_linear(t.fc1, p, {{ff + ".net.0.proj", 4 * d}}, d));
+        MC_TRY(W.add_linear(t.fc2, p, {{ff + ".net.2", d}}, 4 * d));
+        MC_TRY(vec128(t.qn, p + (k ? "attn.norm_added_q.weight" : "attn.norm_q.weight")));
+        MC_TRY(vec128(t.kn, p + (k ? "attn.norm_added_k.weight" : "attn.norm_k.weight")));
       }
     }
   }
   e->singles.resize(c.n_single);
   for (int i = 0; i < c.n_single; ++i) {
     Single& g = e->singles[i];
-    ALLOC(g.w_in, 7 * d * d); ALLOC(g.b_in, 7 * d); ALLOC(g.w_out, 5 * d * d); ALLOC(g.b_out, d);
-    ALLOC(g.qn, 128); ALLOC(g.kn, 128);
     const std::string p = (flux ? "single_transformer_blocks." : "single_blocks.") + std::to_string(i) + ".";
+    W.add_parts(e->mod, p, {{flux ? "norm.linear" : "modulation.linear", 3 * d}}, e->mod_single(i));
     if (flux) {
-      e->weights.add_linear(p + "norm.linear", e->w_mod, e->b_mod, 3 * d, d, e->mod_single(i));
-      e->weights.add_linear(p + "attn.to_q", g.w_in, g.b_in, d, d, 0);
-      e->weights.add_linear(p + "attn.to_k", g.w_in, g.b_in, d, d, d);
-      e->weights.add_linear(p + "attn.to_v", g.w_in, g.b_in, d, d, 2 * d);
-      e->weights.add_linear(p + "proj_mlp", g.w_in, g.b_in, 4 * d, d, 3 * d);
-      e->weights.add_linear(p + "proj_out", g.w_out, g.b_out, d, 5 * d);
-      e->weights.add(p + "attn.norm_q.weight", g.qn, MC_F32, 128); e->weights.add(p + "attn.norm_k.weight", g.kn, MC_F32, 128);
+      MC_TRY(W.add_linear(g.in, p, {{"attn.to_q", d}, {"attn.to_k", d}, {"attn.to_v", d}, {"proj_mlp", 4 * d}}, d));
+      MC_TRY(W.add_linear(g.out, p, {{"proj_out", d}}, 5 * d));
     } else {
-      e->weights.add_linear(p + "modulation.linear", e->w_mod, e->b_mod, 3 * d, d, e->mod_single(i));
-      e->weights.add_linear(p + "linear1", g.w_in, g.b_in, 7 * d, d);
-      e->weights.add_linear(p + "linear2", g.w_out, g.b_out, d, 5 * d);
-      e->weights.add(p + "q_norm.weight", g.qn, MC_F32, 128); e->weights.add(p + "k_norm.weight", g.kn, MC_F32, 128);
+      MC_TRY(W.add_linear(g.in, p, {{"linear1", 7 * d}}, d));
+      MC_TRY(W.add_linear(g.out, p, {{"linear2", d}}, 5 * d));
     }
+    MC_TRY(vec128(g.qn, p + (flux ? "attn.norm_q.weight" : "q_norm.weight")));
+    MC_TRY(vec128(g.kn, p + (flux ? "attn.norm_k.weight" : "k_norm.weight")));
   }
   // ---- final layer
   // (Qwen-Image's head is FLUX's: AdaLayerNormContinuous, chunk order scale, shift)
-  e->weights.add_linear(!hy ? "norm_out.linear" : "final_layer.adaLN_modulation.1", e->w_mod, e->b_mod, 2 * d, d, e->mod_final());
-  ALLOC(e->w_head, (size_t)e->out_feat * d); ALLOC(e->b_head, e->out_feat);
-  e->weights.add(!hy ? "proj_out.weight" : "final_layer.linear.weight", e->w_head, MC_F32, (size_t)e->out_feat * d);
-  e->weights.add(!hy ? "proj_out.bias" : "final_layer.linear.bias", e->b_head, MC_F32, e->out_feat);
-  if (hy) {  // upstream token vector is (c, pt, ph, pw) channel-major; launch_unpatchify wants (ph, pw, c)
-    e->weights.slots["final_layer.linear.weight"].perm_c = c.out_channels;
-    e->weights.slots["final_layer.linear.bias"].perm_c = c.out_channels;
-  }
+  W.add_parts(e->mod, "", {{!hy ? "norm_out.linear" : "final_layer.adaLN_modulation.1", 2 * d}}, e->mod_final());
+  MC_TRY(W.alloc(&e->w_head, (size_t)e->out_feat * d));
+  MC_TRY(W.alloc(&e->b_head, e->out_feat));
+  mc::Slot& w_head = W.add(!hy ? "proj_out.weight" : "final_layer.linear.weight", e->w_head, MC_F32, (size_t)e->out_feat * d);
+  mc::Slot& b_head = W.add(!hy ? "proj_out.bias" : "final_layer.linear.bias", e->b_head, MC_F32, e->out_feat);
+  if (hy) w_head.perm_c = b_head.perm_c = c.out_channels;   // upstream (c, pt, ph, pw) channel-major; launch_unpatchify wants (ph, pw, c)
   // ---- RoPE table, identity rotation until mc_mmdit_set_rope
-  TRY_C(rope_identity(e, e->Sp));
+  MC_TRY(rope_identity(e, e->Sp));
   // ---- workspace plan
   plan_workspace(e, rows, e->work);
   // side stream and fork / join events of the (optional) two-stream double block: created here, never inside a forward
   // (a forward may run under stream capture)
-  if (hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking) != hipSuccess) return cleanup(fail(MC_EHIP, "side stream"));
+  HIP_TRY(hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking));
   for (int i = 0; i < 8; ++i) {
-    if (hipEventCreateWithFlags(&e->ev_fork[i], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&e->ev_join[i], hipEventDisableTiming) != hipSuccess)
-      return cleanup(fail(MC_EHIP, "fork / join events"));
+    HIP_TRY(hipEventCreateWithFlags(&e->ev_fork[i], hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&e->ev_join[i], hipEventDisableTiming));
   }
-  *out = e;
+  *out = own.release();
   return MC_OK;
-#undef TRY_C
 }
 
 void mc_mmdit_destroy(mc_mmdit* e) {
   if (!e) return;
-  if (e->side) {
-    (void)hipStreamDestroy(e->side);
-    for (int i = 0; i < 8; ++i) {
-      (void)hipEventDestroy(e->ev_fork[i]);
-      (void)hipEventDestroy(e->ev_join[i]);
-    }
+  if (e->side) (void)hipStreamDestroy(e->side);
+  for (int i = 0; i < 8; ++i) {   // a create that failed midway made only some of them
+    if (e->ev_fork[i]) (void)hipEventDestroy(e->ev_fork[i]);
+    if (e->ev_join[i]) (void)hipEventDestroy(e->ev_join[i]);
   }
   e->weights.free_all();
   delete e;
@@ -562,52 +549,47 @@ mc_status mc_mmdit_calib_stats(mc_mmdit* e, float out[3], mc_stream stream) {
 namespace {
 
 // y = W2 silu(W1 x + b1) + b2   (TimestepEmbedding / MLPEmbedder / TextProjection); h: scratch [d]
-mc_status run_mlp2(const mc_mmdit* e, const Mlp2& m, const float* x, float* h, float* y, int accumulate, hipStream_t s) {
-  HIP_TRY(mc::launch_gemv_bf16w(m.w1, x, m.b1, h, e->d, m.k_in, 0, 0, 0, s));
-  HIP_TRY(mc::launch_gemv_bf16w(m.w2, h, m.b2, y, e->d, e->d, 1, 0, accumulate, s));
+mc_status run_mlp2(const Mlp2& m, const float* x, float* h, float* y, int accumulate, hipStream_t s) {
+  HIP_TRY(mc::launch_gemv_bf16w(m.l1.w, x, m.l1.b, h, m.l1.n_out, m.l1.k_in, 0, 0, 0, s));
+  HIP_TRY(mc::launch_gemv_bf16w(m.l2.w, h, m.l2.b, y, m.l2.n_out, m.l2.k_in, 1, 0, accumulate, s));
   return MC_OK;
 }
 
-mc_status joint_attention(const mc_mmdit* e, int q_rows_pad, int n_valid, hipStream_t s) {
+// ---------------------------------------------------------------------------------------------- attention
+// The keys and values of one attention launch: n_shards blocks of `rows` rows (a multiple of 64; `stride` elements apart), the
+// first `valid` of each being keys; the rows up to `rows` are read and masked and must be finite (padded text rows, the
+// neighbouring stream's rows or the zeroed tail of "qkv").
+struct Keys {
+  const bf16_t *k, *v;
+  long ld, stride;
+  int rows, valid, n_shards, skip_shard_p1;
+};
+Keys local_keys(const mc_mmdit* e, int row0, int rows_pad, int valid) {   // rows [row0, ..) of the local "qkv"
+  const bf16_t* k = e->buf<bf16_t>("qkv") + (size_t)row0 * 3 * e->d + e->d;
+  return {k, k + e->d, 3L * e->d, 0, rows_pad, valid, 1, 0};
+}
+Keys image_keys(const mc_mmdit* e) { return local_keys(e, e->img0, (int)align_up(e->Li, 64), e->Li); }
+Keys text_keys(const mc_mmdit* e) { return local_keys(e, e->txt0, (int)align_up(e->Lt, 64), e->txt_valid); }
+// the image K|V shards of every rank in "kv_gather"; skip_shard_p1 = k + 1 leaves shard k out
+Keys gathered_keys(const mc_mmdit* e, int skip_shard_p1) {
+  const bf16_t* k = e->buf<bf16_t>("kv_gather");
+  return {k, k + e->d, 2L * e->d, (long)e->Lrp * 2 * e->d, e->Lrp, e->Li, e->P, skip_shard_p1};
+}
+
+// rows [0, q_rows_pad) of "qkv" as queries over one key set -> "am"[:, 0:d].  lse_out: keep the log-sum-exp of this launch;
+// lse_in: "am" already holds the result over other keys with that log-sum-exp, merge with it.
+mc_status attend(const mc_mmdit* e, int q_rows_pad, const Keys& keys, const float* lse_in, float* lse_out, hipStream_t s) {
   const int d = e->d;
-  bf16_t* qkv = e->buf<bf16_t>("qkv");
   mc::AttnParams a;
   memset(&a, 0, sizeof(a));
-  a.Q = qkv; a.ldq = 3 * d;
-  a.K = qkv + d; a.ldk = 3 * d;
-  a.V = qkv + 2 * d; a.ldv = 3 * d;
+  a.Q = e->buf<bf16_t>("qkv"); a.ldq = 3 * d;
+  a.K = keys.k; a.ldk = keys.ld; a.k_shard_stride = keys.stride;
+  a.V = keys.v; a.ldv = keys.ld; a.v_shard_stride = keys.stride;
   a.O = e->buf<bf16_t>("am"); a.ldo = 5 * d;
   a.Lq_pad = q_rows_pad; a.n_heads = e->H; a.scale = 1.0f / std::sqrt(128.0f);
-  a.shard_rows = q_rows_pad; a.shard_valid = n_valid; a.n_shards = 1;
+  a.shard_rows = keys.rows; a.shard_valid = keys.valid; a.n_shards = keys.n_shards; a.skip_shard_p1 = keys.skip_shard_p1;
+  a.lse_in = lse_in; a.lse_out = lse_out;
   HIP_TRY(mc::launch_attention(a, s));
-  return MC_OK;
-}
-
-// Qwen-Image with a prompt shorter than txt_len: the queries of every row over the image keys (log-sum-exp kept), then
-// over the txt_valid text keys merged with it -- the padded text rows [txt_valid, txt_len) are never keys.  (At
-// txt_valid == txt_len the engine takes joint_attention over all S keys, as for FLUX.)
-mc_status qwen_attention(const mc_mmdit* e, hipStream_t s) {
-  const int d = e->d;
-  bf16_t* qkv = e->buf<bf16_t>("qkv");
-  mc::AttnParams a;
-  memset(&a, 0, sizeof(a));
-  a.Q = qkv; a.ldq = 3 * d;
-  a.O = e->buf<bf16_t>("am"); a.ldo = 5 * d;
-  a.Lq_pad = e->Sp; a.n_heads = e->H; a.scale = 1.0f / std::sqrt(128.0f);
-  a.n_shards = 1;
-  float* lse = e->buf<float>("attn_lse");
-  mc::AttnParams im = a;   // image keys: rows [img0, img0 + Li); the padding up to 64 rows is the zeroed tail of qkv
-  im.K = qkv + (size_t)e->img0 * 3 * d + d; im.ldk = 3 * d;
-  im.V = qkv + (size_t)e->img0 * 3 * d + 2 * d; im.ldv = 3 * d;
-  im.shard_rows = (int)align_up(e->Li, 64); im.shard_valid = e->Li;
-  im.lse_out = lse;
-  HIP_TRY(mc::launch_attention(im, s));
-  mc::AttnParams tx = a;   // the valid text keys; rows [txt_valid, align64(Lt)) are read (finite: padded text / image rows)
-  tx.K = qkv + (size_t)e->txt0 * 3 * d + d; tx.ldk = 3 * d;
-  tx.V = qkv + (size_t)e->txt0 * 3 * d + 2 * d; tx.ldv = 3 * d;
-  tx.shard_rows = (int)align_up(e->Lt, 64); tx.shard_valid = e->txt_valid;
-  tx.lse_in = lse;
-  HIP_TRY(mc::launch_attention(tx, s));
   return MC_OK;
 }
 
@@ -622,165 +604,113 @@ mc_status run_refiner(mc_mmdit* e, const float* txt_dev, int txt_valid, float* v
   float* cvec = vecs + 4 * d;       // c = t_embedder(t) + c_embedder(mean of the valid text states)
   float* gates = vecs + 5 * d;      // [2d]
   float* cmean = vecs + 16 * d;     // [txt_dim]
-  MC_TRY(run_mlp2(e, e->ref_t_mlp, sin_t, hid, cvec, 0, s));
+  MC_TRY(run_mlp2(e->ref_t_mlp, sin_t, hid, cvec, 0, s));
   HIP_TRY(mc::launch_colmean(txt_dev, c.txt_dim, txt_valid, c.txt_dim, cmean, s));
-  MC_TRY(run_mlp2(e, e->ref_c_mlp, cmean, hid, cvec, 1, s));
+  MC_TRY(run_mlp2(e->ref_c_mlp, cmean, hid, cvec, 1, s));
   float* xt = e->buf<float>("x") + (size_t)e->txt0 * d;
   bf16_t* xn = e->buf<bf16_t>("xn");
-  bf16_t* qkv = e->buf<bf16_t>("qkv");
   bf16_t* am = e->buf<bf16_t>("am");
   for (const Refiner& r : e->refiners) {
-    HIP_TRY(mc::launch_gemv_bf16w(r.wada, cvec, r.bada, gates, 2 * d, d, 1, 0, 0, s));
+    HIP_TRY(mc::launch_gemv_bf16w(r.ada.w, cvec, r.ada.b, gates, 2 * d, d, 1, 0, 0, s));
     HIP_TRY(mc::launch_ln_modulate(xt, d, nullptr, 0, r.n1w, r.n1b, 1, 1e-6f, xn, d, nullptr, 0, Lt, d, s));
-    mc::GemmParams p = gp(xn, d, r.wqkv, d, r.bqkv, Lt, 3 * d, d);
-    p.Cb = qkv; p.ldc = 3 * d;
-    HIP_TRY(gemm(e, p, mc::EPI_BF16, s));
-    MC_TRY(joint_attention(e, Ltp, txt_valid, s));
-    mc::GemmParams o = gp(am, 5 * d, r.wo, d, r.bo, Lt, d, d);
-    o.X = xt; o.ldx = d; o.gate = gates;
-    HIP_TRY(gemm(e, o, mc::EPI_RESID_GATE, s));
+    mc::GemmParams p = {}, o = {}, f1 = {}, f2 = {};
+    p.Cb = e->buf<bf16_t>("qkv"); p.ldc = 3 * d;
+    MC_TRY(linear(e, r.qkv, Lt, xn, d, p, mc::EPI_BF16, s));
+    MC_TRY(attend(e, Ltp, local_keys(e, 0, Ltp, txt_valid), nullptr, nullptr, s));
+    const int epi_o = resid_epi(e, o, e->txt0, gates, nullptr);
+    MC_TRY(linear(e, r.o, Lt, am, 5 * d, o, epi_o, s));
     HIP_TRY(mc::launch_ln_modulate(xt, d, nullptr, 0, r.n2w, r.n2b, 1, 1e-6f, xn, d, nullptr, 0, Lt, d, s));
-    mc::GemmParams f1 = gp(xn, d, r.w1, d, r.b1, Lt, 4 * d, d);
     f1.Cb = am + d; f1.ldc = 5 * d;
-    HIP_TRY(gemm(e, f1, mc::EPI_SILU_BF16, s));
-    mc::GemmParams f2 = gp(am + d, 5 * d, r.w2, 4 * d, r.b2, Lt, d, 4 * d);
-    f2.X = xt; f2.ldx = d; f2.gate = gates + d;
-    HIP_TRY(gemm(e, f2, mc::EPI_RESID_GATE, s));
+    MC_TRY(linear(e, r.fc1, Lt, xn, d, f1, mc::EPI_SILU_BF16, s));
+    const int epi_f2 = resid_epi(e, f2, e->txt0, gates + d, nullptr);
+    MC_TRY(linear(e, r.fc2, Lt, am + d, 5 * d, f2, epi_f2, s));
   }
   return MC_OK;
 }
 
-// one stream of a double block, before the joint attention: LN + modulate, QKV, per-head q/k norm, RoPE
-// phases (diagnostic split, tests/two_stream_bisect.py): 1 = LN + QKV GEMM, 2 = head norm + RoPE, 3 = both
-mc_status stream_pre_attn(const mc_mmdit* e, const Stream& w, const float* mod, int row0, int rows, hipStream_t s,
-                          int phases = 3) {
-  const int d = e->d;
-  float* x = e->buf<float>("x") + (size_t)row0 * d;
-  bf16_t* xn = e->buf<bf16_t>("xn") + (size_t)row0 * d;
-  bf16_t* qkv = e->buf<bf16_t>("qkv") + (size_t)row0 * 3 * d;
-  if (phases & 1) {
-    HIP_TRY(mc::launch_ln_modulate(x, d, nullptr, 0, mod + d, mod, 0, 1e-6f, xn, d, nullptr, 0, rows, d, s));
-    mc::GemmParams p = gp(xn, d, w.wqkv, d, w.bqkv, rows, 3 * d, d);
-    p.Cb = qkv; p.ldc = 3 * d;
-    HIP_TRY(gemm(e, p, mc::EPI_BF16, s));
-  }
-  if (phases & 2) HIP_TRY(mc::launch_headnorm_rope(qkv, 3 * d, d, w.qn, w.kn, 1e-6f, e->cs, row0, rows, e->H, s));
-  return MC_OK;
-}
-
-// ... and after it: output projection (+gated residual), LN + modulate, MLP (+gated residual)
-// capture_to != null (image stream of the LAST block when there are no single blocks): MagCache residual capture
-// fused into the MLP-out epilogue, R = x_new - x0
-mc_status stream_post_attn(const mc_mmdit* e, const Stream& w, const float* mod, int row0, int rows, hipStream_t s,
-                           float* capture_to = nullptr) {
-  const int d = e->d;
-  float* x = e->buf<float>("x") + (size_t)row0 * d;
-  bf16_t* xn = e->buf<bf16_t>("xn") + (size_t)row0 * d;
-  bf16_t* am = e->buf<bf16_t>("am") + (size_t)row0 * 5 * d;
-  mc::GemmParams o = gp(am, 5 * d, w.wo, d, w.bo, rows, d, d);
-  o.X = x; o.ldx = d; o.gate = mod + 2 * d;
-  HIP_TRY(gemm(e, o, mc::EPI_RESID_GATE, s));
-  HIP_TRY(mc::launch_ln_modulate(x, d, nullptr, 0, mod + 4 * d, mod + 3 * d, 0, 1e-6f, xn, d, nullptr, 0, rows, d, s));
-  mc::GemmParams f1 = gp(xn, d, w.w1, d, w.b1, rows, 4 * d, d);
-  f1.Cb = am + d; f1.ldc = 5 * d;
-  HIP_TRY(gemm(e, f1, mc::EPI_GELU_BF16, s));
-  mc::GemmParams f2 = gp(am + d, 5 * d, w.w2, 4 * d, w.b2, rows, d, 4 * d);
-  f2.X = x; f2.ldx = d; f2.gate = mod + 5 * d;
-  if (capture_to) {
-    f2.X0 = e->buf<bf16_t>("x0") + (size_t)row0 * d; f2.ldx0 = d;
-    f2.R = capture_to + (size_t)row0 * d; f2.ldr = d;
-    HIP_TRY(gemm(e, f2, mc::EPI_RESID_CAPTURE, s));
-  } else {
-    HIP_TRY(gemm(e, f2, mc::EPI_RESID_GATE, s));
-  }
-  return MC_OK;
-}
-
-// Both streams of a double block in merged launches (round 5).  The streams are row ranges of the joint buffers, their
-// Linears have the same shapes: with the range boundary on a 256-row tile boundary (FLUX: [text 512 ; image]) the q|k|v, the
-// output projection and MLP-out of BOTH streams are one row-split GEMM each (GemmParams.m_split: 216 / 72 / 72 x 3 tiles at
-// 512^2 instead of 144 + 72 / 48 + 24 / 48 x 4 + 24 x 6 in two launches); LayerNorm (per-stream modulation), head norm
-// (per-stream weights) and MLP-in (192 + 96 tiles separately beat 288 together: two trips of 256 CUs) stay per stream.
+// ---------------------------------------------------------------------------------------------- double block
+// A double block runs over n = 1 or 2 row ranges of the joint buffers, each with its stream's weights and modulation vector:
+// one stream per call (the two-stream modes; sequence parallel), or BOTH streams in merged launches (round 5, the default).
+// The streams' Linears have the same shapes, so with two adjacent ranges the q|k|v, the output projection and MLP-out are
+// one row-split GEMM each: with the range boundary on a 256-row tile boundary (FLUX: [text 512 ; image]) ONE launch
+// (GemmParams.m_split: 216 / 72 / 72 x 3 tiles at 512^2 instead of 144 + 72 / 48 + 24 / 48 x 4 + 24 x 6 in two launches);
 // HunyuanVideo's boundary (118 800 image rows first) is not on a tile boundary: launch_gemm_bf16 then runs the two launches.
+// LayerNorm (per-stream modulation), head norm (per-stream weights) and MLP-in (192 + 96 tiles separately beat 288 together:
+// two trips of 256 CUs) stay per range.
+struct Range {
+  const Stream* w;
+  const float* mod;   // shift, scale, gate (attention), shift, scale, gate (MLP)
+  int row0, rows;
+};
 bool double_block_merged(const mc_mmdit* e) {
   return g_mmdit_two_streams == 0 && e->P == 1 && e->Lt > 0 && e->Li > 0;
 }
 
-// the row-split form of one Linear over both streams: rows [first0, ..) use `a`'s operands, rows [second0, ..) use `b`'s
+// the two streams of block `blk` as adjacent ranges in row order; img / txt: which of them is which
 struct TwoStreams {
-  const Stream* a; const Stream* b;      // first / second row range
-  const float* moda; const float* modb;  // their modulation vectors
-  int row0, rows_a, rows;                // first row, rows of the first range, rows of both
+  Range r[2];
+  int img, txt;
 };
 TwoStreams two_streams(const mc_mmdit* e, int blk, const float* emod) {
-  const bool txt_first = e->txt0 < e->img0;
-  const Stream* si = &e->dimg[blk];
-  const Stream* st = &e->dtxt[blk];
-  const float* mi = emod + e->mod_double(blk, 0);
-  const float* mt = emod + e->mod_double(blk, 1);
   TwoStreams t;
-  t.a = txt_first ? st : si; t.b = txt_first ? si : st;
-  t.moda = txt_first ? mt : mi; t.modb = txt_first ? mi : mt;
-  t.row0 = txt_first ? e->txt0 : e->img0;
-  t.rows_a = txt_first ? e->Lt : e->Li;
-  t.rows = e->Li + e->Lt;
+  t.txt = e->txt0 < e->img0 ? 0 : 1;
+  t.img = 1 - t.txt;
+  t.r[t.img] = {&e->dimg[blk], emod + e->mod_double(blk, 0), e->img0, e->Li};
+  t.r[t.txt] = {&e->dtxt[blk], emod + e->mod_double(blk, 1), e->txt0, e->Lt};
   return t;
 }
 
-mc_status double_pre_merged(const mc_mmdit* e, int blk, const float* emod, hipStream_t s) {
+// one Linear of the block over all n ranges: rows from r[0].row0 on, row-split at the range boundary when n = 2
+mc_status range_linear(const mc_mmdit* e, const Range* r, int n, Linear Stream::*l, const bf16_t* A, long lda, const mc::GemmParams& p,
+                       int epi, const float* gate_b, hipStream_t s) {
+  const int rows = r[0].rows + (n == 2 ? r[1].rows : 0);
+  return linear(e, r[0].w->*l, rows, A, lda, p, epi, s, n == 2 ? &(r[1].w->*l) : nullptr, r[0].rows, gate_b);
+}
+
+// before the joint attention: LN + modulate, QKV, per-head q/k norm, RoPE
+// phases (diagnostic split, tests/two_stream_bisect.py): 1 = LN + QKV GEMM, 2 = head norm + RoPE, 3 = both
+mc_status double_pre(const mc_mmdit* e, const Range* r, int n, hipStream_t s, int phases = 3) {
   const int d = e->d;
-  const TwoStreams t = two_streams(e, blk, emod);
   float* x = e->buf<float>("x");
   bf16_t* xn = e->buf<bf16_t>("xn");
   bf16_t* qkv = e->buf<bf16_t>("qkv");
-  const int r0 = t.row0, r1 = t.row0 + t.rows_a, nb = t.rows - t.rows_a;
-  HIP_TRY(mc::launch_ln_modulate(x + (size_t)r0 * d, d, nullptr, 0, t.moda + d, t.moda, 0, 1e-6f, xn + (size_t)r0 * d, d, nullptr, 0,
-                                 t.rows_a, d, s));
-  HIP_TRY(mc::launch_ln_modulate(x + (size_t)r1 * d, d, nullptr, 0, t.modb + d, t.modb, 0, 1e-6f, xn + (size_t)r1 * d, d, nullptr, 0,
-                                 nb, d, s));
-  mc::GemmParams p = gp(xn + (size_t)r0 * d, d, t.a->wqkv, d, t.a->bqkv, t.rows, 3 * d, d);
-  p.Cb = qkv + (size_t)r0 * 3 * d; p.ldc = 3 * d;
-  p.m_split = t.rows_a; p.W_b = t.b->wqkv; p.bias_b = t.b->bqkv;
-  HIP_TRY(gemm(e, p, mc::EPI_BF16, s));
-  HIP_TRY(mc::launch_headnorm_rope(qkv + (size_t)r0 * 3 * d, 3 * d, d, t.a->qn, t.a->kn, 1e-6f, e->cs, r0, t.rows_a, e->H, s));
-  HIP_TRY(mc::launch_headnorm_rope(qkv + (size_t)r1 * 3 * d, 3 * d, d, t.b->qn, t.b->kn, 1e-6f, e->cs, r1, nb, e->H, s));
+  if (phases & 1) {
+    for (int i = 0; i < n; ++i)
+      HIP_TRY(mc::launch_ln_modulate(x + (size_t)r[i].row0 * d, d, nullptr, 0, r[i].mod + d, r[i].mod, 0, 1e-6f,
+                                     xn + (size_t)r[i].row0 * d, d, nullptr, 0, r[i].rows, d, s));
+    mc::GemmParams p = {};
+    p.Cb = qkv + (size_t)r[0].row0 * 3 * d; p.ldc = 3 * d;
+    MC_TRY(range_linear(e, r, n, &Stream::qkv, xn + (size_t)r[0].row0 * d, d, p, mc::EPI_BF16, nullptr, s));
+  }
+  if (phases & 2)
+    for (int i = 0; i < n; ++i)
+      HIP_TRY(mc::launch_headnorm_rope(qkv + (size_t)r[i].row0 * 3 * d, 3 * d, d, r[i].w->qn, r[i].w->kn, 1e-6f, e->cs, r[i].row0,
+                                       r[i].rows, e->H, s));
   return MC_OK;
 }
 
-// capture_to != null (LAST block of a model without single blocks): the MagCache residual R = x_new - x0 over the joint rows
-// (the text rows of R are scratch, as in the single blocks)
-mc_status double_post_merged(const mc_mmdit* e, int blk, const float* emod, hipStream_t s, float* capture_to) {
+// ... and after it: output projection (+gated residual), LN + modulate, MLP (+gated residual)
+// capture_to != null (the LAST block of a model without single blocks): the MagCache residual R = x_new - x0 of the ranges'
+// rows fused into the MLP-out epilogue (joint row index; the text rows of R are scratch, as in the single blocks)
+mc_status double_post(const mc_mmdit* e, const Range* r, int n, hipStream_t s, float* capture_to) {
   const int d = e->d;
-  const TwoStreams t = two_streams(e, blk, emod);
   float* x = e->buf<float>("x");
   bf16_t* xn = e->buf<bf16_t>("xn");
   bf16_t* am = e->buf<bf16_t>("am");
-  const int r0 = t.row0, r1 = t.row0 + t.rows_a, nb = t.rows - t.rows_a;
-  mc::GemmParams o = gp(am + (size_t)r0 * 5 * d, 5 * d, t.a->wo, d, t.a->bo, t.rows, d, d);
-  o.X = x + (size_t)r0 * d; o.ldx = d; o.gate = t.moda + 2 * d;
-  o.m_split = t.rows_a; o.W_b = t.b->wo; o.bias_b = t.b->bo; o.gate_b = t.modb + 2 * d;
-  HIP_TRY(gemm(e, o, mc::EPI_RESID_GATE, s));
-  HIP_TRY(mc::launch_ln_modulate(x + (size_t)r0 * d, d, nullptr, 0, t.moda + 4 * d, t.moda + 3 * d, 0, 1e-6f, xn + (size_t)r0 * d, d,
-                                 nullptr, 0, t.rows_a, d, s));
-  HIP_TRY(mc::launch_ln_modulate(x + (size_t)r1 * d, d, nullptr, 0, t.modb + 4 * d, t.modb + 3 * d, 0, 1e-6f, xn + (size_t)r1 * d, d,
-                                 nullptr, 0, nb, d, s));
-  mc::GemmParams fa = gp(xn + (size_t)r0 * d, d, t.a->w1, d, t.a->b1, t.rows_a, 4 * d, d);
-  fa.Cb = am + (size_t)r0 * 5 * d + d; fa.ldc = 5 * d;
-  HIP_TRY(gemm(e, fa, mc::EPI_GELU_BF16, s));
-  mc::GemmParams fb = gp(xn + (size_t)r1 * d, d, t.b->w1, d, t.b->b1, nb, 4 * d, d);
-  fb.Cb = am + (size_t)r1 * 5 * d + d; fb.ldc = 5 * d;
-  HIP_TRY(gemm(e, fb, mc::EPI_GELU_BF16, s));
-  mc::GemmParams f2 = gp(am + (size_t)r0 * 5 * d + d, 5 * d, t.a->w2, 4 * d, t.a->b2, t.rows, d, 4 * d);
-  f2.X = x + (size_t)r0 * d; f2.ldx = d; f2.gate = t.moda + 5 * d;
-  f2.m_split = t.rows_a; f2.W_b = t.b->w2; f2.bias_b = t.b->b2; f2.gate_b = t.modb + 5 * d;
-  if (capture_to) {
-    f2.X0 = e->buf<bf16_t>("x0") + (size_t)r0 * d; f2.ldx0 = d;
-    f2.R = capture_to + (size_t)r0 * d; f2.ldr = d;
-    HIP_TRY(gemm(e, f2, mc::EPI_RESID_CAPTURE, s));
-  } else {
-    HIP_TRY(gemm(e, f2, mc::EPI_RESID_GATE, s));
+  const float* mod_b = n == 2 ? r[1].mod : nullptr;
+  mc::GemmParams o = {}, f2 = {};
+  const int epi_o = resid_epi(e, o, r[0].row0, r[0].mod + 2 * d, nullptr);
+  MC_TRY(range_linear(e, r, n, &Stream::o, am + (size_t)r[0].row0 * 5 * d, 5 * d, o, epi_o, mod_b ? mod_b + 2 * d : nullptr, s));
+  for (int i = 0; i < n; ++i)
+    HIP_TRY(mc::launch_ln_modulate(x + (size_t)r[i].row0 * d, d, nullptr, 0, r[i].mod + 4 * d, r[i].mod + 3 * d, 0, 1e-6f,
+                                   xn + (size_t)r[i].row0 * d, d, nullptr, 0, r[i].rows, d, s));
+  for (int i = 0; i < n; ++i) {
+    mc::GemmParams f1 = {};
+    f1.Cb = am + (size_t)r[i].row0 * 5 * d + d; f1.ldc = 5 * d;
+    MC_TRY(linear(e, r[i].w->fc1, r[i].rows, xn + (size_t)r[i].row0 * d, d, f1, mc::EPI_GELU_BF16, s));
   }
-  return MC_OK;
+  const int epi_f2 = resid_epi(e, f2, r[0].row0, r[0].mod + 5 * d, capture_to);
+  return range_linear(e, r, n, &Stream::fc2, am + (size_t)r[0].row0 * 5 * d + d, 5 * d, f2, epi_f2, mod_b ? mod_b + 5 * d : nullptr, s);
 }
 
 // Image stream and text stream of a double block touch disjoint rows of every buffer: with "mmdit_two_streams" the text
@@ -820,8 +750,7 @@ mc_status begin_impl(mc_mmdit* e, const float* img_dev, double timestep, double 
                      int txt_valid, const float* vec_dev, mc_mode mode, int branch, mc_stream stream_) {
   hipStream_t s = (hipStream_t)stream_;
   if (!e) return fail(MC_EINVAL, "null engine");
-  if (!e->work.ws) return fail(MC_ESTATE, "workspace not set (mc_mmdit_set_workspace)");
-  if (const char* w = nullptr; !e->weights.all_loaded(&w)) return fail(MC_ESTATE, "weight '%s' was never set", w);
+  MC_TRY(mc::check_ready(e->work, e->weights, "mc_mmdit_set_workspace"));
   const mc_mmdit_config& c = e->cfg;
   const bool hy = c.family == MC_FAMILY_HUNYUAN;
   const bool qw = c.family == MC_FAMILY_QWEN;
@@ -856,18 +785,18 @@ mc_status begin_impl(mc_mmdit* e, const float* img_dev, double timestep, double 
   // ---- conditioning vector: time + guidance + pooled text   (flux :303-313, hunyuan :53-67)
   // (Qwen-Image, QwenTimestepProjEmbeddings: the timestep MLP alone, no guidance and no pooled text)
   HIP_TRY(mc::launch_sinusoid(nullptr, timestep, 256, sin_t, s));
-  MC_TRY(run_mlp2(e, e->time_mlp, sin_t, hid, vec, 0, s));
+  MC_TRY(run_mlp2(e->time_mlp, sin_t, hid, vec, 0, s));
   if (!qw) {
     HIP_TRY(mc::launch_sinusoid(nullptr, guidance, 256, sin_g, s));
-    MC_TRY(run_mlp2(e, e->guid_mlp, sin_g, hid, vec, 1, s));
-    MC_TRY(run_mlp2(e, e->vec_mlp, vec_dev, hid, vec, 1, s));
+    MC_TRY(run_mlp2(e->guid_mlp, sin_g, hid, vec, 1, s));
+    MC_TRY(run_mlp2(e->vec_mlp, vec_dev, hid, vec, 1, s));
   }
   // modulation of every block = Linear(silu(vec)); a skipped step needs the final layer's only
   if (mode == MC_MODE_SKIP) {
     const size_t r0 = e->mod_final();
-    HIP_TRY(mc::launch_gemv_bf16w(e->w_mod + r0 * d, vec, e->b_mod + r0, emod + r0, 2 * d, d, 1, 0, 0, s));
+    HIP_TRY(mc::launch_gemv_bf16w(e->mod.w + r0 * d, vec, e->mod.b + r0, emod + r0, 2 * d, d, 1, 0, 0, s));
   } else {
-    HIP_TRY(mc::launch_gemv_bf16w(e->w_mod, vec, e->b_mod, emod, (int)e->mod_rows, d, 1, 0, 0, s));
+    HIP_TRY(mc::launch_gemv_bf16w(e->mod.w, vec, e->mod.b, emod, (int)e->mod_rows, d, 1, 0, 0, s));
   }
   // ---- image embedding of THIS rank's tokens: x_img = x_embedder(tokens) / img_in(latent); ori copy for MagCache
   {
@@ -879,9 +808,9 @@ mc_status begin_impl(mc_mmdit* e, const float* img_dev, double timestep, double 
     } else {
       HIP_TRY(mc::launch_cast_pad_bf16(img_dev + (size_t)e->tok0 * e->Kin, e->Kin, Li, Li, e->Kin, tokens, e->Kp, s));
     }
-    mc::GemmParams p = gp(tokens, e->Kp, e->w_in, e->Kp, e->b_in, Li, d, e->Kp);
+    mc::GemmParams p = {};
     p.X = x + (size_t)e->img0 * d; p.ldx = d; p.X0out = x0; p.ldx0out = d; p.m_valid = Li;
-    HIP_TRY(gemm(e, p, mc::EPI_EMBED, s));
+    MC_TRY(linear(e, e->img_in, Li, tokens, e->Kp, p, mc::EPI_EMBED, s));
   }
   if (mode != MC_MODE_SKIP) {
     // ---- text embedding -> text rows of x   (flux :314; hunyuan :72-78 incl. the token refiner); replicated per rank
@@ -893,10 +822,10 @@ mc_status begin_impl(mc_mmdit* e, const float* img_dev, double timestep, double 
     } else {
       HIP_TRY(mc::launch_cast_pad_bf16(txt_dev, c.txt_dim, Lt, Lt, c.txt_dim, tin, c.txt_dim, s));
     }
-    mc::GemmParams p = gp(tin, c.txt_dim, e->w_ctx, c.txt_dim, e->b_ctx, Lt, d, c.txt_dim);
+    mc::GemmParams p = {};
     p.X = x + (size_t)e->txt0 * d; p.ldx = d; p.X0out = e->buf<bf16_t>("txt_e"); p.ldx0out = d;
     p.m_valid = qw ? txt_valid : Lt;
-    HIP_TRY(gemm(e, p, mc::EPI_EMBED, s));
+    MC_TRY(linear(e, e->txt_in, Lt, tin, c.txt_dim, p, mc::EPI_EMBED, s));
     if (hy) MC_TRY(run_refiner(e, txt_dev, txt_valid, vecs, s));
   }
   return MC_OK;
@@ -974,17 +903,16 @@ mc_status mc_mmdit_block_pre(mc_mmdit* e, int blk, mc_stream stream_) {
   if (!e || !e->begun) return fail(MC_ESTATE, "mc_mmdit_begin must run first");
   const mc_mmdit_config& c = e->cfg;
   if (blk < 0 || blk >= c.n_double + c.n_single) return fail(MC_EINVAL, "block %d out of range", blk);
-  const int d = e->d, Li = e->Li, Lt = e->Lt, S = e->S;
+  const int d = e->d, Li = e->Li, S = e->S;
   const float* emod = e->buf<float>("emod");
   bf16_t* qkv = e->buf<bf16_t>("qkv");
   if (blk < c.n_double) {
-    const float* mi = emod + e->mod_double(blk, 0);
-    const float* mt = emod + e->mod_double(blk, 1);
-    auto img = [&](hipStream_t q, int ph) { return stream_pre_attn(e, e->dimg[blk], mi, e->img0, Li, q, ph); };
-    auto txt = [&](hipStream_t q, int ph) { return stream_pre_attn(e, e->dtxt[blk], mt, e->txt0, Lt, q, ph); };
+    const TwoStreams t = two_streams(e, blk, emod);
+    auto img = [&](hipStream_t q, int ph) { return double_pre(e, &t.r[t.img], 1, q, ph); };
+    auto txt = [&](hipStream_t q, int ph) { return double_pre(e, &t.r[t.txt], 1, q, ph); };
     const int mode = g_mmdit_two_streams;
     if (double_block_merged(e)) {
-      MC_TRY(double_pre_merged(e, blk, emod, s));
+      MC_TRY(double_pre(e, t.r, 2, s));
     } else if (mode <= 2) {
       MC_TRY(run_two(e, s, mode, [&](hipStream_t q) { return img(q, 3); }, [&](hipStream_t q) { return txt(q, 3); }));
     } else {   // diagnostic splits: which pair of kernels must overlap for the results to change
@@ -1016,10 +944,10 @@ mc_status mc_mmdit_block_pre(mc_mmdit* e, int blk, mc_stream stream_) {
     // linear1 of the single block = [q | k | v ; MLP-in] over the same rows: ONE launch with two destinations (the q|k|v
     // columns to "qkv", the GELU'd MLP columns to "am"[:, d:]) -- 504 tiles at FLUX 512^2 are two trips of the 256 CUs, the
     // two launches were 216 + 288 = one + two
-    mc::GemmParams p = gp(xn, d, g.w_in, d, g.b_in, S, 7 * d, d);
+    mc::GemmParams p = {};
     p.Cb = qkv; p.ldc = 3 * d;
     p.n_split = 3 * d; p.Cb2 = am + d; p.ldc2 = 5 * d;
-    HIP_TRY(gemm(e, p, mc::EPI_BF16_GELU_SPLIT, s));
+    MC_TRY(linear(e, g.in, S, xn, d, p, mc::EPI_BF16_GELU_SPLIT, s));
     HIP_TRY(mc::launch_headnorm_rope(qkv, 3 * d, d, g.qn, g.kn, 1e-6f, e->cs, 0, S, e->H, s));
   }
   if (e->P > 1) {
@@ -1038,27 +966,9 @@ mc_status mc_mmdit_block_attn_local(mc_mmdit* e, int blk, mc_stream stream_) {
   hipStream_t s = (hipStream_t)stream_;
   if (!e || !e->begun) return fail(MC_ESTATE, "mc_mmdit_begin must run first");
   if (e->P < 2) return fail(MC_ESTATE, "mc_mmdit_block_attn_local needs sp_size > 1");
-  const int d = e->d, Li = e->Li, Lt = e->Lt;
-  bf16_t* qkv = e->buf<bf16_t>("qkv");
-  mc::AttnParams a;
-  memset(&a, 0, sizeof(a));
-  a.Q = qkv; a.ldq = 3 * d;
-  a.O = e->buf<bf16_t>("am"); a.ldo = 5 * d;
-  a.Lq_pad = e->Sp; a.n_heads = e->H; a.scale = 1.0f / std::sqrt(128.0f);
-  a.n_shards = 1;
   float* lse = e->buf<float>("attn_lse");
-  mc::AttnParams li = a;   // local image keys: rows [img0, img0 + Li) of the local qkv
-  li.K = qkv + (size_t)e->img0 * 3 * d + d; li.ldk = 3 * d;
-  li.V = qkv + (size_t)e->img0 * 3 * d + 2 * d; li.ldv = 3 * d;
-  li.shard_rows = (int)align_up(Li, 64); li.shard_valid = Li;
-  li.lse_out = lse;
-  HIP_TRY(mc::launch_attention(li, s));
-  mc::AttnParams tx = a;   // text keys
-  tx.K = qkv + (size_t)e->txt0 * 3 * d + d; tx.ldk = 3 * d;
-  tx.V = qkv + (size_t)e->txt0 * 3 * d + 2 * d; tx.ldv = 3 * d;
-  tx.shard_rows = (int)align_up(Lt, 64); tx.shard_valid = e->txt_valid;
-  tx.lse_in = lse; tx.lse_out = lse;
-  HIP_TRY(mc::launch_attention(tx, s));
+  MC_TRY(attend(e, e->Sp, image_keys(e), nullptr, lse, s));   // this rank's shard: rows of the local qkv
+  MC_TRY(attend(e, e->Sp, text_keys(e), lse, lse, s));
   e->local_attn_blk = blk;
   return MC_OK;
 }
@@ -1071,67 +981,44 @@ mc_status mc_mmdit_block_post(mc_mmdit* e, int blk, mc_stream stream_) {
   if (blk < 0 || blk >= nb) return fail(MC_EINVAL, "block %d out of range", blk);
   const int d = e->d, Li = e->Li, Lt = e->Lt, S = e->S, Sp = e->Sp;
   const float* emod = e->buf<float>("emod");
-  bf16_t* qkv = e->buf<bf16_t>("qkv");
   // ---- joint attention of the local queries over [all image tokens ; valid text tokens]
   if (e->P == 1 && c.family == MC_FAMILY_QWEN && e->txt_valid < Lt) {
-    MC_TRY(qwen_attention(e, s));
-  } else if (e->P == 1) {
-    const bool hy = c.family == MC_FAMILY_HUNYUAN;
-    MC_TRY(joint_attention(e, Sp, hy ? Li + e->txt_valid : S, s));
+    // Qwen-Image with a prompt shorter than txt_len: the image keys (log-sum-exp kept), then the txt_valid text keys merged
+    // with it -- the padded text rows [txt_valid, txt_len) are never keys
+    float* lse = e->buf<float>("attn_lse");
+    MC_TRY(attend(e, Sp, image_keys(e), nullptr, lse, s));
+    MC_TRY(attend(e, Sp, text_keys(e), lse, nullptr, s));
+  } else if (e->P == 1) {   // all S rows of qkv are keys (HunyuanVideo: its valid text rows are the last of them)
+    MC_TRY(attend(e, Sp, local_keys(e, 0, Sp, c.family == MC_FAMILY_HUNYUAN ? Li + e->txt_valid : S), nullptr, nullptr, s));
+  } else if (e->local_attn_blk == blk) {   // mc_mmdit_block_attn_local did the local shard and the text keys: the remote shards, merged
+    e->local_attn_blk = -1;
+    MC_TRY(attend(e, Sp, gathered_keys(e, e->rank + 1), e->buf<float>("attn_lse"), nullptr, s));
   } else {
     // (1) the image keys of every rank (gathered shards of Li rows), (2) the text keys (replicated, local rows of qkv),
     // merged with the log-sum-exp of (1) in the kernel epilogue
-    mc::AttnParams a;
-    memset(&a, 0, sizeof(a));
-    a.Q = qkv; a.ldq = 3 * d;
-    a.O = e->buf<bf16_t>("am"); a.ldo = 5 * d;
-    a.Lq_pad = Sp; a.n_heads = e->H; a.scale = 1.0f / std::sqrt(128.0f);
-    bf16_t* kvg = e->buf<bf16_t>("kv_gather");
-    mc::AttnParams i1 = a;
-    i1.K = kvg; i1.ldk = 2 * d; i1.k_shard_stride = (long)e->Lrp * 2 * d;
-    i1.V = kvg + d; i1.ldv = 2 * d; i1.v_shard_stride = (long)e->Lrp * 2 * d;
-    i1.shard_rows = e->Lrp; i1.shard_valid = Li; i1.n_shards = e->P;
-    if (e->local_attn_blk == blk) {   // local image shard + text keys are done: the remote shards only, merged
-      e->local_attn_blk = -1;
-      i1.skip_shard_p1 = e->rank + 1;
-      i1.lse_in = e->buf<float>("attn_lse");
-      HIP_TRY(mc::launch_attention(i1, s));
-    } else {
-      i1.lse_out = e->buf<float>("attn_lse");
-      HIP_TRY(mc::launch_attention(i1, s));
-      mc::AttnParams t2 = a;
-      t2.K = qkv + (size_t)e->txt0 * 3 * d + d; t2.ldk = 3 * d;
-      t2.V = qkv + (size_t)e->txt0 * 3 * d + 2 * d; t2.ldv = 3 * d;
-      t2.shard_rows = (int)align_up(Lt, 64); t2.shard_valid = e->txt_valid; t2.n_shards = 1;
-      t2.lse_in = e->buf<float>("attn_lse");
-      HIP_TRY(mc::launch_attention(t2, s));
-    }
+    float* lse = e->buf<float>("attn_lse");
+    MC_TRY(attend(e, Sp, gathered_keys(e, 0), nullptr, lse, s));
+    MC_TRY(attend(e, Sp, text_keys(e), lse, nullptr, s));
   }
   const bool last = (blk == nb - 1);
   const void* cn = (e->cn_double.empty() && e->cn_single.empty()) ? nullptr : controlnet_sample(e, blk);
   const bool capture = last && !cn;   // a sample on the last block: controlnet_add captures after its add
-  if (blk < c.n_double && double_block_merged(e)) {
-    MC_TRY(double_post_merged(e, blk, emod, s, capture ? e->residual_joint(e->dst, e->branch) : nullptr));
-  } else if (blk < c.n_double) {
-    MC_TRY(run_two(
-        e, s, g_mmdit_two_streams > 2 ? 0 : g_mmdit_two_streams,
-        [&](hipStream_t q) {
-          return stream_post_attn(e, e->dimg[blk], emod + e->mod_double(blk, 0), e->img0, Li, q,
-                                  capture ? e->residual_joint(e->dst, e->branch) : nullptr);
-        },
-        [&](hipStream_t q) { return stream_post_attn(e, e->dtxt[blk], emod + e->mod_double(blk, 1), e->txt0, Lt, q); }));
+  float* capture_to = capture ? e->residual_joint(e->dst, e->branch) : nullptr;
+  if (blk < c.n_double) {
+    const TwoStreams t = two_streams(e, blk, emod);
+    if (double_block_merged(e)) {
+      MC_TRY(double_post(e, t.r, 2, s, capture_to));
+    } else {
+      MC_TRY(run_two(
+          e, s, g_mmdit_two_streams > 2 ? 0 : g_mmdit_two_streams,
+          [&](hipStream_t q) { return double_post(e, &t.r[t.img], 1, q, capture_to); },
+          [&](hipStream_t q) { return double_post(e, &t.r[t.txt], 1, q, nullptr); }));
+    }
   } else {
     const int i = blk - c.n_double;
-    const Single& g = e->singles[i];
-    const float* m = emod + e->mod_single(i);
-    mc::GemmParams o = gp(e->buf<bf16_t>("am"), 5 * d, g.w_out, 5 * d, g.b_out, S, d, 5 * d);
-    o.X = e->buf<float>("x"); o.ldx = d; o.gate = m + 2 * d;
-    if (capture) {   // MagCache residual capture (flux :428, hunyuan :140); the text rows of R are scratch
-      o.X0 = e->buf<bf16_t>("x0"); o.ldx0 = d; o.R = e->residual_joint(e->dst, e->branch); o.ldr = d;
-      HIP_TRY(gemm(e, o, mc::EPI_RESID_CAPTURE, s));
-    } else {
-      HIP_TRY(gemm(e, o, mc::EPI_RESID_GATE, s));
-    }
+    mc::GemmParams o = {};   // MagCache residual capture (flux :428, hunyuan :140); the text rows of R are scratch
+    const int epi = resid_epi(e, o, 0, emod + e->mod_single(i) + 2 * d, capture_to);
+    MC_TRY(linear(e, e->singles[i].out, S, e->buf<bf16_t>("am"), 5 * d, o, epi, s));
   }
   if (cn) MC_TRY(controlnet_add(e, cn, last, s));
   if (last) {
