@@ -136,7 +136,7 @@ mc_status mc_create(const mc_config* cfg, mc_engine** out);
 /* ABI rule for mc_config: it only grows at its END and a zero in a new field means "as before".  mc_create reads
  * sizeof(mc_config) of THIS header; a caller compiled against an older header (a shorter struct) must call
  * mc_create_sized(cfg, sizeof(mc_config) as IT knows it, out): the missing tail is taken as zeros.  History: 0.1 ends at
- * vace_in_dim, 0.2 adds fp8_linear, 0.3 no_context_cache and no_token_timesteps, 0.5 sp_phases; mc_version() names the library's. */
+ * vace_in_dim, 0.2 adds fp8_linear, 0.3 no_context_cache and no_token_timesteps, 0.5 sp_phases (0.6 adds calls only: mc_pair_begin / mc_pair_end); mc_version() names the library's. */
 mc_status mc_create_sized(const mc_config* cfg, size_t cfg_bytes, mc_engine** out);
 void mc_destroy(mc_engine* e);
 size_t mc_workspace_bytes(const mc_engine* e);
@@ -163,6 +163,34 @@ int mc_weights_missing(const mc_engine* e, char* buf, size_t buflen); /* count; 
 mc_status mc_forward(mc_engine* e, const float* latent_dev, const float* t_dev, double t_host,
                      const void* context_dev, mc_dtype ctx_dtype, int ctx_len, int branch, mc_mode mode,
                      float* out_dev, mc_stream stream);
+
+/* CFG pair (0.6).  A CFG sampler evaluates the model twice per step on the same latent and the same t (the reference's loop,
+ * wan_magcache.py:296-299); only the text context differs, and the context first enters the model at layer 0's
+ * cross-attention K|V.  Everything before that point -- the embeds of the latent and of t with every modulation vector, and
+ * layer 0's LayerNorm + modulate, q|k|v Linear, q / k norm + RoPE, self-attention, O Linear with the gated residual, norm3,
+ * cross-attention q Linear and its RMSNorm: the "front" -- is therefore computed twice on identical inputs.
+ * mc_pair_begin(e) DECLARES: the next two mc_forward calls receive the same latent values, the same t and the same
+ * conditioning other than the text context.  (The engine cannot find that out: a sampler updates its latent in place, so the
+ * address of latent_dev proves nothing.)  The first of the two that runs its blocks then keeps the front -- "pair_x": it
+ * works on this fp32 stream instead of "x" and copies it to "x" behind layer 0's O epilogue; "pair_cq": the normalised
+ * cross-attention q rows; the embeds' own buffers stay as they are -- and the second continues from it at layer 0's
+ * cross-attention with its own context.  The same kernels run on the same values in the same order: outputs, residual slots
+ * and calibration statistics are the same bits as without the declaration.  mc_pair_end(e) closes the pair.
+ * Falling back to two full forwards is always legal and never an error.  The second forward runs in full when: its
+ * latent_dev, t_dev or t_host is not the first call's; the first forward was MC_MODE_SKIP (it ran no blocks); it is itself
+ * MC_MODE_SKIP (the kept front is dropped unused); mc_set_weight, mc_set_workspace, mc_set_token_timesteps, mc_set_clip_fea,
+ * mc_set_vace_context, mc_sp_set_chunks, mc_embed, mc_head or a block phase call ran in between; the pair has ended (a third forward
+ * after the two is a full one, with or without mc_pair_end).  An engine that is sharded (sp_size > 1 or sp_phases), has VACE
+ * layers, is I2V (clip_dim > 0) or runs an fp8 Linear mode accepts both calls and always runs in full; its "pair_x" /
+ * "pair_cq" are 256-byte stubs.  A forward that continues from a kept front logs no profile pairs for the front
+ * (mc_profile_read_classes: one MC_PROF_ATTN_SELF, GEMM_QKV, GEMM_O and GEMM_CROSS_Q pair, two LN_MODULATE and two
+ * RMSNORM_ROPE pairs fewer, MC_PROF_EMBED only for a context passed by pointer); the first forward's copy is one
+ * MC_PROF_OTHER pair.  Between the two forwards "x" holds the stream behind layer 0's O epilogue, not the first forward's
+ * final stream (a phase call in between ends the pair, but reads that "x").  A host that never calls mc_pair_begin gets the
+ * same launches and results as before; the one thing that changes for it is mc_workspace_bytes of a single-GPU bf16 T2V
+ * engine, which grows by Lp * dim * 6 bytes for "pair_x" / "pair_cq" (302 MB at Wan2.1-1.3B 480p). */
+mc_status mc_pair_begin(mc_engine* e);
+mc_status mc_pair_end(mc_engine* e);
 
 /* Text-context cache.  The context is constant per CFG branch over a whole video, but the reference recomputes
  * text_embedding(context) (:256-262) and every block's cross-attention k / v of it (upstream WanT2VCrossAttention) in

@@ -55,6 +55,8 @@ SIGNATURES = {
     "mc_set_weight": (_i, [_vp, C.c_char_p, _vp, _i, C.POINTER(C.c_int64), _i, _vp]),
     "mc_weights_missing": (_i, [_vp, C.c_char_p, _sz]),
     "mc_forward": (_i, [_vp, _vp, _vp, _d, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "mc_pair_begin": (_i, [_vp]),
+    "mc_pair_end": (_i, [_vp]),
     "mc_set_clip_fea": (_i, [_vp, _vp, _i, _i, _vp]),
     "mc_set_vace_context": (_i, [_vp, _vp, _f, _vp]),
     "mc_set_token_timesteps": (_i, [_vp, _vp, _vp]),

@@ -90,6 +90,18 @@ struct mc_engine {
   bool have_res[2] = {false, false};
   bool have_stats[2] = {false, false};
   bool embedded = false;
+  // CFG pair (mc_pair_begin / mc_pair_end): the caller has declared that the next two mc_forward calls receive the same
+  // latent and the same t.  The first one that runs its blocks keeps the context-free front of the evaluation -- the embeds
+  // of the latent and of t, and layer 0 up to its normalised cross-attention q -- and the second continues from it:
+  // "pair_x" = the fp32 stream after layer 0's O epilogue, "pair_cq" = the cross-attention q rows; "x0", "emod", "ehead"
+  // and "tok_sel" are written by the embeds only and survive as they are.
+  enum { PAIR_NONE, PAIR_ARMED, PAIR_KEPT, PAIR_DEAD };
+  int pair = PAIR_NONE;
+  const float *pair_latent = nullptr, *pair_t_dev = nullptr;   // what the kept front was computed from
+  double pair_t_host = 0.0;
+  // sharded, VACE, I2V and fp8 engines never share: they run every forward in full
+  bool pair_capable() const { return !sp && NV == 0 && cfg.clip_dim == 0 && cfg.fp8_linear == 0; }
+  void pair_drop() { if (pair != PAIR_NONE) pair = PAIR_DEAD; }   // forget a kept front; the pair runs in full from here
 
   template <class T>
   T* buf(const char* name) const { return work.get<T>(name); }
@@ -395,6 +407,9 @@ mc_status mc_create(const mc_config* cfg, mc_engine** out) {
   ws.add("calib_partial", (2048 * 4 + 2) * 8);   // + the arrival ticket of calib_stats_kernel
   ws.add("calib_sums", 4 * 8);
   ws.add("calib_stats", 2 * 3 * 4);
+  // the kept front of a CFG pair (mc_pair_begin): last in the plan, every other offset stays where it was
+  ws.add("pair_x", e->pair_capable() ? Lp * d * 4 : 256);
+  ws.add("pair_cq", e->pair_capable() ? Lp * d * 2 : 256);
   *out = own.release();
   return MC_OK;
 }
@@ -415,6 +430,7 @@ mc_status mc_set_workspace(mc_engine* e, void* ws_dev, size_t bytes) {
   if (!e) return fail(MC_EINVAL, "null argument");
   MC_TRY(e->work.bind(ws_dev, bytes));
   e->have_res[0] = e->have_res[1] = false;
+  e->pair_drop();
   // the arrival ticket of the one-launch calibration reduction starts at zero (the kernel rearms it itself)
   HIP_TRY(hipMemset(e->buf<double>("calib_partial") + 2048 * 4, 0, 16));
   return MC_OK;
@@ -435,6 +451,7 @@ mc_status mc_set_weight(mc_engine* e, const char* name, const void* src_dev, mc_
   if (e) {  // any cached text context was computed with the old weights
     e->ctx_valid[0] = e->ctx_valid[1] = false;
     e->ctx_active = -1;
+    e->pair_drop();   // and so was a kept front
   }
   if (!e || !name || !src_dev || !shape) return fail(MC_EINVAL, "null argument");
   return e->weights.set(name, src_dev, dtype, shape, ndim, (hipStream_t)stream);
@@ -448,6 +465,7 @@ mc_status mc_set_clip_fea(mc_engine* e, const void* clip_dev, mc_dtype dtype, in
   hipStream_t s = (hipStream_t)stream_;
   mc_status st = check_ready(e);
   if (st != MC_OK) return st;
+  e->pair_drop();
   const mc_config& c = e->cfg;
   if (c.clip_dim <= 0) return fail(MC_EINVAL, "engine was created without clip_dim (t2v model)");
   if (!clip_dev || n_tokens != 257) return fail(MC_EINVAL, "clip_fea must be [257, %d]", c.clip_dim);
@@ -483,6 +501,7 @@ mc_status mc_set_vace_context(mc_engine* e, const float* vace_dev, float context
   hipStream_t s = (hipStream_t)stream_;
   mc_status st = check_ready(e);
   if (st != MC_OK) return st;
+  e->pair_drop();
   if (e->NV <= 0) return fail(MC_EINVAL, "engine was created without VACE blocks");
   const mc_config& c = e->cfg;
   const int d = e->d;
@@ -541,17 +560,13 @@ static mc_status context_kv(mc_engine* e, const Layer& l, const bf16_t* ctx, bf1
   return MC_OK;
 }
 
-mc_status mc_embed(mc_engine* e, const float* latent_dev, const float* t_dev, double t_host,
-                   const void* context_dev, mc_dtype ctx_dtype, int ctx_len, mc_stream stream_) {
-  hipStream_t s = (hipStream_t)stream_;
-  mc_status st = check_ready(e);
-  if (st != MC_OK) return st;
-  if (!latent_dev) return fail(MC_EINVAL, "null input");
+// The embeds that depend on the latent and on t -- patch embedding -> x (fp32: "x", or "pair_x" for the first forward of a
+// CFG pair) and ori_x ("x0"), the time embedding, every modulation vector -- and nothing that depends on the context: what
+// the second forward of a CFG pair reuses.
+static mc_status embed_latent_time(mc_engine* e, const float* latent_dev, const float* t_dev, double t_host, float* x,
+                                   hipStream_t s) {
   const mc_config& c = e->cfg;
-  if (c.clip_dim > 0 && !e->have_clip)
-    return fail(MC_ESTATE, "i2v model: mc_set_clip_fea must run before the forward (reference assert :226-227)");
   const int d = e->d;
-  Prof pr(e, MC_PROF_EMBED, s);
   // x = patch_embedding(latent): im2col -> GEMM, x (fp32) and ori_x (bf16), zero rows past seq_len
   bf16_t* tokens = e->buf<bf16_t>("tokens");
   if (e->Kp != c.in_dim * 4) HIP_TRY(hipMemsetAsync(tokens, 0, (size_t)e->Lp * e->Kp * 2, s));
@@ -559,7 +574,7 @@ mc_status mc_embed(mc_engine* e, const float* latent_dev, const float* t_dev, do
                               tokens, e->Kp, s));
   {
     mc::GemmParams p = gp(tokens, e->Kp, e->w_patch, e->Kp, e->b_patch, e->Lp, d, e->Kp);
-    p.X = e->buf<float>("x"); p.ldx = d;
+    p.X = x; p.ldx = d;
     p.X0out = e->buf<bf16_t>("x0"); p.ldx0out = d;
     p.m_valid = e->Lr;
     HIP_TRY(mc::launch_gemm_bf16(p, mc::EPI_EMBED, s));
@@ -589,16 +604,39 @@ mc_status mc_embed(mc_engine* e, const float* latent_dev, const float* t_dev, do
                                    emod + (size_t)l * 6 * d, 6 * d, s));
     HIP_TRY(mc::launch_add_bcast(ev, d, e->head_mod, e->buf<float>("ehead") + set * 2 * d, 2 * d, s));
   }
-  // context = text_embedding(zero-padded context)   (:256-262); NULL: the slot selected by mc_set_context / mc_use_context
+  return MC_OK;
+}
+
+// context = text_embedding(zero-padded context)   (:256-262); NULL: the slot selected by mc_set_context / mc_use_context
+static mc_status embed_text(mc_engine* e, const void* context_dev, mc_dtype ctx_dtype, int ctx_len, hipStream_t s) {
   if (context_dev) {
     e->ctx_active = -1;
-    mc_status cst = embed_context(e, context_dev, ctx_dtype, ctx_len, e->buf<bf16_t>("ctx"), s);
-    if (cst != MC_OK) return cst;
-  } else if (e->ctx_active < 0 || !e->ctx_valid[e->ctx_active]) {
-    return fail(MC_ESTATE, "context_dev is NULL but no cached context is selected (mc_set_context)");
+    return embed_context(e, context_dev, ctx_dtype, ctx_len, e->buf<bf16_t>("ctx"), s);
   }
+  if (e->ctx_active < 0 || !e->ctx_valid[e->ctx_active])
+    return fail(MC_ESTATE, "context_dev is NULL but no cached context is selected (mc_set_context)");
+  return MC_OK;
+}
+
+static mc_status embed(mc_engine* e, const float* latent_dev, const float* t_dev, double t_host, const void* context_dev,
+                       mc_dtype ctx_dtype, int ctx_len, float* x, hipStream_t s) {
+  mc_status st = check_ready(e);
+  if (st != MC_OK) return st;
+  if (!latent_dev) return fail(MC_EINVAL, "null input");
+  if (e->cfg.clip_dim > 0 && !e->have_clip)
+    return fail(MC_ESTATE, "i2v model: mc_set_clip_fea must run before the forward (reference assert :226-227)");
+  Prof pr(e, MC_PROF_EMBED, s);
+  MC_TRY(embed_latent_time(e, latent_dev, t_dev, t_host, x, s));
+  MC_TRY(embed_text(e, context_dev, ctx_dtype, ctx_len, s));
   e->embedded = true;
   return MC_OK;
+}
+
+mc_status mc_embed(mc_engine* e, const float* latent_dev, const float* t_dev, double t_host,
+                   const void* context_dev, mc_dtype ctx_dtype, int ctx_len, mc_stream stream_) {
+  if (e) e->pair_drop();   // a phase call rewrites the embeds a kept front consists of
+  return embed(e, latent_dev, t_dev, t_host, context_dev, ctx_dtype, ctx_len, e ? e->buf<float>("x") : nullptr,
+               (hipStream_t)stream_);
 }
 
 // ---- the one launch path of a block's Linears
@@ -742,6 +780,7 @@ static mc_status check_layer_call(mc_engine* e, int layer) {
 
 mc_status mc_block_pre_attn(mc_engine* e, int layer, mc_stream stream_) {
   if (mc_status st = check_layer_call(e, layer); st != MC_OK) return st;
+  e->pair_drop();   // a phase call works on "x", where a kept front lies
   return block_pre(e, e->layers[layer], e->buf<float>("emod") + (size_t)layer * 6 * e->d, e->buf<float>("x"),
                    (hipStream_t)stream_);
 }
@@ -751,6 +790,7 @@ mc_status mc_block_pre_attn(mc_engine* e, int layer, mc_stream stream_) {
 mc_status mc_block_pre_kv(mc_engine* e, int layer, mc_stream stream_) {
   if (mc_status st = check_layer_call(e, layer); st != MC_OK) return st;
   if (!e->sp) return fail(MC_ESTATE, "mc_block_pre_kv needs a sequence-parallel engine (sp_size > 1 or sp_phases) (one GPU: mc_block_pre_attn / mc_forward)");
+  e->pair_drop();
   return block_pre_kv(e, e->layers[layer], e->buf<float>("emod") + (size_t)layer * 6 * e->d, e->buf<float>("x"),
                       (hipStream_t)stream_);
 }
@@ -758,6 +798,7 @@ mc_status mc_block_pre_kv(mc_engine* e, int layer, mc_stream stream_) {
 mc_status mc_block_pre_q(mc_engine* e, int layer, mc_stream stream_) {
   if (mc_status st = check_layer_call(e, layer); st != MC_OK) return st;
   if (!e->sp) return fail(MC_ESTATE, "mc_block_pre_q needs a sequence-parallel engine (sp_size > 1 or sp_phases)");
+  e->pair_drop();
   return block_pre_q(e, e->layers[layer], (hipStream_t)stream_);
 }
 
@@ -870,6 +911,7 @@ mc_status mc_sp_set_chunks(mc_engine* e, int chunks) {
     return fail(MC_EINVAL, "sp chunks %d: rows per shard %d / chunks must be a multiple of 64", chunks, e->Lp);
   e->sp_chunks = chunks;
   e->attn_layer = -2;
+  e->pair_drop();
   return MC_OK;
 }
 
@@ -898,12 +940,16 @@ mc_status mc_sp_round_info(const mc_engine* e, int round, int* n_rounds, int* ch
   return MC_OK;
 }
 
-// attention -> o (+gated residual) -> norm3 -> cross-attn (+residual) -> LN+mod -> FFN (+gated residual)
+// attention -> o (+gated residual) -> norm3 -> cross-attn (+residual) -> LN+mod -> FFN (+gated residual), in two halves that
+// meet where the text context enters the block:
+//   block_post_self  self-attention, o (+gated residual), norm3, the cross-attention q Linear and its RMSNorm -> cq
+//   block_post_ctx   cross-attention over the context's K|V (+residual), LN+mod, FFN (+gated residual)
 // layer: main-layer index (sequence-parallel two-phase bookkeeping), -1 for a VACE block.  capture: fuse the MagCache
 // residual capture into the last epilogue (the last main layer, unless a VACE hint is still to be added to it).
-static mc_status block_post(mc_engine* e, const Layer& l, const float* em, float* x, int layer, bool capture, int branch,
-                            mc_mode mode, hipStream_t s) {
-  const int d = e->d, Lp = e->Lp, ffn = e->ffn;
+// cq [Lp][d]: the normalised cross-attention q rows -- the head of "qkv" (the self-attention q/k/v are dead by then), or
+// "pair_cq" in the two forwards of a CFG pair.
+static mc_status block_post_self(mc_engine* e, const Layer& l, const float* em, float* x, int layer, bf16_t* cq, hipStream_t s) {
+  const int d = e->d, Lp = e->Lp;
   bf16_t* qkv = e->buf<bf16_t>("qkv");
   bf16_t* ao = e->buf<bf16_t>("ao");
   const float scale = 1.0f / std::sqrt(128.0f);
@@ -938,24 +984,31 @@ static mc_status block_post(mc_engine* e, const Layer& l, const float* em, float
     MC_TRY(linear(e, l.o, whole(l.o), ActSrc{ao, d}, p, mc::EPI_RESID_GATE, s));
   }
   // ---- cross attention: x = x + o(attn(norm_q(q(norm3(x))), norm_k(k(ctx)), v(ctx)))
-  ActSrc xn;   // LayerNorm output: the activation rows of cross-attention Q, then of FFN-1
+  ActSrc xn;   // LayerNorm output: the activation rows of cross-attention Q
   {
     Prof pr(e, MC_PROF_LN_MODULATE, s);
     MC_TRY(ln_for_gemm(e, l.cq, x, l.n3w, l.n3b, 1, nullptr, nullptr, nullptr, s, &xn));
   }
-  bf16_t* cq = qkv;  // the self-attention q/k/v are dead now
+  mc::GemmParams p = {};
+  p.Cb = cq; p.ldc = d;
+  {
+    Prof pr(e, MC_PROF_GEMM_CROSS_Q, s);
+    MC_TRY(linear(e, l.cq, whole(l.cq), xn, p, mc::EPI_BF16, s));
+  }
+  Prof pr(e, MC_PROF_RMSNORM_ROPE, s);
+  HIP_TRY(mc::launch_rmsnorm_rope(cq, d, l.cnq, e->cfg.eps, nullptr, 0, Lp, d, s));
+  return MC_OK;
+}
+
+static mc_status block_post_ctx(mc_engine* e, const Layer& l, const float* em, float* x, int layer, const bf16_t* cq,
+                                bool capture, int branch, mc_mode mode, hipStream_t s) {
+  const int d = e->d, Lp = e->Lp, ffn = e->ffn;
+  bf16_t* ao = e->buf<bf16_t>("ao");
+  const float scale = 1.0f / std::sqrt(128.0f);
+  const float* em2 = second_set(e, em);
+  const uint8_t* sel = tok_sel(e);
   bf16_t* ckv = e->buf<bf16_t>("ckv");
   {
-    mc::GemmParams p = {};
-    p.Cb = cq; p.ldc = d;
-    {
-      Prof pr(e, MC_PROF_GEMM_CROSS_Q, s);
-      MC_TRY(linear(e, l.cq, whole(l.cq), xn, p, mc::EPI_BF16, s));
-    }
-    {
-      Prof pr(e, MC_PROF_RMSNORM_ROPE, s);
-      HIP_TRY(mc::launch_rmsnorm_rope(cq, d, l.cnq, e->cfg.eps, nullptr, 0, Lp, d, s));
-    }
     if (e->ctx_active >= 0) {
       // constant over a video for this context: computed once by mc_set_context
       const size_t li = (size_t)(&l - (layer >= 0 ? e->layers.data() : e->vlayers.data())) + (layer >= 0 ? 0 : e->NL);
@@ -995,6 +1048,7 @@ static mc_status block_post(mc_engine* e, const Layer& l, const float* em, float
     MC_TRY(linear(e, l.co, whole(l.co), ActSrc{ao, d}, o, mc::EPI_RESID_GATE, s));
   }
   // ---- FFN: x = x + ffn(LN(x)*(1+e[4])+e[3]) * e[5]
+  ActSrc xn;   // LayerNorm output: the activation rows of FFN-1
   {
     Prof pr(e, MC_PROF_LN_MODULATE, s);
     MC_TRY(ln_for_gemm(e, l.ffn1, x, em + 4 * d, em + 3 * d, 0, em2 ? em2 + 4 * d : nullptr, em2 ? em2 + 3 * d : nullptr, sel,
@@ -1055,6 +1109,12 @@ static mc_status block_post(mc_engine* e, const Layer& l, const float* em, float
   return MC_OK;
 }
 
+static mc_status block_post(mc_engine* e, const Layer& l, const float* em, float* x, int layer, bf16_t* cq, bool capture,
+                            int branch, mc_mode mode, hipStream_t s) {
+  MC_TRY(block_post_self(e, l, em, x, layer, cq, s));
+  return block_post_ctx(e, l, em, x, layer, cq, capture, branch, mode, s);
+}
+
 // The last main layer receives a VACE hint: no fused capture there, the residual is taken after the hint was added.
 static bool hint_on_last_layer(const mc_engine* e) {
   return e->NV > 0 && (e->NV - 1) * e->cfg.vace_stride == e->NL - 1;
@@ -1064,8 +1124,9 @@ mc_status mc_block_post_attn(mc_engine* e, int layer, int branch, mc_mode mode, 
   if (!e || !e->embedded) return fail(MC_ESTATE, "mc_embed must run first");
   if (layer < 0 || layer >= e->NL) return fail(MC_EINVAL, "layer %d out of range", layer);
   if (branch < 0 || branch >= e->cfg.n_branches) return fail(MC_EINVAL, "branch %d out of range", branch);
+  e->pair_drop();
   return block_post(e, e->layers[layer], e->buf<float>("emod") + (size_t)layer * 6 * e->d, e->buf<float>("x"), layer,
-                    layer == e->NL - 1 && !hint_on_last_layer(e), branch, mode, (hipStream_t)stream_);
+                    e->buf<bf16_t>("qkv"), layer == e->NL - 1 && !hint_on_last_layer(e), branch, mode, (hipStream_t)stream_);
 }
 
 // VACE: control block i on the stream c, then x += after_proj(c) * context_scale (the "hint" of main layer
@@ -1092,8 +1153,8 @@ static mc_status vace_pre(mc_engine* e, int i, hipStream_t s) {
 static mc_status vace_post(mc_engine* e, int i, int branch, mc_mode mode, hipStream_t s) {
   const int d = e->d, Lp = e->Lp;
   float* xc = e->buf<float>("xc");
-  mc_status st = block_post(e, e->vlayers[i], e->buf<float>("emod") + (size_t)(e->NL + i) * 6 * d, xc, -1, false, branch,
-                            mode, s);
+  mc_status st = block_post(e, e->vlayers[i], e->buf<float>("emod") + (size_t)(e->NL + i) * 6 * d, xc, -1,
+                            e->buf<bf16_t>("qkv"), false, branch, mode, s);
   if (st != MC_OK) return st;
   // hint: after_proj(c) needs bf16 rows of c; the LayerNorm scratch xn is free here
   bf16_t* xn = e->buf<bf16_t>("xn");
@@ -1254,8 +1315,7 @@ static mc_status capture_unfused(mc_engine* e, int branch, mc_mode mode, hipStre
 }
 
 // head(x, e) on this rank's tokens -> "head_tokens" [Lr, 4*out_dim] fp32       (reference :304)
-mc_status mc_head(mc_engine* e, int branch, mc_mode mode, mc_stream stream_) {
-  hipStream_t s = (hipStream_t)stream_;
+static mc_status head(mc_engine* e, const float* x, int branch, mc_mode mode, hipStream_t s) {
   if (!e || !e->embedded) return fail(MC_ESTATE, "mc_embed must run first");
   if (branch < 0 || branch >= e->cfg.n_branches) return fail(MC_EINVAL, "branch %d out of range", branch);
   const int d = e->d;
@@ -1270,12 +1330,18 @@ mc_status mc_head(mc_engine* e, int branch, mc_mode mode, mc_stream stream_) {
     HIP_TRY(mc::launch_ln_modulate(e->residual(e->res_slot[branch]), d, e->buf<bf16_t>("x0"), d, eh + d, eh, 0,
                                    e->cfg.eps, nullptr, 0, hn, d, e->Lr, d, s, eh2 ? eh2 + d : nullptr, eh2, sel));
   } else {
-    HIP_TRY(mc::launch_ln_modulate(e->buf<float>("x"), d, nullptr, 0, eh + d, eh, 0, e->cfg.eps, nullptr, 0, hn, d,
+    HIP_TRY(mc::launch_ln_modulate(x, d, nullptr, 0, eh + d, eh, 0, e->cfg.eps, nullptr, 0, hn, d,
                                    e->Lr, d, s, eh2 ? eh2 + d : nullptr, eh2, sel));
   }
   HIP_TRY(mc::launch_head_linear(hn, d, e->w_head, e->b_head, e->buf<float>("head_tokens"), e->HT, e->Lr,
                                  e->cfg.out_dim * 4, d, s));
   return MC_OK;
+}
+
+mc_status mc_head(mc_engine* e, int branch, mc_mode mode, mc_stream stream) {
+  if (!e) return fail(MC_ESTATE, "mc_embed must run first");
+  e->pair_drop();   // every phase call ends a declared pair: between its forwards "x" is not a finished stream
+  return head(e, e->buf<float>("x"), branch, mode, (hipStream_t)stream);
 }
 
 mc_status mc_unpatchify(mc_engine* e, const float* tokens_dev, int tok0, int n_tok, float* out_dev,
@@ -1289,6 +1355,24 @@ mc_status mc_unpatchify(mc_engine* e, const float* tokens_dev, int tok0, int n_t
   return MC_OK;
 }
 
+// CFG pair.  The sampler evaluates the model twice per step on the same latent and the same t; only the text context differs,
+// and the context first enters a block at layer 0's cross-attention K|V.  Between mc_pair_begin and mc_pair_end the first
+// mc_forward that runs its blocks works on "pair_x" / "pair_cq" instead of "x" / "qkv" and copies the stream to "x" behind
+// layer 0's O epilogue (the epilogues update the stream in place: one of the two forwards needs its own copy); the second
+// starts from that "x" at layer 0's cross-attention.  The same kernels run on the same values in the same order as in two
+// full forwards, so the results are the same bits.
+mc_status mc_pair_begin(mc_engine* e) {
+  if (!e) return fail(MC_EINVAL, "null engine");
+  e->pair = e->pair_capable() ? mc_engine::PAIR_ARMED : mc_engine::PAIR_NONE;
+  return MC_OK;
+}
+
+mc_status mc_pair_end(mc_engine* e) {
+  if (!e) return fail(MC_EINVAL, "null engine");
+  e->pair = mc_engine::PAIR_NONE;
+  return MC_OK;
+}
+
 mc_status mc_forward(mc_engine* e, const float* latent_dev, const float* t_dev, double t_host,
                      const void* context_dev, mc_dtype ctx_dtype, int ctx_len, int branch, mc_mode mode,
                      float* out_dev, mc_stream stream) {
@@ -1297,25 +1381,58 @@ mc_status mc_forward(mc_engine* e, const float* latent_dev, const float* t_dev, 
   if (!out_dev) return fail(MC_EINVAL, "null output");
   if (e->NV > 0 && mode != MC_MODE_SKIP && !e->have_vace)
     return fail(MC_ESTATE, "VACE model: mc_set_vace_context must run before a non-skipped forward");
-  mc_status st = mc_embed(e, latent_dev, t_dev, t_host, context_dev, ctx_dtype, ctx_len, stream);
-  if (st != MC_OK) return st;
-  if (mode != MC_MODE_SKIP) {
+  if (branch < 0 || branch >= e->cfg.n_branches) return fail(MC_EINVAL, "branch %d out of range", branch);
+  hipStream_t s = (hipStream_t)stream;
+  const int d = e->d;
+  // this call's place in a declared pair: `keep` = it runs the front and leaves it behind, `reuse` = it continues from the
+  // front the call before it left.  Every other case -- a skipped forward on either side, another t, a third forward -- ends
+  // the sharing, and the call runs in full
+  const bool runs = mode != MC_MODE_SKIP;
+  const bool reuse = e->pair == mc_engine::PAIR_KEPT && runs && latent_dev == e->pair_latent && t_dev == e->pair_t_dev &&
+                     t_host == e->pair_t_host;
+  const bool keep = e->pair == mc_engine::PAIR_ARMED && runs;
+  e->pair = keep ? mc_engine::PAIR_KEPT : e->pair == mc_engine::PAIR_NONE ? mc_engine::PAIR_NONE : mc_engine::PAIR_DEAD;
+  if (keep) { e->pair_latent = latent_dev; e->pair_t_dev = t_dev; e->pair_t_host = t_host; }
+  float* x = e->buf<float>(keep ? "pair_x" : "x");
+  bf16_t* cq = e->buf<bf16_t>(keep || reuse ? "pair_cq" : "qkv");
+  mc_status st;
+  if (reuse) {
+    if ((st = check_ready(e)) != MC_OK) return st;
+    if (context_dev) {
+      Prof pr(e, MC_PROF_EMBED, s);
+      st = embed_text(e, context_dev, ctx_dtype, ctx_len, s);
+    } else {
+      st = embed_text(e, nullptr, ctx_dtype, 0, s);
+    }
+  } else {
+    st = embed(e, latent_dev, t_dev, t_host, context_dev, ctx_dtype, ctx_len, x, s);
+  }
+  if (st != MC_OK) { e->pair_drop(); return st; }
+  if (runs) {
     for (int l = 0; l < e->NL; ++l) {
-      st = mc_block_pre_attn(e, l, stream);
-      if (st != MC_OK) return st;
-      st = mc_block_post_attn(e, l, branch, mode, stream);
-      if (st != MC_OK) return st;
+      const Layer& ly = e->layers[l];
+      const float* em = e->buf<float>("emod") + (size_t)l * 6 * d;
+      const bool capture = l == e->NL - 1 && !hint_on_last_layer(e);
+      if (!(reuse && l == 0)) {
+        if ((st = block_pre(e, ly, em, x, s)) != MC_OK) break;
+        if ((st = block_post_self(e, ly, em, x, l, l == 0 ? cq : e->buf<bf16_t>("qkv"), s)) != MC_OK) break;
+      }
+      if (keep && l == 0) {
+        Prof pr(e, MC_PROF_OTHER, s);
+        if (hipMemcpyAsync(e->buf<float>("x"), x, (size_t)e->Lp * d * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) {
+          st = fail(MC_EHIP, "hipMemcpyAsync of the kept stream failed");
+          break;
+        }
+      }
+      if ((st = block_post_ctx(e, ly, em, x, l, l == 0 ? cq : e->buf<bf16_t>("qkv"), capture, branch, mode, s)) != MC_OK) break;
       if (e->NV > 0 && l % e->cfg.vace_stride == 0 && l / e->cfg.vace_stride < e->NV) {
-        st = vace_block(e, l / e->cfg.vace_stride, branch, mode, (hipStream_t)stream);
-        if (st != MC_OK) return st;
+        if ((st = vace_block(e, l / e->cfg.vace_stride, branch, mode, s)) != MC_OK) break;
       }
     }
-    if (hint_on_last_layer(e)) {
-      st = capture_unfused(e, branch, mode, (hipStream_t)stream);
-      if (st != MC_OK) return st;
-    }
+    if (st == MC_OK && hint_on_last_layer(e)) st = capture_unfused(e, branch, mode, s);
+    if (st != MC_OK) { e->pair_drop(); return st; }
   }
-  st = mc_head(e, branch, mode, stream);
+  st = head(e, x, branch, mode, s);
   if (st != MC_OK) return st;
   return mc_unpatchify(e, e->buf<float>("head_tokens"), 0, e->L, out_dev, stream);
 }
@@ -1382,6 +1499,7 @@ mc_status mc_set_token_timesteps(mc_engine* e, const float* t_tokens_dev, mc_str
   if (t_tokens_dev && e->NV > 0) return fail(MC_EINVAL, "per-token timesteps are not defined for the VACE model");
   if (t_tokens_dev && e->cfg.no_token_timesteps) return fail(MC_ESTATE, "the engine was created with no_token_timesteps");
   e->tok_t = t_tokens_dev;
+  e->pair_drop();   // the modulation sets of a kept front belong to the timesteps it was embedded with
   return MC_OK;
 }
 

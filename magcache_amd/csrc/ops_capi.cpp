@@ -11,7 +11,7 @@ using mc::gp;
 extern "C" {
 
 const char* mc_last_error(void) { return mc::last_error(); }
-const char* mc_version(void) { return "magcache_hip 0.5 (gfx950)"; }
+const char* mc_version(void) { return "magcache_hip 0.6 (gfx950)"; }
 
 // split-K scratch of the single-op entry point (mc_op_set_splitk_workspace): the engines carry their own in their workspace
 static float* g_op_splitk_ws = nullptr;

@@ -275,6 +275,14 @@ class Engine:
             return None, float(t.reshape(-1)[0])
         return None, float(t)
 
+    def pair_begin(self):
+        """declare that the next two forward() calls get the same latent and the same t (the cond / uncond calls of one CFG
+        step): the second reuses everything the first computed before the text context enters (mc_pair_begin)"""
+        check(self.lib.mc_pair_begin(self.h))
+
+    def pair_end(self):
+        check(self.lib.mc_pair_end(self.h))
+
     # ---- phase API (sequence parallel)
     def embed(self, latent, t, context):
         latent = latent.float().contiguous()

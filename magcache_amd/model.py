@@ -248,6 +248,19 @@ class WanModelHIP:
             self._tok_next = (self._tok_next + 1) % len(self._tok_ring)
         return [out.float()]
 
+    def pair_begin(self):
+        """The sampler's declaration that the next two calls are the cond / uncond evaluations of ONE step -- same latent,
+        same t, same conditioning apart from the text context --, passed on to the engine (mc_pair_begin), which then
+        computes what does not depend on the context once.  Bit-identical results; an engine without the call ignores it."""
+        begin = getattr(self.engine, "pair_begin", None)
+        if begin is not None:
+            begin()
+
+    def pair_end(self):
+        end = getattr(self.engine, "pair_end", None)
+        if end is not None:
+            end()
+
     @staticmethod
     def _tok_examine(slot):
         slot[2] = False
