@@ -136,11 +136,39 @@ mc_status mc_create(const mc_config* cfg, mc_engine** out);
 /* ABI rule for mc_config: it only grows at its END and a zero in a new field means "as before".  mc_create reads
  * sizeof(mc_config) of THIS header; a caller compiled against an older header (a shorter struct) must call
  * mc_create_sized(cfg, sizeof(mc_config) as IT knows it, out): the missing tail is taken as zeros.  History: 0.1 ends at
- * vace_in_dim, 0.2 adds fp8_linear, 0.3 no_context_cache and no_token_timesteps, 0.5 sp_phases (0.6 adds calls only: mc_pair_begin / mc_pair_end); mc_version() names the library's. */
+ * vace_in_dim, 0.2 adds fp8_linear, 0.3 no_context_cache and no_token_timesteps, 0.5 sp_phases (0.6 adds calls only: mc_pair_begin / mc_pair_end; 0.7 adds calls only: mc_geometry_bytes / mc_set_geometry,
+ * mc_op_rope_axes / mc_op_rope_expand); mc_version() names the library's. */
 mc_status mc_create_sized(const mc_config* cfg, size_t cfg_bytes, mc_engine** out);
 void mc_destroy(mc_engine* e);
 size_t mc_workspace_bytes(const mc_engine* e);
 mc_status mc_set_workspace(mc_engine* e, void* ws_dev, size_t bytes);
+/* The latent grid as a property of the call (0.7).  mc_config.latent_f / _h / _w is the grid an engine STARTS with;
+ * mc_set_geometry changes it between forwards on the same weights (the reference's --size / --frame_num are per run).
+ * mc_geometry_bytes = the workspace bytes the grid would need (the engine is not changed): a host that serves several grids
+ * binds the MAXIMUM of their needs once and then switches without allocating.
+ * mc_set_geometry:
+ *   - T2V, I2V, VACE, TI2V and fp8 engines.  A sharded engine (sp_size > 1 or sp_phases) is refused with MC_EINVAL: its
+ *     "kv_gather", the RCCL binding of the workspace base and the host's gather views are sized by the shard.
+ *   - MC_ESTATE between mc_embed and mc_head of a phase forward.
+ *   - a grid mc_create would refuse (odd H or W, ...) is refused in the same way; a plan that does not fit the bound
+ *     workspace returns MC_EINVAL (the text names both byte counts) and leaves the engine untouched and usable at its
+ *     old grid.
+ *   - on success, in this order: hipDeviceSynchronize (earlier forwards may still read the old plan); the RoPE table and the
+ *     buffer of its per-axis values grow if they have to -- the only allocation, before anything changes, never inside a
+ *     forward --; the workspace is re-planned under its binding; the grid and the row counts are stored; the per-axis RoPE
+ *     values (mc_op_rope_axes: a few tens of KB) are uploaded and one launch expands them to the per-token table
+ *     (mc_op_rope_expand), the same bits as mc_op_rope_table.
+ *   - afterwards everything that lived at an offset that may have moved is forgotten, as on a new engine: the residual
+ *     caches and calibration statistics (MC_MODE_SKIP needs a new FULL forward), both text-context slots (mc_use_context
+ *     returns MC_ESTATE until mc_set_context), the CLIP image context (mc_set_clip_fea again), the VACE context
+ *     (mc_set_vace_context again), per-token timesteps (mc_set_token_timesteps again), a kept CFG front; offsets from
+ *     mc_buffer_info are those of the new plan.  mc_set_workspace forgets the same things: other memory loses those bytes
+ *     as surely as a re-plan does.
+ *   - it synchronises, so it must not be stream-captured, and a graph captured before it is void (other offsets, other
+ *     launch sizes).
+ * An engine that is never switched runs the launches it ran before on the same bytes: every offset of its plan is unchanged. */
+mc_status mc_geometry_bytes(const mc_engine* e, int latent_f, int latent_h, int latent_w, size_t* bytes);
+mc_status mc_set_geometry(mc_engine* e, int latent_f, int latent_h, int latent_w);
 /* named sub-buffer of the workspace (offset from ws_dev): "x", "x0", "kv_gather", "kv_local",
  * "head_tokens", "residual0", "residual1", "calib_sums", "calib_stats", ... */
 mc_status mc_buffer_info(const mc_engine* e, const char* name, size_t* offset, size_t* bytes);
@@ -188,7 +216,8 @@ mc_status mc_forward(mc_engine* e, const float* latent_dev, const float* t_dev, 
  * MC_PROF_OTHER pair.  Between the two forwards "x" holds the stream behind layer 0's O epilogue, not the first forward's
  * final stream (a phase call in between ends the pair, but reads that "x").  A host that never calls mc_pair_begin gets the
  * same launches and results as before; the one thing that changes for it is mc_workspace_bytes of a single-GPU bf16 T2V
- * engine, which grows by Lp * dim * 6 bytes for "pair_x" / "pair_cq" (302 MB at Wan2.1-1.3B 480p). */
+ * engine, which grows by Lp * dim * 6 bytes for "pair_x" / "pair_cq" (302 MB at Wan2.1-1.3B 480p).  mc_set_geometry drops a
+ * kept front like mc_set_workspace does. */
 mc_status mc_pair_begin(mc_engine* e);
 mc_status mc_pair_end(mc_engine* e);
 
@@ -499,6 +528,16 @@ mc_status mc_op_cast_bf16(const float* src_dev, void* dst_bf16_dev, size_t n, mc
 /* rope table the engine builds for a latent grid: fp32 [n_tok][64][2] (cos, sin), upstream
  * wan/modules/model.py rope_params + rope_apply split (d-4*(d//6), 2*(d//6), 2*(d//6)), d = 128 */
 mc_status mc_op_rope_table(int F, int Hp, int Wp, int tok0, int n_tok, float* cs_host);
+/* The same table in two steps, the way the engine builds its own: entry (token, i) depends on ONE of the token's grid
+ * coordinates, so the host computes only the per-axis (cos, sin) pairs -- F x 22 of the frame axis, then Hp x 21 of the height
+ * axis, then Wp x 21 of the width axis, each by the double expression of mc_op_rope_table -- and a kernel copies them into
+ * the per-token table.  mc_op_rope_axes is host arithmetic: *n_floats = 2 (22 F + 21 Hp + 21 Wp); axes_host == NULL only
+ * returns the count.  mc_op_rope_expand: axes_dev = those floats on the device; row r < n_tok of cs_dev [n_rows][64][2] is
+ * global token tok0 + r, rows >= n_tok and tokens >= F Hp Wp get the identity (1, 0).  MC_EINVAL for a null pointer, a
+ * non-positive size, tok0 < 0, n_tok > n_rows or a cs_dev that is not 16-byte aligned. */
+mc_status mc_op_rope_axes(int F, int Hp, int Wp, float* axes_host, size_t* n_floats);
+mc_status mc_op_rope_expand(const float* axes_dev, int F, int Hp, int Wp, int tok0, int n_tok, int n_rows, float* cs_dev,
+                            mc_stream stream);
 
 #ifdef __cplusplus
 }

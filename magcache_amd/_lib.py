@@ -51,6 +51,8 @@ SIGNATURES = {
     "mc_destroy": (None, [_vp]),
     "mc_workspace_bytes": (_sz, [_vp]),
     "mc_set_workspace": (_i, [_vp, _vp, _sz]),
+    "mc_geometry_bytes": (_i, [_vp, _i, _i, _i, C.POINTER(_sz)]),
+    "mc_set_geometry": (_i, [_vp, _i, _i, _i]),
     "mc_buffer_info": (_i, [_vp, C.c_char_p, C.POINTER(_sz), C.POINTER(_sz)]),
     "mc_set_weight": (_i, [_vp, C.c_char_p, _vp, _i, C.POINTER(C.c_int64), _i, _vp]),
     "mc_weights_missing": (_i, [_vp, C.c_char_p, _sz]),
@@ -126,6 +128,8 @@ SIGNATURES = {
     "mc_op_lincomb": (_i, [_vp, _vp, _i, _vp, _sz, _vp]),
     "mc_op_add_rows": (_i, [_vp, _l, _vp, _i, _vp, _l, _vp, _l, _i, _i, _vp]),
     "mc_op_rope_table": (_i, [_i, _i, _i, _i, _i, _vp]),
+    "mc_op_rope_axes": (_i, [_i, _i, _i, _vp, C.POINTER(_sz)]),
+    "mc_op_rope_expand": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     # include/magcache_mmdit.h
     "mc_mmdit_create": (_i, [_vp, C.POINTER(_vp)]),
     "mc_mmdit_destroy": (None, [_vp]),

@@ -324,6 +324,35 @@ __global__ void rope_table_from_cos_sin_kernel(const float* __restrict__ cosv, c
   cs[2 * i + 1] = sinv[(size_t)r * ld + 2 * p];
 }
 
+// The Wan RoPE table [n_rows][64][(cos,sin)] from its per-axis values (ops.h: launch_rope_expand): a copy, no arithmetic.
+// A row is 512 bytes = 32 lanes x 16 bytes (two pairs each), so a wave stores two whole rows = 1 KiB of consecutive
+// addresses per instruction; the few tens of KB of axis values are read through the caches.  Pairs 21 | 22 fall on a lane
+// boundary, 42 | 43 do not: each of a lane's two pairs finds its own axis.
+__global__ __launch_bounds__(256) void rope_expand_kernel(const float* __restrict__ axes, int F, int Hp, int Wp, int tok0,
+                                                          int n_tok, int n_rows, float* __restrict__ cs) {
+  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  if (i >= (long)n_rows * 32) return;
+  const int r = (int)(i >> 5), p0 = (int)(i & 31) * 2;
+  const long tok = (long)tok0 + r;
+  f32x4 o = {1.f, 0.f, 1.f, 0.f};
+  if (r < n_tok && tok < (long)F * Hp * Wp) {
+    const int f = (int)(tok / (Hp * Wp)), rem = (int)(tok % (Hp * Wp)), h = rem / Wp, w = rem % Wp;
+    const float* af = axes + (size_t)f * 2 * kRopePairsT;
+    const float* ah = axes + (size_t)F * 2 * kRopePairsT + (size_t)h * 2 * kRopePairsHW;
+    const float* aw = axes + (size_t)F * 2 * kRopePairsT + ((size_t)Hp + w) * 2 * kRopePairsHW;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int p = p0 + j;
+      const float* src = p < kRopePairsT ? af + 2 * p
+                         : p < kRopePairsT + kRopePairsHW ? ah + 2 * (p - kRopePairsT)
+                                                          : aw + 2 * (p - kRopePairsT - kRopePairsHW);
+      o[2 * j] = src[0];
+      o[2 * j + 1] = src[1];
+    }
+  }
+  *(f32x4*)(cs + i * 4) = o;
+}
+
 // ------------------------------------------------------------------ row-wise fp8 (OCP e4m3) quantisation
 __global__ __launch_bounds__(256) void quantize_rows_fp8_kernel(const bf16_t* __restrict__ x,
                                                                 const float* __restrict__ xf, long ldx, int M, int K,
@@ -762,6 +791,16 @@ hipError_t launch_rope_table_from_cos_sin(const float* cosv, const float* sinv, 
   if (n_rows <= 0) return hipErrorInvalidValue;
   hipLaunchKernelGGL(rope_table_from_cos_sin_kernel, dim3(((long)n_rows * 64 + 255) / 256), dim3(256), 0, stream, cosv,
                      sinv, ld, n_rows, cs);
+  return hipGetLastError();
+}
+
+hipError_t launch_rope_expand(const float* axes, int F, int Hp, int Wp, int tok0, int n_tok, int n_rows, float* cs,
+                              hipStream_t stream) {
+  if (!axes || !cs || F <= 0 || Hp <= 0 || Wp <= 0 || tok0 < 0 || n_tok <= 0 || n_rows <= 0 || n_tok > n_rows ||
+      (long)F * Hp * Wp > 0x7fffffffL || (long)Hp * Wp > 0x7fffffffL || ((uintptr_t)cs & 15))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(rope_expand_kernel, dim3((unsigned)(((long)n_rows * 32 + 255) / 256)), dim3(256), 0, stream, axes, F, Hp,
+                     Wp, tok0, n_tok, n_rows, cs);
   return hipGetLastError();
 }
 

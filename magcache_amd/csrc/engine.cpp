@@ -82,7 +82,11 @@ struct mc_engine {
   float *b_vpatch = nullptr, *b_before = nullptr, *vscale = nullptr;
   int NV = 0, Kvp = 0;
   bool have_vace = false;
-  float* cs_table = nullptr;  // rope (cos,sin) [Lp][64][2]
+  float* cs_table = nullptr;  // rope (cos,sin) [Lp][64][2]: expanded on the device from the per-axis values in rope_axes
+  float* rope_axes = nullptr; // (cos,sin) pairs of the grid's frame, height and width positions (mc_op_rope_axes layout)
+  int cs_rows = 0;            // rows allocated behind cs_table (>= Lp: mc_set_geometry grows it, never shrinks it)
+  size_t axes_cap = 0;        // floats allocated behind rope_axes
+  bool phase_open = false;    // between mc_embed and mc_head of a phase forward (mc_set_geometry refuses)
   mc::WeightStore weights;
   mc::Workspace work;
   int res_slot[2] = {0, 1};  // residual buffer index held by branch b
@@ -138,10 +142,21 @@ struct Prof {
 };
 
 // upstream rope_params / rope_apply frequency split for head_dim 128 (22 + 21 + 21 complex pairs)
+constexpr int kRopeT = mc::kRopePairsT, kRopeHW = mc::kRopePairsHW;
+constexpr double kRopeDimT = 44.0, kRopeDimHW = 42.0;   // d - 4 * (d / 6), 2 * (d / 6)
+
+// THE per-entry expression: (cos, sin) of position `pos` on an axis, frequency j of the axis' `dim` rotary channels.  The
+// per-token table (rope_table_host) and the per-axis values (rope_axes_host) both come from here, so that the table the
+// device expands from the axes is the host table bit for bit.
+inline void rope_pair(int pos, int j, double dim, float* cs) {
+  const double fr = 1.0 / std::pow(10000.0, (2.0 * j) / dim);
+  const double a = (double)pos * fr;
+  cs[0] = (float)std::cos(a);
+  cs[1] = (float)std::sin(a);
+}
+
 void rope_table_host(int F, int Hp, int Wp, int tok0, int n_tok, float* cs) {
-  const int d = 128, c = d / 2;
-  const int n_hw = c / 3, n_t = c - 2 * n_hw;             // 21, 22
-  const double dim_t = (double)(d - 4 * (d / 6)), dim_hw = (double)(2 * (d / 6));  // 44, 42
+  const int c = kRopeT + 2 * kRopeHW;
   for (int r = 0; r < n_tok; ++r) {
     const int tok = tok0 + r;
     float* row = cs + (size_t)r * 2 * c;
@@ -151,15 +166,173 @@ void rope_table_host(int F, int Hp, int Wp, int tok0, int n_tok, float* cs) {
     }
     const int f = tok / (Hp * Wp), rem = tok % (Hp * Wp), h = rem / Wp, w = rem % Wp;
     for (int i = 0; i < c; ++i) {
-      double pos, fr;
-      if (i < n_t) { pos = f; fr = 1.0 / std::pow(10000.0, (2.0 * i) / dim_t); }
-      else if (i < n_t + n_hw) { pos = h; fr = 1.0 / std::pow(10000.0, (2.0 * (i - n_t)) / dim_hw); }
-      else { pos = w; fr = 1.0 / std::pow(10000.0, (2.0 * (i - n_t - n_hw)) / dim_hw); }
-      const double a = pos * fr;
-      row[2 * i] = (float)std::cos(a);
-      row[2 * i + 1] = (float)std::sin(a);
+      if (i < kRopeT) rope_pair(f, i, kRopeDimT, row + 2 * i);
+      else if (i < kRopeT + kRopeHW) rope_pair(h, i - kRopeT, kRopeDimHW, row + 2 * i);
+      else rope_pair(w, i - kRopeT - kRopeHW, kRopeDimHW, row + 2 * i);
     }
   }
+}
+
+// what the table is separable into: entry (token, i) depends on ONE of the token's grid coordinates.  F x 22 pairs of the
+// frame axis, then Hp x 21 of the height axis, then Wp x 21 of the width axis
+size_t rope_axes_floats(int F, int Hp, int Wp) { return 2 * ((size_t)F * kRopeT + ((size_t)Hp + Wp) * kRopeHW); }
+
+void rope_axes_host(int F, int Hp, int Wp, float* axes) {
+  for (int f = 0; f < F; ++f)
+    for (int j = 0; j < kRopeT; ++j, axes += 2) rope_pair(f, j, kRopeDimT, axes);
+  for (int h = 0; h < Hp; ++h)
+    for (int j = 0; j < kRopeHW; ++j, axes += 2) rope_pair(h, j, kRopeDimHW, axes);
+  for (int w = 0; w < Wp; ++w)
+    for (int j = 0; j < kRopeHW; ++j, axes += 2) rope_pair(w, j, kRopeDimHW, axes);
+}
+
+// ---- the latent grid: what a call may change (mc_set_geometry).  mc_create and mc_set_geometry share all of it.
+struct Rows { int L, Lr, Lp, tok0; };   // tokens of the sequence, of this rank, padded to the attention tile, first global token
+
+mc_status check_geometry(int latent_f, int latent_h, int latent_w, int P) {
+  if ((latent_h & 1) || (latent_w & 1) || latent_f <= 0 || latent_h <= 0 || latent_w <= 0)
+    return fail(MC_EINVAL, "latent grid %dx%dx%d not divisible by patch (1,2,2)", latent_f, latent_h, latent_w);
+  const long long L = (long long)latent_f * (latent_h / 2) * (latent_w / 2);
+  if (L > (1ll << 24)) return fail(MC_EINVAL, "latent grid %dx%dx%d: %lld tokens", latent_f, latent_h, latent_w, L);
+  if (L % P) return fail(MC_EINVAL, "seq_len %d not divisible by sp_size %d", (int)L, P);
+  return MC_OK;
+}
+
+Rows derive_rows(int latent_f, int latent_h, int latent_w, int P, int rank) {
+  Rows r;
+  r.L = latent_f * (latent_h / 2) * (latent_w / 2);
+  r.Lr = r.L / P;
+  r.Lp = (int)align_up(r.Lr, 256);
+  r.tok0 = rank * r.Lr;
+  return r;
+}
+
+// split-K scratch of FFN-2 (K = ffn): a rank of a wide sequence-parallel job has too few 256^2 tiles for the chip (sp 8 at
+// 1.3B: M = 4096 -> 96 tiles), launch_gemm_bf16 then cuts K in slices (policy: gemm_bf16_v2.hip); 0 bytes where it would not
+size_t splitk_need(const mc_engine* e, int Lp) {
+  return e->sp ? mc::gemm_splitk_ws_need(Lp, e->d, e->ffn, mc::EPI_RESID_GATE) : 0;
+}
+
+void plan_workspace(const mc_engine* e, const Rows& rows, mc::Workspace& ws) {
+  const mc_config& c = e->cfg;
+  const size_t d = e->d, ffn = e->ffn;
+  const size_t Lp = rows.Lp;
+  ws.add("x", Lp * d * 4);
+  ws.add("x0", Lp * d * 2);
+  ws.add("xn", Lp * d * 2);
+  ws.add("qkv", Lp * 3 * d * 2);  // P>1: only the first Lp*d (q) is used
+  ws.add("ao", Lp * d * 2);
+  ws.add("h", std::max(Lp * ffn * 2, Lp * d * 4));  // FFN hidden (bf16) / head LN out (fp32)
+  ws.add("tokens", Lp * e->Kp * 2);
+  ws.add("ctx_in", (size_t)e->ctx_rows * c.text_dim * 2);
+  ws.add("ctx_h", (size_t)e->ctx_rows * d * 2);
+  ws.add("ctx", (size_t)e->ctx_rows * d * 2);
+  ws.add("ckv", (size_t)e->ctx_rows * 2 * d * 2);
+  ws.add("ctx_cache", (size_t)2 * e->ctx_rows * d * 2);                              // [2 slots][ctx_rows][d]
+  if (!c.no_context_cache)      // (ADVICE r02: 0.84 GB at 14B that a caller who passes its context every forward never uses)
+    ws.add("ckv_cache", (size_t)2 * (e->NL + e->NV) * e->ctx_rows * 2 * d * 2);      // [2][layers][ctx_rows][2d]
+  // two sets of everything that depends on t: set 0 for the (maximum) timestep, set 1 for the second value per-token
+  // timesteps may carry (Wan2.2 TI2V: the conditioning frame's tokens have t = 0)
+  const size_t tsets = c.no_token_timesteps ? 1 : 2;
+  ws.add("temb", tsets * (c.freq_dim + 2 * d + 6 * d) * 4);  // sets x (sinus | h1 | e | e0)
+  ws.add("emod", tsets * (e->NL + e->NV) * 6 * d * 4);
+  ws.add("tok_sel", c.no_token_timesteps ? 256 : (size_t)Lp + 256);
+  ws.add("tok_t2", 64);
+  if (c.fp8_linear) {
+    ws.add("aq", Lp * std::max(d, ffn));            // e4m3 activations of the current fp8 GEMM
+    ws.add("a_scale", Lp * 4);                      // their per-token scales
+    if (c.fp8_linear >= 2) ws.add("a_mx", (std::max(d, ffn) / 32) * Lp);   // MX: per (token, 32 k) block scales
+  }
+  if (e->NV > 0) {
+    ws.add("xc", Lp * d * 4);                       // VACE control stream c (fp32 like x)
+    ws.add("c0", Lp * d * 2);                       // vace_patch_embedding(vace_context), constant per video
+    ws.add("vtokens", Lp * (size_t)e->Kvp * 2);
+  }
+  ws.add("ehead", 2 * 2 * d * 4);
+  ws.add("head_tokens", (size_t)Lp * e->HT * 4);
+  // sequence parallel: "kv_local" [Lp][2d] = this rank's post-norm, post-RoPE K|V rows (the send buffer of the gather);
+  // "kv_gather" [C][P][Lp / C][2d] = round c of the gather holds rows [c Lp / C, (c + 1) Lp / C) of EVERY rank's shard
+  ws.add("kv_local", e->sp ? Lp * 2 * d * 2 : 256);
+  ws.add("kv_gather", e->sp ? (size_t)e->P * Lp * 2 * d * 2 : 256);
+  ws.add("residual0", Lp * d * 4);
+  ws.add("residual1", c.n_branches > 1 ? Lp * d * 4 : 256);
+  ws.add("residual2", c.calibration ? Lp * d * 4 : 256);
+  if (c.clip_dim > 0) {
+    const size_t ir = e->img_rows, cd = c.clip_dim;
+    ws.add("clip_in", ir * cd * 4);
+    ws.add("clip_n", ir * cd * 2);
+    ws.add("clip_h", ir * cd * 2);
+    ws.add("clip_o", ir * d * 4);
+    ws.add("clip_h2", ir * d * 2);
+    ws.add("ctx_img", ir * d * 2);
+    ws.add("ckv_img", ir * 2 * d * 2);
+    ws.add("ao2", Lp * d * 2);
+  }
+  if (e->sp) ws.add("attn_lse", (size_t)e->H * Lp * 4);
+  const size_t splitk = splitk_need(e, rows.Lp);     // split-K scratch of FFN-2
+  ws.add("splitk", splitk ? splitk : 256);
+  // partial attention results of a layer's chain (local shard + up to 8 gather rounds), merged by attn_merge
+  ws.add("ao_part", e->P > 1 ? (size_t)kSpMaxParts * Lp * d * 2 : 256);
+  ws.add("lse_part", e->P > 1 ? (size_t)kSpMaxParts * e->H * Lp * 4 : 256);
+  ws.add("calib_partial", (2048 * 4 + 2) * 8);   // + the arrival ticket of calib_stats_kernel
+  ws.add("calib_sums", 4 * 8);
+  ws.add("calib_stats", 2 * 3 * 4);
+  // the kept front of a CFG pair (mc_pair_begin): last in the plan, every other offset stays where it was
+  ws.add("pair_x", e->pair_capable() ? Lp * d * 4 : 256);
+  ws.add("pair_cq", e->pair_capable() ? Lp * d * 2 : 256);
+}
+
+// The RoPE table of the engine's grid, for this rank's rows: the per-axis values are computed on the host (the doubles of
+// rope_table_host), uploaded -- a few tens of KB -- and expanded to [Lp][64][2] by one launch; rows >= Lr are padding:
+// identity.  rope_reserve is the one step that allocates (through the weight store, never inside a forward), so that
+// mc_set_geometry can run it before anything changes.
+mc_status rope_reserve(mc_engine* e, int Lp, size_t axes_floats) {
+  if (Lp > e->cs_rows) {
+    float* grown = nullptr;
+    MC_TRY(e->weights.alloc(&grown, (size_t)Lp * 128));
+    if (e->cs_table) e->weights.release(e->cs_table);
+    e->cs_table = grown;
+    e->cs_rows = Lp;
+  }
+  if (axes_floats > e->axes_cap) {
+    float* grown = nullptr;
+    MC_TRY(e->weights.alloc(&grown, axes_floats));
+    if (e->rope_axes) e->weights.release(e->rope_axes);
+    e->rope_axes = grown;
+    e->axes_cap = axes_floats;
+  }
+  return MC_OK;
+}
+
+mc_status rope_build(mc_engine* e) {
+  const int F = e->cfg.latent_f, Hp = e->cfg.latent_h / 2, Wp = e->cfg.latent_w / 2;
+  std::vector<float> axes(rope_axes_floats(F, Hp, Wp));
+  rope_axes_host(F, Hp, Wp, axes.data());
+  HIP_TRY(hipMemcpy(e->rope_axes, axes.data(), axes.size() * sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(mc::launch_rope_expand(e->rope_axes, F, Hp, Wp, e->tok0, e->Lr, e->Lp, e->cs_table, nullptr));
+  HIP_TRY(hipStreamSynchronize(nullptr));   // the forwards run on the caller's streams
+  return MC_OK;
+}
+
+// What a (re)bound or re-planned workspace means for the state: everything that lived at an offset that may have moved, or in
+// memory that is no longer the engine's, is forgotten -- the residual caches and calibration statistics, the embeds of an
+// open phase forward, both text-context slots, the CLIP image context, the VACE context and a kept CFG front; per-token
+// timesteps were a vector over the old sequence.  (Before 0.7 mc_set_workspace kept ctx_valid, have_clip and have_vace, whose
+// bytes a rebind loses as surely as a re-plan does; no caller could tell: the Python shim binds once, before any of them is set.)
+mc_status forget_workspace_state(mc_engine* e) {
+  e->have_res[0] = e->have_res[1] = false;
+  e->have_stats[0] = e->have_stats[1] = false;
+  e->res_slot[0] = 0; e->res_slot[1] = 1; e->res_scratch = 2;
+  e->embedded = e->phase_open = false;
+  e->ctx_valid[0] = e->ctx_valid[1] = false;
+  e->ctx_active = -1;
+  e->have_clip = e->have_vace = false;
+  e->tok_t = nullptr;
+  e->attn_layer = -2;
+  e->pair_drop();
+  // the arrival ticket of the one-launch calibration reduction starts at zero (the kernel rearms it itself)
+  if (e->work.ws) HIP_TRY(hipMemset(e->buf<double>("calib_partial") + 2048 * 4, 0, 16));
+  return MC_OK;
 }
 
 mc_status check_ready(const mc_engine* e) {
@@ -206,9 +379,8 @@ mc_status mc_create(const mc_config* cfg, mc_engine** out) {
     return fail(MC_EINVAL, "dim (%d) must be num_heads (%d) * 128", c.dim, c.num_heads);
   if ((c.dim % 256) || (c.ffn_dim % 64) || (c.text_dim % 64) || (c.freq_dim % 4) || c.num_layers <= 0)
     return fail(MC_EINVAL, "unsupported geometry dim=%d ffn=%d text_dim=%d", c.dim, c.ffn_dim, c.text_dim);
-  if ((c.latent_h & 1) || (c.latent_w & 1) || c.latent_f <= 0)
-    return fail(MC_EINVAL, "latent grid %dx%dx%d not divisible by patch (1,2,2)", c.latent_f, c.latent_h, c.latent_w);
   if (c.sp_size < 1 || c.sp_rank < 0 || c.sp_rank >= c.sp_size) return fail(MC_EINVAL, "bad sp rank/size");
+  MC_TRY(check_geometry(c.latent_f, c.latent_h, c.latent_w, c.sp_size));
   if (c.n_branches != 1 && c.n_branches != 2) return fail(MC_EINVAL, "n_branches must be 1 or 2");
   if (c.out_dim * 4 > 256) return fail(MC_EINVAL, "out_dim*4 > 256 unsupported by the head kernel");
   if (c.clip_dim < 0 || (c.clip_dim % 256) != 0) return fail(MC_EINVAL, "clip_dim %d must be 0 or a multiple of 256", c.clip_dim);
@@ -227,13 +399,10 @@ mc_status mc_create(const mc_config* cfg, mc_engine** out) {
   mc_engine* e = own.get();
   e->cfg = c;
   e->d = c.dim; e->ffn = c.ffn_dim; e->H = c.num_heads; e->NL = c.num_layers;
-  e->L = c.latent_f * (c.latent_h / 2) * (c.latent_w / 2);
   e->P = c.sp_size; e->rank = c.sp_rank;
   e->sp = c.sp_size > 1 || c.sp_phases != 0;
-  if (e->L % e->P) return fail(MC_EINVAL, "seq_len %d not divisible by sp_size %d", e->L, c.sp_size);
-  e->Lr = e->L / e->P;
-  e->Lp = (int)align_up(e->Lr, 256);
-  e->tok0 = e->rank * e->Lr;
+  const Rows rows = derive_rows(c.latent_f, c.latent_h, c.latent_w, e->P, e->rank);
+  e->L = rows.L; e->Lr = rows.Lr; e->Lp = rows.Lp; e->tok0 = rows.tok0;
   e->Kp = (int)align_up((size_t)c.in_dim * 4, 64);
   e->HT = (int)align_up((size_t)c.out_dim * 4, 64);
   e->ctx_rows = (int)align_up(c.text_len, 64);
@@ -330,86 +499,14 @@ mc_status mc_create(const mc_config* cfg, mc_engine** out) {
   W.add("head.head.bias", e->b_head, MC_F32, (size_t)c.out_dim * 4);
   W.add("head.modulation", e->head_mod, MC_F32, 2 * d);
 
-  // RoPE table for this rank's rows
-  ALLOC(e->cs_table, (size_t)e->Lp * 128);
-  {
-    std::vector<float> cs((size_t)e->Lp * 128);
-    // rows >= Lr are padding: identity; rows < Lr are global tokens tok0 + r
-    rope_table_host(c.latent_f, c.latent_h / 2, c.latent_w / 2, e->tok0, e->Lr, cs.data());
-    for (size_t r = e->Lr; r < (size_t)e->Lp; ++r)
-      for (int i = 0; i < 64; ++i) { cs[r * 128 + 2 * i] = 1.f; cs[r * 128 + 2 * i + 1] = 0.f; }
-    HIP_TRY(hipMemcpy(e->cs_table, cs.data(), cs.size() * sizeof(float), hipMemcpyHostToDevice));
-  }
+  // RoPE table for this rank's rows: the two steps mc_set_geometry takes
+  MC_TRY(rope_reserve(e, e->Lp, rope_axes_floats(c.latent_f, c.latent_h / 2, c.latent_w / 2)));
+  MC_TRY(rope_build(e));
 #undef ALLOC
 
   // ---- workspace plan
-  mc::Workspace& ws = e->work;
-  const size_t Lp = e->Lp;
-  ws.add("x", Lp * d * 4);
-  ws.add("x0", Lp * d * 2);
-  ws.add("xn", Lp * d * 2);
-  ws.add("qkv", Lp * 3 * d * 2);  // P>1: only the first Lp*d (q) is used
-  ws.add("ao", Lp * d * 2);
-  ws.add("h", std::max(Lp * ffn * 2, Lp * d * 4));  // FFN hidden (bf16) / head LN out (fp32)
-  ws.add("tokens", Lp * e->Kp * 2);
-  ws.add("ctx_in", (size_t)e->ctx_rows * c.text_dim * 2);
-  ws.add("ctx_h", (size_t)e->ctx_rows * d * 2);
-  ws.add("ctx", (size_t)e->ctx_rows * d * 2);
-  ws.add("ckv", (size_t)e->ctx_rows * 2 * d * 2);
-  ws.add("ctx_cache", (size_t)2 * e->ctx_rows * d * 2);                              // [2 slots][ctx_rows][d]
-  if (!c.no_context_cache)      // (ADVICE r02: 0.84 GB at 14B that a caller who passes its context every forward never uses)
-    ws.add("ckv_cache", (size_t)2 * (e->NL + e->NV) * e->ctx_rows * 2 * d * 2);      // [2][layers][ctx_rows][2d]
-  // two sets of everything that depends on t: set 0 for the (maximum) timestep, set 1 for the second value per-token
-  // timesteps may carry (Wan2.2 TI2V: the conditioning frame's tokens have t = 0)
-  const size_t tsets = c.no_token_timesteps ? 1 : 2;
-  ws.add("temb", tsets * (c.freq_dim + 2 * d + 6 * d) * 4);  // sets x (sinus | h1 | e | e0)
-  ws.add("emod", tsets * (e->NL + e->NV) * 6 * d * 4);
-  ws.add("tok_sel", c.no_token_timesteps ? 256 : (size_t)Lp + 256);
-  ws.add("tok_t2", 64);
-  if (c.fp8_linear) {
-    ws.add("aq", Lp * std::max(d, ffn));            // e4m3 activations of the current fp8 GEMM
-    ws.add("a_scale", Lp * 4);                      // their per-token scales
-    if (c.fp8_linear >= 2) ws.add("a_mx", (std::max(d, ffn) / 32) * Lp);   // MX: per (token, 32 k) block scales
-  }
-  if (e->NV > 0) {
-    ws.add("xc", Lp * d * 4);                       // VACE control stream c (fp32 like x)
-    ws.add("c0", Lp * d * 2);                       // vace_patch_embedding(vace_context), constant per video
-    ws.add("vtokens", Lp * (size_t)e->Kvp * 2);
-  }
-  ws.add("ehead", 2 * 2 * d * 4);
-  ws.add("head_tokens", (size_t)Lp * e->HT * 4);
-  // sequence parallel: "kv_local" [Lp][2d] = this rank's post-norm, post-RoPE K|V rows (the send buffer of the gather);
-  // "kv_gather" [C][P][Lp / C][2d] = round c of the gather holds rows [c Lp / C, (c + 1) Lp / C) of EVERY rank's shard
-  ws.add("kv_local", e->sp ? Lp * 2 * d * 2 : 256);
-  ws.add("kv_gather", e->sp ? (size_t)e->P * Lp * 2 * d * 2 : 256);
-  ws.add("residual0", Lp * d * 4);
-  ws.add("residual1", c.n_branches > 1 ? Lp * d * 4 : 256);
-  ws.add("residual2", c.calibration ? Lp * d * 4 : 256);
-  if (c.clip_dim > 0) {
-    const size_t ir = e->img_rows, cd = c.clip_dim;
-    ws.add("clip_in", ir * cd * 4);
-    ws.add("clip_n", ir * cd * 2);
-    ws.add("clip_h", ir * cd * 2);
-    ws.add("clip_o", ir * d * 4);
-    ws.add("clip_h2", ir * d * 2);
-    ws.add("ctx_img", ir * d * 2);
-    ws.add("ckv_img", ir * 2 * d * 2);
-    ws.add("ao2", Lp * d * 2);
-  }
-  if (e->sp) ws.add("attn_lse", (size_t)e->H * Lp * 4);
-  // split-K scratch of FFN-2 (K = ffn): a rank of a wide sequence-parallel job has too few 256^2 tiles for the chip (sp 8 at
-  // 1.3B: M = 4096 -> 96 tiles), launch_gemm_bf16 then cuts K in slices (policy: gemm_bf16_v2.hip); 0 bytes where it would not
-  e->splitk_bytes = e->sp ? mc::gemm_splitk_ws_need((int)Lp, (int)d, (int)ffn, mc::EPI_RESID_GATE) : 0;
-  ws.add("splitk", e->splitk_bytes ? e->splitk_bytes : 256);
-  // partial attention results of a layer's chain (local shard + up to 8 gather rounds), merged by attn_merge
-  ws.add("ao_part", e->P > 1 ? (size_t)kSpMaxParts * Lp * d * 2 : 256);
-  ws.add("lse_part", e->P > 1 ? (size_t)kSpMaxParts * e->H * Lp * 4 : 256);
-  ws.add("calib_partial", (2048 * 4 + 2) * 8);   // + the arrival ticket of calib_stats_kernel
-  ws.add("calib_sums", 4 * 8);
-  ws.add("calib_stats", 2 * 3 * 4);
-  // the kept front of a CFG pair (mc_pair_begin): last in the plan, every other offset stays where it was
-  ws.add("pair_x", e->pair_capable() ? Lp * d * 4 : 256);
-  ws.add("pair_cq", e->pair_capable() ? Lp * d * 2 : 256);
+  e->splitk_bytes = splitk_need(e, e->Lp);
+  plan_workspace(e, rows, e->work);
   *out = own.release();
   return MC_OK;
 }
@@ -429,11 +526,40 @@ size_t mc_workspace_bytes(const mc_engine* e) { return e ? e->work.need : 0; }
 mc_status mc_set_workspace(mc_engine* e, void* ws_dev, size_t bytes) {
   if (!e) return fail(MC_EINVAL, "null argument");
   MC_TRY(e->work.bind(ws_dev, bytes));
-  e->have_res[0] = e->have_res[1] = false;
-  e->pair_drop();
-  // the arrival ticket of the one-launch calibration reduction starts at zero (the kernel rearms it itself)
-  HIP_TRY(hipMemset(e->buf<double>("calib_partial") + 2048 * 4, 0, 16));
+  return forget_workspace_state(e);
+}
+
+mc_status mc_geometry_bytes(const mc_engine* e, int latent_f, int latent_h, int latent_w, size_t* bytes) {
+  if (!e || !bytes) return fail(MC_EINVAL, "null argument");
+  MC_TRY(check_geometry(latent_f, latent_h, latent_w, e->P));
+  mc::Workspace plan;
+  plan_workspace(e, derive_rows(latent_f, latent_h, latent_w, e->P, e->rank), plan);
+  *bytes = plan.need;
   return MC_OK;
+}
+
+mc_status mc_set_geometry(mc_engine* e, int latent_f, int latent_h, int latent_w) {
+  if (!e) return fail(MC_EINVAL, "null engine");
+  if (e->sp)
+    return fail(MC_EINVAL, "mc_set_geometry: a sharded engine (sp_size %d%s) keeps the grid it was created with", e->P,
+                e->cfg.sp_phases ? ", sp_phases" : "");
+  if (e->phase_open) return fail(MC_ESTATE, "mc_set_geometry between mc_embed and mc_head");
+  MC_TRY(check_geometry(latent_f, latent_h, latent_w, e->P));
+  const Rows r = derive_rows(latent_f, latent_h, latent_w, e->P, e->rank);
+  mc::Workspace plan;
+  plan_workspace(e, r, plan);
+  if (e->work.ws && plan.need > e->work.bound)
+    return fail(MC_EINVAL, "latent grid %dx%dx%d needs a workspace of %zu bytes, %zu bytes are bound (mc_set_workspace)", latent_f,
+                latent_h, latent_w, plan.need, e->work.bound);
+  // earlier forwards may still be reading the RoPE table and the buffers of the old plan
+  HIP_TRY(hipDeviceSynchronize());
+  // the one step that can fail for lack of memory: before anything changes
+  MC_TRY(rope_reserve(e, r.Lp, rope_axes_floats(latent_f, latent_h / 2, latent_w / 2)));
+  MC_TRY(e->work.replan(plan));
+  e->cfg.latent_f = latent_f; e->cfg.latent_h = latent_h; e->cfg.latent_w = latent_w;
+  e->L = r.L; e->Lr = r.Lr; e->Lp = r.Lp; e->tok0 = r.tok0;
+  MC_TRY(rope_build(e));
+  return forget_workspace_state(e);
 }
 
 mc_status mc_buffer_info(const mc_engine* e, const char* name, size_t* offset, size_t* bytes) {
@@ -635,8 +761,10 @@ static mc_status embed(mc_engine* e, const float* latent_dev, const float* t_dev
 mc_status mc_embed(mc_engine* e, const float* latent_dev, const float* t_dev, double t_host,
                    const void* context_dev, mc_dtype ctx_dtype, int ctx_len, mc_stream stream_) {
   if (e) e->pair_drop();   // a phase call rewrites the embeds a kept front consists of
-  return embed(e, latent_dev, t_dev, t_host, context_dev, ctx_dtype, ctx_len, e ? e->buf<float>("x") : nullptr,
-               (hipStream_t)stream_);
+  const mc_status st = embed(e, latent_dev, t_dev, t_host, context_dev, ctx_dtype, ctx_len, e ? e->buf<float>("x") : nullptr,
+                             (hipStream_t)stream_);
+  if (e && st == MC_OK) e->phase_open = true;   // until mc_head: the grid stays (mc_set_geometry)
+  return st;
 }
 
 // ---- the one launch path of a block's Linears
@@ -1341,6 +1469,7 @@ static mc_status head(mc_engine* e, const float* x, int branch, mc_mode mode, hi
 mc_status mc_head(mc_engine* e, int branch, mc_mode mode, mc_stream stream) {
   if (!e) return fail(MC_ESTATE, "mc_embed must run first");
   e->pair_drop();   // every phase call ends a declared pair: between its forwards "x" is not a finished stream
+  e->phase_open = false;
   return head(e, e->buf<float>("x"), branch, mode, (hipStream_t)stream);
 }
 
@@ -1555,6 +1684,13 @@ mc_status mc_state_reset(mc_engine* e) {
 mc_status mc_op_rope_table(int F, int Hp, int Wp, int tok0, int n_tok, float* cs_host) {
   if (!cs_host || n_tok <= 0) return fail(MC_EINVAL, "bad argument");
   rope_table_host(F, Hp, Wp, tok0, n_tok, cs_host);
+  return MC_OK;
+}
+
+mc_status mc_op_rope_axes(int F, int Hp, int Wp, float* axes_host, size_t* n_floats) {
+  if (F <= 0 || Hp <= 0 || Wp <= 0 || (!axes_host && !n_floats)) return fail(MC_EINVAL, "bad argument");
+  if (n_floats) *n_floats = rope_axes_floats(F, Hp, Wp);
+  if (axes_host) rope_axes_host(F, Hp, Wp, axes_host);
   return MC_OK;
 }
 

@@ -173,6 +173,15 @@ hipError_t launch_colmean(const float* x, long ldx, int n_rows, int D, float* ou
 // rows [0, n_rows) of a bf16 [., D] block <- fp32 (optionally (cos,sin)-interleaving two [n, 128] tables, see mmdit)
 hipError_t launch_rope_table_from_cos_sin(const float* cosv, const float* sinv, long ld, int n_rows, float* cs,
                                           hipStream_t stream);
+// Wan's 3-D RoPE for head_dim 128 (upstream rope_params / rope_apply): 22 complex pairs turn with the frame index, 21 with the
+// height and 21 with the width index of a token
+constexpr int kRopePairsT = 22, kRopePairsHW = 21;
+// cs [n_rows][64][(cos,sin)] <- the per-axis pairs `axes` (F x 22 frame | Hp x 21 height | Wp x 21 width, mc_op_rope_axes):
+// row r < n_tok is global token tok0 + r = (f, h, w) of the grid and copies pair i from the axis it belongs to; rows >= n_tok
+// and tokens >= F Hp Wp get the identity (1, 0).  hipErrorInvalidValue for a null pointer, a non-positive size, tok0 < 0,
+// n_tok > n_rows, a grid of more than 2^31 - 1 tokens or a cs that is not 16-byte aligned.
+hipError_t launch_rope_expand(const float* axes, int F, int Hp, int Wp, int tok0, int n_tok, int n_rows, float* cs,
+                              hipStream_t stream);
 
 // latent fp32 [C,F,H,W] -> im2col bf16 tokens [L_pad, C*pt*ph*pw] for patch (1,2,2)
 hipError_t launch_patchify(const float* lat, int C, int F, int H, int W, int tok0, int n_tok, int n_rows,

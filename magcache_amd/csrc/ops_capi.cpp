@@ -11,7 +11,7 @@ using mc::gp;
 extern "C" {
 
 const char* mc_last_error(void) { return mc::last_error(); }
-const char* mc_version(void) { return "magcache_hip 0.6 (gfx950)"; }
+const char* mc_version(void) { return "magcache_hip 0.7 (gfx950)"; }
 
 // split-K scratch of the single-op entry point (mc_op_set_splitk_workspace): the engines carry their own in their workspace
 static float* g_op_splitk_ws = nullptr;
@@ -259,6 +259,15 @@ mc_status mc_op_lincomb(const float* const* xs_dev, const float* coef, int k, fl
   if (!xs_dev || !coef) return fail(MC_EINVAL, "null argument");
   hipError_t err = mc::launch_lincomb(xs_dev, coef, k, out_dev, n, (hipStream_t)s);
   if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "lincomb: 1..6 operands, non-empty output");
+  HIP_TRY(err);
+  return MC_OK;
+}
+
+mc_status mc_op_rope_expand(const float* axes_dev, int F, int Hp, int Wp, int tok0, int n_tok, int n_rows, float* cs_dev,
+                            mc_stream stream) {
+  hipError_t err = mc::launch_rope_expand(axes_dev, F, Hp, Wp, tok0, n_tok, n_rows, cs_dev, (hipStream_t)stream);
+  if (err == hipErrorInvalidValue)
+    return fail(MC_EINVAL, "rope_expand: non-null pointers, positive F / Hp / Wp / n_tok / n_rows, tok0 >= 0, n_tok <= n_rows, cs_dev 16-byte aligned");
   HIP_TRY(err);
   return MC_OK;
 }

@@ -123,15 +123,57 @@ class Engine:
         h = C.c_void_p()
         check(self.lib.mc_create_sized(C.byref(c), C.sizeof(c), C.byref(h)))
         self.h = h
-        nbytes = self.lib.mc_workspace_bytes(self.h)
-        self.workspace = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
-        off = (-self.workspace.data_ptr()) % 256
-        self.ws = self.workspace[off:off + nbytes]
-        # finite, deterministic scratch: padded rows feed MFMAs (0 * NaN would poison valid rows)
-        self.ws.zero_()
-        check(self.lib.mc_set_workspace(self.h, _ptr(self.ws), nbytes))
+        self._bind(self.lib.mc_workspace_bytes(self.h))
         self.tokens_per_rank = self.seq_len // sp_size
         self.head_stride = (4 * cfg["out_dim"] + 63) // 64 * 64    # row stride of "head_tokens" (fp32 elements)
+        self._tok_t = None
+
+    def _bind(self, nbytes):
+        """a zeroed workspace of `nbytes` (at least the current plan), bound with mc_set_workspace; the tensor it replaces is
+        let go after a device synchronise (forwards in flight may still use it)"""
+        workspace = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
+        off = (-workspace.data_ptr()) % 256
+        ws = workspace[off:off + nbytes]
+        # finite, deterministic scratch: padded rows feed MFMAs (0 * NaN would poison valid rows)
+        ws.zero_()
+        torch.cuda.synchronize(self.device)
+        check(self.lib.mc_set_workspace(self.h, _ptr(ws), nbytes))
+        self.workspace, self.ws = workspace, ws
+        self._tok_t = None            # the engine forgot them with everything else that belonged to the old binding
+
+    # ---- the latent grid as a property of the call
+    def geometry_bytes(self, latent_grid):
+        """workspace bytes the latent grid (F, H, W) would need (mc_geometry_bytes); the engine is not changed"""
+        n = C.c_size_t()
+        f, h, w = (int(v) for v in latent_grid)
+        check(self.lib.mc_geometry_bytes(self.h, f, h, w, C.byref(n)))
+        return n.value
+
+    def reserve(self, grids):
+        """Size the workspace once for every latent grid of the list, so that set_geometry among them allocates nothing.
+        The maximum of their needs; a workspace that has to grow is rebound, which forgets what set_geometry forgets."""
+        need = self.ws.numel()
+        for g in grids:
+            need = max(need, self.geometry_bytes(g))
+        if need > self.ws.numel():
+            self._bind(need)
+        return need
+
+    def set_geometry(self, latent_grid):
+        """Change the latent grid (F, H, W) between forwards (mc_set_geometry).  The weights stay; the workspace stays too
+        when the new plan fits it (see reserve), else a larger one is allocated.  The residual caches, the calibration
+        statistics, the cached text contexts, the CLIP and VACE contexts and per-token timesteps are forgotten, and views
+        handed out earlier by buffer() / residual() are invalid: they point into the old plan.  Not for a sharded engine."""
+        grid = tuple(int(v) for v in latent_grid)
+        if self.sharded:
+            raise ValueError("set_geometry: a sharded engine (sp_size > 1 or sp_phases) keeps the grid it was created with")
+        need = self.geometry_bytes(grid)
+        if need > self.ws.numel():
+            self._bind(need)
+        check(self.lib.mc_set_geometry(self.h, *grid))
+        self.grid = grid
+        self.seq_len = grid[0] * (grid[1] // 2) * (grid[2] // 2)
+        self.tokens_per_rank = self.seq_len // self.sp_size
         self._tok_t = None
 
     def __del__(self):

@@ -106,14 +106,16 @@ def _same_tensor(key, t):
 
 class WanModelHIP:
     """Wan2.1 DiT (T2V, or I2V when cfg has model_type='i2v' / clip_dim) whose forward runs on the HIP engine.
-    One latent grid per instance."""
+    One latent grid per instance, unless dynamic_geometry=True: then every call may bring its own (Engine.set_geometry)."""
 
     model_type = "t2v"
     patch_size = (1, 2, 2)
+    dynamic_geometry = False
 
     def __init__(self, cfg, latent_grid, device="cuda:0", calibration=True, engine=None, sp_rank=0, sp_size=1,
-                 sp_group=None, sp_phases=False):
+                 sp_group=None, sp_phases=False, dynamic_geometry=False):
         self.cfg = dict(cfg)
+        self.dynamic_geometry = dynamic_geometry
         for k in ("dim", "ffn_dim", "freq_dim", "text_len", "text_dim", "in_dim", "out_dim", "num_heads",
                   "num_layers"):
             setattr(self, k, cfg[k])
@@ -152,11 +154,44 @@ class WanModelHIP:
         self._ctx_keys[slot] = _tensor_key(ctx)
         self._ctx_lru = 1 - slot
 
+    def _geometry(self, x):
+        """dynamic_geometry: a call whose latent grid differs from the engine's switches the engine first and starts the
+        MagCache state of a new sample, as init_magcache leaves it (cnt = 0, empty accumulators and residual cache): the
+        schedule restarts, also when the sample at the old grid was not finished -- its cached residuals have the old
+        shape.  What the engine forgets with its old plan -- cached text contexts, the CLIP and VACE contexts, per-token
+        timesteps -- is uploaded again by the call."""
+        if not self.dynamic_geometry or len(x) != 1 or x[0].dim() != 4:
+            return
+        grid = tuple(int(v) for v in x[0].shape[1:])
+        if grid == self.latent_grid:
+            return
+        if getattr(self.engine, "sharded", self.engine.sp_size > 1):
+            raise ValueError(f"dynamic_geometry: a sharded engine keeps its latent grid {self.latent_grid} (got {grid})")
+        # Wan2.2: two experts share the MagCache state on their class, and the low-noise expert meets the new grid in the
+        # middle of the sample its sibling restarted: it follows without restarting
+        follows = int(getattr(self, "cnt", 0)) != 0 and getattr(type(self), "_sample_grid", None) == grid
+        self.check_token_timesteps()          # records of the old grid's forwards: "tok_t2" moves with the plan
+        self.engine.set_geometry(grid)
+        self.latent_grid = grid
+        self._ctx_keys, self._ctx_lru = [None, None], 0
+        self._clip_key = self._vace_key = self._tok_t_key = None
+        if follows:
+            return
+        type(self)._sample_grid = grid
+        fresh = dict(cnt=0, accumulated_err=[0.0, 0.0], accumulated_steps=[0, 0], accumulated_ratio=[1.0, 1.0],
+                     residual_cache=[None, None], norm_ratio=[], norm_std=[], cos_dis=[])
+        for k, v in fresh.items():            # where the state lives: on the instance once a call has advanced it, else the class
+            if k in self.__dict__:
+                setattr(self, k, v)
+            elif hasattr(type(self), k):
+                setattr(type(self), k, v)
+
     # -- input checks shared by all forwards (the reference's asserts :226-227, :242)
     def _check_inputs(self, x, context, seq_len, clip_fea, y):
         if self.model_type == "i2v":
             assert clip_fea is not None and y is not None
         assert len(x) == 1 and len(context) == 1, "the engine evaluates one sample per call, as the Wan sampler does"
+        self._geometry(x)
         u = x[0]
         c_in = u.shape[0] + (y[0].shape[0] if y is not None else 0)   # x ++ y along channels (:233-234)
         assert tuple(u.shape[1:]) == self.latent_grid and c_in == self.in_dim, \
