@@ -14,7 +14,7 @@
 using mc::align_up;
 using mc::bf16_t;
 using mc::fail;
-using mc::gp;
+using mc::Keys;
 using mc::Linear;
 using mc::RowRange;
 using mc::whole;
@@ -26,6 +26,7 @@ struct Layer {
   float *nq, *nk, *cnq, *cnk, *n3w, *n3b, *mod;
   Linear ckv_img;  // I2V: [k_img ; v_img]
   float* cnk_img = nullptr;
+  int index = 0;   // flat: main layers 0 .. NL-1, then the VACE blocks (the order of "emod" and "ckv_cache")
 };
 
 }  // namespace
@@ -37,15 +38,13 @@ struct mc_engine {
   int d, ffn, H, NL, L, Lr, Lp, P, rank, tok0, Kp;  // Kp = in_dim*4 padded to 64
   int ctx_rows;                                     // text_len padded to 64
   std::vector<Layer> layers;
-  // non-block weights
-  bf16_t *w_patch, *w_text0, *w_text1;
-  float *b_patch, *b_text0, *b_text1;
+  // non-block weights: the Linears of the embeds; the time MLP and the head are fp32 (gemv_f32 / head_linear)
+  Linear patch, text0, text1;
   float *w_time0, *b_time0, *w_time1, *b_time1, *w_tproj, *b_tproj;
   float *w_head, *b_head, *head_mod;
   // I2V img_emb = MLPProj(clip_dim -> dim): LayerNorm, Linear, GELU, Linear, LayerNorm
-  bf16_t *w_img1 = nullptr, *w_img3 = nullptr;
-  float *ln_img0_w = nullptr, *ln_img0_b = nullptr, *b_img1 = nullptr, *b_img3 = nullptr, *ln_img4_w = nullptr,
-        *ln_img4_b = nullptr;
+  Linear img1, img3;
+  float *ln_img0_w = nullptr, *ln_img0_b = nullptr, *ln_img4_w = nullptr, *ln_img4_b = nullptr;
   int img_rows = 0;     // 257 image tokens padded to a multiple of 64
   bool have_clip = false;
   // sequence parallel (P > 1): the gathered K|V of a layer arrive in sp_chunks rounds (mc_sp_set_chunks); the self-attention
@@ -76,10 +75,9 @@ struct mc_engine {
   // VACE (upstream wan/modules/vace_model.py VaceWanModel): n_vace extra blocks on a control stream c; block i feeds
   // main layer i * vace_stride through after_proj ("hint")
   std::vector<Layer> vlayers;
-  std::vector<bf16_t*> w_after;
-  std::vector<float*> b_after;
-  bf16_t *w_vpatch = nullptr, *w_before = nullptr;
-  float *b_vpatch = nullptr, *b_before = nullptr, *vscale = nullptr;
+  Linear vpatch, before;
+  std::vector<Linear> after;
+  float* vscale = nullptr;
   int NV = 0, Kvp = 0;
   bool have_vace = false;
   float* cs_table = nullptr;  // rope (cos,sin) [Lp][64][2]: expanded on the device from the per-axis values in rope_axes
@@ -113,6 +111,9 @@ struct mc_engine {
     static const char* names[3] = {"residual0", "residual1", "residual2"};
     return buf<float>(names[idx]);
   }
+  // main or VACE layer by flat index, and the 6 modulation vectors of a layer (set 0; second_set() for the other)
+  const Layer& layer(int flat) const { return flat < NL ? layers[flat] : vlayers[flat - NL]; }
+  const float* emod(const Layer& l) const { return buf<float>("emod") + (size_t)l.index * 6 * d; }
 };
 
 namespace {
@@ -120,14 +121,14 @@ namespace {
 // Measurement hook (mc_profile_enable): one hipEvent pair on the launch stream around the launches of the enclosing
 // scope, tagged with its class.  Level 1 brackets the self-attention launches only (what bench.py's timed region carries),
 // level 2 every class.  The pair is reserved at construction, so scopes may nest.  A failed record is not an error of
-// the forward: the pair is dropped from the log.
+// the forward: the pair is dropped from the log.  A negative class logs nothing.
 struct Prof {
   mc_engine* e;
   hipStream_t s;
   size_t idx = 0;
   bool on = false;
   Prof(mc_engine* e_, int cls, hipStream_t s_) : e(e_), s(s_) {
-    if (!e->profile || (e->profile < 2 && cls != MC_PROF_ATTN_SELF) || e->prof_n + 2 > e->prof_ev.size()) return;
+    if (cls < 0 || !e->profile || (e->profile < 2 && cls != MC_PROF_ATTN_SELF) || e->prof_n + 2 > e->prof_ev.size()) return;
     idx = e->prof_n;
     if (hipEventRecord(e->prof_ev[idx], s) != hipSuccess) return;
     e->prof_cls[idx / 2] = (uint8_t)cls;
@@ -340,6 +341,91 @@ mc_status check_ready(const mc_engine* e) {
   return mc::check_ready(e->work, e->weights, "mc_set_workspace");
 }
 
+// ---- the one launch path of the engine's Linears
+// The activation rows [M, k_in] a Linear reads.  A bf16 Linear reads `rows`.  An fp8 Linear reads e4m3 rows + scales:
+// it quantises `rows` into "aq" (+ "a_scale" | "a_mx") first, unless they are `quantised` already -- there by a fused producer
+// or an earlier Linear over the same rows, or, q / mx given, in the caller's buffers (FFN-1's GELU epilogue writes FFN-2's).
+struct ActSrc {
+  const bf16_t* rows = nullptr; long ld = 0;
+  bool quantised = false;
+  uint8_t *q = nullptr, *mx = nullptr;
+};
+
+// y[:, out] = epilogue(a W[out]^T + b[out]) over M rows: p carries the outputs, gates, capture and split-K operands of the
+// epilogue; the operands, the shape and every pointer advance of a row range come from `l`.
+// fp8 (block Linears only, M = Lp: "aq" and its scales are planned for that): per-token activation scales x per-output-channel
+// weight scales (launch_gemm_fp8), or MX block scales on both sides -- activations per (token, 32 k), weights per
+// (channel, 32 k) -- multiplied inside the matrix core (launch_gemm_mxfp8).
+mc_status linear(mc_engine* e, const Linear& l, RowRange out, int M, ActSrc a, mc::GemmParams p, int epi, hipStream_t s) {
+  const int K = l.k_in;
+  if (!l.q) {
+    HIP_TRY(mc::launch_linear_bf16(l, out, a.rows, a.ld, M, p, epi, s));
+    return MC_OK;
+  }
+  const int Lp = e->Lp;
+  if (M != Lp) return fail(MC_EINVAL, "an fp8 Linear runs over the %d rows of a block, not %d", Lp, M);
+  p.M = Lp; p.N = out.count; p.K = K; p.bias = l.b + out.first;
+  uint8_t* aq = a.q ? a.q : e->buf<uint8_t>("aq");
+  p.A = (const bf16_t*)aq; p.lda = K; p.W = (const bf16_t*)(l.q + (size_t)out.first * K); p.ldw = K;
+  if (l.mx) {
+    uint8_t* am = a.mx ? a.mx : e->buf<uint8_t>("a_mx");
+    if (!a.quantised) HIP_TRY(mc::launch_quantize_rows_mx(a.rows, nullptr, a.ld, Lp, K, aq, K, am, (long)Lp, s));
+    p.a_mx = am; p.mx_rows_a = (long)Lp; p.w_mx = l.mx + out.first; p.mx_rows_w = l.n_out;   // block-major: [k / 32][n_out]
+    HIP_TRY(mc::launch_gemm_mxfp8(p, epi, s));
+    return MC_OK;
+  }
+  float* as = e->buf<float>("a_scale");
+  if (!a.quantised) HIP_TRY(mc::launch_quantize_rows_fp8(a.rows, nullptr, a.ld, Lp, K, aq, K, as, s));
+  p.a_scale = as; p.w_scale = l.q_scale + out.first;
+  HIP_TRY(mc::launch_gemm_fp8(p, epi, s));
+  return MC_OK;
+}
+// the common case: every output channel into a bf16 matrix C (ld = n_out)
+mc_status linear_bf16_out(mc_engine* e, const Linear& l, int M, ActSrc a, bf16_t* C, int epi, hipStream_t s) {
+  mc::GemmParams p = {};
+  p.Cb = C; p.ldc = l.n_out;
+  return linear(e, l, whole(l), M, a, p, epi, s);
+}
+
+// ---- the key sets of the engine's attention launches (mc::Keys) and the one launch over them
+Keys kv_pairs(const bf16_t* kv, int d, int rows, int valid) { return {kv, kv + d, 2L * d, 0, rows, valid, 1, 0}; }   // rows of [k | v]
+Keys qkv_keys(const mc_engine* e) {   // one device: the k and v columns of "qkv"
+  const bf16_t* k = e->buf<bf16_t>("qkv") + e->d;
+  return {k, k + e->d, 3L * e->d, 0, e->Lp, e->Lr, 1, 0};
+}
+Keys local_keys(const mc_engine* e) { return kv_pairs(e->buf<bf16_t>("kv_local"), e->d, e->Lp, e->Lr); }   // this rank's shard
+// sequence-parallel geometry of the gather rounds (mc_sp_set_chunks)
+int sp_chunk_rows(const mc_engine* e) { return e->Lp / e->sp_chunks; }
+int sp_round_valid(const mc_engine* e, int c) {   // valid keys at the start of every shard's chunk c
+  const int lc = sp_chunk_rows(e);
+  return std::max(0, std::min(lc, e->Lr - c * lc));
+}
+int sp_rounds(const mc_engine* e) {               // rounds that carry at least one valid key
+  const int lc = sp_chunk_rows(e);
+  return (e->Lr + lc - 1) / lc;
+}
+// round < 0: this rank's own shard; round c: "kv_gather"[c] = [P][Lp / C][2d], with or without this rank's shard
+Keys sp_keys(const mc_engine* e, int round, bool skip_own) {
+  if (round < 0) return local_keys(e);
+  const int lc = sp_chunk_rows(e), d = e->d;
+  Keys k = kv_pairs(e->buf<bf16_t>("kv_gather") + (size_t)round * e->P * lc * 2 * d, d, lc, sp_round_valid(e, round));
+  k.stride = (long)lc * 2 * d; k.n_shards = e->P; k.skip_shard_p1 = skip_own ? e->rank + 1 : 0;
+  return k;
+}
+// the Lp query rows of Q over one key set -> O [Lp][d]
+mc_status attend(const mc_engine* e, const bf16_t* Q, long ldq, bf16_t* O, const Keys& keys, const float* lse_in, float* lse_out,
+                 hipStream_t s) {
+  HIP_TRY(mc::launch_attention_keys(Q, ldq, O, e->d, e->Lp, e->H, keys, lse_in, lse_out, s));
+  return MC_OK;
+}
+// whose self-attention chain is open and how far it got (sequence parallel)
+void attn_chain_set(mc_engine* e, int layer, int launches, bool local_done, int rounds_done) {
+  e->attn_layer = layer; e->attn_launches = launches; e->attn_local_done = local_done; e->attn_rounds_done = rounds_done;
+}
+void attn_chain_open(mc_engine* e, int layer) {
+  if (e->attn_layer != layer) attn_chain_set(e, layer, 0, false, 0);
+}
+
 }  // namespace
 
 namespace mc {
@@ -409,7 +495,6 @@ mc_status mc_create(const mc_config* cfg, mc_engine** out) {
   const size_t d = e->d, ffn = e->ffn;
   mc::WeightStore& W = e->weights;
 
-#define ALLOC(ptr, n) MC_TRY(W.alloc(&(ptr), (n)))
   // fp8_linear only decides which Linears keep an e4m3 copy and of which kind: 1 = QKV, FFN-1, FFN-2 with per-row scales,
   // 2 = the same three with MX block scales, 3 = MX, the d x d Linears (self-attention O, cross-attention Q and O) too
   const mc::Quant q_big = c.fp8_linear >= 2 ? mc::QUANT_MX : c.fp8_linear == 1 ? mc::QUANT_ROW : mc::QUANT_NONE;
@@ -420,6 +505,7 @@ mc_status mc_create(const mc_config* cfg, mc_engine** out) {
   for (int i = 0; i < e->NL + e->NV; ++i) {
     const bool is_vace = i >= e->NL;
     Layer& l = is_vace ? e->vlayers[i - e->NL] : e->layers[i];
+    l.index = i;
     const std::string p = (is_vace ? "vace_blocks." + std::to_string(i - e->NL) : "blocks." + std::to_string(i)) + ".";
     MC_TRY(W.add_linear(l.qkv, p + "self_attn.", {{"q", d}, {"k", d}, {"v", d}}, d, q_big));
     MC_TRY(W.add_linear(l.o, p + "self_attn.", {{"o", d}}, d, q_dd));
@@ -428,81 +514,63 @@ mc_status mc_create(const mc_config* cfg, mc_engine** out) {
     MC_TRY(W.add_linear(l.co, p + "cross_attn.", {{"o", d}}, d, q_dd));
     MC_TRY(W.add_linear(l.ffn1, p + "ffn.", {{"0", ffn}}, d, q_big));
     MC_TRY(W.add_linear(l.ffn2, p + "ffn.", {{"2", d}}, ffn, q_big));
-    ALLOC(l.nq, d); ALLOC(l.nk, d); ALLOC(l.n3w, d); ALLOC(l.n3b, d); ALLOC(l.cnq, d); ALLOC(l.cnk, d); ALLOC(l.mod, 6 * d);
-    W.add(p + "self_attn.norm_q.weight", l.nq, MC_F32, d);
-    W.add(p + "self_attn.norm_k.weight", l.nk, MC_F32, d);
-    W.add(p + "norm3.weight", l.n3w, MC_F32, d);
-    W.add(p + "norm3.bias", l.n3b, MC_F32, d);
-    W.add(p + "cross_attn.norm_q.weight", l.cnq, MC_F32, d);
-    W.add(p + "cross_attn.norm_k.weight", l.cnk, MC_F32, d);
-    W.add(p + "modulation", l.mod, MC_F32, 6 * d);
+    MC_TRY(W.add_f32(l.nq, p + "self_attn.norm_q.weight", d));
+    MC_TRY(W.add_f32(l.nk, p + "self_attn.norm_k.weight", d));
+    MC_TRY(W.add_f32(l.n3w, p + "norm3.weight", d));
+    MC_TRY(W.add_f32(l.n3b, p + "norm3.bias", d));
+    MC_TRY(W.add_f32(l.cnq, p + "cross_attn.norm_q.weight", d));
+    MC_TRY(W.add_f32(l.cnk, p + "cross_attn.norm_k.weight", d));
+    MC_TRY(W.add_f32(l.mod, p + "modulation", 6 * d));
     if (c.clip_dim > 0) {
       MC_TRY(W.add_linear(l.ckv_img, p + "cross_attn.", {{"k_img", d}, {"v_img", d}}, d));
-      ALLOC(l.cnk_img, d);
-      W.add(p + "cross_attn.norm_k_img.weight", l.cnk_img, MC_F32, d);
+      MC_TRY(W.add_f32(l.cnk_img, p + "cross_attn.norm_k_img.weight", d));
     }
   }
   if (e->NV > 0) {
     e->Kvp = (int)align_up((size_t)c.vace_in_dim * 4, 64);
     const size_t kv = (size_t)c.vace_in_dim * 4;
     if (kv != (size_t)e->Kvp) { return fail(MC_EINVAL, "vace_in_dim*4 must be a multiple of 64"); }
-    ALLOC(e->w_vpatch, d * kv); ALLOC(e->b_vpatch, d); ALLOC(e->w_before, d * d); ALLOC(e->b_before, d);
-    ALLOC(e->vscale, d);
-    W.add("vace_patch_embedding.weight", e->w_vpatch, MC_BF16, d * kv);
-    W.add("vace_patch_embedding.bias", e->b_vpatch, MC_F32, d);
-    W.add("vace_blocks.0.before_proj.weight", e->w_before, MC_BF16, d * d);
-    W.add("vace_blocks.0.before_proj.bias", e->b_before, MC_F32, d);
-    e->w_after.resize(e->NV); e->b_after.resize(e->NV);
-    for (int i = 0; i < e->NV; ++i) {
-      ALLOC(e->w_after[i], d * d); ALLOC(e->b_after[i], d);
-      const std::string p = "vace_blocks." + std::to_string(i) + ".after_proj.";
-      W.add(p + "weight", e->w_after[i], MC_BF16, d * d);
-      W.add(p + "bias", e->b_after[i], MC_F32, d);
-    }
+    MC_TRY(W.add_linear(e->vpatch, "", {{"vace_patch_embedding", d}}, kv));
+    MC_TRY(W.add_linear(e->before, "vace_blocks.0.", {{"before_proj", d}}, d));
+    MC_TRY(W.alloc(&e->vscale, d));
+    e->after.resize(e->NV);
+    for (int i = 0; i < e->NV; ++i)
+      MC_TRY(W.add_linear(e->after[i], "vace_blocks." + std::to_string(i) + ".", {{"after_proj", d}}, d));
   }
   if (c.clip_dim > 0) {
     const size_t cd = c.clip_dim;
     e->img_rows = (int)align_up(257, 64);
-    ALLOC(e->ln_img0_w, cd); ALLOC(e->ln_img0_b, cd); ALLOC(e->w_img1, cd * cd); ALLOC(e->b_img1, cd);
-    ALLOC(e->w_img3, d * cd); ALLOC(e->b_img3, d); ALLOC(e->ln_img4_w, d); ALLOC(e->ln_img4_b, d);
-    W.add("img_emb.proj.0.weight", e->ln_img0_w, MC_F32, cd);
-    W.add("img_emb.proj.0.bias", e->ln_img0_b, MC_F32, cd);
-    W.add("img_emb.proj.1.weight", e->w_img1, MC_BF16, cd * cd);
-    W.add("img_emb.proj.1.bias", e->b_img1, MC_F32, cd);
-    W.add("img_emb.proj.3.weight", e->w_img3, MC_BF16, d * cd);
-    W.add("img_emb.proj.3.bias", e->b_img3, MC_F32, d);
-    W.add("img_emb.proj.4.weight", e->ln_img4_w, MC_F32, d);
-    W.add("img_emb.proj.4.bias", e->ln_img4_b, MC_F32, d);
+    MC_TRY(W.add_f32(e->ln_img0_w, "img_emb.proj.0.weight", cd));
+    MC_TRY(W.add_f32(e->ln_img0_b, "img_emb.proj.0.bias", cd));
+    MC_TRY(W.add_linear(e->img1, "img_emb.proj.", {{"1", cd}}, cd));
+    MC_TRY(W.add_linear(e->img3, "img_emb.proj.", {{"3", d}}, cd));
+    MC_TRY(W.add_f32(e->ln_img4_w, "img_emb.proj.4.weight", d));
+    MC_TRY(W.add_f32(e->ln_img4_b, "img_emb.proj.4.bias", d));
   }
+  // patch weight [d, in_dim, 1, 2, 2] is stored [d, Kp] (Kp = in_dim*4 padded to a GEMM K step; the padding stays zero)
   const size_t kin = (size_t)c.in_dim * 4;
-  ALLOC(e->w_patch, d * e->Kp); ALLOC(e->b_patch, d);
-  HIP_TRY(hipMemset(e->w_patch, 0, d * e->Kp * sizeof(bf16_t)));
-  ALLOC(e->w_text0, d * c.text_dim); ALLOC(e->b_text0, d); ALLOC(e->w_text1, d * d); ALLOC(e->b_text1, d);
-  ALLOC(e->w_time0, d * c.freq_dim); ALLOC(e->b_time0, d); ALLOC(e->w_time1, d * d); ALLOC(e->b_time1, d);
-  ALLOC(e->w_tproj, 6 * d * d); ALLOC(e->b_tproj, 6 * d);
-  ALLOC(e->w_head, (size_t)c.out_dim * 4 * d); ALLOC(e->b_head, (size_t)c.out_dim * 4); ALLOC(e->head_mod, 2 * d);
-  // patch weight [d, in_dim, 1, 2, 2] is stored [d, Kp] (Kp = in_dim*4 padded to a GEMM K step)
-  mc::Slot& patch = W.add("patch_embedding.weight", e->w_patch, MC_BF16, d * kin);
-  if (kin != (size_t)e->Kp) patch.pad = {d, kin, (size_t)e->Kp};
-  W.add("patch_embedding.bias", e->b_patch, MC_F32, d);
-  W.add("text_embedding.0.weight", e->w_text0, MC_BF16, d * c.text_dim);
-  W.add("text_embedding.0.bias", e->b_text0, MC_F32, d);
-  W.add("text_embedding.2.weight", e->w_text1, MC_BF16, d * d);
-  W.add("text_embedding.2.bias", e->b_text1, MC_F32, d);
-  W.add("time_embedding.0.weight", e->w_time0, MC_F32, d * c.freq_dim);
-  W.add("time_embedding.0.bias", e->b_time0, MC_F32, d);
-  W.add("time_embedding.2.weight", e->w_time1, MC_F32, d * d);
-  W.add("time_embedding.2.bias", e->b_time1, MC_F32, d);
-  W.add("time_projection.1.weight", e->w_tproj, MC_F32, 6 * d * d);
-  W.add("time_projection.1.bias", e->b_tproj, MC_F32, 6 * d);
-  W.add("head.head.weight", e->w_head, MC_F32, (size_t)c.out_dim * 4 * d);
-  W.add("head.head.bias", e->b_head, MC_F32, (size_t)c.out_dim * 4);
-  W.add("head.modulation", e->head_mod, MC_F32, 2 * d);
+  MC_TRY(W.alloc_linear(e->patch, d, e->Kp));
+  HIP_TRY(hipMemset(e->patch.w, 0, d * e->Kp * sizeof(bf16_t)));
+  mc::Slot& w_patch = W.add_parts(e->patch, "", {{"patch_embedding", d}});
+  if (kin != (size_t)e->Kp) {
+    w_patch.numel = d * kin;
+    w_patch.pad = {d, kin, (size_t)e->Kp};
+  }
+  MC_TRY(W.add_linear(e->text0, "text_embedding.", {{"0", d}}, c.text_dim));
+  MC_TRY(W.add_linear(e->text1, "text_embedding.", {{"2", d}}, d));
+  MC_TRY(W.add_f32(e->w_time0, "time_embedding.0.weight", d * c.freq_dim));
+  MC_TRY(W.add_f32(e->b_time0, "time_embedding.0.bias", d));
+  MC_TRY(W.add_f32(e->w_time1, "time_embedding.2.weight", d * d));
+  MC_TRY(W.add_f32(e->b_time1, "time_embedding.2.bias", d));
+  MC_TRY(W.add_f32(e->w_tproj, "time_projection.1.weight", 6 * d * d));
+  MC_TRY(W.add_f32(e->b_tproj, "time_projection.1.bias", 6 * d));
+  MC_TRY(W.add_f32(e->w_head, "head.head.weight", (size_t)c.out_dim * 4 * d));
+  MC_TRY(W.add_f32(e->b_head, "head.head.bias", (size_t)c.out_dim * 4));
+  MC_TRY(W.add_f32(e->head_mod, "head.modulation", 2 * d));
 
   // RoPE table for this rank's rows: the two steps mc_set_geometry takes
   MC_TRY(rope_reserve(e, e->Lp, rope_axes_floats(c.latent_f, c.latent_h / 2, c.latent_w / 2)));
   MC_TRY(rope_build(e));
-#undef ALLOC
 
   // ---- workspace plan
   e->splitk_bytes = splitk_need(e, e->Lp);
@@ -589,8 +657,7 @@ int mc_weights_missing(const mc_engine* e, char* buf, size_t buflen) { return e 
 // Linear, LayerNorm).  257 tokens; rows up to img_rows are padding (finite, masked in the attention).
 mc_status mc_set_clip_fea(mc_engine* e, const void* clip_dev, mc_dtype dtype, int n_tokens, mc_stream stream_) {
   hipStream_t s = (hipStream_t)stream_;
-  mc_status st = check_ready(e);
-  if (st != MC_OK) return st;
+  MC_TRY(check_ready(e));
   e->pair_drop();
   const mc_config& c = e->cfg;
   if (c.clip_dim <= 0) return fail(MC_EINVAL, "engine was created without clip_dim (t2v model)");
@@ -605,14 +672,9 @@ mc_status mc_set_clip_fea(mc_engine* e, const void* clip_dev, mc_dtype dtype, in
   }
   bf16_t* n0 = e->buf<bf16_t>("clip_n");
   HIP_TRY(mc::launch_ln_modulate(in, cd, nullptr, 0, e->ln_img0_w, e->ln_img0_b, 1, 1e-5f, n0, cd, nullptr, 0, ir, cd, s));
-  {
-    mc::GemmParams p = gp(n0, cd, e->w_img1, cd, e->b_img1, ir, cd, cd);
-    p.Cb = e->buf<bf16_t>("clip_h"); p.ldc = cd;
-    HIP_TRY(mc::launch_gemm_bf16(p, mc::EPI_GELU_ERF_BF16, s));
-    mc::GemmParams q = gp(e->buf<bf16_t>("clip_h"), cd, e->w_img3, cd, e->b_img3, ir, d, cd);
-    q.Cb = e->buf<bf16_t>("clip_h2"); q.ldc = d;   // autocast: the Linear's output is bf16 before the LayerNorm
-    HIP_TRY(mc::launch_gemm_bf16(q, mc::EPI_BF16, s));
-  }
+  MC_TRY(linear_bf16_out(e, e->img1, ir, ActSrc{n0, cd}, e->buf<bf16_t>("clip_h"), mc::EPI_GELU_ERF_BF16, s));
+  // autocast: the Linear's output is bf16 before the LayerNorm
+  MC_TRY(linear_bf16_out(e, e->img3, ir, ActSrc{e->buf<bf16_t>("clip_h"), cd}, e->buf<bf16_t>("clip_h2"), mc::EPI_BF16, s));
   // LayerNorm of the bf16 rows: the kernel's (fp32 x) + (bf16 x0) form with x = 0
   HIP_TRY(hipMemsetAsync(e->buf<float>("clip_o"), 0, (size_t)ir * d * 4, s));
   HIP_TRY(mc::launch_ln_modulate(e->buf<float>("clip_o"), d, e->buf<bf16_t>("clip_h2"), d, e->ln_img4_w,
@@ -625,8 +687,7 @@ mc_status mc_set_clip_fea(mc_engine* e, const void* clip_dev, mc_dtype dtype, in
 // video, and the hint scale (vace_context_scale, :546).
 mc_status mc_set_vace_context(mc_engine* e, const float* vace_dev, float context_scale, mc_stream stream_) {
   hipStream_t s = (hipStream_t)stream_;
-  mc_status st = check_ready(e);
-  if (st != MC_OK) return st;
+  MC_TRY(check_ready(e));
   e->pair_drop();
   if (e->NV <= 0) return fail(MC_EINVAL, "engine was created without VACE blocks");
   const mc_config& c = e->cfg;
@@ -635,11 +696,11 @@ mc_status mc_set_vace_context(mc_engine* e, const float* vace_dev, float context
     bf16_t* vt = e->buf<bf16_t>("vtokens");
     HIP_TRY(mc::launch_patchify(vace_dev, c.vace_in_dim, c.latent_f, c.latent_h, c.latent_w, e->tok0, e->Lr, e->Lp, vt,
                                 e->Kvp, s));
-    mc::GemmParams p = gp(vt, e->Kvp, e->w_vpatch, e->Kvp, e->b_vpatch, e->Lp, d, e->Kvp);
+    mc::GemmParams p = {};
     p.X = e->buf<float>("xc"); p.ldx = d;
     p.X0out = e->buf<bf16_t>("c0"); p.ldx0out = d;
     p.m_valid = e->Lr;
-    HIP_TRY(mc::launch_gemm_bf16(p, mc::EPI_EMBED, s));
+    MC_TRY(linear(e, e->vpatch, whole(e->vpatch), e->Lp, ActSrc{vt, e->Kvp}, p, mc::EPI_EMBED, s));
     e->have_vace = true;
   } else if (!e->have_vace) {
     return fail(MC_EINVAL, "null vace_context and none set before");
@@ -656,7 +717,6 @@ mc_status mc_set_vace_context(mc_engine* e, const float* vace_dev, float context
 static mc_status embed_context(mc_engine* e, const void* context_dev, mc_dtype ctx_dtype, int ctx_len, bf16_t* dst,
                                hipStream_t s) {
   const mc_config& c = e->cfg;
-  const int d = e->d;
   if (ctx_len <= 0 || ctx_len > c.text_len)
     return fail(MC_EINVAL, "context length %d exceeds text_len %d", ctx_len, c.text_len);
   bf16_t* ctx_in = e->buf<bf16_t>("ctx_in");
@@ -667,21 +727,15 @@ static mc_status embed_context(mc_engine* e, const void* context_dev, mc_dtype c
     HIP_TRY(hipMemsetAsync(ctx_in, 0, (size_t)e->ctx_rows * c.text_dim * 2, s));
     HIP_TRY(hipMemcpyAsync(ctx_in, context_dev, (size_t)ctx_len * c.text_dim * 2, hipMemcpyDeviceToDevice, s));
   }
-  mc::GemmParams p = gp(ctx_in, c.text_dim, e->w_text0, c.text_dim, e->b_text0, e->ctx_rows, d, c.text_dim);
-  p.Cb = e->buf<bf16_t>("ctx_h"); p.ldc = d;
-  HIP_TRY(mc::launch_gemm_bf16(p, mc::EPI_GELU_BF16, s));
-  mc::GemmParams q = gp(e->buf<bf16_t>("ctx_h"), d, e->w_text1, d, e->b_text1, e->ctx_rows, d, d);
-  q.Cb = dst; q.ldc = d;
-  HIP_TRY(mc::launch_gemm_bf16(q, mc::EPI_BF16, s));
-  return MC_OK;
+  bf16_t* ctx_h = e->buf<bf16_t>("ctx_h");
+  MC_TRY(linear_bf16_out(e, e->text0, e->ctx_rows, ActSrc{ctx_in, c.text_dim}, ctx_h, mc::EPI_GELU_BF16, s));
+  return linear_bf16_out(e, e->text1, e->ctx_rows, ActSrc{ctx_h, e->d}, dst, mc::EPI_BF16, s);
 }
 
 // the cross-attention K|V of one block for a context: k = norm_k(k(ctx)), v = v(ctx)  (upstream WanT2VCrossAttention)
 static mc_status context_kv(mc_engine* e, const Layer& l, const bf16_t* ctx, bf16_t* ckv, hipStream_t s) {
   const int d = e->d;
-  mc::GemmParams q = gp(ctx, d, l.ckv.w, d, l.ckv.b, e->ctx_rows, 2 * d, d);
-  q.Cb = ckv; q.ldc = 2 * d;
-  HIP_TRY(mc::launch_gemm_bf16(q, mc::EPI_BF16, s));
+  MC_TRY(linear_bf16_out(e, l.ckv, e->ctx_rows, ActSrc{ctx, d}, ckv, mc::EPI_BF16, s));
   HIP_TRY(mc::launch_rmsnorm_rope(ckv, 2 * d, l.cnk, e->cfg.eps, nullptr, 0, e->ctx_rows, d, s));
   return MC_OK;
 }
@@ -699,11 +753,11 @@ static mc_status embed_latent_time(mc_engine* e, const float* latent_dev, const 
   HIP_TRY(mc::launch_patchify(latent_dev, c.in_dim, c.latent_f, c.latent_h, c.latent_w, e->tok0, e->Lr, e->Lp,
                               tokens, e->Kp, s));
   {
-    mc::GemmParams p = gp(tokens, e->Kp, e->w_patch, e->Kp, e->b_patch, e->Lp, d, e->Kp);
+    mc::GemmParams p = {};
     p.X = x; p.ldx = d;
     p.X0out = e->buf<bf16_t>("x0"); p.ldx0out = d;
     p.m_valid = e->Lr;
-    HIP_TRY(mc::launch_gemm_bf16(p, mc::EPI_EMBED, s));
+    MC_TRY(linear(e, e->patch, whole(e->patch), e->Lp, ActSrc{tokens, e->Kp}, p, mc::EPI_EMBED, s));
   }
   // e = time_embedding(sinusoidal(t)) ; e0 = time_projection(e)   (fp32, :249-253).  With per-token timesteps
   // (Wan2.2, MagCache4Wan2.2/magcache_generate.py:261-270: e [B, seq_len, d], e0 [B, seq_len, 6, d]) the same chain
@@ -726,8 +780,7 @@ static mc_status embed_latent_time(mc_engine* e, const float* latent_dev, const 
     // per-layer modulation vectors (block.modulation + e0) and the head's (head.modulation + e)
     float* emod = e->buf<float>("emod") + set * emod_set;
     for (int l = 0; l < e->NL + e->NV; ++l)
-      HIP_TRY(mc::launch_add_bcast(e0, 6 * d, (l < e->NL ? e->layers[l] : e->vlayers[l - e->NL]).mod,
-                                   emod + (size_t)l * 6 * d, 6 * d, s));
+      HIP_TRY(mc::launch_add_bcast(e0, 6 * d, e->layer(l).mod, emod + (size_t)l * 6 * d, 6 * d, s));
     HIP_TRY(mc::launch_add_bcast(ev, d, e->head_mod, e->buf<float>("ehead") + set * 2 * d, 2 * d, s));
   }
   return MC_OK;
@@ -746,8 +799,7 @@ static mc_status embed_text(mc_engine* e, const void* context_dev, mc_dtype ctx_
 
 static mc_status embed(mc_engine* e, const float* latent_dev, const float* t_dev, double t_host, const void* context_dev,
                        mc_dtype ctx_dtype, int ctx_len, float* x, hipStream_t s) {
-  mc_status st = check_ready(e);
-  if (st != MC_OK) return st;
+  MC_TRY(check_ready(e));
   if (!latent_dev) return fail(MC_EINVAL, "null input");
   if (e->cfg.clip_dim > 0 && !e->have_clip)
     return fail(MC_ESTATE, "i2v model: mc_set_clip_fea must run before the forward (reference assert :226-227)");
@@ -765,43 +817,6 @@ mc_status mc_embed(mc_engine* e, const float* latent_dev, const float* t_dev, do
                              (hipStream_t)stream_);
   if (e && st == MC_OK) e->phase_open = true;   // until mc_head: the grid stays (mc_set_geometry)
   return st;
-}
-
-// ---- the one launch path of a block's Linears
-// The activation rows [Lp, k_in] a Linear reads.  A bf16 Linear reads `rows`.  An fp8 Linear reads e4m3 rows + scales:
-// it quantises `rows` into "aq" (+ "a_scale" | "a_mx") first, unless they are `quantised` already -- there by a fused producer
-// or an earlier Linear over the same rows, or, q / mx given, in the caller's buffers (FFN-1's GELU epilogue writes FFN-2's).
-struct ActSrc {
-  const bf16_t* rows = nullptr; long ld = 0;
-  bool quantised = false;
-  uint8_t *q = nullptr, *mx = nullptr;
-};
-
-// y[:, out] = epilogue(a W[out]^T + b[out]): p carries the outputs, gates, capture and split-K operands of the epilogue; the
-// operands, the shape and every pointer advance of a row range come from `l`.
-// fp8: per-token activation scales x per-output-channel weight scales (launch_gemm_fp8), or MX block scales on both sides --
-// activations per (token, 32 k), weights per (channel, 32 k) -- multiplied inside the matrix core (launch_gemm_mxfp8).
-static mc_status linear(mc_engine* e, const Linear& l, RowRange out, ActSrc a, mc::GemmParams p, int epi, hipStream_t s) {
-  const int Lp = e->Lp, K = l.k_in;
-  if (!l.q) {
-    HIP_TRY(mc::launch_linear_bf16(l, out, a.rows, a.ld, Lp, p, epi, s));
-    return MC_OK;
-  }
-  p.M = Lp; p.N = out.count; p.K = K; p.bias = l.b + out.first;
-  uint8_t* aq = a.q ? a.q : e->buf<uint8_t>("aq");
-  p.A = (const bf16_t*)aq; p.lda = K; p.W = (const bf16_t*)(l.q + (size_t)out.first * K); p.ldw = K;
-  if (l.mx) {
-    uint8_t* am = a.mx ? a.mx : e->buf<uint8_t>("a_mx");
-    if (!a.quantised) HIP_TRY(mc::launch_quantize_rows_mx(a.rows, nullptr, a.ld, Lp, K, aq, K, am, (long)Lp, s));
-    p.a_mx = am; p.mx_rows_a = (long)Lp; p.w_mx = l.mx + out.first; p.mx_rows_w = l.n_out;   // block-major: [k / 32][n_out]
-    HIP_TRY(mc::launch_gemm_mxfp8(p, epi, s));
-    return MC_OK;
-  }
-  float* as = e->buf<float>("a_scale");
-  if (!a.quantised) HIP_TRY(mc::launch_quantize_rows_fp8(a.rows, nullptr, a.ld, Lp, K, aq, K, as, s));
-  p.a_scale = as; p.w_scale = l.q_scale + out.first;
-  HIP_TRY(mc::launch_gemm_fp8(p, epi, s));
-  return MC_OK;
 }
 
 // LayerNorm + modulate of x for the Linear `l`, as that Linear's activation source: with fp8_fused_quant an fp8 Linear's row
@@ -829,17 +844,6 @@ static const float* second_set(const mc_engine* e, const float* em) {
 }
 static const uint8_t* tok_sel(const mc_engine* e) { return e->tok_t ? e->buf<uint8_t>("tok_sel") : nullptr; }
 
-// ---- sequence-parallel geometry of the gather rounds (mc_sp_set_chunks)
-static int sp_chunk_rows(const mc_engine* e) { return e->Lp / e->sp_chunks; }
-static int sp_round_valid(const mc_engine* e, int c) {   // valid keys at the start of every shard's chunk c
-  const int lc = sp_chunk_rows(e);
-  return std::max(0, std::min(lc, e->Lr - c * lc));
-}
-static int sp_rounds(const mc_engine* e) {               // rounds that carry at least one valid key
-  const int lc = sp_chunk_rows(e);
-  return (e->Lr + lc - 1) / lc;
-}
-
 // LayerNorm + modulate -> "xn"; one device: q|k|v Linear -> "qkv", RMSNorm + RoPE of q and k (everything before attention).
 // Sequence parallel: only what the OTHER ranks wait for -- the [k|v] Linear into "kv_local" and the k norm / RoPE --, so that
 // the caller can start the all-gather before this rank's q exists (block_pre_q).
@@ -857,7 +861,7 @@ static mc_status block_pre_kv(mc_engine* e, const Layer& l, const float* em, flo
     p.Cb = qkv; p.ldc = 3 * d;
     {
       Prof pr(e, MC_PROF_GEMM_QKV, s);
-      MC_TRY(linear(e, l.qkv, whole(l.qkv), a, p, mc::EPI_BF16, s));
+      MC_TRY(linear(e, l.qkv, whole(l.qkv), Lp, a, p, mc::EPI_BF16, s));
     }
     Prof pr(e, MC_PROF_RMSNORM_ROPE, s);
     HIP_TRY(mc::launch_rmsnorm_rope(qkv, 3 * d, l.nq, e->cfg.eps, e->cs_table, 0, Lp, d, s));
@@ -869,7 +873,7 @@ static mc_status block_pre_kv(mc_engine* e, const Layer& l, const float* em, flo
     p.Cb = kvl; p.ldc = 2 * d;
     {
       Prof pr(e, MC_PROF_GEMM_QKV, s);
-      MC_TRY(linear(e, l.qkv, RowRange{d, 2 * d}, a, p, mc::EPI_BF16, s));
+      MC_TRY(linear(e, l.qkv, RowRange{d, 2 * d}, Lp, a, p, mc::EPI_BF16, s));
     }
     Prof pr(e, MC_PROF_RMSNORM_ROPE, s);
     HIP_TRY(mc::launch_rmsnorm_rope(kvl, 2 * d, l.nk, e->cfg.eps, e->cs_table, 0, Lp, d, s));
@@ -888,7 +892,7 @@ static mc_status block_pre_q(mc_engine* e, const Layer& l, hipStream_t s) {
     Prof pr(e, MC_PROF_GEMM_QKV, s);
     mc::GemmParams p = {};
     p.Cb = qkv; p.ldc = d;
-    MC_TRY(linear(e, l.qkv, RowRange{0, d}, ActSrc{e->buf<bf16_t>("xn"), d, true}, p, mc::EPI_BF16, s));
+    MC_TRY(linear(e, l.qkv, RowRange{0, d}, Lp, ActSrc{e->buf<bf16_t>("xn"), d, true}, p, mc::EPI_BF16, s));
   }
   Prof pr(e, MC_PROF_RMSNORM_ROPE, s);
   HIP_TRY(mc::launch_rmsnorm_rope(qkv, d, l.nq, e->cfg.eps, e->cs_table, 0, Lp, d, s));
@@ -896,8 +900,8 @@ static mc_status block_pre_q(mc_engine* e, const Layer& l, hipStream_t s) {
 }
 
 static mc_status block_pre(mc_engine* e, const Layer& l, const float* em, float* x, hipStream_t s) {
-  mc_status st = block_pre_kv(e, l, em, x, s);
-  return st != MC_OK ? st : block_pre_q(e, l, s);
+  MC_TRY(block_pre_kv(e, l, em, x, s));
+  return block_pre_q(e, l, s);
 }
 
 static mc_status check_layer_call(mc_engine* e, int layer) {
@@ -907,24 +911,22 @@ static mc_status check_layer_call(mc_engine* e, int layer) {
 }
 
 mc_status mc_block_pre_attn(mc_engine* e, int layer, mc_stream stream_) {
-  if (mc_status st = check_layer_call(e, layer); st != MC_OK) return st;
+  MC_TRY(check_layer_call(e, layer));
   e->pair_drop();   // a phase call works on "x", where a kept front lies
-  return block_pre(e, e->layers[layer], e->buf<float>("emod") + (size_t)layer * 6 * e->d, e->buf<float>("x"),
-                   (hipStream_t)stream_);
+  return block_pre(e, e->layers[layer], e->emod(e->layers[layer]), e->buf<float>("x"), (hipStream_t)stream_);
 }
 
 // The two halves of mc_block_pre_attn (sp_size > 1): a caller that starts its all-gather between them overlaps it with the q
 // Linear as well.  mc_block_pre_attn == mc_block_pre_kv + mc_block_pre_q.
 mc_status mc_block_pre_kv(mc_engine* e, int layer, mc_stream stream_) {
-  if (mc_status st = check_layer_call(e, layer); st != MC_OK) return st;
+  MC_TRY(check_layer_call(e, layer));
   if (!e->sp) return fail(MC_ESTATE, "mc_block_pre_kv needs a sequence-parallel engine (sp_size > 1 or sp_phases) (one GPU: mc_block_pre_attn / mc_forward)");
   e->pair_drop();
-  return block_pre_kv(e, e->layers[layer], e->buf<float>("emod") + (size_t)layer * 6 * e->d, e->buf<float>("x"),
-                      (hipStream_t)stream_);
+  return block_pre_kv(e, e->layers[layer], e->emod(e->layers[layer]), e->buf<float>("x"), (hipStream_t)stream_);
 }
 
 mc_status mc_block_pre_q(mc_engine* e, int layer, mc_stream stream_) {
-  if (mc_status st = check_layer_call(e, layer); st != MC_OK) return st;
+  MC_TRY(check_layer_call(e, layer));
   if (!e->sp) return fail(MC_ESTATE, "mc_block_pre_q needs a sequence-parallel engine (sp_size > 1 or sp_phases)");
   e->pair_drop();
   return block_pre_q(e, e->layers[layer], (hipStream_t)stream_);
@@ -935,42 +937,26 @@ mc_status mc_block_pre_q(mc_engine* e, int layer, mc_stream stream_) {
 // rank's shard when the local launch already covered it.  The first launch of a chain writes "ao" and the log2-sum-exp of
 // the keys it visited ("attn_lse"); every later one merges into both in the kernel epilogue (in place).
 static mc_status sp_attn_launch(mc_engine* e, int layer, int round, hipStream_t s) {
-  const int d = e->d, Lp = e->Lp;
-  if (e->attn_layer != layer) {
-    e->attn_layer = layer; e->attn_launches = 0; e->attn_local_done = false; e->attn_rounds_done = 0;
-  }
+  attn_chain_open(e, layer);
   const int n_rounds = sp_rounds(e);
-  mc::AttnParams a;
-  memset(&a, 0, sizeof(a));
-  a.O = e->buf<bf16_t>("ao"); a.ldo = d; a.Lq_pad = Lp; a.n_heads = e->H; a.scale = 1.0f / std::sqrt(128.0f);
-  a.Q = e->buf<bf16_t>("qkv"); a.ldq = d;
   bool more;   // does another launch of this chain follow?
   if (round < 0) {
     if (e->attn_launches) return fail(MC_ESTATE, "the local-shard attention must be the first launch of a layer's chain");
-    bf16_t* kvl = e->buf<bf16_t>("kv_local");
-    a.K = kvl; a.ldk = 2 * d; a.V = kvl + d; a.ldv = 2 * d;
-    a.shard_rows = Lp; a.shard_valid = e->Lr; a.n_shards = 1;
     more = true;
   } else {
     if (round != e->attn_rounds_done || round >= n_rounds)
       return fail(MC_ESTATE, "attention round %d out of order (rounds done %d of %d)", round, e->attn_rounds_done, n_rounds);
-    const int lc = sp_chunk_rows(e);
-    bf16_t* kvg = e->buf<bf16_t>("kv_gather") + (size_t)round * e->P * lc * 2 * d;
-    a.K = kvg; a.ldk = 2 * d; a.k_shard_stride = (long)lc * 2 * d;
-    a.V = kvg + d; a.ldv = 2 * d; a.v_shard_stride = (long)lc * 2 * d;
-    a.shard_rows = lc; a.shard_valid = sp_round_valid(e, round); a.n_shards = e->P;
-    if (e->attn_local_done) a.skip_shard_p1 = e->rank + 1;
     more = round + 1 < n_rounds;
     if (e->attn_local_done && e->P == 1) {   // a world of one (sp_phases): the local launch covered every key
       e->attn_rounds_done++;
       return MC_OK;
     }
   }
-  if (e->attn_launches) a.lse_in = e->buf<float>("attn_lse");
-  if (more) a.lse_out = e->buf<float>("attn_lse");
+  float* lse = e->buf<float>("attn_lse");
   {
     Prof pr(e, MC_PROF_ATTN_SELF, s);   // measurement hook, see mc_profile_enable
-    HIP_TRY(mc::launch_attention(a, s));
+    MC_TRY(attend(e, e->buf<bf16_t>("qkv"), e->d, e->buf<bf16_t>("ao"), sp_keys(e, round, e->attn_local_done),
+                  e->attn_launches ? lse : nullptr, more ? lse : nullptr, s));
   }
   e->attn_launches++;
   if (round < 0) e->attn_local_done = true; else e->attn_rounds_done++;
@@ -980,28 +966,9 @@ static mc_status sp_attn_launch(mc_engine* e, int layer, int round, hipStream_t 
 // One launch of the chain as an INDEPENDENT partial result: slot 0 = this rank's own shard, slot 1 + c = gather round c
 // without this rank's shard; normalised O -> "ao_part"[slot], log2-sum-exp -> "lse_part"[slot]; nothing is merged here.
 static mc_status sp_attn_partial(mc_engine* e, int round, hipStream_t s) {   // (timed by the caller: one pair around the chain)
-  const int d = e->d, Lp = e->Lp;
-  const int slot = round < 0 ? 0 : 1 + round;
-  mc::AttnParams a;
-  memset(&a, 0, sizeof(a));
-  a.O = e->buf<bf16_t>("ao_part") + (size_t)slot * Lp * d; a.ldo = d; a.Lq_pad = Lp; a.n_heads = e->H;
-  a.scale = 1.0f / std::sqrt(128.0f);
-  a.Q = e->buf<bf16_t>("qkv"); a.ldq = d;
-  a.lse_out = e->buf<float>("lse_part") + (size_t)slot * e->H * Lp;
-  if (round < 0) {
-    bf16_t* kvl = e->buf<bf16_t>("kv_local");
-    a.K = kvl; a.ldk = 2 * d; a.V = kvl + d; a.ldv = 2 * d;
-    a.shard_rows = Lp; a.shard_valid = e->Lr; a.n_shards = 1;
-  } else {
-    const int lc = sp_chunk_rows(e);
-    bf16_t* kvg = e->buf<bf16_t>("kv_gather") + (size_t)round * e->P * lc * 2 * d;
-    a.K = kvg; a.ldk = 2 * d; a.k_shard_stride = (long)lc * 2 * d;
-    a.V = kvg + d; a.ldv = 2 * d; a.v_shard_stride = (long)lc * 2 * d;
-    a.shard_rows = lc; a.shard_valid = sp_round_valid(e, round); a.n_shards = e->P;
-    a.skip_shard_p1 = e->rank + 1;
-  }
-  HIP_TRY(mc::launch_attention(a, s));
-  return MC_OK;
+  const size_t slot = round < 0 ? 0 : 1 + round;
+  return attend(e, e->buf<bf16_t>("qkv"), e->d, e->buf<bf16_t>("ao_part") + slot * e->Lp * e->d, sp_keys(e, round, true), nullptr,
+                e->buf<float>("lse_part") + slot * e->H * e->Lp, s);
 }
 
 static mc_status sp_side_stream(mc_engine* e) {
@@ -1015,7 +982,7 @@ static mc_status sp_side_stream(mc_engine* e) {
 // Self-attention over this rank's own K/V shard ("kv_local"): normalised partial result -> "ao", log2-sum-exp ->
 // "attn_lse".  Needs nothing from the other ranks, so the caller overlaps it with the all-gather.
 mc_status mc_block_attn_local(mc_engine* e, int layer, mc_stream stream_) {
-  if (mc_status st = check_layer_call(e, layer); st != MC_OK) return st;
+  MC_TRY(check_layer_call(e, layer));
   if (!e->sp) return fail(MC_ESTATE, "mc_block_attn_local needs a sequence-parallel engine (sp_size > 1 or sp_phases)");
   return sp_attn_launch(e, layer, -1, (hipStream_t)stream_);
 }
@@ -1023,7 +990,7 @@ mc_status mc_block_attn_local(mc_engine* e, int layer, mc_stream stream_) {
 // Self-attention over round `round` of the gathered shards (rounds in order 0 .. mc_sp_rounds - 1; the caller has made
 // `stream` wait for that round of its all-gather).  mc_block_post_attn attends whatever rounds are still missing.
 mc_status mc_block_attn_round(mc_engine* e, int layer, int round, mc_stream stream_) {
-  if (mc_status st = check_layer_call(e, layer); st != MC_OK) return st;
+  MC_TRY(check_layer_call(e, layer));
   if (!e->sp) return fail(MC_ESTATE, "mc_block_attn_round needs a sequence-parallel engine (sp_size > 1 or sp_phases)");
   if (round < 0) return fail(MC_EINVAL, "round %d", round);
   return sp_attn_launch(e, layer, round, (hipStream_t)stream_);
@@ -1078,30 +1045,18 @@ mc_status mc_sp_round_info(const mc_engine* e, int round, int* n_rounds, int* ch
 // "pair_cq" in the two forwards of a CFG pair.
 static mc_status block_post_self(mc_engine* e, const Layer& l, const float* em, float* x, int layer, bf16_t* cq, hipStream_t s) {
   const int d = e->d, Lp = e->Lp;
-  bf16_t* qkv = e->buf<bf16_t>("qkv");
   bf16_t* ao = e->buf<bf16_t>("ao");
-  const float scale = 1.0f / std::sqrt(128.0f);
   const float* em2 = second_set(e, em);
   const uint8_t* sel = tok_sel(e);
 
   // ---- self attention over the full sequence
   if (!e->sp) {
-    mc::AttnParams a;
-    memset(&a, 0, sizeof(a));
-    a.O = ao; a.ldo = d; a.Lq_pad = Lp; a.n_heads = e->H; a.scale = scale;
-    a.Q = qkv; a.ldq = 3 * d;
-    a.K = qkv + d; a.ldk = 3 * d; a.k_shard_stride = 0;
-    a.V = qkv + 2 * d; a.ldv = 3 * d; a.v_shard_stride = 0;
-    a.shard_rows = Lp; a.shard_valid = e->Lr; a.n_shards = 1;
     Prof pr(e, MC_PROF_ATTN_SELF, s);
-    HIP_TRY(mc::launch_attention(a, s));
+    MC_TRY(attend(e, e->buf<bf16_t>("qkv"), 3 * d, ao, qkv_keys(e), nullptr, nullptr, s));
   } else {
     // whatever the caller has not attended yet (mc_block_attn_local / mc_block_attn_round): the remaining gather rounds
-    if (e->attn_layer != layer) { e->attn_layer = layer; e->attn_launches = 0; e->attn_local_done = false; e->attn_rounds_done = 0; }
-    while (e->attn_rounds_done < sp_rounds(e)) {
-      mc_status st = sp_attn_launch(e, layer, e->attn_rounds_done, s);
-      if (st != MC_OK) return st;
-    }
+    attn_chain_open(e, layer);
+    while (e->attn_rounds_done < sp_rounds(e)) MC_TRY(sp_attn_launch(e, layer, e->attn_rounds_done, s));
     e->attn_layer = -2;
   }
   {  // x = x + o(attn) * e[2]
@@ -1109,7 +1064,7 @@ static mc_status block_post_self(mc_engine* e, const Layer& l, const float* em, 
     mc::GemmParams p = {};
     p.X = x; p.ldx = d; p.gate = em + 2 * d;
     if (em2) { p.gate2 = em2 + 2 * d; p.gate_sel = sel; }
-    MC_TRY(linear(e, l.o, whole(l.o), ActSrc{ao, d}, p, mc::EPI_RESID_GATE, s));
+    MC_TRY(linear(e, l.o, whole(l.o), Lp, ActSrc{ao, d}, p, mc::EPI_RESID_GATE, s));
   }
   // ---- cross attention: x = x + o(attn(norm_q(q(norm3(x))), norm_k(k(ctx)), v(ctx)))
   ActSrc xn;   // LayerNorm output: the activation rows of cross-attention Q
@@ -1117,63 +1072,73 @@ static mc_status block_post_self(mc_engine* e, const Layer& l, const float* em, 
     Prof pr(e, MC_PROF_LN_MODULATE, s);
     MC_TRY(ln_for_gemm(e, l.cq, x, l.n3w, l.n3b, 1, nullptr, nullptr, nullptr, s, &xn));
   }
-  mc::GemmParams p = {};
-  p.Cb = cq; p.ldc = d;
   {
     Prof pr(e, MC_PROF_GEMM_CROSS_Q, s);
-    MC_TRY(linear(e, l.cq, whole(l.cq), xn, p, mc::EPI_BF16, s));
+    MC_TRY(linear_bf16_out(e, l.cq, Lp, xn, cq, mc::EPI_BF16, s));
   }
   Prof pr(e, MC_PROF_RMSNORM_ROPE, s);
   HIP_TRY(mc::launch_rmsnorm_rope(cq, d, l.cnq, e->cfg.eps, nullptr, 0, Lp, d, s));
   return MC_OK;
 }
 
-static mc_status block_post_ctx(mc_engine* e, const Layer& l, const float* em, float* x, int layer, const bf16_t* cq,
-                                bool capture, int branch, mc_mode mode, hipStream_t s) {
+// MagCache residual capture (residual = x_out - ori_x, :299-301), the one place that knows where the residual of
+// (branch, mode) goes and what follows once it is there.  Who writes it differs: the fused epilogue of the last FFN-2
+// (block_post_ctx), or a separate launch_residual_sub where the last layer still receives a VACE hint (capture_unfused).
+// A calibration forward writes the scratch slot, compares it with the branch's previous residual and swaps the two.
+static float* capture_dst(const mc_engine* e, int branch, mc_mode mode) {
+  return e->residual(mode == MC_MODE_CALIB ? e->res_scratch : e->res_slot[branch]);
+}
+// timed: the statistics launch is logged as MC_PROF_OTHER (the fused path; the unfused one never was)
+static mc_status capture_written(mc_engine* e, int branch, mc_mode mode, bool timed, hipStream_t s) {
+  const int d = e->d;
+  if (mode == MC_MODE_CALIB) {
+    if (!e->cfg.calibration) return fail(MC_ESTATE, "engine was created without calibration=1");
+    if (e->have_res[branch]) {
+      Prof pr(e, timed ? MC_PROF_OTHER : -1, s);
+      HIP_TRY(mc::launch_calib_stats(e->residual(e->res_scratch), d, e->residual(e->res_slot[branch]), d, e->Lr, d,
+                                     e->buf<double>("calib_partial"), 2048, e->buf<double>("calib_sums"),
+                                     e->buf<float>("calib_stats") + 3 * branch, s));
+    }
+    e->have_stats[branch] = e->have_res[branch];
+    std::swap(e->res_slot[branch], e->res_scratch);
+  }
+  e->have_res[branch] = true;
+  return MC_OK;
+}
+
+static mc_status block_post_ctx(mc_engine* e, const Layer& l, const float* em, float* x, const bf16_t* cq, bool capture,
+                                int branch, mc_mode mode, hipStream_t s) {
   const int d = e->d, Lp = e->Lp, ffn = e->ffn;
   bf16_t* ao = e->buf<bf16_t>("ao");
-  const float scale = 1.0f / std::sqrt(128.0f);
   const float* em2 = second_set(e, em);
   const uint8_t* sel = tok_sel(e);
   bf16_t* ckv = e->buf<bf16_t>("ckv");
   {
     if (e->ctx_active >= 0) {
       // constant over a video for this context: computed once by mc_set_context
-      const size_t li = (size_t)(&l - (layer >= 0 ? e->layers.data() : e->vlayers.data())) + (layer >= 0 ? 0 : e->NL);
-      ckv = e->buf<bf16_t>("ckv_cache") + ((size_t)e->ctx_active * (e->NL + e->NV) + li) * e->ctx_rows * 2 * d;
+      ckv = e->buf<bf16_t>("ckv_cache") + ((size_t)e->ctx_active * (e->NL + e->NV) + l.index) * e->ctx_rows * 2 * d;
     } else {
       Prof pr(e, MC_PROF_OTHER, s);
-      mc_status kst = context_kv(e, l, e->buf<bf16_t>("ctx"), ckv, s);
-      if (kst != MC_OK) return kst;
+      MC_TRY(context_kv(e, l, e->buf<bf16_t>("ctx"), ckv, s));
     }
-    mc::AttnParams a;
-    memset(&a, 0, sizeof(a));
-    a.Q = cq; a.ldq = d; a.K = ckv; a.ldk = 2 * d; a.V = ckv + d; a.ldv = 2 * d;
-    a.O = ao; a.ldo = d; a.Lq_pad = Lp; a.n_heads = e->H; a.scale = scale;
-    a.shard_rows = e->ctx_rows; a.shard_valid = e->cfg.text_len; a.n_shards = 1;
     {
       Prof pr(e, MC_PROF_ATTN_CROSS, s);
-      HIP_TRY(mc::launch_attention(a, s));
+      MC_TRY(attend(e, cq, d, ao, kv_pairs(ckv, d, e->ctx_rows, e->cfg.text_len), nullptr, nullptr, s));
     }
     if (e->cfg.clip_dim > 0) {
       Prof pr(e, MC_PROF_OTHER, s);
       // I2V (upstream WanI2VCrossAttention): + attention over the 257 CLIP image tokens with their own k/v
       bf16_t* ckvi = e->buf<bf16_t>("ckv_img");
       bf16_t* ao2 = e->buf<bf16_t>("ao2");
-      mc::GemmParams qi = gp(e->buf<bf16_t>("ctx_img"), d, l.ckv_img.w, d, l.ckv_img.b, e->img_rows, 2 * d, d);
-      qi.Cb = ckvi; qi.ldc = 2 * d;
-      HIP_TRY(mc::launch_gemm_bf16(qi, mc::EPI_BF16, s));
+      MC_TRY(linear_bf16_out(e, l.ckv_img, e->img_rows, ActSrc{e->buf<bf16_t>("ctx_img"), d}, ckvi, mc::EPI_BF16, s));
       HIP_TRY(mc::launch_rmsnorm_rope(ckvi, 2 * d, l.cnk_img, e->cfg.eps, nullptr, 0, e->img_rows, d, s));
-      mc::AttnParams ai = a;
-      ai.K = ckvi; ai.V = ckvi + d; ai.O = ao2;
-      ai.shard_rows = e->img_rows; ai.shard_valid = 257;
-      HIP_TRY(mc::launch_attention(ai, s));
+      MC_TRY(attend(e, cq, d, ao2, kv_pairs(ckvi, d, e->img_rows, 257), nullptr, nullptr, s));
       HIP_TRY(mc::launch_add_bf16(ao, ao2, (size_t)Lp * d, s));
     }
     Prof pr(e, MC_PROF_GEMM_CROSS_O, s);
     mc::GemmParams o = {};
     o.X = x; o.ldx = d; o.gate = nullptr;
-    MC_TRY(linear(e, l.co, whole(l.co), ActSrc{ao, d}, o, mc::EPI_RESID_GATE, s));
+    MC_TRY(linear(e, l.co, whole(l.co), Lp, ActSrc{ao, d}, o, mc::EPI_RESID_GATE, s));
   }
   // ---- FFN: x = x + ffn(LN(x)*(1+e[4])+e[3]) * e[5]
   ActSrc xn;   // LayerNorm output: the activation rows of FFN-1
@@ -1183,64 +1148,39 @@ static mc_status block_post_ctx(mc_engine* e, const Layer& l, const float* em, f
                        s, &xn));
   }
   bf16_t* h = e->buf<bf16_t>("h");
-  {
-    mc::GemmParams p = {};
-    p.Cb = h; p.ldc = ffn;
-    // MX with fused quantisers: FFN-1's GELU epilogue writes the e4m3 rows + block scales FFN-2 reads (both inside "h":
-    // Lp * ffn bytes, then ffn / 32 * Lp scale bytes), the bf16 hidden tensor never exists
-    const bool h_fp8 = l.ffn1.mx && l.ffn2.mx && mc::g_fp8_fused_quant;
-    ActSrc hidden{h, ffn};
-    if (h_fp8) {
-      hidden.quantised = true; hidden.q = (uint8_t*)h; hidden.mx = hidden.q + (size_t)Lp * ffn;
-      p.Cq = hidden.q; p.ldcq = ffn; p.c_mx = hidden.mx; p.mx_rows_c = Lp;
-    }
-    {
-      Prof pr(e, MC_PROF_GEMM_FFN1, s);
-      MC_TRY(linear(e, l.ffn1, whole(l.ffn1), xn, p, h_fp8 ? mc::EPI_GELU_MXFP8 : mc::EPI_GELU_BF16, s));
-    }
-    mc::GemmParams q = {};
-    q.X = x; q.ldx = d; q.gate = em + 5 * d;
-    if (e->splitk_bytes) { q.splitk_ws = e->buf<float>("splitk"); q.splitk_ws_bytes = e->splitk_bytes; }
-    if (em2) { q.gate2 = em2 + 5 * d; q.gate_sel = sel; }
-    auto ffn2 = [&](int epi) -> mc_status {
-      Prof pr(e, MC_PROF_GEMM_FFN2, s);
-      return linear(e, l.ffn2, whole(l.ffn2), hidden, q, epi, s);
-    };
-    if (capture) {
-      // MagCache residual capture fused into the last epilogue: residual = x_out - ori_x  (:299-301)
-      const int dst = (mode == MC_MODE_CALIB) ? e->res_scratch : e->res_slot[branch];
-      q.X0 = e->buf<bf16_t>("x0"); q.ldx0 = d;
-      q.R = e->residual(dst); q.ldr = d;
-      {
-        mc_status st = ffn2(mc::EPI_RESID_CAPTURE);
-        if (st != MC_OK) return st;
-      }
-      if (mode == MC_MODE_CALIB) {
-        if (!e->cfg.calibration) return fail(MC_ESTATE, "engine was created without calibration=1");
-        if (e->have_res[branch]) {
-          Prof pr(e, MC_PROF_OTHER, s);
-          HIP_TRY(mc::launch_calib_stats(e->residual(dst), d, e->residual(e->res_slot[branch]), d, e->Lr, d,
-                                         e->buf<double>("calib_partial"), 2048, e->buf<double>("calib_sums"),
-                                         e->buf<float>("calib_stats") + 3 * branch, s));
-          e->have_stats[branch] = true;
-        } else {
-          e->have_stats[branch] = false;
-        }
-        std::swap(e->res_slot[branch], e->res_scratch);
-      }
-      e->have_res[branch] = true;
-    } else {
-      mc_status st = ffn2(mc::EPI_RESID_GATE);
-      if (st != MC_OK) return st;
-    }
+  mc::GemmParams p = {};
+  p.Cb = h; p.ldc = ffn;
+  // MX with fused quantisers: FFN-1's GELU epilogue writes the e4m3 rows + block scales FFN-2 reads (both inside "h":
+  // Lp * ffn bytes, then ffn / 32 * Lp scale bytes), the bf16 hidden tensor never exists
+  const bool h_fp8 = l.ffn1.mx && l.ffn2.mx && mc::g_fp8_fused_quant;
+  ActSrc hidden{h, ffn};
+  if (h_fp8) {
+    hidden.quantised = true; hidden.q = (uint8_t*)h; hidden.mx = hidden.q + (size_t)Lp * ffn;
+    p.Cq = hidden.q; p.ldcq = ffn; p.c_mx = hidden.mx; p.mx_rows_c = Lp;
   }
-  return MC_OK;
+  {
+    Prof pr(e, MC_PROF_GEMM_FFN1, s);
+    MC_TRY(linear(e, l.ffn1, whole(l.ffn1), Lp, xn, p, h_fp8 ? mc::EPI_GELU_MXFP8 : mc::EPI_GELU_BF16, s));
+  }
+  mc::GemmParams q = {};
+  q.X = x; q.ldx = d; q.gate = em + 5 * d;
+  if (e->splitk_bytes) { q.splitk_ws = e->buf<float>("splitk"); q.splitk_ws_bytes = e->splitk_bytes; }
+  if (em2) { q.gate2 = em2 + 5 * d; q.gate_sel = sel; }
+  if (capture) {   // fused into the last epilogue
+    q.X0 = e->buf<bf16_t>("x0"); q.ldx0 = d;
+    q.R = capture_dst(e, branch, mode); q.ldr = d;
+  }
+  {
+    Prof pr(e, MC_PROF_GEMM_FFN2, s);
+    MC_TRY(linear(e, l.ffn2, whole(l.ffn2), Lp, hidden, q, capture ? mc::EPI_RESID_CAPTURE : mc::EPI_RESID_GATE, s));
+  }
+  return capture ? capture_written(e, branch, mode, true, s) : MC_OK;
 }
 
 static mc_status block_post(mc_engine* e, const Layer& l, const float* em, float* x, int layer, bf16_t* cq, bool capture,
                             int branch, mc_mode mode, hipStream_t s) {
   MC_TRY(block_post_self(e, l, em, x, layer, cq, s));
-  return block_post_ctx(e, l, em, x, layer, cq, capture, branch, mode, s);
+  return block_post_ctx(e, l, em, x, cq, capture, branch, mode, s);
 }
 
 // The last main layer receives a VACE hint: no fused capture there, the residual is taken after the hint was added.
@@ -1253,8 +1193,8 @@ mc_status mc_block_post_attn(mc_engine* e, int layer, int branch, mc_mode mode, 
   if (layer < 0 || layer >= e->NL) return fail(MC_EINVAL, "layer %d out of range", layer);
   if (branch < 0 || branch >= e->cfg.n_branches) return fail(MC_EINVAL, "branch %d out of range", branch);
   e->pair_drop();
-  return block_post(e, e->layers[layer], e->buf<float>("emod") + (size_t)layer * 6 * e->d, e->buf<float>("x"), layer,
-                    e->buf<bf16_t>("qkv"), layer == e->NL - 1 && !hint_on_last_layer(e), branch, mode, (hipStream_t)stream_);
+  return block_post(e, e->layers[layer], e->emod(e->layers[layer]), e->buf<float>("x"), layer, e->buf<bf16_t>("qkv"),
+                    layer == e->NL - 1 && !hint_on_last_layer(e), branch, mode, (hipStream_t)stream_);
 }
 
 // VACE: control block i on the stream c, then x += after_proj(c) * context_scale (the "hint" of main layer
@@ -1266,36 +1206,33 @@ static mc_status vace_pre_kv(mc_engine* e, int i, hipStream_t s) {
     // c = before_proj(c0) + x, x = the embedded latent (ori_x, bf16 under autocast)
     HIP_TRY(hipMemsetAsync(xc, 0, (size_t)Lp * d * 4, s));
     HIP_TRY(mc::launch_skip_add(e->buf<bf16_t>("x0"), d, xc, d, xc, d, Lp, d, s));
-    mc::GemmParams p = gp(e->buf<bf16_t>("c0"), d, e->w_before, d, e->b_before, Lp, d, d);
+    mc::GemmParams p = {};
     p.X = xc; p.ldx = d; p.gate = nullptr;
-    HIP_TRY(mc::launch_gemm_bf16(p, mc::EPI_RESID_GATE, s));
+    MC_TRY(linear(e, e->before, whole(e->before), Lp, ActSrc{e->buf<bf16_t>("c0"), d}, p, mc::EPI_RESID_GATE, s));
   }
-  return block_pre_kv(e, e->vlayers[i], e->buf<float>("emod") + (size_t)(e->NL + i) * 6 * d, xc, s);
+  return block_pre_kv(e, e->vlayers[i], e->emod(e->vlayers[i]), xc, s);
 }
 
 static mc_status vace_pre(mc_engine* e, int i, hipStream_t s) {
-  mc_status st = vace_pre_kv(e, i, s);
-  return st != MC_OK ? st : block_pre_q(e, e->vlayers[i], s);
+  MC_TRY(vace_pre_kv(e, i, s));
+  return block_pre_q(e, e->vlayers[i], s);
 }
 
 static mc_status vace_post(mc_engine* e, int i, int branch, mc_mode mode, hipStream_t s) {
   const int d = e->d, Lp = e->Lp;
   float* xc = e->buf<float>("xc");
-  mc_status st = block_post(e, e->vlayers[i], e->buf<float>("emod") + (size_t)(e->NL + i) * 6 * d, xc, -1,
-                            e->buf<bf16_t>("qkv"), false, branch, mode, s);
-  if (st != MC_OK) return st;
+  MC_TRY(block_post(e, e->vlayers[i], e->emod(e->vlayers[i]), xc, -1, e->buf<bf16_t>("qkv"), false, branch, mode, s));
   // hint: after_proj(c) needs bf16 rows of c; the LayerNorm scratch xn is free here
   bf16_t* xn = e->buf<bf16_t>("xn");
   HIP_TRY(mc::launch_cast_bf16(xc, xn, (size_t)Lp * d, s));
-  mc::GemmParams h = gp(xn, d, e->w_after[i], d, e->b_after[i], Lp, d, d);
+  mc::GemmParams h = {};
   h.X = e->buf<float>("x"); h.ldx = d; h.gate = e->vscale;
-  HIP_TRY(mc::launch_gemm_bf16(h, mc::EPI_RESID_GATE, s));
-  return MC_OK;
+  return linear(e, e->after[i], whole(e->after[i]), Lp, ActSrc{xn, d}, h, mc::EPI_RESID_GATE, s);
 }
 
 static mc_status vace_block(mc_engine* e, int i, int branch, mc_mode mode, hipStream_t s) {
-  mc_status st = vace_pre(e, i, s);
-  return st != MC_OK ? st : vace_post(e, i, branch, mode, s);
+  MC_TRY(vace_pre(e, i, s));
+  return vace_post(e, i, branch, mode, s);
 }
 
 // Sequence parallel: control block i in two phases, like the main blocks (the caller all-gathers "kv_gather" between
@@ -1360,22 +1297,18 @@ mc_status mc_blocks_sp(mc_engine* e, int layer_begin, int layer_end, int branch,
   const bool underfilled = wg * 10 < waves * g_n_cu * 9;               // < 90 % of the CU slots it occupies (sp 4 / 8 at 1.3B: 75 %;
                                                                        // 14B at sp 8: 1480 workgroups = 96 %: the merge would only cost)
   const bool partials = (mc::g_sp_attn_partials == 2 || (mc::g_sp_attn_partials == 1 && underfilled)) && e->P > 1 && 1 + R <= kSpMaxParts;
-  if (partials)
-    if (mc_status st = sp_side_stream(e); st != MC_OK) return st;
+  if (partials) MC_TRY(sp_side_stream(e));
   // one attention chain: starts, [waits], q, local shard, ([wait] round) x R
-  auto attend = [&](int l, const Layer& ly, int chain) -> mc_status {
-    mc_status st;
-    for (int c = 0; c < R; ++c)
-      if ((st = coll(l, 2 * c)) != MC_OK) return st;
+  auto chain = [&](int l, const Layer& ly, int chain_id) -> mc_status {
+    for (int c = 0; c < R; ++c) MC_TRY(coll(l, 2 * c));
     if (!overlap)
-      for (int c = 0; c < R; ++c)
-        if ((st = wait_round(l, c, s)) != MC_OK) return st;
-    if ((st = block_pre_q(e, ly, s)) != MC_OK) return st;
+      for (int c = 0; c < R; ++c) MC_TRY(wait_round(l, c, s));
+    MC_TRY(block_pre_q(e, ly, s));
     if (!partials) {
-      if ((st = sp_attn_launch(e, chain, -1, s)) != MC_OK) return st;
+      MC_TRY(sp_attn_launch(e, chain_id, -1, s));
       for (int c = 0; c < R; ++c) {
-        if (overlap && (st = wait_round(l, c, s)) != MC_OK) return st;
-        if ((st = sp_attn_launch(e, chain, c, s)) != MC_OK) return st;
+        if (overlap) MC_TRY(wait_round(l, c, s));
+        MC_TRY(sp_attn_launch(e, chain_id, c, s));
       }
       return MC_OK;
     }
@@ -1385,11 +1318,11 @@ mc_status mc_blocks_sp(mc_engine* e, int layer_begin, int layer_end, int branch,
     // q is ready (and the previous layer's merge has read the partial slots) once `s` gets here: the side stream follows
     HIP_TRY(hipEventRecord(e->ev_fork, s));
     HIP_TRY(hipStreamWaitEvent(e->side, e->ev_fork, 0));
-    if ((st = sp_attn_partial(e, -1, s)) != MC_OK) return st;
+    MC_TRY(sp_attn_partial(e, -1, s));
     for (int c = 0; c < R; ++c) {
       hipStream_t on = (c & 1) ? s : e->side;          // round 0 beside the local shard, then alternating
-      if (overlap && (st = wait_round(l, c, on)) != MC_OK) return st;
-      if ((st = sp_attn_partial(e, c, on)) != MC_OK) return st;
+      if (overlap) MC_TRY(wait_round(l, c, on));
+      MC_TRY(sp_attn_partial(e, c, on));
     }
     HIP_TRY(hipEventRecord(e->ev_join, e->side));
     HIP_TRY(hipStreamWaitEvent(s, e->ev_join, 0));
@@ -1401,45 +1334,29 @@ mc_status mc_blocks_sp(mc_engine* e, int layer_begin, int layer_end, int branch,
     }
     HIP_TRY(mc::launch_attn_merge(op, lp, 1 + R, e->buf<bf16_t>("ao"), e->d, e->Lp, e->Lp, e->d, s));
     // the chain is complete: block_post has nothing left to attend
-    e->attn_layer = chain; e->attn_launches = 1 + R; e->attn_local_done = true; e->attn_rounds_done = R;
+    attn_chain_set(e, chain_id, 1 + R, true, R);
     return MC_OK;
   };
-  const int d = e->d;
   for (int l = layer_begin; l < layer_end; ++l) {
-    mc_status st = block_pre_kv(e, e->layers[l], e->buf<float>("emod") + (size_t)l * 6 * d, e->buf<float>("x"), s);
-    if (st != MC_OK) return st;
-    if ((st = attend(l, e->layers[l], l)) != MC_OK) return st;
-    if ((st = mc_block_post_attn(e, l, branch, mode, stream)) != MC_OK) return st;
+    MC_TRY(block_pre_kv(e, e->layers[l], e->emod(e->layers[l]), e->buf<float>("x"), s));
+    MC_TRY(chain(l, e->layers[l], l));
+    MC_TRY(mc_block_post_attn(e, l, branch, mode, stream));
     if (e->NV > 0 && l % e->cfg.vace_stride == 0 && l / e->cfg.vace_stride < e->NV) {
       const int i = l / e->cfg.vace_stride;
       if (!e->have_vace) return fail(MC_ESTATE, "mc_set_vace_context must run first");
-      if ((st = vace_pre_kv(e, i, s)) != MC_OK) return st;
-      if ((st = attend(l, e->vlayers[i], -1)) != MC_OK) return st;
-      if ((st = mc_vace_block_post(e, i, branch, mode, stream)) != MC_OK) return st;
+      MC_TRY(vace_pre_kv(e, i, s));
+      MC_TRY(chain(l, e->vlayers[i], -1));
+      MC_TRY(mc_vace_block_post(e, i, branch, mode, stream));
     }
   }
   return MC_OK;
 }
 
-// residual capture + calibration statistics as separate kernels (only when the last layer carries a VACE hint)
+// residual capture as a separate kernel (only when the last layer carries a VACE hint)
 static mc_status capture_unfused(mc_engine* e, int branch, mc_mode mode, hipStream_t s) {
   const int d = e->d;
-  const int dst = (mode == MC_MODE_CALIB) ? e->res_scratch : e->res_slot[branch];
-  HIP_TRY(mc::launch_residual_sub(e->buf<float>("x"), d, e->buf<bf16_t>("x0"), d, e->residual(dst), d, e->Lp, d, s));
-  if (mode == MC_MODE_CALIB) {
-    if (!e->cfg.calibration) return fail(MC_ESTATE, "engine was created without calibration=1");
-    if (e->have_res[branch]) {
-      HIP_TRY(mc::launch_calib_stats(e->residual(dst), d, e->residual(e->res_slot[branch]), d, e->Lr, d,
-                                     e->buf<double>("calib_partial"), 2048, e->buf<double>("calib_sums"),
-                                     e->buf<float>("calib_stats") + 3 * branch, s));
-      e->have_stats[branch] = true;
-    } else {
-      e->have_stats[branch] = false;
-    }
-    std::swap(e->res_slot[branch], e->res_scratch);
-  }
-  e->have_res[branch] = true;
-  return MC_OK;
+  HIP_TRY(mc::launch_residual_sub(e->buf<float>("x"), d, e->buf<bf16_t>("x0"), d, capture_dst(e, branch, mode), d, e->Lp, d, s));
+  return capture_written(e, branch, mode, false, s);
 }
 
 // head(x, e) on this rank's tokens -> "head_tokens" [Lr, 4*out_dim] fp32       (reference :304)
@@ -1502,16 +1419,9 @@ mc_status mc_pair_end(mc_engine* e) {
   return MC_OK;
 }
 
-mc_status mc_forward(mc_engine* e, const float* latent_dev, const float* t_dev, double t_host,
-                     const void* context_dev, mc_dtype ctx_dtype, int ctx_len, int branch, mc_mode mode,
-                     float* out_dev, mc_stream stream) {
-  if (!e) return fail(MC_EINVAL, "null engine");
-  if (e->sp) return fail(MC_ESTATE, "mc_forward is single-GPU; drive a sharded engine through the phase calls");
-  if (!out_dev) return fail(MC_EINVAL, "null output");
-  if (e->NV > 0 && mode != MC_MODE_SKIP && !e->have_vace)
-    return fail(MC_ESTATE, "VACE model: mc_set_vace_context must run before a non-skipped forward");
-  if (branch < 0 || branch >= e->cfg.n_branches) return fail(MC_EINVAL, "branch %d out of range", branch);
-  hipStream_t s = (hipStream_t)stream;
+// the forward behind mc_forward's argument checks; a failure leaves the pair state to the caller
+static mc_status forward(mc_engine* e, const float* latent_dev, const float* t_dev, double t_host, const void* context_dev,
+                         mc_dtype ctx_dtype, int ctx_len, int branch, mc_mode mode, float* out_dev, hipStream_t s) {
   const int d = e->d;
   // this call's place in a declared pair: `keep` = it runs the front and leaves it behind, `reuse` = it continues from the
   // front the call before it left.  Every other case -- a skipped forward on either side, another t, a third forward -- ends
@@ -1524,46 +1434,48 @@ mc_status mc_forward(mc_engine* e, const float* latent_dev, const float* t_dev, 
   if (keep) { e->pair_latent = latent_dev; e->pair_t_dev = t_dev; e->pair_t_host = t_host; }
   float* x = e->buf<float>(keep ? "pair_x" : "x");
   bf16_t* cq = e->buf<bf16_t>(keep || reuse ? "pair_cq" : "qkv");
-  mc_status st;
   if (reuse) {
-    if ((st = check_ready(e)) != MC_OK) return st;
-    if (context_dev) {
-      Prof pr(e, MC_PROF_EMBED, s);
-      st = embed_text(e, context_dev, ctx_dtype, ctx_len, s);
-    } else {
-      st = embed_text(e, nullptr, ctx_dtype, 0, s);
-    }
+    MC_TRY(check_ready(e));
+    Prof pr(e, context_dev ? MC_PROF_EMBED : -1, s);
+    MC_TRY(embed_text(e, context_dev, ctx_dtype, ctx_len, s));
   } else {
-    st = embed(e, latent_dev, t_dev, t_host, context_dev, ctx_dtype, ctx_len, x, s);
+    MC_TRY(embed(e, latent_dev, t_dev, t_host, context_dev, ctx_dtype, ctx_len, x, s));
   }
-  if (st != MC_OK) { e->pair_drop(); return st; }
-  if (runs) {
-    for (int l = 0; l < e->NL; ++l) {
-      const Layer& ly = e->layers[l];
-      const float* em = e->buf<float>("emod") + (size_t)l * 6 * d;
-      const bool capture = l == e->NL - 1 && !hint_on_last_layer(e);
-      if (!(reuse && l == 0)) {
-        if ((st = block_pre(e, ly, em, x, s)) != MC_OK) break;
-        if ((st = block_post_self(e, ly, em, x, l, l == 0 ? cq : e->buf<bf16_t>("qkv"), s)) != MC_OK) break;
-      }
-      if (keep && l == 0) {
-        Prof pr(e, MC_PROF_OTHER, s);
-        if (hipMemcpyAsync(e->buf<float>("x"), x, (size_t)e->Lp * d * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) {
-          st = fail(MC_EHIP, "hipMemcpyAsync of the kept stream failed");
-          break;
-        }
-      }
-      if ((st = block_post_ctx(e, ly, em, x, l, l == 0 ? cq : e->buf<bf16_t>("qkv"), capture, branch, mode, s)) != MC_OK) break;
-      if (e->NV > 0 && l % e->cfg.vace_stride == 0 && l / e->cfg.vace_stride < e->NV) {
-        if ((st = vace_block(e, l / e->cfg.vace_stride, branch, mode, s)) != MC_OK) break;
-      }
+  for (int l = 0; runs && l < e->NL; ++l) {
+    const Layer& ly = e->layers[l];
+    const float* em = e->emod(ly);
+    bf16_t* lcq = l == 0 ? cq : e->buf<bf16_t>("qkv");
+    if (!(reuse && l == 0)) {
+      MC_TRY(block_pre(e, ly, em, x, s));
+      MC_TRY(block_post_self(e, ly, em, x, l, lcq, s));
     }
-    if (st == MC_OK && hint_on_last_layer(e)) st = capture_unfused(e, branch, mode, s);
-    if (st != MC_OK) { e->pair_drop(); return st; }
+    if (keep && l == 0) {
+      Prof pr(e, MC_PROF_OTHER, s);
+      if (hipMemcpyAsync(e->buf<float>("x"), x, (size_t)e->Lp * d * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)
+        return fail(MC_EHIP, "hipMemcpyAsync of the kept stream failed");
+    }
+    MC_TRY(block_post_ctx(e, ly, em, x, lcq, l == e->NL - 1 && !hint_on_last_layer(e), branch, mode, s));
+    if (e->NV > 0 && l % e->cfg.vace_stride == 0 && l / e->cfg.vace_stride < e->NV)
+      MC_TRY(vace_block(e, l / e->cfg.vace_stride, branch, mode, s));
   }
-  st = head(e, x, branch, mode, s);
-  if (st != MC_OK) return st;
-  return mc_unpatchify(e, e->buf<float>("head_tokens"), 0, e->L, out_dev, stream);
+  if (runs && hint_on_last_layer(e)) MC_TRY(capture_unfused(e, branch, mode, s));
+  MC_TRY(head(e, x, branch, mode, s));
+  return mc_unpatchify(e, e->buf<float>("head_tokens"), 0, e->L, out_dev, (mc_stream)s);
+}
+
+mc_status mc_forward(mc_engine* e, const float* latent_dev, const float* t_dev, double t_host,
+                     const void* context_dev, mc_dtype ctx_dtype, int ctx_len, int branch, mc_mode mode,
+                     float* out_dev, mc_stream stream) {
+  if (!e) return fail(MC_EINVAL, "null engine");
+  if (e->sp) return fail(MC_ESTATE, "mc_forward is single-GPU; drive a sharded engine through the phase calls");
+  if (!out_dev) return fail(MC_EINVAL, "null output");
+  if (e->NV > 0 && mode != MC_MODE_SKIP && !e->have_vace)
+    return fail(MC_ESTATE, "VACE model: mc_set_vace_context must run before a non-skipped forward");
+  if (branch < 0 || branch >= e->cfg.n_branches) return fail(MC_EINVAL, "branch %d out of range", branch);
+  const mc_status st = forward(e, latent_dev, t_dev, t_host, context_dev, ctx_dtype, ctx_len, branch, mode, out_dev,
+                               (hipStream_t)stream);
+  if (st != MC_OK) e->pair_drop();   // whatever failed: a kept front is not continued from
+  return st;
 }
 
 mc_status mc_calib_ready(const mc_engine* e, int branch, int* has_stats) {
@@ -1594,21 +1506,16 @@ mc_status mc_import_residual(mc_engine* e, int branch, const float* src_dev, mc_
 mc_status mc_set_context(mc_engine* e, int slot, const void* context_dev, mc_dtype ctx_dtype, int ctx_len,
                          mc_stream stream_) {
   hipStream_t s = (hipStream_t)stream_;
-  mc_status st = check_ready(e);
-  if (st != MC_OK) return st;
+  MC_TRY(check_ready(e));
   if (slot < 0 || slot > 1) return fail(MC_EINVAL, "context slot %d out of range (0, 1)", slot);
   if (e->cfg.no_context_cache) return fail(MC_ESTATE, "the engine was created with no_context_cache: pass the context to every forward");
   if (!context_dev) return fail(MC_EINVAL, "null context");
   const int d = e->d;
   bf16_t* ctx = e->buf<bf16_t>("ctx_cache") + (size_t)slot * e->ctx_rows * d;
   e->ctx_valid[slot] = false;
-  st = embed_context(e, context_dev, ctx_dtype, ctx_len, ctx, s);
-  if (st != MC_OK) return st;
+  MC_TRY(embed_context(e, context_dev, ctx_dtype, ctx_len, ctx, s));
   bf16_t* base = e->buf<bf16_t>("ckv_cache") + (size_t)slot * (e->NL + e->NV) * e->ctx_rows * 2 * d;
-  for (int l = 0; l < e->NL + e->NV; ++l) {
-    st = context_kv(e, l < e->NL ? e->layers[l] : e->vlayers[l - e->NL], ctx, base + (size_t)l * e->ctx_rows * 2 * d, s);
-    if (st != MC_OK) return st;
-  }
+  for (int l = 0; l < e->NL + e->NV; ++l) MC_TRY(context_kv(e, e->layer(l), ctx, base + (size_t)l * e->ctx_rows * 2 * d, s));
   e->ctx_valid[slot] = true;
   e->ctx_active = slot;
   return MC_OK;
@@ -1667,8 +1574,7 @@ mc_status mc_profile_read(mc_engine* e, double* attn_ms_total, int* attn_launche
   if (!e || !attn_ms_total || !attn_launches) return fail(MC_EINVAL, "null argument");
   double ms[MC_PROF_NCLASS];
   int n[MC_PROF_NCLASS];
-  mc_status st = mc_profile_read_classes(e, ms, n);
-  if (st != MC_OK) return st;
+  MC_TRY(mc_profile_read_classes(e, ms, n));
   *attn_ms_total = ms[MC_PROF_ATTN_SELF];
   *attn_launches = n[MC_PROF_ATTN_SELF];
   return MC_OK;

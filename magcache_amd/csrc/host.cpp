@@ -1,6 +1,7 @@
 // host.h: error text, weight store and workspace plan shared by the engines of this library.
 #include "host.h"
 
+#include <cmath>
 #include <cstdio>
 
 namespace mc {
@@ -33,6 +34,12 @@ Slot& WeightStore::add(const std::string& name, void* dst, mc_dtype dt, size_t n
   Slot s;
   s.dst = dst; s.dst_dtype = dt; s.numel = numel; s.off = off;
   return slots[name] = s;
+}
+
+mc_status WeightStore::add_f32(float*& p, const std::string& name, size_t numel) {
+  MC_TRY(alloc(&p, numel));
+  add(name, p, MC_F32, numel);
+  return MC_OK;
 }
 
 mc_status WeightStore::alloc_linear(Linear& l, size_t n_out, size_t k_in, Quant quant) {
@@ -213,6 +220,19 @@ hipError_t launch_linear_bf16(const Linear& l, RowRange out, const bf16_t* A, lo
   p.A = A; p.lda = lda; p.M = M; p.N = out.count; p.K = l.k_in;
   p.W = l.w + (size_t)out.first * l.k_in; p.ldw = l.k_in; p.bias = l.b + out.first;
   return launch_gemm_bf16(p, epi, s);
+}
+
+hipError_t launch_attention_keys(const bf16_t* Q, long ldq, bf16_t* O, long ldo, int q_rows_pad, int heads, const Keys& keys,
+                                 const float* lse_in, float* lse_out, hipStream_t s) {
+  AttnParams a;
+  memset(&a, 0, sizeof(a));
+  a.Q = Q; a.ldq = ldq; a.O = O; a.ldo = ldo;
+  a.K = keys.k; a.ldk = keys.ld; a.k_shard_stride = keys.stride;
+  a.V = keys.v; a.ldv = keys.ld; a.v_shard_stride = keys.stride;
+  a.Lq_pad = q_rows_pad; a.n_heads = heads; a.scale = 1.0f / std::sqrt(128.0f);   // head_dim is fixed at 128
+  a.shard_rows = keys.rows; a.shard_valid = keys.valid; a.n_shards = keys.n_shards; a.skip_shard_p1 = keys.skip_shard_p1;
+  a.lse_in = lse_in; a.lse_out = lse_out;
+  return launch_attention(a, s);
 }
 
 }  // namespace mc

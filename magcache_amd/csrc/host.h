@@ -1,5 +1,6 @@
 // What the host-side engines (engine.cpp, mmdit_engine.cpp) share, internal like ops.h: the error text mc_last_error()
-// reports, the named weight store behind *_set_weight, the workspace plan behind *_set_workspace, the Linear descriptor.
+// reports, the named weight store behind *_set_weight, the workspace plan behind *_set_workspace, the Linear descriptor and
+// the key set of an attention launch, each with its launch.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -30,13 +31,6 @@ const char* last_error();
   } while (0)
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-inline GemmParams gp(const bf16_t* A, long lda, const bf16_t* W, long ldw, const float* bias, int M, int N, int K) {
-  GemmParams p;
-  memset(&p, 0, sizeof(p));
-  p.A = A; p.lda = lda; p.W = W; p.ldw = ldw; p.bias = bias; p.M = M; p.N = N; p.K = K;
-  return p;
-}
 
 // mc_set_option values (ops_capi.cpp sets them), each defined in the file that reads it
 extern int g_fp8_fused_quant;    // engine.cpp
@@ -83,6 +77,8 @@ struct WeightStore {
   template <class T>
   mc_status alloc(T** p, size_t n) { return alloc_bytes(reinterpret_cast<void**>(p), n * sizeof(T)); }
   Slot& add(const std::string& name, void* dst, mc_dtype dt, size_t numel, size_t off = 0);
+  // an fp32 parameter that is no Linear's (norm weights, modulation, the fp32 matrices of a GEMV): allocates and registers it
+  mc_status add_f32(float*& p, const std::string& name, size_t numel);
   // One Linear [sum of the parts' rows, k_in]: allocates the bf16 weight + fp32 bias (and, quant != QUANT_NONE, the e4m3 copy
   // with its scales) and registers the parts.  alloc_linear / add_parts are its two halves, for a Linear whose parts are
   // added one by one (the fused modulation matrix) or whose slot the caller adjusts (Slot::pad, Slot::perm_c).
@@ -135,5 +131,18 @@ mc_status check_ready(const Workspace& work, const WeightStore& weights, const c
 // y[:, out] = epilogue(A W[out]^T + b[out]) on bf16 operands: p carries what the epilogue needs, the operands, the shape and
 // every pointer advance of a row range come from `l`
 hipError_t launch_linear_bf16(const Linear& l, RowRange out, const bf16_t* A, long lda, int M, GemmParams p, int epi, hipStream_t s);
+
+// The keys and values of one attention launch: n_shards blocks of `rows` rows (a multiple of 64; `stride` elements apart), the
+// first `valid` of each being keys; the rows up to `rows` are read and masked and must be finite.  skip_shard_p1 = k + 1 leaves
+// shard k out.
+struct Keys {
+  const bf16_t *k, *v;
+  long ld, stride;
+  int rows, valid, n_shards, skip_shard_p1;
+};
+// q_rows_pad query rows of Q over one key set -> O.  lse_out: keep the log2-sum-exp of this launch; lse_in: O already holds the
+// result over other keys with that log2-sum-exp, merge with it.
+hipError_t launch_attention_keys(const bf16_t* Q, long ldq, bf16_t* O, long ldo, int q_rows_pad, int heads, const Keys& keys,
+                                 const float* lse_in, float* lse_out, hipStream_t s);
 
 }  // namespace mc

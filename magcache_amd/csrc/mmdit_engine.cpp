@@ -46,6 +46,7 @@
 using mc::align_up;
 using mc::bf16_t;
 using mc::fail;
+using mc::Keys;
 using mc::Linear;
 
 namespace mc {
@@ -313,11 +314,7 @@ mc_status mc_mmdit_create(const mc_mmdit_config* cfg, mc_mmdit** out) {
   const size_t d = e->d;
   const bool flux = c.family == MC_FAMILY_FLUX;
   mc::WeightStore& W = e->weights;
-  auto vec128 = [&](float*& v, const std::string& name) {   // a per-head norm weight
-    MC_TRY(W.alloc(&v, 128));
-    W.add(name, v, MC_F32, 128);
-    return MC_OK;
-  };
+  auto vec128 = [&](float*& v, const std::string& name) { return W.add_f32(v, name, 128); };   // a per-head norm weight
   auto mlp2 = [&](Mlp2& m, size_t k_in, const std::string& l1, const std::string& l2) {
     MC_TRY(W.add_linear(m.l1, l1, {{"", d}}, k_in));
     return W.add_linear(m.l2, l2, {{"", d}}, d);
@@ -336,8 +333,7 @@ mc_status mc_mmdit_create(const mc_mmdit_config* cfg, mc_mmdit** out) {
   }
   MC_TRY(W.add_linear(e->txt_in, "", {{flux ? "context_embedder" : qw ? "txt_in" : "txt_in.input_embedder", d}}, c.txt_dim));
   if (qw) {
-    MC_TRY(W.alloc(&e->w_txt_norm, c.txt_dim));
-    W.add("txt_norm.weight", e->w_txt_norm, MC_F32, c.txt_dim);
+    MC_TRY(W.add_f32(e->w_txt_norm, "txt_norm.weight", c.txt_dim));
     MC_TRY(mlp2(e->time_mlp, 256, "time_text_embed.timestep_embedder.linear_1", "time_text_embed.timestep_embedder.linear_2"));
   } else if (flux) {
     MC_TRY(mlp2(e->time_mlp, 256, "time_text_embed.timestep_embedder.linear_1", "time_text_embed.timestep_embedder.linear_2"));
@@ -360,10 +356,7 @@ mc_status mc_mmdit_create(const mc_mmdit_config* cfg, mc_mmdit** out) {
       MC_TRY(W.add_linear(r.ada, p, {{"adaLN_modulation.1", 2 * d}}, d));
       float** norms[4] = {&r.n1w, &r.n1b, &r.n2w, &r.n2b};
       const char* names[4] = {"norm1.weight", "norm1.bias", "norm2.weight", "norm2.bias"};
-      for (int k = 0; k < 4; ++k) {
-        MC_TRY(W.alloc(norms[k], d));
-        W.add(p + names[k], *norms[k], MC_F32, d);
-      }
+      for (int k = 0; k < 4; ++k) MC_TRY(W.add_f32(*norms[k], p + names[k], d));
     }
   }
   // ---- fused modulation matrix: every block's AdaLN linear stacked, one GEMV per forward; the blocks add their parts
@@ -417,11 +410,11 @@ mc_status mc_mmdit_create(const mc_mmdit_config* cfg, mc_mmdit** out) {
   // ---- final layer
   // (Qwen-Image's head is FLUX's: AdaLayerNormContinuous, chunk order scale, shift)
   W.add_parts(e->mod, "", {{!hy ? "norm_out.linear" : "final_layer.adaLN_modulation.1", 2 * d}}, e->mod_final());
-  MC_TRY(W.alloc(&e->w_head, (size_t)e->out_feat * d));
-  MC_TRY(W.alloc(&e->b_head, e->out_feat));
-  mc::Slot& w_head = W.add(!hy ? "proj_out.weight" : "final_layer.linear.weight", e->w_head, MC_F32, (size_t)e->out_feat * d);
-  mc::Slot& b_head = W.add(!hy ? "proj_out.bias" : "final_layer.linear.bias", e->b_head, MC_F32, e->out_feat);
-  if (hy) w_head.perm_c = b_head.perm_c = c.out_channels;   // upstream (c, pt, ph, pw) channel-major; launch_unpatchify wants (ph, pw, c)
+  const std::string head = !hy ? "proj_out." : "final_layer.linear.";
+  MC_TRY(W.add_f32(e->w_head, head + "weight", (size_t)e->out_feat * d));
+  MC_TRY(W.add_f32(e->b_head, head + "bias", e->out_feat));
+  // upstream (c, pt, ph, pw) channel-major; launch_unpatchify wants (ph, pw, c)
+  if (hy) W.slots.at(head + "weight").perm_c = W.slots.at(head + "bias").perm_c = c.out_channels;
   // ---- RoPE table, identity rotation until mc_mmdit_set_rope
   MC_TRY(rope_identity(e, e->Sp));
   // ---- workspace plan
@@ -556,14 +549,8 @@ mc_status run_mlp2(const Mlp2& m, const float* x, float* h, float* y, int accumu
 }
 
 // ---------------------------------------------------------------------------------------------- attention
-// The keys and values of one attention launch: n_shards blocks of `rows` rows (a multiple of 64; `stride` elements apart), the
-// first `valid` of each being keys; the rows up to `rows` are read and masked and must be finite (padded text rows, the
-// neighbouring stream's rows or the zeroed tail of "qkv").
-struct Keys {
-  const bf16_t *k, *v;
-  long ld, stride;
-  int rows, valid, n_shards, skip_shard_p1;
-};
+// The key sets (mc::Keys) of this engine; the rows between `valid` and `rows` are padded text rows, the neighbouring stream's
+// rows or the zeroed tail of "qkv".
 Keys local_keys(const mc_mmdit* e, int row0, int rows_pad, int valid) {   // rows [row0, ..) of the local "qkv"
   const bf16_t* k = e->buf<bf16_t>("qkv") + (size_t)row0 * 3 * e->d + e->d;
   return {k, k + e->d, 3L * e->d, 0, rows_pad, valid, 1, 0};
@@ -579,17 +566,8 @@ Keys gathered_keys(const mc_mmdit* e, int skip_shard_p1) {
 // rows [0, q_rows_pad) of "qkv" as queries over one key set -> "am"[:, 0:d].  lse_out: keep the log-sum-exp of this launch;
 // lse_in: "am" already holds the result over other keys with that log-sum-exp, merge with it.
 mc_status attend(const mc_mmdit* e, int q_rows_pad, const Keys& keys, const float* lse_in, float* lse_out, hipStream_t s) {
-  const int d = e->d;
-  mc::AttnParams a;
-  memset(&a, 0, sizeof(a));
-  a.Q = e->buf<bf16_t>("qkv"); a.ldq = 3 * d;
-  a.K = keys.k; a.ldk = keys.ld; a.k_shard_stride = keys.stride;
-  a.V = keys.v; a.ldv = keys.ld; a.v_shard_stride = keys.stride;
-  a.O = e->buf<bf16_t>("am"); a.ldo = 5 * d;
-  a.Lq_pad = q_rows_pad; a.n_heads = e->H; a.scale = 1.0f / std::sqrt(128.0f);
-  a.shard_rows = keys.rows; a.shard_valid = keys.valid; a.n_shards = keys.n_shards; a.skip_shard_p1 = keys.skip_shard_p1;
-  a.lse_in = lse_in; a.lse_out = lse_out;
-  HIP_TRY(mc::launch_attention(a, s));
+  HIP_TRY(mc::launch_attention_keys(e->buf<bf16_t>("qkv"), 3L * e->d, e->buf<bf16_t>("am"), 5L * e->d, q_rows_pad, e->H, keys,
+                                    lse_in, lse_out, s));
   return MC_OK;
 }
 

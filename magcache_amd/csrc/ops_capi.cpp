@@ -6,7 +6,14 @@
 
 using mc::bf16_t;
 using mc::fail;
-using mc::gp;
+
+// operands and shape of a GEMM over the caller's buffers
+static mc::GemmParams gp(const bf16_t* A, long lda, const bf16_t* W, long ldw, const float* bias, int M, int N, int K) {
+  mc::GemmParams p;
+  memset(&p, 0, sizeof(p));
+  p.A = A; p.lda = lda; p.W = W; p.ldw = ldw; p.bias = bias; p.M = M; p.N = N; p.K = K;
+  return p;
+}
 
 extern "C" {
 
