@@ -67,9 +67,25 @@ typedef struct {
   int calibration;          /* reserve the second residual slot calibration mode needs (per CFG branch: Qwen-Image) */
   int sp_rank, sp_size;     /* sequence parallel: this rank owns image tokens [rank, rank+1) * img_tokens / sp_size; the
                                text tokens are replicated.  0, 1 (or 0, 0) for one GPU */
+  /* ---- fields behind the first layout: read by mc_mmdit_create_sized only; 0 = as before ---- */
+  int fp8_linear;           /* 0: bf16 Linears (default).  2: the block Linears that read a LayerNorm or GELU output (q|k|v,
+                               MLP-in and MLP-out of both streams of a double block, linear1 of a single block) keep an e4m3
+                               copy with OCP MX block scales (one E8M0 byte per 32 inputs) and run on the MX matrix-core
+                               GEMM, their activations quantised the same way.  3: the Linears that read the attention
+                               output too (the output projections; a single block's linear2 over all of its K = 5 dim).
+                               The embedders, the modulation, the HunyuanVideo token refiner and the head stay bf16.
+                               An optional speed / quality mode, one GPU (sp_size 1), dim >= 512; an fp8
+                               engine runs its blocks on one stream whatever "mmdit_two_streams" says.  1 (the Wan
+                               engine's per-row scales) has no MM-DiT path: MC_EINVAL, as is any other value. */
 } mc_mmdit_config;
 
+/* mc_mmdit_config only ever grows at its END, and a zero in a new field keeps the behaviour older callers had.
+ * mc_mmdit_create is the entry point of the first layout: it reads the struct up to and including sp_size, whatever the
+ * caller's header says behind it (so an fp8_linear set there is NOT seen).  mc_mmdit_create_sized takes cfg_bytes =
+ * the caller's sizeof(mc_mmdit_config): between the first layout's size and this library's, a multiple of sizeof(int)
+ * (MC_EINVAL otherwise); the fields the caller's struct does not have read as zeros. */
 mc_status mc_mmdit_create(const mc_mmdit_config* cfg, mc_mmdit** out);
+mc_status mc_mmdit_create_sized(const mc_mmdit_config* cfg, size_t cfg_bytes, mc_mmdit** out);
 void mc_mmdit_destroy(mc_mmdit* e);
 size_t mc_mmdit_workspace_bytes(const mc_mmdit* e);
 mc_status mc_mmdit_set_workspace(mc_mmdit* e, void* ws_dev, size_t bytes);

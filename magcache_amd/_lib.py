@@ -132,6 +132,7 @@ SIGNATURES = {
     "mc_op_rope_expand": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     # include/magcache_mmdit.h
     "mc_mmdit_create": (_i, [_vp, C.POINTER(_vp)]),
+    "mc_mmdit_create_sized": (_i, [_vp, _sz, C.POINTER(_vp)]),
     "mc_mmdit_destroy": (None, [_vp]),
     "mc_mmdit_workspace_bytes": (_sz, [_vp]),
     "mc_mmdit_set_workspace": (_i, [_vp, _vp, _sz]),
@@ -159,7 +160,8 @@ SIGNATURES = {
 class McMmditConfig(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("family", "dim", "num_heads", "n_double", "n_single", "in_channels", "out_channels",
                                        "txt_dim", "txt_len", "vec_dim", "img_tokens", "latent_f", "latent_h", "latent_w",
-                                       "refiner_depth", "calibration", "sp_rank", "sp_size")]
+                                       "refiner_depth", "calibration", "sp_rank", "sp_size",
+                                       "fp8_linear")]
 
 
 MC_FAMILY_FLUX, MC_FAMILY_HUNYUAN, MC_FAMILY_QWEN = 0, 1, 2

@@ -28,6 +28,13 @@
 //     VALU work, one scale VGPR per fragment set.
 //   Every wave issues 9 LDS-DMA instructions per K tile (1 scale + 8 data), so the counted waits are 11 / 8 / 12 / 11
 //   instead of 10 (derivation at MC_TILE).
+//
+// Rows: any M > 0.  tilesM = ceil(M / 256); a partial last tile clamps the A rows its LDS-DMA reads to M - 1, per half and
+// piece (no byte of A behind row M - 1 is read), reads scale bytes up to the next multiple of 256 (contract: mx_rows_a >=
+// ceil256(M), whatever those bytes hold) and every epilogue skips the rows m >= M.  Every output row depends on its own A
+// row and that row's scale bytes only -- an MFMA keeps the rows of its activation operand apart --, so rows >= M of A and
+// their scale bytes never reach a stored value, and a launch over M rows gives rows [0, M) the bits a launch over ceil256(M)
+// rows gives them.
 // the LDS-DMA asm below names m0 in its clobber list on purpose (reserved register: the compiler only warns)
 #pragma clang diagnostic ignored "-Winline-asm"
 #include "common.h"
@@ -94,16 +101,31 @@ __global__ __launch_bounds__(512, 2) void gemm_mx_kernel(GemmParams p, int tiles
   // same 128 bytes as a bf16 row of 64 k)
   const uint8_t* Aq = (const uint8_t*)p.A;
   const uint8_t* Wq = (const uint8_t*)p.W;
-  // (M is a multiple of 256 here, so the second half of an operand is a uniform 64 / 32 rows further: scalar base)
+  // One LDS-DMA instruction moves 8 consecutive rows (lane / 8) of a half, from a wave-uniform first row: the lane part of
+  // the source, row (lane / 8) and its swizzled chunk, is the same VGPR for both halves, the first row rides in the scalar
+  // base.  Row guard (any M): the first row is clamped to M - 1 and the lane part to lim = (rows of the 8 that exist - 1) *
+  // lda + 112 -- a lane whose row is behind M - 1 then reads chunk 7 of the last row that exists (lda >= K >= 512, so every lane
+  // part of an existing row is <= lim and of a missing row > lim).  No byte behind row M - 1 is read; what the missing rows
+  // receive feeds accumulators the epilogue never stores.  A full tile has lim = 7 lda + 112: the clamp changes nothing.
+  // W has whole tiles (N % 256 == 0): its second half is a uniform 32 rows further.
   uint32_t srcA[2], srcW[2];
+  size_t baseA[2][2];   // [half][piece] byte offset of the piece's first row
+  uint32_t limA[2][2];
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
-    const int r = (wv * 2 + j) * 8 + (lane >> 3);
+    const int r0 = (wv * 2 + j) * 8;
+    const int r = r0 + (lane >> 3);
     const int chunk = (lane & 7) ^ ((r >> 1) & 7);
-    srcA[j] = (uint32_t)(m0 + (r >> 6) * 128 + (r & 63)) * (uint32_t)p.lda + chunk * 16;
+    srcA[j] = (uint32_t)(lane >> 3) * (uint32_t)p.lda + chunk * 16;
     srcW[j] = (uint32_t)(n0 + (r >> 5) * 64 + (r & 31)) * (uint32_t)p.ldw + chunk * 16;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int row = __builtin_amdgcn_readfirstlane(min(m0 + (r0 >> 6) * 128 + h * 64 + (r0 & 63), p.M - 1));
+      baseA[h][j] = (size_t)row * p.lda;
+      limA[h][j] = (uint32_t)(min(p.M - row, 8) - 1) * (uint32_t)p.lda + 112;
+    }
   }
-  const size_t halfA = (size_t)64 * p.lda, halfW = (size_t)32 * p.ldw;
+  const size_t halfW = (size_t)32 * p.ldw;
   const uint32_t lds0 = (uint32_t)(uintptr_t)MC_LDS_PTR(smem);
   const uint32_t dma_lds = lds0 + wv * 2048;
   // ---- the scale piece of this wave: waves 0..3 the A scales of k block wv, waves 4..7 the W scales of k block wv - 4;
@@ -152,8 +174,18 @@ __global__ __launch_bounds__(512, 2) void gemm_mx_kernel(GemmParams p, int tiles
         : "v"(off), "s"(lds), "s"(base)
         : "memory", "m0");
   };
+  // (the clamp sits inside the asm: as C++ it is loop invariant and the compiler keeps the four clamped offsets in
+  // VGPRs this kernel does not have; the v_min also fills the wait state between the m0 write and its use)
   auto dma_a1 = [&](int kt, int st, int h, int j) {
-    dma1(Aq + (size_t)kt * BKB + (h ? halfA : 0), srcA[j], dma_lds + st * STAGE_BYTES + (h ? OFF_AM1 : OFF_AM0) + j * 1024);
+    uint32_t off;
+    asm volatile(
+        "s_mov_b32 m0, %2\n\t"
+        "v_min_u32 %0, %4, %1\n\t"
+        "global_load_lds_dwordx4 %0, %3"
+        : "=&v"(off)
+        : "v"(srcA[j]), "s"(dma_lds + st * STAGE_BYTES + (h ? OFF_AM1 : OFF_AM0) + j * 1024),
+          "s"(Aq + (size_t)kt * BKB + baseA[h][j]), "s"(limA[h][j])
+        : "memory", "m0");
   };
   auto dma_w1 = [&](int kt, int st, int h, int j) {
     dma1(Wq + (size_t)kt * BKB + (h ? halfW : 0), srcW[j], dma_lds + st * STAGE_BYTES + (h ? OFF_WN1 : OFF_WN0) + j * 1024);
@@ -290,7 +322,8 @@ __global__ __launch_bounds__(512, 2) void gemm_mx_kernel(GemmParams p, int tiles
 #undef MC_RD_A
   asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");   // XDL write -> VALU read of the accumulators (asm MFMAs)
 
-  // ---- epilogue: identical to gemm_bf16_big.hip
+  // ---- epilogue: identical to gemm_bf16_big.hip; rows m >= M of a partial last tile are skipped (the lanes of one row, l15,
+  // skip together: the shuffles of EPI_GELU_MXFP8 stay among active lanes)
 #pragma unroll
   for (int mh = 0; mh < 2; ++mh) {
 #pragma unroll
@@ -419,7 +452,7 @@ __global__ __launch_bounds__(256) void quantize_rows_mx_kernel(const bf16_t* __r
 }  // namespace
 
 bool gemm_mxfp8_supported(const GemmParams& p) {
-  return p.M > 0 && p.N > 0 && (p.M % TB) == 0 && (p.N % TB) == 0 && (p.K % (2 * BKB)) == 0 && p.K >= 4 * BKB && (p.lda % 16) == 0 &&
+  return p.M > 0 && p.N > 0 && (p.N % TB) == 0 && (p.K % (2 * BKB)) == 0 && p.K >= 4 * BKB && (p.lda % 16) == 0 &&
          (p.ldw % 16) == 0 && (size_t)p.M * (size_t)p.lda < (1ull << 32) && (size_t)p.N * (size_t)p.ldw < (1ull << 32) &&
          p.a_mx && p.w_mx && p.mx_rows_a >= (long)((p.M + TB - 1) / TB) * TB && p.mx_rows_w >= p.N &&
          (p.mx_rows_a % 64) == 0 && (p.mx_rows_w % 64) == 0;

@@ -29,6 +29,16 @@
 //                           branch, residual0..3 with calibration), joint row index: the
 //                           capture is the epilogue of the LAST block's output GEMM (R = x_new - x0 per row); the image
 //                           rows are the cache, the text rows are scratch
+//   aq   e4m3 [S_pad, 5d]   (fp8_linear != 0 only) the quantised operand rows of the MX Linears, joint row index, columns as
+//                           "am": [0,d) the LayerNorm + modulate output (q|k|v, MLP-in, the single block's linear1) and, mode
+//                           3, the attention output (the output projections); [d,5d) GELU(MLP-in), MLP-out's operand
+//   a_mx E8M0               (fp8_linear != 0 only) the block scales of "aq".  A scale image is block-major [k / 32][rows_pad]
+//                           with the rows of every group of 64 interleaved RELATIVE TO THE LAUNCH'S FIRST ROW, so two row
+//                           ranges must not share one: three regions, [text | image | joint (the single blocks)], each
+//                           rows_pad = ceil256(rows of the range) long per k block and 5d/32 k blocks deep in "aq"'s column
+//                           order (block d/32 starts the GELU columns); mode 3 adds d/32 blocks behind them in the text and
+//                           the image region for the rows the output projections read (the single block's K = 5d output
+//                           projection reads the joint region's whole image)
 // GEMMs over one stream use the exact row count (the 256^2 kernel guards a partial last tile), so neighbouring
 // rows of the other stream are never touched.
 //
@@ -37,6 +47,9 @@
 // (a second Linear makes it the row-split launch over two row ranges); a double block is double_pre / double_post over one
 // or two row ranges (Range) -- both streams in merged launches by default, one stream per call for the two-stream modes and
 // sequence parallel; every attention launch is attend() over a key set (Keys).
+// fp8_linear 2 / 3 (opt-in): the block Linears that read a LayerNorm or GELU output (3: the attention output too) keep an
+// e4m3 copy with MX block scales and run on launch_gemm_mxfp8 over the exact rows of ONE range (the kernel guards a partial
+// last tile and has no row-split launch): a double block is then one pass per stream, in row order, on the launch stream.
 #include <cmath>
 #include <memory>
 
@@ -86,6 +99,7 @@ struct mc_mmdit {
   int txt_valid = 0, dst = 0, local_attn_blk = -1;
   int branch = 0;                                            // CFG branch of the forward in progress (Qwen-Image: 0 / 1)
   bool begun = false;
+  int fp8 = 0;                                               // cfg.fp8_linear: 0 | 2 | 3
   // optional second compute stream: the text stream of a double block next to the image stream (mc_set_option
   // "mmdit_two_streams"); a ring of event pairs so that an event is not re-recorded while an earlier wait on it may
   // still be queued
@@ -127,20 +141,90 @@ struct mc_mmdit {
 
 namespace {
 
+// The e4m3 rows [M, k_in] an MX Linear reads, with their scale image (rows_pad >= ceil256(M) rows per k block)
+struct MxRows {
+  const uint8_t* q; long ld;
+  const uint8_t* mx; long rows_pad;
+};
+
 // Every GEMM of the engine: y = epilogue(A l.w^T + l.b) over M rows, operands and shape from the descriptor, p carrying what
 // the epilogue needs.  `lb` makes it the row-split launch over two row ranges of the same buffers: rows >= m_split use lb's
 // weight and bias and gate_b.  The split-K scratch of the stream it runs on rides along (launch_gemm_bf16 decides by shape
 // whether to use it: the projections back to d at FLUX sizes do, nothing at HunyuanVideo's 119 k tokens does).
+// A Linear with an MX copy reads `a8` instead of A, over one row range (no lb); `out`: a range of its output channels (count
+// 0 = all of them).
 mc_status linear(const mc_mmdit* e, const Linear& l, int M, const bf16_t* A, long lda, mc::GemmParams p, int epi, hipStream_t s,
-                 const Linear* lb = nullptr, int m_split = 0, const float* gate_b = nullptr) {
-  if (l.q || (lb && lb->q)) return fail(MC_ESTATE, "the MM-DiT engine has no fp8 Linears");
+                 const Linear* lb = nullptr, int m_split = 0, const float* gate_b = nullptr, const MxRows* a8 = nullptr,
+                 mc::RowRange out = {0, 0}) {
+  if (out.count == 0) out = mc::whole(l);
+  if (l.q) {
+    if (!l.mx || !a8 || lb) return fail(MC_ESTATE, "an MX Linear runs over one row range of quantised rows");
+    p.M = M; p.N = out.count; p.K = l.k_in; p.bias = l.b + out.first;
+    p.A = (const bf16_t*)a8->q; p.lda = a8->ld; p.W = (const bf16_t*)(l.q + (size_t)out.first * l.k_in); p.ldw = l.k_in;
+    p.a_mx = a8->mx; p.mx_rows_a = a8->rows_pad; p.w_mx = l.mx + out.first; p.mx_rows_w = l.n_out;   // block-major: [k / 32][n_out]
+    HIP_TRY(mc::launch_gemm_mxfp8(p, epi, s));
+    return MC_OK;
+  }
+  if (lb && lb->q) return fail(MC_ESTATE, "an MX Linear runs over one row range of quantised rows");
   const mc::Buf* b = e->work.find((e->side && s == e->side) ? "splitk1" : "splitk0");
   if (b && b->bytes > 0 && e->work.ws) {
     p.splitk_ws = reinterpret_cast<float*>(e->work.ws + b->off);
     p.splitk_ws_bytes = b->bytes;
   }
   if (lb) { p.m_split = m_split; p.W_b = lb->w; p.bias_b = lb->b; p.gate_b = gate_b; }
-  HIP_TRY(mc::launch_linear_bf16(l, mc::whole(l), A, lda, M, p, epi, s));
+  HIP_TRY(mc::launch_linear_bf16(l, out, A, lda, M, p, epi, s));
+  return MC_OK;
+}
+
+// ---- fp8_linear: where the quantised rows of a row range live ("aq" / "a_mx", layout at the top of the file)
+// The range's region of "a_mx": the text range, the image range or the joint range of the single blocks.
+struct MxRegion {
+  uint8_t* base; long rows_pad;
+};
+MxRegion mx_region(const mc_mmdit* e, int row0, int rows) {
+  const size_t Ltp = align_up(e->Lt, 256), Lip = align_up(e->Li, 256);
+  const size_t blocks = (size_t)5 * e->d / 32 + (e->fp8 == 3 ? e->d / 32 : 0);   // per text / image row
+  uint8_t* m = e->buf<uint8_t>("a_mx");
+  if (row0 == e->txt0 && rows == e->Lt) return {m, (long)Ltp};
+  if (row0 == e->img0 && rows == e->Li) return {m + blocks * Ltp, (long)Lip};
+  return {m + blocks * (Ltp + Lip), (long)e->Sp};   // rows [0, S)
+}
+// columns [col0, ..) of "aq" rows [row0, row0 + rows) with their scales; o_proj: the scales of the rows an output projection
+// of a double block reads (mode 3), behind the region's 5d/32 blocks
+struct MxDst {
+  uint8_t* q; long ld;
+  uint8_t* mx; long rows_pad;
+  MxRows rows() const { return {q, ld, mx, rows_pad}; }
+};
+MxDst mx_at(const mc_mmdit* e, int row0, int rows, int col0, bool o_proj = false) {
+  const MxRegion r = mx_region(e, row0, rows);
+  const size_t blk = o_proj ? (size_t)5 * e->d / 32 : (size_t)col0 / 32;
+  return {e->buf<uint8_t>("aq") + (size_t)row0 * 5 * e->d + col0, 5L * e->d, r.base + blk * r.rows_pad, r.rows_pad};
+}
+// bf16 rows -> their place in "aq" (the separate quantise pass: the attention output, and everything with fp8_fused_quant 0)
+mc_status mx_quantise(const mc_mmdit* e, const bf16_t* rows_bf16, long ld, int rows, int K, const MxDst& to, hipStream_t s) {
+  HIP_TRY(mc::launch_quantize_rows_mx(rows_bf16, nullptr, ld, rows, K, to.q, to.ld, to.mx, to.rows_pad, s));
+  return MC_OK;
+}
+// LayerNorm + modulate of "x" rows [row0, row0 + rows) as the operand of `l`: a bf16 Linear reads "xn"; an MX Linear reads
+// "aq"[:, 0:d] (*a8), written by the LayerNorm kernel itself or, fp8_fused_quant 0, quantised from "xn" (the same bits)
+mc_status ln_for_linear(const mc_mmdit* e, const Linear& l, int row0, int rows, const float* scale, const float* shift, MxRows* a8,
+                        hipStream_t s) {
+  const int d = e->d;
+  const float* x = e->buf<float>("x") + (size_t)row0 * d;
+  bf16_t* xn = e->buf<bf16_t>("xn") + (size_t)row0 * d;
+  if (l.mx && mc::g_fp8_fused_quant) {
+    const MxDst to = mx_at(e, row0, rows, 0);
+    *a8 = to.rows();
+    HIP_TRY(mc::launch_ln_modulate_fp8(x, d, scale, shift, 0, 1e-6f, to.q, to.ld, nullptr, to.mx, to.rows_pad, rows, d, s));
+    return MC_OK;
+  }
+  HIP_TRY(mc::launch_ln_modulate(x, d, nullptr, 0, scale, shift, 0, 1e-6f, xn, d, nullptr, 0, rows, d, s));
+  if (l.mx) {
+    const MxDst to = mx_at(e, row0, rows, 0);
+    *a8 = to.rows();
+    MC_TRY(mx_quantise(e, xn, d, rows, d, to, s));
+  }
   return MC_OK;
 }
 
@@ -247,6 +331,10 @@ void plan_workspace(const mc_mmdit* e, const Rows& r, mc::Workspace& ws) {
   ws.add("calib_partial", (2048 * 4 + 2) * 8);   // + the arrival ticket of calib_stats_kernel
   ws.add("calib_sums", 64);
   ws.add("calib_stats", 64);
+  if (c.fp8_linear) {   // behind everything else: the plan of a bf16 engine does not change
+    ws.add("aq", Sp * 5 * d);
+    ws.add("a_mx", (5 * d / 32 + (c.fp8_linear == 3 ? d / 32 : 0)) * (Ltp + align_up(Li, 256)) + 5 * d / 32 * Sp);
+  }
 }
 
 // (re)allocate the RoPE table for `rows` rows where it is shorter, and set every row to the identity rotation
@@ -276,9 +364,27 @@ mc_status forget_workspace_state(mc_mmdit* e) {
 
 extern "C" {
 
-mc_status mc_mmdit_create(const mc_mmdit_config* cfg, mc_mmdit** out) {
+// mc_mmdit_config only ever grows at its END, and a zero in a new field keeps the behaviour older callers had: a caller built
+// against an older header passes ITS sizeof(mc_mmdit_config) and the tail reads as zeros.  mc_mmdit_create is the entry
+// point of the first layout (up to sp_size) and reads no further.
+static mc_status create_engine(const mc_mmdit_config& c, mc_mmdit** out);
+
+mc_status mc_mmdit_create_sized(const mc_mmdit_config* cfg, size_t cfg_bytes, mc_mmdit** out) {
   if (!cfg || !out) return fail(MC_EINVAL, "null argument");
-  const mc_mmdit_config& c = *cfg;
+  if (cfg_bytes < offsetof(mc_mmdit_config, fp8_linear) || cfg_bytes > sizeof(mc_mmdit_config) || (cfg_bytes % sizeof(int)) != 0)
+    return fail(MC_EINVAL, "mc_mmdit_config of %zu bytes: this library knows %zu (first layout) .. %zu", cfg_bytes,
+                offsetof(mc_mmdit_config, fp8_linear), sizeof(mc_mmdit_config));
+  mc_mmdit_config full;
+  memset(&full, 0, sizeof(full));
+  memcpy(&full, cfg, cfg_bytes);
+  return create_engine(full, out);
+}
+
+mc_status mc_mmdit_create(const mc_mmdit_config* cfg, mc_mmdit** out) {
+  return mc_mmdit_create_sized(cfg, offsetof(mc_mmdit_config, fp8_linear), out);
+}
+
+static mc_status create_engine(const mc_mmdit_config& c, mc_mmdit** out) {
   const bool hy = c.family == MC_FAMILY_HUNYUAN;
   const bool qw = c.family == MC_FAMILY_QWEN;
   if (c.family != MC_FAMILY_FLUX && !hy && !qw) return fail(MC_EINVAL, "unknown family %d", c.family);
@@ -300,9 +406,15 @@ mc_status mc_mmdit_create(const mc_mmdit_config* cfg, mc_mmdit** out) {
   const Geometry geo = {c.img_tokens, c.latent_f, c.latent_h, c.latent_w, c.txt_len};
   const int P = c.sp_size > 0 ? c.sp_size : 1;
   MC_TRY(check_geometry(c, geo, P, c.sp_rank));
+  if (c.fp8_linear != 0 && c.fp8_linear != 2 && c.fp8_linear != 3)
+    return fail(MC_EINVAL, "fp8_linear must be 0, 2 (MX block scales: q|k|v, MLP-in, MLP-out, the single block's linear1) or 3 "
+                           "(MX, the output projections too); 1 (per-row scales) has no MM-DiT path");
+  if (c.fp8_linear && c.dim < 512) return fail(MC_EINVAL, "fp8_linear needs dim >= 512 (dim %d)", c.dim);
+  if (c.fp8_linear && P > 1) return fail(MC_EINVAL, "fp8_linear runs on one GPU (sp_size %d)", P);
   std::unique_ptr<mc_mmdit, void (*)(mc_mmdit*)> own(new mc_mmdit(), mc_mmdit_destroy);   // every early return frees it
   mc_mmdit* e = own.get();
   e->cfg = c;
+  e->fp8 = c.fp8_linear;
   e->P = P;
   e->rank = c.sp_rank;
   e->d = c.dim; e->H = c.num_heads;
@@ -314,6 +426,11 @@ mc_status mc_mmdit_create(const mc_mmdit_config* cfg, mc_mmdit** out) {
   const size_t d = e->d;
   const bool flux = c.family == MC_FAMILY_FLUX;
   mc::WeightStore& W = e->weights;
+  // fp8_linear only decides which Linears keep an e4m3 copy with MX block scales: 2 = those that read a LayerNorm or GELU
+  // output, 3 = those that read the attention output too.  The embedders, the modulation matrix, the token refiner and the
+  // head stay bf16.
+  const mc::Quant q_big = c.fp8_linear >= 2 ? mc::QUANT_MX : mc::QUANT_NONE;
+  const mc::Quant q_out = c.fp8_linear == 3 ? mc::QUANT_MX : mc::QUANT_NONE;
   auto vec128 = [&](float*& v, const std::string& name) { return W.add_f32(v, name, 128); };   // a per-head norm weight
   auto mlp2 = [&](Mlp2& m, size_t k_in, const std::string& l1, const std::string& l2) {
     MC_TRY(W.add_linear(m.l1, l1, {{"", d}}, k_in));
@@ -371,10 +488,10 @@ mc_status mc_mmdit_create(const mc_mmdit_config* cfg, mc_mmdit** out) {
       if (hy) {
         const std::string q = p + (k ? "txt" : "img");
         W.add_parts(e->mod, q, {{"_mod.linear", 6 * d}}, e->mod_double(i, k));
-        MC_TRY(W.add_linear(t.qkv, q, {{"_attn_qkv", 3 * d}}, d));
-        MC_TRY(W.add_linear(t.o, q, {{"_attn_proj", d}}, d));
-        MC_TRY(W.add_linear(t.fc1, q, {{"_mlp.fc1", 4 * d}}, d));
-        MC_TRY(W.add_linear(t.fc2, q, {{"_mlp.fc2", d}}, 4 * d));
+        MC_TRY(W.add_linear(t.qkv, q, {{"_attn_qkv", 3 * d}}, d, q_big));
+        MC_TRY(W.add_linear(t.o, q, {{"_attn_proj", d}}, d, q_out));
+        MC_TRY(W.add_linear(t.fc1, q, {{"_mlp.fc1", 4 * d}}, d, q_big));
+        MC_TRY(W.add_linear(t.fc2, q, {{"_mlp.fc2", d}}, 4 * d, q_big));
         MC_TRY(vec128(t.qn, q + "_attn_q_norm.weight"));
         MC_TRY(vec128(t.kn, q + "_attn_k_norm.weight"));
       } else {
@@ -382,11 +499,11 @@ mc_status mc_mmdit_create(const mc_mmdit_config* cfg, mc_mmdit** out) {
         const std::string ff = qw ? (k ? "txt_mlp" : "img_mlp") : (k ? "ff_context" : "ff");
         W.add_parts(e->mod, p, {{qw ? (k ? "txt_mod.1" : "img_mod.1") : (k ? "norm1_context.linear" : "norm1.linear"), 6 * d}},
                     e->mod_double(i, k));
-        if (k) MC_TRY(W.add_linear(t.qkv, p, {{"attn.add_q_proj", d}, {"attn.add_k_proj", d}, {"attn.add_v_proj", d}}, d));
-        else MC_TRY(W.add_linear(t.qkv, p, {{"attn.to_q", d}, {"attn.to_k", d}, {"attn.to_v", d}}, d));
-        MC_TRY(W.add_linear(t.o, p, {{k ? "attn.to_add_out" : "attn.to_out.0", d}}, d));
-        MC_TRY(W.add_linear(t.fc1, p, {{ff + ".net.0.proj", 4 * d}}, d));
-        MC_TRY(W.add_linear(t.fc2, p, {{ff + ".net.2", d}}, 4 * d));
+        if (k) MC_TRY(W.add_linear(t.qkv, p, {{"attn.add_q_proj", d}, {"attn.add_k_proj", d}, {"attn.add_v_proj", d}}, d, q_big));
+        else MC_TRY(W.add_linear(t.qkv, p, {{"attn.to_q", d}, {"attn.to_k", d}, {"attn.to_v", d}}, d, q_big));
+        MC_TRY(W.add_linear(t.o, p, {{k ? "attn.to_add_out" : "attn.to_out.0", d}}, d, q_out));
+        MC_TRY(W.add_linear(t.fc1, p, {{ff + ".net.0.proj", 4 * d}}, d, q_big));
+        MC_TRY(W.add_linear(t.fc2, p, {{ff + ".net.2", d}}, 4 * d, q_big));
         MC_TRY(vec128(t.qn, p + (k ? "attn.norm_added_q.weight" : "attn.norm_q.weight")));
         MC_TRY(vec128(t.kn, p + (k ? "attn.norm_added_k.weight" : "attn.norm_k.weight")));
       }
@@ -398,11 +515,11 @@ mc_status mc_mmdit_create(const mc_mmdit_config* cfg, mc_mmdit** out) {
     const std::string p = (flux ? "single_transformer_blocks." : "single_blocks.") + std::to_string(i) + ".";
     W.add_parts(e->mod, p, {{flux ? "norm.linear" : "modulation.linear", 3 * d}}, e->mod_single(i));
     if (flux) {
-      MC_TRY(W.add_linear(g.in, p, {{"attn.to_q", d}, {"attn.to_k", d}, {"attn.to_v", d}, {"proj_mlp", 4 * d}}, d));
-      MC_TRY(W.add_linear(g.out, p, {{"proj_out", d}}, 5 * d));
+      MC_TRY(W.add_linear(g.in, p, {{"attn.to_q", d}, {"attn.to_k", d}, {"attn.to_v", d}, {"proj_mlp", 4 * d}}, d, q_big));
+      MC_TRY(W.add_linear(g.out, p, {{"proj_out", d}}, 5 * d, q_out));
     } else {
-      MC_TRY(W.add_linear(g.in, p, {{"linear1", 7 * d}}, d));
-      MC_TRY(W.add_linear(g.out, p, {{"linear2", d}}, 5 * d));
+      MC_TRY(W.add_linear(g.in, p, {{"linear1", 7 * d}}, d, q_big));
+      MC_TRY(W.add_linear(g.out, p, {{"linear2", d}}, 5 * d, q_out));
     }
     MC_TRY(vec128(g.qn, p + (flux ? "attn.norm_q.weight" : "q_norm.weight")));
     MC_TRY(vec128(g.kn, p + (flux ? "attn.norm_k.weight" : "k_norm.weight")));
@@ -621,7 +738,7 @@ struct Range {
   int row0, rows;
 };
 bool double_block_merged(const mc_mmdit* e) {
-  return g_mmdit_two_streams == 0 && e->P == 1 && e->Lt > 0 && e->Li > 0;
+  return g_mmdit_two_streams == 0 && e->P == 1 && e->Lt > 0 && e->Li > 0 && !e->fp8;
 }
 
 // the two streams of block `blk` as adjacent ranges in row order; img / txt: which of them is which
@@ -639,26 +756,26 @@ TwoStreams two_streams(const mc_mmdit* e, int blk, const float* emod) {
 }
 
 // one Linear of the block over all n ranges: rows from r[0].row0 on, row-split at the range boundary when n = 2
+// (a8: the quantised rows of r[0] when the Linear is MX -- an fp8 engine runs a block one range at a time, n = 1)
 mc_status range_linear(const mc_mmdit* e, const Range* r, int n, Linear Stream::*l, const bf16_t* A, long lda, const mc::GemmParams& p,
-                       int epi, const float* gate_b, hipStream_t s) {
+                       int epi, const float* gate_b, hipStream_t s, const MxRows* a8 = nullptr) {
   const int rows = r[0].rows + (n == 2 ? r[1].rows : 0);
-  return linear(e, r[0].w->*l, rows, A, lda, p, epi, s, n == 2 ? &(r[1].w->*l) : nullptr, r[0].rows, gate_b);
+  return linear(e, r[0].w->*l, rows, A, lda, p, epi, s, n == 2 ? &(r[1].w->*l) : nullptr, r[0].rows, gate_b, a8);
 }
 
 // before the joint attention: LN + modulate, QKV, per-head q/k norm, RoPE
 // phases (diagnostic split, tests/two_stream_bisect.py): 1 = LN + QKV GEMM, 2 = head norm + RoPE, 3 = both
 mc_status double_pre(const mc_mmdit* e, const Range* r, int n, hipStream_t s, int phases = 3) {
   const int d = e->d;
-  float* x = e->buf<float>("x");
   bf16_t* xn = e->buf<bf16_t>("xn");
   bf16_t* qkv = e->buf<bf16_t>("qkv");
   if (phases & 1) {
+    MxRows a8 = {};
     for (int i = 0; i < n; ++i)
-      HIP_TRY(mc::launch_ln_modulate(x + (size_t)r[i].row0 * d, d, nullptr, 0, r[i].mod + d, r[i].mod, 0, 1e-6f,
-                                     xn + (size_t)r[i].row0 * d, d, nullptr, 0, r[i].rows, d, s));
+      MC_TRY(ln_for_linear(e, r[i].w->qkv, r[i].row0, r[i].rows, r[i].mod + d, r[i].mod, &a8, s));
     mc::GemmParams p = {};
     p.Cb = qkv + (size_t)r[0].row0 * 3 * d; p.ldc = 3 * d;
-    MC_TRY(range_linear(e, r, n, &Stream::qkv, xn + (size_t)r[0].row0 * d, d, p, mc::EPI_BF16, nullptr, s));
+    MC_TRY(range_linear(e, r, n, &Stream::qkv, xn + (size_t)r[0].row0 * d, d, p, mc::EPI_BF16, nullptr, s, &a8));
   }
   if (phases & 2)
     for (int i = 0; i < n; ++i)
@@ -672,23 +789,41 @@ mc_status double_pre(const mc_mmdit* e, const Range* r, int n, hipStream_t s, in
 // rows fused into the MLP-out epilogue (joint row index; the text rows of R are scratch, as in the single blocks)
 mc_status double_post(const mc_mmdit* e, const Range* r, int n, hipStream_t s, float* capture_to) {
   const int d = e->d;
-  float* x = e->buf<float>("x");
   bf16_t* xn = e->buf<bf16_t>("xn");
   bf16_t* am = e->buf<bf16_t>("am");
   const float* mod_b = n == 2 ? r[1].mod : nullptr;
   mc::GemmParams o = {}, f2 = {};
+  MxRows a_o = {}, a_f1 = {}, a_f2 = {};
+  if (r[0].w->o.mx) {   // mode 3: the attention output rows, quantised
+    const MxDst to = mx_at(e, r[0].row0, r[0].rows, 0, true);
+    a_o = to.rows();
+    MC_TRY(mx_quantise(e, am + (size_t)r[0].row0 * 5 * d, 5 * d, r[0].rows, d, to, s));
+  }
   const int epi_o = resid_epi(e, o, r[0].row0, r[0].mod + 2 * d, nullptr);
-  MC_TRY(range_linear(e, r, n, &Stream::o, am + (size_t)r[0].row0 * 5 * d, 5 * d, o, epi_o, mod_b ? mod_b + 2 * d : nullptr, s));
+  MC_TRY(range_linear(e, r, n, &Stream::o, am + (size_t)r[0].row0 * 5 * d, 5 * d, o, epi_o, mod_b ? mod_b + 2 * d : nullptr, s, &a_o));
   for (int i = 0; i < n; ++i)
-    HIP_TRY(mc::launch_ln_modulate(x + (size_t)r[i].row0 * d, d, nullptr, 0, r[i].mod + 4 * d, r[i].mod + 3 * d, 0, 1e-6f,
-                                   xn + (size_t)r[i].row0 * d, d, nullptr, 0, r[i].rows, d, s));
+    MC_TRY(ln_for_linear(e, r[i].w->fc1, r[i].row0, r[i].rows, r[i].mod + 4 * d, r[i].mod + 3 * d, &a_f1, s));
   for (int i = 0; i < n; ++i) {
     mc::GemmParams f1 = {};
     f1.Cb = am + (size_t)r[i].row0 * 5 * d + d; f1.ldc = 5 * d;
-    MC_TRY(linear(e, r[i].w->fc1, r[i].rows, xn + (size_t)r[i].row0 * d, d, f1, mc::EPI_GELU_BF16, s));
+    int epi_f1 = mc::EPI_GELU_BF16;
+    if (r[i].w->fc2.mx) {   // MLP-out's operand: "aq"[:, d:5d], written by MLP-in's epilogue or quantised from "am"[:, d:5d]
+      const MxDst to = mx_at(e, r[i].row0, r[i].rows, d);
+      a_f2 = to.rows();
+      if (r[i].w->fc1.mx && mc::g_fp8_fused_quant) {
+        f1.Cq = to.q; f1.ldcq = to.ld; f1.c_mx = to.mx; f1.mx_rows_c = to.rows_pad;
+        epi_f1 = mc::EPI_GELU_MXFP8;
+      }
+    }
+    MC_TRY(linear(e, r[i].w->fc1, r[i].rows, xn + (size_t)r[i].row0 * d, d, f1, epi_f1, s, nullptr, 0, nullptr, &a_f1));
+    if (r[i].w->fc2.mx && epi_f1 != mc::EPI_GELU_MXFP8) {
+      const MxDst to = mx_at(e, r[i].row0, r[i].rows, d);
+      MC_TRY(mx_quantise(e, am + (size_t)r[i].row0 * 5 * d + d, 5 * d, r[i].rows, 4 * d, to, s));
+    }
   }
   const int epi_f2 = resid_epi(e, f2, r[0].row0, r[0].mod + 5 * d, capture_to);
-  return range_linear(e, r, n, &Stream::fc2, am + (size_t)r[0].row0 * 5 * d + d, 5 * d, f2, epi_f2, mod_b ? mod_b + 5 * d : nullptr, s);
+  return range_linear(e, r, n, &Stream::fc2, am + (size_t)r[0].row0 * 5 * d + d, 5 * d, f2, epi_f2, mod_b ? mod_b + 5 * d : nullptr, s,
+                      &a_f2);
 }
 
 // Image stream and text stream of a double block touch disjoint rows of every buffer: with "mmdit_two_streams" the text
@@ -889,7 +1024,10 @@ mc_status mc_mmdit_block_pre(mc_mmdit* e, int blk, mc_stream stream_) {
     auto img = [&](hipStream_t q, int ph) { return double_pre(e, &t.r[t.img], 1, q, ph); };
     auto txt = [&](hipStream_t q, int ph) { return double_pre(e, &t.r[t.txt], 1, q, ph); };
     const int mode = g_mmdit_two_streams;
-    if (double_block_merged(e)) {
+    if (e->fp8) {   // one range at a time, in row order, on the launch stream whatever "mmdit_two_streams" says
+      MC_TRY(double_pre(e, &t.r[0], 1, s));
+      MC_TRY(double_pre(e, &t.r[1], 1, s));
+    } else if (double_block_merged(e)) {
       MC_TRY(double_pre(e, t.r, 2, s));
     } else if (mode <= 2) {
       MC_TRY(run_two(e, s, mode, [&](hipStream_t q) { return img(q, 3); }, [&](hipStream_t q) { return txt(q, 3); }));
@@ -915,17 +1053,32 @@ mc_status mc_mmdit_block_pre(mc_mmdit* e, int blk, mc_stream stream_) {
     const int i = blk - c.n_double;
     const Single& g = e->singles[i];
     const float* m = emod + e->mod_single(i);
-    float* x = e->buf<float>("x");
     bf16_t* xn = e->buf<bf16_t>("xn");
     bf16_t* am = e->buf<bf16_t>("am");
-    HIP_TRY(mc::launch_ln_modulate(x, d, nullptr, 0, m + d, m, 0, 1e-6f, xn, d, nullptr, 0, S, d, s));
-    // linear1 of the single block = [q | k | v ; MLP-in] over the same rows: ONE launch with two destinations (the q|k|v
-    // columns to "qkv", the GELU'd MLP columns to "am"[:, d:]) -- 504 tiles at FLUX 512^2 are two trips of the 256 CUs, the
-    // two launches were 216 + 288 = one + two
+    MxRows a8 = {};
+    MC_TRY(ln_for_linear(e, g.in, 0, S, m + d, m, &a8, s));
     mc::GemmParams p = {};
     p.Cb = qkv; p.ldc = 3 * d;
-    p.n_split = 3 * d; p.Cb2 = am + d; p.ldc2 = 5 * d;
-    MC_TRY(linear(e, g.in, S, xn, d, p, mc::EPI_BF16_GELU_SPLIT, s));
+    if (g.in.mx) {
+      // MX has no two-destination epilogue: two launches over row ranges of the fused weight, q|k|v into "qkv" and the GELU'd
+      // MLP-in columns into "am"[:, d:] -- or, mode 3 with fused quantisers, straight into the output projection's operand
+      MC_TRY(linear(e, g.in, S, nullptr, 0, p, mc::EPI_BF16, s, nullptr, 0, nullptr, &a8, {0, 3 * d}));
+      mc::GemmParams f = {};
+      f.Cb = am + d; f.ldc = 5 * d;
+      int epi = mc::EPI_GELU_BF16;
+      if (g.out.mx && mc::g_fp8_fused_quant) {
+        const MxDst to = mx_at(e, 0, S, d);
+        f.Cq = to.q; f.ldcq = to.ld; f.c_mx = to.mx; f.mx_rows_c = to.rows_pad;
+        epi = mc::EPI_GELU_MXFP8;
+      }
+      MC_TRY(linear(e, g.in, S, nullptr, 0, f, epi, s, nullptr, 0, nullptr, &a8, {3 * d, 4 * d}));
+    } else {
+      // linear1 of the single block = [q | k | v ; MLP-in] over the same rows: ONE launch with two destinations (the q|k|v
+      // columns to "qkv", the GELU'd MLP columns to "am"[:, d:]) -- 504 tiles at FLUX 512^2 are two trips of the 256 CUs, the
+      // two launches were 216 + 288 = one + two
+      p.n_split = 3 * d; p.Cb2 = am + d; p.ldc2 = 5 * d;
+      MC_TRY(linear(e, g.in, S, xn, d, p, mc::EPI_BF16_GELU_SPLIT, s));
+    }
     HIP_TRY(mc::launch_headnorm_rope(qkv, 3 * d, d, g.qn, g.kn, 1e-6f, e->cs, 0, S, e->H, s));
   }
   if (e->P > 1) {
@@ -984,7 +1137,10 @@ mc_status mc_mmdit_block_post(mc_mmdit* e, int blk, mc_stream stream_) {
   float* capture_to = capture ? e->residual_joint(e->dst, e->branch) : nullptr;
   if (blk < c.n_double) {
     const TwoStreams t = two_streams(e, blk, emod);
-    if (double_block_merged(e)) {
+    if (e->fp8) {
+      MC_TRY(double_post(e, &t.r[0], 1, s, capture_to));
+      MC_TRY(double_post(e, &t.r[1], 1, s, capture_to));
+    } else if (double_block_merged(e)) {
       MC_TRY(double_post(e, t.r, 2, s, capture_to));
     } else {
       MC_TRY(run_two(
@@ -996,7 +1152,17 @@ mc_status mc_mmdit_block_post(mc_mmdit* e, int blk, mc_stream stream_) {
     const int i = blk - c.n_double;
     mc::GemmParams o = {};   // MagCache residual capture (flux :428, hunyuan :140); the text rows of R are scratch
     const int epi = resid_epi(e, o, 0, emod + e->mod_single(i) + 2 * d, capture_to);
-    MC_TRY(linear(e, e->singles[i].out, S, e->buf<bf16_t>("am"), 5 * d, o, epi, s));
+    const Single& g = e->singles[i];
+    bf16_t* am = e->buf<bf16_t>("am");
+    MxRows a8 = {};
+    if (g.out.mx) {
+      // mode 3: the K = 5d operand [attention | GELU(MLP-in)] in "aq"; with fused quantisers linear1's epilogue wrote the
+      // GELU columns and their scales already, so only the attention columns are quantised here
+      const MxDst to = mx_at(e, 0, S, 0);
+      a8 = to.rows();
+      MC_TRY(mx_quantise(e, am, 5 * d, S, (g.in.mx && mc::g_fp8_fused_quant) ? d : 5 * d, to, s));
+    }
+    MC_TRY(linear(e, g.out, S, am, 5 * d, o, epi, s, nullptr, 0, nullptr, &a8));
   }
   if (cn) MC_TRY(controlnet_add(e, cn, last, s));
   if (last) {

@@ -54,7 +54,8 @@ class MMDiTEngine:
 
     def __init__(self, family, dim, num_heads, n_double, n_single, in_channels, out_channels, txt_dim, txt_len, vec_dim,
                  img_tokens, latent_grid=(0, 0, 0), refiner_depth=0, calibration=False, device="cuda:0", sp_rank=0,
-                 sp_size=1):
+                 sp_size=1, fp8_linear=0):
+        """fp8_linear: 0 bf16 Linears; 2 / 3 the opt-in MX fp8 modes of mc_mmdit_config.fp8_linear (one GPU, dim >= 512)"""
         if not torch.cuda.is_available():
             raise RuntimeError("magcache_amd.MMDiTEngine needs a ROCm device; there is no CPU fallback")
         self.lib = _lib.load()
@@ -63,14 +64,15 @@ class MMDiTEngine:
         self.family, self.dim, self.img_tokens, self.txt_len = family, dim, img_tokens, txt_len
         self.out_channels, self.latent_grid = out_channels, tuple(latent_grid)
         self.sp_rank, self.sp_size, self.n_blocks = sp_rank, sp_size, n_double + n_single
+        self.fp8_linear = int(fp8_linear)
         self.tokens_per_rank = img_tokens // sp_size
         c = McMmditConfig(family=family, dim=dim, num_heads=num_heads, n_double=n_double, n_single=n_single,
                           in_channels=in_channels, out_channels=out_channels, txt_dim=txt_dim, txt_len=txt_len,
                           vec_dim=vec_dim, img_tokens=img_tokens, latent_f=latent_grid[0], latent_h=latent_grid[1],
                           latent_w=latent_grid[2], refiner_depth=refiner_depth, calibration=int(calibration),
-                          sp_rank=sp_rank, sp_size=sp_size)
+                          sp_rank=sp_rank, sp_size=sp_size, fp8_linear=int(fp8_linear))
         h = C.c_void_p()
-        check(self.lib.mc_mmdit_create(C.byref(c), C.byref(h)))
+        check(self.lib.mc_mmdit_create_sized(C.byref(c), C.sizeof(c), C.byref(h)))
         self.h = h
         self._bind(self.lib.mc_mmdit_workspace_bytes(self.h))
         self._rope_key = None
@@ -373,7 +375,7 @@ class FluxTransformer2DModelHIP:
     dynamic_geometry = False
 
     def __init__(self, cfg, img_tokens, txt_len=512, device="cuda:0", calibration=True, engine=None, sp_rank=0,
-                 sp_size=1, sp_group=None, dynamic_geometry=False):
+                 sp_size=1, sp_group=None, dynamic_geometry=False, fp8_linear=0):
         self.config = SimpleNamespace(**cfg)
         self.cfg = dict(cfg)
         dim = cfg["attention_head_dim"] * cfg["num_attention_heads"]
@@ -383,7 +385,8 @@ class FluxTransformer2DModelHIP:
         self.engine = engine or MMDiTEngine(MC_FAMILY_FLUX, dim, cfg["num_attention_heads"], cfg["num_layers"],
                                             cfg["num_single_layers"], cfg["in_channels"], cfg["in_channels"],
                                             cfg["joint_attention_dim"], txt_len, cfg["pooled_projection_dim"], img_tokens,
-                                            calibration=calibration, device=device, sp_rank=sp_rank, sp_size=sp_size)
+                                            calibration=calibration, device=device, sp_rank=sp_rank, sp_size=sp_size,
+                                            fp8_linear=fp8_linear)
         self.device = self.engine.device
         self.sp_group = sp_group
         self._ids_key = None
@@ -561,7 +564,7 @@ class HYVideoDiffusionTransformerHIP:
     dynamic_geometry = False
 
     def __init__(self, cfg, latent_grid, txt_len=256, device="cuda:0", calibration=True, engine=None, sp_rank=0,
-                 sp_size=1, sp_group=None, dynamic_geometry=False):
+                 sp_size=1, sp_group=None, dynamic_geometry=False, fp8_linear=0):
         self.cfg = dict(cfg)
         self.sp_group = sp_group
         self.dynamic_geometry = dynamic_geometry
@@ -577,7 +580,8 @@ class HYVideoDiffusionTransformerHIP:
                                             cfg["mm_double_blocks_depth"], cfg["mm_single_blocks_depth"], cfg["in_channels"],
                                             cfg["out_channels"], cfg["text_states_dim"], txt_len, cfg["text_states_dim_2"],
                                             self.img_tokens, latent_grid=self.latent_grid, refiner_depth=2,
-                                            calibration=calibration, device=device, sp_rank=sp_rank, sp_size=sp_size)
+                                            calibration=calibration, device=device, sp_rank=sp_rank, sp_size=sp_size,
+                                            fp8_linear=fp8_linear)
         self.device = self.engine.device
 
     def load_state_dict(self, sd):
@@ -749,7 +753,7 @@ class QwenImageTransformer2DModelHIP:
     dynamic_geometry = False
 
     def __init__(self, cfg, img_tokens, txt_len=1024, device="cuda:0", calibration=True, engine=None, sp_size=1,
-                 dynamic_geometry=False):
+                 dynamic_geometry=False, fp8_linear=0):
         self.config = SimpleNamespace(**cfg)
         self.cfg = dict(cfg)
         self.dynamic_geometry = dynamic_geometry
@@ -759,7 +763,7 @@ class QwenImageTransformer2DModelHIP:
         self.inner_dim, self.img_tokens, self.txt_len, self.out_features = dim, img_tokens, txt_len, out
         self.engine = engine or MMDiTEngine(MC_FAMILY_QWEN, dim, cfg["num_attention_heads"], cfg["num_layers"], 0,
                                             cfg["in_channels"], out, cfg["joint_attention_dim"], txt_len, 0, img_tokens,
-                                            calibration=calibration, device=device, sp_size=sp_size)
+                                            calibration=calibration, device=device, sp_size=sp_size, fp8_linear=fp8_linear)
         self.device = self.engine.device
         self._shapes_key = None
 

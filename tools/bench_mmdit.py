@@ -14,6 +14,11 @@ headline bench line):
                                           MMDiTEngine.set_geometry, against a fresh engine per size: per size the full-forward
                                           time of both (alternating windows), the set_geometry time with and without reserve(),
                                           the workspace bytes, and the HBM the weights hold once (`--depth D,S`: fewer blocks)
+    python tools/bench_mmdit.py flux --fp8_linear 0,2,3 [--size 1024x1024,512x512] [--depth D,S]
+    python tools/bench_mmdit.py qwen --fp8_linear 0,2,3 [--size 1664x928]
+                                          one engine per mc_mmdit_config.fp8_linear mode on the same weights and inputs, full
+                                          forwards in alternating windows: ms per forward and the spread of the windows per mode,
+                                          workspace bytes, distance of every mode's output from the first mode's
 
 Synthetic inputs, seeded random-init weights of the real architecture (no checkpoints offline).  One JSON line each.
 Also checks the size-independent MagCache properties at full size: a skipped forward equals the final layer applied
@@ -326,6 +331,64 @@ def bench_regeometry(which, sizes, depth=None, rounds=7, per_round=4):
                       "switch_without_reserve": no_reserve, "per_size": res}))
 
 
+def bench_fp8(which, sizes, modes, depth=None, rounds=5, per_round=3, txt_len=512):
+    """`sizes`: [(width, height)] in pixels; image tokens (H/16) * (W/16).  One engine per fp8_linear mode of `modes` (the same
+    seeded weights: an fp8 engine quantises them as it takes them), switched from size to size with set_geometry; engine-level
+    full forwards.  Per size, windows of `per_round` forwards alternate between the modes after a warm-up of each; host clock
+    around a device synchronise.  One JSON line per size."""
+    from magcache_amd.qwen_bench import random_state_dict
+    flux = which == "flux"
+    cfg = dict(MM.FLUX_DEV if flux else MM.QWEN_IMAGE)
+    if depth:
+        cfg.update(num_layers=depth[0], **({"num_single_layers": depth[1]} if flux else {}))
+    grids = [(h // 16, w // 16) for w, h in sizes]
+    engines = {}
+    for mode in modes:
+        n0 = grids[0][0] * grids[0][1]
+        if flux:
+            m = MM.FluxTransformer2DModelHIP(cfg, n0, txt_len=txt_len, device=DEV, calibration=False, fp8_linear=mode)
+            synth_load(m, flux_names(cfg))
+        else:
+            m = MM.QwenImageTransformer2DModelHIP(cfg, n0, txt_len=txt_len, device=DEV, calibration=False, fp8_linear=mode)
+            m.engine.load_weights(random_state_dict(cfg, DEV))
+        engines[mode] = m.engine
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+    for size, (h2, w2) in zip(sizes, grids):
+        g = torch.Generator(device=DEV).manual_seed(h2 * 1000 + w2)
+        img = torch.randn(h2 * w2, 64, generator=g, device=DEV)
+        txt = torch.randn(txt_len, cfg["joint_attention_dim"], generator=g, device=DEV)
+        if flux:
+            ids = torch.zeros(txt_len + h2 * w2, 3)
+            ids[txt_len:, 1] = torch.arange(h2).repeat_interleave(w2)
+            ids[txt_len:, 2] = torch.arange(w2).repeat(h2)
+            vec, rope = torch.randn(768, generator=g, device=DEV), MM.flux_rope(ids)
+        else:
+            vec, rope = None, MM.qwen_rope([(1, h2, w2)], txt_len)
+        for e in engines.values():
+            e.set_geometry(h2 * w2, (0, 0, 0), txt_len)
+            e.set_rope(*rope)
+        fwd = {mode: (lambda e=e: e.forward(img, 500.0, 3500.0, txt, txt_len, vec, branch=None if flux else 0))
+               for mode, e in engines.items()}
+        outs = {mode: timed(fwd[mode], 2)[1].clone() for mode in modes}
+        ms = {mode: [] for mode in modes}
+        for _ in range(rounds):
+            for mode in modes:
+                ms[mode].append(timed(fwd[mode], per_round)[0] * 1e3)
+        base = outs[modes[0]]
+        print(json.dumps({"config": f"{'FLUX.1-dev' if flux else 'Qwen-Image'} {cfg['num_layers']} double"
+                                    f"{' + %d single' % cfg['num_single_layers'] if flux else ''} blocks, {size[0]}x{size[1]}: "
+                                    f"{h2 * w2} image + {txt_len} text tokens, full forward, synthetic weights/inputs",
+                          "forwards_per_window": per_round, "windows": rounds,
+                          "per_mode": {str(mode): {"forward_ms": float(np.median(ms[mode])),
+                                                   "window_spread_ms": float(max(ms[mode]) - min(ms[mode])),
+                                                   "windows_ms": [round(v, 3) for v in ms[mode]],
+                                                   "workspace_bytes": engines[mode].geometry_bytes(h2 * w2, (0, 0, 0), txt_len),
+                                                   "finite": bool(torch.isfinite(outs[mode]).all()),
+                                                   "rel_l2_vs_mode_%d" % modes[0]: float((outs[mode] - base).norm() / base.norm())}
+                                       for mode in modes}}), flush=True)
+
+
 if __name__ == "__main__":
     lib = load()
     which = sys.argv[1] if len(sys.argv) > 1 else "flux"
@@ -333,7 +396,16 @@ if __name__ == "__main__":
         from magcache_amd._lib import check
         check(lib.mc_set_option(b"mmdit_two_streams", 1))
         print("mmdit_two_streams = 1")
-    if "--regeometry" in sys.argv[2:]:
+    if "--fp8_linear" in sys.argv[2:]:
+        if which not in ("flux", "qwen"):
+            sys.exit(f"--fp8_linear benches FLUX and Qwen-Image, not '{which}'")
+        modes = [int(v) for v in sys.argv[sys.argv.index("--fp8_linear") + 1].split(",")]
+        default = "1024x1024" if which == "flux" else "1664x928"
+        sizes = [tuple(int(v) for v in g.split("x"))
+                 for g in (sys.argv[sys.argv.index("--size") + 1] if "--size" in sys.argv else default).split(",")]
+        depth = [int(v) for v in sys.argv[sys.argv.index("--depth") + 1].split(",")] if "--depth" in sys.argv else None
+        bench_fp8(which, sizes, modes, depth)
+    elif "--regeometry" in sys.argv[2:]:
         if which not in ("flux", "qwen"):
             sys.exit(f"--regeometry benches FLUX and Qwen-Image, not '{which}'")
         sizes = [tuple(int(v) for v in g.split("x")) for g in sys.argv[sys.argv.index("--regeometry") + 1].split(",")]
