@@ -539,6 +539,26 @@ mc_status mc_op_rope_axes(int F, int Hp, int Wp, float* axes_host, size_t* n_flo
 mc_status mc_op_rope_expand(const float* axes_dev, int F, int Hp, int Wp, int tok0, int n_tok, int n_rows, float* cs_dev,
                             mc_stream stream);
 
+/* The LoRA merge the MM-DiT engine rebuilds its weights with (magcache_mmdit.h: mc_mmdit_lora_apply), on the caller's
+ * buffers: out[rows, K] = bf16(base + sum_j scale_j * (up_j down_j)), base / out bf16 with row pitches ld_base / ld_out (elements),
+ * term j = bf16 down [rank, K] and up [rows, rank], contiguous, any rank >= 1.  Per term an fp32 product accumulated from zero
+ * on bf16 MFMAs, the fp32 delta summed in term order, ONE fp32 add of the widened base element last, one round-to-nearest-even.
+ * out may alias base; nothing outside [rows, K] is written.  The call first copies both matrices into scratch in the order its
+ * MFMAs read them (rank zero-padded to a multiple of 16, rows to a multiple of 32): `scratch_dev` (256-byte aligned, at least mc_op_lora_merge_scratch bytes), or with NULL an
+ * allocation of its own, which makes the call synchronous.  Not a forward-path call.  MC_EINVAL, and nothing launched, for a
+ * rank < 1, more than MC_LORA_MAX_TERMS terms, K or a pitch that is no multiple of 8, a base / out pointer that is not 16-byte
+ * aligned, or a scratch that is too small. */
+#define MC_LORA_MAX_TERMS 8
+typedef struct mc_lora_term {
+  const void* down;
+  const void* up;
+  int rank;
+  float scale;
+} mc_lora_term;
+size_t mc_op_lora_merge_scratch(int rows, int K, const mc_lora_term* terms, int n_terms);
+mc_status mc_op_lora_merge(const void* base_dev, long ld_base, void* out_dev, long ld_out, int rows, int K,
+                           const mc_lora_term* terms, int n_terms, void* scratch_dev, size_t scratch_bytes, mc_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

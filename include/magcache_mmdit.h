@@ -127,6 +127,41 @@ int mc_mmdit_weights_missing(const mc_mmdit* e, char* buf, size_t buflen);
  * HunyuanVideo: n_rows = img_tokens. */
 mc_status mc_mmdit_set_rope(mc_mmdit* e, const float* cos_dev, const float* sin_dev, int n_rows, mc_stream stream);
 
+/* LoRA adapters, merged on the device.  The reference forwards open with scale_lora_layers(self, lora_scale) and close with
+ * unscale_lora_layers (MagCache4FLUX/magcache_flux.py:62-67, MagCache4QwenImage/magcache_generate.py:107-113); this engine keeps
+ * its forward as it is -- the same launches on the same weight pointers -- and rebuilds the weights instead: every Linear an
+ * adapter touches keeps its pristine bf16 weight once, and mc_mmdit_lora_apply rewrites the live one in place,
+ *   W_eff = bf16(W + sum_j scale_j * factor_j * up_j down_j)
+ * (per term an fp32 product on bf16 MFMAs, the fp32 sum in the order the pairs were set, one fp32 add of W, one rounding),
+ * then requantises exactly the touched rows of an MX copy (fp8_linear).  A delta far below half a bf16 ulp of W is partly
+ * rounded away, as with diffusers' fuse_lora on bf16 weights.
+ *   mc_mmdit_lora_set    one pair of `adapter` on `weight_name`, an upstream name of mc_mmdit_set_weight such as
+ *                        "transformer_blocks.3.attn.to_q.weight" (a part of a fused matrix is addressed by its own name):
+ *                        down_dev [rank, in_features], up_dev [out_features of that name, rank], both fp32 or bf16 (`dtype`),
+ *                        copied; factor = alpha / rank of the target.  MC_EINVAL, naming the weight, for a name that is no bf16
+ *                        matrix of a GEMM (the fp32 head, a padded image embedder, norm weights, biases), for element counts that
+ *                        do not fit, and for a ninth adapter on one weight.  The same (adapter, weight_name) again replaces the
+ *                        pair.  A new adapter starts at scale 1.
+ *   mc_mmdit_lora_scale  the adapter's scale; a term's multiplier is scale * factor, and a multiplier of 0 leaves the term out
+ *   mc_mmdit_lora_remove the adapter's pairs, or with NULL every adapter's; a Linear no adapter touches any more gets its
+ *                        pristine weight back bit for bit and gives the copy up (with the next apply)
+ *   mc_mmdit_lora_apply  merges every part whose pairs, multipliers or base weight changed since the last apply (a few ms for
+ *                        all of FLUX.1-dev).  mc_mmdit_set_weight on a touched Linear stores into the pristine
+ *                        copy and needs an apply as well.
+ *   mc_mmdit_lora_info   adapters known, Linears with a pristine copy, bytes of those copies (any pointer may be NULL)
+ * All of them work between forwards only (MC_ESTATE between mc_mmdit_begin and mc_mmdit_end), may allocate or free device
+ * memory and must not be stream-captured; a captured forward stays valid across them, since no pointer it reads moves.
+ * While a change waits for its apply, mc_mmdit_begin / _forward / _forward2 return MC_ESTATE.  Residual caches and
+ * calibration statistics are left alone (an adapter change never resets MagCache state in the reference either), and
+ * adapters survive mc_mmdit_set_geometry.  Sequence parallel: weights are replicated, every rank makes the same calls. */
+mc_status mc_mmdit_lora_set(mc_mmdit* e, const char* adapter, const char* weight_name, const void* down_dev,
+                            const int64_t* down_shape, const void* up_dev, const int64_t* up_shape, mc_dtype dtype, float factor,
+                            mc_stream stream);   /* both shapes are 2-D; rank = down_shape[0] */
+mc_status mc_mmdit_lora_scale(mc_mmdit* e, const char* adapter, float scale);
+mc_status mc_mmdit_lora_remove(mc_mmdit* e, const char* adapter);
+mc_status mc_mmdit_lora_apply(mc_mmdit* e, mc_stream stream);
+mc_status mc_mmdit_lora_info(const mc_mmdit* e, int* adapters, int* linears, size_t* base_bytes);
+
 /* FLUX ControlNet residuals (the reference keeps upstream's controlnet_block_samples, controlnet_single_block_samples and
  * controlnet_blocks_repeat, MagCache4FLUX/magcache_flux.py:374-384 and :416-423; the ControlNet itself is the caller's).
  * Every sample is a caller-owned device tensor [img_tokens, dim] of `dtype` (16-byte aligned; always the FULL tensor, like

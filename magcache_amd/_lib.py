@@ -130,6 +130,8 @@ SIGNATURES = {
     "mc_op_rope_table": (_i, [_i, _i, _i, _i, _i, _vp]),
     "mc_op_rope_axes": (_i, [_i, _i, _i, _vp, C.POINTER(_sz)]),
     "mc_op_rope_expand": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "mc_op_lora_merge_scratch": (_sz, [_i, _i, _vp, _i]),
+    "mc_op_lora_merge": (_i, [_vp, _l, _vp, _l, _i, _i, _vp, _i, _vp, _sz, _vp]),
     # include/magcache_mmdit.h
     "mc_mmdit_create": (_i, [_vp, C.POINTER(_vp)]),
     "mc_mmdit_create_sized": (_i, [_vp, _sz, C.POINTER(_vp)]),
@@ -141,6 +143,11 @@ SIGNATURES = {
     "mc_mmdit_set_geometry": (_i, [_vp, _i, _i, _i, _i, _i]),
     "mc_mmdit_set_weight": (_i, [_vp, C.c_char_p, _vp, _i, C.POINTER(C.c_int64), _i, _vp]),
     "mc_mmdit_weights_missing": (_i, [_vp, C.c_char_p, _sz]),
+    "mc_mmdit_lora_set": (_i, [_vp, C.c_char_p, C.c_char_p, _vp, C.POINTER(C.c_int64), _vp, C.POINTER(C.c_int64), _i, _f, _vp]),
+    "mc_mmdit_lora_scale": (_i, [_vp, C.c_char_p, _f]),
+    "mc_mmdit_lora_remove": (_i, [_vp, C.c_char_p]),
+    "mc_mmdit_lora_apply": (_i, [_vp, _vp]),
+    "mc_mmdit_lora_info": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_sz)]),
     "mc_mmdit_set_rope": (_i, [_vp, _vp, _vp, _i, _vp]),
     "mc_mmdit_set_controlnet": (_i, [_vp, _vp, _i, _vp, _i, _i, _i]),
     "mc_mmdit_controlnet_index": (_i, [_i, _i, _i, _i]),
@@ -165,6 +172,12 @@ class McMmditConfig(C.Structure):
 
 
 MC_FAMILY_FLUX, MC_FAMILY_HUNYUAN, MC_FAMILY_QWEN = 0, 1, 2
+MC_LORA_MAX_TERMS = 8
+
+
+class McLoraTerm(C.Structure):   # mc_lora_term: bf16 down [rank, K] and up [rows, rank] on the device
+    _fields_ = [("down", C.c_void_p), ("up", C.c_void_p), ("rank", C.c_int), ("scale", C.c_float)]
+
 
 _lib = None
 

@@ -52,13 +52,14 @@ mc_status WeightStore::alloc_linear(Linear& l, size_t n_out, size_t k_in, Quant 
   return MC_OK;
 }
 
-Slot& WeightStore::add_parts(const Linear& l, const std::string& prefix, const std::vector<Part>& parts, size_t row0) {
+Slot& WeightStore::add_parts(Linear& l, const std::string& prefix, const std::vector<Part>& parts, size_t row0) {
   const size_t k = l.k_in;
   Slot* last = nullptr;
   for (const Part& part : parts) {
     add(prefix + part.name + ".bias", l.b, MC_F32, part.rows, row0);
     last = &add(prefix + part.name + ".weight", l.w, MC_BF16, part.rows * k, row0 * k);
     last->q8 = l.q; last->q8_scale = l.q_scale; last->q8_k = k; last->mx = l.mx; last->mx_rows = l.n_out;
+    last->lin = &l;
     row0 += part.rows;
   }
   return *last;
@@ -93,7 +94,9 @@ mc_status WeightStore::set(const char* name, const void* src_dev, mc_dtype dtype
       HIP_TRY(hipMemcpyAsync(dst, src_dev, numel * 4, hipMemcpyDeviceToDevice, stream));
     }
   } else {
-    bf16_t* dst = (bf16_t*)s.dst + s.off;
+    // a Linear with a base copy keeps the given rows there; the live rows follow with the next lora_apply
+    const bool to_base = s.lin && s.lin->w_base;
+    bf16_t* dst = (to_base ? s.lin->w_base : (bf16_t*)s.dst) + s.off;
     if (s.pad.rows) {  // [rows, k_in] -> [rows, k_pitch] row pitch (the padding columns stay zero)
       const size_t rows = s.pad.rows, k = s.pad.k_in, pitch = s.pad.k_pitch;
       if (dtype == MC_F32) {
@@ -106,19 +109,151 @@ mc_status WeightStore::set(const char* name, const void* src_dev, mc_dtype dtype
     } else {
       HIP_TRY(hipMemcpyAsync(dst, src_dev, numel * 2, hipMemcpyDeviceToDevice, stream));
     }
-    if (s.q8) {  // e4m3 copy of the rows just stored
-      const size_t rows = numel / s.q8_k, row0 = s.off / s.q8_k;
-      if (s.mx) {  // MX: the e4m3 bytes are relative to the block scales, not to a row scale
-        HIP_TRY(launch_quantize_rows_mx(dst, nullptr, (long)s.q8_k, (int)rows, (int)s.q8_k, s.q8 + s.off, (long)s.q8_k,
-                                        s.mx + row0, (long)s.mx_rows, stream));
-      } else {
-        HIP_TRY(launch_quantize_rows_fp8(dst, nullptr, (long)s.q8_k, (int)rows, (int)s.q8_k, s.q8 + s.off, (long)s.q8_k,
-                                         s.q8_scale + row0, stream));
-      }
-    }
+    if (to_base) lora_dirty.insert(name);
+    else MC_TRY(requantise(s, stream));
   }
   s.loaded = true;
   return MC_OK;
+}
+
+mc_status WeightStore::requantise(const Slot& s, hipStream_t stream) {
+  if (!s.q8) return MC_OK;
+  const bf16_t* src = (const bf16_t*)s.dst + s.off;
+  const size_t rows = s.numel / s.q8_k, row0 = s.off / s.q8_k;
+  if (s.mx) {  // MX: the e4m3 bytes are relative to the block scales, not to a row scale
+    HIP_TRY(launch_quantize_rows_mx(src, nullptr, (long)s.q8_k, (int)rows, (int)s.q8_k, s.q8 + s.off, (long)s.q8_k, s.mx + row0,
+                                    (long)s.mx_rows, stream));
+  } else {
+    HIP_TRY(launch_quantize_rows_fp8(src, nullptr, (long)s.q8_k, (int)rows, (int)s.q8_k, s.q8 + s.off, (long)s.q8_k,
+                                     s.q8_scale + row0, stream));
+  }
+  return MC_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ LoRA adapters
+mc_status WeightStore::lora_set(const char* adapter, const char* weight_name, const void* down_dev, size_t down_numel,
+                                const void* up_dev, size_t up_numel, mc_dtype dtype, int rank, float factor, hipStream_t stream) {
+  auto it = slots.find(weight_name);
+  if (it == slots.end()) return fail(MC_EINVAL, "LoRA: unknown weight '%s'", weight_name);
+  Slot& s = it->second;
+  if (!s.lin || s.dst_dtype != MC_BF16 || s.pad.rows || s.perm_c)
+    return fail(MC_EINVAL, "LoRA: '%s' is no plain bf16 part of a Linear (an fp32, padded or permuted weight takes no adapter)",
+                weight_name);
+  if (dtype != MC_F32 && dtype != MC_BF16) return fail(MC_EINVAL, "LoRA '%s': down / up are fp32 or bf16", weight_name);
+  Linear& l = *s.lin;
+  const size_t k = l.k_in, rows = s.numel / k;
+  if (rank <= 0) return fail(MC_EINVAL, "LoRA '%s': rank %d", weight_name, rank);
+  if (down_numel != (size_t)rank * k || up_numel != rows * (size_t)rank)
+    return fail(MC_EINVAL, "LoRA '%s': down has %zu elements, up %zu; rank %d wants [%d, %zu] = %zu and [%zu, %d] = %zu", weight_name,
+                down_numel, up_numel, rank, rank, k, (size_t)rank * k, rows, rank, rows * (size_t)rank);
+  if ((k % 8) != 0) return fail(MC_EINVAL, "LoRA '%s': in_features %zu is no multiple of 8", weight_name, k);
+  size_t at = lora.size(), on_target = 0;
+  for (size_t i = 0; i < lora.size(); ++i) {
+    if (lora[i].target != weight_name) continue;
+    if (lora[i].adapter == adapter) at = i;
+    else ++on_target;
+  }
+  if (on_target + 1 > (size_t)kLoraMaxTerms)
+    return fail(MC_EINVAL, "LoRA '%s': more than %d adapters on one weight", weight_name, kLoraMaxTerms);
+  const int rank_pad = (int)align_up(rank, kLoraRankStep);
+  LoraPair p;
+  p.adapter = adapter; p.target = weight_name; p.rank_pad = rank_pad; p.factor = factor;
+  MC_TRY(alloc(&p.up, lora_packed_elems(rows, rank_pad)));
+  if (mc_status st = alloc(&p.down_t, lora_packed_elems(k, rank_pad))) { release(p.up); return st; }
+  bool new_base = false;
+  if (!l.w_base) {  // the first adapter on this Linear: its pristine copy
+    if (mc_status st = alloc(&l.w_base, (size_t)l.n_out * k)) { release(p.up); release(p.down_t); return st; }
+    new_base = true;
+  }
+  hipError_t err = hipSuccess;
+  if (new_base) err = hipMemcpyAsync(l.w_base, l.w, (size_t)l.n_out * k * 2, hipMemcpyDeviceToDevice, stream);
+  if (err == hipSuccess) err = launch_lora_pack(up_dev, dtype == MC_F32, rank, 1, (int)rows, rank, rank_pad, p.up, stream);
+  if (err == hipSuccess) err = launch_lora_pack(down_dev, dtype == MC_F32, 1, (long)k, (int)k, rank, rank_pad, p.down_t, stream);
+  if (err != hipSuccess) {
+    release(p.up); release(p.down_t);
+    if (new_base) { release(l.w_base); l.w_base = nullptr; }
+    return fail(MC_EHIP, "LoRA '%s': %s", weight_name, hipGetErrorString(err));
+  }
+  if (at < lora.size()) {  // replaced: the old pair's copies go (hipFree waits for a merge that may still read them)
+    release(lora[at].up); release(lora[at].down_t);
+    lora[at] = p;
+  } else {
+    lora.push_back(p);
+  }
+  lora_scales.emplace(adapter, 1.f);
+  lora_dirty.insert(weight_name);
+  return MC_OK;
+}
+
+mc_status WeightStore::lora_scale(const char* adapter, float scale) {
+  auto it = lora_scales.find(adapter);
+  if (it == lora_scales.end()) return fail(MC_EINVAL, "LoRA: unknown adapter '%s'", adapter);
+  if (it->second == scale) return MC_OK;
+  it->second = scale;
+  for (const LoraPair& p : lora)
+    if (p.adapter == adapter) lora_dirty.insert(p.target);
+  return MC_OK;
+}
+
+mc_status WeightStore::lora_remove(const char* adapter) {
+  if (adapter && !lora_scales.count(adapter)) return fail(MC_EINVAL, "LoRA: unknown adapter '%s'", adapter);
+  std::vector<LoraPair> kept;
+  for (const LoraPair& p : lora) {
+    if (adapter && p.adapter != adapter) { kept.push_back(p); continue; }
+    lora_dirty.insert(p.target);
+    release(p.up); release(p.down_t);
+  }
+  lora.swap(kept);
+  if (adapter) lora_scales.erase(adapter);
+  else lora_scales.clear();
+  return MC_OK;
+}
+
+mc_status WeightStore::lora_apply(hipStream_t stream) {
+  std::set<Linear*> touched;
+  while (!lora_dirty.empty()) {
+    const std::string name = *lora_dirty.begin();
+    Slot& s = slots.at(name);
+    Linear& l = *s.lin;
+    const size_t k = l.k_in, rows = s.numel / k;
+    LoraTerm terms[kLoraMaxTerms];
+    int n = 0;
+    for (const LoraPair& p : lora) {
+      const float m = lora_scales.at(p.adapter) * p.factor;
+      if (p.target != name || m == 0.f) continue;
+      terms[n++] = LoraTerm{p.up, p.down_t, p.rank_pad, m};
+    }
+    if (n == 0) {
+      HIP_TRY(hipMemcpyAsync(l.w + s.off, l.w_base + s.off, s.numel * 2, hipMemcpyDeviceToDevice, stream));
+    } else {
+      hipError_t err = launch_lora_merge(l.w_base + s.off, (long)k, l.w + s.off, (long)k, (int)rows, (int)k, terms, n, stream);
+      if (err != hipSuccess) return fail(MC_EHIP, "LoRA merge of '%s': %s", name.c_str(), hipGetErrorString(err));
+    }
+    MC_TRY(requantise(s, stream));
+    touched.insert(&l);
+    lora_dirty.erase(name);
+  }
+  for (Linear* l : touched) {  // no adapter left on any part: w is the base again, bit for bit
+    bool live = false;
+    for (const LoraPair& p : lora) live = live || slots.at(p.target).lin == l;
+    if (!live) {
+      release(l->w_base);  // hipFree waits for the copies above
+      l->w_base = nullptr;
+    }
+  }
+  return MC_OK;
+}
+
+void WeightStore::lora_info(int* adapters, int* linears, size_t* base_bytes) const {
+  std::set<const Linear*> seen;
+  size_t bytes = 0;
+  for (auto& kv : slots) {
+    const Linear* l = kv.second.lin;
+    if (l && l->w_base && seen.insert(l).second) bytes += (size_t)l->n_out * l->k_in * 2;
+  }
+  if (adapters) *adapters = (int)lora_scales.size();
+  if (linears) *linears = (int)seen.size();
+  if (base_bytes) *base_bytes = bytes;
 }
 
 int WeightStore::missing(char* buf, size_t buflen) const {

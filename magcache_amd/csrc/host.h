@@ -7,6 +7,7 @@
 #include <cstdarg>
 #include <cstring>
 #include <map>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -47,6 +48,7 @@ struct Linear {
   uint8_t* q = nullptr;
   float* q_scale = nullptr;
   uint8_t* mx = nullptr;
+  bf16_t* w_base = nullptr;  // the pristine weight while a LoRA adapter touches this Linear (w is then the merged one)
 };
 enum Quant { QUANT_NONE, QUANT_ROW, QUANT_MX };   // one scale per output channel | one E8M0 byte per (channel, 32 inputs)
 struct Part { std::string name; size_t rows; };   // an upstream Linear whose rows are stacked into a fused one (q | k | v -> qkv)
@@ -68,6 +70,17 @@ struct Slot {  // one named parameter
   size_t q8_k = 0;  // row length (in_features)
   uint8_t* mx = nullptr;
   size_t mx_rows = 0;
+  Linear* lin = nullptr;  // the Linear whose rows this weight is (add_parts); null for every other parameter
+};
+
+// One adapter's low-rank pair on one weight slot, as the merge kernel reads it: bf16 copies owned by the store in the
+// kernel's operand order (ops.h: LoraTerm), the rank zero-padded to the kernel's step
+struct LoraPair {
+  std::string adapter, target;
+  bf16_t* up = nullptr;      // rows of the part x rank_pad, packed
+  bf16_t* down_t = nullptr;  // k_in x rank_pad (down transposed), packed
+  int rank_pad = 0;
+  float factor = 1.f;        // alpha / rank of the target
 };
 
 struct WeightStore {
@@ -86,9 +99,26 @@ struct WeightStore {
   mc_status alloc_linear(Linear& l, size_t n_out, size_t k_in, Quant quant = QUANT_NONE);
   // "<prefix><part>.weight" [rows, k_in] (bf16) and "<prefix><part>.bias" [rows] (fp32) of every part, stacked from row row0 of
   // `l`; every slot carries the quantised copy, so that setting a part requantises its rows.  Returns the last weight's slot.
-  Slot& add_parts(const Linear& l, const std::string& prefix, const std::vector<Part>& parts, size_t row0 = 0);
+  Slot& add_parts(Linear& l, const std::string& prefix, const std::vector<Part>& parts, size_t row0 = 0);
   // copy / cast / permute / pad one parameter into place (and requantise its rows) on the caller's stream
   mc_status set(const char* name, const void* src_dev, mc_dtype dtype, const int64_t* shape, int ndim, hipStream_t stream);
+  // ---- LoRA adapters, merged into the live weight: w = bf16(w_base + sum_j scale_j factor_j up_j down_j) per touched part, in the
+  // order the pairs were set.  Host bookkeeping + launches on the caller's stream; they may allocate and free (never inside a
+  // forward, never under stream capture).  The forward reads the same pointers as ever.
+  // `weight_name`: a bf16 part of a Linear with no pad and no perm_c; down [rank, k_in], up [rows of the part, rank], fp32 or bf16.
+  // The first pair on a Linear makes its base copy; setting (adapter, weight_name) again replaces the pair.  A new adapter
+  // starts at scale 1.
+  mc_status lora_set(const char* adapter, const char* weight_name, const void* down_dev, size_t down_numel, const void* up_dev,
+                     size_t up_numel, mc_dtype dtype, int rank, float factor, hipStream_t stream);
+  mc_status lora_scale(const char* adapter, float scale);   // a term's multiplier is scale * factor
+  mc_status lora_remove(const char* adapter);               // null: every adapter
+  // every part whose terms, multipliers or base changed since the last apply: one merge over its rows (a term with multiplier 0
+  // is skipped; no live term: the base rows are copied back), then the quantised copy of exactly those rows.  A Linear that no
+  // adapter touches any more gives its base copy back.
+  mc_status lora_apply(hipStream_t stream);
+  bool dirty() const { return !lora_dirty.empty(); }
+  void lora_info(int* adapters, int* linears, size_t* base_bytes) const;
+
   int missing(char* buf, size_t buflen) const;  // count; names, one per line, as far as buf holds them
   bool all_loaded(const char** first_missing) const;
   void release(void* p);  // free one allocation of alloc() (never inside a forward)
@@ -96,6 +126,11 @@ struct WeightStore {
 
  private:
   mc_status alloc_bytes(void** p, size_t bytes);
+  // the quantised copy (q8 / mx) of the rows of `s`, from the bf16 rows just stored in the live weight
+  mc_status requantise(const Slot& s, hipStream_t stream);
+  std::vector<LoraPair> lora;                 // in the order they were set: the term order of a merge
+  std::map<std::string, float> lora_scales;   // adapter -> scale
+  std::set<std::string> lora_dirty;           // weight slots to merge again
 };
 
 // ---------------------------------------------------------------- workspace

@@ -626,6 +626,47 @@ int mc_mmdit_weights_missing(const mc_mmdit* e, char* buf, size_t buflen) {
   return e ? e->weights.missing(buf, buflen) : -1;
 }
 
+// ---- LoRA adapters: the store does the work (host.h), between forwards only
+static mc_status lora_entry(const mc_mmdit* e, const char* what) {
+  if (!e) return fail(MC_EINVAL, "null engine");
+  if (e->begun) return fail(MC_ESTATE, "%s between mc_mmdit_begin and mc_mmdit_end", what);
+  return MC_OK;
+}
+
+mc_status mc_mmdit_lora_set(mc_mmdit* e, const char* adapter, const char* weight_name, const void* down_dev,
+                            const int64_t* down_shape, const void* up_dev, const int64_t* up_shape, mc_dtype dtype, float factor,
+                            mc_stream stream) {
+  MC_TRY(lora_entry(e, "mc_mmdit_lora_set"));
+  if (!adapter || !weight_name || !down_dev || !down_shape || !up_dev || !up_shape) return fail(MC_EINVAL, "null argument");
+  if (down_shape[0] <= 0 || down_shape[0] > (1 << 20) || down_shape[1] <= 0 || up_shape[0] <= 0 || up_shape[1] != down_shape[0])
+    return fail(MC_EINVAL, "LoRA '%s': down [%lld, %lld] and up [%lld, %lld] share no rank", weight_name, (long long)down_shape[0],
+                (long long)down_shape[1], (long long)up_shape[0], (long long)up_shape[1]);
+  return e->weights.lora_set(adapter, weight_name, down_dev, (size_t)down_shape[0] * down_shape[1], up_dev,
+                             (size_t)up_shape[0] * up_shape[1], dtype, (int)down_shape[0], factor, (hipStream_t)stream);
+}
+
+mc_status mc_mmdit_lora_scale(mc_mmdit* e, const char* adapter, float scale) {
+  MC_TRY(lora_entry(e, "mc_mmdit_lora_scale"));
+  if (!adapter) return fail(MC_EINVAL, "null argument");
+  return e->weights.lora_scale(adapter, scale);
+}
+
+mc_status mc_mmdit_lora_remove(mc_mmdit* e, const char* adapter) {
+  MC_TRY(lora_entry(e, "mc_mmdit_lora_remove"));
+  return e->weights.lora_remove(adapter);
+}
+
+mc_status mc_mmdit_lora_apply(mc_mmdit* e, mc_stream stream) {
+  MC_TRY(lora_entry(e, "mc_mmdit_lora_apply"));
+  return e->weights.lora_apply((hipStream_t)stream);
+}
+
+mc_status mc_mmdit_lora_info(const mc_mmdit* e, int* adapters, int* linears, size_t* base_bytes) {
+  if (!e) return fail(MC_EINVAL, "null engine");
+  e->weights.lora_info(adapters, linears, base_bytes);
+  return MC_OK;
+}
+
 mc_status mc_mmdit_set_rope(mc_mmdit* e, const float* cos_dev, const float* sin_dev, int n_rows, mc_stream stream) {
   if (!e || !cos_dev || !sin_dev) return fail(MC_EINVAL, "null argument");
   const bool hy = e->cfg.family == MC_FAMILY_HUNYUAN;
@@ -864,6 +905,7 @@ mc_status begin_impl(mc_mmdit* e, const float* img_dev, double timestep, double 
   hipStream_t s = (hipStream_t)stream_;
   if (!e) return fail(MC_EINVAL, "null engine");
   MC_TRY(mc::check_ready(e->work, e->weights, "mc_mmdit_set_workspace"));
+  if (e->weights.dirty()) return fail(MC_ESTATE, "LoRA adapters, scales or a touched weight changed: call mc_mmdit_lora_apply first");
   const mc_mmdit_config& c = e->cfg;
   const bool hy = c.family == MC_FAMILY_HUNYUAN;
   const bool qw = c.family == MC_FAMILY_QWEN;

@@ -105,6 +105,33 @@ bool gemm_mxfp8_supported(const GemmParams& p);
 hipError_t launch_quantize_rows_mx(const bf16_t* x, const float* x_f32, long ldx, int M, int K, uint8_t* q, long ldq,
                                    uint8_t* s, long rows_pad, hipStream_t stream);
 
+// ---------------------------------------------------------------- LoRA merge (lora_merge.hip)
+// out[rows, K] = bf16(base + sum_j scale_j * (up_j down_j)), up_j [rows, rank], down_j [rank, K].  Per term an fp32 accumulator
+// from zero on bf16 MFMAs, the fp32 delta summed in term order, one fp32 add of the widened base element last, one
+// round-to-nearest-even.  out may alias base; nothing outside [rows, K] is written (ld_out > K is legal).
+// The operands are copies launch_lora_pack makes, bf16 in the order the kernel's 32x32x16 MFMAs read them: the rank zero-padded
+// to a multiple of kLoraRankStep, the rows (of up; the columns of down) to a multiple of 32, and element (row, k) at
+//   [((row / 32) * (rank_pad / 16) + k / 16) * 64 + 32 * ((k % 16) / 8) + row % 32][k % 8]
+// -- per 32 rows and 16 rank elements the 64 lanes' 8-element fragments, consecutive.  lora_packed_elems: elements of one.
+// hipErrorInvalidValue, and nothing launched, for more than kLoraMaxTerms terms, a rank_pad that is no positive multiple of
+// kLoraRankStep, K or a leading dimension that is no multiple of 8, or a pointer that is not 16-byte aligned.  n_terms == 0
+// copies base to out.
+constexpr int kLoraMaxTerms = 8;
+constexpr int kLoraRankStep = 16;
+struct LoraTerm {
+  const bf16_t* up;     // rows x rank_pad, packed
+  const bf16_t* down;   // K x rank_pad (down transposed), packed
+  int rank_pad;
+  float scale;
+};
+inline size_t lora_packed_elems(size_t n, size_t rank_pad) { return (n + 31) / 32 * 32 * rank_pad; }
+hipError_t launch_lora_merge(const bf16_t* base, long ld_base, bf16_t* out, long ld_out, int rows, int K, const LoraTerm* terms,
+                             int n_terms, hipStream_t stream);
+// dst (lora_packed_elems(n, rank_pad) elements) <- element (row, k) of an [n, rank] matrix at src[row * row_stride + k * col_stride],
+// fp32 (src_f32) or bf16: `up` as given (strides rank, 1), `down` [rank, K] transposed (strides 1, K)
+hipError_t launch_lora_pack(const void* src, int src_f32, long row_stride, long col_stride, int n, int rank, int rank_pad, bf16_t* dst,
+                            hipStream_t stream);
+
 // ---------------------------------------------------------------- attention (attention.hip)
 struct AttnParams {
   const bf16_t* Q; long ldq;

@@ -289,6 +289,57 @@ mc_status mc_op_add_rows(float* x, long ldx, const void* s, mc_dtype s_dtype, fl
   return MC_OK;
 }
 
+size_t mc_op_lora_merge_scratch(int rows, int K, const mc_lora_term* terms, int n_terms) {
+  size_t bytes = 0;
+  for (int j = 0; terms && j < n_terms; ++j) {
+    if (terms[j].rank < 1 || rows < 1 || K < 1) return 0;
+    const size_t rank_pad = mc::align_up(terms[j].rank, mc::kLoraRankStep);
+    bytes += mc::align_up(mc::lora_packed_elems(rows, rank_pad) * 2, 256) + mc::align_up(mc::lora_packed_elems(K, rank_pad) * 2, 256);
+  }
+  return bytes;
+}
+
+mc_status mc_op_lora_merge(const void* base, long ld_base, void* out, long ld_out, int rows, int K, const mc_lora_term* terms,
+                           int n_terms, void* scratch, size_t scratch_bytes, mc_stream s) {
+  hipStream_t stream = (hipStream_t)s;
+  if (!base || !out || rows <= 0 || K <= 0 || n_terms < 0 || (n_terms > 0 && !terms)) return fail(MC_EINVAL, "lora_merge: null or empty operand");
+  if (n_terms > MC_LORA_MAX_TERMS) return fail(MC_EINVAL, "lora_merge: %d terms, at most %d", n_terms, MC_LORA_MAX_TERMS);
+  for (int j = 0; j < n_terms; ++j)
+    if (!terms[j].down || !terms[j].up || terms[j].rank < 1) return fail(MC_EINVAL, "lora_merge: term %d has rank %d or a null matrix", j, terms[j].rank);
+  if ((K % 8) != 0 || ld_base < K || ld_out < K || (ld_base % 8) != 0 || (ld_out % 8) != 0 || (((uintptr_t)base | (uintptr_t)out) & 15))
+    return fail(MC_EINVAL, "lora_merge: K and the pitches are multiples of 8, pitch >= K, base and out 16-byte aligned");
+  const size_t need = mc_op_lora_merge_scratch(rows, K, terms, n_terms);
+  char* ws = (char*)scratch;
+  if (ws && (scratch_bytes < need || ((uintptr_t)ws & 255)))
+    return fail(MC_EINVAL, "lora_merge: scratch of %zu bytes, %zu needed, 256-byte aligned", scratch_bytes, need);
+  bool own = false;
+  if (!ws && need) {
+    hipError_t err = hipMalloc((void**)&ws, need);
+    if (err != hipSuccess) return fail(MC_ENOMEM, "hipMalloc(%zu) failed: %s", need, hipGetErrorString(err));
+    own = true;
+  }
+  mc::LoraTerm t[MC_LORA_MAX_TERMS];
+  hipError_t err = hipSuccess;
+  size_t off = 0;
+  for (int j = 0; j < n_terms && err == hipSuccess; ++j) {
+    const int rank = terms[j].rank, rank_pad = (int)mc::align_up(rank, mc::kLoraRankStep);
+    bf16_t* up = (bf16_t*)(ws + off);
+    off += mc::align_up(mc::lora_packed_elems(rows, rank_pad) * 2, 256);
+    bf16_t* down_t = (bf16_t*)(ws + off);
+    off += mc::align_up(mc::lora_packed_elems(K, rank_pad) * 2, 256);
+    t[j] = mc::LoraTerm{up, down_t, rank_pad, terms[j].scale};
+    err = mc::launch_lora_pack(terms[j].up, 0, rank, 1, rows, rank, rank_pad, up, stream);
+    if (err == hipSuccess) err = mc::launch_lora_pack(terms[j].down, 0, 1, K, K, rank, rank_pad, down_t, stream);
+  }
+  if (err == hipSuccess) err = mc::launch_lora_merge((const bf16_t*)base, ld_base, (bf16_t*)out, ld_out, rows, K, t, n_terms, stream);
+  if (own) {
+    if (err == hipSuccess) err = hipStreamSynchronize(stream);
+    (void)hipFree(ws);
+  }
+  HIP_TRY(err);
+  return MC_OK;
+}
+
 mc_status mc_op_cast_bf16(const float* src, void* dst, size_t n, mc_stream s) {
   HIP_TRY(mc::launch_cast_bf16(src, (bf16_t*)dst, n, (hipStream_t)s));
   return MC_OK;

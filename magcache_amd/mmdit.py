@@ -77,6 +77,8 @@ class MMDiTEngine:
         self._bind(self.lib.mc_mmdit_workspace_bytes(self.h))
         self._rope_key = None
         self._controlnet = None
+        self._lora = {}           # adapter -> the scale set_adapters / load_lora gave it
+        self._lora_call = 1.0     # the per-call factor on top of it (the shims' joint_attention_kwargs["scale"])
 
     def _bind(self, nbytes):
         """a zeroed workspace of `nbytes` (at least the current plan), bound with mc_mmdit_set_workspace; the tensor it
@@ -159,6 +161,94 @@ class MMDiTEngine:
         n = self.lib.mc_mmdit_weights_missing(self.h, buf, 4096)
         if n:
             raise KeyError(f"{n} weights missing, e.g.: {buf.value.decode().split()[:5]}")
+
+    # ---- LoRA adapters, merged into the weights on the device (mc_mmdit_lora_*; magcache_amd/lora.py reads the files)
+    def load_lora(self, sd, adapter="default", scale=1.0, strict=True, prefix="transformer."):
+        """Load a LoRA state dict (PEFT / diffusers spellings, lora.parse_lora_state_dict) as `adapter` at `scale` and merge
+        it.  A target the engine takes no adapter on (an unknown name, the fp32 head, a padded embedder, wrong shapes) raises
+        under `strict` -- the engine is then as before the call --, and is skipped otherwise: the skipped weight names are
+        returned.  Loading a known adapter again replaces the pairs it brings."""
+        from .lora import lora_factor, parse_lora_state_dict
+        pairs = parse_lora_state_dict(sd, prefix=prefix)
+        known, skipped, done = adapter in self._lora, [], 0
+        for target, (down, up, alpha) in pairs.items():
+            dt = torch.bfloat16 if down.dtype == torch.bfloat16 and up.dtype == torch.bfloat16 else torch.float32
+            d = down.detach().to(device=self.device, dtype=dt).contiguous()
+            u = up.detach().to(device=self.device, dtype=dt).contiguous()
+            st = self.lib.mc_mmdit_lora_set(self.h, adapter.encode(), target.encode(), _ptr(d), (C.c_int64 * 2)(*d.shape), _ptr(u),
+                                            (C.c_int64 * 2)(*u.shape), MC_BF16 if dt == torch.bfloat16 else MC_F32,
+                                            lora_factor(down, alpha), _stream())
+            torch.cuda.current_stream().synchronize()      # d / u are read by launches on the stream
+            if st == _lib.MC_OK:
+                done += 1
+            elif st == _lib.MC_EINVAL and not strict:
+                skipped.append(target)
+            else:
+                msg = self.lib.mc_last_error().decode()
+                if done and not known:
+                    self.unload_lora(adapter, _known=True)
+                elif done:
+                    self.apply_lora()
+                raise _lib.MagCacheHipError(st, msg)
+        if done or known:
+            self._lora[adapter] = float(scale)
+            check(self.lib.mc_mmdit_lora_scale(self.h, adapter.encode(), float(scale) * self._lora_call))
+        self.apply_lora()
+        return skipped
+
+    def set_adapters(self, names, scales=None):
+        """diffusers' set_adapters: the adapters of `names` (a name or a list) are active at `scales` (a number, a list, None
+        = 1.0), every other loaded adapter is off (scale 0, its pairs kept); merged at once."""
+        names = [names] if isinstance(names, str) else list(names)
+        scales = [1.0 if scales is None else scales] * len(names) if not isinstance(scales, (list, tuple)) else list(scales)
+        if len(scales) != len(names):
+            raise ValueError(f"{len(names)} adapters, {len(scales)} scales")
+        unknown = [n for n in names if n not in self._lora]
+        if unknown:
+            raise KeyError(f"unknown adapters {unknown}; loaded: {sorted(self._lora)}")
+        want = {n: 0.0 for n in self._lora}
+        want.update({n: float(s) for n, s in zip(names, scales)})
+        self._lora = want
+        self._push_lora_scales()
+
+    def _push_lora_scales(self):
+        for n, s in self._lora.items():
+            check(self.lib.mc_mmdit_lora_scale(self.h, n.encode(), s * self._lora_call))
+        self.apply_lora()
+
+    def set_lora_call_scale(self, scale):
+        """The factor of one call on every adapter's scale -- what scale_lora_layers(model, lora_scale) does at the top of
+        the reference forwards and unscale_lora_layers undoes at their end.  Nothing happens without adapters or while the
+        factor stays what it is; else every adapter is rescaled and the weights are merged again."""
+        scale = float(scale)
+        if not self._lora or scale == self._lora_call:
+            return
+        self._lora_call = scale
+        self._push_lora_scales()
+
+    def unload_lora(self, adapter=None, _known=False):
+        """remove one adapter, or all of them (None): the weights it touched are the loaded ones again, bit for bit"""
+        if adapter is not None and adapter not in self._lora and not _known:
+            raise KeyError(f"unknown adapter '{adapter}'; loaded: {sorted(self._lora)}")
+        check(self.lib.mc_mmdit_lora_remove(self.h, adapter.encode() if adapter is not None else None))
+        if adapter is None:
+            self._lora = {}
+        else:
+            self._lora.pop(adapter, None)
+        if not self._lora:
+            self._lora_call = 1.0
+        self.apply_lora()
+
+    def apply_lora(self):
+        """merge what changed (mc_mmdit_lora_apply): after set_weight on a weight an adapter touches; the other calls here
+        apply by themselves"""
+        check(self.lib.mc_mmdit_lora_apply(self.h, _stream()))
+        torch.cuda.current_stream().synchronize()
+
+    def lora_info(self):
+        a, n, b = C.c_int(), C.c_int(), C.c_size_t()
+        check(self.lib.mc_mmdit_lora_info(self.h, C.byref(a), C.byref(n), C.byref(b)))
+        return dict(adapters=a.value, linears=n.value, base_bytes=b.value, scales=dict(self._lora), call_scale=self._lora_call)
 
     def buffer(self, name, dtype=torch.uint8):
         off, nb = C.c_size_t(), C.c_size_t()
@@ -340,6 +430,34 @@ def _dispatch(self, *args, **kwargs):
     return type(self).forward(self, *args, **kwargs)
 
 
+class _LoraMethods:
+    """the adapter calls of MMDiTEngine on the model objects"""
+
+    def load_lora(self, sd, adapter="default", scale=1.0, strict=True, prefix="transformer."):
+        return self.engine.load_lora(sd, adapter=adapter, scale=scale, strict=strict, prefix=prefix)
+
+    def set_adapters(self, names, scales=None):
+        return self.engine.set_adapters(names, scales)
+
+    def unload_lora(self, adapter=None):
+        return self.engine.unload_lora(adapter)
+
+    def apply_lora(self):
+        return self.engine.apply_lora()
+
+    def lora_info(self):
+        return self.engine.lora_info()
+
+
+def _lora_call_scale(model, kwargs):
+    """joint_attention_kwargs / attention_kwargs["scale"] of a call, as scale_lora_layers reads it (magcache_flux.py:62-67,
+    magcache_generate.py:107-113): the call's factor on every loaded adapter, 1.0 without the key.  Without adapters the key
+    is ignored (upstream warns and ignores it too)."""
+    e = model.engine
+    if getattr(e, "_lora", None):
+        e.set_lora_call_scale(1.0 if not kwargs or kwargs.get("scale") is None else kwargs["scale"])
+
+
 def _shim_set_geometry(model, img_tokens, latent_grid, txt_len, fresh):
     """dynamic_geometry: a call whose shapes differ from the engine's geometry switches the engine first and starts the
     MagCache state of a new sample, as init_*_magcache would (`fresh`: the family's attributes).  Only between samples:
@@ -369,7 +487,7 @@ def flux_rope(ids, axes_dim=(16, 56, 56), theta=10000.0):
     return (torch.from_numpy(np.concatenate(cos, 1).astype(np.float32)), torch.from_numpy(np.concatenate(sin, 1).astype(np.float32)))
 
 
-class FluxTransformer2DModelHIP:
+class FluxTransformer2DModelHIP(_LoraMethods):
     """Stands where diffusers' FluxTransformer2DModel stands.  One (image tokens, text length) geometry per instance, unless
     dynamic_geometry=True: then every call may bring its own (MMDiTEngine.set_geometry)."""
     dynamic_geometry = False
@@ -460,6 +578,7 @@ def flux_plain_forward(self, hidden_states, encoder_hidden_states=None, pooled_p
                        img_ids=None, txt_ids=None, guidance=None, joint_attention_kwargs=None,
                        controlnet_block_samples=None, controlnet_single_block_samples=None, return_dict=True,
                        controlnet_blocks_repeat=False, **_):
+    _lora_call_scale(self, joint_attention_kwargs)
     _flux_set_controlnet(self, controlnet_block_samples, controlnet_single_block_samples, controlnet_blocks_repeat,
                          hidden_states, encoder_hidden_states)
     out = self._run(hidden_states, encoder_hidden_states, pooled_projections, timestep, img_ids, txt_ids, guidance, MC_MODE_FULL)
@@ -474,6 +593,7 @@ def flux_magcache_forward(self, hidden_states, encoder_hidden_states=None, poole
                           controlnet_block_samples=None, controlnet_single_block_samples=None, return_dict=True,
                           controlnet_blocks_repeat=False):
     """Drop-in for MagCache4FLUX/magcache_flux.py magcache_forward (:234-445)."""
+    _lora_call_scale(self, joint_attention_kwargs)
     _flux_set_controlnet(self, controlnet_block_samples, controlnet_single_block_samples, controlnet_blocks_repeat,
                          hidden_states, encoder_hidden_states)
     skip_forward = False
@@ -508,6 +628,7 @@ def flux_magcache_calibration(self, hidden_states, encoder_hidden_states=None, p
                               controlnet_block_samples=None, controlnet_single_block_samples=None, return_dict=True,
                               controlnet_blocks_repeat=False):
     """Drop-in for magcache_flux.py magcache_calibration (:37-232)."""
+    _lora_call_scale(self, joint_attention_kwargs)
     _flux_set_controlnet(self, controlnet_block_samples, controlnet_single_block_samples, controlnet_blocks_repeat,
                          hidden_states, encoder_hidden_states)
     out = self._run(hidden_states, encoder_hidden_states, pooled_projections, timestep, img_ids, txt_ids, guidance, MC_MODE_CALIB)
@@ -558,7 +679,7 @@ def init_flux_magcache(model, num_inference_steps=28, magcache_thresh=0.24, K=5,
 
 
 # ============================================================================================== HunyuanVideo
-class HYVideoDiffusionTransformerHIP:
+class HYVideoDiffusionTransformerHIP(_LoraMethods):
     """Stands where hyvideo's HYVideoDiffusionTransformer stands.  One latent grid / text length per instance, unless
     dynamic_geometry=True: then every call may bring its own (MMDiTEngine.set_geometry)."""
     dynamic_geometry = False
@@ -744,7 +865,7 @@ def qwen_rope(img_shapes, max_txt_len, axes_dim=(16, 56, 56), theta=10000.0):
     return torch.cat(cos, 1).contiguous(), torch.cat(sin, 1).contiguous()
 
 
-class QwenImageTransformer2DModelHIP:
+class QwenImageTransformer2DModelHIP(_LoraMethods):
     """Stands where diffusers' QwenImageTransformer2DModel stands (Qwen-Image and Qwen-Image-Edit: the same transformer;
     Edit's image tokens are the noisy latent's followed by the reference image's).  One (image tokens, longest prompt)
     geometry per instance; every call may carry a shorter prompt (cond vs the " " negative prompt, unpadded).  The two
@@ -814,6 +935,7 @@ class QwenImageTransformer2DModelHIP:
 
 def qwen_plain_forward(self, hidden_states, encoder_hidden_states=None, encoder_hidden_states_mask=None, timestep=None,
                        img_shapes=None, txt_seq_lens=None, guidance=None, attention_kwargs=None, return_dict=True, **_):
+    _lora_call_scale(self, attention_kwargs)
     self._geometry(hidden_states, encoder_hidden_states, txt_seq_lens)
     out = self._run(hidden_states, encoder_hidden_states, timestep, img_shapes, txt_seq_lens, MC_MODE_FULL, 0)
     return _flux_output(out, return_dict)
@@ -826,6 +948,7 @@ def qwen_magcache_forward(self, hidden_states, encoder_hidden_states=None, encod
                           img_shapes=None, txt_seq_lens=None, guidance=None, attention_kwargs=None, return_dict=True):
     """Drop-in for MagCache4QwenImage/magcache_generate.py magcache_forward (:173-253): calls alternate cond / uncond
     (branch cnt % 2), strict `<`, and the accumulators are NOT reset when cnt wraps."""
+    _lora_call_scale(self, attention_kwargs)
     self._geometry(hidden_states, encoder_hidden_states, txt_seq_lens)
     cnt = int(self.cnt)
     b = cnt % 2
@@ -857,6 +980,7 @@ def qwen_magcache_calibration(self, hidden_states, encoder_hidden_states=None, e
                               return_dict=True):
     """Drop-in for magcache_generate.py magcache_calibration (:94-171): statistics against the same branch's previous
     residual from the third call on."""
+    _lora_call_scale(self, attention_kwargs)
     self._geometry(hidden_states, encoder_hidden_states, txt_seq_lens)
     cnt = int(self.cnt)
     b = cnt % 2
