@@ -44,7 +44,7 @@ def _stale(target, deps):
 def _headers():
     hs = [os.path.join(CSRC, h) for h in ("common.h", "ops.h", "host.h", "gemm_epilogue.h", "attention_v5_body.inc",
                                           "attention_v5_clobbers.inc", "attention_v5_config.h", "gemm_v2_body.inc",
-                                          "gemm_v2_clobbers.inc", "gemm_v2_config.h")]
+                                          "gemm_v2_clobbers.inc", "gemm_v2_config.h", "quant.h", "gemm_pipe8.h")]
     return hs + [os.path.join(HERE, "..", "include", "magcache_hip.h"), os.path.join(HERE, "..", "include", "magcache_mmdit.h")]
 
 
@@ -63,8 +63,12 @@ def _compile(src, obj, extra_flags, force, verbose):
 
 
 def _link(target, objs, force, verbose):
+    """objs -> target, linked under a temporary name and renamed into place: the linker removes its output file before it
+    writes it, and a process that looks for the library meanwhile (a test run beside a build) must not find it missing"""
     if force or _stale(target, objs):
-        _run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", target] + objs + ["-ldl"], verbose)
+        tmp = target + ".linking"
+        _run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", tmp] + objs + ["-ldl"], verbose)
+        os.replace(tmp, target)
 
 
 def build(force=False, verbose=False):

@@ -96,6 +96,23 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   return base + idx;
 }
 
+// Grouped tile rasterisation behind xcd_remap: virtual tile v walks groups of group_m M-tiles x all N-tiles, M fastest, so
+// that neighbouring tiles (one XCD's contiguous chunk) share W panels in L2; the last group may be shorter.  Sets (m0, n0),
+// the origin of the tile in elements, for square tiles of `edge`.
+// (A macro, not a function: behind a call the compiler folds this index arithmetic in another order and allocates the
+// registers of the 8-wave GEMMs differently; the macro leaves every kernel's instruction stream as it was, which
+// tools/isa_same.py checks.)
+#define MC_GROUPED_TILE(v, tilesM, tilesN, group_m, edge, m0, n0)    \
+  do {                                                               \
+    const int per_group_ = (group_m) * (tilesN);                     \
+    const int grp_ = (v) / per_group_;                               \
+    const int first_m_ = grp_ * (group_m);                           \
+    const int gsz_ = min((tilesM) - first_m_, (group_m));            \
+    const int in_grp_ = (v) - grp_ * per_group_;                     \
+    m0 = (first_m_ + in_grp_ % gsz_) * (edge);                       \
+    n0 = (in_grp_ / gsz_) * (edge);                                  \
+  } while (0)
+
 // Raise a kernel's dynamic-LDS limit once per DEVICE (the attribute belongs to the device that is current when it is
 // set; a process may hold engines on several GPUs).  `done` is the kernel's own bit mask of devices already prepared.
 inline hipError_t ensure_dynamic_lds(const void* kernel, int bytes, std::atomic<uint64_t>& done) {
@@ -107,6 +124,16 @@ inline hipError_t ensure_dynamic_lds(const void* kernel, int bytes, std::atomic<
   e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
   if (e == hipSuccess) done.fetch_or(bit, std::memory_order_release);
   return e;
+}
+
+// The launch of a kernel with more dynamic LDS than the default limit: the limit raised on this device if it has not been
+// (the mask of prepared devices is this instantiation's, i.e. the kernel's own), the launch, the launch error.
+template <auto Kernel, typename... Args>
+inline hipError_t launch_dynamic_lds(dim3 grid, dim3 block, int lds_bytes, hipStream_t stream, Args... args) {
+  static std::atomic<uint64_t> lds_ready{0};
+  if (hipError_t e = ensure_dynamic_lds((const void*)Kernel, lds_bytes, lds_ready); e != hipSuccess) return e;
+  hipLaunchKernelGGL(Kernel, grid, block, lds_bytes, stream, args...);
+  return hipGetLastError();
 }
 
 }  // namespace mc

@@ -9,6 +9,7 @@
 // they are bound by HBM, not by MFMA, and there is nothing to tile.
 #include "common.h"
 #include "ops.h"
+#include "quant.h"
 
 namespace mc {
 
@@ -17,14 +18,14 @@ namespace {
 // ------------------------------------------------------------------ LayerNorm (+ modulate / affine)
 // one wave per row; lane holds NV float4 (row element e = i*256 + lane*4 + j)
 // QM (fp8 Linear modes of the engine): 0 = bf16 / fp32 rows out; 1 = the row leaves as OCP e4m3 with one scale per row;
-// 2 = as e4m3 with one E8M0 scale per 32 elements (MX).  Both quantise the bf16-ROUNDED row exactly as
-// quantize_rows_fp8_kernel / quantize_rows_mx_kernel would from the bf16 row this kernel otherwise writes: the same bits
+// 2 = as e4m3 with one E8M0 scale per 32 elements (MX).  Both quantise the bf16-ROUNDED row with the arithmetic
+// quantize_rows_fp8_kernel / quantize_rows_mx_kernel apply to the bf16 row this kernel otherwise writes (quant.h): the same bits
 // without the 2-byte row ever reaching memory (round 4: drops one pass over the activations per fp8 GEMM).
 struct LnQuantOut {
   uint8_t* q;       // [M, ldq] e4m3
   long ldq;
   float* scale;     // QM 1: [M]
-  uint8_t* mx;      // QM 2: block-major E8M0, mx[kb * mx_rows + perm(row)] (gemm_mxfp8.hip)
+  uint8_t* mx;      // QM 2: block-major E8M0, mx[kb * mx_rows + mx_scale_row(row)] (quant.h)
   long mx_rows;
 };
 
@@ -95,21 +96,20 @@ MC_NO_PK_F32 __global__ __launch_bounds__(256) void ln_modulate_kernel(const flo
       *(u32x2*)(out + (size_t)row * ldo + e) = w;
     }
   }
-  if constexpr (QM == 1) {   // one scale per row: max|row| / 448
+  if constexpr (QM == 1) {   // one scale per row (quant.h: fp8_row_scale)
     float amax = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i)
       amax = fmaxf(fmaxf(amax, fmaxf(fabsf(v[i][0]), fabsf(v[i][1]))), fmaxf(fabsf(v[i][2]), fabsf(v[i][3])));
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
-    const float sc1 = amax > 0.f ? amax * (1.0f / 448.0f) : 1.0f;
+    const float sc1 = fp8_row_scale(amax);
     const float inv = 1.0f / sc1;
     if (lane == 0) qo.scale[row] = sc1;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-      int w = __builtin_amdgcn_cvt_pk_fp8_f32(v[i][0] * inv, v[i][1] * inv, 0, false);
-      w = __builtin_amdgcn_cvt_pk_fp8_f32(v[i][2] * inv, v[i][3] * inv, w, true);
-      *(int*)(qo.q + (size_t)row * qo.ldq + i * 256 + lane * 4) = w;
+      *(int*)(qo.q + (size_t)row * qo.ldq + i * 256 + lane * 4) =
+          pack4_e4m3(v[i][0], v[i][1], v[i][2], v[i][3], inv);
     }
   }
   if constexpr (QM == 2) {   // MX: the 32-element block of (i, lane / 8) sits in 8 neighbouring lanes
@@ -119,20 +119,12 @@ MC_NO_PK_F32 __global__ __launch_bounds__(256) void ln_modulate_kernel(const flo
       amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
       amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
       amax = fmaxf(amax, __shfl_xor(amax, 4, 64));
-      int ex = -127;
-      if (amax > 0.f) {   // e = ceil(log2(amax / 448)), as quantize_rows_mx_kernel
-        int fx;
-        const float f = frexpf(amax * (1.0f / 448.0f), &fx);
-        ex = (f == 0.5f) ? fx - 1 : fx;
-        ex = max(-127, min(127, ex));
-      }
-      const float inv = __uint_as_float((uint32_t)(127 - ex) << 23);
-      int w = __builtin_amdgcn_cvt_pk_fp8_f32(v[i][0] * inv, v[i][1] * inv, 0, false);
-      w = __builtin_amdgcn_cvt_pk_fp8_f32(v[i][2] * inv, v[i][3] * inv, w, true);
-      *(int*)(qo.q + (size_t)row * qo.ldq + i * 256 + lane * 4) = w;
+      const int ex = mx_exponent(amax);
+      const float inv = mx_inv_scale(ex);
+      *(int*)(qo.q + (size_t)row * qo.ldq + i * 256 + lane * 4) =
+          pack4_e4m3(v[i][0], v[i][1], v[i][2], v[i][3], inv);
       if ((lane & 7) == 0)
-        qo.mx[(size_t)(i * 8 + (lane >> 3)) * qo.mx_rows + ((row & ~63) | ((row & 15) << 2) | ((row >> 4) & 3))] =
-            (uint8_t)(ex + 127);
+        qo.mx[(size_t)(i * 8 + (lane >> 3)) * qo.mx_rows + mx_scale_row(row)] = mx_scale_byte(ex);
     }
   }
 }
@@ -375,7 +367,7 @@ __global__ __launch_bounds__(256) void quantize_rows_fp8_kernel(const bf16_t* __
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
-  const float s = amax > 0.f ? amax * (1.0f / 448.0f) : 1.0f;
+  const float s = fp8_row_scale(amax);
   const float inv = 1.0f / s;
   if (lane == 0) scale[row] = s;
   for (int k = lane * 4; k < K; k += 256) {
@@ -387,9 +379,7 @@ __global__ __launch_bounds__(256) void quantize_rows_fp8_kernel(const bf16_t* __
       v = f32x4{__uint_as_float(b[0] << 16), __uint_as_float(b[0] & 0xffff0000u), __uint_as_float(b[1] << 16),
                 __uint_as_float(b[1] & 0xffff0000u)};
     }
-    int w = __builtin_amdgcn_cvt_pk_fp8_f32(v[0] * inv, v[1] * inv, 0, false);
-    w = __builtin_amdgcn_cvt_pk_fp8_f32(v[2] * inv, v[3] * inv, w, true);
-    *(int*)(q + (size_t)row * ldq + k) = w;
+    *(int*)(q + (size_t)row * ldq + k) = pack4_e4m3(v[0], v[1], v[2], v[3], inv);
   }
 }
 

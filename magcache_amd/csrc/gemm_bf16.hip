@@ -27,6 +27,7 @@ namespace mc {
 namespace {
 
 constexpr int BM = 128, BN = 128, BK = 64;
+static_assert(BM == BN, "MC_GROUPED_TILE (common.h) places square tiles");
 constexpr int STAGE_BYTES = (BM + BN) * BK * 2;  // 32 KiB
 constexpr int OPND_BYTES = BM * BK * 2;          // 16 KiB
 constexpr int GROUP_M = 8;
@@ -41,15 +42,9 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_tn_kernel(GemmParams p, int 
   const int l31 = lane & 31;
 
   // ---- tile mapping: XCD-contiguous, grouped along M so a group of tiles shares W panels in L2
-  int v = xcd_remap(blockIdx.x, tilesM * tilesN);
-  const int per_group = GROUP_M * tilesN;
-  const int grp = v / per_group;
-  const int first_m = grp * GROUP_M;
-  const int gsz = min(tilesM - first_m, GROUP_M);
-  const int in_grp = v - grp * per_group;
-  const int tm = first_m + in_grp % gsz;
-  const int tn = in_grp / gsz;
-  const int m0 = tm * BM, n0 = tn * BN;
+  const int v = xcd_remap(blockIdx.x, tilesM * tilesN);
+  int m0, n0;
+  MC_GROUPED_TILE(v, tilesM, tilesN, GROUP_M, BM, m0, n0);
 
   // ---- global_load_lds source pointers: 4 x 1 KiB pieces per operand per wave
   // piece g covers tile rows g*8 .. g*8+7; lane -> (row = g*8 + lane/8, slot = lane%8),
@@ -192,12 +187,8 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_tn_kernel(GemmParams p, int 
 template <int EPI>
 hipError_t launch_t(const GemmParams& p, hipStream_t stream) {
   const int tilesM = (p.M + BM - 1) / BM, tilesN = (p.N + BN - 1) / BN;
-  static std::atomic<uint64_t> lds_ready{0};
-  if (hipError_t e = ensure_dynamic_lds((const void*)gemm_bf16_tn_kernel<EPI>, 2 * STAGE_BYTES, lds_ready); e != hipSuccess)
-    return e;
-  hipLaunchKernelGGL((gemm_bf16_tn_kernel<EPI>), dim3(tilesM * tilesN), dim3(256), 2 * STAGE_BYTES, stream, p,
-                     tilesM, tilesN);
-  return hipGetLastError();
+  return launch_dynamic_lds<gemm_bf16_tn_kernel<EPI>>(dim3(tilesM * tilesN), dim3(256), 2 * STAGE_BYTES, stream, p, tilesM,
+                                                      tilesN);
 }
 
 }  // namespace

@@ -14,7 +14,8 @@
 // 16 K MACs through the register file, a 16x16x32 2 KB per 8 K MACs.  Round 1's kernel was the same pipeline on
 // 32x32x16 (retired in round 4; git history has it as tools/kernels_ab/gemm_bf16_big_32x32.hip) and stopped at ~1.2 PFLOP/s in its main loop.
 //
-// Geometry
+// Geometry (tile and LDS constants, piece and swizzle arithmetic, the LDS-DMA issue and the barrier / wait macros are shared
+// with gemm_fp8_big.hip and gemm_mxfp8.hip: gemm_pipe8.h)
 //   * workgroup = 8 waves (2 along M x 4 along N), one 256x256 output tile, 1 workgroup per CU
 //     (128 KiB LDS); wave tile 128(M) x 64(N) = 8 x 4 MFMA blocks of 16x16 = 128 fp32 accumulators.
 //   * MFMA issued "swapped" (operand A = weight rows, B = activation rows) like the 128^2 kernel, so
@@ -50,30 +51,22 @@
 //   their latency hides behind the epilogue: +5.3 % (QKV), +2.8 % (FFN-1), +4.6 % (cross-attention Q shape),
 //   profiles/r02/kbench_gemm_persistent.log.  The residual epilogues (loads in every quad, which the compiler makes wait
 //   for everything queued before them) keep one tile per workgroup.
-// the LDS-DMA asm below names m0 in its clobber list on purpose (reserved register: the compiler only warns)
+// the LDS-DMA asm (below and in gemm_pipe8.h) names m0 in its clobber list on purpose (reserved register: the compiler only warns)
 #pragma clang diagnostic ignored "-Winline-asm"
 #include "common.h"
 #include <type_traits>
 
 #include "gemm_epilogue.h"
+#include "gemm_pipe8.h"
 #include "ops.h"
 
 namespace mc {
 
 namespace {
 
-constexpr int TB = 256;                // tile edge (M and N)
-constexpr int BK = 64;
-constexpr int HALF_BYTES = 128 * BK * 2;   // 16 KiB
-constexpr int STAGE_BYTES = 4 * HALF_BYTES;  // Am0 | Am1 | Wn0 | Wn1
-constexpr int OFF_AM0 = 0, OFF_AM1 = HALF_BYTES, OFF_WN0 = 2 * HALF_BYTES, OFF_WN1 = 3 * HALF_BYTES;
-// tile rasterisation: an XCD walks groups of GROUP_M M-tiles x all N-tiles, M fastest.  Measured (kbench, M = 32768):
-// 8 for N = 4608 (QKV: 1176 vs 1168 TF), 4 for N = 8960 (FFN-1: 1138 vs 1096 TF), no difference for N = 1536.
-#ifdef MC_GROUP_M
-#define MC_GROUP_M_OF(tilesN) (MC_GROUP_M)
-#else
-#define MC_GROUP_M_OF(tilesN) ((tilesN) >= 32 ? 4 : 8)
-#endif
+using namespace pipe8;
+
+constexpr int BK = 64;                 // bf16 elements of K per tile (ROW_BYTES / 2)
 
 #ifndef MC_ABL
 #define MC_ABL 0
@@ -92,25 +85,20 @@ constexpr int OFF_AM0 = 0, OFF_AM1 = HALF_BYTES, OFF_WN0 = 2 * HALF_BYTES, OFF_W
 #define MC_VAR 0
 #endif
 
-// end-of-interval wait: at most n LDS-DMA instructions of this wave still in flight.  (ds_reads need
-// no wait here: a region is re-filled two barriers after its last read, and every read has been
-// consumed by an MFMA -- i.e. waited for -- one barrier earlier.)
-#define MC_WAIT_(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
+// This file alone (test-only, built in variants by the tools above) wraps the wait and the barrier of gemm_pipe8.h in its
+// MC_VAR / MC_ABL switches
 #define MC_WAIT(n)                                       \
   do {                                                   \
     if (MC_VAR & 16) MC_WAIT_(0);                        \
     else if ((MC_VAR & 2) && (n) == 10) MC_WAIT_(8);     \
     else MC_WAIT_(n);                                    \
   } while (0)
-// interval boundary: nothing (MFMAs included -- they are register-only and would otherwise drift
-// across the asm statements) is scheduled across it
+#undef MC_BARRIER
 #define MC_BARRIER()                                          \
   do {                                                        \
     if (!(MC_ABL & 8)) asm volatile("s_barrier" ::: "memory"); \
     __builtin_amdgcn_sched_barrier(0);                        \
   } while (0)
-
-#define MC_PIN() __builtin_amdgcn_sched_barrier(0)
 
 // epilogues that run the persistent tile loop (one workgroup per CU walks tiles; the next tile's first two K tiles are
 // queued before the epilogue).  MC_PERSIST_RESID: the residual epilogues too (their x loads then queue behind that LDS-DMA).
@@ -143,29 +131,19 @@ __global__ __launch_bounds__(512, 2) void gemm_big_kernel(GemmParams p, int tile
   const int ntiles = tilesM * tilesN;
   const int tstride = PERSIST ? (int)gridDim.x : ntiles;
   int m0 = 0, n0 = 0;
-  // ---- LDS-DMA sources.  Piece g (0..15) of a half = image rows 8g..8g+7; a wave owns pieces
-  // 2wv, 2wv+1; lane -> (image row = 8g + lane/8, slot = lane%8), source chunk = slot ^ ((row>>1)&7).
-  // image row r of Am<h>: tile row (r>>6)*128 + h*64 + (r&63);  of Wn<h>: (r>>5)*64 + h*32 + (r&31)
+  // ---- LDS-DMA sources (pieces, image rows and swizzled chunks: gemm_pipe8.h); a partial last M tile re-reads row M-1
   uint32_t srcA[2][2], srcW[2][2];  // [half][piece] BYTE offsets from p.A / p.W (without k)
   auto setup_tile = [&](int t) {
     const int v = xcd_remap(t, ntiles);
-    const int per_group = GROUP_M * tilesN;
-    const int grp = v / per_group;
-    const int first_m = grp * GROUP_M;
-    const int gsz = min(tilesM - first_m, GROUP_M);
-    const int in_grp = v - grp * per_group;
-    const int tm = first_m + in_grp % gsz;
-    const int tn = in_grp / gsz;
-    m0 = tm * TB;
-    n0 = tn * TB;
+    MC_GROUPED_TILE(v, tilesM, tilesN, GROUP_M, TB, m0, n0);
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
-        const int r = (wv * 2 + j) * 8 + (lane >> 3);
-        const int chunk = (lane & 7) ^ ((r >> 1) & 7);
-        const int ra = min(m0 + (r >> 6) * 128 + h * 64 + (r & 63), p.M - 1);
-        const int rw = n0 + (r >> 5) * 64 + h * 32 + (r & 31);
+        const int r = MC_PIECE_ROW(wv, j, lane);
+        const int chunk = MC_PIECE_CHUNK(r, lane);
+        const int ra = min(m0 + MC_A_TILE_ROW(r, h), p.M - 1);
+        const int rw = n0 + MC_W_TILE_ROW(r, h);
         srcA[h][j] = ((uint32_t)ra * (uint32_t)p.lda) * 2 + chunk * 16;
         srcW[h][j] = ((uint32_t)rw * (uint32_t)p.ldw) * 2 + chunk * 16;
       }
@@ -208,13 +186,8 @@ __global__ __launch_bounds__(512, 2) void gemm_big_kernel(GemmParams p, int tile
 
   const int nk = p.K / BK;
 
-  // LDS-DMA issue in inline asm: hipcc's waitcnt pass makes every ds_read that follows a
-  // __builtin_amdgcn_global_load_lds wait for it (vmcnt(0) in the loop); an asm DMA is invisible to
-  // that pass and ordered only by the counted waits below.  One 1 KiB piece per call.  saddr form: 64-bit
-  // uniform base in SGPRs + one 32-bit byte offset per lane; M0 = LDS byte address of the piece
-  // (wave-uniform); s_nop covers the SALU-write-M0 -> LDS-DMA hazard.
+  // dma_piece (gemm_pipe8.h), or its MC_VAR & 4 form
   auto dma1 = [&](const bf16_t* base, uint32_t off, uint32_t lds) {
-    // M0 is clobbered, not saved: nothing the compiler emits in this kernel reads it
     if (MC_VAR & 4) {
       asm volatile(
           "s_mov_b32 m0, %1\n\t"
@@ -224,13 +197,7 @@ __global__ __launch_bounds__(512, 2) void gemm_big_kernel(GemmParams p, int tile
           : "v"(off), "s"(lds), "s"(base)
           : "memory", "m0");
     } else {
-      asm volatile(
-          "s_mov_b32 m0, %1\n\t"
-          "s_nop 0\n\t"
-          "global_load_lds_dwordx4 %0, %2"
-          :
-          : "v"(off), "s"(lds), "s"(base)
-          : "memory", "m0");
+      dma_piece(base, off, lds);
     }
   };
   // piece j (0/1) of half h of K tile kt into stage st (= kt & 1)
@@ -495,9 +462,6 @@ __global__ __launch_bounds__(512, 2) void gemm_big_kernel(GemmParams p, int tile
 template <int EPI>
 hipError_t launch_big_t(const GemmParams& p, hipStream_t stream) {
   const int tilesM = (p.M + TB - 1) / TB, tilesN = p.N / TB;
-  static std::atomic<uint64_t> lds_ready{0};
-  if (hipError_t e = ensure_dynamic_lds((const void*)gemm_big_kernel<EPI>, 2 * STAGE_BYTES, lds_ready); e != hipSuccess)
-    return e;
   int grid = tilesM * tilesN;
   static int n_cu = 0;
   if (!n_cu) {
@@ -509,9 +473,8 @@ hipError_t launch_big_t(const GemmParams& p, hipStream_t stream) {
   if (big_persistent(EPI)) {
     if (grid > n_cu) grid = n_cu;
   }
-  hipLaunchKernelGGL((gemm_big_kernel<EPI>), dim3(grid), dim3(512), 2 * STAGE_BYTES, stream, p,
-                     tilesM, tilesN, MC_GROUP_M_OF(tilesN));
-  return hipGetLastError();
+  return launch_dynamic_lds<gemm_big_kernel<EPI>>(dim3(grid), dim3(512), 2 * STAGE_BYTES, stream, p, tilesM, tilesN,
+                                                  MC_GROUP_M_OF(tilesN));
 }
 
 }  // namespace

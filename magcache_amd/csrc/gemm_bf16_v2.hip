@@ -92,18 +92,12 @@ __device__ __forceinline__ float agpr_read(float a) {
   return x;
 }
 
-// virtual work unit vt (XCD-contiguous, v2_unit) -> K slice and output tile origin; tiles grouped along M (as gemm_bf16_big.hip)
+// virtual work unit vt (XCD-contiguous, v2_unit) -> K slice and output tile origin; tiles grouped along M (MC_GROUPED_TILE, common.h)
 __device__ __forceinline__ void v2_place(int vt, int tilesM, int tilesN, int GROUP_M, int& slice, int& tile, int& tm0, int& tn0) {
   const int ntiles = tilesM * tilesN;
   slice = vt / ntiles;
   tile = vt - slice * ntiles;
-  const int per_group = GROUP_M * tilesN;
-  const int grp = tile / per_group;
-  const int first_m = grp * GROUP_M;
-  const int gsz = min(tilesM - first_m, GROUP_M);
-  const int in_grp = tile - grp * per_group;
-  tm0 = (first_m + in_grp % gsz) * TB;
-  tn0 = (in_grp / gsz) * TB;
+  MC_GROUPED_TILE(tile, tilesM, tilesN, GROUP_M, TB, tm0, tn0);
 }
 
 // split-K scratch: the accumulators of (slice, tile) in the MFMA layout itself -- quad (nb, mb) of wave w is 64 lanes x 16
@@ -647,8 +641,6 @@ inline int v2_group_m(int tilesN) { return tilesN >= 32 ? MC_V2_GROUP_M_WIDE : t
 template <int EPI>
 hipError_t launch_v2_t(const GemmParams& p, hipStream_t stream, int slices = 1) {
   const int tilesM = (p.M + TB - 1) / TB, tilesN = p.N / TB;
-  static std::atomic<uint64_t> lds_ready{0};
-  if (hipError_t e = ensure_dynamic_lds((const void*)gemm_v2_kernel<EPI>, V2_LDS_BYTES, lds_ready); e != hipSuccess) return e;
   int grid = tilesM * tilesN * slices;
   bf16_t* scratch = nullptr;
 #if MC_GEMM_V2_PERSIST
@@ -666,9 +658,8 @@ hipError_t launch_v2_t(const GemmParams& p, hipStream_t stream, int slices = 1) 
   if (EPI == EPI_RESID_GATE && tilesM * tilesN > grid && g_gemm_defer) scratch = v2_scratch(stream, n_cu);
 #endif
 #endif
-  hipLaunchKernelGGL((gemm_v2_kernel<EPI>), dim3(grid), dim3(256), V2_LDS_BYTES, stream, p, tilesM, tilesN,
-                     v2_group_m(tilesN), scratch, slices);
-  return hipGetLastError();
+  return launch_dynamic_lds<gemm_v2_kernel<EPI>>(dim3(grid), dim3(256), V2_LDS_BYTES, stream, p, tilesM, tilesN,
+                                                 v2_group_m(tilesN), scratch, slices);
 }
 
 template <int EPI>

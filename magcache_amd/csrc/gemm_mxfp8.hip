@@ -3,8 +3,8 @@
 //            (+ the fused epilogues of gemm_epilogue.h)
 // A_q, W_q: OCP e4m3 bytes, K contiguous; sa, sw: E8M0 scale bytes, one per (row, 32 consecutive k) -- the OCP
 // microscaling (MX) format, multiplied by the matrix core itself (HW-fused dequantisation), stored block-major with
-// the rows of every group of 64 interleaved 16 x 4: s[kb * rows_pad + perm(row)], perm(row) = (row & ~63) |
-// ((row & 15) << 2) | ((row >> 4) & 3) -- the four 16-row blocks a lane works on are then the four bytes of ONE dword.
+// the rows of every group of 64 interleaved 16 x 4: s[kb * rows_pad + mx_scale_row(row)] (quant.h) -- the four 16-row
+// blocks a lane works on are then the four bytes of ONE dword.
 // An OPTIONAL speed / quality mode of the engine (mc_config.fp8_linear = 2), never the default and never the headline (BASELINE.json config 4 "fp8 MFMA weight path"; no reference counterpart: the reference runs
 // bf16 autocast, MagCache4Wan2.1/magcache_generate.py:297-298).  The older per-row-scaled fp8 path (gemm_fp8_big.hip,
 // fp8_linear = 1, 32x32x64 MFMA with unit block scales) stays for comparison.
@@ -15,8 +15,8 @@
 // multiplies MX block g = k 32 g .. 32 g + 31 of that row, wherever its elements sit; the first operand's rows are
 // D's rows; C/D layout as every 16x16 MFMA (col = l % 16, row = 4 (l / 16) + reg).
 //
-// The kernel is gemm_bf16_big.hip's pipeline with a K tile of 128 fp8 (the same 128-byte LDS rows, XOR swizzle, LDS-DMA
-// pieces, four intervals per K tile, counted vmcnt waits):
+// The kernel is the 8-wave LDS-DMA pipeline of gemm_pipe8.h (128-byte LDS rows, XOR swizzle, LDS-DMA pieces) with a K tile
+// of 128 fp8, gemm_bf16_big.hip's four intervals per K tile and counted vmcnt waits:
 //   * 8 waves (2 x 4), wave tile 128(M) x 64(N), one interval = one 64 x 32 quadrant = 8 MFMAs of 16x16x128
 //     (the same matrix-pipe time as the 16 bf16 MFMAs of 16x16x32 it replaces, for twice the k);
 //   * a fragment is 32 bytes per lane = two ds_read_b128: 16-byte chunks kgrp and 4 + kgrp of the 128-byte row (the
@@ -35,11 +35,13 @@
 // row and that row's scale bytes only -- an MFMA keeps the rows of its activation operand apart --, so rows >= M of A and
 // their scale bytes never reach a stored value, and a launch over M rows gives rows [0, M) the bits a launch over ceil256(M)
 // rows gives them.
-// the LDS-DMA asm below names m0 in its clobber list on purpose (reserved register: the compiler only warns)
+// the LDS-DMA asm (below and in gemm_pipe8.h) names m0 in its clobber list on purpose (reserved register: the compiler only warns)
 #pragma clang diagnostic ignored "-Winline-asm"
 #include "common.h"
 #include "gemm_epilogue.h"
+#include "gemm_pipe8.h"
 #include "ops.h"
+#include "quant.h"
 
 namespace mc {
 
@@ -48,25 +50,14 @@ namespace {
 typedef __attribute__((ext_vector_type(8))) int i32x8;
 typedef __attribute__((ext_vector_type(4))) int i32x4v;
 
-constexpr int TB = 256;
+using namespace pipe8;
+
 constexpr int BKB = 128;                         // bytes (= fp8 elements) of K per tile
-constexpr int HALF_BYTES = 128 * BKB;            // 16 KiB
-constexpr int STAGE_BYTES = 4 * HALF_BYTES;      // Am0 | Am1 | Wn0 | Wn1
-constexpr int OFF_AM0 = 0, OFF_AM1 = HALF_BYTES, OFF_WN0 = 2 * HALF_BYTES, OFF_WN1 = 3 * HALF_BYTES;
 constexpr int SC_KSTRIDE = 320;                  // bytes between the k blocks of a scale image (256 rows + 64 pad: banks)
 constexpr int SC_OPND = 4 * SC_KSTRIDE;          // one operand's scales of a K tile
 constexpr int SC_STAGE = 2 * SC_OPND;            // A | W
 constexpr int SC_BASE = 2 * STAGE_BYTES;         // scale images behind the two data stages
 constexpr int LDS_TOTAL = SC_BASE + 2 * SC_STAGE;
-#define MC_MX_GROUP_M_OF(tilesN) ((tilesN) >= 32 ? 4 : 8)
-
-#define MC_PIN() __builtin_amdgcn_sched_barrier(0)
-#define MC_WAIT_(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
-#define MC_BARRIER()                              \
-  do {                                            \
-    asm volatile("s_barrier" ::: "memory");       \
-    __builtin_amdgcn_sched_barrier(0);            \
-  } while (0)
 
 struct FragA {   // one A half of a wave: 64 rows x 128 k = 4 m blocks of 16, 32 bytes per lane each
   i32x8 v[4];
@@ -87,18 +78,11 @@ __global__ __launch_bounds__(512, 2) void gemm_mx_kernel(GemmParams p, int tiles
   const int kgrp = lane >> 4;
   const int wr = wv >> 2, wc = wv & 3;
 
-  int v = xcd_remap(blockIdx.x, tilesM * tilesN);
-  const int per_group = GROUP_M * tilesN;
-  const int grp = v / per_group;
-  const int first_m = grp * GROUP_M;
-  const int gsz = min(tilesM - first_m, GROUP_M);
-  const int in_grp = v - grp * per_group;
-  const int tm = first_m + in_grp % gsz;
-  const int tn = in_grp / gsz;
-  const int m0 = tm * TB, n0 = tn * TB;
+  const int v = xcd_remap(blockIdx.x, tilesM * tilesN);
+  int m0, n0;
+  MC_GROUPED_TILE(v, tilesM, tilesN, GROUP_M, TB, m0, n0);
 
-  // ---- LDS-DMA sources of the data halves: exactly gemm_bf16_big.hip with byte strides (an fp8 row of a K tile is the
-  // same 128 bytes as a bf16 row of 64 k)
+  // ---- LDS-DMA sources of the data halves: the pieces, image rows and swizzled chunks of gemm_pipe8.h
   const uint8_t* Aq = (const uint8_t*)p.A;
   const uint8_t* Wq = (const uint8_t*)p.W;
   // One LDS-DMA instruction moves 8 consecutive rows (lane / 8) of a half, from a wave-uniform first row: the lane part of
@@ -113,14 +97,14 @@ __global__ __launch_bounds__(512, 2) void gemm_mx_kernel(GemmParams p, int tiles
   uint32_t limA[2][2];
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
-    const int r0 = (wv * 2 + j) * 8;
+    const int r0 = MC_PIECE_ROW(wv, j, 0);   // the piece's first image row
     const int r = r0 + (lane >> 3);
-    const int chunk = (lane & 7) ^ ((r >> 1) & 7);
+    const int chunk = MC_PIECE_CHUNK(r, lane);
     srcA[j] = (uint32_t)(lane >> 3) * (uint32_t)p.lda + chunk * 16;
-    srcW[j] = (uint32_t)(n0 + (r >> 5) * 64 + (r & 31)) * (uint32_t)p.ldw + chunk * 16;
+    srcW[j] = (uint32_t)(n0 + MC_W_TILE_ROW(r, 0)) * (uint32_t)p.ldw + chunk * 16;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-      const int row = __builtin_amdgcn_readfirstlane(min(m0 + (r0 >> 6) * 128 + h * 64 + (r0 & 63), p.M - 1));
+      const int row = __builtin_amdgcn_readfirstlane(min(m0 + MC_A_TILE_ROW(r0, h), p.M - 1));
       baseA[h][j] = (size_t)row * p.lda;
       limA[h][j] = (uint32_t)(min(p.M - row, 8) - 1) * (uint32_t)p.lda + 112;
     }
@@ -165,15 +149,7 @@ __global__ __launch_bounds__(512, 2) void gemm_mx_kernel(GemmParams p, int tiles
 
   const int nk = p.K / BKB;
 
-  auto dma1 = [&](const uint8_t* base, uint32_t off, uint32_t lds) {
-    asm volatile(
-        "s_mov_b32 m0, %1\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %0, %2"
-        :
-        : "v"(off), "s"(lds), "s"(base)
-        : "memory", "m0");
-  };
+  // A pieces: dma_piece (gemm_pipe8.h) with the row clamp in front of the load
   // (the clamp sits inside the asm: as C++ it is loop invariant and the compiler keeps the four clamped offsets in
   // VGPRs this kernel does not have; the v_min also fills the wait state between the m0 write and its use)
   auto dma_a1 = [&](int kt, int st, int h, int j) {
@@ -188,7 +164,7 @@ __global__ __launch_bounds__(512, 2) void gemm_mx_kernel(GemmParams p, int tiles
         : "memory", "m0");
   };
   auto dma_w1 = [&](int kt, int st, int h, int j) {
-    dma1(Wq + (size_t)kt * BKB + (h ? halfW : 0), srcW[j], dma_lds + st * STAGE_BYTES + (h ? OFF_WN1 : OFF_WN0) + j * 1024);
+    dma_piece(Wq + (size_t)kt * BKB + (h ? halfW : 0), srcW[j], dma_lds + st * STAGE_BYTES + (h ? OFF_WN1 : OFF_WN0) + j * 1024);
   };
   auto dma_a = [&](int kt, int st, int h) { dma_a1(kt, st, h, 0); dma_a1(kt, st, h, 1); };
   auto dma_w = [&](int kt, int st, int h) { dma_w1(kt, st, h, 0); dma_w1(kt, st, h, 1); };
@@ -224,7 +200,7 @@ __global__ __launch_bounds__(512, 2) void gemm_mx_kernel(GemmParams p, int tiles
 #pragma unroll
     for (int i = 0; i < 2; ++i) read_w1(st, h, i, f);
   };
-  // MFMA i (0..7) of an interval: m block i/2, n block i%2.  asm with the accumulator pinned (see gemm_bf16_big.hip);
+  // MFMA i (0..7) of an interval: m block i/2, n block i%2.  asm with the accumulator pinned (why: gemm_bf16_big.hip, mma1);
   // first operand = weight rows (D rows = n), its scale first; op_sel / op_sel_hi = low / high bit of the scale byte index
   // of (first, second) operand: W byte 2 nh + nb, A byte mb.
 #define MC_MX_MFMA(SEL)                                                                                  \
@@ -322,7 +298,7 @@ __global__ __launch_bounds__(512, 2) void gemm_mx_kernel(GemmParams p, int tiles
 #undef MC_RD_A
   asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");   // XDL write -> VALU read of the accumulators (asm MFMAs)
 
-  // ---- epilogue: identical to gemm_bf16_big.hip; rows m >= M of a partial last tile are skipped (the lanes of one row, l15,
+  // ---- epilogue: the accumulator layout of gemm_bf16_big.hip (same MFMA shape, same wave tile); rows m >= M of a partial last tile are skipped (the lanes of one row, l15,
   // skip together: the shuffles of EPI_GELU_MXFP8 stay among active lanes)
 #pragma unroll
   for (int mh = 0; mh < 2; ++mh) {
@@ -335,7 +311,7 @@ __global__ __launch_bounds__(512, 2) void gemm_mx_kernel(GemmParams p, int tiles
         if constexpr (EPI == EPI_GELU_MXFP8) {
           // The 32 columns n0 + wc*64 + nh*32 .. +31 of row m are ONE MX block of the next GEMM's A operand: 8 values in
           // this lane (nb = 0, 1), the rest in the lanes kgrp' != kgrp with the same l15 (lane ^ 16, ^ 32).  Values as
-          // the bf16 epilogue would store them; e = ceil(log2(amax / 448)) and the bytes as quantize_rows_mx_kernel.
+          // the bf16 epilogue would store them; exponent, bytes and scale row by the helpers of quant.h.
           const int nblk0 = n0 + wc * 64 + nh * 32;
           float y[8];
           float amax = 0.f;
@@ -353,22 +329,14 @@ __global__ __launch_bounds__(512, 2) void gemm_mx_kernel(GemmParams p, int tiles
           }
           amax = fmaxf(amax, __shfl_xor(amax, 16, 64));
           amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
-          int ex = -127;
-          if (amax > 0.f) {
-            int fx;
-            const float f = frexpf(amax * (1.0f / 448.0f), &fx);
-            ex = (f == 0.5f) ? fx - 1 : fx;
-            ex = max(-127, min(127, ex));
-          }
-          const float inv = __uint_as_float((uint32_t)(127 - ex) << 23);
+          const int ex = mx_exponent(amax);
+          const float inv = mx_inv_scale(ex);
 #pragma unroll
           for (int nb = 0; nb < 2; ++nb) {
-            int w = __builtin_amdgcn_cvt_pk_fp8_f32(y[4 * nb] * inv, y[4 * nb + 1] * inv, 0, false);
-            w = __builtin_amdgcn_cvt_pk_fp8_f32(y[4 * nb + 2] * inv, y[4 * nb + 3] * inv, w, true);
+            const int w = pack4_e4m3(y[4 * nb], y[4 * nb + 1], y[4 * nb + 2], y[4 * nb + 3], inv);
             *(int*)(p.Cq + (size_t)m * p.ldcq + nblk0 + nb * 16 + 4 * kgrp) = w;
           }
-          if (kgrp == 0)
-            p.c_mx[(size_t)(nblk0 >> 5) * p.mx_rows_c + ((m & ~63) | ((m & 15) << 2) | ((m >> 4) & 3))] = (uint8_t)(ex + 127);
+          if (kgrp == 0) p.c_mx[(size_t)(nblk0 >> 5) * p.mx_rows_c + MC_MX_SCALE_ROW(m)] = mx_scale_byte(ex);   // (macro: quant.h)
           continue;
         }
 #pragma unroll
@@ -386,17 +354,13 @@ __global__ __launch_bounds__(512, 2) void gemm_mx_kernel(GemmParams p, int tiles
 template <int EPI>
 hipError_t launch_mx_t(const GemmParams& p, hipStream_t stream) {
   const int tilesM = (p.M + TB - 1) / TB, tilesN = p.N / TB;
-  static std::atomic<uint64_t> lds_ready{0};
-  if (hipError_t e = ensure_dynamic_lds((const void*)gemm_mx_kernel<EPI>, LDS_TOTAL, lds_ready); e != hipSuccess) return e;
-  hipLaunchKernelGGL((gemm_mx_kernel<EPI>), dim3(tilesM * tilesN), dim3(512), LDS_TOTAL, stream, p, tilesM, tilesN,
-                     MC_MX_GROUP_M_OF(tilesN));
-  return hipGetLastError();
+  return launch_dynamic_lds<gemm_mx_kernel<EPI>>(dim3(tilesM * tilesN), dim3(512), LDS_TOTAL, stream, p, tilesM, tilesN,
+                                                 MC_GROUP_M_OF(tilesN));
 }
 
 // ------------------------------------------------------------------ MX quantisation of rows
-// One wave per row; lane b (+64, +128, ...) owns the 32-element block b: scale exponent e = ceil(log2(amax / 448))
-// (clamped to [-127, 127]; 448 = the largest e4m3 value, so nothing saturates), elements e4m3(x * 2^-e), scale byte e + 127
-// at s[b * rows_pad + perm(row)] (perm: see the top of the file).  An all-zero block gets e = -127 and zeros.
+// One wave per row; lane b (+64, +128, ...) owns the 32-element block b: scale exponent e = mx_exponent(amax), elements
+// e4m3(x * 2^-e), scale byte e + 127 at s[b * rows_pad + mx_scale_row(row)] (all of it quant.h).
 __global__ __launch_bounds__(256) void quantize_rows_mx_kernel(const bf16_t* __restrict__ x, const float* __restrict__ xf,
                                                                long ldx, int M, int K, uint8_t* __restrict__ q, long ldq,
                                                                uint8_t* __restrict__ s, long rows_pad) {
@@ -425,27 +389,15 @@ __global__ __launch_bounds__(256) void quantize_rows_mx_kernel(const bf16_t* __r
     float amax = 0.f;
 #pragma unroll
     for (int i = 0; i < 32; ++i) amax = fmaxf(amax, fabsf(v[i]));
-    // e = ceil(log2(amax / 448)), exactly: frexp gives amax / 448 = f * 2^ex with f in [0.5, 1) -> ceil(log2) = ex unless
-    // f == 0.5 (a power of two), then ex - 1
-    int e = -127;
-    if (amax > 0.f) {
-      int ex;
-      const float f = frexpf(amax * (1.0f / 448.0f), &ex);
-      e = (f == 0.5f) ? ex - 1 : ex;
-      e = max(-127, min(127, e));
-    }
-    const float inv = __uint_as_float((uint32_t)(127 - e) << 23);   // 2^-e (e in [-127, 127] -> exponent field 0..254)
+    const int e = mx_exponent(amax);
+    const float inv = mx_inv_scale(e);
     uint32_t w[8];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      int t = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * i] * inv, v[4 * i + 1] * inv, 0, false);
-      t = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * i + 2] * inv, v[4 * i + 3] * inv, t, true);
-      w[i] = (uint32_t)t;
-    }
+    for (int i = 0; i < 8; ++i) w[i] = (uint32_t)pack4_e4m3(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3], inv);
     u32x4* dst = (u32x4*)(q + (size_t)row * ldq + b * 32);
     dst[0] = u32x4{w[0], w[1], w[2], w[3]};
     dst[1] = u32x4{w[4], w[5], w[6], w[7]};
-    s[(size_t)b * rows_pad + ((row & ~63) | ((row & 15) << 2) | ((row >> 4) & 3))] = (uint8_t)(e + 127);
+    s[(size_t)b * rows_pad + mx_scale_row(row)] = mx_scale_byte(e);
   }
 }
 

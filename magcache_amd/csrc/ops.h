@@ -60,10 +60,10 @@ struct GemmParams {
   const float* a_scale;
   const float* w_scale;
   // MX fp8 GEMM (launch_gemm_mxfp8): A / W point to e4m3 bytes (lda / ldw in bytes), a_mx / w_mx to E8M0 scale bytes,
-  // block-major: scale of (row, k block kb of 32) at [kb * mx_rows + row]
+  // block-major: scale of (row, k block kb of 32) at [kb * mx_rows + mx_scale_row(row)] (quant.h)
   const uint8_t* a_mx; long mx_rows_a;
   const uint8_t* w_mx; long mx_rows_w;
-  // EPI_GELU_MXFP8: e4m3 output rows (ldcq bytes) and their block scales, c_mx[(n / 32) * mx_rows_c + perm(m)]
+  // EPI_GELU_MXFP8: e4m3 output rows (ldcq bytes) and their block scales, c_mx[(n / 32) * mx_rows_c + mx_scale_row(m)] (quant.h)
   uint8_t* Cq; long ldcq;
   uint8_t* c_mx; long mx_rows_c;
 };
@@ -93,7 +93,8 @@ extern int g_gemm_kernel;  // 0 by shape, 1 small, 2 big where supported (refere
 // fp8 (e4m3) operands, 256x256 tiles, v_mfma_f32_32x32x64_f8f6f4; K (fp8 elements) a multiple of 256
 hipError_t launch_gemm_fp8(const GemmParams& p, int epi, hipStream_t stream);
 bool gemm_fp8_supported(const GemmParams& p);
-// row-wise fp8 quantisation: q[m, :] = e4m3(x[m, :] / s[m]), s[m] = max|x[m, :]| / 448 (1 for an all-zero row).
+// row-wise fp8 quantisation: q[m, :] = e4m3(x[m, :] / s[m]), s[m] = max|x[m, :]| / 448 (1 for an all-zero row); the
+// arithmetic itself, shared with the fused producers of elementwise.hip: quant.h.
 // x bf16 (x_f32 null) or fp32.  Used for activations (per token) and for weights (per output channel).
 hipError_t launch_quantize_rows_fp8(const bf16_t* x, const float* x_f32, long ldx, int M, int K, uint8_t* q, long ldq,
                                     float* scale, hipStream_t stream);
@@ -101,7 +102,8 @@ hipError_t launch_quantize_rows_fp8(const bf16_t* x, const float* x_f32, long ld
 // MX block-scaled fp8 (gemm_mxfp8.hip): v_mfma_scale_f32_16x16x128_f8f6f4, one E8M0 scale per (row, 32 k)
 hipError_t launch_gemm_mxfp8(const GemmParams& p, int epi, hipStream_t stream);
 bool gemm_mxfp8_supported(const GemmParams& p);
-// q[m, kb*32 .. +31] = e4m3(x * 2^-e), e = ceil(log2(max|block| / 448)), scale byte e + 127 at s[kb * rows_pad + m]
+// q[m, kb*32 .. +31] = e4m3(x * 2^-e), e = ceil(log2(max|block| / 448)), scale byte e + 127 at
+// s[kb * rows_pad + mx_scale_row(m)]; exponent, packing and scale row are quant.h's, as in every fused producer
 hipError_t launch_quantize_rows_mx(const bf16_t* x, const float* x_f32, long ldx, int M, int K, uint8_t* q, long ldq,
                                    uint8_t* s, long rows_pad, hipStream_t stream);
 

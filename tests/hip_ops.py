@@ -105,11 +105,15 @@ def quantize_rows_mx(x):
     return q, s
 
 
+def mx_perm(rows):
+    """where the kernels keep the scale bytes of row `rows` (int tensor): mx_scale_row of csrc/quant.h, the rows of every
+    group of 64 interleaved 16 x 4"""
+    return (rows & ~63) | ((rows & 15) << 2) | ((rows >> 4) & 3)
+
+
 def mx_unpermute(s, M):
     """scales [K/32, rows_pad] in the kernel's row order -> [M, K/32] in natural order"""
-    rows = torch.arange(M, device=s.device)
-    pos = (rows & ~63) | ((rows & 15) << 2) | ((rows >> 4) & 3)
-    return s[:, pos].t().contiguous()
+    return s[:, mx_perm(torch.arange(M, device=s.device))].t().contiguous()
 
 
 def gemm_mxfp8(Aq, sa, Wq, sw, bias, epi, Cb=None, X=None, gate=None):
@@ -369,6 +373,15 @@ def mx_quantize_ref(x):
     e = torch.where(amax > 0, e, torch.full_like(e, -127))
     q = (xb * torch.exp2(-e.float())[..., None]).to(torch.float8_e4m3fn)
     return q.view(M, K), (e + 127).to(torch.uint8)
+
+
+def fp8_rows_quantize_ref(x):
+    """torch restatement of quantize_rows_fp8: per row s = amax * fl32(1/448) (1 for an all-zero row), elements
+    e4m3fn(x * (1 / s))."""
+    xf = x.float()
+    amax = xf.abs().amax(dim=-1)
+    s = torch.where(amax > 0, amax * torch.tensor(1.0 / 448.0, dtype=torch.float32, device=x.device), torch.ones_like(amax))
+    return (xf * (1.0 / s)[:, None]).to(torch.float8_e4m3fn), s
 
 
 def v2_sample_rows(M, device="cuda:0"):

@@ -57,6 +57,12 @@ def test_product_sources_carry_no_wrong_result_switches():
             src = open(os.path.join(csrc, fn)).read()
             for macro in ("MC_V2_EPI_ABL", "MC_V2_DEFER_ABL", "MC_V2_NO_EPI", "MC_V2_RESID_SPLIT", "MC_V2_XAHEAD"):
                 assert macro not in src, (fn, macro)
+    # the shipped 8-wave GEMMs and the header they share: none of the reference kernel's (gemm_bf16_big.hip, test-only)
+    # timing ablations or race-bisect variants
+    for fn in ("gemm_fp8_big.hip", "gemm_mxfp8.hip", "gemm_pipe8.h", "quant.h"):
+        src = open(os.path.join(csrc, fn)).read()
+        for macro in ("MC_ABL", "MC_VAR"):
+            assert macro not in src, (fn, macro)
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import build_gemm_v2_variants as BV
     text = open(os.path.join(csrc, "gemm_bf16_v2.hip")).read()

@@ -438,6 +438,50 @@ def test_ln_modulate_fp8_refusals():
     refused(H.T, "ln_modulate_fp8", *args, H.P(q), 1024, H.P(s), None, 0, 8, 768, None, None, None, H.S())         # D / 256 = 3
 
 
+# ----------------------------------------------------------------------------- quantize_rows_fp8 / quantize_rows_mx
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32], ids=["bf16", "f32"])
+@pytest.mark.parametrize("K", [32, 544])
+@pytest.mark.parametrize("M", [1, 67])
+def test_quantize_rows_equal_their_torch_restatements(M, K, dtype):
+    """The two stand-alone quantisers (csrc/quant.h is their arithmetic) against hip_ops.fp8_rows_quantize_ref /
+    mx_quantize_ref, bytes and scales bit for bit, on bf16 and on fp32 rows.  Special 32-blocks (values within [-1, 1] beside
+    the one that sets amax): an all-zero row, an all-zero block, amax 3.5 = 2^-7 * 448 and amax 3584 = 2^3 * 448 -- both give
+    frexp the mantissa 0.5 exactly, the branch that takes one off the exponent: E8M0 bytes 127 - 7 and 127 + 3.  M = 1 has one
+    row, so there the blocks of that row carry the cases (K = 32: one block, amax 3.5) and the all-zero row is M = 67's."""
+    nb = K // 32
+    x = rnd(M, K, seed=M + K, scale=2.0).view(M, nb, 32)
+    special = {}                                        # (row, block) -> amax
+    if M == 1:
+        special = {(0, 0): 3.5} if nb == 1 else {(0, 0): 0.0, (0, 1): 3.5, (0, nb - 1): 3584.0}
+    else:
+        x[0] = 0.0                                      # the all-zero row
+        special = {(1, 0): 0.0, (2, nb - 1): 3.5, (3, 0): 3584.0, (64, nb // 2): 3.5, (66, nb - 1): 0.0}
+    for (r, b), amax in special.items():
+        x[r, b] = x[r, b].clamp(-1.0, 1.0) if amax else 0.0
+        if amax:
+            x[r, b, 5] = -amax
+    x = x.view(M, K).to(dtype).contiguous()
+    assert pow2_amax_hits_half_branch(3.5) and pow2_amax_hits_half_branch(3584.0)
+
+    q, s = H.quantize_rows_fp8(x)
+    qr, sr = H.fp8_rows_quantize_ref(x)
+    assert torch.equal(bits(s), bits(sr))
+    assert torch.equal(q, qr.view(torch.uint8))
+    if M > 1:
+        assert float(s[0]) == 1.0 and int(q[0].max()) == 0
+
+    q, s = H.quantize_rows_mx(x)
+    qr, sr = H.mx_quantize_ref(x)
+    want = torch.full_like(s, 127)                      # the bytes no row owns keep what they were filled with
+    want[:, H.mx_perm(torch.arange(M, device=DEV))] = sr.t()
+    assert torch.equal(s, want)
+    assert torch.equal(q, qr.view(torch.uint8))
+    for (r, b), amax in special.items():
+        assert int(sr[r, b]) == {0.0: 0, 3.5: 127 - 7, 3584.0: 127 + 3}[amax]
+    if M > 1:
+        assert int(sr[0].max()) == 0 and int(q[0].max()) == 0
+
+
 # ----------------------------------------------------------------------------- EPI_GELU_MXFP8
 @pytest.mark.parametrize("M,N,K", [(256, 256, 512), (1024, 8960 - 8960 % 256, 1536), (32768, 8960 - 8960 % 256, 1536)])
 def test_gemm_mxfp8_gelu_quant_epilogue_equals_quantising_the_gelu_output(M, N, K):

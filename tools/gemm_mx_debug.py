@@ -22,9 +22,7 @@ def perm_scales(s_nat, rows_pad):
     """[M, K/32] natural -> [K/32, rows_pad] kernel order"""
     M = s_nat.shape[0]
     out = torch.full((s_nat.shape[1], rows_pad), 127, dtype=torch.uint8, device=s_nat.device)
-    rows = torch.arange(M, device=s_nat.device)
-    pos = (rows & ~63) | ((rows & 15) << 2) | ((rows >> 4) & 3)
-    out[:, pos] = s_nat.t()
+    out[:, H.mx_perm(torch.arange(M, device=s_nat.device))] = s_nat.t()
     return out
 
 
