@@ -289,6 +289,32 @@ def test_v5_lazy_reference_spike_between_2p120_and_2p128_with_large_values(spike
     assert np.abs(got[5] - want[5]).max() <= 2e-2 * np.abs(want[5]).max()                       # the row with the spike
 
 
+@pytest.mark.parametrize("mfma", [32, 16])
+@pytest.mark.parametrize("spike_row,target", [(390, 119.0), (440, 119.0), (447, 100.0)])
+def test_v5_lazy_reference_spike_in_the_last_tile_with_large_values(spike_row, target, mfma):
+    """The same spike IN the last tile (key steps 0 and 3 of 448 keys), 2^119 above the reference of the first tile and so just
+    below the 2^120 vote threshold, with |V| ~ 1000:
+    every row sum stays finite and under the threshold, so nothing restarts, and P ~ 2^118 times |V| ~ 2^12 does not fit an
+    fp32 accumulator.  The row-sum check has to run for the last tile too, before its P meets V (tests/
+    test_attention_edges_gpu.py::test_spike_in_a_later_shard found the pipelined last tile without one: O = inf)."""
+    pb = Problem(448, 1, 2, 1, 1.0, 7, False)
+    nh, head = pb.n_heads, pb.head
+    q5 = pb.qkv[5, head * 128:(head + 1) * 128]
+    c = 1.4426950408889634 / np.sqrt(128.0)
+    k0 = pb.qkv[:64, nh * 128 + head * 128:nh * 128 + (head + 1) * 128]
+    ref0 = float((k0.astype(np.float64) @ q5.astype(np.float64)).max()) * c                     # the reference the first tile sets
+    gain = (ref0 + target) / (float(q5.astype(np.float64) @ q5.astype(np.float64)) * c)         # P = 2^target relative to it
+    pb.qkv[spike_row, nh * 128 + head * 128:nh * 128 + (head + 1) * 128] = bf16_round(gain * q5)
+    pb.qkv[:, 2 * nh * 128:] = bf16_round(1000.0 * pb.qkv[:, 2 * nh * 128:])
+    pb.qkv_bits = emu.bf16_rne(pb.qkv).astype(np.uint16)
+    out_bits, _, m = launch(pb, dma_late=True, load_late=True, cfg={"mfma": mfma})
+    got = emu.bf16_to_f32(out_bits[:, head * 128:(head + 1) * 128].astype(np.uint32))
+    want, _ = pb.reference([0])
+    assert np.isfinite(got).all()
+    assert np.linalg.norm(got - want) / np.linalg.norm(want) < 8e-3
+    assert np.abs(got[5] - want[5]).max() <= 2e-2 * np.abs(want[5]).max()                       # the row with the spike
+
+
 def test_v5_row_major_epilogue_and_q_images_keep_the_bits():
     # the LDS-transposed epilogue and the LDS-DMA'd Q images change how bytes travel, not one bit of the result
     pb = Problem(200, 1, 2, 1, 1.0, 21, False)

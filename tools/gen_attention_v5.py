@@ -19,7 +19,8 @@ The stream that ships (cfg lazy = 1, pipe = 1, 32x32x16), per 64-key tile t:
    ONE exponential per MFMA gap over the whole iteration, every gap one of the compositions tools/gen_ubench_gap2.py
    measured to be free (exp + 1 VALU + one LDS read / LDS-DMA piece, or exp + 4 VALU); no lane maxima in the loop (LAZY
    reference); a workgroup whose row sums end non-finite or >= 2^120 votes and starts over in the exact loop below before
-   anything is written.  One s_waitcnt vmcnt(0) + s_barrier per TWO tiles; K / V tiles in 4-deep LDS rings, 2 tiles ahead.
+   anything is written.  The last tile, which no boundary follows, gets the same row-sum check between its finish and its
+   P V product.  One s_waitcnt vmcnt(0) + s_barrier per TWO tiles; K / V tiles in 4-deep LDS rings, 2 tiles ahead.
 The exact loop (cfg lazy = 0; also the second pass of an overflowed workgroup, and the only form of the 16x16x32 shape):
    phase 1   S(t+1)^T = K(t+1) Q^T             ||  P(t) = exp2(S(t)) (first part), row sums, pack; LDS-DMA; first V^T fragments
    phase 2   O^T += V(t)^T P(t)^T              ||  rest of P(t), V^T fragments just in time, K(t+2) fragments, lane maxima of
@@ -976,8 +977,11 @@ def emit_pipe_entry(E):
     fin.drain()
 
 
-def emit_last_pipe(E, par):
-    """last tile, pipelined flavour: key steps 0, 1 of P are done, the padding mask (if any) was applied before them"""
+def emit_last_pipe(E, par, ret):
+    """last tile, pipelined flavour: key steps 0, 1 of P are done, the padding mask (if any) was applied before them.
+    Its row sums are checked like every other tile's, after the finish and before P meets V: no loop boundary follows the last
+    tile, and without the check a score in it up to 2^120 above the reference (below the vote threshold: no restart) went
+    into the O accumulators as P ~ 2^119 times V -- inf for |V| ~ 1000 with every row sum finite."""
     M = E.M
     E.comment(f"---- last tile (pipelined finish), S_cur = buffer {par}")
     E.i("s_waitcnt vmcnt(0)")
@@ -987,6 +991,7 @@ def emit_last_pipe(E, par):
         E.i(f"v_add_u32 {v(va + db)}, {s(S_VSLOT)}, {v(M.V_VOFF + db)}")
     fin = Finish(E, par, pipe_groups(M, 1))
     fin.drain()
+    emit_decide(E, par, ret, lazy=True)   # rare: the reference moves, the packed P words of this tile with it
     E.i("s_nop 1")
     nfr = M.NKS * M.NDB
     for f in range(nfr):
@@ -1558,7 +1563,7 @@ def emit_region(E, U, n_ret, exit_label):
     for par in range(2):
         E.label(f"L_last{par}")
         if E.pipe:
-            emit_last_pipe(E, par)
+            emit_last_pipe(E, par, U + 1 + par)
         else:
             emit_last(E, par, U + 1 + par)
         E.i(f"s_branch {exit_label}")
