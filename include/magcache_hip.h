@@ -137,7 +137,7 @@ mc_status mc_create(const mc_config* cfg, mc_engine** out);
  * sizeof(mc_config) of THIS header; a caller compiled against an older header (a shorter struct) must call
  * mc_create_sized(cfg, sizeof(mc_config) as IT knows it, out): the missing tail is taken as zeros.  History: 0.1 ends at
  * vace_in_dim, 0.2 adds fp8_linear, 0.3 no_context_cache and no_token_timesteps, 0.5 sp_phases (0.6 adds calls only: mc_pair_begin / mc_pair_end; 0.7 adds calls only: mc_geometry_bytes / mc_set_geometry,
- * mc_op_rope_axes / mc_op_rope_expand); mc_version() names the library's. */
+ * mc_op_rope_axes / mc_op_rope_expand; 0.7.1 adds calls only: mc_lora_*, mc_op_lora_merge_f32, mc_op_param_delta); mc_version() names the library's. */
 mc_status mc_create_sized(const mc_config* cfg, size_t cfg_bytes, mc_engine** out);
 void mc_destroy(mc_engine* e);
 size_t mc_workspace_bytes(const mc_engine* e);
@@ -179,6 +179,47 @@ mc_status mc_buffer_info(const mc_engine* e, const char* name, size_t* offset, s
 mc_status mc_set_weight(mc_engine* e, const char* name, const void* src_dev, mc_dtype dtype, const int64_t* shape,
                         int ndim, mc_stream stream);
 int mc_weights_missing(const mc_engine* e, char* buf, size_t buflen); /* count; names into buf */
+
+/* ---- LoRA adapters, merged into the weights on the device (0.7.1) -- the contracts of magcache_mmdit.h's mc_mmdit_lora_*, on
+ * the same weight store, plus what Wan adapters need: fp32 targets and additive deltas.
+ *   mc_lora_set        one low-rank pair of `adapter` on `weight_name`, a name of mc_set_weight: down [rank, in_features] and
+ *                      up [rows of that weight, rank], fp32 or bf16, copied; factor = alpha / rank of the target.  Targets: every bf16
+ *                      matrix of a block, of the text / image / VACE embedders, AND the fp32 matrices time_embedding.0/.2,
+ *                      time_projection.1 and head.head.  A bf16 target is rebuilt as bf16(W + sum_j m_j up_j down_j) (one
+ *                      rounding, mc_op_lora_merge); an fp32 target as W + sum_j m_j up_j down_j with the operands rounded to
+ *                      bf16, fp32 accumulation and NO rounding of the sum (mc_op_lora_merge_f32).  patch_embedding.weight and
+ *                      vace_patch_embedding.weight take no adapter.  The same (adapter, weight_name) again replaces the pair; at
+ *                      most MC_LORA_MAX_TERMS adapters per weight; a new adapter starts at scale 1.
+ *   mc_lora_set_delta  an additive delta of `adapter` on an fp32 parameter -- a bias (that of a part of a fused Linear by its
+ *                      own name, "blocks.0.self_attn.q.bias"), a norm weight, "blocks.N.modulation", "head.modulation", an fp32
+ *                      matrix: p = p0 + sum_j scale_j delta_j (mc_op_param_delta; on an fp32 matrix the pairs are merged first
+ *                      and the deltas added to that).  `delta_dev`: `numel` fp32 elements (dtype must be MC_F32), copied.
+ *                      Same replace rule and the same limit per parameter.  A delta on a bf16 matrix is MC_EINVAL: a
+ *                      full-rank delta is a checkpoint, not an adapter.
+ *   mc_lora_scale      the adapter's scale; a term's multiplier is scale * factor (deltas: factor 1), and 0 leaves it out
+ *   mc_lora_remove     the adapter's terms, or with NULL every adapter's
+ *   mc_lora_apply      rebuilds every parameter whose terms, multipliers or base changed since the last apply from its pristine
+ *                      copy (kept while an adapter touches it; mc_set_weight on such a parameter stores into the copy), and
+ *                      requantises exactly the touched rows of an fp8 Linear (fp8_linear 1, 2, 3).  A parameter no adapter
+ *                      touches any more is its pristine value again, bit for bit, and its copy is freed.
+ *   mc_lora_info       adapters known, parameters with a pristine copy, bytes of those copies (any pointer may be NULL)
+ * Between forwards only: MC_ESTATE between mc_pair_begin and mc_pair_end, and between mc_embed and mc_head of a phased
+ * forward.  They may allocate and are not capturable.  While a change waits for its apply, mc_forward, mc_embed,
+ * mc_set_context, mc_set_clip_fea and mc_set_vace_context return MC_ESTATE.  An apply that rebuilt at least one parameter
+ * invalidates everything the engine derived from weights: both text-context slots (the selected slot becomes -1), the CLIP
+ * context, the VACE context and a kept pair front -- set them again before the next forward, which otherwise returns MC_ESTATE
+ * naming what is missing.  The MagCache state (residual caches, calibration statistics) is left alone, and adapters survive
+ * mc_set_geometry.  No pointer moves: a captured forward stays valid -- upload the contexts again outside the graph and replay.
+ * An engine with no adapter runs the launches it always ran on the pointers it always read.  With sequence parallelism every
+ * rank makes the same calls. */
+mc_status mc_lora_set(mc_engine* e, const char* adapter, const char* weight_name, const void* down_dev, const int64_t* down_shape,
+                      const void* up_dev, const int64_t* up_shape, mc_dtype dtype, float factor, mc_stream stream);
+mc_status mc_lora_set_delta(mc_engine* e, const char* adapter, const char* param_name, const void* delta_dev, size_t numel,
+                            mc_dtype dtype, mc_stream stream);
+mc_status mc_lora_scale(mc_engine* e, const char* adapter, float scale);
+mc_status mc_lora_remove(mc_engine* e, const char* adapter);
+mc_status mc_lora_apply(mc_engine* e, mc_stream stream);
+mc_status mc_lora_info(const mc_engine* e, int* adapters, int* params, size_t* base_bytes);
 
 /* ---- one DiT evaluation = the body of magcache_forward (:229-305) ------------------------------
  * latent_dev : fp32 [in_dim, F, H, W]
@@ -558,6 +599,18 @@ typedef struct mc_lora_term {
 size_t mc_op_lora_merge_scratch(int rows, int K, const mc_lora_term* terms, int n_terms);
 mc_status mc_op_lora_merge(const void* base_dev, long ld_base, void* out_dev, long ld_out, int rows, int K,
                            const mc_lora_term* terms, int n_terms, void* scratch_dev, size_t scratch_bytes, mc_stream stream);
+/* The same merge into an fp32 matrix (0.7.1; what mc_lora_apply rebuilds the Wan engine's fp32 matrices with): base / out
+ * fp32, the terms bf16 as above, out = base + delta with the ONE fp32 add last and no rounding step.  K and the pitches are
+ * multiples of 4 here; every other rule and refusal is mc_op_lora_merge's. */
+mc_status mc_op_lora_merge_f32(const float* base_dev, long ld_base, float* out_dev, long ld_out, int rows, int K,
+                               const mc_lora_term* terms, int n_terms, void* scratch_dev, size_t scratch_bytes, mc_stream stream);
+/* The additive rule of a parameter that is no matrix product (0.7.1): out[i] = base[i] + sum_j scales[j] * deltas[j][i], all
+ * fp32, i < n, any n > 0, 1 to MC_LORA_MAX_TERMS terms (`deltas`: a HOST array of device pointers, `scales`: a host array).
+ * The sum is formed from zero in term order, a multiply and an add per term, never contracted; the base element is added last.
+ * A term with scale 0 is left out, and with no live term out is a copy of base.  out may alias base.  MC_EINVAL, and nothing
+ * launched, for n == 0, a term count out of range, a null pointer or one that is not 4-byte aligned. */
+mc_status mc_op_param_delta(const float* base_dev, float* out_dev, size_t n, const float* const* deltas, const float* scales,
+                            int n_terms, mc_stream stream);
 
 #ifdef __cplusplus
 }

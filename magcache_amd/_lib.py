@@ -132,6 +132,14 @@ SIGNATURES = {
     "mc_op_rope_expand": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "mc_op_lora_merge_scratch": (_sz, [_i, _i, _vp, _i]),
     "mc_op_lora_merge": (_i, [_vp, _l, _vp, _l, _i, _i, _vp, _i, _vp, _sz, _vp]),
+    "mc_op_lora_merge_f32": (_i, [_vp, _l, _vp, _l, _i, _i, _vp, _i, _vp, _sz, _vp]),
+    "mc_op_param_delta": (_i, [_vp, _vp, _sz, C.POINTER(_vp), C.POINTER(_f), _i, _vp]),
+    "mc_lora_set": (_i, [_vp, C.c_char_p, C.c_char_p, _vp, C.POINTER(C.c_int64), _vp, C.POINTER(C.c_int64), _i, _f, _vp]),
+    "mc_lora_set_delta": (_i, [_vp, C.c_char_p, C.c_char_p, _vp, _sz, _i, _vp]),
+    "mc_lora_scale": (_i, [_vp, C.c_char_p, _f]),
+    "mc_lora_remove": (_i, [_vp, C.c_char_p]),
+    "mc_lora_apply": (_i, [_vp, _vp]),
+    "mc_lora_info": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_sz)]),
     # include/magcache_mmdit.h
     "mc_mmdit_create": (_i, [_vp, C.POINTER(_vp)]),
     "mc_mmdit_create_sized": (_i, [_vp, _sz, C.POINTER(_vp)]),

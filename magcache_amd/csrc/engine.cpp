@@ -338,6 +338,7 @@ mc_status forget_workspace_state(mc_engine* e) {
 
 mc_status check_ready(const mc_engine* e) {
   if (!e) return fail(MC_EINVAL, "null engine");
+  if (e->weights.dirty()) return fail(MC_ESTATE, "LoRA adapters, scales or a touched weight changed: call mc_lora_apply first");
   return mc::check_ready(e->work, e->weights, "mc_set_workspace");
 }
 
@@ -494,6 +495,7 @@ mc_status mc_create(const mc_config* cfg, mc_engine** out) {
   e->ctx_rows = (int)align_up(c.text_len, 64);
   const size_t d = e->d, ffn = e->ffn;
   mc::WeightStore& W = e->weights;
+  W.allow_f32_targets = true;   // adapters on the fp32 matrices below and deltas on the fp32 parameters (mc_lora_set / _set_delta)
 
   // fp8_linear only decides which Linears keep an e4m3 copy and of which kind: 1 = QKV, FFN-1, FFN-2 with per-row scales,
   // 2 = the same three with MX block scales, 3 = MX, the d x d Linears (self-attention O, cross-attention Q and O) too
@@ -531,6 +533,7 @@ mc_status mc_create(const mc_config* cfg, mc_engine** out) {
     const size_t kv = (size_t)c.vace_in_dim * 4;
     if (kv != (size_t)e->Kvp) { return fail(MC_EINVAL, "vace_in_dim*4 must be a multiple of 64"); }
     MC_TRY(W.add_linear(e->vpatch, "", {{"vace_patch_embedding", d}}, kv));
+    W.slots.at("vace_patch_embedding.weight").fixed = true;
     MC_TRY(W.add_linear(e->before, "vace_blocks.0.", {{"before_proj", d}}, d));
     MC_TRY(W.alloc(&e->vscale, d));
     e->after.resize(e->NV);
@@ -552,19 +555,20 @@ mc_status mc_create(const mc_config* cfg, mc_engine** out) {
   MC_TRY(W.alloc_linear(e->patch, d, e->Kp));
   HIP_TRY(hipMemset(e->patch.w, 0, d * e->Kp * sizeof(bf16_t)));
   mc::Slot& w_patch = W.add_parts(e->patch, "", {{"patch_embedding", d}});
+  w_patch.fixed = true;   // the patch embedders take no adapter, padded or not
   if (kin != (size_t)e->Kp) {
     w_patch.numel = d * kin;
     w_patch.pad = {d, kin, (size_t)e->Kp};
   }
   MC_TRY(W.add_linear(e->text0, "text_embedding.", {{"0", d}}, c.text_dim));
   MC_TRY(W.add_linear(e->text1, "text_embedding.", {{"2", d}}, d));
-  MC_TRY(W.add_f32(e->w_time0, "time_embedding.0.weight", d * c.freq_dim));
+  MC_TRY(W.add_f32(e->w_time0, "time_embedding.0.weight", d * c.freq_dim, c.freq_dim));
   MC_TRY(W.add_f32(e->b_time0, "time_embedding.0.bias", d));
-  MC_TRY(W.add_f32(e->w_time1, "time_embedding.2.weight", d * d));
+  MC_TRY(W.add_f32(e->w_time1, "time_embedding.2.weight", d * d, d));
   MC_TRY(W.add_f32(e->b_time1, "time_embedding.2.bias", d));
-  MC_TRY(W.add_f32(e->w_tproj, "time_projection.1.weight", 6 * d * d));
+  MC_TRY(W.add_f32(e->w_tproj, "time_projection.1.weight", 6 * d * d, d));
   MC_TRY(W.add_f32(e->b_tproj, "time_projection.1.bias", 6 * d));
-  MC_TRY(W.add_f32(e->w_head, "head.head.weight", (size_t)c.out_dim * 4 * d));
+  MC_TRY(W.add_f32(e->w_head, "head.head.weight", (size_t)c.out_dim * 4 * d, d));
   MC_TRY(W.add_f32(e->b_head, "head.head.bias", (size_t)c.out_dim * 4));
   MC_TRY(W.add_f32(e->head_mod, "head.modulation", 2 * d));
 
@@ -652,6 +656,64 @@ mc_status mc_set_weight(mc_engine* e, const char* name, const void* src_dev, mc_
 }
 
 int mc_weights_missing(const mc_engine* e, char* buf, size_t buflen) { return e ? e->weights.missing(buf, buflen) : -1; }
+
+// ---- LoRA adapters: the store does the work (host.h), between forwards only
+static mc_status lora_entry(const mc_engine* e, const char* what) {
+  if (!e) return fail(MC_EINVAL, "null engine");
+  if (e->pair != mc_engine::PAIR_NONE) return fail(MC_ESTATE, "%s between mc_pair_begin and mc_pair_end", what);
+  if (e->phase_open) return fail(MC_ESTATE, "%s between mc_embed and mc_head", what);
+  return MC_OK;
+}
+
+mc_status mc_lora_set(mc_engine* e, const char* adapter, const char* weight_name, const void* down_dev, const int64_t* down_shape,
+                      const void* up_dev, const int64_t* up_shape, mc_dtype dtype, float factor, mc_stream stream) {
+  MC_TRY(lora_entry(e, "mc_lora_set"));
+  if (!adapter || !weight_name || !down_dev || !down_shape || !up_dev || !up_shape) return fail(MC_EINVAL, "null argument");
+  if (down_shape[0] <= 0 || down_shape[0] > (1 << 20) || down_shape[1] <= 0 || up_shape[0] <= 0 || up_shape[1] != down_shape[0])
+    return fail(MC_EINVAL, "LoRA '%s': down [%lld, %lld] and up [%lld, %lld] share no rank", weight_name, (long long)down_shape[0],
+                (long long)down_shape[1], (long long)up_shape[0], (long long)up_shape[1]);
+  return e->weights.lora_set(adapter, weight_name, down_dev, (size_t)down_shape[0] * down_shape[1], up_dev,
+                             (size_t)up_shape[0] * up_shape[1], dtype, (int)down_shape[0], factor, (hipStream_t)stream);
+}
+
+mc_status mc_lora_set_delta(mc_engine* e, const char* adapter, const char* param_name, const void* delta_dev, size_t numel,
+                            mc_dtype dtype, mc_stream stream) {
+  MC_TRY(lora_entry(e, "mc_lora_set_delta"));
+  if (!adapter || !param_name || !delta_dev) return fail(MC_EINVAL, "null argument");
+  return e->weights.lora_set_delta(adapter, param_name, delta_dev, numel, dtype, (hipStream_t)stream);
+}
+
+mc_status mc_lora_scale(mc_engine* e, const char* adapter, float scale) {
+  MC_TRY(lora_entry(e, "mc_lora_scale"));
+  if (!adapter) return fail(MC_EINVAL, "null argument");
+  return e->weights.lora_scale(adapter, scale);
+}
+
+mc_status mc_lora_remove(mc_engine* e, const char* adapter) {
+  MC_TRY(lora_entry(e, "mc_lora_remove"));
+  return e->weights.lora_remove(adapter);
+}
+
+// Everything the engine derived from weights goes with a merge, as with mc_set_weight, and the two contexts that call keeps
+// as well: the cached text contexts, the CLIP context, the VACE c0 and a kept pair front.  The MagCache state stays.
+mc_status mc_lora_apply(mc_engine* e, mc_stream stream) {
+  MC_TRY(lora_entry(e, "mc_lora_apply"));
+  int merged = 0;
+  const mc_status st = e->weights.lora_apply((hipStream_t)stream, &merged);
+  if (merged > 0) {
+    e->ctx_valid[0] = e->ctx_valid[1] = false;
+    e->ctx_active = -1;
+    e->have_clip = e->have_vace = false;
+    e->pair_drop();
+  }
+  return st;
+}
+
+mc_status mc_lora_info(const mc_engine* e, int* adapters, int* params, size_t* base_bytes) {
+  if (!e) return fail(MC_EINVAL, "null engine");
+  e->weights.lora_info(adapters, params, base_bytes);
+  return MC_OK;
+}
 
 // I2V: context_clip = img_emb(clip_fea)   (reference :264-266; upstream MLPProj: LayerNorm, Linear, GELU(erf),
 // Linear, LayerNorm).  257 tokens; rows up to img_rows are padding (finite, masked in the attention).

@@ -36,9 +36,9 @@ Slot& WeightStore::add(const std::string& name, void* dst, mc_dtype dt, size_t n
   return slots[name] = s;
 }
 
-mc_status WeightStore::add_f32(float*& p, const std::string& name, size_t numel) {
+mc_status WeightStore::add_f32(float*& p, const std::string& name, size_t numel, size_t k_in) {
   MC_TRY(alloc(&p, numel));
-  add(name, p, MC_F32, numel);
+  add(name, p, MC_F32, numel).f32_k = k_in;
   return MC_OK;
 }
 
@@ -83,7 +83,9 @@ mc_status WeightStore::set(const char* name, const void* src_dev, mc_dtype dtype
   if (numel != s.numel) return fail(MC_EINVAL, "weight '%s': %zu elements given, %zu expected", name, numel, s.numel);
   if (s.dst_dtype == MC_F32) {
     if (dtype != MC_F32) return fail(MC_EINVAL, "weight '%s' must be given as fp32", name);
-    float* dst = (float*)s.dst + s.off;
+    // a parameter with a base copy keeps the given values there; the live ones follow with the next lora_apply
+    float* dst = s.f32_base ? s.f32_base : (float*)s.dst + s.off;
+    if (s.f32_base) lora_dirty.insert(name);
     if (s.perm_c > 0) {  // rows (c, pq) -> (pq, c)
       const size_t C = s.perm_c, row = numel / (4 * C);
       for (size_t c = 0; c < C; ++c)
@@ -136,17 +138,18 @@ mc_status WeightStore::lora_set(const char* adapter, const char* weight_name, co
   auto it = slots.find(weight_name);
   if (it == slots.end()) return fail(MC_EINVAL, "LoRA: unknown weight '%s'", weight_name);
   Slot& s = it->second;
-  if (!s.lin || s.dst_dtype != MC_BF16 || s.pad.rows || s.perm_c)
+  const bool f32_matrix = allow_f32_targets && s.dst_dtype == MC_F32 && s.f32_k > 0 && !s.perm_c && !s.fixed;
+  if (!f32_matrix && (!s.lin || s.dst_dtype != MC_BF16 || s.pad.rows || s.perm_c || s.fixed))
     return fail(MC_EINVAL, "LoRA: '%s' is no plain bf16 part of a Linear (an fp32, padded or permuted weight takes no adapter)",
                 weight_name);
   if (dtype != MC_F32 && dtype != MC_BF16) return fail(MC_EINVAL, "LoRA '%s': down / up are fp32 or bf16", weight_name);
-  Linear& l = *s.lin;
-  const size_t k = l.k_in, rows = s.numel / k;
+  const size_t k = f32_matrix ? s.f32_k : (size_t)s.lin->k_in, rows = s.numel / k;
   if (rank <= 0) return fail(MC_EINVAL, "LoRA '%s': rank %d", weight_name, rank);
   if (down_numel != (size_t)rank * k || up_numel != rows * (size_t)rank)
     return fail(MC_EINVAL, "LoRA '%s': down has %zu elements, up %zu; rank %d wants [%d, %zu] = %zu and [%zu, %d] = %zu", weight_name,
                 down_numel, up_numel, rank, rank, k, (size_t)rank * k, rows, rank, rows * (size_t)rank);
-  if ((k % 8) != 0) return fail(MC_EINVAL, "LoRA '%s': in_features %zu is no multiple of 8", weight_name, k);
+  if ((k % (f32_matrix ? 4 : 8)) != 0)
+    return fail(MC_EINVAL, "LoRA '%s': in_features %zu is no multiple of %d", weight_name, k, f32_matrix ? 4 : 8);
   size_t at = lora.size(), on_target = 0;
   for (size_t i = 0; i < lora.size(); ++i) {
     if (lora[i].target != weight_name) continue;
@@ -160,18 +163,13 @@ mc_status WeightStore::lora_set(const char* adapter, const char* weight_name, co
   p.adapter = adapter; p.target = weight_name; p.rank_pad = rank_pad; p.factor = factor;
   MC_TRY(alloc(&p.up, lora_packed_elems(rows, rank_pad)));
   if (mc_status st = alloc(&p.down_t, lora_packed_elems(k, rank_pad))) { release(p.up); return st; }
-  bool new_base = false;
-  if (!l.w_base) {  // the first adapter on this Linear: its pristine copy
-    if (mc_status st = alloc(&l.w_base, (size_t)l.n_out * k)) { release(p.up); release(p.down_t); return st; }
-    new_base = true;
-  }
-  hipError_t err = hipSuccess;
-  if (new_base) err = hipMemcpyAsync(l.w_base, l.w, (size_t)l.n_out * k * 2, hipMemcpyDeviceToDevice, stream);
-  if (err == hipSuccess) err = launch_lora_pack(up_dev, dtype == MC_F32, rank, 1, (int)rows, rank, rank_pad, p.up, stream);
+  bool new_base = false;   // the first adapter on this Linear (this fp32 matrix): its pristine copy
+  if (mc_status st = make_base(s, stream, &new_base)) { release(p.up); release(p.down_t); return st; }
+  hipError_t err = launch_lora_pack(up_dev, dtype == MC_F32, rank, 1, (int)rows, rank, rank_pad, p.up, stream);
   if (err == hipSuccess) err = launch_lora_pack(down_dev, dtype == MC_F32, 1, (long)k, (int)k, rank, rank_pad, p.down_t, stream);
   if (err != hipSuccess) {
     release(p.up); release(p.down_t);
-    if (new_base) { release(l.w_base); l.w_base = nullptr; }
+    if (new_base) drop_base(s);
     return fail(MC_EHIP, "LoRA '%s': %s", weight_name, hipGetErrorString(err));
   }
   if (at < lora.size()) {  // replaced: the old pair's copies go (hipFree waits for a merge that may still read them)
@@ -185,6 +183,73 @@ mc_status WeightStore::lora_set(const char* adapter, const char* weight_name, co
   return MC_OK;
 }
 
+mc_status WeightStore::make_base(Slot& s, hipStream_t stream, bool* made) {
+  *made = false;
+  if (s.lin ? s.lin->w_base != nullptr : s.f32_base != nullptr) return MC_OK;
+  hipError_t err;
+  if (s.lin) {
+    Linear& l = *s.lin;
+    const size_t n = (size_t)l.n_out * l.k_in;
+    MC_TRY(alloc(&l.w_base, n));
+    err = hipMemcpyAsync(l.w_base, l.w, n * 2, hipMemcpyDeviceToDevice, stream);
+  } else {
+    MC_TRY(alloc(&s.f32_base, s.numel));
+    err = hipMemcpyAsync(s.f32_base, (const float*)s.dst + s.off, s.numel * 4, hipMemcpyDeviceToDevice, stream);
+  }
+  if (err != hipSuccess) {
+    drop_base(s);
+    return fail(MC_EHIP, "LoRA: the base copy failed: %s", hipGetErrorString(err));
+  }
+  *made = true;
+  return MC_OK;
+}
+
+void WeightStore::drop_base(Slot& s) {   // hipFree waits for the launches that may still read the copy
+  if (s.lin) { release(s.lin->w_base); s.lin->w_base = nullptr; }
+  else { release(s.f32_base); s.f32_base = nullptr; }
+}
+
+mc_status WeightStore::lora_set_delta(const char* adapter, const char* param_name, const void* delta_dev, size_t numel, mc_dtype dtype,
+                                      hipStream_t stream) {
+  auto it = slots.find(param_name);
+  if (it == slots.end()) return fail(MC_EINVAL, "LoRA: unknown weight '%s'", param_name);
+  Slot& s = it->second;
+  if (s.dst_dtype != MC_F32)
+    return fail(MC_EINVAL, "LoRA: '%s' is a bf16 matrix and takes low-rank pairs only (a full-rank delta is a checkpoint, not an adapter)",
+                param_name);
+  if (!allow_f32_targets || s.perm_c || s.fixed) return fail(MC_EINVAL, "LoRA: '%s' takes no delta in this engine", param_name);
+  if (dtype != MC_F32) return fail(MC_EINVAL, "LoRA '%s': a delta must be given as fp32", param_name);
+  if (numel != s.numel) return fail(MC_EINVAL, "LoRA '%s': a delta of %zu elements, %zu expected", param_name, numel, s.numel);
+  size_t at = deltas.size(), on_target = 0;
+  for (size_t i = 0; i < deltas.size(); ++i) {
+    if (deltas[i].target != param_name) continue;
+    if (deltas[i].adapter == adapter) at = i;
+    else ++on_target;
+  }
+  if (on_target + 1 > (size_t)kLoraMaxTerms)
+    return fail(MC_EINVAL, "LoRA '%s': more than %d adapters on one weight", param_name, kLoraMaxTerms);
+  LoraDelta d;
+  d.adapter = adapter; d.target = param_name;
+  MC_TRY(alloc(&d.delta, numel));
+  bool new_base = false;
+  if (mc_status st = make_base(s, stream, &new_base)) { release(d.delta); return st; }
+  hipError_t err = hipMemcpyAsync(d.delta, delta_dev, numel * 4, hipMemcpyDeviceToDevice, stream);
+  if (err != hipSuccess) {
+    release(d.delta);
+    if (new_base) drop_base(s);
+    return fail(MC_EHIP, "LoRA '%s': %s", param_name, hipGetErrorString(err));
+  }
+  if (at < deltas.size()) {
+    release(deltas[at].delta);
+    deltas[at] = d;
+  } else {
+    deltas.push_back(d);
+  }
+  lora_scales.emplace(adapter, 1.f);
+  lora_dirty.insert(param_name);
+  return MC_OK;
+}
+
 mc_status WeightStore::lora_scale(const char* adapter, float scale) {
   auto it = lora_scales.find(adapter);
   if (it == lora_scales.end()) return fail(MC_EINVAL, "LoRA: unknown adapter '%s'", adapter);
@@ -192,6 +257,8 @@ mc_status WeightStore::lora_scale(const char* adapter, float scale) {
   it->second = scale;
   for (const LoraPair& p : lora)
     if (p.adapter == adapter) lora_dirty.insert(p.target);
+  for (const LoraDelta& d : deltas)
+    if (d.adapter == adapter) lora_dirty.insert(d.target);
   return MC_OK;
 }
 
@@ -204,16 +271,66 @@ mc_status WeightStore::lora_remove(const char* adapter) {
     release(p.up); release(p.down_t);
   }
   lora.swap(kept);
+  std::vector<LoraDelta> kept_d;
+  for (const LoraDelta& d : deltas) {
+    if (adapter && d.adapter != adapter) { kept_d.push_back(d); continue; }
+    lora_dirty.insert(d.target);
+    release(d.delta);
+  }
+  deltas.swap(kept_d);
   if (adapter) lora_scales.erase(adapter);
   else lora_scales.clear();
   return MC_OK;
 }
 
-mc_status WeightStore::lora_apply(hipStream_t stream) {
+// an fp32 parameter: the pairs of a matrix first (base -> live), then the deltas (base, or that result, -> live)
+mc_status WeightStore::apply_f32(const std::string& name, Slot& s, hipStream_t stream) {
+  float* live = (float*)s.dst + s.off;
+  if (!s.f32_base) return MC_OK;   // set before its first term and never touched: live is the value
+  LoraTerm terms[kLoraMaxTerms];
+  const float* dl[kLoraMaxTerms];
+  float ds[kLoraMaxTerms];
+  int n = 0, m = 0;
+  bool any = false;
+  for (const LoraPair& p : lora) {
+    if (p.target != name) continue;
+    any = true;
+    const float mult = lora_scales.at(p.adapter) * p.factor;
+    if (mult != 0.f) terms[n++] = LoraTerm{p.up, p.down_t, p.rank_pad, mult};
+  }
+  for (const LoraDelta& d : deltas) {
+    if (d.target != name) continue;
+    any = true;
+    const float mult = lora_scales.at(d.adapter);
+    if (mult != 0.f) { dl[m] = d.delta; ds[m] = mult; ++m; }
+  }
+  hipError_t err = hipSuccess;
+  if (n > 0) {
+    const size_t k = s.f32_k;
+    err = launch_lora_merge_f32(s.f32_base, (long)k, live, (long)k, (int)(s.numel / k), (int)k, terms, n, stream);
+    if (err == hipSuccess && m > 0) err = launch_param_delta(live, live, s.numel, dl, ds, m, stream);
+  } else if (m > 0) {
+    err = launch_param_delta(s.f32_base, live, s.numel, dl, ds, m, stream);
+  } else {
+    err = hipMemcpyAsync(live, s.f32_base, s.numel * 4, hipMemcpyDeviceToDevice, stream);
+  }
+  if (err != hipSuccess) return fail(MC_EHIP, "LoRA merge of '%s': %s", name.c_str(), hipGetErrorString(err));
+  if (!any) drop_base(s);   // no adapter left: live is the base again, bit for bit
+  return MC_OK;
+}
+
+mc_status WeightStore::lora_apply(hipStream_t stream, int* merged) {
   std::set<Linear*> touched;
+  if (merged) *merged = 0;
   while (!lora_dirty.empty()) {
     const std::string name = *lora_dirty.begin();
     Slot& s = slots.at(name);
+    if (merged) ++*merged;
+    if (!s.lin) {
+      MC_TRY(apply_f32(name, s, stream));
+      lora_dirty.erase(name);
+      continue;
+    }
     Linear& l = *s.lin;
     const size_t k = l.k_in, rows = s.numel / k;
     LoraTerm terms[kLoraMaxTerms];
@@ -247,12 +364,14 @@ mc_status WeightStore::lora_apply(hipStream_t stream) {
 void WeightStore::lora_info(int* adapters, int* linears, size_t* base_bytes) const {
   std::set<const Linear*> seen;
   size_t bytes = 0;
+  int n_f32 = 0;
   for (auto& kv : slots) {
     const Linear* l = kv.second.lin;
     if (l && l->w_base && seen.insert(l).second) bytes += (size_t)l->n_out * l->k_in * 2;
+    if (kv.second.f32_base) { ++n_f32; bytes += kv.second.numel * 4; }
   }
   if (adapters) *adapters = (int)lora_scales.size();
-  if (linears) *linears = (int)seen.size();
+  if (linears) *linears = (int)seen.size() + n_f32;
   if (base_bytes) *base_bytes = bytes;
 }
 

@@ -71,6 +71,10 @@ struct Slot {  // one named parameter
   uint8_t* mx = nullptr;
   size_t mx_rows = 0;
   Linear* lin = nullptr;  // the Linear whose rows this weight is (add_parts); null for every other parameter
+  // adapters on an fp32 parameter (WeightStore::allow_f32_targets)
+  size_t f32_k = 0;           // > 0: an fp32 matrix [numel / f32_k, f32_k], which takes low-rank pairs; 0: deltas only
+  float* f32_base = nullptr;  // its numel pristine elements while an adapter touches it (dst + off is then the merged value)
+  bool fixed = false;         // takes no adapter whatever its layout (the Wan patch embedders)
 };
 
 // One adapter's low-rank pair on one weight slot, as the merge kernel reads it: bf16 copies owned by the store in the
@@ -82,16 +86,25 @@ struct LoraPair {
   int rank_pad = 0;
   float factor = 1.f;        // alpha / rank of the target
 };
+// One adapter's additive delta on one fp32 parameter: an fp32 copy owned by the store
+struct LoraDelta {
+  std::string adapter, target;
+  float* delta = nullptr;
+};
 
 struct WeightStore {
   std::map<std::string, Slot> slots;
   std::vector<void*> owned;
+  // the owning engine's opt-in (the Wan engine sets it at mc_create): fp32 matrices take pairs, fp32 parameters take deltas.
+  // false: lora_set refuses every fp32 weight and lora_set_delta everything
+  bool allow_f32_targets = false;
 
   template <class T>
   mc_status alloc(T** p, size_t n) { return alloc_bytes(reinterpret_cast<void**>(p), n * sizeof(T)); }
   Slot& add(const std::string& name, void* dst, mc_dtype dt, size_t numel, size_t off = 0);
   // an fp32 parameter that is no Linear's (norm weights, modulation, the fp32 matrices of a GEMV): allocates and registers it
-  mc_status add_f32(float*& p, const std::string& name, size_t numel);
+  // (k_in > 0: a matrix [numel / k_in, k_in], Slot::f32_k)
+  mc_status add_f32(float*& p, const std::string& name, size_t numel, size_t k_in = 0);
   // One Linear [sum of the parts' rows, k_in]: allocates the bf16 weight + fp32 bias (and, quant != QUANT_NONE, the e4m3 copy
   // with its scales) and registers the parts.  alloc_linear / add_parts are its two halves, for a Linear whose parts are
   // added one by one (the fused modulation matrix) or whose slot the caller adjusts (Slot::pad, Slot::perm_c).
@@ -110,13 +123,24 @@ struct WeightStore {
   // starts at scale 1.
   mc_status lora_set(const char* adapter, const char* weight_name, const void* down_dev, size_t down_numel, const void* up_dev,
                      size_t up_numel, mc_dtype dtype, int rank, float factor, hipStream_t stream);
+  // With allow_f32_targets `weight_name` may also be an fp32 matrix (Slot::f32_k): it keeps its own pristine fp32 copy and is
+  // rebuilt as base + sum_j ... by launch_lora_merge_f32, with no rounding step.
+  // lora_set_delta (allow_f32_targets only): p = base + sum_j scale_j delta_j on an fp32 parameter -- a bias (that of a part of
+  // a fused Linear through the slot's offset), a norm weight, a modulation table, an fp32 matrix (there the pairs are merged
+  // first and the deltas added to the result) -- by launch_param_delta.  delta_dev: numel fp32 elements, copied.  The rules of
+  // a pair: the same (adapter, name) replaces, at most kLoraMaxTerms per parameter, a pristine copy while touched.  A bf16
+  // matrix is refused: a full-rank delta is a checkpoint, not an adapter.
+  mc_status lora_set_delta(const char* adapter, const char* param_name, const void* delta_dev, size_t numel, mc_dtype dtype,
+                           hipStream_t stream);
   mc_status lora_scale(const char* adapter, float scale);   // a term's multiplier is scale * factor
   mc_status lora_remove(const char* adapter);               // null: every adapter
   // every part whose terms, multipliers or base changed since the last apply: one merge over its rows (a term with multiplier 0
   // is skipped; no live term: the base rows are copied back), then the quantised copy of exactly those rows.  A Linear that no
   // adapter touches any more gives its base copy back.
-  mc_status lora_apply(hipStream_t stream);
+  // An fp32 parameter that no adapter touches any more gives its copy back likewise.  merged: parameters rebuilt by this call.
+  mc_status lora_apply(hipStream_t stream, int* merged = nullptr);
   bool dirty() const { return !lora_dirty.empty(); }
+  // adapters known; Linears and fp32 parameters with a pristine copy; bytes of those copies
   void lora_info(int* adapters, int* linears, size_t* base_bytes) const;
 
   int missing(char* buf, size_t buflen) const;  // count; names, one per line, as far as buf holds them
@@ -128,7 +152,12 @@ struct WeightStore {
   mc_status alloc_bytes(void** p, size_t bytes);
   // the quantised copy (q8 / mx) of the rows of `s`, from the bf16 rows just stored in the live weight
   mc_status requantise(const Slot& s, hipStream_t stream);
+  // the pristine copy the first term on `s` makes (a Linear's whole bf16 weight | the fp32 parameter's own elements)
+  mc_status make_base(Slot& s, hipStream_t stream, bool* made);
+  void drop_base(Slot& s);
+  mc_status apply_f32(const std::string& name, Slot& s, hipStream_t stream);
   std::vector<LoraPair> lora;                 // in the order they were set: the term order of a merge
+  std::vector<LoraDelta> deltas;              // likewise
   std::map<std::string, float> lora_scales;   // adapter -> scale
   std::set<std::string> lora_dirty;           // weight slots to merge again
 };

@@ -1,5 +1,8 @@
 // LoRA merge: out[rows, K] = bf16( base + sum_j scale_j * (up_j down_j) ), the live weight of a Linear rebuilt from its pristine
 // copy whenever adapters or scales change (host.cpp: WeightStore::lora_apply).  Not a forward-path kernel.
+// The same kernel with fp32 base and out (launch_lora_merge_f32: the Wan engine's fp32 matrices) ends in the fp32 add, with no
+// rounding step; a chunk of 8 columns is then two 16-byte vectors, each inside or outside the matrix as a whole (K % 4 == 0).
+// launch_param_delta, at the end of the file, is the additive rule of the parameters that are no matrices.
 //
 // Arithmetic (tests/test_lora_merge_gpu.py depends on it): per term an fp32 accumulator from zero on bf16 MFMAs over the
 // rank, zero-padded to kLoraRankStep; the fp32 delta = sum_j scale_j * acc_j in term order (a multiply and an add, never contracted); ONE fp32
@@ -25,9 +28,10 @@ constexpr int kTile = 128;       // rows and columns of a workgroup's tile
 constexpr int kHalf = 64;        // columns that pass through LDS at a time
 constexpr int kPitch = kHalf + 4;
 
+template <class T>   // bf16_t | float: the element of base and out
 struct MergeArgs {
-  const bf16_t* base; long ld_base;
-  bf16_t* out; long ld_out;
+  const T* base; long ld_base;
+  T* out; long ld_out;
   int rows, K, n_terms, tiles_n;
   LoraTerm t[kLoraMaxTerms];
 };
@@ -57,8 +61,10 @@ __device__ __forceinline__ void load_frags(Frags& f, const LoraTerm& t, int rb, 
 }
 
 // kMulti = false: exactly one term, whose accumulators become the delta in place (64 registers fewer, more waves in flight)
-template <bool kMulti>
-__global__ __launch_bounds__(256) void lora_merge_kernel(MergeArgs a) {
+template <bool kMulti, class T>
+__global__ __launch_bounds__(256) void lora_merge_kernel(MergeArgs<T> a) {
+  constexpr int kVecs = sizeof(T) / 2;      // 16-byte vectors of an 8-column chunk: 1 (bf16) | 2 (fp32)
+  constexpr int kVecCols = 8 / kVecs;
   __shared__ float lds[4][32][kPitch];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -70,15 +76,17 @@ __global__ __launch_bounds__(256) void lora_merge_kernel(MergeArgs a) {
 
   // the base tile first: its 8 x 16 bytes per lane are in flight while the operands are fetched and multiplied.  Chunk
   // (hf, it) = 8 columns from 64 hf + 8 (lane & 7) of row 8 it + (lane >> 3), the order the epilogue stores in
-  u32x4 w[2][4];
+  u32x4 w[2][4][kVecs];
 #pragma unroll
   for (int hf = 0; hf < 2; ++hf)
 #pragma unroll
-    for (int it = 0; it < 4; ++it) {
-      const int row = row0 + it * 8 + (lane >> 3), col = col0 + kHalf * hf + (lane & 7) * 8;
-      w[hf][it] = u32x4{0u, 0u, 0u, 0u};
-      if (row < a.rows && col < a.K) w[hf][it] = *reinterpret_cast<const u32x4*>(a.base + (size_t)row * a.ld_base + col);
-    }
+    for (int it = 0; it < 4; ++it)
+#pragma unroll
+      for (int v = 0; v < kVecs; ++v) {
+        const int row = row0 + it * 8 + (lane >> 3), col = col0 + kHalf * hf + (lane & 7) * 8 + v * kVecCols;
+        w[hf][it][v] = u32x4{0u, 0u, 0u, 0u};
+        if (row < a.rows && col < a.K) w[hf][it][v] = *reinterpret_cast<const u32x4*>(a.base + (size_t)row * a.ld_base + col);
+      }
 
   f32x16 delta[4];
   const int n_terms = kMulti ? a.n_terms : 1;
@@ -128,18 +136,29 @@ __global__ __launch_bounds__(256) void lora_merge_kernel(MergeArgs a) {
     for (int it = 0; it < 4; ++it) {
       const int r = it * 8 + (lane >> 3), c = (lane & 7) * 8;
       const int row = row0 + r, col = col0 + kHalf * hf + c;
-      if (row < a.rows && col < a.K) {   // K is a multiple of 8: a chunk is inside or outside as a whole
+      if (row < a.rows && col < a.K) {   // bf16: K is a multiple of 8, a chunk is inside or outside as a whole
         const f32x4 d0 = *reinterpret_cast<const f32x4*>(&lds[wv][r][c]);
         const f32x4 d1 = *reinterpret_cast<const f32x4*>(&lds[wv][r][c + 4]);
-        u32x4 o;
+        if constexpr (kVecs == 1) {
+          u32x4 o;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const float dl = q < 2 ? d0[2 * q] : d1[2 * q - 4], dh = q < 2 ? d0[2 * q + 1] : d1[2 * q - 3];
-          const float lo = __fadd_rn(__uint_as_float(w[hf][it][q] << 16), dl);
-          const float hi = __fadd_rn(__uint_as_float(w[hf][it][q] & 0xffff0000u), dh);
-          o[q] = pack_bf16x2(lo, hi);
+          for (int q = 0; q < 4; ++q) {
+            const float dl = q < 2 ? d0[2 * q] : d1[2 * q - 4], dh = q < 2 ? d0[2 * q + 1] : d1[2 * q - 3];
+            const float lo = __fadd_rn(__uint_as_float(w[hf][it][0][q] << 16), dl);
+            const float hi = __fadd_rn(__uint_as_float(w[hf][it][0][q] & 0xffff0000u), dh);
+            o[q] = pack_bf16x2(lo, hi);
+          }
+          *reinterpret_cast<u32x4*>(a.out + (size_t)row * a.ld_out + col) = o;
+        } else {   // fp32: K is a multiple of 4, the chunk's second vector may lie outside
+#pragma unroll
+          for (int v = 0; v < kVecs; ++v) {
+            const f32x4 dv = v == 0 ? d0 : d1;
+            u32x4 o;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) o[q] = __float_as_uint(__fadd_rn(__uint_as_float(w[hf][it][v][q]), dv[q]));
+            if (col + v * kVecCols < a.K) *reinterpret_cast<u32x4*>(a.out + (size_t)row * a.ld_out + col + v * kVecCols) = o;
+          }
         }
-        *reinterpret_cast<u32x4*>(a.out + (size_t)row * a.ld_out + col) = o;
       }
     }
     __syncthreads();
@@ -165,14 +184,15 @@ __global__ __launch_bounds__(256) void lora_pack_kernel(const void* src, int src
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-}  // namespace
-
-hipError_t launch_lora_merge(const bf16_t* base, long ld_base, bf16_t* out, long ld_out, int rows, int K, const LoraTerm* terms,
-                             int n_terms, hipStream_t stream) {
-  if (!base || !out || rows <= 0 || K <= 0 || (K % 8) != 0 || ld_base < K || ld_out < K || (ld_base % 8) != 0 || (ld_out % 8) != 0 ||
-      !aligned16(base) || !aligned16(out) || n_terms < 0 || n_terms > kLoraMaxTerms || (n_terms > 0 && !terms))
+// the checks and the launch of both element widths; kAlign = elements of a 16-byte vector, what K and the pitches are multiples of
+template <class T>
+hipError_t launch_merge(const T* base, long ld_base, T* out, long ld_out, int rows, int K, const LoraTerm* terms, int n_terms,
+                        hipStream_t stream) {
+  constexpr int kAlign = 16 / sizeof(T);
+  if (!base || !out || rows <= 0 || K <= 0 || (K % kAlign) != 0 || ld_base < K || ld_out < K || (ld_base % kAlign) != 0 ||
+      (ld_out % kAlign) != 0 || !aligned16(base) || !aligned16(out) || n_terms < 0 || n_terms > kLoraMaxTerms || (n_terms > 0 && !terms))
     return hipErrorInvalidValue;
-  MergeArgs a;
+  MergeArgs<T> a;
   a.base = base; a.ld_base = ld_base; a.out = out; a.ld_out = ld_out; a.rows = rows; a.K = K; a.n_terms = n_terms;
   for (int j = 0; j < n_terms; ++j) {
     const LoraTerm& t = terms[j];
@@ -187,10 +207,93 @@ hipError_t launch_lora_merge(const bf16_t* base, long ld_base, bf16_t* out, long
   const dim3 grid((unsigned)(tiles_m * a.tiles_n));
   if (n_terms == 0) {   // no live term: the base rows as they are
     if (out == base) return hipSuccess;
-    return hipMemcpy2DAsync(out, (size_t)ld_out * 2, base, (size_t)ld_base * 2, (size_t)K * 2, rows, hipMemcpyDeviceToDevice, stream);
+    return hipMemcpy2DAsync(out, (size_t)ld_out * sizeof(T), base, (size_t)ld_base * sizeof(T), (size_t)K * sizeof(T), rows,
+                            hipMemcpyDeviceToDevice, stream);
   }
-  if (n_terms == 1) hipLaunchKernelGGL(lora_merge_kernel<false>, grid, dim3(256), 0, stream, a);
-  else hipLaunchKernelGGL(lora_merge_kernel<true>, grid, dim3(256), 0, stream, a);
+  if (n_terms == 1) hipLaunchKernelGGL((lora_merge_kernel<false, T>), grid, dim3(256), 0, stream, a);
+  else hipLaunchKernelGGL((lora_merge_kernel<true, T>), grid, dim3(256), 0, stream, a);
+  return hipGetLastError();
+}
+
+// ---- out[i] = base[i] + sum_j scale_j * delta_j[i] (fp32): the delta sum from zero in term order, a multiply and an add per
+// term, never contracted; ONE add of the base element last.  Thread t takes vector t of the body, then element t of the tail.
+struct DeltaArgs {
+  const float* base; float* out;
+  size_t n_vec, tail0, n;   // 16-byte vectors of the body, first element of the scalar tail, elements
+  int n_terms;
+  const float* delta[kLoraMaxTerms];
+  float scale[kLoraMaxTerms];
+};
+
+// The products and sums are written out under contract(off): the toolchain's __fmul_rn / __fadd_rn are a plain * and + that it
+// is free to fuse into one fma, and this kernel's result is defined bit for bit.
+__global__ __launch_bounds__(256) void param_delta_kernel(DeltaArgs a) {
+#pragma clang fp contract(off)
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < a.n_vec) {
+    f32x4 sum = {0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < a.n_terms; ++j) {
+      const f32x4 dl = reinterpret_cast<const f32x4*>(a.delta[j])[i];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const float term = a.scale[j] * dl[q];
+        sum[q] = sum[q] + term;
+      }
+    }
+    const f32x4 b = reinterpret_cast<const f32x4*>(a.base)[i];
+    f32x4 o;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) o[q] = b[q] + sum[q];
+    reinterpret_cast<f32x4*>(a.out)[i] = o;
+  }
+  const size_t e = a.tail0 + i;
+  if (e < a.n) {
+    float sum = 0.f;
+    for (int j = 0; j < a.n_terms; ++j) {
+      const float term = a.scale[j] * a.delta[j][e];
+      sum = sum + term;
+    }
+    a.out[e] = a.base[e] + sum;
+  }
+}
+
+}  // namespace
+
+hipError_t launch_lora_merge(const bf16_t* base, long ld_base, bf16_t* out, long ld_out, int rows, int K, const LoraTerm* terms,
+                             int n_terms, hipStream_t stream) {
+  return launch_merge<bf16_t>(base, ld_base, out, ld_out, rows, K, terms, n_terms, stream);
+}
+
+hipError_t launch_lora_merge_f32(const float* base, long ld_base, float* out, long ld_out, int rows, int K, const LoraTerm* terms,
+                                 int n_terms, hipStream_t stream) {
+  return launch_merge<float>(base, ld_base, out, ld_out, rows, K, terms, n_terms, stream);
+}
+
+hipError_t launch_param_delta(const float* base, float* out, size_t n, const float* const* deltas, const float* scales, int n_terms,
+                              hipStream_t stream) {
+  if (!base || !out || n == 0 || n_terms < 1 || n_terms > kLoraMaxTerms || !deltas || !scales ||
+      ((reinterpret_cast<uintptr_t>(base) | reinterpret_cast<uintptr_t>(out)) & 3))
+    return hipErrorInvalidValue;
+  DeltaArgs a;
+  a.base = base; a.out = out; a.n = n; a.n_terms = 0;
+  bool vec = aligned16(base) && aligned16(out);   // one operand off a 16-byte boundary: every element goes through the tail
+  for (int j = 0; j < n_terms; ++j) {
+    if (!deltas[j] || (reinterpret_cast<uintptr_t>(deltas[j]) & 3)) return hipErrorInvalidValue;
+    if (scales[j] == 0.f) continue;   // left out, as the merge's callers leave a term with multiplier 0 out
+    vec = vec && aligned16(deltas[j]);
+    a.delta[a.n_terms] = deltas[j]; a.scale[a.n_terms] = scales[j];
+    ++a.n_terms;
+  }
+  for (int j = a.n_terms; j < kLoraMaxTerms; ++j) { a.delta[j] = nullptr; a.scale[j] = 0.f; }
+  if (a.n_terms == 0) {   // no live term: base as it is
+    if (out == base) return hipSuccess;
+    return hipMemcpyAsync(out, base, n * sizeof(float), hipMemcpyDeviceToDevice, stream);
+  }
+  a.n_vec = vec ? n / 4 : 0;
+  a.tail0 = a.n_vec * 4;
+  const size_t threads = a.n_vec > n - a.tail0 ? a.n_vec : n - a.tail0;
+  if ((threads + 255) / 256 > 0x7fffffffUL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(param_delta_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, a);
   return hipGetLastError();
 }
 

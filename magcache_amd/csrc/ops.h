@@ -129,6 +129,17 @@ struct LoraTerm {
 inline size_t lora_packed_elems(size_t n, size_t rank_pad) { return (n + 31) / 32 * 32 * rank_pad; }
 hipError_t launch_lora_merge(const bf16_t* base, long ld_base, bf16_t* out, long ld_out, int rows, int K, const LoraTerm* terms,
                              int n_terms, hipStream_t stream);
+// The same merge into an fp32 matrix (the Wan engine's time MLP, time projection and head): out = base + delta, the ONE fp32 add
+// last and no rounding step; same terms, same tiling.  K and the leading dimensions are multiples of 4 here.
+hipError_t launch_lora_merge_f32(const float* base, long ld_base, float* out, long ld_out, int rows, int K, const LoraTerm* terms,
+                                 int n_terms, hipStream_t stream);
+// out[i] = base[i] + sum_j scales[j] * deltas[j][i], fp32, i < n (any n > 0): the sum from zero in term order, a multiply and an
+// add per term (never contracted), one add of the base element last.  A term whose scale is 0 is left out; with no live term
+// out is a copy of base.  out may alias base.  16-byte vectors where base, out and every live delta are 16-byte aligned, single
+// elements for the tail (and for everything, where one of them is not).  hipErrorInvalidValue, and nothing launched, for
+// n == 0, fewer than 1 or more than kLoraMaxTerms terms, a null pointer or one that is not 4-byte aligned.
+hipError_t launch_param_delta(const float* base, float* out, size_t n, const float* const* deltas, const float* scales, int n_terms,
+                              hipStream_t stream);
 // dst (lora_packed_elems(n, rank_pad) elements) <- element (row, k) of an [n, rank] matrix at src[row * row_stride + k * col_stride],
 // fp32 (src_f32) or bf16: `up` as given (strides rank, 1), `down` [rank, K] transposed (strides 1, K)
 hipError_t launch_lora_pack(const void* src, int src_f32, long row_stride, long col_stride, int n, int rank, int rank_pad, bf16_t* dst,

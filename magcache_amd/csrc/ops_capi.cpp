@@ -18,7 +18,7 @@ static mc::GemmParams gp(const bf16_t* A, long lda, const bf16_t* W, long ldw, c
 extern "C" {
 
 const char* mc_last_error(void) { return mc::last_error(); }
-const char* mc_version(void) { return "magcache_hip 0.7 (gfx950)"; }
+const char* mc_version(void) { return "magcache_hip 0.7.1 (gfx950)"; }
 
 // split-K scratch of the single-op entry point (mc_op_set_splitk_workspace): the engines carry their own in their workspace
 static float* g_op_splitk_ws = nullptr;
@@ -299,15 +299,17 @@ size_t mc_op_lora_merge_scratch(int rows, int K, const mc_lora_term* terms, int 
   return bytes;
 }
 
-mc_status mc_op_lora_merge(const void* base, long ld_base, void* out, long ld_out, int rows, int K, const mc_lora_term* terms,
-                           int n_terms, void* scratch, size_t scratch_bytes, mc_stream s) {
+// both element widths of the merge: kAlign = elements of a 16-byte vector (8 bf16, 4 fp32)
+static mc_status op_lora_merge(bool f32, const void* base, long ld_base, void* out, long ld_out, int rows, int K,
+                               const mc_lora_term* terms, int n_terms, void* scratch, size_t scratch_bytes, mc_stream s) {
   hipStream_t stream = (hipStream_t)s;
+  const int kAlign = f32 ? 4 : 8;
   if (!base || !out || rows <= 0 || K <= 0 || n_terms < 0 || (n_terms > 0 && !terms)) return fail(MC_EINVAL, "lora_merge: null or empty operand");
   if (n_terms > MC_LORA_MAX_TERMS) return fail(MC_EINVAL, "lora_merge: %d terms, at most %d", n_terms, MC_LORA_MAX_TERMS);
   for (int j = 0; j < n_terms; ++j)
     if (!terms[j].down || !terms[j].up || terms[j].rank < 1) return fail(MC_EINVAL, "lora_merge: term %d has rank %d or a null matrix", j, terms[j].rank);
-  if ((K % 8) != 0 || ld_base < K || ld_out < K || (ld_base % 8) != 0 || (ld_out % 8) != 0 || (((uintptr_t)base | (uintptr_t)out) & 15))
-    return fail(MC_EINVAL, "lora_merge: K and the pitches are multiples of 8, pitch >= K, base and out 16-byte aligned");
+  if ((K % kAlign) != 0 || ld_base < K || ld_out < K || (ld_base % kAlign) != 0 || (ld_out % kAlign) != 0 || (((uintptr_t)base | (uintptr_t)out) & 15))
+    return fail(MC_EINVAL, "lora_merge: K and the pitches are multiples of %d, pitch >= K, base and out 16-byte aligned", kAlign);
   const size_t need = mc_op_lora_merge_scratch(rows, K, terms, n_terms);
   char* ws = (char*)scratch;
   if (ws && (scratch_bytes < need || ((uintptr_t)ws & 255)))
@@ -331,12 +333,35 @@ mc_status mc_op_lora_merge(const void* base, long ld_base, void* out, long ld_ou
     err = mc::launch_lora_pack(terms[j].up, 0, rank, 1, rows, rank, rank_pad, up, stream);
     if (err == hipSuccess) err = mc::launch_lora_pack(terms[j].down, 0, 1, K, K, rank, rank_pad, down_t, stream);
   }
-  if (err == hipSuccess) err = mc::launch_lora_merge((const bf16_t*)base, ld_base, (bf16_t*)out, ld_out, rows, K, t, n_terms, stream);
+  if (err == hipSuccess)
+    err = f32 ? mc::launch_lora_merge_f32((const float*)base, ld_base, (float*)out, ld_out, rows, K, t, n_terms, stream)
+              : mc::launch_lora_merge((const bf16_t*)base, ld_base, (bf16_t*)out, ld_out, rows, K, t, n_terms, stream);
   if (own) {
     if (err == hipSuccess) err = hipStreamSynchronize(stream);
     (void)hipFree(ws);
   }
   HIP_TRY(err);
+  return MC_OK;
+}
+
+mc_status mc_op_lora_merge(const void* base, long ld_base, void* out, long ld_out, int rows, int K, const mc_lora_term* terms,
+                           int n_terms, void* scratch, size_t scratch_bytes, mc_stream s) {
+  return op_lora_merge(false, base, ld_base, out, ld_out, rows, K, terms, n_terms, scratch, scratch_bytes, s);
+}
+
+mc_status mc_op_lora_merge_f32(const float* base, long ld_base, float* out, long ld_out, int rows, int K, const mc_lora_term* terms,
+                               int n_terms, void* scratch, size_t scratch_bytes, mc_stream s) {
+  return op_lora_merge(true, base, ld_base, out, ld_out, rows, K, terms, n_terms, scratch, scratch_bytes, s);
+}
+
+mc_status mc_op_param_delta(const float* base, float* out, size_t n, const float* const* deltas, const float* scales, int n_terms,
+                            mc_stream s) {
+  if (!base || !out || n == 0 || !deltas || !scales) return fail(MC_EINVAL, "param_delta: null or empty operand");
+  if (n_terms < 1 || n_terms > MC_LORA_MAX_TERMS) return fail(MC_EINVAL, "param_delta: %d terms, 1 to %d", n_terms, MC_LORA_MAX_TERMS);
+  for (int j = 0; j < n_terms; ++j)
+    if (!deltas[j] || ((uintptr_t)deltas[j] & 3)) return fail(MC_EINVAL, "param_delta: delta %d is null or not 4-byte aligned", j);
+  if (((uintptr_t)base | (uintptr_t)out) & 3) return fail(MC_EINVAL, "param_delta: base and out are 4-byte aligned");
+  HIP_TRY(mc::launch_param_delta(base, out, n, deltas, scales, n_terms, (hipStream_t)s));
   return MC_OK;
 }
 

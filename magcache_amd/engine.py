@@ -6,6 +6,7 @@ import torch
 
 from . import _lib
 from ._lib import MC_BF16, MC_F32, MC_MODE_CALIB, MC_MODE_FULL, MC_MODE_SKIP, McConfig, check
+from .adapters import LoraHost
 
 WAN_T2V_1_3B = dict(dim=1536, ffn_dim=8960, freq_dim=256, num_heads=12, num_layers=30, text_len=512, in_dim=16,
                     out_dim=16, text_dim=4096, eps=1e-6)
@@ -93,8 +94,20 @@ def synthetic_weights(cfg, seed=0, std=0.02, device="cuda"):
         yield name, t
 
 
-class Engine:
-    """One DiT engine on one device (one per process).  latent grid = (F, H, W) of the VAE latent."""
+class Engine(LoraHost):
+    """One DiT engine on one device (one per process).  latent grid = (F, H, W) of the VAE latent.
+
+    LoRA adapters (adapters.LoraHost over mc_lora_*): load_lora / set_adapters / set_lora_call_scale / unload_lora /
+    apply_lora / lora_info.  An adapter file is read by lora.parse_wan_lora_state_dict: low-rank pairs on the bf16 matrices
+    and on the fp32 time MLP, time projection and head, additive deltas on biases, norm weights and modulation tables.
+    Every apply that changed a weight makes the engine forget the cached text contexts, the CLIP context and the VACE
+    context (set them again; WanModelHIP does by itself)."""
+    _lora_abi = "mc_lora_"
+    _lora_prefix = ""
+
+    def _lora_entries(self, sd, prefix):
+        from .lora import parse_wan_lora_state_dict
+        return parse_wan_lora_state_dict(sd)
 
     def __init__(self, cfg, latent_grid, device="cuda:0", sp_rank=0, sp_size=1, n_branches=2, calibration=False,
                  sp_phases=False):
@@ -127,6 +140,7 @@ class Engine:
         self.tokens_per_rank = self.seq_len // sp_size
         self.head_stride = (4 * cfg["out_dim"] + 63) // 64 * 64    # row stride of "head_tokens" (fp32 elements)
         self._tok_t = None
+        self._lora_init()
 
     def _bind(self, nbytes):
         """a zeroed workspace of `nbytes` (at least the current plan), bound with mc_set_workspace; the tensor it replaces is

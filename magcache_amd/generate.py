@@ -113,6 +113,9 @@ def _parse_args(argv=None):
     p.add_argument("--y_file", type=str, default=None, help="i2v: torch tensor [20, F, H/8, W/8] (mask + conditioning latent)")
     p.add_argument("--vace_context_file", type=str, default=None, help="vace: torch tensor [96, F, H/8, W/8]")
     p.add_argument("--vace_context_scale", type=float, default=1.0)
+    p.add_argument("--lora_file", action="append", default=[], metavar="PATH[:SCALE]",
+                   help="a LoRA adapter (*.safetensors), merged into the DiT weights on the device at SCALE (default 1); "
+                        "repeatable: the files are loaded in order as adapters lora0, lora1, ...")
     # accepted for command-line compatibility; they configure parts that are not in this repository
     for flag, kw in (("--offload_model", dict(type=str2bool, default=None)), ("--ulysses_size", dict(type=int, default=1)),
                      ("--ring_size", dict(type=int, default=1)), ("--t5_fsdp", dict(action="store_true")),
@@ -128,6 +131,28 @@ def _parse_args(argv=None):
     args = p.parse_args(argv)
     _validate_args(args)
     return args
+
+
+def _lora_spec(spec):
+    """'PATH[:SCALE]' -> (path, scale): the part behind the last colon is the scale where it reads as a number"""
+    path, sep, tail = spec.rpartition(":")
+    if sep and path:
+        try:
+            return path, float(tail)
+        except ValueError:
+            pass
+    return spec, 1.0
+
+
+def _load_loras(model, specs):
+    """--lora_file: every adapter read with the loader of the checkpoints and merged before sampling"""
+    if not specs:
+        return
+    from safetensors.torch import load_file
+    for i, spec in enumerate(specs):
+        path, scale = _lora_spec(spec)
+        model.load_lora(load_file(path, device="cpu"), adapter=f"lora{i}", scale=scale)
+        logging.info(f"adapter lora{i}: {path} at scale {scale:g}; {model.lora_info()}")
 
 
 def _context(path, prompt, seed, text_dim, device):
@@ -171,6 +196,9 @@ def generate(args):
         logging.info("--ulysses_size/--ring_size are ignored: the token sequence is sharded over WORLD_SIZE ranks")
 
     if args.task.endswith("A14B"):
+        if args.lora_file:   # two experts, two sets of weights: which file is whose is the caller's knowledge
+            raise ValueError("--lora_file: the A14B tasks run two experts, each of which takes its own adapters "
+                             "(WanModelHIP.load_lora on the high-noise and the low-noise model)")
         return _generate_wan22(args, device, rank, world, layout)
     if args.task == "ti2v-5B":
         return _generate_ti2v(args, device, rank, world, layout)
@@ -200,6 +228,7 @@ def generate(args):
     else:
         logging.warning("no *.safetensors under --ckpt_dir: using seeded RANDOM-INIT weights of the architecture")
         model.engine.load_weights(synthetic_weights(cfg, seed=0, device=device))
+    _load_loras(model, args.lora_file)
 
     if args.use_magcache:
         name = args.ckpt_dir or ("Wan2.1-T2V-1.3B" if "1.3B" in args.task else "Wan2.1-T2V-14B")
@@ -282,6 +311,7 @@ def _generate_ti2v(args, device, rank, world, layout):
     else:
         logging.warning("no *.safetensors under --ckpt_dir: seeded RANDOM-INIT weights of the architecture")
         model.engine.load_weights(synthetic_weights(cfg, seed=0, device=device))
+    _load_loras(model, args.lora_file)
     i2v = args.y_file is not None
     if args.use_magcache:
         table = wan22.table_without_pad("wan2.2_ti2v_5B_i2v" if i2v else "wan2.2_ti2v_5B_t2v")     # :735-738

@@ -1,4 +1,5 @@
-"""LoRA state dicts -> the weight names of the MM-DiT engine.  Pure Python: no GPU, no library.
+"""LoRA state dicts -> the weight names of the engines.  Pure Python: no GPU, no library.  The MM-DiT engine's reader comes
+first; the Wan engine's (parse_wan_lora_state_dict, wan_lora_target_names) is at the end of the file.
 
 An adapter file names the MODULE it wraps; the engine names WEIGHTS, by their upstream state_dict names
 (mc_mmdit_set_weight), and takes an adapter pair per such name (mc_mmdit_lora_set) -- also where it stores several upstream
@@ -109,3 +110,115 @@ def lora_target_names(family, n_double, n_single=0, refiner_depth=0):
     else:
         raise ValueError(f"unknown family '{family}'")
     return names
+
+
+# ------------------------------------------------------------------------------------------------ Wan
+_WAN_PREFIXES = ("model.diffusion_model.", "diffusion_model.", "transformer.")   # longest first
+_WAN_PAIR = re.compile(r"^(?P<module>.+)\.(?:lora_(?P<ab>[AB])(?:\.[^.]+)?|lora\.(?P<du>down|up)|lora_(?P<du2>down|up))\.weight$")
+_WAN_DELTA = re.compile(r"^(?P<module>.+)\.(?P<kind>diff|diff_b|diff_m)$")
+# diffusers' WanTransformer3DModel module names -> upstream WanModel's, inside a block ...
+_WAN_BLOCK_TABLE = {
+    "attn1.to_q": "self_attn.q", "attn1.to_k": "self_attn.k", "attn1.to_v": "self_attn.v", "attn1.to_out.0": "self_attn.o",
+    "attn1.norm_q": "self_attn.norm_q", "attn1.norm_k": "self_attn.norm_k",
+    "attn2.to_q": "cross_attn.q", "attn2.to_k": "cross_attn.k", "attn2.to_v": "cross_attn.v", "attn2.to_out.0": "cross_attn.o",
+    "attn2.norm_q": "cross_attn.norm_q", "attn2.norm_k": "cross_attn.norm_k",
+    "attn2.add_k_proj": "cross_attn.k_img", "attn2.add_v_proj": "cross_attn.v_img", "attn2.norm_added_k": "cross_attn.norm_k_img",
+    "ffn.net.0.proj": "ffn.0", "ffn.net.2": "ffn.2", "norm2": "norm3", "scale_shift_table": "modulation",
+}
+# ... and outside the blocks
+_WAN_TOP_TABLE = {
+    "condition_embedder.time_embedder.linear_1": "time_embedding.0", "condition_embedder.time_embedder.linear_2": "time_embedding.2",
+    "condition_embedder.time_proj": "time_projection.1",
+    "condition_embedder.text_embedder.linear_1": "text_embedding.0", "condition_embedder.text_embedder.linear_2": "text_embedding.2",
+    "proj_out": "head.head", "scale_shift_table": "head.modulation",
+}
+_WAN_BLOCK = re.compile(r"^(?P<block>(?:vace_)?blocks\.\d+)\.(?P<rest>.+)$")
+
+
+def _wan_module(module):
+    """an adapter file's module name as upstream WanModel spells it (diffusers' names through the tables, others as given)"""
+    m = _WAN_BLOCK.match(module)
+    if m:
+        return m.group("block") + "." + _WAN_BLOCK_TABLE.get(m.group("rest"), m.group("rest"))
+    return _WAN_TOP_TABLE.get(module, module)
+
+
+def parse_wan_lora_state_dict(sd):
+    """{target: ("pair", down [rank, in], up [out, rank], alpha or None) | ("delta", tensor)} of a Wan adapter state dict,
+    keyed by upstream WanModel parameter names ("blocks.3.self_attn.q.weight", "blocks.3.modulation", "head.modulation"):
+    the names mc_lora_set / mc_lora_set_delta take.
+
+    Read: the pair spellings of parse_lora_state_dict plus <module>.lora_down.weight / <module>.lora_up.weight; one of the
+    prefixes "model.diffusion_model.", "diffusion_model.", "transformer." (where any key carries one, the keys that carry it
+    are the adapter and the others another component's); the additive spellings of the ComfyUI family, <module>.diff
+    (-> <module>.weight), <module>.diff_b (-> <module>.bias) and <block>.diff_m (-> <block>.modulation; "head.diff_m" ->
+    "head.modulation"); and diffusers' WanTransformer3DModel module names, mapped to upstream's by _WAN_BLOCK_TABLE /
+    _WAN_TOP_TABLE.  The delta spellings and the tables are written from knowledge of those projects: neither an adapter
+    file nor a copy of diffusers was at hand to check them against.
+
+    ValueError for a key that is none of these, half a pair, an alpha without a pair, a pair whose ranks differ, and a
+    matrix or parameter that two keys address."""
+    keys = list(sd.keys())
+    strip = 0
+    for prefix in _WAN_PREFIXES:
+        if any(k.startswith(prefix) for k in keys):
+            keys = [k for k in keys if k.startswith(prefix)]
+            strip = len(prefix)
+            break
+    down, up, alpha, delta, orphans = {}, {}, {}, {}, []
+    for key in keys:
+        name = key[strip:]
+        m = _WAN_PAIR.match(name)
+        if m:
+            module = _wan_module(m.group("module"))
+            is_down = m.group("ab") == "A" or "down" in (m.group("du"), m.group("du2"))
+            half = down if is_down else up
+            if module in half:
+                raise ValueError(f"LoRA state dict: '{key}' repeats a matrix of '{module}' (several adapters in one state "
+                                 "dict: load them one by one)")
+            half[module] = sd[key]
+            continue
+        m = _ALPHA.match(name)
+        if m:
+            alpha[_wan_module(m.group("module"))] = sd[key]
+            continue
+        m = _WAN_DELTA.match(name)
+        if m:
+            module, kind = _wan_module(m.group("module")), m.group("kind")
+            if kind == "diff_m":
+                target = module + ".modulation"
+            elif module.endswith("modulation"):     # diffusers' scale_shift_table is a parameter, not a module
+                target = module
+            else:
+                target = module + (".bias" if kind == "diff_b" else ".weight")
+            if target in delta:
+                raise ValueError(f"LoRA state dict: '{key}' repeats the delta of '{target}'")
+            delta[target] = sd[key]
+            continue
+        orphans.append(key)
+    orphans += [f"{m} (down without up)" for m in down if m not in up]
+    orphans += [f"{m} (up without down)" for m in up if m not in down]
+    orphans += [f"{m}.alpha (no pair)" for m in alpha if m not in down and m not in up]
+    if orphans:
+        raise ValueError(f"LoRA state dict: {len(orphans)} keys belong to no down / up pair and are no delta, e.g. {sorted(orphans)[:5]}")
+    out = {}
+    for module, d in down.items():
+        u = up[module]
+        if len(d.shape) != 2 or len(u.shape) != 2 or d.shape[0] != u.shape[1]:
+            raise ValueError(f"LoRA pair of '{module}': down {tuple(d.shape)} and up {tuple(u.shape)} share no rank")
+        a = alpha.get(module)
+        out[module + ".weight"] = ("pair", d, u, None if a is None else float(a))
+    for target, t in delta.items():
+        if target in out:
+            raise ValueError(f"LoRA state dict: '{target}' has a low-rank pair and a delta")
+        out[target] = ("delta", t)
+    return out
+
+
+def wan_lora_target_names(cfg):
+    """Every parameter name of a Wan engine built from `cfg` that takes a low-rank pair (the matrices: "....weight" of a
+    Linear, bf16 in the blocks and embedders, fp32 for time_embedding, time_projection and head.head) or an additive delta
+    (biases, norm weights, modulation tables, the fp32 matrices): the engine's whole state dict minus the patch embedders'
+    weights, which take neither."""
+    from .engine import weight_names
+    return [n for n, _ in weight_names(cfg) if n not in ("patch_embedding.weight", "vace_patch_embedding.weight")]

@@ -26,6 +26,7 @@ import torch
 from . import _lib
 from ._lib import (MC_F32, MC_BF16, MC_FAMILY_FLUX, MC_FAMILY_HUNYUAN, MC_FAMILY_QWEN, MC_MODE_CALIB, MC_MODE_FULL,
                    MC_MODE_SKIP, McMmditConfig, check)
+from .adapters import LoraHost
 from .mag_ratios import TABLES
 from .model import nearest_interp
 from .parallel import SP_OVERLAP
@@ -49,7 +50,7 @@ def _f32(t, device):
     return t.detach().to(device=device, dtype=torch.float32).contiguous()
 
 
-class MMDiTEngine:
+class MMDiTEngine(LoraHost):
     """One MM-DiT engine on one device.  PyTorch-ROCm owns the workspace and the stream, the library the rest."""
 
     def __init__(self, family, dim, num_heads, n_double, n_single, in_channels, out_channels, txt_dim, txt_len, vec_dim,
@@ -162,93 +163,8 @@ class MMDiTEngine:
         if n:
             raise KeyError(f"{n} weights missing, e.g.: {buf.value.decode().split()[:5]}")
 
-    # ---- LoRA adapters, merged into the weights on the device (mc_mmdit_lora_*; magcache_amd/lora.py reads the files)
-    def load_lora(self, sd, adapter="default", scale=1.0, strict=True, prefix="transformer."):
-        """Load a LoRA state dict (PEFT / diffusers spellings, lora.parse_lora_state_dict) as `adapter` at `scale` and merge
-        it.  A target the engine takes no adapter on (an unknown name, the fp32 head, a padded embedder, wrong shapes) raises
-        under `strict` -- the engine is then as before the call --, and is skipped otherwise: the skipped weight names are
-        returned.  Loading a known adapter again replaces the pairs it brings."""
-        from .lora import lora_factor, parse_lora_state_dict
-        pairs = parse_lora_state_dict(sd, prefix=prefix)
-        known, skipped, done = adapter in self._lora, [], 0
-        for target, (down, up, alpha) in pairs.items():
-            dt = torch.bfloat16 if down.dtype == torch.bfloat16 and up.dtype == torch.bfloat16 else torch.float32
-            d = down.detach().to(device=self.device, dtype=dt).contiguous()
-            u = up.detach().to(device=self.device, dtype=dt).contiguous()
-            st = self.lib.mc_mmdit_lora_set(self.h, adapter.encode(), target.encode(), _ptr(d), (C.c_int64 * 2)(*d.shape), _ptr(u),
-                                            (C.c_int64 * 2)(*u.shape), MC_BF16 if dt == torch.bfloat16 else MC_F32,
-                                            lora_factor(down, alpha), _stream())
-            torch.cuda.current_stream().synchronize()      # d / u are read by launches on the stream
-            if st == _lib.MC_OK:
-                done += 1
-            elif st == _lib.MC_EINVAL and not strict:
-                skipped.append(target)
-            else:
-                msg = self.lib.mc_last_error().decode()
-                if done and not known:
-                    self.unload_lora(adapter, _known=True)
-                elif done:
-                    self.apply_lora()
-                raise _lib.MagCacheHipError(st, msg)
-        if done or known:
-            self._lora[adapter] = float(scale)
-            check(self.lib.mc_mmdit_lora_scale(self.h, adapter.encode(), float(scale) * self._lora_call))
-        self.apply_lora()
-        return skipped
-
-    def set_adapters(self, names, scales=None):
-        """diffusers' set_adapters: the adapters of `names` (a name or a list) are active at `scales` (a number, a list, None
-        = 1.0), every other loaded adapter is off (scale 0, its pairs kept); merged at once."""
-        names = [names] if isinstance(names, str) else list(names)
-        scales = [1.0 if scales is None else scales] * len(names) if not isinstance(scales, (list, tuple)) else list(scales)
-        if len(scales) != len(names):
-            raise ValueError(f"{len(names)} adapters, {len(scales)} scales")
-        unknown = [n for n in names if n not in self._lora]
-        if unknown:
-            raise KeyError(f"unknown adapters {unknown}; loaded: {sorted(self._lora)}")
-        want = {n: 0.0 for n in self._lora}
-        want.update({n: float(s) for n, s in zip(names, scales)})
-        self._lora = want
-        self._push_lora_scales()
-
-    def _push_lora_scales(self):
-        for n, s in self._lora.items():
-            check(self.lib.mc_mmdit_lora_scale(self.h, n.encode(), s * self._lora_call))
-        self.apply_lora()
-
-    def set_lora_call_scale(self, scale):
-        """The factor of one call on every adapter's scale -- what scale_lora_layers(model, lora_scale) does at the top of
-        the reference forwards and unscale_lora_layers undoes at their end.  Nothing happens without adapters or while the
-        factor stays what it is; else every adapter is rescaled and the weights are merged again."""
-        scale = float(scale)
-        if not self._lora or scale == self._lora_call:
-            return
-        self._lora_call = scale
-        self._push_lora_scales()
-
-    def unload_lora(self, adapter=None, _known=False):
-        """remove one adapter, or all of them (None): the weights it touched are the loaded ones again, bit for bit"""
-        if adapter is not None and adapter not in self._lora and not _known:
-            raise KeyError(f"unknown adapter '{adapter}'; loaded: {sorted(self._lora)}")
-        check(self.lib.mc_mmdit_lora_remove(self.h, adapter.encode() if adapter is not None else None))
-        if adapter is None:
-            self._lora = {}
-        else:
-            self._lora.pop(adapter, None)
-        if not self._lora:
-            self._lora_call = 1.0
-        self.apply_lora()
-
-    def apply_lora(self):
-        """merge what changed (mc_mmdit_lora_apply): after set_weight on a weight an adapter touches; the other calls here
-        apply by themselves"""
-        check(self.lib.mc_mmdit_lora_apply(self.h, _stream()))
-        torch.cuda.current_stream().synchronize()
-
-    def lora_info(self):
-        a, n, b = C.c_int(), C.c_int(), C.c_size_t()
-        check(self.lib.mc_mmdit_lora_info(self.h, C.byref(a), C.byref(n), C.byref(b)))
-        return dict(adapters=a.value, linears=n.value, base_bytes=b.value, scales=dict(self._lora), call_scale=self._lora_call)
+    # ---- LoRA adapters, merged into the weights on the device (mc_mmdit_lora_*; magcache_amd/lora.py reads the files):
+    # load_lora / set_adapters / set_lora_call_scale / unload_lora / apply_lora / lora_info are adapters.LoraHost's
 
     def buffer(self, name, dtype=torch.uint8):
         off, nb = C.c_size_t(), C.c_size_t()

@@ -283,6 +283,35 @@ class WanModelHIP:
             self._tok_next = (self._tok_next + 1) % len(self._tok_ring)
         return [out.float()]
 
+    # ---- LoRA adapters (Engine.load_lora & co.): a merge changes what the cached contexts were computed from, so the
+    # identity keys go with it and the next call uploads the text, CLIP and VACE contexts again
+    def _lora_call(self, name, *args, **kw):
+        try:
+            return getattr(self.engine, name)(*args, **kw)
+        finally:
+            self._ctx_keys, self._ctx_lru = [None, None], 0
+            self._clip_key = self._vace_key = None
+
+    def load_lora(self, sd, adapter="default", scale=1.0, strict=True):
+        """Load a Wan adapter state dict (lora.parse_wan_lora_state_dict) as `adapter` at `scale` and merge it; returns the
+        names skipped under strict=False.  For Wan2.2 each expert is a WanModelHIP and takes its own adapters."""
+        return self._lora_call("load_lora", sd, adapter=adapter, scale=scale, strict=strict)
+
+    def set_adapters(self, names, scales=None):
+        return self._lora_call("set_adapters", names, scales)
+
+    def set_lora_call_scale(self, scale):
+        return self._lora_call("set_lora_call_scale", scale)
+
+    def unload_lora(self, adapter=None):
+        return self._lora_call("unload_lora", adapter)
+
+    def apply_lora(self):
+        return self._lora_call("apply_lora")
+
+    def lora_info(self):
+        return self.engine.lora_info()
+
     def pair_begin(self):
         """The sampler's declaration that the next two calls are the cond / uncond evaluations of ONE step -- same latent,
         same t, same conditioning apart from the text context --, passed on to the engine (mc_pair_begin), which then
