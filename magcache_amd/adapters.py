@@ -1,6 +1,8 @@
-"""The adapter bookkeeping both engines' Python wrappers share: load / set_adapters / per-call scale / unload / apply / info
-over the C calls of one weight store (mc_mmdit_lora_* for MMDiTEngine, mc_lora_* for the Wan Engine).  The class that mixes
-this in has `lib`, `h` and `device`, names its C calls' prefix in `_lora_abi` and reads an adapter file in `_lora_entries`."""
+"""What both engines' Python wrappers share, over the C calls of one prefix (`_abi`: mc_ for the Wan Engine, mc_mmdit_ for
+MMDiTEngine).  EngineHost: the workspace PyTorch owns and the engine is bound to, weights in, buffers out, destruction.
+LoraHost: the adapter bookkeeping -- load / set_adapters / per-call scale / unload / apply / info -- over the <_abi>lora_*
+calls of the weight store; the class that mixes it in has `lib`, `h` and `device` and reads an adapter file in
+`_lora_entries`.  LoraModel: the adapter calls of the engine on the model objects."""
 import ctypes as C
 
 import torch
@@ -14,14 +16,22 @@ def _stream():
 
 
 def _ptr(t):
-    return C.c_void_p(t.data_ptr())
+    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
 _CLASS_DEFAULT = object()     # load_lora(prefix=...): the class's _lora_prefix
 
 
+class _LoraAbi:
+    """`_lora_abi`, derived from the class's `_abi`; readable on the class as on an instance"""
+
+    def __get__(self, obj, cls):
+        return cls._abi + "lora_"
+
+
 class LoraHost:
-    _lora_abi = "mc_mmdit_lora_"
+    _abi = "mc_mmdit_"
+    _lora_abi = _LoraAbi()
     _lora_prefix = "transformer."       # default `prefix` of load_lora
 
     def _lora_init(self):
@@ -132,3 +142,100 @@ class LoraHost:
         a, n, b = C.c_int(), C.c_int(), C.c_size_t()
         check(self._lora_fn("info")(self.h, C.byref(a), C.byref(n), C.byref(b)))
         return dict(adapters=a.value, linears=n.value, base_bytes=b.value, scales=dict(self._lora), call_scale=self._lora_call)
+
+
+class EngineHost(LoraHost):
+    """An engine handle `h` of `lib` on `device`, bound to a workspace tensor.  The subclass creates the handle, says in
+    _rebound() what its Python side holds that the engine forgot with the old binding and in _release() what goes before
+    the handle is destroyed, and keeps the geometry calls: their arguments differ."""
+
+    def _fn(self, name):
+        return getattr(self.lib, self._abi + name)
+
+    def _rebound(self):
+        pass
+
+    def _release(self):
+        pass
+
+    def _bind(self, nbytes):
+        """a zeroed workspace of `nbytes` (at least the current plan), bound with <_abi>set_workspace; the tensor it replaces
+        is let go after a device synchronise (forwards in flight may still use it)"""
+        workspace = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
+        off = (-workspace.data_ptr()) % 256
+        ws = workspace[off:off + nbytes]
+        # finite, deterministic scratch: padded rows feed MFMAs (0 * NaN would poison valid rows)
+        ws.zero_()
+        torch.cuda.synchronize(self.device)
+        check(self._fn("set_workspace")(self.h, _ptr(ws), nbytes))
+        self.workspace, self.ws = workspace, ws
+        self._rebound()               # the engine forgot them with everything else that belonged to the old binding
+
+    def _grow(self, need):
+        """rebind when the workspace is smaller than `need` (reserve, set_geometry)"""
+        if need > self.ws.numel():
+            self._bind(need)
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                torch.cuda.synchronize(self.device)
+                self._release()
+                self._fn("destroy")(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def set_weight(self, name, tensor):
+        t = tensor.detach()
+        if t.dtype not in (torch.float32, torch.bfloat16):
+            t = t.float()
+        t = t.to(self.device).contiguous()
+        shape = (C.c_int64 * t.dim())(*t.shape)
+        dt = MC_F32 if t.dtype == torch.float32 else MC_BF16
+        st = self._fn("set_weight")(self.h, name.encode(), _ptr(t), dt, shape, t.dim(), _stream())
+        if st != 0 and dt == MC_BF16 and b"must be given as fp32" in self.lib.mc_last_error():
+            # fp32 slots (biases, norm weights, modulation, time MLP, head): a state_dict converted with
+            # .to(bfloat16) (upstream convert_model_dtype) still loads, widened exactly
+            t = t.float()
+            st = self._fn("set_weight")(self.h, name.encode(), _ptr(t), MC_F32, shape, t.dim(), _stream())
+        check(st)
+        torch.cuda.current_stream().synchronize()  # t may be freed by the caller right after
+
+    def load_weights(self, named_tensors):
+        items = named_tensors.items() if hasattr(named_tensors, "items") else named_tensors
+        for name, t in items:
+            self.set_weight(name, t)
+        buf = C.create_string_buffer(4096)
+        n = self._fn("weights_missing")(self.h, buf, 4096)
+        if n:
+            raise KeyError(f"{n} weights missing, e.g.: {buf.value.decode().split()[:5]}")
+
+    def buffer(self, name, dtype=torch.uint8):
+        off, nb = C.c_size_t(), C.c_size_t()
+        check(self._fn("buffer_info")(self.h, name.encode(), C.byref(off), C.byref(nb)))
+        return self.ws[off.value:off.value + nb.value].view(dtype)
+
+
+class LoraModel:
+    """the adapter calls of the model's engine on the model object; _lora_call is where a model does more than delegate"""
+
+    def _lora_call(self, name, *args, **kw):
+        return getattr(self.engine, name)(*args, **kw)
+
+    def load_lora(self, sd, adapter="default", scale=1.0, strict=True):
+        """Load an adapter state dict (the spellings the engine's _lora_entries reads) as `adapter` at `scale` and merge it;
+        returns the names skipped under strict=False."""
+        return self._lora_call("load_lora", sd, adapter=adapter, scale=scale, strict=strict)
+
+    def set_adapters(self, names, scales=None):
+        return self._lora_call("set_adapters", names, scales)
+
+    def unload_lora(self, adapter=None):
+        return self._lora_call("unload_lora", adapter)
+
+    def apply_lora(self):
+        return self._lora_call("apply_lora")
+
+    def lora_info(self):
+        return self.engine.lora_info()

@@ -6,7 +6,7 @@ import torch
 
 from . import _lib
 from ._lib import MC_BF16, MC_F32, MC_MODE_CALIB, MC_MODE_FULL, MC_MODE_SKIP, McConfig, check
-from .adapters import LoraHost
+from .adapters import EngineHost, _ptr, _stream
 
 WAN_T2V_1_3B = dict(dim=1536, ffn_dim=8960, freq_dim=256, num_heads=12, num_layers=30, text_len=512, in_dim=16,
                     out_dim=16, text_dim=4096, eps=1e-6)
@@ -29,14 +29,6 @@ def vace_geometry(cfg):
     assert layers[0] == 0 and all(b - a == stride for a, b in zip(layers, layers[1:])), \
         f"vace_layers {layers}: the engine takes an arithmetic progression starting at 0 (upstream's configs are)"
     return len(layers), stride
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
 def weight_names(cfg):
@@ -94,15 +86,16 @@ def synthetic_weights(cfg, seed=0, std=0.02, device="cuda"):
         yield name, t
 
 
-class Engine(LoraHost):
+class Engine(EngineHost):
     """One DiT engine on one device (one per process).  latent grid = (F, H, W) of the VAE latent.
 
+    The workspace, set_weight / load_weights, buffer and destruction are adapters.EngineHost's.
     LoRA adapters (adapters.LoraHost over mc_lora_*): load_lora / set_adapters / set_lora_call_scale / unload_lora /
     apply_lora / lora_info.  An adapter file is read by lora.parse_wan_lora_state_dict: low-rank pairs on the bf16 matrices
     and on the fp32 time MLP, time projection and head, additive deltas on biases, norm weights and modulation tables.
     Every apply that changed a weight makes the engine forget the cached text contexts, the CLIP context and the VACE
     context (set them again; WanModelHIP does by itself)."""
-    _lora_abi = "mc_lora_"
+    _abi = "mc_"
     _lora_prefix = ""
 
     def _lora_entries(self, sd, prefix):
@@ -139,21 +132,15 @@ class Engine(LoraHost):
         self._bind(self.lib.mc_workspace_bytes(self.h))
         self.tokens_per_rank = self.seq_len // sp_size
         self.head_stride = (4 * cfg["out_dim"] + 63) // 64 * 64    # row stride of "head_tokens" (fp32 elements)
-        self._tok_t = None
         self._lora_init()
 
-    def _bind(self, nbytes):
-        """a zeroed workspace of `nbytes` (at least the current plan), bound with mc_set_workspace; the tensor it replaces is
-        let go after a device synchronise (forwards in flight may still use it)"""
-        workspace = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
-        off = (-workspace.data_ptr()) % 256
-        ws = workspace[off:off + nbytes]
-        # finite, deterministic scratch: padded rows feed MFMAs (0 * NaN would poison valid rows)
-        ws.zero_()
-        torch.cuda.synchronize(self.device)
-        check(self.lib.mc_set_workspace(self.h, _ptr(ws), nbytes))
-        self.workspace, self.ws = workspace, ws
-        self._tok_t = None            # the engine forgot them with everything else that belonged to the old binding
+    def _rebound(self):
+        self._tok_t = None
+
+    def _release(self):
+        for comm in getattr(self, "_rccl", []):
+            self.lib.mc_sp_comm_destroy(comm)
+        self._rccl = []
 
     # ---- the latent grid as a property of the call
     def geometry_bytes(self, latent_grid):
@@ -169,8 +156,7 @@ class Engine(LoraHost):
         need = self.ws.numel()
         for g in grids:
             need = max(need, self.geometry_bytes(g))
-        if need > self.ws.numel():
-            self._bind(need)
+        self._grow(need)
         return need
 
     def set_geometry(self, latent_grid):
@@ -181,58 +167,12 @@ class Engine(LoraHost):
         grid = tuple(int(v) for v in latent_grid)
         if self.sharded:
             raise ValueError("set_geometry: a sharded engine (sp_size > 1 or sp_phases) keeps the grid it was created with")
-        need = self.geometry_bytes(grid)
-        if need > self.ws.numel():
-            self._bind(need)
+        self._grow(self.geometry_bytes(grid))
         check(self.lib.mc_set_geometry(self.h, *grid))
         self.grid = grid
         self.seq_len = grid[0] * (grid[1] // 2) * (grid[2] // 2)
         self.tokens_per_rank = self.seq_len // self.sp_size
         self._tok_t = None
-
-    def __del__(self):
-        try:
-            if getattr(self, "h", None):
-                torch.cuda.synchronize(self.device)
-                for comm in getattr(self, "_rccl", []):
-                    self.lib.mc_sp_comm_destroy(comm)
-                self._rccl = []
-                self.lib.mc_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
-
-    # ---- weights
-    def set_weight(self, name, tensor):
-        t = tensor.detach()
-        if t.dtype not in (torch.float32, torch.bfloat16):
-            t = t.float()
-        t = t.to(self.device).contiguous()
-        shape = (C.c_int64 * t.dim())(*t.shape)
-        dt = MC_F32 if t.dtype == torch.float32 else MC_BF16
-        st = self.lib.mc_set_weight(self.h, name.encode(), _ptr(t), dt, shape, t.dim(), _stream())
-        if st != 0 and dt == MC_BF16 and b"must be given as fp32" in self.lib.mc_last_error():
-            # fp32 slots (biases, norm weights, modulation, time MLP, head): a state_dict converted with
-            # .to(bfloat16) (upstream convert_model_dtype) still loads, widened exactly
-            t = t.float()
-            st = self.lib.mc_set_weight(self.h, name.encode(), _ptr(t), MC_F32, shape, t.dim(), _stream())
-        check(st)
-        torch.cuda.current_stream().synchronize()  # t may be freed by the caller right after
-
-    def load_weights(self, named_tensors):
-        items = named_tensors.items() if hasattr(named_tensors, "items") else named_tensors
-        for name, t in items:
-            self.set_weight(name, t)
-        buf = C.create_string_buffer(4096)
-        n = self.lib.mc_weights_missing(self.h, buf, 4096)
-        if n:
-            raise KeyError(f"{n} weights missing, e.g.: {buf.value.decode().split()[:5]}")
-
-    # ---- buffers
-    def buffer(self, name, dtype=torch.uint8):
-        off, nb = C.c_size_t(), C.c_size_t()
-        check(self.lib.mc_buffer_info(self.h, name.encode(), C.byref(off), C.byref(nb)))
-        return self.ws[off.value:off.value + nb.value].view(dtype)
 
     def residual(self, branch):
         """fp32 [seq_len/sp, dim] view of residual_cache[branch] (rows past the valid tokens cut off)."""

@@ -26,7 +26,8 @@ import torch
 from . import _lib
 from ._lib import (MC_F32, MC_BF16, MC_FAMILY_FLUX, MC_FAMILY_HUNYUAN, MC_FAMILY_QWEN, MC_MODE_CALIB, MC_MODE_FULL,
                    MC_MODE_SKIP, McMmditConfig, check)
-from .adapters import LoraHost
+from . import rule
+from .adapters import EngineHost, LoraModel, _ptr, _stream
 from .mag_ratios import TABLES
 from .model import nearest_interp
 from .parallel import SP_OVERLAP
@@ -38,20 +39,16 @@ HUNYUAN_VIDEO = dict(patch_size=(1, 2, 2), in_channels=16, out_channels=16, hidd
                      text_states_dim=4096, text_states_dim_2=768, guidance_embed=True)
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
-
-
 def _f32(t, device):
     return t.detach().to(device=device, dtype=torch.float32).contiguous()
 
 
-class MMDiTEngine(LoraHost):
-    """One MM-DiT engine on one device.  PyTorch-ROCm owns the workspace and the stream, the library the rest."""
+class MMDiTEngine(EngineHost):
+    """One MM-DiT engine on one device.  PyTorch-ROCm owns the workspace and the stream, the library the rest.  The
+    workspace, set_weight / load_weights, buffer and destruction are adapters.EngineHost's; load_lora / set_adapters /
+    set_lora_call_scale / unload_lora / apply_lora / lora_info (adapters merged into the weights on the device,
+    mc_mmdit_lora_*; magcache_amd/lora.py reads the files) adapters.LoraHost's."""
+    _abi = "mc_mmdit_"
 
     def __init__(self, family, dim, num_heads, n_double, n_single, in_channels, out_channels, txt_dim, txt_len, vec_dim,
                  img_tokens, latent_grid=(0, 0, 0), refiner_depth=0, calibration=False, device="cuda:0", sp_rank=0,
@@ -78,19 +75,7 @@ class MMDiTEngine(LoraHost):
         self._bind(self.lib.mc_mmdit_workspace_bytes(self.h))
         self._rope_key = None
         self._controlnet = None
-        self._lora = {}           # adapter -> the scale set_adapters / load_lora gave it
-        self._lora_call = 1.0     # the per-call factor on top of it (the shims' joint_attention_kwargs["scale"])
-
-    def _bind(self, nbytes):
-        """a zeroed workspace of `nbytes` (at least the current plan), bound with mc_mmdit_set_workspace; the tensor it
-        replaces is let go after a device synchronise (forwards in flight may still use it)"""
-        workspace = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
-        off = (-workspace.data_ptr()) % 256
-        ws = workspace[off:off + nbytes]
-        ws.zero_()
-        torch.cuda.synchronize(self.device)
-        check(self.lib.mc_mmdit_set_workspace(self.h, _ptr(ws), nbytes))
-        self.workspace, self.ws = workspace, ws
+        self._lora_init()
 
     def geometry_bytes(self, img_tokens, latent_grid=(0, 0, 0), txt_len=None):
         """workspace bytes the geometry would need (mc_mmdit_geometry_bytes); the engine is not changed"""
@@ -108,8 +93,7 @@ class MMDiTEngine(LoraHost):
         need = self.ws.numel()
         for g in geometries:
             need = max(need, self.geometry_bytes(**g) if isinstance(g, dict) else self.geometry_bytes(*g))
-        if need > self.ws.numel():
-            self._bind(need)
+        self._grow(need)
         return need
 
     def set_geometry(self, img_tokens, latent_grid=(0, 0, 0), txt_len=None):
@@ -120,56 +104,12 @@ class MMDiTEngine(LoraHost):
         invalid: they point into the old plan."""
         txt_len = int(self.txt_len if txt_len is None else txt_len)
         grid = tuple(int(v) for v in latent_grid)
-        need = self.geometry_bytes(img_tokens, grid, txt_len)
-        if need > self.ws.numel():
-            self._bind(need)
+        self._grow(self.geometry_bytes(img_tokens, grid, txt_len))
         check(self.lib.mc_mmdit_set_geometry(self.h, int(img_tokens), grid[0], grid[1], grid[2], txt_len))
         self.img_tokens, self.txt_len, self.latent_grid = int(img_tokens), txt_len, grid
         self.tokens_per_rank = self.img_tokens // self.sp_size
         self._rope_key = None
         self._controlnet = None
-
-    def __del__(self):
-        try:
-            if getattr(self, "h", None):
-                torch.cuda.synchronize(self.device)
-                self.lib.mc_mmdit_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
-
-    def set_weight(self, name, tensor):
-        t = tensor.detach()
-        if t.dtype not in (torch.float32, torch.bfloat16):
-            t = t.float()
-        t = t.to(self.device).contiguous()
-        shape = (C.c_int64 * t.dim())(*t.shape)
-        try:
-            check(self.lib.mc_mmdit_set_weight(self.h, name.encode(), _ptr(t), MC_F32 if t.dtype == torch.float32 else MC_BF16,
-                                               shape, t.dim(), _stream()))
-        except _lib.MagCacheHipError as ex:
-            if "must be given as fp32" not in str(ex):
-                raise
-            t = t.float()
-            check(self.lib.mc_mmdit_set_weight(self.h, name.encode(), _ptr(t), MC_F32, shape, t.dim(), _stream()))
-        torch.cuda.current_stream().synchronize()
-
-    def load_weights(self, named_tensors):
-        items = named_tensors.items() if hasattr(named_tensors, "items") else named_tensors
-        for name, t in items:
-            self.set_weight(name, t)
-        buf = C.create_string_buffer(4096)
-        n = self.lib.mc_mmdit_weights_missing(self.h, buf, 4096)
-        if n:
-            raise KeyError(f"{n} weights missing, e.g.: {buf.value.decode().split()[:5]}")
-
-    # ---- LoRA adapters, merged into the weights on the device (mc_mmdit_lora_*; magcache_amd/lora.py reads the files):
-    # load_lora / set_adapters / set_lora_call_scale / unload_lora / apply_lora / lora_info are adapters.LoraHost's
-
-    def buffer(self, name, dtype=torch.uint8):
-        off, nb = C.c_size_t(), C.c_size_t()
-        check(self.lib.mc_mmdit_buffer_info(self.h, name.encode(), C.byref(off), C.byref(nb)))
-        return self.ws[off.value:off.value + nb.value].view(dtype)
 
     def residual(self, branch=None):
         """fp32 [img_tokens / sp_size, dim] view of the cached residual (reference previous_residual / residual_cache);
@@ -346,23 +286,11 @@ def _dispatch(self, *args, **kwargs):
     return type(self).forward(self, *args, **kwargs)
 
 
-class _LoraMethods:
-    """the adapter calls of MMDiTEngine on the model objects"""
+class _LoraMethods(LoraModel):
+    """the adapter calls of MMDiTEngine on the model objects (adapters.LoraModel); an MM-DiT adapter file's names carry a prefix"""
 
     def load_lora(self, sd, adapter="default", scale=1.0, strict=True, prefix="transformer."):
         return self.engine.load_lora(sd, adapter=adapter, scale=scale, strict=strict, prefix=prefix)
-
-    def set_adapters(self, names, scales=None):
-        return self.engine.set_adapters(names, scales)
-
-    def unload_lora(self, adapter=None):
-        return self.engine.unload_lora(adapter)
-
-    def apply_lora(self):
-        return self.engine.apply_lora()
-
-    def lora_info(self):
-        return self.engine.lora_info()
 
 
 def _lora_call_scale(model, kwargs):
@@ -376,7 +304,7 @@ def _lora_call_scale(model, kwargs):
 
 def _shim_set_geometry(model, img_tokens, latent_grid, txt_len, fresh):
     """dynamic_geometry: a call whose shapes differ from the engine's geometry switches the engine first and starts the
-    MagCache state of a new sample, as init_*_magcache would (`fresh`: the family's attributes).  Only between samples:
+    MagCache state of a new sample, as init_*_magcache would (`fresh`: the family's rule.fresh_state).  Only between samples:
     the reference cannot change shapes in the middle of one either (its cached residual has the old shape)."""
     cnt = int(getattr(model, "cnt", 0))
     if cnt != 0:
@@ -435,8 +363,7 @@ class FluxTransformer2DModelHIP(_LoraMethods):
             return
         li, lt = int(hidden_states.shape[1]), int(encoder_hidden_states.shape[1])
         if (li, lt) != (self.img_tokens, self.txt_len):
-            _shim_set_geometry(self, li, (0, 0, 0), lt, dict(accumulated_ratio=1, accumulated_err=0, accumulated_steps=0,
-                                                              previous_residual=None, norm_ratio=[], norm_std=[], cos_dis=[]))
+            _shim_set_geometry(self, li, (0, 0, 0), lt, rule.fresh_state("flux", None))
             self._ids_key = None
 
     def _run(self, hidden_states, encoder_hidden_states, pooled_projections, timestep, img_ids, txt_ids, guidance, mode):
@@ -512,30 +439,11 @@ def flux_magcache_forward(self, hidden_states, encoder_hidden_states=None, poole
     _lora_call_scale(self, joint_attention_kwargs)
     _flux_set_controlnet(self, controlnet_block_samples, controlnet_single_block_samples, controlnet_blocks_repeat,
                          hidden_states, encoder_hidden_states)
-    skip_forward = False
-    if self.cnt >= int(self.retention_ratio * self.num_steps + 0.5):                       # :333
-        cur_scale = self.mag_ratios[self.cnt]
-        self.accumulated_ratio = self.accumulated_ratio * cur_scale
-        self.accumulated_steps += 1
-        self.accumulated_err += np.abs(1 - self.accumulated_ratio)
-        if (self.accumulated_err <= self.magcache_thresh and self.accumulated_steps <= self.K
-                and np.round(self.cnt * ((28 - 1) / (self.num_steps - 1))).astype(int) != 11):   # :338
-            skip_forward = True
-        else:
-            self.accumulated_ratio = 1.0
-            self.accumulated_steps = 0
-            self.accumulated_err = 0
-    if skip_forward and self.previous_residual is None:
-        raise RuntimeError("MagCache asked to skip before any residual was cached")
+    _, skip_forward = rule.decide(self, "flux")      # :333-344: int(R n + 0.5), `<=`, step 11 of 28 never skipped
     out = self._run(hidden_states, encoder_hidden_states, pooled_projections, timestep, img_ids, txt_ids, guidance,
                     MC_MODE_SKIP if skip_forward else MC_MODE_FULL)
-    self.previous_residual = self.engine.residual()
-    self.cnt += 1
-    if self.cnt >= self.num_steps:                                                          # :434-438
-        self.cnt = 0
-        self.accumulated_ratio = 1.0
-        self.accumulated_steps = 0
-        self.accumulated_err = 0
+    rule.store_residual(self, "flux", 0, self.engine.residual())
+    rule.advance(self, "flux")                                                              # :434-438
     return _flux_output(out, return_dict)
 
 
@@ -548,27 +456,26 @@ def flux_magcache_calibration(self, hidden_states, encoder_hidden_states=None, p
     _flux_set_controlnet(self, controlnet_block_samples, controlnet_single_block_samples, controlnet_blocks_repeat,
                          hidden_states, encoder_hidden_states)
     out = self._run(hidden_states, encoder_hidden_states, pooled_projections, timestep, img_ids, txt_ids, guidance, MC_MODE_CALIB)
-    if self.cnt >= 1:                                                                       # :199-207
-        norm_ratio, norm_std, cos_dis = self.engine.calib_stats()
-        self.norm_ratio.append(round(norm_ratio, 5))
-        self.norm_std.append(round(norm_std, 5))
-        self.cos_dis.append(round(cos_dis, 5))
-        print(f"time: {self.cnt}, norm_ratio: {norm_ratio}, norm_std: {norm_std}, cos_dis: {cos_dis}")
-    self.previous_residual = self.engine.residual()
-    if self.cnt >= self.num_steps - 1:
+    stats = rule.calibrate(self, "flux", 0, self.engine.calib_stats, self.engine.residual)   # :199-207
+    _print_calibration(self, stats, self.cnt >= self.num_steps - 1)
+    if rule.advance(self, "flux", reset=False):                                             # :219-223
+        self.norm_ratio = []
+        self.norm_std = []
+        self.cos_dis = []
+    return _flux_output(out, return_dict)
+
+
+def _print_calibration(self, stats, last):
+    """what the FLUX and HunyuanVideo calibration forwards print: the call's statistics, the three lists at the end"""
+    if stats:
+        print(f"time: {self.cnt}, norm_ratio: {stats[0]}, norm_std: {stats[1]}, cos_dis: {stats[2]}")
+    if last:
         print("norm ratio")
         print(self.norm_ratio)
         print("norm std")
         print(self.norm_std)
         print("cos_dis")
         print(self.cos_dis)
-    self.cnt += 1
-    if self.cnt >= self.num_steps:                                                          # :219-223
-        self.cnt = 0
-        self.norm_ratio = []
-        self.norm_std = []
-        self.cos_dis = []
-    return _flux_output(out, return_dict)
 
 
 def init_flux_magcache(model, num_inference_steps=28, magcache_thresh=0.24, K=5, retention_ratio=0.1, mag_ratios=None,
@@ -576,9 +483,8 @@ def init_flux_magcache(model, num_inference_steps=28, magcache_thresh=0.24, K=5,
     """The reference's patch site (magcache_flux.py:445-470) on the model's CLASS."""
     cls = model.__class__
     cls.forward = flux_magcache_calibration if calibration else flux_magcache_forward
-    cls.cnt = 0
+    rule.init_state(cls, "flux", calibration)
     cls.num_steps = num_inference_steps
-    cls.norm_ratio, cls.norm_std, cls.cos_dis = [], [], []
     table = np.asarray(TABLES["flux_dev"] if mag_ratios is None else mag_ratios, dtype=np.float64)
     if len(table) != num_inference_steps:
         table = nearest_interp(table, num_inference_steps)
@@ -586,10 +492,6 @@ def init_flux_magcache(model, num_inference_steps=28, magcache_thresh=0.24, K=5,
     cls.K = K
     cls.magcache_thresh = magcache_thresh
     cls.retention_ratio = retention_ratio
-    cls.accumulated_ratio = 1
-    cls.accumulated_err = 0
-    cls.accumulated_steps = 0
-    cls.previous_residual = None
     model.engine.reset()
     return model
 
@@ -631,9 +533,7 @@ class HYVideoDiffusionTransformerHIP(_LoraMethods):
             return
         grid, lt = tuple(int(v) for v in x.shape[2:]), int(text_states.shape[1])
         if (grid, lt) != (self.latent_grid, self.txt_len):
-            _shim_set_geometry(self, grid[0] * (grid[1] // 2) * (grid[2] // 2), grid, lt,
-                               dict(accumulated_ratio=1, accumulated_err=0, accumulated_steps=0, residual_cache=None,
-                                    norm_ratio=[], norm_std=[], cos_dis=[]))
+            _shim_set_geometry(self, grid[0] * (grid[1] // 2) * (grid[2] // 2), grid, lt, rule.fresh_state("hunyuan", None))
             self.latent_grid = grid
 
     def _run(self, x, t, text_states, text_mask, text_states_2, freqs_cos, freqs_sin, guidance, mode):
@@ -671,30 +571,11 @@ def hunyuan_magcache_forward(self, x, t, text_states=None, text_mask=None, text_
                              freqs_sin=None, guidance=None, return_dict=True):
     """Drop-in for MagCache4HunyuanVideo/magcache_sample_video.py magcache_forward (:29-160)."""
     self._geometry(x, text_states)
-    skip_forward = False
-    if self.cnt >= int(self.retention_ratio * self.num_steps):                               # :91
-        cur_mag_ratio = self.mag_ratios[self.cnt]
-        self.accumulated_ratio = self.accumulated_ratio * cur_mag_ratio
-        cur_skip_err = np.abs(1 - self.accumulated_ratio)
-        self.accumulated_err += cur_skip_err
-        self.accumulated_steps += 1
-        if self.accumulated_err <= self.magcache_thresh and self.accumulated_steps <= self.K:   # :97
-            skip_forward = True
-        else:
-            self.accumulated_ratio = 1.0
-            self.accumulated_steps = 0
-            self.accumulated_err = 0
-    if skip_forward and self.residual_cache is None:
-        raise RuntimeError("MagCache asked to skip before any residual was cached")
+    _, skip_forward = rule.decide(self, "hunyuan")                                           # :91-102
     img = self._run(x, t, text_states, text_mask, text_states_2, freqs_cos, freqs_sin, guidance,
                     MC_MODE_SKIP if skip_forward else MC_MODE_FULL)
-    self.residual_cache = self.engine.residual()
-    self.cnt += 1
-    if self.cnt >= self.num_steps:                                                           # :149-153
-        self.cnt = 0
-        self.accumulated_ratio = 1.0
-        self.accumulated_steps = 0
-        self.accumulated_err = 0
+    rule.store_residual(self, "hunyuan", 0, self.engine.residual())
+    rule.advance(self, "hunyuan")                                                            # :149-153
     return _hy_output(img, return_dict)
 
 
@@ -703,21 +584,9 @@ def hunyuan_magcache_calibration(self, x, t, text_states=None, text_mask=None, t
     """Drop-in for magcache_sample_video.py magcache_calibration (:162-281)."""
     self._geometry(x, text_states)
     img = self._run(x, t, text_states, text_mask, text_states_2, freqs_cos, freqs_sin, guidance, MC_MODE_CALIB)
-    if self.cnt >= 1:
-        norm_ratio, norm_std, cos_dis = self.engine.calib_stats()
-        self.norm_ratio.append(round(norm_ratio, 5))
-        self.norm_std.append(round(norm_std, 5))
-        self.cos_dis.append(round(cos_dis, 5))
-        print(f"time: {self.cnt}, norm_ratio: {norm_ratio}, norm_std: {norm_std}, cos_dis: {cos_dis}")
-    self.residual_cache = self.engine.residual()
-    if self.cnt >= 49:                                                                       # :263 (hard-coded upstream)
-        print("norm ratio")
-        print(self.norm_ratio)
-        print("norm std")
-        print(self.norm_std)
-        print("cos_dis")
-        print(self.cos_dis)
-    self.cnt += 1
+    stats = rule.calibrate(self, "hunyuan", 0, self.engine.calib_stats, self.engine.residual)
+    _print_calibration(self, stats, self.cnt >= 49)                                          # :263 (hard-coded upstream)
+    self.cnt += 1                                                                            # never wraps, as upstream
     return _hy_output(img, return_dict)
 
 
@@ -725,12 +594,10 @@ def init_hunyuan_magcache(model, infer_steps=50, magcache_thresh=0.24, K=6, rete
                           mag_ratios=None, calibration=False):
     """The reference's patch site (magcache_sample_video.py:300-328) on the model's CLASS."""
     cls = model.__class__
-    cls.cnt = 0
+    rule.init_state(cls, "hunyuan", calibration)
     cls.num_steps = infer_steps
     cls.magcache_thresh = magcache_thresh
     cls.K = K
-    cls.norm_ratio, cls.norm_std, cls.cos_dis = [], [], []
-    cls.residual_cache = None
     if mag_ratios is None:
         mag_ratios = TABLES["hunyuan_720p" if video_height == 720 else "hunyuan_540p"]
     table = np.asarray(mag_ratios, dtype=np.float64)
@@ -739,9 +606,6 @@ def init_hunyuan_magcache(model, infer_steps=50, magcache_thresh=0.24, K=6, rete
     cls.mag_ratios = table
     cls.retention_ratio = retention_ratio
     cls.forward = hunyuan_magcache_calibration if calibration else hunyuan_magcache_forward
-    cls.accumulated_ratio = 1
-    cls.accumulated_err = 0
-    cls.accumulated_steps = 0
     model.engine.reset()
     return model
 
@@ -824,9 +688,7 @@ class QwenImageTransformer2DModelHIP(_LoraMethods):
         li = int(hidden_states.shape[1])
         n = int(txt_seq_lens[0]) if txt_seq_lens is not None else int(encoder_hidden_states.shape[1])
         if li != self.img_tokens or n > self.txt_len:
-            _shim_set_geometry(self, li, (0, 0, 0), max(n, self.txt_len),
-                               dict(accumulated_err=[0.0, 0.0], accumulated_steps=[0, 0], accumulated_ratio=[1.0, 1.0],
-                                    residual_cache=[None, None], norm_ratio=[], norm_std=[], cos_dis=[]))
+            _shim_set_geometry(self, li, (0, 0, 0), max(n, self.txt_len), rule.fresh_state("qwen", None))
             self._shapes_key = None
 
     def _run(self, hidden_states, encoder_hidden_states, timestep, img_shapes, txt_seq_lens, mode, branch):
@@ -866,28 +728,11 @@ def qwen_magcache_forward(self, hidden_states, encoder_hidden_states=None, encod
     (branch cnt % 2), strict `<`, and the accumulators are NOT reset when cnt wraps."""
     _lora_call_scale(self, attention_kwargs)
     self._geometry(hidden_states, encoder_hidden_states, txt_seq_lens)
-    cnt = int(self.cnt)
-    b = cnt % 2
-    skip_forward = False
-    if cnt >= int(self.num_steps * self.retention_ratio):                                    # :205
-        cur_mag_ratio = self.mag_ratios[cnt]
-        self.accumulated_ratio[b] *= cur_mag_ratio
-        self.accumulated_steps[b] += 1
-        self.accumulated_err[b] += np.abs(1 - self.accumulated_ratio[b])
-        if self.accumulated_err[b] < self.magcache_thresh and self.accumulated_steps[b] <= self.K:   # :213
-            skip_forward = True
-        else:
-            self.accumulated_err[b] = 0.0
-            self.accumulated_steps[b] = 0
-            self.accumulated_ratio[b] = 1.0
-    if skip_forward and self.residual_cache[b] is None:
-        raise RuntimeError("MagCache asked to skip before any residual was cached")
+    b, skip_forward = rule.decide(self, "qwen")                                              # :205-219
     out = self._run(hidden_states, encoder_hidden_states, timestep, img_shapes, txt_seq_lens,
                     MC_MODE_SKIP if skip_forward else MC_MODE_FULL, b)
-    self.residual_cache[b] = self.engine.residual(b)                                          # :242
-    self.cnt = cnt + 1
-    if self.cnt >= self.num_steps:
-        self.cnt = 0
+    rule.store_residual(self, "qwen", b, self.engine.residual(b))                             # :242
+    rule.advance(self, "qwen")
     return _flux_output(out, return_dict)
 
 
@@ -901,16 +746,10 @@ def qwen_magcache_calibration(self, hidden_states, encoder_hidden_states=None, e
     cnt = int(self.cnt)
     b = cnt % 2
     out = self._run(hidden_states, encoder_hidden_states, timestep, img_shapes, txt_seq_lens, MC_MODE_CALIB, b)
-    if cnt >= 2:                                                                              # :140
-        norm_ratio, norm_std, cos_dis = self.engine.calib_stats()
-        self.norm_ratio.append(round(norm_ratio, 5))
-        self.norm_std.append(round(norm_std, 5))
-        self.cos_dis.append(round(cos_dis, 5))
-        print(f"Step {cnt}: norm_ratio={norm_ratio:.5f}, norm_std={norm_std:.5f}, cos_dis={cos_dis:.5f}")
-    self.residual_cache[b] = self.engine.residual(b)
-    self.cnt = cnt + 1
-    if self.cnt >= self.num_steps:                                                            # :156-161
-        self.cnt = 0
+    stats = rule.calibrate(self, "qwen", b, self.engine.calib_stats, lambda: self.engine.residual(b))   # :140
+    if stats:
+        print(f"Step {cnt}: norm_ratio={stats[0]:.5f}, norm_std={stats[1]:.5f}, cos_dis={stats[2]:.5f}")
+    if rule.advance(self, "qwen"):                                                            # :156-161
         print("\nCalibration Results:")
         print("norm_ratio:", self.norm_ratio)
         print("norm_std:", self.norm_std)
@@ -923,21 +762,16 @@ def init_qwen_magcache(model, sample_steps=50, magcache_thresh=0.06, K=2, retent
     """The reference's patch site on the model's CLASS: init_magcache (:63-83) / init_magcache_calibration (:85-92).
     `mag_ratios` is the reference's list WITHOUT the two leading 1.0 pads (default: the Qwen-Image or -Edit table)."""
     cls = model.__class__
-    cls.cnt = 0
+    rule.init_state(cls, "qwen", calibration)
     cls.num_steps = sample_steps * 2
-    cls.residual_cache = [None, None]
     if calibration:
         cls.forward = qwen_magcache_calibration
-        cls.norm_ratio, cls.norm_std, cls.cos_dis = [], [], []
     else:
         cls.forward = qwen_magcache_forward
         cls.split_step = None
         cls.mode = "t2v"
         cls.magcache_thresh = magcache_thresh
         cls.K = K
-        cls.accumulated_err = [0.0, 0.0]
-        cls.accumulated_steps = [0, 0]
-        cls.accumulated_ratio = [1.0, 1.0]
         cls.retention_ratio = retention_ratio
         if mag_ratios is None:
             mag_ratios = list(TABLES["qwen_image_edit" if edit else "qwen_image"][2:])

@@ -20,6 +20,8 @@ import os
 import numpy as np
 import torch
 
+from . import rule
+from .adapters import LoraModel
 from .engine import MC_MODE_CALIB, MC_MODE_FULL, MC_MODE_SKIP, Engine
 from .mag_ratios import TABLES
 
@@ -104,7 +106,7 @@ def _same_tensor(key, t):
     return same
 
 
-class WanModelHIP:
+class WanModelHIP(LoraModel):
     """Wan2.1 DiT (T2V, or I2V when cfg has model_type='i2v' / clip_dim) whose forward runs on the HIP engine.
     One latent grid per instance, unless dynamic_geometry=True: then every call may bring its own (Engine.set_geometry)."""
 
@@ -178,10 +180,8 @@ class WanModelHIP:
         if follows:
             return
         type(self)._sample_grid = grid
-        fresh = dict(cnt=0, accumulated_err=[0.0, 0.0], accumulated_steps=[0, 0], accumulated_ratio=[1.0, 1.0],
-                     residual_cache=[None, None], norm_ratio=[], norm_std=[], cos_dis=[])
-        for k, v in fresh.items():            # where the state lives: on the instance once a call has advanced it, else the class
-            if k in self.__dict__:
+        for k, v in rule.fresh_state("wan21", None).items():
+            if k in self.__dict__:            # where the state lives: on the instance once a call has advanced it, else the class
                 setattr(self, k, v)
             elif hasattr(type(self), k):
                 setattr(type(self), k, v)
@@ -283,7 +283,8 @@ class WanModelHIP:
             self._tok_next = (self._tok_next + 1) % len(self._tok_ring)
         return [out.float()]
 
-    # ---- LoRA adapters (Engine.load_lora & co.): a merge changes what the cached contexts were computed from, so the
+    # ---- LoRA adapters (adapters.LoraModel over Engine.load_lora & co.; for Wan2.2 each expert is a WanModelHIP and takes its
+    # own adapters): a merge changes what the cached contexts were computed from, so the
     # identity keys go with it and the next call uploads the text, CLIP and VACE contexts again
     def _lora_call(self, name, *args, **kw):
         try:
@@ -292,25 +293,8 @@ class WanModelHIP:
             self._ctx_keys, self._ctx_lru = [None, None], 0
             self._clip_key = self._vace_key = None
 
-    def load_lora(self, sd, adapter="default", scale=1.0, strict=True):
-        """Load a Wan adapter state dict (lora.parse_wan_lora_state_dict) as `adapter` at `scale` and merge it; returns the
-        names skipped under strict=False.  For Wan2.2 each expert is a WanModelHIP and takes its own adapters."""
-        return self._lora_call("load_lora", sd, adapter=adapter, scale=scale, strict=strict)
-
-    def set_adapters(self, names, scales=None):
-        return self._lora_call("set_adapters", names, scales)
-
     def set_lora_call_scale(self, scale):
         return self._lora_call("set_lora_call_scale", scale)
-
-    def unload_lora(self, adapter=None):
-        return self._lora_call("unload_lora", adapter)
-
-    def apply_lora(self):
-        return self._lora_call("apply_lora")
-
-    def lora_info(self):
-        return self.engine.lora_info()
 
     def pair_begin(self):
         """The sampler's declaration that the next two calls are the cond / uncond evaluations of ONE step -- same latent,
@@ -371,73 +355,38 @@ def plain_forward(self, x, t, context, seq_len, clip_fea=None, y=None):
 WanModelHIP.forward = plain_forward
 
 
-def _advance(self):
-    # :306-311 -- the residual cache is NOT cleared, only the accumulators
-    self.cnt += 1
-    if self.cnt >= self.num_steps:
-        self.cnt = 0
-        self.accumulated_ratio = [1.0, 1.0]
-        self.accumulated_err = [0.0, 0.0]
-        self.accumulated_steps = [0, 0]
-
-
-def _decide(self):
-    """The MagCache decision (:277-292; the VACE twin :521-536 is the same code): host scalars only.  Returns
-    (state slot p, skip_forward)."""
-    p = self.cnt % 2  # cond calls are even, uncond odd
-    skip_forward = False
-    if self.cnt >= int(self.num_steps * self.retention_ratio):
-        self.accumulated_ratio[p] = self.accumulated_ratio[p] * self.mag_ratios[self.cnt]
-        self.accumulated_steps[p] += 1
-        self.accumulated_err[p] += np.abs(1 - self.accumulated_ratio[p])
-        if self.accumulated_err[p] < self.magcache_thresh and self.accumulated_steps[p] <= self.K:
-            skip_forward = True
-        else:
-            self.accumulated_err[p] = 0
-            self.accumulated_steps[p] = 0
-            self.accumulated_ratio[p] = 1.0
-    if skip_forward and self.residual_cache[p] is None:
-        raise RuntimeError("MagCache asked to skip before any residual was cached (retention_ratio too small?)")
-    return p, skip_forward
-
-
 def _cached_forward(self, x, t, context, **run_kw):
-    p, skip_forward = _decide(self)
+    """The MagCache rule (:277-292, :306-311; the VACE twin :521-536 is the same code) around one engine forward: host
+    scalars only."""
+    p, skip_forward = rule.decide(self, "wan21")
     out = self._run(x, t, context, p, MC_MODE_SKIP if skip_forward else MC_MODE_FULL, **run_kw)
-    self.residual_cache[p] = self.engine.residual(p)  # a view of the engine's HBM slot (:301)
-    _advance(self)
+    rule.store_residual(self, "wan21", p, self.engine.residual(p))  # a view of the engine's HBM slot (:301)
+    rule.advance(self, "wan21")
     return out
 
 
 def _calibration_forward(self, x, t, context, **run_kw):
     """:165-193 (VACE twin :405-437): never skips, records norm_ratio / norm_std / cos_dis against the previous
     residual of the same branch and dumps the three JSON files when the video is finished."""
-    p = self.cnt % 2
+    cnt = self.cnt
+    p = cnt % 2
     out = self._run(x, t, context, p, MC_MODE_CALIB, **run_kw)
-    if self.cnt >= 2:
-        norm_ratio, norm_std, cos_dis = self.engine.calib_stats(p)
-        self.norm_ratio.append(round(norm_ratio, 5))
-        self.norm_std.append(round(norm_std, 5))
-        self.cos_dis.append(round(cos_dis, 5))
-        print(f"time: {self.cnt}, norm_ratio: {norm_ratio}, norm_std: {norm_std}, cos_dis: {cos_dis}")
-    self.residual_cache[p] = self.engine.residual(p)
-    self.cnt += 1
-    if self.cnt >= self.num_steps:
-        self.cnt = 0
-        self.accumulated_ratio = [1.0, 1.0]
-        self.accumulated_err = [0.0, 0.0]
-        self.accumulated_steps = [0, 0]
-        print("norm ratio")
-        print(self.norm_ratio)
-        print("norm std")
-        print(self.norm_std)
-        print("cos_dis")
-        print(self.cos_dis)
-        for fn, v in (("wan2_1_mag_ratio", self.norm_ratio), ("wan2_1_mag_std", self.norm_std),
-                      ("wan2_1_cos_dis", self.cos_dis)):
-            with open(fn + ".json", "w") as f:
-                json.dump(v, f)
+    stats = rule.calibrate(self, "wan21", p, lambda: self.engine.calib_stats(p), lambda: self.engine.residual(p))
+    if stats:
+        print(f"time: {cnt}, norm_ratio: {stats[0]}, norm_std: {stats[1]}, cos_dis: {stats[2]}")
+    if rule.advance(self, "wan21"):
+        dump_calibration(self.norm_ratio, self.norm_std, self.cos_dis)
     return out
+
+
+def dump_calibration(norm_ratio, norm_std, cos_dis):
+    """the end of a calibration video (:181-193; the Wan2.2 script keeps the wan2_1_* file names, :205-207)"""
+    for title, name, v in (("norm ratio", "wan2_1_mag_ratio", norm_ratio), ("norm std", "wan2_1_mag_std", norm_std),
+                           ("cos_dis", "wan2_1_cos_dis", cos_dis)):
+        print(title)
+        print(v)
+        with open(name + ".json", "w") as f:
+            json.dump(v, f)
 
 
 def magcache_forward(self, x, t, context, seq_len, clip_fea=None, y=None):
@@ -490,7 +439,7 @@ def call_branch(model, step, branch, x, t, context, seq_len, **kw):
         model.cnt = 2 * step + branch
     out = model(x, t=t, context=context, seq_len=seq_len, **kw)
     if has_state and branch == 0:
-        _advance(model)                    # the uncond call made by the other half of the node
+        rule.advance(model, "wan21")       # the uncond call made by the other half of the node
     return out
 
 
@@ -499,15 +448,11 @@ def init_magcache(model, sample_steps, magcache_thresh=0.12, magcache_K=2, reten
     """What the reference does at its patch site (:896-919), on the model's CLASS."""
     cls = model.__class__
     cls.forward = magcache_forward
-    cls.cnt = 0
+    rule.init_state(cls, "wan21")
     cls.num_steps = sample_steps * 2
     cls.magcache_thresh = magcache_thresh
     cls.K = magcache_K
-    cls.accumulated_err = [0.0, 0.0]
-    cls.accumulated_steps = [0, 0]
-    cls.accumulated_ratio = [1.0, 1.0]
     cls.retention_ratio = retention_ratio
-    cls.residual_cache = [None, None]
     table = select_table(ckpt_dir) if mag_ratios is None else np.asarray(mag_ratios, dtype=np.float64)
     cls.mag_ratios = resample_cfg_table(table, sample_steps)
     model.engine.reset()
@@ -518,11 +463,8 @@ def init_magcache_calibration(model, sample_steps):
     """The calibration patch site (:921-928)."""
     cls = model.__class__
     cls.forward = magcache_calibration
-    cls.cnt = 0
+    rule.init_state(cls, "wan21", calibration=True)
     cls.num_steps = sample_steps * 2
-    cls.norm_ratio, cls.norm_std, cls.cos_dis = [], [], []
-    cls.residual_cache = [None, None]
-    cls.accumulated_err, cls.accumulated_steps, cls.accumulated_ratio = [0.0, 0.0], [0, 0], [1.0, 1.0]
     model.engine.reset()
     return model
 

@@ -16,14 +16,13 @@ What differs from Wan2.1 on the hot path:
     tokens carry the same t, which makes it the Wan2.1 computation -- what the engine runs.  (TI2V-5B gives
     the first-frame tokens their own t: not implemented.)
 """
-import json
-
 import numpy as np
 import torch
 
+from . import rule
 from .engine import MC_MODE_CALIB, MC_MODE_FULL, MC_MODE_SKIP, WAN_T2V_14B
 from .mag_ratios import TABLES
-from .model import WanModelHIP, nearest_interp
+from .model import WanModelHIP, dump_calibration, nearest_interp
 
 # upstream wan/configs/wan_t2v_A14B.py / wan_i2v_A14B.py [UPSTREAM, not in the reference tree]
 WAN22_T2V_A14B = dict(WAN_T2V_14B)
@@ -50,19 +49,7 @@ def high_noise_steps(shift, sample_steps, boundary, num_train_timesteps=1000):
     return int((ts >= num_train_timesteps * boundary).sum())
 
 
-def _use_magcache(self):
-    """retention gate, :294-303"""
-    if self.split_step is not None:
-        if self.mode == "i2v":
-            return not (self.cnt < int(self.split_step + (self.num_steps - self.split_step) * self.retention_ratio))
-        return not (self.cnt < int(self.split_step * self.retention_ratio) or
-                    (self.cnt <= ((self.num_steps - self.split_step) * self.retention_ratio + self.split_step) and
-                     self.cnt >= self.split_step))
-    return not (self.cnt < int(self.num_steps * self.retention_ratio))
-
-
-def magcache_forward(self, x, t, context, seq_len, clip_fea=None, y=None):
-    """Drop-in for MagCache4Wan2.2/magcache_generate.py magcache_forward (:198-338)."""
+def _inputs(self, x, context, seq_len, y):
     if self.model_type == "i2v":
         assert y is not None
     if y is not None:
@@ -70,34 +57,26 @@ def magcache_forward(self, x, t, context, seq_len, clip_fea=None, y=None):
     # Wan2.2's i2v takes y only (no CLIP branch): the shared input checks run in t2v mode on the
     # concatenated latent
     type(self)._check_inputs(_T2VChecks(self), x, context, seq_len, None, None)
-    cls = type(self)
-    p = int(self.cnt) % 2
-    skip_forward = False
-    if _use_magcache(self):
-        self.accumulated_ratio[p] = self.accumulated_ratio[p] * self.mag_ratios[int(self.cnt)]
-        self.accumulated_steps[p] += 1
-        self.accumulated_err[p] += np.abs(1 - self.accumulated_ratio[p])
-        if self.accumulated_err[p] < self.magcache_thresh and self.accumulated_steps[p] <= self.K:
-            skip_forward = True
-        else:
-            self.accumulated_err[p] = 0
-            self.accumulated_steps[p] = 0
-            self.accumulated_ratio[p] = 1.0
+    return x
+
+
+def _hand_over(self, p):
+    """the class-shared cache: a residual the other expert cached goes to this expert's engine (mc_import_residual)"""
+    cached = type(self).residual_cache[p]
+    if cached is not None and cached.data_ptr() != self.engine.residual(p).data_ptr():
+        self.engine.import_residual(p, cached)
+
+
+def magcache_forward(self, x, t, context, seq_len, clip_fea=None, y=None):
+    """Drop-in for MagCache4Wan2.2/magcache_generate.py magcache_forward (:198-338): the rule with the split-step
+    retention gates (:294-303) on the state both experts share."""
+    x = _inputs(self, x, context, seq_len, y)
+    p, skip_forward = rule.decide(self, "wan22")
     if skip_forward:
-        cached = self.residual_cache[p]
-        if cached is None:
-            raise RuntimeError("MagCache asked to skip before any residual was cached")
-        mine = self.engine.residual(p)
-        if cached.data_ptr() != mine.data_ptr():       # cached by the other expert (class-shared cache)
-            self.engine.import_residual(p, cached)
+        _hand_over(self, p)
     out = self._run(x, t, context, p, MC_MODE_SKIP if skip_forward else MC_MODE_FULL)
-    cls.residual_cache[p] = self.engine.residual(p)
-    cls.cnt = int(self.cnt) + 1
-    if cls.cnt >= self.num_steps:                        # :333-337
-        cls.cnt = 0
-        cls.accumulated_ratio = [1.0, 1.0]
-        cls.accumulated_err = [0.0, 0.0]
-        cls.accumulated_steps = [0, 0]
+    rule.store_residual(self, "wan22", p, self.engine.residual(p))
+    rule.advance(self, "wan22")                          # :333-337
     return out
 
 
@@ -107,34 +86,18 @@ def magcache_calibration(self, x, t, context, seq_len, clip_fea=None, y=None):
     the first two calls after the expert switch, is the residual the OTHER expert produced (the cache is a class
     attribute): it is handed to this expert's engine before the forward.  The three JSON files keep the reference's
     names (it writes wan2_1_* here too, :205-207)."""
-    if self.model_type == "i2v":
-        assert y is not None
-    if y is not None:
-        x = [torch.cat([u, v], dim=0) for u, v in zip(x, y)]
-    type(self)._check_inputs(_T2VChecks(self), x, context, seq_len, None, None)
+    x = _inputs(self, x, context, seq_len, y)
     cls = type(self)
     cnt = int(cls.cnt)
     p = cnt % 2
-    cached = cls.residual_cache[p]
-    if cnt >= 2 and cached is not None and cached.data_ptr() != self.engine.residual(p).data_ptr():
-        self.engine.import_residual(p, cached)
-    out = self._run(x, t, context, p, MC_MODE_CALIB)
     if cnt >= 2:
-        norm_ratio, norm_std, cos_dis = self.engine.calib_stats(p)
-        cls.norm_ratio.append(round(norm_ratio, 5))
-        cls.norm_std.append(round(norm_std, 5))
-        cls.cos_dis.append(round(cos_dis, 5))
-        print(f"time: {cnt}, norm_ratio: {norm_ratio}, norm_std: {norm_std}, cos_dis: {cos_dis}")
-    cls.residual_cache[p] = self.engine.residual(p)
-    cls.cnt = cnt + 1
-    if cls.cnt >= cls.num_steps:
-        cls.cnt = 0
-        for title, name, v in (("norm ratio", "wan2_1_mag_ratio", cls.norm_ratio), ("norm std", "wan2_1_mag_std", cls.norm_std),
-                               ("cos_dis", "wan2_1_cos_dis", cls.cos_dis)):
-            print(title)
-            print(v)
-            with open(name + ".json", "w") as f:
-                json.dump(v, f)
+        _hand_over(self, p)
+    out = self._run(x, t, context, p, MC_MODE_CALIB)
+    stats = rule.calibrate(self, "wan22", p, lambda: self.engine.calib_stats(p), lambda: self.engine.residual(p))
+    if stats:
+        print(f"time: {cnt}, norm_ratio: {stats[0]}, norm_std: {stats[1]}, cos_dis: {stats[2]}")
+    if rule.advance(self, "wan22", reset=False):
+        dump_calibration(cls.norm_ratio, cls.norm_std, cls.cos_dis)
     return out
 
 
@@ -142,10 +105,8 @@ def init_magcache_calibration(model, sample_steps):
     """:365-373.  `model` is either expert (created with make_experts(..., calibration=True))."""
     cls = model.__class__
     cls.forward = magcache_calibration
-    cls.cnt = 0
+    rule.init_state(cls, "wan22", calibration=True)
     cls.num_steps = sample_steps * 2
-    cls.norm_ratio, cls.norm_std, cls.cos_dis = [], [], []
-    cls.residual_cache = [None, None]
     return model
 
 
@@ -167,17 +128,13 @@ def init_magcache(model, mag_ratios, sample_steps, magcache_thresh=0.12, magcach
     kept as None here.)"""
     cls = model.__class__
     cls.forward = magcache_forward
-    cls.cnt = 0
+    rule.init_state(cls, "wan22")
     cls.num_steps = sample_steps * 2
     cls.split_step = None if split_steps is None else split_steps * 2
     cls.mode = mode
     cls.magcache_thresh = magcache_thresh
     cls.K = magcache_K
-    cls.accumulated_err = [0.0, 0.0]
-    cls.accumulated_steps = [0, 0]
-    cls.accumulated_ratio = [1.0, 1.0]
     cls.retention_ratio = retention_ratio
-    cls.residual_cache = [None, None]
     table = np.array([1.0] * 2 + list(mag_ratios), dtype=np.float64)          # :356, pad of the first step
     if len(table) != sample_steps * 2:
         con, ucon = nearest_interp(table[0::2], sample_steps), nearest_interp(table[1::2], sample_steps)
@@ -213,12 +170,7 @@ def call_branch(model, step, branch, x, t, context, seq_len, **kw):
         cls.cnt = 2 * step + branch
     out = model(x, t=t, context=context, seq_len=seq_len, **kw)
     if has_state and branch == 0:
-        cls.cnt = int(cls.cnt) + 1
-        if cls.cnt >= cls.num_steps:
-            cls.cnt = 0
-            cls.accumulated_ratio = [1.0, 1.0]
-            cls.accumulated_err = [0.0, 0.0]
-            cls.accumulated_steps = [0, 0]
+        rule.advance(model, "wan22")
     return out
 
 
