@@ -540,6 +540,25 @@ mc_status mc_op_residual_sub(const float* x_dev, long ldx, const void* x0_bf16_d
  * that is not 16-byte aligned. */
 mc_status mc_op_add_rows(float* x_dev, long ldx, const void* s_dev, mc_dtype s_dtype, float* r_dev, long ldr,
                          const void* x0_bf16_dev, long ldx0, int rows, int D, mc_stream stream);
+/* IP-Adapter cross-attention of the FLUX double block (diffusers FluxIPAdapterJointAttnProcessor2_0), one launch:
+ *   out[m, head] = sum_j scale_j * softmax(q_n[m, head] K_j[head]^T / sqrt(128)) V_j[head]     m < rows, bf16 [rows, heads * 128]
+ * q_bf16_dev: the RAW q rows (before the per-head norm), normalised per head of 128 by the kernel itself exactly as the
+ * engine's head norm does without a RoPE table, q_n = bf16(bf16(q * rstd) * wq) with wq_dev [128] fp32; adapter j (1 to
+ * MC_IP_MAX_ADAPTERS of them) is rows of [K | V] bf16 with leading dimension ld >= 2 * heads * 128, the first `valid`
+ * (1..MC_IP_MAX_KEYS) being its keys -- rows behind them are never read.  Softmax per adapter in fp32, P rounded to bf16 for
+ * P V on the matrix cores, the sum over the adapters in fp32, one rounding to bf16.  An adapter with scale 0 is skipped.
+ * MC_EINVAL, and nothing launched, for an adapter or key count out of range, rows < 1, a pointer that is not 16-byte aligned
+ * or a leading dimension that is too short or no multiple of 8. */
+#define MC_IP_MAX_ADAPTERS 4
+#define MC_IP_MAX_KEYS 256
+typedef struct mc_ip_keys {
+  const void* kv;
+  long ld;
+  int valid;
+  float scale;
+} mc_ip_keys;
+mc_status mc_op_ip_attention(const void* q_bf16_dev, long ldq, const float* wq_dev, float eps, const mc_ip_keys* adapters,
+                             int n_adapters, void* out_bf16_dev, long ldo, int rows, int heads, mc_stream stream);
 /* One launch: per-token ratios + the cross-block reduction by the last block to arrive.  partial_dev: 4*n_blocks + 1
  * doubles of scratch whose LAST 8 bytes (the arrival ticket) must be zero before the first call -- the kernel rearms it;
  * sums_dev: 4 doubles (sum rho, sum rho^2, sum 1-cos, count); stats_dev: 3 floats or NULL */

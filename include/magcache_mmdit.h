@@ -179,6 +179,46 @@ mc_status mc_mmdit_set_controlnet(mc_mmdit* e, const void* const* double_samples
  * refuses the pair (n_samples > n_blocks, or an index past the list).  blocks_repeat applies to double blocks only. */
 int mc_mmdit_controlnet_index(int n_blocks, int n_samples, int block, int blocks_repeat);
 
+/* FLUX IP-Adapters: joint_attention_kwargs["ip_adapter_image_embeds"] of the reference forwards, which run
+ * encoder_hid_proj on it and hand ip_hidden_states to every block (MagCache4FLUX/magcache_flux.py; the block side is
+ * diffusers' FluxIPAdapterJointAttnProcessor2_0 and MultiIPAdapterImageProjection).  Per double block, on the image rows:
+ *   ip_out = sum_j scale_j[block] * softmax(q_n K_j^T / sqrt(128)) V_j,    hidden_states += ip_out
+ * with q_n the image stream's q after norm_q and before RoPE, K_j | V_j = to_k_ip_j | to_v_ip_j of adapter j's projected
+ * image embeds (bias, heads of 128, no RoPE, no mask, no output projection, no gate); the add comes after the block's MLP
+ * and before its ControlNet sample.  The single blocks have no IP processor.  Up to MC_IP_MAX_ADAPTERS adapters of up to
+ * MC_IP_MAX_KEYS keys (images x tokens per image) each.
+ *   mc_mmdit_ip_adapter_add        registers adapter j = *index (0, 1, ..) under the names diffusers gives its weights after
+ *                        load_ip_adapter, to be set with mc_mmdit_set_weight and reported by mc_mmdit_weights_missing:
+ *                          encoder_hid_proj.image_projection_layers.{j}.image_embeds.{weight,bias}  [tokens * cross_dim, embed_dim]
+ *                          encoder_hid_proj.image_projection_layers.{j}.norm.{weight,bias}          [cross_dim] fp32
+ *                          transformer_blocks.{i}.attn.processor.to_k_ip.{j}.{weight,bias}          [dim, cross_dim]
+ *                          transformer_blocks.{i}.attn.processor.to_v_ip.{j}.{weight,bias}          [dim, cross_dim]
+ *                        cross_dim: 256 x (1, 2, 4, 5, 6, 8, 12, 16 or 20); embed_dim a multiple of 8.  Scales start at 1.
+ *   mc_mmdit_ip_adapter_set_image  the image prompt of `adapter` in slot 0 or 1: embeds_dev [n_images, embed_dim] fp32 (16-byte
+ *                        aligned) -> projection, affine LayerNorm (eps 1e-5), then K | V of EVERY double block into the slot's
+ *                        cache [n_double][rows][2 dim] bf16.  Once per image prompt, never per forward; two slots so that the
+ *                        positive and the negative image of a true-CFG pipeline alternate without recomputing.  n_images = 0
+ *                        empties the adapter's slot.  MC_EINVAL for more than MC_IP_MAX_KEYS keys, MC_ESTATE while a weight
+ *                        of the adapter is not set.  May allocate (a cache that grows) and then synchronises the device.
+ *   mc_mmdit_ip_adapter_scale      n = 1 (every block) or n_double values; launch arguments of the following forwards, free
+ *   mc_mmdit_ip_adapter_select     the slot the following forwards read; -1 = none (the state after _add)
+ *   mc_mmdit_ip_adapter_clear      removes every adapter, its weights, names and caches; selection -1
+ * All of them: MC_FAMILY_FLUX only, between forwards only (MC_ESTATE between mc_mmdit_begin and mc_mmdit_end).  A block in
+ * which no adapter counts (nothing selected, no image in the slot, scale 0) gets no launch and no bit of any output
+ * changes; otherwise one attention launch in front of the image range's head norm and one add per double block.  On the
+ * last block of a model without single blocks the residual is taken after the add, as with a ControlNet sample.
+ * MC_MODE_SKIP runs no block: the cached residual already holds the contribution.  Sequence parallel: keys are replicated,
+ * every rank makes the same calls and attends its own rows; nothing is gathered.
+ * mc_mmdit_set_geometry and mc_mmdit_set_workspace keep adapters, images, scales and selection: they depend on no token
+ * geometry (keys come from the image prompt) and live outside the workspace -- unlike the ControlNet lists, which point at
+ * caller tensors of the old [img_tokens, dim] and are cleared. */
+mc_status mc_mmdit_ip_adapter_add(mc_mmdit* e, int embed_dim, int cross_dim, int tokens_per_image, int* index);
+mc_status mc_mmdit_ip_adapter_set_image(mc_mmdit* e, int adapter, int slot, const float* embeds_dev, int n_images,
+                                        mc_stream stream);
+mc_status mc_mmdit_ip_adapter_scale(mc_mmdit* e, int adapter, const float* scales, int n);
+mc_status mc_mmdit_ip_adapter_select(mc_mmdit* e, int slot);
+mc_status mc_mmdit_ip_adapter_clear(mc_mmdit* e);
+
 /* One transformer evaluation (the body of the reference's magcache_forward).
  *   img_dev    FLUX: packed latent tokens [img_tokens, in_channels]; HunyuanVideo: latent [16, F, H, W]   (fp32)
  *   timestep   the value the embedding sees: FLUX timestep*1000 (:303), HunyuanVideo t (:54); guidance likewise

@@ -127,6 +127,7 @@ SIGNATURES = {
     "mc_op_rmsnorm_rows_bf16": (_i, [_vp, _l, _vp, _f, _vp, _l, _i, _i, _i, _vp]),
     "mc_op_lincomb": (_i, [_vp, _vp, _i, _vp, _sz, _vp]),
     "mc_op_add_rows": (_i, [_vp, _l, _vp, _i, _vp, _l, _vp, _l, _i, _i, _vp]),
+    "mc_op_ip_attention": (_i, [_vp, _l, _vp, _f, _vp, _i, _vp, _l, _i, _i, _vp]),
     "mc_op_rope_table": (_i, [_i, _i, _i, _i, _i, _vp]),
     "mc_op_rope_axes": (_i, [_i, _i, _i, _vp, C.POINTER(_sz)]),
     "mc_op_rope_expand": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
@@ -159,6 +160,11 @@ SIGNATURES = {
     "mc_mmdit_set_rope": (_i, [_vp, _vp, _vp, _i, _vp]),
     "mc_mmdit_set_controlnet": (_i, [_vp, _vp, _i, _vp, _i, _i, _i]),
     "mc_mmdit_controlnet_index": (_i, [_i, _i, _i, _i]),
+    "mc_mmdit_ip_adapter_add": (_i, [_vp, _i, _i, _i, C.POINTER(_i)]),
+    "mc_mmdit_ip_adapter_set_image": (_i, [_vp, _i, _i, _vp, _i, _vp]),
+    "mc_mmdit_ip_adapter_scale": (_i, [_vp, _i, C.POINTER(_f), _i]),
+    "mc_mmdit_ip_adapter_select": (_i, [_vp, _i]),
+    "mc_mmdit_ip_adapter_clear": (_i, [_vp]),
     "mc_mmdit_forward": (_i, [_vp, _vp, _d, _d, _vp, _i, _vp, _i, _vp, _vp]),
     "mc_mmdit_forward2": (_i, [_vp, _vp, _d, _d, _vp, _i, _vp, _i, _i, _vp, _vp]),
     "mc_mmdit_begin": (_i, [_vp, _vp, _d, _d, _vp, _i, _vp, _i, _vp]),
@@ -185,6 +191,13 @@ MC_LORA_MAX_TERMS = 8
 
 class McLoraTerm(C.Structure):   # mc_lora_term: bf16 down [rank, K] and up [rows, rank] on the device
     _fields_ = [("down", C.c_void_p), ("up", C.c_void_p), ("rank", C.c_int), ("scale", C.c_float)]
+
+
+MC_IP_MAX_ADAPTERS, MC_IP_MAX_KEYS = 4, 256
+
+
+class McIpKeys(C.Structure):   # mc_ip_keys: one adapter's [K | V] rows of one block (bf16, on the device), key count and scale
+    _fields_ = [("kv", C.c_void_p), ("ld", C.c_long), ("valid", C.c_int), ("scale", C.c_float)]
 
 
 _lib = None

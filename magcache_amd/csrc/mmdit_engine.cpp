@@ -88,6 +88,19 @@ struct Refiner {
   Linear qkv, o, fc1, fc2, ada;
   float *n1w, *n1b, *n2w, *n2b;
 };
+// One IP-Adapter (FLUX): diffusers' ImageProjection (Linear + affine LayerNorm) and, per double block, to_k_ip | to_v_ip as ONE
+// Linear.  Two image slots (the positive and the negative image prompt of a true-CFG pipeline): the K|V of every double block
+// for the slot's image, [n_double][rows][2d] bf16, computed once per image by mc_mmdit_ip_adapter_set_image.
+struct IpAdapter {
+  int embed_dim = 0, cross_dim = 0, tokens = 0;
+  Linear proj;                       // [tokens * cross_dim, embed_dim]
+  float *ln_w = nullptr, *ln_b = nullptr;
+  std::vector<Linear> kv;            // per double block: [2d, cross_dim], rows to_k_ip | to_v_ip
+  std::vector<float> scale;          // per double block
+  bf16_t* cache[2] = {nullptr, nullptr};
+  int keys[2] = {0, 0}, rows[2] = {0, 0};   // valid keys of the slot; rows allocated per block
+  std::vector<std::string> names;    // what it registered in the store
+};
 
 }  // namespace
 
@@ -124,6 +137,14 @@ struct mc_mmdit {
   std::vector<const void*> cn_double, cn_single;
   mc_dtype cn_dtype = MC_F32;
   bool cn_repeat = false;
+  // IP-Adapters (mc_mmdit_ip_adapter_*, FLUX): everything lives in the weight store, outside the workspace
+  std::vector<std::unique_ptr<IpAdapter>> ip;   // (the store keeps pointers to the Linears: the adapters never move)
+  int ip_slot = -1;                  // the image slot the forwards read; -1: none
+  bf16_t* ip_out = nullptr;          // [Li, d]: the attention result of the block in progress
+  int ip_out_rows = 0;
+  float* ip_h32 = nullptr;           // set_image scratch: the projection [kIpMaxKeys, cross_dim] fp32 ...
+  bf16_t* ip_hb = nullptr;           // ... and its LayerNorm, the operand of the K|V Linears
+  int ip_h_cross = 0;
 
   template <class T>
   T* buf(const char* name) const { return work.get<T>(name); }
@@ -350,6 +371,17 @@ mc_status rope_identity(mc_mmdit* e, int rows) {
   for (size_t i = 0; i < ident.size(); i += 2) { ident[i] = 1.f; ident[i + 1] = 0.f; }
   if (hipMemcpy(e->cs, ident.data(), ident.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
     return fail(MC_EHIP, "RoPE table upload failed");
+  return MC_OK;
+}
+
+// "ip_out" [rows, d] in the store, grown where it is shorter (never inside a forward)
+mc_status ip_grow_out(mc_mmdit* e, int rows) {
+  if (rows <= e->ip_out_rows) return MC_OK;
+  bf16_t* grown = nullptr;
+  MC_TRY(e->weights.alloc(&grown, (size_t)rows * e->d));
+  if (e->ip_out) e->weights.release(e->ip_out);
+  e->ip_out = grown;
+  e->ip_out_rows = rows;
   return MC_OK;
 }
 
@@ -592,7 +624,8 @@ mc_status mc_mmdit_set_geometry(mc_mmdit* e, int img_tokens, int latent_f, int l
                 e->work.bound);
   // earlier forwards may still be reading the RoPE table and the buffers of the old plan
   HIP_TRY(hipDeviceSynchronize());
-  MC_TRY(rope_identity(e, r.Sp));   // the one step that can fail for lack of memory: before anything changes
+  MC_TRY(rope_identity(e, r.Sp));   // the steps that can fail for lack of memory: before anything changes
+  if (!e->ip.empty()) MC_TRY(ip_grow_out(e, r.Li));
   MC_TRY(e->work.replan(plan));
   apply_geometry(e, g, r);
   e->cn_double.clear();   // the samples were [img_tokens, d] of the old geometry
@@ -804,6 +837,28 @@ mc_status range_linear(const mc_mmdit* e, const Range* r, int n, Linear Stream::
   return linear(e, r[0].w->*l, rows, A, lda, p, epi, s, n == 2 ? &(r[1].w->*l) : nullptr, r[0].rows, gate_b, a8);
 }
 
+// ---- IP-Adapter: the adapters that count in double block `blk` (an image in the selected slot, a scale that is not 0)
+int ip_live(const mc_mmdit* e, int blk, mc::IpKeys* keys) {
+  int n = 0;
+  if (e->ip_slot < 0 || blk >= e->cfg.n_double) return 0;
+  for (const auto& a : e->ip) {
+    const int k = a->keys[e->ip_slot];
+    if (k <= 0 || a->scale[blk] == 0.f) continue;
+    if (keys) keys[n] = {a->cache[e->ip_slot] + (size_t)blk * a->rows[e->ip_slot] * 2 * e->d, 2L * e->d, k, a->scale[blk]};
+    ++n;
+  }
+  return n;
+}
+// "ip_out" = sum_j scale_j softmax(q_n K_j^T / sqrt(128)) V_j over the image rows, from the RAW q of "qkv"
+mc_status ip_attend(const mc_mmdit* e, int blk, hipStream_t s) {
+  mc::IpKeys keys[mc::kIpMaxAdapters];
+  const int n = ip_live(e, blk, keys);
+  if (n == 0) return MC_OK;
+  HIP_TRY(mc::launch_ip_attention(e->buf<bf16_t>("qkv") + (size_t)e->img0 * 3 * e->d, 3L * e->d, e->dimg[blk].qn, 1e-6f, keys, n,
+                                  e->ip_out, e->d, e->Li, e->H, s));
+  return MC_OK;
+}
+
 // before the joint attention: LN + modulate, QKV, per-head q/k norm, RoPE
 // phases (diagnostic split, tests/two_stream_bisect.py): 1 = LN + QKV GEMM, 2 = head norm + RoPE, 3 = both
 mc_status double_pre(const mc_mmdit* e, const Range* r, int n, hipStream_t s, int phases = 3) {
@@ -819,9 +874,13 @@ mc_status double_pre(const mc_mmdit* e, const Range* r, int n, hipStream_t s, in
     MC_TRY(range_linear(e, r, n, &Stream::qkv, xn + (size_t)r[0].row0 * d, d, p, mc::EPI_BF16, nullptr, s, &a8));
   }
   if (phases & 2)
-    for (int i = 0; i < n; ++i)
+    for (int i = 0; i < n; ++i) {
+      // the image range of a block with a live image prompt: the IP attention reads the raw q this head norm is about to rotate
+      if (!e->dimg.empty() && r[i].w >= e->dimg.data() && r[i].w < e->dimg.data() + e->dimg.size())
+        MC_TRY(ip_attend(e, (int)(r[i].w - e->dimg.data()), s));
       HIP_TRY(mc::launch_headnorm_rope(qkv + (size_t)r[i].row0 * 3 * d, 3 * d, d, r[i].w->qn, r[i].w->kn, 1e-6f, e->cs, r[i].row0,
                                        r[i].rows, e->H, s));
+    }
   return MC_OK;
 }
 
@@ -1047,6 +1106,136 @@ mc_status mc_mmdit_set_controlnet(mc_mmdit* e, const void* const* double_samples
   return MC_OK;
 }
 
+// ---- IP-Adapters
+static mc_status ip_entry(const mc_mmdit* e, const char* what) {
+  if (!e) return fail(MC_EINVAL, "null engine");
+  if (e->cfg.family != MC_FAMILY_FLUX) return fail(MC_EINVAL, "%s: IP-Adapters are a FLUX input; this engine is another family", what);
+  if (e->begun) return fail(MC_ESTATE, "%s between mc_mmdit_begin and mc_mmdit_end", what);
+  return MC_OK;
+}
+static mc_status ip_which(const mc_mmdit* e, int adapter) {
+  if (adapter < 0 || adapter >= (int)e->ip.size()) return fail(MC_EINVAL, "IP-Adapter %d of %zu", adapter, e->ip.size());
+  return MC_OK;
+}
+
+mc_status mc_mmdit_ip_adapter_add(mc_mmdit* e, int embed_dim, int cross_dim, int tokens_per_image, int* index) {
+  MC_TRY(ip_entry(e, "mc_mmdit_ip_adapter_add"));
+  if (e->cfg.n_double == 0) return fail(MC_EINVAL, "IP-Adapter: the engine has no double blocks");
+  if ((int)e->ip.size() >= mc::kIpMaxAdapters) return fail(MC_EINVAL, "IP-Adapter: at most %d adapters", mc::kIpMaxAdapters);
+  static const int ln_ok[] = {1, 2, 4, 5, 6, 8, 12, 16, 20};   // launch_ln_modulate's widths, in units of 256
+  bool cross_ok = cross_dim > 0 && (cross_dim % 256) == 0;
+  if (cross_ok) { cross_ok = false; for (int v : ln_ok) cross_ok |= v == cross_dim / 256; }
+  if (!cross_ok) return fail(MC_EINVAL, "IP-Adapter: cross_dim %d is no LayerNorm width of this library (256 x 1, 2, 4, 5, 6, 8, 12, 16, 20)", cross_dim);
+  if (embed_dim <= 0 || (embed_dim % 8) != 0 || embed_dim > 16384) return fail(MC_EINVAL, "IP-Adapter: embed_dim %d (a multiple of 8, at most 16384)", embed_dim);
+  if (tokens_per_image < 1 || tokens_per_image > mc::kIpMaxKeys) return fail(MC_EINVAL, "IP-Adapter: %d tokens per image (1..%d)", tokens_per_image, mc::kIpMaxKeys);
+  const int j = (int)e->ip.size();
+  const size_t d = e->d;
+  mc::WeightStore& W = e->weights;
+  if (cross_dim > e->ip_h_cross) {   // the scratch of set_image: kIpMaxKeys rows of the widest adapter
+    float* h32 = nullptr; bf16_t* hb = nullptr;
+    MC_TRY(W.alloc(&h32, (size_t)mc::kIpMaxKeys * cross_dim));
+    if (mc_status st = W.alloc(&hb, (size_t)mc::kIpMaxKeys * cross_dim)) { W.release(h32); return st; }
+    HIP_TRY(hipMemset(hb, 0, (size_t)mc::kIpMaxKeys * cross_dim * 2));
+    if (e->ip_h32) { W.release(e->ip_h32); W.release(e->ip_hb); }
+    e->ip_h32 = h32; e->ip_hb = hb; e->ip_h_cross = cross_dim;
+  }
+  MC_TRY(ip_grow_out(e, e->Li));
+  auto a = std::make_unique<IpAdapter>();
+  a->embed_dim = embed_dim; a->cross_dim = cross_dim; a->tokens = tokens_per_image;
+  a->scale.assign(e->cfg.n_double, 1.f);
+  a->kv.resize(e->cfg.n_double);
+  const std::string js = std::to_string(j), pp = "encoder_hid_proj.image_projection_layers." + js + ".";
+  MC_TRY(W.add_linear(a->proj, pp, {{"image_embeds", (size_t)tokens_per_image * cross_dim}}, embed_dim));
+  MC_TRY(W.add_f32(a->ln_w, pp + "norm.weight", cross_dim));
+  MC_TRY(W.add_f32(a->ln_b, pp + "norm.bias", cross_dim));
+  a->names = {pp + "image_embeds.weight", pp + "image_embeds.bias", pp + "norm.weight", pp + "norm.bias"};
+  for (int i = 0; i < e->cfg.n_double; ++i) {
+    const std::string p = "transformer_blocks." + std::to_string(i) + ".attn.processor.";
+    MC_TRY(W.add_linear(a->kv[i], p, {{"to_k_ip." + js, d}, {"to_v_ip." + js, d}}, cross_dim));
+    for (const char* part : {"to_k_ip.", "to_v_ip."})
+      for (const char* leaf : {".weight", ".bias"}) a->names.push_back(p + part + js + leaf);
+  }
+  e->ip.push_back(std::move(a));
+  if (index) *index = j;
+  return MC_OK;
+}
+
+mc_status mc_mmdit_ip_adapter_set_image(mc_mmdit* e, int adapter, int slot, const float* embeds_dev, int n_images, mc_stream stream) {
+  MC_TRY(ip_entry(e, "mc_mmdit_ip_adapter_set_image"));
+  MC_TRY(ip_which(e, adapter));
+  if (slot < 0 || slot > 1) return fail(MC_EINVAL, "IP-Adapter image slot %d (0 or 1)", slot);
+  IpAdapter& a = *e->ip[adapter];
+  if (n_images == 0) { a.keys[slot] = 0; return MC_OK; }
+  const int keys = n_images * a.tokens;
+  if (n_images < 0 || n_images > mc::kIpMaxKeys || keys > mc::kIpMaxKeys)
+    return fail(MC_EINVAL, "IP-Adapter %d: %d images of %d tokens are more than %d keys", adapter, n_images, a.tokens, mc::kIpMaxKeys);
+  if (!embeds_dev || (reinterpret_cast<uintptr_t>(embeds_dev) & 15)) return fail(MC_EINVAL, "IP-Adapter: the image embeds are null or not 16-byte aligned");
+  for (const std::string& n : a.names)
+    if (!e->weights.slots.at(n).loaded) return fail(MC_ESTATE, "IP-Adapter %d: weight '%s' is not set", adapter, n.c_str());
+  hipStream_t s = (hipStream_t)stream;
+  const size_t d = e->d;
+  if (keys > a.rows[slot]) {   // the slot's cache grows: an earlier forward may still read the old one
+    HIP_TRY(hipDeviceSynchronize());
+    const int rows = (int)align_up(keys, 32);
+    bf16_t* grown = nullptr;
+    MC_TRY(e->weights.alloc(&grown, (size_t)e->cfg.n_double * rows * 2 * d));
+    if (a.cache[slot]) e->weights.release(a.cache[slot]);
+    a.cache[slot] = grown;
+    a.rows[slot] = rows;
+  }
+  a.keys[slot] = 0;   // until everything below is launched
+  // ImageProjection: Linear per image (its [tokens * cross_dim] output is tokens rows of the hidden states), affine LayerNorm
+  const int row_w = a.tokens * a.cross_dim;
+  for (int i = 0; i < n_images; ++i)
+    HIP_TRY(mc::launch_gemv_bf16w(a.proj.w, embeds_dev + (size_t)i * a.embed_dim, a.proj.b, e->ip_h32 + (size_t)i * row_w, row_w, a.embed_dim,
+                                  0, 0, 0, s));
+  HIP_TRY(mc::launch_ln_modulate(e->ip_h32, a.cross_dim, nullptr, 0, a.ln_w, a.ln_b, 1, 1e-5f, e->ip_hb, a.cross_dim, nullptr, 0, keys,
+                                 a.cross_dim, s));
+  for (int i = 0; i < e->cfg.n_double; ++i) {
+    mc::GemmParams p = {};
+    p.Cb = a.cache[slot] + (size_t)i * a.rows[slot] * 2 * d; p.ldc = 2 * d;
+    // not through linear(): no split-K scratch of the workspace, so that a slot's bits depend on no geometry and no forward
+    // on another stream shares scratch with this call
+    HIP_TRY(mc::launch_linear_bf16(a.kv[i], mc::whole(a.kv[i]), e->ip_hb, a.cross_dim, keys, p, mc::EPI_BF16, s));
+  }
+  a.keys[slot] = keys;
+  return MC_OK;
+}
+
+mc_status mc_mmdit_ip_adapter_scale(mc_mmdit* e, int adapter, const float* scales, int n) {
+  MC_TRY(ip_entry(e, "mc_mmdit_ip_adapter_scale"));
+  MC_TRY(ip_which(e, adapter));
+  if (!scales || (n != 1 && n != e->cfg.n_double)) return fail(MC_EINVAL, "IP-Adapter scales: 1 or %d values, %d given", e->cfg.n_double, n);
+  for (int i = 0; i < n; ++i)
+    if (!std::isfinite(scales[i])) return fail(MC_EINVAL, "IP-Adapter scale %d is not finite", i);
+  IpAdapter& a = *e->ip[adapter];
+  for (int i = 0; i < e->cfg.n_double; ++i) a.scale[i] = scales[n == 1 ? 0 : i];
+  return MC_OK;
+}
+
+mc_status mc_mmdit_ip_adapter_select(mc_mmdit* e, int slot) {
+  MC_TRY(ip_entry(e, "mc_mmdit_ip_adapter_select"));
+  if (slot < -1 || slot > 1) return fail(MC_EINVAL, "IP-Adapter image slot %d (-1: none, 0, 1)", slot);
+  e->ip_slot = slot;
+  return MC_OK;
+}
+
+mc_status mc_mmdit_ip_adapter_clear(mc_mmdit* e) {
+  MC_TRY(ip_entry(e, "mc_mmdit_ip_adapter_clear"));
+  if (e->ip.empty()) { e->ip_slot = -1; return MC_OK; }
+  HIP_TRY(hipDeviceSynchronize());   // an earlier forward may still read what goes
+  for (auto& a : e->ip) {
+    for (const std::string& n : a->names) e->weights.slots.erase(n);
+    e->weights.release(a->proj.w); e->weights.release(a->proj.b);
+    e->weights.release(a->ln_w); e->weights.release(a->ln_b);
+    for (Linear& l : a->kv) { e->weights.release(l.w); e->weights.release(l.b); }
+    for (bf16_t* c : a->cache) if (c) e->weights.release(c);
+  }
+  e->ip.clear();
+  e->ip_slot = -1;
+  return MC_OK;
+}
+
 mc_status mc_mmdit_begin(mc_mmdit* e, const float* img_dev, double timestep, double guidance, const float* txt_dev,
                          int txt_valid, const float* vec_dev, mc_mode mode, mc_stream stream) {
   return begin_impl(e, img_dev, timestep, guidance, txt_dev, txt_valid, vec_dev, mode, 0, stream);
@@ -1175,7 +1364,9 @@ mc_status mc_mmdit_block_post(mc_mmdit* e, int blk, mc_stream stream_) {
   }
   const bool last = (blk == nb - 1);
   const void* cn = (e->cn_double.empty() && e->cn_single.empty()) ? nullptr : controlnet_sample(e, blk);
-  const bool capture = last && !cn;   // a sample on the last block: controlnet_add captures after its add
+  const bool ip = ip_live(e, blk, nullptr) > 0;
+  // the add that runs last on the last block captures after it: a ControlNet sample's, else the IP-Adapter's, else MLP-out
+  const bool capture = last && !cn && !ip;
   float* capture_to = capture ? e->residual_joint(e->dst, e->branch) : nullptr;
   if (blk < c.n_double) {
     const TwoStreams t = two_streams(e, blk, emod);
@@ -1205,6 +1396,11 @@ mc_status mc_mmdit_block_post(mc_mmdit* e, int blk, mc_stream stream_) {
       MC_TRY(mx_quantise(e, am, 5 * d, S, (g.in.mx && mc::g_fp8_fused_quant) ? d : 5 * d, to, s));
     }
     MC_TRY(linear(e, g.out, S, am, 5 * d, o, epi, s, nullptr, 0, nullptr, &a8));
+  }
+  if (ip) {   // hidden_states + ip_attn_output (FluxTransformerBlock.forward): behind the MLP, in front of the ControlNet sample
+    const bool cap = last && !cn;
+    HIP_TRY(mc::launch_add_rows(e->buf<float>("x") + (size_t)e->img0 * d, d, e->ip_out, 1, cap ? e->residual(e->dst, e->branch) : nullptr,
+                                d, cap ? e->buf<bf16_t>("x0") + (size_t)e->img0 * d : nullptr, d, Li, d, s));
   }
   if (cn) MC_TRY(controlnet_add(e, cn, last, s));
   if (last) {

@@ -252,6 +252,26 @@ hipError_t launch_add_bf16(bf16_t* a, const bf16_t* b, size_t n, hipStream_t str
 // add.  hipErrorInvalidValue for D % 8 != 0 or a pointer that is not 16-byte aligned.
 hipError_t launch_add_rows(float* x, long ldx, const void* s, int s_bf16, float* r, long ldr, const bf16_t* x0, long ldx0,
                            int rows, int D, hipStream_t stream);
+// IP-Adapter cross-attention of the FLUX double block (ip_attention.hip): one adapter's keys and values of one block, rows of
+// [K | V] bf16 ([.., 2 * heads * 128], leading dimension ld), the first `valid` (1..kIpMaxKeys) of them keys, and its scale
+constexpr int kIpMaxAdapters = 4, kIpMaxKeys = 256;
+struct IpKeys {
+  const bf16_t* kv;
+  long ld;
+  int valid;
+  float scale;
+};
+// out[m, head] = sum_j scale_j softmax(q_n[m, head] K_j[head]^T / sqrt(128)) V_j[head] for m < rows, bf16 [rows, heads * 128];
+// q: the RAW q columns (launch_headnorm_rope has not run), normalised per head as that kernel does without a table,
+// q_n = bf16(bf16(q rstd) wq); softmax per adapter, fp32 sum over the adapters, one bf16 rounding.  Rows of a cache past `valid`
+// are never read; an adapter with scale 0 is skipped (all of them: zeros).  hipErrorInvalidValue for 0 or more than
+// kIpMaxAdapters adapters, a key count outside 1..kIpMaxKeys, a pointer that is not 16-byte aligned, a leading dimension that
+// is no multiple of 8 or too short.
+hipError_t launch_ip_attention(const bf16_t* q, long ldq, const float* wq, float eps, const IpKeys* adapters, int n_adapters,
+                               bf16_t* out, long ldo, int rows, int heads, hipStream_t stream);
+// test entry (mc_test_ip_qnorm): out = q_n as launch_ip_attention forms it, the same kernel stopped after its first step
+hipError_t launch_ip_attention_qnorm(const bf16_t* q, long ldq, const float* wq, float eps, bf16_t* out, long ldo, int rows, int heads,
+                                     hipStream_t stream);
 // head: out[m, n] = dot(xn[m,:], W[n,:]) + b[n], fp32, N <= 256 (64 columns per block)
 hipError_t launch_head_linear(const float* xn, long ldx, const float* W, const float* b, float* out, long ldo,
                               int M, int N, int K, hipStream_t stream);

@@ -289,6 +289,22 @@ mc_status mc_op_add_rows(float* x, long ldx, const void* s, mc_dtype s_dtype, fl
   return MC_OK;
 }
 
+mc_status mc_op_ip_attention(const void* q, long ldq, const float* wq, float eps, const mc_ip_keys* adapters, int n_adapters,
+                             void* out, long ldo, int rows, int heads, mc_stream stream) {
+  mc::IpKeys keys[mc::kIpMaxAdapters] = {};
+  static_assert(mc::kIpMaxAdapters == MC_IP_MAX_ADAPTERS && mc::kIpMaxKeys == MC_IP_MAX_KEYS, "header and kernel limits");
+  hipError_t err = hipErrorInvalidValue;
+  if (adapters && n_adapters >= 1 && n_adapters <= mc::kIpMaxAdapters) {
+    for (int j = 0; j < n_adapters; ++j) keys[j] = {(const bf16_t*)adapters[j].kv, adapters[j].ld, adapters[j].valid, adapters[j].scale};
+    err = mc::launch_ip_attention((const bf16_t*)q, ldq, wq, eps, keys, n_adapters, (bf16_t*)out, ldo, rows, heads, (hipStream_t)stream);
+  }
+  if (err == hipErrorInvalidValue)
+    return fail(MC_EINVAL, "ip_attention: 1..%d adapters of 1..%d keys, rows >= 1, 16-byte aligned pointers, ldq / ldo >= heads * 128 and "
+                           "ld >= 2 * heads * 128, all multiples of 8", mc::kIpMaxAdapters, mc::kIpMaxKeys);
+  HIP_TRY(err);
+  return MC_OK;
+}
+
 size_t mc_op_lora_merge_scratch(int rows, int K, const mc_lora_term* terms, int n_terms) {
   size_t bytes = 0;
   for (int j = 0; terms && j < n_terms; ++j) {

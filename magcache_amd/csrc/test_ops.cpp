@@ -14,6 +14,10 @@ int mc_test_headnorm_rope(void* x, long ldx, long k_col0, const float* wq, const
   return (int)mc::launch_headnorm_rope((bf16_t*)x, ldx, k_col0, wq, wk, eps, cs, cs_row0, M, n_heads, (hipStream_t)s);
 }
 
+int mc_test_ip_qnorm(const void* q, long ldq, const float* wq, float eps, void* out, long ldo, int rows, int heads, void* s) {
+  return (int)mc::launch_ip_attention_qnorm((const bf16_t*)q, ldq, wq, eps, (bf16_t*)out, ldo, rows, heads, (hipStream_t)s);
+}
+
 int mc_test_gemv_bf16w(const void* W, const float* x, const float* b, float* y, int N, int K, int act_in, int act_out,
                        int accumulate, void* s) {
   return (int)mc::launch_gemv_bf16w((const bf16_t*)W, x, b, y, N, K, act_in, act_out, accumulate, (hipStream_t)s);

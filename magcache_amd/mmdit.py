@@ -26,6 +26,7 @@ import torch
 from . import _lib
 from ._lib import (MC_F32, MC_BF16, MC_FAMILY_FLUX, MC_FAMILY_HUNYUAN, MC_FAMILY_QWEN, MC_MODE_CALIB, MC_MODE_FULL,
                    MC_MODE_SKIP, McMmditConfig, check)
+from . import ip_adapter as IP
 from . import rule
 from .adapters import EngineHost, LoraModel, _ptr, _stream
 from .mag_ratios import TABLES
@@ -75,6 +76,8 @@ class MMDiTEngine(EngineHost):
         self._bind(self.lib.mc_mmdit_workspace_bytes(self.h))
         self._rope_key = None
         self._controlnet = None
+        self._ip = []                 # loaded IP-Adapters: (embed_dim, tokens per image)
+        self._ip_keep = {}            # (adapter, slot) -> the staged embeds the last set_ip_adapter_image launched on
         self._lora_init()
 
     def geometry_bytes(self, img_tokens, latent_grid=(0, 0, 0), txt_len=None):
@@ -158,6 +161,42 @@ class MMDiTEngine(EngineHost):
         check(self.lib.mc_mmdit_set_controlnet(self.h, lists[0], len(keep[0]), lists[1], len(keep[1]),
                                                MC_F32 if dtypes == {torch.float32} else MC_BF16, int(bool(blocks_repeat))))
         self._controlnet = keep
+
+    # ---- FLUX IP-Adapters (mc_mmdit_ip_adapter_*; magcache_amd/ip_adapter.py reads the files and keeps the slots)
+    def add_ip_adapter(self, embed_dim, cross_dim, tokens_per_image):
+        """register one more adapter; its weights are then set by name (ip_adapter.weight_names).  Returns its index."""
+        j = C.c_int(-1)
+        check(self.lib.mc_mmdit_ip_adapter_add(self.h, int(embed_dim), int(cross_dim), int(tokens_per_image), C.byref(j)))
+        self._ip.append((int(embed_dim), int(tokens_per_image)))
+        return j.value
+
+    def set_ip_adapter_image(self, adapter, slot, embeds):
+        """the image prompt of `adapter` in slot 0 / 1: embeds [n_images, embed_dim] -> projection, LayerNorm and the K|V of
+        every double block, once (None: empty the slot).  Not a per-forward call."""
+        if embeds is None:
+            check(self.lib.mc_mmdit_ip_adapter_set_image(self.h, int(adapter), int(slot), None, 0, _stream()))
+            self._ip_keep.pop((adapter, slot), None)
+            return
+        t = _f32(embeds, self.device)
+        if t.dim() != 2:
+            raise ValueError(f"IP-Adapter image embeds {tuple(t.shape)}: expected [n_images, embed_dim]")
+        if 0 <= adapter < len(self._ip) and t.shape[1] != self._ip[adapter][0]:
+            raise ValueError(f"IP-Adapter {adapter} image embeds {tuple(t.shape)}: embed_dim is {self._ip[adapter][0]}")
+        check(self.lib.mc_mmdit_ip_adapter_set_image(self.h, int(adapter), int(slot), _ptr(t), t.shape[0], _stream()))
+        self._ip_keep[(adapter, slot)] = t      # the launches are asynchronous
+
+    def set_ip_adapter_scale(self, adapter, scales):
+        """a number (every double block) or one number per double block; launch arguments of the following forwards"""
+        v = [float(scales)] if not isinstance(scales, (list, tuple)) else [float(x) for x in scales]
+        check(self.lib.mc_mmdit_ip_adapter_scale(self.h, int(adapter), (C.c_float * len(v))(*v), len(v)))
+
+    def select_ip_adapter(self, slot):
+        """the image slot the following forwards read: 0, 1 or -1 / None for none"""
+        check(self.lib.mc_mmdit_ip_adapter_select(self.h, -1 if slot is None else int(slot)))
+
+    def clear_ip_adapter(self):
+        check(self.lib.mc_mmdit_ip_adapter_clear(self.h))
+        self._ip, self._ip_keep = [], {}
 
     def forward(self, img, timestep, guidance, txt, txt_valid, vec, mode=MC_MODE_FULL, out=None, branch=None):
         """`branch` (None = the one-slot mc_mmdit_forward): the CFG branch of mc_mmdit_forward2 (Qwen-Image 0 / 1).
@@ -243,7 +282,10 @@ class MMDiTSequenceParallel:
     def forward(self, img, timestep, guidance, txt, txt_valid, vec, mode):
         """FLUX ControlNet samples are state of the rank's engine, not an argument: MMDiTEngine.set_controlnet ahead of
         this call (the FLUX shims do it), with the FULL [img_tokens, dim] tensors on every rank; block_post adds this
-        rank's rows of them."""
+        rank's rows of them.
+        FLUX IP-Adapters likewise: the adapters, the image prompt of each slot and the selection belong to the rank's
+        engine (load_ip_adapter on every rank's model; the shims set and select the image ahead of this call).  The keys
+        of an image prompt are replicated, every rank attends its own image rows over them, and nothing is gathered."""
         e = self.e
         e.begin(img, timestep, guidance, txt, txt_valid, vec, mode)
         if mode != MC_MODE_SKIP:
@@ -357,6 +399,39 @@ class FluxTransformer2DModelHIP(_LoraMethods):
         self.engine.load_weights(sd)
         return self
 
+    # ---- IP-Adapters (diffusers FluxIPAdapterMixin)
+    def load_ip_adapter(self, state_dict, tokens_per_image=None, strict=True):
+        """Load ONE IP-Adapter (the spellings ip_adapter.parse_state_dict reads); a second call loads a second adapter, and the
+        list in joint_attention_kwargs["ip_adapter_image_embeds"] then has one tensor per adapter in that order.  embed_dim,
+        cross_dim and the tokens per image come from the shapes.  Keys that are no IP-Adapter weight raise under `strict` and
+        are returned otherwise, like load_lora's.  Scales start at 1.0 (set_ip_adapter_scale)."""
+        a = IP.parse_state_dict(state_dict, self.cfg["num_layers"], tokens_per_image)
+        if a["unknown"] and strict:
+            raise ValueError(f"IP-Adapter state dict has {len(a['unknown'])} keys that are no IP-Adapter weight, e.g. {a['unknown'][:3]}")
+        e = self.engine
+        if len(e._ip) >= IP.MAX_ADAPTERS:
+            raise ValueError(f"at most {IP.MAX_ADAPTERS} IP-Adapters")
+        j = e.add_ip_adapter(a["embed_dim"], a["cross_dim"], a["tokens"])
+        for name, t in a["weights"].items():
+            e.set_weight(name.format(j=j), t)
+        self._ip_slots().forget()
+        return a["unknown"]
+
+    def set_ip_adapter_scale(self, scale):
+        """diffusers' set_ip_adapter_scale: a number, a list with one entry per adapter, each a number or a list with one
+        number per double block.  Costs nothing: the scales are arguments of the next forward's launches."""
+        for j, s in enumerate(IP.normalise_scales(scale, len(self.engine._ip), self.cfg["num_layers"])):
+            self.engine.set_ip_adapter_scale(j, s)
+
+    def unload_ip_adapter(self):
+        self.engine.clear_ip_adapter()
+        self._ip_slots().forget()
+
+    def _ip_slots(self):
+        if getattr(self, "_ip_image_slots", None) is None:
+            self._ip_image_slots = IP.ImageSlots()
+        return self._ip_image_slots
+
     def _geometry(self, hidden_states, encoder_hidden_states):
         """dynamic_geometry: follow the call's image tokens / text length (the RoPE comes from the call's ids as always)"""
         if not self.dynamic_geometry or hidden_states.dim() != 3:
@@ -413,6 +488,20 @@ def _flux_set_controlnet(model, double, single, blocks_repeat, hidden_states=Non
         e.set_controlnet(double, single, blocks_repeat)
 
 
+def _flux_set_ip_adapter(model, kwargs):
+    """joint_attention_kwargs["ip_adapter_image_embeds"] of a call (magcache_flux.py:108-111, :321-324) -> the engine, ahead
+    of the forward: the list is checked against the loaded adapters, the slot that holds these tensors is selected (computed
+    first where neither slot does); a call without the key selects none.  The key without a loaded adapter is an error --
+    it used to be dropped without a word."""
+    e = model.engine
+    if kwargs is None or "ip_adapter_image_embeds" not in kwargs:
+        if getattr(e, "_ip", None):
+            e.select_ip_adapter(None)
+        return
+    embeds = IP.check_embeds(kwargs["ip_adapter_image_embeds"], getattr(e, "_ip", []))
+    model._ip_slots().use(e, embeds)
+
+
 def _flux_output(output, return_dict):
     return SimpleNamespace(sample=output) if return_dict else (output,)
 
@@ -422,6 +511,7 @@ def flux_plain_forward(self, hidden_states, encoder_hidden_states=None, pooled_p
                        controlnet_block_samples=None, controlnet_single_block_samples=None, return_dict=True,
                        controlnet_blocks_repeat=False, **_):
     _lora_call_scale(self, joint_attention_kwargs)
+    _flux_set_ip_adapter(self, joint_attention_kwargs)
     _flux_set_controlnet(self, controlnet_block_samples, controlnet_single_block_samples, controlnet_blocks_repeat,
                          hidden_states, encoder_hidden_states)
     out = self._run(hidden_states, encoder_hidden_states, pooled_projections, timestep, img_ids, txt_ids, guidance, MC_MODE_FULL)
@@ -437,6 +527,7 @@ def flux_magcache_forward(self, hidden_states, encoder_hidden_states=None, poole
                           controlnet_blocks_repeat=False):
     """Drop-in for MagCache4FLUX/magcache_flux.py magcache_forward (:234-445)."""
     _lora_call_scale(self, joint_attention_kwargs)
+    _flux_set_ip_adapter(self, joint_attention_kwargs)
     _flux_set_controlnet(self, controlnet_block_samples, controlnet_single_block_samples, controlnet_blocks_repeat,
                          hidden_states, encoder_hidden_states)
     _, skip_forward = rule.decide(self, "flux")      # :333-344: int(R n + 0.5), `<=`, step 11 of 28 never skipped
@@ -453,6 +544,7 @@ def flux_magcache_calibration(self, hidden_states, encoder_hidden_states=None, p
                               controlnet_blocks_repeat=False):
     """Drop-in for magcache_flux.py magcache_calibration (:37-232)."""
     _lora_call_scale(self, joint_attention_kwargs)
+    _flux_set_ip_adapter(self, joint_attention_kwargs)
     _flux_set_controlnet(self, controlnet_block_samples, controlnet_single_block_samples, controlnet_blocks_repeat,
                          hidden_states, encoder_hidden_states)
     out = self._run(hidden_states, encoder_hidden_states, pooled_projections, timestep, img_ids, txt_ids, guidance, MC_MODE_CALIB)

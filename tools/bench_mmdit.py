@@ -20,6 +20,13 @@ headline bench line):
                                           forwards in alternating windows: ms per forward and the spread of the windows per mode,
                                           workspace bytes, distance of every mode's output from the first mode's
 
+    python tools/bench_mmdit.py flux --ip-adapter TOKENS[xIMAGES][,...] [--depth D,S]
+                                          FLUX.1-dev 1024x1024, one full forward with one IP-Adapter per entry (768-wide embeds,
+                                          cross_dim 4096, TOKENS per image, IMAGES images) against the same engine without
+                                          the key, alternating windows; the set_ip_adapter_image wall time (projection,
+                                          LayerNorm and the K|V of every double block) and the kernel and the add alone at
+                                          the forward's shapes (mc_op_ip_attention, mc_op_add_rows)
+
 Synthetic inputs, seeded random-init weights of the real architecture (no checkpoints offline).  One JSON line each.
 Also checks the size-independent MagCache properties at full size: a skipped forward equals the final layer applied
 to ori + cached residual, i.e. re-running a skip is idempotent and finite.
@@ -204,6 +211,99 @@ def bench_flux_controlnet(n_double, n_single, rounds=7, per_round=4):
                       "forward_ms_without": float(np.median(ms["without"])), "forward_ms_with": float(np.median(ms["with"])),
                       "windows_without_ms": [round(v, 3) for v in ms["without"]], "windows_with_ms": [round(v, 3) for v in ms["with"]],
                       "forwards_per_window": per_round, "finite": bool(torch.isfinite(o_with).all()),
+                      "output_moved_rel_l2": float((o_with - o_without).norm() / o_without.norm())}))
+
+
+def bench_flux_ip_adapter(specs, depth=None, rounds=7, per_round=4):
+    """One FULL forward at FLUX.1-dev 1024x1024 with image prompts and without, on ONE engine, in alternating windows of
+    `per_round` forwards after a warm-up of both; then the wall time of set_ip_adapter_image and, through the single-op
+    entries at the forward's shapes, the attention launch and the add launch alone (100 launches each between two
+    synchronises; operands of 25 to 75 MB each, so partly served by the last-level cache like in the forward)."""
+    import ctypes as C
+    from magcache_amd import _lib, ip_adapter as IP
+    cfg = dict(MM.FLUX_DEV)
+    if depth:
+        cfg["num_layers"], cfg["num_single_layers"] = depth
+    h2 = w2 = 64
+    txt_len, d, heads, embed_dim, cross = 512, 3072, 24, 768, 4096
+    n_img = h2 * w2
+    cls = type("FluxIpAdapterBench", (MM.FluxTransformer2DModelHIP,), {})
+    m = cls(cfg, n_img, txt_len=txt_len, device=DEV, calibration=False)
+    synth_load(m, flux_names(cfg))
+    g = torch.Generator(device=DEV).manual_seed(42)
+    embeds = []
+    for j, (tokens, images) in enumerate(specs):
+        shapes = {n: None for n in IP.name_templates(cfg["num_layers"])}
+        sd = {}
+        for n in shapes:
+            if "image_embeds.weight" in n:
+                shape = (tokens * cross, embed_dim)
+            elif "image_embeds.bias" in n:
+                shape = (tokens * cross,)
+            elif ".norm." in n:
+                shape = (cross,)
+            else:
+                shape = (d, cross) if n.endswith("weight") else (d,)
+            t = 0.02 * torch.randn(shape, generator=g, device=DEV)
+            sd[n.format(j=0)] = (1.0 + t) if n.endswith("norm.weight") else (t.bfloat16() if len(shape) == 2 else t)
+        m.load_ip_adapter(sd)
+        embeds.append(torch.randn(1, images, embed_dim, generator=g, device=DEV))
+    lat = torch.randn(1, n_img, 64, generator=g, device=DEV)
+    ids = torch.zeros(h2, w2, 3, device=DEV)
+    ids[..., 1] += torch.arange(h2, device=DEV)[:, None]
+    ids[..., 2] += torch.arange(w2, device=DEV)[None, :]
+    kw = dict(encoder_hidden_states=torch.randn(1, txt_len, 4096, generator=g, device=DEV),
+              pooled_projections=torch.randn(1, 768, generator=g, device=DEV), img_ids=ids.reshape(-1, 3),
+              txt_ids=torch.zeros(txt_len, 3, device=DEV), guidance=torch.tensor([3.5], device=DEV), return_dict=False)
+    t = torch.tensor([0.5], device=DEV)
+    joint = dict(ip_adapter_image_embeds=embeds)
+    without = lambda: m(hidden_states=lat, timestep=t, **kw)[0]
+    with_ip = lambda: m(hidden_states=lat, timestep=t, joint_attention_kwargs=joint, **kw)[0]
+    for f in (without, with_ip, without, with_ip):
+        timed(f)
+    ms = {"without": [], "with": []}
+    for _ in range(rounds):
+        ms["without"].append(timed(without, per_round)[0] * 1e3)
+        ms["with"].append(timed(with_ip, per_round)[0] * 1e3)
+    o_with, o_without = with_ip(), without()
+    # set_image: every adapter of the list into slot 1 (the forwards above used slot 0), wall time to completion
+    e = m.engine
+    set_ms = []
+    for _ in range(5):
+        set_ms.append(timed(lambda: [e.set_ip_adapter_image(j, 1, v[0]) for j, v in enumerate(embeds)])[0] * 1e3)
+    # the two launches alone, at the forward's shapes
+    lib = _lib.load()
+    qkv = torch.randn(n_img, 3 * d, generator=g, device=DEV).bfloat16()
+    wq = torch.ones(128, device=DEV)
+    out = torch.empty(n_img, d, device=DEV, dtype=torch.bfloat16)
+    x = torch.zeros(n_img, d, device=DEV)
+    arr = (_lib.McIpKeys * len(specs))()
+    caches = []
+    for j, (tokens, images) in enumerate(specs):
+        keys = tokens * images
+        caches.append(torch.randn(keys, 2 * d, generator=g, device=DEV).bfloat16())
+        arr[j] = _lib.McIpKeys(caches[-1].data_ptr(), 2 * d, keys, 1.0)
+    stream = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    attn = lambda: _lib.check(lib.mc_op_ip_attention(C.c_void_p(qkv.data_ptr()), 3 * d, C.c_void_p(wq.data_ptr()), 1e-6, arr, len(specs),
+                                                     C.c_void_p(out.data_ptr()), d, n_img, heads, stream()))
+    add = lambda: _lib.check(lib.mc_op_add_rows(C.c_void_p(x.data_ptr()), d, C.c_void_p(out.data_ptr()), _lib.MC_BF16, None, 0, None, 0,
+                                                n_img, d, stream()))
+    for f in (attn, add):
+        timed(f, 10)
+    attn_us = [timed(attn, 100)[0] * 1e6 for _ in range(5)]
+    add_us = [timed(add, 100)[0] * 1e6 for _ in range(5)]
+    keys_total = sum(tk * im for tk, im in specs)
+    bytes_attn = n_img * d * 2 * 2 + sum(tk * im for tk, im in specs) * 2 * d * 2      # q in, out; K|V once
+    bytes_add = n_img * d * (2 + 4 + 4)                                                # bf16 source, fp32 read-modify-write
+    print(json.dumps({"config": f"FLUX.1-dev 1024x1024 full forward ({cfg['num_layers']} double + {cfg['num_single_layers']} single blocks), "
+                                f"IP-Adapters (tokens x images) {specs}, synthetic weights/inputs",
+                      "forward_ms_without": float(np.median(ms["without"])), "forward_ms_with": float(np.median(ms["with"])),
+                      "windows_without_ms": [round(v, 3) for v in ms["without"]], "windows_with_ms": [round(v, 3) for v in ms["with"]],
+                      "forwards_per_window": per_round, "set_image_ms": [round(v, 3) for v in set_ms],
+                      "ip_attention_us_per_launch": [round(v, 2) for v in attn_us], "add_rows_us_per_launch": [round(v, 2) for v in add_us],
+                      "ip_attention_bytes": bytes_attn, "add_rows_bytes": bytes_add,
+                      "ip_attention_flop": n_img * heads * keys_total * 512,
+                      "finite": bool(torch.isfinite(o_with).all()),
                       "output_moved_rel_l2": float((o_with - o_without).norm() / o_without.norm())}))
 
 
@@ -411,6 +511,12 @@ if __name__ == "__main__":
         sizes = [tuple(int(v) for v in g.split("x")) for g in sys.argv[sys.argv.index("--regeometry") + 1].split(",")]
         depth = [int(v) for v in sys.argv[sys.argv.index("--depth") + 1].split(",")] if "--depth" in sys.argv else None
         bench_regeometry(which, sizes, depth)
+    elif "--ip-adapter" in sys.argv[2:]:
+        if which != "flux":
+            sys.exit(f"--ip-adapter benches FLUX (IP-Adapters are a FLUX input), not '{which}'")
+        specs = [tuple(int(v) for v in (e + "x1").split("x")[:2]) for e in sys.argv[sys.argv.index("--ip-adapter") + 1].split(",")]
+        depth = [int(v) for v in sys.argv[sys.argv.index("--depth") + 1].split(",")] if "--depth" in sys.argv else None
+        bench_flux_ip_adapter(specs, depth)
     elif "--controlnet" in sys.argv[2:]:
         if which != "flux":
             sys.exit(f"--controlnet benches FLUX (ControlNet residuals are a FLUX input), not '{which}'")
