@@ -530,6 +530,9 @@ mc_status mc_op_ln_modulate(const float* x_dev, long ldx, const void* x0_dev, lo
                             float* out_f32_dev, long ldof, int M, int D, mc_stream stream);
 mc_status mc_op_rmsnorm_rope(void* x_bf16_dev, long ldx, const float* w_dev, float eps, const float* cs_dev,
                              int cs_row0, int M, int D, mc_stream stream);
+/* out = float(x0) + r and r = x - float(x0), one fp32 operation per element.  MC_EINVAL, and nothing launched, for D % 8 != 0,
+ * ldx0 % 8 != 0, an fp32 leading dimension that is no multiple of 4, an x0 that is not 8-byte aligned or an fp32 pointer that
+ * is not 16-byte aligned. */
 mc_status mc_op_skip_add(const void* x0_bf16_dev, long ldx0, const float* r_dev, long ldr, float* out_dev, long ldo,
                          int M, int D, mc_stream stream);
 mc_status mc_op_residual_sub(const float* x_dev, long ldx, const void* x0_bf16_dev, long ldx0, float* r_dev,
@@ -561,7 +564,8 @@ mc_status mc_op_ip_attention(const void* q_bf16_dev, long ldq, const float* wq_d
                              int n_adapters, void* out_bf16_dev, long ldo, int rows, int heads, mc_stream stream);
 /* One launch: per-token ratios + the cross-block reduction by the last block to arrive.  partial_dev: 4*n_blocks + 1
  * doubles of scratch whose LAST 8 bytes (the arrival ticket) must be zero before the first call -- the kernel rearms it;
- * sums_dev: 4 doubles (sum rho, sum rho^2, sum 1-cos, count); stats_dev: 3 floats or NULL */
+ * sums_dev: 4 doubles (sum rho, sum rho^2, sum 1-cos, count); stats_dev: 3 floats or NULL.  MC_EINVAL, and nothing written,
+ * for M < 2, D % 4 != 0, n_blocks < 1, ldr / ldrp shorter than D or no multiple of 4, r_dev / rp_dev not 16-byte aligned. */
 mc_status mc_op_calib_stats(const float* r_dev, long ldr, const float* rp_dev, long ldrp, int M, int D,
                             double* partial_dev, int n_blocks, double* sums_dev, float* stats_dev,
                             mc_stream stream);

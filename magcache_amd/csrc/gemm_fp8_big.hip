@@ -280,7 +280,21 @@ __global__ __launch_bounds__(512, 2) void gemm_fp8_kernel(GemmParams p, int tile
   MC_TILE(2, kt + 1, 1, W2, W0);
 #undef MC_TILE
 
-  // ---- epilogue.  acc[mh][ms][nh][r] = C[m][n], m = m0 + wr*128 + mh*64 + ms*32 + l31,
+  // ---- every MFMA retires HERE, in front of the row guard of the epilogue.  The guard is a divergent branch, and hipcc sank
+  // the last MFMAs of an accumulator into the block that stores it.  An MFMA reads its operands from all 64 lanes whatever
+  // EXEC says, but a fragment register the compiler had spilled was reloaded inside the block, under the block's EXEC: only
+  // in the lanes of rows < M.  With fewer than 32 valid rows in a 32-row block of the last M tile the other lanes fed stale
+  // registers to that MFMA, and one 64-k chunk of half the columns of those rows was wrong (M = 1, 257, 2309 at K = 512;
+  // tests/test_fp8_gemm_rows_gpu.py).  An empty asm that takes each accumulator as an in/out operand costs no instruction
+  // and cannot be crossed by the MFMA that writes it.
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int c = 0; c < 2; ++c) asm volatile("" : "+v"(acc[a][b][c]));
+
+  // ---- epilogue. acc[mh][ms][nh][r] = C[m][n], m = m0 + wr*128 + mh*64 + ms*32 + l31,
   //      n = n0 + wc*64 + nh*32 + (r&3) + 8*(r>>2) + 4*half  -> 4 consecutive n per (r>>2)
 #pragma unroll
   for (int mh = 0; mh < 2; ++mh) {

@@ -183,6 +183,9 @@ __global__ void calib_finalize_kernel(const double* __restrict__ sums, float* __
   if (threadIdx.x == 0 && blockIdx.x == 0) calib_finalize(sums, stats);
 }
 
+// the kernels' vector accesses: 16 bytes of fp32, 8 bytes of bf16 (the row strides are checked beside the pointers)
+inline bool aligned_to(const void* p, uintptr_t bytes) { return ((uintptr_t)p % bytes) == 0; }
+
 inline int grid_for(long total, int block, int cap = 2048) {
   long g = (total + block - 1) / block;
   if (g < 1) g = 1;
@@ -194,6 +197,7 @@ inline int grid_for(long total, int block, int cap = 2048) {
 hipError_t launch_skip_add(const bf16_t* x0, long ldx0, const float* r, long ldr, float* out, long ldo, int M,
                            int D, hipStream_t stream) {
   if ((D % 8) || (ldx0 % 8) || (ldr % 4) || (ldo % 4) || (long)M * (D / 4) >= (1l << 31)) return hipErrorInvalidValue;
+  if (!aligned_to(x0, 8) || !aligned_to(r, 16) || !aligned_to(out, 16)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(skip_add_kernel<false>, dim3(grid_for((long)M * (D / 4), 512, 8192)), dim3(256), 0, stream, x0,
                      ldx0, r, ldr, out, ldo, (uint32_t)M * (uint32_t)(D / 4), (uint32_t)(D / 4));
   return hipGetLastError();
@@ -202,6 +206,7 @@ hipError_t launch_skip_add(const bf16_t* x0, long ldx0, const float* r, long ldr
 hipError_t launch_residual_sub(const float* x, long ldx, const bf16_t* x0, long ldx0, float* r, long ldr, int M,
                                int D, hipStream_t stream) {
   if ((D % 8) || (ldx0 % 8) || (ldr % 4) || (ldx % 4) || (long)M * (D / 4) >= (1l << 31)) return hipErrorInvalidValue;
+  if (!aligned_to(x0, 8) || !aligned_to(x, 16) || !aligned_to(r, 16)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(skip_add_kernel<true>, dim3(grid_for((long)M * (D / 4), 512, 8192)), dim3(256), 0, stream, x0,
                      ldx0, x, ldx, r, ldr, (uint32_t)M * (uint32_t)(D / 4), (uint32_t)(D / 4));
   return hipGetLastError();
@@ -210,6 +215,8 @@ hipError_t launch_residual_sub(const float* x, long ldx, const bf16_t* x0, long 
 hipError_t launch_calib_stats(const float* r, long ldr, const float* rp, long ldrp, int M, int D, double* partial,
                               int n_blocks, double* sums, float* stats, hipStream_t stream) {
   if ((D % 4) || n_blocks <= 0 || M < 2) return hipErrorInvalidValue;
+  // 16-byte loads from every row of both slabs
+  if ((ldr % 4) || (ldrp % 4) || ldr < D || ldrp < D || !aligned_to(r, 16) || !aligned_to(rp, 16)) return hipErrorInvalidValue;
   // the arrival ticket sits behind the 4*n_blocks partial sums (scratch of 4*n_blocks + 1 doubles).  It is zeroed on
   // the stream before EVERY launch (a memset node under capture): a launch that was aborted, or a caller's buffer
   // that was never cleared, can then not leave a stale count that silently disables the last-block reduction.

@@ -293,6 +293,8 @@ hipError_t launch_rmsnorm_rows_bf16(const float* x, long ldx, const float* w, fl
 hipError_t launch_lincomb(const float* const* xs, const float* coef, int k, float* out, size_t n, hipStream_t stream);
 
 // ---------------------------------------------------------------- MagCache ops (magcache_ops.hip)
+// hipErrorInvalidValue, and nothing launched, for D % 8, ldx0 % 8, an fp32 leading dimension % 4, an x0 that is not 8-byte
+// aligned or an fp32 pointer that is not 16-byte aligned (8-byte bf16 and 16-byte fp32 accesses), M * D/4 >= 2^31.
 // out = x0 (bf16) + r (fp32)     -- the skipped-step path (reference :294-295)
 hipError_t launch_skip_add(const bf16_t* x0, long ldx0, const float* r, long ldr, float* out, long ldo, int M,
                            int D, hipStream_t stream);
@@ -302,7 +304,8 @@ hipError_t launch_residual_sub(const float* x, long ldx, const bf16_t* x0, long 
 // calibration statistics (reference :167-169): per token rho = |r|/|rp|, cos; then
 // stats[0]=mean(rho) stats[1]=std(rho, unbiased) stats[2]=mean(1-cos). partial = workspace of
 // 4*n_blocks doubles; sums[4] (double) receives (sum rho, sum rho^2, sum (1-cos), count) for
-// multi-rank reduction.
+// multi-rank reduction.  hipErrorInvalidValue, and nothing launched or written, for M < 2, D % 4, n_blocks < 1, a leading
+// dimension that is shorter than D or no multiple of 4, r / rp not 16-byte aligned (the kernel reads 16 bytes at a time).
 hipError_t launch_calib_stats(const float* r, long ldr, const float* rp, long ldrp, int M, int D, double* partial,
                               int n_blocks, double* sums, float* stats, hipStream_t stream);
 hipError_t launch_calib_finalize(const double* sums, float* stats, hipStream_t stream);

@@ -217,7 +217,7 @@ mc_status mc_op_rmsnorm_rope(void* x, long ldx, const float* w, float eps, const
 mc_status mc_op_skip_add(const void* x0, long ldx0, const float* r, long ldr, float* out, long ldo, int M, int D,
                          mc_stream s) {
   hipError_t err = mc::launch_skip_add((const bf16_t*)x0, ldx0, r, ldr, out, ldo, M, D, (hipStream_t)s);
-  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "skip_add: unsupported shape");
+  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "skip_add: needs D %% 8 == 0, ldx0 %% 8 == 0, ldr/ldo %% 4 == 0, x0 8-byte and r/out 16-byte aligned");
   HIP_TRY(err);
   return MC_OK;
 }
@@ -225,7 +225,7 @@ mc_status mc_op_skip_add(const void* x0, long ldx0, const float* r, long ldr, fl
 mc_status mc_op_residual_sub(const float* x, long ldx, const void* x0, long ldx0, float* r, long ldr, int M, int D,
                              mc_stream s) {
   hipError_t err = mc::launch_residual_sub(x, ldx, (const bf16_t*)x0, ldx0, r, ldr, M, D, (hipStream_t)s);
-  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "residual_sub: unsupported shape");
+  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "residual_sub: needs D %% 8 == 0, ldx0 %% 8 == 0, ldx/ldr %% 4 == 0, x0 8-byte and x/r 16-byte aligned");
   HIP_TRY(err);
   return MC_OK;
 }
@@ -233,7 +233,7 @@ mc_status mc_op_residual_sub(const float* x, long ldx, const void* x0, long ldx0
 mc_status mc_op_calib_stats(const float* r, long ldr, const float* rp, long ldrp, int M, int D, double* partial,
                             int n_blocks, double* sums, float* stats, mc_stream s) {
   hipError_t err = mc::launch_calib_stats(r, ldr, rp, ldrp, M, D, partial, n_blocks, sums, stats, (hipStream_t)s);
-  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "calib_stats: unsupported shape");
+  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "calib_stats: needs M >= 2, D %% 4 == 0, n_blocks >= 1, ldr/ldrp >= D and %% 4 == 0, r/rp 16-byte aligned");
   HIP_TRY(err);
   return MC_OK;
 }

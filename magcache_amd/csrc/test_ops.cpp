@@ -2,7 +2,8 @@
 // ONLY into tests/_ref/libmagcache_hip_ref.so (magcache_amd/build.py: REF_EXTRA) -- libmagcache_hip.so does not contain this
 // file and include/*.h do not declare it.  Every wrapper passes its arguments through unchanged and returns the launcher's
 // hipError_t as an int (hipSuccess = 0, hipErrorInvalidValue = 1): no logic lives here, so what the tests exercise is the
-// launcher's own host checks and the kernel objects (elementwise.hip.o, gemm_mxfp8.hip.o) the shipped library links too.
+// launcher's own host checks and the kernel objects (elementwise.hip.o, gemm_mxfp8.hip.o, gemm_fp8_big.hip.o,
+// magcache_ops.hip.o) the shipped library links too.
 #include "ops.h"
 
 using mc::bf16_t;
@@ -68,6 +69,23 @@ int mc_test_gemm_mxfp8_capture(const void* A, long lda, const void* a_mx, long m
   p.a_mx = (const uint8_t*)a_mx; p.mx_rows_a = mx_rows_a; p.w_mx = (const uint8_t*)w_mx; p.mx_rows_w = mx_rows_w;
   p.X = X; p.ldx = ldx; p.gate = gate; p.X0 = (const bf16_t*)X0; p.ldx0 = ldx0; p.R = R; p.ldr = ldr;
   return (int)mc::launch_gemm_mxfp8(p, mc::EPI_RESID_CAPTURE, (hipStream_t)s);
+}
+
+// EPI_RESID_CAPTURE of launch_gemm_fp8 (per-row / per-channel scales): mc_op_gemm_fp8 has no X0 / R arguments
+int mc_test_gemm_fp8_capture(const void* A, long lda, const float* a_scale, const void* W, long ldw, const float* w_scale,
+                             const float* bias, int M, int N, int K, float* X, long ldx, const float* gate, const void* X0,
+                             long ldx0, float* R, long ldr, void* s) {
+  mc::GemmParams p = {};
+  p.A = (const bf16_t*)A; p.lda = lda; p.W = (const bf16_t*)W; p.ldw = ldw; p.bias = bias;
+  p.M = M; p.N = N; p.K = K;
+  p.a_scale = a_scale; p.w_scale = w_scale;
+  p.X = X; p.ldx = ldx; p.gate = gate; p.X0 = (const bf16_t*)X0; p.ldx0 = ldx0; p.R = R; p.ldr = ldr;
+  return (int)mc::launch_gemm_fp8(p, mc::EPI_RESID_CAPTURE, (hipStream_t)s);
+}
+
+// the finalize launch of the multi-rank calibration path: stats[3] from sums[4] that the caller reduced over the ranks
+int mc_test_calib_finalize(const double* sums, float* stats, void* s) {
+  return (int)mc::launch_calib_finalize(sums, stats, (hipStream_t)s);
 }
 
 int mc_test_token_t_prepare(const float* t, int n_all, int row0, int n_rows, int n_rows_pad, float* t2, unsigned char* sel,

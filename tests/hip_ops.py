@@ -190,15 +190,36 @@ def residual_sub(x, x0, r):
                                  S()))
 
 
-def calib_stats(r, rp, n_blocks=2048):     # 2048 = what both engines launch (32 waves per CU)
+CALIB_SENTINEL = -7.0     # what sums / stats hold where calib_stats did not write them
+
+
+def calib_stats(r, rp, n_blocks=2048, partial=None, want_stats=True, ldr=None, ldrp=None, M=None, D=None, out=None):
+    """-> (stats fp32 [3], sums fp64 [4]) on the host.  n_blocks = 2048 is what both engines launch (32 waves per CU).
+    partial: the caller's scratch of at least 4 * n_blocks + 1 doubles, in any state (the launcher clears the ticket);
+    want_stats=False passes stats = NULL (the launch of a sequence-parallel rank: sums only); ldr / ldrp / M / D override
+    what the tensors say; out = (sums, stats): device tensors to write to instead of fresh ones, which stay readable
+    when the call is refused.  Whatever the call leaves unwritten holds CALIB_SENTINEL."""
     lib = L()
-    # 4 partial sums per block + the arrival ticket, which must be zero before the first launch (the kernel rearms it)
-    partial = torch.zeros(4 * n_blocks + 1, dtype=torch.float64, device=r.device)
-    sums = torch.empty(4, dtype=torch.float64, device=r.device)
-    stats = torch.empty(3, dtype=torch.float32, device=r.device)
-    check(lib.mc_op_calib_stats(P(r), r.stride(0), P(rp), rp.stride(0), r.shape[0], r.shape[1], P(partial), n_blocks,
-                                P(sums), P(stats), S()))
+    if partial is None:
+        # 4 partial sums per block + the arrival ticket
+        partial = torch.zeros(4 * n_blocks + 1, dtype=torch.float64, device=r.device)
+    assert partial.dtype == torch.float64 and partial.numel() >= 4 * n_blocks + 1
+    if out is None:
+        out = (torch.full((4,), CALIB_SENTINEL, dtype=torch.float64, device=r.device),
+               torch.full((3,), CALIB_SENTINEL, dtype=torch.float32, device=r.device))
+    sums, stats = out
+    check(lib.mc_op_calib_stats(P(r), r.stride(0) if ldr is None else ldr, P(rp), rp.stride(0) if ldrp is None else ldrp,
+                                r.shape[0] if M is None else M, r.shape[1] if D is None else D, P(partial), n_blocks,
+                                P(sums), P(stats) if want_stats else None, S()))
     return stats.cpu(), sums.cpu()
+
+
+def calib_finalize(sums):
+    """launch_calib_finalize: stats fp32 [3] (host) from sums fp64 [4] on the device, as a rank of a sequence-parallel
+    group computes them after the all-reduce of the sums"""
+    stats = torch.full((3,), CALIB_SENTINEL, dtype=torch.float32, device=sums.device)
+    T("calib_finalize", P(sums), P(stats), S())
+    return stats.cpu()
 
 
 # ----------------------------------------------------------------------------- test-only entry points (mc_test_*)
@@ -215,6 +236,8 @@ TEST_SIGNATURES = {
     "mc_test_ln_modulate": [_vp, _l, _vp, _l, _vp, _vp, _i, _f, _vp, _l, _vp, _l, _i, _i, _vp, _vp, _vp, _vp],
     "mc_test_ln_modulate_fp8": [_vp, _l, _vp, _vp, _i, _f, _vp, _l, _vp, _vp, _l, _i, _i, _vp, _vp, _vp, _vp],
     "mc_test_gemm_mxfp8_gelu_quant": [_vp, _l, _vp, _l, _vp, _l, _vp, _l, _vp, _i, _i, _i, _vp, _l, _vp, _l, _vp],
+    "mc_test_gemm_fp8_capture": [_vp, _l, _vp, _vp, _l, _vp, _vp, _i, _i, _i, _vp, _l, _vp, _vp, _l, _vp, _l, _vp],
+    "mc_test_calib_finalize": [_vp, _vp, _vp],
     "mc_test_token_t_prepare": [_vp, _i, _i, _i, _i, _vp, _vp, _vp],
     "mc_test_patchify": [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _l, _vp],
     "mc_test_unpatchify": [_vp, _l, _i, _i, _i, _i, _i, _i, _vp, _vp],
@@ -305,6 +328,13 @@ def gemm_mxfp8_gelu_quant(Aq, sa, Wq, sw, bias):
     T("gemm_mxfp8_gelu_quant", P(Aq), Aq.stride(0), P(sa), sa.shape[1], P(Wq), Wq.stride(0), P(sw), sw.shape[1], P(bias), M, N, K,
       P(cq), cq.stride(0), P(cs), rows_pad, S())
     return cq, cs
+
+
+def gemm_fp8_capture(Aq, sa, Wq, sw, bias, X, gate, X0, R):
+    """EPI_RESID_CAPTURE of launch_gemm_fp8: X += gate * bf16(acc * sa * sw + bias), R = X_new - float(X0)"""
+    M, K = Aq.shape
+    T("gemm_fp8_capture", P(Aq), Aq.stride(0), P(sa), P(Wq), Wq.stride(0), P(sw), P(bias), M, Wq.shape[0], K, P(X), X.stride(0),
+      P(gate), P(X0), X0.stride(0), P(R), R.stride(0), S())
 
 
 def token_t_prepare(t, n_all, row0, n_rows, n_rows_pad, t2, sel):
