@@ -118,6 +118,12 @@ const char* mc_version(void);
  *                   (8 waves x 32 rows) otherwise.  3 = attention_v3 everywhere.
  *   "fp8_fused_quant"  1 (default) = with mc_config.fp8_linear the LayerNorm + modulate kernel (and, MX modes, the GELU
  *                   epilogue of FFN-1) write the e4m3 operand of the next GEMM; 0 = separate quantise passes.  Same bits.
+ *   "mx_fp4"        0 (default) | 1.  Read ONCE by mc_create / mc_create_sized; the engine keeps what it read (mc_engine_mx_fp4).
+ *                   1 with mc_config.fp8_linear 2 | 3: the Linears that would hold an MX fp8 copy hold an MXFP4 copy instead
+ *                   (e2m1 elements, the same E8M0 block scales) and run on mc_op_gemm_mxfp4's kernel, their activations
+ *                   quantised to MXFP4 by separate passes (W4A4; no fused FP4 producer).  Coarser than MX fp8; its quality on
+ *                   real weights has not been judged; never a default.  With fp8_linear 0 | 1 it does nothing.  A width the
+ *                   kernel cannot tile (dim or ffn_dim no multiple of 256, or < 512) is MC_EINVAL at mc_create.  Wan engine only.
  *   "mmdit_two_streams"  the text stream of an MM-DiT double block (FLUX / HunyuanVideo) runs on a second HIP stream next
  *                   to the image stream between a fork and a join event.  OPT-IN (default 0 = off): 1 = on, -1 = by shape
  *                   (on when the text half is at least 1/16 of the image half and the engine is not sequence parallel);
@@ -130,6 +136,8 @@ const char* mc_version(void);
  * Used by the parity tests and the A/B micro-benchmarks (tools/kbench.cpp loads several builds of this library side by side:
  * tools/build_v5_variants.py, build_gemm_v2_variants.py). */
 mc_status mc_set_option(const char* key, int value);
+/* the value a key holds now (a caller that sets an option around one call puts the previous value back) */
+mc_status mc_get_option(const char* key, int* value);
 
 /* ---- lifecycle ------------------------------------------------------------------------------ */
 mc_status mc_create(const mc_config* cfg, mc_engine** out);
@@ -140,6 +148,8 @@ mc_status mc_create(const mc_config* cfg, mc_engine** out);
  * mc_op_rope_axes / mc_op_rope_expand; 0.7.1 adds calls only: mc_lora_*, mc_op_lora_merge_f32, mc_op_param_delta); mc_version() names the library's. */
 mc_status mc_create_sized(const mc_config* cfg, size_t cfg_bytes, mc_engine** out);
 void mc_destroy(mc_engine* e);
+/* 1: this engine's quantised Linears are MXFP4 (it was created under mc_set_option("mx_fp4", 1) with fp8_linear 2 | 3); else 0 */
+int mc_engine_mx_fp4(const mc_engine* e);
 size_t mc_workspace_bytes(const mc_engine* e);
 mc_status mc_set_workspace(mc_engine* e, void* ws_dev, size_t bytes);
 /* The latent grid as a property of the call (0.7).  mc_config.latent_f / _h / _w is the grid an engine STARTS with;
@@ -503,6 +513,22 @@ mc_status mc_op_gemm_fp8(const void* A_q_dev, long lda, const float* a_scale_dev
 mc_status mc_op_quantize_rows_mx(const void* x_dev, mc_dtype dtype, long ldx, int M, int K, void* q_dev, long ldq,
                                  void* scales_dev, long rows_pad, mc_stream stream);
 mc_status mc_op_gemm_mxfp8(const void* A_q_dev, long lda, const void* a_scales_dev, long rows_pad_a, const void* W_q_dev,
+                           long ldw, const void* w_scales_dev, long rows_pad_w, const float* bias_dev, int M, int N, int K,
+                           int epi, void* Cb_dev, long ldc, float* X_dev, long ldx, const float* gate_dev,
+                           mc_stream stream);
+/* MXFP4 (OCP microscaling: e2m1 elements -- magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6, bit 3 of a code the sign --, the same E8M0
+ * scale image as MX fp8, both operands FP4 on v_mfma_scale_f32_16x16x128_f8f6f4; the Wan engine's option "mx_fp4").  Two codes
+ * per byte, the EVEN k in the LOW nibble: a row of K elements is K / 2 bytes, and lda / ldw / ldq count BYTES of packed rows.
+ * quantize: e = ceil(log2(max|block| / 6)) (clamped to [-127, 127]; an all-zero block: -127), code = e2m1(x * 2^-e) rounded to
+ * nearest, a tie to the even mantissa; K % 32 == 0, ldx % 8 == 0, ldq % 16 == 0, 16-byte aligned pointers, rows_pad >= M
+ * rounded up to 64.  gemm: M > 0 (any), N % 256 == 0, K a multiple of 256 ELEMENTS and >= 512, lda / ldw % 16 == 0 and
+ * >= K / 2, 16-byte aligned operands, rows_pad_a >= M rounded up to 256, rows_pad_w >= N, both multiples of 64; no byte of A
+ * behind row M - 1 is read, scale bytes are read up to rows_pad_a's first ceil256(M) rows, rows >= M of every output stay
+ * untouched.  Epilogues MC_EPI_BF16, _GELU_BF16, _RESID_GATE, _F32 (as mc_op_gemm_mxfp8).  Anything else: MC_EINVAL, and
+ * nothing is launched or written. */
+mc_status mc_op_quantize_rows_mxfp4(const void* x_dev, mc_dtype dtype, long ldx, int M, int K, void* q_dev, long ldq,
+                                    void* scales_dev, long rows_pad, mc_stream stream);
+mc_status mc_op_gemm_mxfp4(const void* A_q_dev, long lda, const void* a_scales_dev, long rows_pad_a, const void* W_q_dev,
                            long ldw, const void* w_scales_dev, long rows_pad_w, const float* bias_dev, int M, int N, int K,
                            int epi, void* Cb_dev, long ldc, float* X_dev, long ldx, const float* gate_dev,
                            mc_stream stream);

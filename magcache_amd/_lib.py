@@ -46,6 +46,8 @@ SIGNATURES = {
     "mc_last_error": (C.c_char_p, []),
     "mc_version": (C.c_char_p, []),
     "mc_set_option": (_i, [C.c_char_p, _i]),
+    "mc_get_option": (_i, [C.c_char_p, C.POINTER(_i)]),
+    "mc_engine_mx_fp4": (_i, [_vp]),
     "mc_create": (_i, [C.POINTER(McConfig), C.POINTER(_vp)]),
     "mc_create_sized": (_i, [C.POINTER(McConfig), _sz, C.POINTER(_vp)]),
     "mc_destroy": (None, [_vp]),
@@ -114,6 +116,8 @@ SIGNATURES = {
     "mc_op_gemm_fp8": (_i, [_vp, _l, _vp, _vp, _l, _vp, _vp, _i, _i, _i, _i, _vp, _l, _vp, _l, _vp, _vp]),
     "mc_op_quantize_rows_mx": (_i, [_vp, _i, _l, _i, _i, _vp, _l, _vp, _l, _vp]),
     "mc_op_gemm_mxfp8": (_i, [_vp, _l, _vp, _l, _vp, _l, _vp, _l, _vp, _i, _i, _i, _i, _vp, _l, _vp, _l, _vp, _vp]),
+    "mc_op_quantize_rows_mxfp4": (_i, [_vp, _i, _l, _i, _i, _vp, _l, _vp, _l, _vp]),
+    "mc_op_gemm_mxfp4": (_i, [_vp, _l, _vp, _l, _vp, _l, _vp, _l, _vp, _i, _i, _i, _i, _vp, _l, _vp, _l, _vp, _vp]),
     "mc_op_attention_partial": (_i, [_vp, _l, _vp, _l, _l, _vp, _l, _l, _vp, _l, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp]),
     "mc_op_attn_merge": (_i, [_vp, _vp, _i, _vp, _l, _i, _i, _i, _vp]),
     "mc_op_ln_modulate": (_i, [_vp, _l, _vp, _l, _vp, _vp, _i, _f, _vp, _l, _vp, _l, _i, _i, _vp]),

@@ -1,10 +1,10 @@
 // The shared skeleton of the 8-wave 256x256 LDS-DMA GEMMs: gemm_bf16_big.hip (bf16, the test-only reference kernel),
-// gemm_fp8_big.hip (per-row-scaled fp8) and gemm_mxfp8.hip (MX fp8).  What the three have in common lives here once; the
+// gemm_fp8_big.hip (per-row-scaled fp8), gemm_mxfp8.hip (MX fp8) and gemm_mxfp4.hip (MXFP4).  What they have in common lives here once; the
 // interval schedules, wait counts, fragment structs, MFMAs and epilogues differ and stay with each kernel.
 //
 // Geometry
 //   * workgroup = 8 waves (2 along M x 4 along N), one 256x256 output tile; wave tile 128(M) x 64(N).
-//   * a K tile is 128 BYTES of every row (64 bf16 or 128 fp8), and each operand's K tile is split into two 16 KiB
+//   * a K tile is 128 BYTES of every row (64 bf16, 128 fp8 or 256 fp4), and each operand's K tile is split into two 16 KiB
 //     "halves" by WHEN a wave needs them:
 //        Am0 / Am1 : for each wave row wr, rows wr*128 + [0,64) / [64,128) of the A tile
 //        Wn0 / Wn1 : for each wave col wc, rows wc*64  + [0,32) / [32,64)  of the W tile

@@ -1,6 +1,6 @@
-// The arithmetic of the two fp8 (OCP e4m3) quantisers, defined once.  Every producer of quantised rows -- the stand-alone
+// The arithmetic of the two fp8 (OCP e4m3) quantisers and of the MXFP4 (e2m1) quantiser, defined once.  Every producer of quantised rows -- the stand-alone
 // kernels (quantize_rows_fp8_kernel, quantize_rows_mx_kernel), the fused tails of the LayerNorm + modulate kernel
-// (elementwise.hip) and the EPI_GELU_MXFP8 epilogue (gemm_mxfp8.hip) -- goes through these helpers, so "the same bits as
+// (elementwise.hip), the EPI_GELU_MXFP8 epilogue (gemm_mxfp8.hip) and quantize_rows_mxfp4_kernel (gemm_mxfp4.hip) -- goes through these helpers, so "the same bits as
 // quantising the bf16 row" (ops.h) holds by construction.
 #pragma once
 #include "common.h"
@@ -43,6 +43,40 @@ __device__ __forceinline__ int mx_scale_row(int row) { return MC_MX_SCALE_ROW(ro
 __device__ __forceinline__ int pack4_e4m3(float a, float b, float c, float d, float inv) {
   const int w = __builtin_amdgcn_cvt_pk_fp8_f32(a * inv, b * inv, 0, false);
   return __builtin_amdgcn_cvt_pk_fp8_f32(c * inv, d * inv, w, true);
+}
+
+// ---- MXFP4 (the Wan engine's option "mx_fp4"): OCP e2m1 elements, magnitudes {0, 0.5, 1, 1.5, 2, 3, 4, 6} = codes 0..7, bit
+// 3 the sign, with the MX scale image above: one E8M0 byte e + 127 per 32 consecutive k at s[kb * rows_pad +
+// mx_scale_row(row)].  e = ceil(log2(amax / 6)) clamped to [-127, 127] (6 = the largest e2m1 value, so nothing saturates;
+// an all-zero block gets e = -127 and zeros) -- mx_exponent with 448 replaced by 6.
+// Packing: two codes per byte, the EVEN k in the LOW nibble; a row of K elements is K / 2 bytes.  That is the order the matrix
+// core reads (tools/ubench_mx_probe.cpp: an FP4 operand of v_mfma_scale_f32_16x16x128_f8f6f4 is 16 bytes per lane, nibble i
+// of lane group g is k = 32 g + i, even i in the low nibble of byte i / 2).
+__device__ __forceinline__ int mxfp4_exponent(float amax) {
+  int e = -127;
+  if (amax > 0.f) {
+    int ex;
+    const float f = frexpf(amax * (1.0f / 6.0f), &ex);
+    e = (f == 0.5f) ? ex - 1 : ex;
+    e = max(-127, min(127, e));
+  }
+  return e;
+}
+// one value times the inverse scale -> its e2m1 code, round to nearest, a tie to the even mantissa (= the even code: 0.25 -> 0,
+// 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4); the sign bit is x's own (a negative that rounds to zero is -0).
+// Coded, not v_cvt_scalef32_pk_fp4_f32: its rounding has not been probed in this project.  The product is exact (a power of two).
+__device__ __forceinline__ uint32_t e2m1_code(float x, float inv) {
+  const float a = fabsf(x * inv);
+  const uint32_t mag = (uint32_t)(a > 0.25f) + (uint32_t)(a >= 0.75f) + (uint32_t)(a > 1.25f) + (uint32_t)(a >= 1.75f) +
+                       (uint32_t)(a > 2.5f) + (uint32_t)(a >= 3.5f) + (uint32_t)(a > 5.0f);
+  return mag | ((__float_as_uint(x) >> 28) & 8u);
+}
+// eight consecutive k times the inverse scale -> one dword of codes, v[0] in the lowest nibble
+__device__ __forceinline__ uint32_t pack8_e2m1(const float* v, float inv) {
+  uint32_t w = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) w |= e2m1_code(v[i], inv) << (4 * i);
+  return w;
 }
 
 }  // namespace mc

@@ -103,7 +103,10 @@ class Engine(EngineHost):
         return parse_wan_lora_state_dict(sd)
 
     def __init__(self, cfg, latent_grid, device="cuda:0", sp_rank=0, sp_size=1, n_branches=2, calibration=False,
-                 sp_phases=False):
+                 sp_phases=False, mx_fp4=False):
+        """mx_fp4: with cfg["fp8_linear"] 2 | 3 the quantised Linears are MXFP4 (W4A4) instead of MX fp8 -- coarser, an
+        opt-in speed / quality experiment, never a default.  The process-wide option "mx_fp4" is set around the create call
+        only and put back; the engine keeps what it read (self.mx_fp4)."""
         if not torch.cuda.is_available():
             raise RuntimeError("magcache_amd.Engine needs a ROCm device; there is no CPU fallback")
         self.lib = _lib.load()
@@ -127,8 +130,16 @@ class Engine(EngineHost):
         self.sharded = sp_size > 1 or bool(sp_phases)     # driven through the phase calls (parallel.SequenceParallelForward)
         self.vace_layers, self.vace_stride = vace_geometry(cfg)
         h = C.c_void_p()
-        check(self.lib.mc_create_sized(C.byref(c), C.sizeof(c), C.byref(h)))
+        prev = C.c_int(0)
+        check(self.lib.mc_get_option(b"mx_fp4", C.byref(prev)))
+        # an explicit request wins; otherwise the process-wide value (MAGCACHE_HIP_OPTIONS=mx_fp4=1) stands
+        check(self.lib.mc_set_option(b"mx_fp4", 1 if (mx_fp4 or cfg.get("mx_fp4")) else prev.value))
+        try:
+            check(self.lib.mc_create_sized(C.byref(c), C.sizeof(c), C.byref(h)))
+        finally:
+            self.lib.mc_set_option(b"mx_fp4", prev.value)
         self.h = h
+        self.mx_fp4 = bool(self.lib.mc_engine_mx_fp4(self.h))
         self._bind(self.lib.mc_workspace_bytes(self.h))
         self.tokens_per_rank = self.seq_len // sp_size
         self.head_stride = (4 * cfg["out_dim"] + 63) // 64 * 64    # row stride of "head_tokens" (fp32 elements)

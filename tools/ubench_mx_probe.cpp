@@ -2,9 +2,14 @@
 // carry, which rows / k blocks a lane's scale byte applies to, what op_sel selects.  One wave; prints PASS / the values.
 // Finding that mattered (last block of the output): the scale of lane group g multiplies k = 32 g .. 32 g + 31, but a
 // lane's 32 bytes are k = 16 g + 0..15 and 64 + 16 g + 0..15 -- the all-ones tests above cannot see that.
+// Second part (probe_fp4, round 12, before gemm_mxfp4.hip): the same instruction with FP4 (e2m1) operands -- the code book, which
+// k nibble i of lane group g carries (against an e4m3 operand with a distinct value at every k: k = 32 g + i, the even i in the
+// low nibble), which lane group's scale byte multiplies it, op_sel, and that only 16 bytes per lane are read
+// (profiles/r12/mx_probe_fp4.log).
 //   hipcc --offload-arch=gfx950 -O2 tools/ubench_mx_probe.cpp -o tools/ubench_mx_probe.bin
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -56,6 +61,145 @@ static void run(Dev& d, const std::vector<unsigned char>& A, const std::vector<u
   CK(hipMemcpy(o, d.out, sizeof(o), hipMemcpyDeviceToHost));
   for (int l = 0; l < 64; ++l)
     for (int r = 0; r < 4; ++r) D[4 * (l >> 4) + r][l & 15] = o[l][r];   // C/D map: col = lane%16, row = 4*(lane/16)+reg
+}
+
+// ---- FP4 (e2m1) operands on the same instruction: cbsz / blgp = 4 declare the first / second operand FP4; such an operand
+// is 16 bytes per lane (the low four dwords of the register argument), two codes per byte.
+template <int FA, int FB, int OPA, int OPB>
+__global__ void k_mx_fmt(const i32x8* a, const i32x8* b, const int* sa, const int* sb, f32x4* out) {
+  const int l = threadIdx.x;
+  f32x4 c = {0.f, 0.f, 0.f, 0.f};
+  c = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a[l], b[l], c, FA, FB, OPA, sa[l], OPB, sb[l]);
+  out[l] = c;
+}
+
+template <int FA, int FB, int OPA, int OPB>
+static void run_fmt(Dev& d, const std::vector<unsigned char>& A, const std::vector<unsigned char>& B, const std::vector<int>& SA,
+                    const std::vector<int>& SB, float D[16][16]) {
+  CK(hipMemcpy(d.a, A.data(), 2048, hipMemcpyHostToDevice));
+  CK(hipMemcpy(d.b, B.data(), 2048, hipMemcpyHostToDevice));
+  CK(hipMemcpy(d.sa, SA.data(), 256, hipMemcpyHostToDevice));
+  CK(hipMemcpy(d.sb, SB.data(), 256, hipMemcpyHostToDevice));
+  k_mx_fmt<FA, FB, OPA, OPB><<<1, 64>>>((i32x8*)d.a, (i32x8*)d.b, d.sa, d.sb, d.out);
+  CK(hipDeviceSynchronize());
+  float o[64][4];
+  CK(hipMemcpy(o, d.out, sizeof(o), hipMemcpyDeviceToHost));
+  for (int l = 0; l < 64; ++l)
+    for (int r = 0; r < 4; ++r) D[4 * (l >> 4) + r][l & 15] = o[l][r];
+}
+
+// e4m3 byte of the k-th of 128 distinct values: magnitudes 2^-6 .. (codes 0x08 + k / 2, all normal), sign = k & 1
+static unsigned char e4m3_tag(int k) { return (unsigned char)((0x08 + (k >> 1)) | ((k & 1) << 7)); }
+static float e4m3_value(unsigned char c) {
+  const int e = (c >> 3) & 15, m = c & 7;
+  const float v = (e ? (1.f + m / 8.f) * ldexpf(1.f, e - 7) : (m / 8.f) * ldexpf(1.f, -6));
+  return (c & 0x80) ? -v : v;
+}
+// the k (in the order the e4m3 probe above established: lane group g, byte p -> k = 16 g + p, 64 + 16 g + p - 16) of an
+// e4m3 operand's (lane group, byte)
+static int e4m3_k(int g, int p) { return p < 16 ? 16 * g + p : 64 + 16 * g + (p - 16); }
+
+static void probe_fp4(Dev& d) {
+  float D[16][16];
+  std::vector<int> S1(64, 127);
+  printf("---- FP4 (e2m1) operands\n");
+  // every code of the code book against e4m3 1.0: first operand FP4 (cbsz = 4), second e4m3
+  {
+    std::vector<unsigned char> B(2048, ONE);
+    printf("code book (one code in lane 3, low nibble of byte 0): ");
+    for (int c = 0; c < 16; ++c) {
+      std::vector<unsigned char> A(2048, 0);
+      A[3 * 32] = (unsigned char)c;
+      run_fmt<4, 0, 0, 0>(d, A, B, S1, S1, D);
+      printf("%g ", D[3][0]);
+    }
+    printf("\n");
+  }
+  // which k does nibble i of lane group g carry?  FP4 one-hot (code 2 = 1.0) in the first operand, row 3; the second
+  // operand is e4m3 with a distinct value at every k of column 5
+  int map_a[4][32], map_b[4][32];
+  for (int which = 0; which < 2; ++which)
+    for (int g = 0; g < 4; ++g)
+      for (int i = 0; i < 32; ++i) {
+        std::vector<unsigned char> F(2048, 0), E(2048, 0);
+        const int frow = which == 0 ? 3 : 5, erow = which == 0 ? 5 : 3;
+        F[(16 * g + frow) * 32 + i / 2] = (unsigned char)(2 << (4 * (i & 1)));
+        for (int g2 = 0; g2 < 4; ++g2)
+          for (int p = 0; p < 32; ++p) E[(16 * g2 + erow) * 32 + p] = e4m3_tag(e4m3_k(g2, p));
+        if (which == 0) run_fmt<4, 0, 0, 0>(d, F, E, S1, S1, D);
+        else run_fmt<0, 4, 0, 0>(d, E, F, S1, S1, D);
+        int k = -1;
+        for (int kk = 0; kk < 128; ++kk)
+          if (e4m3_value(e4m3_tag(kk)) == D[3][5]) k = kk;
+        (which == 0 ? map_a : map_b)[g][i] = k;
+      }
+  for (int which = 0; which < 2; ++which) {
+    bool consecutive = true;
+    for (int g = 0; g < 4; ++g)
+      for (int i = 0; i < 32; ++i) consecutive &= (which == 0 ? map_a : map_b)[g][i] == 32 * g + i;
+    printf("%s operand FP4: k of nibble i (even i = low nibble of byte i / 2) of lane group g = 32 g + i: %s\n",
+           which == 0 ? "first" : "second", consecutive ? "PASS" : "NO");
+    if (!consecutive)
+      for (int g = 0; g < 4; ++g) {
+        printf("  g %d:", g);
+        for (int i = 0; i < 32; ++i) printf(" %d", (which == 0 ? map_a : map_b)[g][i]);
+        printf("\n");
+      }
+  }
+  // both operands FP4: one-hot against one-hot, same (g, i) must meet and no other
+  {
+    int bad = 0;
+    for (int g = 0; g < 4; ++g)
+      for (int i : {0, 1, 2, 15, 16, 30, 31}) {
+        std::vector<unsigned char> A(2048, 0), B(2048, 0);
+        A[(16 * g + 3) * 32 + i / 2] = (unsigned char)(4 << (4 * (i & 1)));   // 2.0
+        for (int g2 = 0; g2 < 4; ++g2)
+          for (int b = 0; b < 16; ++b) B[(16 * g2 + 5) * 32 + b] = 0x22;      // 1.0 at every k
+        run_fmt<4, 4, 0, 0>(d, A, B, S1, S1, D);
+        if (D[3][5] != 2.f) ++bad;
+        std::fill(B.begin(), B.end(), 0);
+        B[(16 * g + 5) * 32 + i / 2] = (unsigned char)(6 << (4 * (i & 1)));   // 4.0 (code 6)
+        run_fmt<4, 4, 0, 0>(d, A, B, S1, S1, D);
+        if (D[3][5] != 8.f) { ++bad; printf("  FP4 x FP4 (g %d, i %d): D = %g, expected 8\n", g, i, D[3][5]); }
+      }
+    printf("FP4 x FP4: the same (lane group, nibble) of both operands meet: %s\n", bad ? "NO" : "PASS");
+  }
+  // whose scale multiplies nibble i of lane group g?  scale = 2^(lane group), the other operand all ones with unit scales
+  for (int which = 0; which < 2; ++which) {
+    std::vector<int> SG(64);
+    for (int l = 0; l < 64; ++l) SG[l] = 127 + (l >> 4);
+    int bad = 0;
+    for (int g = 0; g < 4; ++g)
+      for (int i = 0; i < 32; ++i) {
+        std::vector<unsigned char> F(2048, 0), O(2048, 0x22);
+        F[(16 * g + (which == 0 ? 3 : 5)) * 32 + i / 2] = (unsigned char)(2 << (4 * (i & 1)));
+        if (which == 0) run_fmt<4, 4, 0, 0>(d, F, O, SG, S1, D);
+        else run_fmt<4, 4, 0, 0>(d, O, F, S1, SG, D);
+        if (D[3][5] != (float)(1 << g)) { ++bad; printf("  operand %d (g %d, i %d): D = %g, expected %d\n", which, g, i, D[3][5], 1 << g); }
+      }
+    printf("%s operand FP4: the scale byte of lane group g multiplies all 32 codes of lane group g: %s\n",
+           which == 0 ? "first" : "second", bad ? "NO" : "PASS");
+  }
+  // the scale follows the lane's row, op_sel picks the byte
+  {
+    std::vector<unsigned char> A(2048, 0x22), B(2048, 0x22);
+    std::vector<int> SR(64), S4(64, 127 | (128 << 8) | (129 << 16) | (130 << 24));
+    for (int l = 0; l < 64; ++l) SR[l] = 127 + (l & 15) % 4;
+    run_fmt<4, 4, 0, 0>(d, A, B, SR, S1, D);
+    printf("FP4 all ones, scaleA = 2^((lane%%16)%%4): D[i][0] i = 0..4: %g %g %g %g %g (expect 128 256 512 1024 128)\n", D[0][0], D[1][0],
+           D[2][0], D[3][0], D[4][0]);
+    run_fmt<4, 4, 0, 0>(d, A, B, S1, SR, D);
+    printf("FP4 all ones, scaleB = 2^((lane%%16)%%4): D[0][j] j = 0..4: %g %g %g %g %g\n", D[0][0], D[0][1], D[0][2], D[0][3], D[0][4]);
+    run_fmt<4, 4, 3, 0>(d, A, B, S4, S1, D);
+    printf("FP4 op_sel A = 3: D[0][0] = %g (expect 1024)\n", D[0][0]);
+    run_fmt<4, 4, 0, 2>(d, A, B, S1, S4, D);
+    printf("FP4 op_sel B = 2: D[0][0] = %g (expect 512)\n", D[0][0]);
+    // the high four dwords of an FP4 operand register are ignored
+    for (int l = 0; l < 64; ++l)
+      for (int b = 16; b < 32; ++b) A[l * 32 + b] = 0x77, B[l * 32 + b] = 0x77;
+    run_fmt<4, 4, 0, 0>(d, A, B, S1, S1, D);
+    printf("FP4 all ones, bytes 16..31 of every lane = 0x77: D[0][0] = %g (expect 128: only 16 bytes per lane are read)\n", D[0][0]);
+  }
 }
 
 int main() {
@@ -150,5 +294,6 @@ int main() {
     run(d, A1, B1, SA, SB, D);
     printf("B one-hot in lane group %d, scaleB = 2^(lane group): D[0][5] = %g\n", kb, D[0][5]);
   }
+  probe_fp4(d);
   return 0;
 }
