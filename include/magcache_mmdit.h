@@ -76,7 +76,8 @@ typedef struct {
                                The embedders, the modulation, the HunyuanVideo token refiner and the head stay bf16.
                                An optional speed / quality mode, one GPU (sp_size 1), dim >= 512; an fp8
                                engine runs its blocks on one stream whatever "mmdit_two_streams" says.  1 (the Wan
-                               engine's per-row scales) has no MM-DiT path: MC_EINVAL, as is any other value. */
+                               engine's per-row scales) has no MM-DiT path: MC_EINVAL, as is any other value.
+                               The process option "mx_fp4" turns the MX copies of modes 2 | 3 into MXFP4 (see mc_mmdit_mx_fp4). */
 } mc_mmdit_config;
 
 /* mc_mmdit_config only ever grows at its END, and a zero in a new field keeps the behaviour older callers had.
@@ -88,6 +89,17 @@ mc_status mc_mmdit_create(const mc_mmdit_config* cfg, mc_mmdit** out);
 mc_status mc_mmdit_create_sized(const mc_mmdit_config* cfg, size_t cfg_bytes, mc_mmdit** out);
 void mc_mmdit_destroy(mc_mmdit* e);
 size_t mc_mmdit_workspace_bytes(const mc_mmdit* e);
+/* Option "mx_fp4" (mc_set_option, 0 | 1; default 0): read ONCE by mc_mmdit_create / _create_sized, like mc_create reads it, and
+ * kept by the engine whatever the option is set to afterwards.  With fp8_linear 2 | 3 the same Linears hold an MXFP4 copy (W4A4:
+ * OCP e2m1 elements, two per byte, with the E8M0 block scales of the MX path) and run on the MXFP4 matrix-core GEMM; their
+ * activations reach the workspace buffer "aq" as packed e2m1 rows of 5 dim / 2 bytes (column c at byte c / 2, "a_mx"
+ * unchanged), written by the FP4 tail of the LayerNorm kernel and the GELU epilogue of MLP-in (option "fp8_fused_quant" 1, the
+ * default) or by separate quantise passes (0): the same bits either way.  With fp8_linear 0 the option does nothing.  dim must
+ * be a multiple of 256 and >= 512 (an even head count; MC_EINVAL names the Linear), sp_size 1.  mc_mmdit_config does not change.
+ * MXFP4 is much coarser than MX fp8 (2e-1 .. 3e-1 relative L2 from the fp32 model on synthetic weights against
+ * 5e-2 .. 7e-2); it is an opt-in speed / quality experiment, not judged on real weights, never a default.
+ * mc_mmdit_mx_fp4: 1 when this engine's MX Linears are MXFP4, else 0. */
+int mc_mmdit_mx_fp4(const mc_mmdit* e);
 mc_status mc_mmdit_set_workspace(mc_mmdit* e, void* ws_dev, size_t bytes);
 mc_status mc_mmdit_buffer_info(const mc_mmdit* e, const char* name, size_t* offset, size_t* bytes);
 

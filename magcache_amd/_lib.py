@@ -150,6 +150,7 @@ SIGNATURES = {
     "mc_mmdit_create_sized": (_i, [_vp, _sz, C.POINTER(_vp)]),
     "mc_mmdit_destroy": (None, [_vp]),
     "mc_mmdit_workspace_bytes": (_sz, [_vp]),
+    "mc_mmdit_mx_fp4": (_i, [_vp]),
     "mc_mmdit_set_workspace": (_i, [_vp, _vp, _sz]),
     "mc_mmdit_buffer_info": (_i, [_vp, C.c_char_p, C.POINTER(_sz), C.POINTER(_sz)]),
     "mc_mmdit_geometry_bytes": (_i, [_vp, _i, _i, _i, _i, _i, C.POINTER(_sz)]),

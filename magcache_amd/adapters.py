@@ -158,6 +158,19 @@ class EngineHost(LoraHost):
     def _release(self):
         pass
 
+    def _create_latching_mx_fp4(self, create, mx_fp4, query):
+        """Run create() (which makes the handle and returns it) with the process-wide option "mx_fp4" set around that call
+        only: an explicit request wins, otherwise the process-wide value (MAGCACHE_HIP_OPTIONS=mx_fp4=1) stands; the previous
+        value is put back.  The engine keeps what it read: self.mx_fp4 = `query`(handle)."""
+        prev = C.c_int(0)
+        check(self.lib.mc_get_option(b"mx_fp4", C.byref(prev)))
+        check(self.lib.mc_set_option(b"mx_fp4", 1 if mx_fp4 else prev.value))
+        try:
+            self.h = create()
+        finally:
+            self.lib.mc_set_option(b"mx_fp4", prev.value)
+        self.mx_fp4 = bool(getattr(self.lib, query)(self.h))
+
     def _bind(self, nbytes):
         """a zeroed workspace of `nbytes` (at least the current plan), bound with <_abi>set_workspace; the tensor it replaces
         is let go after a device synchronise (forwards in flight may still use it)"""

@@ -18,8 +18,9 @@ namespace {
 // ------------------------------------------------------------------ LayerNorm (+ modulate / affine)
 // one wave per row; lane holds NV float4 (row element e = i*256 + lane*4 + j)
 // QM (fp8 Linear modes of the engine): 0 = bf16 / fp32 rows out; 1 = the row leaves as OCP e4m3 with one scale per row;
-// 2 = as e4m3 with one E8M0 scale per 32 elements (MX).  Both quantise the bf16-ROUNDED row with the arithmetic
-// quantize_rows_fp8_kernel / quantize_rows_mx_kernel apply to the bf16 row this kernel otherwise writes (quant.h): the same bits
+// 2 = as e4m3 with one E8M0 scale per 32 elements (MX); 3 = as packed e2m1 codes with the same scale image (MXFP4, q rows of
+// D / 2 bytes).  All quantise the bf16-ROUNDED row with the arithmetic quantize_rows_fp8_kernel / quantize_rows_mx_kernel /
+// quantize_rows_mxfp4_kernel apply to the bf16 row this kernel otherwise writes (quant.h): the same bits
 // without the 2-byte row ever reaching memory (round 4: drops one pass over the activations per fp8 GEMM).
 struct LnQuantOut {
   uint8_t* q;       // [M, ldq] e4m3
@@ -123,6 +124,21 @@ MC_NO_PK_F32 __global__ __launch_bounds__(256) void ln_modulate_kernel(const flo
       const float inv = mx_inv_scale(ex);
       *(int*)(qo.q + (size_t)row * qo.ldq + i * 256 + lane * 4) =
           pack4_e4m3(v[i][0], v[i][1], v[i][2], v[i][3], inv);
+      if ((lane & 7) == 0)
+        qo.mx[(size_t)(i * 8 + (lane >> 3)) * qo.mx_rows + mx_scale_row(row)] = mx_scale_byte(ex);
+    }
+  }
+  if constexpr (QM == 3) {   // MXFP4: the same blocks; a lane's four codes are 16 bits, an even lane stores its pair's dword
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      float amax = fmaxf(fmaxf(fabsf(v[i][0]), fabsf(v[i][1])), fmaxf(fabsf(v[i][2]), fabsf(v[i][3])));
+      amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
+      amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
+      amax = fmaxf(amax, __shfl_xor(amax, 4, 64));
+      const int ex = mxfp4_exponent(amax);
+      const uint32_t w = pack4_e2m1(v[i][0], v[i][1], v[i][2], v[i][3], mx_inv_scale(ex));
+      const uint32_t hi = __shfl_xor(w, 1, 64);   // every lane of the wave is here: the row is the wave's
+      if ((lane & 1) == 0) *(uint32_t*)(qo.q + (size_t)row * qo.ldq + i * 128 + lane * 2) = w | (hi << 16);
       if ((lane & 7) == 0)
         qo.mx[(size_t)(i * 8 + (lane >> 3)) * qo.mx_rows + mx_scale_row(row)] = mx_scale_byte(ex);
     }
@@ -742,6 +758,15 @@ hipError_t launch_ln_modulate_fp8(const float* x, long ldx, const float* sc, con
     return launch_ln_t<2>(x, ldx, nullptr, 0, sc, sh, mode, eps, nullptr, 0, nullptr, 0, M, D, stream, sc2, sh2, sel, qo);
   }
   return launch_ln_t<1>(x, ldx, nullptr, 0, sc, sh, mode, eps, nullptr, 0, nullptr, 0, M, D, stream, sc2, sh2, sel, qo);
+}
+
+hipError_t launch_ln_modulate_mxfp4(const float* x, long ldx, const float* sc, const float* sh, int mode, float eps, uint8_t* q,
+                                    long ldq, uint8_t* mx, long mx_rows, int M, int D, hipStream_t stream, const float* sc2,
+                                    const float* sh2, const uint8_t* sel) {
+  if (!q || !mx || ((uintptr_t)q & 3) != 0 || (ldq % 16) != 0 || ldq < D / 2 || (mx_rows % 64) != 0 || mx_rows < ((M + 63) / 64) * 64)
+    return hipErrorInvalidValue;
+  const LnQuantOut qo{q, ldq, nullptr, mx, mx_rows};
+  return launch_ln_t<3>(x, ldx, nullptr, 0, sc, sh, mode, eps, nullptr, 0, nullptr, 0, M, D, stream, sc2, sh2, sel, qo);
 }
 
 hipError_t launch_rmsnorm_rope(bf16_t* x, long ldx, const float* w, float eps, const float* cs, int cs_row0,

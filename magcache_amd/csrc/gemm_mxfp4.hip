@@ -1,9 +1,9 @@
 // MXFP4 block-scaled GEMM for gfx950 on v_mfma_scale_f32_16x16x128_f8f6f4 with both operands declared FP4 (cbsz:4 blgp:4):
 //   C[M,N] = sum over 32-element K blocks kb of 2^(sa[m][kb] - 127) 2^(sw[n][kb] - 127) (A_q[m, kb] . W_q[n, kb])
-//            (+ the fused epilogues of gemm_epilogue.h, the fused-quantising GELU excepted)
+//            (+ the fused epilogues of gemm_epilogue.h, and EPI_GELU_MXFP4: GELU rows leave as the next MXFP4 GEMM's A operand)
 // A_q, W_q: OCP e2m1 codes, two per byte, K contiguous, the even k in the low nibble (a row of K elements is K / 2 bytes; lda /
 // ldw count bytes); sa, sw: E8M0 scale bytes, one per (row, 32 consecutive k), in the scale image of the MX fp8 GEMM:
-// block-major, s[kb * rows_pad + mx_scale_row(row)] (quant.h).  W4A4: an OPTIONAL mode of the Wan engine (option "mx_fp4" on
+// block-major, s[kb * rows_pad + mx_scale_row(row)] (quant.h).  W4A4: an OPTIONAL mode of both engines (option "mx_fp4" on
 // top of mc_config.fp8_linear = 2 | 3), coarser than MX fp8, never a default.
 //
 // What the instruction does with FP4 operands was probed on the hardware first (tools/ubench_mx_probe.cpp,
@@ -329,12 +329,45 @@ __global__ __launch_bounds__(512, 2) void gemm_mxfp4_kernel(GemmParams p, int ti
       if (m >= p.M) continue;
 #pragma unroll
       for (int nh = 0; nh < 2; ++nh) {
+        if constexpr (EPI == EPI_GELU_MXFP4) {
+          // The 32 columns n0 + wc*64 + nh*32 .. +31 of row m are ONE block of the next GEMM's A operand (the position of
+          // EPI_GELU_MXFP8 in gemm_mxfp8.hip): 2 x 4 consecutive columns in this lane (nb = 0, 1), the rest in the lanes ^ 16
+          // and ^ 32 -- same l15 = same row, so they skip rows m >= M together and every shuffle stays among active lanes.
+          // Values as the bf16 epilogue would store them; exponent, codes and scale row by quant.h.  A lane's codes are 16
+          // bits per nb at byte nb * 8 + 2 kgrp of the block's 16; the pair kgrp ^ 1 trades one half so that each lane stores
+          // ONE dword: an even kgrp the nb = 0 columns of both, an odd kgrp the nb = 1 columns.
+          const int nblk0 = n0 + wc * 64 + nh * 32;
+          float y[8];
+          float amax = 0.f;
+#pragma unroll
+          for (int nb = 0; nb < 2; ++nb) {
+            const int n = nblk0 + nb * 16 + 4 * kgrp;
+            f32x4 b = {0.f, 0.f, 0.f, 0.f};
+            if (p.bias) b = *(const f32x4*)(p.bias + n);
+            const f32x4 val = acc[mh][mb][nh][nb] + b;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              y[4 * nb + i] = bf16_round(gelu_tanh_fast(bf16_round(val[i])));
+              amax = fmaxf(amax, fabsf(y[4 * nb + i]));
+            }
+          }
+          amax = fmaxf(amax, __shfl_xor(amax, 16, 64));
+          amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
+          const int ex = mxfp4_exponent(amax);
+          const float inv = mx_inv_scale(ex);
+          const uint32_t c0 = pack4_e2m1(y[0], y[1], y[2], y[3], inv), c1 = pack4_e2m1(y[4], y[5], y[6], y[7], inv);
+          const uint32_t got = __shfl_xor((kgrp & 1) ? c0 : c1, 16, 64);
+          const uint32_t w = (kgrp & 1) ? (got | (c1 << 16)) : (c0 | (got << 16));
+          *(uint32_t*)(p.Cq + (size_t)m * p.ldcq + (nblk0 >> 1) + (kgrp & 1) * 8 + (kgrp & 2) * 2) = w;
+          if (kgrp == 0) p.c_mx[(size_t)(nblk0 >> 5) * p.mx_rows_c + mx_scale_row(m)] = mx_scale_byte(ex);
+          continue;
+        }
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb) {
           const int n = n0 + wc * 64 + nh * 32 + nb * 16 + 4 * kgrp;
           f32x4 b = {0.f, 0.f, 0.f, 0.f};
           if (p.bias) b = *(const f32x4*)(p.bias + n);
-          gemm_epilogue_quad<EPI>(p, m, n, acc[mh][mb][nh][nb] + b);
+          if constexpr (EPI != EPI_GELU_MXFP4) gemm_epilogue_quad<EPI>(p, m, n, acc[mh][mb][nh][nb] + b);
         }
       }
     }
@@ -405,7 +438,12 @@ hipError_t launch_gemm_mxfp4(const GemmParams& p, int epi, hipStream_t stream) {
     case EPI_RESID_GATE: return p.X ? launch_mx4_t<EPI_RESID_GATE>(p, stream) : hipErrorInvalidValue;
     case EPI_RESID_CAPTURE: return p.X ? launch_mx4_t<EPI_RESID_CAPTURE>(p, stream) : hipErrorInvalidValue;
     case EPI_F32: return p.X ? launch_mx4_t<EPI_F32>(p, stream) : hipErrorInvalidValue;
-    default: return hipErrorInvalidValue;   // EPI_GELU_MXFP8 included: no fused FP4 producer
+    case EPI_GELU_MXFP4:
+      if (!p.Cq || !p.c_mx || ((uintptr_t)p.Cq & 3) != 0 || (p.ldcq % 16) != 0 || p.ldcq < p.N / 2 || (p.mx_rows_c % 64) != 0 ||
+          p.mx_rows_c < (long)((p.M + TB - 1) / TB) * TB)
+        return hipErrorInvalidValue;
+      return launch_mx4_t<EPI_GELU_MXFP4>(p, stream);
+    default: return hipErrorInvalidValue;   // EPI_GELU_MXFP8 included: its bytes are e4m3
   }
 }
 

@@ -36,7 +36,7 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 // mc_set_option values (ops_capi.cpp sets them), each defined in the file that reads it
 extern int g_fp8_fused_quant;    // engine.cpp
 extern int g_sp_attn_partials;   // engine.cpp
-extern int g_mx_fp4;             // engine.cpp: read once by mc_create
+extern int g_mx_fp4;             // engine.cpp: read once by mc_create and by mc_mmdit_create / _create_sized
 extern int g_mmdit_two_streams;  // mmdit_engine.cpp
 
 // ---------------------------------------------------------------- weights

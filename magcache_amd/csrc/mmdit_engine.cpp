@@ -32,6 +32,7 @@
 //   aq   e4m3 [S_pad, 5d]   (fp8_linear != 0 only) the quantised operand rows of the MX Linears, joint row index, columns as
 //                           "am": [0,d) the LayerNorm + modulate output (q|k|v, MLP-in, the single block's linear1) and, mode
 //                           3, the attention output (the output projections); [d,5d) GELU(MLP-in), MLP-out's operand
+//                           (option "mx_fp4": packed e2m1 instead, rows of 5d / 2 bytes, column c at byte c / 2, same order)
 //   a_mx E8M0               (fp8_linear != 0 only) the block scales of "aq".  A scale image is block-major [k / 32][rows_pad]
 //                           with the rows of every group of 64 interleaved RELATIVE TO THE LAUNCH'S FIRST ROW, so two row
 //                           ranges must not share one: three regions, [text | image | joint (the single blocks)], each
@@ -50,6 +51,9 @@
 // fp8_linear 2 / 3 (opt-in): the block Linears that read a LayerNorm or GELU output (3: the attention output too) keep an
 // e4m3 copy with MX block scales and run on launch_gemm_mxfp8 over the exact rows of ONE range (the kernel guards a partial
 // last tile and has no row-split launch): a double block is then one pass per stream, in row order, on the launch stream.
+// Option "mx_fp4" (read once by the create call, opt-in, W4A4): the same Linears hold an MXFP4 copy and run on
+// launch_gemm_mxfp4; "aq" holds packed e2m1 rows, written by the FP4 tail of the LayerNorm kernel and the EPI_GELU_MXFP4
+// epilogue (fp8_fused_quant 1) or by launch_quantize_rows_mxfp4 (0, and the attention output): the same bits either way.
 #include <cmath>
 #include <memory>
 
@@ -113,6 +117,7 @@ struct mc_mmdit {
   int branch = 0;                                            // CFG branch of the forward in progress (Qwen-Image: 0 / 1)
   bool begun = false;
   int fp8 = 0;                                               // cfg.fp8_linear: 0 | 2 | 3
+  bool mx_fp4 = false;   // option "mx_fp4" as the create call read it (with fp8_linear 2 | 3): the MX Linears and "aq" are MXFP4
   // optional second compute stream: the text stream of a double block next to the image stream (mc_set_option
   // "mmdit_two_streams"); a ring of event pairs so that an event is not re-recorded while an earlier wait on it may
   // still be queued
@@ -162,7 +167,8 @@ struct mc_mmdit {
 
 namespace {
 
-// The e4m3 rows [M, k_in] an MX Linear reads, with their scale image (rows_pad >= ceil256(M) rows per k block)
+// The e4m3 rows [M, k_in] an MX Linear reads (ld bytes apart; MXFP4: packed e2m1 rows of k_in / 2 bytes), with their scale
+// image (rows_pad >= ceil256(M) rows per k block)
 struct MxRows {
   const uint8_t* q; long ld;
   const uint8_t* mx; long rows_pad;
@@ -183,6 +189,11 @@ mc_status linear(const mc_mmdit* e, const Linear& l, int M, const bf16_t* A, lon
     p.M = M; p.N = out.count; p.K = l.k_in; p.bias = l.b + out.first;
     p.A = (const bf16_t*)a8->q; p.lda = a8->ld; p.W = (const bf16_t*)(l.q + (size_t)out.first * l.k_in); p.ldw = l.k_in;
     p.a_mx = a8->mx; p.mx_rows_a = a8->rows_pad; p.w_mx = l.mx + out.first; p.mx_rows_w = l.n_out;   // block-major: [k / 32][n_out]
+    if (l.fp4) {   // packed rows of k_in / 2 bytes
+      p.W = (const bf16_t*)(l.q + (size_t)out.first * l.k_in / 2); p.ldw = l.k_in / 2;
+      HIP_TRY(mc::launch_gemm_mxfp4(p, epi, s));
+      return MC_OK;
+    }
     HIP_TRY(mc::launch_gemm_mxfp8(p, epi, s));
     return MC_OK;
   }
@@ -220,11 +231,15 @@ struct MxDst {
 MxDst mx_at(const mc_mmdit* e, int row0, int rows, int col0, bool o_proj = false) {
   const MxRegion r = mx_region(e, row0, rows);
   const size_t blk = o_proj ? (size_t)5 * e->d / 32 : (size_t)col0 / 32;
-  return {e->buf<uint8_t>("aq") + (size_t)row0 * 5 * e->d + col0, 5L * e->d, r.base + blk * r.rows_pad, r.rows_pad};
+  const int per = e->mx_fp4 ? 2 : 1;   // elements per byte: MXFP4 rows are 5d / 2 bytes, column c at byte c / 2
+  return {e->buf<uint8_t>("aq") + ((size_t)row0 * 5 * e->d + col0) / per, 5L * e->d / per, r.base + blk * r.rows_pad, r.rows_pad};
 }
+// the fused-quantising GELU epilogue of the engine's format
+int gelu_quant_epi(const mc_mmdit* e) { return e->mx_fp4 ? mc::EPI_GELU_MXFP4 : mc::EPI_GELU_MXFP8; }
 // bf16 rows -> their place in "aq" (the separate quantise pass: the attention output, and everything with fp8_fused_quant 0)
 mc_status mx_quantise(const mc_mmdit* e, const bf16_t* rows_bf16, long ld, int rows, int K, const MxDst& to, hipStream_t s) {
-  HIP_TRY(mc::launch_quantize_rows_mx(rows_bf16, nullptr, ld, rows, K, to.q, to.ld, to.mx, to.rows_pad, s));
+  if (e->mx_fp4) HIP_TRY(mc::launch_quantize_rows_mxfp4(rows_bf16, nullptr, ld, rows, K, to.q, to.ld, to.mx, to.rows_pad, s));
+  else HIP_TRY(mc::launch_quantize_rows_mx(rows_bf16, nullptr, ld, rows, K, to.q, to.ld, to.mx, to.rows_pad, s));
   return MC_OK;
 }
 // LayerNorm + modulate of "x" rows [row0, row0 + rows) as the operand of `l`: a bf16 Linear reads "xn"; an MX Linear reads
@@ -237,7 +252,8 @@ mc_status ln_for_linear(const mc_mmdit* e, const Linear& l, int row0, int rows, 
   if (l.mx && mc::g_fp8_fused_quant) {
     const MxDst to = mx_at(e, row0, rows, 0);
     *a8 = to.rows();
-    HIP_TRY(mc::launch_ln_modulate_fp8(x, d, scale, shift, 0, 1e-6f, to.q, to.ld, nullptr, to.mx, to.rows_pad, rows, d, s));
+    if (e->mx_fp4) HIP_TRY(mc::launch_ln_modulate_mxfp4(x, d, scale, shift, 0, 1e-6f, to.q, to.ld, to.mx, to.rows_pad, rows, d, s));
+    else HIP_TRY(mc::launch_ln_modulate_fp8(x, d, scale, shift, 0, 1e-6f, to.q, to.ld, nullptr, to.mx, to.rows_pad, rows, d, s));
     return MC_OK;
   }
   HIP_TRY(mc::launch_ln_modulate(x, d, nullptr, 0, scale, shift, 0, 1e-6f, xn, d, nullptr, 0, rows, d, s));
@@ -353,7 +369,7 @@ void plan_workspace(const mc_mmdit* e, const Rows& r, mc::Workspace& ws) {
   ws.add("calib_sums", 64);
   ws.add("calib_stats", 64);
   if (c.fp8_linear) {   // behind everything else: the plan of a bf16 engine does not change
-    ws.add("aq", Sp * 5 * d);
+    ws.add("aq", e->mx_fp4 ? Sp * 5 * d / 2 : Sp * 5 * d);
     ws.add("a_mx", (5 * d / 32 + (c.fp8_linear == 3 ? d / 32 : 0)) * (Ltp + align_up(Li, 256)) + 5 * d / 32 * Sp);
   }
 }
@@ -421,6 +437,12 @@ static mc_status create_engine(const mc_mmdit_config& c, mc_mmdit** out) {
   const bool qw = c.family == MC_FAMILY_QWEN;
   if (c.family != MC_FAMILY_FLUX && !hy && !qw) return fail(MC_EINVAL, "unknown family %d", c.family);
   if (c.num_heads <= 0 || c.dim != c.num_heads * 128) return fail(MC_EINVAL, "dim must be num_heads * 128 (head_dim 128)");
+  // option "mx_fp4" (latched here, as mc_create latches it): with fp8_linear 2 | 3 the MX copies are MXFP4.  gemm_mxfp4 tiles K
+  // by 256 from 512 up; every such Linear reads dim, 4 dim or 5 dim features, so the first one decides -- refused by name
+  const bool mx_fp4 = mc::g_mx_fp4 != 0 && (c.fp8_linear == 2 || c.fp8_linear == 3);
+  if (mx_fp4 && ((c.dim % 256) != 0 || c.dim < 512))
+    return fail(MC_EINVAL, "mx_fp4: q|k|v / MLP-in (in_features = dim): %d input features are no multiple of 256 >= 512 (the K tile of "
+                           "the MXFP4 GEMM; MLP-out reads 4 dim, a single block's linear2 5 dim)", c.dim);
   if ((c.dim % 256) != 0) return fail(MC_EINVAL, "dim %d must be a multiple of 256", c.dim);
   if (c.n_double < 0 || c.n_single < 0 || c.n_double + c.n_single == 0) return fail(MC_EINVAL, "no blocks");
   if (c.txt_dim <= 0 || (c.txt_dim % 64) != 0 || (!qw && (c.vec_dim <= 0 || (c.vec_dim % 8) != 0)))
@@ -447,6 +469,7 @@ static mc_status create_engine(const mc_mmdit_config& c, mc_mmdit** out) {
   mc_mmdit* e = own.get();
   e->cfg = c;
   e->fp8 = c.fp8_linear;
+  e->mx_fp4 = mx_fp4;
   e->P = P;
   e->rank = c.sp_rank;
   e->d = c.dim; e->H = c.num_heads;
@@ -461,8 +484,9 @@ static mc_status create_engine(const mc_mmdit_config& c, mc_mmdit** out) {
   // fp8_linear only decides which Linears keep an e4m3 copy with MX block scales: 2 = those that read a LayerNorm or GELU
   // output, 3 = those that read the attention output too.  The embedders, the modulation matrix, the token refiner and the
   // head stay bf16.
-  const mc::Quant q_big = c.fp8_linear >= 2 ? mc::QUANT_MX : mc::QUANT_NONE;
-  const mc::Quant q_out = c.fp8_linear == 3 ? mc::QUANT_MX : mc::QUANT_NONE;
+  const mc::Quant q_mx = mx_fp4 ? mc::QUANT_MXFP4 : mc::QUANT_MX;
+  const mc::Quant q_big = c.fp8_linear >= 2 ? q_mx : mc::QUANT_NONE;
+  const mc::Quant q_out = c.fp8_linear == 3 ? q_mx : mc::QUANT_NONE;
   auto vec128 = [&](float*& v, const std::string& name) { return W.add_f32(v, name, 128); };   // a per-head norm weight
   auto mlp2 = [&](Mlp2& m, size_t k_in, const std::string& l1, const std::string& l2) {
     MC_TRY(W.add_linear(m.l1, l1, {{"", d}}, k_in));
@@ -591,6 +615,8 @@ void mc_mmdit_destroy(mc_mmdit* e) {
 }
 
 size_t mc_mmdit_workspace_bytes(const mc_mmdit* e) { return e ? e->work.need : 0; }
+
+int mc_mmdit_mx_fp4(const mc_mmdit* e) { return e && e->mx_fp4 ? 1 : 0; }
 
 mc_status mc_mmdit_set_workspace(mc_mmdit* e, void* ws_dev, size_t bytes) {
   if (!e) return fail(MC_EINVAL, "null argument");
@@ -912,11 +938,11 @@ mc_status double_post(const mc_mmdit* e, const Range* r, int n, hipStream_t s, f
       a_f2 = to.rows();
       if (r[i].w->fc1.mx && mc::g_fp8_fused_quant) {
         f1.Cq = to.q; f1.ldcq = to.ld; f1.c_mx = to.mx; f1.mx_rows_c = to.rows_pad;
-        epi_f1 = mc::EPI_GELU_MXFP8;
+        epi_f1 = gelu_quant_epi(e);
       }
     }
     MC_TRY(linear(e, r[i].w->fc1, r[i].rows, xn + (size_t)r[i].row0 * d, d, f1, epi_f1, s, nullptr, 0, nullptr, &a_f1));
-    if (r[i].w->fc2.mx && epi_f1 != mc::EPI_GELU_MXFP8) {
+    if (r[i].w->fc2.mx && epi_f1 == mc::EPI_GELU_BF16) {
       const MxDst to = mx_at(e, r[i].row0, r[i].rows, d);
       MC_TRY(mx_quantise(e, am + (size_t)r[i].row0 * 5 * d + d, 5 * d, r[i].rows, 4 * d, to, s));
     }
@@ -1300,7 +1326,7 @@ mc_status mc_mmdit_block_pre(mc_mmdit* e, int blk, mc_stream stream_) {
       if (g.out.mx && mc::g_fp8_fused_quant) {
         const MxDst to = mx_at(e, 0, S, d);
         f.Cq = to.q; f.ldcq = to.ld; f.c_mx = to.mx; f.mx_rows_c = to.rows_pad;
-        epi = mc::EPI_GELU_MXFP8;
+        epi = gelu_quant_epi(e);
       }
       MC_TRY(linear(e, g.in, S, nullptr, 0, f, epi, s, nullptr, 0, nullptr, &a8, {3 * d, 4 * d}));
     } else {

@@ -27,6 +27,9 @@ enum GemmEpi {
   EPI_SPLITK_PARTIAL = 9,// (internal, gemm_bf16_v2 split-K) the fp32 accumulators of one K slice of a tile -> splitk_ws
   EPI_GELU_MXFP8 = 8,    // as 1, then MX-quantised in the epilogue: Cq = e4m3 bytes, c_mx = E8M0 block scales -- the A
                          // operand of the next MX GEMM, the bits launch_quantize_rows_mx would make of Cb (gemm_mxfp8 only)
+  EPI_GELU_MXFP4 = 13,   // as 1, then MXFP4-quantised in the epilogue: Cq = packed e2m1 codes (column n at byte n / 2), c_mx =
+                         // E8M0 block scales -- the A operand of the next MXFP4 GEMM, the bits launch_quantize_rows_mxfp4 would
+                         // make of Cb (gemm_mxfp4 only)
 };
 
 struct GemmParams {
@@ -63,7 +66,8 @@ struct GemmParams {
   // block-major: scale of (row, k block kb of 32) at [kb * mx_rows + mx_scale_row(row)] (quant.h)
   const uint8_t* a_mx; long mx_rows_a;
   const uint8_t* w_mx; long mx_rows_w;
-  // EPI_GELU_MXFP8: e4m3 output rows (ldcq bytes) and their block scales, c_mx[(n / 32) * mx_rows_c + mx_scale_row(m)] (quant.h)
+  // EPI_GELU_MXFP8: e4m3 output rows (ldcq bytes) and their block scales, c_mx[(n / 32) * mx_rows_c + mx_scale_row(m)] (quant.h);
+  // EPI_GELU_MXFP4: packed e2m1 output rows, Cq[m * ldcq + n / 2], the same scale image
   uint8_t* Cq; long ldcq;
   uint8_t* c_mx; long mx_rows_c;
 };
@@ -109,7 +113,8 @@ hipError_t launch_quantize_rows_mx(const bf16_t* x, const float* x_f32, long ldx
 
 // MXFP4 (gemm_mxfp4.hip): the same instruction with both operands e2m1, two codes per byte (the even k in the low nibble; lda /
 // ldw / ldq in BYTES of packed rows), the scale image of the MX fp8 path.  M > 0 (the row contract of launch_gemm_mxfp8),
-// N % 256 == 0, K % 256 == 0 elements, K >= 512; the epilogues of gemm_epilogue.h except EPI_GELU_MXFP8.
+// N % 256 == 0, K % 256 == 0 elements, K >= 512; the epilogues of gemm_epilogue.h and EPI_GELU_MXFP4 (ldcq in bytes, % 16 == 0
+// and >= N / 2, mx_rows_c % 64 == 0 and >= ceil256(M); rows m >= M store nothing); EPI_GELU_MXFP8 is refused.
 hipError_t launch_gemm_mxfp4(const GemmParams& p, int epi, hipStream_t stream);
 bool gemm_mxfp4_supported(const GemmParams& p);
 // codes e2m1(x * 2^-e), e = ceil(log2(max|block| / 6)), scale byte e + 127 at s[kb * rows_pad + mx_scale_row(m)] (quant.h)
@@ -198,6 +203,11 @@ hipError_t launch_ln_modulate_fp8(const float* x, long ldx, const float* sc, con
                                   uint8_t* q, long ldq, float* row_scale, uint8_t* mx, long mx_rows, int M, int D,
                                   hipStream_t stream, const float* sc2 = nullptr, const float* sh2 = nullptr,
                                   const uint8_t* sel = nullptr);
+// The same row as MXFP4: packed e2m1 codes q[m, d / 2] (ldq in bytes, % 16 == 0, >= D / 2) and one E8M0 scale per 32 elements in
+// mx (mx_rows % 64 == 0, >= ceil64(M)) -- bit-identical to launch_quantize_rows_mxfp4 of the bf16 row launch_ln_modulate writes.
+hipError_t launch_ln_modulate_mxfp4(const float* x, long ldx, const float* sc, const float* sh, int mode, float eps, uint8_t* q,
+                                    long ldq, uint8_t* mx, long mx_rows, int M, int D, hipStream_t stream,
+                                    const float* sc2 = nullptr, const float* sh2 = nullptr, const uint8_t* sel = nullptr);
 // Wan2.2 TI2V per-token timesteps (at most two distinct values per forward): t2[0] = max, t2[1] = min of t[0, n_all);
 // sel[i] = 1 where t[row0 + i] == min and min != max (rows >= n_rows: 0); t2[2] = number of tokens that are neither
 hipError_t launch_token_t_prepare(const float* t, int n_all, int row0, int n_rows, int n_rows_pad, float* t2, uint8_t* sel,

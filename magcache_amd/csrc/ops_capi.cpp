@@ -442,7 +442,7 @@ mc_status mc_set_option(const char* key, int value) {
     if (value != 0 && value != 1) return fail(MC_EINVAL, "fp8_fused_quant must be 0 (separate quantise passes) or 1 (fused into the producers)");
     mc::g_fp8_fused_quant = value;
   } else if (k == "mx_fp4") {
-    if (value != 0 && value != 1) return fail(MC_EINVAL, "mx_fp4 must be 0 (MX fp8 Linears) or 1 (MXFP4 Linears where fp8_linear is 2 or 3; Wan engine)");
+    if (value != 0 && value != 1) return fail(MC_EINVAL, "mx_fp4 must be 0 (MX fp8 Linears) or 1 (MXFP4 Linears where fp8_linear is 2 or 3; read when an engine is created)");
     mc::g_mx_fp4 = value;
   } else if (k == "attn_kernel") {
     if (value != 0 && value != 3 && value != 5)

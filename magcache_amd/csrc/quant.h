@@ -1,6 +1,6 @@
 // The arithmetic of the two fp8 (OCP e4m3) quantisers and of the MXFP4 (e2m1) quantiser, defined once.  Every producer of quantised rows -- the stand-alone
 // kernels (quantize_rows_fp8_kernel, quantize_rows_mx_kernel), the fused tails of the LayerNorm + modulate kernel
-// (elementwise.hip), the EPI_GELU_MXFP8 epilogue (gemm_mxfp8.hip) and quantize_rows_mxfp4_kernel (gemm_mxfp4.hip) -- goes through these helpers, so "the same bits as
+// (elementwise.hip), the EPI_GELU_MXFP8 / EPI_GELU_MXFP4 epilogues (gemm_mxfp8.hip, gemm_mxfp4.hip) and quantize_rows_mxfp4_kernel (gemm_mxfp4.hip) -- goes through these helpers, so "the same bits as
 // quantising the bf16 row" (ops.h) holds by construction.
 #pragma once
 #include "common.h"
@@ -45,7 +45,7 @@ __device__ __forceinline__ int pack4_e4m3(float a, float b, float c, float d, fl
   return __builtin_amdgcn_cvt_pk_fp8_f32(c * inv, d * inv, w, true);
 }
 
-// ---- MXFP4 (the Wan engine's option "mx_fp4"): OCP e2m1 elements, magnitudes {0, 0.5, 1, 1.5, 2, 3, 4, 6} = codes 0..7, bit
+// ---- MXFP4 (both engines' option "mx_fp4"): OCP e2m1 elements, magnitudes {0, 0.5, 1, 1.5, 2, 3, 4, 6} = codes 0..7, bit
 // 3 the sign, with the MX scale image above: one E8M0 byte e + 127 per 32 consecutive k at s[kb * rows_pad +
 // mx_scale_row(row)].  e = ceil(log2(amax / 6)) clamped to [-127, 127] (6 = the largest e2m1 value, so nothing saturates;
 // an all-zero block gets e = -127 and zeros) -- mx_exponent with 448 replaced by 6.
@@ -77,6 +77,11 @@ __device__ __forceinline__ uint32_t pack8_e2m1(const float* v, float inv) {
 #pragma unroll
   for (int i = 0; i < 8; ++i) w |= e2m1_code(v[i], inv) << (4 * i);
   return w;
+}
+// four consecutive k (the first one even) -> 16 bits of codes, a in the lowest nibble: the packing width of the fused producers,
+// whose lanes own four consecutive columns (the LayerNorm tail of elementwise.hip, the EPI_GELU_MXFP4 epilogue of gemm_mxfp4.hip)
+__device__ __forceinline__ uint32_t pack4_e2m1(float a, float b, float c, float d, float inv) {
+  return e2m1_code(a, inv) | (e2m1_code(b, inv) << 4) | (e2m1_code(c, inv) << 8) | (e2m1_code(d, inv) << 12);
 }
 
 }  // namespace mc

@@ -71,6 +71,24 @@ int mc_test_gemm_mxfp8_capture(const void* A, long lda, const void* a_mx, long m
   return (int)mc::launch_gemm_mxfp8(p, mc::EPI_RESID_CAPTURE, (hipStream_t)s);
 }
 
+int mc_test_ln_modulate_mxfp4(const float* x, long ldx, const float* sc, const float* sh, int mode, float eps, unsigned char* q,
+                              long ldq, unsigned char* mx, long mx_rows, int M, int D, const float* sc2, const float* sh2,
+                              const unsigned char* sel, void* s) {
+  return (int)mc::launch_ln_modulate_mxfp4(x, ldx, sc, sh, mode, eps, q, ldq, mx, mx_rows, M, D, (hipStream_t)s, sc2, sh2, sel);
+}
+
+// EPI_GELU_MXFP4: the one epilogue of launch_gemm_mxfp4 that mc_op_gemm_mxfp4 cannot name (it has no Cq / c_mx arguments)
+int mc_test_gemm_mxfp4_gelu_quant(const void* A, long lda, const void* a_mx, long mx_rows_a, const void* W, long ldw,
+                                  const void* w_mx, long mx_rows_w, const float* bias, int M, int N, int K, void* Cq, long ldcq,
+                                  void* c_mx, long mx_rows_c, void* s) {
+  mc::GemmParams p = {};
+  p.A = (const bf16_t*)A; p.lda = lda; p.W = (const bf16_t*)W; p.ldw = ldw; p.bias = bias;
+  p.M = M; p.N = N; p.K = K;
+  p.a_mx = (const uint8_t*)a_mx; p.mx_rows_a = mx_rows_a; p.w_mx = (const uint8_t*)w_mx; p.mx_rows_w = mx_rows_w;
+  p.Cq = (uint8_t*)Cq; p.ldcq = ldcq; p.c_mx = (uint8_t*)c_mx; p.mx_rows_c = mx_rows_c;
+  return (int)mc::launch_gemm_mxfp4(p, mc::EPI_GELU_MXFP4, (hipStream_t)s);
+}
+
 // EPI_RESID_CAPTURE of launch_gemm_mxfp4: mc_op_gemm_mxfp4 has no X0 / R arguments
 int mc_test_gemm_mxfp4_capture(const void* A, long lda, const void* a_mx, long mx_rows_a, const void* W, long ldw,
                                const void* w_mx, long mx_rows_w, const float* bias, int M, int N, int K, float* X, long ldx,

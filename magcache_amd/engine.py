@@ -129,17 +129,12 @@ class Engine(EngineHost):
         self.sp_rank, self.sp_size, self.n_branches = sp_rank, sp_size, n_branches
         self.sharded = sp_size > 1 or bool(sp_phases)     # driven through the phase calls (parallel.SequenceParallelForward)
         self.vace_layers, self.vace_stride = vace_geometry(cfg)
-        h = C.c_void_p()
-        prev = C.c_int(0)
-        check(self.lib.mc_get_option(b"mx_fp4", C.byref(prev)))
-        # an explicit request wins; otherwise the process-wide value (MAGCACHE_HIP_OPTIONS=mx_fp4=1) stands
-        check(self.lib.mc_set_option(b"mx_fp4", 1 if (mx_fp4 or cfg.get("mx_fp4")) else prev.value))
-        try:
+
+        def create():
+            h = C.c_void_p()
             check(self.lib.mc_create_sized(C.byref(c), C.sizeof(c), C.byref(h)))
-        finally:
-            self.lib.mc_set_option(b"mx_fp4", prev.value)
-        self.h = h
-        self.mx_fp4 = bool(self.lib.mc_engine_mx_fp4(self.h))
+            return h
+        self._create_latching_mx_fp4(create, mx_fp4 or cfg.get("mx_fp4"), "mc_engine_mx_fp4")
         self._bind(self.lib.mc_workspace_bytes(self.h))
         self.tokens_per_rank = self.seq_len // sp_size
         self.head_stride = (4 * cfg["out_dim"] + 63) // 64 * 64    # row stride of "head_tokens" (fp32 elements)

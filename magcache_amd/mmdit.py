@@ -53,8 +53,11 @@ class MMDiTEngine(EngineHost):
 
     def __init__(self, family, dim, num_heads, n_double, n_single, in_channels, out_channels, txt_dim, txt_len, vec_dim,
                  img_tokens, latent_grid=(0, 0, 0), refiner_depth=0, calibration=False, device="cuda:0", sp_rank=0,
-                 sp_size=1, fp8_linear=0):
-        """fp8_linear: 0 bf16 Linears; 2 / 3 the opt-in MX fp8 modes of mc_mmdit_config.fp8_linear (one GPU, dim >= 512)"""
+                 sp_size=1, fp8_linear=0, mx_fp4=False):
+        """fp8_linear: 0 bf16 Linears; 2 / 3 the opt-in MX fp8 modes of mc_mmdit_config.fp8_linear (one GPU, dim >= 512).
+        mx_fp4: with fp8_linear 2 | 3 those Linears are MXFP4 (W4A4) instead -- much coarser, an opt-in speed /
+        quality experiment, never a default; dim a multiple of 256.  The process-wide option "mx_fp4" is set around the create
+        call only and put back; the engine keeps what it read (self.mx_fp4)."""
         if not torch.cuda.is_available():
             raise RuntimeError("magcache_amd.MMDiTEngine needs a ROCm device; there is no CPU fallback")
         self.lib = _lib.load()
@@ -70,9 +73,12 @@ class MMDiTEngine(EngineHost):
                           vec_dim=vec_dim, img_tokens=img_tokens, latent_f=latent_grid[0], latent_h=latent_grid[1],
                           latent_w=latent_grid[2], refiner_depth=refiner_depth, calibration=int(calibration),
                           sp_rank=sp_rank, sp_size=sp_size, fp8_linear=int(fp8_linear))
-        h = C.c_void_p()
-        check(self.lib.mc_mmdit_create_sized(C.byref(c), C.sizeof(c), C.byref(h)))
-        self.h = h
+
+        def create():
+            h = C.c_void_p()
+            check(self.lib.mc_mmdit_create_sized(C.byref(c), C.sizeof(c), C.byref(h)))
+            return h
+        self._create_latching_mx_fp4(create, mx_fp4, "mc_mmdit_mx_fp4")
         self._bind(self.lib.mc_mmdit_workspace_bytes(self.h))
         self._rope_key = None
         self._controlnet = None
@@ -379,7 +385,7 @@ class FluxTransformer2DModelHIP(_LoraMethods):
     dynamic_geometry = False
 
     def __init__(self, cfg, img_tokens, txt_len=512, device="cuda:0", calibration=True, engine=None, sp_rank=0,
-                 sp_size=1, sp_group=None, dynamic_geometry=False, fp8_linear=0):
+                 sp_size=1, sp_group=None, dynamic_geometry=False, fp8_linear=0, mx_fp4=False):
         self.config = SimpleNamespace(**cfg)
         self.cfg = dict(cfg)
         dim = cfg["attention_head_dim"] * cfg["num_attention_heads"]
@@ -390,7 +396,7 @@ class FluxTransformer2DModelHIP(_LoraMethods):
                                             cfg["num_single_layers"], cfg["in_channels"], cfg["in_channels"],
                                             cfg["joint_attention_dim"], txt_len, cfg["pooled_projection_dim"], img_tokens,
                                             calibration=calibration, device=device, sp_rank=sp_rank, sp_size=sp_size,
-                                            fp8_linear=fp8_linear)
+                                            fp8_linear=fp8_linear, mx_fp4=mx_fp4)
         self.device = self.engine.device
         self.sp_group = sp_group
         self._ids_key = None
@@ -595,7 +601,7 @@ class HYVideoDiffusionTransformerHIP(_LoraMethods):
     dynamic_geometry = False
 
     def __init__(self, cfg, latent_grid, txt_len=256, device="cuda:0", calibration=True, engine=None, sp_rank=0,
-                 sp_size=1, sp_group=None, dynamic_geometry=False, fp8_linear=0):
+                 sp_size=1, sp_group=None, dynamic_geometry=False, fp8_linear=0, mx_fp4=False):
         self.cfg = dict(cfg)
         self.sp_group = sp_group
         self.dynamic_geometry = dynamic_geometry
@@ -612,7 +618,7 @@ class HYVideoDiffusionTransformerHIP(_LoraMethods):
                                             cfg["out_channels"], cfg["text_states_dim"], txt_len, cfg["text_states_dim_2"],
                                             self.img_tokens, latent_grid=self.latent_grid, refiner_depth=2,
                                             calibration=calibration, device=device, sp_rank=sp_rank, sp_size=sp_size,
-                                            fp8_linear=fp8_linear)
+                                            fp8_linear=fp8_linear, mx_fp4=mx_fp4)
         self.device = self.engine.device
 
     def load_state_dict(self, sd):
@@ -746,7 +752,7 @@ class QwenImageTransformer2DModelHIP(_LoraMethods):
     dynamic_geometry = False
 
     def __init__(self, cfg, img_tokens, txt_len=1024, device="cuda:0", calibration=True, engine=None, sp_size=1,
-                 dynamic_geometry=False, fp8_linear=0):
+                 dynamic_geometry=False, fp8_linear=0, mx_fp4=False):
         self.config = SimpleNamespace(**cfg)
         self.cfg = dict(cfg)
         self.dynamic_geometry = dynamic_geometry
@@ -756,7 +762,7 @@ class QwenImageTransformer2DModelHIP(_LoraMethods):
         self.inner_dim, self.img_tokens, self.txt_len, self.out_features = dim, img_tokens, txt_len, out
         self.engine = engine or MMDiTEngine(MC_FAMILY_QWEN, dim, cfg["num_attention_heads"], cfg["num_layers"], 0,
                                             cfg["in_channels"], out, cfg["joint_attention_dim"], txt_len, 0, img_tokens,
-                                            calibration=calibration, device=device, sp_size=sp_size, fp8_linear=fp8_linear)
+                                            calibration=calibration, device=device, sp_size=sp_size, fp8_linear=fp8_linear, mx_fp4=mx_fp4)
         self.device = self.engine.device
         self._shapes_key = None
 

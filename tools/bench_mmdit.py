@@ -19,6 +19,9 @@ headline bench line):
                                           one engine per mc_mmdit_config.fp8_linear mode on the same weights and inputs, full
                                           forwards in alternating windows: ms per forward and the spread of the windows per mode,
                                           workspace bytes, distance of every mode's output from the first mode's
+                                          `--mx_fp4` adds, per mode 2 | 3 of the list, an MXFP4 engine (option "mx_fp4": W4A4,
+                                          opt-in) as "<mode>+mxfp4" and the same engine with fp8_fused_quant 0 (separate quantise
+                                          passes instead of the fused FP4 producers) as "<mode>+mxfp4 separate"
 
     python tools/bench_mmdit.py flux --ip-adapter TOKENS[xIMAGES][,...] [--depth D,S]
                                           FLUX.1-dev 1024x1024, one full forward with one IP-Adapter per entry (768-wide embeds,
@@ -431,29 +434,37 @@ def bench_regeometry(which, sizes, depth=None, rounds=7, per_round=4):
                       "switch_without_reserve": no_reserve, "per_size": res}))
 
 
-def bench_fp8(which, sizes, modes, depth=None, rounds=5, per_round=3, txt_len=512):
+def bench_fp8(which, sizes, modes, depth=None, rounds=5, per_round=3, txt_len=512, mx_fp4=False):
     """`sizes`: [(width, height)] in pixels; image tokens (H/16) * (W/16).  One engine per fp8_linear mode of `modes` (the same
     seeded weights: an fp8 engine quantises them as it takes them), switched from size to size with set_geometry; engine-level
     full forwards.  Per size, windows of `per_round` forwards alternate between the modes after a warm-up of each; host clock
-    around a device synchronise.  One JSON line per size."""
+    around a device synchronise.  One JSON line per size.  mx_fp4: the variants "<mode>+mxfp4" (an MXFP4 engine of mode 2 | 3) and
+    "<mode>+mxfp4 separate" (the same engine under fp8_fused_quant 0) join the table, keyed by those labels."""
+    from magcache_amd._lib import check
     from magcache_amd.qwen_bench import random_state_dict
+    lib = load()
     flux = which == "flux"
     cfg = dict(MM.FLUX_DEV if flux else MM.QWEN_IMAGE)
     if depth:
         cfg.update(num_layers=depth[0], **({"num_single_layers": depth[1]} if flux else {}))
     grids = [(h // 16, w // 16) for w, h in sizes]
-    engines = {}
-    for mode in modes:
+    engines, fused = {}, {}
+    variants = [(mode, mode, False) for mode in modes] + [(f"{mode}+mxfp4", mode, True) for mode in modes if mx_fp4 and mode in (2, 3)]
+    for label, mode, fp4 in variants:
         n0 = grids[0][0] * grids[0][1]
         if flux:
-            m = MM.FluxTransformer2DModelHIP(cfg, n0, txt_len=txt_len, device=DEV, calibration=False, fp8_linear=mode)
+            m = MM.FluxTransformer2DModelHIP(cfg, n0, txt_len=txt_len, device=DEV, calibration=False, fp8_linear=mode, mx_fp4=fp4)
             synth_load(m, flux_names(cfg))
         else:
-            m = MM.QwenImageTransformer2DModelHIP(cfg, n0, txt_len=txt_len, device=DEV, calibration=False, fp8_linear=mode)
+            m = MM.QwenImageTransformer2DModelHIP(cfg, n0, txt_len=txt_len, device=DEV, calibration=False, fp8_linear=mode, mx_fp4=fp4)
             m.engine.load_weights(random_state_dict(cfg, DEV))
-        engines[mode] = m.engine
+        assert m.engine.mx_fp4 is fp4
+        engines[label], fused[label] = m.engine, 1
+        if fp4:
+            engines[label + " separate"], fused[label + " separate"] = m.engine, 0
         torch.cuda.synchronize()
         torch.cuda.empty_cache()
+    modes = list(engines)
     for size, (h2, w2) in zip(sizes, grids):
         g = torch.Generator(device=DEV).manual_seed(h2 * 1000 + w2)
         img = torch.randn(h2 * w2, 64, generator=g, device=DEV)
@@ -465,11 +476,18 @@ def bench_fp8(which, sizes, modes, depth=None, rounds=5, per_round=3, txt_len=51
             vec, rope = torch.randn(768, generator=g, device=DEV), MM.flux_rope(ids)
         else:
             vec, rope = None, MM.qwen_rope([(1, h2, w2)], txt_len)
-        for e in engines.values():
-            e.set_geometry(h2 * w2, (0, 0, 0), txt_len)
-            e.set_rope(*rope)
-        fwd = {mode: (lambda e=e: e.forward(img, 500.0, 3500.0, txt, txt_len, vec, branch=None if flux else 0))
-               for mode, e in engines.items()}
+        for label, e in engines.items():
+            if fused[label]:          # a "separate" variant is its fused twin's engine
+                e.set_geometry(h2 * w2, (0, 0, 0), txt_len)
+                e.set_rope(*rope)
+
+        def forward(e, fq):
+            check(lib.mc_set_option(b"fp8_fused_quant", fq))       # read by every launch of the forward; 1 is the default
+            try:
+                return e.forward(img, 500.0, 3500.0, txt, txt_len, vec, branch=None if flux else 0)
+            finally:
+                check(lib.mc_set_option(b"fp8_fused_quant", 1))
+        fwd = {mode: (lambda e=e, fq=fused[mode]: forward(e, fq)) for mode, e in engines.items()}
         outs = {mode: timed(fwd[mode], 2)[1].clone() for mode in modes}
         ms = {mode: [] for mode in modes}
         for _ in range(rounds):
@@ -485,7 +503,7 @@ def bench_fp8(which, sizes, modes, depth=None, rounds=5, per_round=3, txt_len=51
                                                    "windows_ms": [round(v, 3) for v in ms[mode]],
                                                    "workspace_bytes": engines[mode].geometry_bytes(h2 * w2, (0, 0, 0), txt_len),
                                                    "finite": bool(torch.isfinite(outs[mode]).all()),
-                                                   "rel_l2_vs_mode_%d" % modes[0]: float((outs[mode] - base).norm() / base.norm())}
+                                                   "rel_l2_vs_mode_%s" % modes[0]: float((outs[mode] - base).norm() / base.norm())}
                                        for mode in modes}}), flush=True)
 
 
@@ -504,7 +522,7 @@ if __name__ == "__main__":
         sizes = [tuple(int(v) for v in g.split("x"))
                  for g in (sys.argv[sys.argv.index("--size") + 1] if "--size" in sys.argv else default).split(",")]
         depth = [int(v) for v in sys.argv[sys.argv.index("--depth") + 1].split(",")] if "--depth" in sys.argv else None
-        bench_fp8(which, sizes, modes, depth)
+        bench_fp8(which, sizes, modes, depth, mx_fp4="--mx_fp4" in sys.argv[2:])
     elif "--regeometry" in sys.argv[2:]:
         if which not in ("flux", "qwen"):
             sys.exit(f"--regeometry benches FLUX and Qwen-Image, not '{which}'")
