@@ -124,6 +124,14 @@ const char* mc_version(void);
  *                   quantised to MXFP4 by separate passes (W4A4; no fused FP4 producer).  Coarser than MX fp8; its quality on
  *                   real weights has not been judged; never a default.  With fp8_linear 0 | 1 it does nothing.  A width the
  *                   kernel cannot tile (dim or ffn_dim no multiple of 256, or < 512) is MC_EINVAL at mc_create.  Wan engine only.
+ *   "mx_fp6"        0 (default) | 1.  Read ONCE by mc_create / mc_create_sized and by mc_mmdit_create / _create_sized; the engine
+ *                   keeps what it read (mc_engine_mx_fp6, mc_mmdit_mx_fp6).  1 with fp8_linear 2 | 3: the Linears that would
+ *                   hold an MX fp8 copy hold an MXFP6 copy instead (OCP e2m3 elements -- the three mantissa bits of e4m3 --,
+ *                   packed rows of 3 k / 4 bytes, the same E8M0 block scales) and run on mc_op_gemm_mxfp6's kernel, their
+ *                   activations quantised to MXFP6 by separate passes whatever "fp8_fused_quant" says (W6A6; no fused FP6
+ *                   producer).  Not judged on real weights; never a default.  With fp8_linear 0 | 1 it does nothing.  A
+ *                   width the kernel cannot tile (an in_features that is no multiple of 256, or < 512) is MC_EINVAL at
+ *                   create time, and so is a create with "mx_fp4" and "mx_fp6" both 1.
  *   "mmdit_two_streams"  the text stream of an MM-DiT double block (FLUX / HunyuanVideo) runs on a second HIP stream next
  *                   to the image stream between a fork and a join event.  OPT-IN (default 0 = off): 1 = on, -1 = by shape
  *                   (on when the text half is at least 1/16 of the image half and the engine is not sequence parallel);
@@ -145,11 +153,14 @@ mc_status mc_create(const mc_config* cfg, mc_engine** out);
  * sizeof(mc_config) of THIS header; a caller compiled against an older header (a shorter struct) must call
  * mc_create_sized(cfg, sizeof(mc_config) as IT knows it, out): the missing tail is taken as zeros.  History: 0.1 ends at
  * vace_in_dim, 0.2 adds fp8_linear, 0.3 no_context_cache and no_token_timesteps, 0.5 sp_phases (0.6 adds calls only: mc_pair_begin / mc_pair_end; 0.7 adds calls only: mc_geometry_bytes / mc_set_geometry,
- * mc_op_rope_axes / mc_op_rope_expand; 0.7.1 adds calls only: mc_lora_*, mc_op_lora_merge_f32, mc_op_param_delta); mc_version() names the library's. */
+ * mc_op_rope_axes / mc_op_rope_expand; 0.7.1 adds calls only: mc_lora_*, mc_op_lora_merge_f32, mc_op_param_delta; the MXFP4 and MXFP6 modes add calls only: mc_get_option,
+ * mc_engine_mx_fp4 / _mx_fp6, mc_op_quantize_rows_mxfp4 / _mxfp6, mc_op_gemm_mxfp4 / _mxfp6); mc_version() names the library's. */
 mc_status mc_create_sized(const mc_config* cfg, size_t cfg_bytes, mc_engine** out);
 void mc_destroy(mc_engine* e);
 /* 1: this engine's quantised Linears are MXFP4 (it was created under mc_set_option("mx_fp4", 1) with fp8_linear 2 | 3); else 0 */
 int mc_engine_mx_fp4(const mc_engine* e);
+/* the same for MXFP6 and the option "mx_fp6" (an engine is never both: such a create is MC_EINVAL) */
+int mc_engine_mx_fp6(const mc_engine* e);
 size_t mc_workspace_bytes(const mc_engine* e);
 mc_status mc_set_workspace(mc_engine* e, void* ws_dev, size_t bytes);
 /* The latent grid as a property of the call (0.7).  mc_config.latent_f / _h / _w is the grid an engine STARTS with;
@@ -529,6 +540,24 @@ mc_status mc_op_gemm_mxfp8(const void* A_q_dev, long lda, const void* a_scales_d
 mc_status mc_op_quantize_rows_mxfp4(const void* x_dev, mc_dtype dtype, long ldx, int M, int K, void* q_dev, long ldq,
                                     void* scales_dev, long rows_pad, mc_stream stream);
 mc_status mc_op_gemm_mxfp4(const void* A_q_dev, long lda, const void* a_scales_dev, long rows_pad_a, const void* W_q_dev,
+                           long ldw, const void* w_scales_dev, long rows_pad_w, const float* bias_dev, int M, int N, int K,
+                           int epi, void* Cb_dev, long ldc, float* X_dev, long ldx, const float* gate_dev,
+                           mc_stream stream);
+/* MXFP6 (OCP microscaling: e2m3 elements -- sign, two exponent bits of bias 1, three mantissa bits: magnitudes 0 .. 0.875 by
+ * 0.125, 1 .. 1.875 by 0.125, 2 .. 3.75 by 0.25, 4 .. 7.5 by 0.5, bit 5 of a code the sign --, the same E8M0 scale image as MX
+ * fp8, both operands FP6 on v_mfma_scale_f32_16x16x128_f8f6f4; both engines' option "mx_fp6").  The 32 codes of a block are ONE
+ * little-endian bit stream of 24 bytes: bit b (bit b % 8 of byte b / 8) is bit b % 6 of the code of k = b / 6, so code i starts
+ * at bit 6 i and four codes fill three bytes.  A row of K elements is 3 K / 4 bytes, and lda / ldw / ldq count BYTES of packed
+ * rows.  quantize: e = ceil(log2(max|block| / 7.5)) (clamped to [-127, 127]; an all-zero block: -127), code = e2m3(x * 2^-e)
+ * rounded to nearest, a tie to the even mantissa, the sign bit x's own; any M > 0, K % 32 == 0, ldx % 8 == 0, ldq % 16 == 0 and
+ * >= 3 K / 4, 16-byte aligned pointers, rows_pad >= M rounded up to 64.  gemm: M > 0 (any), N % 256 == 0, K a multiple of 256
+ * ELEMENTS and >= 512, lda / ldw % 16 == 0 and >= 3 K / 4, 16-byte aligned operands, rows_pad_a >= M rounded up to 256,
+ * rows_pad_w >= N, both multiples of 64; no byte of A behind row M - 1 is read, scale bytes are read up to rows_pad_a's first
+ * ceil256(M) rows, rows >= M of every output stay untouched.  Epilogues MC_EPI_BF16, _GELU_BF16, _RESID_GATE, _F32 (as
+ * mc_op_gemm_mxfp8).  Anything else: MC_EINVAL, and nothing is launched or written. */
+mc_status mc_op_quantize_rows_mxfp6(const void* x_dev, mc_dtype dtype, long ldx, int M, int K, void* q_dev, long ldq,
+                                    void* scales_dev, long rows_pad, mc_stream stream);
+mc_status mc_op_gemm_mxfp6(const void* A_q_dev, long lda, const void* a_scales_dev, long rows_pad_a, const void* W_q_dev,
                            long ldw, const void* w_scales_dev, long rows_pad_w, const float* bias_dev, int M, int N, int K,
                            int epi, void* Cb_dev, long ldc, float* X_dev, long ldx, const float* gate_dev,
                            mc_stream stream);

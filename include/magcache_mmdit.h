@@ -100,6 +100,15 @@ size_t mc_mmdit_workspace_bytes(const mc_mmdit* e);
  * 5e-2 .. 7e-2); it is an opt-in speed / quality experiment, not judged on real weights, never a default.
  * mc_mmdit_mx_fp4: 1 when this engine's MX Linears are MXFP4, else 0. */
 int mc_mmdit_mx_fp4(const mc_mmdit* e);
+/* Option "mx_fp6" (mc_set_option, 0 | 1; default 0; magcache_hip.h): latched by mc_mmdit_create / _create_sized in the same way.
+ * With fp8_linear 2 | 3 the same Linears hold an MXFP6 copy (W6A6: OCP e2m3 elements, 32 per 24 bytes, with the E8M0 block
+ * scales of the MX path) and run on the MXFP6 matrix-core GEMM; their activations reach "aq" as packed e2m3 rows of
+ * 5 dim * 3 / 4 bytes (column c in bits 6 (c % 32) .. + 5 of the 24 bytes at 24 (c / 32); "a_mx" unchanged), always written by
+ * separate quantise passes: there is no fused FP6 producer, and "fp8_fused_quant" changes nothing in this mode.  dim a
+ * multiple of 256 and >= 512 (MC_EINVAL names the Linear), sp_size 1, and "mx_fp4" and "mx_fp6" both 1 is MC_EINVAL (the
+ * message names both options).  mc_mmdit_config does not change.  Not judged on real weights, never a default.
+ * mc_mmdit_mx_fp6: 1 when this engine's MX Linears are MXFP6, else 0. */
+int mc_mmdit_mx_fp6(const mc_mmdit* e);
 mc_status mc_mmdit_set_workspace(mc_mmdit* e, void* ws_dev, size_t bytes);
 mc_status mc_mmdit_buffer_info(const mc_mmdit* e, const char* name, size_t* offset, size_t* bytes);
 

@@ -48,6 +48,7 @@ SIGNATURES = {
     "mc_set_option": (_i, [C.c_char_p, _i]),
     "mc_get_option": (_i, [C.c_char_p, C.POINTER(_i)]),
     "mc_engine_mx_fp4": (_i, [_vp]),
+    "mc_engine_mx_fp6": (_i, [_vp]),
     "mc_create": (_i, [C.POINTER(McConfig), C.POINTER(_vp)]),
     "mc_create_sized": (_i, [C.POINTER(McConfig), _sz, C.POINTER(_vp)]),
     "mc_destroy": (None, [_vp]),
@@ -118,6 +119,8 @@ SIGNATURES = {
     "mc_op_gemm_mxfp8": (_i, [_vp, _l, _vp, _l, _vp, _l, _vp, _l, _vp, _i, _i, _i, _i, _vp, _l, _vp, _l, _vp, _vp]),
     "mc_op_quantize_rows_mxfp4": (_i, [_vp, _i, _l, _i, _i, _vp, _l, _vp, _l, _vp]),
     "mc_op_gemm_mxfp4": (_i, [_vp, _l, _vp, _l, _vp, _l, _vp, _l, _vp, _i, _i, _i, _i, _vp, _l, _vp, _l, _vp, _vp]),
+    "mc_op_quantize_rows_mxfp6": (_i, [_vp, _i, _l, _i, _i, _vp, _l, _vp, _l, _vp]),
+    "mc_op_gemm_mxfp6": (_i, [_vp, _l, _vp, _l, _vp, _l, _vp, _l, _vp, _i, _i, _i, _i, _vp, _l, _vp, _l, _vp, _vp]),
     "mc_op_attention_partial": (_i, [_vp, _l, _vp, _l, _l, _vp, _l, _l, _vp, _l, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp]),
     "mc_op_attn_merge": (_i, [_vp, _vp, _i, _vp, _l, _i, _i, _i, _vp]),
     "mc_op_ln_modulate": (_i, [_vp, _l, _vp, _l, _vp, _vp, _i, _f, _vp, _l, _vp, _l, _i, _i, _vp]),
@@ -151,6 +154,7 @@ SIGNATURES = {
     "mc_mmdit_destroy": (None, [_vp]),
     "mc_mmdit_workspace_bytes": (_sz, [_vp]),
     "mc_mmdit_mx_fp4": (_i, [_vp]),
+    "mc_mmdit_mx_fp6": (_i, [_vp]),
     "mc_mmdit_set_workspace": (_i, [_vp, _vp, _sz]),
     "mc_mmdit_buffer_info": (_i, [_vp, C.c_char_p, C.POINTER(_sz), C.POINTER(_sz)]),
     "mc_mmdit_geometry_bytes": (_i, [_vp, _i, _i, _i, _i, _i, C.POINTER(_sz)]),

@@ -158,18 +158,23 @@ class EngineHost(LoraHost):
     def _release(self):
         pass
 
-    def _create_latching_mx_fp4(self, create, mx_fp4, query):
-        """Run create() (which makes the handle and returns it) with the process-wide option "mx_fp4" set around that call
-        only: an explicit request wins, otherwise the process-wide value (MAGCACHE_HIP_OPTIONS=mx_fp4=1) stands; the previous
-        value is put back.  The engine keeps what it read: self.mx_fp4 = `query`(handle)."""
-        prev = C.c_int(0)
-        check(self.lib.mc_get_option(b"mx_fp4", C.byref(prev)))
-        check(self.lib.mc_set_option(b"mx_fp4", 1 if mx_fp4 else prev.value))
+    def _create_latching(self, create, requests, query_prefix):
+        """Run create() (which makes the handle and returns it) with the two process-wide element-format options set around
+        that call only.  requests: {"mx_fp4": bool, "mx_fp6": bool}; for each option an explicit request wins, otherwise the
+        process-wide value (MAGCACHE_HIP_OPTIONS=mx_fp6=1) stands; the previous values are put back.  The engine keeps what it
+        read: self.mx_fp4 / self.mx_fp6 = <query_prefix>mx_fp4 / _mx_fp6 (handle).  Both options at 1 is the library's MC_EINVAL."""
+        prev4, prev6 = C.c_int(0), C.c_int(0)
+        check(self.lib.mc_get_option(b"mx_fp4", C.byref(prev4)))
+        check(self.lib.mc_get_option(b"mx_fp6", C.byref(prev6)))
         try:
+            check(self.lib.mc_set_option(b"mx_fp4", 1 if requests.get("mx_fp4") else prev4.value))
+            check(self.lib.mc_set_option(b"mx_fp6", 1 if requests.get("mx_fp6") else prev6.value))
             self.h = create()
         finally:
-            self.lib.mc_set_option(b"mx_fp4", prev.value)
-        self.mx_fp4 = bool(getattr(self.lib, query)(self.h))
+            self.lib.mc_set_option(b"mx_fp4", prev4.value)
+            self.lib.mc_set_option(b"mx_fp6", prev6.value)
+        self.mx_fp4 = bool(getattr(self.lib, query_prefix + "mx_fp4")(self.h))
+        self.mx_fp6 = bool(getattr(self.lib, query_prefix + "mx_fp6")(self.h))
 
     def _bind(self, nbytes):
         """a zeroed workspace of `nbytes` (at least the current plan), bound with <_abi>set_workspace; the tensor it replaces

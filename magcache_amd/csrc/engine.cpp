@@ -36,6 +36,7 @@ constexpr int kSpMaxParts = 9;   // local shard + 8 gather rounds
 struct mc_engine {
   mc_config cfg;
   bool mx_fp4 = false;   // option "mx_fp4" as mc_create read it (with fp8_linear 2 | 3): the quantised Linears are MXFP4
+  bool mx_fp6 = false;   // option "mx_fp6" likewise: the quantised Linears are MXFP6 (never both)
   int d, ffn, H, NL, L, Lr, Lp, P, rank, tok0, Kp;  // Kp = in_dim*4 padded to 64
   int ctx_rows;                                     // text_len padded to 64
   std::vector<Layer> layers;
@@ -376,6 +377,15 @@ mc_status linear(mc_engine* e, const Linear& l, RowRange out, int M, ActSrc a, m
     HIP_TRY(mc::launch_gemm_mxfp4(p, epi, s));
     return MC_OK;
   }
+  if (l.fp6) {   // MXFP6 (option "mx_fp6"): packed rows of 3 K / 4 bytes on both sides, the scale images of the MX path
+    const long kb = (long)K / 4 * 3;
+    uint8_t* am = a.mx ? a.mx : e->buf<uint8_t>("a_mx");
+    if (!a.quantised) HIP_TRY(mc::launch_quantize_rows_mxfp6(a.rows, nullptr, a.ld, Lp, K, aq, kb, am, (long)Lp, s));
+    p.A = (const bf16_t*)aq; p.lda = kb; p.W = (const bf16_t*)(l.q + (size_t)out.first * kb); p.ldw = kb;
+    p.a_mx = am; p.mx_rows_a = (long)Lp; p.w_mx = l.mx + out.first; p.mx_rows_w = l.n_out;
+    HIP_TRY(mc::launch_gemm_mxfp6(p, epi, s));
+    return MC_OK;
+  }
   p.A = (const bf16_t*)aq; p.lda = K; p.W = (const bf16_t*)(l.q + (size_t)out.first * K); p.ldw = K;
   if (l.mx) {
     uint8_t* am = a.mx ? a.mx : e->buf<uint8_t>("a_mx");
@@ -452,6 +462,8 @@ int g_sp_attn_partials = 1;
 // option "mx_fp4" (0 | 1): read once by mc_create; 1 with fp8_linear 2 | 3 = the MX Linears hold an MXFP4 copy (W4A4,
 // gemm_mxfp4.hip) and their activations are quantised by separate passes.  The engine keeps what it read (mc_engine::mx_fp4).
 int g_mx_fp4 = 0;
+// option "mx_fp6" (0 | 1): the same latch for MXFP6 copies (W6A6, gemm_mxfp6.hip); a create call that finds both at 1 is refused
+int g_mx_fp6 = 0;
 }  // namespace mc
 static int g_n_cu = 0;
 
@@ -514,7 +526,17 @@ mc_status mc_create(const mc_config* cfg, mc_engine** out) {
   // option "mx_fp4" (latched here): the MX copies are MXFP4 instead.  dim and ffn_dim are multiples of 256 and >= 512 by the
   // fp8_linear check above, which is what gemm_mxfp4's K tiling asks of a Linear's k_in; checked again by name so that a
   // width the kernel cannot tile is refused here, never met at a launch
+  if (mc::g_mx_fp4 != 0 && mc::g_mx_fp6 != 0)
+    return fail(MC_EINVAL, "the options \"mx_fp4\" and \"mx_fp6\" are both 1: an engine's MX Linears hold one element format, set one of them");
   e->mx_fp4 = mc::g_mx_fp4 != 0 && c.fp8_linear >= 2;
+  e->mx_fp6 = mc::g_mx_fp6 != 0 && c.fp8_linear >= 2;
+  if (e->mx_fp6) {
+    const struct { const char* name; int k; } widths[] = {{"self_attn.q|k|v / ffn.0 / the dim x dim Linears (in_features = dim)", c.dim},
+                                                          {"ffn.2 (in_features = ffn_dim)", c.ffn_dim}};
+    for (const auto& w : widths)
+      if ((w.k % 256) != 0 || w.k < 512)
+        return fail(MC_EINVAL, "mx_fp6: %s: %d input features are no multiple of 256 >= 512 (the K contract of the MXFP6 GEMM)", w.name, w.k);
+  }
   if (e->mx_fp4) {
     const struct { const char* name; int k; } widths[] = {{"self_attn.q|k|v / ffn.0 / the dim x dim Linears (in_features = dim)", c.dim},
                                                           {"ffn.2 (in_features = ffn_dim)", c.ffn_dim}};
@@ -522,7 +544,7 @@ mc_status mc_create(const mc_config* cfg, mc_engine** out) {
       if ((w.k % 256) != 0 || w.k < 512)
         return fail(MC_EINVAL, "mx_fp4: %s: %d input features are no multiple of 256 >= 512 (the K tile of the MXFP4 GEMM)", w.name, w.k);
   }
-  const mc::Quant q_mx = e->mx_fp4 ? mc::QUANT_MXFP4 : mc::QUANT_MX;
+  const mc::Quant q_mx = e->mx_fp4 ? mc::QUANT_MXFP4 : e->mx_fp6 ? mc::QUANT_MXFP6 : mc::QUANT_MX;
   const mc::Quant q_big = c.fp8_linear >= 2 ? q_mx : c.fp8_linear == 1 ? mc::QUANT_ROW : mc::QUANT_NONE;
   const mc::Quant q_dd = c.fp8_linear == 3 ? q_mx : mc::QUANT_NONE;
   e->layers.resize(e->NL);
@@ -620,6 +642,7 @@ void mc_destroy(mc_engine* e) {
 size_t mc_workspace_bytes(const mc_engine* e) { return e ? e->work.need : 0; }
 
 int mc_engine_mx_fp4(const mc_engine* e) { return e && e->mx_fp4 ? 1 : 0; }
+int mc_engine_mx_fp6(const mc_engine* e) { return e && e->mx_fp6 ? 1 : 0; }
 
 mc_status mc_set_workspace(mc_engine* e, void* ws_dev, size_t bytes) {
   if (!e) return fail(MC_EINVAL, "null argument");
@@ -913,7 +936,7 @@ static mc_status ln_for_gemm(mc_engine* e, const Linear& l, const float* x, cons
                              const float* sc2, const float* sh2, const uint8_t* sel, hipStream_t s, ActSrc* a) {
   const int d = e->d, Lp = e->Lp;
   bf16_t* xn = e->buf<bf16_t>("xn");
-  *a = ActSrc{xn, d, l.q && mc::g_fp8_fused_quant && !l.fp4};   // MXFP4 has no fused producer: the separate pass
+  *a = ActSrc{xn, d, l.q && mc::g_fp8_fused_quant && !l.fp4 && !l.fp6};   // MXFP4 / MXFP6 have no fused producer here: the separate pass
   if (a->quantised) {
     HIP_TRY(mc::launch_ln_modulate_fp8(x, d, sc, sh, mode, e->cfg.eps, e->buf<uint8_t>("aq"), d,
                                        l.mx ? nullptr : e->buf<float>("a_scale"), l.mx ? e->buf<uint8_t>("a_mx") : nullptr,
@@ -1240,7 +1263,7 @@ static mc_status block_post_ctx(mc_engine* e, const Layer& l, const float* em, f
   p.Cb = h; p.ldc = ffn;
   // MX with fused quantisers: FFN-1's GELU epilogue writes the e4m3 rows + block scales FFN-2 reads (both inside "h":
   // Lp * ffn bytes, then ffn / 32 * Lp scale bytes), the bf16 hidden tensor never exists
-  const bool h_fp8 = l.ffn1.mx && l.ffn2.mx && mc::g_fp8_fused_quant && !l.ffn1.fp4;
+  const bool h_fp8 = l.ffn1.mx && l.ffn2.mx && mc::g_fp8_fused_quant && !l.ffn1.fp4 && !l.ffn1.fp6;
   ActSrc hidden{h, ffn};
   if (h_fp8) {
     hidden.quantised = true; hidden.q = (uint8_t*)h; hidden.mx = hidden.q + (size_t)Lp * ffn;

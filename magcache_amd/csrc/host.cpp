@@ -47,9 +47,10 @@ mc_status WeightStore::alloc_linear(Linear& l, size_t n_out, size_t k_in, Quant 
   MC_TRY(alloc(&l.w, n_out * k_in));
   MC_TRY(alloc(&l.b, n_out));
   l.fp4 = quant == QUANT_MXFP4;
-  if (quant != QUANT_NONE) MC_TRY(alloc(&l.q, l.fp4 ? n_out * k_in / 2 : n_out * k_in));
+  l.fp6 = quant == QUANT_MXFP6;
+  if (quant != QUANT_NONE) MC_TRY(alloc(&l.q, l.fp4 ? n_out * k_in / 2 : l.fp6 ? n_out * k_in / 4 * 3 : n_out * k_in));
   if (quant == QUANT_ROW) MC_TRY(alloc(&l.q_scale, n_out));
-  if (quant == QUANT_MX || quant == QUANT_MXFP4) MC_TRY(alloc(&l.mx, (k_in / 32) * n_out));
+  if (quant == QUANT_MX || quant == QUANT_MXFP4 || quant == QUANT_MXFP6) MC_TRY(alloc(&l.mx, (k_in / 32) * n_out));
   return MC_OK;
 }
 
@@ -60,7 +61,7 @@ Slot& WeightStore::add_parts(Linear& l, const std::string& prefix, const std::ve
     add(prefix + part.name + ".bias", l.b, MC_F32, part.rows, row0);
     last = &add(prefix + part.name + ".weight", l.w, MC_BF16, part.rows * k, row0 * k);
     last->q8 = l.q; last->q8_scale = l.q_scale; last->q8_k = k; last->mx = l.mx; last->mx_rows = l.n_out;
-    last->fp4 = l.fp4;
+    last->fp4 = l.fp4; last->fp6 = l.fp6;
     last->lin = &l;
     row0 += part.rows;
   }
@@ -126,6 +127,9 @@ mc_status WeightStore::requantise(const Slot& s, hipStream_t stream) {
   const size_t rows = s.numel / s.q8_k, row0 = s.off / s.q8_k;
   if (s.fp4) {  // MXFP4: packed rows of q8_k / 2 bytes, the scale image of MX
     HIP_TRY(launch_quantize_rows_mxfp4(src, nullptr, (long)s.q8_k, (int)rows, (int)s.q8_k, s.q8 + s.off / 2, (long)s.q8_k / 2,
+                                       s.mx + row0, (long)s.mx_rows, stream));
+  } else if (s.fp6) {  // MXFP6: packed rows of 3 q8_k / 4 bytes (s.off is a whole number of rows), the scale image of MX
+    HIP_TRY(launch_quantize_rows_mxfp6(src, nullptr, (long)s.q8_k, (int)rows, (int)s.q8_k, s.q8 + s.off / 4 * 3, (long)s.q8_k / 4 * 3,
                                        s.mx + row0, (long)s.mx_rows, stream));
   } else if (s.mx) {  // MX: the e4m3 bytes are relative to the block scales, not to a row scale
     HIP_TRY(launch_quantize_rows_mx(src, nullptr, (long)s.q8_k, (int)rows, (int)s.q8_k, s.q8 + s.off, (long)s.q8_k, s.mx + row0,

@@ -37,12 +37,14 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 extern int g_fp8_fused_quant;    // engine.cpp
 extern int g_sp_attn_partials;   // engine.cpp
 extern int g_mx_fp4;             // engine.cpp: read once by mc_create and by mc_mmdit_create / _create_sized
+extern int g_mx_fp6;             // engine.cpp: the same for MXFP6; both 1 at create time is MC_EINVAL
 extern int g_mmdit_two_streams;  // mmdit_engine.cpp
 
 // ---------------------------------------------------------------- weights
 // y = x W^T + b with W [n_out, k_in] bf16 and, optionally, an e4m3 copy of W made when the weight is set: with one scale
 // per output channel (q_scale) or with MX block scales (mx: E8M0, block-major [k_in / 32][n_out]).  q == null: bf16 only.
 // fp4: the copy is MXFP4 instead -- e2m1 codes, two per byte, rows of k_in / 2 bytes in q, the same scale image in mx (quant.h).
+// fp6: the copy is MXFP6 -- e2m3 codes, 32 per 24 bytes, rows of 3 k_in / 4 bytes in q, the same scale image.
 struct Linear {
   bf16_t* w = nullptr;
   float* b = nullptr;
@@ -51,10 +53,11 @@ struct Linear {
   float* q_scale = nullptr;
   uint8_t* mx = nullptr;
   bool fp4 = false;
+  bool fp6 = false;
   bf16_t* w_base = nullptr;  // the pristine weight while a LoRA adapter touches this Linear (w is then the merged one)
 };
-// one scale per output channel | one E8M0 byte per (channel, 32 inputs) with e4m3 elements | the same with e2m1 elements
-enum Quant { QUANT_NONE, QUANT_ROW, QUANT_MX, QUANT_MXFP4 };
+// one scale per output channel | one E8M0 byte per (channel, 32 inputs) with e4m3 elements | the same with e2m1 | e2m3 elements
+enum Quant { QUANT_NONE, QUANT_ROW, QUANT_MX, QUANT_MXFP4, QUANT_MXFP6 };
 struct Part { std::string name; size_t rows; };   // an upstream Linear whose rows are stacked into a fused one (q | k | v -> qkv)
 struct RowRange { int first, count; };            // output channels of a Linear: all of them, or k|v / q of the fused q|k|v
 inline RowRange whole(const Linear& l) { return {0, l.n_out}; }
@@ -75,6 +78,7 @@ struct Slot {  // one named parameter
   uint8_t* mx = nullptr;
   size_t mx_rows = 0;
   bool fp4 = false;   // the copy is MXFP4: packed rows of q8_k / 2 bytes
+  bool fp6 = false;   // the copy is MXFP6: packed rows of 3 q8_k / 4 bytes
   Linear* lin = nullptr;  // the Linear whose rows this weight is (add_parts); null for every other parameter
   // adapters on an fp32 parameter (WeightStore::allow_f32_targets)
   size_t f32_k = 0;           // > 0: an fp32 matrix [numel / f32_k, f32_k], which takes low-rank pairs; 0: deltas only

@@ -32,7 +32,8 @@
 //   aq   e4m3 [S_pad, 5d]   (fp8_linear != 0 only) the quantised operand rows of the MX Linears, joint row index, columns as
 //                           "am": [0,d) the LayerNorm + modulate output (q|k|v, MLP-in, the single block's linear1) and, mode
 //                           3, the attention output (the output projections); [d,5d) GELU(MLP-in), MLP-out's operand
-//                           (option "mx_fp4": packed e2m1 instead, rows of 5d / 2 bytes, column c at byte c / 2, same order)
+//                           (option "mx_fp4": packed e2m1 instead, rows of 5d / 2 bytes, column c at byte c / 2, same order;
+//                           option "mx_fp6": packed e2m3, rows of 5d * 3 / 4 bytes, the 32 columns of block b in the 24 bytes at 24 b)
 //   a_mx E8M0               (fp8_linear != 0 only) the block scales of "aq".  A scale image is block-major [k / 32][rows_pad]
 //                           with the rows of every group of 64 interleaved RELATIVE TO THE LAUNCH'S FIRST ROW, so two row
 //                           ranges must not share one: three regions, [text | image | joint (the single blocks)], each
@@ -54,6 +55,8 @@
 // Option "mx_fp4" (read once by the create call, opt-in, W4A4): the same Linears hold an MXFP4 copy and run on
 // launch_gemm_mxfp4; "aq" holds packed e2m1 rows, written by the FP4 tail of the LayerNorm kernel and the EPI_GELU_MXFP4
 // epilogue (fp8_fused_quant 1) or by launch_quantize_rows_mxfp4 (0, and the attention output): the same bits either way.
+// Option "mx_fp6" (latched the same way, W6A6): an MXFP6 copy on launch_gemm_mxfp6; "aq" holds packed e2m3 rows, ALWAYS written
+// by launch_quantize_rows_mxfp6 -- the format has no fused producer, so fp8_fused_quant changes nothing (fused_quant below).
 #include <cmath>
 #include <memory>
 
@@ -118,6 +121,7 @@ struct mc_mmdit {
   bool begun = false;
   int fp8 = 0;                                               // cfg.fp8_linear: 0 | 2 | 3
   bool mx_fp4 = false;   // option "mx_fp4" as the create call read it (with fp8_linear 2 | 3): the MX Linears and "aq" are MXFP4
+  bool mx_fp6 = false;   // option "mx_fp6" likewise: MXFP6 (never both)
   // optional second compute stream: the text stream of a double block next to the image stream (mc_set_option
   // "mmdit_two_streams"); a ring of event pairs so that an event is not re-recorded while an earlier wait on it may
   // still be queued
@@ -167,7 +171,8 @@ struct mc_mmdit {
 
 namespace {
 
-// The e4m3 rows [M, k_in] an MX Linear reads (ld bytes apart; MXFP4: packed e2m1 rows of k_in / 2 bytes), with their scale
+// The e4m3 rows [M, k_in] an MX Linear reads (ld bytes apart; MXFP4: packed e2m1 rows of k_in / 2 bytes; MXFP6: packed e2m3 rows
+// of 3 k_in / 4 bytes), with their scale
 // image (rows_pad >= ceil256(M) rows per k block)
 struct MxRows {
   const uint8_t* q; long ld;
@@ -192,6 +197,11 @@ mc_status linear(const mc_mmdit* e, const Linear& l, int M, const bf16_t* A, lon
     if (l.fp4) {   // packed rows of k_in / 2 bytes
       p.W = (const bf16_t*)(l.q + (size_t)out.first * l.k_in / 2); p.ldw = l.k_in / 2;
       HIP_TRY(mc::launch_gemm_mxfp4(p, epi, s));
+      return MC_OK;
+    }
+    if (l.fp6) {   // packed rows of 3 k_in / 4 bytes
+      p.W = (const bf16_t*)(l.q + (size_t)out.first * l.k_in / 4 * 3); p.ldw = l.k_in / 4 * 3;
+      HIP_TRY(mc::launch_gemm_mxfp6(p, epi, s));
       return MC_OK;
     }
     HIP_TRY(mc::launch_gemm_mxfp8(p, epi, s));
@@ -231,14 +241,19 @@ struct MxDst {
 MxDst mx_at(const mc_mmdit* e, int row0, int rows, int col0, bool o_proj = false) {
   const MxRegion r = mx_region(e, row0, rows);
   const size_t blk = o_proj ? (size_t)5 * e->d / 32 : (size_t)col0 / 32;
+  if (e->mx_fp6)   // MXFP6 rows are 5d * 3 / 4 bytes, column c (a multiple of 32) at byte 3 c / 4
+    return {e->buf<uint8_t>("aq") + ((size_t)row0 * 5 * e->d + col0) / 4 * 3, 5L * e->d / 4 * 3, r.base + blk * r.rows_pad, r.rows_pad};
   const int per = e->mx_fp4 ? 2 : 1;   // elements per byte: MXFP4 rows are 5d / 2 bytes, column c at byte c / 2
   return {e->buf<uint8_t>("aq") + ((size_t)row0 * 5 * e->d + col0) / per, 5L * e->d / per, r.base + blk * r.rows_pad, r.rows_pad};
 }
 // the fused-quantising GELU epilogue of the engine's format
 int gelu_quant_epi(const mc_mmdit* e) { return e->mx_fp4 ? mc::EPI_GELU_MXFP4 : mc::EPI_GELU_MXFP8; }
+// do the producers (the LayerNorm tail, MLP-in's GELU epilogue) write the quantised rows themselves?  MXFP6 has no such producer
+bool fused_quant(const mc_mmdit* e) { return mc::g_fp8_fused_quant && !e->mx_fp6; }
 // bf16 rows -> their place in "aq" (the separate quantise pass: the attention output, and everything with fp8_fused_quant 0)
 mc_status mx_quantise(const mc_mmdit* e, const bf16_t* rows_bf16, long ld, int rows, int K, const MxDst& to, hipStream_t s) {
   if (e->mx_fp4) HIP_TRY(mc::launch_quantize_rows_mxfp4(rows_bf16, nullptr, ld, rows, K, to.q, to.ld, to.mx, to.rows_pad, s));
+  else if (e->mx_fp6) HIP_TRY(mc::launch_quantize_rows_mxfp6(rows_bf16, nullptr, ld, rows, K, to.q, to.ld, to.mx, to.rows_pad, s));
   else HIP_TRY(mc::launch_quantize_rows_mx(rows_bf16, nullptr, ld, rows, K, to.q, to.ld, to.mx, to.rows_pad, s));
   return MC_OK;
 }
@@ -249,7 +264,7 @@ mc_status ln_for_linear(const mc_mmdit* e, const Linear& l, int row0, int rows, 
   const int d = e->d;
   const float* x = e->buf<float>("x") + (size_t)row0 * d;
   bf16_t* xn = e->buf<bf16_t>("xn") + (size_t)row0 * d;
-  if (l.mx && mc::g_fp8_fused_quant) {
+  if (l.mx && fused_quant(e)) {
     const MxDst to = mx_at(e, row0, rows, 0);
     *a8 = to.rows();
     if (e->mx_fp4) HIP_TRY(mc::launch_ln_modulate_mxfp4(x, d, scale, shift, 0, 1e-6f, to.q, to.ld, to.mx, to.rows_pad, rows, d, s));
@@ -369,7 +384,7 @@ void plan_workspace(const mc_mmdit* e, const Rows& r, mc::Workspace& ws) {
   ws.add("calib_sums", 64);
   ws.add("calib_stats", 64);
   if (c.fp8_linear) {   // behind everything else: the plan of a bf16 engine does not change
-    ws.add("aq", e->mx_fp4 ? Sp * 5 * d / 2 : Sp * 5 * d);
+    ws.add("aq", e->mx_fp4 ? Sp * 5 * d / 2 : e->mx_fp6 ? Sp * 5 * d / 4 * 3 : Sp * 5 * d);
     ws.add("a_mx", (5 * d / 32 + (c.fp8_linear == 3 ? d / 32 : 0)) * (Ltp + align_up(Li, 256)) + 5 * d / 32 * Sp);
   }
 }
@@ -443,6 +458,12 @@ static mc_status create_engine(const mc_mmdit_config& c, mc_mmdit** out) {
   if (mx_fp4 && ((c.dim % 256) != 0 || c.dim < 512))
     return fail(MC_EINVAL, "mx_fp4: q|k|v / MLP-in (in_features = dim): %d input features are no multiple of 256 >= 512 (the K tile of "
                            "the MXFP4 GEMM; MLP-out reads 4 dim, a single block's linear2 5 dim)", c.dim);
+  if (mc::g_mx_fp4 != 0 && mc::g_mx_fp6 != 0)
+    return fail(MC_EINVAL, "the options \"mx_fp4\" and \"mx_fp6\" are both 1: an engine's MX Linears hold one element format, set one of them");
+  const bool mx_fp6 = mc::g_mx_fp6 != 0 && (c.fp8_linear == 2 || c.fp8_linear == 3);
+  if (mx_fp6 && ((c.dim % 256) != 0 || c.dim < 512))
+    return fail(MC_EINVAL, "mx_fp6: q|k|v / MLP-in (in_features = dim): %d input features are no multiple of 256 >= 512 (the K contract "
+                           "of the MXFP6 GEMM; MLP-out reads 4 dim, a single block's linear2 5 dim)", c.dim);
   if ((c.dim % 256) != 0) return fail(MC_EINVAL, "dim %d must be a multiple of 256", c.dim);
   if (c.n_double < 0 || c.n_single < 0 || c.n_double + c.n_single == 0) return fail(MC_EINVAL, "no blocks");
   if (c.txt_dim <= 0 || (c.txt_dim % 64) != 0 || (!qw && (c.vec_dim <= 0 || (c.vec_dim % 8) != 0)))
@@ -470,6 +491,7 @@ static mc_status create_engine(const mc_mmdit_config& c, mc_mmdit** out) {
   e->cfg = c;
   e->fp8 = c.fp8_linear;
   e->mx_fp4 = mx_fp4;
+  e->mx_fp6 = mx_fp6;
   e->P = P;
   e->rank = c.sp_rank;
   e->d = c.dim; e->H = c.num_heads;
@@ -484,7 +506,7 @@ static mc_status create_engine(const mc_mmdit_config& c, mc_mmdit** out) {
   // fp8_linear only decides which Linears keep an e4m3 copy with MX block scales: 2 = those that read a LayerNorm or GELU
   // output, 3 = those that read the attention output too.  The embedders, the modulation matrix, the token refiner and the
   // head stay bf16.
-  const mc::Quant q_mx = mx_fp4 ? mc::QUANT_MXFP4 : mc::QUANT_MX;
+  const mc::Quant q_mx = mx_fp4 ? mc::QUANT_MXFP4 : mx_fp6 ? mc::QUANT_MXFP6 : mc::QUANT_MX;
   const mc::Quant q_big = c.fp8_linear >= 2 ? q_mx : mc::QUANT_NONE;
   const mc::Quant q_out = c.fp8_linear == 3 ? q_mx : mc::QUANT_NONE;
   auto vec128 = [&](float*& v, const std::string& name) { return W.add_f32(v, name, 128); };   // a per-head norm weight
@@ -617,6 +639,7 @@ void mc_mmdit_destroy(mc_mmdit* e) {
 size_t mc_mmdit_workspace_bytes(const mc_mmdit* e) { return e ? e->work.need : 0; }
 
 int mc_mmdit_mx_fp4(const mc_mmdit* e) { return e && e->mx_fp4 ? 1 : 0; }
+int mc_mmdit_mx_fp6(const mc_mmdit* e) { return e && e->mx_fp6 ? 1 : 0; }
 
 mc_status mc_mmdit_set_workspace(mc_mmdit* e, void* ws_dev, size_t bytes) {
   if (!e) return fail(MC_EINVAL, "null argument");
@@ -936,7 +959,7 @@ mc_status double_post(const mc_mmdit* e, const Range* r, int n, hipStream_t s, f
     if (r[i].w->fc2.mx) {   // MLP-out's operand: "aq"[:, d:5d], written by MLP-in's epilogue or quantised from "am"[:, d:5d]
       const MxDst to = mx_at(e, r[i].row0, r[i].rows, d);
       a_f2 = to.rows();
-      if (r[i].w->fc1.mx && mc::g_fp8_fused_quant) {
+      if (r[i].w->fc1.mx && fused_quant(e)) {
         f1.Cq = to.q; f1.ldcq = to.ld; f1.c_mx = to.mx; f1.mx_rows_c = to.rows_pad;
         epi_f1 = gelu_quant_epi(e);
       }
@@ -1323,7 +1346,7 @@ mc_status mc_mmdit_block_pre(mc_mmdit* e, int blk, mc_stream stream_) {
       mc::GemmParams f = {};
       f.Cb = am + d; f.ldc = 5 * d;
       int epi = mc::EPI_GELU_BF16;
-      if (g.out.mx && mc::g_fp8_fused_quant) {
+      if (g.out.mx && fused_quant(e)) {
         const MxDst to = mx_at(e, 0, S, d);
         f.Cq = to.q; f.ldcq = to.ld; f.c_mx = to.mx; f.mx_rows_c = to.rows_pad;
         epi = gelu_quant_epi(e);
@@ -1419,7 +1442,7 @@ mc_status mc_mmdit_block_post(mc_mmdit* e, int blk, mc_stream stream_) {
       // GELU columns and their scales already, so only the attention columns are quantised here
       const MxDst to = mx_at(e, 0, S, 0);
       a8 = to.rows();
-      MC_TRY(mx_quantise(e, am, 5 * d, S, (g.in.mx && mc::g_fp8_fused_quant) ? d : 5 * d, to, s));
+      MC_TRY(mx_quantise(e, am, 5 * d, S, (g.in.mx && fused_quant(e)) ? d : 5 * d, to, s));
     }
     MC_TRY(linear(e, g.out, S, am, 5 * d, o, epi, s, nullptr, 0, nullptr, &a8));
   }

@@ -121,6 +121,18 @@ bool gemm_mxfp4_supported(const GemmParams& p);
 hipError_t launch_quantize_rows_mxfp4(const bf16_t* x, const float* x_f32, long ldx, int M, int K, uint8_t* q, long ldq,
                                       uint8_t* s, long rows_pad, hipStream_t stream);
 
+// MXFP6 (gemm_mxfp6.hip): the same instruction with both operands e2m3; 32 consecutive k per 24 bytes, one little-endian bit
+// stream with code i at bit 6 i (quant.h), so a row of K elements is 3 K / 4 bytes (lda / ldw / ldq in BYTES of packed rows,
+// % 16 == 0); the scale image of the MX fp8 path.  M > 0 (the row contract of launch_gemm_mxfp8), N % 256 == 0, K % 256 == 0
+// elements, K >= 512; the epilogues of gemm_epilogue.h (EPI_BF16, _GELU_BF16, _RESID_GATE, _RESID_CAPTURE, _F32), no
+// quantising epilogue.
+hipError_t launch_gemm_mxfp6(const GemmParams& p, int epi, hipStream_t stream);
+bool gemm_mxfp6_supported(const GemmParams& p);
+// codes e2m3(x * 2^-e), e = ceil(log2(max|block| / 7.5)), scale byte e + 127 at s[kb * rows_pad + mx_scale_row(m)] (quant.h);
+// any M > 0, K % 32 == 0, ldq >= 3 K / 4
+hipError_t launch_quantize_rows_mxfp6(const bf16_t* x, const float* x_f32, long ldx, int M, int K, uint8_t* q, long ldq,
+                                      uint8_t* s, long rows_pad, hipStream_t stream);
+
 // ---------------------------------------------------------------- LoRA merge (lora_merge.hip)
 // out[rows, K] = bf16(base + sum_j scale_j * (up_j down_j)), up_j [rows, rank], down_j [rank, K].  Per term an fp32 accumulator
 // from zero on bf16 MFMAs, the fp32 delta summed in term order, one fp32 add of the widened base element last, one

@@ -197,6 +197,34 @@ mc_status mc_op_gemm_mxfp4(const void* A, long lda, const void* a_scales, long r
   return MC_OK;
 }
 
+mc_status mc_op_quantize_rows_mxfp6(const void* x, mc_dtype dtype, long ldx, int M, int K, void* q, long ldq, void* scales,
+                                    long rows_pad, mc_stream s) {
+  if (dtype != MC_BF16 && dtype != MC_F32) return fail(MC_EINVAL, "quantize_rows_mxfp6: x is bf16 or fp32");
+  hipError_t err = mc::launch_quantize_rows_mxfp6(dtype == MC_BF16 ? (const bf16_t*)x : nullptr,
+                                                  dtype == MC_F32 ? (const float*)x : nullptr, ldx, M, K, (uint8_t*)q, ldq,
+                                                  (uint8_t*)scales, rows_pad, (hipStream_t)s);
+  if (err == hipErrorInvalidValue)
+    return fail(MC_EINVAL, "quantize_rows_mxfp6: M, K > 0, K %% 32 == 0, ldx %% 8 == 0 and >= K, ldq (bytes) %% 16 == 0 and >= 3 K / 4, "
+                           "16-byte aligned pointers, rows_pad %% 64 == 0 and >= M");
+  HIP_TRY(err);
+  return MC_OK;
+}
+
+mc_status mc_op_gemm_mxfp6(const void* A, long lda, const void* a_scales, long rows_pad_a, const void* W, long ldw,
+                           const void* w_scales, long rows_pad_w, const float* bias, int M, int N, int K, int epi, void* Cb,
+                           long ldc, float* X, long ldx, const float* gate, mc_stream s) {
+  mc::GemmParams p = gp((const bf16_t*)A, lda, (const bf16_t*)W, ldw, bias, M, N, K);
+  p.a_mx = (const uint8_t*)a_scales; p.mx_rows_a = rows_pad_a; p.w_mx = (const uint8_t*)w_scales; p.mx_rows_w = rows_pad_w;
+  p.Cb = (bf16_t*)Cb; p.ldc = ldc; p.X = X; p.ldx = ldx; p.gate = gate;
+  hipError_t err = epi == mc::EPI_RESID_CAPTURE ? hipErrorInvalidValue : mc::launch_gemm_mxfp6(p, epi, (hipStream_t)s);
+  if (err == hipErrorInvalidValue)
+    return fail(MC_EINVAL, "gemm_mxfp6: needs M > 0, N %% 256 == 0, K %% 256 == 0 (elements), K >= 512, lda/ldw (bytes) %% 16 == 0 and "
+                           ">= 3 K / 4, 16-byte aligned operands, block scales with rows_pad_a >= M rounded up to 256, rows_pad_w >= N, "
+                           "both multiples of 64, epilogue 0, 1, 2 or 5 with its output");
+  HIP_TRY(err);
+  return MC_OK;
+}
+
 mc_status mc_op_attention_partial(const void* Q, long ldq, const void* K, long ldk, long kss, const void* V, long ldv,
                                   long vss, void* O, long ldo, int Lq_pad, int n_heads, int shard_rows,
                                   int shard_valid, int n_shards, float scale, int skip_shard, float* lse_out,
@@ -444,6 +472,9 @@ mc_status mc_set_option(const char* key, int value) {
   } else if (k == "mx_fp4") {
     if (value != 0 && value != 1) return fail(MC_EINVAL, "mx_fp4 must be 0 (MX fp8 Linears) or 1 (MXFP4 Linears where fp8_linear is 2 or 3; read when an engine is created)");
     mc::g_mx_fp4 = value;
+  } else if (k == "mx_fp6") {
+    if (value != 0 && value != 1) return fail(MC_EINVAL, "mx_fp6 must be 0 (MX fp8 Linears) or 1 (MXFP6 Linears where fp8_linear is 2 or 3; read when an engine is created)");
+    mc::g_mx_fp6 = value;
   } else if (k == "attn_kernel") {
     if (value != 0 && value != 3 && value != 5)
       return fail(MC_EINVAL, "attn_kernel must be 0 (default), 3 (8 waves x 32 rows) or 5 (4 waves x 64 rows, hand-scheduled)");
@@ -467,6 +498,7 @@ mc_status mc_get_option(const char* key, int* value) {
   else if (k == "gemm_defer") *value = mc::g_gemm_defer;
   else if (k == "fp8_fused_quant") *value = mc::g_fp8_fused_quant;
   else if (k == "mx_fp4") *value = mc::g_mx_fp4;
+  else if (k == "mx_fp6") *value = mc::g_mx_fp6;
   else if (k == "attn_kernel") *value = mc::g_attn_kernel;
   else if (k == "mmdit_two_streams") *value = mc::g_mmdit_two_streams;
   else return fail(MC_EINVAL, "unknown option '%s'", key);

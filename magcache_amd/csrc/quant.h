@@ -1,4 +1,4 @@
-// The arithmetic of the two fp8 (OCP e4m3) quantisers and of the MXFP4 (e2m1) quantiser, defined once.  Every producer of quantised rows -- the stand-alone
+// The arithmetic of the two fp8 (OCP e4m3) quantisers and of the MXFP4 (e2m1) and MXFP6 (e2m3) quantisers, defined once.  Every producer of quantised rows -- the stand-alone
 // kernels (quantize_rows_fp8_kernel, quantize_rows_mx_kernel), the fused tails of the LayerNorm + modulate kernel
 // (elementwise.hip), the EPI_GELU_MXFP8 / EPI_GELU_MXFP4 epilogues (gemm_mxfp8.hip, gemm_mxfp4.hip) and quantize_rows_mxfp4_kernel (gemm_mxfp4.hip) -- goes through these helpers, so "the same bits as
 // quantising the bf16 row" (ops.h) holds by construction.
@@ -82,6 +82,54 @@ __device__ __forceinline__ uint32_t pack8_e2m1(const float* v, float inv) {
 // whose lanes own four consecutive columns (the LayerNorm tail of elementwise.hip, the EPI_GELU_MXFP4 epilogue of gemm_mxfp4.hip)
 __device__ __forceinline__ uint32_t pack4_e2m1(float a, float b, float c, float d, float inv) {
   return e2m1_code(a, inv) | (e2m1_code(b, inv) << 4) | (e2m1_code(c, inv) << 8) | (e2m1_code(d, inv) << 12);
+}
+
+// ---- MXFP6 (both engines' option "mx_fp6"): OCP e2m3 elements -- sign, two exponent bits (bias 1), three mantissa bits:
+// magnitudes 0 .. 0.875 by 0.125 (codes 0..7, subnormal), 1 .. 1.875 by 0.125 (8..15), 2 .. 3.75 by 0.25 (16..23), 4 .. 7.5 by
+// 0.5 (24..31), bit 5 the sign -- with the MX scale image above: one E8M0 byte e + 127 per 32 consecutive k at s[kb * rows_pad +
+// mx_scale_row(row)].  e = ceil(log2(amax / 7.5)) clamped to [-127, 127] (7.5 = the largest e2m3 value, so nothing saturates;
+// an all-zero block gets e = -127 and zeros) -- mx_exponent with 448 replaced by 7.5.
+// Packing: the 32 codes of a block are ONE little-endian bit stream of 24 bytes: bit b of the 192 (bit b % 8 of byte b / 8) is
+// bit b % 6 of the code of k = b / 6, so code i starts at bit 6 i and four codes fill three bytes; a row of K elements is
+// 3 K / 4 bytes.  That is the order the matrix core reads (tools/ubench_mxfp6_probe.cpp, profiles/r14/mxfp6_probe.log: an FP6
+// operand of v_mfma_scale_f32_16x16x128_f8f6f4, cbsz / blgp = 2, is the low 24 bytes of a lane's register argument, and bit b
+// of lane group g is bit b % 6 of the code of k = 32 g + b / 6).
+__device__ __forceinline__ int mxfp6_exponent(float amax) {
+  int e = -127;
+  if (amax > 0.f) {
+    int ex;
+    const float f = frexpf(amax * (1.0f / 7.5f), &ex);
+    e = (f == 0.5f) ? ex - 1 : ex;
+    e = max(-127, min(127, e));
+  }
+  return e;
+}
+// (amax * (1 / 7.5f) is one rounding away from amax / 7.5; at amax = 7.5 * 2^n the product must land on 2^n exactly for the
+// f == 0.5 test: 7.5f * fl(1 / 7.5) rounds to 1.0f -- tests/test_mxfp6_cpu.py restates the rule in float64 and the GPU test
+// compares the bits at and just above every such amax.)
+// one value times the inverse scale -> its e2m3 code, round to nearest, a tie to the even mantissa; the sign bit is x's own (a
+// negative that rounds to zero is -0).  CODED, not v_cvt_scalef32_pk*_fp6_*: the hardware conversion's rounding has not been
+// probed in this project.  The product is exact (a power of two); the code book is uniform inside each binade -- steps of
+// 1/8 below 2, 1/4 below 4, 1/2 above -- so the code is rint (to nearest even) of |x| in units of the binade's step plus the
+// binade's first code less its first value in steps: rint(8 a) for a < 2 (0..16), 8 + rint(4 a) for a < 4, 16 + rint(2 a)
+// above; the offsets are even, so an even integer is an even mantissa, and a value that rounds up to the next binade lands on
+// that binade's first code.  Magnitudes above 7.5 (not produced by mxfp6_exponent's scale) clamp to code 31.
+__device__ __forceinline__ uint32_t e2m3_code(float x, float inv) {
+  const float a = fminf(fabsf(x * inv), 7.5f);
+  const float q = a < 2.0f ? rintf(a * 8.0f) : a < 4.0f ? 8.0f + rintf(a * 4.0f) : 16.0f + rintf(a * 2.0f);
+  return (uint32_t)q | ((__float_as_uint(x) >> 26) & 32u);
+}
+// sixteen consecutive k (the first one a multiple of 16) times the inverse scale -> 96 bits of codes, v[0] in the lowest six
+__device__ __forceinline__ void pack16_e2m3(const float* v, float inv, uint32_t (&w)[3]) {
+  uint64_t lo = 0;   // codes 0..9 and the low four bits of code 10
+#pragma unroll
+  for (int i = 0; i < 10; ++i) lo |= (uint64_t)e2m3_code(v[i], inv) << (6 * i);
+  const uint32_t c10 = e2m3_code(v[10], inv);
+  lo |= (uint64_t)(c10 & 15u) << 60;
+  uint32_t hi = c10 >> 4;   // the high two bits of code 10, then codes 11..15
+#pragma unroll
+  for (int i = 11; i < 16; ++i) hi |= e2m3_code(v[i], inv) << (6 * i - 64);
+  w[0] = (uint32_t)lo; w[1] = (uint32_t)(lo >> 32); w[2] = hi;
 }
 
 }  // namespace mc

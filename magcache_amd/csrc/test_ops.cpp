@@ -101,6 +101,18 @@ int mc_test_gemm_mxfp4_capture(const void* A, long lda, const void* a_mx, long m
   return (int)mc::launch_gemm_mxfp4(p, mc::EPI_RESID_CAPTURE, (hipStream_t)s);
 }
 
+// EPI_RESID_CAPTURE of launch_gemm_mxfp6: mc_op_gemm_mxfp6 has no X0 / R arguments
+int mc_test_gemm_mxfp6_capture(const void* A, long lda, const void* a_mx, long mx_rows_a, const void* W, long ldw,
+                               const void* w_mx, long mx_rows_w, const float* bias, int M, int N, int K, float* X, long ldx,
+                               const float* gate, const void* X0, long ldx0, float* R, long ldr, void* s) {
+  mc::GemmParams p = {};
+  p.A = (const bf16_t*)A; p.lda = lda; p.W = (const bf16_t*)W; p.ldw = ldw; p.bias = bias;
+  p.M = M; p.N = N; p.K = K;
+  p.a_mx = (const uint8_t*)a_mx; p.mx_rows_a = mx_rows_a; p.w_mx = (const uint8_t*)w_mx; p.mx_rows_w = mx_rows_w;
+  p.X = X; p.ldx = ldx; p.gate = gate; p.X0 = (const bf16_t*)X0; p.ldx0 = ldx0; p.R = R; p.ldr = ldr;
+  return (int)mc::launch_gemm_mxfp6(p, mc::EPI_RESID_CAPTURE, (hipStream_t)s);
+}
+
 // EPI_RESID_CAPTURE of launch_gemm_fp8 (per-row / per-channel scales): mc_op_gemm_fp8 has no X0 / R arguments
 int mc_test_gemm_fp8_capture(const void* A, long lda, const float* a_scale, const void* W, long ldw, const float* w_scale,
                              const float* bias, int M, int N, int K, float* X, long ldx, const float* gate, const void* X0,

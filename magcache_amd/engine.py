@@ -103,10 +103,12 @@ class Engine(EngineHost):
         return parse_wan_lora_state_dict(sd)
 
     def __init__(self, cfg, latent_grid, device="cuda:0", sp_rank=0, sp_size=1, n_branches=2, calibration=False,
-                 sp_phases=False, mx_fp4=False):
+                 sp_phases=False, mx_fp4=False, mx_fp6=False):
         """mx_fp4: with cfg["fp8_linear"] 2 | 3 the quantised Linears are MXFP4 (W4A4) instead of MX fp8 -- coarser, an
         opt-in speed / quality experiment, never a default.  The process-wide option "mx_fp4" is set around the create call
-        only and put back; the engine keeps what it read (self.mx_fp4)."""
+        only and put back; the engine keeps what it read (self.mx_fp4).
+        mx_fp6 (or cfg["mx_fp6"]): the same latch for MXFP6 (W6A6, e2m3 elements: the mantissa of e4m3 at 3/4 of its bytes);
+        self.mx_fp6.  Asking for both is refused by the library."""
         if not torch.cuda.is_available():
             raise RuntimeError("magcache_amd.Engine needs a ROCm device; there is no CPU fallback")
         self.lib = _lib.load()
@@ -134,7 +136,7 @@ class Engine(EngineHost):
             h = C.c_void_p()
             check(self.lib.mc_create_sized(C.byref(c), C.sizeof(c), C.byref(h)))
             return h
-        self._create_latching_mx_fp4(create, mx_fp4 or cfg.get("mx_fp4"), "mc_engine_mx_fp4")
+        self._create_latching(create, {"mx_fp4": mx_fp4 or cfg.get("mx_fp4"), "mx_fp6": mx_fp6 or cfg.get("mx_fp6")}, "mc_engine_")
         self._bind(self.lib.mc_workspace_bytes(self.h))
         self.tokens_per_rank = self.seq_len // sp_size
         self.head_stride = (4 * cfg["out_dim"] + 63) // 64 * 64    # row stride of "head_tokens" (fp32 elements)

@@ -53,11 +53,13 @@ class MMDiTEngine(EngineHost):
 
     def __init__(self, family, dim, num_heads, n_double, n_single, in_channels, out_channels, txt_dim, txt_len, vec_dim,
                  img_tokens, latent_grid=(0, 0, 0), refiner_depth=0, calibration=False, device="cuda:0", sp_rank=0,
-                 sp_size=1, fp8_linear=0, mx_fp4=False):
+                 sp_size=1, fp8_linear=0, mx_fp4=False, mx_fp6=False):
         """fp8_linear: 0 bf16 Linears; 2 / 3 the opt-in MX fp8 modes of mc_mmdit_config.fp8_linear (one GPU, dim >= 512).
         mx_fp4: with fp8_linear 2 | 3 those Linears are MXFP4 (W4A4) instead -- much coarser, an opt-in speed /
         quality experiment, never a default; dim a multiple of 256.  The process-wide option "mx_fp4" is set around the create
-        call only and put back; the engine keeps what it read (self.mx_fp4)."""
+        call only and put back; the engine keeps what it read (self.mx_fp4).
+        mx_fp6: the same latch for MXFP6 (W6A6, e2m3 elements; activations always quantised by separate passes); self.mx_fp6.
+        Asking for both is refused by the library."""
         if not torch.cuda.is_available():
             raise RuntimeError("magcache_amd.MMDiTEngine needs a ROCm device; there is no CPU fallback")
         self.lib = _lib.load()
@@ -78,7 +80,7 @@ class MMDiTEngine(EngineHost):
             h = C.c_void_p()
             check(self.lib.mc_mmdit_create_sized(C.byref(c), C.sizeof(c), C.byref(h)))
             return h
-        self._create_latching_mx_fp4(create, mx_fp4, "mc_mmdit_mx_fp4")
+        self._create_latching(create, {"mx_fp4": mx_fp4, "mx_fp6": mx_fp6}, "mc_mmdit_")
         self._bind(self.lib.mc_mmdit_workspace_bytes(self.h))
         self._rope_key = None
         self._controlnet = None
@@ -385,7 +387,7 @@ class FluxTransformer2DModelHIP(_LoraMethods):
     dynamic_geometry = False
 
     def __init__(self, cfg, img_tokens, txt_len=512, device="cuda:0", calibration=True, engine=None, sp_rank=0,
-                 sp_size=1, sp_group=None, dynamic_geometry=False, fp8_linear=0, mx_fp4=False):
+                 sp_size=1, sp_group=None, dynamic_geometry=False, fp8_linear=0, mx_fp4=False, mx_fp6=False):
         self.config = SimpleNamespace(**cfg)
         self.cfg = dict(cfg)
         dim = cfg["attention_head_dim"] * cfg["num_attention_heads"]
@@ -396,7 +398,7 @@ class FluxTransformer2DModelHIP(_LoraMethods):
                                             cfg["num_single_layers"], cfg["in_channels"], cfg["in_channels"],
                                             cfg["joint_attention_dim"], txt_len, cfg["pooled_projection_dim"], img_tokens,
                                             calibration=calibration, device=device, sp_rank=sp_rank, sp_size=sp_size,
-                                            fp8_linear=fp8_linear, mx_fp4=mx_fp4)
+                                            fp8_linear=fp8_linear, mx_fp4=mx_fp4, mx_fp6=mx_fp6)
         self.device = self.engine.device
         self.sp_group = sp_group
         self._ids_key = None
@@ -601,7 +603,7 @@ class HYVideoDiffusionTransformerHIP(_LoraMethods):
     dynamic_geometry = False
 
     def __init__(self, cfg, latent_grid, txt_len=256, device="cuda:0", calibration=True, engine=None, sp_rank=0,
-                 sp_size=1, sp_group=None, dynamic_geometry=False, fp8_linear=0, mx_fp4=False):
+                 sp_size=1, sp_group=None, dynamic_geometry=False, fp8_linear=0, mx_fp4=False, mx_fp6=False):
         self.cfg = dict(cfg)
         self.sp_group = sp_group
         self.dynamic_geometry = dynamic_geometry
@@ -618,7 +620,7 @@ class HYVideoDiffusionTransformerHIP(_LoraMethods):
                                             cfg["out_channels"], cfg["text_states_dim"], txt_len, cfg["text_states_dim_2"],
                                             self.img_tokens, latent_grid=self.latent_grid, refiner_depth=2,
                                             calibration=calibration, device=device, sp_rank=sp_rank, sp_size=sp_size,
-                                            fp8_linear=fp8_linear, mx_fp4=mx_fp4)
+                                            fp8_linear=fp8_linear, mx_fp4=mx_fp4, mx_fp6=mx_fp6)
         self.device = self.engine.device
 
     def load_state_dict(self, sd):
@@ -752,7 +754,7 @@ class QwenImageTransformer2DModelHIP(_LoraMethods):
     dynamic_geometry = False
 
     def __init__(self, cfg, img_tokens, txt_len=1024, device="cuda:0", calibration=True, engine=None, sp_size=1,
-                 dynamic_geometry=False, fp8_linear=0, mx_fp4=False):
+                 dynamic_geometry=False, fp8_linear=0, mx_fp4=False, mx_fp6=False):
         self.config = SimpleNamespace(**cfg)
         self.cfg = dict(cfg)
         self.dynamic_geometry = dynamic_geometry
@@ -762,7 +764,7 @@ class QwenImageTransformer2DModelHIP(_LoraMethods):
         self.inner_dim, self.img_tokens, self.txt_len, self.out_features = dim, img_tokens, txt_len, out
         self.engine = engine or MMDiTEngine(MC_FAMILY_QWEN, dim, cfg["num_attention_heads"], cfg["num_layers"], 0,
                                             cfg["in_channels"], out, cfg["joint_attention_dim"], txt_len, 0, img_tokens,
-                                            calibration=calibration, device=device, sp_size=sp_size, fp8_linear=fp8_linear, mx_fp4=mx_fp4)
+                                            calibration=calibration, device=device, sp_size=sp_size, fp8_linear=fp8_linear, mx_fp4=mx_fp4, mx_fp6=mx_fp6)
         self.device = self.engine.device
         self._shapes_key = None
 

@@ -21,7 +21,9 @@ headline bench line):
                                           workspace bytes, distance of every mode's output from the first mode's
                                           `--mx_fp4` adds, per mode 2 | 3 of the list, an MXFP4 engine (option "mx_fp4": W4A4,
                                           opt-in) as "<mode>+mxfp4" and the same engine with fp8_fused_quant 0 (separate quantise
-                                          passes instead of the fused FP4 producers) as "<mode>+mxfp4 separate"
+                                          passes instead of the fused FP4 producers) as "<mode>+mxfp4 separate";
+                                          `--mx_fp6` adds an MXFP6 engine (option "mx_fp6": W6A6, opt-in, always separate
+                                          quantise passes) as "<mode>+mxfp6"
 
     python tools/bench_mmdit.py flux --ip-adapter TOKENS[xIMAGES][,...] [--depth D,S]
                                           FLUX.1-dev 1024x1024, one full forward with one IP-Adapter per entry (768-wide embeds,
@@ -434,12 +436,13 @@ def bench_regeometry(which, sizes, depth=None, rounds=7, per_round=4):
                       "switch_without_reserve": no_reserve, "per_size": res}))
 
 
-def bench_fp8(which, sizes, modes, depth=None, rounds=5, per_round=3, txt_len=512, mx_fp4=False):
+def bench_fp8(which, sizes, modes, depth=None, rounds=5, per_round=3, txt_len=512, mx_fp4=False, mx_fp6=False):
     """`sizes`: [(width, height)] in pixels; image tokens (H/16) * (W/16).  One engine per fp8_linear mode of `modes` (the same
     seeded weights: an fp8 engine quantises them as it takes them), switched from size to size with set_geometry; engine-level
     full forwards.  Per size, windows of `per_round` forwards alternate between the modes after a warm-up of each; host clock
     around a device synchronise.  One JSON line per size.  mx_fp4: the variants "<mode>+mxfp4" (an MXFP4 engine of mode 2 | 3) and
-    "<mode>+mxfp4 separate" (the same engine under fp8_fused_quant 0) join the table, keyed by those labels."""
+    "<mode>+mxfp4 separate" (the same engine under fp8_fused_quant 0) join the table, keyed by those labels; mx_fp6: the variant
+    "<mode>+mxfp6" (an MXFP6 engine; its quantise passes are always separate)."""
     from magcache_amd._lib import check
     from magcache_amd.qwen_bench import random_state_dict
     lib = load()
@@ -449,16 +452,18 @@ def bench_fp8(which, sizes, modes, depth=None, rounds=5, per_round=3, txt_len=51
         cfg.update(num_layers=depth[0], **({"num_single_layers": depth[1]} if flux else {}))
     grids = [(h // 16, w // 16) for w, h in sizes]
     engines, fused = {}, {}
-    variants = [(mode, mode, False) for mode in modes] + [(f"{mode}+mxfp4", mode, True) for mode in modes if mx_fp4 and mode in (2, 3)]
-    for label, mode, fp4 in variants:
+    variants = ([(mode, mode, False, False) for mode in modes] +
+                [(f"{mode}+mxfp6", mode, False, True) for mode in modes if mx_fp6 and mode in (2, 3)] +
+                [(f"{mode}+mxfp4", mode, True, False) for mode in modes if mx_fp4 and mode in (2, 3)])
+    for label, mode, fp4, fp6 in variants:
         n0 = grids[0][0] * grids[0][1]
         if flux:
-            m = MM.FluxTransformer2DModelHIP(cfg, n0, txt_len=txt_len, device=DEV, calibration=False, fp8_linear=mode, mx_fp4=fp4)
+            m = MM.FluxTransformer2DModelHIP(cfg, n0, txt_len=txt_len, device=DEV, calibration=False, fp8_linear=mode, mx_fp4=fp4, mx_fp6=fp6)
             synth_load(m, flux_names(cfg))
         else:
-            m = MM.QwenImageTransformer2DModelHIP(cfg, n0, txt_len=txt_len, device=DEV, calibration=False, fp8_linear=mode, mx_fp4=fp4)
+            m = MM.QwenImageTransformer2DModelHIP(cfg, n0, txt_len=txt_len, device=DEV, calibration=False, fp8_linear=mode, mx_fp4=fp4, mx_fp6=fp6)
             m.engine.load_weights(random_state_dict(cfg, DEV))
-        assert m.engine.mx_fp4 is fp4
+        assert m.engine.mx_fp4 is fp4 and m.engine.mx_fp6 is fp6
         engines[label], fused[label] = m.engine, 1
         if fp4:
             engines[label + " separate"], fused[label + " separate"] = m.engine, 0
@@ -522,7 +527,7 @@ if __name__ == "__main__":
         sizes = [tuple(int(v) for v in g.split("x"))
                  for g in (sys.argv[sys.argv.index("--size") + 1] if "--size" in sys.argv else default).split(",")]
         depth = [int(v) for v in sys.argv[sys.argv.index("--depth") + 1].split(",")] if "--depth" in sys.argv else None
-        bench_fp8(which, sizes, modes, depth, mx_fp4="--mx_fp4" in sys.argv[2:])
+        bench_fp8(which, sizes, modes, depth, mx_fp4="--mx_fp4" in sys.argv[2:], mx_fp6="--mx_fp6" in sys.argv[2:])
     elif "--regeometry" in sys.argv[2:]:
         if which not in ("flux", "qwen"):
             sys.exit(f"--regeometry benches FLUX and Qwen-Image, not '{which}'")

@@ -3,14 +3,15 @@
 random weights (no checkpoint offline), cond / negative prompts of 120 / 6 tokens, 50 steps of true CFG (4.0), without
 and with MagCache E006K2R02 (thresh 0.06, K 2, retention 0.2, the Qwen-Image table).
 
-    python tools/bench_qwen_image.py [steps] [--fp8_linear M] [--mx_fp4]
-    python tools/bench_qwen_image.py --fp8_linear 0,2,3 [--mx_fp4] [--depth D]
+    python tools/bench_qwen_image.py [steps] [--fp8_linear M] [--mx_fp4 | --mx_fp6]
+    python tools/bench_qwen_image.py --fp8_linear 0,2,3 [--mx_fp4] [--mx_fp6] [--depth D]
 
 `--fp8_linear M` (2 | 3) runs the same measurement on an engine with MX fp8 block Linears (mc_mmdit_config.fp8_linear).  A
 list of modes instead compares them: one engine per mode on the same weights, full forwards at 1664 x 928 in alternating
 windows (tools/bench_mmdit.py bench_fp8), ms per forward and the spread of the windows per mode (`--depth D`: D blocks
 instead of 60).  `--mx_fp4`: with one mode (2 | 3), that engine's Linears are MXFP4 (option "mx_fp4": W4A4, opt-in, much
 coarser); with a list, the MXFP4 variants of modes 2 and 3 join the table, with fused and with separate quantise passes.
+`--mx_fp6`: the same for MXFP6 (option "mx_fp6": W6A6, opt-in; its quantise passes are always separate).
 
 Prints one JSON line: seconds per image each way, forwards skipped of 2 * steps (the schedule is known on the host
 beforehand and is checked against the run), the time of one full and one skipped forward, and the model's achieved
@@ -52,6 +53,9 @@ def main():
     mx_fp4 = "--mx_fp4" in argv
     if mx_fp4:
         argv.remove("--mx_fp4")
+    mx_fp6 = "--mx_fp6" in argv
+    if mx_fp6:
+        argv.remove("--mx_fp6")
     depth = None
     if "--depth" in argv:
         i = argv.index("--depth")
@@ -60,7 +64,7 @@ def main():
     if len(fp8) > 1:
         sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
         from bench_mmdit import bench_fp8
-        return bench_fp8("qwen", [(1664, 928)], fp8, depth=depth, txt_len=120, mx_fp4=mx_fp4)
+        return bench_fp8("qwen", [(1664, 928)], fp8, depth=depth, txt_len=120, mx_fp4=mx_fp4, mx_fp6=mx_fp6)
     steps = int(argv[0]) if argv else 50
     cfg = MM.QWEN_IMAGE
     h2, w2 = 928 // 16, 1664 // 16
@@ -71,12 +75,12 @@ def main():
     ne = torch.randn(1, 6, 3584, generator=g, device=DEV)
     lat = torch.randn(1, n, 64, generator=g, device=DEV)
     t0 = time.time()
-    m = MM.QwenImageTransformer2DModelHIP(cfg, n, txt_len=120, device=DEV, calibration=False, fp8_linear=fp8[0], mx_fp4=mx_fp4)
+    m = MM.QwenImageTransformer2DModelHIP(cfg, n, txt_len=120, device=DEV, calibration=False, fp8_linear=fp8[0], mx_fp4=mx_fp4, mx_fp6=mx_fp6)
     m.load_state_dict(random_state_dict(cfg, DEV, seed=1))
     torch.cuda.synchronize()
     load_s = time.time() - t0
     sig, _ = qwen_image_sigmas(steps, n)
-    res = dict(config="qwen_image_1664x928", fp8_linear=fp8[0], mx_fp4=m.engine.mx_fp4, steps=steps, img_tokens=n, txt_tokens=[120, 6], weights_load_s=round(load_s, 1))
+    res = dict(config="qwen_image_1664x928", fp8_linear=fp8[0], mx_fp4=m.engine.mx_fp4, mx_fp6=m.engine.mx_fp6, steps=steps, img_tokens=n, txt_tokens=[120, 6], weights_load_s=round(load_s, 1))
     # one full and one skipped forward (warm-up first)
     t = torch.tensor([0.5], device=DEV)
     for mode in (MM.MC_MODE_FULL, MM.MC_MODE_FULL):

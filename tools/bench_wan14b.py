@@ -18,6 +18,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--fp8_linear", type=int, default=0, choices=(0, 1, 2, 3),
                 help="OPTIONAL reduced-precision mode (BASELINE.json config 5's fp8 MFMA weight path): 1 per-row scales, 2 MX, 3 MX incl. the d x d Linears")
 ap.add_argument("--mx_fp4", action="store_true", help="with --fp8_linear 2 | 3: MXFP4 Linears (W4A4) instead of MX fp8")
+ap.add_argument("--mx_fp6", action="store_true", help="with --fp8_linear 2 | 3: MXFP6 Linears (W6A6) instead of MX fp8")
 ap.add_argument("--layers", type=int, default=0, help="run this many of the 40 layers (0 = all); per-layer time = the difference of two counts")
 args = ap.parse_args()
 DEV = "cuda:0"
@@ -28,6 +29,8 @@ if args.layers:
     cfg["num_layers"] = args.layers
 if args.mx_fp4:
     cfg["mx_fp4"] = True
+if args.mx_fp6:
+    cfg["mx_fp6"] = True
 m = M.WanModelHIP(cfg, grid, device=DEV, calibration=False)
 m.engine.load_weights(synthetic_weights(cfg, seed=0, device=DEV))
 g = torch.Generator(device=DEV).manual_seed(42)
@@ -51,7 +54,7 @@ ts, s1 = timed(lambda: e.forward(lat, 900.0, ctx, branch=0, mode=MC_MODE_SKIP).c
 d, f, nl = cfg["dim"], cfg["ffn_dim"], cfg["num_layers"]
 fl = nl * (8.0 * L * d * d + 4.0 * L * L * d + 4.0 * L * d * d + 4.0 * 512 * d * d + 4.0 * L * 512 * d + 4.0 * L * d * f)
 print(json.dumps({"config": "Wan2.1-T2V-14B 1280x720 81 frames: 75600 tokens, d=5120, 40 heads, ffn 13824, 40 layers; one GPU",
-                  "fp8_linear": args.fp8_linear, "mx_fp4": bool(e.mx_fp4), "layers_run": nl,
+                  "fp8_linear": args.fp8_linear, "mx_fp4": bool(e.mx_fp4), "mx_fp6": bool(e.mx_fp6), "layers_run": nl,
                   "full_forward_s": t2, "first_forward_s": t1, "skipped_forward_ms": ts * 1e3,
                   "model_pflop_per_forward": fl / 1e15, "model_tflops_per_s": fl / t2 / 1e12,
                   "deterministic": bool(torch.equal(o1, o2)), "finite": bool(torch.isfinite(o2).all()),
