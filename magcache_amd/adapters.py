@@ -144,6 +144,10 @@ class LoraHost:
         return dict(adapters=a.value, linears=n.value, base_bytes=b.value, scales=dict(self._lora), call_scale=self._lora_call)
 
 
+# the options that select an engine's MX element format at create time (csrc/ops.h: MxInfo::option); none set: e4m3
+MX_FORMAT_OPTIONS = ("mx_fp4", "mx_fp6")
+
+
 class EngineHost(LoraHost):
     """An engine handle `h` of `lib` on `device`, bound to a workspace tensor.  The subclass creates the handle, says in
     _rebound() what its Python side holds that the engine forgot with the old binding and in _release() what goes before
@@ -159,22 +163,24 @@ class EngineHost(LoraHost):
         pass
 
     def _create_latching(self, create, requests, query_prefix):
-        """Run create() (which makes the handle and returns it) with the two process-wide element-format options set around
-        that call only.  requests: {"mx_fp4": bool, "mx_fp6": bool}; for each option an explicit request wins, otherwise the
+        """Run create() (which makes the handle and returns it) with the process-wide element-format options (MX_FORMAT_OPTIONS) set
+        around that call only.  requests: {"mx_fp4": bool, "mx_fp6": bool}; for each option an explicit request wins, otherwise the
         process-wide value (MAGCACHE_HIP_OPTIONS=mx_fp6=1) stands; the previous values are put back.  The engine keeps what it
         read: self.mx_fp4 / self.mx_fp6 = <query_prefix>mx_fp4 / _mx_fp6 (handle).  Both options at 1 is the library's MC_EINVAL."""
-        prev4, prev6 = C.c_int(0), C.c_int(0)
-        check(self.lib.mc_get_option(b"mx_fp4", C.byref(prev4)))
-        check(self.lib.mc_get_option(b"mx_fp6", C.byref(prev6)))
+        prev = {}
+        for name in MX_FORMAT_OPTIONS:
+            v = C.c_int(0)
+            check(self.lib.mc_get_option(name.encode(), C.byref(v)))
+            prev[name] = v.value
         try:
-            check(self.lib.mc_set_option(b"mx_fp4", 1 if requests.get("mx_fp4") else prev4.value))
-            check(self.lib.mc_set_option(b"mx_fp6", 1 if requests.get("mx_fp6") else prev6.value))
+            for name in MX_FORMAT_OPTIONS:
+                check(self.lib.mc_set_option(name.encode(), 1 if requests.get(name) else prev[name]))
             self.h = create()
         finally:
-            self.lib.mc_set_option(b"mx_fp4", prev4.value)
-            self.lib.mc_set_option(b"mx_fp6", prev6.value)
-        self.mx_fp4 = bool(getattr(self.lib, query_prefix + "mx_fp4")(self.h))
-        self.mx_fp6 = bool(getattr(self.lib, query_prefix + "mx_fp6")(self.h))
+            for name in MX_FORMAT_OPTIONS:
+                self.lib.mc_set_option(name.encode(), prev[name])
+        for name in MX_FORMAT_OPTIONS:   # self.mx_fp4, self.mx_fp6
+            setattr(self, name, bool(getattr(self.lib, query_prefix + name)(self.h)))
 
     def _bind(self, nbytes):
         """a zeroed workspace of `nbytes` (at least the current plan), bound with <_abi>set_workspace; the tensor it replaces

@@ -35,8 +35,8 @@ constexpr int kSpMaxParts = 9;   // local shard + 8 gather rounds
 
 struct mc_engine {
   mc_config cfg;
-  bool mx_fp4 = false;   // option "mx_fp4" as mc_create read it (with fp8_linear 2 | 3): the quantised Linears are MXFP4
-  bool mx_fp6 = false;   // option "mx_fp6" likewise: the quantised Linears are MXFP6 (never both)
+  mc::MxFormat mx_fmt = mc::MX_E4M3;   // the element format of the MX Linears (fp8_linear 2 | 3), as mc_create latched it from the
+                                       // options "mx_fp4" / "mx_fp6" (host.h: latch_mx_format)
   int d, ffn, H, NL, L, Lr, Lp, P, rank, tok0, Kp;  // Kp = in_dim*4 padded to 64
   int ctx_rows;                                     // text_len padded to 64
   std::vector<Layer> layers;
@@ -354,11 +354,15 @@ struct ActSrc {
   uint8_t *q = nullptr, *mx = nullptr;
 };
 
+// Does a fused producer (the LayerNorm tail, FFN-1's GELU epilogue) write the quantised rows this Linear reads?  With
+// fp8_fused_quant, for the per-row and the e4m3 MX copies; this engine has no fused producer of e2m1 or e2m3 rows: the separate pass.
+bool fused_quant(const Linear& l) { return l.q && mc::g_fp8_fused_quant && (!l.mx || l.fmt == mc::MX_E4M3); }
+
 // y[:, out] = epilogue(a W[out]^T + b[out]) over M rows: p carries the outputs, gates, capture and split-K operands of the
 // epilogue; the operands, the shape and every pointer advance of a row range come from `l`.
 // fp8 (block Linears only, M = Lp: "aq" and its scales are planned for that): per-token activation scales x per-output-channel
 // weight scales (launch_gemm_fp8), or MX block scales on both sides -- activations per (token, 32 k), weights per
-// (channel, 32 k) -- multiplied inside the matrix core (launch_gemm_mxfp8).
+// (channel, 32 k), in the Linear's element format -- multiplied inside the matrix core (launch_gemm_mx).
 mc_status linear(mc_engine* e, const Linear& l, RowRange out, int M, ActSrc a, mc::GemmParams p, int epi, hipStream_t s) {
   const int K = l.k_in;
   if (!l.q) {
@@ -369,31 +373,16 @@ mc_status linear(mc_engine* e, const Linear& l, RowRange out, int M, ActSrc a, m
   if (M != Lp) return fail(MC_EINVAL, "an fp8 Linear runs over the %d rows of a block, not %d", Lp, M);
   p.M = Lp; p.N = out.count; p.K = K; p.bias = l.b + out.first;
   uint8_t* aq = a.q ? a.q : e->buf<uint8_t>("aq");
-  if (l.fp4) {   // MXFP4 (option "mx_fp4"): packed rows of K / 2 bytes on both sides, the scale images of the MX path
+  if (l.mx) {   // packed rows of q_row_bytes on both sides, block-major scale images: [k / 32][rows]
+    const long kb = l.q_row_bytes();
     uint8_t* am = a.mx ? a.mx : e->buf<uint8_t>("a_mx");
-    if (!a.quantised) HIP_TRY(mc::launch_quantize_rows_mxfp4(a.rows, nullptr, a.ld, Lp, K, aq, K / 2, am, (long)Lp, s));
-    p.A = (const bf16_t*)aq; p.lda = K / 2; p.W = (const bf16_t*)(l.q + (size_t)out.first * (K / 2)); p.ldw = K / 2;
-    p.a_mx = am; p.mx_rows_a = (long)Lp; p.w_mx = l.mx + out.first; p.mx_rows_w = l.n_out;
-    HIP_TRY(mc::launch_gemm_mxfp4(p, epi, s));
-    return MC_OK;
-  }
-  if (l.fp6) {   // MXFP6 (option "mx_fp6"): packed rows of 3 K / 4 bytes on both sides, the scale images of the MX path
-    const long kb = (long)K / 4 * 3;
-    uint8_t* am = a.mx ? a.mx : e->buf<uint8_t>("a_mx");
-    if (!a.quantised) HIP_TRY(mc::launch_quantize_rows_mxfp6(a.rows, nullptr, a.ld, Lp, K, aq, kb, am, (long)Lp, s));
+    if (!a.quantised) HIP_TRY(mc::launch_quantize_rows_mx(l.fmt, a.rows, nullptr, a.ld, Lp, K, aq, kb, am, (long)Lp, s));
     p.A = (const bf16_t*)aq; p.lda = kb; p.W = (const bf16_t*)(l.q + (size_t)out.first * kb); p.ldw = kb;
     p.a_mx = am; p.mx_rows_a = (long)Lp; p.w_mx = l.mx + out.first; p.mx_rows_w = l.n_out;
-    HIP_TRY(mc::launch_gemm_mxfp6(p, epi, s));
+    HIP_TRY(mc::launch_gemm_mx(l.fmt, p, epi, s));
     return MC_OK;
   }
   p.A = (const bf16_t*)aq; p.lda = K; p.W = (const bf16_t*)(l.q + (size_t)out.first * K); p.ldw = K;
-  if (l.mx) {
-    uint8_t* am = a.mx ? a.mx : e->buf<uint8_t>("a_mx");
-    if (!a.quantised) HIP_TRY(mc::launch_quantize_rows_mx(a.rows, nullptr, a.ld, Lp, K, aq, K, am, (long)Lp, s));
-    p.a_mx = am; p.mx_rows_a = (long)Lp; p.w_mx = l.mx + out.first; p.mx_rows_w = l.n_out;   // block-major: [k / 32][n_out]
-    HIP_TRY(mc::launch_gemm_mxfp8(p, epi, s));
-    return MC_OK;
-  }
   float* as = e->buf<float>("a_scale");
   if (!a.quantised) HIP_TRY(mc::launch_quantize_rows_fp8(a.rows, nullptr, a.ld, Lp, K, aq, K, as, s));
   p.a_scale = as; p.w_scale = l.q_scale + out.first;
@@ -460,7 +449,7 @@ int g_fp8_fused_quant = 1;
 // (one stream, merged in place launch by launch)
 int g_sp_attn_partials = 1;
 // option "mx_fp4" (0 | 1): read once by mc_create; 1 with fp8_linear 2 | 3 = the MX Linears hold an MXFP4 copy (W4A4,
-// gemm_mxfp4.hip) and their activations are quantised by separate passes.  The engine keeps what it read (mc_engine::mx_fp4).
+// gemm_mxfp4.hip) and their activations are quantised by separate passes.  The engine keeps what it read (mc_engine::mx_fmt).
 int g_mx_fp4 = 0;
 // option "mx_fp6" (0 | 1): the same latch for MXFP6 copies (W6A6, gemm_mxfp6.hip); a create call that finds both at 1 is refused
 int g_mx_fp6 = 0;
@@ -523,30 +512,17 @@ mc_status mc_create(const mc_config* cfg, mc_engine** out) {
 
   // fp8_linear only decides which Linears keep an e4m3 copy and of which kind: 1 = QKV, FFN-1, FFN-2 with per-row scales,
   // 2 = the same three with MX block scales, 3 = MX, the d x d Linears (self-attention O, cross-attention Q and O) too
-  // option "mx_fp4" (latched here): the MX copies are MXFP4 instead.  dim and ffn_dim are multiples of 256 and >= 512 by the
-  // fp8_linear check above, which is what gemm_mxfp4's K tiling asks of a Linear's k_in; checked again by name so that a
+  // options "mx_fp4" / "mx_fp6" (latched here): the element format of the MX copies.  dim and ffn_dim are multiples of 256 and
+  // >= 512 by the fp8_linear check above, which is what the MX GEMMs ask of a Linear's k_in; checked again by name so that a
   // width the kernel cannot tile is refused here, never met at a launch
-  if (mc::g_mx_fp4 != 0 && mc::g_mx_fp6 != 0)
-    return fail(MC_EINVAL, "the options \"mx_fp4\" and \"mx_fp6\" are both 1: an engine's MX Linears hold one element format, set one of them");
-  e->mx_fp4 = mc::g_mx_fp4 != 0 && c.fp8_linear >= 2;
-  e->mx_fp6 = mc::g_mx_fp6 != 0 && c.fp8_linear >= 2;
-  if (e->mx_fp6) {
-    const struct { const char* name; int k; } widths[] = {{"self_attn.q|k|v / ffn.0 / the dim x dim Linears (in_features = dim)", c.dim},
-                                                          {"ffn.2 (in_features = ffn_dim)", c.ffn_dim}};
-    for (const auto& w : widths)
-      if ((w.k % 256) != 0 || w.k < 512)
-        return fail(MC_EINVAL, "mx_fp6: %s: %d input features are no multiple of 256 >= 512 (the K contract of the MXFP6 GEMM)", w.name, w.k);
+  MC_TRY(mc::latch_mx_format(c.fp8_linear >= 2, &e->mx_fmt));
+  if (e->mx_fmt != mc::MX_E4M3) {
+    MC_TRY(mc::check_mx_k(e->mx_fmt, "self_attn.q|k|v / ffn.0 / the dim x dim Linears (in_features = dim)", c.dim));
+    MC_TRY(mc::check_mx_k(e->mx_fmt, "ffn.2 (in_features = ffn_dim)", c.ffn_dim));
   }
-  if (e->mx_fp4) {
-    const struct { const char* name; int k; } widths[] = {{"self_attn.q|k|v / ffn.0 / the dim x dim Linears (in_features = dim)", c.dim},
-                                                          {"ffn.2 (in_features = ffn_dim)", c.ffn_dim}};
-    for (const auto& w : widths)
-      if ((w.k % 256) != 0 || w.k < 512)
-        return fail(MC_EINVAL, "mx_fp4: %s: %d input features are no multiple of 256 >= 512 (the K tile of the MXFP4 GEMM)", w.name, w.k);
-  }
-  const mc::Quant q_mx = e->mx_fp4 ? mc::QUANT_MXFP4 : e->mx_fp6 ? mc::QUANT_MXFP6 : mc::QUANT_MX;
-  const mc::Quant q_big = c.fp8_linear >= 2 ? q_mx : c.fp8_linear == 1 ? mc::QUANT_ROW : mc::QUANT_NONE;
-  const mc::Quant q_dd = c.fp8_linear == 3 ? q_mx : mc::QUANT_NONE;
+  const mc::MxFormat fmt = e->mx_fmt;
+  const mc::Quant q_big = c.fp8_linear >= 2 ? mc::QUANT_MX : c.fp8_linear == 1 ? mc::QUANT_ROW : mc::QUANT_NONE;
+  const mc::Quant q_dd = c.fp8_linear == 3 ? mc::QUANT_MX : mc::QUANT_NONE;
   e->layers.resize(e->NL);
   e->NV = c.vace_layers;
   e->vlayers.resize(e->NV);
@@ -555,13 +531,13 @@ mc_status mc_create(const mc_config* cfg, mc_engine** out) {
     Layer& l = is_vace ? e->vlayers[i - e->NL] : e->layers[i];
     l.index = i;
     const std::string p = (is_vace ? "vace_blocks." + std::to_string(i - e->NL) : "blocks." + std::to_string(i)) + ".";
-    MC_TRY(W.add_linear(l.qkv, p + "self_attn.", {{"q", d}, {"k", d}, {"v", d}}, d, q_big));
-    MC_TRY(W.add_linear(l.o, p + "self_attn.", {{"o", d}}, d, q_dd));
-    MC_TRY(W.add_linear(l.cq, p + "cross_attn.", {{"q", d}}, d, q_dd));
+    MC_TRY(W.add_linear(l.qkv, p + "self_attn.", {{"q", d}, {"k", d}, {"v", d}}, d, q_big, fmt));
+    MC_TRY(W.add_linear(l.o, p + "self_attn.", {{"o", d}}, d, q_dd, fmt));
+    MC_TRY(W.add_linear(l.cq, p + "cross_attn.", {{"q", d}}, d, q_dd, fmt));
     MC_TRY(W.add_linear(l.ckv, p + "cross_attn.", {{"k", d}, {"v", d}}, d));
-    MC_TRY(W.add_linear(l.co, p + "cross_attn.", {{"o", d}}, d, q_dd));
-    MC_TRY(W.add_linear(l.ffn1, p + "ffn.", {{"0", ffn}}, d, q_big));
-    MC_TRY(W.add_linear(l.ffn2, p + "ffn.", {{"2", d}}, ffn, q_big));
+    MC_TRY(W.add_linear(l.co, p + "cross_attn.", {{"o", d}}, d, q_dd, fmt));
+    MC_TRY(W.add_linear(l.ffn1, p + "ffn.", {{"0", ffn}}, d, q_big, fmt));
+    MC_TRY(W.add_linear(l.ffn2, p + "ffn.", {{"2", d}}, ffn, q_big, fmt));
     MC_TRY(W.add_f32(l.nq, p + "self_attn.norm_q.weight", d));
     MC_TRY(W.add_f32(l.nk, p + "self_attn.norm_k.weight", d));
     MC_TRY(W.add_f32(l.n3w, p + "norm3.weight", d));
@@ -641,8 +617,8 @@ void mc_destroy(mc_engine* e) {
 
 size_t mc_workspace_bytes(const mc_engine* e) { return e ? e->work.need : 0; }
 
-int mc_engine_mx_fp4(const mc_engine* e) { return e && e->mx_fp4 ? 1 : 0; }
-int mc_engine_mx_fp6(const mc_engine* e) { return e && e->mx_fp6 ? 1 : 0; }
+int mc_engine_mx_fp4(const mc_engine* e) { return e && e->mx_fmt == mc::MX_E2M1 ? 1 : 0; }
+int mc_engine_mx_fp6(const mc_engine* e) { return e && e->mx_fmt == mc::MX_E2M3 ? 1 : 0; }
 
 mc_status mc_set_workspace(mc_engine* e, void* ws_dev, size_t bytes) {
   if (!e) return fail(MC_EINVAL, "null argument");
@@ -936,7 +912,7 @@ static mc_status ln_for_gemm(mc_engine* e, const Linear& l, const float* x, cons
                              const float* sc2, const float* sh2, const uint8_t* sel, hipStream_t s, ActSrc* a) {
   const int d = e->d, Lp = e->Lp;
   bf16_t* xn = e->buf<bf16_t>("xn");
-  *a = ActSrc{xn, d, l.q && mc::g_fp8_fused_quant && !l.fp4 && !l.fp6};   // MXFP4 / MXFP6 have no fused producer here: the separate pass
+  *a = ActSrc{xn, d, fused_quant(l)};
   if (a->quantised) {
     HIP_TRY(mc::launch_ln_modulate_fp8(x, d, sc, sh, mode, e->cfg.eps, e->buf<uint8_t>("aq"), d,
                                        l.mx ? nullptr : e->buf<float>("a_scale"), l.mx ? e->buf<uint8_t>("a_mx") : nullptr,
@@ -1263,7 +1239,7 @@ static mc_status block_post_ctx(mc_engine* e, const Layer& l, const float* em, f
   p.Cb = h; p.ldc = ffn;
   // MX with fused quantisers: FFN-1's GELU epilogue writes the e4m3 rows + block scales FFN-2 reads (both inside "h":
   // Lp * ffn bytes, then ffn / 32 * Lp scale bytes), the bf16 hidden tensor never exists
-  const bool h_fp8 = l.ffn1.mx && l.ffn2.mx && mc::g_fp8_fused_quant && !l.ffn1.fp4 && !l.ffn1.fp6;
+  const bool h_fp8 = l.ffn1.mx && l.ffn2.mx && fused_quant(l.ffn1);
   ActSrc hidden{h, ffn};
   if (h_fp8) {
     hidden.quantised = true; hidden.q = (uint8_t*)h; hidden.mx = hidden.q + (size_t)Lp * ffn;

@@ -382,56 +382,17 @@ hipError_t launch_mx4_t(const GemmParams& p, hipStream_t stream) {
 }
 
 // ------------------------------------------------------------------ MXFP4 quantisation of rows
-// One wave per row; lane b (+64, +128, ...) owns the 32-element block b: scale exponent e = mxfp4_exponent(amax), codes
-// e2m1(x * 2^-e) packed into 16 bytes, scale byte e + 127 at s[b * rows_pad + mx_scale_row(row)] (all of it quant.h).
+// quant.h's body with this format's exponent and packing
 __global__ __launch_bounds__(256) void quantize_rows_mxfp4_kernel(const bf16_t* __restrict__ x, const float* __restrict__ xf,
                                                                   long ldx, int M, int K, uint8_t* __restrict__ q, long ldq,
                                                                   uint8_t* __restrict__ s, long rows_pad) {
-  const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= M) return;
-  for (int b = lane; b < K / 32; b += 64) {
-    float v[32];
-    if (xf) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const f32x4 t = *(const f32x4*)(xf + (size_t)row * ldx + b * 32 + i * 4);
-        v[4 * i] = t[0]; v[4 * i + 1] = t[1]; v[4 * i + 2] = t[2]; v[4 * i + 3] = t[3];
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const u32x4 t = *(const u32x4*)(x + (size_t)row * ldx + b * 32 + i * 8);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          v[8 * i + 2 * j] = __uint_as_float(t[j] << 16);
-          v[8 * i + 2 * j + 1] = __uint_as_float(t[j] & 0xffff0000u);
-        }
-      }
-    }
-    float amax = 0.f;
-#pragma unroll
-    for (int i = 0; i < 32; ++i) amax = fmaxf(amax, fabsf(v[i]));
-    const int e = mxfp4_exponent(amax);
-    const float inv = mx_inv_scale(e);
-    *(u32x4*)(q + (size_t)row * ldq + b * 16) =
-        u32x4{pack8_e2m1(v, inv), pack8_e2m1(v + 8, inv), pack8_e2m1(v + 16, inv), pack8_e2m1(v + 24, inv)};
-    s[(size_t)b * rows_pad + mx_scale_row(row)] = mx_scale_byte(e);
-  }
+  MC_QUANTIZE_ROWS_MX_BODY(QuantE2m1)
 }
 
 }  // namespace
 
-bool gemm_mxfp4_supported(const GemmParams& p) {
-  return p.M > 0 && p.N > 0 && (p.N % TB) == 0 && p.K >= 2 * BKE && (p.K % BKE) == 0 && (p.lda % 16) == 0 && (p.ldw % 16) == 0 &&
-         p.lda >= p.K / 2 && p.ldw >= p.K / 2 && p.A && p.W && (((uintptr_t)p.A | (uintptr_t)p.W) & 15) == 0 &&
-         (size_t)p.M * (size_t)p.lda < (1ull << 32) && (size_t)p.N * (size_t)p.ldw < (1ull << 32) && p.a_mx && p.w_mx &&
-         (((uintptr_t)p.a_mx | (uintptr_t)p.w_mx) & 3) == 0 && p.mx_rows_a >= (long)((p.M + TB - 1) / TB) * TB &&
-         p.mx_rows_w >= p.N && (p.mx_rows_a % 64) == 0 && (p.mx_rows_w % 64) == 0;
-}
-
 hipError_t launch_gemm_mxfp4(const GemmParams& p, int epi, hipStream_t stream) {
-  if (!gemm_mxfp4_supported(p)) return hipErrorInvalidValue;
+  if (!gemm_mx_supported(MX_E2M1, p)) return hipErrorInvalidValue;
   switch (epi) {
     case EPI_BF16: return p.Cb ? launch_mx4_t<EPI_BF16>(p, stream) : hipErrorInvalidValue;
     case EPI_GELU_BF16: return p.Cb ? launch_mx4_t<EPI_GELU_BF16>(p, stream) : hipErrorInvalidValue;
@@ -449,13 +410,7 @@ hipError_t launch_gemm_mxfp4(const GemmParams& p, int epi, hipStream_t stream) {
 
 hipError_t launch_quantize_rows_mxfp4(const bf16_t* x, const float* x_f32, long ldx, int M, int K, uint8_t* q, long ldq,
                                       uint8_t* s, long rows_pad, hipStream_t stream) {
-  if ((!x && !x_f32) || !q || !s || M <= 0 || K <= 0 || (K % 32) != 0 || (ldx % 8) != 0 || ldx < K || (ldq % 16) != 0 ||
-      ldq < K / 2 || rows_pad < ((M + 63) / 64) * 64 || (rows_pad % 64) != 0 ||
-      (((uintptr_t)x | (uintptr_t)x_f32 | (uintptr_t)q) & 15) != 0)
-    return hipErrorInvalidValue;
-  hipLaunchKernelGGL(quantize_rows_mxfp4_kernel, dim3((M + 3) / 4), dim3(256), 0, stream, x, x_f32, ldx, M, K, q, ldq, s,
-                     rows_pad);
-  return hipGetLastError();
+  return launch_quantize_rows_mx_kernel<quantize_rows_mxfp4_kernel>(MX_E2M1, x, x_f32, ldx, M, K, q, ldq, s, rows_pad, stream);
 }
 
 }  // namespace mc

@@ -89,7 +89,7 @@ __global__ __launch_bounds__(512, 2) void gemm_mxfp6_kernel(GemmParams p, int ti
   // ---- LDS-DMA sources.  This wave's 32 rows of an operand = 3 instructions; lane -> byte P = 1024 j + 16 lane of the group's
   // dense image = row P / 96, bytes [P % 96, + 16).  The row guard of gemm_mxfp8.hip, per lane: an A row behind M - 1 is replaced
   // by row M - 1 (its bytes land in the missing row's place and reach no stored value).  No byte behind row M - 1 is read.
-  // (32-bit offsets: M * lda and N * ldw are below 2^32, gemm_mxfp6_supported.)
+  // (32-bit offsets: M * lda and N * ldw are below 2^32, gemm_mx_supported.)
   const uint8_t* Aq = (const uint8_t*)p.A;
   const uint8_t* Wq = (const uint8_t*)p.W;
   uint32_t srcA[3], srcW[3];
@@ -265,16 +265,8 @@ __global__ __launch_bounds__(256) void quantize_rows_mxfp6_kernel(const bf16_t* 
 
 }  // namespace
 
-bool gemm_mxfp6_supported(const GemmParams& p) {
-  return p.M > 0 && p.N > 0 && (p.N % TB) == 0 && p.K >= 512 && (p.K % 256) == 0 && (p.lda % 16) == 0 && (p.ldw % 16) == 0 &&
-         p.lda >= p.K / 4 * 3 && p.ldw >= p.K / 4 * 3 && p.A && p.W && (((uintptr_t)p.A | (uintptr_t)p.W) & 15) == 0 &&
-         (size_t)p.M * (size_t)p.lda < (1ull << 32) && (size_t)p.N * (size_t)p.ldw < (1ull << 32) && p.a_mx && p.w_mx &&
-         (((uintptr_t)p.a_mx | (uintptr_t)p.w_mx) & 3) == 0 && p.mx_rows_a >= (long)((p.M + TB - 1) / TB) * TB &&
-         p.mx_rows_w >= p.N && (p.mx_rows_a % 64) == 0 && (p.mx_rows_w % 64) == 0;
-}
-
 hipError_t launch_gemm_mxfp6(const GemmParams& p, int epi, hipStream_t stream) {
-  if (!gemm_mxfp6_supported(p)) return hipErrorInvalidValue;
+  if (!gemm_mx_supported(MX_E2M3, p)) return hipErrorInvalidValue;
   switch (epi) {
     case EPI_BF16: return p.Cb ? launch_mx6_t<EPI_BF16>(p, stream) : hipErrorInvalidValue;
     case EPI_GELU_BF16: return p.Cb ? launch_mx6_t<EPI_GELU_BF16>(p, stream) : hipErrorInvalidValue;
@@ -287,13 +279,7 @@ hipError_t launch_gemm_mxfp6(const GemmParams& p, int epi, hipStream_t stream) {
 
 hipError_t launch_quantize_rows_mxfp6(const bf16_t* x, const float* x_f32, long ldx, int M, int K, uint8_t* q, long ldq,
                                       uint8_t* s, long rows_pad, hipStream_t stream) {
-  if ((!x && !x_f32) || !q || !s || M <= 0 || K <= 0 || (K % 32) != 0 || (ldx % 8) != 0 || ldx < K || (ldq % 16) != 0 ||
-      ldq < K / 4 * 3 || rows_pad < ((M + 63) / 64) * 64 || (rows_pad % 64) != 0 ||
-      (((uintptr_t)x | (uintptr_t)x_f32 | (uintptr_t)q) & 15) != 0)
-    return hipErrorInvalidValue;
-  hipLaunchKernelGGL(quantize_rows_mxfp6_kernel, dim3((M + 3) / 4), dim3(256), 0, stream, x, x_f32, ldx, M, K, q, ldq, s,
-                     rows_pad);
-  return hipGetLastError();
+  return launch_quantize_rows_mx_kernel<quantize_rows_mxfp6_kernel>(MX_E2M3, x, x_f32, ldx, M, K, q, ldq, s, rows_pad, stream);
 }
 
 }  // namespace mc

@@ -359,59 +359,17 @@ hipError_t launch_mx_t(const GemmParams& p, hipStream_t stream) {
 }
 
 // ------------------------------------------------------------------ MX quantisation of rows
-// One wave per row; lane b (+64, +128, ...) owns the 32-element block b: scale exponent e = mx_exponent(amax), elements
-// e4m3(x * 2^-e), scale byte e + 127 at s[b * rows_pad + mx_scale_row(row)] (all of it quant.h).
+// quant.h's body with this format's exponent and packing
 __global__ __launch_bounds__(256) void quantize_rows_mx_kernel(const bf16_t* __restrict__ x, const float* __restrict__ xf,
                                                                long ldx, int M, int K, uint8_t* __restrict__ q, long ldq,
                                                                uint8_t* __restrict__ s, long rows_pad) {
-  const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= M) return;
-  for (int b = lane; b < K / 32; b += 64) {
-    float v[32];
-    if (xf) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const f32x4 t = *(const f32x4*)(xf + (size_t)row * ldx + b * 32 + i * 4);
-        v[4 * i] = t[0]; v[4 * i + 1] = t[1]; v[4 * i + 2] = t[2]; v[4 * i + 3] = t[3];
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const u32x4 t = *(const u32x4*)(x + (size_t)row * ldx + b * 32 + i * 8);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          v[8 * i + 2 * j] = __uint_as_float(t[j] << 16);
-          v[8 * i + 2 * j + 1] = __uint_as_float(t[j] & 0xffff0000u);
-        }
-      }
-    }
-    float amax = 0.f;
-#pragma unroll
-    for (int i = 0; i < 32; ++i) amax = fmaxf(amax, fabsf(v[i]));
-    const int e = mx_exponent(amax);
-    const float inv = mx_inv_scale(e);
-    uint32_t w[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) w[i] = (uint32_t)pack4_e4m3(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3], inv);
-    u32x4* dst = (u32x4*)(q + (size_t)row * ldq + b * 32);
-    dst[0] = u32x4{w[0], w[1], w[2], w[3]};
-    dst[1] = u32x4{w[4], w[5], w[6], w[7]};
-    s[(size_t)b * rows_pad + mx_scale_row(row)] = mx_scale_byte(e);
-  }
+  MC_QUANTIZE_ROWS_MX_BODY(QuantE4m3)
 }
 
 }  // namespace
 
-bool gemm_mxfp8_supported(const GemmParams& p) {
-  return p.M > 0 && p.N > 0 && (p.N % TB) == 0 && (p.K % (2 * BKB)) == 0 && p.K >= 4 * BKB && (p.lda % 16) == 0 &&
-         (p.ldw % 16) == 0 && (size_t)p.M * (size_t)p.lda < (1ull << 32) && (size_t)p.N * (size_t)p.ldw < (1ull << 32) &&
-         p.a_mx && p.w_mx && p.mx_rows_a >= (long)((p.M + TB - 1) / TB) * TB && p.mx_rows_w >= p.N &&
-         (p.mx_rows_a % 64) == 0 && (p.mx_rows_w % 64) == 0;
-}
-
 hipError_t launch_gemm_mxfp8(const GemmParams& p, int epi, hipStream_t stream) {
-  if (!gemm_mxfp8_supported(p)) return hipErrorInvalidValue;
+  if (!gemm_mx_supported(MX_E4M3, p)) return hipErrorInvalidValue;
   switch (epi) {
     case EPI_BF16: return launch_mx_t<EPI_BF16>(p, stream);
     case EPI_GELU_BF16: return launch_mx_t<EPI_GELU_BF16>(p, stream);
@@ -426,13 +384,9 @@ hipError_t launch_gemm_mxfp8(const GemmParams& p, int epi, hipStream_t stream) {
   }
 }
 
-hipError_t launch_quantize_rows_mx(const bf16_t* x, const float* x_f32, long ldx, int M, int K, uint8_t* q, long ldq,
-                                   uint8_t* s, long rows_pad, hipStream_t stream) {
-  if (M <= 0 || K <= 0 || (K % 32) != 0 || (ldx % 8) != 0 || (ldq % 16) != 0 || rows_pad < ((M + 63) / 64) * 64 || (rows_pad % 64) != 0)
-    return hipErrorInvalidValue;
-  hipLaunchKernelGGL(quantize_rows_mx_kernel, dim3((M + 3) / 4), dim3(256), 0, stream, x, x_f32, ldx, M, K, q, ldq, s,
-                     rows_pad);
-  return hipGetLastError();
+hipError_t launch_quantize_rows_mxfp8(const bf16_t* x, const float* x_f32, long ldx, int M, int K, uint8_t* q, long ldq,
+                                      uint8_t* s, long rows_pad, hipStream_t stream) {
+  return launch_quantize_rows_mx_kernel<quantize_rows_mx_kernel>(MX_E4M3, x, x_f32, ldx, M, K, q, ldq, s, rows_pad, stream);
 }
 
 }  // namespace mc

@@ -42,15 +42,18 @@ mc_status WeightStore::add_f32(float*& p, const std::string& name, size_t numel,
   return MC_OK;
 }
 
-mc_status WeightStore::alloc_linear(Linear& l, size_t n_out, size_t k_in, Quant quant) {
+mc_status WeightStore::alloc_linear(Linear& l, size_t n_out, size_t k_in, Quant quant, MxFormat fmt) {
   l.n_out = (int)n_out; l.k_in = (int)k_in;
+  l.fmt = fmt;
   MC_TRY(alloc(&l.w, n_out * k_in));
   MC_TRY(alloc(&l.b, n_out));
-  l.fp4 = quant == QUANT_MXFP4;
-  l.fp6 = quant == QUANT_MXFP6;
-  if (quant != QUANT_NONE) MC_TRY(alloc(&l.q, l.fp4 ? n_out * k_in / 2 : l.fp6 ? n_out * k_in / 4 * 3 : n_out * k_in));
-  if (quant == QUANT_ROW) MC_TRY(alloc(&l.q_scale, n_out));
-  if (quant == QUANT_MX || quant == QUANT_MXFP4 || quant == QUANT_MXFP6) MC_TRY(alloc(&l.mx, (k_in / 32) * n_out));
+  if (quant == QUANT_ROW) {
+    MC_TRY(alloc(&l.q, n_out * k_in));
+    MC_TRY(alloc(&l.q_scale, n_out));
+  } else if (quant == QUANT_MX) {
+    MC_TRY(alloc(&l.q, n_out * (size_t)mx_row_bytes(fmt, (long)k_in)));
+    MC_TRY(alloc(&l.mx, (k_in / 32) * n_out));
+  }
   return MC_OK;
 }
 
@@ -61,17 +64,18 @@ Slot& WeightStore::add_parts(Linear& l, const std::string& prefix, const std::ve
     add(prefix + part.name + ".bias", l.b, MC_F32, part.rows, row0);
     last = &add(prefix + part.name + ".weight", l.w, MC_BF16, part.rows * k, row0 * k);
     last->q8 = l.q; last->q8_scale = l.q_scale; last->q8_k = k; last->mx = l.mx; last->mx_rows = l.n_out;
-    last->fp4 = l.fp4; last->fp6 = l.fp6;
+    last->fmt = l.fmt;
     last->lin = &l;
     row0 += part.rows;
   }
   return *last;
 }
 
-mc_status WeightStore::add_linear(Linear& l, const std::string& prefix, const std::vector<Part>& parts, size_t k_in, Quant quant) {
+mc_status WeightStore::add_linear(Linear& l, const std::string& prefix, const std::vector<Part>& parts, size_t k_in, Quant quant,
+                                  MxFormat fmt) {
   size_t n_out = 0;
   for (const Part& part : parts) n_out += part.rows;
-  MC_TRY(alloc_linear(l, n_out, k_in, quant));
+  MC_TRY(alloc_linear(l, n_out, k_in, quant, fmt));
   add_parts(l, prefix, parts);
   return MC_OK;
 }
@@ -125,20 +129,29 @@ mc_status WeightStore::requantise(const Slot& s, hipStream_t stream) {
   if (!s.q8) return MC_OK;
   const bf16_t* src = (const bf16_t*)s.dst + s.off;
   const size_t rows = s.numel / s.q8_k, row0 = s.off / s.q8_k;
-  if (s.fp4) {  // MXFP4: packed rows of q8_k / 2 bytes, the scale image of MX
-    HIP_TRY(launch_quantize_rows_mxfp4(src, nullptr, (long)s.q8_k, (int)rows, (int)s.q8_k, s.q8 + s.off / 2, (long)s.q8_k / 2,
-                                       s.mx + row0, (long)s.mx_rows, stream));
-  } else if (s.fp6) {  // MXFP6: packed rows of 3 q8_k / 4 bytes (s.off is a whole number of rows), the scale image of MX
-    HIP_TRY(launch_quantize_rows_mxfp6(src, nullptr, (long)s.q8_k, (int)rows, (int)s.q8_k, s.q8 + s.off / 4 * 3, (long)s.q8_k / 4 * 3,
-                                       s.mx + row0, (long)s.mx_rows, stream));
-  } else if (s.mx) {  // MX: the e4m3 bytes are relative to the block scales, not to a row scale
-    HIP_TRY(launch_quantize_rows_mx(src, nullptr, (long)s.q8_k, (int)rows, (int)s.q8_k, s.q8 + s.off, (long)s.q8_k, s.mx + row0,
-                                    (long)s.mx_rows, stream));
+  if (s.mx) {  // MX: the packed rows are relative to the block scales, not to a row scale (s.off is a whole number of rows)
+    const long row_bytes = mx_row_bytes(s.fmt, (long)s.q8_k);
+    HIP_TRY(launch_quantize_rows_mx(s.fmt, src, nullptr, (long)s.q8_k, (int)rows, (int)s.q8_k, s.q8 + row0 * row_bytes, row_bytes,
+                                    s.mx + row0, (long)s.mx_rows, stream));
   } else {
     HIP_TRY(launch_quantize_rows_fp8(src, nullptr, (long)s.q8_k, (int)rows, (int)s.q8_k, s.q8 + s.off, (long)s.q8_k,
                                      s.q8_scale + row0, stream));
   }
   return MC_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ the MX format latch
+mc_status latch_mx_format(bool mx_linears, MxFormat* out) {
+  if (g_mx_fp4 != 0 && g_mx_fp6 != 0)
+    return fail(MC_EINVAL, "the options \"mx_fp4\" and \"mx_fp6\" are both 1: an engine's MX Linears hold one element format, set one of them");
+  *out = !mx_linears ? MX_E4M3 : g_mx_fp4 != 0 ? MX_E2M1 : g_mx_fp6 != 0 ? MX_E2M3 : MX_E4M3;
+  return MC_OK;
+}
+
+mc_status check_mx_k(MxFormat fmt, const char* what, int k) {
+  if ((k % 256) == 0 && k >= 512) return MC_OK;
+  return fail(MC_EINVAL, "%s: %s: %d input features are no multiple of 256 >= 512 (the K contract of the %s GEMM)", mx_info(fmt).option,
+              what, k, mx_info(fmt).name);
 }
 
 // ------------------------------------------------------------------------------------------------ LoRA adapters

@@ -36,15 +36,15 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 // mc_set_option values (ops_capi.cpp sets them), each defined in the file that reads it
 extern int g_fp8_fused_quant;    // engine.cpp
 extern int g_sp_attn_partials;   // engine.cpp
-extern int g_mx_fp4;             // engine.cpp: read once by mc_create and by mc_mmdit_create / _create_sized
+extern int g_mx_fp4;             // engine.cpp: read once, through latch_mx_format, by mc_create and by mc_mmdit_create / _create_sized
 extern int g_mx_fp6;             // engine.cpp: the same for MXFP6; both 1 at create time is MC_EINVAL
 extern int g_mmdit_two_streams;  // mmdit_engine.cpp
 
 // ---------------------------------------------------------------- weights
 // y = x W^T + b with W [n_out, k_in] bf16 and, optionally, an e4m3 copy of W made when the weight is set: with one scale
 // per output channel (q_scale) or with MX block scales (mx: E8M0, block-major [k_in / 32][n_out]).  q == null: bf16 only.
-// fp4: the copy is MXFP4 instead -- e2m1 codes, two per byte, rows of k_in / 2 bytes in q, the same scale image in mx (quant.h).
-// fp6: the copy is MXFP6 -- e2m3 codes, 32 per 24 bytes, rows of 3 k_in / 4 bytes in q, the same scale image.
+// fmt (meaningful where mx != null): the element format of the MX copy -- packed rows of mx_row_bytes(fmt, k_in) bytes in q
+// (ops.h: MxFormat), the same scale image for every format.
 struct Linear {
   bf16_t* w = nullptr;
   float* b = nullptr;
@@ -52,12 +52,12 @@ struct Linear {
   uint8_t* q = nullptr;
   float* q_scale = nullptr;
   uint8_t* mx = nullptr;
-  bool fp4 = false;
-  bool fp6 = false;
+  MxFormat fmt = MX_E4M3;
   bf16_t* w_base = nullptr;  // the pristine weight while a LoRA adapter touches this Linear (w is then the merged one)
+  long q_row_bytes() const { return mx ? mx_row_bytes(fmt, k_in) : k_in; }   // of one row of q
 };
-// one scale per output channel | one E8M0 byte per (channel, 32 inputs) with e4m3 elements | the same with e2m1 | e2m3 elements
-enum Quant { QUANT_NONE, QUANT_ROW, QUANT_MX, QUANT_MXFP4, QUANT_MXFP6 };
+// one scale per output channel | one E8M0 byte per (channel, 32 inputs), the elements in the MxFormat given beside it
+enum Quant { QUANT_NONE, QUANT_ROW, QUANT_MX };
 struct Part { std::string name; size_t rows; };   // an upstream Linear whose rows are stacked into a fused one (q | k | v -> qkv)
 struct RowRange { int first, count; };            // output channels of a Linear: all of them, or k|v / q of the fused q|k|v
 inline RowRange whole(const Linear& l) { return {0, l.n_out}; }
@@ -77,8 +77,7 @@ struct Slot {  // one named parameter
   size_t q8_k = 0;  // row length (in_features)
   uint8_t* mx = nullptr;
   size_t mx_rows = 0;
-  bool fp4 = false;   // the copy is MXFP4: packed rows of q8_k / 2 bytes
-  bool fp6 = false;   // the copy is MXFP6: packed rows of 3 q8_k / 4 bytes
+  MxFormat fmt = MX_E4M3;   // mx != null: the copy's element format, packed rows of mx_row_bytes(fmt, q8_k) bytes
   Linear* lin = nullptr;  // the Linear whose rows this weight is (add_parts); null for every other parameter
   // adapters on an fp32 parameter (WeightStore::allow_f32_targets)
   size_t f32_k = 0;           // > 0: an fp32 matrix [numel / f32_k, f32_k], which takes low-rank pairs; 0: deltas only
@@ -114,11 +113,12 @@ struct WeightStore {
   // an fp32 parameter that is no Linear's (norm weights, modulation, the fp32 matrices of a GEMV): allocates and registers it
   // (k_in > 0: a matrix [numel / k_in, k_in], Slot::f32_k)
   mc_status add_f32(float*& p, const std::string& name, size_t numel, size_t k_in = 0);
-  // One Linear [sum of the parts' rows, k_in]: allocates the bf16 weight + fp32 bias (and, quant != QUANT_NONE, the e4m3 copy
-  // with its scales) and registers the parts.  alloc_linear / add_parts are its two halves, for a Linear whose parts are
+  // One Linear [sum of the parts' rows, k_in]: allocates the bf16 weight + fp32 bias (and, quant != QUANT_NONE, the quantised
+  // copy with its scales; fmt: its element format where quant == QUANT_MX) and registers the parts.  alloc_linear / add_parts are its two halves, for a Linear whose parts are
   // added one by one (the fused modulation matrix) or whose slot the caller adjusts (Slot::pad, Slot::perm_c).
-  mc_status add_linear(Linear& l, const std::string& prefix, const std::vector<Part>& parts, size_t k_in, Quant quant = QUANT_NONE);
-  mc_status alloc_linear(Linear& l, size_t n_out, size_t k_in, Quant quant = QUANT_NONE);
+  mc_status add_linear(Linear& l, const std::string& prefix, const std::vector<Part>& parts, size_t k_in, Quant quant = QUANT_NONE,
+                       MxFormat fmt = MX_E4M3);
+  mc_status alloc_linear(Linear& l, size_t n_out, size_t k_in, Quant quant = QUANT_NONE, MxFormat fmt = MX_E4M3);
   // "<prefix><part>.weight" [rows, k_in] (bf16) and "<prefix><part>.bias" [rows] (fp32) of every part, stacked from row row0 of
   // `l`; every slot carries the quantised copy, so that setting a part requantises its rows.  Returns the last weight's slot.
   Slot& add_parts(Linear& l, const std::string& prefix, const std::vector<Part>& parts, size_t row0 = 0);
@@ -170,6 +170,12 @@ struct WeightStore {
   std::map<std::string, float> lora_scales;   // adapter -> scale
   std::set<std::string> lora_dirty;           // weight slots to merge again
 };
+
+// The element format of an engine's MX Linears, read once by its create call from the options "mx_fp4" / "mx_fp6": MC_EINVAL for
+// both at 1; e4m3 when neither is set or the engine has no MX Linears (mx_linears false: fp8_linear < 2).
+mc_status latch_mx_format(bool mx_linears, MxFormat* out);
+// the K contract of the MX GEMMs on a Linear's in_features (a multiple of 256, at least 512); `what` names the Linear
+mc_status check_mx_k(MxFormat fmt, const char* what, int k);
 
 // ---------------------------------------------------------------- workspace
 struct Buf {

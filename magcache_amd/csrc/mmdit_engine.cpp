@@ -29,11 +29,11 @@
 //                           branch, residual0..3 with calibration), joint row index: the
 //                           capture is the epilogue of the LAST block's output GEMM (R = x_new - x0 per row); the image
 //                           rows are the cache, the text rows are scratch
-//   aq   e4m3 [S_pad, 5d]   (fp8_linear != 0 only) the quantised operand rows of the MX Linears, joint row index, columns as
+//   aq   packed [S_pad, 5d] (fp8_linear != 0 only) the quantised operand rows of the MX Linears, joint row index, columns as
 //                           "am": [0,d) the LayerNorm + modulate output (q|k|v, MLP-in, the single block's linear1) and, mode
 //                           3, the attention output (the output projections); [d,5d) GELU(MLP-in), MLP-out's operand
-//                           (option "mx_fp4": packed e2m1 instead, rows of 5d / 2 bytes, column c at byte c / 2, same order;
-//                           option "mx_fp6": packed e2m3, rows of 5d * 3 / 4 bytes, the 32 columns of block b in the 24 bytes at 24 b)
+//                           in the engine's element format (ops.h: MxFormat; e4m3, or e2m1 / e2m3 with the option "mx_fp4" /
+//                           "mx_fp6"): rows of mx_row_bytes(fmt, 5d) bytes, column c (a multiple of 32) at byte mx_row_bytes(fmt, c)
 //   a_mx E8M0               (fp8_linear != 0 only) the block scales of "aq".  A scale image is block-major [k / 32][rows_pad]
 //                           with the rows of every group of 64 interleaved RELATIVE TO THE LAUNCH'S FIRST ROW, so two row
 //                           ranges must not share one: three regions, [text | image | joint (the single blocks)], each
@@ -50,13 +50,12 @@
 // or two row ranges (Range) -- both streams in merged launches by default, one stream per call for the two-stream modes and
 // sequence parallel; every attention launch is attend() over a key set (Keys).
 // fp8_linear 2 / 3 (opt-in): the block Linears that read a LayerNorm or GELU output (3: the attention output too) keep an
-// e4m3 copy with MX block scales and run on launch_gemm_mxfp8 over the exact rows of ONE range (the kernel guards a partial
-// last tile and has no row-split launch): a double block is then one pass per stream, in row order, on the launch stream.
-// Option "mx_fp4" (read once by the create call, opt-in, W4A4): the same Linears hold an MXFP4 copy and run on
-// launch_gemm_mxfp4; "aq" holds packed e2m1 rows, written by the FP4 tail of the LayerNorm kernel and the EPI_GELU_MXFP4
-// epilogue (fp8_fused_quant 1) or by launch_quantize_rows_mxfp4 (0, and the attention output): the same bits either way.
-// Option "mx_fp6" (latched the same way, W6A6): an MXFP6 copy on launch_gemm_mxfp6; "aq" holds packed e2m3 rows, ALWAYS written
-// by launch_quantize_rows_mxfp6 -- the format has no fused producer, so fp8_fused_quant changes nothing (fused_quant below).
+// MX copy -- block scales, elements in the engine's MxFormat -- and run on launch_gemm_mx over the exact rows of ONE range (the
+// kernels guard a partial last tile and have no row-split launch): a double block is then one pass per stream, in row order, on
+// the launch stream.  The format is e4m3 unless the create call finds the option "mx_fp4" (W4A4, e2m1) or "mx_fp6" (W6A6, e2m3)
+// set (host.h: latch_mx_format).  "aq" is written by the quantising tail of the LayerNorm kernel and MLP-in's quantising GELU
+// epilogue (fp8_fused_quant 1; e4m3 and e2m1) or by launch_quantize_rows_mx (0, the attention output, and everything in e2m3,
+// which has no fused producer: fused_quant below): the same bits either way.
 #include <cmath>
 #include <memory>
 
@@ -120,8 +119,8 @@ struct mc_mmdit {
   int branch = 0;                                            // CFG branch of the forward in progress (Qwen-Image: 0 / 1)
   bool begun = false;
   int fp8 = 0;                                               // cfg.fp8_linear: 0 | 2 | 3
-  bool mx_fp4 = false;   // option "mx_fp4" as the create call read it (with fp8_linear 2 | 3): the MX Linears and "aq" are MXFP4
-  bool mx_fp6 = false;   // option "mx_fp6" likewise: MXFP6 (never both)
+  mc::MxFormat mx_fmt = mc::MX_E4M3;   // the element format of the MX Linears and of "aq" (fp8_linear 2 | 3), as the create call
+                                       // latched it from the options "mx_fp4" / "mx_fp6" (host.h: latch_mx_format)
   // optional second compute stream: the text stream of a double block next to the image stream (mc_set_option
   // "mmdit_two_streams"); a ring of event pairs so that an event is not re-recorded while an earlier wait on it may
   // still be queued
@@ -171,8 +170,7 @@ struct mc_mmdit {
 
 namespace {
 
-// The e4m3 rows [M, k_in] an MX Linear reads (ld bytes apart; MXFP4: packed e2m1 rows of k_in / 2 bytes; MXFP6: packed e2m3 rows
-// of 3 k_in / 4 bytes), with their scale
+// The packed rows [M, k_in] an MX Linear reads (ld bytes apart, mx_row_bytes of the Linear's format each), with their scale
 // image (rows_pad >= ceil256(M) rows per k block)
 struct MxRows {
   const uint8_t* q; long ld;
@@ -192,19 +190,9 @@ mc_status linear(const mc_mmdit* e, const Linear& l, int M, const bf16_t* A, lon
   if (l.q) {
     if (!l.mx || !a8 || lb) return fail(MC_ESTATE, "an MX Linear runs over one row range of quantised rows");
     p.M = M; p.N = out.count; p.K = l.k_in; p.bias = l.b + out.first;
-    p.A = (const bf16_t*)a8->q; p.lda = a8->ld; p.W = (const bf16_t*)(l.q + (size_t)out.first * l.k_in); p.ldw = l.k_in;
+    p.A = (const bf16_t*)a8->q; p.lda = a8->ld; p.W = (const bf16_t*)(l.q + (size_t)out.first * l.q_row_bytes()); p.ldw = l.q_row_bytes();
     p.a_mx = a8->mx; p.mx_rows_a = a8->rows_pad; p.w_mx = l.mx + out.first; p.mx_rows_w = l.n_out;   // block-major: [k / 32][n_out]
-    if (l.fp4) {   // packed rows of k_in / 2 bytes
-      p.W = (const bf16_t*)(l.q + (size_t)out.first * l.k_in / 2); p.ldw = l.k_in / 2;
-      HIP_TRY(mc::launch_gemm_mxfp4(p, epi, s));
-      return MC_OK;
-    }
-    if (l.fp6) {   // packed rows of 3 k_in / 4 bytes
-      p.W = (const bf16_t*)(l.q + (size_t)out.first * l.k_in / 4 * 3); p.ldw = l.k_in / 4 * 3;
-      HIP_TRY(mc::launch_gemm_mxfp6(p, epi, s));
-      return MC_OK;
-    }
-    HIP_TRY(mc::launch_gemm_mxfp8(p, epi, s));
+    HIP_TRY(mc::launch_gemm_mx(l.fmt, p, epi, s));
     return MC_OK;
   }
   if (lb && lb->q) return fail(MC_ESTATE, "an MX Linear runs over one row range of quantised rows");
@@ -241,20 +229,16 @@ struct MxDst {
 MxDst mx_at(const mc_mmdit* e, int row0, int rows, int col0, bool o_proj = false) {
   const MxRegion r = mx_region(e, row0, rows);
   const size_t blk = o_proj ? (size_t)5 * e->d / 32 : (size_t)col0 / 32;
-  if (e->mx_fp6)   // MXFP6 rows are 5d * 3 / 4 bytes, column c (a multiple of 32) at byte 3 c / 4
-    return {e->buf<uint8_t>("aq") + ((size_t)row0 * 5 * e->d + col0) / 4 * 3, 5L * e->d / 4 * 3, r.base + blk * r.rows_pad, r.rows_pad};
-  const int per = e->mx_fp4 ? 2 : 1;   // elements per byte: MXFP4 rows are 5d / 2 bytes, column c at byte c / 2
-  return {e->buf<uint8_t>("aq") + ((size_t)row0 * 5 * e->d + col0) / per, 5L * e->d / per, r.base + blk * r.rows_pad, r.rows_pad};
+  const long ld = mc::mx_row_bytes(e->mx_fmt, 5L * e->d);   // col0 is a multiple of 32
+  return {e->buf<uint8_t>("aq") + (size_t)row0 * ld + mc::mx_row_bytes(e->mx_fmt, col0), ld, r.base + blk * r.rows_pad, r.rows_pad};
 }
 // the fused-quantising GELU epilogue of the engine's format
-int gelu_quant_epi(const mc_mmdit* e) { return e->mx_fp4 ? mc::EPI_GELU_MXFP4 : mc::EPI_GELU_MXFP8; }
-// do the producers (the LayerNorm tail, MLP-in's GELU epilogue) write the quantised rows themselves?  MXFP6 has no such producer
-bool fused_quant(const mc_mmdit* e) { return mc::g_fp8_fused_quant && !e->mx_fp6; }
+int gelu_quant_epi(const mc_mmdit* e) { return mc::mx_info(e->mx_fmt).gelu_epi; }
+// do the producers (the LayerNorm tail, MLP-in's GELU epilogue) write the quantised rows themselves?  e2m3 has no such producer
+bool fused_quant(const mc_mmdit* e) { return mc::g_fp8_fused_quant && e->mx_fmt != mc::MX_E2M3; }
 // bf16 rows -> their place in "aq" (the separate quantise pass: the attention output, and everything with fp8_fused_quant 0)
 mc_status mx_quantise(const mc_mmdit* e, const bf16_t* rows_bf16, long ld, int rows, int K, const MxDst& to, hipStream_t s) {
-  if (e->mx_fp4) HIP_TRY(mc::launch_quantize_rows_mxfp4(rows_bf16, nullptr, ld, rows, K, to.q, to.ld, to.mx, to.rows_pad, s));
-  else if (e->mx_fp6) HIP_TRY(mc::launch_quantize_rows_mxfp6(rows_bf16, nullptr, ld, rows, K, to.q, to.ld, to.mx, to.rows_pad, s));
-  else HIP_TRY(mc::launch_quantize_rows_mx(rows_bf16, nullptr, ld, rows, K, to.q, to.ld, to.mx, to.rows_pad, s));
+  HIP_TRY(mc::launch_quantize_rows_mx(e->mx_fmt, rows_bf16, nullptr, ld, rows, K, to.q, to.ld, to.mx, to.rows_pad, s));
   return MC_OK;
 }
 // LayerNorm + modulate of "x" rows [row0, row0 + rows) as the operand of `l`: a bf16 Linear reads "xn"; an MX Linear reads
@@ -267,7 +251,7 @@ mc_status ln_for_linear(const mc_mmdit* e, const Linear& l, int row0, int rows, 
   if (l.mx && fused_quant(e)) {
     const MxDst to = mx_at(e, row0, rows, 0);
     *a8 = to.rows();
-    if (e->mx_fp4) HIP_TRY(mc::launch_ln_modulate_mxfp4(x, d, scale, shift, 0, 1e-6f, to.q, to.ld, to.mx, to.rows_pad, rows, d, s));
+    if (e->mx_fmt == mc::MX_E2M1) HIP_TRY(mc::launch_ln_modulate_mxfp4(x, d, scale, shift, 0, 1e-6f, to.q, to.ld, to.mx, to.rows_pad, rows, d, s));
     else HIP_TRY(mc::launch_ln_modulate_fp8(x, d, scale, shift, 0, 1e-6f, to.q, to.ld, nullptr, to.mx, to.rows_pad, rows, d, s));
     return MC_OK;
   }
@@ -384,7 +368,7 @@ void plan_workspace(const mc_mmdit* e, const Rows& r, mc::Workspace& ws) {
   ws.add("calib_sums", 64);
   ws.add("calib_stats", 64);
   if (c.fp8_linear) {   // behind everything else: the plan of a bf16 engine does not change
-    ws.add("aq", e->mx_fp4 ? Sp * 5 * d / 2 : e->mx_fp6 ? Sp * 5 * d / 4 * 3 : Sp * 5 * d);
+    ws.add("aq", Sp * (size_t)mc::mx_row_bytes(e->mx_fmt, 5L * d));
     ws.add("a_mx", (5 * d / 32 + (c.fp8_linear == 3 ? d / 32 : 0)) * (Ltp + align_up(Li, 256)) + 5 * d / 32 * Sp);
   }
 }
@@ -452,18 +436,12 @@ static mc_status create_engine(const mc_mmdit_config& c, mc_mmdit** out) {
   const bool qw = c.family == MC_FAMILY_QWEN;
   if (c.family != MC_FAMILY_FLUX && !hy && !qw) return fail(MC_EINVAL, "unknown family %d", c.family);
   if (c.num_heads <= 0 || c.dim != c.num_heads * 128) return fail(MC_EINVAL, "dim must be num_heads * 128 (head_dim 128)");
-  // option "mx_fp4" (latched here, as mc_create latches it): with fp8_linear 2 | 3 the MX copies are MXFP4.  gemm_mxfp4 tiles K
-  // by 256 from 512 up; every such Linear reads dim, 4 dim or 5 dim features, so the first one decides -- refused by name
-  const bool mx_fp4 = mc::g_mx_fp4 != 0 && (c.fp8_linear == 2 || c.fp8_linear == 3);
-  if (mx_fp4 && ((c.dim % 256) != 0 || c.dim < 512))
-    return fail(MC_EINVAL, "mx_fp4: q|k|v / MLP-in (in_features = dim): %d input features are no multiple of 256 >= 512 (the K tile of "
-                           "the MXFP4 GEMM; MLP-out reads 4 dim, a single block's linear2 5 dim)", c.dim);
-  if (mc::g_mx_fp4 != 0 && mc::g_mx_fp6 != 0)
-    return fail(MC_EINVAL, "the options \"mx_fp4\" and \"mx_fp6\" are both 1: an engine's MX Linears hold one element format, set one of them");
-  const bool mx_fp6 = mc::g_mx_fp6 != 0 && (c.fp8_linear == 2 || c.fp8_linear == 3);
-  if (mx_fp6 && ((c.dim % 256) != 0 || c.dim < 512))
-    return fail(MC_EINVAL, "mx_fp6: q|k|v / MLP-in (in_features = dim): %d input features are no multiple of 256 >= 512 (the K contract "
-                           "of the MXFP6 GEMM; MLP-out reads 4 dim, a single block's linear2 5 dim)", c.dim);
+  // options "mx_fp4" / "mx_fp6" (latched here, as mc_create latches them): the element format of the MX copies.  The MX GEMMs
+  // tile K by 256 from 512 up; every such Linear reads dim, 4 dim or 5 dim features, so the first one decides -- refused by name
+  mc::MxFormat mx_fmt;
+  MC_TRY(mc::latch_mx_format(c.fp8_linear == 2 || c.fp8_linear == 3, &mx_fmt));
+  if (mx_fmt != mc::MX_E4M3)
+    MC_TRY(mc::check_mx_k(mx_fmt, "q|k|v / MLP-in (in_features = dim; MLP-out reads 4 dim, a single block's linear2 5 dim)", c.dim));
   if ((c.dim % 256) != 0) return fail(MC_EINVAL, "dim %d must be a multiple of 256", c.dim);
   if (c.n_double < 0 || c.n_single < 0 || c.n_double + c.n_single == 0) return fail(MC_EINVAL, "no blocks");
   if (c.txt_dim <= 0 || (c.txt_dim % 64) != 0 || (!qw && (c.vec_dim <= 0 || (c.vec_dim % 8) != 0)))
@@ -490,8 +468,7 @@ static mc_status create_engine(const mc_mmdit_config& c, mc_mmdit** out) {
   mc_mmdit* e = own.get();
   e->cfg = c;
   e->fp8 = c.fp8_linear;
-  e->mx_fp4 = mx_fp4;
-  e->mx_fp6 = mx_fp6;
+  e->mx_fmt = mx_fmt;
   e->P = P;
   e->rank = c.sp_rank;
   e->d = c.dim; e->H = c.num_heads;
@@ -506,9 +483,8 @@ static mc_status create_engine(const mc_mmdit_config& c, mc_mmdit** out) {
   // fp8_linear only decides which Linears keep an e4m3 copy with MX block scales: 2 = those that read a LayerNorm or GELU
   // output, 3 = those that read the attention output too.  The embedders, the modulation matrix, the token refiner and the
   // head stay bf16.
-  const mc::Quant q_mx = mx_fp4 ? mc::QUANT_MXFP4 : mx_fp6 ? mc::QUANT_MXFP6 : mc::QUANT_MX;
-  const mc::Quant q_big = c.fp8_linear >= 2 ? q_mx : mc::QUANT_NONE;
-  const mc::Quant q_out = c.fp8_linear == 3 ? q_mx : mc::QUANT_NONE;
+  const mc::Quant q_big = c.fp8_linear >= 2 ? mc::QUANT_MX : mc::QUANT_NONE;
+  const mc::Quant q_out = c.fp8_linear == 3 ? mc::QUANT_MX : mc::QUANT_NONE;
   auto vec128 = [&](float*& v, const std::string& name) { return W.add_f32(v, name, 128); };   // a per-head norm weight
   auto mlp2 = [&](Mlp2& m, size_t k_in, const std::string& l1, const std::string& l2) {
     MC_TRY(W.add_linear(m.l1, l1, {{"", d}}, k_in));
@@ -566,10 +542,10 @@ static mc_status create_engine(const mc_mmdit_config& c, mc_mmdit** out) {
       if (hy) {
         const std::string q = p + (k ? "txt" : "img");
         W.add_parts(e->mod, q, {{"_mod.linear", 6 * d}}, e->mod_double(i, k));
-        MC_TRY(W.add_linear(t.qkv, q, {{"_attn_qkv", 3 * d}}, d, q_big));
-        MC_TRY(W.add_linear(t.o, q, {{"_attn_proj", d}}, d, q_out));
-        MC_TRY(W.add_linear(t.fc1, q, {{"_mlp.fc1", 4 * d}}, d, q_big));
-        MC_TRY(W.add_linear(t.fc2, q, {{"_mlp.fc2", d}}, 4 * d, q_big));
+        MC_TRY(W.add_linear(t.qkv, q, {{"_attn_qkv", 3 * d}}, d, q_big, mx_fmt));
+        MC_TRY(W.add_linear(t.o, q, {{"_attn_proj", d}}, d, q_out, mx_fmt));
+        MC_TRY(W.add_linear(t.fc1, q, {{"_mlp.fc1", 4 * d}}, d, q_big, mx_fmt));
+        MC_TRY(W.add_linear(t.fc2, q, {{"_mlp.fc2", d}}, 4 * d, q_big, mx_fmt));
         MC_TRY(vec128(t.qn, q + "_attn_q_norm.weight"));
         MC_TRY(vec128(t.kn, q + "_attn_k_norm.weight"));
       } else {
@@ -577,11 +553,11 @@ static mc_status create_engine(const mc_mmdit_config& c, mc_mmdit** out) {
         const std::string ff = qw ? (k ? "txt_mlp" : "img_mlp") : (k ? "ff_context" : "ff");
         W.add_parts(e->mod, p, {{qw ? (k ? "txt_mod.1" : "img_mod.1") : (k ? "norm1_context.linear" : "norm1.linear"), 6 * d}},
                     e->mod_double(i, k));
-        if (k) MC_TRY(W.add_linear(t.qkv, p, {{"attn.add_q_proj", d}, {"attn.add_k_proj", d}, {"attn.add_v_proj", d}}, d, q_big));
-        else MC_TRY(W.add_linear(t.qkv, p, {{"attn.to_q", d}, {"attn.to_k", d}, {"attn.to_v", d}}, d, q_big));
-        MC_TRY(W.add_linear(t.o, p, {{k ? "attn.to_add_out" : "attn.to_out.0", d}}, d, q_out));
-        MC_TRY(W.add_linear(t.fc1, p, {{ff + ".net.0.proj", 4 * d}}, d, q_big));
-        MC_TRY(W.add_linear(t.fc2, p, {{ff + ".net.2", d}}, 4 * d, q_big));
+        if (k) MC_TRY(W.add_linear(t.qkv, p, {{"attn.add_q_proj", d}, {"attn.add_k_proj", d}, {"attn.add_v_proj", d}}, d, q_big, mx_fmt));
+        else MC_TRY(W.add_linear(t.qkv, p, {{"attn.to_q", d}, {"attn.to_k", d}, {"attn.to_v", d}}, d, q_big, mx_fmt));
+        MC_TRY(W.add_linear(t.o, p, {{k ? "attn.to_add_out" : "attn.to_out.0", d}}, d, q_out, mx_fmt));
+        MC_TRY(W.add_linear(t.fc1, p, {{ff + ".net.0.proj", 4 * d}}, d, q_big, mx_fmt));
+        MC_TRY(W.add_linear(t.fc2, p, {{ff + ".net.2", d}}, 4 * d, q_big, mx_fmt));
         MC_TRY(vec128(t.qn, p + (k ? "attn.norm_added_q.weight" : "attn.norm_q.weight")));
         MC_TRY(vec128(t.kn, p + (k ? "attn.norm_added_k.weight" : "attn.norm_k.weight")));
       }
@@ -593,11 +569,11 @@ static mc_status create_engine(const mc_mmdit_config& c, mc_mmdit** out) {
     const std::string p = (flux ? "single_transformer_blocks." : "single_blocks.") + std::to_string(i) + ".";
     W.add_parts(e->mod, p, {{flux ? "norm.linear" : "modulation.linear", 3 * d}}, e->mod_single(i));
     if (flux) {
-      MC_TRY(W.add_linear(g.in, p, {{"attn.to_q", d}, {"attn.to_k", d}, {"attn.to_v", d}, {"proj_mlp", 4 * d}}, d, q_big));
-      MC_TRY(W.add_linear(g.out, p, {{"proj_out", d}}, 5 * d, q_out));
+      MC_TRY(W.add_linear(g.in, p, {{"attn.to_q", d}, {"attn.to_k", d}, {"attn.to_v", d}, {"proj_mlp", 4 * d}}, d, q_big, mx_fmt));
+      MC_TRY(W.add_linear(g.out, p, {{"proj_out", d}}, 5 * d, q_out, mx_fmt));
     } else {
-      MC_TRY(W.add_linear(g.in, p, {{"linear1", 7 * d}}, d, q_big));
-      MC_TRY(W.add_linear(g.out, p, {{"linear2", d}}, 5 * d, q_out));
+      MC_TRY(W.add_linear(g.in, p, {{"linear1", 7 * d}}, d, q_big, mx_fmt));
+      MC_TRY(W.add_linear(g.out, p, {{"linear2", d}}, 5 * d, q_out, mx_fmt));
     }
     MC_TRY(vec128(g.qn, p + (flux ? "attn.norm_q.weight" : "q_norm.weight")));
     MC_TRY(vec128(g.kn, p + (flux ? "attn.norm_k.weight" : "k_norm.weight")));
@@ -638,8 +614,8 @@ void mc_mmdit_destroy(mc_mmdit* e) {
 
 size_t mc_mmdit_workspace_bytes(const mc_mmdit* e) { return e ? e->work.need : 0; }
 
-int mc_mmdit_mx_fp4(const mc_mmdit* e) { return e && e->mx_fp4 ? 1 : 0; }
-int mc_mmdit_mx_fp6(const mc_mmdit* e) { return e && e->mx_fp6 ? 1 : 0; }
+int mc_mmdit_mx_fp4(const mc_mmdit* e) { return e && e->mx_fmt == mc::MX_E2M1 ? 1 : 0; }
+int mc_mmdit_mx_fp6(const mc_mmdit* e) { return e && e->mx_fmt == mc::MX_E2M3 ? 1 : 0; }
 
 mc_status mc_mmdit_set_workspace(mc_mmdit* e, void* ws_dev, size_t bytes) {
   if (!e) return fail(MC_EINVAL, "null argument");

@@ -26,7 +26,7 @@ enum GemmEpi {
   EPI_RESID_CAPTURE_SEL = 12, // when gate_sel != null, so that the form without per-token gates keeps its code
   EPI_SPLITK_PARTIAL = 9,// (internal, gemm_bf16_v2 split-K) the fp32 accumulators of one K slice of a tile -> splitk_ws
   EPI_GELU_MXFP8 = 8,    // as 1, then MX-quantised in the epilogue: Cq = e4m3 bytes, c_mx = E8M0 block scales -- the A
-                         // operand of the next MX GEMM, the bits launch_quantize_rows_mx would make of Cb (gemm_mxfp8 only)
+                         // operand of the next MX GEMM, the bits launch_quantize_rows_mxfp8 would make of Cb (gemm_mxfp8 only)
   EPI_GELU_MXFP4 = 13,   // as 1, then MXFP4-quantised in the epilogue: Cq = packed e2m1 codes (column n at byte n / 2), c_mx =
                          // E8M0 block scales -- the A operand of the next MXFP4 GEMM, the bits launch_quantize_rows_mxfp4 would
                          // make of Cb (gemm_mxfp4 only)
@@ -103,35 +103,78 @@ bool gemm_fp8_supported(const GemmParams& p);
 hipError_t launch_quantize_rows_fp8(const bf16_t* x, const float* x_f32, long ldx, int M, int K, uint8_t* q, long ldq,
                                     float* scale, hipStream_t stream);
 
-// MX block-scaled fp8 (gemm_mxfp8.hip): v_mfma_scale_f32_16x16x128_f8f6f4, one E8M0 scale per (row, 32 k)
-hipError_t launch_gemm_mxfp8(const GemmParams& p, int epi, hipStream_t stream);
-bool gemm_mxfp8_supported(const GemmParams& p);
-// q[m, kb*32 .. +31] = e4m3(x * 2^-e), e = ceil(log2(max|block| / 448)), scale byte e + 127 at
-// s[kb * rows_pad + mx_scale_row(m)]; exponent, packing and scale row are quant.h's, as in every fused producer
-hipError_t launch_quantize_rows_mx(const bf16_t* x, const float* x_f32, long ldx, int M, int K, uint8_t* q, long ldq,
-                                   uint8_t* s, long rows_pad, hipStream_t stream);
+// ---------------------------------------------------------------- MX block-scaled Linears: the element formats
+// One E8M0 scale per (row, 32 k) on v_mfma_scale_f32_16x16x128_f8f6f4, in one scale image (quant.h: mx_scale_row) for every
+// element format.  MxFormat is what the host asks "which format" with: a Linear, a weight slot and an engine hold ONE value of
+// it.  The table holds facts about a format only; which producers an engine fuses is that engine's own predicate.
+enum MxFormat { MX_E4M3, MX_E2M3, MX_E2M1 };
+struct MxInfo {
+  const char* name;     // as the error texts spell it
+  const char* option;   // the mc_set_option key that selects it at create time; null: the default
+  int block_bytes;      // bytes of 32 consecutive k in a packed row
+  int gelu_epi;         // the quantising GELU epilogue of its GEMM, -1: it has none
+};
+constexpr MxInfo kMxInfo[] = {{"MX fp8", nullptr, 32, EPI_GELU_MXFP8}, {"MXFP6", "mx_fp6", 24, -1}, {"MXFP4", "mx_fp4", 16, EPI_GELU_MXFP4}};
+constexpr const MxInfo& mx_info(MxFormat f) { return kMxInfo[f]; }
+// bytes of k elements (a multiple of 32) in a packed row: every lda / ldw / ldq below is at least this and % 16 == 0
+constexpr long mx_row_bytes(MxFormat f, long k) { return k / 32 * mx_info(f).block_bytes; }
 
-// MXFP4 (gemm_mxfp4.hip): the same instruction with both operands e2m1, two codes per byte (the even k in the low nibble; lda /
-// ldw / ldq in BYTES of packed rows), the scale image of the MX fp8 path.  M > 0 (the row contract of launch_gemm_mxfp8),
-// N % 256 == 0, K % 256 == 0 elements, K >= 512; the epilogues of gemm_epilogue.h and EPI_GELU_MXFP4 (ldcq in bytes, % 16 == 0
-// and >= N / 2, mx_rows_c % 64 == 0 and >= ceil256(M); rows m >= M store nothing); EPI_GELU_MXFP8 is refused.
+// The operand contract of all three GEMMs: M > 0 (rows m >= M of a partial tile are guarded), N % 256 == 0, K a multiple of
+// 256 elements and >= 512, 16-byte aligned packed rows of at least mx_row_bytes within 32-bit byte offsets, scale images with
+// mx_rows_a >= ceil256(M), mx_rows_w >= N, both % 64 == 0.
+inline bool gemm_mx_supported(MxFormat f, const GemmParams& p) {
+  const long rb = mx_row_bytes(f, p.K);
+  return p.M > 0 && p.N > 0 && (p.N % 256) == 0 && p.K >= 512 && (p.K % 256) == 0 && (p.lda % 16) == 0 && (p.ldw % 16) == 0 &&
+         p.lda >= rb && p.ldw >= rb && p.A && p.W && (((uintptr_t)p.A | (uintptr_t)p.W) & 15) == 0 &&
+         (size_t)p.M * (size_t)p.lda < (1ull << 32) && (size_t)p.N * (size_t)p.ldw < (1ull << 32) && p.a_mx && p.w_mx &&
+         (((uintptr_t)p.a_mx | (uintptr_t)p.w_mx) & 3) == 0 && p.mx_rows_a >= (long)((p.M + 255) / 256) * 256 &&
+         p.mx_rows_w >= p.N && (p.mx_rows_a % 64) == 0 && (p.mx_rows_w % 64) == 0;
+}
+// The argument contract of all three row quantisers: x bf16 (x_f32 null) or fp32, any M > 0, K % 32 == 0, ldx % 8 == 0 and
+// >= K, ldq (bytes) % 16 == 0 and >= mx_row_bytes, x and q 16-byte aligned, rows_pad % 64 == 0 and >= ceil64(M).
+inline bool quantize_rows_mx_supported(MxFormat f, const bf16_t* x, const float* x_f32, long ldx, int M, int K, const uint8_t* q,
+                                       long ldq, const uint8_t* s, long rows_pad) {
+  return (x || x_f32) && q && s && M > 0 && K > 0 && (K % 32) == 0 && (ldx % 8) == 0 && ldx >= K && (ldq % 16) == 0 &&
+         ldq >= mx_row_bytes(f, K) && rows_pad >= ((M + 63) / 64) * 64 && (rows_pad % 64) == 0 &&
+         (((uintptr_t)x | (uintptr_t)x_f32 | (uintptr_t)q) & 15) == 0;
+}
+
+// The per-format launchers (gemm_mxfp8.hip, gemm_mxfp4.hip, gemm_mxfp6.hip); lda / ldw / ldq / ldcq in BYTES of packed rows.
+//   e4m3: one byte per element; the epilogues of gemm_epilogue.h and EPI_GELU_MXFP8.
+//   e2m1: two codes per byte, the even k in the low nibble; the same epilogues with EPI_GELU_MXFP4 in its place (ldcq % 16 == 0
+//         and >= N / 2, mx_rows_c % 64 == 0 and >= ceil256(M); rows m >= M store nothing).
+//   e2m3: 32 consecutive k per 24 bytes, one little-endian bit stream with code i at bit 6 i; EPI_BF16, _GELU_BF16, _RESID_GATE,
+//         _RESID_CAPTURE, _F32, no quantising epilogue.
+hipError_t launch_gemm_mxfp8(const GemmParams& p, int epi, hipStream_t stream);
 hipError_t launch_gemm_mxfp4(const GemmParams& p, int epi, hipStream_t stream);
-bool gemm_mxfp4_supported(const GemmParams& p);
-// codes e2m1(x * 2^-e), e = ceil(log2(max|block| / 6)), scale byte e + 127 at s[kb * rows_pad + mx_scale_row(m)] (quant.h)
+hipError_t launch_gemm_mxfp6(const GemmParams& p, int epi, hipStream_t stream);
+// q[m, block kb] = the 32 codes of x * 2^-e, e = ceil(log2(max|block| / the format's largest value: 448 | 6 | 7.5)), scale byte
+// e + 127 at s[kb * rows_pad + mx_scale_row(m)]; exponent, packing and scale row are quant.h's, as in every fused producer
+hipError_t launch_quantize_rows_mxfp8(const bf16_t* x, const float* x_f32, long ldx, int M, int K, uint8_t* q, long ldq,
+                                      uint8_t* s, long rows_pad, hipStream_t stream);
 hipError_t launch_quantize_rows_mxfp4(const bf16_t* x, const float* x_f32, long ldx, int M, int K, uint8_t* q, long ldq,
                                       uint8_t* s, long rows_pad, hipStream_t stream);
-
-// MXFP6 (gemm_mxfp6.hip): the same instruction with both operands e2m3; 32 consecutive k per 24 bytes, one little-endian bit
-// stream with code i at bit 6 i (quant.h), so a row of K elements is 3 K / 4 bytes (lda / ldw / ldq in BYTES of packed rows,
-// % 16 == 0); the scale image of the MX fp8 path.  M > 0 (the row contract of launch_gemm_mxfp8), N % 256 == 0, K % 256 == 0
-// elements, K >= 512; the epilogues of gemm_epilogue.h (EPI_BF16, _GELU_BF16, _RESID_GATE, _RESID_CAPTURE, _F32), no
-// quantising epilogue.
-hipError_t launch_gemm_mxfp6(const GemmParams& p, int epi, hipStream_t stream);
-bool gemm_mxfp6_supported(const GemmParams& p);
-// codes e2m3(x * 2^-e), e = ceil(log2(max|block| / 7.5)), scale byte e + 127 at s[kb * rows_pad + mx_scale_row(m)] (quant.h);
-// any M > 0, K % 32 == 0, ldq >= 3 K / 4
 hipError_t launch_quantize_rows_mxfp6(const bf16_t* x, const float* x_f32, long ldx, int M, int K, uint8_t* q, long ldq,
                                       uint8_t* s, long rows_pad, hipStream_t stream);
+
+// ... and the one place that maps a format to them
+inline hipError_t launch_gemm_mx(MxFormat f, const GemmParams& p, int epi, hipStream_t s) {
+  switch (f) {
+    case MX_E4M3: return launch_gemm_mxfp8(p, epi, s);
+    case MX_E2M3: return launch_gemm_mxfp6(p, epi, s);
+    case MX_E2M1: return launch_gemm_mxfp4(p, epi, s);
+  }
+  return hipErrorInvalidValue;
+}
+inline hipError_t launch_quantize_rows_mx(MxFormat f, const bf16_t* x, const float* x_f32, long ldx, int M, int K, uint8_t* q,
+                                          long ldq, uint8_t* s, long rows_pad, hipStream_t stream) {
+  switch (f) {
+    case MX_E4M3: return launch_quantize_rows_mxfp8(x, x_f32, ldx, M, K, q, ldq, s, rows_pad, stream);
+    case MX_E2M3: return launch_quantize_rows_mxfp6(x, x_f32, ldx, M, K, q, ldq, s, rows_pad, stream);
+    case MX_E2M1: return launch_quantize_rows_mxfp4(x, x_f32, ldx, M, K, q, ldq, s, rows_pad, stream);
+  }
+  return hipErrorInvalidValue;
+}
 
 // ---------------------------------------------------------------- LoRA merge (lora_merge.hip)
 // out[rows, K] = bf16(base + sum_j scale_j * (up_j down_j)), up_j [rows, rank], down_j [rank, K].  Per term an fp32 accumulator
@@ -209,7 +252,7 @@ hipError_t launch_ln_modulate(const float* x, long ldx, const bf16_t* x0, long l
                               const float* sh2 = nullptr, const uint8_t* sel = nullptr);
 // The same row, quantised for an fp8 GEMM instead of stored as bf16: e4m3 bytes q[m, :] relative to one scale per row
 // (row_scale != null; launch_quantize_rows_fp8's arithmetic) or to one E8M0 scale per 32 elements (mx != null;
-// launch_quantize_rows_mx's arithmetic and scale layout) -- bit-identical to quantising the bf16 row launch_ln_modulate
+// launch_quantize_rows_mxfp8's arithmetic and scale layout) -- bit-identical to quantising the bf16 row launch_ln_modulate
 // writes, without that row's round trip through memory.
 hipError_t launch_ln_modulate_fp8(const float* x, long ldx, const float* sc, const float* sh, int mode, float eps,
                                   uint8_t* q, long ldq, float* row_scale, uint8_t* mx, long mx_rows, int M, int D,

@@ -144,85 +144,77 @@ mc_status mc_op_gemm_fp8(const void* A, long lda, const float* a_scale, const vo
   return MC_OK;
 }
 
-mc_status mc_op_quantize_rows_mx(const void* x, mc_dtype dtype, long ldx, int M, int K, void* q, long ldq, void* scales,
-                                 long rows_pad, mc_stream s) {
-  hipError_t err = mc::launch_quantize_rows_mx(dtype == MC_BF16 ? (const bf16_t*)x : nullptr,
+// the three MX row quantisers and the three MX GEMMs of the C ABI: one body each, the format's own words in the refusal
+static mc_status quantize_rows_mx_op(mc::MxFormat fmt, const char* refusal, const void* x, mc_dtype dtype, long ldx, int M, int K,
+                                     void* q, long ldq, void* scales, long rows_pad, mc_stream s) {
+  hipError_t err = mc::launch_quantize_rows_mx(fmt, dtype == MC_BF16 ? (const bf16_t*)x : nullptr,
                                                dtype == MC_F32 ? (const float*)x : nullptr, ldx, M, K, (uint8_t*)q, ldq,
                                                (uint8_t*)scales, rows_pad, (hipStream_t)s);
-  if (err == hipErrorInvalidValue)
-    return fail(MC_EINVAL, "quantize_rows_mx: K %% 32 == 0, ldx %% 8 == 0, ldq %% 16 == 0, rows_pad >= M");
+  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "%s", refusal);
   HIP_TRY(err);
   return MC_OK;
+}
+
+static mc_status gemm_mx_op(mc::MxFormat fmt, const char* refusal, const void* A, long lda, const void* a_scales, long rows_pad_a,
+                            const void* W, long ldw, const void* w_scales, long rows_pad_w, const float* bias, int M, int N, int K,
+                            int epi, void* Cb, long ldc, float* X, long ldx, const float* gate, mc_stream s) {
+  mc::GemmParams p = gp((const bf16_t*)A, lda, (const bf16_t*)W, ldw, bias, M, N, K);
+  p.a_mx = (const uint8_t*)a_scales; p.mx_rows_a = rows_pad_a; p.w_mx = (const uint8_t*)w_scales; p.mx_rows_w = rows_pad_w;
+  p.Cb = (bf16_t*)Cb; p.ldc = ldc; p.X = X; p.ldx = ldx; p.gate = gate;
+  hipError_t err = mc::launch_gemm_mx(fmt, p, epi, (hipStream_t)s);
+  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "%s", refusal);
+  HIP_TRY(err);
+  return MC_OK;
+}
+
+mc_status mc_op_quantize_rows_mx(const void* x, mc_dtype dtype, long ldx, int M, int K, void* q, long ldq, void* scales,
+                                 long rows_pad, mc_stream s) {
+  return quantize_rows_mx_op(mc::MX_E4M3, "quantize_rows_mx: K % 32 == 0, ldx % 8 == 0, ldq % 16 == 0, rows_pad >= M", x, dtype, ldx, M, K,
+                             q, ldq, scales, rows_pad, s);
 }
 
 mc_status mc_op_gemm_mxfp8(const void* A, long lda, const void* a_scales, long rows_pad_a, const void* W, long ldw,
                            const void* w_scales, long rows_pad_w, const float* bias, int M, int N, int K, int epi, void* Cb,
                            long ldc, float* X, long ldx, const float* gate, mc_stream s) {
-  mc::GemmParams p = gp((const bf16_t*)A, lda, (const bf16_t*)W, ldw, bias, M, N, K);
-  p.a_mx = (const uint8_t*)a_scales; p.mx_rows_a = rows_pad_a; p.w_mx = (const uint8_t*)w_scales; p.mx_rows_w = rows_pad_w;
-  p.Cb = (bf16_t*)Cb; p.ldc = ldc; p.X = X; p.ldx = ldx; p.gate = gate;
-  hipError_t err = mc::launch_gemm_mxfp8(p, epi, (hipStream_t)s);
-  if (err == hipErrorInvalidValue)
-    return fail(MC_EINVAL, "gemm_mxfp8: needs N %% 256 == 0, K %% 256 == 0, K >= 512, lda/ldw %% 16 == 0, block scales with "
-                           "rows_pad_a >= M rounded up to 256, rows_pad_w >= N, both multiples of 4");
-  HIP_TRY(err);
-  return MC_OK;
+  return gemm_mx_op(mc::MX_E4M3, "gemm_mxfp8: needs N % 256 == 0, K % 256 == 0, K >= 512, lda/ldw % 16 == 0, block scales with "
+                                 "rows_pad_a >= M rounded up to 256, rows_pad_w >= N, both multiples of 4",
+                    A, lda, a_scales, rows_pad_a, W, ldw, w_scales, rows_pad_w, bias, M, N, K, epi, Cb, ldc, X, ldx, gate, s);
 }
 
 mc_status mc_op_quantize_rows_mxfp4(const void* x, mc_dtype dtype, long ldx, int M, int K, void* q, long ldq, void* scales,
                                     long rows_pad, mc_stream s) {
   if (dtype != MC_BF16 && dtype != MC_F32) return fail(MC_EINVAL, "quantize_rows_mxfp4: x is bf16 or fp32");
-  hipError_t err = mc::launch_quantize_rows_mxfp4(dtype == MC_BF16 ? (const bf16_t*)x : nullptr,
-                                                  dtype == MC_F32 ? (const float*)x : nullptr, ldx, M, K, (uint8_t*)q, ldq,
-                                                  (uint8_t*)scales, rows_pad, (hipStream_t)s);
-  if (err == hipErrorInvalidValue)
-    return fail(MC_EINVAL, "quantize_rows_mxfp4: M, K > 0, K %% 32 == 0, ldx %% 8 == 0 and >= K, ldq (bytes) %% 16 == 0 and >= K / 2, "
-                           "16-byte aligned pointers, rows_pad %% 64 == 0 and >= M");
-  HIP_TRY(err);
-  return MC_OK;
+  return quantize_rows_mx_op(mc::MX_E2M1, "quantize_rows_mxfp4: M, K > 0, K % 32 == 0, ldx % 8 == 0 and >= K, ldq (bytes) % 16 == 0 and >= K / 2, "
+                                          "16-byte aligned pointers, rows_pad % 64 == 0 and >= M",
+                             x, dtype, ldx, M, K, q, ldq, scales, rows_pad, s);
 }
 
 mc_status mc_op_gemm_mxfp4(const void* A, long lda, const void* a_scales, long rows_pad_a, const void* W, long ldw,
                            const void* w_scales, long rows_pad_w, const float* bias, int M, int N, int K, int epi, void* Cb,
                            long ldc, float* X, long ldx, const float* gate, mc_stream s) {
-  mc::GemmParams p = gp((const bf16_t*)A, lda, (const bf16_t*)W, ldw, bias, M, N, K);
-  p.a_mx = (const uint8_t*)a_scales; p.mx_rows_a = rows_pad_a; p.w_mx = (const uint8_t*)w_scales; p.mx_rows_w = rows_pad_w;
-  p.Cb = (bf16_t*)Cb; p.ldc = ldc; p.X = X; p.ldx = ldx; p.gate = gate;
-  hipError_t err = epi == mc::EPI_RESID_CAPTURE ? hipErrorInvalidValue : mc::launch_gemm_mxfp4(p, epi, (hipStream_t)s);
-  if (err == hipErrorInvalidValue)
-    return fail(MC_EINVAL, "gemm_mxfp4: needs M > 0, N %% 256 == 0, K %% 256 == 0 (elements), K >= 512, lda/ldw (bytes) %% 16 == 0 and "
-                           ">= K / 2, 16-byte aligned operands, block scales with rows_pad_a >= M rounded up to 256, rows_pad_w >= N, "
-                           "both multiples of 64, epilogue 0, 1, 2 or 5 with its output");
-  HIP_TRY(err);
-  return MC_OK;
+  const char* refusal = "gemm_mxfp4: needs M > 0, N % 256 == 0, K % 256 == 0 (elements), K >= 512, lda/ldw (bytes) % 16 == 0 and "
+                        ">= K / 2, 16-byte aligned operands, block scales with rows_pad_a >= M rounded up to 256, rows_pad_w >= N, "
+                        "both multiples of 64, epilogue 0, 1, 2 or 5 with its output";
+  if (epi == mc::EPI_RESID_CAPTURE) return fail(MC_EINVAL, "%s", refusal);   // no X0 / R arguments here
+  return gemm_mx_op(mc::MX_E2M1, refusal, A, lda, a_scales, rows_pad_a, W, ldw, w_scales, rows_pad_w, bias, M, N, K, epi, Cb, ldc, X, ldx, gate, s);
 }
 
 mc_status mc_op_quantize_rows_mxfp6(const void* x, mc_dtype dtype, long ldx, int M, int K, void* q, long ldq, void* scales,
                                     long rows_pad, mc_stream s) {
   if (dtype != MC_BF16 && dtype != MC_F32) return fail(MC_EINVAL, "quantize_rows_mxfp6: x is bf16 or fp32");
-  hipError_t err = mc::launch_quantize_rows_mxfp6(dtype == MC_BF16 ? (const bf16_t*)x : nullptr,
-                                                  dtype == MC_F32 ? (const float*)x : nullptr, ldx, M, K, (uint8_t*)q, ldq,
-                                                  (uint8_t*)scales, rows_pad, (hipStream_t)s);
-  if (err == hipErrorInvalidValue)
-    return fail(MC_EINVAL, "quantize_rows_mxfp6: M, K > 0, K %% 32 == 0, ldx %% 8 == 0 and >= K, ldq (bytes) %% 16 == 0 and >= 3 K / 4, "
-                           "16-byte aligned pointers, rows_pad %% 64 == 0 and >= M");
-  HIP_TRY(err);
-  return MC_OK;
+  return quantize_rows_mx_op(mc::MX_E2M3, "quantize_rows_mxfp6: M, K > 0, K % 32 == 0, ldx % 8 == 0 and >= K, ldq (bytes) % 16 == 0 and >= 3 K / 4, "
+                                          "16-byte aligned pointers, rows_pad % 64 == 0 and >= M",
+                             x, dtype, ldx, M, K, q, ldq, scales, rows_pad, s);
 }
 
 mc_status mc_op_gemm_mxfp6(const void* A, long lda, const void* a_scales, long rows_pad_a, const void* W, long ldw,
                            const void* w_scales, long rows_pad_w, const float* bias, int M, int N, int K, int epi, void* Cb,
                            long ldc, float* X, long ldx, const float* gate, mc_stream s) {
-  mc::GemmParams p = gp((const bf16_t*)A, lda, (const bf16_t*)W, ldw, bias, M, N, K);
-  p.a_mx = (const uint8_t*)a_scales; p.mx_rows_a = rows_pad_a; p.w_mx = (const uint8_t*)w_scales; p.mx_rows_w = rows_pad_w;
-  p.Cb = (bf16_t*)Cb; p.ldc = ldc; p.X = X; p.ldx = ldx; p.gate = gate;
-  hipError_t err = epi == mc::EPI_RESID_CAPTURE ? hipErrorInvalidValue : mc::launch_gemm_mxfp6(p, epi, (hipStream_t)s);
-  if (err == hipErrorInvalidValue)
-    return fail(MC_EINVAL, "gemm_mxfp6: needs M > 0, N %% 256 == 0, K %% 256 == 0 (elements), K >= 512, lda/ldw (bytes) %% 16 == 0 and "
-                           ">= 3 K / 4, 16-byte aligned operands, block scales with rows_pad_a >= M rounded up to 256, rows_pad_w >= N, "
-                           "both multiples of 64, epilogue 0, 1, 2 or 5 with its output");
-  HIP_TRY(err);
-  return MC_OK;
+  const char* refusal = "gemm_mxfp6: needs M > 0, N % 256 == 0, K % 256 == 0 (elements), K >= 512, lda/ldw (bytes) % 16 == 0 and "
+                        ">= 3 K / 4, 16-byte aligned operands, block scales with rows_pad_a >= M rounded up to 256, rows_pad_w >= N, "
+                        "both multiples of 64, epilogue 0, 1, 2 or 5 with its output";
+  if (epi == mc::EPI_RESID_CAPTURE) return fail(MC_EINVAL, "%s", refusal);   // no X0 / R arguments here
+  return gemm_mx_op(mc::MX_E2M3, refusal, A, lda, a_scales, rows_pad_a, W, ldw, w_scales, rows_pad_w, bias, M, N, K, epi, Cb, ldc, X, ldx, gate, s);
 }
 
 mc_status mc_op_attention_partial(const void* Q, long ldq, const void* K, long ldk, long kss, const void* V, long ldv,

@@ -1,9 +1,11 @@
-// The arithmetic of the two fp8 (OCP e4m3) quantisers and of the MXFP4 (e2m1) and MXFP6 (e2m3) quantisers, defined once.  Every producer of quantised rows -- the stand-alone
-// kernels (quantize_rows_fp8_kernel, quantize_rows_mx_kernel), the fused tails of the LayerNorm + modulate kernel
-// (elementwise.hip), the EPI_GELU_MXFP8 / EPI_GELU_MXFP4 epilogues (gemm_mxfp8.hip, gemm_mxfp4.hip) and quantize_rows_mxfp4_kernel (gemm_mxfp4.hip) -- goes through these helpers, so "the same bits as
-// quantising the bf16 row" (ops.h) holds by construction.
+// The arithmetic of the two fp8 (OCP e4m3) quantisers and of the MXFP4 (e2m1) and MXFP6 (e2m3) quantisers, defined once.  Every
+// producer of quantised rows -- the stand-alone kernels (quantize_rows_fp8_kernel and the three quantize_rows_mx*_kernel, whose
+// body is at the end of this file), the fused tails of the LayerNorm + modulate kernel (elementwise.hip), the EPI_GELU_MXFP8 /
+// EPI_GELU_MXFP4 epilogues (gemm_mxfp8.hip, gemm_mxfp4.hip) -- goes through these helpers, so "the same bits as quantising the
+// bf16 row" (ops.h) holds by construction.
 #pragma once
 #include "common.h"
+#include "ops.h"
 
 namespace mc {
 
@@ -130,6 +132,71 @@ __device__ __forceinline__ void pack16_e2m3(const float* v, float inv, uint32_t 
 #pragma unroll
   for (int i = 11; i < 16; ++i) hi |= e2m3_code(v[i], inv) << (6 * i - 64);
   w[0] = (uint32_t)lo; w[1] = (uint32_t)(lo >> 32); w[2] = hi;
+}
+
+// ---- the stand-alone row quantisers of the element formats (ops.h: MxFormat), one body.  A format is its exponent rule and
+// "pack the 32 scaled values of a block and store them": the block's mx_info().block_bytes at q_row + at in the packed row.
+struct QuantE4m3 {
+  static constexpr MxFormat format = MX_E4M3;
+  static __device__ __forceinline__ int exponent(float amax) { return mx_exponent(amax); }
+  static __device__ __forceinline__ void store_block(const float* v, float inv, uint8_t* q_row, int at) {
+    uint32_t w[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) w[i] = (uint32_t)pack4_e4m3(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3], inv);
+    u32x4* dst = (u32x4*)(q_row + at);
+    dst[0] = u32x4{w[0], w[1], w[2], w[3]};
+    dst[1] = u32x4{w[4], w[5], w[6], w[7]};
+  }
+};
+struct QuantE2m1 {
+  static constexpr MxFormat format = MX_E2M1;
+  static __device__ __forceinline__ int exponent(float amax) { return mxfp4_exponent(amax); }
+  static __device__ __forceinline__ void store_block(const float* v, float inv, uint8_t* q_row, int at) {
+    *(u32x4*)(q_row + at) = u32x4{pack8_e2m1(v, inv), pack8_e2m1(v + 8, inv), pack8_e2m1(v + 16, inv), pack8_e2m1(v + 24, inv)};
+  }
+};
+
+// One wave per row, four rows per block of 256; lane b (+64, +128, ...) owns the 32-element block b: scale exponent
+// e = F::exponent(amax), the codes of x * 2^-e stored by F, scale byte e + 127 at s[b * rows_pad + mx_scale_row(row)].
+// The whole body of a kernel with the parameters (x, xf, ldx, M, K, q, ldq, s, rows_pad).  (A macro, not a function: inlined
+// from a function the same IR reaches the back end with the predecessors of its blocks in another order, and the two input
+// branches are laid out the other way round; the macro leaves the kernels' instruction streams as they were -- tools/isa_same.py.
+// quantize_rows_mxfp6_kernel keeps a body of its own in gemm_mxfp6.hip: with its 24-byte store behind a trait the compiler
+// threads the branches of e2m3_code differently, macro or not.)
+#define MC_QUANTIZE_ROWS_MX_BODY(F)                                                                          \
+  const int lane = threadIdx.x & 63;                                                                         \
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);                                                       \
+  if (row >= M) return;                                                                                      \
+  for (int b = lane; b < K / 32; b += 64) {                                                                  \
+    float v[32];                                                                                             \
+    if (xf) {                                                                                                \
+      _Pragma("unroll") for (int i = 0; i < 8; ++i) {                                                        \
+        const f32x4 t = *(const f32x4*)(xf + (size_t)row * ldx + b * 32 + i * 4);                            \
+        v[4 * i] = t[0]; v[4 * i + 1] = t[1]; v[4 * i + 2] = t[2]; v[4 * i + 3] = t[3];                      \
+      }                                                                                                      \
+    } else {                                                                                                 \
+      _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                        \
+        const u32x4 t = *(const u32x4*)(x + (size_t)row * ldx + b * 32 + i * 8);                             \
+        _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                      \
+          v[8 * i + 2 * j] = __uint_as_float(t[j] << 16);                                                    \
+          v[8 * i + 2 * j + 1] = __uint_as_float(t[j] & 0xffff0000u);                                        \
+        }                                                                                                    \
+      }                                                                                                      \
+    }                                                                                                        \
+    float amax = 0.f;                                                                                        \
+    _Pragma("unroll") for (int i = 0; i < 32; ++i) amax = fmaxf(amax, fabsf(v[i]));                          \
+    const int e = F::exponent(amax);                                                                         \
+    F::store_block(v, mx_inv_scale(e), q + (size_t)row * ldq, b * mx_info(F::format).block_bytes);           \
+    s[(size_t)b * rows_pad + mx_scale_row(row)] = mx_scale_byte(e);                                          \
+  }
+
+// the launch of one of the three row-quantiser kernels, behind the argument contract of ops.h
+template <auto Kernel>
+inline hipError_t launch_quantize_rows_mx_kernel(MxFormat f, const bf16_t* x, const float* x_f32, long ldx, int M, int K, uint8_t* q,
+                                                 long ldq, uint8_t* s, long rows_pad, hipStream_t stream) {
+  if (!quantize_rows_mx_supported(f, x, x_f32, ldx, M, K, q, ldq, s, rows_pad)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(Kernel, dim3((M + 3) / 4), dim3(256), 0, stream, x, x_f32, ldx, M, K, q, ldq, s, rows_pad);
+  return hipGetLastError();
 }
 
 }  // namespace mc

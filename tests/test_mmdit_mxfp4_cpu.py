@@ -57,9 +57,13 @@ def test_python_surface_takes_the_keyword_and_shares_one_latch():
         assert inspect.signature(cls.__init__).parameters["mx_fp4"].default is False, cls
     # the set / create / put back sequence exists once, in the base both engine classes derive from
     assert issubclass(mmdit.MMDiTEngine, adapters.EngineHost) and issubclass(engine.Engine, adapters.EngineHost)
+    # (over the tuple of element-format options, which names this one)
     for mod in (engine, mmdit):
-        assert 'mc_set_option(b"mx_fp4"' not in inspect.getsource(mod)
-    assert inspect.getsource(adapters.EngineHost).count('mc_set_option(b"mx_fp4"') == 2   # set, put back
+        assert "mc_set_option(" not in inspect.getsource(mod)
+    assert "mx_fp4" in adapters.MX_FORMAT_OPTIONS
+    latch = inspect.getsource(adapters.EngineHost._create_latching)
+    assert latch.count("mc_set_option(") == 2 and latch.count("in MX_FORMAT_OPTIONS") == 4   # get, set, put back, query
+    assert inspect.getsource(adapters.EngineHost).count("mc_set_option(") == 2
 
 
 @pytest.mark.parametrize("mode", [2, 3])

@@ -161,3 +161,33 @@ def test_row_count_is_no_longer_a_condition_and_the_other_conditions_stay():
         H.gemm_mxfp8(aq, sa, wq[:128], sw, bias, EPI_F32, X=out)
     with pytest.raises(H._lib.MagCacheHipError):                                 # K < 512
         H.gemm_mxfp8(aq[:, :256], sa, wq[:, :256], sw, bias, EPI_F32, X=out)
+
+
+def test_the_e4m3_row_quantiser_takes_the_argument_contract_of_the_other_formats():
+    """mc_op_quantize_rows_mx at M = 4, K = 64, the smallest shape it accepts: rows that overlap (ldq < K, ldx < K), an x or q
+    that is not 16-byte aligned (the kernel moves 16 bytes at a time) and a null q are MC_EINVAL and nothing is launched -- q and
+    the scale image keep their sentinels; the same call with valid arguments gives the bits of hip_ops.mx_quantize_ref."""
+    M, K, rows_pad = 4, 64, 64
+    lib, bf16_dt, einval = H.L(), H._lib.MC_BF16, H._lib.MC_EINVAL
+    x = rnd(M + 1, K, seed=41, dtype=torch.bfloat16)           # a spare row: every refused call would stay inside the buffers
+    x[0, 5] *= 40.0
+    x[2, 32:] = 0.0                                            # an all-zero block: scale byte 0
+    q = torch.full((M + 1, K), 0x55, dtype=torch.uint8, device=DEV)
+    s = torch.full((K // 32, rows_pad), 0xEE, dtype=torch.uint8, device=DEV)   # 2^111: no scale of these values
+    assert x.data_ptr() % 16 == 0 and q.data_ptr() % 16 == 0
+
+    def call(xp, ldx, qp, ldq):
+        return lib.mc_op_quantize_rows_mx(C.c_void_p(xp), bf16_dt, ldx, M, K, C.c_void_p(qp), ldq, P(s), rows_pad, S())
+    assert call(x.data_ptr(), K, q.data_ptr(), 48) == einval          # ldq < K (a multiple of 16: the old check passed it)
+    assert call(x.data_ptr(), 56, q.data_ptr(), K) == einval          # ldx < K (a multiple of 8)
+    assert call(x.data_ptr() + 8, K, q.data_ptr(), K) == einval       # x not 16-byte aligned
+    assert call(x.data_ptr(), K, q.data_ptr() + 8, K) == einval       # q not 16-byte aligned
+    assert call(x.data_ptr(), K, 0, K) == einval                      # null q
+    torch.cuda.synchronize()
+    assert bool((q == 0x55).all()) and bool((s == 0xEE).all())
+
+    assert call(x.data_ptr(), K, q.data_ptr(), K) == 0
+    want_q, want_s = H.mx_quantize_ref(x[:M])
+    assert torch.equal(q[:M], want_q.view(torch.uint8)) and bool((q[M:] == 0x55).all())
+    assert torch.equal(H.mx_unpermute(s, M), want_s)
+    assert int(want_s[2, 1]) == 0 and int((s == 0xEE).sum()) == (rows_pad - M) * (K // 32)

@@ -61,14 +61,29 @@ hipError_t launch_quantize_rows_fp8(const bf16_t* x, const float*, long ldx, int
   }
   return hipSuccess;
 }
-hipError_t launch_quantize_rows_mx(const bf16_t* x, const float*, long ldx, int M, int K, uint8_t* q, long ldq, uint8_t* s, long rows_pad,
-                                   hipStream_t) {
+// the three per-format launchers behind launch_quantize_rows_mx (ops.h): exactly M rows of mx_row_bytes and K / 32 scale bytes each
+static long g_mx_q_bytes = 0, g_mx_scale_bytes = 0;   // written by the last call
+static hipError_t quantize_mx_stub(MxFormat f, const bf16_t* x, long ldx, int M, int K, uint8_t* q, long ldq, uint8_t* s, long rows_pad) {
+  g_mx_q_bytes = g_mx_scale_bytes = 0;
   for (int r = 0; r < M; ++r) {
     touch(x + (size_t)r * ldx, (size_t)K * 2);
-    memset(q + (size_t)r * ldq, 2, K);
-    for (int kb = 0; kb < K / 32; ++kb) s[(size_t)kb * rows_pad + r] = 127;
+    memset(q + (size_t)r * ldq, 2, mx_row_bytes(f, K));
+    g_mx_q_bytes += mx_row_bytes(f, K);
+    for (int kb = 0; kb < K / 32; ++kb, ++g_mx_scale_bytes) s[(size_t)kb * rows_pad + r] = 127;
   }
   return hipSuccess;
+}
+hipError_t launch_quantize_rows_mxfp8(const bf16_t* x, const float*, long ldx, int M, int K, uint8_t* q, long ldq, uint8_t* s, long rows_pad,
+                                      hipStream_t) {
+  return quantize_mx_stub(MX_E4M3, x, ldx, M, K, q, ldq, s, rows_pad);
+}
+hipError_t launch_quantize_rows_mxfp4(const bf16_t* x, const float*, long ldx, int M, int K, uint8_t* q, long ldq, uint8_t* s, long rows_pad,
+                                      hipStream_t) {
+  return quantize_mx_stub(MX_E2M1, x, ldx, M, K, q, ldq, s, rows_pad);
+}
+hipError_t launch_quantize_rows_mxfp6(const bf16_t* x, const float*, long ldx, int M, int K, uint8_t* q, long ldq, uint8_t* s, long rows_pad,
+                                      hipStream_t) {
+  return quantize_mx_stub(MX_E2M3, x, ldx, M, K, q, ldq, s, rows_pad);
 }
 hipError_t launch_lora_pack(const void* src, int src_f32, long rs, long cs, int n, int rank, int rank_pad, bf16_t* dst, hipStream_t) {
   for (int r = 0; r < n; ++r)
@@ -105,6 +120,7 @@ hipError_t launch_param_delta(const float* base, float* out, size_t n, const flo
   return hipSuccess;
 }
 hipError_t launch_gemm_bf16(const GemmParams&, int, hipStream_t) { return hipSuccess; }
+int g_mx_fp4 = 0, g_mx_fp6 = 0;   // engine.cpp's, read by latch_mx_format
 hipError_t launch_attention(const AttnParams&, hipStream_t) { return hipSuccess; }
 }  // namespace mc
 
@@ -225,6 +241,42 @@ int main() {
     EXPECT(W.lora_set_delta("a", "head.weight", v.data(), 64 * 16, MC_F32, nullptr), MC_EINVAL);
     W.free_all();
     EXPECT_TRUE(g_live == 0);
+  }
+  {  // MX copies in every element format: setting the LAST part of a fused Linear writes the last rows of q and of every scale
+     // block, so a row size or a row offset that is too large runs off the allocation
+    constexpr size_t n = 64, k = 512;
+    std::vector<float> w(n * k, 0.25f);
+    const int64_t mat[2] = {(int64_t)n, (int64_t)k};
+    for (MxFormat f : {MX_E4M3, MX_E2M1, MX_E2M3}) {
+      WeightStore W;
+      Linear kv;
+      EXPECT(W.add_linear(kv, "", {{"k", n}, {"v", n}}, k, QUANT_MX, f), MC_OK);
+      EXPECT_TRUE(kv.fmt == f && kv.q_row_bytes() == mx_row_bytes(f, k));
+      for (const char* name : {"k.weight", "v.weight"}) {
+        EXPECT(W.set(name, w.data(), MC_F32, mat, 2, nullptr), MC_OK);
+        EXPECT_TRUE(g_mx_q_bytes == (long)n * mx_row_bytes(f, k) && g_mx_scale_bytes == (long)(k / 32 * n));
+      }
+      W.free_all();
+      EXPECT_TRUE(g_live == 0);
+    }
+    EXPECT_TRUE(mx_row_bytes(MX_E4M3, k) == 512 && mx_row_bytes(MX_E2M1, k) == 256 && mx_row_bytes(MX_E2M3, k) == 384);
+    // the create-time latch: one format, e4m3 without MX Linears, both options refused
+    MxFormat f = MX_E2M1;
+    EXPECT(latch_mx_format(true, &f), MC_OK);
+    EXPECT_TRUE(f == MX_E4M3);
+    g_mx_fp6 = 1;
+    EXPECT(latch_mx_format(true, &f), MC_OK);
+    EXPECT_TRUE(f == MX_E2M3);
+    EXPECT(latch_mx_format(false, &f), MC_OK);
+    EXPECT_TRUE(f == MX_E4M3);
+    g_mx_fp4 = 1;
+    EXPECT(latch_mx_format(true, &f), MC_EINVAL);
+    g_mx_fp6 = 0;
+    EXPECT(latch_mx_format(true, &f), MC_OK);
+    EXPECT_TRUE(f == MX_E2M1);
+    EXPECT(check_mx_k(f, "q", 768), MC_OK);
+    EXPECT(check_mx_k(f, "q", 640), MC_EINVAL);
+    EXPECT(check_mx_k(f, "q", 256), MC_EINVAL);
   }
   if (g_failed) {
     printf("weight store: %d of %d checks FAILED\n", g_failed, g_checks);
