@@ -82,6 +82,11 @@ typedef struct {
                            path (mc_blocks_sp, mc_forward_sp_rccl) even with sp_size 1 -- a world of ONE: the collective
                            path, RCCL included, exercised on a single GPU (tests/test_rccl_gpu.py).  mc_forward refuses
                            such an engine like any sharded one. */
+  int token_timestep_sets; /* 0: per-token timesteps carry at most two distinct values per forward (two modulation sets, as
+                           before).  3..64: the engine's capacity C of distinct per-token timesteps per forward -- "temb",
+                           "emod" and "ehead" hold C sets, the time chain runs batched over them and every consumer selects
+                           from a table (mc_set_token_timesteps).  1, 2, > 64, or non-zero with no_token_timesteps:
+                           MC_EINVAL */
 } mc_config;
 
 const char* mc_last_error(void);
@@ -154,7 +159,8 @@ mc_status mc_create(const mc_config* cfg, mc_engine** out);
  * mc_create_sized(cfg, sizeof(mc_config) as IT knows it, out): the missing tail is taken as zeros.  History: 0.1 ends at
  * vace_in_dim, 0.2 adds fp8_linear, 0.3 no_context_cache and no_token_timesteps, 0.5 sp_phases (0.6 adds calls only: mc_pair_begin / mc_pair_end; 0.7 adds calls only: mc_geometry_bytes / mc_set_geometry,
  * mc_op_rope_axes / mc_op_rope_expand; 0.7.1 adds calls only: mc_lora_*, mc_op_lora_merge_f32, mc_op_param_delta; the MXFP4 and MXFP6 modes add calls only: mc_get_option,
- * mc_engine_mx_fp4 / _mx_fp6, mc_op_quantize_rows_mxfp4 / _mxfp6, mc_op_gemm_mxfp4 / _mxfp6); mc_version() names the library's. */
+ * mc_engine_mx_fp4 / _mx_fp6, mc_op_quantize_rows_mxfp4 / _mxfp6, mc_op_gemm_mxfp4 / _mxfp6); 0.8 adds token_timestep_sets (and the calls
+ * mc_engine_token_timestep_sets, mc_op_gemm_bf16_resid_sets); mc_version() names the library's. */
 mc_status mc_create_sized(const mc_config* cfg, size_t cfg_bytes, mc_engine** out);
 void mc_destroy(mc_engine* e);
 /* 1: this engine's quantised Linears are MXFP4 (it was created under mc_set_option("mx_fp4", 1) with fp8_linear 2 | 3); else 0 */
@@ -302,15 +308,26 @@ mc_status mc_set_clip_fea(mc_engine* e, const void* clip_dev, mc_dtype dtype, in
  * change the scale only. */
 mc_status mc_set_vace_context(mc_engine* e, const float* vace_dev, float context_scale, mc_stream stream);
 
-/* Wan2.2 TI2V-5B: per-token timesteps.  The Wan2.2 forward takes t [B, seq_len] and builds e [B, seq_len, d] /
- * e0 [B, seq_len, 6, d] (MagCache4Wan2.2/magcache_generate.py:261-270); the upstream pipeline passes t * mask, i.e. the
- * tokens of the conditioning frame carry t = 0 and all others the step's t: at most TWO distinct values per forward.
- * The engine evaluates the time MLP for max(t) and min(t) and selects per token (LayerNorm modulation, both gated
- * residual epilogues, the head) instead of materialising e0 (9.3 GB fp32 at 14B / 720p).  t_tokens_dev: fp32
- * [seq_len of the whole video] that must stay valid until the forward has run, or NULL to return to the scalar t of
- * mc_forward.  "tok_t2" (3 floats: max, min, number of tokens that are NEITHER -- must read 0) is the device-side
- * record of what was found. */
+/* Per-token timesteps.  The Wan2.2 forward takes t [B, seq_len] and builds e [B, seq_len, d] / e0 [B, seq_len, 6, d]
+ * (MagCache4Wan2.2/magcache_generate.py:261-270).  The engine never materialises e0 (9.3 GB fp32 at 14B / 720p): it
+ * evaluates the time MLP once per DISTINCT value and every consumer (LayerNorm modulation, both gated residual epilogues,
+ * the head) selects a modulation set per token through one selector byte.
+ *   default engine (token_timestep_sets = 0): at most TWO distinct values per forward -- the upstream TI2V pipeline passes
+ *     t * mask: the conditioning frame's tokens carry 0, all others the step's t.  Set 0 = max(t), set 1 = min(t).
+ *   capacity engine (token_timestep_sets = C, 3..64): up to C distinct values (one timestep per latent frame, several
+ *     conditioning frames at their own noise levels).  One device pass finds the distinct values in DESCENDING order into
+ *     "tok_vals" (C floats, padded with the last value found), the time chain runs once, batched over the C sets, and the
+ *     consumers take row min(sel, C - 1) of the set tables.  Such an engine uses the table forms for every per-token forward,
+ *     also when one or two values occur; a forward with scalar t (NULL here) runs the single-set path.
+ * t_tokens_dev: fp32 [seq_len of the whole video] that must stay valid until the forward has run (it is read on the
+ * forward's stream; nothing here synchronises with the host), or NULL to return to the scalar t of mc_forward.
+ * "tok_t2" is the device-side record of what was found: [0] max, [1] min, [2] the number of tokens whose value received NO
+ * modulation set -- neither max nor min on a default engine; beyond the capacity, or NaN, on a capacity engine, where they
+ * are modulated with set C - 1 -- which must read 0, [3] (capacity engines) the number of sets in use.
+ * Not defined for VACE engines (MC_EINVAL); MC_ESTATE with no_token_timesteps. */
 mc_status mc_set_token_timesteps(mc_engine* e, const float* t_tokens_dev, mc_stream stream);
+/* the capacity in force: token_timestep_sets, 2 for a default engine, 0 with no_token_timesteps (and for NULL) */
+int mc_engine_token_timestep_sets(const mc_engine* e);
 
 /* Measurement hook: hipEvent pairs on the launch stream around the launches of a forward, summed per class.
  * mc_profile_enable(e, 1): every SELF-attention launch (sequence parallel: the local-shard and the remote-shards launch of a
@@ -481,6 +498,13 @@ mc_status mc_op_gemm_bf16_resid_sel(const void* A_dev, long lda, const void* W_d
                                     int N, int K, int capture, float* X_dev, long ldx, const float* gate_dev,
                                     const float* gate2_dev, const unsigned char* gate_sel_dev, const void* X0_dev, long ldx0,
                                     float* R_dev, long ldr, mc_stream stream);
+/* ... with a TABLE of gate vectors (an engine with token_timestep_sets): X[m] += gates[min(sel[m], n_sets - 1) * gate_stride + n]
+ * * bf16(acc + bias); capture != 0: and R = X_new - X0.  n_sets 1..64, gate_stride >= N and a multiple of 4 floats; the
+ * selector byte is clamped before it forms an address.  MC_EINVAL, and nothing launched, otherwise. */
+mc_status mc_op_gemm_bf16_resid_sets(const void* A_dev, long lda, const void* W_dev, long ldw, const float* bias_dev, int M,
+                                     int N, int K, int capture, float* X_dev, long ldx, const float* gates_dev,
+                                     long gate_stride, int n_sets, const unsigned char* sel_dev, const void* X0_dev, long ldx0,
+                                     float* R_dev, long ldr, mc_stream stream);
 /* two Linears with the same shapes over two ROW RANGES of the same buffers as one launch: rows [0, m_split) multiply with W
  * (+ bias, gate), rows [m_split, M) with W_b (+ bias_b, gate_b) -- the text and the image stream of an MM-DiT double block are
  * row ranges of the joint buffers (MagCache4FLUX/magcache_flux.py:342-387 calls them through diffusers' FluxTransformerBlock).

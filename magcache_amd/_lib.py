@@ -28,7 +28,7 @@ class McConfig(C.Structure):
                [("eps", C.c_float)] + \
                [(n, C.c_int) for n in ("sp_rank", "sp_size", "n_branches", "calibration", "clip_dim", "vace_layers",
                                          "vace_stride", "vace_in_dim", "fp8_linear", "no_context_cache",
-                                         "no_token_timesteps", "sp_phases")]
+                                         "no_token_timesteps", "sp_phases", "token_timestep_sets")]
 
 
 class MagCacheHipError(RuntimeError):
@@ -49,6 +49,7 @@ SIGNATURES = {
     "mc_get_option": (_i, [C.c_char_p, C.POINTER(_i)]),
     "mc_engine_mx_fp4": (_i, [_vp]),
     "mc_engine_mx_fp6": (_i, [_vp]),
+    "mc_engine_token_timestep_sets": (_i, [_vp]),
     "mc_create": (_i, [C.POINTER(McConfig), C.POINTER(_vp)]),
     "mc_create_sized": (_i, [C.POINTER(McConfig), _sz, C.POINTER(_vp)]),
     "mc_destroy": (None, [_vp]),
@@ -106,6 +107,7 @@ SIGNATURES = {
     "mc_op_gemm_bf16": (_i, [_vp, _l, _vp, _l, _vp, _i, _i, _i, _i, _vp, _l, _vp, _l, _vp, _vp, _l, _vp, _l, _vp, _l,
                              _i, _vp]),
     "mc_op_gemm_bf16_resid_sel": (_i, [_vp, _l, _vp, _l, _vp, _i, _i, _i, _i, _vp, _l, _vp, _vp, _vp, _vp, _l, _vp, _l, _vp]),
+    "mc_op_gemm_bf16_resid_sets": (_i, [_vp, _l, _vp, _l, _vp, _i, _i, _i, _i, _vp, _l, _vp, _l, _i, _vp, _vp, _l, _vp, _l, _vp]),
     "mc_op_gemm_bf16_rowsplit": (_i, [_vp, _l, _vp, _vp, _l, _vp, _vp, _i, _i, _i, _i, _i, _vp, _l, _vp, _l, _vp, _vp, _vp]),
     "mc_op_gemm_bf16_gelu_split": (_i, [_vp, _l, _vp, _l, _vp, _i, _i, _i, _i, _vp, _l, _vp, _l, _vp]),
     "mc_op_gemm_bf16_kernel": (_i, [_i, _i, _i, _i]),

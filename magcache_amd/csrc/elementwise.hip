@@ -39,11 +39,16 @@ MC_NO_PK_F32 __global__ __launch_bounds__(256) void ln_modulate_kernel(const flo
                                                           float* __restrict__ out_f32, long ldof, int M, int D,
                                                           const float* __restrict__ sc2,
                                                           const float* __restrict__ sh2,
-                                                          const uint8_t* __restrict__ sel, LnQuantOut qo) {
+                                                          const uint8_t* __restrict__ sel, LnQuantOut qo, long set_stride,
+                                                          int n_sets) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= M) return;
-  if (sel && sel[row]) {   // per-token modulation (one wave per row: uniform)
+  if (sel && set_stride != 0) {   // a table of modulation sets: the byte is clamped before it forms an address
+    const long k = min((int)sel[row], n_sets - 1);
+    sc += k * set_stride;
+    sh += k * set_stride;
+  } else if (sel && sel[row]) {   // per-token modulation (one wave per row: uniform)
     sc = sc2;
     sh = sh2;
   }
@@ -715,13 +720,16 @@ inline int grid_for(long total, int block, int cap = 2048) {
 template <int QM>
 static hipError_t launch_ln_t(const float* x, long ldx, const bf16_t* x0, long ldx0, const float* sc, const float* sh,
                               int mode, float eps, bf16_t* out, long ldo, float* out_f32, long ldof, int M, int D,
-                              hipStream_t stream, const float* sc2, const float* sh2, const uint8_t* sel, LnQuantOut qo) {
-  if (M <= 0 || D <= 0 || (D % 256) != 0 || (sel && (!sc2 || !sh2))) return hipErrorInvalidValue;
+                              hipStream_t stream, const float* sc2, const float* sh2, const uint8_t* sel, LnQuantOut qo,
+                              long set_stride, int n_sets) {
+  if (M <= 0 || D <= 0 || (D % 256) != 0) return hipErrorInvalidValue;
+  if (set_stride != 0 ? (!sel || n_sets < 1 || n_sets > kMaxTokenSets || (set_stride % 4) != 0) : (sel && (!sc2 || !sh2)))
+    return hipErrorInvalidValue;
   const dim3 grid((M + 3) / 4), block(256);
 #define MC_LN_CASE(NV)                                                                                      \
   case NV:                                                                                                  \
     hipLaunchKernelGGL((ln_modulate_kernel<NV, QM>), grid, block, 0, stream, x, ldx, x0, ldx0, sc, sh, mode, eps, out, \
-                       ldo, out_f32, ldof, M, D, sc2, sh2, sel, qo);                                                   \
+                       ldo, out_f32, ldof, M, D, sc2, sh2, sel, qo, set_stride, n_sets);                                                   \
     break;
   switch (D / 256) {
     MC_LN_CASE(1)
@@ -742,31 +750,32 @@ static hipError_t launch_ln_t(const float* x, long ldx, const bf16_t* x0, long l
 hipError_t launch_ln_modulate(const float* x, long ldx, const bf16_t* x0, long ldx0, const float* sc,
                               const float* sh, int mode, float eps, bf16_t* out, long ldo, float* out_f32,
                               long ldof, int M, int D, hipStream_t stream, const float* sc2, const float* sh2,
-                              const uint8_t* sel) {
+                              const uint8_t* sel, long set_stride, int n_sets) {
   if (!out && !out_f32) return hipErrorInvalidValue;   // the kernel stores through one of the two
   return launch_ln_t<0>(x, ldx, x0, ldx0, sc, sh, mode, eps, out, ldo, out_f32, ldof, M, D, stream, sc2, sh2, sel,
-                        LnQuantOut{nullptr, 0, nullptr, nullptr, 0});
+                        LnQuantOut{nullptr, 0, nullptr, nullptr, 0}, set_stride, n_sets);
 }
 
 hipError_t launch_ln_modulate_fp8(const float* x, long ldx, const float* sc, const float* sh, int mode, float eps,
                                   uint8_t* q, long ldq, float* row_scale, uint8_t* mx, long mx_rows, int M, int D,
-                                  hipStream_t stream, const float* sc2, const float* sh2, const uint8_t* sel) {
+                                  hipStream_t stream, const float* sc2, const float* sh2, const uint8_t* sel,
+                                  long set_stride, int n_sets) {
   if (!q || (ldq % 4) != 0 || (!row_scale && !mx)) return hipErrorInvalidValue;
   const LnQuantOut qo{q, ldq, row_scale, mx, mx_rows};
   if (mx) {
     if ((D % 32) != 0 || (ldq % 16) != 0 || (mx_rows % 64) != 0 || mx_rows < ((M + 63) / 64) * 64) return hipErrorInvalidValue;
-    return launch_ln_t<2>(x, ldx, nullptr, 0, sc, sh, mode, eps, nullptr, 0, nullptr, 0, M, D, stream, sc2, sh2, sel, qo);
+    return launch_ln_t<2>(x, ldx, nullptr, 0, sc, sh, mode, eps, nullptr, 0, nullptr, 0, M, D, stream, sc2, sh2, sel, qo, set_stride, n_sets);
   }
-  return launch_ln_t<1>(x, ldx, nullptr, 0, sc, sh, mode, eps, nullptr, 0, nullptr, 0, M, D, stream, sc2, sh2, sel, qo);
+  return launch_ln_t<1>(x, ldx, nullptr, 0, sc, sh, mode, eps, nullptr, 0, nullptr, 0, M, D, stream, sc2, sh2, sel, qo, set_stride, n_sets);
 }
 
 hipError_t launch_ln_modulate_mxfp4(const float* x, long ldx, const float* sc, const float* sh, int mode, float eps, uint8_t* q,
                                     long ldq, uint8_t* mx, long mx_rows, int M, int D, hipStream_t stream, const float* sc2,
-                                    const float* sh2, const uint8_t* sel) {
+                                    const float* sh2, const uint8_t* sel, long set_stride, int n_sets) {
   if (!q || !mx || ((uintptr_t)q & 3) != 0 || (ldq % 16) != 0 || ldq < D / 2 || (mx_rows % 64) != 0 || mx_rows < ((M + 63) / 64) * 64)
     return hipErrorInvalidValue;
   const LnQuantOut qo{q, ldq, nullptr, mx, mx_rows};
-  return launch_ln_t<3>(x, ldx, nullptr, 0, sc, sh, mode, eps, nullptr, 0, nullptr, 0, M, D, stream, sc2, sh2, sel, qo);
+  return launch_ln_t<3>(x, ldx, nullptr, 0, sc, sh, mode, eps, nullptr, 0, nullptr, 0, M, D, stream, sc2, sh2, sel, qo, set_stride, n_sets);
 }
 
 hipError_t launch_rmsnorm_rope(bf16_t* x, long ldx, const float* w, float eps, const float* cs, int cs_row0,
@@ -928,6 +937,202 @@ hipError_t launch_token_t_prepare(const float* t, int n_all, int row0, int n_row
                                   hipStream_t stream) {
   if (!t || n_all <= 0 || row0 < 0 || n_rows <= 0 || row0 + n_rows > n_all || n_rows_pad < n_rows) return hipErrorInvalidValue;
   hipLaunchKernelGGL(token_t_prepare_kernel, dim3(1), dim3(1024), 0, stream, t, n_all, row0, n_rows, n_rows_pad, t2, sel);
+  return hipGetLastError();
+}
+
+// Up to `cap` distinct per-token timesteps, see ops.h.  One block, like token_t_prepare_kernel: round s finds the largest
+// value below the one round s - 1 found (a block-wide maximum over all tokens), until nothing is left or the table is full --
+// as many passes over t (a few 100 KB, L2-resident after the first) as there are values.  x + 0.0f maps -0.0 to 0.0; NaN
+// fails every comparison, so it never enters the table and is counted with the tokens that have no set.
+__global__ __launch_bounds__(1024) void token_t_sets_kernel(const float* __restrict__ t, int n_all, int row0, int n_rows,
+                                                            int n_rows_pad, int cap, float* __restrict__ t2,
+                                                            float* __restrict__ vals, uint8_t* __restrict__ sel) {
+  __shared__ float s_red[16], s_min[16], s_vals[kMaxTokenSets];
+  __shared__ int s_any[16], s_cnt[16], s_count;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const float inf = __builtin_huge_valf();
+  float mn = inf;
+  float cur = inf;
+  int count = 0;
+  for (int s = 0; s < cap; ++s) {
+    float best = -inf;
+    int any = 0;
+    for (int i = threadIdx.x; i < n_all; i += 1024) {
+      const float v = t[i] + 0.0f;
+      if (s == 0) mn = fminf(mn, v);
+      if (s == 0 ? v == v : v < cur) {
+        best = fmaxf(best, v);
+        any = 1;
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      best = fmaxf(best, __shfl_xor(best, o, 64));
+      any |= __shfl_xor(any, o, 64);
+    }
+    __syncthreads();   // the previous round's readers of s_red / s_any are done
+    if (lane == 0) { s_red[wv] = best; s_any[wv] = any; }
+    __syncthreads();
+    best = s_red[0];
+    any = s_any[0];
+#pragma unroll
+    for (int w = 1; w < 16; ++w) {
+      best = fmaxf(best, s_red[w]);
+      any |= s_any[w];
+    }
+    if (!any) break;   // uniform: every thread read the same 16 slots
+    if (threadIdx.x == 0) s_vals[s] = best;
+    cur = best;
+    count = s + 1;
+  }
+  // min over all tokens (NaN ignored by fminf), and the table padded with the last value found
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mn = fminf(mn, __shfl_xor(mn, o, 64));
+  if (lane == 0) s_min[wv] = mn;
+  if (threadIdx.x == 0) {
+    const float last = count > 0 ? s_vals[count - 1] : 0.f;   // (all NaN: a finite timestep all the same)
+    for (int s = count; s < cap; ++s) s_vals[s] = last;
+  }
+  __syncthreads();
+  if (threadIdx.x < cap) vals[threadIdx.x] = s_vals[threadIdx.x];
+  // tokens without a set: below the last value of a full table, or NaN
+  const float last = s_vals[cap - 1];
+  int other = 0;
+  for (int i = threadIdx.x; i < n_all; i += 1024) other += !((t[i] + 0.0f) >= last);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) other += __shfl_xor(other, o, 64);
+  if (lane == 0) s_cnt[wv] = other;
+  for (int i = threadIdx.x; i < n_rows_pad; i += 1024) {
+    int k = 0;
+    if (i < n_rows) {
+      const float v = t[row0 + i] + 0.0f;
+      k = cap - 1;
+      for (int j = 0; j < count; ++j)
+        if (s_vals[j] == v) { k = j; break; }
+    }
+    sel[i] = (uint8_t)k;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int c = 0;
+    float m = s_min[0];
+    for (int w = 0; w < 16; ++w) { c += s_cnt[w]; m = fminf(m, s_min[w]); }
+    t2[0] = s_vals[0];
+    t2[1] = m;
+    t2[2] = (float)c;
+    t2[3] = (float)count;
+  }
+}
+
+hipError_t launch_token_t_sets(const float* t, int n_all, int row0, int n_rows, int n_rows_pad, int cap, float* t2, float* vals,
+                               uint8_t* sel, hipStream_t stream) {
+  if (!t || !t2 || !vals || !sel || n_all <= 0 || row0 < 0 || n_rows <= 0 || row0 + n_rows > n_all || n_rows_pad < n_rows ||
+      cap < 1 || cap > kMaxTokenSets)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(token_t_sets_kernel, dim3(1), dim3(1024), 0, stream, t, n_all, row0, n_rows, n_rows_pad, cap, t2, vals, sel);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ the time chain over R rows (ops.h)
+__global__ void sinusoid_rows_kernel(const float* __restrict__ t_dev, int dim, float* __restrict__ out, long ldo) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int halfd = dim / 2;
+  if (i >= halfd) return;
+  float* o = out + (size_t)blockIdx.y * ldo;
+  const double t = (double)t_dev[blockIdx.y];
+  const double fr = pow(10000.0, -(double)i / (double)halfd);
+  const double a = t * fr;
+  o[i] = (float)cos(a);
+  o[halfd + i] = (float)sin(a);
+}
+
+// one wave per weight row, the row in registers (NK 16-byte vectors per lane), then gemv_f32_kernel's sum per right-hand side
+template <int NK>
+__global__ __launch_bounds__(256) void gemv_f32_rows_kernel(const float* __restrict__ Wt, const float* __restrict__ x, long ldx,
+                                                            const float* __restrict__ b, float* __restrict__ y, long ldy, int R,
+                                                            int N, int K, int act_in, int act_out) {
+  const int lane = threadIdx.x & 63;
+  const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (n >= N) return;
+  const float* wr = Wt + (size_t)n * K;
+  f32x4 wv[NK];
+#pragma unroll
+  for (int i = 0; i < NK; ++i) {
+    const int k = i * 256 + lane * 4;
+    wv[i] = k < K ? *(const f32x4*)(wr + k) : f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  const float bn = b ? b[n] : 0.f;
+  for (int r = 0; r < R; ++r) {
+    const float* xr = x + (size_t)r * ldx;
+    float acc = 0.f;
+#pragma unroll
+    for (int i = 0; i < NK; ++i) {
+      const int k = i * 256 + lane * 4;
+      if (k < K) {
+        f32x4 xv = *(const f32x4*)(xr + k);
+        if (act_in == 1) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) xv[j] = silu(xv[j]);
+        }
+        acc += (wv[i][0] * xv[0] + wv[i][1] * xv[1]) + (wv[i][2] * xv[2] + wv[i][3] * xv[3]);
+      }
+    }
+    acc = wave_sum(acc);
+    if (lane == 0) {
+      float v = acc + bn;
+      if (act_out == 1) v = silu(v);
+      y[(size_t)r * ldy + n] = v;
+    }
+  }
+}
+
+struct BcastPtrs {   // the b vectors of one launch, by value in the kernel arguments (no device-side pointer array to keep)
+  const float* b[64];
+};
+__global__ void add_bcast_rows_kernel(const float* __restrict__ a, long lda, int na, BcastPtrs b, int n, float* __restrict__ out,
+                                      long ld_set) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int j = blockIdx.y, r = blockIdx.z;
+  out[(size_t)r * ld_set + (size_t)j * n + i] = a[(size_t)r * lda + i % na] + b.b[j][i];
+}
+
+hipError_t launch_sinusoid_rows(const float* t_dev, int R, int dim, float* out, long ldo, hipStream_t stream) {
+  if (!t_dev || !out || R < 1 || R > kMaxTokenSets || dim < 2) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(sinusoid_rows_kernel, dim3((dim / 2 + 127) / 128, R), dim3(128), 0, stream, t_dev, dim, out, ldo);
+  return hipGetLastError();
+}
+
+hipError_t launch_gemv_f32_rows(const float* W, const float* x, long ldx, const float* b, float* y, long ldy, int R, int N, int K,
+                                int act_in, int act_out, hipStream_t stream) {
+  if (!W || !x || !y || R < 1 || R > kMaxTokenSets || N <= 0 || K <= 0 || (K % 4) != 0 || K > 8192 || (ldx % 4) != 0)
+    return hipErrorInvalidValue;
+  const dim3 grid((N + 3) / 4), block(256);
+  const int nk = (K + 255) / 256;
+#define MC_GEMV_ROWS(NK) \
+  hipLaunchKernelGGL(gemv_f32_rows_kernel<NK>, grid, block, 0, stream, W, x, ldx, b, y, ldy, R, N, K, act_in, act_out)
+  if (nk <= 1) MC_GEMV_ROWS(1);
+  else if (nk <= 6) MC_GEMV_ROWS(6);
+  else if (nk <= 12) MC_GEMV_ROWS(12);
+  else if (nk <= 20) MC_GEMV_ROWS(20);
+  else MC_GEMV_ROWS(32);
+#undef MC_GEMV_ROWS
+  return hipGetLastError();
+}
+
+hipError_t launch_add_bcast_rows(const float* a, long lda, int R, int na, const float* const* b, int n_b, int n, float* out,
+                                 long ld_set, hipStream_t stream) {
+  if (!a || !b || !out || R < 1 || R > kMaxTokenSets || na <= 0 || n <= 0 || n_b < 1) return hipErrorInvalidValue;
+  for (int j0 = 0; j0 < n_b; j0 += 64) {   // (one launch up to 64 vectors: every Wan depth; never a function of R)
+    BcastPtrs bp = {};
+    const int nj = n_b - j0 < 64 ? n_b - j0 : 64;
+    for (int j = 0; j < nj; ++j) {
+      if (!b[j0 + j]) return hipErrorInvalidValue;
+      bp.b[j] = b[j0 + j];
+    }
+    hipLaunchKernelGGL(add_bcast_rows_kernel, dim3((n + 255) / 256, nj, R), dim3(256), 0, stream, a, lda, na, bp, n,
+                       out + (size_t)j0 * n, ld_set);
+  }
   return hipGetLastError();
 }
 

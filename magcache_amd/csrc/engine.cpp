@@ -236,7 +236,8 @@ void plan_workspace(const mc_engine* e, const Rows& rows, mc::Workspace& ws) {
     ws.add("ckv_cache", (size_t)2 * (e->NL + e->NV) * e->ctx_rows * 2 * d * 2);      // [2][layers][ctx_rows][2d]
   // two sets of everything that depends on t: set 0 for the (maximum) timestep, set 1 for the second value per-token
   // timesteps may carry (Wan2.2 TI2V: the conditioning frame's tokens have t = 0)
-  const size_t tsets = c.no_token_timesteps ? 1 : 2;
+  // token_timestep_sets = C: C sets at the same per-set strides, one per distinct per-token timestep ("tok_vals": the values)
+  const size_t tsets = c.no_token_timesteps ? 1 : c.token_timestep_sets ? (size_t)c.token_timestep_sets : 2;
   ws.add("temb", tsets * (c.freq_dim + 2 * d + 6 * d) * 4);  // sets x (sinus | h1 | e | e0)
   ws.add("emod", tsets * (e->NL + e->NV) * 6 * d * 4);
   ws.add("tok_sel", c.no_token_timesteps ? 256 : (size_t)Lp + 256);
@@ -251,7 +252,7 @@ void plan_workspace(const mc_engine* e, const Rows& rows, mc::Workspace& ws) {
     ws.add("c0", Lp * d * 2);                       // vace_patch_embedding(vace_context), constant per video
     ws.add("vtokens", Lp * (size_t)e->Kvp * 2);
   }
-  ws.add("ehead", 2 * 2 * d * 4);
+  ws.add("ehead", std::max<size_t>(2, tsets) * 2 * d * 4);
   ws.add("head_tokens", (size_t)Lp * e->HT * 4);
   // sequence parallel: "kv_local" [Lp][2d] = this rank's post-norm, post-RoPE K|V rows (the send buffer of the gather);
   // "kv_gather" [C][P][Lp / C][2d] = round c of the gather holds rows [c Lp / C, (c + 1) Lp / C) of EVERY rank's shard
@@ -283,6 +284,7 @@ void plan_workspace(const mc_engine* e, const Rows& rows, mc::Workspace& ws) {
   // the kept front of a CFG pair (mc_pair_begin): last in the plan, every other offset stays where it was
   ws.add("pair_x", e->pair_capable() ? Lp * d * 4 : 256);
   ws.add("pair_cq", e->pair_capable() ? Lp * d * 2 : 256);
+  if (c.token_timestep_sets) ws.add("tok_vals", 256);   // (behind the kept front: a default engine's plan is what it was)
 }
 
 // The RoPE table of the engine's grid, for this rank's rows: the per-axis values are computed on the host (the doubles of
@@ -488,6 +490,10 @@ mc_status mc_create(const mc_config* cfg, mc_engine** out) {
                                                    (c.vace_layers - 1) * c.vace_stride >= c.num_layers)))
     return fail(MC_EINVAL, "bad VACE geometry: %d blocks, stride %d, in_dim %d", c.vace_layers, c.vace_stride, c.vace_in_dim);
   if ((c.no_context_cache | c.no_token_timesteps) & ~1) return fail(MC_EINVAL, "no_context_cache / no_token_timesteps must be 0 or 1");
+  if (c.token_timestep_sets != 0 && (c.token_timestep_sets < 3 || c.token_timestep_sets > mc::kMaxTokenSets))
+    return fail(MC_EINVAL, "token_timestep_sets must be 0 (two sets) or 3..%d, not %d", mc::kMaxTokenSets, c.token_timestep_sets);
+  if (c.token_timestep_sets != 0 && c.no_token_timesteps)
+    return fail(MC_EINVAL, "token_timestep_sets = %d with no_token_timesteps = 1", c.token_timestep_sets);
   if (c.fp8_linear < 0 || c.fp8_linear > 3)
     return fail(MC_EINVAL, "fp8_linear must be 0, 1 (per-row scales), 2 (MX block scales: QKV, FFN-1, FFN-2) or 3 (MX, the d x d Linears too)");
   if (c.fp8_linear && ((c.dim % 256) || (c.ffn_dim % 256) || c.dim < 512 || c.ffn_dim < 512))
@@ -617,6 +623,9 @@ void mc_destroy(mc_engine* e) {
 
 size_t mc_workspace_bytes(const mc_engine* e) { return e ? e->work.need : 0; }
 
+int mc_engine_token_timestep_sets(const mc_engine* e) {
+  return !e || e->cfg.no_token_timesteps ? 0 : e->cfg.token_timestep_sets ? e->cfg.token_timestep_sets : 2;
+}
 int mc_engine_mx_fp4(const mc_engine* e) { return e && e->mx_fmt == mc::MX_E2M1 ? 1 : 0; }
 int mc_engine_mx_fp6(const mc_engine* e) { return e && e->mx_fmt == mc::MX_E2M3 ? 1 : 0; }
 
@@ -851,9 +860,31 @@ static mc_status embed_latent_time(mc_engine* e, const float* latent_dev, const 
   // runs for the two values the tokens carry -- max (set 0) and min (set 1) -- and every consumer selects per token.
   const int n_sets = e->tok_t ? 2 : 1;
   float* t2 = e->buf<float>("tok_t2");
+  const size_t temb_set = (size_t)c.freq_dim + 2 * d + 6 * d, emod_set = (size_t)(e->NL + e->NV) * 6 * d;
+  if (e->tok_t && c.token_timestep_sets) {
+    // a capacity engine: the distinct values in one pass ("tok_vals", descending, padded), then the SAME chain over all C
+    // sets at once -- seven launches whatever C is, every weight row read once, every set's bits those of the loop below
+    const int C = c.token_timestep_sets;
+    float* vals = e->buf<float>("tok_vals");
+    HIP_TRY(mc::launch_token_t_sets(e->tok_t, e->L, e->tok0, e->Lr, e->Lp, C, t2, vals, e->buf<uint8_t>("tok_sel"), s));
+    float* temb = e->buf<float>("temb");
+    float* h1 = temb + c.freq_dim;
+    float* ev = h1 + d;
+    float* e0 = ev + d;
+    const long ts = (long)temb_set;
+    HIP_TRY(mc::launch_sinusoid_rows(vals, C, c.freq_dim, temb, ts, s));
+    HIP_TRY(mc::launch_gemv_f32_rows(e->w_time0, temb, ts, e->b_time0, h1, ts, C, d, c.freq_dim, 0, 1, s));
+    HIP_TRY(mc::launch_gemv_f32_rows(e->w_time1, h1, ts, e->b_time1, ev, ts, C, d, d, 0, 0, s));
+    HIP_TRY(mc::launch_gemv_f32_rows(e->w_tproj, ev, ts, e->b_tproj, e0, ts, C, 6 * d, d, 1, 0, s));
+    std::vector<const float*> mods(e->NL + e->NV);
+    for (int l = 0; l < e->NL + e->NV; ++l) mods[l] = e->layer(l).mod;
+    HIP_TRY(mc::launch_add_bcast_rows(e0, ts, C, 6 * d, mods.data(), (int)mods.size(), 6 * d, e->buf<float>("emod"), (long)emod_set, s));
+    const float* hm = e->head_mod;
+    HIP_TRY(mc::launch_add_bcast_rows(ev, ts, C, d, &hm, 1, 2 * d, e->buf<float>("ehead"), 2 * d, s));
+    return MC_OK;
+  }
   if (e->tok_t)
     HIP_TRY(mc::launch_token_t_prepare(e->tok_t, e->L, e->tok0, e->Lr, e->Lp, t2, e->buf<uint8_t>("tok_sel"), s));
-  const size_t temb_set = (size_t)c.freq_dim + 2 * d + 6 * d, emod_set = (size_t)(e->NL + e->NV) * 6 * d;
   for (int set = 0; set < n_sets; ++set) {
     float* temb = e->buf<float>("temb") + set * temb_set;
     float* sinus = temb;
@@ -908,17 +939,21 @@ mc_status mc_embed(mc_engine* e, const float* latent_dev, const float* t_dev, do
 
 // LayerNorm + modulate of x for the Linear `l`, as that Linear's activation source: with fp8_fused_quant an fp8 Linear's row
 // goes straight to "aq" (+ scales); otherwise the bf16 row goes to "xn" as ever (and an fp8 Linear quantises it).
+// set_stride != 0: sc / sh are the first of the engine's token_timestep_sets sets, set_stride floats apart (sc2 / sh2 unused)
 static mc_status ln_for_gemm(mc_engine* e, const Linear& l, const float* x, const float* sc, const float* sh, int mode,
-                             const float* sc2, const float* sh2, const uint8_t* sel, hipStream_t s, ActSrc* a) {
+                             const float* sc2, const float* sh2, const uint8_t* sel, hipStream_t s, ActSrc* a,
+                             long set_stride = 0) {
+  const int n_sets = set_stride ? e->cfg.token_timestep_sets : 0;
   const int d = e->d, Lp = e->Lp;
   bf16_t* xn = e->buf<bf16_t>("xn");
   *a = ActSrc{xn, d, fused_quant(l)};
   if (a->quantised) {
     HIP_TRY(mc::launch_ln_modulate_fp8(x, d, sc, sh, mode, e->cfg.eps, e->buf<uint8_t>("aq"), d,
                                        l.mx ? nullptr : e->buf<float>("a_scale"), l.mx ? e->buf<uint8_t>("a_mx") : nullptr,
-                                       (long)Lp, Lp, d, s, sc2, sh2, sel));
+                                       (long)Lp, Lp, d, s, sc2, sh2, sel, set_stride, n_sets));
   } else {
-    HIP_TRY(mc::launch_ln_modulate(x, d, nullptr, 0, sc, sh, mode, e->cfg.eps, xn, d, nullptr, 0, Lp, d, s, sc2, sh2, sel));
+    HIP_TRY(mc::launch_ln_modulate(x, d, nullptr, 0, sc, sh, mode, e->cfg.eps, xn, d, nullptr, 0, Lp, d, s, sc2, sh2, sel,
+                                   set_stride, n_sets));
   }
   return MC_OK;
 }
@@ -926,8 +961,16 @@ static mc_status ln_for_gemm(mc_engine* e, const Linear& l, const float* x, cons
 // l / em / x: the block's weights, its 6 modulation vectors and the residual stream it works on (the main stream
 // "x", or the VACE control stream "xc")
 // em2 / sel: the second modulation set (em + one "emod" set) and the per-token selector when per-token timesteps are on
+// A capacity engine (token_timestep_sets) has no "second" set: its consumers get (em, set_stride, sel) and take row
+// min(sel, C - 1) of the table of sets that starts at em.
 static const float* second_set(const mc_engine* e, const float* em) {
-  return e->tok_t ? em + (size_t)(e->NL + e->NV) * 6 * e->d : nullptr;
+  return e->tok_t && !e->cfg.token_timestep_sets ? em + (size_t)(e->NL + e->NV) * 6 * e->d : nullptr;
+}
+static long set_stride(const mc_engine* e) {
+  return e->tok_t && e->cfg.token_timestep_sets ? (long)(e->NL + e->NV) * 6 * e->d : 0;
+}
+static void gate_table(const mc_engine* e, mc::GemmParams& p) {
+  if (const long st = set_stride(e)) { p.gate_sel = e->buf<uint8_t>("tok_sel"); p.gate_stride = st; p.gate_sets = e->cfg.token_timestep_sets; }
 }
 static const uint8_t* tok_sel(const mc_engine* e) { return e->tok_t ? e->buf<uint8_t>("tok_sel") : nullptr; }
 
@@ -940,7 +983,7 @@ static mc_status block_pre_kv(mc_engine* e, const Layer& l, const float* em, flo
   ActSrc a;
   {
     Prof pr(e, MC_PROF_LN_MODULATE, s);
-    MC_TRY(ln_for_gemm(e, l.qkv, x, em + d, em, 0, em2 ? em2 + d : nullptr, em2, tok_sel(e), s, &a));
+    MC_TRY(ln_for_gemm(e, l.qkv, x, em + d, em, 0, em2 ? em2 + d : nullptr, em2, tok_sel(e), s, &a, set_stride(e)));
   }
   mc::GemmParams p = {};
   if (!e->sp) {
@@ -1151,6 +1194,7 @@ static mc_status block_post_self(mc_engine* e, const Layer& l, const float* em, 
     mc::GemmParams p = {};
     p.X = x; p.ldx = d; p.gate = em + 2 * d;
     if (em2) { p.gate2 = em2 + 2 * d; p.gate_sel = sel; }
+    gate_table(e, p);
     MC_TRY(linear(e, l.o, whole(l.o), Lp, ActSrc{ao, d}, p, mc::EPI_RESID_GATE, s));
   }
   // ---- cross attention: x = x + o(attn(norm_q(q(norm3(x))), norm_k(k(ctx)), v(ctx)))
@@ -1232,7 +1276,7 @@ static mc_status block_post_ctx(mc_engine* e, const Layer& l, const float* em, f
   {
     Prof pr(e, MC_PROF_LN_MODULATE, s);
     MC_TRY(ln_for_gemm(e, l.ffn1, x, em + 4 * d, em + 3 * d, 0, em2 ? em2 + 4 * d : nullptr, em2 ? em2 + 3 * d : nullptr, sel,
-                       s, &xn));
+                       s, &xn, set_stride(e)));
   }
   bf16_t* h = e->buf<bf16_t>("h");
   mc::GemmParams p = {};
@@ -1253,6 +1297,7 @@ static mc_status block_post_ctx(mc_engine* e, const Layer& l, const float* em, f
   q.X = x; q.ldx = d; q.gate = em + 5 * d;
   if (e->splitk_bytes) { q.splitk_ws = e->buf<float>("splitk"); q.splitk_ws_bytes = e->splitk_bytes; }
   if (em2) { q.gate2 = em2 + 5 * d; q.gate_sel = sel; }
+  gate_table(e, q);
   if (capture) {   // fused into the last epilogue
     q.X0 = e->buf<bf16_t>("x0"); q.ldx0 = d;
     q.R = capture_dst(e, branch, mode); q.ldr = d;
@@ -1452,18 +1497,20 @@ static mc_status head(mc_engine* e, const float* x, int branch, mc_mode mode, hi
   if (branch < 0 || branch >= e->cfg.n_branches) return fail(MC_EINVAL, "branch %d out of range", branch);
   const int d = e->d;
   const float* eh = e->buf<float>("ehead");
-  const float* eh2 = e->tok_t ? eh + 2 * d : nullptr;
+  const float* eh2 = e->tok_t && !e->cfg.token_timestep_sets ? eh + 2 * d : nullptr;
   const uint8_t* sel = tok_sel(e);
+  const long hst = e->tok_t && e->cfg.token_timestep_sets ? 2 * d : 0;   // a capacity engine: "ehead" is a table of C sets
+  const int hsets = hst ? e->cfg.token_timestep_sets : 0;
   float* hn = e->buf<float>("h");
   Prof pr(e, MC_PROF_HEAD, s);
   if (mode == MC_MODE_SKIP) {
     // skipped step: x = ori_x + residual_cache[branch] (:294-295), folded into the LayerNorm load
     if (!e->have_res[branch]) return fail(MC_ESTATE, "skip requested but residual_cache[%d] is empty", branch);
     HIP_TRY(mc::launch_ln_modulate(e->residual(e->res_slot[branch]), d, e->buf<bf16_t>("x0"), d, eh + d, eh, 0,
-                                   e->cfg.eps, nullptr, 0, hn, d, e->Lr, d, s, eh2 ? eh2 + d : nullptr, eh2, sel));
+                                   e->cfg.eps, nullptr, 0, hn, d, e->Lr, d, s, eh2 ? eh2 + d : nullptr, eh2, sel, hst, hsets));
   } else {
     HIP_TRY(mc::launch_ln_modulate(x, d, nullptr, 0, eh + d, eh, 0, e->cfg.eps, nullptr, 0, hn, d,
-                                   e->Lr, d, s, eh2 ? eh2 + d : nullptr, eh2, sel));
+                                   e->Lr, d, s, eh2 ? eh2 + d : nullptr, eh2, sel, hst, hsets));
   }
   HIP_TRY(mc::launch_head_linear(hn, d, e->w_head, e->b_head, e->buf<float>("head_tokens"), e->HT, e->Lr,
                                  e->cfg.out_dim * 4, d, s));

@@ -135,7 +135,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_tn_kernel(GemmParams p, int 
     for (int mi = 0; mi < 2; ++mi) {
       const int m = m0 + wm * 64 + mi * 32 + l31;
       const int ml = min(m, p.M - 1);           // rows past M: loaded (clamped), not stored
-      const float* gp = (p.gate_sel && p.gate_sel[ml]) ? p.gate2 : p.gate;
+      const float* gp = gate_row(p, ml);
       ResidIn in[2][4];
       f32x4 gt[2][4], bv[2][4];
 #pragma unroll
@@ -274,6 +274,7 @@ int gemm_bf16_kernel_for(const GemmParams& p, int epi) {
 }
 
 hipError_t launch_gemm_bf16(const GemmParams& p, int epi, hipStream_t stream) {
+  if (p.gate_stride != 0 && !gemm_gate_table_ok(p)) return hipErrorInvalidValue;
   if (p.m_split > 0) {
     // two Linears over two row ranges: one gemm_bf16_v2 launch where that kernel can do it, otherwise the two launches
     if (p.m_split >= p.M || !p.W_b) return hipErrorInvalidValue;

@@ -379,9 +379,10 @@ __global__ __launch_bounds__(512, 2) void gemm_big_kernel(GemmParams p, int tile
 #define MC_EPI_DEPTH 2
 #endif
     constexpr int MBB = (EPI == EPI_RESID_CAPTURE) ? 1 : MC_EPI_MBB;
-    auto resid = [&](auto with_sel) {
+    auto resid = [&](auto with_sel, auto with_sets) {
       constexpr bool SEL = decltype(with_sel)::value;          // per-row choice between two gate vectors (Wan2.2 TI2V)
-      constexpr int DEPTH = SEL ? 1 : MC_EPI_DEPTH;            // (the second gate vector takes the second batch's registers)
+      constexpr bool SETS = decltype(with_sets)::value;        // per-row choice of a row of a gate table (gate_stride != 0)
+      constexpr int DEPTH = (SEL || SETS) ? 1 : MC_EPI_DEPTH;  // (the second gate vector takes the second batch's registers)
       f32x4 g2[2][2];
 #pragma unroll
       for (int nh = 0; nh < 2; ++nh)
@@ -396,16 +397,20 @@ __global__ __launch_bounds__(512, 2) void gemm_big_kernel(GemmParams p, int tile
       constexpr int NBATCH = 8 / MBB;
       ResidIn in[DEPTH][MBB][2][2];
       uint8_t sel[DEPTH][MBB];
+      f32x4 gt[SETS ? MBB : 1][2][2];                          // SETS: the row's own gate quads, loaded with its x
       auto load_batch = [&](int b, int slot) {
 #pragma unroll
         for (int j = 0; j < MBB; ++j) {
           const int m = min(em0 + wr * 128 + (b * MBB + j) * 16 + l15, p.M - 1);   // rows past M: loaded (clamped), not stored
           sel[slot][j] = SEL ? p.gate_sel[m] : (uint8_t)0;
+          const float* grow = SETS ? gate_row(p, m) : p.gate;
 #pragma unroll
           for (int nh = 0; nh < 2; ++nh)
 #pragma unroll
-            for (int nb = 0; nb < 2; ++nb)
+            for (int nb = 0; nb < 2; ++nb) {
               in[slot][j][nh][nb] = resid_load<EPI>(p, m, en0 + wc * 64 + nh * 32 + nb * 16 + 4 * kgrp);
+              if constexpr (SETS) gt[j][nh][nb] = *(const f32x4*)(grow + en0 + wc * 64 + nh * 32 + nb * 16 + 4 * kgrp);
+            }
         }
       };
       auto apply_batch = [&](int b, int slot) {
@@ -420,7 +425,8 @@ __global__ __launch_bounds__(512, 2) void gemm_big_kernel(GemmParams p, int tile
             for (int nb = 0; nb < 2; ++nb)
               resid_apply<EPI>(p, m, en0 + wc * 64 + nh * 32 + nb * 16 + 4 * kgrp,
                                acc[mblk >> 2][mblk & 3][nh][nb] + bq[nh][nb],
-                               (SEL && sel[slot][j]) ? g2[nh][nb] : g1[nh][nb], in[slot][j][nh][nb]);
+                               SETS ? gt[SETS ? j : 0][nh][nb] : (SEL && sel[slot][j]) ? g2[nh][nb] : g1[nh][nb],
+                               in[slot][j][nh][nb]);
         }
       };
 #pragma unroll
@@ -431,8 +437,9 @@ __global__ __launch_bounds__(512, 2) void gemm_big_kernel(GemmParams p, int tile
         if (b + DEPTH < NBATCH) load_batch(b + DEPTH, b % DEPTH);
       }
     };
-    if (p.gate_sel) resid(std::true_type{});
-    else resid(std::false_type{});
+    if (p.gate_sel && p.gate_stride != 0) resid(std::false_type{}, std::true_type{});
+    else if (p.gate_sel) resid(std::true_type{}, std::false_type{});
+    else resid(std::false_type{}, std::false_type{});
   } else {
 #pragma unroll
     for (int mh = 0; mh < 2; ++mh) {

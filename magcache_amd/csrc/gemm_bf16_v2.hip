@@ -67,6 +67,10 @@ int g_gemm_defer = 1;   // only read when the stream was generated with --defer 
 namespace {
 
 constexpr int TB = 256;
+// internal instantiations, like EPI_RESID_GATE_SEL / _CAPTURE_SEL of ops.h: the gated residual (+ capture) with a TABLE of gate
+// vectors -- row m takes gate + min(gate_sel[m], gate_sets - 1) * gate_stride; the launcher picks them when gate_stride != 0.
+// (Not in GemmEpi: its values are what callers pass, and its last one stays the last.)
+constexpr int EPI_RESID_GATE_SETS = 100, EPI_RESID_CAPTURE_SETS = 101;
 constexpr int V2_RING_BYTES = 4 * 32768;     // the operand ring (two 64 KiB K tiles, or four 32 KiB sub-stages)
 constexpr int V2_STRIP_BYTES = 16 * 272;      // per wave: the epilogue's transposition strip (16 rows x 128 bf16, rows padded)
 constexpr int V2_LDS_BYTES = V2_RING_BYTES + 4 * V2_STRIP_BYTES;
@@ -128,9 +132,11 @@ __global__ __launch_bounds__(256, 1) void gemm_v2_kernel(GemmParams p, int tiles
   const uint32_t lds0 = (uint32_t)(uintptr_t)MC_LDS_PTR(smem);
   // residual forms: x += gate * bf16(acc + bias); CAPTURE: and R = x_new - ori_x (the MagCache residual, last layer's FFN-2);
   // SEL: the gate vector is chosen per row (gate_sel[m] ? gate2 : gate -- Wan2.2 TI2V's two timesteps per forward)
-  constexpr bool CAPTURE = EPI == EPI_RESID_CAPTURE || EPI == EPI_RESID_CAPTURE_SEL;
+  // SETS: the gate vector is row min(gate_sel[m], gate_sets - 1) of a table (gate + k * gate_stride): up to 64 timesteps
+  constexpr bool CAPTURE = EPI == EPI_RESID_CAPTURE || EPI == EPI_RESID_CAPTURE_SEL || EPI == EPI_RESID_CAPTURE_SETS;
   constexpr bool SEL = EPI == EPI_RESID_GATE_SEL || EPI == EPI_RESID_CAPTURE_SEL;
-  constexpr bool RESID = EPI == EPI_RESID_GATE || CAPTURE || SEL;
+  constexpr bool SETS = EPI == EPI_RESID_GATE_SETS || EPI == EPI_RESID_CAPTURE_SETS;
+  constexpr bool RESID = EPI == EPI_RESID_GATE || CAPTURE || SEL || SETS;
   constexpr bool LEAN = MC_GEMM_V2_MFMA == 16 && (EPI == EPI_BF16 || EPI == EPI_GELU_BF16 || RESID || EPI == EPI_BF16_GELU_SPLIT);
   constexpr bool CAN_DEFER = MC_GEMM_V2_PERSIST && MC_GEMM_V2_SCHED_H && MC_GEMM_V2_DEFER && EPI == EPI_RESID_GATE;
 
@@ -184,7 +190,7 @@ __global__ __launch_bounds__(256, 1) void gemm_v2_kernel(GemmParams p, int tiles
     } else if (RESID) {
       // lane -> columns 4 c16 .. + 3 and 64 + 4 c16 .. + 3 of the wave's 128: every x load / store instruction then covers 256
       // CONTIGUOUS bytes of a row (two whole 128-byte lines), instead of 16 bytes out of every 32 over all four lines
-      if (gate_v) {
+      if (gate_v && !SETS) {
         const float* gp = gate_v + tn0 + wc_ * 128 + c16 * 4;
         gA = *(const f32x4*)gp;
         gB = *(const f32x4*)(gp + 64);
@@ -229,6 +235,30 @@ __global__ __launch_bounds__(256, 1) void gemm_v2_kernel(GemmParams p, int tiles
     f32x4 xin[XS][4][2];
     u32x2 x0in[CAPTURE ? XS : 1][4][2];        // CAPTURE: ori_x quads of the same rows
     uint32_t selin[SEL ? XS : 1][4];           // SEL: gate_sel of the lane's 4 rows of the m block
+    // SETS: the set indices of ALL of the lane's 32 rows, fetched (and clamped) here, ahead of the loop -- a gate load's
+    // address hangs on its row's selector byte, and a byte load in front of every m block's loads would put a memory round
+    // trip between the x prefetch and its issue -- four to a register (32 offsets would be 32 VGPRs: the capture form then
+    // spills).  gin: the two gate quads of each row, loaded with that m block's x (L2-resident: gate_sets rows of N floats)
+    uint32_t gsel[SETS ? 8 : 1];
+    f32x4 gin[SETS ? XS : 1][4][2];
+    __amdgpu_buffer_rsrc_t rgate = rio;          // (only read when SETS)
+    uint32_t gstride_b = 0, gcol_b = 0;
+    if constexpr (SETS) {
+      if (resid_here) {
+        gstride_b = (uint32_t)p.gate_stride * 4u;
+        gcol_b = (uint32_t)(wc_ * 128 + c16 * 4) * 4u;
+        rgate = __builtin_amdgcn_make_buffer_rsrc((void*)(p.gate + tn0), 0, (uint32_t)(p.gate_sets - 1) * gstride_b + TB * 4u, 0x00020000);
+#pragma unroll
+        for (int mb = 0; mb < 8; ++mb) {
+          gsel[mb] = 0;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const uint32_t k = p.gate_sel[min(tm0 + wr_ * 128 + mb * 16 + 4 * i + rr, p.M - 1)];
+            gsel[mb] |= min(k, (uint32_t)(p.gate_sets - 1)) << (8 * i);   // clamped before it forms an address
+          }
+        }
+      }
+    }
     auto load_x = [&](int mb, int set) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -241,6 +271,11 @@ __global__ __launch_bounds__(256, 1) void gemm_v2_kernel(GemmParams p, int tiles
           x0in[set][i][1] = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(rx0, v0row + 128u, 0, 0));
         }
         if constexpr (SEL) selin[set][i] = p.gate_sel[min(tm0 + wr_ * 128 + mb * 16 + 4 * i + rr, p.M - 1)];
+        if constexpr (SETS) {
+          const uint32_t goff = ((gsel[mb] >> (8 * i)) & 0xffu) * gstride_b + gcol_b;
+          gin[set][i][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rgate, goff, 0, 0));
+          gin[set][i][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rgate, goff + X2_OFF, 0, 0));
+        }
       }
     };
     if (resid_here) {
@@ -287,6 +322,10 @@ __global__ __launch_bounds__(256, 1) void gemm_v2_kernel(GemmParams p, int tiles
               ga = gA2;
               gb = gB2;
             }
+          }
+          if constexpr (SETS) {
+            ga = gin[mb % XS][i][0];
+            gb = gin[mb % XS][i][1];
           }
           xa[0] += __uint_as_float(w[0] << 16) * ga[0];
           xa[1] += __uint_as_float(w[0] & 0xffff0000u) * ga[1];
@@ -410,7 +449,7 @@ __global__ __launch_bounds__(256, 1) void gemm_v2_kernel(GemmParams p, int tiles
         for (int ri = 0; ri < NR; ++ri) {
           const int m = m_of(ri);
           const int ml = min(m, p.M - 1);
-          const float* gp = (SEL && p.gate_sel[ml]) ? p.gate2 : p.gate;
+          const float* gp = SEL ? gate_row(p, ml) : p.gate;
 #pragma unroll
           for (int q0 = 0; q0 < NQ; q0 += 8) {
             ResidIn in[8];
@@ -687,12 +726,19 @@ bool gemm_bf16_v2_rowsplit_ok(const GemmParams& p, int epi) {
 // can gemm_bf16_v2 run THIS epilogue on these operands?  (the dispatcher asks before it picks the kernel, so that forms the
 // kernel lacks -- a split point off the 256-column grid, strides beyond its 32-bit epilogue offsets -- take the launches they
 // replace instead of failing: ADVICE r05)
+// per-row gates: both vectors of the two-set form, or a table whose last row ends within the 32-bit offsets of its descriptor
+static bool v2_row_gates_ok(const GemmParams& p) {
+  if (!p.gate_sel) return true;
+  if (p.gate_stride == 0) return p.gate && p.gate2;
+  return gemm_gate_table_ok(p) && (size_t)(p.gate_sets - 1) * (size_t)p.gate_stride * 4 + TB * 4 < (1ull << 31);
+}
+
 bool gemm_bf16_v2_epi_ok(const GemmParams& p, int epi) {
   switch (epi) {
     case EPI_BF16: case EPI_GELU_BF16: case EPI_F32: return true;
-    case EPI_RESID_GATE: return !p.gate_sel || (p.gate && p.gate2);
+    case EPI_RESID_GATE: return v2_row_gates_ok(p);
     case EPI_RESID_CAPTURE:
-      return p.X0 && p.R && (size_t)TB * (size_t)p.ldr * 4 < (1ull << 31) && (!p.gate_sel || (p.gate && p.gate2));
+      return p.X0 && p.R && (size_t)TB * (size_t)p.ldr * 4 < (1ull << 31) && v2_row_gates_ok(p);
     case EPI_BF16_GELU_SPLIT:
       return p.n_split > 0 && p.n_split < p.N && (p.n_split % TB) == 0 && p.Cb2 && (size_t)TB * (size_t)p.ldc2 * 4 < (1ull << 31);
     default: return false;
@@ -702,13 +748,17 @@ bool gemm_bf16_v2_epi_ok(const GemmParams& p, int epi) {
 hipError_t launch_gemm_bf16_v2(const GemmParams& p, int epi, hipStream_t stream) {
   if (!gemm_bf16_v2_supported(p)) return hipErrorInvalidValue;
   if (p.m_split != 0 && !gemm_bf16_v2_rowsplit_ok(p, epi)) return hipErrorInvalidValue;
-  if (p.gate_sel && (!p.gate || !p.gate2)) return hipErrorInvalidValue;   // the per-token epilogues read both gate vectors
+  if (!v2_row_gates_ok(p)) return hipErrorInvalidValue;   // the per-token epilogues read both gate vectors, or a whole table
+  const bool sets = p.gate_sel && p.gate_stride != 0;
   switch (epi) {
     case EPI_BF16: return launch_v2_t<EPI_BF16>(p, stream);
     case EPI_GELU_BF16: return launch_v2_t<EPI_GELU_BF16>(p, stream);
-    case EPI_RESID_GATE: return p.gate_sel ? launch_v2_t<EPI_RESID_GATE_SEL>(p, stream) : launch_v2_t<EPI_RESID_GATE>(p, stream);
+    case EPI_RESID_GATE:
+      if (sets) return launch_v2_t<EPI_RESID_GATE_SETS>(p, stream);
+      return p.gate_sel ? launch_v2_t<EPI_RESID_GATE_SEL>(p, stream) : launch_v2_t<EPI_RESID_GATE>(p, stream);
     case EPI_RESID_CAPTURE:
       if (!p.X0 || !p.R || (size_t)TB * (size_t)p.ldr * 4 >= (1ull << 31)) return hipErrorInvalidValue;
+      if (sets) return launch_v2_t<EPI_RESID_CAPTURE_SETS>(p, stream);
       return p.gate_sel ? launch_v2_t<EPI_RESID_CAPTURE_SEL>(p, stream) : launch_v2_t<EPI_RESID_CAPTURE>(p, stream);
     case EPI_F32: return launch_v2_t<EPI_F32>(p, stream);
     case EPI_BF16_GELU_SPLIT:

@@ -39,6 +39,15 @@ __device__ __forceinline__ f32x2 bf16_round2(float a, float b) {
   return f32x2{__uint_as_float(w << 16), __uint_as_float(w & 0xffff0000u)};
 }
 
+// The gate vector of row m (p.gate != null): the one vector, the two-set choice (gate_sel[m] ? gate2 : gate) or, with
+// gate_stride != 0, row min(gate_sel[m], gate_sets - 1) of a table -- the byte is clamped before it forms an address.
+__device__ __forceinline__ const float* gate_row(const GemmParams& p, int m) {
+  if (!p.gate_sel) return p.gate;
+  const int k = p.gate_sel[m];
+  if (p.gate_stride != 0) return p.gate + (long)min(k, p.gate_sets - 1) * p.gate_stride;
+  return k ? p.gate2 : p.gate;
+}
+
 // val = acc + bias for columns n..n+3 of row m.
 template <int EPI>
 __device__ __forceinline__ void gemm_epilogue_quad(const GemmParams& p, int m, int n, f32x4 val) {
@@ -62,7 +71,7 @@ __device__ __forceinline__ void gemm_epilogue_quad(const GemmParams& p, int m, i
     *(u32x2*)(p.Cb + (size_t)m * p.ldc + n) = o;
   } else if constexpr (EPI == EPI_RESID_GATE || EPI == EPI_RESID_CAPTURE) {
     f32x4 gt = {1.f, 1.f, 1.f, 1.f};
-    if (p.gate) gt = *(const f32x4*)(((p.gate_sel && p.gate_sel[m]) ? p.gate2 : p.gate) + n);
+    if (p.gate) gt = *(const f32x4*)(gate_row(p, m) + n);
     float* xp = p.X + (size_t)m * p.ldx + n;
     // (non-temporal load / store of the residual row: measured 9 % slower on the O projection, 2 % on FFN-2 -- the
     // write then waits for HBM instead of L2; profiles/r02/kbench_gemm_epi_nt.log)

@@ -47,6 +47,9 @@ struct GemmParams {
   // per-token modulation (Wan2.2 TI2V: two timestep values per forward): rows with gate_sel[m] != 0 use gate2
   const float* gate2;
   const uint8_t* gate_sel;
+  // table form (gate_stride != 0, with gate_sel): gate is the first of gate_sets (1..64) vectors gate_stride floats apart and
+  // row m takes vector min(gate_sel[m], gate_sets - 1) -- the byte is clamped before it forms an address; gate2 is ignored
+  long gate_stride; int gate_sets;
   // split-K scratch (gemm_bf16_v2 only, optional): when a shape's 256 x 256 tiles fill less than half of the CUs and K is
   // long, launch_gemm_bf16 cuts K into S slices, every (tile, slice) workgroup parks its fp32 accumulators here and a second
   // launch sums the slices in index order and applies the epilogue (deterministic; not bit-identical to the unsplit sum).
@@ -72,6 +75,10 @@ struct GemmParams {
   uint8_t* c_mx; long mx_rows_c;
 };
 
+// the table form's operands (gate_stride != 0): a selector, a table, 1..64 rows at least N floats (a multiple of 4) apart
+inline bool gemm_gate_table_ok(const GemmParams& p) {
+  return p.gate_sel && p.gate && p.gate_sets >= 1 && p.gate_sets <= 64 && p.gate_stride >= p.N && (p.gate_stride % 4) == 0;
+}
 hipError_t launch_gemm_bf16(const GemmParams& p, int epi, hipStream_t stream);        // picks a kernel
 int gemm_bf16_kernel_for(const GemmParams& p, int epi);                               // ... this one: 1 small, 2 8-wave 256^2, 4 v2
 hipError_t launch_gemm_bf16_small(const GemmParams& p, int epi, hipStream_t stream);  // 128x128 tiles
@@ -246,10 +253,12 @@ extern int g_attn_kernel;  // 0: by support (see launch_attention), 3: attention
 //   mode 1: a = sc[d],     b = sh[d]      (affine LayerNorm: weight / bias)
 // If x0 != null the row is x0[m,:] (bf16) + x[m,:] (fp32): the fused MagCache skip path.
 // sel != null: rows with sel[m] != 0 take (sc2, sh2) instead of (sc, sh) -- per-token modulation (Wan2.2 TI2V)
+// set_stride != 0 (with sel and n_sets in 1..64): row m takes sc + k * set_stride and sh + k * set_stride, k = min(sel[m],
+// n_sets - 1) -- a table of modulation sets; sc2 / sh2 are ignored.  The same for the quantising forms below.
 hipError_t launch_ln_modulate(const float* x, long ldx, const bf16_t* x0, long ldx0, const float* sc,
                               const float* sh, int mode, float eps, bf16_t* out, long ldo, float* out_f32,
                               long ldof, int M, int D, hipStream_t stream, const float* sc2 = nullptr,
-                              const float* sh2 = nullptr, const uint8_t* sel = nullptr);
+                              const float* sh2 = nullptr, const uint8_t* sel = nullptr, long set_stride = 0, int n_sets = 0);
 // The same row, quantised for an fp8 GEMM instead of stored as bf16: e4m3 bytes q[m, :] relative to one scale per row
 // (row_scale != null; launch_quantize_rows_fp8's arithmetic) or to one E8M0 scale per 32 elements (mx != null;
 // launch_quantize_rows_mxfp8's arithmetic and scale layout) -- bit-identical to quantising the bf16 row launch_ln_modulate
@@ -257,16 +266,24 @@ hipError_t launch_ln_modulate(const float* x, long ldx, const bf16_t* x0, long l
 hipError_t launch_ln_modulate_fp8(const float* x, long ldx, const float* sc, const float* sh, int mode, float eps,
                                   uint8_t* q, long ldq, float* row_scale, uint8_t* mx, long mx_rows, int M, int D,
                                   hipStream_t stream, const float* sc2 = nullptr, const float* sh2 = nullptr,
-                                  const uint8_t* sel = nullptr);
+                                  const uint8_t* sel = nullptr, long set_stride = 0, int n_sets = 0);
 // The same row as MXFP4: packed e2m1 codes q[m, d / 2] (ldq in bytes, % 16 == 0, >= D / 2) and one E8M0 scale per 32 elements in
 // mx (mx_rows % 64 == 0, >= ceil64(M)) -- bit-identical to launch_quantize_rows_mxfp4 of the bf16 row launch_ln_modulate writes.
 hipError_t launch_ln_modulate_mxfp4(const float* x, long ldx, const float* sc, const float* sh, int mode, float eps, uint8_t* q,
                                     long ldq, uint8_t* mx, long mx_rows, int M, int D, hipStream_t stream,
-                                    const float* sc2 = nullptr, const float* sh2 = nullptr, const uint8_t* sel = nullptr);
+                                    const float* sc2 = nullptr, const float* sh2 = nullptr, const uint8_t* sel = nullptr,
+                                    long set_stride = 0, int n_sets = 0);
 // Wan2.2 TI2V per-token timesteps (at most two distinct values per forward): t2[0] = max, t2[1] = min of t[0, n_all);
 // sel[i] = 1 where t[row0 + i] == min and min != max (rows >= n_rows: 0); t2[2] = number of tokens that are neither
 hipError_t launch_token_t_prepare(const float* t, int n_all, int row0, int n_rows, int n_rows_pad, float* t2, uint8_t* sel,
                                   hipStream_t stream);
+// Up to cap (1..kMaxTokenSets) distinct per-token timesteps: vals[0, cap) = the distinct values of t[0, n_all) in DESCENDING
+// order (set 0 = the maximum, as above), padded with the last one found; sel[i] = the index of t[row0 + i] in vals (rows >=
+// n_rows: 0); a token whose value has no set -- more than cap values, or NaN -- selects cap - 1.  t2[0] = max, t2[1] = min over
+// all tokens, t2[2] = number of tokens without a set, t2[3] = sets in use.  -0.0 and 0.0 are one value.  One launch, one block.
+constexpr int kMaxTokenSets = 64;
+hipError_t launch_token_t_sets(const float* t, int n_all, int row0, int n_rows, int n_rows_pad, int cap, float* t2, float* vals,
+                               uint8_t* sel, hipStream_t stream);
 
 // in-place RMSNorm over D (all heads) + optional 3-D RoPE on bf16 rows.
 //   y = bf16(x * rsqrt(mean(x^2)+eps)) * w ; rope pairs (2i,2i+1) with cs[token][64] (cos,sin)
@@ -310,6 +327,17 @@ hipError_t launch_gemv_f32(const float* W, const float* x, const float* b, float
 hipError_t launch_sinusoid(const float* t_dev, double t_host, int dim, float* out, hipStream_t stream);
 // out[i] = a[i % na] + b[i]   (modulation + e0 broadcast)
 hipError_t launch_add_bcast(const float* a, int na, const float* b, float* out, int n, hipStream_t stream);
+// The same three over R (1..kMaxTokenSets) rows at once, ONE launch each whatever R is; every output row holds the bits the
+// single-row launcher gives for that row alone (the same expressions in the same order).
+//   sinusoid: out + r * ldo <- the embedding of t_dev[r]
+//   gemv:     y + r * ldy <- W (x + r * ldx) + b; a wave owns a weight row, reads it from memory once and keeps it in registers
+//             for all R right-hand sides (K <= 8192)
+//   add:      out[r * ld_set + j * n + i] = a[r * lda + i % na] + b[j][i] for j < n_b, i < n -- b: HOST array of n_b device pointers
+hipError_t launch_sinusoid_rows(const float* t_dev, int R, int dim, float* out, long ldo, hipStream_t stream);
+hipError_t launch_gemv_f32_rows(const float* W, const float* x, long ldx, const float* b, float* y, long ldy, int R, int N, int K,
+                                int act_in, int act_out, hipStream_t stream);
+hipError_t launch_add_bcast_rows(const float* a, long lda, int R, int na, const float* const* b, int n_b, int n, float* out,
+                                 long ld_set, hipStream_t stream);
 // fp32 -> bf16 cast with zero padding of rows >= rows_valid
 hipError_t launch_cast_pad_bf16(const float* src, long lds, int rows_valid, int rows, int cols, bf16_t* dst,
                                 long ldd, hipStream_t stream);

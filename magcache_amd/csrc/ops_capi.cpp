@@ -18,7 +18,7 @@ static mc::GemmParams gp(const bf16_t* A, long lda, const bf16_t* W, long ldw, c
 extern "C" {
 
 const char* mc_last_error(void) { return mc::last_error(); }
-const char* mc_version(void) { return "magcache_hip 0.7.1 (gfx950)"; }
+const char* mc_version(void) { return "magcache_hip 0.8 (gfx950; 0.7.1 + token_timestep_sets)"; }
 
 // split-K scratch of the single-op entry point (mc_op_set_splitk_workspace): the engines carry their own in their workspace
 static float* g_op_splitk_ws = nullptr;
@@ -47,6 +47,21 @@ mc_status mc_op_gemm_bf16_resid_sel(const void* A, long lda, const void* W, long
   if (!gate || !gate2 || !gate_sel) return fail(MC_EINVAL, "gemm (per-token gates): gate, gate2 and gate_sel are required");
   hipError_t err = mc::launch_gemm_bf16(p, capture ? mc::EPI_RESID_CAPTURE : mc::EPI_RESID_GATE, (hipStream_t)s);
   if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "gemm (per-token gates): unsupported shape M=%d N=%d K=%d", M, N, K);
+  HIP_TRY(err);
+  return MC_OK;
+}
+
+mc_status mc_op_gemm_bf16_resid_sets(const void* A, long lda, const void* W, long ldw, const float* bias, int M, int N, int K,
+                                     int capture, float* X, long ldx, const float* gates, long gate_stride, int n_sets,
+                                     const unsigned char* sel, const void* X0, long ldx0, float* R, long ldr, mc_stream s) {
+  mc::GemmParams p = gp((const bf16_t*)A, lda, (const bf16_t*)W, ldw, bias, M, N, K);
+  p.X = X; p.ldx = ldx; p.gate = gates; p.gate_sel = sel; p.gate_stride = gate_stride; p.gate_sets = n_sets;
+  p.X0 = (const bf16_t*)X0; p.ldx0 = ldx0; p.R = R; p.ldr = ldr;
+  if (!mc::gemm_gate_table_ok(p))
+    return fail(MC_EINVAL, "gemm (gate table): a table, a selector, n_sets 1..64 (%d) and gate_stride >= N, %% 4 == 0 (%ld) are required",
+                n_sets, gate_stride);
+  hipError_t err = mc::launch_gemm_bf16(p, capture ? mc::EPI_RESID_CAPTURE : mc::EPI_RESID_GATE, (hipStream_t)s);
+  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "gemm (gate table): unsupported shape M=%d N=%d K=%d", M, N, K);
   HIP_TRY(err);
   return MC_OK;
 }

@@ -135,6 +135,63 @@ int mc_test_token_t_prepare(const float* t, int n_all, int row0, int n_rows, int
   return (int)mc::launch_token_t_prepare(t, n_all, row0, n_rows, n_rows_pad, t2, sel, (hipStream_t)s);
 }
 
+// ---- the table forms of an engine with token_timestep_sets (tests/test_token_sets_ops_gpu.py)
+int mc_test_token_t_sets(const float* t, int n_all, int row0, int n_rows, int n_rows_pad, int cap, float* t2, float* vals,
+                         unsigned char* sel, void* s) {
+  return (int)mc::launch_token_t_sets(t, n_all, row0, n_rows, n_rows_pad, cap, t2, vals, sel, (hipStream_t)s);
+}
+
+int mc_test_sinusoid_rows(const float* t_dev, int R, int dim, float* out, long ldo, void* s) {
+  return (int)mc::launch_sinusoid_rows(t_dev, R, dim, out, ldo, (hipStream_t)s);
+}
+
+int mc_test_gemv_f32_rows(const float* W, const float* x, long ldx, const float* b, float* y, long ldy, int R, int N, int K,
+                          int act_in, int act_out, void* s) {
+  return (int)mc::launch_gemv_f32_rows(W, x, ldx, b, y, ldy, R, N, K, act_in, act_out, (hipStream_t)s);
+}
+
+// b: a HOST array of n_b device pointers
+int mc_test_add_bcast_rows(const float* a, long lda, int R, int na, const float* const* b, int n_b, int n, float* out,
+                           long ld_set, void* s) {
+  return (int)mc::launch_add_bcast_rows(a, lda, R, na, b, n_b, n, out, ld_set, (hipStream_t)s);
+}
+
+int mc_test_ln_modulate_sets(const float* x, long ldx, const void* x0, long ldx0, const float* sc, const float* sh, int mode,
+                             float eps, void* out, long ldo, float* out_f32, long ldof, int M, int D,
+                             const unsigned char* sel, long set_stride, int n_sets, void* s) {
+  return (int)mc::launch_ln_modulate(x, ldx, (const bf16_t*)x0, ldx0, sc, sh, mode, eps, (bf16_t*)out, ldo, out_f32, ldof, M, D,
+                                     (hipStream_t)s, nullptr, nullptr, sel, set_stride, n_sets);
+}
+
+int mc_test_ln_modulate_fp8_sets(const float* x, long ldx, const float* sc, const float* sh, int mode, float eps,
+                                 unsigned char* q, long ldq, float* row_scale, unsigned char* mx, long mx_rows, int M, int D,
+                                 const unsigned char* sel, long set_stride, int n_sets, void* s) {
+  return (int)mc::launch_ln_modulate_fp8(x, ldx, sc, sh, mode, eps, q, ldq, row_scale, mx, mx_rows, M, D, (hipStream_t)s,
+                                         nullptr, nullptr, sel, set_stride, n_sets);
+}
+
+int mc_test_ln_modulate_mxfp4_sets(const float* x, long ldx, const float* sc, const float* sh, int mode, float eps,
+                                   unsigned char* q, long ldq, unsigned char* mx, long mx_rows, int M, int D,
+                                   const unsigned char* sel, long set_stride, int n_sets, void* s) {
+  return (int)mc::launch_ln_modulate_mxfp4(x, ldx, sc, sh, mode, eps, q, ldq, mx, mx_rows, M, D, (hipStream_t)s, nullptr, nullptr,
+                                           sel, set_stride, n_sets);
+}
+
+// the gated residual of launch_gemm_mxfp8 with per-row gates: mc_op_gemm_mxfp8 names neither gate2 / gate_sel nor a table.
+// gate_stride == 0: the two-set form (gate, gate2, sel); != 0: the table form (gate = table, n_sets rows)
+int mc_test_gemm_mxfp8_resid_rows(const void* A, long lda, const void* a_mx, long mx_rows_a, const void* W, long ldw,
+                                  const void* w_mx, long mx_rows_w, const float* bias, int M, int N, int K, float* X, long ldx,
+                                  const float* gate, const float* gate2, const unsigned char* sel, long gate_stride, int n_sets,
+                                  void* s) {
+  mc::GemmParams p = {};
+  p.A = (const bf16_t*)A; p.lda = lda; p.W = (const bf16_t*)W; p.ldw = ldw; p.bias = bias;
+  p.M = M; p.N = N; p.K = K;
+  p.a_mx = (const uint8_t*)a_mx; p.mx_rows_a = mx_rows_a; p.w_mx = (const uint8_t*)w_mx; p.mx_rows_w = mx_rows_w;
+  p.X = X; p.ldx = ldx; p.gate = gate; p.gate2 = gate2; p.gate_sel = sel; p.gate_stride = gate_stride; p.gate_sets = n_sets;
+  if (gate_stride != 0 && !mc::gemm_gate_table_ok(p)) return (int)hipErrorInvalidValue;
+  return (int)mc::launch_gemm_mxfp8(p, mc::EPI_RESID_GATE, (hipStream_t)s);
+}
+
 int mc_test_patchify(const float* lat, int C, int F, int H, int W, int tok0, int n_tok, int n_rows, void* out, long ldo,
                      void* s) {
   return (int)mc::launch_patchify(lat, C, F, H, W, tok0, n_tok, n_rows, (bf16_t*)out, ldo, (hipStream_t)s);

@@ -126,7 +126,8 @@ class Engine(EngineHost):
                      vace_in_dim=cfg.get("vace_in_dim", 0) if vace_geometry(cfg)[0] else 0,
                      fp8_linear=int(cfg.get("fp8_linear", 0) or 0),
                      no_context_cache=int(bool(cfg.get("no_context_cache", 0))),
-                     no_token_timesteps=int(bool(cfg.get("no_token_timesteps", 0))), sp_phases=int(bool(sp_phases)))
+                     no_token_timesteps=int(bool(cfg.get("no_token_timesteps", 0))), sp_phases=int(bool(sp_phases)),
+                     token_timestep_sets=int(cfg.get("token_timestep_sets", 0) or 0))
         self.context_cache = not cfg.get("no_context_cache", 0)
         self.sp_rank, self.sp_size, self.n_branches = sp_rank, sp_size, n_branches
         self.sharded = sp_size > 1 or bool(sp_phases)     # driven through the phase calls (parallel.SequenceParallelForward)
@@ -138,6 +139,8 @@ class Engine(EngineHost):
             return h
         self._create_latching(create, {"mx_fp4": mx_fp4 or cfg.get("mx_fp4"), "mx_fp6": mx_fp6 or cfg.get("mx_fp6")}, "mc_engine_")
         self._bind(self.lib.mc_workspace_bytes(self.h))
+        # distinct per-token timesteps a forward may carry: cfg["token_timestep_sets"] (3..64), 2 by default, 0 without them
+        self.token_timestep_capacity = int(self.lib.mc_engine_token_timestep_sets(self.h))
         self.tokens_per_rank = self.seq_len // sp_size
         self.head_stride = (4 * cfg["out_dim"] + 63) // 64 * 64    # row stride of "head_tokens" (fp32 elements)
         self._lora_init()
@@ -195,8 +198,9 @@ class Engine(EngineHost):
         torch.cuda.current_stream().synchronize()
 
     def set_token_timesteps(self, t_tokens):
-        """Wan2.2 TI2V: per-token timesteps for the following forwards (fp32 [seq_len], at most two distinct values
-        -- the conditioning frame's tokens carry t = 0), or None for the scalar t of forward()."""
+        """Per-token timesteps for the following forwards (fp32 [seq_len], at most token_timestep_capacity distinct
+        values: two by default -- Wan2.2 TI2V, the conditioning frame's tokens carry t = 0 --, cfg["token_timestep_sets"]
+        otherwise), or None for the scalar t of forward()."""
         if t_tokens is None:
             if self._tok_t is not None:
                 check(self.lib.mc_set_token_timesteps(self.h, C.c_void_p(0), _stream()))
@@ -211,6 +215,14 @@ class Engine(EngineHost):
         """(max t, min t, number of tokens carrying neither) found by the last per-token forward (device sync)"""
         r = self.buffer("tok_t2", torch.float32)[:3].cpu()
         return float(r[0]), float(r[1]), int(r[2])
+
+    def token_timestep_values(self):
+        """The distinct per-token timesteps the last per-token forward of a capacity engine (cfg["token_timestep_sets"])
+        found, in descending order -- set k of the modulation tables belongs to value k (device sync)"""
+        if int(self.cfg.get("token_timestep_sets", 0) or 0) == 0:
+            raise ValueError("token_timestep_values: the engine was created without token_timestep_sets")
+        n = int(self.buffer("tok_t2", torch.float32)[3].item())
+        return self.buffer("tok_vals", torch.float32)[:n].cpu().tolist()
 
     def profile(self, on=True):
         """hipEvent pairs on the launch stream (mc_profile_enable): True / 1 = every self-attention launch, 2 = every launch

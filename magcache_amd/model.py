@@ -115,7 +115,12 @@ class WanModelHIP(LoraModel):
     dynamic_geometry = False
 
     def __init__(self, cfg, latent_grid, device="cuda:0", calibration=True, engine=None, sp_rank=0, sp_size=1,
-                 sp_group=None, sp_phases=False, dynamic_geometry=False):
+                 sp_group=None, sp_phases=False, dynamic_geometry=False, token_timestep_sets=0):
+        """token_timestep_sets (3..64): the engine's capacity of distinct per-token timesteps per forward -- one timestep per
+        latent frame (wan22.frame_timesteps / sample_frames), several conditioning frames at their own noise levels.  0: two,
+        what Wan2.2 TI2V's `mask * t` needs."""
+        if token_timestep_sets:
+            cfg = dict(cfg, token_timestep_sets=int(token_timestep_sets))
         self.cfg = dict(cfg)
         self.dynamic_geometry = dynamic_geometry
         for k in ("dim", "ffn_dim", "freq_dim", "text_len", "text_dim", "in_dim", "out_dim", "num_heads",
@@ -235,12 +240,21 @@ class WanModelHIP(LoraModel):
             assert tv.numel() >= self.engine.seq_len, f"t has {tv.numel()} entries, the sequence {self.engine.seq_len}"
             tv = tv[:self.engine.seq_len]
             k = getattr(self, "_tok_t_key", None)
-            trusted = getattr(t, "_mc_two_valued", False) or os.environ.get("MAGCACHE_VALIDATE_TOKEN_T") == "0"
+            # An engine created with token_timestep_sets = C takes up to C distinct values (capacity); a builder vouches
+            # for such a tensor with `t._mc_distinct_at_most = n` (wan22.frame_timesteps: one value per latent frame),
+            # trusted when n <= C.
+            cap = int(getattr(self.engine, "token_timestep_capacity", 2) or 2)
+            vouched = getattr(t, "_mc_distinct_at_most", None)
+            trusted = getattr(t, "_mc_two_valued", False) or (vouched is not None and vouched <= cap) or \
+                os.environ.get("MAGCACHE_VALIDATE_TOKEN_T") == "0"
             if not trusted and (k is None or not _same_tensor(k, t)):
                 n = int(torch.unique(tv).numel())
-                if n > 2:
+                if n > 2 and cap <= 2:
                     raise ValueError(f"per-token timesteps with {n} distinct values: the engine supports at most two "
                                      "per forward (Wan2.2 TI2V: conditioning frame + the step's t)")
+                if n > cap:
+                    raise ValueError(f"per-token timesteps with {n} distinct values: the engine was created with "
+                                     f"token_timestep_sets = {cap} and supports at most that many per forward")
                 self._tok_t_key = _tensor_key(t)
             self.check_token_timesteps(block=False)       # the record of an EARLIER trusted forward, if it has arrived
             self.engine.set_token_timesteps(tv)
@@ -270,7 +284,7 @@ class WanModelHIP(LoraModel):
             # record of forward i with forward i + 1's before it was ever looked at, so only a run's LAST forward was
             # verified): every trusted forward gets its own slot; a slot is examined before it is reused
             if getattr(self, "_tok_ring", None) is None:
-                self._tok_ring = [[torch.zeros(3, dtype=torch.float32).pin_memory(), torch.cuda.Event(), False]
+                self._tok_ring = [[torch.zeros(3, dtype=torch.float32).pin_memory(), torch.cuda.Event(), False, 0]
                                   for _ in range(16)]
                 self._tok_next = 0
             slot = self._tok_ring[self._tok_next]
@@ -280,6 +294,9 @@ class WanModelHIP(LoraModel):
             slot[0].copy_(self.engine.buffer("tok_t2", torch.float32)[:3], non_blocking=True)
             slot[1].record()
             slot[2] = True
+            if len(slot) > 3:      # a capacity engine's record counts the tokens that received no modulation set
+                cap = int(getattr(self.engine, "token_timestep_capacity", 2) or 2)
+                slot[3] = cap if cap > 2 else 0
             self._tok_next = (self._tok_next + 1) % len(self._tok_ring)
         return [out.float()]
 
@@ -313,6 +330,11 @@ class WanModelHIP(LoraModel):
     def _tok_examine(slot):
         slot[2] = False
         tmax, tmin, neither = (float(v) for v in slot[0])
+        cap = slot[3] if len(slot) > 3 else 0
+        if neither > 0 and cap:
+            raise ValueError(f"per-token timesteps: {int(neither)} tokens received no modulation set in a forward whose "
+                             f"tensor was tagged as carrying at most {cap} distinct values (max t = {tmax:g}, min t = "
+                             f"{tmin:g}; the engine was created with token_timestep_sets = {cap})")
         if neither > 0:
             raise ValueError(f"per-token timesteps: {int(neither)} tokens carried neither t = {tmax:g} nor t = {tmin:g} in a "
                              "forward whose tensor was tagged two-valued (the engine supports at most two distinct values)")

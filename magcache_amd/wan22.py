@@ -245,3 +245,56 @@ def sample_ti2v(model, noise, context, context_null, sampling_steps=50, shift=5.
     if hasattr(model, "check_token_timesteps"):
         model.check_token_timesteps()            # the vouched-for `mask * t` really was two-valued in every forward
     return latent
+
+
+def frame_timesteps(t_frames, grid):
+    """One timestep per LATENT FRAME -> the per-token tensor the Wan2.2 forward takes: t_frames [F] expanded to
+    [1, F * (H / 2) * (W / 2)] in the engine's token order (frame-major: a frame's (H / 2) * (W / 2) patches are
+    consecutive), tagged `_mc_distinct_at_most = F` so that a shim whose engine has that capacity
+    (WanModelHIP(..., token_timestep_sets >= F)) skips the value check, as sample_ti2v's `mask * t` does."""
+    F_, H_, W_ = (int(v) for v in grid)
+    tf = torch.as_tensor(t_frames, dtype=torch.float32).reshape(-1)
+    if tf.numel() != F_:
+        raise ValueError(f"frame_timesteps: {tf.numel()} timesteps for {F_} latent frames")
+    tt = tf.reshape(F_, 1).expand(F_, (H_ // 2) * (W_ // 2)).reshape(1, -1).contiguous()
+    tt._mc_distinct_at_most = F_
+    return tt
+
+
+def sample_frames(model, noise, context, context_null, step_matrix, sigmas, guide_scale, z_cond=None):
+    """Euler flow sampler with ONE TIMESTEP PER LATENT FRAME (the diffusion-forcing / autoregressive fine-tunes of the Wan
+    backbone): row i of step_matrix [iterations, F] is each frame's index into `sigmas` at iteration i, its timestep is
+    1000 * sigmas[index].  Iteration i moves frame f from step_matrix[i][f] to step_matrix[i + 1][f] (after the last row:
+    one index further, at most the last sigma): latent[:, f] += (sigma[next] - sigma[cur]) * v[:, f].  A frame whose
+    index does not move keeps its bits.  z_cond [C, Fc, H, W]: the first Fc frames are given; they are re-imposed before
+    every call and at the end (their indices should not move).  Cond, then uncond, once per iteration through
+    call_branch, so a MagCache forward installed by init_magcache applies; the engine needs token_timestep_sets >= the
+    number of distinct indices in a row (at most F).  No device code of its own."""
+    steps = torch.as_tensor(step_matrix, dtype=torch.long).reshape(-1, noise.shape[1]).cpu()
+    sig = torch.as_tensor(sigmas, dtype=torch.float64).reshape(-1).cpu()
+    if int(steps.min()) < 0 or int(steps.max()) >= sig.numel():
+        raise ValueError("sample_frames: a step index lies outside sigmas")
+    device = noise.device
+    latent = noise.clone().float().contiguous()
+    grid = tuple(latent.shape[1:])
+    seq_len = model.engine.seq_len
+    fc = 0 if z_cond is None else int(z_cond.shape[1])
+    if fc:
+        z = z_cond.to(device).float()
+        latent[:, :fc] = z
+    for i in range(steps.shape[0]):
+        cur = steps[i]
+        nxt = steps[i + 1] if i + 1 < steps.shape[0] else torch.clamp(cur + 1, max=sig.numel() - 1)
+        tt = frame_timesteps((sig[cur] * 1000.0).float(), grid).to(device)
+        tt._mc_distinct_at_most = grid[0]                       # (.to() returns a new tensor object: tag that one)
+        eps_c = call_branch(model, i, 0, [latent], tt, [context], seq_len)[0]
+        eps_u = call_branch(model, i, 1, [latent], tt, [context_null], seq_len)[0]
+        v = eps_u.float() + guide_scale * (eps_c.float() - eps_u.float())
+        dt = (sig[nxt] - sig[cur]).float().to(device).reshape(1, -1, 1, 1)
+        moved = (nxt != cur).to(device).reshape(1, -1, 1, 1)
+        latent = torch.where(moved, latent + dt * v, latent)
+        if fc:
+            latent[:, :fc] = z
+    if hasattr(model, "check_token_timesteps"):
+        model.check_token_timesteps()            # every vouched-for per-frame tensor fitted the engine's capacity
+    return latent
