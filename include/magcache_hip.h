@@ -160,7 +160,8 @@ mc_status mc_create(const mc_config* cfg, mc_engine** out);
  * vace_in_dim, 0.2 adds fp8_linear, 0.3 no_context_cache and no_token_timesteps, 0.5 sp_phases (0.6 adds calls only: mc_pair_begin / mc_pair_end; 0.7 adds calls only: mc_geometry_bytes / mc_set_geometry,
  * mc_op_rope_axes / mc_op_rope_expand; 0.7.1 adds calls only: mc_lora_*, mc_op_lora_merge_f32, mc_op_param_delta; the MXFP4 and MXFP6 modes add calls only: mc_get_option,
  * mc_engine_mx_fp4 / _mx_fp6, mc_op_quantize_rows_mxfp4 / _mxfp6, mc_op_gemm_mxfp4 / _mxfp6); 0.8 adds token_timestep_sets (and the calls
- * mc_engine_token_timestep_sets, mc_op_gemm_bf16_resid_sets); mc_version() names the library's. */
+ * mc_engine_token_timestep_sets, mc_op_gemm_bf16_resid_sets); the adapter kinds add calls only: mc_lora_set_kron / _set_hada /
+ * _set_magnitude, mc_op_adapter_merge / _scratch; mc_version() names the library's. */
 mc_status mc_create_sized(const mc_config* cfg, size_t cfg_bytes, mc_engine** out);
 void mc_destroy(mc_engine* e);
 /* 1: this engine's quantised Linears are MXFP4 (it was created under mc_set_option("mx_fp4", 1) with fp8_linear 2 | 3); else 0 */
@@ -243,6 +244,33 @@ mc_status mc_lora_set(mc_engine* e, const char* adapter, const char* weight_name
                       const void* up_dev, const int64_t* up_shape, mc_dtype dtype, float factor, mc_stream stream);
 mc_status mc_lora_set_delta(mc_engine* e, const char* adapter, const char* param_name, const void* delta_dev, size_t numel,
                             mc_dtype dtype, mc_stream stream);
+/* The other kinds of term (LyCORIS LoKr and LoHa) and the DoRA magnitude, on the bf16 matrices mc_lora_set takes (a part of a
+ * fused matrix by its own name).  An fp32 matrix (time_embedding.0/.2, time_projection.1, head.head), a padded embedder or a
+ * shape that does not factor is MC_EINVAL naming the weight.  Operands fp32 or bf16 (`dtype`), copied and widened to fp32.
+ *   mc_lora_set_kron       m * kron(w1 [r1, c1], w2 [r2, c2]), r1 r2 = rows of the weight, c1 c2 = in_features:
+ *                          element (r, c) = w1[r / r2, c / c2] * w2[r % r2, c % c2]
+ *   mc_lora_set_hada       m * (u1 d1) (.) (u2 d2), element-wise; u1, u2 [rows, rank] (u_shape), d1, d2 [rank, in_features]
+ *                          (d_shape)
+ *   mc_lora_set_magnitude  the DoRA magnitude g [rows] (`numel` = rows) of `adapter` on the weight: with it the weight is
+ *                          bf16(g[r] / |V[r, :]| * V[r, :]), V = W + every live term -- PEFT's merged DoRA weight
+ *                          magnitude / |W + s B A|_row * (W + s B A).  It is live while its adapter's scale is not 0; with the
+ *                          scale at 0 the adapter's terms and its magnitude are both left out.  The norm is recomputed by every
+ *                          apply, so a DoRA adapter at scale 0.5 is NOT half way between W and the scale-1 weight.  Where other
+ *                          adapters are live on the same weight their deltas sit inside the normalised direction (PEFT has no
+ *                          merged form for that case).  One magnitude per weight: a second adapter's is MC_EINVAL naming both.
+ *                          A row of V that is all zero stays zero.
+ * The same (adapter, weight_name) and kind replaces; pairs, Kronecker and Hadamard terms together are at most
+ * MC_LORA_MAX_TERMS per weight.  A weight that carries one of these is rebuilt by the arithmetic of mc_op_adapter_merge, with an
+ * fp32 scratch of rows x in_features x 4 bytes that mc_lora_apply allocates and frees; a weight whose live terms are all
+ * low-rank pairs, with no magnitude, keeps mc_op_lora_merge bit for bit.  mc_lora_scale / _remove / _apply / _info, the
+ * MC_ESTATE rules and the invalidation after an apply treat these entries as they treat pairs. */
+mc_status mc_lora_set_kron(mc_engine* e, const char* adapter, const char* weight_name, const void* w1_dev, const int64_t* w1_shape,
+                           const void* w2_dev, const int64_t* w2_shape, mc_dtype dtype, float factor, mc_stream stream);
+mc_status mc_lora_set_hada(mc_engine* e, const char* adapter, const char* weight_name, const void* u1_dev, const int64_t* u_shape,
+                           const void* d1_dev, const int64_t* d_shape, const void* u2_dev, const void* d2_dev, mc_dtype dtype,
+                           float factor, mc_stream stream);
+mc_status mc_lora_set_magnitude(mc_engine* e, const char* adapter, const char* weight_name, const void* magnitude_dev, size_t numel,
+                                mc_dtype dtype, mc_stream stream);
 mc_status mc_lora_scale(mc_engine* e, const char* adapter, float scale);
 mc_status mc_lora_remove(mc_engine* e, const char* adapter);
 mc_status mc_lora_apply(mc_engine* e, mc_stream stream);
@@ -706,6 +734,34 @@ mc_status mc_op_lora_merge(const void* base_dev, long ld_base, void* out_dev, lo
  * multiples of 4 here; every other rule and refusal is mc_op_lora_merge's. */
 mc_status mc_op_lora_merge_f32(const float* base_dev, long ld_base, float* out_dev, long ld_out, int rows, int K,
                                const mc_lora_term* terms, int n_terms, void* scratch_dev, size_t scratch_bytes, mc_stream stream);
+/* The merge of every kind of term (what mc_lora_apply / mc_mmdit_lora_apply rebuild a bf16 weight with that carries a Kronecker
+ * or Hadamard term or a DoRA magnitude), on the caller's buffers.  base / out bf16 as in mc_op_lora_merge.  fp32 throughout:
+ *   delta  = sum of the PAIR terms as mc_op_lora_merge_f32 forms it on a zero base (bf16 operands, fp32 MFMA accumulation)
+ *   delta += scale * (w1[r / r2, c / c2] * w2[r % r2, c % c2])      KRON: one multiply for the product, one for the scale, one add
+ *   delta += scale * ((u1 d1)[r, c] * (u2 d2)[r, c])                 HADA: two rank-long fp32 dot products in k order
+ *   V      = fp32(base) + delta                                      ONE add of the base element, last
+ *   out    = bf16(V)                                                 magnitude == NULL
+ *   out    = bf16(g[r] / sqrt(sum_k V[r, k]^2) * V[r, k])            magnitude g [rows], fp32 on the device
+ * Kinds are summed in this order, the terms of a kind in array order; nothing is contracted into an fma; the row's sum of
+ * squares is formed in a fixed order (no atomics), so two calls give the same bits.  out may alias base; nothing outside
+ * [rows, K] of out is written.  `scratch_dev`: 256-byte aligned, at least mc_op_adapter_merge_scratch bytes (rows x K x 4 for V,
+ * plus the packed copies of the pairs), or NULL for an allocation of the call's own, which makes it synchronous.  Not a
+ * forward-path call.  MC_EINVAL, and nothing launched, for an unknown kind, r1 * r2 != rows or c1 * c2 != K, a rank < 1, more
+ * than MC_LORA_MAX_TERMS terms, the alignment and pitch rules of mc_op_lora_merge, or a scratch that is too small. */
+#define MC_ADAPTER_PAIR 0
+#define MC_ADAPTER_KRON 1
+#define MC_ADAPTER_HADA 2
+typedef struct mc_adapter_term {
+  int kind;    /* MC_ADAPTER_PAIR | MC_ADAPTER_KRON | MC_ADAPTER_HADA */
+  float scale;
+  const void *a, *b, *c, *d; /* PAIR: a = down [rank, K], b = up [rows, rank] (bf16, as mc_lora_term); KRON: a = w1 [r1, c1],
+                                b = w2 [r2, c2] (fp32); HADA: a = u1 [rows, rank], b = d1 [rank, K], c = u2, d = d2 (fp32) */
+  int rank, r1, c1, r2, c2;
+} mc_adapter_term;
+size_t mc_op_adapter_merge_scratch(int rows, int K, const mc_adapter_term* terms, int n_terms);
+mc_status mc_op_adapter_merge(const void* base_dev, long ld_base, void* out_dev, long ld_out, int rows, int K,
+                              const mc_adapter_term* terms, int n_terms, const float* magnitude_dev, void* scratch_dev,
+                              size_t scratch_bytes, mc_stream stream);
 /* The additive rule of a parameter that is no matrix product (0.7.1): out[i] = base[i] + sum_j scales[j] * deltas[j][i], all
  * fp32, i < n, any n > 0, 1 to MC_LORA_MAX_TERMS terms (`deltas`: a HOST array of device pointers, `scales`: a host array).
  * The sum is formed from zero in term order, a multiply and an add per term, never contracted; the base element is added last.

@@ -178,6 +178,20 @@ mc_status mc_mmdit_set_rope(mc_mmdit* e, const float* cos_dev, const float* sin_
 mc_status mc_mmdit_lora_set(mc_mmdit* e, const char* adapter, const char* weight_name, const void* down_dev,
                             const int64_t* down_shape, const void* up_dev, const int64_t* up_shape, mc_dtype dtype, float factor,
                             mc_stream stream);   /* both shapes are 2-D; rank = down_shape[0] */
+/* LoKr and LoHa terms and DoRA magnitudes: the contracts of mc_lora_set_kron / _set_hada / _set_magnitude (magcache_hip.h), on
+ * the same weight store.  Targets are the bf16 matrices mc_mmdit_lora_set takes; the fp32 head, a padded image embedder or a
+ * shape that does not factor is MC_EINVAL naming the weight.  A weight that carries one of these is rebuilt by the arithmetic
+ * of mc_op_adapter_merge (fp32 scratch of the part's size, allocated and freed by the apply), then its MX / fp8 rows are
+ * requantised as after any merge; a weight with low-rank pairs only keeps the merge above bit for bit.  A magnitude is live
+ * while its adapter's scale is not 0; a second adapter's magnitude on one weight is MC_EINVAL naming both adapters. */
+mc_status mc_mmdit_lora_set_kron(mc_mmdit* e, const char* adapter, const char* weight_name, const void* w1_dev,
+                                 const int64_t* w1_shape, const void* w2_dev, const int64_t* w2_shape, mc_dtype dtype, float factor,
+                                 mc_stream stream);
+mc_status mc_mmdit_lora_set_hada(mc_mmdit* e, const char* adapter, const char* weight_name, const void* u1_dev,
+                                 const int64_t* u_shape, const void* d1_dev, const int64_t* d_shape, const void* u2_dev,
+                                 const void* d2_dev, mc_dtype dtype, float factor, mc_stream stream);
+mc_status mc_mmdit_lora_set_magnitude(mc_mmdit* e, const char* adapter, const char* weight_name, const void* magnitude_dev,
+                                      size_t numel, mc_dtype dtype, mc_stream stream);
 mc_status mc_mmdit_lora_scale(mc_mmdit* e, const char* adapter, float scale);
 mc_status mc_mmdit_lora_remove(mc_mmdit* e, const char* adapter);
 mc_status mc_mmdit_lora_apply(mc_mmdit* e, mc_stream stream);

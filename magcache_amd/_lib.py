@@ -146,6 +146,12 @@ SIGNATURES = {
     "mc_op_param_delta": (_i, [_vp, _vp, _sz, C.POINTER(_vp), C.POINTER(_f), _i, _vp]),
     "mc_lora_set": (_i, [_vp, C.c_char_p, C.c_char_p, _vp, C.POINTER(C.c_int64), _vp, C.POINTER(C.c_int64), _i, _f, _vp]),
     "mc_lora_set_delta": (_i, [_vp, C.c_char_p, C.c_char_p, _vp, _sz, _i, _vp]),
+    "mc_op_adapter_merge_scratch": (_sz, [_i, _i, _vp, _i]),
+    "mc_op_adapter_merge": (_i, [_vp, _l, _vp, _l, _i, _i, _vp, _i, _vp, _vp, _sz, _vp]),
+    "mc_lora_set_kron": (_i, [_vp, C.c_char_p, C.c_char_p, _vp, C.POINTER(C.c_int64), _vp, C.POINTER(C.c_int64), _i, _f, _vp]),
+    "mc_lora_set_hada": (_i, [_vp, C.c_char_p, C.c_char_p, _vp, C.POINTER(C.c_int64), _vp, C.POINTER(C.c_int64), _vp, _vp, _i, _f,
+                              _vp]),
+    "mc_lora_set_magnitude": (_i, [_vp, C.c_char_p, C.c_char_p, _vp, _sz, _i, _vp]),
     "mc_lora_scale": (_i, [_vp, C.c_char_p, _f]),
     "mc_lora_remove": (_i, [_vp, C.c_char_p]),
     "mc_lora_apply": (_i, [_vp, _vp]),
@@ -164,6 +170,10 @@ SIGNATURES = {
     "mc_mmdit_set_weight": (_i, [_vp, C.c_char_p, _vp, _i, C.POINTER(C.c_int64), _i, _vp]),
     "mc_mmdit_weights_missing": (_i, [_vp, C.c_char_p, _sz]),
     "mc_mmdit_lora_set": (_i, [_vp, C.c_char_p, C.c_char_p, _vp, C.POINTER(C.c_int64), _vp, C.POINTER(C.c_int64), _i, _f, _vp]),
+    "mc_mmdit_lora_set_kron": (_i, [_vp, C.c_char_p, C.c_char_p, _vp, C.POINTER(C.c_int64), _vp, C.POINTER(C.c_int64), _i, _f, _vp]),
+    "mc_mmdit_lora_set_hada": (_i, [_vp, C.c_char_p, C.c_char_p, _vp, C.POINTER(C.c_int64), _vp, C.POINTER(C.c_int64), _vp, _vp, _i,
+                                    _f, _vp]),
+    "mc_mmdit_lora_set_magnitude": (_i, [_vp, C.c_char_p, C.c_char_p, _vp, _sz, _i, _vp]),
     "mc_mmdit_lora_scale": (_i, [_vp, C.c_char_p, _f]),
     "mc_mmdit_lora_remove": (_i, [_vp, C.c_char_p]),
     "mc_mmdit_lora_apply": (_i, [_vp, _vp]),
@@ -202,6 +212,14 @@ MC_LORA_MAX_TERMS = 8
 
 class McLoraTerm(C.Structure):   # mc_lora_term: bf16 down [rank, K] and up [rows, rank] on the device
     _fields_ = [("down", C.c_void_p), ("up", C.c_void_p), ("rank", C.c_int), ("scale", C.c_float)]
+
+
+MC_ADAPTER_PAIR, MC_ADAPTER_KRON, MC_ADAPTER_HADA = 0, 1, 2
+
+
+class McAdapterTerm(C.Structure):   # mc_adapter_term: one term of mc_op_adapter_merge (the header says what a .. d are per kind)
+    _fields_ = [("kind", C.c_int), ("scale", C.c_float), ("a", C.c_void_p), ("b", C.c_void_p), ("c", C.c_void_p), ("d", C.c_void_p),
+                ("rank", C.c_int), ("r1", C.c_int), ("c1", C.c_int), ("r2", C.c_int), ("c2", C.c_int)]
 
 
 MC_IP_MAX_ADAPTERS, MC_IP_MAX_KEYS = 4, 256

@@ -42,14 +42,42 @@ class LoraHost:
         return getattr(self.lib, self._lora_abi + name)
 
     def _lora_entries(self, sd, prefix):
-        """{target: ("pair", down, up, alpha) | ("delta", tensor)} of an adapter state dict"""
-        from .lora import parse_lora_state_dict
-        return {t: ("pair",) + p for t, p in parse_lora_state_dict(sd, prefix=prefix).items()}
+        """{target: ("pair", down, up, alpha) | ("delta", tensor) | ("kron", ...) | ("hada", ...) | ("dora", inner, magnitude)} of
+        an adapter state dict (lora.py says what the last three hold)"""
+        from .lora import parse_adapter_state_dict
+        return {t: e if isinstance(e[0], str) else ("pair",) + tuple(e) for t, e in parse_adapter_state_dict(sd, prefix=prefix).items()}
+
+    def _f32(self, t):
+        """a tensor, or the (a, b) of a factorised half multiplied out, as contiguous fp32 on the device"""
+        if isinstance(t, tuple):
+            a, b = (x.detach().to(device=self.device, dtype=torch.float32) for x in t)
+            return (a @ b).contiguous()
+        return t.detach().to(device=self.device, dtype=torch.float32).contiguous()
 
     def _lora_set(self, adapter, target, entry):
-        """one entry into the store; the status of the C call"""
+        """one entry into the store; the status of the C call.  A "dora" entry is its magnitude (which meets every refusal of
+        the target first), then its term: the status of the first call that fails; self._lora_half says that the magnitude
+        went in and the term did not, which load_lora never leaves behind."""
         from .lora import lora_factor
-        if entry[0] == "delta":
+        self._lora_half = False
+        if entry[0] == "dora":
+            g = self._f32(entry[2])
+            st = self._lora_fn("set_magnitude")(self.h, adapter.encode(), target.encode(), _ptr(g), g.numel(), MC_F32, _stream())
+            torch.cuda.current_stream().synchronize()
+            if st != _lib.MC_OK:
+                return st
+            st = self._lora_set(adapter, target, entry[1])
+            self._lora_half = st != _lib.MC_OK
+            return st
+        elif entry[0] == "kron":
+            w1, w2 = self._f32(entry[1]), self._f32(entry[2])
+            st = self._lora_fn("set_kron")(self.h, adapter.encode(), target.encode(), _ptr(w1), (C.c_int64 * 2)(*w1.shape), _ptr(w2),
+                                           (C.c_int64 * 2)(*w2.shape), MC_F32, float(entry[3]), _stream())
+        elif entry[0] == "hada":
+            u1, d1, u2, d2 = (self._f32(t) for t in entry[1:5])
+            st = self._lora_fn("set_hada")(self.h, adapter.encode(), target.encode(), _ptr(u1), (C.c_int64 * 2)(*u1.shape), _ptr(d1),
+                                           (C.c_int64 * 2)(*d1.shape), _ptr(u2), _ptr(d2), MC_F32, float(entry[5]), _stream())
+        elif entry[0] == "delta":
             t = entry[1].detach().to(device=self.device, dtype=torch.float32).contiguous()
             st = self._lora_fn("set_delta")(self.h, adapter.encode(), target.encode(), _ptr(t), t.numel(), MC_F32, _stream())
         else:
@@ -74,10 +102,11 @@ class LoraHost:
             st = self._lora_set(adapter, target, entry)
             if st == _lib.MC_OK:
                 done += 1
-            elif st == _lib.MC_EINVAL and not strict:
+            elif st == _lib.MC_EINVAL and not strict and not self._lora_half:
                 skipped.append(target)
-            else:
+            else:     # also half a DoRA entry under strict=False: a magnitude without its term is not skipped, it is undone
                 msg = self.lib.mc_last_error().decode()
+                done += self._lora_half
                 if done and not known:
                     self.unload_lora(adapter, _known=True)
                 elif done:

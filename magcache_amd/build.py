@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmagcache_hip.so")
 SOURCES = ["gemm_bf16.hip", "gemm_bf16_v2.hip", "gemm_fp8_big.hip", "gemm_mxfp8.hip", "gemm_mxfp4.hip", "gemm_mxfp6.hip", "attention_v3.hip", "attention_v5.hip", "ip_attention.hip", "elementwise.hip",
-           "magcache_ops.hip", "lora_merge.hip", "host.cpp", "engine.cpp", "mmdit_engine.cpp", "ops_capi.cpp", "rule.cpp", "sp_rccl.cpp"]
+           "magcache_ops.hip", "lora_merge.hip", "adapter_merge.hip", "host.cpp", "engine.cpp", "mmdit_engine.cpp", "ops_capi.cpp", "rule.cpp", "sp_rccl.cpp"]
 # the attention kernel's hand-interleaved VALU stream must stay scalar: the SLP vectoriser packs the row-sum
 # adds into v_pk_add_f32 and moves them out of the MFMA shadow
 EXTRA_FLAGS = {"attention_v3.hip": ["-fno-slp-vectorize"]}

@@ -172,13 +172,10 @@ mc_status WeightStore::lora_set(const char* adapter, const char* weight_name, co
                 down_numel, up_numel, rank, rank, k, (size_t)rank * k, rows, rank, rows * (size_t)rank);
   if ((k % (f32_matrix ? 4 : 8)) != 0)
     return fail(MC_EINVAL, "LoRA '%s': in_features %zu is no multiple of %d", weight_name, k, f32_matrix ? 4 : 8);
-  size_t at = lora.size(), on_target = 0;
-  for (size_t i = 0; i < lora.size(); ++i) {
-    if (lora[i].target != weight_name) continue;
-    if (lora[i].adapter == adapter) at = i;
-    else ++on_target;
-  }
-  if (on_target + 1 > (size_t)kLoraMaxTerms)
+  size_t at = lora.size();
+  for (size_t i = 0; i < lora.size(); ++i)
+    if (lora[i].target == weight_name && lora[i].adapter == adapter) at = i;
+  if (other_terms(adapter, weight_name, -1) + 1 > (size_t)kLoraMaxTerms)
     return fail(MC_EINVAL, "LoRA '%s': more than %d adapters on one weight", weight_name, kLoraMaxTerms);
   const int rank_pad = (int)align_up(rank, kLoraRankStep);
   LoraPair p;
@@ -231,6 +228,127 @@ void WeightStore::drop_base(Slot& s) {   // hipFree waits for the launches that 
   else { release(s.f32_base); s.f32_base = nullptr; }
 }
 
+// ---- Kronecker and Hadamard terms, DoRA magnitudes
+size_t WeightStore::other_terms(const char* adapter, const char* weight_name, int kind) const {
+  size_t n = 0;
+  for (const LoraPair& p : lora)
+    if (p.target == weight_name && !(kind < 0 && p.adapter == adapter)) ++n;
+  for (const AdapterExtra& x : extras)
+    if (x.target == weight_name && x.kind != AdapterExtra::MAGNITUDE && !(kind == (int)x.kind && x.adapter == adapter)) ++n;
+  return n;
+}
+
+mc_status WeightStore::extra_target(const char* what, const char* weight_name, Slot** slot) {
+  auto it = slots.find(weight_name);
+  if (it == slots.end()) return fail(MC_EINVAL, "%s: unknown weight '%s'", what, weight_name);
+  Slot& s = it->second;
+  if (!s.lin || s.dst_dtype != MC_BF16 || s.pad.rows || s.perm_c || s.fixed)
+    return fail(MC_EINVAL, "%s: '%s' is no plain bf16 part of a Linear (an fp32, padded or permuted weight takes low-rank pairs at most)",
+                what, weight_name);
+  if ((s.lin->k_in % 8) != 0) return fail(MC_EINVAL, "%s '%s': in_features %d is no multiple of 8", what, weight_name, s.lin->k_in);
+  *slot = &s;
+  return MC_OK;
+}
+
+void WeightStore::release_extra(AdapterExtra& x) {
+  for (float*& q : x.p) {
+    if (q) release(q);
+    q = nullptr;
+  }
+}
+
+mc_status WeightStore::store_extra(AdapterExtra x, Slot& s, const void* const* src, const size_t* numel, int n_ops, mc_dtype dtype,
+                                   hipStream_t stream) {
+  if (dtype != MC_F32 && dtype != MC_BF16) return fail(MC_EINVAL, "adapter '%s' on '%s': operands are fp32 or bf16", x.adapter.c_str(), x.target.c_str());
+  for (int i = 0; i < n_ops; ++i)
+    if (mc_status st = alloc(&x.p[i], numel[i])) { release_extra(x); return st; }
+  bool new_base = false;
+  if (mc_status st = make_base(s, stream, &new_base)) { release_extra(x); return st; }
+  hipError_t err = hipSuccess;
+  for (int i = 0; i < n_ops && err == hipSuccess; ++i) err = launch_widen_f32(src[i], dtype == MC_F32, x.p[i], numel[i], stream);
+  if (err != hipSuccess) {
+    release_extra(x);
+    if (new_base) drop_base(s);
+    return fail(MC_EHIP, "adapter '%s' on '%s': %s", x.adapter.c_str(), x.target.c_str(), hipGetErrorString(err));
+  }
+  size_t at = extras.size();
+  for (size_t i = 0; i < extras.size(); ++i)
+    if (extras[i].target == x.target && extras[i].adapter == x.adapter && extras[i].kind == x.kind) at = i;
+  if (at < extras.size()) {  // replaced: the old copies go (hipFree waits for a merge that may still read them)
+    release_extra(extras[at]);
+    extras[at] = x;
+  } else {
+    extras.push_back(x);
+  }
+  lora_scales.emplace(x.adapter, 1.f);
+  lora_dirty.insert(x.target);
+  return MC_OK;
+}
+
+mc_status WeightStore::lora_set_kron(const char* adapter, const char* weight_name, const void* w1_dev, const int64_t* w1_shape,
+                                     const void* w2_dev, const int64_t* w2_shape, mc_dtype dtype, float factor, hipStream_t stream) {
+  if (!adapter || !weight_name || !w1_dev || !w1_shape || !w2_dev || !w2_shape) return fail(MC_EINVAL, "null argument");
+  Slot* s = nullptr;
+  MC_TRY(extra_target("LoKr", weight_name, &s));
+  const size_t k = (size_t)s->lin->k_in, rows = s->numel / k;
+  const int64_t lim = 1 << 30;
+  for (const int64_t v : {w1_shape[0], w1_shape[1], w2_shape[0], w2_shape[1]})
+    if (v < 1 || v > lim)
+      return fail(MC_EINVAL, "LoKr '%s': factor shapes [%lld, %lld] and [%lld, %lld]", weight_name, (long long)w1_shape[0],
+                  (long long)w1_shape[1], (long long)w2_shape[0], (long long)w2_shape[1]);
+  const int r1 = (int)w1_shape[0], c1 = (int)w1_shape[1], r2 = (int)w2_shape[0], c2 = (int)w2_shape[1];
+  if ((size_t)r1 * (size_t)r2 != rows || (size_t)c1 * (size_t)c2 != k)
+    return fail(MC_EINVAL, "LoKr '%s': [%d, %d] (x) [%d, %d] is no factorisation of [%zu, %zu]", weight_name, r1, c1, r2, c2, rows, k);
+  if (other_terms(adapter, weight_name, AdapterExtra::KRON) + 1 > (size_t)kLoraMaxTerms)
+    return fail(MC_EINVAL, "LoKr '%s': more than %d adapters on one weight", weight_name, kLoraMaxTerms);
+  AdapterExtra x;
+  x.adapter = adapter; x.target = weight_name; x.kind = AdapterExtra::KRON; x.factor = factor;
+  x.r1 = r1; x.c1 = c1; x.r2 = r2; x.c2 = c2;
+  const void* src[2] = {w1_dev, w2_dev};
+  const size_t numel[2] = {(size_t)r1 * c1, (size_t)r2 * c2};
+  return store_extra(x, *s, src, numel, 2, dtype, stream);
+}
+
+mc_status WeightStore::lora_set_hada(const char* adapter, const char* weight_name, const void* u1_dev, const int64_t* u_shape,
+                                     const void* d1_dev, const int64_t* d_shape, const void* u2_dev, const void* d2_dev, mc_dtype dtype,
+                                     float factor, hipStream_t stream) {
+  if (!adapter || !weight_name || !u1_dev || !u_shape || !d1_dev || !d_shape || !u2_dev || !d2_dev) return fail(MC_EINVAL, "null argument");
+  Slot* s = nullptr;
+  MC_TRY(extra_target("LoHa", weight_name, &s));
+  const size_t k = (size_t)s->lin->k_in, rows = s->numel / k;
+  if (u_shape[1] < 1 || u_shape[1] > (1 << 20) || d_shape[0] != u_shape[1])
+    return fail(MC_EINVAL, "LoHa '%s': [%lld, %lld] and [%lld, %lld] share no rank", weight_name, (long long)u_shape[0],
+                (long long)u_shape[1], (long long)d_shape[0], (long long)d_shape[1]);
+  const int rank = (int)u_shape[1];
+  if (u_shape[0] != (int64_t)rows || d_shape[1] != (int64_t)k)
+    return fail(MC_EINVAL, "LoHa '%s': factors for a [%lld, %lld] weight, the weight is [%zu, %zu]", weight_name, (long long)u_shape[0],
+                (long long)d_shape[1], rows, k);
+  if (other_terms(adapter, weight_name, AdapterExtra::HADA) + 1 > (size_t)kLoraMaxTerms)
+    return fail(MC_EINVAL, "LoHa '%s': more than %d adapters on one weight", weight_name, kLoraMaxTerms);
+  AdapterExtra x;
+  x.adapter = adapter; x.target = weight_name; x.kind = AdapterExtra::HADA; x.factor = factor; x.rank = rank;
+  const void* src[4] = {u1_dev, d1_dev, u2_dev, d2_dev};
+  const size_t numel[4] = {rows * (size_t)rank, (size_t)rank * k, rows * (size_t)rank, (size_t)rank * k};
+  return store_extra(x, *s, src, numel, 4, dtype, stream);
+}
+
+mc_status WeightStore::lora_set_magnitude(const char* adapter, const char* weight_name, const void* mag_dev, size_t numel, mc_dtype dtype,
+                                          hipStream_t stream) {
+  if (!adapter || !weight_name || !mag_dev) return fail(MC_EINVAL, "null argument");
+  Slot* s = nullptr;
+  MC_TRY(extra_target("DoRA", weight_name, &s));
+  const size_t rows = s->numel / (size_t)s->lin->k_in;
+  if (numel != rows) return fail(MC_EINVAL, "DoRA '%s': a magnitude of %zu elements, %zu output rows", weight_name, numel, rows);
+  for (const AdapterExtra& o : extras)
+    if (o.kind == AdapterExtra::MAGNITUDE && o.target == weight_name && o.adapter != adapter)
+      return fail(MC_EINVAL, "DoRA '%s': adapter '%s' brings a magnitude, adapter '%s' already has one on this weight (one magnitude "
+                             "normalises a weight)", weight_name, adapter, o.adapter.c_str());
+  AdapterExtra x;
+  x.adapter = adapter; x.target = weight_name; x.kind = AdapterExtra::MAGNITUDE;
+  const void* src[1] = {mag_dev};
+  return store_extra(x, *s, src, &numel, 1, dtype, stream);
+}
+
 mc_status WeightStore::lora_set_delta(const char* adapter, const char* param_name, const void* delta_dev, size_t numel, mc_dtype dtype,
                                       hipStream_t stream) {
   auto it = slots.find(param_name);
@@ -281,6 +399,8 @@ mc_status WeightStore::lora_scale(const char* adapter, float scale) {
     if (p.adapter == adapter) lora_dirty.insert(p.target);
   for (const LoraDelta& d : deltas)
     if (d.adapter == adapter) lora_dirty.insert(d.target);
+  for (const AdapterExtra& x : extras)
+    if (x.adapter == adapter) lora_dirty.insert(x.target);
   return MC_OK;
 }
 
@@ -300,6 +420,13 @@ mc_status WeightStore::lora_remove(const char* adapter) {
     release(d.delta);
   }
   deltas.swap(kept_d);
+  std::vector<AdapterExtra> kept_x;
+  for (AdapterExtra& x : extras) {
+    if (adapter && x.adapter != adapter) { kept_x.push_back(x); continue; }
+    lora_dirty.insert(x.target);
+    release_extra(x);
+  }
+  extras.swap(kept_x);
   if (adapter) lora_scales.erase(adapter);
   else lora_scales.clear();
   return MC_OK;
@@ -362,7 +489,31 @@ mc_status WeightStore::lora_apply(hipStream_t stream, int* merged) {
       if (p.target != name || m == 0.f) continue;
       terms[n++] = LoraTerm{p.up, p.down_t, p.rank_pad, m};
     }
-    if (n == 0) {
+    KronTerm krons[kLoraMaxTerms];
+    HadaTerm hadas[kLoraMaxTerms];
+    int nk = 0, nh = 0;
+    const float* magnitude = nullptr;   // at most one per weight (lora_set_magnitude)
+    for (const AdapterExtra& x : extras) {
+      if (x.target != name) continue;
+      const float scale = lora_scales.at(x.adapter), m = scale * x.factor;
+      if (x.kind == AdapterExtra::MAGNITUDE) {
+        if (scale != 0.f) magnitude = x.p[0];
+      } else if (m != 0.f && x.kind == AdapterExtra::KRON) {
+        krons[nk++] = KronTerm{x.p[0], x.p[1], x.r1, x.c1, x.r2, x.c2, m};
+      } else if (m != 0.f) {
+        hadas[nh++] = HadaTerm{x.p[0], x.p[1], x.p[2], x.p[3], x.rank, m};
+      }
+    }
+    if (nk + nh > 0 || magnitude) {  // the general merge, over an fp32 image of the part that lives for this launch only
+      float* scratch = nullptr;
+      hipError_t err = hipMalloc((void**)&scratch, rows * k * sizeof(float));
+      if (err != hipSuccess) return fail(MC_ENOMEM, "adapter merge of '%s': hipMalloc(%zu) failed: %s", name.c_str(), rows * k * sizeof(float), hipGetErrorString(err));
+      err = launch_adapter_merge(l.w_base + s.off, (long)k, l.w + s.off, (long)k, (int)rows, (int)k, terms, n, krons, nk, hadas, nh,
+                                 magnitude, scratch, stream);
+      if (err == hipSuccess) err = hipStreamSynchronize(stream);
+      (void)hipFree(scratch);
+      if (err != hipSuccess) return fail(MC_EHIP, "adapter merge of '%s': %s", name.c_str(), hipGetErrorString(err));
+    } else if (n == 0) {
       HIP_TRY(hipMemcpyAsync(l.w + s.off, l.w_base + s.off, s.numel * 2, hipMemcpyDeviceToDevice, stream));
     } else {
       hipError_t err = launch_lora_merge(l.w_base + s.off, (long)k, l.w + s.off, (long)k, (int)rows, (int)k, terms, n, stream);
@@ -375,6 +526,7 @@ mc_status WeightStore::lora_apply(hipStream_t stream, int* merged) {
   for (Linear* l : touched) {  // no adapter left on any part: w is the base again, bit for bit
     bool live = false;
     for (const LoraPair& p : lora) live = live || slots.at(p.target).lin == l;
+    for (const AdapterExtra& x : extras) live = live || slots.at(x.target).lin == l;
     if (!live) {
       release(l->w_base);  // hipFree waits for the copies above
       l->w_base = nullptr;

@@ -100,6 +100,17 @@ struct LoraDelta {
   float* delta = nullptr;
 };
 
+// One adapter's Kronecker (LoKr) or Hadamard (LoHa) term, or its DoRA magnitude, on one bf16 part of a Linear: fp32 copies
+// owned by the store, as launch_adapter_merge reads them
+struct AdapterExtra {
+  enum Kind { KRON, HADA, MAGNITUDE };
+  std::string adapter, target;
+  Kind kind = KRON;
+  float* p[4] = {nullptr, nullptr, nullptr, nullptr};   // KRON: w1, w2; HADA: u1, d1, u2, d2; MAGNITUDE: g [rows]
+  int rank = 0, r1 = 0, c1 = 0, r2 = 0, c2 = 0;
+  float factor = 1.f;
+};
+
 struct WeightStore {
   std::map<std::string, Slot> slots;
   std::vector<void*> owned;
@@ -141,6 +152,25 @@ struct WeightStore {
   // matrix is refused: a full-rank delta is a checkpoint, not an adapter.
   mc_status lora_set_delta(const char* adapter, const char* param_name, const void* delta_dev, size_t numel, mc_dtype dtype,
                            hipStream_t stream);
+  // ---- the other kinds of term, on the bf16 parts lora_set takes (an fp32 matrix, a padded or permuted weight: MC_EINVAL
+  // naming it).  Operands fp32 or bf16, copied and widened to fp32.  The same (adapter, weight_name) and kind replaces; pairs,
+  // Kronecker and Hadamard terms together are at most kLoraMaxTerms per weight.  A part that carries one of these, or a
+  // magnitude, is rebuilt by launch_adapter_merge (ops.h states the arithmetic) with an fp32 scratch of the part's size that
+  // the apply allocates and frees; a part with live pairs only keeps launch_lora_merge.
+  // lora_set_kron: m * kron(w1 [r1, c1], w2 [r2, c2]) with r1 r2 = rows of the part and c1 c2 = in_features.
+  // The shapes are the 2-D shapes the C calls take (mc_lora_set_kron / _set_hada pass their arguments through); a null argument
+  // is MC_EINVAL.
+  mc_status lora_set_kron(const char* adapter, const char* weight_name, const void* w1_dev, const int64_t* w1_shape, const void* w2_dev,
+                          const int64_t* w2_shape, mc_dtype dtype, float factor, hipStream_t stream);
+  // lora_set_hada: m * (u1 d1) * (u2 d2) element-wise, u1 and u2 [rows, rank] (u_shape), d1 and d2 [rank, in_features] (d_shape)
+  mc_status lora_set_hada(const char* adapter, const char* weight_name, const void* u1_dev, const int64_t* u_shape, const void* d1_dev,
+                          const int64_t* d_shape, const void* u2_dev, const void* d2_dev, mc_dtype dtype, float factor,
+                          hipStream_t stream);
+  // lora_set_magnitude: the DoRA magnitude g [rows] of `adapter` on the part: live while the adapter's scale is not 0, the part is
+  // then g[r] / |V[r, :]| * V[r, :] with V = W + every live term (other adapters' included).  One magnitude per weight: a second
+  // adapter's is MC_EINVAL naming both adapters.
+  mc_status lora_set_magnitude(const char* adapter, const char* weight_name, const void* mag_dev, size_t numel, mc_dtype dtype,
+                               hipStream_t stream);
   mc_status lora_scale(const char* adapter, float scale);   // a term's multiplier is scale * factor
   mc_status lora_remove(const char* adapter);               // null: every adapter
   // every part whose terms, multipliers or base changed since the last apply: one merge over its rows (a term with multiplier 0
@@ -165,6 +195,16 @@ struct WeightStore {
   mc_status make_base(Slot& s, hipStream_t stream, bool* made);
   void drop_base(Slot& s);
   mc_status apply_f32(const std::string& name, Slot& s, hipStream_t stream);
+  // the slot of a Kronecker / Hadamard term or a magnitude (`what` names the kind in the error text), or MC_EINVAL naming the weight
+  mc_status extra_target(const char* what, const char* weight_name, Slot** slot);
+  // pairs, Kronecker and Hadamard terms on `weight_name` other than the (adapter, kind) being set; kind < 0: a pair
+  size_t other_terms(const char* adapter, const char* weight_name, int kind) const;
+  // `n_ops` operands of `numel[i]` elements copied into fresh fp32 allocations, the entry stored (replacing the one of the same
+  // adapter, weight and kind), the base copy made and the weight marked dirty
+  mc_status store_extra(AdapterExtra x, Slot& s, const void* const* src, const size_t* numel, int n_ops, mc_dtype dtype,
+                        hipStream_t stream);
+  void release_extra(AdapterExtra& x);
+  std::vector<AdapterExtra> extras;           // in the order they were set, like the pairs
   std::vector<LoraPair> lora;                 // in the order they were set: the term order of a merge
   std::vector<LoraDelta> deltas;              // likewise
   std::map<std::string, float> lora_scales;   // adapter -> scale

@@ -703,6 +703,27 @@ mc_status mc_mmdit_lora_set(mc_mmdit* e, const char* adapter, const char* weight
                              (size_t)up_shape[0] * up_shape[1], dtype, (int)down_shape[0], factor, (hipStream_t)stream);
 }
 
+mc_status mc_mmdit_lora_set_kron(mc_mmdit* e, const char* adapter, const char* weight_name, const void* w1_dev,
+                                 const int64_t* w1_shape, const void* w2_dev, const int64_t* w2_shape, mc_dtype dtype, float factor,
+                                 mc_stream stream) {
+  MC_TRY(lora_entry(e, "mc_mmdit_lora_set_kron"));
+  return e->weights.lora_set_kron(adapter, weight_name, w1_dev, w1_shape, w2_dev, w2_shape, dtype, factor, (hipStream_t)stream);
+}
+
+mc_status mc_mmdit_lora_set_hada(mc_mmdit* e, const char* adapter, const char* weight_name, const void* u1_dev,
+                                 const int64_t* u_shape, const void* d1_dev, const int64_t* d_shape, const void* u2_dev,
+                                 const void* d2_dev, mc_dtype dtype, float factor, mc_stream stream) {
+  MC_TRY(lora_entry(e, "mc_mmdit_lora_set_hada"));
+  return e->weights.lora_set_hada(adapter, weight_name, u1_dev, u_shape, d1_dev, d_shape, u2_dev, d2_dev, dtype, factor,
+                                  (hipStream_t)stream);
+}
+
+mc_status mc_mmdit_lora_set_magnitude(mc_mmdit* e, const char* adapter, const char* weight_name, const void* magnitude_dev,
+                                      size_t numel, mc_dtype dtype, mc_stream stream) {
+  MC_TRY(lora_entry(e, "mc_mmdit_lora_set_magnitude"));
+  return e->weights.lora_set_magnitude(adapter, weight_name, magnitude_dev, numel, dtype, (hipStream_t)stream);
+}
+
 mc_status mc_mmdit_lora_scale(mc_mmdit* e, const char* adapter, float scale) {
   MC_TRY(lora_entry(e, "mc_mmdit_lora_scale"));
   if (!adapter) return fail(MC_EINVAL, "null argument");

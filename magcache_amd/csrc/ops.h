@@ -221,6 +221,37 @@ hipError_t launch_param_delta(const float* base, float* out, size_t n, const flo
 hipError_t launch_lora_pack(const void* src, int src_f32, long row_stride, long col_stride, int n, int rank, int rank_pad, bf16_t* dst,
                             hipStream_t stream);
 
+// ---------------------------------------------------------------- adapter merge of every kind (adapter_merge.hip)
+// out[rows, K] (bf16) from a bf16 base, any mix of low-rank pairs, Kronecker (LoKr) and Hadamard (LoHa) terms and an optional
+// DoRA magnitude.  fp32 throughout, in `scratch` (rows * K floats, 16-byte aligned, owned by the caller):
+//   delta  = the pairs as launch_lora_merge_f32 forms them on a zero base (bf16 operands, fp32 MFMA accumulation, term order)
+//   delta += m_j * (w1_j[r / r2, c / c2] * w2_j[r % r2, c % c2])     one multiply for the product, one for m_j, one add
+//   delta += m_j * ((u1_j d1_j)[r, c] * (u2_j d2_j)[r, c])           two rank-long dot products in k order, then as above
+//   V      = fp32(base) + delta                                      ONE add of the base element, last
+//   out    = bf16(V)                                                 magnitude == null
+//   out    = bf16((g[r] / sqrt(sum_k V[r, k]^2)) * V[r, k])          magnitude g [rows]: thread t of the row's workgroup sums
+//            columns t, t + 256, ... in that order and a fixed tree adds the 256 partial sums; a row whose V is all zero stays zero
+// No product is contracted into an fma.  Kinds in the order above, terms of a kind in array order.  Element-wise launches, every
+// thread guarded on its row and its 8-column chunk; nothing outside [rows, K] of out is written; out may alias base.  Not a
+// forward-path launch.  hipErrorInvalidValue, and nothing launched, for what launch_lora_merge refuses, more than kLoraMaxTerms
+// terms in all, r1 * r2 != rows, c1 * c2 != K, a rank < 1, a null or misaligned operand or scratch.
+struct KronTerm {
+  const float* w1;   // [r1, c1]
+  const float* w2;   // [r2, c2]
+  int r1, c1, r2, c2;
+  float scale;
+};
+struct HadaTerm {
+  const float *u1, *d1, *u2, *d2;   // u [rows, rank], d [rank, K]
+  int rank;
+  float scale;
+};
+hipError_t launch_adapter_merge(const bf16_t* base, long ld_base, bf16_t* out, long ld_out, int rows, int K, const LoraTerm* pairs,
+                                int n_pairs, const KronTerm* krons, int n_kron, const HadaTerm* hadas, int n_hada,
+                                const float* magnitude, float* scratch, hipStream_t stream);
+// dst[i] = fp32(src[i]), i < n: src fp32 (a copy) or bf16 (widened exactly)
+hipError_t launch_widen_f32(const void* src, int src_f32, float* dst, size_t n, hipStream_t stream);
+
 // ---------------------------------------------------------------- attention (attention.hip)
 struct AttnParams {
   const bf16_t* Q; long ldq;

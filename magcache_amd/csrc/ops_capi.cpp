@@ -18,7 +18,7 @@ static mc::GemmParams gp(const bf16_t* A, long lda, const bf16_t* W, long ldw, c
 extern "C" {
 
 const char* mc_last_error(void) { return mc::last_error(); }
-const char* mc_version(void) { return "magcache_hip 0.8 (gfx950; 0.7.1 + token_timestep_sets)"; }
+const char* mc_version(void) { return "magcache_hip 0.8 (gfx950; 0.7.1 + token_timestep_sets + adapter_kinds)"; }
 
 // split-K scratch of the single-op entry point (mc_op_set_splitk_workspace): the engines carry their own in their workspace
 static float* g_op_splitk_ws = nullptr;
@@ -431,6 +431,89 @@ mc_status mc_op_lora_merge(const void* base, long ld_base, void* out, long ld_ou
 mc_status mc_op_lora_merge_f32(const float* base, long ld_base, float* out, long ld_out, int rows, int K, const mc_lora_term* terms,
                                int n_terms, void* scratch, size_t scratch_bytes, mc_stream s) {
   return op_lora_merge(true, base, ld_base, out, ld_out, rows, K, terms, n_terms, scratch, scratch_bytes, s);
+}
+
+// the fp32 image of the part first, then the packed copies of the pairs in term order
+size_t mc_op_adapter_merge_scratch(int rows, int K, const mc_adapter_term* terms, int n_terms) {
+  if (rows < 1 || K < 1) return 0;
+  size_t bytes = mc::align_up((size_t)rows * (size_t)K * sizeof(float), 256);
+  for (int j = 0; terms && j < n_terms; ++j) {
+    if (terms[j].kind != MC_ADAPTER_PAIR) continue;
+    if (terms[j].rank < 1) return 0;
+    const size_t rank_pad = mc::align_up(terms[j].rank, mc::kLoraRankStep);
+    bytes += mc::align_up(mc::lora_packed_elems(rows, rank_pad) * 2, 256) + mc::align_up(mc::lora_packed_elems(K, rank_pad) * 2, 256);
+  }
+  return bytes;
+}
+
+mc_status mc_op_adapter_merge(const void* base, long ld_base, void* out, long ld_out, int rows, int K, const mc_adapter_term* terms,
+                              int n_terms, const float* magnitude, void* scratch, size_t scratch_bytes, mc_stream s) {
+  hipStream_t stream = (hipStream_t)s;
+  static_assert(mc::kLoraMaxTerms == MC_LORA_MAX_TERMS, "header and kernel limits");
+  if (!base || !out || rows <= 0 || K <= 0 || n_terms < 0 || (n_terms > 0 && !terms)) return fail(MC_EINVAL, "adapter_merge: null or empty operand");
+  if (n_terms > MC_LORA_MAX_TERMS) return fail(MC_EINVAL, "adapter_merge: %d terms, at most %d", n_terms, MC_LORA_MAX_TERMS);
+  for (int j = 0; j < n_terms; ++j) {
+    const mc_adapter_term& t = terms[j];
+    if (t.kind == MC_ADAPTER_PAIR) {
+      if (!t.a || !t.b || t.rank < 1) return fail(MC_EINVAL, "adapter_merge: term %d (pair) has rank %d or a null matrix", j, t.rank);
+    } else if (t.kind == MC_ADAPTER_KRON) {
+      if (!t.a || !t.b || t.r1 < 1 || t.c1 < 1 || t.r2 < 1 || t.c2 < 1 || (long)t.r1 * t.r2 != rows || (long)t.c1 * t.c2 != K)
+        return fail(MC_EINVAL, "adapter_merge: term %d: [%d, %d] (x) [%d, %d] is no factorisation of [%d, %d], or a null factor", j, t.r1,
+                    t.c1, t.r2, t.c2, rows, K);
+    } else if (t.kind == MC_ADAPTER_HADA) {
+      if (!t.a || !t.b || !t.c || !t.d || t.rank < 1) return fail(MC_EINVAL, "adapter_merge: term %d (hada) has rank %d or a null matrix", j, t.rank);
+    } else {
+      return fail(MC_EINVAL, "adapter_merge: term %d has the unknown kind %d", j, t.kind);
+    }
+    if (t.kind != MC_ADAPTER_PAIR && (((uintptr_t)t.a | (uintptr_t)t.b | (uintptr_t)t.c | (uintptr_t)t.d) & 3))
+      return fail(MC_EINVAL, "adapter_merge: term %d: fp32 factors are 4-byte aligned", j);
+  }
+  if ((uintptr_t)magnitude & 3) return fail(MC_EINVAL, "adapter_merge: the magnitude is 4-byte aligned");
+  if ((K % 8) != 0 || ld_base < K || ld_out < K || (ld_base % 8) != 0 || (ld_out % 8) != 0 || (((uintptr_t)base | (uintptr_t)out) & 15))
+    return fail(MC_EINVAL, "adapter_merge: K and the pitches are multiples of 8, pitch >= K, base and out 16-byte aligned");
+  const size_t need = mc_op_adapter_merge_scratch(rows, K, terms, n_terms);
+  char* ws = (char*)scratch;
+  if (ws && (scratch_bytes < need || ((uintptr_t)ws & 255)))
+    return fail(MC_EINVAL, "adapter_merge: scratch of %zu bytes, %zu needed, 256-byte aligned", scratch_bytes, need);
+  bool own = false;
+  if (!ws) {
+    hipError_t err = hipMalloc((void**)&ws, need);
+    if (err != hipSuccess) return fail(MC_ENOMEM, "hipMalloc(%zu) failed: %s", need, hipGetErrorString(err));
+    own = true;
+  }
+  mc::LoraTerm pairs[MC_LORA_MAX_TERMS];
+  mc::KronTerm krons[MC_LORA_MAX_TERMS];
+  mc::HadaTerm hadas[MC_LORA_MAX_TERMS];
+  int np = 0, nk = 0, nh = 0;
+  hipError_t err = hipSuccess;
+  size_t off = mc::align_up((size_t)rows * (size_t)K * sizeof(float), 256);
+  for (int j = 0; j < n_terms && err == hipSuccess; ++j) {
+    const mc_adapter_term& t = terms[j];
+    if (t.kind == MC_ADAPTER_KRON) {
+      krons[nk++] = mc::KronTerm{(const float*)t.a, (const float*)t.b, t.r1, t.c1, t.r2, t.c2, t.scale};
+    } else if (t.kind == MC_ADAPTER_HADA) {
+      hadas[nh++] = mc::HadaTerm{(const float*)t.a, (const float*)t.b, (const float*)t.c, (const float*)t.d, t.rank, t.scale};
+    } else {   // a = down [rank, K], b = up [rows, rank], bf16: packed as mc_op_lora_merge packs them
+      const int rank_pad = (int)mc::align_up(t.rank, mc::kLoraRankStep);
+      bf16_t* up = (bf16_t*)(ws + off);
+      off += mc::align_up(mc::lora_packed_elems(rows, rank_pad) * 2, 256);
+      bf16_t* down_t = (bf16_t*)(ws + off);
+      off += mc::align_up(mc::lora_packed_elems(K, rank_pad) * 2, 256);
+      pairs[np++] = mc::LoraTerm{up, down_t, rank_pad, t.scale};
+      err = mc::launch_lora_pack(t.b, 0, t.rank, 1, rows, t.rank, rank_pad, up, stream);
+      if (err == hipSuccess) err = mc::launch_lora_pack(t.a, 0, 1, K, K, t.rank, rank_pad, down_t, stream);
+    }
+  }
+  if (err == hipSuccess)
+    err = mc::launch_adapter_merge((const bf16_t*)base, ld_base, (bf16_t*)out, ld_out, rows, K, pairs, np, krons, nk, hadas, nh, magnitude,
+                                   (float*)ws, stream);
+  if (own) {
+    if (err == hipSuccess) err = hipStreamSynchronize(stream);
+    (void)hipFree(ws);
+  }
+  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "adapter_merge: a misaligned operand (factors and magnitude 4-byte, pairs 16-byte aligned)");
+  HIP_TRY(err);
+  return MC_OK;
 }
 
 mc_status mc_op_param_delta(const float* base, float* out, size_t n, const float* const* deltas, const float* scales, int n_terms,

@@ -91,16 +91,17 @@ class Engine(EngineHost):
 
     The workspace, set_weight / load_weights, buffer and destruction are adapters.EngineHost's.
     LoRA adapters (adapters.LoraHost over mc_lora_*): load_lora / set_adapters / set_lora_call_scale / unload_lora /
-    apply_lora / lora_info.  An adapter file is read by lora.parse_wan_lora_state_dict: low-rank pairs on the bf16 matrices
-    and on the fp32 time MLP, time projection and head, additive deltas on biases, norm weights and modulation tables.
+    apply_lora / lora_info.  An adapter file is read by lora.parse_wan_adapter_state_dict: low-rank pairs on the bf16 matrices
+    and on the fp32 time MLP, time projection and head, additive deltas on biases, norm weights and modulation tables, and on
+    the bf16 matrices LoKr and LoHa terms and DoRA magnitudes.
     Every apply that changed a weight makes the engine forget the cached text contexts, the CLIP context and the VACE
     context (set them again; WanModelHIP does by itself)."""
     _abi = "mc_"
     _lora_prefix = ""
 
     def _lora_entries(self, sd, prefix):
-        from .lora import parse_wan_lora_state_dict
-        return parse_wan_lora_state_dict(sd)
+        from .lora import parse_wan_adapter_state_dict
+        return parse_wan_adapter_state_dict(sd)
 
     def __init__(self, cfg, latent_grid, device="cuda:0", sp_rank=0, sp_size=1, n_branches=2, calibration=False,
                  sp_phases=False, mx_fp4=False, mx_fp6=False):

@@ -1,5 +1,7 @@
 """LoRA state dicts -> the weight names of the engines.  Pure Python: no GPU, no library.  The MM-DiT engine's reader comes
-first; the Wan engine's (parse_wan_lora_state_dict, wan_lora_target_names) is at the end of the file.
+first, then the Wan engine's (parse_wan_lora_state_dict, wan_lora_target_names at the end of the file); between them the
+readers both engines load files through, which add DoRA, LoKr and LoHa to what those two read (parse_adapter_state_dict,
+parse_wan_adapter_state_dict).
 
 An adapter file names the MODULE it wraps; the engine names WEIGHTS, by their upstream state_dict names
 (mc_mmdit_set_weight), and takes an adapter pair per such name (mc_mmdit_lora_set) -- also where it stores several upstream
@@ -213,6 +215,158 @@ def parse_wan_lora_state_dict(sd):
             raise ValueError(f"LoRA state dict: '{target}' has a low-rank pair and a delta")
         out[target] = ("delta", t)
     return out
+
+
+# ------------------------------------------------------------------------------------------------ DoRA, LoKr, LoHa
+# The readers both engines use (adapters.LoraHost._lora_entries, engine.Engine._lora_entries).  They read everything the two
+# readers above read -- through them, so a plain LoRA file gives exactly their entries -- and three more kinds of key, each
+# also with a trailing ".<adapter>" infix:
+#
+#   <module>.lora_magnitude_vector[.<adapter>][.weight]  | <module>.dora_scale     DoRA magnitude, [out] or [out, 1]
+#   <module>.lokr_w1 | .lokr_w1_a @ .lokr_w1_b,  <module>.lokr_w2 | .lokr_w2_a @ .lokr_w2_b      LoKr: kron(w1, w2)
+#   <module>.hada_w1_a [out, r], .hada_w1_b [r, in], .hada_w2_a, .hada_w2_b        LoHa: (w1_a w1_b) * (w2_a w2_b)
+#   <module>.alpha                                                                 optional, as for pairs
+#
+# Entries, next to the pair / delta entries of the reader above:
+#   ("kron", w1, w2, factor)                    w1, w2: a tensor, or the tuple (a, b) of a factorised half (a @ b is the half)
+#   ("hada", w1_a, w1_b, w2_a, w2_b, factor)
+#   ("dora", inner, magnitude [out])            inner: ("pair", down, up, alpha) or one of the two above
+# Refused (ValueError): lokr_t2 / hada_t1 / hada_t2 (Tucker / conv forms), a per-input-column magnitude [1, in], a magnitude
+# on a module that has no term, two spellings of one tensor, halves that share no rank, half a LoKr / LoHa set, LoKr and LoHa
+# (or one of them and a pair) on one module.  Whether kron(w1, w2) has the weight's shape only the engine can say
+# (mc_lora_set_kron: MC_EINVAL).  Key names and the three rules below are LyCORIS's and PEFT's as remembered: [UPSTREAM] in
+# INTEGRATION.md.
+_MAGNITUDE = re.compile(r"^(?P<module>.+)\.(?:lora_magnitude_vector(?:\.[^.]+)?(?:\.weight)?|dora_scale(?:\.[^.]+)?)$")
+_KIND = re.compile(r"^(?P<module>.+)\.(?P<what>lokr_w[12](?:_[ab])?|lokr_t2|hada_w[12]_[ab]|hada_t[12])(?:\.[^.]+)?$")
+_TUCKER = ("lokr_t2", "hada_t1", "hada_t2")
+
+
+def dora_magnitude(module, t):
+    """[UPSTREAM] the magnitude of a module as a 1-D [out] tensor: PEFT stores [out], LyCORIS's dora_scale [out, 1]"""
+    shape = tuple(t.shape)
+    if len(shape) == 1:
+        return t
+    if len(shape) == 2 and shape[1] == 1:
+        return t.reshape(shape[0])
+    if len(shape) == 2 and shape[0] == 1:
+        raise ValueError(f"DoRA magnitude of '{module}' is {shape}: one value per input column (LyCORIS's per-input-column "
+                         "variant), which is not supported; the engines take one value per output row")
+    raise ValueError(f"DoRA magnitude of '{module}' is {shape}, expected [out] or [out, 1]")
+
+
+def lokr_factor(alpha, rank):
+    """[UPSTREAM] alpha / rank where a half is factorised (rank: its inner dimension), 1 where both halves are full (rank None)
+    or the file carries no alpha"""
+    return 1.0 if alpha is None or rank is None else float(alpha) / int(rank)
+
+
+def loha_factor(alpha, rank):
+    """[UPSTREAM] alpha / rank; 1 where the file carries no alpha"""
+    return 1.0 if alpha is None else float(alpha) / int(rank)
+
+
+def _lokr_half(module, parts, n):
+    """(half, rank or None): lokr_w<n>, or (lokr_w<n>_a, lokr_w<n>_b)"""
+    full, a, b = (parts.get(f"lokr_w{n}{s}") for s in ("", "_a", "_b"))
+    if full is not None and (a is not None or b is not None):
+        raise ValueError(f"LoKr of '{module}': lokr_w{n} repeats what lokr_w{n}_a / lokr_w{n}_b spell (two spellings of one tensor)")
+    if full is not None:
+        if len(full.shape) != 2:
+            raise ValueError(f"LoKr of '{module}': lokr_w{n} is {tuple(full.shape)}, not a matrix (conv forms are not supported)")
+        return full, None
+    if a is None or b is None:
+        raise ValueError(f"LoKr of '{module}': keys belong to no complete set (lokr_w{n}, or lokr_w{n}_a and lokr_w{n}_b, is missing)")
+    if len(a.shape) != 2 or len(b.shape) != 2 or a.shape[1] != b.shape[0]:
+        raise ValueError(f"LoKr of '{module}': lokr_w{n}_a {tuple(a.shape)} and lokr_w{n}_b {tuple(b.shape)} share no rank")
+    return (a, b), int(a.shape[1])
+
+
+def _kind_entry(module, parts, alpha):
+    lokr = any(k.startswith("lokr") for k in parts)
+    if lokr and any(k.startswith("hada") for k in parts):
+        raise ValueError(f"adapter state dict: '{module}' has LoKr and LoHa keys")
+    if lokr:
+        (w1, rank1), (w2, rank2) = _lokr_half(module, parts, 1), _lokr_half(module, parts, 2)
+        if rank1 is not None and rank2 is not None and rank1 != rank2:
+            raise ValueError(f"LoKr of '{module}': the factorised halves share no rank ({rank1} and {rank2})")
+        return ("kron", w1, w2, lokr_factor(alpha, rank2 if rank2 is not None else rank1))
+    names = ("hada_w1_a", "hada_w1_b", "hada_w2_a", "hada_w2_b")
+    missing = [n for n in names if n not in parts]
+    if missing:
+        raise ValueError(f"LoHa of '{module}': keys belong to no complete set ({missing} missing)")
+    w1a, w1b, w2a, w2b = (parts[n] for n in names)
+    if any(len(t.shape) != 2 for t in (w1a, w1b, w2a, w2b)):
+        raise ValueError(f"LoHa of '{module}': the factors are matrices (conv forms are not supported)")
+    rank = int(w1a.shape[1])
+    if w1b.shape[0] != rank or w2a.shape[1] != rank or w2b.shape[0] != rank or w1a.shape[0] != w2a.shape[0] or w1b.shape[1] != w2b.shape[1]:
+        raise ValueError(f"LoHa of '{module}': {[tuple(t.shape) for t in (w1a, w1b, w2a, w2b)]} share no rank")
+    return ("hada", w1a, w1b, w2a, w2b, loha_factor(alpha, rank))
+
+
+def _parse_adapter(items, old_reader, module_of, tag_pair):
+    """items: [(name with the file's prefix removed, key as the file has it, tensor)].  The keys of the three new kinds are taken
+    out, the rest goes through `old_reader`; module_of: a file's module name -> the engine's; tag_pair: an entry of the old
+    reader -> the ("pair", ...) form a "dora" entry holds."""
+    rest, parts, mags = {}, {}, {}
+    for name, key, t in items:
+        m = _MAGNITUDE.match(name)
+        if m:
+            module = module_of(m.group("module"))
+            if module in mags:
+                raise ValueError(f"adapter state dict: '{key}' repeats the magnitude of '{module}' (two spellings of one tensor)")
+            mags[module] = t
+            continue
+        m = _KIND.match(name)
+        if m:
+            module, what = module_of(m.group("module")), m.group("what")
+            if what in _TUCKER:
+                raise ValueError(f"adapter state dict: '{key}' is a Tucker / conv factor ({what}), which is not supported")
+            if what in parts.setdefault(module, {}):
+                raise ValueError(f"adapter state dict: '{key}' repeats {what} of '{module}' (two spellings of one tensor)")
+            parts[module][what] = t
+            continue
+        rest[name] = t
+    alpha = {}
+    for name in list(rest):
+        m = _ALPHA.match(name)
+        if m and module_of(m.group("module")) in parts:
+            alpha[module_of(m.group("module"))] = float(rest.pop(name))
+    out = dict(old_reader(rest))
+    for module, p in parts.items():
+        target = module + ".weight"
+        if target in out:
+            raise ValueError(f"adapter state dict: '{target}' has two kinds of term in one file")
+        out[target] = _kind_entry(module, p, alpha.get(module))
+    for module, t in mags.items():
+        target = module + ".weight"
+        if target not in out or (isinstance(out[target][0], str) and out[target][0] == "delta"):
+            raise ValueError(f"adapter state dict: '{module}' has a DoRA magnitude and no term (a magnitude with no term is no adapter)")
+        out[target] = ("dora", tag_pair(out[target]), dora_magnitude(module, t))
+    return out
+
+
+def parse_adapter_state_dict(sd, prefix="transformer."):
+    """parse_lora_state_dict plus DoRA, LoKr and LoHa (the comment above): {target weight name: entry}, a plain pair as the
+    3-tuple (down, up, alpha) of parse_lora_state_dict -- on a plain LoRA file exactly its result."""
+    keys = list(sd.keys())
+    strip = 0
+    if prefix and any(k.startswith(prefix) for k in keys):
+        keys = [k for k in keys if k.startswith(prefix)]
+        strip = len(prefix)
+    return _parse_adapter([(k[strip:], k, sd[k]) for k in keys], lambda rest: parse_lora_state_dict(rest, prefix=None),
+                          lambda module: module, lambda e: e if isinstance(e[0], str) else ("pair",) + tuple(e))
+
+
+def parse_wan_adapter_state_dict(sd):
+    """parse_wan_lora_state_dict plus DoRA, LoKr and LoHa on the bf16 matrices: on a plain Wan adapter file exactly its result"""
+    keys = list(sd.keys())
+    strip = 0
+    for prefix in _WAN_PREFIXES:
+        if any(k.startswith(prefix) for k in keys):
+            keys = [k for k in keys if k.startswith(prefix)]
+            strip = len(prefix)
+            break
+    return _parse_adapter([(k[strip:], k, sd[k]) for k in keys], parse_wan_lora_state_dict, _wan_module, lambda e: e)
 
 
 def wan_lora_target_names(cfg):

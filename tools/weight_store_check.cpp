@@ -34,6 +34,7 @@ extern "C" hipError_t hipMemcpy2DAsync(void* dst, size_t dp, const void* src, si
   return hipSuccess;
 }
 extern "C" const char* hipGetErrorString(hipError_t) { return "stub"; }
+extern "C" hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
 
 // ---------------------------------------------------------------- the launchers, as the bytes they touch
 namespace mc {
@@ -108,6 +109,31 @@ hipError_t launch_lora_merge(const bf16_t* base, long ld_base, bf16_t* out, long
 hipError_t launch_lora_merge_f32(const float* base, long ld_base, float* out, long ld_out, int rows, int K, const LoraTerm* t, int n,
                                  hipStream_t) {
   return merge_stub(base, ld_base, out, ld_out, rows, K, t, n);
+}
+hipError_t launch_widen_f32(const void* src, int src_f32, float* dst, size_t n, hipStream_t) {
+  touch(src, n * (src_f32 ? 4 : 2));
+  for (size_t i = 0; i < n; ++i) dst[i] = 1.f;
+  return hipSuccess;
+}
+static int g_adapter_merges = 0, g_adapter_magnitudes = 0;   // general merges launched; those that had a magnitude
+hipError_t launch_adapter_merge(const bf16_t* base, long ld_base, bf16_t* out, long ld_out, int rows, int K, const LoraTerm* pairs,
+                                int n_pairs, const KronTerm* krons, int n_kron, const HadaTerm* hadas, int n_hada,
+                                const float* magnitude, float* scratch, hipStream_t) {
+  if (n_pairs + n_kron + n_hada > kLoraMaxTerms) return hipErrorInvalidValue;
+  for (int j = 0; j < n_kron; ++j) {
+    if ((long)krons[j].r1 * krons[j].r2 != rows || (long)krons[j].c1 * krons[j].c2 != K) return hipErrorInvalidValue;
+    touch(krons[j].w1, (size_t)krons[j].r1 * krons[j].c1 * 4);
+    touch(krons[j].w2, (size_t)krons[j].r2 * krons[j].c2 * 4);
+  }
+  for (int j = 0; j < n_hada; ++j) {
+    for (const float* u : {hadas[j].u1, hadas[j].u2}) touch(u, (size_t)rows * hadas[j].rank * 4);
+    for (const float* dd : {hadas[j].d1, hadas[j].d2}) touch(dd, (size_t)hadas[j].rank * K * 4);
+  }
+  if (magnitude) touch(magnitude, (size_t)rows * 4);
+  memset(scratch, 0, (size_t)rows * K * 4);
+  ++g_adapter_merges;
+  g_adapter_magnitudes += magnitude != nullptr;
+  return merge_stub(base, ld_base, out, ld_out, rows, K, pairs, n_pairs);
 }
 hipError_t launch_param_delta(const float* base, float* out, size_t n, const float* const* deltas, const float* scales, int n_terms,
                               hipStream_t) {
@@ -239,6 +265,74 @@ int main() {
     EXPECT(W.add_f32(head, "head.weight", 64 * 16, 16), MC_OK);
     EXPECT(W.lora_set("a", "head.weight", v.data(), 4 * 16, v.data(), 64 * 4, MC_F32, 4, 1.f, nullptr), MC_EINVAL);
     EXPECT(W.lora_set_delta("a", "head.weight", v.data(), 64 * 16, MC_F32, nullptr), MC_EINVAL);
+    W.free_all();
+    EXPECT_TRUE(g_live == 0);
+  }
+  {  // Kronecker and Hadamard terms and DoRA magnitudes: fp32 copies, the general merge with its scratch, the shared limit
+    WeightStore W;
+    W.allow_f32_targets = true;
+    Linear qkv;
+    float* w_time = nullptr;
+    EXPECT(W.add_linear(qkv, "blk.", {{"q", d}, {"k", d}, {"v", d}}, d, QUANT_ROW), MC_OK);
+    EXPECT(W.add_f32(w_time, "time.weight", d * kt, kt), MC_OK);
+    std::vector<float> src(d * d, 0.5f), w1(4 * 8, 0.1f), w2(16 * 8, 0.2f), g(d, 1.f), down(rank * d, 0.1f), up(d * rank, 0.2f);
+    std::vector<uint16_t> ub(d * rank, 0x3c00), db(rank * d, 0x3c00);   // bf16 operands: widened on the way in
+    const int64_t mat[2] = {(int64_t)d, (int64_t)d}, tm[2] = {(int64_t)d, (int64_t)kt};
+    const int64_t s1[2] = {4, 8}, s2[2] = {16, 8}, bad[2] = {5, 8}, us[2] = {(int64_t)d, (int64_t)rank}, ds[2] = {(int64_t)rank, (int64_t)d},
+                  ds_bad[2] = {(int64_t)rank + 1, (int64_t)d};
+    for (const char* p : {"q", "k", "v"}) EXPECT(W.set((std::string("blk.") + p + ".weight").c_str(), src.data(), MC_F32, mat, 2, nullptr), MC_OK);
+    EXPECT(W.set("time.weight", src.data(), MC_F32, tm, 2, nullptr), MC_OK);
+    EXPECT(W.lora_set_kron("a", "blk.q.weight", w1.data(), s1, w2.data(), s2, MC_F32, 1.f, nullptr), MC_OK);
+    EXPECT(W.lora_set_hada("a", "blk.q.weight", ub.data(), us, db.data(), ds, ub.data(), db.data(), MC_BF16, 0.5f, nullptr), MC_OK);
+    EXPECT(W.lora_set_magnitude("a", "blk.q.weight", g.data(), d, MC_F32, nullptr), MC_OK);
+    EXPECT(W.lora_set("a", "blk.q.weight", down.data(), rank * d, up.data(), d * rank, MC_F32, rank, 2.f, nullptr), MC_OK);
+    long live = g_live;
+    // replace: the same (adapter, weight) and kind again
+    EXPECT(W.lora_set_kron("a", "blk.q.weight", w2.data(), s2, w1.data(), s1, MC_F32, 1.f, nullptr), MC_OK);
+    EXPECT(W.lora_set_hada("a", "blk.q.weight", ub.data(), us, db.data(), ds, ub.data(), db.data(), MC_BF16, 1.f, nullptr), MC_OK);
+    EXPECT(W.lora_set_magnitude("a", "blk.q.weight", g.data(), d, MC_F32, nullptr), MC_OK);
+    EXPECT_TRUE(g_live == live);
+    // refusals: nothing may stay allocated behind them
+    EXPECT(W.lora_set_kron("a", "blk.q.weight", w1.data(), bad, w2.data(), s2, MC_F32, 1.f, nullptr), MC_EINVAL);
+    EXPECT(W.lora_set_kron("a", "time.weight", w1.data(), s1, w2.data(), s2, MC_F32, 1.f, nullptr), MC_EINVAL);
+    EXPECT(W.lora_set_kron("a", "nope.weight", w1.data(), s1, w2.data(), s2, MC_F32, 1.f, nullptr), MC_EINVAL);
+    EXPECT(W.lora_set_kron("a", "blk.q.weight", nullptr, s1, w2.data(), s2, MC_F32, 1.f, nullptr), MC_EINVAL);
+    EXPECT(W.lora_set_hada("a", "blk.q.weight", ub.data(), us, db.data(), ds_bad, ub.data(), db.data(), MC_BF16, 1.f, nullptr), MC_EINVAL);
+    EXPECT(W.lora_set_hada("a", "time.weight", ub.data(), us, db.data(), ds, ub.data(), db.data(), MC_BF16, 1.f, nullptr), MC_EINVAL);
+    EXPECT(W.lora_set_magnitude("a", "blk.q.weight", g.data(), d - 1, MC_F32, nullptr), MC_EINVAL);
+    EXPECT(W.lora_set_magnitude("a", "time.weight", g.data(), d, MC_F32, nullptr), MC_EINVAL);
+    EXPECT(W.lora_set_magnitude("b", "blk.q.weight", g.data(), d, MC_F32, nullptr), MC_EINVAL);   // a second adapter's magnitude
+    EXPECT_TRUE(strstr(last_error(), "'a'") && strstr(last_error(), "'b'"));
+    EXPECT_TRUE(g_live == live);
+    // all kinds count towards the limit: q carries a pair, a Kronecker and a Hadamard term
+    for (int i = 0; i < kLoraMaxTerms - 3; ++i)
+      EXPECT(W.lora_set_kron(("n" + std::to_string(i)).c_str(), "blk.q.weight", w1.data(), s1, w2.data(), s2, MC_F32, 1.f, nullptr), MC_OK);
+    EXPECT(W.lora_set_kron("ninth", "blk.q.weight", w1.data(), s1, w2.data(), s2, MC_F32, 1.f, nullptr), MC_EINVAL);
+    EXPECT(W.lora_set("ninth", "blk.q.weight", down.data(), rank * d, up.data(), d * rank, MC_F32, rank, 1.f, nullptr), MC_EINVAL);
+    EXPECT(W.lora_set_hada("ninth", "blk.q.weight", ub.data(), us, db.data(), ds, ub.data(), db.data(), MC_BF16, 1.f, nullptr), MC_EINVAL);
+    // a pair alone on another part of the same Linear keeps the pair merge
+    EXPECT(W.lora_set("a", "blk.k.weight", down.data(), rank * d, up.data(), d * rank, MC_F32, rank, 1.f, nullptr), MC_OK);
+    int merged = -1;
+    live = g_live;
+    EXPECT(W.lora_apply(nullptr, &merged), MC_OK);
+    EXPECT_TRUE(merged == 2 && g_adapter_merges == 1 && g_adapter_magnitudes == 1 && g_live == live);   // the scratch came and went
+    // scale 0: the terms and the magnitude of "a" are left out, the others' Kronecker terms stay
+    EXPECT(W.lora_scale("a", 0.f), MC_OK);
+    EXPECT(W.lora_apply(nullptr, &merged), MC_OK);
+    EXPECT_TRUE(merged == 2 && g_adapter_merges == 2 && g_adapter_magnitudes == 1);
+    for (int i = 0; i < kLoraMaxTerms - 3; ++i) EXPECT(W.lora_remove(("n" + std::to_string(i)).c_str()), MC_OK);
+    EXPECT(W.lora_apply(nullptr, &merged), MC_OK);
+    EXPECT_TRUE(merged == 1 && g_adapter_merges == 2 && qkv.w_base != nullptr);   // nothing live on q: the base rows, copied back
+    EXPECT(W.lora_scale("a", 1.f), MC_OK);
+    EXPECT(W.lora_remove("a"), MC_OK);
+    EXPECT(W.lora_apply(nullptr, &merged), MC_OK);
+    int adapters = -1, params = -1;
+    size_t bytes = 1;
+    W.lora_info(&adapters, &params, &bytes);
+    EXPECT_TRUE(adapters == 0 && params == 0 && bytes == 0 && qkv.w_base == nullptr && g_adapter_merges == 2);
+    // entries still set when the store goes: free_all takes everything
+    EXPECT(W.lora_set_hada("c", "blk.v.weight", ub.data(), us, db.data(), ds, ub.data(), db.data(), MC_BF16, 1.f, nullptr), MC_OK);
+    EXPECT(W.lora_set_magnitude("c", "blk.v.weight", g.data(), d, MC_F32, nullptr), MC_OK);
     W.free_all();
     EXPECT_TRUE(g_live == 0);
   }
