@@ -155,53 +155,6 @@ mc_status check_mx_k(MxFormat fmt, const char* what, int k) {
 }
 
 // ------------------------------------------------------------------------------------------------ LoRA adapters
-mc_status WeightStore::lora_set(const char* adapter, const char* weight_name, const void* down_dev, size_t down_numel,
-                                const void* up_dev, size_t up_numel, mc_dtype dtype, int rank, float factor, hipStream_t stream) {
-  auto it = slots.find(weight_name);
-  if (it == slots.end()) return fail(MC_EINVAL, "LoRA: unknown weight '%s'", weight_name);
-  Slot& s = it->second;
-  const bool f32_matrix = allow_f32_targets && s.dst_dtype == MC_F32 && s.f32_k > 0 && !s.perm_c && !s.fixed;
-  if (!f32_matrix && (!s.lin || s.dst_dtype != MC_BF16 || s.pad.rows || s.perm_c || s.fixed))
-    return fail(MC_EINVAL, "LoRA: '%s' is no plain bf16 part of a Linear (an fp32, padded or permuted weight takes no adapter)",
-                weight_name);
-  if (dtype != MC_F32 && dtype != MC_BF16) return fail(MC_EINVAL, "LoRA '%s': down / up are fp32 or bf16", weight_name);
-  const size_t k = f32_matrix ? s.f32_k : (size_t)s.lin->k_in, rows = s.numel / k;
-  if (rank <= 0) return fail(MC_EINVAL, "LoRA '%s': rank %d", weight_name, rank);
-  if (down_numel != (size_t)rank * k || up_numel != rows * (size_t)rank)
-    return fail(MC_EINVAL, "LoRA '%s': down has %zu elements, up %zu; rank %d wants [%d, %zu] = %zu and [%zu, %d] = %zu", weight_name,
-                down_numel, up_numel, rank, rank, k, (size_t)rank * k, rows, rank, rows * (size_t)rank);
-  if ((k % (f32_matrix ? 4 : 8)) != 0)
-    return fail(MC_EINVAL, "LoRA '%s': in_features %zu is no multiple of %d", weight_name, k, f32_matrix ? 4 : 8);
-  size_t at = lora.size();
-  for (size_t i = 0; i < lora.size(); ++i)
-    if (lora[i].target == weight_name && lora[i].adapter == adapter) at = i;
-  if (other_terms(adapter, weight_name, -1) + 1 > (size_t)kLoraMaxTerms)
-    return fail(MC_EINVAL, "LoRA '%s': more than %d adapters on one weight", weight_name, kLoraMaxTerms);
-  const int rank_pad = (int)align_up(rank, kLoraRankStep);
-  LoraPair p;
-  p.adapter = adapter; p.target = weight_name; p.rank_pad = rank_pad; p.factor = factor;
-  MC_TRY(alloc(&p.up, lora_packed_elems(rows, rank_pad)));
-  if (mc_status st = alloc(&p.down_t, lora_packed_elems(k, rank_pad))) { release(p.up); return st; }
-  bool new_base = false;   // the first adapter on this Linear (this fp32 matrix): its pristine copy
-  if (mc_status st = make_base(s, stream, &new_base)) { release(p.up); release(p.down_t); return st; }
-  hipError_t err = launch_lora_pack(up_dev, dtype == MC_F32, rank, 1, (int)rows, rank, rank_pad, p.up, stream);
-  if (err == hipSuccess) err = launch_lora_pack(down_dev, dtype == MC_F32, 1, (long)k, (int)k, rank, rank_pad, p.down_t, stream);
-  if (err != hipSuccess) {
-    release(p.up); release(p.down_t);
-    if (new_base) drop_base(s);
-    return fail(MC_EHIP, "LoRA '%s': %s", weight_name, hipGetErrorString(err));
-  }
-  if (at < lora.size()) {  // replaced: the old pair's copies go (hipFree waits for a merge that may still read them)
-    release(lora[at].up); release(lora[at].down_t);
-    lora[at] = p;
-  } else {
-    lora.push_back(p);
-  }
-  lora_scales.emplace(adapter, 1.f);
-  lora_dirty.insert(weight_name);
-  return MC_OK;
-}
-
 mc_status WeightStore::make_base(Slot& s, hipStream_t stream, bool* made) {
   *made = false;
   if (s.lin ? s.lin->w_base != nullptr : s.f32_base != nullptr) return MC_OK;
@@ -228,85 +181,162 @@ void WeightStore::drop_base(Slot& s) {   // hipFree waits for the launches that 
   else { release(s.f32_base); s.f32_base = nullptr; }
 }
 
-// ---- Kronecker and Hadamard terms, DoRA magnitudes
-size_t WeightStore::other_terms(const char* adapter, const char* weight_name, int kind) const {
-  size_t n = 0;
-  for (const LoraPair& p : lora)
-    if (p.target == weight_name && !(kind < 0 && p.adapter == adapter)) ++n;
-  for (const AdapterExtra& x : extras)
-    if (x.target == weight_name && x.kind != AdapterExtra::MAGNITUDE && !(kind == (int)x.kind && x.adapter == adapter)) ++n;
-  return n;
+bool WeightStore::base_in_use(const Slot& s) const {
+  for (const AdapterTerm& t : terms) {
+    const Slot& o = slots.at(t.target);
+    if (s.lin ? o.lin == s.lin : &o == &s) return true;
+  }
+  return false;
 }
 
-mc_status WeightStore::extra_target(const char* what, const char* weight_name, Slot** slot) {
-  auto it = slots.find(weight_name);
-  if (it == slots.end()) return fail(MC_EINVAL, "%s: unknown weight '%s'", what, weight_name);
-  Slot& s = it->second;
-  if (!s.lin || s.dst_dtype != MC_BF16 || s.pad.rows || s.perm_c || s.fixed)
-    return fail(MC_EINVAL, "%s: '%s' is no plain bf16 part of a Linear (an fp32, padded or permuted weight takes low-rank pairs at most)",
-                what, weight_name);
-  if ((s.lin->k_in % 8) != 0) return fail(MC_EINVAL, "%s '%s': in_features %d is no multiple of 8", what, weight_name, s.lin->k_in);
-  *slot = &s;
-  return MC_OK;
-}
-
-void WeightStore::release_extra(AdapterExtra& x) {
-  for (float*& q : x.p) {
+void WeightStore::release_term(AdapterTerm& t) {
+  for (void*& q : t.p) {
     if (q) release(q);
     q = nullptr;
   }
 }
 
-mc_status WeightStore::store_extra(AdapterExtra x, Slot& s, const void* const* src, const size_t* numel, int n_ops, mc_dtype dtype,
-                                   hipStream_t stream) {
-  if (dtype != MC_F32 && dtype != MC_BF16) return fail(MC_EINVAL, "adapter '%s' on '%s': operands are fp32 or bf16", x.adapter.c_str(), x.target.c_str());
-  for (int i = 0; i < n_ops; ++i)
-    if (mc_status st = alloc(&x.p[i], numel[i])) { release_extra(x); return st; }
-  bool new_base = false;
-  if (mc_status st = make_base(s, stream, &new_base)) { release_extra(x); return st; }
-  hipError_t err = hipSuccess;
-  for (int i = 0; i < n_ops && err == hipSuccess; ++i) err = launch_widen_f32(src[i], dtype == MC_F32, x.p[i], numel[i], stream);
+// in_features of a matrix that takes terms: a part of a Linear, or an fp32 matrix
+static size_t matrix_k(const Slot& s) { return s.lin ? (size_t)s.lin->k_in : s.f32_k; }
+// ... which are whole 16-byte vectors of the merge kernels: 8 bf16, 4 fp32 elements
+static mc_status check_matrix_k(const char* what, const char* name, const Slot& s) {
+  const int step = s.lin ? 8 : 4;
+  if ((matrix_k(s) % step) == 0) return MC_OK;
+  return fail(MC_EINVAL, "%s '%s': in_features %zu is no multiple of %d", what, name, matrix_k(s), step);
+}
+
+mc_status WeightStore::term_target(const char* what, const char* name, AdapterTerm::Kind kind, Slot** slot) {
+  auto it = slots.find(name);
+  if (it == slots.end()) return fail(MC_EINVAL, "%s: unknown weight '%s'", what, name);
+  Slot& s = it->second;
+  *slot = &s;
+  if (kind == AdapterTerm::DELTA) {
+    if (s.dst_dtype != MC_F32)
+      return fail(MC_EINVAL, "%s: '%s' is a bf16 matrix and takes low-rank pairs only (a full-rank delta is a checkpoint, not an adapter)",
+                  what, name);
+    if (!allow_f32_targets || s.perm_c || s.fixed) return fail(MC_EINVAL, "%s: '%s' takes no delta in this engine", what, name);
+    return MC_OK;
+  }
+  const bool part = s.lin && s.dst_dtype == MC_BF16 && !s.pad.rows && !s.perm_c && !s.fixed;
+  const bool f32_matrix = kind == AdapterTerm::PAIR && allow_f32_targets && s.dst_dtype == MC_F32 && s.f32_k > 0 && !s.perm_c && !s.fixed;
+  if (!part && !f32_matrix)
+    return fail(MC_EINVAL, "%s: '%s' is no plain bf16 part of a Linear (an fp32, padded or permuted weight takes %s)", what, name,
+                kind == AdapterTerm::PAIR ? "no adapter" : "low-rank pairs at most");
+  return kind == AdapterTerm::PAIR ? MC_OK : check_matrix_k(what, name, s);   // a pair: after its shape checks (lora_set)
+}
+
+template <class Fill>
+mc_status WeightStore::put_term(AdapterTerm t, Slot& s, const char* what, mc_dtype dtype, const size_t (&bytes)[4], Fill fill,
+                                hipStream_t stream) {
+  size_t at = terms.size(), counted = 0;
+  for (size_t i = 0; i < terms.size(); ++i) {
+    if (terms[i].target != t.target) continue;
+    if (terms[i].adapter == t.adapter && terms[i].kind == t.kind) at = i;
+    else if (terms[i].counts_with(t.kind)) ++counted;
+  }
+  if (counted + 1 > (size_t)kLoraMaxTerms)
+    return fail(MC_EINVAL, "%s '%s': more than %d adapters on one weight", what, t.target.c_str(), kLoraMaxTerms);
+  if (dtype != MC_F32 && dtype != MC_BF16) return fail(MC_EINVAL, "adapter '%s' on '%s': operands are fp32 or bf16", t.adapter.c_str(), t.target.c_str());
+  for (int i = 0; i < 4; ++i)
+    if (bytes[i] > 0)
+      if (mc_status st = alloc_bytes(&t.p[i], bytes[i])) { release_term(t); return st; }
+  bool new_base = false;   // the first term on this Linear (this fp32 parameter): its pristine copy
+  if (mc_status st = make_base(s, stream, &new_base)) { release_term(t); return st; }
+  const hipError_t err = fill(t);
   if (err != hipSuccess) {
-    release_extra(x);
+    release_term(t);
     if (new_base) drop_base(s);
-    return fail(MC_EHIP, "adapter '%s' on '%s': %s", x.adapter.c_str(), x.target.c_str(), hipGetErrorString(err));
+    return fail(MC_EHIP, "%s '%s': %s", what, t.target.c_str(), hipGetErrorString(err));
   }
-  size_t at = extras.size();
-  for (size_t i = 0; i < extras.size(); ++i)
-    if (extras[i].target == x.target && extras[i].adapter == x.adapter && extras[i].kind == x.kind) at = i;
-  if (at < extras.size()) {  // replaced: the old copies go (hipFree waits for a merge that may still read them)
-    release_extra(extras[at]);
-    extras[at] = x;
+  if (at < terms.size()) {  // replaced, in its place: the old copies go (hipFree waits for a merge that may still read them)
+    release_term(terms[at]);
+    terms[at] = t;
   } else {
-    extras.push_back(x);
+    terms.push_back(t);
   }
-  lora_scales.emplace(x.adapter, 1.f);
-  lora_dirty.insert(x.target);
+  lora_scales.emplace(t.adapter, 1.f);
+  lora_dirty.insert(t.target);
   return MC_OK;
+}
+
+mc_status WeightStore::lora_set(const char* adapter, const char* weight_name, const void* down_dev, const int64_t* down_shape,
+                                const void* up_dev, const int64_t* up_shape, mc_dtype dtype, float factor, hipStream_t stream) {
+  if (!adapter || !weight_name || !down_dev || !down_shape || !up_dev || !up_shape) return fail(MC_EINVAL, "null argument");
+  if (down_shape[0] <= 0 || down_shape[0] > (1 << 20) || down_shape[1] <= 0 || up_shape[0] <= 0 || up_shape[1] != down_shape[0])
+    return fail(MC_EINVAL, "LoRA '%s': down [%lld, %lld] and up [%lld, %lld] share no rank", weight_name, (long long)down_shape[0],
+                (long long)down_shape[1], (long long)up_shape[0], (long long)up_shape[1]);
+  return lora_set(adapter, weight_name, down_dev, (size_t)down_shape[0] * down_shape[1], up_dev, (size_t)up_shape[0] * up_shape[1], dtype,
+                  (int)down_shape[0], factor, stream);
+}
+
+mc_status WeightStore::lora_set(const char* adapter, const char* weight_name, const void* down_dev, size_t down_numel,
+                                const void* up_dev, size_t up_numel, mc_dtype dtype, int rank, float factor, hipStream_t stream) {
+  Slot* s = nullptr;
+  MC_TRY(term_target("LoRA", weight_name, AdapterTerm::PAIR, &s));
+  if (dtype != MC_F32 && dtype != MC_BF16) return fail(MC_EINVAL, "LoRA '%s': down / up are fp32 or bf16", weight_name);
+  const size_t k = matrix_k(*s), rows = s->numel / k;
+  if (rank <= 0) return fail(MC_EINVAL, "LoRA '%s': rank %d", weight_name, rank);
+  if (down_numel != (size_t)rank * k || up_numel != rows * (size_t)rank)
+    return fail(MC_EINVAL, "LoRA '%s': down has %zu elements, up %zu; rank %d wants [%d, %zu] = %zu and [%zu, %d] = %zu", weight_name,
+                down_numel, up_numel, rank, rank, k, (size_t)rank * k, rows, rank, rows * (size_t)rank);
+  MC_TRY(check_matrix_k("LoRA", weight_name, *s));
+  AdapterTerm t;
+  t.adapter = adapter; t.target = weight_name; t.kind = AdapterTerm::PAIR; t.factor = factor;
+  t.rank = rank; t.rank_pad = (int)align_up(rank, kLoraRankStep);
+  const size_t bytes[4] = {lora_packed_elems(rows, t.rank_pad) * sizeof(bf16_t), lora_packed_elems(k, t.rank_pad) * sizeof(bf16_t), 0, 0};
+  return put_term(t, *s, "LoRA", dtype, bytes, [&](const AdapterTerm& n) {
+    hipError_t err = launch_lora_pack(up_dev, dtype == MC_F32, rank, 1, (int)rows, rank, n.rank_pad, (bf16_t*)n.p[0], stream);
+    if (err == hipSuccess) err = launch_lora_pack(down_dev, dtype == MC_F32, 1, (long)k, (int)k, rank, n.rank_pad, (bf16_t*)n.p[1], stream);
+    return err;
+  }, stream);
+}
+
+mc_status WeightStore::lora_set_delta(const char* adapter, const char* param_name, const void* delta_dev, size_t numel, mc_dtype dtype,
+                                      hipStream_t stream) {
+  if (!adapter || !param_name || !delta_dev) return fail(MC_EINVAL, "null argument");
+  Slot* s = nullptr;
+  MC_TRY(term_target("LoRA", param_name, AdapterTerm::DELTA, &s));
+  if (dtype != MC_F32) return fail(MC_EINVAL, "LoRA '%s': a delta must be given as fp32", param_name);
+  if (numel != s->numel) return fail(MC_EINVAL, "LoRA '%s': a delta of %zu elements, %zu expected", param_name, numel, s->numel);
+  AdapterTerm t;
+  t.adapter = adapter; t.target = param_name; t.kind = AdapterTerm::DELTA;
+  const size_t bytes[4] = {numel * sizeof(float), 0, 0, 0};
+  return put_term(t, *s, "LoRA", dtype, bytes, [&](const AdapterTerm& n) {
+    return hipMemcpyAsync(n.p[0], delta_dev, numel * sizeof(float), hipMemcpyDeviceToDevice, stream);
+  }, stream);
+}
+
+// ---- Kronecker and Hadamard terms, DoRA magnitudes
+mc_status WeightStore::put_widened(AdapterTerm t, Slot& s, const char* what, const void* const* src, const size_t* numel, int n_ops,
+                                   mc_dtype dtype, hipStream_t stream) {
+  size_t bytes[4] = {0, 0, 0, 0};
+  for (int i = 0; i < n_ops; ++i) bytes[i] = numel[i] * sizeof(float);
+  return put_term(t, s, what, dtype, bytes, [&](const AdapterTerm& n) {
+    hipError_t err = hipSuccess;
+    for (int i = 0; i < n_ops && err == hipSuccess; ++i) err = launch_widen_f32(src[i], dtype == MC_F32, (float*)n.p[i], numel[i], stream);
+    return err;
+  }, stream);
 }
 
 mc_status WeightStore::lora_set_kron(const char* adapter, const char* weight_name, const void* w1_dev, const int64_t* w1_shape,
                                      const void* w2_dev, const int64_t* w2_shape, mc_dtype dtype, float factor, hipStream_t stream) {
   if (!adapter || !weight_name || !w1_dev || !w1_shape || !w2_dev || !w2_shape) return fail(MC_EINVAL, "null argument");
   Slot* s = nullptr;
-  MC_TRY(extra_target("LoKr", weight_name, &s));
-  const size_t k = (size_t)s->lin->k_in, rows = s->numel / k;
+  MC_TRY(term_target("LoKr", weight_name, AdapterTerm::KRON, &s));
+  const size_t k = matrix_k(*s), rows = s->numel / k;
   const int64_t lim = 1 << 30;
   for (const int64_t v : {w1_shape[0], w1_shape[1], w2_shape[0], w2_shape[1]})
     if (v < 1 || v > lim)
       return fail(MC_EINVAL, "LoKr '%s': factor shapes [%lld, %lld] and [%lld, %lld]", weight_name, (long long)w1_shape[0],
                   (long long)w1_shape[1], (long long)w2_shape[0], (long long)w2_shape[1]);
-  const int r1 = (int)w1_shape[0], c1 = (int)w1_shape[1], r2 = (int)w2_shape[0], c2 = (int)w2_shape[1];
-  if ((size_t)r1 * (size_t)r2 != rows || (size_t)c1 * (size_t)c2 != k)
-    return fail(MC_EINVAL, "LoKr '%s': [%d, %d] (x) [%d, %d] is no factorisation of [%zu, %zu]", weight_name, r1, c1, r2, c2, rows, k);
-  if (other_terms(adapter, weight_name, AdapterExtra::KRON) + 1 > (size_t)kLoraMaxTerms)
-    return fail(MC_EINVAL, "LoKr '%s': more than %d adapters on one weight", weight_name, kLoraMaxTerms);
-  AdapterExtra x;
-  x.adapter = adapter; x.target = weight_name; x.kind = AdapterExtra::KRON; x.factor = factor;
-  x.r1 = r1; x.c1 = c1; x.r2 = r2; x.c2 = c2;
+  AdapterTerm t;
+  t.adapter = adapter; t.target = weight_name; t.kind = AdapterTerm::KRON; t.factor = factor;
+  t.r1 = (int)w1_shape[0]; t.c1 = (int)w1_shape[1]; t.r2 = (int)w2_shape[0]; t.c2 = (int)w2_shape[1];
+  if ((size_t)t.r1 * (size_t)t.r2 != rows || (size_t)t.c1 * (size_t)t.c2 != k)
+    return fail(MC_EINVAL, "LoKr '%s': [%d, %d] (x) [%d, %d] is no factorisation of [%zu, %zu]", weight_name, t.r1, t.c1, t.r2, t.c2, rows, k);
   const void* src[2] = {w1_dev, w2_dev};
-  const size_t numel[2] = {(size_t)r1 * c1, (size_t)r2 * c2};
-  return store_extra(x, *s, src, numel, 2, dtype, stream);
+  const size_t numel[2] = {(size_t)t.r1 * t.c1, (size_t)t.r2 * t.c2};
+  return put_widened(t, *s, "LoKr", src, numel, 2, dtype, stream);
 }
 
 mc_status WeightStore::lora_set_hada(const char* adapter, const char* weight_name, const void* u1_dev, const int64_t* u_shape,
@@ -314,162 +344,119 @@ mc_status WeightStore::lora_set_hada(const char* adapter, const char* weight_nam
                                      float factor, hipStream_t stream) {
   if (!adapter || !weight_name || !u1_dev || !u_shape || !d1_dev || !d_shape || !u2_dev || !d2_dev) return fail(MC_EINVAL, "null argument");
   Slot* s = nullptr;
-  MC_TRY(extra_target("LoHa", weight_name, &s));
-  const size_t k = (size_t)s->lin->k_in, rows = s->numel / k;
+  MC_TRY(term_target("LoHa", weight_name, AdapterTerm::HADA, &s));
+  const size_t k = matrix_k(*s), rows = s->numel / k;
   if (u_shape[1] < 1 || u_shape[1] > (1 << 20) || d_shape[0] != u_shape[1])
     return fail(MC_EINVAL, "LoHa '%s': [%lld, %lld] and [%lld, %lld] share no rank", weight_name, (long long)u_shape[0],
                 (long long)u_shape[1], (long long)d_shape[0], (long long)d_shape[1]);
-  const int rank = (int)u_shape[1];
   if (u_shape[0] != (int64_t)rows || d_shape[1] != (int64_t)k)
     return fail(MC_EINVAL, "LoHa '%s': factors for a [%lld, %lld] weight, the weight is [%zu, %zu]", weight_name, (long long)u_shape[0],
                 (long long)d_shape[1], rows, k);
-  if (other_terms(adapter, weight_name, AdapterExtra::HADA) + 1 > (size_t)kLoraMaxTerms)
-    return fail(MC_EINVAL, "LoHa '%s': more than %d adapters on one weight", weight_name, kLoraMaxTerms);
-  AdapterExtra x;
-  x.adapter = adapter; x.target = weight_name; x.kind = AdapterExtra::HADA; x.factor = factor; x.rank = rank;
+  AdapterTerm t;
+  t.adapter = adapter; t.target = weight_name; t.kind = AdapterTerm::HADA; t.factor = factor; t.rank = (int)u_shape[1];
   const void* src[4] = {u1_dev, d1_dev, u2_dev, d2_dev};
-  const size_t numel[4] = {rows * (size_t)rank, (size_t)rank * k, rows * (size_t)rank, (size_t)rank * k};
-  return store_extra(x, *s, src, numel, 4, dtype, stream);
+  const size_t up = rows * (size_t)t.rank, down = (size_t)t.rank * k;
+  const size_t numel[4] = {up, down, up, down};
+  return put_widened(t, *s, "LoHa", src, numel, 4, dtype, stream);
 }
 
 mc_status WeightStore::lora_set_magnitude(const char* adapter, const char* weight_name, const void* mag_dev, size_t numel, mc_dtype dtype,
                                           hipStream_t stream) {
   if (!adapter || !weight_name || !mag_dev) return fail(MC_EINVAL, "null argument");
   Slot* s = nullptr;
-  MC_TRY(extra_target("DoRA", weight_name, &s));
-  const size_t rows = s->numel / (size_t)s->lin->k_in;
+  MC_TRY(term_target("DoRA", weight_name, AdapterTerm::MAGNITUDE, &s));
+  const size_t rows = s->numel / matrix_k(*s);
   if (numel != rows) return fail(MC_EINVAL, "DoRA '%s': a magnitude of %zu elements, %zu output rows", weight_name, numel, rows);
-  for (const AdapterExtra& o : extras)
-    if (o.kind == AdapterExtra::MAGNITUDE && o.target == weight_name && o.adapter != adapter)
+  for (const AdapterTerm& o : terms)
+    if (o.kind == AdapterTerm::MAGNITUDE && o.target == weight_name && o.adapter != adapter)
       return fail(MC_EINVAL, "DoRA '%s': adapter '%s' brings a magnitude, adapter '%s' already has one on this weight (one magnitude "
                              "normalises a weight)", weight_name, adapter, o.adapter.c_str());
-  AdapterExtra x;
-  x.adapter = adapter; x.target = weight_name; x.kind = AdapterExtra::MAGNITUDE;
+  AdapterTerm t;
+  t.adapter = adapter; t.target = weight_name; t.kind = AdapterTerm::MAGNITUDE;
   const void* src[1] = {mag_dev};
-  return store_extra(x, *s, src, &numel, 1, dtype, stream);
-}
-
-mc_status WeightStore::lora_set_delta(const char* adapter, const char* param_name, const void* delta_dev, size_t numel, mc_dtype dtype,
-                                      hipStream_t stream) {
-  auto it = slots.find(param_name);
-  if (it == slots.end()) return fail(MC_EINVAL, "LoRA: unknown weight '%s'", param_name);
-  Slot& s = it->second;
-  if (s.dst_dtype != MC_F32)
-    return fail(MC_EINVAL, "LoRA: '%s' is a bf16 matrix and takes low-rank pairs only (a full-rank delta is a checkpoint, not an adapter)",
-                param_name);
-  if (!allow_f32_targets || s.perm_c || s.fixed) return fail(MC_EINVAL, "LoRA: '%s' takes no delta in this engine", param_name);
-  if (dtype != MC_F32) return fail(MC_EINVAL, "LoRA '%s': a delta must be given as fp32", param_name);
-  if (numel != s.numel) return fail(MC_EINVAL, "LoRA '%s': a delta of %zu elements, %zu expected", param_name, numel, s.numel);
-  size_t at = deltas.size(), on_target = 0;
-  for (size_t i = 0; i < deltas.size(); ++i) {
-    if (deltas[i].target != param_name) continue;
-    if (deltas[i].adapter == adapter) at = i;
-    else ++on_target;
-  }
-  if (on_target + 1 > (size_t)kLoraMaxTerms)
-    return fail(MC_EINVAL, "LoRA '%s': more than %d adapters on one weight", param_name, kLoraMaxTerms);
-  LoraDelta d;
-  d.adapter = adapter; d.target = param_name;
-  MC_TRY(alloc(&d.delta, numel));
-  bool new_base = false;
-  if (mc_status st = make_base(s, stream, &new_base)) { release(d.delta); return st; }
-  hipError_t err = hipMemcpyAsync(d.delta, delta_dev, numel * 4, hipMemcpyDeviceToDevice, stream);
-  if (err != hipSuccess) {
-    release(d.delta);
-    if (new_base) drop_base(s);
-    return fail(MC_EHIP, "LoRA '%s': %s", param_name, hipGetErrorString(err));
-  }
-  if (at < deltas.size()) {
-    release(deltas[at].delta);
-    deltas[at] = d;
-  } else {
-    deltas.push_back(d);
-  }
-  lora_scales.emplace(adapter, 1.f);
-  lora_dirty.insert(param_name);
-  return MC_OK;
+  return put_widened(t, *s, "DoRA", src, &numel, 1, dtype, stream);
 }
 
 mc_status WeightStore::lora_scale(const char* adapter, float scale) {
+  if (!adapter) return fail(MC_EINVAL, "null argument");
   auto it = lora_scales.find(adapter);
   if (it == lora_scales.end()) return fail(MC_EINVAL, "LoRA: unknown adapter '%s'", adapter);
   if (it->second == scale) return MC_OK;
   it->second = scale;
-  for (const LoraPair& p : lora)
-    if (p.adapter == adapter) lora_dirty.insert(p.target);
-  for (const LoraDelta& d : deltas)
-    if (d.adapter == adapter) lora_dirty.insert(d.target);
-  for (const AdapterExtra& x : extras)
-    if (x.adapter == adapter) lora_dirty.insert(x.target);
+  for (const AdapterTerm& t : terms)
+    if (t.adapter == adapter) lora_dirty.insert(t.target);
   return MC_OK;
 }
 
 mc_status WeightStore::lora_remove(const char* adapter) {
   if (adapter && !lora_scales.count(adapter)) return fail(MC_EINVAL, "LoRA: unknown adapter '%s'", adapter);
-  std::vector<LoraPair> kept;
-  for (const LoraPair& p : lora) {
-    if (adapter && p.adapter != adapter) { kept.push_back(p); continue; }
-    lora_dirty.insert(p.target);
-    release(p.up); release(p.down_t);
+  std::vector<AdapterTerm> kept;
+  for (AdapterTerm& t : terms) {
+    if (adapter && t.adapter != adapter) { kept.push_back(t); continue; }
+    lora_dirty.insert(t.target);
+    release_term(t);
   }
-  lora.swap(kept);
-  std::vector<LoraDelta> kept_d;
-  for (const LoraDelta& d : deltas) {
-    if (adapter && d.adapter != adapter) { kept_d.push_back(d); continue; }
-    lora_dirty.insert(d.target);
-    release(d.delta);
-  }
-  deltas.swap(kept_d);
-  std::vector<AdapterExtra> kept_x;
-  for (AdapterExtra& x : extras) {
-    if (adapter && x.adapter != adapter) { kept_x.push_back(x); continue; }
-    lora_dirty.insert(x.target);
-    release_extra(x);
-  }
-  extras.swap(kept_x);
+  terms.swap(kept);
   if (adapter) lora_scales.erase(adapter);
   else lora_scales.clear();
   return MC_OK;
+}
+
+// ---- apply
+struct TermArrays {
+  LoraTerm pairs[kLoraMaxTerms];
+  KronTerm krons[kLoraMaxTerms];
+  HadaTerm hadas[kLoraMaxTerms];
+  const float* deltas[kLoraMaxTerms];
+  float delta_scales[kLoraMaxTerms];
+  int n = 0, nk = 0, nh = 0, nd = 0;
+  const float* magnitude = nullptr;   // at most one per weight (lora_set_magnitude)
+};
+
+void WeightStore::gather(const std::string& name, TermArrays& a) const {
+  for (const AdapterTerm& t : terms) {
+    if (t.target != name) continue;
+    const float scale = lora_scales.at(t.adapter), m = scale * t.factor;
+    if (t.kind == AdapterTerm::MAGNITUDE) {
+      if (scale != 0.f) a.magnitude = t.f32(0);
+    } else if (m == 0.f) {
+      continue;
+    } else if (t.kind == AdapterTerm::PAIR) {
+      a.pairs[a.n++] = LoraTerm{(const bf16_t*)t.p[0], (const bf16_t*)t.p[1], t.rank_pad, m};
+    } else if (t.kind == AdapterTerm::DELTA) {
+      a.deltas[a.nd] = t.f32(0);
+      a.delta_scales[a.nd++] = m;
+    } else if (t.kind == AdapterTerm::KRON) {
+      a.krons[a.nk++] = KronTerm{t.f32(0), t.f32(1), t.r1, t.c1, t.r2, t.c2, m};
+    } else {
+      a.hadas[a.nh++] = HadaTerm{t.f32(0), t.f32(1), t.f32(2), t.f32(3), t.rank, m};
+    }
+  }
 }
 
 // an fp32 parameter: the pairs of a matrix first (base -> live), then the deltas (base, or that result, -> live)
 mc_status WeightStore::apply_f32(const std::string& name, Slot& s, hipStream_t stream) {
   float* live = (float*)s.dst + s.off;
   if (!s.f32_base) return MC_OK;   // set before its first term and never touched: live is the value
-  LoraTerm terms[kLoraMaxTerms];
-  const float* dl[kLoraMaxTerms];
-  float ds[kLoraMaxTerms];
-  int n = 0, m = 0;
-  bool any = false;
-  for (const LoraPair& p : lora) {
-    if (p.target != name) continue;
-    any = true;
-    const float mult = lora_scales.at(p.adapter) * p.factor;
-    if (mult != 0.f) terms[n++] = LoraTerm{p.up, p.down_t, p.rank_pad, mult};
-  }
-  for (const LoraDelta& d : deltas) {
-    if (d.target != name) continue;
-    any = true;
-    const float mult = lora_scales.at(d.adapter);
-    if (mult != 0.f) { dl[m] = d.delta; ds[m] = mult; ++m; }
-  }
+  TermArrays a;
+  gather(name, a);
   hipError_t err = hipSuccess;
-  if (n > 0) {
+  if (a.n > 0) {
     const size_t k = s.f32_k;
-    err = launch_lora_merge_f32(s.f32_base, (long)k, live, (long)k, (int)(s.numel / k), (int)k, terms, n, stream);
-    if (err == hipSuccess && m > 0) err = launch_param_delta(live, live, s.numel, dl, ds, m, stream);
-  } else if (m > 0) {
-    err = launch_param_delta(s.f32_base, live, s.numel, dl, ds, m, stream);
+    err = launch_lora_merge_f32(s.f32_base, (long)k, live, (long)k, (int)(s.numel / k), (int)k, a.pairs, a.n, stream);
+    if (err == hipSuccess && a.nd > 0) err = launch_param_delta(live, live, s.numel, a.deltas, a.delta_scales, a.nd, stream);
+  } else if (a.nd > 0) {
+    err = launch_param_delta(s.f32_base, live, s.numel, a.deltas, a.delta_scales, a.nd, stream);
   } else {
     err = hipMemcpyAsync(live, s.f32_base, s.numel * 4, hipMemcpyDeviceToDevice, stream);
   }
   if (err != hipSuccess) return fail(MC_EHIP, "LoRA merge of '%s': %s", name.c_str(), hipGetErrorString(err));
-  if (!any) drop_base(s);   // no adapter left: live is the base again, bit for bit
+  if (!base_in_use(s)) drop_base(s);   // no adapter left: live is the base again, bit for bit
   return MC_OK;
 }
 
 mc_status WeightStore::lora_apply(hipStream_t stream, int* merged) {
-  std::set<Linear*> touched;
+  std::vector<Slot*> touched;
   if (merged) *merged = 0;
   while (!lora_dirty.empty()) {
     const std::string name = *lora_dirty.begin();
@@ -482,56 +469,29 @@ mc_status WeightStore::lora_apply(hipStream_t stream, int* merged) {
     }
     Linear& l = *s.lin;
     const size_t k = l.k_in, rows = s.numel / k;
-    LoraTerm terms[kLoraMaxTerms];
-    int n = 0;
-    for (const LoraPair& p : lora) {
-      const float m = lora_scales.at(p.adapter) * p.factor;
-      if (p.target != name || m == 0.f) continue;
-      terms[n++] = LoraTerm{p.up, p.down_t, p.rank_pad, m};
-    }
-    KronTerm krons[kLoraMaxTerms];
-    HadaTerm hadas[kLoraMaxTerms];
-    int nk = 0, nh = 0;
-    const float* magnitude = nullptr;   // at most one per weight (lora_set_magnitude)
-    for (const AdapterExtra& x : extras) {
-      if (x.target != name) continue;
-      const float scale = lora_scales.at(x.adapter), m = scale * x.factor;
-      if (x.kind == AdapterExtra::MAGNITUDE) {
-        if (scale != 0.f) magnitude = x.p[0];
-      } else if (m != 0.f && x.kind == AdapterExtra::KRON) {
-        krons[nk++] = KronTerm{x.p[0], x.p[1], x.r1, x.c1, x.r2, x.c2, m};
-      } else if (m != 0.f) {
-        hadas[nh++] = HadaTerm{x.p[0], x.p[1], x.p[2], x.p[3], x.rank, m};
-      }
-    }
-    if (nk + nh > 0 || magnitude) {  // the general merge, over an fp32 image of the part that lives for this launch only
+    TermArrays a;
+    gather(name, a);
+    if (a.nk + a.nh > 0 || a.magnitude) {  // the general merge, over an fp32 image of the part that lives for this launch only
       float* scratch = nullptr;
       hipError_t err = hipMalloc((void**)&scratch, rows * k * sizeof(float));
       if (err != hipSuccess) return fail(MC_ENOMEM, "adapter merge of '%s': hipMalloc(%zu) failed: %s", name.c_str(), rows * k * sizeof(float), hipGetErrorString(err));
-      err = launch_adapter_merge(l.w_base + s.off, (long)k, l.w + s.off, (long)k, (int)rows, (int)k, terms, n, krons, nk, hadas, nh,
-                                 magnitude, scratch, stream);
+      err = launch_adapter_merge(l.w_base + s.off, (long)k, l.w + s.off, (long)k, (int)rows, (int)k, a.pairs, a.n, a.krons, a.nk, a.hadas,
+                                 a.nh, a.magnitude, scratch, stream);
       if (err == hipSuccess) err = hipStreamSynchronize(stream);
       (void)hipFree(scratch);
       if (err != hipSuccess) return fail(MC_EHIP, "adapter merge of '%s': %s", name.c_str(), hipGetErrorString(err));
-    } else if (n == 0) {
+    } else if (a.n == 0) {
       HIP_TRY(hipMemcpyAsync(l.w + s.off, l.w_base + s.off, s.numel * 2, hipMemcpyDeviceToDevice, stream));
     } else {
-      hipError_t err = launch_lora_merge(l.w_base + s.off, (long)k, l.w + s.off, (long)k, (int)rows, (int)k, terms, n, stream);
+      hipError_t err = launch_lora_merge(l.w_base + s.off, (long)k, l.w + s.off, (long)k, (int)rows, (int)k, a.pairs, a.n, stream);
       if (err != hipSuccess) return fail(MC_EHIP, "LoRA merge of '%s': %s", name.c_str(), hipGetErrorString(err));
     }
     MC_TRY(requantise(s, stream));
-    touched.insert(&l);
+    touched.push_back(&s);
     lora_dirty.erase(name);
   }
-  for (Linear* l : touched) {  // no adapter left on any part: w is the base again, bit for bit
-    bool live = false;
-    for (const LoraPair& p : lora) live = live || slots.at(p.target).lin == l;
-    for (const AdapterExtra& x : extras) live = live || slots.at(x.target).lin == l;
-    if (!live) {
-      release(l->w_base);  // hipFree waits for the copies above
-      l->w_base = nullptr;
-    }
-  }
+  for (Slot* s : touched)   // no adapter left on any part of the Linear: w is the base again, bit for bit
+    if (s->lin->w_base && !base_in_use(*s)) drop_base(*s);   // hipFree waits for the copies above
   return MC_OK;
 }
 

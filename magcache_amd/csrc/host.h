@@ -85,31 +85,23 @@ struct Slot {  // one named parameter
   bool fixed = false;         // takes no adapter whatever its layout (the Wan patch embedders)
 };
 
-// One adapter's low-rank pair on one weight slot, as the merge kernel reads it: bf16 copies owned by the store in the
-// kernel's operand order (ops.h: LoraTerm), the rank zero-padded to the kernel's step
-struct LoraPair {
+// One adapter's term of one kind on one weight slot: device copies owned by the store, as the merge launches read them
+// (ops.h: LoraTerm, KronTerm, HadaTerm, launch_param_delta).  (adapter, target, kind) names a term.
+struct AdapterTerm {
+  enum Kind { PAIR, DELTA, KRON, HADA, MAGNITUDE };
   std::string adapter, target;
-  bf16_t* up = nullptr;      // rows of the part x rank_pad, packed
-  bf16_t* down_t = nullptr;  // k_in x rank_pad (down transposed), packed
-  int rank_pad = 0;
-  float factor = 1.f;        // alpha / rank of the target
+  Kind kind = PAIR;
+  float factor = 1.f;   // alpha / rank of the target (PAIR), the term's own factor (KRON, HADA); 1 for a DELTA and a MAGNITUDE
+  // PAIR: up [rows x rank_pad], down_t [k_in x rank_pad], packed bf16 with the rank zero-padded to the kernel's step
+  // DELTA: numel fp32 | KRON: w1, w2 fp32 | HADA: u1, d1, u2, d2 fp32 | MAGNITUDE: g [rows] fp32
+  void* p[4] = {nullptr, nullptr, nullptr, nullptr};
+  int rank_pad = 0, rank = 0, r1 = 0, c1 = 0, r2 = 0, c2 = 0;
+  const float* f32(int i) const { return (const float*)p[i]; }
+  // what the limit of kLoraMaxTerms counts together: the deltas of an fp32 parameter | the pairs, Kronecker and Hadamard
+  // terms of a matrix; a magnitude never counts
+  bool counts_with(Kind k) const { return kind != MAGNITUDE && k != MAGNITUDE && (kind == DELTA) == (k == DELTA); }
 };
-// One adapter's additive delta on one fp32 parameter: an fp32 copy owned by the store
-struct LoraDelta {
-  std::string adapter, target;
-  float* delta = nullptr;
-};
-
-// One adapter's Kronecker (LoKr) or Hadamard (LoHa) term, or its DoRA magnitude, on one bf16 part of a Linear: fp32 copies
-// owned by the store, as launch_adapter_merge reads them
-struct AdapterExtra {
-  enum Kind { KRON, HADA, MAGNITUDE };
-  std::string adapter, target;
-  Kind kind = KRON;
-  float* p[4] = {nullptr, nullptr, nullptr, nullptr};   // KRON: w1, w2; HADA: u1, d1, u2, d2; MAGNITUDE: g [rows]
-  int rank = 0, r1 = 0, c1 = 0, r2 = 0, c2 = 0;
-  float factor = 1.f;
-};
+struct TermArrays;   // host.cpp: the launch arrays of one target
 
 struct WeightStore {
   std::map<std::string, Slot> slots;
@@ -138,11 +130,16 @@ struct WeightStore {
   // ---- LoRA adapters, merged into the live weight: w = bf16(w_base + sum_j scale_j factor_j up_j down_j) per touched part, in the
   // order the pairs were set.  Host bookkeeping + launches on the caller's stream; they may allocate and free (never inside a
   // forward, never under stream capture).  The forward reads the same pointers as ever.
+  // Every lora_* call below is the whole body of its C entry point on either engine (mc_lora_* / mc_mmdit_lora_*): a null
+  // argument is MC_EINVAL, shapes are the 2-D shapes the C calls take.
   // `weight_name`: a bf16 part of a Linear with no pad and no perm_c; down [rank, k_in], up [rows of the part, rank], fp32 or bf16.
   // The first pair on a Linear makes its base copy; setting (adapter, weight_name) again replaces the pair.  A new adapter
   // starts at scale 1.
   mc_status lora_set(const char* adapter, const char* weight_name, const void* down_dev, size_t down_numel, const void* up_dev,
                      size_t up_numel, mc_dtype dtype, int rank, float factor, hipStream_t stream);
+  // the same from the shapes: down_shape [rank, k_in] and up_shape [rows, rank] must share the rank
+  mc_status lora_set(const char* adapter, const char* weight_name, const void* down_dev, const int64_t* down_shape, const void* up_dev,
+                     const int64_t* up_shape, mc_dtype dtype, float factor, hipStream_t stream);
   // With allow_f32_targets `weight_name` may also be an fp32 matrix (Slot::f32_k): it keeps its own pristine fp32 copy and is
   // rebuilt as base + sum_j ... by launch_lora_merge_f32, with no rounding step.
   // lora_set_delta (allow_f32_targets only): p = base + sum_j scale_j delta_j on an fp32 parameter -- a bias (that of a part of
@@ -158,8 +155,6 @@ struct WeightStore {
   // magnitude, is rebuilt by launch_adapter_merge (ops.h states the arithmetic) with an fp32 scratch of the part's size that
   // the apply allocates and frees; a part with live pairs only keeps launch_lora_merge.
   // lora_set_kron: m * kron(w1 [r1, c1], w2 [r2, c2]) with r1 r2 = rows of the part and c1 c2 = in_features.
-  // The shapes are the 2-D shapes the C calls take (mc_lora_set_kron / _set_hada pass their arguments through); a null argument
-  // is MC_EINVAL.
   mc_status lora_set_kron(const char* adapter, const char* weight_name, const void* w1_dev, const int64_t* w1_shape, const void* w2_dev,
                           const int64_t* w2_shape, mc_dtype dtype, float factor, hipStream_t stream);
   // lora_set_hada: m * (u1 d1) * (u2 d2) element-wise, u1 and u2 [rows, rank] (u_shape), d1 and d2 [rank, in_features] (d_shape)
@@ -195,18 +190,32 @@ struct WeightStore {
   mc_status make_base(Slot& s, hipStream_t stream, bool* made);
   void drop_base(Slot& s);
   mc_status apply_f32(const std::string& name, Slot& s, hipStream_t stream);
-  // the slot of a Kronecker / Hadamard term or a magnitude (`what` names the kind in the error text), or MC_EINVAL naming the weight
-  mc_status extra_target(const char* what, const char* weight_name, Slot** slot);
-  // pairs, Kronecker and Hadamard terms on `weight_name` other than the (adapter, kind) being set; kind < 0: a pair
-  size_t other_terms(const char* adapter, const char* weight_name, int kind) const;
-  // `n_ops` operands of `numel[i]` elements copied into fresh fp32 allocations, the entry stored (replacing the one of the same
-  // adapter, weight and kind), the base copy made and the weight marked dirty
-  mc_status store_extra(AdapterExtra x, Slot& s, const void* const* src, const size_t* numel, int n_ops, mc_dtype dtype,
-                        hipStream_t stream);
-  void release_extra(AdapterExtra& x);
-  std::vector<AdapterExtra> extras;           // in the order they were set, like the pairs
-  std::vector<LoraPair> lora;                 // in the order they were set: the term order of a merge
-  std::vector<LoraDelta> deltas;              // likewise
+  // The slot a term of kind `kind` may go on (`what` names the kind in the error text), or MC_EINVAL naming the weight:
+  // KRON, HADA, MAGNITUDE: a plain bf16 part of a Linear | PAIR: that, or with allow_f32_targets an fp32 matrix |
+  // DELTA: with allow_f32_targets an fp32 parameter.  A matrix's in_features are a multiple of 8 (bf16) / 4 (fp32): checked
+  // here, for a pair by lora_set after its shape checks (one function, host.cpp: check_matrix_k).
+  mc_status term_target(const char* what, const char* name, AdapterTerm::Kind kind, Slot** slot);
+  // The one way a term gets into `terms`.  Refuses a term beyond kLoraMaxTerms counted ones on the target
+  // (AdapterTerm::counts_with), then operands that are neither fp32 nor bf16; allocates t.p[i] of bytes[i] (0: none), makes the
+  // base copy of `s`, has `fill` launch the copies into t.p, then replaces the term of the same (adapter, target, kind) in place, freeing its copies, or appends;
+  // the adapter is known from then on (scale 1 if new) and the target dirty.  A refusal or failure leaves terms, scales, the
+  // dirty set and the base copies as they were.
+  template <class Fill>
+  mc_status put_term(AdapterTerm t, Slot& s, const char* what, mc_dtype dtype, const size_t (&bytes)[4], Fill fill, hipStream_t stream);
+  // KRON, HADA, MAGNITUDE: `n_ops` fp32 or bf16 operands of numel[i] elements, widened into the term's fp32 copies
+  mc_status put_widened(AdapterTerm t, Slot& s, const char* what, const void* const* src, const size_t* numel, int n_ops,
+                        mc_dtype dtype, hipStream_t stream);
+  void release_term(AdapterTerm& t);   // frees whatever copies it holds
+  // does a term still need the pristine copy of `s` (a Linear's is shared by its parts)
+  bool base_in_use(const Slot& s) const;
+  // the launch arrays of `name`: its terms of each kind in list order, a term with multiplier scale * factor == 0 left out; the
+  // magnitude is live while its adapter's scale is not 0
+  void gather(const std::string& name, TermArrays& a) const;
+  // Every adapter's terms, in the order they were set; a replaced term keeps its position.  THE ORDERING INVARIANT: the launch
+  // arrays of a merge are the live terms of each kind on the target in this list's order -- pairs, then Kronecker terms, then
+  // Hadamard terms, as ops.h states the arithmetic of launch_adapter_merge; on an fp32 parameter the deltas follow the pairs.
+  // fp32 sums depend on that order, so merged weights stay bit-identical only while gather() filters this one list by kind.
+  std::vector<AdapterTerm> terms;
   std::map<std::string, float> lora_scales;   // adapter -> scale
   std::set<std::string> lora_dirty;           // weight slots to merge again
 };

@@ -695,12 +695,7 @@ mc_status mc_mmdit_lora_set(mc_mmdit* e, const char* adapter, const char* weight
                             const int64_t* down_shape, const void* up_dev, const int64_t* up_shape, mc_dtype dtype, float factor,
                             mc_stream stream) {
   MC_TRY(lora_entry(e, "mc_mmdit_lora_set"));
-  if (!adapter || !weight_name || !down_dev || !down_shape || !up_dev || !up_shape) return fail(MC_EINVAL, "null argument");
-  if (down_shape[0] <= 0 || down_shape[0] > (1 << 20) || down_shape[1] <= 0 || up_shape[0] <= 0 || up_shape[1] != down_shape[0])
-    return fail(MC_EINVAL, "LoRA '%s': down [%lld, %lld] and up [%lld, %lld] share no rank", weight_name, (long long)down_shape[0],
-                (long long)down_shape[1], (long long)up_shape[0], (long long)up_shape[1]);
-  return e->weights.lora_set(adapter, weight_name, down_dev, (size_t)down_shape[0] * down_shape[1], up_dev,
-                             (size_t)up_shape[0] * up_shape[1], dtype, (int)down_shape[0], factor, (hipStream_t)stream);
+  return e->weights.lora_set(adapter, weight_name, down_dev, down_shape, up_dev, up_shape, dtype, factor, (hipStream_t)stream);
 }
 
 mc_status mc_mmdit_lora_set_kron(mc_mmdit* e, const char* adapter, const char* weight_name, const void* w1_dev,
@@ -726,7 +721,6 @@ mc_status mc_mmdit_lora_set_magnitude(mc_mmdit* e, const char* adapter, const ch
 
 mc_status mc_mmdit_lora_scale(mc_mmdit* e, const char* adapter, float scale) {
   MC_TRY(lora_entry(e, "mc_mmdit_lora_scale"));
-  if (!adapter) return fail(MC_EINVAL, "null argument");
   return e->weights.lora_scale(adapter, scale);
 }
 

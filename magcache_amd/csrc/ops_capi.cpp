@@ -368,12 +368,26 @@ mc_status mc_op_ip_attention(const void* q, long ldq, const float* wq, float eps
   return MC_OK;
 }
 
+// One low-rank pair of a merge op in scratch memory: the packed bf16 copies of up [rows, rank] and down [rank, K] the kernels
+// read (ops.h: launch_lora_pack), each from a 256-byte boundary.  Advances *off by the bytes of both; ws != null: packs them at
+// ws + *off first and writes the kernel's term.
+static hipError_t pack_pair(const void* down, const void* up, int rank, float scale, int rows, int K, char* ws, size_t* off,
+                            mc::LoraTerm* term, hipStream_t stream) {
+  const int rank_pad = (int)mc::align_up(rank, mc::kLoraRankStep);
+  const size_t up_bytes = mc::align_up(mc::lora_packed_elems(rows, rank_pad) * 2, 256), at = *off;
+  *off += up_bytes + mc::align_up(mc::lora_packed_elems(K, rank_pad) * 2, 256);
+  if (!ws) return hipSuccess;
+  *term = mc::LoraTerm{(bf16_t*)(ws + at), (bf16_t*)(ws + at + up_bytes), rank_pad, scale};
+  hipError_t err = mc::launch_lora_pack(up, 0, rank, 1, rows, rank, rank_pad, (bf16_t*)(ws + at), stream);
+  if (err == hipSuccess) err = mc::launch_lora_pack(down, 0, 1, K, K, rank, rank_pad, (bf16_t*)(ws + at + up_bytes), stream);
+  return err;
+}
+
 size_t mc_op_lora_merge_scratch(int rows, int K, const mc_lora_term* terms, int n_terms) {
   size_t bytes = 0;
   for (int j = 0; terms && j < n_terms; ++j) {
     if (terms[j].rank < 1 || rows < 1 || K < 1) return 0;
-    const size_t rank_pad = mc::align_up(terms[j].rank, mc::kLoraRankStep);
-    bytes += mc::align_up(mc::lora_packed_elems(rows, rank_pad) * 2, 256) + mc::align_up(mc::lora_packed_elems(K, rank_pad) * 2, 256);
+    (void)pack_pair(nullptr, nullptr, terms[j].rank, 0.f, rows, K, nullptr, &bytes, nullptr, nullptr);   // sizes only
   }
   return bytes;
 }
@@ -402,16 +416,8 @@ static mc_status op_lora_merge(bool f32, const void* base, long ld_base, void* o
   mc::LoraTerm t[MC_LORA_MAX_TERMS];
   hipError_t err = hipSuccess;
   size_t off = 0;
-  for (int j = 0; j < n_terms && err == hipSuccess; ++j) {
-    const int rank = terms[j].rank, rank_pad = (int)mc::align_up(rank, mc::kLoraRankStep);
-    bf16_t* up = (bf16_t*)(ws + off);
-    off += mc::align_up(mc::lora_packed_elems(rows, rank_pad) * 2, 256);
-    bf16_t* down_t = (bf16_t*)(ws + off);
-    off += mc::align_up(mc::lora_packed_elems(K, rank_pad) * 2, 256);
-    t[j] = mc::LoraTerm{up, down_t, rank_pad, terms[j].scale};
-    err = mc::launch_lora_pack(terms[j].up, 0, rank, 1, rows, rank, rank_pad, up, stream);
-    if (err == hipSuccess) err = mc::launch_lora_pack(terms[j].down, 0, 1, K, K, rank, rank_pad, down_t, stream);
-  }
+  for (int j = 0; j < n_terms && err == hipSuccess; ++j)
+    err = pack_pair(terms[j].down, terms[j].up, terms[j].rank, terms[j].scale, rows, K, ws, &off, &t[j], stream);
   if (err == hipSuccess)
     err = f32 ? mc::launch_lora_merge_f32((const float*)base, ld_base, (float*)out, ld_out, rows, K, t, n_terms, stream)
               : mc::launch_lora_merge((const bf16_t*)base, ld_base, (bf16_t*)out, ld_out, rows, K, t, n_terms, stream);
@@ -440,8 +446,7 @@ size_t mc_op_adapter_merge_scratch(int rows, int K, const mc_adapter_term* terms
   for (int j = 0; terms && j < n_terms; ++j) {
     if (terms[j].kind != MC_ADAPTER_PAIR) continue;
     if (terms[j].rank < 1) return 0;
-    const size_t rank_pad = mc::align_up(terms[j].rank, mc::kLoraRankStep);
-    bytes += mc::align_up(mc::lora_packed_elems(rows, rank_pad) * 2, 256) + mc::align_up(mc::lora_packed_elems(K, rank_pad) * 2, 256);
+    (void)pack_pair(nullptr, nullptr, terms[j].rank, 0.f, rows, K, nullptr, &bytes, nullptr, nullptr);   // sizes only
   }
   return bytes;
 }
@@ -493,15 +498,8 @@ mc_status mc_op_adapter_merge(const void* base, long ld_base, void* out, long ld
       krons[nk++] = mc::KronTerm{(const float*)t.a, (const float*)t.b, t.r1, t.c1, t.r2, t.c2, t.scale};
     } else if (t.kind == MC_ADAPTER_HADA) {
       hadas[nh++] = mc::HadaTerm{(const float*)t.a, (const float*)t.b, (const float*)t.c, (const float*)t.d, t.rank, t.scale};
-    } else {   // a = down [rank, K], b = up [rows, rank], bf16: packed as mc_op_lora_merge packs them
-      const int rank_pad = (int)mc::align_up(t.rank, mc::kLoraRankStep);
-      bf16_t* up = (bf16_t*)(ws + off);
-      off += mc::align_up(mc::lora_packed_elems(rows, rank_pad) * 2, 256);
-      bf16_t* down_t = (bf16_t*)(ws + off);
-      off += mc::align_up(mc::lora_packed_elems(K, rank_pad) * 2, 256);
-      pairs[np++] = mc::LoraTerm{up, down_t, rank_pad, t.scale};
-      err = mc::launch_lora_pack(t.b, 0, t.rank, 1, rows, t.rank, rank_pad, up, stream);
-      if (err == hipSuccess) err = mc::launch_lora_pack(t.a, 0, 1, K, K, t.rank, rank_pad, down_t, stream);
+    } else {   // a = down [rank, K], b = up [rows, rank], bf16
+      err = pack_pair(t.a, t.b, t.rank, t.scale, rows, K, ws, &off, &pairs[np++], stream);
     }
   }
   if (err == hipSuccess)
