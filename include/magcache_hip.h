@@ -514,7 +514,11 @@ void mc_nearest_interp(const double* src, int src_len, double* dst, int target_l
 
 /* ---- single ops, exported for parity tests and micro-benchmarks --------------------------------
  * gemm: C[M,N] = A[M,K] . W[N,K]^T  bf16 in, fp32 accumulate; epi: 0 bf16(+bias) 1 gelu_tanh->bf16
- *       2 X += gate*bf16(acc+bias)  3 as 2 and R = X - X0  4 embed (X fp32, X0 bf16)  5 fp32 store */
+ *       2 X += gate*bf16(acc+bias)  3 as 2 and R = X - X0  4 embed (X fp32, X0 bf16)  5 fp32 store
+ *       MC_EINVAL, nothing launched and nothing written, unless: M > 0, N % 4 == 0, K % 64 == 0; A and W non-null and 16-byte
+ *       aligned with lda, ldw >= K and % 8 == 0; bias and gate null or 16-byte aligned; every buffer the epilogue reads or
+ *       writes non-null, its leading dimension >= N and % 4 == 0, bf16 buffers 8-byte and fp32 buffers 16-byte aligned (the
+ *       same holds for the other gemm_bf16 forms below; the contract is stated once, at gemm_bf16_args_ok in csrc/ops.h) */
 mc_status mc_op_gemm_bf16(const void* A_dev, long lda, const void* W_dev, long ldw, const float* bias_dev, int M,
                           int N, int K, int epi, void* Cb_dev, long ldc, float* X_dev, long ldx,
                           const float* gate_dev, const void* X0_dev, long ldx0, float* R_dev, long ldr,

@@ -194,8 +194,8 @@ hipError_t launch_t(const GemmParams& p, hipStream_t stream) {
 }  // namespace
 
 hipError_t launch_gemm_bf16_small(const GemmParams& p, int epi, hipStream_t stream) {
-  if (p.M <= 0 || p.N <= 0 || p.K <= 0 || (p.K % BK) != 0 || (p.N % 4) != 0) return hipErrorInvalidValue;
-  if ((p.lda % 8) != 0 || (p.ldw % 8) != 0) return hipErrorInvalidValue;
+  static_assert(BK == 64, "gemm_bf16_args_ok (ops.h) states K % 64 == 0");
+  if (!gemm_bf16_args_ok(p, epi)) return hipErrorInvalidValue;
   switch (epi) {
     case EPI_BF16: return launch_t<EPI_BF16>(p, stream);
     case EPI_GELU_BF16: return launch_t<EPI_GELU_BF16>(p, stream);
@@ -274,12 +274,14 @@ int gemm_bf16_kernel_for(const GemmParams& p, int epi) {
 }
 
 hipError_t launch_gemm_bf16(const GemmParams& p, int epi, hipStream_t stream) {
-  if (p.gate_stride != 0 && !gemm_gate_table_ok(p)) return hipErrorInvalidValue;
+  // the argument contract (ops.h), before any dispatch: the two-launch forms below must not run their first half and then
+  // refuse the second
+  if (!gemm_bf16_args_ok(p, epi)) return hipErrorInvalidValue;
   if (p.m_split > 0) {
     // two Linears over two row ranges: one gemm_bf16_v2 launch where that kernel can do it, otherwise the two launches
     if (p.m_split >= p.M || !p.W_b) return hipErrorInvalidValue;
     const bool one = (g_gemm_kernel == 0 || g_gemm_kernel == 4) && p.K >= 1024 && gemm_bf16_v2_supported(p) &&
-                     gemm_bf16_v2_rowsplit_ok(p, epi);
+                     gemm_bf16_v2_rowsplit_ok(p, epi) && gemm_bf16_v2_epi_ok(p, epi);
     if (one) {
       const int slices = gemm_splitk_slices(p, epi);
       return slices > 1 ? launch_gemm_bf16_v2_splitk(p, epi, slices, stream) : launch_gemm_bf16_v2(p, epi, stream);

@@ -733,22 +733,28 @@ static bool v2_row_gates_ok(const GemmParams& p) {
   return gemm_gate_table_ok(p) && (size_t)(p.gate_sets - 1) * (size_t)p.gate_stride * 4 + TB * 4 < (1ull << 31);
 }
 
+// the row-major bf16 epilogues store 16 bytes per lane (raw_buffer_store_b128 at column 8 c16 of a row)
+static bool v2_bf16_rows_ok(const bf16_t* c, long ldc) { return ((uintptr_t)c & 15) == 0 && (ldc % 8) == 0; }
+
 bool gemm_bf16_v2_epi_ok(const GemmParams& p, int epi) {
   switch (epi) {
-    case EPI_BF16: case EPI_GELU_BF16: case EPI_F32: return true;
+    case EPI_BF16: case EPI_GELU_BF16: return v2_bf16_rows_ok(p.Cb, p.ldc);
+    case EPI_F32: return true;
     case EPI_RESID_GATE: return v2_row_gates_ok(p);
     case EPI_RESID_CAPTURE:
       return p.X0 && p.R && (size_t)TB * (size_t)p.ldr * 4 < (1ull << 31) && v2_row_gates_ok(p);
     case EPI_BF16_GELU_SPLIT:
-      return p.n_split > 0 && p.n_split < p.N && (p.n_split % TB) == 0 && p.Cb2 && (size_t)TB * (size_t)p.ldc2 * 4 < (1ull << 31);
+      return p.n_split > 0 && p.n_split < p.N && (p.n_split % TB) == 0 && p.Cb2 && (size_t)TB * (size_t)p.ldc2 * 4 < (1ull << 31) &&
+             v2_bf16_rows_ok(p.Cb, p.ldc) && v2_bf16_rows_ok(p.Cb2, p.ldc2);
     default: return false;
   }
 }
 
 hipError_t launch_gemm_bf16_v2(const GemmParams& p, int epi, hipStream_t stream) {
-  if (!gemm_bf16_v2_supported(p)) return hipErrorInvalidValue;
+  if (!gemm_bf16_args_ok(p, epi) || !gemm_bf16_v2_supported(p)) return hipErrorInvalidValue;
   if (p.m_split != 0 && !gemm_bf16_v2_rowsplit_ok(p, epi)) return hipErrorInvalidValue;
   if (!v2_row_gates_ok(p)) return hipErrorInvalidValue;   // the per-token epilogues read both gate vectors, or a whole table
+  if ((epi == EPI_BF16 || epi == EPI_GELU_BF16) && !v2_bf16_rows_ok(p.Cb, p.ldc)) return hipErrorInvalidValue;
   const bool sets = p.gate_sel && p.gate_stride != 0;
   switch (epi) {
     case EPI_BF16: return launch_v2_t<EPI_BF16>(p, stream);
@@ -762,8 +768,7 @@ hipError_t launch_gemm_bf16_v2(const GemmParams& p, int epi, hipStream_t stream)
       return p.gate_sel ? launch_v2_t<EPI_RESID_CAPTURE_SEL>(p, stream) : launch_v2_t<EPI_RESID_CAPTURE>(p, stream);
     case EPI_F32: return launch_v2_t<EPI_F32>(p, stream);
     case EPI_BF16_GELU_SPLIT:
-      if (p.n_split <= 0 || p.n_split >= p.N || (p.n_split % TB) != 0 || !p.Cb2 || (size_t)TB * (size_t)p.ldc2 * 4 >= (1ull << 31))
-        return hipErrorInvalidValue;
+      if (!gemm_bf16_v2_epi_ok(p, epi)) return hipErrorInvalidValue;
       return launch_v2_t<EPI_BF16_GELU_SPLIT>(p, stream);
     default: return hipErrorInvalidValue;
   }
@@ -795,7 +800,7 @@ static int splitk_choose(int M, int N, int K, int epi, size_t ws_bytes, bool unl
 }
 
 int gemm_splitk_slices(const GemmParams& p, int epi) {
-  if (!p.splitk_ws || p.gate_sel || !gemm_bf16_v2_supported(p)) return 1;
+  if (!p.splitk_ws || ((uintptr_t)p.splitk_ws & 15) != 0 || p.gate_sel || !gemm_bf16_v2_supported(p)) return 1;
   return splitk_choose(p.M, p.N, p.K, epi, p.splitk_ws_bytes, false);
 }
 
@@ -806,7 +811,10 @@ size_t gemm_splitk_ws_need(int M, int N, int K, int epi) {
 
 hipError_t launch_gemm_bf16_v2_splitk(const GemmParams& p, int epi, int slices, hipStream_t stream) {
   if (p.m_split != 0 && !gemm_bf16_v2_rowsplit_ok(p, epi)) return hipErrorInvalidValue;
-  if (!gemm_bf16_v2_supported(p) || slices < 2 || !p.splitk_ws || p.K % (slices * 128) != 0 || p.K / slices < 256 ||
+  if (!gemm_bf16_args_ok(p, epi) || (epi != EPI_BF16 && epi != EPI_GELU_BF16 && epi != EPI_RESID_GATE && epi != EPI_RESID_CAPTURE))
+    return hipErrorInvalidValue;   // ... before the partial launch, not after it
+  if (!gemm_bf16_v2_supported(p) || slices < 2 || !p.splitk_ws || ((uintptr_t)p.splitk_ws & 15) != 0 || p.K % (slices * 128) != 0 ||
+      p.K / slices < 256 ||
       (size_t)slices * ((p.M + TB - 1) / TB) * (p.N / TB) * TB * TB * sizeof(float) > p.splitk_ws_bytes)
     return hipErrorInvalidValue;
   if (epi == EPI_RESID_CAPTURE && (!p.X0 || !p.R)) return hipErrorInvalidValue;

@@ -79,6 +79,44 @@ struct GemmParams {
 inline bool gemm_gate_table_ok(const GemmParams& p) {
   return p.gate_sel && p.gate && p.gate_sets >= 1 && p.gate_sets <= 64 && p.gate_stride >= p.N && (p.gate_stride % 4) == 0;
 }
+// The argument contract of the bf16 GEMM, stated once: launch_gemm_bf16 (before any dispatch) and the launchers of the shipped
+// kernels (_small, _v2, _v2_splitk) return hipErrorInvalidValue, with nothing launched and nothing written, unless it holds.
+//   shape     M > 0, N > 0 and % 4 == 0 (an epilogue handles a quad of 4 columns), K > 0 and % 64 == 0
+//   operands  A [M, K] and W [N, K] (W_b too when m_split > 0) non-null and 16-byte aligned, lda and ldw >= K and % 8 == 0:
+//             every kernel fetches them 16 bytes at a time.  Only rows [0, M) / [0, N) and columns [0, K) are read.
+//   vectors   bias, bias_b, gate, gate2, gate_b: null or 16-byte aligned (read as one 16-byte quad per 4 columns); a gate table
+//             as gemm_gate_table_ok; gate_sel with a gate and no table needs gate2
+//   per epilogue, what it reads and writes -- non-null, a leading dimension >= N and % 4 == 0, and the quad's alignment:
+//             EPI_BF16, _GELU_BF16, _GELU_ERF_BF16, _SILU_BF16   Cb (8 bytes: a quad of bf16)
+//             EPI_RESID_GATE, EPI_F32                             X (16 bytes: a quad of fp32)
+//             EPI_RESID_CAPTURE                                   X, X0 (8), R (16)
+//             EPI_EMBED                                           X, X0out (8)
+//             EPI_BF16_GELU_SPLIT                                 0 < n_split < N and % 4 == 0; Cb with ldc >= n_split, Cb2 with
+//                                                                 ldc2 >= N - n_split (8 each)
+//             anything else (the internal values included)        refused
+//   Nothing outside rows [0, M) x columns [0, N) (of the widths above) of an output is written, whatever its leading dimension.
+// gemm_bf16_v2 stores bf16 rows 16 bytes at a time (its row-major epilogues): a Cb / Cb2 that is not 16-byte aligned or whose
+// leading dimension is no multiple of 8 is legal and runs on the 128x128 kernel instead (gemm_bf16_v2_epi_ok), like every
+// other form that kernel lacks.  A split-K workspace that is not 16-byte aligned is not used.
+inline bool gemm_bf16_args_ok(const GemmParams& p, int epi) {
+  auto al = [](const void* q, uintptr_t a) { return ((uintptr_t)q & (a - 1)) == 0; };
+  auto out = [&](const void* q, long ld, long width, uintptr_t a) { return q && al(q, a) && ld >= width && (ld % 4) == 0; };
+  if (p.M <= 0 || p.N <= 0 || p.K <= 0 || (p.N % 4) != 0 || (p.K % 64) != 0) return false;
+  if (!p.A || !p.W || !al(p.A, 16) || !al(p.W, 16) || (p.lda % 8) != 0 || (p.ldw % 8) != 0 || p.lda < p.K || p.ldw < p.K) return false;
+  if (!al(p.bias, 16) || !al(p.gate, 16) || !al(p.gate2, 16)) return false;
+  if (p.m_split > 0 && (!p.W_b || !al(p.W_b, 16) || !al(p.bias_b, 16) || !al(p.gate_b, 16))) return false;
+  if (p.gate_stride != 0 ? !gemm_gate_table_ok(p) : (p.gate_sel && p.gate && !p.gate2)) return false;
+  switch (epi) {
+    case EPI_BF16: case EPI_GELU_BF16: case EPI_GELU_ERF_BF16: case EPI_SILU_BF16: return out(p.Cb, p.ldc, p.N, 8);
+    case EPI_RESID_GATE: case EPI_F32: return out(p.X, p.ldx, p.N, 16);
+    case EPI_RESID_CAPTURE: return out(p.X, p.ldx, p.N, 16) && out(p.X0, p.ldx0, p.N, 8) && out(p.R, p.ldr, p.N, 16);
+    case EPI_EMBED: return out(p.X, p.ldx, p.N, 16) && out(p.X0out, p.ldx0out, p.N, 8);
+    case EPI_BF16_GELU_SPLIT:
+      return p.n_split > 0 && p.n_split < p.N && (p.n_split % 4) == 0 && out(p.Cb, p.ldc, p.n_split, 8) &&
+             out(p.Cb2, p.ldc2, p.N - p.n_split, 8);
+    default: return false;
+  }
+}
 hipError_t launch_gemm_bf16(const GemmParams& p, int epi, hipStream_t stream);        // picks a kernel
 int gemm_bf16_kernel_for(const GemmParams& p, int epi);                               // ... this one: 1 small, 2 8-wave 256^2, 4 v2
 hipError_t launch_gemm_bf16_small(const GemmParams& p, int epi, hipStream_t stream);  // 128x128 tiles

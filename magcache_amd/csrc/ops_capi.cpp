@@ -99,7 +99,7 @@ int mc_op_gemm_bf16_kernel(int M, int N, int K, int epi) {
   if (M <= 0 || N <= 0 || K <= 0 || (K % 64) != 0 || (N % 4) != 0) return 0;
   // the operands an epilogue form needs, as the engines pass them (never dereferenced here): the dispatch asks whether
   // gemm_bf16_v2 can run THIS form (gemm_bf16_v2_epi_ok), not only the shape
-  static char dummy[16];
+  alignas(16) static char dummy[16];
   if (epi == mc::EPI_RESID_CAPTURE) { p.X0 = (const bf16_t*)dummy; p.ldx0 = N; p.R = (float*)dummy; p.ldr = N; }
   if (epi == mc::EPI_BF16_GELU_SPLIT) { p.n_split = N > 256 ? (N / 2) / 256 * 256 : 0; p.Cb2 = (bf16_t*)dummy; p.ldc2 = N; }
   return mc::gemm_bf16_kernel_for(p, epi);

@@ -16,7 +16,13 @@ at most 24 + 14 bits and is exact in any order too (asserted by the CPU test); t
 
 fp8_int_case.  e4m3 bytes of integers in [-2, 2] for A [M, K] and W [N, K], a_scale[m] = 2^((m % 5) - 2), w_scale[n] =
 2^((n % 3) - 1), bias multiples of 0.25 in [-2, 2].  Every partial sum of A W^T is an integer of magnitude <= 4 K <= 34816, the
-scales shift its exponent, the bias adds multiples of 1/4 to multiples of 1/8: acc * (sa * sw) + bias is exact in fp32."""
+scales shift its exponent, the bias adds multiples of 1/4 to multiples of 1/8: acc * (sa * sw) + bias is exact in fp32.
+
+bf16_int_case (test_gemm_bf16_exact_gpu.py).  Integers in [-8, 8] as bf16 for A [M, K] and W [N, K]: |A| |W|^T <= 64 K < 2^24 for
+every K here, so fp32 accumulation is exact in any order and under any K split; a bias of quarters keeps acc + bias within 24
+bits.  Unlike the fp8 case the sums are LARGE against bf16's 8 significant bits: most outputs are no bf16 value and a good share
+lie exactly between two, so EPI_BF16 has one right bit pattern only under round-to-nearest-even (truncation, or ties away from
+zero, differ).  Gates are powers of two: x + gate * bf16(acc + bias) is exact in fp32 as well."""
 import functools
 import math
 from types import SimpleNamespace
@@ -132,6 +138,77 @@ def fp8_int_case(M, N, K, seed=FP8_SEED):
     return SimpleNamespace(M=M, N=N, K=K, ai=ai, wi=wi, aq=aq, wq=wq, sa=sa, sw=sw, bias=bias, gate=gate, x=x, x0=x0, acc=acc,
                            c64=c64, c32=c32, cb=cb, x_gate=x.double() + gate.double() * cb.double(),
                            x_nogate=x.double() + cb.double())
+
+
+# ----------------------------------------------------------------------------- the bf16 GEMM
+# (M, N, K), the smallest shapes at which each piece of index arithmetic of the three paths changes.
+# 128 x 128 kernel: one row x one quad; N off the tile (the column clamp min(n, N - 4)); one row / one quad into a second tile
+# with 3 K steps; 3 x 4 tiles; 9 M tiles against GROUP_M = 8 (a group remainder) x 3 N tiles = 27 workgroups over 8 XCDs
+BF16_SMALL_SHAPES = [(1, 4, 64), (127, 132, 64), (129, 260, 192), (300, 388, 128), (1100, 260, 64)]
+# gemm_bf16_v2: the shortest K (4 K tiles) with one row; one row short of a tile, an odd number of K-tile pairs; one row into a
+# second M tile; 3 x 3 tiles; 9 N tiles (MC_V2_GROUP_M_MID); 32 N tiles (MC_V2_GROUP_M_WIDE) x 3 M tiles (a group remainder)
+BF16_V2_SHAPES = [(1, 256, 256), (255, 256, 384), (257, 512, 256), (700, 768, 512), (300, 2304, 256), (513, 8192, 256)]
+BF16_V2_TRIP_SHAPES = [(700, 768, 512), (257, 512, 256)]      # ... walked by 1, 2 and 4 persistent workgroups
+BF16_SPLITK_MN = [(77, 256), (300, 512), (513, 768)]          # split-K: slices 2, 3, 8 x K = 256 s, 512 s
+BF16_SPLITK_SLICES = [2, 3, 8]
+BF16_COMMON_SHAPE = (300, 512, 512)                           # a shape all three paths accept
+BF16_ROWSPLIT_SHAPES = [(513, 768, 512), (700, 768, 512), (700, 768, 1024)]
+BF16_SEED = 4242
+
+
+def bf16_all_shapes():
+    s = BF16_SMALL_SHAPES + BF16_V2_SHAPES + [BF16_COMMON_SHAPE] + BF16_ROWSPLIT_SHAPES
+    s += [(M, N, k * sl) for M, N in BF16_SPLITK_MN for sl in BF16_SPLITK_SLICES for k in (256, 512)]
+    return sorted(set(s))
+
+
+def bf16_gate_set(N, k):
+    """gate vector k of the case: 2^((n + k) % 4 - 2) -- k = 0 the gate, 1 the second gate, 0..2 the rows of the table"""
+    return torch.exp2(((torch.arange(N) + k) % 4 - 2).float())
+
+
+@functools.lru_cache(maxsize=None)
+def bf16_int_case(M, N, K, seed=BF16_SEED):
+    """-> a [M, K], w [N, K] bf16 (integers in [-8, 8]), bias [N] (multiples of 1/4 in [-2, 2]), gate / gate2 [N] and table [3, N]
+    (powers of two), sel uint8 [M] (every value of 0..2 inside every 16-row block), x [M, N] fp32 and x0 [M, N] bf16 (integers in
+    [-8, 8]); and, in fp64: acc = a w^T, c32 = acc + bias, cb = the bf16 rounding (nearest even) of c32, x_gate / x_nogate /
+    x_sel / x_sets = x + g * cb with g = gate / 1 / (sel ? gate2 : gate) / table[sel].  All CPU tensors."""
+    g = torch.Generator().manual_seed(seed + 131 * M + 7 * N + K)
+    ai = torch.randint(-8, 9, (M, K), generator=g)
+    wi = torch.randint(-8, 9, (N, K), generator=g)
+    bias = torch.randint(-8, 9, (N,), generator=g).float() * 0.25
+    x = torch.randint(-8, 9, (M, N), generator=g).float()
+    x0 = torch.randint(-8, 9, (M, N), generator=g).float().bfloat16()
+    table = torch.stack([bf16_gate_set(N, k) for k in range(3)])
+    rows = torch.arange(M)
+    sel = ((rows + rows // 16) % 3).to(torch.uint8)
+    acc = ai.double() @ wi.double().t()
+    c32 = acc + bias.double()
+    cb = torch.from_numpy(bf16_rne(c32.float().numpy())).double()
+    t64 = table.double()
+    g_sel = torch.where(sel[:, None] != 0, t64[1][None, :], t64[0][None, :])
+    return SimpleNamespace(M=M, N=N, K=K, ai=ai, wi=wi, a=ai.float().bfloat16(), w=wi.float().bfloat16(), bias=bias, gate=table[0],
+                           gate2=table[1], table=table, sel=sel, x=x, x0=x0, acc=acc, c32=c32, cb=cb,
+                           x_gate=x.double() + t64[0] * cb, x_nogate=x.double() + cb, x_sel=x.double() + g_sel * cb,
+                           x_sets=x.double() + t64[sel.long()] * cb)
+
+
+@functools.lru_cache(maxsize=None)
+def bf16_rowsplit_case(M, N, K, m_split, seed=BF16_SEED):
+    """bf16_int_case(M, N, K) whose rows [m_split, M) multiply with a second Linear: w_b / bias_b of the case seeded seed + 1 and
+    gate_b = its gate2.  -> w_b, bias_b, gate_b and the fp64 c32, cb, x_gate of all M rows"""
+    c, c2 = bf16_int_case(M, N, K, seed), bf16_int_case(M, N, K, seed + 1)
+    acc = torch.cat([c.acc[:m_split], c.ai[m_split:].double() @ c2.wi.double().t()])
+    c32 = acc + torch.cat([c.bias.double().expand(m_split, N), c2.bias.double().expand(M - m_split, N)])
+    cb = torch.from_numpy(bf16_rne(c32.float().numpy())).double()
+    g = torch.cat([c.gate.double().expand(m_split, N), c.gate2.double().expand(M - m_split, N)])
+    return SimpleNamespace(w_b=c2.w, bias_b=c2.bias, gate_b=c.gate2, c32=c32, cb=cb, x_gate=c.x.double() + g * cb)
+
+
+def bf16_ties(c32):
+    """fp64 tensor of fp32-representable values -> (share that lies exactly between two bf16 values, share that is no bf16 value)"""
+    low = c32.float().numpy().view(np.uint32) & 0xFFFF
+    return float((low == 0x8000).mean()), float((low != 0).mean())
 
 
 def gelu_tanh64(x):

@@ -81,3 +81,52 @@ def test_fp8_int_case_expected_values_are_exact(M, N, K):
     for xg in (c.x_gate, c.x_nogate):
         assert torch.equal(xg.float().double(), xg)
     assert torch.equal(c.x0.float(), c.x0.float().round())
+
+
+@pytest.mark.parametrize("M,N,K", MC.bf16_all_shapes())
+def test_bf16_int_case_expected_values_are_exact(M, N, K):
+    """what test_gemm_bf16_exact_gpu.py rests on: |A| |W|^T < 2^24 (fp32 accumulation exact in any order and under any K split),
+    acc + bias and every gated residual round-trip through fp32, the bf16 value is round-to-nearest-even of the fp32 one, and
+    the rounding mode is observable: at least 5 % ties and 40 % inexact outputs wherever there are 1000 outputs"""
+    c = MC.bf16_int_case(M, N, K)
+    assert torch.equal(c.a.double(), c.ai.double()) and torch.equal(c.w.double(), c.wi.double())      # bf16 holds the integers
+    assert int(c.ai.abs().max()) <= 8 and int(c.wi.abs().max()) <= 8
+    if M * K >= 1000:
+        assert sorted(torch.unique(c.ai).tolist()) == list(range(-8, 9))
+    bound = float((c.ai.abs().double() @ c.wi.abs().double().t()).max())
+    assert bound <= 64 * K < 2 ** 24 and float(c.acc.abs().max()) <= bound
+    assert torch.equal(c.bias * 4, (c.bias * 4).round()) and float(c.bias.abs().max()) <= 2
+    for k in range(3):
+        e = torch.log2(c.table[k])
+        assert torch.equal(e, ((torch.arange(N) + k) % 4 - 2).float())
+    assert torch.equal(c.gate, c.table[0]) and torch.equal(c.gate2, c.table[1])
+    # the selector takes every value inside every full 16-row block
+    for b in range(M // 16):
+        assert sorted(torch.unique(c.sel[16 * b:16 * b + 16]).tolist()) == [0, 1, 2]
+    assert int(c.sel.max()) <= 2
+    # exactly representable in fp32: the kernel's fp32 adds and multiplies have no rounding
+    for v in (c.acc, c.c32, c.x_gate, c.x_nogate, c.x_sel, c.x_sets):
+        assert torch.equal(v.float().double(), v)
+    assert torch.equal(c.x0.float(), c.x0.float().round()) and torch.equal(c.x, c.x.round())
+    assert torch.equal((c.x_gate - c.x0.double()).float().double(), c.x_gate - c.x0.double())     # the captured residual too
+    # torch's bf16 rounding agrees with the bit-pattern restatement, and bf16 holds the result
+    assert torch.equal(c.c32.float().bfloat16().double(), c.cb) and torch.equal(c.cb.bfloat16().double(), c.cb)
+    ties, inexact = MC.bf16_ties(c.c32)
+    print(f"M {M} N {N} K {K}: max |A||W|^T {bound:.0f}, ties {ties:.3f}, inexact {inexact:.3f}")
+    if M * N >= 1000:
+        assert ties >= 0.05 and inexact >= 0.40
+        trunc = (c.c32.float().view(torch.int32) & -65536).view(torch.float32).double()
+        assert float((trunc != c.cb).double().mean()) >= 0.20          # a truncating store differs on a fifth of the outputs
+
+
+@pytest.mark.parametrize("M,N,K", MC.BF16_ROWSPLIT_SHAPES)
+def test_bf16_rowsplit_case_is_exact_and_its_second_linear_differs(M, N, K):
+    c = MC.bf16_int_case(M, N, K)
+    for m_split in (200, 256):
+        r = MC.bf16_rowsplit_case(M, N, K, m_split)
+        for v in (r.c32, r.x_gate):
+            assert torch.equal(v.float().double(), v)
+        assert torch.equal(r.cb[:m_split], c.cb[:m_split]) and torch.equal(r.x_gate[:m_split], c.x_gate[:m_split])
+        # the wrong weight, the wrong bias or the wrong gate on the second range shows on most of its outputs
+        assert float((r.cb[m_split:] != c.cb[m_split:]).double().mean()) > 0.9
+        assert bool((r.bias_b != c.bias).any()) and bool((r.gate_b != c.gate).all())
