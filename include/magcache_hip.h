@@ -137,6 +137,13 @@ const char* mc_version(void);
  *                   producer).  Not judged on real weights; never a default.  With fp8_linear 0 | 1 it does nothing.  A
  *                   width the kernel cannot tile (an in_features that is no multiple of 256, or < 512) is MC_EINVAL at
  *                   create time, and so is a create with "mx_fp4" and "mx_fp6" both 1.
+ *   "attn_mx8"      0 (default) | 1.  Read ONCE by mc_create / mc_create_sized; the engine keeps what it read (mc_engine_attn_mx8).
+ *                   1: the self-attention of every block (VACE blocks included) runs on the MX fp8 kernel -- a pre-pass
+ *                   quantises the q, k and v columns to e4m3 with E8M0 scales per 32 elements (mc_op_attn_quantize_mx8), the
+ *                   kernel runs both products on the block-scaled fp8 matrix instruction (mc_op_attention_mx8).  A precision
+ *                   change, opt-in, never a default; cross-attention and the I2V image keys stay bf16.  Costs a workspace of
+ *                   about 3 * 33 / 32 bytes per token and channel more.  MC_EINVAL at create time on a sequence-parallel engine
+ *                   (sp_size > 1 or sp_phases).  Wan engine only.
  *   "mmdit_two_streams"  the text stream of an MM-DiT double block (FLUX / HunyuanVideo) runs on a second HIP stream next
  *                   to the image stream between a fork and a join event.  OPT-IN (default 0 = off): 1 = on, -1 = by shape
  *                   (on when the text half is at least 1/16 of the image half and the engine is not sequence parallel);
@@ -159,7 +166,8 @@ mc_status mc_create(const mc_config* cfg, mc_engine** out);
  * mc_create_sized(cfg, sizeof(mc_config) as IT knows it, out): the missing tail is taken as zeros.  History: 0.1 ends at
  * vace_in_dim, 0.2 adds fp8_linear, 0.3 no_context_cache and no_token_timesteps, 0.5 sp_phases (0.6 adds calls only: mc_pair_begin / mc_pair_end; 0.7 adds calls only: mc_geometry_bytes / mc_set_geometry,
  * mc_op_rope_axes / mc_op_rope_expand; 0.7.1 adds calls only: mc_lora_*, mc_op_lora_merge_f32, mc_op_param_delta; the MXFP4 and MXFP6 modes add calls only: mc_get_option,
- * mc_engine_mx_fp4 / _mx_fp6, mc_op_quantize_rows_mxfp4 / _mxfp6, mc_op_gemm_mxfp4 / _mxfp6); 0.8 adds token_timestep_sets (and the calls
+ * mc_engine_mx_fp4 / _mx_fp6, mc_op_quantize_rows_mxfp4 / _mxfp6, mc_op_gemm_mxfp4 / _mxfp6; the MX fp8 attention adds calls only:
+ * mc_engine_attn_mx8, mc_op_attn_quantize_mx8, mc_op_attention_mx8); 0.8 adds token_timestep_sets (and the calls
  * mc_engine_token_timestep_sets, mc_op_gemm_bf16_resid_sets); the adapter kinds add calls only: mc_lora_set_kron / _set_hada /
  * _set_magnitude, mc_op_adapter_merge / _scratch; mc_version() names the library's. */
 mc_status mc_create_sized(const mc_config* cfg, size_t cfg_bytes, mc_engine** out);
@@ -168,6 +176,8 @@ void mc_destroy(mc_engine* e);
 int mc_engine_mx_fp4(const mc_engine* e);
 /* the same for MXFP6 and the option "mx_fp6" (an engine is never both: such a create is MC_EINVAL) */
 int mc_engine_mx_fp6(const mc_engine* e);
+/* 1: this engine's self-attention runs on the MX fp8 kernel (it was created under mc_set_option("attn_mx8", 1)); else 0 */
+int mc_engine_attn_mx8(const mc_engine* e);
 size_t mc_workspace_bytes(const mc_engine* e);
 mc_status mc_set_workspace(mc_engine* e, void* ws_dev, size_t bytes);
 /* The latent grid as a property of the call (0.7).  mc_config.latent_f / _h / _w is the grid an engine STARTS with;
@@ -623,6 +633,21 @@ mc_status mc_op_attention(const void* Q_dev, long ldq, const void* K_dev, long l
                           const void* V_dev, long ldv, long v_shard_stride, void* O_dev, long ldo, int Lq_pad,
                           int n_heads, int shard_rows, int shard_valid, int n_shards, float scale,
                           mc_stream stream);
+/* MX fp8 self-attention (option "attn_mx8"; attention_mx8.hip), d = n_heads * 128.  mc_op_attn_quantize_mx8 turns the bf16 q, k
+ * and v rows into the six images mc_op_attention_mx8 reads: q_img [Lq_pad][d] e4m3 of q * scale * log2(e) and k_img [rows][d]
+ * e4m3 (rows >= valid zero), each with rows * d / 32 E8M0 scale bytes, one per (row, 32 channels) (q_sc, k_sc); vt_img [d][rows]
+ * e4m3 = V transposed per head, rows >= valid counted as zero, the keys of every 64 in the kernel's operand order, with
+ * rows * d / 32 scale bytes, one per (channel, 32 key slots) (v_sc).  Scale layouts: csrc/quant.h.  mc_op_attention_mx8: O bf16
+ * [Lq_pad][ldo] = softmax(q k^T scale) v over the first `valid` keys, from the images alone.
+ * Both refuse with MC_EINVAL, nothing launched: Lq_pad % 256 != 0, rows % 64 != 0, valid outside 1..rows, a leading dimension
+ * that is no multiple of 8 or shorter than d, an operand or image that is null or not 16-byte aligned, Lq_pad * d or rows * d
+ * >= 2^32; mc_op_attention_mx8 also n_shards != 1 and a non-null lse (one key shard, no log-sum-exp, no merge). */
+mc_status mc_op_attn_quantize_mx8(const void* Q_dev, long ldq, const void* K_dev, long ldk, const void* V_dev, long ldv, int Lq_pad,
+                                  int n_heads, int rows, int valid, float scale, void* q_img, void* q_sc, void* k_img, void* k_sc,
+                                  void* vt_img, void* v_sc, mc_stream stream);
+mc_status mc_op_attention_mx8(const void* q_img, const void* q_sc, const void* k_img, const void* k_sc, const void* vt_img,
+                              const void* v_sc, void* O_dev, long ldo, int Lq_pad, int n_heads, int rows, int valid, int n_shards,
+                              const float* lse_dev, mc_stream stream);
 /* two-phase form (sequence parallel): skip_shard >= 0 leaves that shard out; lse_out [n_heads][Lq_pad] fp32 receives
  * the log2-sum-exp of the keys visited; lse_in != NULL merges with the result already in O_dev (see
  * mc_block_attn_local) */

@@ -49,6 +49,7 @@ SIGNATURES = {
     "mc_get_option": (_i, [C.c_char_p, C.POINTER(_i)]),
     "mc_engine_mx_fp4": (_i, [_vp]),
     "mc_engine_mx_fp6": (_i, [_vp]),
+    "mc_engine_attn_mx8": (_i, [_vp]),
     "mc_engine_token_timestep_sets": (_i, [_vp]),
     "mc_create": (_i, [C.POINTER(McConfig), C.POINTER(_vp)]),
     "mc_create_sized": (_i, [C.POINTER(McConfig), _sz, C.POINTER(_vp)]),
@@ -123,6 +124,8 @@ SIGNATURES = {
     "mc_op_gemm_mxfp4": (_i, [_vp, _l, _vp, _l, _vp, _l, _vp, _l, _vp, _i, _i, _i, _i, _vp, _l, _vp, _l, _vp, _vp]),
     "mc_op_quantize_rows_mxfp6": (_i, [_vp, _i, _l, _i, _i, _vp, _l, _vp, _l, _vp]),
     "mc_op_gemm_mxfp6": (_i, [_vp, _l, _vp, _l, _vp, _l, _vp, _l, _vp, _i, _i, _i, _i, _vp, _l, _vp, _l, _vp, _vp]),
+    "mc_op_attn_quantize_mx8": (_i, [_vp, _l, _vp, _l, _vp, _l, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mc_op_attention_mx8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _vp, _vp]),
     "mc_op_attention_partial": (_i, [_vp, _l, _vp, _l, _l, _vp, _l, _l, _vp, _l, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp]),
     "mc_op_attn_merge": (_i, [_vp, _vp, _i, _vp, _l, _i, _i, _i, _vp]),
     "mc_op_ln_modulate": (_i, [_vp, _l, _vp, _l, _vp, _vp, _i, _f, _vp, _l, _vp, _l, _i, _i, _vp]),

@@ -177,6 +177,18 @@ class LoraHost:
 MX_FORMAT_OPTIONS = ("mx_fp4", "mx_fp6")
 
 
+def with_option(lib, name, request, fn):
+    """fn() with the process-wide option `name` at 1 if `request` is true (at its present value otherwise), the previous value put
+    back: for an option that a create call latches beside the element formats (the Wan engine's "attn_mx8")"""
+    prev = C.c_int(0)
+    check(lib.mc_get_option(name.encode(), C.byref(prev)))
+    try:
+        check(lib.mc_set_option(name.encode(), 1 if request else prev.value))
+        return fn()
+    finally:
+        lib.mc_set_option(name.encode(), prev.value)
+
+
 class EngineHost(LoraHost):
     """An engine handle `h` of `lib` on `device`, bound to a workspace tensor.  The subclass creates the handle, says in
     _rebound() what its Python side holds that the engine forgot with the old binding and in _release() what goes before

@@ -37,6 +37,8 @@ struct mc_engine {
   mc_config cfg;
   mc::MxFormat mx_fmt = mc::MX_E4M3;   // the element format of the MX Linears (fp8_linear 2 | 3), as mc_create latched it from the
                                        // options "mx_fp4" / "mx_fp6" (host.h: latch_mx_format)
+  bool attn_mx8 = false;               // the self-attention of every block runs on attention_mx8.hip, as mc_create latched it from
+                                       // the option "attn_mx8" (never on a sequence-parallel engine)
   int d, ffn, H, NL, L, Lr, Lp, P, rank, tok0, Kp;  // Kp = in_dim*4 padded to 64
   int ctx_rows;                                     // text_len padded to 64
   std::vector<Layer> layers;
@@ -285,6 +287,10 @@ void plan_workspace(const mc_engine* e, const Rows& rows, mc::Workspace& ws) {
   ws.add("pair_x", e->pair_capable() ? Lp * d * 4 : 256);
   ws.add("pair_cq", e->pair_capable() ? Lp * d * 2 : 256);
   if (c.token_timestep_sets) ws.add("tok_vals", 256);   // (behind the kept front: a default engine's plan is what it was)
+  if (e->attn_mx8) {   // the operand images of the MX fp8 self-attention (ops.h: AttnMx8Images): 3 Lp d 33 / 32 bytes in all
+    for (const char* name : {"mx8_q", "mx8_k", "mx8_vt"}) ws.add(name, Lp * d);
+    for (const char* name : {"mx8_qs", "mx8_ks", "mx8_vs"}) ws.add(name, Lp * d / 32);
+  }
 }
 
 // The RoPE table of the engine's grid, for this rank's rows: the per-axis values are computed on the host (the doubles of
@@ -429,6 +435,22 @@ mc_status attend(const mc_engine* e, const bf16_t* Q, long ldq, bf16_t* O, const
   HIP_TRY(mc::launch_attention_keys(Q, ldq, O, e->d, e->Lp, e->H, keys, lse_in, lse_out, s));
   return MC_OK;
 }
+// The MX fp8 form of the one-device self-attention (option "attn_mx8"): the pre-pass quantises the q, k and v columns of "qkv"
+// into the planned images, the kernel reads the images alone
+mc_status attend_mx8(const mc_engine* e, bf16_t* O, hipStream_t s) {
+  const Keys keys = qkv_keys(e);
+  mc::AttnParams a;
+  memset(&a, 0, sizeof(a));
+  a.Q = e->buf<bf16_t>("qkv"); a.ldq = keys.ld; a.K = keys.k; a.ldk = keys.ld; a.V = keys.v; a.ldv = keys.ld;
+  a.O = O; a.ldo = e->d;
+  a.Lq_pad = e->Lp; a.n_heads = e->H; a.shard_rows = keys.rows; a.shard_valid = keys.valid; a.n_shards = 1;
+  a.scale = 1.0f / std::sqrt(128.0f);   // head_dim is fixed at 128
+  const mc::AttnMx8Images im = {e->buf<uint8_t>("mx8_q"), e->buf<uint8_t>("mx8_qs"), e->buf<uint8_t>("mx8_k"),
+                                e->buf<uint8_t>("mx8_ks"), e->buf<uint8_t>("mx8_vt"), e->buf<uint8_t>("mx8_vs")};
+  HIP_TRY(mc::launch_attn_quantize_mx8(a, im, s));
+  HIP_TRY(mc::launch_attention_mx8(a, im, s));
+  return MC_OK;
+}
 // whose self-attention chain is open and how far it got (sequence parallel)
 void attn_chain_set(mc_engine* e, int layer, int launches, bool local_done, int rounds_done) {
   e->attn_layer = layer; e->attn_launches = launches; e->attn_local_done = local_done; e->attn_rounds_done = rounds_done;
@@ -455,6 +477,9 @@ int g_sp_attn_partials = 1;
 int g_mx_fp4 = 0;
 // option "mx_fp6" (0 | 1): the same latch for MXFP6 copies (W6A6, gemm_mxfp6.hip); a create call that finds both at 1 is refused
 int g_mx_fp6 = 0;
+// option "attn_mx8" (0 | 1): read once by mc_create; 1 = the engine's self-attention runs on the MX fp8 kernel (attention_mx8.hip:
+// a pre-pass quantises q, k and v, both products on the block-scaled fp8 MFMA).  The engine keeps what it read (mc_engine::attn_mx8).
+int g_attn_mx8 = 0;
 }  // namespace mc
 static int g_n_cu = 0;
 
@@ -526,6 +551,11 @@ mc_status mc_create(const mc_config* cfg, mc_engine** out) {
     MC_TRY(mc::check_mx_k(e->mx_fmt, "self_attn.q|k|v / ffn.0 / the dim x dim Linears (in_features = dim)", c.dim));
     MC_TRY(mc::check_mx_k(e->mx_fmt, "ffn.2 (in_features = ffn_dim)", c.ffn_dim));
   }
+  // option "attn_mx8" (latched here): the kernel has one key shard and no log-sum-exp, which is what the phase path needs
+  if (mc::g_attn_mx8 != 0 && e->sp)
+    return fail(MC_EINVAL, "the option \"attn_mx8\" is 1 and the engine is sequence parallel (sp_size %d%s): the MX fp8 self-attention "
+                           "kernel serves one device", e->P, c.sp_phases ? ", sp_phases" : "");
+  e->attn_mx8 = mc::g_attn_mx8 != 0;
   const mc::MxFormat fmt = e->mx_fmt;
   const mc::Quant q_big = c.fp8_linear >= 2 ? mc::QUANT_MX : c.fp8_linear == 1 ? mc::QUANT_ROW : mc::QUANT_NONE;
   const mc::Quant q_dd = c.fp8_linear == 3 ? mc::QUANT_MX : mc::QUANT_NONE;
@@ -628,6 +658,7 @@ int mc_engine_token_timestep_sets(const mc_engine* e) {
 }
 int mc_engine_mx_fp4(const mc_engine* e) { return e && e->mx_fmt == mc::MX_E2M1 ? 1 : 0; }
 int mc_engine_mx_fp6(const mc_engine* e) { return e && e->mx_fmt == mc::MX_E2M3 ? 1 : 0; }
+int mc_engine_attn_mx8(const mc_engine* e) { return e && e->attn_mx8 ? 1 : 0; }
 
 mc_status mc_set_workspace(mc_engine* e, void* ws_dev, size_t bytes) {
   if (!e) return fail(MC_EINVAL, "null argument");
@@ -1195,7 +1226,8 @@ static mc_status block_post_self(mc_engine* e, const Layer& l, const float* em, 
   // ---- self attention over the full sequence
   if (!e->sp) {
     Prof pr(e, MC_PROF_ATTN_SELF, s);
-    MC_TRY(attend(e, e->buf<bf16_t>("qkv"), 3 * d, ao, qkv_keys(e), nullptr, nullptr, s));
+    if (e->attn_mx8) MC_TRY(attend_mx8(e, ao, s));
+    else MC_TRY(attend(e, e->buf<bf16_t>("qkv"), 3 * d, ao, qkv_keys(e), nullptr, nullptr, s));
   } else {
     // whatever the caller has not attended yet (mc_block_attn_local / mc_block_attn_round): the remaining gather rounds
     attn_chain_open(e, layer);

@@ -38,6 +38,7 @@ extern int g_fp8_fused_quant;    // engine.cpp
 extern int g_sp_attn_partials;   // engine.cpp
 extern int g_mx_fp4;             // engine.cpp: read once, through latch_mx_format, by mc_create and by mc_mmdit_create / _create_sized
 extern int g_mx_fp6;             // engine.cpp: the same for MXFP6; both 1 at create time is MC_EINVAL
+extern int g_attn_mx8;           // engine.cpp: read once by mc_create -- the engine's self-attention runs on attention_mx8.hip
 extern int g_mmdit_two_streams;  // mmdit_engine.cpp
 
 // ---------------------------------------------------------------- weights

@@ -316,6 +316,22 @@ bool attention_v5_supports(const AttnParams& p);                          // K /
 hipError_t launch_attention_v3(const AttnParams& p, hipStream_t stream);  // 8 waves x 32 rows, pipelined, 32x32x16 MFMA (round 1)
 extern int g_attn_kernel;  // 0: by support (see launch_attention), 3: attention_v3.hip, 5: attention_v5.hip where it applies
 
+// ---------------------------------------------------------------- MX fp8 self-attention (attention_mx8.hip; option "attn_mx8")
+// The operand images launch_attn_quantize_mx8 writes and launch_attention_mx8 reads, d = n_heads * 128 (layouts: quant.h):
+//   q   [Lq_pad][d] e4m3 of q * scale * log2(e)      qs  Lq_pad * d / 32 E8M0 bytes, one per (row, 32 channels)
+//   k   [shard_rows][d] e4m3, rows >= valid zero     ks  shard_rows * d / 32, rows >= valid the unit scale
+//   vt  [d][shard_rows] e4m3, V transposed per head with the keys of every 64 in the order of mx8_slot_key, rows >= valid
+//       counted as zero                              vs  shard_rows * d / 32, one per (channel, 32 key slots)
+struct AttnMx8Images {
+  uint8_t *q, *qs, *k, *ks, *vt, *vs;
+};
+// Both launchers take the AttnParams of launch_attention and serve one form of it: n_shards == 1, no skip_shard_p1, no lse_in /
+// lse_out, Lq_pad % 256 == 0, shard_rows % 64 == 0, 1 <= shard_valid <= shard_rows, ldq / ldk / ldv / ldo % 8 == 0, 16-byte
+// aligned operands and images, Lq_pad * d and shard_rows * d below 2^32.  Anything else: hipErrorInvalidValue, nothing launched.
+bool attention_mx8_supports(const AttnParams& p, const AttnMx8Images& im);
+hipError_t launch_attn_quantize_mx8(const AttnParams& p, const AttnMx8Images& im, hipStream_t stream);   // bf16 Q, K, V -> the images
+hipError_t launch_attention_mx8(const AttnParams& p, const AttnMx8Images& im, hipStream_t stream);       // the images -> O (bf16)
+
 // ---------------------------------------------------------------- token-wise ops (elementwise.hip)
 // out[m,:] = bf16( LN(x[m,:]) * a + b ),  a = 1+scale (modulate) or weight (affine)
 //   mode 0: a = 1 + sc[d], b = sh[d]      (AdaLN modulate; sc/sh fp32 vectors)

@@ -136,6 +136,44 @@ mc_status mc_op_attention(const void* Q, long ldq, const void* K, long ldk, long
   return MC_OK;
 }
 
+// MX fp8 self-attention (attention_mx8.hip): the pre-pass and the kernel share one argument contract
+static const char* kAttnMx8Refusal =
+    "needs Lq_pad % 256 == 0, rows % 64 == 0, 1 <= valid <= rows, leading dimensions % 8 == 0 and >= n_heads * 128, operands and "
+    "images non-null and 16-byte aligned, Lq_pad * d and rows * d < 2^32, n_shards == 1 and no lse (one key shard, no log-sum-exp, no merge)";
+
+mc_status mc_op_attn_quantize_mx8(const void* Q, long ldq, const void* K, long ldk, const void* V, long ldv, int Lq_pad, int n_heads,
+                                  int rows, int valid, float scale, void* q_img, void* q_sc, void* k_img, void* k_sc, void* vt_img,
+                                  void* v_sc, mc_stream s) {
+  mc::AttnParams a;
+  memset(&a, 0, sizeof(a));
+  // the pre-pass writes no O: its checks see the query rows in O's place
+  a.Q = (const bf16_t*)Q; a.ldq = ldq; a.K = (const bf16_t*)K; a.ldk = ldk; a.V = (const bf16_t*)V; a.ldv = ldv;
+  a.O = (bf16_t*)Q; a.ldo = ldq;
+  a.Lq_pad = Lq_pad; a.n_heads = n_heads; a.shard_rows = rows; a.shard_valid = valid; a.n_shards = 1; a.scale = scale;
+  const mc::AttnMx8Images im = {(uint8_t*)q_img, (uint8_t*)q_sc, (uint8_t*)k_img, (uint8_t*)k_sc, (uint8_t*)vt_img, (uint8_t*)v_sc};
+  hipError_t err = mc::launch_attn_quantize_mx8(a, im, (hipStream_t)s);
+  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "attn_quantize_mx8: %s", kAttnMx8Refusal);
+  HIP_TRY(err);
+  return MC_OK;
+}
+
+mc_status mc_op_attention_mx8(const void* q_img, const void* q_sc, const void* k_img, const void* k_sc, const void* vt_img,
+                              const void* v_sc, void* O, long ldo, int Lq_pad, int n_heads, int rows, int valid, int n_shards,
+                              const float* lse, mc_stream s) {
+  mc::AttnParams a;
+  memset(&a, 0, sizeof(a));
+  // the kernel reads the images only: its checks see O in the place of the bf16 operands
+  a.Q = a.K = a.V = (const bf16_t*)O; a.ldq = a.ldk = a.ldv = ldo;
+  a.O = (bf16_t*)O; a.ldo = ldo;
+  a.Lq_pad = Lq_pad; a.n_heads = n_heads; a.shard_rows = rows; a.shard_valid = valid; a.n_shards = n_shards;
+  a.lse_in = lse;   // (the softmax scale is in the q image already)
+  const mc::AttnMx8Images im = {(uint8_t*)q_img, (uint8_t*)q_sc, (uint8_t*)k_img, (uint8_t*)k_sc, (uint8_t*)vt_img, (uint8_t*)v_sc};
+  hipError_t err = mc::launch_attention_mx8(a, im, (hipStream_t)s);
+  if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "attention_mx8: %s", kAttnMx8Refusal);
+  HIP_TRY(err);
+  return MC_OK;
+}
+
 mc_status mc_op_quantize_rows_fp8(const void* x, mc_dtype dtype, long ldx, int M, int K, void* q, long ldq, float* scale,
                                   mc_stream s) {
   hipError_t err = mc::launch_quantize_rows_fp8(dtype == MC_BF16 ? (const bf16_t*)x : nullptr,
@@ -563,6 +601,9 @@ mc_status mc_set_option(const char* key, int value) {
   } else if (k == "mx_fp6") {
     if (value != 0 && value != 1) return fail(MC_EINVAL, "mx_fp6 must be 0 (MX fp8 Linears) or 1 (MXFP6 Linears where fp8_linear is 2 or 3; read when an engine is created)");
     mc::g_mx_fp6 = value;
+  } else if (k == "attn_mx8") {
+    if (value != 0 && value != 1) return fail(MC_EINVAL, "attn_mx8 must be 0 (bf16 self-attention) or 1 (the MX fp8 self-attention kernel; read when an engine is created)");
+    mc::g_attn_mx8 = value;
   } else if (k == "attn_kernel") {
     if (value != 0 && value != 3 && value != 5)
       return fail(MC_EINVAL, "attn_kernel must be 0 (default), 3 (8 waves x 32 rows) or 5 (4 waves x 64 rows, hand-scheduled)");
@@ -587,6 +628,7 @@ mc_status mc_get_option(const char* key, int* value) {
   else if (k == "fp8_fused_quant") *value = mc::g_fp8_fused_quant;
   else if (k == "mx_fp4") *value = mc::g_mx_fp4;
   else if (k == "mx_fp6") *value = mc::g_mx_fp6;
+  else if (k == "attn_mx8") *value = mc::g_attn_mx8;
   else if (k == "attn_kernel") *value = mc::g_attn_kernel;
   else if (k == "mmdit_two_streams") *value = mc::g_mmdit_two_streams;
   else return fail(MC_EINVAL, "unknown option '%s'", key);

@@ -39,6 +39,32 @@ __device__ __forceinline__ uint8_t mx_scale_byte(int e) { return (uint8_t)(e + 1
 #define MC_MX_SCALE_ROW(row) (((row) & ~63) | (((row) & 15) << 2) | (((row) >> 4) & 3))
 __device__ __forceinline__ int mx_scale_row(int row) { return MC_MX_SCALE_ROW(row); }
 
+// ---- MX fp8 attention (attention_mx8.hip, option "attn_mx8"): the operand order of v_mfma_scale_f32_32x32x64_f8f6f4 and the
+// scale images of its pre-pass, stated once for the pre-pass and the kernel.
+// An fp8 operand of the 32x32x64 MFMA is 32 bytes per lane; lane l holds row l % 32 and, with h = l / 32, its byte p carries
+// k = 16 h + p % 16 + 32 (p / 16): two stacked K = 32 halves, as the 16x16x128 form stacks two K = 64 halves
+// (tools/ubench_mx_probe.cpp); the scale byte lane half h supplies multiplies MX block h = k 32 h .. 32 h + 31 of its row.
+constexpr int mx8_operand_k(int half, int byte) { return 16 * half + (byte & 15) + 32 * (byte >> 4); }
+// row of register r of a 32x32 accumulator in lane half h (the column is l % 32)
+constexpr int mfma32_acc_row(int half, int r) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
+// The key permutation of V^T: a lane packs the 2 x 16 probabilities of its two S^T accumulator blocks (keys as rows) as bytes
+// p = 16 kb + r of the P^T operand, so k slot s = mx8_operand_k(h, p) of the P V product holds key 32 kb + mfma32_acc_row(h, r)
+// of the 64-key tile, and V^T stores that key's value in slot s.  A 32-slot block is a 32-key block (s / 32 == key / 32).
+constexpr int mx8_slot_key(int s) {
+  const int half = (s >> 4) & 1, byte = (s & 15) | ((s >> 5) << 4);   // the inverse of mx8_operand_k
+  return 32 * (byte >> 4) + mfma32_acc_row(half, byte & 15);
+}
+// Scale images, 256 bytes per head and 64 rows (q rows, keys) / 64-key tile (V^T), so that lane l of a wave fetches the dword
+// at 4 l and op_sel picks the byte -- one load per image and tile:
+//   Q^ / K^   [head][rows / 64][h][row % 32][2 (row / 32 % 2) + c / 64]   the scale of (row, 32-channel block c / 32), h = c / 32 % 2
+//   V^T       [head][keys / 64][h][ch % 32][ch / 32]                      the scale of (channel ch, 32-slot block 2 tile + h)
+constexpr long mx8_row_scale_index(int row, int blk) {
+  return (long)(row & ~63) * 4 + (((blk & 1) * 32 + (row & 31)) * 4 + ((row >> 5) & 1) * 2 + (blk >> 1));
+}
+constexpr long mx8_v_scale_index(int ch, int slot_block) {
+  return (long)(slot_block >> 1) * 256 + (((slot_block & 1) * 32 + (ch & 31)) * 4 + (ch >> 5));
+}
+
 // four values times the inverse scale -> four e4m3 bytes, a in the lowest (two v_cvt_pk_fp8_f32).  (The products are formed
 // here, two in front of each conversion as the open-coded form had them: taken as four scaled arguments the LayerNorm
 // tails are scheduled differently -- tools/isa_same.py)

@@ -6,7 +6,7 @@ import torch
 
 from . import _lib
 from ._lib import MC_BF16, MC_F32, MC_MODE_CALIB, MC_MODE_FULL, MC_MODE_SKIP, McConfig, check
-from .adapters import EngineHost, _ptr, _stream
+from .adapters import EngineHost, _ptr, _stream, with_option
 
 WAN_T2V_1_3B = dict(dim=1536, ffn_dim=8960, freq_dim=256, num_heads=12, num_layers=30, text_len=512, in_dim=16,
                     out_dim=16, text_dim=4096, eps=1e-6)
@@ -104,12 +104,14 @@ class Engine(EngineHost):
         return parse_wan_adapter_state_dict(sd)
 
     def __init__(self, cfg, latent_grid, device="cuda:0", sp_rank=0, sp_size=1, n_branches=2, calibration=False,
-                 sp_phases=False, mx_fp4=False, mx_fp6=False):
+                 sp_phases=False, mx_fp4=False, mx_fp6=False, attn_mx8=False):
         """mx_fp4: with cfg["fp8_linear"] 2 | 3 the quantised Linears are MXFP4 (W4A4) instead of MX fp8 -- coarser, an
         opt-in speed / quality experiment, never a default.  The process-wide option "mx_fp4" is set around the create call
         only and put back; the engine keeps what it read (self.mx_fp4).
         mx_fp6 (or cfg["mx_fp6"]): the same latch for MXFP6 (W6A6, e2m3 elements: the mantissa of e4m3 at 3/4 of its bytes);
-        self.mx_fp6.  Asking for both is refused by the library."""
+        self.mx_fp6.  Asking for both is refused by the library.
+        attn_mx8 (or cfg["attn_mx8"]): the same latch for the MX fp8 self-attention kernel (q, k, v and P as e4m3 with block
+        scales: a precision change, opt-in); self.attn_mx8.  Refused by the library on a sequence-parallel engine."""
         if not torch.cuda.is_available():
             raise RuntimeError("magcache_amd.Engine needs a ROCm device; there is no CPU fallback")
         self.lib = _lib.load()
@@ -134,11 +136,15 @@ class Engine(EngineHost):
         self.sharded = sp_size > 1 or bool(sp_phases)     # driven through the phase calls (parallel.SequenceParallelForward)
         self.vace_layers, self.vace_stride = vace_geometry(cfg)
 
-        def create():
+        def create_handle():
             h = C.c_void_p()
             check(self.lib.mc_create_sized(C.byref(c), C.sizeof(c), C.byref(h)))
             return h
+
+        def create():   # "attn_mx8" is latched by the same create call as the element formats
+            return with_option(self.lib, "attn_mx8", attn_mx8 or cfg.get("attn_mx8"), create_handle)
         self._create_latching(create, {"mx_fp4": mx_fp4 or cfg.get("mx_fp4"), "mx_fp6": mx_fp6 or cfg.get("mx_fp6")}, "mc_engine_")
+        self.attn_mx8 = bool(self.lib.mc_engine_attn_mx8(self.h))
         self._bind(self.lib.mc_workspace_bytes(self.h))
         # distinct per-token timesteps a forward may carry: cfg["token_timestep_sets"] (3..64), 2 by default, 0 without them
         self.token_timestep_capacity = int(self.lib.mc_engine_token_timestep_sets(self.h))

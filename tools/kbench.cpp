@@ -1,7 +1,7 @@
 // Torch-free kernel A/B harness for the two MFMA-bound kernels at the Wan2.1-1.3B 480p shapes, through the C ABI.
 //
 //   kbench.bin <what> <rounds> <launches> libA.so [libB.so ...]
-//      what: gemm | attn | calib | all
+//      what: gemm | attn | attn_mx8 | calib | all
 //
 // Every library given on the command line is dlopen'ed privately (RTLD_LOCAL), so build variants of
 // libmagcache_hip.so (tools/build_variants.py, tools/build_v5_variants.py, tools/build_gemm_v2_variants.py) are measured INTERLEAVED IN ONE PROCESS on the same
@@ -38,6 +38,8 @@ struct Lib {
   decltype(&mc_op_gemm_bf16) gemm;
   decltype(&mc_op_attention) attn;
   decltype(&mc_op_calib_stats) calib;
+  decltype(&mc_op_attn_quantize_mx8) quant_mx8;   // null in a library older than the MX fp8 attention (attn_mx8 only)
+  decltype(&mc_op_attention_mx8) attn_mx8;
   decltype(&mc_set_option) set_option;
   decltype(&mc_last_error) last_error;
 };
@@ -326,6 +328,79 @@ static void bench_attn_keys(int Lq_pad, int H, int rounds, int launches) {
   CK(hipFree(Q)); CK(hipFree(K)); CK(hipFree(V)); CK(hipFree(O));
 }
 
+// The opt-in MX fp8 self-attention beside the bf16 kernel on the same q, k, v -- library 0 only, the three launches interleaved
+// round by round: attn (the bf16 line above), its pre-pass (quantise q, k, v: HBM-bound, GB/s of bf16 read + images written)
+// and its kernel (TF over the same 4 L^2 D).  The outputs are two precisions of one result: their relative L2 distance is printed.
+static void bench_attn_mx8(int Lq_pad, int H, int valid, int rounds, int launches) {
+  const Lib& lib = g_libs[0];
+  if (!lib.quant_mx8 || !lib.attn_mx8) {
+    fprintf(stderr, "%s: no mc_op_attention_mx8\n", lib.path.c_str());
+    exit(2);
+  }
+  const int D = H * 128;
+  const size_t n = (size_t)Lq_pad * D;
+  uint16_t *Q, *K, *V, *O, *O8;
+  uint8_t* im[6];
+  for (uint16_t** p : {&Q, &K, &V, &O, &O8}) CK(hipMalloc(p, n * 2));
+  for (int i = 0; i < 6; ++i) CK(hipMalloc(&im[i], i % 2 ? n / 32 : n));   // q, qs, k, ks, vt, vs
+  fill_bf16<<<2048, 256>>>(Q, n, 11, g_amp);
+  fill_bf16<<<2048, 256>>>(K, n, 12, g_amp);
+  fill_bf16<<<2048, 256>>>(V, n, 13, g_amp);
+  CK(hipDeviceSynchronize());
+  const float scale = 1.0f / std::sqrt(128.0f);
+  auto launch = [&](int kind) {
+    if (kind == 0) MCL(lib, lib.attn(Q, D, K, D, 0, V, D, 0, O, D, Lq_pad, H, Lq_pad, valid, 1, scale, nullptr));
+    if (kind == 1) MCL(lib, lib.quant_mx8(Q, D, K, D, V, D, Lq_pad, H, Lq_pad, valid, scale, im[0], im[1], im[2], im[3], im[4], im[5], nullptr));
+    if (kind == 2) MCL(lib, lib.attn_mx8(im[0], im[1], im[2], im[3], im[4], im[5], O8, D, Lq_pad, H, Lq_pad, valid, 1, nullptr, nullptr));
+  };
+  printf("# attn_mx8: Lq_pad=%d heads=%d valid keys=%d\n", Lq_pad, H, valid);
+  hipEvent_t a, b;
+  CK(hipEventCreate(&a));
+  CK(hipEventCreate(&b));
+  float ms = 0;
+  CK(hipEventRecord(a, nullptr));
+  do {   // ~1 s warm-up of all three
+    for (int kind = 0; kind < 3; ++kind) launch(kind);
+    CK(hipEventRecord(b, nullptr));
+    CK(hipEventSynchronize(b));
+    CK(hipEventElapsedTime(&ms, a, b));
+  } while (ms < 1000.f);
+  std::vector<double> t[3];
+  for (int r = 0; r < rounds; ++r)
+    for (int kind = 0; kind < 3; ++kind) {
+      launch(kind);
+      CK(hipEventRecord(a, nullptr));
+      for (int i = 0; i < launches; ++i) launch(kind);
+      CK(hipEventRecord(b, nullptr));
+      CK(hipEventSynchronize(b));
+      CK(hipEventElapsedTime(&ms, a, b));
+      t[kind].push_back(ms / launches);
+    }
+  const char* names[3] = {"attn (bf16)", "mx8 pre-pass", "mx8 kernel"};
+  const double work[3] = {4.0 * valid * (double)valid * D * 1e-12, (3.0 * n * 2 + 3.0 * n * 33 / 32) * 1e-9, 4.0 * valid * (double)valid * D * 1e-12};
+  double med[3];
+  for (int kind = 0; kind < 3; ++kind) {
+    std::sort(t[kind].begin(), t[kind].end());
+    med[kind] = t[kind][t[kind].size() / 2];
+    printf("%-13s median %8.4f ms %8.1f %s | min %8.4f ms\n", names[kind], med[kind], work[kind] / (med[kind] * 1e-3), kind == 1 ? "GB/s" : "TF",
+           t[kind][0]);
+  }
+  printf("mx8 kernel x%.3f, pre-pass + kernel x%.3f vs attn (bf16) (median)\n", med[0] / med[2], med[0] / (med[1] + med[2]));
+  std::vector<uint16_t> h16(n), h8(n);
+  CK(hipMemcpy(h16.data(), O, n * 2, hipMemcpyDeviceToHost));
+  CK(hipMemcpy(h8.data(), O8, n * 2, hipMemcpyDeviceToHost));
+  double num = 0, den = 0;
+  for (size_t i = 0; i < (size_t)valid * D; ++i) {
+    const double x = bf16_to_f(h16[i]), y = bf16_to_f(h8[i]);
+    num += (x - y) * (x - y);
+    den += x * x;
+  }
+  printf("  attn_mx8 vs attn (bf16): rel l2 %.3e over %d rows\n", std::sqrt(num / den), valid);
+  fflush(stdout);
+  for (void* p : {(void*)Q, (void*)K, (void*)V, (void*)O, (void*)O8}) CK(hipFree(p));
+  for (int i = 0; i < 6; ++i) CK(hipFree(im[i]));
+}
+
 // ------------------------------------------------------------------------------------- calibration statistics
 static void bench_calib(int M, int D, int rounds, int launches) {
   float *r, *rp, *stats;
@@ -353,7 +428,7 @@ static void bench_calib(int M, int D, int rounds, int launches) {
 
 int main(int argc, char** argv) {
   if (argc < 5) {
-    fprintf(stderr, "usage: kbench.bin <gemm|attn|attn_keys|calib|all> <rounds> <launches> libA.so [libB.so ...]\n");
+    fprintf(stderr, "usage: kbench.bin <gemm|attn|attn_mx8|attn_keys|calib|all> <rounds> <launches> libA.so [libB.so ...]\n");
     return 2;
   }
   if (getenv("KBENCH_AMP")) g_amp = (float)atof(getenv("KBENCH_AMP"));
@@ -370,6 +445,8 @@ int main(int argc, char** argv) {
     l.gemm = (decltype(l.gemm))dlsym(l.h, "mc_op_gemm_bf16");
     l.attn = (decltype(l.attn))dlsym(l.h, "mc_op_attention");
     l.calib = (decltype(l.calib))dlsym(l.h, "mc_op_calib_stats");
+    l.quant_mx8 = (decltype(l.quant_mx8))dlsym(l.h, "mc_op_attn_quantize_mx8");
+    l.attn_mx8 = (decltype(l.attn_mx8))dlsym(l.h, "mc_op_attention_mx8");
     l.set_option = (decltype(l.set_option))dlsym(l.h, "mc_set_option");
     l.last_error = (decltype(l.last_error))dlsym(l.h, "mc_last_error");
     if (!l.gemm || !l.attn || !l.calib || !l.set_option || !l.last_error) {
@@ -399,6 +476,7 @@ int main(int argc, char** argv) {
     bench_attn("self480p", 32768, 12, 32760, 1.0f, rounds, std::max(1, launches / 4));
     bench_attn("self480p_q6", 32768, 12, 32760, 6.0f, rounds, std::max(1, launches / 4));
   }
+  if (what == "attn_mx8") bench_attn_mx8(32768, 12, 32760, rounds, std::max(1, launches / 4));
   if (what == "attn_strided" || what == "all") bench_attn("self480p_qkv", 32768, 12, 32760, 1.0f, rounds, std::max(1, launches / 4), true);
   if (what == "attn_keys") bench_attn_keys(32768, 12, rounds, launches);
   if (what == "attn1") bench_attn("self480p", 32768, 12, 32760, 1.0f, rounds, launches);          // one shape (PMC passes)
