@@ -169,7 +169,8 @@ mc_status mc_create(const mc_config* cfg, mc_engine** out);
  * mc_engine_mx_fp4 / _mx_fp6, mc_op_quantize_rows_mxfp4 / _mxfp6, mc_op_gemm_mxfp4 / _mxfp6; the MX fp8 attention adds calls only:
  * mc_engine_attn_mx8, mc_op_attn_quantize_mx8, mc_op_attention_mx8); 0.8 adds token_timestep_sets (and the calls
  * mc_engine_token_timestep_sets, mc_op_gemm_bf16_resid_sets); the adapter kinds add calls only: mc_lora_set_kron / _set_hada /
- * _set_magnitude, mc_op_adapter_merge / _scratch; mc_version() names the library's. */
+ * _set_magnitude, mc_op_adapter_merge / _scratch; the frame-block causal self-attention adds calls only: mc_set_causal_blocks,
+ * mc_engine_causal_blocks, mc_op_attention_band; mc_version() names the library's. */
 mc_status mc_create_sized(const mc_config* cfg, size_t cfg_bytes, mc_engine** out);
 void mc_destroy(mc_engine* e);
 /* 1: this engine's quantised Linears are MXFP4 (it was created under mc_set_option("mx_fp4", 1) with fp8_linear 2 | 3); else 0 */
@@ -178,6 +179,17 @@ int mc_engine_mx_fp4(const mc_engine* e);
 int mc_engine_mx_fp6(const mc_engine* e);
 /* 1: this engine's self-attention runs on the MX fp8 kernel (it was created under mc_set_option("attn_mx8", 1)); else 0 */
 int mc_engine_attn_mx8(const mc_engine* e);
+/* Frame-block causal (and windowed) self-attention: the mask of diffusion-forcing / autoregressive Wan fine-tunes
+ * (SkyReels-V2-DF causal_block_size, CausVid / Self-Forcing style models).  frames_per_block == 0 (the default) turns it off:
+ * every launch is the one an engine that never heard of it makes.  frames_per_block >= 1: the self-attention of every block
+ * (VACE blocks included) runs on attention_band.hip with block_tokens = frames_per_block * Hp * Wp of the latent grid IN FORCE
+ * (it follows mc_set_geometry) and the given window_blocks, under the semantics stated at mc_op_attention_band.  Exact, not an
+ * approximation: the model's definition.  Cross-attention and the I2V image keys are untouched; MagCache, CFG pairs and
+ * per-frame timesteps need no change.  Between forwards only.  MC_EINVAL for a negative argument, on a sequence-parallel engine
+ * (sp_size > 1 or sp_phases: the kernel has no log-sum-exp to merge shards with) and on an "attn_mx8" engine; the error text
+ * names which.  mc_engine_causal_blocks reads the two values back (NULL outputs are skipped). */
+mc_status mc_set_causal_blocks(mc_engine* e, int frames_per_block, int window_blocks);
+mc_status mc_engine_causal_blocks(const mc_engine* e, int* frames_per_block, int* window_blocks);
 size_t mc_workspace_bytes(const mc_engine* e);
 mc_status mc_set_workspace(mc_engine* e, void* ws_dev, size_t bytes);
 /* The latent grid as a property of the call (0.7).  mc_config.latent_f / _h / _w is the grid an engine STARTS with;
@@ -633,6 +645,23 @@ mc_status mc_op_attention(const void* Q_dev, long ldq, const void* K_dev, long l
                           const void* V_dev, long ldv, long v_shard_stride, void* O_dev, long ldo, int Lq_pad,
                           int n_heads, int shard_rows, int shard_valid, int n_shards, float scale,
                           mc_stream stream);
+/* Frame-block causal / windowed self-attention (attention_band.hip): one key shard of `rows` rows (multiple of 64), the first
+ * `valid` of them keys; head_dim 128; O bf16 [Lq_pad][ldo].  The inputs are block_tokens >= 1 and window_blocks >= 0:
+ *   - query row i belongs to block b = i / block_tokens and sees the keys j with lo(b) <= j < hi(b);
+ *   - hi(b) = min((b + 1) * block_tokens, valid);
+ *   - lo(b) = 0 when window_blocks == 0, else max(0, b - window_blocks + 1) * block_tokens;
+ *   - query rows >= valid (padding) behave as rows of the last valid block: their output is finite, nothing reads it;
+ *   - every valid query sees at least its own block, so no row is empty; block_tokens >= valid is plain attention.
+ * A workgroup visits only the 64-key tiles its 128 query rows can see: a causal mask over B blocks costs about (B + 1) / (2 B)
+ * of the key tiles of the unmasked launch, a window of w blocks about w / B.  Measured on an MI355X at L = 32 760, 12 heads
+ * (DESIGN 3.1c): 0.68 x the unmasked launch's time for 21 causal blocks, 0.75 x for 7, 0.86 x for 3, 0.20 x for 21
+ * blocks with a window of 3 -- always faster, and 1.28 - 1.44 x the visited-tile ideal (the interior is not a v5-class stream).
+ * Refused with MC_EINVAL, nothing launched: Lq_pad % 256 != 0, rows % 64 != 0, valid outside 1..rows, a leading dimension that
+ * is no multiple of 8 or shorter than n_heads * 128, an operand that is null or not 16-byte aligned, block_tokens < 1,
+ * window_blocks < 0, Lq_pad * ld or rows * ld beyond 32-bit byte offsets (with a window: more than 16383 * 128 query rows). */
+mc_status mc_op_attention_band(const void* Q_dev, long ldq, const void* K_dev, long ldk, const void* V_dev, long ldv, void* O_dev,
+                               long ldo, int Lq_pad, int n_heads, int rows, int valid, int block_tokens, int window_blocks,
+                               float scale, mc_stream stream);
 /* MX fp8 self-attention (option "attn_mx8"; attention_mx8.hip), d = n_heads * 128.  mc_op_attn_quantize_mx8 turns the bf16 q, k
  * and v rows into the six images mc_op_attention_mx8 reads: q_img [Lq_pad][d] e4m3 of q * scale * log2(e) and k_img [rows][d]
  * e4m3 (rows >= valid zero), each with rows * d / 32 E8M0 scale bytes, one per (row, 32 channels) (q_sc, k_sc); vt_img [d][rows]

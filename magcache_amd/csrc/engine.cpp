@@ -39,6 +39,8 @@ struct mc_engine {
                                        // options "mx_fp4" / "mx_fp6" (host.h: latch_mx_format)
   bool attn_mx8 = false;               // the self-attention of every block runs on attention_mx8.hip, as mc_create latched it from
                                        // the option "attn_mx8" (never on a sequence-parallel engine)
+  int causal_frames = 0;                // mc_set_causal_blocks: frames per causal block of the self-attention, 0 = off (plain attention)
+  int causal_window = 0;                // ... and the blocks a query looks back over, 0 = all of them
   int d, ffn, H, NL, L, Lr, Lp, P, rank, tok0, Kp;  // Kp = in_dim*4 padded to 64
   int ctx_rows;                                     // text_len padded to 64
   std::vector<Layer> layers;
@@ -451,6 +453,21 @@ mc_status attend_mx8(const mc_engine* e, bf16_t* O, hipStream_t s) {
   HIP_TRY(mc::launch_attention_mx8(a, im, s));
   return MC_OK;
 }
+// The frame-block causal form (mc_set_causal_blocks): the same operands as attend(e, "qkv", ..., qkv_keys(e)), on
+// attention_band.hip with the block in tokens of the grid in force
+mc_status attend_band(const mc_engine* e, bf16_t* O, hipStream_t s) {
+  const Keys keys = qkv_keys(e);
+  mc::AttnParams a;
+  memset(&a, 0, sizeof(a));
+  a.Q = e->buf<bf16_t>("qkv"); a.ldq = keys.ld; a.K = keys.k; a.ldk = keys.ld; a.V = keys.v; a.ldv = keys.ld;
+  a.O = O; a.ldo = e->d;
+  a.Lq_pad = e->Lp; a.n_heads = e->H; a.shard_rows = keys.rows; a.shard_valid = keys.valid; a.n_shards = 1;
+  a.scale = 1.0f / std::sqrt(128.0f);   // head_dim is fixed at 128
+  const long block_tokens = (long)e->causal_frames * (e->cfg.latent_h / 2) * (e->cfg.latent_w / 2);
+  const mc::AttnBand band = {(int)std::min<long>(block_tokens, e->Lp), e->causal_window};   // >= valid: plain attention either way
+  HIP_TRY(mc::launch_attention_band(a, band, s));
+  return MC_OK;
+}
 // whose self-attention chain is open and how far it got (sequence parallel)
 void attn_chain_set(mc_engine* e, int layer, int launches, bool local_done, int rounds_done) {
   e->attn_layer = layer; e->attn_launches = launches; e->attn_local_done = local_done; e->attn_rounds_done = rounds_done;
@@ -659,6 +676,28 @@ int mc_engine_token_timestep_sets(const mc_engine* e) {
 int mc_engine_mx_fp4(const mc_engine* e) { return e && e->mx_fmt == mc::MX_E2M1 ? 1 : 0; }
 int mc_engine_mx_fp6(const mc_engine* e) { return e && e->mx_fmt == mc::MX_E2M3 ? 1 : 0; }
 int mc_engine_attn_mx8(const mc_engine* e) { return e && e->attn_mx8 ? 1 : 0; }
+
+mc_status mc_set_causal_blocks(mc_engine* e, int frames_per_block, int window_blocks) {
+  if (!e) return fail(MC_EINVAL, "null engine");
+  if (frames_per_block < 0 || window_blocks < 0)
+    return fail(MC_EINVAL, "mc_set_causal_blocks: frames_per_block (%d) and window_blocks (%d) must be >= 0", frames_per_block, window_blocks);
+  if (e->phase_open) return fail(MC_ESTATE, "mc_set_causal_blocks between mc_embed and mc_head");
+  if (frames_per_block != 0 && e->sp)
+    return fail(MC_EINVAL, "mc_set_causal_blocks: the engine is sequence parallel (sp_size %d%s) and the frame-block causal kernel "
+                           "has no log-sum-exp to merge key shards with", e->P, e->cfg.sp_phases ? ", sp_phases" : "");
+  if (frames_per_block != 0 && e->attn_mx8)
+    return fail(MC_EINVAL, "mc_set_causal_blocks: the engine was created under the option \"attn_mx8\" and the MX fp8 "
+                           "self-attention kernel has no mask");
+  e->causal_frames = frames_per_block;
+  e->causal_window = frames_per_block ? window_blocks : 0;
+  return MC_OK;
+}
+mc_status mc_engine_causal_blocks(const mc_engine* e, int* frames_per_block, int* window_blocks) {
+  if (!e) return fail(MC_EINVAL, "null engine");
+  if (frames_per_block) *frames_per_block = e->causal_frames;
+  if (window_blocks) *window_blocks = e->causal_window;
+  return MC_OK;
+}
 
 mc_status mc_set_workspace(mc_engine* e, void* ws_dev, size_t bytes) {
   if (!e) return fail(MC_EINVAL, "null argument");
@@ -1227,6 +1266,7 @@ static mc_status block_post_self(mc_engine* e, const Layer& l, const float* em, 
   if (!e->sp) {
     Prof pr(e, MC_PROF_ATTN_SELF, s);
     if (e->attn_mx8) MC_TRY(attend_mx8(e, ao, s));
+    else if (e->causal_frames) MC_TRY(attend_band(e, ao, s));
     else MC_TRY(attend(e, e->buf<bf16_t>("qkv"), 3 * d, ao, qkv_keys(e), nullptr, nullptr, s));
   } else {
     // whatever the caller has not attended yet (mc_block_attn_local / mc_block_attn_round): the remaining gather rounds

@@ -332,6 +332,18 @@ bool attention_mx8_supports(const AttnParams& p, const AttnMx8Images& im);
 hipError_t launch_attn_quantize_mx8(const AttnParams& p, const AttnMx8Images& im, hipStream_t stream);   // bf16 Q, K, V -> the images
 hipError_t launch_attention_mx8(const AttnParams& p, const AttnMx8Images& im, hipStream_t stream);       // the images -> O (bf16)
 
+// ---------------------------------------------------------------- frame-block causal / windowed self-attention (attention_band.hip)
+// Query row i belongs to block b = min(i, shard_valid - 1) / block_tokens and sees the keys lo(b) <= j < hi(b):
+// hi(b) = min((b + 1) block_tokens, shard_valid), lo(b) = window_blocks ? max(0, b - window_blocks + 1) block_tokens : 0.
+// Padding rows are rows of the last valid block (finite output); block_tokens >= shard_valid is plain attention.
+struct AttnBand { int block_tokens; int window_blocks; };
+// The AttnParams of launch_attention, one form of it: n_shards == 1, no skip_shard_p1, no lse_in / lse_out, Lq_pad % 256 == 0,
+// shard_rows % 64 == 0, 1 <= shard_valid <= shard_rows, ldq / ldk / ldv / ldo % 8 == 0 and >= n_heads * 128, 16-byte aligned
+// operands, block_tokens >= 1, window_blocks >= 0, Lq_pad * ld and shard_rows * ld within 32-bit byte offsets (and, with a
+// window, at most 16383 query tiles of 128 rows).  Anything else: hipErrorInvalidValue, nothing launched.
+bool attention_band_supports(const AttnParams& p, const AttnBand& b);
+hipError_t launch_attention_band(const AttnParams& p, const AttnBand& b, hipStream_t stream);
+
 // ---------------------------------------------------------------- token-wise ops (elementwise.hip)
 // out[m,:] = bf16( LN(x[m,:]) * a + b ),  a = 1+scale (modulate) or weight (affine)
 //   mode 0: a = 1 + sc[d], b = sh[d]      (AdaLN modulate; sc/sh fp32 vectors)

@@ -136,6 +136,23 @@ mc_status mc_op_attention(const void* Q, long ldq, const void* K, long ldk, long
   return MC_OK;
 }
 
+// frame-block causal / windowed self-attention (attention_band.hip)
+mc_status mc_op_attention_band(const void* Q, long ldq, const void* K, long ldk, const void* V, long ldv, void* O, long ldo, int Lq_pad,
+                               int n_heads, int rows, int valid, int block_tokens, int window_blocks, float scale, mc_stream s) {
+  mc::AttnParams a;
+  memset(&a, 0, sizeof(a));
+  a.Q = (const bf16_t*)Q; a.ldq = ldq; a.K = (const bf16_t*)K; a.ldk = ldk; a.V = (const bf16_t*)V; a.ldv = ldv;
+  a.O = (bf16_t*)O; a.ldo = ldo;
+  a.Lq_pad = Lq_pad; a.n_heads = n_heads; a.shard_rows = rows; a.shard_valid = valid; a.n_shards = 1; a.scale = scale;
+  hipError_t err = mc::launch_attention_band(a, mc::AttnBand{block_tokens, window_blocks}, (hipStream_t)s);
+  if (err == hipErrorInvalidValue)
+    return fail(MC_EINVAL, "attention_band: needs Lq_pad %% 256 == 0, rows %% 64 == 0, 1 <= valid <= rows, leading dimensions %% 8 == 0 "
+                           "and >= n_heads * 128, operands non-null and 16-byte aligned, block_tokens >= 1, window_blocks >= 0, "
+                           "Lq_pad * ld and rows * ld within 32-bit byte offsets");
+  HIP_TRY(err);
+  return MC_OK;
+}
+
 // MX fp8 self-attention (attention_mx8.hip): the pre-pass and the kernel share one argument contract
 static const char* kAttnMx8Refusal =
     "needs Lq_pad % 256 == 0, rows % 64 == 0, 1 <= valid <= rows, leading dimensions % 8 == 0 and >= n_heads * 128, operands and "

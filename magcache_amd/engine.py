@@ -192,6 +192,23 @@ class Engine(EngineHost):
         self.tokens_per_rank = self.seq_len // self.sp_size
         self._tok_t = None
 
+    # ---- frame-block causal self-attention
+    def set_causal_blocks(self, frames_per_block, window_blocks=0):
+        """Self-attention that is block-causal over latent frames (mc_set_causal_blocks): a token of frame block b attends
+        to the keys of the blocks <= b, with window_blocks >= 1 only to the last window_blocks of them -- the mask of
+        diffusion-forcing / autoregressive Wan fine-tunes.  frames_per_block = 0 turns it off (the default: plain attention,
+        the launches an engine makes that never called this).  The block follows set_geometry (frames, not tokens).
+        MagCache, CFG pairs and per-frame timesteps need no change: the mask only picks the kernel of the self-attention
+        launch.  Refused on a sharded engine and on an attn_mx8 engine."""
+        check(self.lib.mc_set_causal_blocks(self.h, int(frames_per_block), int(window_blocks)))
+
+    @property
+    def causal_blocks(self):
+        """(frames_per_block, window_blocks) in force; (0, 0) = plain attention"""
+        f, w = C.c_int(), C.c_int()
+        check(self.lib.mc_engine_causal_blocks(self.h, C.byref(f), C.byref(w)))
+        return f.value, w.value
+
     def residual(self, branch):
         """fp32 [seq_len/sp, dim] view of residual_cache[branch] (rows past the valid tokens cut off)."""
         d = self.cfg["dim"]

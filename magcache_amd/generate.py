@@ -119,6 +119,11 @@ def _parse_args(argv=None):
     p.add_argument("--attn_mx8", action="store_true",
                    help="self-attention on the opt-in MX fp8 kernel (q, k, v and the probabilities as e4m3 with block scales): a "
                         "precision change, one device only")
+    p.add_argument("--causal_block_frames", type=int, default=0, metavar="N",
+                   help="self-attention block-causal over blocks of N latent frames (diffusion-forcing / autoregressive fine-tunes); "
+                        "0 = plain attention.  One device only")
+    p.add_argument("--causal_window_blocks", type=int, default=0, metavar="W",
+                   help="with --causal_block_frames: attend to the last W blocks only (0 = all earlier blocks)")
     # accepted for command-line compatibility; they configure parts that are not in this repository
     for flag, kw in (("--offload_model", dict(type=str2bool, default=None)), ("--ulysses_size", dict(type=int, default=1)),
                      ("--ring_size", dict(type=int, default=1)), ("--t5_fsdp", dict(action="store_true")),
@@ -218,7 +223,8 @@ def generate(args):
     logging.info(f"latent grid {grid}, {grid[0] * (grid[1] // 2) * (grid[2] // 2)} tokens, {cfg['num_layers']} layers d={cfg['dim']}")
     model = M.WanModelHIP(cfg, grid, device=device, calibration=args.magcache_calibration,
                           sp_rank=layout.sp_rank if layout else 0, sp_size=layout.sp_size if layout else 1,
-                          sp_group=layout.sp_group if layout else None, attn_mx8=args.attn_mx8)
+                          sp_group=layout.sp_group if layout else None, attn_mx8=args.attn_mx8,
+                          causal_block_frames=args.causal_block_frames, causal_window_blocks=args.causal_window_blocks)
 
     files = sorted(glob.glob(os.path.join(args.ckpt_dir or "", "*.safetensors")))
     if files:

@@ -115,11 +115,16 @@ class WanModelHIP(LoraModel):
     dynamic_geometry = False
 
     def __init__(self, cfg, latent_grid, device="cuda:0", calibration=True, engine=None, sp_rank=0, sp_size=1,
-                 sp_group=None, sp_phases=False, dynamic_geometry=False, token_timestep_sets=0, attn_mx8=False):
+                 sp_group=None, sp_phases=False, dynamic_geometry=False, token_timestep_sets=0, attn_mx8=False,
+                 causal_block_frames=0, causal_window_blocks=0):
         """token_timestep_sets (3..64): the engine's capacity of distinct per-token timesteps per forward -- one timestep per
         latent frame (wan22.frame_timesteps / sample_frames), several conditioning frames at their own noise levels.  0: two,
         what Wan2.2 TI2V's `mask * t` needs.
-        attn_mx8: self-attention on the opt-in MX fp8 kernel (Engine(..., attn_mx8=True)); self.attn_mx8 is what the engine latched."""
+        attn_mx8: self-attention on the opt-in MX fp8 kernel (Engine(..., attn_mx8=True)); self.attn_mx8 is what the engine latched.
+        causal_block_frames (>= 1): self-attention block-causal over blocks of that many latent frames, causal_window_blocks
+        (>= 1) only over the last so many blocks (Engine.set_causal_blocks): set once here, kept across set_geometry
+        (dynamic_geometry) because the engine counts the block in frames.  MagCache, CFG pairs and per-frame timesteps need
+        no change.  wan22.make_experts passes both keywords through."""
         if token_timestep_sets:
             cfg = dict(cfg, token_timestep_sets=int(token_timestep_sets))
         self.cfg = dict(cfg)
@@ -137,6 +142,8 @@ class WanModelHIP(LoraModel):
         self.engine = engine or Engine(cfg, latent_grid, device=device, n_branches=2, calibration=calibration,
                                        sp_rank=sp_rank, sp_size=sp_size, sp_phases=sp_phases, attn_mx8=attn_mx8)
         self.attn_mx8 = getattr(self.engine, "attn_mx8", False)     # (an engine passed in may predate the option)
+        if causal_block_frames or causal_window_blocks:
+            self.engine.set_causal_blocks(causal_block_frames, causal_window_blocks)
         self.device = self.engine.device
         self.sp_group = sp_group      # torch.distributed group of the ranks that share this token sequence
 

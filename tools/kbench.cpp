@@ -1,7 +1,7 @@
 // Torch-free kernel A/B harness for the two MFMA-bound kernels at the Wan2.1-1.3B 480p shapes, through the C ABI.
 //
 //   kbench.bin <what> <rounds> <launches> libA.so [libB.so ...]
-//      what: gemm | attn | attn_mx8 | calib | all
+//      what: gemm | attn | attn_mx8 | attn_band | calib | all
 //
 // Every library given on the command line is dlopen'ed privately (RTLD_LOCAL), so build variants of
 // libmagcache_hip.so (tools/build_variants.py, tools/build_v5_variants.py, tools/build_gemm_v2_variants.py) are measured INTERLEAVED IN ONE PROCESS on the same
@@ -40,6 +40,7 @@ struct Lib {
   decltype(&mc_op_calib_stats) calib;
   decltype(&mc_op_attn_quantize_mx8) quant_mx8;   // null in a library older than the MX fp8 attention (attn_mx8 only)
   decltype(&mc_op_attention_mx8) attn_mx8;
+  decltype(&mc_op_attention_band) attn_band;      // null in a library older than the frame-block causal kernel (attn_band only)
   decltype(&mc_set_option) set_option;
   decltype(&mc_last_error) last_error;
 };
@@ -401,6 +402,115 @@ static void bench_attn_mx8(int Lq_pad, int H, int valid, int rounds, int launche
   for (int i = 0; i < 6; ++i) CK(hipFree(im[i]));
 }
 
+// The frame-block causal / windowed kernel beside the unmasked launch on the same q, k, v -- library 0 only, all launches
+// interleaved round by round.  Per band: the time, its ratio to the unmasked launch, the fraction of (128-row item, 64-key
+// tile) pairs the kernel visits, and the time against the ideal "fraction x unmasked time".  Eight rows of the first band are
+// checked against an fp64 sum over their visible keys.
+static void bench_attn_band(int Lq_pad, int H, int valid, int rounds, int launches) {
+  const Lib& lib = g_libs[0];
+  if (!lib.attn_band) {
+    fprintf(stderr, "%s: no mc_op_attention_band\n", lib.path.c_str());
+    exit(2);
+  }
+  struct BandCase { const char* name; int bt, win; };
+  const int frame = valid / 21;   // 32760 = 21 latent frames of 1560 tokens
+  const BandCase bands[] = {{"causal 21 blocks", frame, 0}, {"causal 7 blocks", 3 * frame, 0}, {"causal 3 blocks", 7 * frame, 0},
+                            {"21 blocks, window 3", frame, 3}};
+  constexpr int NB = 4;
+  const int D = H * 128;
+  const size_t n = (size_t)Lq_pad * D;
+  uint16_t *Q, *K, *V, *O, *Ob;
+  for (uint16_t** p : {&Q, &K, &V, &O, &Ob}) CK(hipMalloc(p, n * 2));
+  fill_bf16<<<2048, 256>>>(Q, n, 11, g_amp);
+  fill_bf16<<<2048, 256>>>(K, n, 12, g_amp);
+  fill_bf16<<<2048, 256>>>(V, n, 13, g_amp);
+  CK(hipDeviceSynchronize());
+  const float scale = 1.0f / std::sqrt(128.0f);
+  auto lo = [&](const BandCase& c, int b) { return c.win ? std::max(0, b - c.win + 1) * c.bt : 0; };
+  auto hi = [&](const BandCase& c, int b) { return std::min((b + 1) * c.bt, valid); };
+  auto blk = [&](const BandCase& c, int row) { return std::min(row, valid - 1) / c.bt; };
+  auto launch = [&](int kind) {
+    if (kind == 0) MCL(lib, lib.attn(Q, D, K, D, 0, V, D, 0, O, D, Lq_pad, H, Lq_pad, valid, 1, scale, nullptr));
+    else MCL(lib, lib.attn_band(Q, D, K, D, V, D, Ob, D, Lq_pad, H, Lq_pad, valid, bands[kind - 1].bt, bands[kind - 1].win, scale, nullptr));
+  };
+  printf("# attn_band: Lq_pad=%d heads=%d valid keys=%d\n", Lq_pad, H, valid);
+  hipEvent_t a, b;
+  CK(hipEventCreate(&a));
+  CK(hipEventCreate(&b));
+  float ms = 0;
+  CK(hipEventRecord(a, nullptr));
+  do {   // ~1 s warm-up of all of them
+    for (int kind = 0; kind <= NB; ++kind) launch(kind);
+    CK(hipEventRecord(b, nullptr));
+    CK(hipEventSynchronize(b));
+    CK(hipEventElapsedTime(&ms, a, b));
+  } while (ms < 1000.f);
+  std::vector<double> t[NB + 1];
+  for (int r = 0; r < rounds; ++r)
+    for (int kind = 0; kind <= NB; ++kind) {
+      launch(kind);
+      CK(hipEventRecord(a, nullptr));
+      for (int i = 0; i < launches; ++i) launch(kind);
+      CK(hipEventRecord(b, nullptr));
+      CK(hipEventSynchronize(b));
+      CK(hipEventElapsedTime(&ms, a, b));
+      t[kind].push_back(ms / launches);
+    }
+  double med[NB + 1];
+  for (int kind = 0; kind <= NB; ++kind) {
+    std::sort(t[kind].begin(), t[kind].end());
+    med[kind] = t[kind][t[kind].size() / 2];
+  }
+  printf("%-20s median %8.4f ms %8.1f TF | min %8.4f ms\n", "attn (unmasked)", med[0], 4.0 * valid * (double)valid * D * 1e-12 / (med[0] * 1e-3), t[0][0]);
+  for (int kind = 1; kind <= NB; ++kind) {
+    const BandCase& c = bands[kind - 1];
+    double visited = 0, all = 0;
+    for (int q0 = 0; q0 < Lq_pad; q0 += 128) {
+      visited += (hi(c, blk(c, q0 + 127)) - 1) / 64 - lo(c, blk(c, q0)) / 64 + 1;
+      all += (valid + 63) / 64;
+    }
+    const double frac = visited / all;
+    printf("%-20s median %8.4f ms | min %8.4f ms | x%.3f of unmasked | tiles visited %.4f, ideal %8.4f ms, measured / ideal %.3f\n", c.name,
+           med[kind], t[kind][0], med[kind] / med[0], frac, frac * med[0], med[kind] / (frac * med[0]));
+  }
+  {   // spot check: the first band
+    const BandCase& c = bands[0];
+    launch(1);
+    CK(hipDeviceSynchronize());
+    std::vector<uint16_t> hq(n), hk(n), hv(n), ho(n);
+    CK(hipMemcpy(hq.data(), Q, n * 2, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(hk.data(), K, n * 2, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(hv.data(), V, n * 2, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(ho.data(), Ob, n * 2, hipMemcpyDeviceToHost));
+    double num = 0, den = 0;
+    for (int i = 0; i < 8; ++i) {
+      const int row = (int)(((long)i * 4099 + 17) % valid), head = i % H;
+      const int k0 = lo(c, blk(c, row)), k1 = hi(c, blk(c, row));
+      std::vector<double> s(k1 - k0);
+      double mx = -1e300, z = 0, acc[128] = {0};
+      for (int k = k0; k < k1; ++k) {
+        double d = 0;
+        for (int j = 0; j < 128; ++j) d += (double)bf16_to_f(hq[(size_t)row * D + head * 128 + j]) * bf16_to_f(hk[(size_t)k * D + head * 128 + j]);
+        s[k - k0] = d * scale;
+        mx = std::max(mx, s[k - k0]);
+      }
+      for (int k = k0; k < k1; ++k) {
+        const double pw = std::exp(s[k - k0] - mx);
+        z += pw;
+        for (int j = 0; j < 128; ++j) acc[j] += pw * bf16_to_f(hv[(size_t)k * D + head * 128 + j]);
+      }
+      for (int j = 0; j < 128; ++j) {
+        const double got = bf16_to_f(ho[(size_t)row * D + head * 128 + j]), want = acc[j] / z;
+        num += (got - want) * (got - want);
+        den += want * want;
+      }
+    }
+    printf("  attn_band (%s) vs fp64 (8 rows): rel_l2 %.3e\n", c.name, std::sqrt(num / den));
+  }
+  fflush(stdout);
+  for (void* p : {(void*)Q, (void*)K, (void*)V, (void*)O, (void*)Ob}) CK(hipFree(p));
+}
+
 // ------------------------------------------------------------------------------------- calibration statistics
 static void bench_calib(int M, int D, int rounds, int launches) {
   float *r, *rp, *stats;
@@ -428,7 +538,7 @@ static void bench_calib(int M, int D, int rounds, int launches) {
 
 int main(int argc, char** argv) {
   if (argc < 5) {
-    fprintf(stderr, "usage: kbench.bin <gemm|attn|attn_mx8|attn_keys|calib|all> <rounds> <launches> libA.so [libB.so ...]\n");
+    fprintf(stderr, "usage: kbench.bin <gemm|attn|attn_mx8|attn_band|attn_keys|calib|all> <rounds> <launches> libA.so [libB.so ...]\n");
     return 2;
   }
   if (getenv("KBENCH_AMP")) g_amp = (float)atof(getenv("KBENCH_AMP"));
@@ -447,6 +557,7 @@ int main(int argc, char** argv) {
     l.calib = (decltype(l.calib))dlsym(l.h, "mc_op_calib_stats");
     l.quant_mx8 = (decltype(l.quant_mx8))dlsym(l.h, "mc_op_attn_quantize_mx8");
     l.attn_mx8 = (decltype(l.attn_mx8))dlsym(l.h, "mc_op_attention_mx8");
+    l.attn_band = (decltype(l.attn_band))dlsym(l.h, "mc_op_attention_band");
     l.set_option = (decltype(l.set_option))dlsym(l.h, "mc_set_option");
     l.last_error = (decltype(l.last_error))dlsym(l.h, "mc_last_error");
     if (!l.gemm || !l.attn || !l.calib || !l.set_option || !l.last_error) {
@@ -477,6 +588,7 @@ int main(int argc, char** argv) {
     bench_attn("self480p_q6", 32768, 12, 32760, 6.0f, rounds, std::max(1, launches / 4));
   }
   if (what == "attn_mx8") bench_attn_mx8(32768, 12, 32760, rounds, std::max(1, launches / 4));
+  if (what == "attn_band") bench_attn_band(32768, 12, 32760, rounds, std::max(1, launches / 4));
   if (what == "attn_strided" || what == "all") bench_attn("self480p_qkv", 32768, 12, 32760, 1.0f, rounds, std::max(1, launches / 4), true);
   if (what == "attn_keys") bench_attn_keys(32768, 12, rounds, launches);
   if (what == "attn1") bench_attn("self480p", 32768, 12, 32760, 1.0f, rounds, launches);          // one shape (PMC passes)
