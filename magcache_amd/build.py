@@ -48,7 +48,8 @@ def _stale(target, deps):
 def _headers():
     hs = [os.path.join(CSRC, h) for h in ("common.h", "ops.h", "host.h", "gemm_epilogue.h", "attention_v5_body.inc",
                                           "attention_v5_clobbers.inc", "attention_v5_config.h", "gemm_v2_body.inc",
-                                          "gemm_v2_clobbers.inc", "gemm_v2_config.h", "quant.h", "gemm_pipe8.h")]
+                                          "gemm_v2_clobbers.inc", "gemm_v2_config.h", "quant.h", "gemm_pipe8.h",
+                                          "attention_tile.h")]
     return hs + [os.path.join(HERE, "..", "include", "magcache_hip.h"), os.path.join(HERE, "..", "include", "magcache_mmdit.h")]
 
 

@@ -41,28 +41,22 @@
 //     to +inf and make 0 * inf;
 //   * a tile whose maximum is -inf for an unseen row moves nothing (d = 0) and contributes P = 0.
 //
-// Data movement.  Q: 8 fragments in registers for the launch.  K/V: LDS-DMA (global_load_lds_dwordx4, the technique and the
-// bank swizzles of attention_v3.hip) into a ring of two 32 KiB stages; tile t + 1 is issued right after the barrier that opens
-// tile t and waited for (vmcnt(0)) before the next barrier: one barrier per tile, a whole tile of matrix work over the latency.
-// O: O^T accumulators scaled by 1 / l, 8-byte stores, as v3.
-// the LDS-DMA asm below names m0 in its clobber list on purpose (reserved register: the compiler only warns)
+// Data movement.  Q fragments, tile images, fragment reads, the PV step and the O store are attention_tile.h's, shared with
+// attention_v3.hip.  K/V: LDS-DMA into a ring of two 32 KiB stages (a K image, the V image behind it); tile t + 1 is issued
+// right after the barrier that opens tile t and waited for (vmcnt(0)) before the next barrier: one barrier per tile, a whole
+// tile of matrix work over the latency.
+// the LDS-DMA asm of attention_tile.h names m0 in its clobber list on purpose (reserved register: the compiler only warns)
 #pragma clang diagnostic ignored "-Winline-asm"
-#include "common.h"
-#include "ops.h"
+#include "attention_tile.h"
 
 namespace mc {
 
 namespace {
 
 constexpr int QT = 128;   // query rows per workgroup (4 waves x 32)
-constexpr int KT = 64;    // keys per tile
-constexpr int HD = 128;   // head dim
-constexpr int TILE_BYTES = KT * HD * 2;      // 16 KiB: one operand's tile
 constexpr int STAGE_BYTES = 2 * TILE_BYTES;  // K tile, V tile
 constexpr int LDS_BYTES = 2 * STAGE_BYTES;   // 64 KiB: two workgroups per CU
 constexpr int MAX_RANKED = LDS_BYTES / 4 - 1;  // query tiles the window form can rank in LDS
-constexpr float NEG_INF = -__builtin_huge_valf();
-constexpr float RTHR = 4.0f;  // rescale threshold in log2 units: P <= 2^4
 
 struct Band {
   int bt, win, valid;
@@ -75,20 +69,6 @@ struct Band {
     t1 = (hi(block(row0 + n - 1)) - 1) / KT;
   }
 };
-
-__device__ __forceinline__ float max3(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
-
-// row maximum over a lane's 32 scores and the other half's
-__device__ __forceinline__ float rowmax32(const f32x16& a, const f32x16& b) {
-  float m0 = max3(a[0], a[1], a[2]), m1 = max3(a[3], a[4], a[5]);
-  float m2 = max3(a[6], a[7], a[8]), m3 = max3(a[9], a[10], a[11]);
-  m0 = max3(m0, a[12], a[13]); m1 = max3(m1, a[14], a[15]);
-  m2 = max3(m2, b[0], b[1]);   m3 = max3(m3, b[2], b[3]);
-  m0 = max3(m0, b[4], b[5]);   m1 = max3(m1, b[6], b[7]);
-  m2 = max3(m2, b[8], b[9]);   m3 = max3(m3, b[10], b[11]);
-  m0 = max3(m0, b[12], b[13]); m1 = max3(m1, b[14], b[15]);
-  return half_swap_max(fmaxf(fmaxf(m0, m1), fmaxf(m2, m3)));
-}
 
 __global__ __launch_bounds__(256, 2) void attn_band_kernel(AttnParams p, Band band, int nqt) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -138,63 +118,29 @@ __global__ __launch_bounds__(256, 2) void attn_band_kernel(AttnParams p, Band ba
   const int r_lo = band.lo(r_blk);
   const unsigned r_span = (unsigned)(band.hi(r_blk) - r_lo);   // >= 1
 
-  // ---- Q fragments (B operand of the S^T MFMA): lane -> query row l31, d = ds*16 + 8*half + 0..7, times scale * log2(e)
-  const float c = p.scale * 1.4426950408889634f;
   bf16x8 qf[8];
-  {
-    const bf16_t* qp = p.Q + (size_t)qrow * p.ldq + head * HD + 8 * half;
-#pragma unroll
-    for (int ds = 0; ds < 8; ++ds) {
-      const bf16x8 raw = *(const bf16x8*)(qp + ds * 16);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) qf[ds][i] = (__bf16)((float)raw[i] * c);
-    }
-  }
-
-  // ---- LDS-DMA: 16 pieces of 1 KiB per operand tile, 4 per wave.  piece g = rows 4g..4g+3, lane -> (row = 4g + lane/16,
-  // slot = lane%16); the 16-byte source chunk of a slot is K: slot ^ (row&15), V: slot ^ ((row&3)<<2) (v3's swizzles)
-  uint32_t srcK[4], srcV[4];  // byte offsets from the tile's first row
+  MC_ATTN_LOAD_Q(p, qrow, head, half, qf)
+  uint32_t srcK[4], srcV[4];  // this wave's 4 of the 16 pieces per operand tile: byte offsets from the tile's first row
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int row = (wv * 4 + j) * 4 + (lane >> 4);
     const int slot = lane & 15;
-    srcK[j] = (uint32_t)(row * (int)p.ldk + head * HD + (slot ^ (row & 15)) * 8) * 2u;
-    srcV[j] = (uint32_t)(row * (int)p.ldv + head * HD + (slot ^ ((row & 3) << 2)) * 8) * 2u;
+    srcK[j] = MC_ATTN_PIECE_SRC(row, p.ldk, head, MC_ATTN_K_SRC_CHUNK(slot, row));
+    srcV[j] = MC_ATTN_PIECE_SRC(row, p.ldv, head, MC_ATTN_V_SRC_CHUNK(slot, row));
   }
   const uint32_t dma_lds = (uint32_t)(uintptr_t)MC_LDS_PTR(smem) + wv * 4096;  // this wave's 4 pieces inside a tile image
-  // one 1 KiB piece.  saddr form: uniform 64-bit base + 32-bit lane offset; M0 = LDS byte address of the piece; s_nop covers
-  // the SALU-write-M0 -> LDS-DMA hazard
-  auto dma1 = [&](const bf16_t* base, uint32_t off, uint32_t lds) {
-    asm volatile(
-        "s_mov_b32 m0, %1\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %0, %2"
-        :
-        : "v"(off), "s"(lds), "s"(base)
-        : "memory", "m0");
-  };
   auto dma_tile = [&](int t, int stage) {
     const bf16_t* kp = p.K + (size_t)t * KT * p.ldk;
     const bf16_t* vp = p.V + (size_t)t * KT * p.ldv;
     const uint32_t dst = dma_lds + stage * STAGE_BYTES;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      dma1(kp, srcK[j], dst + j * 1024);
-      dma1(vp, srcV[j], dst + TILE_BYTES + j * 1024);
+      dma_piece(kp, srcK[j], dst + j * 1024);
+      dma_piece(vp, srcV[j], dst + TILE_BYTES + j * 1024);
     }
   };
-
-  // ---- K fragment read: row = kb*32 + l31, chunk (2*ds + half) ^ (row & 15), row&15 == lane&15
-  int koff[8];
-#pragma unroll
-  for (int ds = 0; ds < 8; ++ds) koff[ds] = l31 * 256 + (((2 * ds + half) ^ (lane & 15)) << 4);
-  // ---- V^T fragment (transposing read): key = ks*16 + 4*half + r (+8 for the second read), r = (lane&15)>>2;
-  //   d = db*32 + dg*16 + 4*c, dg = (lane>>4)&1, c = lane&3; 64-B chunk (= db) ^= (key&3) = r
-  const int vr = (lane & 15) >> 2;
-  const int vbase = TILE_BYTES + (4 * half + vr) * 256 + ((lane >> 4) & 1) * 32 + (lane & 3) * 8;
-  int voff[4];
-#pragma unroll
-  for (int db = 0; db < 4; ++db) voff[db] = vbase + ((db ^ vr) << 6);
+  int koff[8], voff[4];
+  MC_ATTN_FRAG_OFFSETS(lane, half, l31, TILE_BYTES, koff, voff)
 
   f32x16 o[4];
 #pragma unroll
@@ -245,8 +191,7 @@ __global__ __launch_bounds__(256, 2) void attn_band_kernel(AttnParams p, Band ba
       c_init = c_init - d;
       seen = seen || fresh;
     }
-    // ---- P = exp2(S): registers 2j, 2j+1 of key block kb -> the packed pair 8*kb + j, word j%4 of the B operand of key
-    // step ks = 2*kb + j/4 (the accumulator layout of S^T IS that operand: both products agree on the key order)
+    // ---- P = exp2(S): registers 2j, 2j+1 of key block kb -> the packed pair 8*kb + j (pv_step's operand words)
     uint32_t pk[16];
     float rs0 = 0.f, rs1 = 0.f;
 #pragma unroll
@@ -261,15 +206,7 @@ __global__ __launch_bounds__(256, 2) void attn_band_kernel(AttnParams p, Band ba
     l_run += rs0 + rs1;
     // ---- O^T += V^T P^T, micro-step i = 4*ks + db
 #pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const char* vp = st + voff[i & 3] + (i >> 2) * (16 * 256);
-      const bf16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)(vp));
-      const bf16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)(vp + 8 * 256));
-      const bf16x8 vf = __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
-      const int ks = i >> 2;
-      const u32x4 pw = {pk[4 * ks], pk[4 * ks + 1], pk[4 * ks + 2], pk[4 * ks + 3]};
-      o[i & 3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, __builtin_bit_cast(bf16x8, pw), o[i & 3], 0, 0, 0);
-    }
+    for (int i = 0; i < 16; ++i) pv_step(o, i, read_vt(st + voff[i & 3] + (i >> 2) * (16 * 256)), pk);
   };
   // one ring step: tile t has landed in `stage` for every wave and the other stage is free (every wave is past tile t - 1)
   auto step = [&](int t, int stage) __attribute__((always_inline)) {
@@ -285,39 +222,22 @@ __global__ __launch_bounds__(256, 2) void attn_band_kernel(AttnParams p, Band ba
     if (t < t1) step(t + 1, 1);
   }
 
-  // ---- epilogue: O[q][d] = O^T[d][q] / l ; lane holds d = db*32 + 8*g + 4*half + 0..3.  Every row has seen its own block: l > 0
+  // ---- epilogue: O = O^T / l.  Every row has seen its own block: l > 0
   const float inv = 1.0f / half_swap_sum(l_run);
   bf16_t* op = p.O + (size_t)qrow * p.ldo + head * HD + 4 * half;
-#pragma unroll
-  for (int db = 0; db < 4; ++db) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      u32x2 w = {pack_bf16x2(o[db][4 * g] * inv, o[db][4 * g + 1] * inv),
-                 pack_bf16x2(o[db][4 * g + 2] * inv, o[db][4 * g + 3] * inv)};
-      *(u32x2*)(op + db * 32 + 8 * g) = w;
-    }
-  }
+  MC_ATTN_STORE_O(op, o, inv)
 }
 
 }  // namespace
 
 bool attention_band_supports(const AttnParams& p, const AttnBand& b) {
-  auto al16 = [](const void* q) { return q && ((uintptr_t)q & 15) == 0; };
-  if (p.n_shards != 1 || p.skip_shard_p1 != 0 || p.lse_in || p.lse_out) return false;
-  if (p.Lq_pad <= 0 || (p.Lq_pad % 256) != 0 || p.shard_rows <= 0 || (p.shard_rows % KT) != 0 || p.shard_valid < 1 ||
-      p.shard_valid > p.shard_rows || p.n_heads <= 0)
-    return false;
-  if (b.block_tokens < 1 || b.window_blocks < 0) return false;
-  if ((p.ldq % 8) || (p.ldk % 8) || (p.ldv % 8) || (p.ldo % 8)) return false;
-  const size_t d = (size_t)p.n_heads * HD;
-  if ((size_t)p.ldq < d || (size_t)p.ldk < d || (size_t)p.ldv < d || (size_t)p.ldo < d) return false;
+  if (!attention_shape_ok(p) || !attention_plain_form(p) || b.block_tokens < 1 || b.window_blocks < 0) return false;
   // a lane's K / V offset inside a tile is 32-bit, and so is every row offset the contract promises
   if ((size_t)p.shard_rows * p.ldk * 2 >= (1ull << 32) || (size_t)p.shard_rows * p.ldv * 2 >= (1ull << 32) ||
       (size_t)p.Lq_pad * p.ldq * 2 >= (1ull << 32) || (size_t)p.Lq_pad * p.ldo * 2 >= (1ull << 32))
     return false;
   const size_t nqt = p.Lq_pad / QT;
-  if (nqt * p.n_heads >= (1ull << 31) || (b.window_blocks != 0 && nqt > (size_t)MAX_RANKED)) return false;
-  return al16(p.Q) && al16(p.K) && al16(p.V) && al16(p.O);
+  return nqt * p.n_heads < (1ull << 31) && (b.window_blocks == 0 || nqt <= (size_t)MAX_RANKED);
 }
 
 hipError_t launch_attention_band(const AttnParams& p, const AttnBand& b, hipStream_t stream) {

@@ -364,16 +364,10 @@ __global__ __launch_bounds__(256, 1) void attn_mx8_kernel(AttnMx8Images im, bf16
 
 bool attention_mx8_supports(const AttnParams& p, const AttnMx8Images& im) {
   auto al16 = [](const void* q) { return q && ((uintptr_t)q & 15) == 0; };
-  if (p.n_shards != 1 || p.skip_shard_p1 != 0 || p.lse_in || p.lse_out) return false;
-  if (p.Lq_pad <= 0 || (p.Lq_pad % QB) != 0 || p.shard_rows <= 0 || (p.shard_rows % KT) != 0 || p.shard_valid < 1 ||
-      p.shard_valid > p.shard_rows || p.n_heads <= 0)
-    return false;
-  if ((p.ldq % 8) || (p.ldk % 8) || (p.ldv % 8) || (p.ldo % 8)) return false;
-  const size_t d = (size_t)p.n_heads * HD;
-  if ((size_t)p.ldq < d || (size_t)p.ldk < d || (size_t)p.ldv < d || (size_t)p.ldo < d) return false;
+  if (!attention_shape_ok(p) || !attention_plain_form(p)) return false;
+  const size_t d = (size_t)p.n_heads * HD;   // byte offsets into the e4m3 images are 32-bit
   if ((size_t)p.Lq_pad * d >= (1ull << 32) || (size_t)p.shard_rows * d >= (1ull << 32)) return false;
-  return al16(p.Q) && al16(p.K) && al16(p.V) && al16(p.O) && al16(im.q) && al16(im.qs) && al16(im.k) && al16(im.ks) && al16(im.vt) &&
-         al16(im.vs);
+  return al16(im.q) && al16(im.qs) && al16(im.k) && al16(im.ks) && al16(im.vt) && al16(im.vs);
 }
 
 hipError_t launch_attn_quantize_mx8(const AttnParams& p, const AttnMx8Images& im, hipStream_t stream) {

@@ -22,42 +22,23 @@
 //    P(t) is exponentiated.
 //  * S^T = K Q^T is issued swapped and its accumulator layout is the B operand of the PV MFMA, as
 //    (an MFMA's contraction index may be permuted if both operands agree).
-//  * K/V tiles: LDS-DMA (global_load_lds_dwordx4, inline asm so hipcc's waitcnt pass does not
-//    serialise ds_reads behind it) into 3-deep rings; the 4 pieces a wave moves per tile are issued
-//    between MFMAs; one counted s_waitcnt vmcnt(4) + s_barrier per tile.
+//  * K/V tiles: LDS-DMA into 3-deep rings of the swizzled tile images of attention_tile.h (which has the
+//    layouts, the DMA piece, the fragment reads and the O store); the 4 pieces a wave moves per tile are
+//    issued between MFMAs; one counted s_waitcnt vmcnt(4) + s_barrier per tile.
 //  * the VALU work is written between the MFMAs it should hide behind and pinned with
 //    sched_barrier(0): the compiler otherwise sinks the softmax out of the MFMA shadow.
-// the LDS-DMA asm below names m0 in its clobber list on purpose (reserved register: the compiler only warns)
+// the LDS-DMA asm of attention_tile.h names m0 in its clobber list on purpose (reserved register: the compiler only warns)
 #pragma clang diagnostic ignored "-Winline-asm"
-#include "common.h"
-#include "ops.h"
+#include "attention_tile.h"
 
 namespace mc {
 
 namespace {
 
 constexpr int QB = 256;   // query rows per workgroup (8 waves x 32)
-constexpr int KT = 64;    // keys per tile
-constexpr int HD = 128;   // head dim
-constexpr int TILE_BYTES = KT * HD * 2;  // 16 KiB
 constexpr int NST = 3;                   // ring depth
 constexpr int V_RING = NST * TILE_BYTES; // K ring at 0, V ring behind it
 constexpr int LDS_BYTES = 2 * NST * TILE_BYTES;  // 96 KiB
-constexpr float NEG_INF = -__builtin_huge_valf();
-constexpr float RTHR = 4.0f;  // rescale threshold in log2 units: P <= 2^4
-
-__device__ __forceinline__ float max3(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
-
-__device__ __forceinline__ float rowmax32(const f32x16& a, const f32x16& b) {
-  float m0 = max3(a[0], a[1], a[2]), m1 = max3(a[3], a[4], a[5]);
-  float m2 = max3(a[6], a[7], a[8]), m3 = max3(a[9], a[10], a[11]);
-  m0 = max3(m0, a[12], a[13]); m1 = max3(m1, a[14], a[15]);
-  m2 = max3(m2, b[0], b[1]);   m3 = max3(m3, b[2], b[3]);
-  m0 = max3(m0, b[4], b[5]);   m1 = max3(m1, b[6], b[7]);
-  m2 = max3(m2, b[8], b[9]);   m3 = max3(m3, b[10], b[11]);
-  m0 = max3(m0, b[12], b[13]); m1 = max3(m1, b[14], b[15]);
-  return half_swap_max(fmaxf(fmaxf(m0, m1), fmaxf(m2, m3)));
-}
 
 #ifndef MC_ABL
 #define MC_ABL 0  // timing ablations (tools/build_variants.py; results are wrong by construction): 1 no exp2,
@@ -81,34 +62,18 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v3_kernel(AttnParams p, int n
   const int head = vb / nqb;
   const int qb = vb - head * nqb;
 
-  // ---- Q fragments (B operand of the S^T MFMA): lane -> query row l31, d = ds*16 + 8*half + 0..7
   const int qrow = qb * QB + wv * 32 + l31;
-  // Q is pre-multiplied by c = scale * log2(e) (one extra bf16 rounding of q, 2^-9 relative: below
-  // the rounding q and k already carry), so the MFMA delivers scores in log2 units and, with the
-  // accumulator initialised to -m (see c_init), P = exp2(S) needs no multiply-add per element.
-  const float c = p.scale * 1.4426950408889634f;
   bf16x8 qf[8];
-  {
-    const bf16_t* qp = p.Q + (size_t)qrow * p.ldq + head * HD + 8 * half;
-#pragma unroll
-    for (int ds = 0; ds < 8; ++ds) {
-      const bf16x8 raw = *(const bf16x8*)(qp + ds * 16);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) qf[ds][i] = (__bf16)((float)raw[i] * c);
-    }
-  }
-
-  // ---- LDS-DMA: 16 x 1 KiB pieces per operand tile, 2 per wave.  piece g = rows 4g..4g+3,
-  // lane -> (row = 4g + lane/16, slot = lane%16); source chunk K: slot ^ (row&15), V: slot ^ ((row&3)<<2)
-  uint32_t srcK[2], srcV[2];  // byte offsets inside a tile (from the tile's first row, head 0 col 0)
+  MC_ATTN_LOAD_Q(p, qrow, head, half, qf)
+  uint32_t srcK[2], srcV[2];  // this wave's 2 of the 16 pieces per operand tile: byte offsets inside a tile
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int row = (wv * 2 + j) * 4 + (lane >> 4);
     const int slot = lane & 15;
-    const int ck = slot ^ (row & 15);
-    const int cv = slot ^ ((row & 3) << 2);
-    srcK[j] = (uint32_t)(row * (int)p.ldk + head * HD + ck * 8) * 2u;
-    srcV[j] = (uint32_t)(row * (int)p.ldv + head * HD + cv * 8) * 2u;
+    const int ck = MC_ATTN_K_SRC_CHUNK(slot, row);
+    const int cv = MC_ATTN_V_SRC_CHUNK(slot, row);
+    srcK[j] = MC_ATTN_PIECE_SRC(row, p.ldk, head, ck);
+    srcV[j] = MC_ATTN_PIECE_SRC(row, p.ldv, head, cv);
   }
   const uint32_t lds0 = (uint32_t)(uintptr_t)MC_LDS_PTR(smem);
   const uint32_t dma_lds = lds0 + wv * 2048;  // this wave's 2 pieces inside a tile image
@@ -116,17 +81,6 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v3_kernel(AttnParams p, int n
   const int skip_sh = p.skip_shard_p1 - 1;  // -1: none
   const int ntiles = (p.n_shards - (skip_sh >= 0 ? 1 : 0)) * tiles_per_shard;
 
-  // one 1 KiB piece.  saddr form: uniform 64-bit base + 32-bit lane offset; M0 = LDS byte address of
-  // the piece; s_nop covers the SALU-write-M0 -> LDS-DMA hazard; M0 is restored for the compiler.
-  auto dma1 = [&](const bf16_t* base, uint32_t off, uint32_t lds) {
-    asm volatile(
-        "s_mov_b32 m0, %1\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %0, %2"
-        :
-        : "v"(off), "s"(lds), "s"(base)
-        : "memory", "m0");
-  };
   // Tile cursors (all scalar): the DMA streams run ahead of the compute, each with its
   // own position.  Past the last tile a cursor stays on it: the reload lands in a dead slot and
   // keeps the number of DMA instructions per iteration constant (the vmcnt counts rely on that).
@@ -155,28 +109,18 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v3_kernel(AttnParams p, int n
     cv.ptr += p.v_shard_stride;
   }
   auto dma_k = [&](int slot) {  // whole next K tile (this wave's pieces) -> ring slot; prologue only
-    dma1(ck.ptr, srcK[0], dma_lds + slot * TILE_BYTES);
-    dma1(ck.ptr, srcK[1], dma_lds + slot * TILE_BYTES + 1024);
+    dma_piece(ck.ptr, srcK[0], dma_lds + slot * TILE_BYTES);
+    dma_piece(ck.ptr, srcK[1], dma_lds + slot * TILE_BYTES + 1024);
     advance(ck, p.ldk, p.k_shard_stride);
   };
   auto dma_v = [&](int slot) {
-    dma1(cv.ptr, srcV[0], dma_lds + V_RING + slot * TILE_BYTES);
-    dma1(cv.ptr, srcV[1], dma_lds + V_RING + slot * TILE_BYTES + 1024);
+    dma_piece(cv.ptr, srcV[0], dma_lds + V_RING + slot * TILE_BYTES);
+    dma_piece(cv.ptr, srcV[1], dma_lds + V_RING + slot * TILE_BYTES + 1024);
     advance(cv, p.ldv, p.v_shard_stride);
   };
 
-  // ---- K fragment read: row = kb*32 + l31, chunk (2*ds + half) ^ (row & 15), row&15 == lane&15
-  const int ksw = lane & 15;
-  int koff[8];
-#pragma unroll
-  for (int ds = 0; ds < 8; ++ds) koff[ds] = l31 * 256 + (((2 * ds + half) ^ ksw) << 4);
-  // ---- V^T fragment (tr read): key = ks*16 + 4*half + r (+8 for the second read), r = (lane&15)>>2;
-  //   d = db*32 + dg*16 + 4*c, dg = (lane>>4)&1, c = lane&3; 64-B chunk (= db) ^= (key&3) = r
-  const int vr = (lane & 15) >> 2;
-  const int vbase = V_RING + (4 * half + vr) * 256 + ((lane >> 4) & 1) * 32 + (lane & 3) * 8;
-  int voff[4];
-#pragma unroll
-  for (int db = 0; db < 4; ++db) voff[db] = vbase + ((db ^ vr) << 6);
+  int koff[8], voff[4];
+  MC_ATTN_FRAG_OFFSETS(lane, half, l31, V_RING, koff, voff)
 
   f32x16 o[4];
 #pragma unroll
@@ -199,11 +143,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v3_kernel(AttnParams p, int n
   };
   auto read_v = [&](const char* st, int i, bf16x8& vf) {  // V^T fragment of PV micro-step i = 4*ks + db
     if ((MC_ABL & 8) && i > 3) return;     // timing ablation: no V fragment traffic after the first reads
-    const char* vp = st + voff[i & 3] + (i >> 2) * (16 * 256);
-    const bf16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)(vp));
-    const bf16x4 v1 =
-        __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)(vp + 8 * 256));
-    vf = __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
+    vf = read_vt(st + voff[i & 3] + (i >> 2) * (16 * 256));
   };
   // keys >= nvalid of a tile are padding: -inf before the max and the exponentials
   auto mask_tail = [&](int nvalid, f32x16 (&s)[2]) {
@@ -312,8 +252,8 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v3_kernel(AttnParams p, int n
   if ((ds) == 7) read_v(stv_, 3, vd_);                                                               \
   S_nxt[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(KC0, qf[ds], (ds) ? S_nxt[0] : c_init, 0, 0, 0); \
   MC_FIN_N(S_cur, (ds));                                                                             \
-  if ((ds) == 2) dma1(kptr_, srcK[0], kdst_);                                                        \
-  if ((ds) == 5) dma1(kptr_, srcK[1], kdst_ + 1024);                                                 \
+  if ((ds) == 2) dma_piece(kptr_, srcK[0], kdst_);                                                        \
+  if ((ds) == 5) dma_piece(kptr_, srcK[1], kdst_ + 1024);                                                 \
   MC_PIN();                                                                                          \
   S_nxt[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(KC1, qf[ds], (ds) ? S_nxt[1] : c_init, 0, 0, 0); \
   if ((ds) == 3) MC_FIN_N(S_cur, 8);                                                                 \
@@ -345,15 +285,11 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v3_kernel(AttnParams p, int n
   if ((i) == 13) read_k(stk_, 0, kx0, kx1);                                                          \
   if ((i) == 14) read_k(stk_, 1, ky0, ky1);                                                          \
   if ((i) == 15) read_k(stk_, 2, kz0, kz1);                                                          \
-  {                                                                                                  \
-    const int ks_ = (i) >> 2;                                                                        \
-    const u32x4 pw_ = {pk[4 * ks_], pk[4 * ks_ + 1], pk[4 * ks_ + 2], pk[4 * ks_ + 3]};               \
-    o[(i) & 3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(VC, __builtin_bit_cast(bf16x8, pw_), o[(i) & 3], 0, 0, 0); \
-  }                                                                                                  \
+  pv_step(o, (i), VC, pk);                                                                           \
   if ((i) < 6) MC_FIN_N(S_cur, 10 + (i))                                                             \
   else if ((i) >= 8 && (i) < 12) { if (MC_ABL & 4) mx = 0.f; else MC_ROWMAX_PART(S_nxt, (i) - 8, rm_, mx) }                             \
-  if ((i) == 6) dma1(vptr_, srcV[0], vdst_);                                                         \
-  if ((i) == 12) dma1(vptr_, srcV[1], vdst_ + 1024);                                                 \
+  if ((i) == 6) dma_piece(vptr_, srcV[0], vdst_);                                                         \
+  if ((i) == 12) dma_piece(vptr_, srcV[1], vdst_ + 1024);                                                 \
   MC_PIN();
 
   // One iteration: S_cur = S(t) (row maximum in mx) -> P(t), O += V(t)^T P(t); S_nxt = S(t+1).
@@ -446,9 +382,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v3_kernel(AttnParams p, int n
     for (int i = 0; i < 16; ++i) {
       bf16x8 vf;
       read_v(st_, i, vf);
-      const int ks = i >> 2;
-      const u32x4 pw = {pk[4 * ks], pk[4 * ks + 1], pk[4 * ks + 2], pk[4 * ks + 3]};
-      o[i & 3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, __builtin_bit_cast(bf16x8, pw), o[i & 3], 0, 0, 0);
+      pv_step(o, i, vf, pk);
     }
   }
 #undef MC_ATTN_BODY
@@ -491,25 +425,18 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v3_kernel(AttnParams p, int n
     }
     if (p.lse_out && half == 0) p.lse_out[(size_t)head * p.Lq_pad + qrow] = lse;
   }
-#pragma unroll
-  for (int db = 0; db < 4; ++db) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      u32x2 w = {pack_bf16x2(o[db][4 * g] * inv, o[db][4 * g + 1] * inv),
-                 pack_bf16x2(o[db][4 * g + 2] * inv, o[db][4 * g + 3] * inv)};
-      *(u32x2*)(op + db * 32 + 8 * g) = w;
-    }
-  }
+  MC_ATTN_STORE_O(op, o, inv)
 }
 
 }  // namespace
 
+bool attention_v3_supports(const AttnParams& p) {
+  // O leaves in 8-byte stores; a lane's offset inside a 64-key tile (piece_src_offsets) is a 32-bit int
+  return attention_shape_ok(p) && (p.ldo % 4) == 0 && p.ldk * KT * 2 < (1l << 31) && p.ldv * KT * 2 < (1l << 31);
+}
+
 hipError_t launch_attention_v3(const AttnParams& p, hipStream_t stream) {
-  if (p.Lq_pad <= 0 || (p.Lq_pad % QB) != 0 || (p.shard_rows % KT) != 0 || p.shard_valid <= 0 ||
-      p.shard_valid > p.shard_rows || p.n_shards <= 0 || p.n_heads <= 0)
-    return hipErrorInvalidValue;
-  if ((p.ldq % 8) || (p.ldk % 8) || (p.ldv % 8) || (p.ldo % 4)) return hipErrorInvalidValue;
-  if (p.ldk * 64 * 2 >= (1l << 31) || p.ldv * 64 * 2 >= (1l << 31)) return hipErrorInvalidValue;
+  if (!attention_v3_supports(p)) return hipErrorInvalidValue;
   const int nqb = p.Lq_pad / QB;
   const int tiles_per_shard = (p.shard_valid + KT - 1) / KT;
   return launch_dynamic_lds<attn_fwd_v3_kernel>(dim3(nqb * p.n_heads), dim3(512), LDS_BYTES, stream, p, nqb, tiles_per_shard);

@@ -437,32 +437,23 @@ mc_status attend(const mc_engine* e, const bf16_t* Q, long ldq, bf16_t* O, const
   HIP_TRY(mc::launch_attention_keys(Q, ldq, O, e->d, e->Lp, e->H, keys, lse_in, lse_out, s));
   return MC_OK;
 }
-// The MX fp8 form of the one-device self-attention (option "attn_mx8"): the pre-pass quantises the q, k and v columns of "qkv"
-// into the planned images, the kernel reads the images alone
-mc_status attend_mx8(const mc_engine* e, bf16_t* O, hipStream_t s) {
+// The one-device self-attention, "qkv" over its own k and v columns -> O, in the form the engine was set to:
+//   option "attn_mx8"      the pre-pass quantises the q, k and v columns into the planned images, attention_mx8.hip reads the
+//                          images alone
+//   mc_set_causal_blocks   attention_band.hip with the block in tokens of the grid in force
+//   otherwise              attend() over the same operands
+mc_status attend_self(const mc_engine* e, bf16_t* O, hipStream_t s) {
   const Keys keys = qkv_keys(e);
-  mc::AttnParams a;
-  memset(&a, 0, sizeof(a));
-  a.Q = e->buf<bf16_t>("qkv"); a.ldq = keys.ld; a.K = keys.k; a.ldk = keys.ld; a.V = keys.v; a.ldv = keys.ld;
-  a.O = O; a.ldo = e->d;
-  a.Lq_pad = e->Lp; a.n_heads = e->H; a.shard_rows = keys.rows; a.shard_valid = keys.valid; a.n_shards = 1;
-  a.scale = 1.0f / std::sqrt(128.0f);   // head_dim is fixed at 128
-  const mc::AttnMx8Images im = {e->buf<uint8_t>("mx8_q"), e->buf<uint8_t>("mx8_qs"), e->buf<uint8_t>("mx8_k"),
-                                e->buf<uint8_t>("mx8_ks"), e->buf<uint8_t>("mx8_vt"), e->buf<uint8_t>("mx8_vs")};
-  HIP_TRY(mc::launch_attn_quantize_mx8(a, im, s));
-  HIP_TRY(mc::launch_attention_mx8(a, im, s));
-  return MC_OK;
-}
-// The frame-block causal form (mc_set_causal_blocks): the same operands as attend(e, "qkv", ..., qkv_keys(e)), on
-// attention_band.hip with the block in tokens of the grid in force
-mc_status attend_band(const mc_engine* e, bf16_t* O, hipStream_t s) {
-  const Keys keys = qkv_keys(e);
-  mc::AttnParams a;
-  memset(&a, 0, sizeof(a));
-  a.Q = e->buf<bf16_t>("qkv"); a.ldq = keys.ld; a.K = keys.k; a.ldk = keys.ld; a.V = keys.v; a.ldv = keys.ld;
-  a.O = O; a.ldo = e->d;
-  a.Lq_pad = e->Lp; a.n_heads = e->H; a.shard_rows = keys.rows; a.shard_valid = keys.valid; a.n_shards = 1;
-  a.scale = 1.0f / std::sqrt(128.0f);   // head_dim is fixed at 128
+  const bf16_t* Q = e->buf<bf16_t>("qkv");
+  if (!e->attn_mx8 && !e->causal_frames) return attend(e, Q, keys.ld, O, keys, nullptr, nullptr, s);
+  const mc::AttnParams a = mc::attn_params(Q, keys.ld, O, e->d, e->Lp, e->H, keys, mc::kAttnScale, nullptr, nullptr);
+  if (e->attn_mx8) {
+    const mc::AttnMx8Images im = {e->buf<uint8_t>("mx8_q"), e->buf<uint8_t>("mx8_qs"), e->buf<uint8_t>("mx8_k"),
+                                  e->buf<uint8_t>("mx8_ks"), e->buf<uint8_t>("mx8_vt"), e->buf<uint8_t>("mx8_vs")};
+    HIP_TRY(mc::launch_attn_quantize_mx8(a, im, s));
+    HIP_TRY(mc::launch_attention_mx8(a, im, s));
+    return MC_OK;
+  }
   const long block_tokens = (long)e->causal_frames * (e->cfg.latent_h / 2) * (e->cfg.latent_w / 2);
   const mc::AttnBand band = {(int)std::min<long>(block_tokens, e->Lp), e->causal_window};   // >= valid: plain attention either way
   HIP_TRY(mc::launch_attention_band(a, band, s));
@@ -1265,9 +1256,7 @@ static mc_status block_post_self(mc_engine* e, const Layer& l, const float* em, 
   // ---- self attention over the full sequence
   if (!e->sp) {
     Prof pr(e, MC_PROF_ATTN_SELF, s);
-    if (e->attn_mx8) MC_TRY(attend_mx8(e, ao, s));
-    else if (e->causal_frames) MC_TRY(attend_band(e, ao, s));
-    else MC_TRY(attend(e, e->buf<bf16_t>("qkv"), 3 * d, ao, qkv_keys(e), nullptr, nullptr, s));
+    MC_TRY(attend_self(e, ao, s));
   } else {
     // whatever the caller has not attended yet (mc_block_attn_local / mc_block_attn_round): the remaining gather rounds
     attn_chain_open(e, layer);

@@ -612,15 +612,7 @@ hipError_t launch_linear_bf16(const Linear& l, RowRange out, const bf16_t* A, lo
 
 hipError_t launch_attention_keys(const bf16_t* Q, long ldq, bf16_t* O, long ldo, int q_rows_pad, int heads, const Keys& keys,
                                  const float* lse_in, float* lse_out, hipStream_t s) {
-  AttnParams a;
-  memset(&a, 0, sizeof(a));
-  a.Q = Q; a.ldq = ldq; a.O = O; a.ldo = ldo;
-  a.K = keys.k; a.ldk = keys.ld; a.k_shard_stride = keys.stride;
-  a.V = keys.v; a.ldv = keys.ld; a.v_shard_stride = keys.stride;
-  a.Lq_pad = q_rows_pad; a.n_heads = heads; a.scale = 1.0f / std::sqrt(128.0f);   // head_dim is fixed at 128
-  a.shard_rows = keys.rows; a.shard_valid = keys.valid; a.n_shards = keys.n_shards; a.skip_shard_p1 = keys.skip_shard_p1;
-  a.lse_in = lse_in; a.lse_out = lse_out;
-  return launch_attention(a, s);
+  return launch_attention(attn_params(Q, ldq, O, ldo, q_rows_pad, heads, keys, kAttnScale, lse_in, lse_out), s);
 }
 
 }  // namespace mc

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <cstring>
 #include <map>
@@ -269,8 +270,23 @@ struct Keys {
   long ld, stride;
   int rows, valid, n_shards, skip_shard_p1;
 };
-// q_rows_pad query rows of Q over one key set -> O.  lse_out: keep the log2-sum-exp of this launch; lse_in: O already holds the
-// result over other keys with that log2-sum-exp, merge with it.
+const float kAttnScale = 1.0f / std::sqrt(128.0f);   // the softmax scale of the engines: head_dim is fixed at 128
+// The AttnParams of q_rows_pad query rows of Q over one key set -> O: the one place that zero-fills the struct and names every
+// field (K and V share the key set's leading dimension and shard stride).
+inline AttnParams attn_params(const bf16_t* Q, long ldq, bf16_t* O, long ldo, int q_rows_pad, int heads, const Keys& keys, float scale,
+                              const float* lse_in, float* lse_out) {
+  AttnParams a;
+  memset(&a, 0, sizeof(a));
+  a.Q = Q; a.ldq = ldq; a.O = O; a.ldo = ldo;
+  a.K = keys.k; a.ldk = keys.ld; a.k_shard_stride = keys.stride;
+  a.V = keys.v; a.ldv = keys.ld; a.v_shard_stride = keys.stride;
+  a.Lq_pad = q_rows_pad; a.n_heads = heads; a.scale = scale;
+  a.shard_rows = keys.rows; a.shard_valid = keys.valid; a.n_shards = keys.n_shards; a.skip_shard_p1 = keys.skip_shard_p1;
+  a.lse_in = lse_in; a.lse_out = lse_out;
+  return a;
+}
+// The launch of that with kAttnScale.  lse_out: keep the log2-sum-exp of this launch; lse_in: O already holds the result over
+// other keys with that log2-sum-exp, merge with it.
 hipError_t launch_attention_keys(const bf16_t* Q, long ldq, bf16_t* O, long ldo, int q_rows_pad, int heads, const Keys& keys,
                                  const float* lse_in, float* lse_out, hipStream_t s);
 

@@ -290,18 +290,20 @@ hipError_t launch_adapter_merge(const bf16_t* base, long ld_base, bf16_t* out, l
 // dst[i] = fp32(src[i]), i < n: src fp32 (a copy) or bf16 (widened exactly)
 hipError_t launch_widen_f32(const void* src, int src_f32, float* dst, size_t n, hipStream_t stream);
 
-// ---------------------------------------------------------------- attention (attention.hip)
+// ---------------------------------------------------------------- attention (attention_v3.hip, attention_v5.hip,
+// attention_mx8.hip, attention_band.hip; the tile geometry v3 and band share: attention_tile.h)
 struct AttnParams {
   const bf16_t* Q; long ldq;
   const bf16_t* K; long ldk; long k_shard_stride;
   const bf16_t* V; long ldv; long v_shard_stride;
   bf16_t* O; long ldo;
-  int Lq_pad;       // query rows, multiple of 256
+  int Lq_pad;       // query rows, a multiple of 256 for every kernel (v3, v5 and mx8 hand a workgroup 256 rows, band two
+                    // workgroups 128 each)
   int n_heads;      // head_dim is fixed at 128
   int shard_rows;   // rows per KV shard in memory (multiple of 64)
   int shard_valid;  // valid keys at the start of every shard
   int n_shards;
-  float scale;      // softmax scale (1/sqrt(128))
+  float scale;      // softmax scale (the engines pass host.h's kAttnScale)
   // Two-phase attention (sequence parallel: the local K/V shard is attended while the other shards are still in
   // flight over xGMI, the rest afterwards).  All three default to "off" when the struct is zero-filled.
   int skip_shard_p1;    // k + 1: shard k is left out of the key sequence; 0: none
@@ -310,10 +312,30 @@ struct AttnParams {
                         // lse_in; the kernel merges both and writes the combined O (and lse_out if given)
 };
 // K/V rows in [shard_valid, shard_rows) are read (and masked) but must hold finite values.
+// The argument contract, stated once.  Every launcher returns hipErrorInvalidValue, with nothing launched, unless its kernel's
+// *_supports holds; each of those is attention_shape_ok, for band and mx8 attention_plain_form, and the kernel's own conditions.
+//   shape: what all four kernels need -- whole 256-row query blocks, whole 64-key tiles, rows fetched 16 bytes at a time
+inline bool attention_shape_ok(const AttnParams& p) {
+  return p.Lq_pad > 0 && (p.Lq_pad % 256) == 0 && (p.shard_rows % 64) == 0 && p.shard_valid >= 1 && p.shard_valid <= p.shard_rows &&
+         p.n_heads > 0 && p.n_shards >= 1 && (p.ldq % 8) == 0 && (p.ldk % 8) == 0 && (p.ldv % 8) == 0;
+}
+//   plain form: what band and mx8 serve of it -- one key shard, no skip, no log-sum-exp in or out, 16-byte rows of O, no row
+//   shorter than its n_heads * 128 columns, Q / K / V / O non-null and 16-byte aligned
+inline bool attention_plain_form(const AttnParams& p) {
+  const auto al16 = [](const void* q) { return q && ((uintptr_t)q & 15) == 0; };
+  const size_t d = (size_t)p.n_heads * 128;   // (compared as unsigned, as ever: a negative ld is no shorter than d)
+  return p.n_shards == 1 && p.skip_shard_p1 == 0 && !p.lse_in && !p.lse_out && (p.ldo % 8) == 0 && (size_t)p.ldq >= d &&
+         (size_t)p.ldk >= d && (size_t)p.ldv >= d && (size_t)p.ldo >= d && al16(p.Q) && al16(p.K) && al16(p.V) && al16(p.O);
+}
 hipError_t launch_attention(const AttnParams& p, hipStream_t stream);     // picks a kernel
-hipError_t launch_attention_v5(const AttnParams& p, hipStream_t stream);  // 4 waves x 64 rows, one wave per SIMD, hand-scheduled (round 3)
-bool attention_v5_supports(const AttnParams& p);                          // K / V span within 32-bit byte offsets
-hipError_t launch_attention_v3(const AttnParams& p, hipStream_t stream);  // 8 waves x 32 rows, pipelined, 32x32x16 MFMA (round 1)
+// 4 waves x 64 rows, one wave per SIMD, hand-scheduled (round 3).  Its own conditions: ldo % 8, O and both lse arrays 16-byte
+// aligned (null counts), the K / V span and the shard strides within 32-bit byte offsets, a shard left to visit after the skip
+hipError_t launch_attention_v5(const AttnParams& p, hipStream_t stream);
+bool attention_v5_supports(const AttnParams& p);
+// 8 waves x 32 rows, pipelined, 32x32x16 MFMA (round 1).  Its own conditions: ldo % 4, a 64-key tile of K and of V within 2^31
+// bytes; it checks no pointer and not the skip (launch_attention refuses a skip that leaves no shard before it picks a kernel)
+hipError_t launch_attention_v3(const AttnParams& p, hipStream_t stream);
+bool attention_v3_supports(const AttnParams& p);
 extern int g_attn_kernel;  // 0: by support (see launch_attention), 3: attention_v3.hip, 5: attention_v5.hip where it applies
 
 // ---------------------------------------------------------------- MX fp8 self-attention (attention_mx8.hip; option "attn_mx8")
@@ -325,9 +347,8 @@ extern int g_attn_kernel;  // 0: by support (see launch_attention), 3: attention
 struct AttnMx8Images {
   uint8_t *q, *qs, *k, *ks, *vt, *vs;
 };
-// Both launchers take the AttnParams of launch_attention and serve one form of it: n_shards == 1, no skip_shard_p1, no lse_in /
-// lse_out, Lq_pad % 256 == 0, shard_rows % 64 == 0, 1 <= shard_valid <= shard_rows, ldq / ldk / ldv / ldo % 8 == 0, 16-byte
-// aligned operands and images, Lq_pad * d and shard_rows * d below 2^32.  Anything else: hipErrorInvalidValue, nothing launched.
+// Both launchers take the AttnParams of launch_attention in its plain form (attention_shape_ok, attention_plain_form); their
+// own conditions: non-null 16-byte aligned images, Lq_pad * d and shard_rows * d below 2^32.
 bool attention_mx8_supports(const AttnParams& p, const AttnMx8Images& im);
 hipError_t launch_attn_quantize_mx8(const AttnParams& p, const AttnMx8Images& im, hipStream_t stream);   // bf16 Q, K, V -> the images
 hipError_t launch_attention_mx8(const AttnParams& p, const AttnMx8Images& im, hipStream_t stream);       // the images -> O (bf16)
@@ -337,10 +358,9 @@ hipError_t launch_attention_mx8(const AttnParams& p, const AttnMx8Images& im, hi
 // hi(b) = min((b + 1) block_tokens, shard_valid), lo(b) = window_blocks ? max(0, b - window_blocks + 1) block_tokens : 0.
 // Padding rows are rows of the last valid block (finite output); block_tokens >= shard_valid is plain attention.
 struct AttnBand { int block_tokens; int window_blocks; };
-// The AttnParams of launch_attention, one form of it: n_shards == 1, no skip_shard_p1, no lse_in / lse_out, Lq_pad % 256 == 0,
-// shard_rows % 64 == 0, 1 <= shard_valid <= shard_rows, ldq / ldk / ldv / ldo % 8 == 0 and >= n_heads * 128, 16-byte aligned
-// operands, block_tokens >= 1, window_blocks >= 0, Lq_pad * ld and shard_rows * ld within 32-bit byte offsets (and, with a
-// window, at most 16383 query tiles of 128 rows).  Anything else: hipErrorInvalidValue, nothing launched.
+// The AttnParams of launch_attention in its plain form (attention_shape_ok, attention_plain_form); its own conditions:
+// block_tokens >= 1, window_blocks >= 0, Lq_pad * ld and shard_rows * ld within 32-bit byte offsets and, with a window, at most
+// 16383 query tiles of 128 rows.
 bool attention_band_supports(const AttnParams& p, const AttnBand& b);
 hipError_t launch_attention_band(const AttnParams& p, const AttnBand& b, hipStream_t stream);
 

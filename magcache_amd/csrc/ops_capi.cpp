@@ -15,6 +15,17 @@ static mc::GemmParams gp(const bf16_t* A, long lda, const bf16_t* W, long ldw, c
   return p;
 }
 
+// The AttnParams of an mc_op_attention* call over the caller's buffers, through the one builder (host.h: attn_params).  The C
+// ABI names V's leading dimension and shard stride on their own; a key set has one of each, so those two are set after it.
+static mc::AttnParams attn_op(const void* Q, long ldq, const void* K, long ldk, long kss, const void* V, long ldv, long vss, void* O,
+                              long ldo, int Lq_pad, int n_heads, int rows, int valid, int n_shards, float scale, int skip_shard_p1 = 0,
+                              const float* lse_in = nullptr, float* lse_out = nullptr) {
+  const mc::Keys keys = {(const bf16_t*)K, (const bf16_t*)V, ldk, kss, rows, valid, n_shards, skip_shard_p1};
+  mc::AttnParams a = mc::attn_params((const bf16_t*)Q, ldq, (bf16_t*)O, ldo, Lq_pad, n_heads, keys, scale, lse_in, lse_out);
+  a.ldv = ldv; a.v_shard_stride = vss;
+  return a;
+}
+
 extern "C" {
 
 const char* mc_last_error(void) { return mc::last_error(); }
@@ -124,12 +135,7 @@ mc_status mc_op_set_splitk_workspace(void* ws_dev, size_t bytes) {
 mc_status mc_op_attention(const void* Q, long ldq, const void* K, long ldk, long kss, const void* V, long ldv,
                           long vss, void* O, long ldo, int Lq_pad, int n_heads, int shard_rows, int shard_valid,
                           int n_shards, float scale, mc_stream s) {
-  mc::AttnParams a;
-  memset(&a, 0, sizeof(a));
-  a.Q = (const bf16_t*)Q; a.ldq = ldq; a.K = (const bf16_t*)K; a.ldk = ldk; a.k_shard_stride = kss;
-  a.V = (const bf16_t*)V; a.ldv = ldv; a.v_shard_stride = vss; a.O = (bf16_t*)O; a.ldo = ldo;
-  a.Lq_pad = Lq_pad; a.n_heads = n_heads; a.shard_rows = shard_rows; a.shard_valid = shard_valid;
-  a.n_shards = n_shards; a.scale = scale;
+  const mc::AttnParams a = attn_op(Q, ldq, K, ldk, kss, V, ldv, vss, O, ldo, Lq_pad, n_heads, shard_rows, shard_valid, n_shards, scale);
   hipError_t err = mc::launch_attention(a, (hipStream_t)s);
   if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "attention: unsupported shape");
   HIP_TRY(err);
@@ -139,11 +145,7 @@ mc_status mc_op_attention(const void* Q, long ldq, const void* K, long ldk, long
 // frame-block causal / windowed self-attention (attention_band.hip)
 mc_status mc_op_attention_band(const void* Q, long ldq, const void* K, long ldk, const void* V, long ldv, void* O, long ldo, int Lq_pad,
                                int n_heads, int rows, int valid, int block_tokens, int window_blocks, float scale, mc_stream s) {
-  mc::AttnParams a;
-  memset(&a, 0, sizeof(a));
-  a.Q = (const bf16_t*)Q; a.ldq = ldq; a.K = (const bf16_t*)K; a.ldk = ldk; a.V = (const bf16_t*)V; a.ldv = ldv;
-  a.O = (bf16_t*)O; a.ldo = ldo;
-  a.Lq_pad = Lq_pad; a.n_heads = n_heads; a.shard_rows = rows; a.shard_valid = valid; a.n_shards = 1; a.scale = scale;
+  const mc::AttnParams a = attn_op(Q, ldq, K, ldk, 0, V, ldv, 0, O, ldo, Lq_pad, n_heads, rows, valid, 1, scale);
   hipError_t err = mc::launch_attention_band(a, mc::AttnBand{block_tokens, window_blocks}, (hipStream_t)s);
   if (err == hipErrorInvalidValue)
     return fail(MC_EINVAL, "attention_band: needs Lq_pad %% 256 == 0, rows %% 64 == 0, 1 <= valid <= rows, leading dimensions %% 8 == 0 "
@@ -161,12 +163,8 @@ static const char* kAttnMx8Refusal =
 mc_status mc_op_attn_quantize_mx8(const void* Q, long ldq, const void* K, long ldk, const void* V, long ldv, int Lq_pad, int n_heads,
                                   int rows, int valid, float scale, void* q_img, void* q_sc, void* k_img, void* k_sc, void* vt_img,
                                   void* v_sc, mc_stream s) {
-  mc::AttnParams a;
-  memset(&a, 0, sizeof(a));
   // the pre-pass writes no O: its checks see the query rows in O's place
-  a.Q = (const bf16_t*)Q; a.ldq = ldq; a.K = (const bf16_t*)K; a.ldk = ldk; a.V = (const bf16_t*)V; a.ldv = ldv;
-  a.O = (bf16_t*)Q; a.ldo = ldq;
-  a.Lq_pad = Lq_pad; a.n_heads = n_heads; a.shard_rows = rows; a.shard_valid = valid; a.n_shards = 1; a.scale = scale;
+  const mc::AttnParams a = attn_op(Q, ldq, K, ldk, 0, V, ldv, 0, (void*)Q, ldq, Lq_pad, n_heads, rows, valid, 1, scale);
   const mc::AttnMx8Images im = {(uint8_t*)q_img, (uint8_t*)q_sc, (uint8_t*)k_img, (uint8_t*)k_sc, (uint8_t*)vt_img, (uint8_t*)v_sc};
   hipError_t err = mc::launch_attn_quantize_mx8(a, im, (hipStream_t)s);
   if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "attn_quantize_mx8: %s", kAttnMx8Refusal);
@@ -177,13 +175,9 @@ mc_status mc_op_attn_quantize_mx8(const void* Q, long ldq, const void* K, long l
 mc_status mc_op_attention_mx8(const void* q_img, const void* q_sc, const void* k_img, const void* k_sc, const void* vt_img,
                               const void* v_sc, void* O, long ldo, int Lq_pad, int n_heads, int rows, int valid, int n_shards,
                               const float* lse, mc_stream s) {
-  mc::AttnParams a;
-  memset(&a, 0, sizeof(a));
-  // the kernel reads the images only: its checks see O in the place of the bf16 operands
-  a.Q = a.K = a.V = (const bf16_t*)O; a.ldq = a.ldk = a.ldv = ldo;
-  a.O = (bf16_t*)O; a.ldo = ldo;
-  a.Lq_pad = Lq_pad; a.n_heads = n_heads; a.shard_rows = rows; a.shard_valid = valid; a.n_shards = n_shards;
-  a.lse_in = lse;   // (the softmax scale is in the q image already)
+  // the kernel reads the images only: its checks see O in the place of the bf16 operands; n_shards and lse are passed to be
+  // refused (any shard count but 1, any lse); the softmax scale is in the q image already
+  const mc::AttnParams a = attn_op(O, ldo, O, ldo, 0, O, ldo, 0, O, ldo, Lq_pad, n_heads, rows, valid, n_shards, 0.f, 0, lse);
   const mc::AttnMx8Images im = {(uint8_t*)q_img, (uint8_t*)q_sc, (uint8_t*)k_img, (uint8_t*)k_sc, (uint8_t*)vt_img, (uint8_t*)v_sc};
   hipError_t err = mc::launch_attention_mx8(a, im, (hipStream_t)s);
   if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "attention_mx8: %s", kAttnMx8Refusal);
@@ -291,13 +285,8 @@ mc_status mc_op_attention_partial(const void* Q, long ldq, const void* K, long l
                                   long vss, void* O, long ldo, int Lq_pad, int n_heads, int shard_rows,
                                   int shard_valid, int n_shards, float scale, int skip_shard, float* lse_out,
                                   const float* lse_in, mc_stream s) {
-  mc::AttnParams a;
-  memset(&a, 0, sizeof(a));
-  a.Q = (const bf16_t*)Q; a.ldq = ldq; a.K = (const bf16_t*)K; a.ldk = ldk; a.k_shard_stride = kss;
-  a.V = (const bf16_t*)V; a.ldv = ldv; a.v_shard_stride = vss; a.O = (bf16_t*)O; a.ldo = ldo;
-  a.Lq_pad = Lq_pad; a.n_heads = n_heads; a.shard_rows = shard_rows; a.shard_valid = shard_valid;
-  a.n_shards = n_shards; a.scale = scale;
-  a.skip_shard_p1 = skip_shard >= 0 ? skip_shard + 1 : 0; a.lse_out = lse_out; a.lse_in = lse_in;
+  const mc::AttnParams a = attn_op(Q, ldq, K, ldk, kss, V, ldv, vss, O, ldo, Lq_pad, n_heads, shard_rows, shard_valid, n_shards, scale,
+                                   skip_shard >= 0 ? skip_shard + 1 : 0, lse_in, lse_out);
   hipError_t err = mc::launch_attention(a, (hipStream_t)s);
   if (err == hipErrorInvalidValue) return fail(MC_EINVAL, "attention: unsupported shape / shard selection");
   HIP_TRY(err);

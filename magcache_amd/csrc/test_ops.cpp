@@ -4,6 +4,8 @@
 // hipError_t as an int (hipSuccess = 0, hipErrorInvalidValue = 1): no logic lives here, so what the tests exercise is the
 // launcher's own host checks and the kernel objects (elementwise.hip.o, gemm_mxfp8.hip.o, gemm_fp8_big.hip.o,
 // magcache_ops.hip.o) the shipped library links too.
+#include <string>
+
 #include "ops.h"
 
 using mc::bf16_t;
@@ -237,6 +239,27 @@ int mc_test_attn_merge(const void* const* o_parts, const float* const* lse_parts
                        int rows_pad, int d, void* s) {
   return (int)mc::launch_attn_merge((const bf16_t* const*)o_parts, lse_parts, n, (bf16_t*)out, ldo, rows, rows_pad, d,
                                     (hipStream_t)s);
+}
+
+// The argument contract of an attention launcher (ops.h), asked without a launch: 1 / 0 = the predicate of `kernel` ("v3",
+// "v5", "band", "mx8") accepts / refuses these arguments, -1 = no such kernel.  Nothing is dereferenced.
+int mc_test_attention_accepts(const char* kernel, const void* Q, long ldq, const void* K, long ldk, long kss, const void* V, long ldv,
+                              long vss, void* O, long ldo, int Lq_pad, int n_heads, int shard_rows, int shard_valid, int n_shards,
+                              int skip_shard_p1, const float* lse_in, float* lse_out, int block_tokens, int window_blocks, void* q_img,
+                              void* q_sc, void* k_img, void* k_sc, void* vt_img, void* v_sc) {
+  mc::AttnParams a = {};
+  a.Q = (const bf16_t*)Q; a.ldq = ldq; a.K = (const bf16_t*)K; a.ldk = ldk; a.k_shard_stride = kss;
+  a.V = (const bf16_t*)V; a.ldv = ldv; a.v_shard_stride = vss; a.O = (bf16_t*)O; a.ldo = ldo;
+  a.Lq_pad = Lq_pad; a.n_heads = n_heads; a.shard_rows = shard_rows; a.shard_valid = shard_valid; a.n_shards = n_shards;
+  a.skip_shard_p1 = skip_shard_p1; a.lse_in = lse_in; a.lse_out = lse_out;
+  const std::string k = kernel;
+  if (k == "v3") return mc::attention_v3_supports(a);
+  if (k == "v5") return mc::attention_v5_supports(a);
+  if (k == "band") return mc::attention_band_supports(a, mc::AttnBand{block_tokens, window_blocks});
+  if (k == "mx8")
+    return mc::attention_mx8_supports(a, mc::AttnMx8Images{(uint8_t*)q_img, (uint8_t*)q_sc, (uint8_t*)k_img, (uint8_t*)k_sc,
+                                                           (uint8_t*)vt_img, (uint8_t*)v_sc});
+  return -1;
 }
 
 }  // extern "C"

@@ -250,6 +250,9 @@ TEST_SIGNATURES = {
     "mc_test_rope_table_from_cos_sin": [_vp, _vp, _l, _i, _vp, _vp],
     "mc_test_cfg_euler": [_vp, _vp, _f, _f, _vp, _vp, _sz, _vp],
     "mc_test_attn_merge": [_vp, _vp, _i, _vp, _l, _i, _i, _i, _vp],
+    # no launch: 1 / 0 = the kernel's predicate accepts / refuses the arguments (tests/test_attention_contract_cpu.py)
+    "mc_test_attention_accepts": [C.c_char_p, _vp, _l, _vp, _l, _l, _vp, _l, _l, _vp, _l, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i,
+                                  _vp, _vp, _vp, _vp, _vp, _vp],
 }
 _test_bound = False
 
