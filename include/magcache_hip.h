@@ -170,7 +170,8 @@ mc_status mc_create(const mc_config* cfg, mc_engine** out);
  * mc_engine_attn_mx8, mc_op_attn_quantize_mx8, mc_op_attention_mx8); 0.8 adds token_timestep_sets (and the calls
  * mc_engine_token_timestep_sets, mc_op_gemm_bf16_resid_sets); the adapter kinds add calls only: mc_lora_set_kron / _set_hada /
  * _set_magnitude, mc_op_adapter_merge / _scratch; the frame-block causal self-attention adds calls only: mc_set_causal_blocks,
- * mc_engine_causal_blocks, mc_op_attention_band; mc_version() names the library's. */
+ * mc_engine_causal_blocks, mc_op_attention_band; the tile-sparse self-attention adds calls only: mc_set_attention_tile_mask,
+ * mc_engine_attention_tile_mask, mc_op_attention_sparse; mc_version() names the library's. */
 mc_status mc_create_sized(const mc_config* cfg, size_t cfg_bytes, mc_engine** out);
 void mc_destroy(mc_engine* e);
 /* 1: this engine's quantised Linears are MXFP4 (it was created under mc_set_option("mx_fp4", 1) with fp8_linear 2 | 3); else 0 */
@@ -190,6 +191,24 @@ int mc_engine_attn_mx8(const mc_engine* e);
  * names which.  mc_engine_causal_blocks reads the two values back (NULL outputs are skipped). */
 mc_status mc_set_causal_blocks(mc_engine* e, int frames_per_block, int window_blocks);
 mc_status mc_engine_causal_blocks(const mc_engine* e, int* frames_per_block, int* window_blocks);
+/* Tile-sparse self-attention: one static block mask over (128-row query tile, 64-key tile) of the flattened sequence -- the
+ * contract training-free sparse video-DiT methods share (temporal decay, sink + local windows, per-head spatial / temporal
+ * heads, sliding tiles).  bits_host: uint32 [mask_heads][nqt][(nkt + 31) / 32] on the HOST, under the semantics stated at
+ * mc_op_attention_sparse; nqt and nkt must be Lp / 128 and Lp / 64 of the grid in force (Lp: the sequence padded to 256),
+ * mask_heads 1 or num_heads.  The self-attention of every block l >= dense_layers (a VACE block counts as the main layer it
+ * feeds) then runs on attention_sparse.hip; blocks below stay dense.  The library copies the mask to the device and builds the
+ * heavy-first order table there, both allocated at this call outside the workspace and freed on replace, off and mc_destroy.
+ * bits_host == NULL turns the feature off: every launch afterwards is the one an engine makes that never heard of the call.
+ * An approximation the caller chooses; cross-attention and the I2V image keys are untouched; it composes with MagCache (whose
+ * shipped ratios were calibrated on dense attention).  Between forwards only (MC_ESTATE between mc_embed and mc_head).
+ * MC_EINVAL: sizes that do not match the grid, a negative dense_layers, a mask in which a query tile that holds a valid row
+ * sees no key tile with a valid key, a sequence-parallel engine (the kernel has no log-sum-exp), an "attn_mx8" engine, or
+ * while mc_set_causal_blocks is on (which, in turn, is refused while a mask is set); the error text names which.  The mask does
+ * not follow mc_set_geometry: a forward whose Lp no longer matches it returns MC_ESTATE with nothing launched -- set it again
+ * or turn it off.  mc_engine_attention_tile_mask reads back the sizes and the density = visited (item, valid key tile) pairs
+ * over all of them (NULL outputs are skipped; mask_heads 0 = off). */
+mc_status mc_set_attention_tile_mask(mc_engine* e, const uint32_t* bits_host, int mask_heads, int nqt, int nkt, int dense_layers);
+mc_status mc_engine_attention_tile_mask(const mc_engine* e, int* mask_heads, int* nqt, int* nkt, int* dense_layers, double* density);
 size_t mc_workspace_bytes(const mc_engine* e);
 mc_status mc_set_workspace(mc_engine* e, void* ws_dev, size_t bytes);
 /* The latent grid as a property of the call (0.7).  mc_config.latent_f / _h / _w is the grid an engine STARTS with;
@@ -662,6 +681,24 @@ mc_status mc_op_attention(const void* Q_dev, long ldq, const void* K_dev, long l
 mc_status mc_op_attention_band(const void* Q_dev, long ldq, const void* K_dev, long ldk, const void* V_dev, long ldv, void* O_dev,
                                long ldo, int Lq_pad, int n_heads, int rows, int valid, int block_tokens, int window_blocks,
                                float scale, mc_stream stream);
+/* Tile-sparse self-attention (attention_sparse.hip): one key shard of `rows` rows (multiple of 64), the first `valid` of them
+ * keys; head_dim 128; O bf16 [Lq_pad][ldo].  With nqt = Lq_pad / 128, nkt = rows / 64, words = (nkt + 31) / 32:
+ *   - tile_mask_dev is uint32 [mask_heads][nqt][words] in device memory, mask_heads 1 (one mask for every head) or n_heads;
+ *   - query row i of head h sees key j iff j < valid and bit (j / 64) & 31 of word (j / 64) >> 5 of row
+ *     [mask_heads == 1 ? 0 : h][i / 128] is set;
+ *   - bits at key tiles >= nkt, and at tiles whose first key is >= valid, are ignored;
+ *   - a query tile that sees no key writes O = 0 exactly for its 128 rows;
+ *   - query rows >= valid (padding) get whatever their tile's mask row gives them: finite, nothing reads it;
+ *   - all bits set is plain attention.
+ * order_dev: NULL, or int32 [nqt * n_heads] in device memory, a permutation of the item ids qt * n_heads + head in the order the
+ * launch should start them (heaviest first); the result does not depend on it, bit for bit, and an entry out of range is
+ * clamped.  A workgroup visits exactly the set bits of its mask row: a launch costs about its density of the unmasked one
+ * (DESIGN 3.1d has what was measured and what was not).
+ * Refused with MC_EINVAL, nothing launched: what mc_op_attention_band refuses of the shape and the operands, a tile mask that is
+ * null or not 4-byte aligned, an order table that is not 4-byte aligned, mask_heads other than 1 or n_heads. */
+mc_status mc_op_attention_sparse(const void* Q_dev, long ldq, const void* K_dev, long ldk, const void* V_dev, long ldv, void* O_dev,
+                                 long ldo, int Lq_pad, int n_heads, int rows, int valid, const uint32_t* tile_mask_dev,
+                                 int mask_heads, const int32_t* order_dev, float scale, mc_stream stream);
 /* MX fp8 self-attention (option "attn_mx8"; attention_mx8.hip), d = n_heads * 128.  mc_op_attn_quantize_mx8 turns the bf16 q, k
  * and v rows into the six images mc_op_attention_mx8 reads: q_img [Lq_pad][d] e4m3 of q * scale * log2(e) and k_img [rows][d]
  * e4m3 (rows >= valid zero), each with rows * d / 32 E8M0 scale bytes, one per (row, 32 channels) (q_sc, k_sc); vt_img [d][rows]

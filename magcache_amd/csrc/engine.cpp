@@ -5,6 +5,7 @@
 // Nothing here allocates or synchronises during a forward: weights are converted once at
 // mc_set_weight, all scratch + the residual cache are carved from one caller-owned workspace, the
 // MagCache decision is made by the caller on the host (reference :277-292 never touches the GPU).
+#include <algorithm>
 #include <cmath>
 #include <cstddef>
 #include <memory>
@@ -41,6 +42,19 @@ struct mc_engine {
                                        // the option "attn_mx8" (never on a sequence-parallel engine)
   int causal_frames = 0;                // mc_set_causal_blocks: frames per causal block of the self-attention, 0 = off (plain attention)
   int causal_window = 0;                // ... and the blocks a query looks back over, 0 = all of them
+  // mc_set_attention_tile_mask: the device copies of the mask words and of the heavy-first order table (owned here, outside the
+  // workspace), the sizes they were built for and the first block that runs on attention_sparse.hip; mask_heads 0 = off
+  uint32_t* mask_bits = nullptr;
+  int32_t* mask_order = nullptr;
+  int mask_heads = 0, mask_nqt = 0, mask_nkt = 0, mask_dense_layers = 0;
+  double mask_density = 0.0;
+  void mask_drop() {
+    if (mask_bits) (void)hipFree(mask_bits);
+    if (mask_order) (void)hipFree(mask_order);
+    mask_bits = nullptr; mask_order = nullptr;
+    mask_heads = mask_nqt = mask_nkt = mask_dense_layers = 0;
+    mask_density = 0.0;
+  }
   int d, ffn, H, NL, L, Lr, Lp, P, rank, tok0, Kp;  // Kp = in_dim*4 padded to 64
   int ctx_rows;                                     // text_len padded to 64
   std::vector<Layer> layers;
@@ -441,12 +455,27 @@ mc_status attend(const mc_engine* e, const bf16_t* Q, long ldq, bf16_t* O, const
 //   option "attn_mx8"      the pre-pass quantises the q, k and v columns into the planned images, attention_mx8.hip reads the
 //                          images alone
 //   mc_set_causal_blocks   attention_band.hip with the block in tokens of the grid in force
+//   mc_set_attention_tile_mask   attention_sparse.hip over the engine's mask, for the blocks l >= dense_layers (l: the main
+//                          layer; a VACE block counts as the main layer it feeds)
 //   otherwise              attend() over the same operands
-mc_status attend_self(const mc_engine* e, bf16_t* O, hipStream_t s) {
+// (the three are exclusive: each setter refuses while another is on)
+mc_status tile_mask_fits(const mc_engine* e) {
+  if (e->mask_heads && (e->mask_nqt != e->Lp / 128 || e->mask_nkt != e->Lp / 64))
+    return fail(MC_ESTATE, "the attention tile mask was set for %d x %d tiles (a sequence padded to %d rows) and the grid in force pads "
+                           "to %d rows: call mc_set_attention_tile_mask again, or with NULL", e->mask_nqt, e->mask_nkt, e->mask_nqt * 128, e->Lp);
+  return MC_OK;
+}
+mc_status attend_self(const mc_engine* e, int l, bf16_t* O, hipStream_t s) {
   const Keys keys = qkv_keys(e);
   const bf16_t* Q = e->buf<bf16_t>("qkv");
-  if (!e->attn_mx8 && !e->causal_frames) return attend(e, Q, keys.ld, O, keys, nullptr, nullptr, s);
+  const bool sparse = e->mask_heads && l >= e->mask_dense_layers;
+  if (!e->attn_mx8 && !e->causal_frames && !sparse) return attend(e, Q, keys.ld, O, keys, nullptr, nullptr, s);
   const mc::AttnParams a = mc::attn_params(Q, keys.ld, O, e->d, e->Lp, e->H, keys, mc::kAttnScale, nullptr, nullptr);
+  if (sparse) {
+    MC_TRY(tile_mask_fits(e));   // (every forward checks this before its first launch; here no launch may read past the mask)
+    HIP_TRY(mc::launch_attention_sparse(a, mc::AttnTileMask{e->mask_bits, e->mask_heads, e->mask_order}, s));
+    return MC_OK;
+  }
   if (e->attn_mx8) {
     const mc::AttnMx8Images im = {e->buf<uint8_t>("mx8_q"), e->buf<uint8_t>("mx8_qs"), e->buf<uint8_t>("mx8_k"),
                                   e->buf<uint8_t>("mx8_ks"), e->buf<uint8_t>("mx8_vt"), e->buf<uint8_t>("mx8_vs")};
@@ -652,6 +681,7 @@ mc_status mc_create(const mc_config* cfg, mc_engine** out) {
 void mc_destroy(mc_engine* e) {
   if (!e) return;
   e->weights.free_all();
+  e->mask_drop();
   for (hipEvent_t ev : e->prof_ev) (void)hipEventDestroy(ev);
   if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
   if (e->ev_join) (void)hipEventDestroy(e->ev_join);
@@ -679,6 +709,9 @@ mc_status mc_set_causal_blocks(mc_engine* e, int frames_per_block, int window_bl
   if (frames_per_block != 0 && e->attn_mx8)
     return fail(MC_EINVAL, "mc_set_causal_blocks: the engine was created under the option \"attn_mx8\" and the MX fp8 "
                            "self-attention kernel has no mask");
+  if (frames_per_block != 0 && e->mask_heads)
+    return fail(MC_EINVAL, "mc_set_causal_blocks: an attention tile mask is set (mc_set_attention_tile_mask); express the causal "
+                           "blocks in the mask, or turn the mask off first");
   e->causal_frames = frames_per_block;
   e->causal_window = frames_per_block ? window_blocks : 0;
   return MC_OK;
@@ -687,6 +720,81 @@ mc_status mc_engine_causal_blocks(const mc_engine* e, int* frames_per_block, int
   if (!e) return fail(MC_EINVAL, "null engine");
   if (frames_per_block) *frames_per_block = e->causal_frames;
   if (window_blocks) *window_blocks = e->causal_window;
+  return MC_OK;
+}
+
+mc_status mc_set_attention_tile_mask(mc_engine* e, const uint32_t* bits_host, int mask_heads, int nqt, int nkt, int dense_layers) {
+  if (!e) return fail(MC_EINVAL, "null engine");
+  if (e->phase_open) return fail(MC_ESTATE, "mc_set_attention_tile_mask between mc_embed and mc_head");
+  if (!bits_host) {   // off: earlier forwards may still be reading the copies
+    if (e->mask_heads) HIP_TRY(hipDeviceSynchronize());
+    e->mask_drop();
+    return MC_OK;
+  }
+  if (e->sp)
+    return fail(MC_EINVAL, "mc_set_attention_tile_mask: the engine is sequence parallel (sp_size %d%s) and the tile-sparse kernel "
+                           "has no log-sum-exp to merge key shards with", e->P, e->cfg.sp_phases ? ", sp_phases" : "");
+  if (e->attn_mx8)
+    return fail(MC_EINVAL, "mc_set_attention_tile_mask: the engine was created under the option \"attn_mx8\" and the MX fp8 "
+                           "self-attention kernel has no mask");
+  if (e->causal_frames)
+    return fail(MC_EINVAL, "mc_set_attention_tile_mask: mc_set_causal_blocks is on (%d frames per block); express the causal blocks "
+                           "in the mask, or turn them off first", e->causal_frames);
+  if (nqt != e->Lp / 128 || nkt != e->Lp / 64)
+    return fail(MC_EINVAL, "mc_set_attention_tile_mask: %d x %d tiles, the grid in force (%d rows padded to %d) has %d x %d", nqt, nkt,
+                e->Lr, e->Lp, e->Lp / 128, e->Lp / 64);
+  if (mask_heads != 1 && mask_heads != e->H)
+    return fail(MC_EINVAL, "mc_set_attention_tile_mask: mask_heads %d must be 1 or num_heads (%d)", mask_heads, e->H);
+  if (dense_layers < 0) return fail(MC_EINVAL, "mc_set_attention_tile_mask: dense_layers (%d) must be >= 0", dense_layers);
+  // visited valid key tiles per (mask head, query tile); a valid query tile with none is a bug of the mask, not a request
+  const int words = (nkt + 31) / 32, vq = (e->Lr + 127) / 128, vk = (e->Lr + 63) / 64;
+  std::vector<int> count((size_t)mask_heads * nqt);
+  long visited = 0;
+  for (int h = 0; h < mask_heads; ++h)
+    for (int qt = 0; qt < nqt; ++qt) {
+      const uint32_t* row = bits_host + ((size_t)h * nqt + qt) * words;
+      int c = 0;
+      for (int kt = 0; kt < vk; ++kt) c += (row[kt >> 5] >> (kt & 31)) & 1;
+      count[(size_t)h * nqt + qt] = c;
+      if (qt < vq) visited += c;
+      if (qt < vq && c == 0)
+        return fail(MC_EINVAL, "mc_set_attention_tile_mask: query tile %d of mask head %d holds valid rows and sees no key tile with a "
+                               "valid key", qt, h);
+    }
+  // heavy first: descending visited-tile count, ties to the higher tile, heads innermost
+  const int H = e->H;
+  std::vector<int32_t> order((size_t)nqt * H);
+  for (size_t i = 0; i < order.size(); ++i) order[i] = (int32_t)i;
+  auto cnt = [&](int32_t item) { return count[(size_t)(mask_heads == 1 ? 0 : item % H) * nqt + item / H]; };
+  std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
+    const int ca = cnt(a), cb = cnt(b);
+    return ca != cb ? ca > cb : a / H != b / H ? a / H > b / H : a < b;
+  });
+  uint32_t* bits_dev = nullptr;
+  int32_t* order_dev = nullptr;
+  const size_t bits_bytes = (size_t)mask_heads * nqt * words * 4, order_bytes = order.size() * 4;
+  if (hipMalloc((void**)&bits_dev, bits_bytes) != hipSuccess || hipMalloc((void**)&order_dev, order_bytes) != hipSuccess ||
+      hipMemcpy(bits_dev, bits_host, bits_bytes, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(order_dev, order.data(), order_bytes, hipMemcpyHostToDevice) != hipSuccess) {
+    if (bits_dev) (void)hipFree(bits_dev);
+    if (order_dev) (void)hipFree(order_dev);
+    return fail(MC_EHIP, "mc_set_attention_tile_mask: no device memory for the mask (%zu bytes) and its order table (%zu bytes)",
+                bits_bytes, order_bytes);
+  }
+  if (e->mask_heads) HIP_TRY(hipDeviceSynchronize());   // earlier forwards may still be reading the copies this one replaces
+  e->mask_drop();
+  e->mask_bits = bits_dev; e->mask_order = order_dev;
+  e->mask_heads = mask_heads; e->mask_nqt = nqt; e->mask_nkt = nkt; e->mask_dense_layers = dense_layers;
+  e->mask_density = (double)visited / ((double)mask_heads * vq * vk);
+  return MC_OK;
+}
+mc_status mc_engine_attention_tile_mask(const mc_engine* e, int* mask_heads, int* nqt, int* nkt, int* dense_layers, double* density) {
+  if (!e) return fail(MC_EINVAL, "null engine");
+  if (mask_heads) *mask_heads = e->mask_heads;
+  if (nqt) *nqt = e->mask_nqt;
+  if (nkt) *nkt = e->mask_nkt;
+  if (dense_layers) *dense_layers = e->mask_dense_layers;
+  if (density) *density = e->mask_density;
   return MC_OK;
 }
 
@@ -992,6 +1100,7 @@ static mc_status embed_text(mc_engine* e, const void* context_dev, mc_dtype ctx_
 static mc_status embed(mc_engine* e, const float* latent_dev, const float* t_dev, double t_host, const void* context_dev,
                        mc_dtype ctx_dtype, int ctx_len, float* x, hipStream_t s) {
   MC_TRY(check_ready(e));
+  MC_TRY(tile_mask_fits(e));
   if (!latent_dev) return fail(MC_EINVAL, "null input");
   if (e->cfg.clip_dim > 0 && !e->have_clip)
     return fail(MC_ESTATE, "i2v model: mc_set_clip_fea must run before the forward (reference assert :226-227)");
@@ -1256,7 +1365,7 @@ static mc_status block_post_self(mc_engine* e, const Layer& l, const float* em, 
   // ---- self attention over the full sequence
   if (!e->sp) {
     Prof pr(e, MC_PROF_ATTN_SELF, s);
-    MC_TRY(attend_self(e, ao, s));
+    MC_TRY(attend_self(e, l.index < e->NL ? l.index : (l.index - e->NL) * e->cfg.vace_stride, ao, s));
   } else {
     // whatever the caller has not attended yet (mc_block_attn_local / mc_block_attn_round): the remaining gather rounds
     attn_chain_open(e, layer);
@@ -1644,6 +1753,7 @@ static mc_status forward(mc_engine* e, const float* latent_dev, const float* t_d
   bf16_t* cq = e->buf<bf16_t>(keep || reuse ? "pair_cq" : "qkv");
   if (reuse) {
     MC_TRY(check_ready(e));
+    MC_TRY(tile_mask_fits(e));
     Prof pr(e, context_dev ? MC_PROF_EMBED : -1, s);
     MC_TRY(embed_text(e, context_dev, ctx_dtype, ctx_len, s));
   } else {

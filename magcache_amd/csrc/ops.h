@@ -291,7 +291,7 @@ hipError_t launch_adapter_merge(const bf16_t* base, long ld_base, bf16_t* out, l
 hipError_t launch_widen_f32(const void* src, int src_f32, float* dst, size_t n, hipStream_t stream);
 
 // ---------------------------------------------------------------- attention (attention_v3.hip, attention_v5.hip,
-// attention_mx8.hip, attention_band.hip; the tile geometry v3 and band share: attention_tile.h)
+// attention_mx8.hip, attention_band.hip, attention_sparse.hip; the tile geometry v3, band and sparse share: attention_tile.h)
 struct AttnParams {
   const bf16_t* Q; long ldq;
   const bf16_t* K; long ldk; long k_shard_stride;
@@ -363,6 +363,19 @@ struct AttnBand { int block_tokens; int window_blocks; };
 // 16383 query tiles of 128 rows.
 bool attention_band_supports(const AttnParams& p, const AttnBand& b);
 hipError_t launch_attention_band(const AttnParams& p, const AttnBand& b, hipStream_t stream);
+
+// ---------------------------------------------------------------- tile-sparse self-attention (attention_sparse.hip)
+// bits: uint32 [mask_heads][Lq_pad / 128][(shard_rows / 64 + 31) / 32] in device memory, mask_heads 1 or n_heads.  Query row i of
+// head h sees key j iff j < shard_valid and bit (j / 64) & 31 of word (j / 64) >> 5 of row [mask_heads == 1 ? 0 : h][i / 128] is
+// set; bits at padding tiles are ignored; a query tile that sees no key writes zeros; all bits set is plain attention.
+// order: null, or a device permutation of the item ids qt * n_heads + head that blockIdx.x indexes (clamped, never an address
+// out of range; the result does not depend on it).
+struct AttnTileMask { const uint32_t* bits; int mask_heads; const int32_t* order; };
+// The AttnParams of launch_attention in its plain form (attention_shape_ok, attention_plain_form); its own conditions:
+// Lq_pad * ld and shard_rows * ld within 32-bit byte offsets, bits non-null, bits and order 4-byte aligned, mask_heads 1 or
+// n_heads, fewer than 2^31 items.
+bool attention_sparse_supports(const AttnParams& p, const AttnTileMask& m);
+hipError_t launch_attention_sparse(const AttnParams& p, const AttnTileMask& m, hipStream_t stream);
 
 // ---------------------------------------------------------------- token-wise ops (elementwise.hip)
 // out[m,:] = bf16( LN(x[m,:]) * a + b ),  a = 1+scale (modulate) or weight (affine)

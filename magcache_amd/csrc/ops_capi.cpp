@@ -155,6 +155,20 @@ mc_status mc_op_attention_band(const void* Q, long ldq, const void* K, long ldk,
   return MC_OK;
 }
 
+// tile-sparse self-attention (attention_sparse.hip)
+mc_status mc_op_attention_sparse(const void* Q, long ldq, const void* K, long ldk, const void* V, long ldv, void* O, long ldo, int Lq_pad,
+                                 int n_heads, int rows, int valid, const uint32_t* tile_mask, int mask_heads, const int32_t* order,
+                                 float scale, mc_stream s) {
+  const mc::AttnParams a = attn_op(Q, ldq, K, ldk, 0, V, ldv, 0, O, ldo, Lq_pad, n_heads, rows, valid, 1, scale);
+  hipError_t err = mc::launch_attention_sparse(a, mc::AttnTileMask{tile_mask, mask_heads, order}, (hipStream_t)s);
+  if (err == hipErrorInvalidValue)
+    return fail(MC_EINVAL, "attention_sparse: needs Lq_pad %% 256 == 0, rows %% 64 == 0, 1 <= valid <= rows, leading dimensions %% 8 == 0 "
+                           "and >= n_heads * 128, operands non-null and 16-byte aligned, a non-null 4-byte aligned tile mask, "
+                           "mask_heads 1 or n_heads (%d), Lq_pad * ld and rows * ld within 32-bit byte offsets", mask_heads);
+  HIP_TRY(err);
+  return MC_OK;
+}
+
 // MX fp8 self-attention (attention_mx8.hip): the pre-pass and the kernel share one argument contract
 static const char* kAttnMx8Refusal =
     "needs Lq_pad % 256 == 0, rows % 64 == 0, 1 <= valid <= rows, leading dimensions % 8 == 0 and >= n_heads * 128, operands and "

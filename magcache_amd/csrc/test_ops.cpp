@@ -242,7 +242,7 @@ int mc_test_attn_merge(const void* const* o_parts, const float* const* lse_parts
 }
 
 // The argument contract of an attention launcher (ops.h), asked without a launch: 1 / 0 = the predicate of `kernel` ("v3",
-// "v5", "band", "mx8") accepts / refuses these arguments, -1 = no such kernel.  Nothing is dereferenced.
+// "v5", "band", "mx8", "sparse") accepts / refuses these arguments, -1 = no such kernel.  Nothing is dereferenced.
 int mc_test_attention_accepts(const char* kernel, const void* Q, long ldq, const void* K, long ldk, long kss, const void* V, long ldv,
                               long vss, void* O, long ldo, int Lq_pad, int n_heads, int shard_rows, int shard_valid, int n_shards,
                               int skip_shard_p1, const float* lse_in, float* lse_out, int block_tokens, int window_blocks, void* q_img,
@@ -256,6 +256,8 @@ int mc_test_attention_accepts(const char* kernel, const void* Q, long ldq, const
   if (k == "v3") return mc::attention_v3_supports(a);
   if (k == "v5") return mc::attention_v5_supports(a);
   if (k == "band") return mc::attention_band_supports(a, mc::AttnBand{block_tokens, window_blocks});
+  // "sparse": the mask words in q_img's place, the order table in q_sc's, mask_heads in block_tokens'
+  if (k == "sparse") return mc::attention_sparse_supports(a, mc::AttnTileMask{(const uint32_t*)q_img, block_tokens, (const int32_t*)q_sc});
   if (k == "mx8")
     return mc::attention_mx8_supports(a, mc::AttnMx8Images{(uint8_t*)q_img, (uint8_t*)q_sc, (uint8_t*)k_img, (uint8_t*)k_sc,
                                                            (uint8_t*)vt_img, (uint8_t*)v_sc});

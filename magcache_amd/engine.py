@@ -209,6 +209,31 @@ class Engine(EngineHost):
         check(self.lib.mc_engine_causal_blocks(self.h, C.byref(f), C.byref(w)))
         return f.value, w.value
 
+    # ---- tile-sparse self-attention
+    def set_attention_tile_mask(self, mask, dense_layers=0):
+        """Self-attention under a static block mask (mc_set_attention_tile_mask): mask is a bool tensor [mask_heads, Lp / 128,
+        Lp / 64] over (128-row query tile, 64-key tile) of the token sequence padded to Lp = a multiple of 256, mask_heads 1 or
+        num_heads (sparse_masks has builders); None turns it off (plain attention, the launches an engine makes that never
+        called this).  Blocks below dense_layers stay dense.  The mask belongs to the grid it was built for: after
+        set_geometry set it again (a forward under a stale mask raises).  Refused on a sharded engine, on an attn_mx8 engine,
+        while set_causal_blocks is on, and for a mask that leaves a valid query tile without a key."""
+        if mask is None:
+            check(self.lib.mc_set_attention_tile_mask(self.h, None, 0, 0, 0, 0))
+            return
+        from .sparse_masks import pack_tile_mask
+        m = torch.as_tensor(mask).detach().cpu()
+        if m.dtype != torch.bool or m.dim() != 3:
+            raise ValueError(f"set_attention_tile_mask: a bool tensor [mask_heads, Lp / 128, Lp / 64], got {m.dtype} {tuple(m.shape)}")
+        words = pack_tile_mask(m)                                       # int32 [mask_heads, nqt, words], host
+        check(self.lib.mc_set_attention_tile_mask(self.h, words.data_ptr(), m.shape[0], m.shape[1], m.shape[2], int(dense_layers)))
+
+    @property
+    def attention_tile_mask(self):
+        """(mask_heads, nqt, nkt, dense_layers, density) of the mask in force, or None"""
+        h, q, k, dl, dens = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_double()
+        check(self.lib.mc_engine_attention_tile_mask(self.h, C.byref(h), C.byref(q), C.byref(k), C.byref(dl), C.byref(dens)))
+        return (h.value, q.value, k.value, dl.value, dens.value) if h.value else None
+
     def residual(self, branch):
         """fp32 [seq_len/sp, dim] view of residual_cache[branch] (rows past the valid tokens cut off)."""
         d = self.cfg["dim"]

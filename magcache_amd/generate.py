@@ -124,6 +124,15 @@ def _parse_args(argv=None):
                         "0 = plain attention.  One device only")
     p.add_argument("--causal_window_blocks", type=int, default=0, metavar="W",
                    help="with --causal_block_frames: attend to the last W blocks only (0 = all earlier blocks)")
+    p.add_argument("--sparse_attention", type=str, default=None, metavar="decay[:DENSE[:SINK]]",
+                   help="training-free tile-sparse self-attention under a static block mask: 'decay' = the temporal-decay mask of "
+                        "sparse_masks.temporal_decay_tile_mask (frames nearer than DENSE whole, the first SINK frames always, a spatial "
+                        "window that halves as the frame distance doubles; default 1:1).  An approximation: it shortens the forwards "
+                        "MagCache does not skip, and the shipped mag_ratios were calibrated on DENSE attention.  One GPU; t2v tasks.")
+    p.add_argument("--sparse_dense_layers", type=int, default=0, metavar="N",
+                   help="with --sparse_attention: the first N blocks keep dense self-attention")
+    p.add_argument("--sparse_dense_steps", type=int, default=0, metavar="N",
+                   help="with --sparse_attention: the mask is set after the first N sampler steps; until then the engine is the plain one")
     # accepted for command-line compatibility; they configure parts that are not in this repository
     for flag, kw in (("--offload_model", dict(type=str2bool, default=None)), ("--ulysses_size", dict(type=int, default=1)),
                      ("--ring_size", dict(type=int, default=1)), ("--t5_fsdp", dict(action="store_true")),
@@ -176,6 +185,27 @@ def _context(path, prompt, seed, text_dim, device):
     return torch.randn(n, text_dim, generator=g).to(device)
 
 
+def _sparse_attention(args, model):
+    """--sparse_attention: sets the mask now (no dense steps) or returns the sampler callback that sets it after step
+    --sparse_dense_steps; None without the flag"""
+    if not args.sparse_attention:
+        return None
+    from .sparse_masks import temporal_decay_tile_mask
+    kind, *nums = args.sparse_attention.split(":")
+    if kind != "decay" or len(nums) > 2:
+        raise ValueError(f"--sparse_attention {args.sparse_attention!r}: decay[:DENSE[:SINK]]")
+    dense, sink = (int(nums[0]) if nums else 1), (int(nums[1]) if len(nums) > 1 else 1)
+
+    def turn_on():
+        model.set_attention_tile_mask(lambda g: temporal_decay_tile_mask(g, dense, sink), args.sparse_dense_layers)
+        logging.info(f"tile-sparse self-attention from block {args.sparse_dense_layers}: decay {dense}:{sink}, "
+                     f"density {model.engine.attention_tile_mask[4]:.3f}")
+    if args.sparse_dense_steps <= 0:
+        turn_on()
+        return None
+    return lambda i, _latent: turn_on() if i + 1 == args.sparse_dense_steps else None
+
+
 def generate(args):
     import torch
     import torch.distributed as dist
@@ -225,6 +255,7 @@ def generate(args):
                           sp_rank=layout.sp_rank if layout else 0, sp_size=layout.sp_size if layout else 1,
                           sp_group=layout.sp_group if layout else None, attn_mx8=args.attn_mx8,
                           causal_block_frames=args.causal_block_frames, causal_window_blocks=args.causal_window_blocks)
+    sparse_on = _sparse_attention(args, model)
 
     files = sorted(glob.glob(os.path.join(args.ckpt_dir or "", "*.safetensors")))
     if files:
@@ -278,7 +309,7 @@ def generate(args):
     t0 = time.perf_counter()
     latent = mca.sample(model, noise, ctx, ctx_null, sampling_steps=args.sample_steps, shift=args.sample_shift,
                         guide_scale=args.sample_guide_scale, solver=args.sample_solver, layout=layout,
-                        model_kwargs=extra, sigma_grid="upstream")
+                        model_kwargs=extra, sigma_grid="upstream", callback=sparse_on)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     logging.info(f"denoising: {dt:.2f} s, {args.sample_steps / dt:.3f} steps/s")

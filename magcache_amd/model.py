@@ -116,7 +116,7 @@ class WanModelHIP(LoraModel):
 
     def __init__(self, cfg, latent_grid, device="cuda:0", calibration=True, engine=None, sp_rank=0, sp_size=1,
                  sp_group=None, sp_phases=False, dynamic_geometry=False, token_timestep_sets=0, attn_mx8=False,
-                 causal_block_frames=0, causal_window_blocks=0):
+                 causal_block_frames=0, causal_window_blocks=0, attention_tile_mask=None, sparse_dense_layers=0):
         """token_timestep_sets (3..64): the engine's capacity of distinct per-token timesteps per forward -- one timestep per
         latent frame (wan22.frame_timesteps / sample_frames), several conditioning frames at their own noise levels.  0: two,
         what Wan2.2 TI2V's `mask * t` needs.
@@ -124,7 +124,11 @@ class WanModelHIP(LoraModel):
         causal_block_frames (>= 1): self-attention block-causal over blocks of that many latent frames, causal_window_blocks
         (>= 1) only over the last so many blocks (Engine.set_causal_blocks): set once here, kept across set_geometry
         (dynamic_geometry) because the engine counts the block in frames.  MagCache, CFG pairs and per-frame timesteps need
-        no change.  wan22.make_experts passes both keywords through."""
+        no change.  wan22.make_experts passes both keywords through.
+        attention_tile_mask: tile-sparse self-attention (Engine.set_attention_tile_mask) for the blocks >= sparse_dense_layers --
+        a bool tensor [mask_heads, Lp / 128, Lp / 64] for this grid, or a callable grid -> tensor (sparse_masks has builders),
+        which is called again for the new grid after set_geometry (dynamic_geometry); a tensor is not, and the first forward at
+        another grid raises.  set_attention_tile_mask changes or clears it later."""
         if token_timestep_sets:
             cfg = dict(cfg, token_timestep_sets=int(token_timestep_sets))
         self.cfg = dict(cfg)
@@ -144,8 +148,16 @@ class WanModelHIP(LoraModel):
         self.attn_mx8 = getattr(self.engine, "attn_mx8", False)     # (an engine passed in may predate the option)
         if causal_block_frames or causal_window_blocks:
             self.engine.set_causal_blocks(causal_block_frames, causal_window_blocks)
+        self._tile_mask, self._sparse_dense_layers = None, 0
+        if attention_tile_mask is not None:
+            self.set_attention_tile_mask(attention_tile_mask, sparse_dense_layers)
         self.device = self.engine.device
         self.sp_group = sp_group      # torch.distributed group of the ranks that share this token sequence
+
+    def set_attention_tile_mask(self, mask, dense_layers=0):
+        """a tensor, a callable grid -> tensor (kept, and asked again after set_geometry), or None for plain attention"""
+        self._tile_mask, self._sparse_dense_layers = (mask if callable(mask) else None), int(dense_layers)
+        self.engine.set_attention_tile_mask(mask(self.latent_grid) if callable(mask) else mask, dense_layers)
 
     def load_state_dict(self, state_dict):
         self.engine.load_weights(state_dict)
@@ -189,6 +201,8 @@ class WanModelHIP(LoraModel):
         self.check_token_timesteps()          # records of the old grid's forwards: "tok_t2" moves with the plan
         self.engine.set_geometry(grid)
         self.latent_grid = grid
+        if getattr(self, "_tile_mask", None) is not None:       # the callable form: the mask of the new grid
+            self.engine.set_attention_tile_mask(self._tile_mask(grid), self._sparse_dense_layers)
         self._ctx_keys, self._ctx_lru = [None, None], 0
         self._clip_key = self._vace_key = self._tok_t_key = None
         if follows:

@@ -1,7 +1,7 @@
 // Torch-free kernel A/B harness for the two MFMA-bound kernels at the Wan2.1-1.3B 480p shapes, through the C ABI.
 //
 //   kbench.bin <what> <rounds> <launches> libA.so [libB.so ...]
-//      what: gemm | attn | attn_mx8 | attn_band | calib | all
+//      what: gemm | attn | attn_mx8 | attn_band | attn_sparse | calib | all
 //
 // Every library given on the command line is dlopen'ed privately (RTLD_LOCAL), so build variants of
 // libmagcache_hip.so (tools/build_variants.py, tools/build_v5_variants.py, tools/build_gemm_v2_variants.py) are measured INTERLEAVED IN ONE PROCESS on the same
@@ -41,6 +41,7 @@ struct Lib {
   decltype(&mc_op_attn_quantize_mx8) quant_mx8;   // null in a library older than the MX fp8 attention (attn_mx8 only)
   decltype(&mc_op_attention_mx8) attn_mx8;
   decltype(&mc_op_attention_band) attn_band;      // null in a library older than the frame-block causal kernel (attn_band only)
+  decltype(&mc_op_attention_sparse) attn_sparse;  // null in a library older than the tile-sparse kernel (attn_sparse only)
   decltype(&mc_set_option) set_option;
   decltype(&mc_last_error) last_error;
 };
@@ -511,6 +512,178 @@ static void bench_attn_band(int Lq_pad, int H, int valid, int rounds, int launch
   for (void* p : {(void*)Q, (void*)K, (void*)V, (void*)O, (void*)Ob}) CK(hipFree(p));
 }
 
+// The tile-sparse kernel beside the unmasked launch (and, where a mask is a band rounded out to tiles, beside the band kernel)
+// on the same q, k, v -- library 0 only, all launches interleaved round by round.  Every mask carries the heavy-first order
+// table the engine would build for it.  Per mask: the time, its ratio to the unmasked launch, the density = visited (item,
+// valid key tile) pairs over all of them, and the time against the ideal "density x unmasked time".  Eight rows of the
+// temporal-decay mask are checked against an fp64 sum over their visible keys.
+static void bench_attn_sparse(int Lq_pad, int H, int valid, int rounds, int launches) {
+  const Lib& lib = g_libs[0];
+  if (!lib.attn_sparse || !lib.attn_band) {
+    fprintf(stderr, "%s: no mc_op_attention_sparse / mc_op_attention_band\n", lib.path.c_str());
+    exit(2);
+  }
+  const int F = 21, tpf = valid / F;   // 32760 = 21 latent frames of 1560 tokens
+  const int nqt = Lq_pad / 128, nkt = Lq_pad / 64, words = (nkt + 31) / 32, vk = (valid + 63) / 64;
+  typedef std::vector<uint32_t> Bits;   // [nqt][words]
+  auto span = [&](Bits& m, int qt, int k_lo, int k_hi) {   // keys k_lo .. k_hi (inclusive) -> their tiles
+    for (int kt = k_lo / 64; kt <= k_hi / 64; ++kt) m[(size_t)qt * words + (kt >> 5)] |= 1u << (kt & 31);
+  };
+  auto band_cover = [&](int win) {   // the tile cover of 21 causal blocks, window `win` (0: all earlier blocks)
+    Bits m((size_t)nqt * words, 0);
+    for (int qt = 0; qt < nqt; ++qt) {
+      const int b0 = std::min(qt * 128, valid - 1) / tpf, b1 = std::min(qt * 128 + 127, valid - 1) / tpf;
+      span(m, qt, win ? std::max(0, b0 - win + 1) * tpf : 0, std::min((b1 + 1) * tpf, valid) - 1);
+    }
+    return m;
+  };
+  auto decay_cover = [&](int dense, int sink) {   // sparse_masks.temporal_decay_tile_mask, the same intervals
+    Bits m((size_t)nqt * words, 0);
+    for (int qt = 0; qt * 128 < valid; ++qt) {
+      const int q0 = qt * 128, q1 = std::min(q0 + 127, valid - 1);
+      for (int fi = q0 / tpf; fi <= q1 / tpf; ++fi) {
+        const int a = std::max(q0, fi * tpf) - fi * tpf, b = std::min(q1, fi * tpf + tpf - 1) - fi * tpf;
+        for (int fj = 0; fj < F; ++fj) {
+          const int d = std::abs(fi - fj);
+          if (d < dense || fj < sink) { span(m, qt, fj * tpf, fj * tpf + tpf - 1); continue; }
+          int s = 1;
+          while ((dense << s) <= d) ++s;
+          const int w = (tpf + (1 << s) - 1) / (1 << s) - 1;
+          span(m, qt, fj * tpf + std::max(a - w, 0), fj * tpf + std::min(b + w, tpf - 1));
+        }
+      }
+    }
+    return m;
+  };
+  struct MaskCase { const char* name; Bits even, odd; int band_win; };   // odd empty: one mask for every head; band_win < 0: no band twin
+  const Bits ones((size_t)nqt * words, 0xffffffffu);
+  std::vector<MaskCase> cases = {{"all bits set", ones, {}, -1}, {"21 causal blocks", band_cover(0), {}, 0},
+                                 {"21 blocks, window 3", band_cover(3), {}, 3}, {"decay 1:1", decay_cover(1, 1), {}, -1},
+                                 {"decay 2:1", decay_cover(2, 1), {}, -1}, {"decay 1:1 | window 3", decay_cover(1, 1), band_cover(3), -1}};
+  const int NM = (int)cases.size();
+  const int D = H * 128;
+  const size_t n = (size_t)Lq_pad * D;
+  uint16_t *Q, *K, *V, *O, *Ob;
+  for (uint16_t** p : {&Q, &K, &V, &O, &Ob}) CK(hipMalloc(p, n * 2));
+  fill_bf16<<<2048, 256>>>(Q, n, 11, g_amp);
+  fill_bf16<<<2048, 256>>>(K, n, 12, g_amp);
+  fill_bf16<<<2048, 256>>>(V, n, 13, g_amp);
+  std::vector<uint32_t*> bits_dev(NM);
+  std::vector<int32_t*> order_dev(NM);
+  std::vector<double> density(NM);
+  for (int c = 0; c < NM; ++c) {
+    const int mh = cases[c].odd.empty() ? 1 : H;
+    Bits all;
+    for (int h = 0; h < mh; ++h) { const Bits& m = (h & 1) ? cases[c].odd : cases[c].even; all.insert(all.end(), m.begin(), m.end()); }
+    std::vector<int> count((size_t)mh * nqt, 0);
+    double visited = 0;
+    for (int r = 0; r < mh * nqt; ++r) {
+      for (int kt = 0; kt < vk; ++kt) count[r] += (all[(size_t)r * words + (kt >> 5)] >> (kt & 31)) & 1;
+      visited += count[r];
+    }
+    density[c] = visited / ((double)mh * nqt * vk);
+    std::vector<int32_t> order((size_t)nqt * H);
+    for (size_t i = 0; i < order.size(); ++i) order[i] = (int32_t)i;
+    auto cnt = [&](int32_t it) { return count[(size_t)(mh == 1 ? 0 : it % H) * nqt + it / H]; };
+    std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) {
+      return cnt(x) != cnt(y) ? cnt(x) > cnt(y) : x / H != y / H ? x / H > y / H : x < y;
+    });
+    CK(hipMalloc(&bits_dev[c], all.size() * 4));
+    CK(hipMalloc(&order_dev[c], order.size() * 4));
+    CK(hipMemcpy(bits_dev[c], all.data(), all.size() * 4, hipMemcpyHostToDevice));
+    CK(hipMemcpy(order_dev[c], order.data(), order.size() * 4, hipMemcpyHostToDevice));
+  }
+  CK(hipDeviceSynchronize());
+  const float scale = 1.0f / std::sqrt(128.0f);
+  // kinds: 0 unmasked, 1 .. NM the masks, NM + 1 / NM + 2 the band kernel at window 0 / 3
+  const int NK = NM + 3;
+  auto launch = [&](int kind) {
+    if (kind == 0) MCL(lib, lib.attn(Q, D, K, D, 0, V, D, 0, O, D, Lq_pad, H, Lq_pad, valid, 1, scale, nullptr));
+    else if (kind <= NM)
+      MCL(lib, lib.attn_sparse(Q, D, K, D, V, D, Ob, D, Lq_pad, H, Lq_pad, valid, bits_dev[kind - 1], cases[kind - 1].odd.empty() ? 1 : H,
+                               order_dev[kind - 1], scale, nullptr));
+    else MCL(lib, lib.attn_band(Q, D, K, D, V, D, Ob, D, Lq_pad, H, Lq_pad, valid, tpf, kind == NM + 1 ? 0 : 3, scale, nullptr));
+  };
+  printf("# attn_sparse: Lq_pad=%d heads=%d valid keys=%d\n", Lq_pad, H, valid);
+  hipEvent_t a, b;
+  CK(hipEventCreate(&a));
+  CK(hipEventCreate(&b));
+  float ms = 0;
+  CK(hipEventRecord(a, nullptr));
+  do {   // ~1 s warm-up of all of them
+    for (int kind = 0; kind < NK; ++kind) launch(kind);
+    CK(hipEventRecord(b, nullptr));
+    CK(hipEventSynchronize(b));
+    CK(hipEventElapsedTime(&ms, a, b));
+  } while (ms < 1000.f);
+  std::vector<std::vector<double>> t(NK);
+  for (int r = 0; r < rounds; ++r)
+    for (int kind = 0; kind < NK; ++kind) {
+      launch(kind);
+      CK(hipEventRecord(a, nullptr));
+      for (int i = 0; i < launches; ++i) launch(kind);
+      CK(hipEventRecord(b, nullptr));
+      CK(hipEventSynchronize(b));
+      CK(hipEventElapsedTime(&ms, a, b));
+      t[kind].push_back(ms / launches);
+    }
+  std::vector<double> med(NK);
+  for (int kind = 0; kind < NK; ++kind) {
+    std::sort(t[kind].begin(), t[kind].end());
+    med[kind] = t[kind][t[kind].size() / 2];
+  }
+  printf("%-24s median %8.4f ms %8.1f TF | min %8.4f ms\n", "attn (unmasked)", med[0], 4.0 * valid * (double)valid * D * 1e-12 / (med[0] * 1e-3), t[0][0]);
+  for (int kind = 1; kind <= NM; ++kind) {
+    const MaskCase& c = cases[kind - 1];
+    printf("%-24s median %8.4f ms | min %8.4f ms | x%.3f of unmasked | density %.4f, ideal %8.4f ms, measured / ideal %.3f", c.name, med[kind],
+           t[kind][0], med[kind] / med[0], density[kind - 1], density[kind - 1] * med[0], med[kind] / (density[kind - 1] * med[0]));
+    if (c.band_win >= 0) {
+      const int bk = c.band_win == 0 ? NM + 1 : NM + 2;
+      printf(" | band kernel %8.4f ms, sparse / band %.3f", med[bk], med[kind] / med[bk]);
+    }
+    printf("\n");
+  }
+  {   // spot check: the temporal-decay mask
+    const Bits& m = cases[3].even;
+    launch(4);
+    CK(hipDeviceSynchronize());
+    std::vector<uint16_t> hq(n), hk(n), hv(n), ho(n);
+    CK(hipMemcpy(hq.data(), Q, n * 2, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(hk.data(), K, n * 2, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(hv.data(), V, n * 2, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(ho.data(), Ob, n * 2, hipMemcpyDeviceToHost));
+    double num = 0, den = 0;
+    for (int i = 0; i < 8; ++i) {
+      const int row = (int)(((long)i * 4099 + 17) % valid), head = i % H;
+      std::vector<int> keys;
+      for (int k = 0; k < valid; ++k)
+        if ((m[(size_t)(row / 128) * words + (k / 64 >> 5)] >> (k / 64 & 31)) & 1) keys.push_back(k);
+      std::vector<double> s(keys.size());
+      double mx = -1e300, z = 0, acc[128] = {0};
+      for (size_t k = 0; k < keys.size(); ++k) {
+        double d = 0;
+        for (int j = 0; j < 128; ++j) d += (double)bf16_to_f(hq[(size_t)row * D + head * 128 + j]) * bf16_to_f(hk[(size_t)keys[k] * D + head * 128 + j]);
+        s[k] = d * scale;
+        mx = std::max(mx, s[k]);
+      }
+      for (size_t k = 0; k < keys.size(); ++k) {
+        const double pw = std::exp(s[k] - mx);
+        z += pw;
+        for (int j = 0; j < 128; ++j) acc[j] += pw * bf16_to_f(hv[(size_t)keys[k] * D + head * 128 + j]);
+      }
+      for (int j = 0; j < 128; ++j) {
+        const double got = bf16_to_f(ho[(size_t)row * D + head * 128 + j]), want = acc[j] / z;
+        num += (got - want) * (got - want);
+        den += want * want;
+      }
+    }
+    printf("  attn_sparse (%s) vs fp64 (8 rows): rel_l2 %.3e\n", cases[3].name, std::sqrt(num / den));
+  }
+  fflush(stdout);
+  for (void* p : {(void*)Q, (void*)K, (void*)V, (void*)O, (void*)Ob}) CK(hipFree(p));
+  for (int c = 0; c < NM; ++c) { CK(hipFree(bits_dev[c])); CK(hipFree(order_dev[c])); }
+}
+
 // ------------------------------------------------------------------------------------- calibration statistics
 static void bench_calib(int M, int D, int rounds, int launches) {
   float *r, *rp, *stats;
@@ -538,7 +711,7 @@ static void bench_calib(int M, int D, int rounds, int launches) {
 
 int main(int argc, char** argv) {
   if (argc < 5) {
-    fprintf(stderr, "usage: kbench.bin <gemm|attn|attn_mx8|attn_band|attn_keys|calib|all> <rounds> <launches> libA.so [libB.so ...]\n");
+    fprintf(stderr, "usage: kbench.bin <gemm|attn|attn_mx8|attn_band|attn_sparse|attn_keys|calib|all> <rounds> <launches> libA.so [libB.so ...]\n");
     return 2;
   }
   if (getenv("KBENCH_AMP")) g_amp = (float)atof(getenv("KBENCH_AMP"));
@@ -558,6 +731,7 @@ int main(int argc, char** argv) {
     l.quant_mx8 = (decltype(l.quant_mx8))dlsym(l.h, "mc_op_attn_quantize_mx8");
     l.attn_mx8 = (decltype(l.attn_mx8))dlsym(l.h, "mc_op_attention_mx8");
     l.attn_band = (decltype(l.attn_band))dlsym(l.h, "mc_op_attention_band");
+    l.attn_sparse = (decltype(l.attn_sparse))dlsym(l.h, "mc_op_attention_sparse");
     l.set_option = (decltype(l.set_option))dlsym(l.h, "mc_set_option");
     l.last_error = (decltype(l.last_error))dlsym(l.h, "mc_last_error");
     if (!l.gemm || !l.attn || !l.calib || !l.set_option || !l.last_error) {
@@ -589,6 +763,7 @@ int main(int argc, char** argv) {
   }
   if (what == "attn_mx8") bench_attn_mx8(32768, 12, 32760, rounds, std::max(1, launches / 4));
   if (what == "attn_band") bench_attn_band(32768, 12, 32760, rounds, std::max(1, launches / 4));
+  if (what == "attn_sparse") bench_attn_sparse(32768, 12, 32760, rounds, std::max(1, launches / 4));
   if (what == "attn_strided" || what == "all") bench_attn("self480p_qkv", 32768, 12, 32760, 1.0f, rounds, std::max(1, launches / 4), true);
   if (what == "attn_keys") bench_attn_keys(32768, 12, rounds, launches);
   if (what == "attn1") bench_attn("self480p", 32768, 12, 32760, 1.0f, rounds, launches);          // one shape (PMC passes)
