@@ -171,7 +171,9 @@ mc_status mc_create(const mc_config* cfg, mc_engine** out);
  * mc_engine_token_timestep_sets, mc_op_gemm_bf16_resid_sets); the adapter kinds add calls only: mc_lora_set_kron / _set_hada /
  * _set_magnitude, mc_op_adapter_merge / _scratch; the frame-block causal self-attention adds calls only: mc_set_causal_blocks,
  * mc_engine_causal_blocks, mc_op_attention_band; the tile-sparse self-attention adds calls only: mc_set_attention_tile_mask,
- * mc_engine_attention_tile_mask, mc_op_attention_sparse; mc_version() names the library's. */
+ * mc_engine_attention_tile_mask, mc_op_attention_sparse; the predicted tile mask adds calls only: mc_set_attention_tile_mass,
+ * mc_engine_attention_tile_mass, mc_read_attention_tile_mask, mc_op_attention_tile_predict / _scratch; mc_version() names the
+ * library's. */
 mc_status mc_create_sized(const mc_config* cfg, size_t cfg_bytes, mc_engine** out);
 void mc_destroy(mc_engine* e);
 /* 1: this engine's quantised Linears are MXFP4 (it was created under mc_set_option("mx_fp4", 1) with fp8_linear 2 | 3); else 0 */
@@ -209,6 +211,29 @@ mc_status mc_engine_causal_blocks(const mc_engine* e, int* frames_per_block, int
  * over all of them (NULL outputs are skipped; mask_heads 0 = off). */
 mc_status mc_set_attention_tile_mask(mc_engine* e, const uint32_t* bits_host, int mask_heads, int nqt, int nkt, int dense_layers);
 mc_status mc_engine_attention_tile_mask(const mc_engine* e, int* mask_heads, int* nqt, int* nkt, int* dense_layers, double* density);
+/* Predicted tile mask: the content-adaptive first stage the training-free sparse video-DiT methods share (pool q and k per
+ * block, score the pooled blocks, keep the smallest set of key blocks that carries a chosen share of each query block's softmax
+ * mass), run on the device inside the forward, once per layer, from that layer's own q and k (after q/k RMSNorm and RoPE).
+ * With mass in (0, 1]: the self-attention of every block l >= dense_layers (a VACE block counts as the main layer it feeds)
+ * becomes two launches -- mc_op_attention_tile_predict's over the block's q and k columns (the rule is stated there), then
+ * attention_sparse.hip over the mask it wrote, one mask row per (head, query tile), no order table.  mass == 0 turns it off:
+ * every launch afterwards is the one an engine makes that never heard of the call.  While on, one mask buffer and the
+ * predictor's two pool buffers belong to the engine: allocated at this call, outside the workspace, for the grid in force;
+ * freed on off, replace and mc_destroy.  Nothing is allocated, copied or synchronised during a forward.
+ * An approximation the caller chooses; density and quality on real checkpoints are not judged.  Between forwards only
+ * (MC_ESTATE between mc_embed and mc_head).  MC_EINVAL: mass outside [0, 1], a negative dense_layers, a sequence-parallel
+ * engine, an "attn_mx8" engine, while mc_set_causal_blocks is on, while a static tile mask is set (and both of those setters
+ * refuse while the tile mass is on); the error text names which.  The buffers do not follow mc_set_geometry: a forward whose
+ * Lp no longer matches them returns MC_ESTATE with nothing launched -- set the mass again or turn it off.
+ * mc_engine_attention_tile_mass reads the two values back (NULL outputs are skipped; mass 0 = off). */
+mc_status mc_set_attention_tile_mass(mc_engine* e, float mass, int dense_layers);
+mc_status mc_engine_attention_tile_mass(const mc_engine* e, float* mass, int* dense_layers);
+/* The tile mask in force, copied to the host after a device synchronisation: the static one (mc_set_attention_tile_mask), or
+ * the one the last predicted self-attention wrote (mc_set_attention_tile_mass; zeros before the first).  bits_host receives
+ * uint32 [mask_heads][nqt][(nkt + 31) / 32] in mc_op_attention_sparse's bit order; bytes is the room behind it (MC_EINVAL when
+ * too small, or bits_host NULL); the sizes are returned, also with that MC_EINVAL, so a first call with NULL asks for them
+ * (NULL outputs are skipped).  MC_ESTATE when neither is on. */
+mc_status mc_read_attention_tile_mask(const mc_engine* e, uint32_t* bits_host, size_t bytes, int* mask_heads, int* nqt, int* nkt);
 size_t mc_workspace_bytes(const mc_engine* e);
 mc_status mc_set_workspace(mc_engine* e, void* ws_dev, size_t bytes);
 /* The latent grid as a property of the call (0.7).  mc_config.latent_f / _h / _w is the grid an engine STARTS with;
@@ -699,6 +724,33 @@ mc_status mc_op_attention_band(const void* Q_dev, long ldq, const void* K_dev, l
 mc_status mc_op_attention_sparse(const void* Q_dev, long ldq, const void* K_dev, long ldk, const void* V_dev, long ldv, void* O_dev,
                                  long ldo, int Lq_pad, int n_heads, int rows, int valid, const uint32_t* tile_mask_dev,
                                  int mask_heads, const int32_t* order_dev, float scale, mc_stream stream);
+/* The tile-mask predictor (attention_predict.hip): writes the mask mc_op_attention_sparse reads, mask_heads == n_heads, from
+ * the launch's own operands.  Q bf16 [Lq_pad][ldq] and K bf16 [rows][ldk] exactly as the attention kernels read them, head_dim
+ * 128, the first `valid` rows of each are tokens; softmax `scale`; `mass` tau with 0 < tau <= 1.  With nqt = Lq_pad / 128,
+ * nkt = rows / 64, vk = ceil(valid / 64), words = (nkt + 31) / 32, for every head h and query tile qt:
+ *   - valid row counts: n_q(qt) is the number of rows i of the tile with i < valid, n_k(kt) the same for key tile kt;
+ *   - pooled means over the VALID rows only, in fp32 (zero where the count is 0): q~[h][qt] of the tile's q rows (128
+ *     channels), k~[h][kt] of the tile's k rows;
+ *   - scores and shares, for kt < vk: s[kt] = scale * <q~, k~[kt]>, w[kt] = n_k(kt) * exp(s[kt] - max s), p[kt] = w[kt] / sum w;
+ *   - forced tiles: {2 qt, 2 qt + 1} below vk, the key tiles that hold the query tile's own rows -- always kept, so a query
+ *     tile with a valid row never sees nothing;
+ *   - threshold: theta is the largest value among {p[kt] : kt not forced} for which
+ *     sum_forced p + sum_{kt not forced, p[kt] >= theta} p[kt] >= tau.  If the forced tiles alone reach tau, no other tile is
+ *     kept; if no theta reaches tau (possible only through rounding), every tile < vk is kept;
+ *   - bit kt is set iff kt is forced or p[kt] >= theta.  Ties at theta are all kept: the rule is a threshold, not a sort.
+ *     Bits at kt >= vk are clear.  If n_q(qt) = 0 the row holds only its forced bits (possibly none: mc_op_attention_sparse then
+ *     writes zeros).
+ * tau = 1 keeps every tile whose share the fp32 sums can still resolve; it is not a promise that all bits are set.
+ * tile_mask_dev: uint32 [n_heads][nqt][words] in device memory, every word written.  scratch_dev: at least
+ * mc_op_attention_tile_predict_scratch(Lq_pad, n_heads, rows) bytes of device memory, 16-byte aligned (the pooled rows, fp32).
+ * Two plain launches on `stream`; the same input gives the same bits on every run.  At most 2048 key tiles (rows <= 131 072).
+ * Refused with MC_EINVAL, nothing launched: Lq_pad % 256, rows % 64, valid outside 1..rows, a leading dimension % 8 or below
+ * n_heads * 128, Q or K null or not 16-byte aligned, Lq_pad * ldq or rows * ldk beyond 32-bit byte offsets, mass outside (0, 1],
+ * a mask that is null or not 4-byte aligned, scratch null or not 16-byte aligned, more than 2048 key tiles. */
+size_t mc_op_attention_tile_predict_scratch(int Lq_pad, int n_heads, int rows);
+mc_status mc_op_attention_tile_predict(const void* Q_dev, long ldq, const void* K_dev, long ldk, int Lq_pad, int n_heads,
+                                       int rows, int valid, float scale, float mass, uint32_t* tile_mask_dev,
+                                       void* scratch_dev, mc_stream stream);
 /* MX fp8 self-attention (option "attn_mx8"; attention_mx8.hip), d = n_heads * 128.  mc_op_attn_quantize_mx8 turns the bf16 q, k
  * and v rows into the six images mc_op_attention_mx8 reads: q_img [Lq_pad][d] e4m3 of q * scale * log2(e) and k_img [rows][d]
  * e4m3 (rows >= valid zero), each with rows * d / 32 E8M0 scale bytes, one per (row, 32 channels) (q_sc, k_sc); vt_img [d][rows]

@@ -54,6 +54,9 @@ SIGNATURES = {
     "mc_engine_causal_blocks": (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
     "mc_set_attention_tile_mask": (_i, [_vp, _vp, _i, _i, _i, _i]),
     "mc_engine_attention_tile_mask": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_d)]),
+    "mc_set_attention_tile_mass": (_i, [_vp, _f, _i]),
+    "mc_engine_attention_tile_mass": (_i, [_vp, C.POINTER(_f), C.POINTER(_i)]),
+    "mc_read_attention_tile_mask": (_i, [_vp, _vp, _sz, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "mc_engine_token_timestep_sets": (_i, [_vp]),
     "mc_create": (_i, [C.POINTER(McConfig), C.POINTER(_vp)]),
     "mc_create_sized": (_i, [C.POINTER(McConfig), _sz, C.POINTER(_vp)]),
@@ -131,6 +134,8 @@ SIGNATURES = {
     "mc_op_attn_quantize_mx8": (_i, [_vp, _l, _vp, _l, _vp, _l, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mc_op_attention_band": (_i, [_vp, _l, _vp, _l, _vp, _l, _vp, _l, _i, _i, _i, _i, _i, _i, _f, _vp]),
     "mc_op_attention_sparse": (_i, [_vp, _l, _vp, _l, _vp, _l, _vp, _l, _i, _i, _i, _i, _vp, _i, _vp, _f, _vp]),
+    "mc_op_attention_tile_predict_scratch": (_sz, [_i, _i, _i]),
+    "mc_op_attention_tile_predict": (_i, [_vp, _l, _vp, _l, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp]),
     "mc_op_attention_mx8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _vp, _vp]),
     "mc_op_attention_partial": (_i, [_vp, _l, _vp, _l, _l, _vp, _l, _l, _vp, _l, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp]),
     "mc_op_attn_merge": (_i, [_vp, _vp, _i, _vp, _l, _i, _i, _i, _vp]),

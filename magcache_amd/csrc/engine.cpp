@@ -55,6 +55,20 @@ struct mc_engine {
     mask_heads = mask_nqt = mask_nkt = mask_dense_layers = 0;
     mask_density = 0.0;
   }
+  // mc_set_attention_tile_mass: the share of the softmax mass the predicted mask keeps (0 = off), the first block it applies to,
+  // and what the predictor writes per launch -- the mask words [H][nqt][words] and its pooled rows --, owned here, outside the
+  // workspace, for the tile counts they were allocated at
+  float tile_mass = 0.f;
+  int mass_dense_layers = 0, mass_nqt = 0, mass_nkt = 0;
+  uint32_t* mass_bits = nullptr;
+  void* mass_scratch = nullptr;
+  void mass_drop() {
+    if (mass_bits) (void)hipFree(mass_bits);
+    if (mass_scratch) (void)hipFree(mass_scratch);
+    mass_bits = nullptr; mass_scratch = nullptr;
+    tile_mass = 0.f;
+    mass_dense_layers = mass_nqt = mass_nkt = 0;
+  }
   int d, ffn, H, NL, L, Lr, Lp, P, rank, tok0, Kp;  // Kp = in_dim*4 padded to 64
   int ctx_rows;                                     // text_len padded to 64
   std::vector<Layer> layers;
@@ -457,20 +471,34 @@ mc_status attend(const mc_engine* e, const bf16_t* Q, long ldq, bf16_t* O, const
 //   mc_set_causal_blocks   attention_band.hip with the block in tokens of the grid in force
 //   mc_set_attention_tile_mask   attention_sparse.hip over the engine's mask, for the blocks l >= dense_layers (l: the main
 //                          layer; a VACE block counts as the main layer it feeds)
+//   mc_set_attention_tile_mass   for the same blocks, attention_predict.hip over the block's q and k columns, then
+//                          attention_sparse.hip over the mask it wrote: one row per (head, query tile), no order table
 //   otherwise              attend() over the same operands
-// (the three are exclusive: each setter refuses while another is on)
+// (the four are exclusive: each setter refuses while another is on)
 mc_status tile_mask_fits(const mc_engine* e) {
   if (e->mask_heads && (e->mask_nqt != e->Lp / 128 || e->mask_nkt != e->Lp / 64))
     return fail(MC_ESTATE, "the attention tile mask was set for %d x %d tiles (a sequence padded to %d rows) and the grid in force pads "
                            "to %d rows: call mc_set_attention_tile_mask again, or with NULL", e->mask_nqt, e->mask_nkt, e->mask_nqt * 128, e->Lp);
+  if (e->tile_mass > 0.f && (e->mass_nqt != e->Lp / 128 || e->mass_nkt != e->Lp / 64))
+    return fail(MC_ESTATE, "the attention tile mass was set for %d x %d tiles (a sequence padded to %d rows) and the grid in force pads "
+                           "to %d rows: call mc_set_attention_tile_mass again, or with 0", e->mass_nqt, e->mass_nkt, e->mass_nqt * 128, e->Lp);
   return MC_OK;
 }
 mc_status attend_self(const mc_engine* e, int l, bf16_t* O, hipStream_t s) {
   const Keys keys = qkv_keys(e);
   const bf16_t* Q = e->buf<bf16_t>("qkv");
   const bool sparse = e->mask_heads && l >= e->mask_dense_layers;
-  if (!e->attn_mx8 && !e->causal_frames && !sparse) return attend(e, Q, keys.ld, O, keys, nullptr, nullptr, s);
+  const bool predicted = e->tile_mass > 0.f && l >= e->mass_dense_layers;
+  if (!e->attn_mx8 && !e->causal_frames && !sparse && !predicted) return attend(e, Q, keys.ld, O, keys, nullptr, nullptr, s);
   const mc::AttnParams a = mc::attn_params(Q, keys.ld, O, e->d, e->Lp, e->H, keys, mc::kAttnScale, nullptr, nullptr);
+  if (predicted) {
+    MC_TRY(tile_mask_fits(e));   // (as below: no launch may write past the buffers)
+    const mc::AttnPredict pr = {Q, keys.ld, keys.k, keys.ld, e->Lp, e->H, keys.rows, keys.valid, mc::kAttnScale, e->tile_mass,
+                                e->mass_bits, e->mass_scratch};
+    HIP_TRY(mc::launch_attention_predict(pr, s));
+    HIP_TRY(mc::launch_attention_sparse(a, mc::AttnTileMask{e->mass_bits, e->H, nullptr}, s));
+    return MC_OK;
+  }
   if (sparse) {
     MC_TRY(tile_mask_fits(e));   // (every forward checks this before its first launch; here no launch may read past the mask)
     HIP_TRY(mc::launch_attention_sparse(a, mc::AttnTileMask{e->mask_bits, e->mask_heads, e->mask_order}, s));
@@ -682,6 +710,7 @@ void mc_destroy(mc_engine* e) {
   if (!e) return;
   e->weights.free_all();
   e->mask_drop();
+  e->mass_drop();
   for (hipEvent_t ev : e->prof_ev) (void)hipEventDestroy(ev);
   if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
   if (e->ev_join) (void)hipEventDestroy(e->ev_join);
@@ -712,6 +741,9 @@ mc_status mc_set_causal_blocks(mc_engine* e, int frames_per_block, int window_bl
   if (frames_per_block != 0 && e->mask_heads)
     return fail(MC_EINVAL, "mc_set_causal_blocks: an attention tile mask is set (mc_set_attention_tile_mask); express the causal "
                            "blocks in the mask, or turn the mask off first");
+  if (frames_per_block != 0 && e->tile_mass > 0.f)
+    return fail(MC_EINVAL, "mc_set_causal_blocks: the attention tile mass is on (mc_set_attention_tile_mass, %g); the predicted mask "
+                           "knows no causal blocks, turn it off first", (double)e->tile_mass);
   e->causal_frames = frames_per_block;
   e->causal_window = frames_per_block ? window_blocks : 0;
   return MC_OK;
@@ -740,6 +772,9 @@ mc_status mc_set_attention_tile_mask(mc_engine* e, const uint32_t* bits_host, in
   if (e->causal_frames)
     return fail(MC_EINVAL, "mc_set_attention_tile_mask: mc_set_causal_blocks is on (%d frames per block); express the causal blocks "
                            "in the mask, or turn them off first", e->causal_frames);
+  if (e->tile_mass > 0.f)
+    return fail(MC_EINVAL, "mc_set_attention_tile_mask: the attention tile mass is on (mc_set_attention_tile_mass, %g) and predicts "
+                           "the mask of every launch; turn it off first", (double)e->tile_mass);
   if (nqt != e->Lp / 128 || nkt != e->Lp / 64)
     return fail(MC_EINVAL, "mc_set_attention_tile_mask: %d x %d tiles, the grid in force (%d rows padded to %d) has %d x %d", nqt, nkt,
                 e->Lr, e->Lp, e->Lp / 128, e->Lp / 64);
@@ -795,6 +830,72 @@ mc_status mc_engine_attention_tile_mask(const mc_engine* e, int* mask_heads, int
   if (nkt) *nkt = e->mask_nkt;
   if (dense_layers) *dense_layers = e->mask_dense_layers;
   if (density) *density = e->mask_density;
+  return MC_OK;
+}
+
+mc_status mc_set_attention_tile_mass(mc_engine* e, float mass, int dense_layers) {
+  if (!e) return fail(MC_EINVAL, "null engine");
+  if (e->phase_open) return fail(MC_ESTATE, "mc_set_attention_tile_mass between mc_embed and mc_head");
+  if (!(mass >= 0.f && mass <= 1.f)) return fail(MC_EINVAL, "mc_set_attention_tile_mass: mass (%g) must lie in [0, 1]", (double)mass);
+  if (mass == 0.f) {   // off: earlier forwards may still be using the buffers
+    if (e->tile_mass > 0.f) HIP_TRY(hipDeviceSynchronize());
+    e->mass_drop();
+    return MC_OK;
+  }
+  if (dense_layers < 0) return fail(MC_EINVAL, "mc_set_attention_tile_mass: dense_layers (%d) must be >= 0", dense_layers);
+  if (e->sp)
+    return fail(MC_EINVAL, "mc_set_attention_tile_mass: the engine is sequence parallel (sp_size %d%s): a rank holds a shard of the "
+                           "keys, and the tile-sparse kernel has no log-sum-exp to merge shards with", e->P,
+                e->cfg.sp_phases ? ", sp_phases" : "");
+  if (e->attn_mx8)
+    return fail(MC_EINVAL, "mc_set_attention_tile_mass: the engine was created under the option \"attn_mx8\" and the MX fp8 "
+                           "self-attention kernel has no mask");
+  if (e->causal_frames)
+    return fail(MC_EINVAL, "mc_set_attention_tile_mass: mc_set_causal_blocks is on (%d frames per block); the predicted mask knows no "
+                           "causal blocks, turn them off first", e->causal_frames);
+  if (e->mask_heads)
+    return fail(MC_EINVAL, "mc_set_attention_tile_mass: a static tile mask is set (mc_set_attention_tile_mask); turn it off first");
+  const int nqt = e->Lp / 128, nkt = e->Lp / 64;
+  if (nkt > mc::kAttnPredictMaxNkt)
+    return fail(MC_EINVAL, "mc_set_attention_tile_mass: the grid in force has %d key tiles, the predictor serves %d", nkt,
+                mc::kAttnPredictMaxNkt);
+  uint32_t* bits = nullptr;
+  void* scratch = nullptr;
+  const size_t bits_bytes = (size_t)e->H * nqt * ((nkt + 31) / 32) * 4, scratch_bytes = mc::attention_predict_scratch_bytes(e->Lp, e->H, e->Lp);
+  if (hipMalloc((void**)&bits, bits_bytes) != hipSuccess || hipMalloc(&scratch, scratch_bytes) != hipSuccess ||
+      hipMemset(bits, 0, bits_bytes) != hipSuccess) {   // (zeros: what mc_read_attention_tile_mask shows before the first forward)
+    if (bits) (void)hipFree(bits);
+    if (scratch) (void)hipFree(scratch);
+    return fail(MC_EHIP, "mc_set_attention_tile_mass: no device memory for the mask (%zu bytes) and the pooled rows (%zu bytes)",
+                bits_bytes, scratch_bytes);
+  }
+  HIP_TRY(hipDeviceSynchronize());   // the mask is clear before a forward on any stream; earlier forwards are done with the old buffers
+  e->mass_drop();
+  e->mass_bits = bits; e->mass_scratch = scratch;
+  e->tile_mass = mass; e->mass_dense_layers = dense_layers; e->mass_nqt = nqt; e->mass_nkt = nkt;
+  return MC_OK;
+}
+mc_status mc_engine_attention_tile_mass(const mc_engine* e, float* mass, int* dense_layers) {
+  if (!e) return fail(MC_EINVAL, "null engine");
+  if (mass) *mass = e->tile_mass;
+  if (dense_layers) *dense_layers = e->mass_dense_layers;
+  return MC_OK;
+}
+mc_status mc_read_attention_tile_mask(const mc_engine* e, uint32_t* bits_host, size_t bytes, int* mask_heads, int* nqt, int* nkt) {
+  if (!e) return fail(MC_EINVAL, "null engine");
+  const bool predicted = e->tile_mass > 0.f;
+  if (!predicted && !e->mask_heads)
+    return fail(MC_ESTATE, "mc_read_attention_tile_mask: neither mc_set_attention_tile_mask nor mc_set_attention_tile_mass is on");
+  const int mh = predicted ? e->H : e->mask_heads, q = predicted ? e->mass_nqt : e->mask_nqt, k = predicted ? e->mass_nkt : e->mask_nkt;
+  const size_t need = (size_t)mh * q * ((k + 31) / 32) * 4;
+  if (mask_heads) *mask_heads = mh;   // (also when the room is too small: a caller may ask for the sizes first)
+  if (nqt) *nqt = q;
+  if (nkt) *nkt = k;
+  if (!bits_host || bytes < need)
+    return fail(MC_EINVAL, "mc_read_attention_tile_mask: the mask of %d x %d x %d tiles takes %zu bytes, %zu are offered", mh, q, k, need,
+                bits_host ? bytes : (size_t)0);
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(bits_host, predicted ? e->mass_bits : e->mask_bits, need, hipMemcpyDeviceToHost));
   return MC_OK;
 }
 

@@ -377,6 +377,31 @@ struct AttnTileMask { const uint32_t* bits; int mask_heads; const int32_t* order
 bool attention_sparse_supports(const AttnParams& p, const AttnTileMask& m);
 hipError_t launch_attention_sparse(const AttnParams& p, const AttnTileMask& m, hipStream_t stream);
 
+// ---------------------------------------------------------------- tile-mask predictor (attention_predict.hip)
+// Writes the bits launch_attention_sparse reads, mask_heads == n_heads, from the launch's own Q and K: per (head, 128-row query
+// tile) the smallest set of 64-key tiles that carries the share `mass` of the softmax over the tile-pooled q and k (the rule
+// in full: include/magcache_hip.h at mc_op_attention_tile_predict, and the head of attention_predict.hip).
+//   bits     uint32 [n_heads][Lq_pad / 128][(rows / 64 + 31) / 32], every word written
+//   scratch  attention_predict_scratch_bytes(): q_pool fp32 [n_heads][Lq_pad / 128][128], then k_pool fp32 [n_heads][rows / 64][128]
+struct AttnPredict {
+  const bf16_t* Q; long ldq;
+  const bf16_t* K; long ldk;
+  int Lq_pad, n_heads, rows, valid;
+  float scale, mass;
+  uint32_t* bits;
+  void* scratch;
+};
+constexpr int kAttnPredictMaxNkt = 2048;   // key tiles (131 072 keys) the select pass holds per wave: 8 KiB of LDS each
+inline size_t attention_predict_scratch_bytes(int Lq_pad, int n_heads, int rows) {
+  return Lq_pad <= 0 || n_heads <= 0 || rows <= 0 ? 0 : (size_t)n_heads * ((size_t)Lq_pad / 128 + (size_t)rows / 64) * 128 * sizeof(float);
+}
+// attention_shape_ok's shape rules (K's leading dimension in V's place); its own conditions: Q and K non-null and 16-byte
+// aligned, ld >= n_heads * 128, Lq_pad * ldq and rows * ldk within 32-bit byte offsets, 0 < mass <= 1, bits non-null and 4-byte
+// aligned, scratch non-null and 16-byte aligned, rows / 64 <= kAttnPredictMaxNkt.
+bool attention_predict_supports(const AttnPredict& p);
+// two plain launches on `stream` (pool, select): no allocation, copy or synchronisation
+hipError_t launch_attention_predict(const AttnPredict& p, hipStream_t stream);
+
 // ---------------------------------------------------------------- token-wise ops (elementwise.hip)
 // out[m,:] = bf16( LN(x[m,:]) * a + b ),  a = 1+scale (modulate) or weight (affine)
 //   mode 0: a = 1 + sc[d], b = sh[d]      (AdaLN modulate; sc/sh fp32 vectors)

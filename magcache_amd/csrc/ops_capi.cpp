@@ -169,6 +169,23 @@ mc_status mc_op_attention_sparse(const void* Q, long ldq, const void* K, long ld
   return MC_OK;
 }
 
+// the tile-mask predictor (attention_predict.hip)
+size_t mc_op_attention_tile_predict_scratch(int Lq_pad, int n_heads, int rows) {
+  return mc::attention_predict_scratch_bytes(Lq_pad, n_heads, rows);
+}
+mc_status mc_op_attention_tile_predict(const void* Q, long ldq, const void* K, long ldk, int Lq_pad, int n_heads, int rows, int valid,
+                                       float scale, float mass, uint32_t* tile_mask, void* scratch, mc_stream s) {
+  const mc::AttnPredict p = {(const bf16_t*)Q, ldq, (const bf16_t*)K, ldk, Lq_pad, n_heads, rows, valid, scale, mass, tile_mask, scratch};
+  hipError_t err = mc::launch_attention_predict(p, (hipStream_t)s);
+  if (err == hipErrorInvalidValue)
+    return fail(MC_EINVAL, "attention_tile_predict: needs Lq_pad %% 256 == 0, rows %% 64 == 0, 1 <= valid <= rows, leading dimensions "
+                           "%% 8 == 0 and >= n_heads * 128, Q and K non-null and 16-byte aligned, Lq_pad * ldq and rows * ldk within "
+                           "32-bit byte offsets, 0 < mass <= 1 (%g), a non-null 4-byte aligned tile mask, non-null 16-byte aligned "
+                           "scratch, at most %d key tiles (%d)", (double)mass, mc::kAttnPredictMaxNkt, rows / 64);
+  HIP_TRY(err);
+  return MC_OK;
+}
+
 // MX fp8 self-attention (attention_mx8.hip): the pre-pass and the kernel share one argument contract
 static const char* kAttnMx8Refusal =
     "needs Lq_pad % 256 == 0, rows % 64 == 0, 1 <= valid <= rows, leading dimensions % 8 == 0 and >= n_heads * 128, operands and "

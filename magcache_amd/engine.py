@@ -234,6 +234,36 @@ class Engine(EngineHost):
         check(self.lib.mc_engine_attention_tile_mask(self.h, C.byref(h), C.byref(q), C.byref(k), C.byref(dl), C.byref(dens)))
         return (h.value, q.value, k.value, dl.value, dens.value) if h.value else None
 
+    # ---- predicted tile mask
+    def set_attention_tile_mass(self, mass, dense_layers=0):
+        """Self-attention under a mask predicted on the device, per layer, from the layer's own q and k
+        (mc_set_attention_tile_mass): per (head, 128-row query tile) the smallest set of 64-key tiles that carries the share
+        `mass` in (0, 1] of the softmax over tile-pooled q and k, the tile's own two key tiles always included
+        (mc_op_attention_tile_predict states the rule).  0 or None turns it off (plain attention, the launches an engine makes
+        that never called this).  Blocks below dense_layers stay dense.  The buffers belong to the grid in force: after
+        set_geometry set it again (a forward under stale buffers raises).  Refused on a sharded engine, on an attn_mx8 engine,
+        while set_causal_blocks is on and while a static tile mask is set."""
+        check(self.lib.mc_set_attention_tile_mass(self.h, float(mass or 0.0), int(dense_layers)))
+
+    @property
+    def attention_tile_mass(self):
+        """(mass, dense_layers) in force, or None"""
+        m, dl = C.c_float(), C.c_int()
+        check(self.lib.mc_engine_attention_tile_mass(self.h, C.byref(m), C.byref(dl)))
+        return (m.value, dl.value) if m.value > 0 else None
+
+    def read_attention_tile_mask(self):
+        """bool [mask_heads, nqt, nkt] on the CPU: the tile mask in force -- the static one, or the one the last predicted
+        self-attention wrote (mc_read_attention_tile_mask; synchronises the device)"""
+        from .sparse_masks import unpack_tile_mask
+        mh, q, k = C.c_int(), C.c_int(), C.c_int()
+        status = self.lib.mc_read_attention_tile_mask(self.h, None, 0, C.byref(mh), C.byref(q), C.byref(k))     # the sizes
+        if status != _lib.MC_EINVAL:
+            check(status)
+        words = torch.zeros(mh.value, q.value, (k.value + 31) // 32, dtype=torch.int32)
+        check(self.lib.mc_read_attention_tile_mask(self.h, words.data_ptr(), words.numel() * 4, None, None, None))
+        return unpack_tile_mask(words, k.value)
+
     def residual(self, branch):
         """fp32 [seq_len/sp, dim] view of residual_cache[branch] (rows past the valid tokens cut off)."""
         d = self.cfg["dim"]

@@ -124,8 +124,10 @@ def _parse_args(argv=None):
                         "0 = plain attention.  One device only")
     p.add_argument("--causal_window_blocks", type=int, default=0, metavar="W",
                    help="with --causal_block_frames: attend to the last W blocks only (0 = all earlier blocks)")
-    p.add_argument("--sparse_attention", type=str, default=None, metavar="decay[:DENSE[:SINK]]",
-                   help="training-free tile-sparse self-attention under a static block mask: 'decay' = the temporal-decay mask of "
+    p.add_argument("--sparse_attention", type=str, default=None, metavar="decay[:DENSE[:SINK]] | topmass:MASS",
+                   help="training-free tile-sparse self-attention.  'topmass:MASS' = a mask predicted on the device, per layer and head, "
+                        "from the layer's own q and k: the smallest set of key tiles that carries the share MASS in (0, 1] of the "
+                        "tile-pooled softmax (Engine.set_attention_tile_mass).  'decay' = a static block mask, the temporal-decay mask of "
                         "sparse_masks.temporal_decay_tile_mask (frames nearer than DENSE whole, the first SINK frames always, a spatial "
                         "window that halves as the frame distance doubles; default 1:1).  An approximation: it shortens the forwards "
                         "MagCache does not skip, and the shipped mag_ratios were calibrated on DENSE attention.  One GPU; t2v tasks.")
@@ -185,18 +187,33 @@ def _context(path, prompt, seed, text_dim, device):
     return torch.randn(n, text_dim, generator=g).to(device)
 
 
+def parse_sparse_attention(spec):
+    """--sparse_attention's value -> ("decay", dense_frames, sink_frames) or ("topmass", mass); ValueError for anything else"""
+    kind, *nums = spec.split(":")
+    try:
+        if kind == "decay" and len(nums) <= 2:
+            return "decay", (int(nums[0]) if nums else 1), (int(nums[1]) if len(nums) > 1 else 1)
+        if kind == "topmass" and len(nums) == 1 and 0.0 < float(nums[0]) <= 1.0:
+            return "topmass", float(nums[0])
+    except ValueError:
+        pass
+    raise ValueError(f"--sparse_attention {spec!r}: decay[:DENSE[:SINK]] with integers, or topmass:MASS with 0 < MASS <= 1")
+
+
 def _sparse_attention(args, model):
-    """--sparse_attention: sets the mask now (no dense steps) or returns the sampler callback that sets it after step
-    --sparse_dense_steps; None without the flag"""
+    """--sparse_attention: sets the mask (or the mass of the predicted one) now (no dense steps) or returns the sampler callback
+    that sets it after step --sparse_dense_steps; None without the flag"""
     if not args.sparse_attention:
         return None
     from .sparse_masks import temporal_decay_tile_mask
-    kind, *nums = args.sparse_attention.split(":")
-    if kind != "decay" or len(nums) > 2:
-        raise ValueError(f"--sparse_attention {args.sparse_attention!r}: decay[:DENSE[:SINK]]")
-    dense, sink = (int(nums[0]) if nums else 1), (int(nums[1]) if len(nums) > 1 else 1)
+    kind, *nums = parse_sparse_attention(args.sparse_attention)
 
     def turn_on():
+        if kind == "topmass":
+            model.set_attention_tile_mass(nums[0], args.sparse_dense_layers)
+            logging.info(f"tile-sparse self-attention from block {args.sparse_dense_layers}: predicted mask, mass {nums[0]:g}")
+            return
+        dense, sink = nums
         model.set_attention_tile_mask(lambda g: temporal_decay_tile_mask(g, dense, sink), args.sparse_dense_layers)
         logging.info(f"tile-sparse self-attention from block {args.sparse_dense_layers}: decay {dense}:{sink}, "
                      f"density {model.engine.attention_tile_mask[4]:.3f}")
@@ -204,6 +221,17 @@ def _sparse_attention(args, model):
         turn_on()
         return None
     return lambda i, _latent: turn_on() if i + 1 == args.sparse_dense_steps else None
+
+
+def _log_predicted_density(model):
+    """after a run under topmass: the density, over valid tiles, of the mask the last predicted layer wrote"""
+    e = model.engine
+    if e.attention_tile_mass is None:
+        return
+    mask = e.read_attention_tile_mask()
+    vq, vk = (e.seq_len + 127) // 128, (e.seq_len + 63) // 64
+    logging.info(f"predicted tile mask of the last sparse layer: density {float(mask[:, :vq, :vk].double().mean()):.3f} "
+                 f"over {mask.shape[0]} heads x {vq} x {vk} valid tiles")
 
 
 def generate(args):
@@ -313,6 +341,8 @@ def generate(args):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     logging.info(f"denoising: {dt:.2f} s, {args.sample_steps / dt:.3f} steps/s")
+    if args.sparse_attention:
+        _log_predicted_density(model)
     if rank == 0:
         out = args.save_file or f"{args.task}_{args.size.replace('*', 'x')}_{args.base_seed}_latent.pt"
         torch.save(latent.cpu(), out)
@@ -373,6 +403,8 @@ def _generate_ti2v(args, device, rank, world, layout):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     logging.info(f"denoising: {dt:.2f} s, {args.sample_steps / dt:.3f} steps/s")
+    if args.sparse_attention:
+        _log_predicted_density(model)
     out = args.save_file or f"{args.task}_{args.size.replace('*', 'x')}_{args.base_seed}_latent.pt"
     torch.save(latent.cpu(), out)
     logging.info(f"Saving the final latent to {out} (no VAE decoder in this repository)")

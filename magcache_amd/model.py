@@ -116,7 +116,8 @@ class WanModelHIP(LoraModel):
 
     def __init__(self, cfg, latent_grid, device="cuda:0", calibration=True, engine=None, sp_rank=0, sp_size=1,
                  sp_group=None, sp_phases=False, dynamic_geometry=False, token_timestep_sets=0, attn_mx8=False,
-                 causal_block_frames=0, causal_window_blocks=0, attention_tile_mask=None, sparse_dense_layers=0):
+                 causal_block_frames=0, causal_window_blocks=0, attention_tile_mask=None, sparse_dense_layers=0,
+                 attention_tile_mass=None):
         """token_timestep_sets (3..64): the engine's capacity of distinct per-token timesteps per forward -- one timestep per
         latent frame (wan22.frame_timesteps / sample_frames), several conditioning frames at their own noise levels.  0: two,
         what Wan2.2 TI2V's `mask * t` needs.
@@ -128,7 +129,10 @@ class WanModelHIP(LoraModel):
         attention_tile_mask: tile-sparse self-attention (Engine.set_attention_tile_mask) for the blocks >= sparse_dense_layers --
         a bool tensor [mask_heads, Lp / 128, Lp / 64] for this grid, or a callable grid -> tensor (sparse_masks has builders),
         which is called again for the new grid after set_geometry (dynamic_geometry); a tensor is not, and the first forward at
-        another grid raises.  set_attention_tile_mask changes or clears it later."""
+        another grid raises.  set_attention_tile_mask changes or clears it later.
+        attention_tile_mass: instead of a static mask, the mask predicted on the device per layer from its own q and k
+        (Engine.set_attention_tile_mass: the share in (0, 1] of the pooled softmax mass to keep), for the blocks >=
+        sparse_dense_layers; set again for the new grid after set_geometry.  set_attention_tile_mass changes or clears it."""
         if token_timestep_sets:
             cfg = dict(cfg, token_timestep_sets=int(token_timestep_sets))
         self.cfg = dict(cfg)
@@ -151,6 +155,9 @@ class WanModelHIP(LoraModel):
         self._tile_mask, self._sparse_dense_layers = None, 0
         if attention_tile_mask is not None:
             self.set_attention_tile_mask(attention_tile_mask, sparse_dense_layers)
+        self._tile_mass = None
+        if attention_tile_mass:
+            self.set_attention_tile_mass(attention_tile_mass, sparse_dense_layers)
         self.device = self.engine.device
         self.sp_group = sp_group      # torch.distributed group of the ranks that share this token sequence
 
@@ -158,6 +165,11 @@ class WanModelHIP(LoraModel):
         """a tensor, a callable grid -> tensor (kept, and asked again after set_geometry), or None for plain attention"""
         self._tile_mask, self._sparse_dense_layers = (mask if callable(mask) else None), int(dense_layers)
         self.engine.set_attention_tile_mask(mask(self.latent_grid) if callable(mask) else mask, dense_layers)
+
+    def set_attention_tile_mass(self, mass, dense_layers=0):
+        """the predicted tile mask at this mass (kept, and set again for the new grid after set_geometry); 0 or None: off"""
+        self._tile_mass, self._sparse_dense_layers = (float(mass) if mass else None), int(dense_layers)
+        self.engine.set_attention_tile_mass(mass, dense_layers)
 
     def load_state_dict(self, state_dict):
         self.engine.load_weights(state_dict)
@@ -203,6 +215,8 @@ class WanModelHIP(LoraModel):
         self.latent_grid = grid
         if getattr(self, "_tile_mask", None) is not None:       # the callable form: the mask of the new grid
             self.engine.set_attention_tile_mask(self._tile_mask(grid), self._sparse_dense_layers)
+        if getattr(self, "_tile_mass", None):                   # the predictor's buffers for the new grid
+            self.engine.set_attention_tile_mass(self._tile_mass, self._sparse_dense_layers)
         self._ctx_keys, self._ctx_lru = [None, None], 0
         self._clip_key = self._vace_key = self._tok_t_key = None
         if follows:

@@ -1,7 +1,7 @@
 // Torch-free kernel A/B harness for the two MFMA-bound kernels at the Wan2.1-1.3B 480p shapes, through the C ABI.
 //
 //   kbench.bin <what> <rounds> <launches> libA.so [libB.so ...]
-//      what: gemm | attn | attn_mx8 | attn_band | attn_sparse | calib | all
+//      what: gemm | attn | attn_mx8 | attn_band | attn_sparse | attn_predict | attn_predict_sparse | calib | all
 //
 // Every library given on the command line is dlopen'ed privately (RTLD_LOCAL), so build variants of
 // libmagcache_hip.so (tools/build_variants.py, tools/build_v5_variants.py, tools/build_gemm_v2_variants.py) are measured INTERLEAVED IN ONE PROCESS on the same
@@ -42,6 +42,7 @@ struct Lib {
   decltype(&mc_op_attention_mx8) attn_mx8;
   decltype(&mc_op_attention_band) attn_band;      // null in a library older than the frame-block causal kernel (attn_band only)
   decltype(&mc_op_attention_sparse) attn_sparse;  // null in a library older than the tile-sparse kernel (attn_sparse only)
+  decltype(&mc_op_attention_tile_predict) predict;  // null in a library older than the tile-mask predictor (attn_predict* only)
   decltype(&mc_set_option) set_option;
   decltype(&mc_last_error) last_error;
 };
@@ -84,6 +85,7 @@ __global__ void count_diff(const uint32_t* a, const uint32_t* b, size_t n, unsig
   if (c) atomicAdd(out, c);
 }
 
+__device__ __forceinline__ float bf16_to_f32_dev(uint16_t v) { return __uint_as_float((uint32_t)v << 16); }
 static float bf16_to_f(uint16_t v) {
   uint32_t u = (uint32_t)v << 16;
   float f;
@@ -684,6 +686,126 @@ static void bench_attn_sparse(int Lq_pad, int H, int valid, int rounds, int laun
   for (int c = 0; c < NM; ++c) { CK(hipFree(bits_dev[c])); CK(hipFree(order_dev[c])); }
 }
 
+// The tile-mask predictor (library 0) beside the dense launch of the LAST library given (the parent commit's build, to compare
+// with it in one process; library 0's own when it is the only one), all launches interleaved round by round.
+//   with_sparse = false: the predictor alone at mass 0.9 on randn operands (its cost does not depend on the content).
+//   with_sparse = true:  operands whose attention is concentrated -- q and k are randn plus 0.6 x a direction of the token's
+//   latent frame (21 frames of 1560 tokens), q also 0.3 x the directions of the two neighbouring frames: the own frame scores
+//   ~4 nats, its neighbours ~2 nats above the rest -- and per mass: predictor + sparse launch (order NULL, what the engine
+//   runs), the sparse launch alone on the predicted bits, and the same with the heavy-first order table of the static path.
+__global__ void add_frame_directions(uint16_t* p, int rows, int valid, int D, int tpf, float own, float side) {
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < (size_t)rows * D; i += (size_t)gridDim.x * blockDim.x) {
+    const int row = (int)(i / D), col = (int)(i % D), f = min(row, valid - 1) / tpf;
+    float v = bf16_to_f32_dev(p[i]) + own * randn((size_t)f * D + col, 77);
+    if (side != 0.f) v += side * (randn((size_t)(f + 1) * D + col, 77) + (f ? randn((size_t)(f - 1) * D + col, 77) : 0.f));
+    __bf16 b = (__bf16)v;
+    p[i] = __builtin_bit_cast(uint16_t, b);
+  }
+}
+static void bench_attn_predict(int Lq_pad, int H, int valid, int rounds, int launches, bool with_sparse) {
+  const Lib& lib = g_libs[0];
+  const Lib& dense = g_libs.back();
+  if (!lib.predict || !lib.attn_sparse) {
+    fprintf(stderr, "%s: no mc_op_attention_tile_predict / mc_op_attention_sparse\n", lib.path.c_str());
+    exit(2);
+  }
+  auto scratch_bytes = (decltype(&mc_op_attention_tile_predict_scratch))dlsym(lib.h, "mc_op_attention_tile_predict_scratch");
+  const int D = H * 128, nqt = Lq_pad / 128, nkt = Lq_pad / 64, words = (nkt + 31) / 32, vq = (valid + 127) / 128, vk = (valid + 63) / 64;
+  const size_t n = (size_t)Lq_pad * D, nbits = (size_t)H * nqt * words;
+  uint16_t *Q, *K, *V, *O, *Ob;
+  for (uint16_t** p : {&Q, &K, &V, &O, &Ob}) CK(hipMalloc(p, n * 2));
+  fill_bf16<<<2048, 256>>>(Q, n, 11, g_amp);
+  fill_bf16<<<2048, 256>>>(K, n, 12, g_amp);
+  fill_bf16<<<2048, 256>>>(V, n, 13, g_amp);
+  if (with_sparse) {
+    add_frame_directions<<<2048, 256>>>(Q, Lq_pad, valid, D, valid / 21, 0.6f, 0.3f);
+    add_frame_directions<<<2048, 256>>>(K, Lq_pad, valid, D, valid / 21, 0.6f, 0.f);
+  }
+  const float masses[2] = {0.7f, 0.9f};
+  const int NMASS = with_sparse ? 2 : 0;
+  const float scale = 1.0f / std::sqrt(128.0f);
+  void* scratch;
+  uint32_t *bits_live, *bits[2];
+  int32_t* order[2];
+  double density[2] = {0, 0};
+  CK(hipMalloc(&scratch, scratch_bytes(Lq_pad, H, Lq_pad)));
+  CK(hipMalloc(&bits_live, nbits * 4));
+  for (int m = 0; m < NMASS; ++m) {   // the bits of each mass, kept, and the order table the static path would build for them
+    CK(hipMalloc(&bits[m], nbits * 4));
+    CK(hipMalloc(&order[m], (size_t)nqt * H * 4));
+    MCL(lib, lib.predict(Q, D, K, D, Lq_pad, H, Lq_pad, valid, scale, masses[m], bits[m], scratch, nullptr));
+    std::vector<uint32_t> hb(nbits);
+    CK(hipMemcpy(hb.data(), bits[m], nbits * 4, hipMemcpyDeviceToHost));
+    std::vector<int> count((size_t)H * nqt, 0);
+    for (int r = 0; r < H * nqt; ++r) {
+      for (int kt = 0; kt < vk; ++kt) count[r] += (hb[(size_t)r * words + (kt >> 5)] >> (kt & 31)) & 1;
+      if (r % nqt < vq) density[m] += count[r];
+    }
+    density[m] /= (double)H * vq * vk;
+    std::vector<int32_t> ord((size_t)nqt * H);
+    for (size_t i = 0; i < ord.size(); ++i) ord[i] = (int32_t)i;
+    auto cnt = [&](int32_t it) { return count[(size_t)(it % H) * nqt + it / H]; };
+    std::stable_sort(ord.begin(), ord.end(), [&](int32_t x, int32_t y) {
+      return cnt(x) != cnt(y) ? cnt(x) > cnt(y) : x / H != y / H ? x / H > y / H : x < y;
+    });
+    CK(hipMemcpy(order[m], ord.data(), ord.size() * 4, hipMemcpyHostToDevice));
+  }
+  CK(hipDeviceSynchronize());
+  // kinds: 0 dense, 1 predictor alone (mass 0.9); per mass m: 2 + 3 m predictor + sparse, 3 + 3 m sparse alone, 4 + 3 m sparse, heavy first
+  const int NK = 2 + 3 * NMASS;
+  auto launch = [&](int kind) {
+    if (kind == 0) { MCL(dense, dense.attn(Q, D, K, D, 0, V, D, 0, O, D, Lq_pad, H, Lq_pad, valid, 1, scale, nullptr)); return; }
+    if (kind == 1) { MCL(lib, lib.predict(Q, D, K, D, Lq_pad, H, Lq_pad, valid, scale, 0.9f, bits_live, scratch, nullptr)); return; }
+    const int m = (kind - 2) / 3, sub = (kind - 2) % 3;
+    if (sub == 0) MCL(lib, lib.predict(Q, D, K, D, Lq_pad, H, Lq_pad, valid, scale, masses[m], bits_live, scratch, nullptr));
+    MCL(lib, lib.attn_sparse(Q, D, K, D, V, D, Ob, D, Lq_pad, H, Lq_pad, valid, sub == 0 ? bits_live : bits[m], H, sub == 2 ? order[m] : nullptr,
+                             scale, nullptr));
+  };
+  printf("# attn_predict%s: Lq_pad=%d heads=%d valid keys=%d; dense launch of %s\n", with_sparse ? "_sparse" : "", Lq_pad, H, valid,
+         dense.path.c_str());
+  hipEvent_t a, b;
+  CK(hipEventCreate(&a));
+  CK(hipEventCreate(&b));
+  float ms = 0;
+  CK(hipEventRecord(a, nullptr));
+  do {   // ~1 s warm-up of all of them
+    for (int kind = 0; kind < NK; ++kind) launch(kind);
+    CK(hipEventRecord(b, nullptr));
+    CK(hipEventSynchronize(b));
+    CK(hipEventElapsedTime(&ms, a, b));
+  } while (ms < 1000.f);
+  std::vector<std::vector<double>> t(NK);
+  for (int r = 0; r < rounds; ++r)
+    for (int kind = 0; kind < NK; ++kind) {
+      launch(kind);
+      CK(hipEventRecord(a, nullptr));
+      for (int i = 0; i < launches; ++i) launch(kind);
+      CK(hipEventRecord(b, nullptr));
+      CK(hipEventSynchronize(b));
+      CK(hipEventElapsedTime(&ms, a, b));
+      t[kind].push_back(ms / launches);
+    }
+  std::vector<double> med(NK);
+  for (int kind = 0; kind < NK; ++kind) {
+    std::sort(t[kind].begin(), t[kind].end());
+    med[kind] = t[kind][t[kind].size() / 2];
+  }
+  const double pool_bytes = 2.0 * valid * D * 2;
+  printf("%-28s median %8.4f ms | min %8.4f ms\n", "attn (dense)", med[0], t[0][0]);
+  printf("%-28s median %8.4f ms | min %8.4f ms | x%.4f of dense | one read of Q and K = %.1f MB: %.0f GB/s if it were all\n", "predict (mass 0.9)",
+         med[1], t[1][0], med[1] / med[0], pool_bytes * 1e-6, pool_bytes * 1e-9 / (med[1] * 1e-3));
+  for (int m = 0; m < NMASS; ++m) {
+    const double* x = &med[2 + 3 * m];
+    // t(density) ~ c density + predictor, c from this point: the density at which predictor + sparse would equal the dense launch
+    const double breakeven = density[m] * (med[0] - (x[0] - x[1])) / x[1];
+    printf("mass %.2f: density %.4f | predict + sparse %8.4f ms x%.3f of dense | sparse alone %8.4f ms | sparse, heavy first %8.4f ms "
+           "(order NULL costs x%.3f) | break-even density %.3f\n", masses[m], density[m], x[0], x[0] / med[0], x[1], x[2], x[1] / x[2], breakeven);
+  }
+  fflush(stdout);
+  for (void* p : {(void*)Q, (void*)K, (void*)V, (void*)O, (void*)Ob, (void*)scratch, (void*)bits_live}) CK(hipFree(p));
+  for (int m = 0; m < NMASS; ++m) { CK(hipFree(bits[m])); CK(hipFree(order[m])); }
+}
+
 // ------------------------------------------------------------------------------------- calibration statistics
 static void bench_calib(int M, int D, int rounds, int launches) {
   float *r, *rp, *stats;
@@ -711,7 +833,7 @@ static void bench_calib(int M, int D, int rounds, int launches) {
 
 int main(int argc, char** argv) {
   if (argc < 5) {
-    fprintf(stderr, "usage: kbench.bin <gemm|attn|attn_mx8|attn_band|attn_sparse|attn_keys|calib|all> <rounds> <launches> libA.so [libB.so ...]\n");
+    fprintf(stderr, "usage: kbench.bin <gemm|attn|attn_mx8|attn_band|attn_sparse|attn_predict|attn_predict_sparse|attn_keys|calib|all> <rounds> <launches> libA.so [libB.so ...]\n");
     return 2;
   }
   if (getenv("KBENCH_AMP")) g_amp = (float)atof(getenv("KBENCH_AMP"));
@@ -732,6 +854,7 @@ int main(int argc, char** argv) {
     l.attn_mx8 = (decltype(l.attn_mx8))dlsym(l.h, "mc_op_attention_mx8");
     l.attn_band = (decltype(l.attn_band))dlsym(l.h, "mc_op_attention_band");
     l.attn_sparse = (decltype(l.attn_sparse))dlsym(l.h, "mc_op_attention_sparse");
+    l.predict = (decltype(l.predict))dlsym(l.h, "mc_op_attention_tile_predict");
     l.set_option = (decltype(l.set_option))dlsym(l.h, "mc_set_option");
     l.last_error = (decltype(l.last_error))dlsym(l.h, "mc_last_error");
     if (!l.gemm || !l.attn || !l.calib || !l.set_option || !l.last_error) {
@@ -764,6 +887,8 @@ int main(int argc, char** argv) {
   if (what == "attn_mx8") bench_attn_mx8(32768, 12, 32760, rounds, std::max(1, launches / 4));
   if (what == "attn_band") bench_attn_band(32768, 12, 32760, rounds, std::max(1, launches / 4));
   if (what == "attn_sparse") bench_attn_sparse(32768, 12, 32760, rounds, std::max(1, launches / 4));
+  if (what == "attn_predict") bench_attn_predict(32768, 12, 32760, rounds, std::max(1, launches / 4), false);
+  if (what == "attn_predict_sparse") bench_attn_predict(32768, 12, 32760, rounds, std::max(1, launches / 4), true);
   if (what == "attn_strided" || what == "all") bench_attn("self480p_qkv", 32768, 12, 32760, 1.0f, rounds, std::max(1, launches / 4), true);
   if (what == "attn_keys") bench_attn_keys(32768, 12, rounds, launches);
   if (what == "attn1") bench_attn("self480p", 32768, 12, 32760, 1.0f, rounds, launches);          // one shape (PMC passes)
