@@ -254,6 +254,66 @@ mc_status mc_mmdit_ip_adapter_scale(mc_mmdit* e, int adapter, const float* scale
 mc_status mc_mmdit_ip_adapter_select(mc_mmdit* e, int slot);
 mc_status mc_mmdit_ip_adapter_clear(mc_mmdit* e);
 
+/* Tile-sparse joint attention (csrc/attention_joint.hip): the tile-sparse self-attention of mc_op_attention_sparse for a joint
+ * text + image sequence, with the rule for the text rows inside the kernel.  Operands as mc_op_attention_sparse: Q [Lq_pad, ldq],
+ * K / V [rows, ld] of which the first `valid` rows are keys, O [Lq_pad, ldo], bf16, head_dim 128; tile_mask_dev uint32
+ * [mask_heads][nqt][words] in device memory.
+ * Let nqt = Lq_pad / 128, nkt = rows / 64, words = (nkt + 31) / 32.  Two half-open tile ranges are passed by value:
+ * qdense = [q0, q1) in query tiles and kalways = [k0, k1) in key tiles.  Either may be empty.
+ *   Query row i of head h sees key j iff j < valid and at least one of these holds:
+ *   - i / 128 in qdense,
+ *   - j / 64 in kalways,
+ *   - bit (j/64) & 31 of word (j/64) >> 5 of mask row [mask_heads == 1 ? 0 : h][i / 128] is set.
+ * Bits at tiles >= nkt are ignored, and so are bits at tiles whose first key is >= valid.  A query tile that sees no key stores
+ * O = 0.  All bits set, or qdense covering every tile, is plain attention.
+ * Launch order: without a table the (q1 - q0) * n_heads dense items are the first blocks of the launch (they are the heaviest),
+ * the others follow in ascending order, heads innermost.  order_dev: NULL, or a device permutation of the item ids
+ * qt * n_heads + head that overrides this (clamped, never an address out of range; the result does not depend on it).
+ * MC_EINVAL, with nothing launched, for: Lq_pad % 256 != 0, rows % 64 != 0, valid outside [1, rows], a leading dimension that is
+ * no multiple of 8 or shorter than n_heads * 128, a null or not 16-byte aligned operand, Lq_pad * ld or rows * ld beyond 32-bit
+ * byte offsets, mask_heads neither 1 nor n_heads, q0 < 0, q0 > q1, q1 > nqt, k0 < 0, k0 > k1, k1 > nkt, a mask or table that is
+ * not 4-byte aligned, a NULL mask unless qdense covers every query tile (a dense query tile never reads the bitmap). */
+mc_status mc_op_attention_joint_sparse(const void* Q, long ldq, const void* K, long ldk, const void* V, long ldv, void* O, long ldo,
+                                       int Lq_pad, int n_heads, int rows, int valid, const uint32_t* tile_mask_dev, int mask_heads,
+                                       int q0, int q1, int k0, int k1, const int32_t* order_dev, float scale, mc_stream stream);
+
+/* Tile-sparse joint attention in the engine.  The blocks with index >= dense_blocks (double and single blocks alike, counted in
+ * forward order) run their joint attention on mc_op_attention_joint_sparse's kernel instead of the dense one, Q and K | V read in
+ * place; every other attention (the HunyuanVideo token refiner, the IP-Adapters) and everything else is untouched.  The caller's
+ * mask speaks about tiles of the joint rows in the engine's own row order (FLUX, Qwen-Image [text ; image]; HunyuanVideo
+ * [image ; text]) with nqt = Sp / 128 and nkt = Sp / 64, Sp = txt_len + img_tokens padded to 256; it never states the text rule.
+ * The engine derives the two ranges per forward from its own rows:
+ *   kalways = the key tiles that intersect the rows [txt0, txt0 + valid text rows)
+ *   qdense  = the query tiles that intersect the rows [txt0, txt0 + txt_len)
+ * so every query sees every valid text key and every text query sees every key.  A tile that holds text AND image rows
+ * (HunyuanVideo: img_tokens is no multiple of the tile) is therefore dense as a whole: the conservative choice.
+ *   mc_mmdit_set_attention_tile_mask   a static mask: bits_host uint32 [mask_heads][nqt][words], mask_heads 1 or num_heads, copied to
+ *                        device memory the engine owns, outside the workspace.  NULL turns it off.
+ *   mc_mmdit_set_attention_tile_mass   the predicted mask: before each sparse block, mc_op_attention_tile_predict's two launches
+ *                        (magcache_hip.h states the rule) over the joint q and k columns with the block's valid key count write
+ *                        one engine-owned mask [num_heads][nqt][words]; mask and pool buffers are allocated at this call.  The
+ *                        kernel only adds tiles to what the predictor kept, so the kept share of the pooled softmax is >= mass.
+ *                        mass == 0 turns it off.
+ *   mc_mmdit_attention_tile_state      mode 0 off, 1 static, 2 predicted; the sizes, dense_blocks and mass in force (0 when off;
+ *                        NULL outputs are skipped).  density: for a static mask the visited (item, valid key tile) pairs under the
+ *                        full rule over all such pairs, counted for a prompt of txt_len valid rows; -1 in predicted mode, 0 when off.
+ *   mc_mmdit_read_attention_tile_mask  the mask in force, copied after a device synchronisation: the static one, or what the
+ *                        predictor wrote for the last sparse block (zeros before the first forward).  A first call with
+ *                        bits_host NULL asks for the sizes (they are written, the status is MC_EINVAL); MC_ESTATE when off.
+ * MC_EINVAL at the setters, each named in the error text: a sequence-parallel engine (sp_size > 1: this kernel has no
+ * log-sum-exp to merge key shards with), nqt / nkt that do not match the geometry in force, mask_heads neither 1 nor num_heads,
+ * mass outside [0, 1], more key tiles than the predictor serves, a negative dense_blocks, the other mode being on.
+ * MC_ESTATE: a setter between mc_mmdit_begin and mc_mmdit_end; a forward whose geometry no longer matches the buffers after
+ * mc_mmdit_set_geometry (set the mode again, or off); a Qwen-Image forward with txt_valid < txt_len while a mode is on, with
+ * nothing launched -- that attention is two launches merged by their log-sum-exp and this kernel has none, so it is refused
+ * and never silently run dense.  With neither mode ever set every launch is what it was.  The setters may allocate and
+ * synchronise the device: between forwards only, never stream-captured. */
+mc_status mc_mmdit_set_attention_tile_mask(mc_mmdit* e, const uint32_t* bits_host, int mask_heads, int nqt, int nkt, int dense_blocks);
+mc_status mc_mmdit_set_attention_tile_mass(mc_mmdit* e, float mass, int dense_blocks);
+mc_status mc_mmdit_attention_tile_state(const mc_mmdit* e, int* mode, int* mask_heads, int* nqt, int* nkt, int* dense_blocks,
+                                        float* mass, double* density);
+mc_status mc_mmdit_read_attention_tile_mask(const mc_mmdit* e, uint32_t* bits_host, size_t bytes, int* mask_heads, int* nqt, int* nkt);
+
 /* One transformer evaluation (the body of the reference's magcache_forward).
  *   img_dev    FLUX: packed latent tokens [img_tokens, in_channels]; HunyuanVideo: latent [16, F, H, W]   (fp32)
  *   timestep   the value the embedding sees: FLUX timestep*1000 (:303), HunyuanVideo t (:54); guidance likewise

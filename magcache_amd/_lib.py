@@ -210,6 +210,12 @@ SIGNATURES = {
     "mc_mmdit_unpatchify": (_i, [_vp, _vp, _vp, _vp]),
     "mc_mmdit_calib_stats": (_i, [_vp, C.POINTER(C.c_float), _vp]),
     "mc_mmdit_state_reset": (_i, [_vp]),
+    "mc_op_attention_joint_sparse": (_i, [_vp, _l, _vp, _l, _vp, _l, _vp, _l, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _f, _vp]),
+    "mc_mmdit_set_attention_tile_mask": (_i, [_vp, _vp, _i, _i, _i, _i]),
+    "mc_mmdit_set_attention_tile_mass": (_i, [_vp, _f, _i]),
+    "mc_mmdit_attention_tile_state": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i),
+                                           C.POINTER(_f), C.POINTER(_d)]),
+    "mc_mmdit_read_attention_tile_mask": (_i, [_vp, _vp, _sz, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
 }
 
 

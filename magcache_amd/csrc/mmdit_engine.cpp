@@ -48,7 +48,8 @@
 // registers under its upstream names; every GEMM goes through linear(), which takes operands and shape from the descriptor
 // (a second Linear makes it the row-split launch over two row ranges); a double block is double_pre / double_post over one
 // or two row ranges (Range) -- both streams in merged launches by default, one stream per call for the two-stream modes and
-// sequence parallel; every attention launch is attend() over a key set (Keys).
+// sequence parallel; every attention launch is attend() over a key set (Keys), or, for the joint attention of the blocks an
+// attention tile mask or mass names (opt-in, one GPU), attend_joint_sparse() over the same key set.
 // fp8_linear 2 / 3 (opt-in): the block Linears that read a LayerNorm or GELU output (3: the attention output too) keep an
 // MX copy -- block scales, elements in the engine's MxFormat -- and run on launch_gemm_mx over the exact rows of ONE range (the
 // kernels guard a partial last tile and have no row-split launch): a double block is then one pass per stream, in row order, on
@@ -153,6 +154,23 @@ struct mc_mmdit {
   float* ip_h32 = nullptr;           // set_image scratch: the projection [kIpMaxKeys, cross_dim] fp32 ...
   bf16_t* ip_hb = nullptr;           // ... and its LayerNorm, the operand of the K|V Linears
   int ip_h_cross = 0;
+  // Tile-sparse joint attention (mc_mmdit_set_attention_tile_mask / _mass): 0 off, 1 a static mask, 2 the mask predicted per
+  // block.  tile_bits: the device copy of the static mask [tile_heads][nqt][words], or what the predictor writes ([H][nqt]
+  // [words]); tile_scratch: the predictor's pooled rows.  Both owned here, outside the workspace, for the tile counts they were
+  // allocated at; tile_dense_blocks: the first block that runs on attention_joint.hip.
+  int tile_mode = 0;
+  uint32_t* tile_bits = nullptr;
+  void* tile_scratch = nullptr;
+  int tile_heads = 0, tile_nqt = 0, tile_nkt = 0, tile_dense_blocks = 0;
+  float tile_mass = 0.f;
+  double tile_density = 0.0;
+  void tile_drop() {
+    if (tile_bits) (void)hipFree(tile_bits);
+    if (tile_scratch) (void)hipFree(tile_scratch);
+    tile_bits = nullptr; tile_scratch = nullptr;
+    tile_mode = tile_heads = tile_nqt = tile_nkt = tile_dense_blocks = 0;
+    tile_mass = 0.f; tile_density = 0.0;
+  }
 
   template <class T>
   T* buf(const char* name) const { return work.get<T>(name); }
@@ -316,6 +334,21 @@ void apply_geometry(mc_mmdit* e, const Geometry& g, const Rows& r) {
   e->cfg.latent_f = g.latent_f; e->cfg.latent_h = g.latent_h; e->cfg.latent_w = g.latent_w;
   e->Li = r.Li; e->Lt = r.Lt; e->S = r.S; e->Sp = r.Sp; e->Lrp = r.Lrp;
   e->tok0 = r.tok0; e->img0 = r.img0; e->txt0 = r.txt0;
+}
+
+// The two tile ranges attention_joint.hip takes, from the engine's own rows (the rule: magcache_mmdit.h): kalways = the key tiles
+// that intersect the `txt_valid` valid text rows, qdense = the query tiles that intersect all Lt text rows.  A tile that holds
+// text and image rows counts as text.
+mc::AttnJointRanges joint_ranges(const mc_mmdit* e, int txt_valid) {
+  return {e->txt0 / 128, (e->txt0 + e->Lt + 127) / 128, e->txt0 / 64, (e->txt0 + txt_valid + 63) / 64};
+}
+// the buffers of the tile-sparse joint attention were sized for the geometry in force
+mc_status tile_mask_fits(const mc_mmdit* e) {
+  if (e->tile_mode && (e->tile_nqt != e->Sp / 128 || e->tile_nkt != e->Sp / 64))
+    return fail(MC_ESTATE, "the attention tile %s was set for %d x %d tiles (a joint sequence padded to %d rows) and the geometry in "
+                           "force pads to %d rows: call mc_mmdit_set_attention_tile_%s again, or turn it off",
+                e->tile_mode == 1 ? "mask" : "mass", e->tile_nqt, e->tile_nkt, e->tile_nqt * 128, e->Sp, e->tile_mode == 1 ? "mask" : "mass");
+  return MC_OK;
 }
 
 // the workspace of a geometry: needs of `e` only what mc_mmdit_create fixed (cfg widths, d, H, P, Kp, mod_rows)
@@ -609,6 +642,7 @@ void mc_mmdit_destroy(mc_mmdit* e) {
     if (e->ev_join[i]) (void)hipEventDestroy(e->ev_join[i]);
   }
   e->weights.free_all();
+  e->tile_drop();
   delete e;
 }
 
@@ -656,6 +690,123 @@ mc_status mc_mmdit_set_geometry(mc_mmdit* e, int img_tokens, int latent_f, int l
   e->cn_double.clear();   // the samples were [img_tokens, d] of the old geometry
   e->cn_single.clear();
   return forget_workspace_state(e);
+}
+
+// ---- tile-sparse joint attention (attention_joint.hip): the two modes, their state and the mask in force
+mc_status mc_mmdit_set_attention_tile_mask(mc_mmdit* e, const uint32_t* bits_host, int mask_heads, int nqt, int nkt, int dense_blocks) {
+  if (!e) return fail(MC_EINVAL, "null engine");
+  if (e->begun) return fail(MC_ESTATE, "mc_mmdit_set_attention_tile_mask between mc_mmdit_begin and mc_mmdit_end");
+  if (!bits_host) {   // off (a predicted mask stays): earlier forwards may still be reading the copy
+    if (e->tile_mode == 1) {
+      HIP_TRY(hipDeviceSynchronize());
+      e->tile_drop();
+    }
+    return MC_OK;
+  }
+  if (e->tile_mode == 2)
+    return fail(MC_EINVAL, "mc_mmdit_set_attention_tile_mask: the attention tile mass is on (mc_mmdit_set_attention_tile_mass, %g) "
+                           "and predicts the mask of every launch; turn it off first", (double)e->tile_mass);
+  if (e->P > 1)
+    return fail(MC_EINVAL, "mc_mmdit_set_attention_tile_mask: the engine is sequence parallel (sp_size %d) and the tile-sparse joint "
+                           "kernel has no log-sum-exp to merge key shards with", e->P);
+  if (nqt != e->Sp / 128 || nkt != e->Sp / 64)
+    return fail(MC_EINVAL, "mc_mmdit_set_attention_tile_mask: %d x %d tiles, the geometry in force (%d joint rows padded to %d) has "
+                           "%d x %d", nqt, nkt, e->S, e->Sp, e->Sp / 128, e->Sp / 64);
+  if (mask_heads != 1 && mask_heads != e->H)
+    return fail(MC_EINVAL, "mc_mmdit_set_attention_tile_mask: mask_heads %d must be 1 or num_heads (%d)", mask_heads, e->H);
+  if (dense_blocks < 0) return fail(MC_EINVAL, "mc_mmdit_set_attention_tile_mask: dense_blocks (%d) must be >= 0", dense_blocks);
+  // density under the full rule, for a prompt of Lt valid rows: all S joint rows are keys
+  const mc::AttnJointRanges r = joint_ranges(e, e->Lt);
+  const int words = (nkt + 31) / 32, vq = (e->S + 127) / 128, vk = (e->S + 63) / 64;
+  long visited = 0;
+  for (int h = 0; h < mask_heads; ++h)
+    for (int qt = 0; qt < vq; ++qt) {
+      const uint32_t* row = bits_host + ((size_t)h * nqt + qt) * words;
+      const bool dense = qt >= r.q0 && qt < r.q1;
+      for (int kt = 0; kt < vk; ++kt) visited += (dense || (kt >= r.k0 && kt < r.k1) || ((row[kt >> 5] >> (kt & 31)) & 1)) ? 1 : 0;
+    }
+  uint32_t* bits_dev = nullptr;
+  const size_t bits_bytes = (size_t)mask_heads * nqt * words * 4;
+  if (hipMalloc((void**)&bits_dev, bits_bytes) != hipSuccess || hipMemcpy(bits_dev, bits_host, bits_bytes, hipMemcpyHostToDevice) != hipSuccess) {
+    if (bits_dev) (void)hipFree(bits_dev);
+    return fail(MC_EHIP, "mc_mmdit_set_attention_tile_mask: no device memory for the mask (%zu bytes)", bits_bytes);
+  }
+  if (e->tile_mode) HIP_TRY(hipDeviceSynchronize());   // earlier forwards may still be reading the copy this one replaces
+  e->tile_drop();
+  e->tile_mode = 1; e->tile_bits = bits_dev;
+  e->tile_heads = mask_heads; e->tile_nqt = nqt; e->tile_nkt = nkt; e->tile_dense_blocks = dense_blocks;
+  e->tile_density = (double)visited / ((double)mask_heads * vq * vk);
+  return MC_OK;
+}
+
+mc_status mc_mmdit_set_attention_tile_mass(mc_mmdit* e, float mass, int dense_blocks) {
+  if (!e) return fail(MC_EINVAL, "null engine");
+  if (e->begun) return fail(MC_ESTATE, "mc_mmdit_set_attention_tile_mass between mc_mmdit_begin and mc_mmdit_end");
+  if (!(mass >= 0.f && mass <= 1.f)) return fail(MC_EINVAL, "mc_mmdit_set_attention_tile_mass: mass (%g) must lie in [0, 1]", (double)mass);
+  if (mass == 0.f) {   // off (a static mask stays): earlier forwards may still be using the buffers
+    if (e->tile_mode == 2) {
+      HIP_TRY(hipDeviceSynchronize());
+      e->tile_drop();
+    }
+    return MC_OK;
+  }
+  if (e->tile_mode == 1)
+    return fail(MC_EINVAL, "mc_mmdit_set_attention_tile_mass: a static tile mask is set (mc_mmdit_set_attention_tile_mask); turn it "
+                           "off first");
+  if (dense_blocks < 0) return fail(MC_EINVAL, "mc_mmdit_set_attention_tile_mass: dense_blocks (%d) must be >= 0", dense_blocks);
+  if (e->P > 1)
+    return fail(MC_EINVAL, "mc_mmdit_set_attention_tile_mass: the engine is sequence parallel (sp_size %d): a rank holds a shard of the "
+                           "keys, and the tile-sparse joint kernel has no log-sum-exp to merge shards with", e->P);
+  const int nqt = e->Sp / 128, nkt = e->Sp / 64;
+  if (nkt > mc::kAttnPredictMaxNkt)
+    return fail(MC_EINVAL, "mc_mmdit_set_attention_tile_mass: the geometry in force has %d key tiles, the predictor serves %d", nkt,
+                mc::kAttnPredictMaxNkt);
+  uint32_t* bits = nullptr;
+  void* scratch = nullptr;
+  const size_t bits_bytes = (size_t)e->H * nqt * ((nkt + 31) / 32) * 4, scratch_bytes = mc::attention_predict_scratch_bytes(e->Sp, e->H, e->Sp);
+  if (hipMalloc((void**)&bits, bits_bytes) != hipSuccess || hipMalloc(&scratch, scratch_bytes) != hipSuccess ||
+      hipMemset(bits, 0, bits_bytes) != hipSuccess) {   // (zeros: what mc_mmdit_read_attention_tile_mask shows before the first forward)
+    if (bits) (void)hipFree(bits);
+    if (scratch) (void)hipFree(scratch);
+    return fail(MC_EHIP, "mc_mmdit_set_attention_tile_mass: no device memory for the mask (%zu bytes) and the pooled rows (%zu bytes)",
+                bits_bytes, scratch_bytes);
+  }
+  HIP_TRY(hipDeviceSynchronize());   // the mask is clear before a forward on any stream; earlier forwards are done with the old buffers
+  e->tile_drop();
+  e->tile_mode = 2; e->tile_bits = bits; e->tile_scratch = scratch;
+  e->tile_heads = e->H; e->tile_nqt = nqt; e->tile_nkt = nkt; e->tile_dense_blocks = dense_blocks;
+  e->tile_mass = mass; e->tile_density = -1.0;
+  return MC_OK;
+}
+
+mc_status mc_mmdit_attention_tile_state(const mc_mmdit* e, int* mode, int* mask_heads, int* nqt, int* nkt, int* dense_blocks,
+                                        float* mass, double* density) {
+  if (!e) return fail(MC_EINVAL, "null engine");
+  if (mode) *mode = e->tile_mode;
+  if (mask_heads) *mask_heads = e->tile_heads;
+  if (nqt) *nqt = e->tile_nqt;
+  if (nkt) *nkt = e->tile_nkt;
+  if (dense_blocks) *dense_blocks = e->tile_dense_blocks;
+  if (mass) *mass = e->tile_mass;
+  if (density) *density = e->tile_density;
+  return MC_OK;
+}
+
+mc_status mc_mmdit_read_attention_tile_mask(const mc_mmdit* e, uint32_t* bits_host, size_t bytes, int* mask_heads, int* nqt, int* nkt) {
+  if (!e) return fail(MC_EINVAL, "null engine");
+  if (!e->tile_mode)
+    return fail(MC_ESTATE, "mc_mmdit_read_attention_tile_mask: neither mc_mmdit_set_attention_tile_mask nor mc_mmdit_set_attention_tile_mass "
+                           "is on");
+  const size_t need = (size_t)e->tile_heads * e->tile_nqt * ((e->tile_nkt + 31) / 32) * 4;
+  if (mask_heads) *mask_heads = e->tile_heads;   // (also when the room is too small: a caller may ask for the sizes first)
+  if (nqt) *nqt = e->tile_nqt;
+  if (nkt) *nkt = e->tile_nkt;
+  if (!bits_host || bytes < need)
+    return fail(MC_EINVAL, "mc_mmdit_read_attention_tile_mask: the mask of %d x %d x %d tiles takes %zu bytes, %zu are offered",
+                e->tile_heads, e->tile_nqt, e->tile_nkt, need, bits_host ? bytes : (size_t)0);
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(bits_host, e->tile_bits, need, hipMemcpyDeviceToHost));
+  return MC_OK;
 }
 
 mc_status mc_mmdit_buffer_info(const mc_mmdit* e, const char* name, size_t* offset, size_t* bytes) {
@@ -799,6 +950,21 @@ Keys gathered_keys(const mc_mmdit* e, int skip_shard_p1) {
 mc_status attend(const mc_mmdit* e, int q_rows_pad, const Keys& keys, const float* lse_in, float* lse_out, hipStream_t s) {
   HIP_TRY(mc::launch_attention_keys(e->buf<bf16_t>("qkv"), 3L * e->d, e->buf<bf16_t>("am"), 5L * e->d, q_rows_pad, e->H, keys,
                                     lse_in, lse_out, s));
+  return MC_OK;
+}
+// The joint attention of a block in the tile-sparse form (mc_mmdit_set_attention_tile_mask / _mass): all Sp rows of "qkv" as
+// queries over the joint key set -> "am"[:, 0:d] on attention_joint.hip, the text ranges from the engine's own rows.  Predicted
+// mode first writes the mask from the block's q and k columns (attention_predict.hip, unchanged: the kernel adds the text rule).
+mc_status attend_joint_sparse(const mc_mmdit* e, const Keys& keys, hipStream_t s) {
+  MC_TRY(tile_mask_fits(e));   // (every forward checks this before its first launch; here no launch may touch memory past the mask)
+  const bf16_t* Q = e->buf<bf16_t>("qkv");
+  const mc::AttnParams a = mc::attn_params(Q, keys.ld, e->buf<bf16_t>("am"), 5L * e->d, e->Sp, e->H, keys, mc::kAttnScale, nullptr, nullptr);
+  if (e->tile_mode == 2) {
+    const mc::AttnPredict pr = {Q, keys.ld, keys.k, keys.ld, e->Sp, e->H, keys.rows, keys.valid, mc::kAttnScale, e->tile_mass,
+                                e->tile_bits, e->tile_scratch};
+    HIP_TRY(mc::launch_attention_predict(pr, s));
+  }
+  HIP_TRY(mc::launch_attention_joint(a, mc::AttnTileMask{e->tile_bits, e->tile_heads, nullptr}, joint_ranges(e, e->txt_valid), s));
   return MC_OK;
 }
 
@@ -1017,6 +1183,11 @@ mc_status begin_impl(mc_mmdit* e, const float* img_dev, double timestep, double 
     return fail(MC_ESTATE, "skip requested but the residual cache is empty");
   if (mode == MC_MODE_CALIB && !c.calibration) return fail(MC_ESTATE, "engine was created without calibration");
   if (mode == MC_MODE_CALIB && e->P > 1) return fail(MC_ESTATE, "calibration runs on one GPU in this engine");
+  MC_TRY(tile_mask_fits(e));   // before the first launch: no attention launch may read or write past the mask
+  if (e->tile_mode && qw && txt_valid < e->Lt)
+    return fail(MC_ESTATE, "Qwen-Image forward with txt_valid %d < txt_len %d while the attention tile %s is on: that attention is two "
+                           "launches merged by their log-sum-exp and the tile-sparse joint kernel has none; turn the mode off or run "
+                           "at txt_len == txt_valid (mc_mmdit_set_geometry)", txt_valid, e->Lt, e->tile_mode == 1 ? "mask" : "mass");
   e->mode = mode;
   e->branch = branch;
   e->txt_valid = (hy || qw) ? txt_valid : e->Lt;
@@ -1391,7 +1562,9 @@ mc_status mc_mmdit_block_post(mc_mmdit* e, int blk, mc_stream stream_) {
     MC_TRY(attend(e, Sp, image_keys(e), nullptr, lse, s));
     MC_TRY(attend(e, Sp, text_keys(e), lse, nullptr, s));
   } else if (e->P == 1) {   // all S rows of qkv are keys (HunyuanVideo: its valid text rows are the last of them)
-    MC_TRY(attend(e, Sp, local_keys(e, 0, Sp, c.family == MC_FAMILY_HUNYUAN ? Li + e->txt_valid : S), nullptr, nullptr, s));
+    const Keys keys = local_keys(e, 0, Sp, c.family == MC_FAMILY_HUNYUAN ? Li + e->txt_valid : S);
+    if (e->tile_mode && blk >= e->tile_dense_blocks) MC_TRY(attend_joint_sparse(e, keys, s));
+    else MC_TRY(attend(e, Sp, keys, nullptr, nullptr, s));
   } else if (e->local_attn_blk == blk) {   // mc_mmdit_block_attn_local did the local shard and the text keys: the remote shards, merged
     e->local_attn_blk = -1;
     MC_TRY(attend(e, Sp, gathered_keys(e, e->rank + 1), e->buf<float>("attn_lse"), nullptr, s));

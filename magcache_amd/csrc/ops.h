@@ -291,7 +291,8 @@ hipError_t launch_adapter_merge(const bf16_t* base, long ld_base, bf16_t* out, l
 hipError_t launch_widen_f32(const void* src, int src_f32, float* dst, size_t n, hipStream_t stream);
 
 // ---------------------------------------------------------------- attention (attention_v3.hip, attention_v5.hip,
-// attention_mx8.hip, attention_band.hip, attention_sparse.hip; the tile geometry v3, band and sparse share: attention_tile.h)
+// attention_mx8.hip, attention_band.hip, attention_sparse.hip, attention_joint.hip; the tile geometry v3, band, sparse and joint
+// share: attention_tile.h)
 struct AttnParams {
   const bf16_t* Q; long ldq;
   const bf16_t* K; long ldk; long k_shard_stride;
@@ -376,6 +377,18 @@ struct AttnTileMask { const uint32_t* bits; int mask_heads; const int32_t* order
 // n_heads, fewer than 2^31 items.
 bool attention_sparse_supports(const AttnParams& p, const AttnTileMask& m);
 hipError_t launch_attention_sparse(const AttnParams& p, const AttnTileMask& m, hipStream_t stream);
+
+// ---------------------------------------------------------------- tile-sparse joint attention (attention_joint.hip)
+// The same bitmap, for a joint text + image sequence (MM-DiT).  With qdense = [q0, q1) in 128-row query tiles and kalways =
+// [k0, k1) in 64-key tiles, query row i of head h sees key j iff j < shard_valid and at least one of: i / 128 in qdense, j / 64
+// in kalways, the bit of (j / 64) in mask row [mask_heads == 1 ? 0 : h][i / 128] is set (the rule in full:
+// include/magcache_mmdit.h at mc_op_attention_joint_sparse, and the head of attention_joint.hip).  Without an order table the
+// qdense items are the first blocks of the launch.
+struct AttnJointRanges { int q0, q1, k0, k1; };
+// attention_sparse_supports' conditions, except that bits may be null when qdense covers every query tile; and
+// 0 <= q0 <= q1 <= Lq_pad / 128, 0 <= k0 <= k1 <= shard_rows / 64.
+bool attention_joint_supports(const AttnParams& p, const AttnTileMask& m, const AttnJointRanges& r);
+hipError_t launch_attention_joint(const AttnParams& p, const AttnTileMask& m, const AttnJointRanges& r, hipStream_t stream);
 
 // ---------------------------------------------------------------- tile-mask predictor (attention_predict.hip)
 // Writes the bits launch_attention_sparse reads, mask_heads == n_heads, from the launch's own Q and K: per (head, 128-row query

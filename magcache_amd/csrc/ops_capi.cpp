@@ -2,6 +2,7 @@
 // own buffers -- the sampler, the parity tests, the A/B tools), mc_set_option, mc_last_error and mc_version.
 #include <string>
 
+#include "../../include/magcache_mmdit.h"   // mc_op_attention_joint_sparse is declared beside the engine it serves
 #include "host.h"
 
 using mc::bf16_t;
@@ -165,6 +166,23 @@ mc_status mc_op_attention_sparse(const void* Q, long ldq, const void* K, long ld
     return fail(MC_EINVAL, "attention_sparse: needs Lq_pad %% 256 == 0, rows %% 64 == 0, 1 <= valid <= rows, leading dimensions %% 8 == 0 "
                            "and >= n_heads * 128, operands non-null and 16-byte aligned, a non-null 4-byte aligned tile mask, "
                            "mask_heads 1 or n_heads (%d), Lq_pad * ld and rows * ld within 32-bit byte offsets", mask_heads);
+  HIP_TRY(err);
+  return MC_OK;
+}
+
+// tile-sparse joint attention (attention_joint.hip; declared in include/magcache_mmdit.h)
+mc_status mc_op_attention_joint_sparse(const void* Q, long ldq, const void* K, long ldk, const void* V, long ldv, void* O, long ldo,
+                                       int Lq_pad, int n_heads, int rows, int valid, const uint32_t* tile_mask, int mask_heads, int q0,
+                                       int q1, int k0, int k1, const int32_t* order, float scale, mc_stream s) {
+  const mc::AttnParams a = attn_op(Q, ldq, K, ldk, 0, V, ldv, 0, O, ldo, Lq_pad, n_heads, rows, valid, 1, scale);
+  hipError_t err = mc::launch_attention_joint(a, mc::AttnTileMask{tile_mask, mask_heads, order}, mc::AttnJointRanges{q0, q1, k0, k1},
+                                              (hipStream_t)s);
+  if (err == hipErrorInvalidValue)
+    return fail(MC_EINVAL, "attention_joint_sparse: needs Lq_pad %% 256 == 0, rows %% 64 == 0, 1 <= valid <= rows, leading dimensions "
+                           "%% 8 == 0 and >= n_heads * 128, operands non-null and 16-byte aligned, 0 <= q0 <= q1 <= Lq_pad / 128 "
+                           "(%d, %d), 0 <= k0 <= k1 <= rows / 64 (%d, %d), a 4-byte aligned tile mask that is non-null unless qdense "
+                           "covers every query tile, mask_heads 1 or n_heads (%d), Lq_pad * ld and rows * ld within 32-bit byte offsets",
+                q0, q1, k0, k1, mask_heads);
   HIP_TRY(err);
   return MC_OK;
 }

@@ -122,6 +122,64 @@ class MMDiTEngine(EngineHost):
         self._rope_key = None
         self._controlnet = None
 
+    # ---- tile-sparse joint attention (csrc/attention_joint.hip; the rule: include/magcache_mmdit.h)
+    @property
+    def joint_tiles(self):
+        """(nqt, nkt) of the joint sequence in force: Sp / 128 query tiles and Sp / 64 key tiles, Sp = txt_len + img_tokens
+        padded to 256"""
+        sp = (self.txt_len + self.img_tokens + 255) // 256 * 256
+        return sp // 128, sp // 64
+
+    def set_attention_tile_mask(self, mask, dense_blocks=0):
+        """Joint attention under a static block mask (mc_mmdit_set_attention_tile_mask): a bool tensor [mask_heads, Sp / 128,
+        Sp / 64] over tiles of the joint rows in the engine's own row order, mask_heads 1 or num_heads
+        (sparse_masks.joint_tile_mask lifts an image mask); None turns it off.  The mask never states the text rule: every
+        query sees every valid text key and every text query sees every key, whatever its bits say.  Blocks below dense_blocks
+        (double and single alike, in forward order) stay dense.  The mask belongs to the geometry it was built for: after
+        set_geometry set it again (a forward under a stale mask raises).  Refused on a sharded engine and while the tile mass
+        is on; a Qwen-Image forward with txt_valid < txt_len raises while it is on."""
+        if mask is None:
+            check(self.lib.mc_mmdit_set_attention_tile_mask(self.h, None, 0, 0, 0, 0))
+            return
+        from .sparse_masks import pack_tile_mask
+        m = torch.as_tensor(mask).detach().cpu()
+        if m.dtype != torch.bool or m.dim() != 3:
+            raise ValueError(f"set_attention_tile_mask: a bool tensor [mask_heads, Sp / 128, Sp / 64], got {m.dtype} {tuple(m.shape)}")
+        words = pack_tile_mask(m)                                       # int32 [mask_heads, nqt, words], host
+        check(self.lib.mc_mmdit_set_attention_tile_mask(self.h, words.data_ptr(), m.shape[0], m.shape[1], m.shape[2], int(dense_blocks)))
+
+    def set_attention_tile_mass(self, mass, dense_blocks=0):
+        """Joint attention under a mask predicted on the device, per block, from the block's own joint q and k
+        (mc_mmdit_set_attention_tile_mass; mc_op_attention_tile_predict states the predictor's rule, the kernel adds the text
+        rule on top, so the kept share of the pooled softmax is >= mass).  0 or None turns it off.  Same refusals and the same
+        life across set_geometry as set_attention_tile_mask; refused while a static mask is set."""
+        check(self.lib.mc_mmdit_set_attention_tile_mass(self.h, float(mass or 0.0), int(dense_blocks)))
+
+    @property
+    def attention_tile_state(self):
+        """None when off, else a dict: mode ("static" | "predicted"), mask_heads, nqt, nkt, dense_blocks, mass (0 for a static
+        mask), density (visited share of the valid tile pairs under the full rule for a static mask, None when predicted)"""
+        mode, mh, q, k, db, mass, dens = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_float(), C.c_double()
+        check(self.lib.mc_mmdit_attention_tile_state(self.h, C.byref(mode), C.byref(mh), C.byref(q), C.byref(k), C.byref(db),
+                                                     C.byref(mass), C.byref(dens)))
+        if not mode.value:
+            return None
+        return dict(mode="static" if mode.value == 1 else "predicted", mask_heads=mh.value, nqt=q.value, nkt=k.value,
+                    dense_blocks=db.value, mass=mass.value, density=dens.value if mode.value == 1 else None)
+
+    def read_attention_tile_mask(self):
+        """bool [mask_heads, nqt, nkt] on the CPU: the tile mask in force -- the static one, or the one the predictor wrote for
+        the last sparse block (mc_mmdit_read_attention_tile_mask; synchronises the device).  The bits alone: the text rule is
+        the kernel's."""
+        from .sparse_masks import unpack_tile_mask
+        mh, q, k = C.c_int(), C.c_int(), C.c_int()
+        status = self.lib.mc_mmdit_read_attention_tile_mask(self.h, None, 0, C.byref(mh), C.byref(q), C.byref(k))     # the sizes
+        if status != _lib.MC_EINVAL:
+            check(status)
+        words = torch.zeros(mh.value, q.value, (k.value + 31) // 32, dtype=torch.int32)
+        check(self.lib.mc_mmdit_read_attention_tile_mask(self.h, words.data_ptr(), words.numel() * 4, None, None, None))
+        return unpack_tile_mask(words, k.value)
+
     def residual(self, branch=None):
         """fp32 [img_tokens / sp_size, dim] view of the cached residual (reference previous_residual / residual_cache);
         `branch` 0 / 1: that CFG branch's cache (Qwen-Image), None: the branch of the last forward."""
@@ -343,6 +401,43 @@ class _LoraMethods(LoraModel):
         return self.engine.load_lora(sd, adapter=adapter, scale=scale, strict=strict, prefix=prefix)
 
 
+class _SparseAttention:
+    """Tile-sparse joint attention on the model objects, as WanModelHIP has it: attention_tile_mask= (a bool tensor [mask_heads,
+    Sp / 128, Sp / 64] over the joint rows, or a callable (nqt, nkt, geometry) -> such a tensor, called again for every new
+    geometry; geometry: dict(text_first, txt_len, img_tokens, latent_grid)) or attention_tile_mass= (the predicted mask), for the
+    blocks >= sparse_dense_blocks.  The text rule is the kernel's (MMDiTEngine.set_attention_tile_mask)."""
+    _tile_mask = _tile_mass = None
+    _sparse_dense_blocks = 0
+
+    def _sparse_init(self, attention_tile_mask, attention_tile_mass, sparse_dense_blocks):
+        if attention_tile_mask is not None and attention_tile_mass:
+            raise ValueError("attention_tile_mask and attention_tile_mass are exclusive")
+        if attention_tile_mask is not None:
+            self.set_attention_tile_mask(attention_tile_mask, sparse_dense_blocks)
+        if attention_tile_mass:
+            self.set_attention_tile_mass(attention_tile_mass, sparse_dense_blocks)
+
+    def _sparse_geometry(self):
+        e = self.engine
+        return dict(text_first=e.family != MC_FAMILY_HUNYUAN, txt_len=e.txt_len, img_tokens=e.img_tokens, latent_grid=e.latent_grid)
+
+    def set_attention_tile_mask(self, mask, dense_blocks=0):
+        """a tensor serves the geometry it was built for (a call at another one raises); a callable follows the geometry"""
+        self._tile_mask, self._sparse_dense_blocks = mask, int(dense_blocks)
+        self.engine.set_attention_tile_mask(mask(*self.engine.joint_tiles, self._sparse_geometry()) if callable(mask) else mask, dense_blocks)
+
+    def set_attention_tile_mass(self, mass, dense_blocks=0):
+        self._tile_mass, self._sparse_dense_blocks = (mass or None), int(dense_blocks)
+        self.engine.set_attention_tile_mass(mass, dense_blocks)
+
+    def _sparse_follow_geometry(self):
+        """after MMDiTEngine.set_geometry: what can follow the new geometry is set again for it"""
+        if callable(self._tile_mask):
+            self.set_attention_tile_mask(self._tile_mask, self._sparse_dense_blocks)
+        elif self._tile_mass:
+            self.set_attention_tile_mass(self._tile_mass, self._sparse_dense_blocks)
+
+
 def _lora_call_scale(model, kwargs):
     """joint_attention_kwargs / attention_kwargs["scale"] of a call, as scale_lora_layers reads it (magcache_flux.py:62-67,
     magcache_generate.py:107-113): the call's factor on every loaded adapter, 1.0 without the key.  Without adapters the key
@@ -362,6 +457,7 @@ def _shim_set_geometry(model, img_tokens, latent_grid, txt_len, fresh):
                          f"{model.txt_len} text tokens -> {img_tokens} / {txt_len}")
     model.engine.set_geometry(img_tokens, latent_grid, txt_len)
     model.img_tokens, model.txt_len = img_tokens, txt_len
+    model._sparse_follow_geometry()
     if hasattr(model, "cnt"):
         for k, v in fresh.items():
             if hasattr(model, k):
@@ -381,13 +477,14 @@ def flux_rope(ids, axes_dim=(16, 56, 56), theta=10000.0):
     return (torch.from_numpy(np.concatenate(cos, 1).astype(np.float32)), torch.from_numpy(np.concatenate(sin, 1).astype(np.float32)))
 
 
-class FluxTransformer2DModelHIP(_LoraMethods):
+class FluxTransformer2DModelHIP(_LoraMethods, _SparseAttention):
     """Stands where diffusers' FluxTransformer2DModel stands.  One (image tokens, text length) geometry per instance, unless
     dynamic_geometry=True: then every call may bring its own (MMDiTEngine.set_geometry)."""
     dynamic_geometry = False
 
     def __init__(self, cfg, img_tokens, txt_len=512, device="cuda:0", calibration=True, engine=None, sp_rank=0,
-                 sp_size=1, sp_group=None, dynamic_geometry=False, fp8_linear=0, mx_fp4=False, mx_fp6=False):
+                 sp_size=1, sp_group=None, dynamic_geometry=False, fp8_linear=0, mx_fp4=False, mx_fp6=False,
+                 attention_tile_mask=None, attention_tile_mass=None, sparse_dense_blocks=0):
         self.config = SimpleNamespace(**cfg)
         self.cfg = dict(cfg)
         dim = cfg["attention_head_dim"] * cfg["num_attention_heads"]
@@ -402,6 +499,7 @@ class FluxTransformer2DModelHIP(_LoraMethods):
         self.device = self.engine.device
         self.sp_group = sp_group
         self._ids_key = None
+        self._sparse_init(attention_tile_mask, attention_tile_mass, sparse_dense_blocks)
 
     def load_state_dict(self, sd):
         self.engine.load_weights(sd)
@@ -597,13 +695,14 @@ def init_flux_magcache(model, num_inference_steps=28, magcache_thresh=0.24, K=5,
 
 
 # ============================================================================================== HunyuanVideo
-class HYVideoDiffusionTransformerHIP(_LoraMethods):
+class HYVideoDiffusionTransformerHIP(_LoraMethods, _SparseAttention):
     """Stands where hyvideo's HYVideoDiffusionTransformer stands.  One latent grid / text length per instance, unless
     dynamic_geometry=True: then every call may bring its own (MMDiTEngine.set_geometry)."""
     dynamic_geometry = False
 
     def __init__(self, cfg, latent_grid, txt_len=256, device="cuda:0", calibration=True, engine=None, sp_rank=0,
-                 sp_size=1, sp_group=None, dynamic_geometry=False, fp8_linear=0, mx_fp4=False, mx_fp6=False):
+                 sp_size=1, sp_group=None, dynamic_geometry=False, fp8_linear=0, mx_fp4=False, mx_fp6=False,
+                 attention_tile_mask=None, attention_tile_mass=None, sparse_dense_blocks=0):
         self.cfg = dict(cfg)
         self.sp_group = sp_group
         self.dynamic_geometry = dynamic_geometry
@@ -622,6 +721,7 @@ class HYVideoDiffusionTransformerHIP(_LoraMethods):
                                             calibration=calibration, device=device, sp_rank=sp_rank, sp_size=sp_size,
                                             fp8_linear=fp8_linear, mx_fp4=mx_fp4, mx_fp6=mx_fp6)
         self.device = self.engine.device
+        self._sparse_init(attention_tile_mask, attention_tile_mass, sparse_dense_blocks)
 
     def load_state_dict(self, sd):
         self.engine.load_weights(sd)
@@ -745,7 +845,7 @@ def qwen_rope(img_shapes, max_txt_len, axes_dim=(16, 56, 56), theta=10000.0):
     return torch.cat(cos, 1).contiguous(), torch.cat(sin, 1).contiguous()
 
 
-class QwenImageTransformer2DModelHIP(_LoraMethods):
+class QwenImageTransformer2DModelHIP(_LoraMethods, _SparseAttention):
     """Stands where diffusers' QwenImageTransformer2DModel stands (Qwen-Image and Qwen-Image-Edit: the same transformer;
     Edit's image tokens are the noisy latent's followed by the reference image's).  One (image tokens, longest prompt)
     geometry per instance; every call may carry a shorter prompt (cond vs the " " negative prompt, unpadded).  The two
@@ -754,7 +854,8 @@ class QwenImageTransformer2DModelHIP(_LoraMethods):
     dynamic_geometry = False
 
     def __init__(self, cfg, img_tokens, txt_len=1024, device="cuda:0", calibration=True, engine=None, sp_size=1,
-                 dynamic_geometry=False, fp8_linear=0, mx_fp4=False, mx_fp6=False):
+                 dynamic_geometry=False, fp8_linear=0, mx_fp4=False, mx_fp6=False,
+                 attention_tile_mask=None, attention_tile_mass=None, sparse_dense_blocks=0):
         self.config = SimpleNamespace(**cfg)
         self.cfg = dict(cfg)
         self.dynamic_geometry = dynamic_geometry
@@ -767,6 +868,7 @@ class QwenImageTransformer2DModelHIP(_LoraMethods):
                                             calibration=calibration, device=device, sp_size=sp_size, fp8_linear=fp8_linear, mx_fp4=mx_fp4, mx_fp6=mx_fp6)
         self.device = self.engine.device
         self._shapes_key = None
+        self._sparse_init(attention_tile_mask, attention_tile_mass, sparse_dense_blocks)
 
     def load_state_dict(self, sd):
         """diffusers state_dict names (img_in, txt_norm, txt_in, time_text_embed.timestep_embedder, transformer_blocks.{i}.*,

@@ -4,7 +4,10 @@ A mask is a bool tensor [mask_heads, nqt, nkt] over (128-row query tile, 64-key 
 Lp = a multiple of 256 rows: nqt = Lp / 128, nkt = Lp / 64.  The kernel is tile-granular by contract, so a rule stated on
 elements is served by its conservative TILE COVER: tile (qt, kt) is visible iff some visible element pair (i, j), i, j < L,
 lies inside it.  Nothing here loops over elements at real sizes: temporal_decay_tile_mask works on (query tile, key frame)
-intervals."""
+intervals.
+
+The MM-DiT engine (MMDiTEngine.set_attention_tile_mask, mc_op_attention_joint_sparse) takes the same words over its JOINT text +
+image rows; joint_tile_mask lifts an image mask there and leaves the text bits clear, because that kernel supplies the text rule."""
 import numpy as np
 import torch
 
@@ -51,6 +54,38 @@ def tile_cover(vis, L):
         cols[:L] = np.asarray(rows, dtype=bool).any(0)
         out[qt] = cols.reshape(nkt, KT).any(1)
     return torch.from_numpy(out)
+
+
+def joint_tile_mask(image_mask, text_first, txt_len, img_tokens):
+    """Lift a mask over the IMAGE tokens to the joint rows of an MM-DiT engine (MMDiTEngine.set_attention_tile_mask).
+    image_mask: bool [mask_heads, >= ceil(Li / 128), >= ceil(Li / 64)] over tiles of the Li = img_tokens image tokens counted
+    from 0 (what a grid builder such as temporal_decay_tile_mask returns); the joint rows are [text ; image] (text_first: FLUX,
+    Qwen-Image) or [image ; text] (HunyuanVideo), S = txt_len + Li of them, padded to Sp.  Element rule: joint rows (i, j) that
+    are both image rows are visible iff image_mask holds tile ((i - img0) / 128, (j - img0) / 64), img0 = the first image row;
+    a pair with a text row is NOT stated here -- the kernel supplies the text rule (every query sees the valid text keys, text
+    queries see everything), so text bits stay clear.  Returns the tile cover of that rule, bool [mask_heads, Sp / 128,
+    Sp / 64]: the image tiles offset by img0, which need not be a multiple of the tile (a joint tile then covers two image
+    tiles and takes the union)."""
+    m = torch.as_tensor(image_mask).detach().cpu().numpy().astype(bool)
+    Lt, Li = int(txt_len), int(img_tokens)
+    if m.ndim != 3 or m.shape[1] < (Li + QT - 1) // QT or m.shape[2] < (Li + KT - 1) // KT:
+        raise ValueError(f"joint_tile_mask: a bool [mask_heads, >= {(Li + QT - 1) // QT}, >= {(Li + KT - 1) // KT}] image mask, got {m.shape}")
+    img0 = Lt if text_first else 0
+    Sp = padded_len(Lt + Li)
+
+    def spans(tile, n):   # per joint tile: does it hold image rows, and the first and last image tile they fall into
+        t = np.arange(n)
+        lo = np.maximum(t * tile, img0) - img0
+        hi = np.minimum((t + 1) * tile, img0 + Li) - 1 - img0
+        ok = hi >= lo
+        return ok, np.where(ok, lo // tile, 0), np.where(ok, hi // tile, 0)
+    okq, q_lo, q_hi = spans(QT, Sp // QT)
+    okk, k_lo, k_hi = spans(KT, Sp // KT)
+    out = np.zeros((m.shape[0], Sp // QT, Sp // KT), dtype=bool)
+    for qa in (q_lo, q_hi):
+        for ka in (k_lo, k_hi):
+            out |= m[:, qa][:, :, ka]
+    return torch.from_numpy(out & okq[None, :, None] & okk[None, None, :])
 
 
 def decay_shift(d, dense_frames):

@@ -1,7 +1,8 @@
 // Torch-free kernel A/B harness for the two MFMA-bound kernels at the Wan2.1-1.3B 480p shapes, through the C ABI.
 //
 //   kbench.bin <what> <rounds> <launches> libA.so [libB.so ...]
-//      what: gemm | attn | attn_mx8 | attn_band | attn_sparse | attn_predict | attn_predict_sparse | calib | all
+//      what: gemm | attn | attn_mx8 | attn_band | attn_sparse | attn_joint | attn_predict | attn_predict_sparse | calib | all
+//      (attn_joint: the MM-DiT joint shapes, HunyuanVideo 720p and FLUX 1024^2; KBENCH_JOINT picks another)
 //
 // Every library given on the command line is dlopen'ed privately (RTLD_LOCAL), so build variants of
 // libmagcache_hip.so (tools/build_variants.py, tools/build_v5_variants.py, tools/build_gemm_v2_variants.py) are measured INTERLEAVED IN ONE PROCESS on the same
@@ -806,6 +807,114 @@ static void bench_attn_predict(int Lq_pad, int H, int valid, int rounds, int lau
   for (int m = 0; m < NMASS; ++m) { CK(hipFree(bits[m])); CK(hipFree(order[m])); }
 }
 
+// The tile-sparse JOINT kernel (library 0) beside the dense launch of the LAST library given, on the MM-DiT engine's layout:
+// q | k | v in one [Sp, 3d] buffer, O in [Sp, 5d].  The joint rows are [text ; image] (text_first) or [image ; text]; the ranges
+// are the engine's (kalways = key tiles of the valid text rows, qdense = query tiles of the text rows).  Per density p: a random
+// bitmap, one row per (head, query tile), each bit set with probability p; the launch with the kernel's own arithmetic item order
+// (dense items first) and with the identity order passed as a table (memory order: in [image ; text] the dense tiles run last) --
+// the difference is the tail the item order removes.  density = visited (item, valid key tile) pairs under the full rule over all
+// pairs; ideal = density x dense time.  Last, the predictor (mass 0.9) on the same q and k as a share of the dense launch.
+static void bench_attn_joint(const char* name, bool text_first, int Li, int Lt, const std::vector<double>& ps, int rounds, int launches) {
+  const Lib& lib = g_libs[0];
+  const Lib& dense = g_libs.back();
+  auto joint = (mc_status (*)(const void*, long, const void*, long, const void*, long, void*, long, int, int, int, int, const uint32_t*, int,
+                              int, int, int, int, const int32_t*, float, void*))dlsym(lib.h, "mc_op_attention_joint_sparse");
+  auto scratch_bytes = (decltype(&mc_op_attention_tile_predict_scratch))dlsym(lib.h, "mc_op_attention_tile_predict_scratch");
+  if (!joint || !lib.predict || !scratch_bytes) {
+    fprintf(stderr, "%s: no mc_op_attention_joint_sparse / mc_op_attention_tile_predict\n", lib.path.c_str());
+    exit(2);
+  }
+  const int H = 24, d = H * 128, S = Li + Lt, Sp = (S + 255) / 256 * 256, valid = S;
+  const int nqt = Sp / 128, nkt = Sp / 64, words = (nkt + 31) / 32, vq = (S + 127) / 128, vk = (valid + 63) / 64;
+  const int txt0 = text_first ? 0 : Li;
+  const int q0 = txt0 / 128, q1 = (txt0 + Lt + 127) / 128, k0 = txt0 / 64, k1 = (txt0 + Lt + 63) / 64;
+  const int NP = (int)ps.size();
+  uint16_t *qkv, *am;
+  CK(hipMalloc(&qkv, (size_t)Sp * 3 * d * 2));
+  CK(hipMalloc(&am, (size_t)Sp * 5 * d * 2));
+  fill_bf16<<<2048, 256>>>(qkv, (size_t)Sp * 3 * d, 31, g_amp);
+  std::vector<uint32_t*> bits(NP);
+  std::vector<double> density(NP);
+  for (int c = 0; c < NP; ++c) {
+    std::vector<uint32_t> m((size_t)H * nqt * words, 0);
+    uint64_t lcg = 0x9e3779b97f4a7c15ull + (uint64_t)c;
+    double visited = 0;
+    for (int h = 0; h < H; ++h)
+      for (int qt = 0; qt < nqt; ++qt)
+        for (int kt = 0; kt < nkt; ++kt) {
+          lcg = lcg * 6364136223846793005ull + 1442695040888963407ull;
+          const bool bit = (double)(lcg >> 11) * (1.0 / 9007199254740992.0) < ps[c];
+          if (bit) m[((size_t)h * nqt + qt) * words + (kt >> 5)] |= 1u << (kt & 31);
+          if (qt < vq && kt < vk && (bit || (qt >= q0 && qt < q1) || (kt >= k0 && kt < k1))) visited += 1;
+        }
+    density[c] = visited / ((double)H * vq * vk);
+    CK(hipMalloc(&bits[c], m.size() * 4));
+    CK(hipMemcpy(bits[c], m.data(), m.size() * 4, hipMemcpyHostToDevice));
+  }
+  std::vector<int32_t> ident((size_t)nqt * H);
+  for (size_t i = 0; i < ident.size(); ++i) ident[i] = (int32_t)i;
+  int32_t* ident_dev;
+  CK(hipMalloc(&ident_dev, ident.size() * 4));
+  CK(hipMemcpy(ident_dev, ident.data(), ident.size() * 4, hipMemcpyHostToDevice));
+  uint32_t* bits_live;
+  void* scratch;
+  CK(hipMalloc(&bits_live, (size_t)H * nqt * words * 4));
+  CK(hipMalloc(&scratch, scratch_bytes(Sp, H, Sp)));
+  CK(hipDeviceSynchronize());
+  const float scale = 1.0f / std::sqrt(128.0f);
+  const uint16_t *Q = qkv, *K = qkv + d, *V = qkv + 2 * d;
+  // kinds: 0 dense (last library), 1 + 2c / 2 + 2c density c in arithmetic / identity order, 2 NP + 1 the predictor
+  const int NK = 2 * NP + 2;
+  auto launch = [&](int kind) {
+    if (kind == 0) MCL(dense, dense.attn(Q, 3L * d, K, 3L * d, 0, V, 3L * d, 0, am, 5L * d, Sp, H, Sp, valid, 1, scale, nullptr));
+    else if (kind <= 2 * NP)
+      MCL(lib, joint(Q, 3L * d, K, 3L * d, V, 3L * d, am, 5L * d, Sp, H, Sp, valid, bits[(kind - 1) / 2], H, q0, q1, k0, k1,
+                     (kind - 1) % 2 ? ident_dev : nullptr, scale, nullptr));
+    else MCL(lib, lib.predict(Q, 3L * d, K, 3L * d, Sp, H, Sp, valid, scale, 0.9f, bits_live, scratch, nullptr));
+  };
+  printf("# attn_joint %s: %s, image %d + text %d rows padded to %d, %d heads, ld 3d / 5d; dense launch from %s\n", name,
+         text_first ? "[text ; image]" : "[image ; text]", Li, Lt, Sp, H, dense.path.c_str());
+  hipEvent_t a, b;
+  CK(hipEventCreate(&a));
+  CK(hipEventCreate(&b));
+  float ms = 0;
+  for (int kind = 0; kind < NK; ++kind) launch(kind);   // warm-up: every kind once, then the dense launch for ~0.5 s
+  CK(hipEventRecord(a, nullptr));
+  do {
+    launch(0);
+    CK(hipEventRecord(b, nullptr));
+    CK(hipEventSynchronize(b));
+    CK(hipEventElapsedTime(&ms, a, b));
+  } while (ms < 500.f);
+  std::vector<std::vector<double>> t(NK);
+  for (int r = 0; r < rounds; ++r)
+    for (int kind = 0; kind < NK; ++kind) {
+      launch(kind);
+      CK(hipEventRecord(a, nullptr));
+      for (int i = 0; i < launches; ++i) launch(kind);
+      CK(hipEventRecord(b, nullptr));
+      CK(hipEventSynchronize(b));
+      CK(hipEventElapsedTime(&ms, a, b));
+      t[kind].push_back(ms / launches);
+    }
+  std::vector<double> med(NK);
+  for (int kind = 0; kind < NK; ++kind) {
+    std::sort(t[kind].begin(), t[kind].end());
+    med[kind] = t[kind][t[kind].size() / 2];
+  }
+  printf("%-22s median %9.4f ms %7.1f TF | min %9.4f ms\n", "attn (dense)", med[0], 4.0 * valid * (double)valid * d * 1e-12 / (med[0] * 1e-3), t[0][0]);
+  for (int c = 0; c < NP; ++c) {
+    const double ar = med[1 + 2 * c], id = med[2 + 2 * c];
+    printf("bitmap p %.2f: density %.4f | dense first %9.4f ms (min %9.4f) x%.3f of dense, measured / ideal %.3f | identity order %9.4f ms "
+           "(min %9.4f) | identity / dense first %.3f\n", ps[c], density[c], ar, t[1 + 2 * c][0], ar / med[0], ar / (density[c] * med[0]), id,
+           t[2 + 2 * c][0], id / ar);
+  }
+  printf("predictor (mass 0.9)   median %9.4f ms | min %9.4f ms | %.2f %% of the dense launch\n", med[NK - 1], t[NK - 1][0], 100.0 * med[NK - 1] / med[0]);
+  fflush(stdout);
+  for (void* p : {(void*)qkv, (void*)am, (void*)ident_dev, (void*)bits_live, scratch}) CK(hipFree(p));
+  for (int c = 0; c < NP; ++c) CK(hipFree(bits[c]));
+}
+
 // ------------------------------------------------------------------------------------- calibration statistics
 static void bench_calib(int M, int D, int rounds, int launches) {
   float *r, *rp, *stats;
@@ -833,7 +942,7 @@ static void bench_calib(int M, int D, int rounds, int launches) {
 
 int main(int argc, char** argv) {
   if (argc < 5) {
-    fprintf(stderr, "usage: kbench.bin <gemm|attn|attn_mx8|attn_band|attn_sparse|attn_predict|attn_predict_sparse|attn_keys|calib|all> <rounds> <launches> libA.so [libB.so ...]\n");
+    fprintf(stderr, "usage: kbench.bin <gemm|attn|attn_mx8|attn_band|attn_sparse|attn_joint|attn_predict|attn_predict_sparse|attn_keys|calib|all> <rounds> <launches> libA.so [libB.so ...]\n");
     return 2;
   }
   if (getenv("KBENCH_AMP")) g_amp = (float)atof(getenv("KBENCH_AMP"));
@@ -889,6 +998,23 @@ int main(int argc, char** argv) {
   if (what == "attn_sparse") bench_attn_sparse(32768, 12, 32760, rounds, std::max(1, launches / 4));
   if (what == "attn_predict") bench_attn_predict(32768, 12, 32760, rounds, std::max(1, launches / 4), false);
   if (what == "attn_predict_sparse") bench_attn_predict(32768, 12, 32760, rounds, std::max(1, launches / 4), true);
+  if (what == "attn_joint") {
+    // KBENCH_JOINT="first|last:image rows:text rows:p1,p2,..": one shape of the caller's; default: HunyuanVideo 720p 129 f and FLUX 1024^2
+    if (const char* o = getenv("KBENCH_JOINT")) {
+      char pos[8] = {0}, list[128] = {0};
+      int li = 0, lt = 0;
+      if (sscanf(o, "%7[a-z]:%d:%d:%127s", pos, &li, &lt, list) != 4 || li <= 0 || lt < 0) {
+        fprintf(stderr, "KBENCH_JOINT=first|last:image rows:text rows:p1,p2,..\n");
+        return 2;
+      }
+      std::vector<double> ps;
+      for (char* tok = strtok(list, ","); tok; tok = strtok(nullptr, ",")) ps.push_back(atof(tok));
+      bench_attn_joint("custom", std::string(pos) == "first", li, lt, ps, rounds, std::max(1, launches / 4));
+    } else {
+      bench_attn_joint("hunyuan720p", false, 118800, 256, {0.14, 0.45, 1.0}, rounds, std::max(1, launches / 16));
+      bench_attn_joint("flux1024", true, 4096, 512, {0.14, 0.45, 1.0}, rounds, launches);
+    }
+  }
   if (what == "attn_strided" || what == "all") bench_attn("self480p_qkv", 32768, 12, 32760, 1.0f, rounds, std::max(1, launches / 4), true);
   if (what == "attn_keys") bench_attn_keys(32768, 12, rounds, launches);
   if (what == "attn1") bench_attn("self480p", 32768, 12, 32760, 1.0f, rounds, launches);          // one shape (PMC passes)
