@@ -172,8 +172,8 @@ mc_status mc_create(const mc_config* cfg, mc_engine** out);
  * _set_magnitude, mc_op_adapter_merge / _scratch; the frame-block causal self-attention adds calls only: mc_set_causal_blocks,
  * mc_engine_causal_blocks, mc_op_attention_band; the tile-sparse self-attention adds calls only: mc_set_attention_tile_mask,
  * mc_engine_attention_tile_mask, mc_op_attention_sparse; the predicted tile mask adds calls only: mc_set_attention_tile_mass,
- * mc_engine_attention_tile_mass, mc_read_attention_tile_mask, mc_op_attention_tile_predict / _scratch; mc_version() names the
- * library's. */
+ * mc_engine_attention_tile_mass, mc_read_attention_tile_mask, mc_op_attention_tile_predict / _scratch; the sharded tile mask adds calls
+ * only: mc_set_attention_tile_mask_sharded, mc_op_attention_sparse_partial; mc_version() names the library's. */
 mc_status mc_create_sized(const mc_config* cfg, size_t cfg_bytes, mc_engine** out);
 void mc_destroy(mc_engine* e);
 /* 1: this engine's quantised Linears are MXFP4 (it was created under mc_set_option("mx_fp4", 1) with fp8_linear 2 | 3); else 0 */
@@ -211,6 +211,18 @@ mc_status mc_engine_causal_blocks(const mc_engine* e, int* frames_per_block, int
  * over all of them (NULL outputs are skipped; mask_heads 0 = off). */
 mc_status mc_set_attention_tile_mask(mc_engine* e, const uint32_t* bits_host, int mask_heads, int nqt, int nkt, int dense_layers);
 mc_status mc_engine_attention_tile_mask(const mc_engine* e, int* mask_heads, int* nqt, int* nkt, int* dense_layers, double* density);
+/* The same static mask on a SEQUENCE-PARALLEL engine (sp_size > 1 or sp_phases; MC_ESTATE on any other), in the tile space of the
+ * shards: this rank's Lp query rows (nqt = Lp / 128) against the keys of all P ranks, nkt = P * Lp / 64, bit p * (Lp / 64) + t =
+ * key tile t of rank p's shard (tiles are counted per shard: L / P need not be a multiple of 64; rank p holds tokens
+ * [p L / P, (p + 1) L / P)).  bits_host: uint32 [mask_heads][nqt][(nkt + 31) / 32].  Every launch of the self-attention chain of
+ * a block l >= dense_layers (a VACE block counts as the main layer it feeds) -- the local shard and each gather round -- then
+ * runs on attention_sparse_shards.hip over its slice of the mask row, always in the chained form (merged in place by the
+ * log-sum-exp, whatever the option "sp_attn_partials" says); blocks below, and the engine once the mask is off (NULL), launch
+ * what they always did.  Copy at the call, exclusivity (causal blocks, tile mass, "attn_mx8"), MC_ESTATE between mc_embed and
+ * mc_head, and the check that every query tile with valid rows sees a valid key -- taken over all shards -- are
+ * mc_set_attention_tile_mask's; there is no order table.  mc_engine_attention_tile_mask reports this mask with the nkt above. */
+mc_status mc_set_attention_tile_mask_sharded(mc_engine* e, const uint32_t* bits_host, int mask_heads, int nqt, int nkt,
+                                             int dense_layers);
 /* Predicted tile mask: the content-adaptive first stage the training-free sparse video-DiT methods share (pool q and k per
  * block, score the pooled blocks, keep the smallest set of key blocks that carries a chosen share of each query block's softmax
  * mass), run on the device inside the forward, once per layer, from that layer's own q and k (after q/k RMSNorm and RoPE).
@@ -774,6 +786,29 @@ mc_status mc_op_attention_partial(const void* Q_dev, long ldq, const void* K_dev
                                   int Lq_pad, int n_heads, int shard_rows, int shard_valid, int n_shards,
                                   float scale, int skip_shard, float* lse_out_dev, const float* lse_in_dev,
                                   mc_stream stream);
+/* Tile-sparse self-attention over key shards, with the log-sum-exp (attention_sparse_shards.hip): mc_op_attention_partial's
+ * arguments and meaning -- n_shards shards of shard_rows rows (multiple of 64), the first shard_valid of each are keys,
+ * skip_shard >= 0 leaves that shard out, lse_out / lse_in as there --, restricted by a slice of a tile-mask row:
+ *   - bits_dev is uint32 [mask_heads][Lq_pad / 128][row_words] in device memory, mask_heads 1 or n_heads;
+ *   - query row i of head h sees key j (j < shard_valid) of shard s iff bit bit0 + s * bit_shard_stride + j / 64 of row
+ *     [mask_heads == 1 ? 0 : h][i / 128] is set (bit b: bit b & 31 of word b >> 5);
+ *   - only the ranges [bit0 + s * bit_shard_stride, + ceil(shard_valid / 64)) of the visited shards are read: other bits mean
+ *     nothing to this launch, so one mask row can serve every launch of a sequence-parallel chain (the local shard and each
+ *     gather round), each with its own bit0 and stride;
+ *   - a query tile that sees no key in this launch: without lse_in, O = 0 exactly and lse_out = -inf; with lse_in, O is not
+ *     touched and lse_out = lse_in.  A row whose lse_in is -inf takes this launch's result alone.  No NaN arises;
+ *   - all addressed bits set is mc_op_attention_partial.
+ * order_dev as at mc_op_attention_sparse.  Refused with MC_EINVAL, nothing launched: Lq_pad % 256, shard_rows % 64, shard_valid
+ * outside 1..shard_rows, a leading dimension % 8 or below n_heads * 128, Q / K / V / O null or not 16-byte aligned, an lse
+ * array not 16-byte aligned, a skip that leaves no shard, a shard stride that is negative or no multiple of 8, a K / V span
+ * beyond 32-bit byte offsets, a mask that is null or not 4-byte aligned, mask_heads other than 1 or n_heads, a negative bit0 or
+ * stride, an addressed bit at or beyond 32 * row_words. */
+mc_status mc_op_attention_sparse_partial(const void* Q_dev, long ldq, const void* K_dev, long ldk, long k_shard_stride,
+                                         const void* V_dev, long ldv, long v_shard_stride, void* O_dev, long ldo, int Lq_pad,
+                                         int n_heads, int shard_rows, int shard_valid, int n_shards, float scale, int skip_shard,
+                                         float* lse_out_dev, const float* lse_in_dev, const uint32_t* bits_dev, int mask_heads,
+                                         int row_words, int bit0, int bit_shard_stride, const int32_t* order_dev,
+                                         mc_stream stream);
 /* the join of the two-stream attention chain (sequence parallel, sp_attn_partials): out[row, head] = sum_i w_i O_i / sum_i w_i
  * with w_i = 2^(lse_i[head][row] - max_i lse_i) over n (1..9) normalised partial results on disjoint key sets; o_parts / lse_parts
  * are HOST arrays of n device pointers (bf16 [rows][ldo] each / fp32 [d / 128][rows_pad] each, log2 units) */

@@ -53,6 +53,7 @@ SIGNATURES = {
     "mc_set_causal_blocks": (_i, [_vp, _i, _i]),
     "mc_engine_causal_blocks": (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
     "mc_set_attention_tile_mask": (_i, [_vp, _vp, _i, _i, _i, _i]),
+    "mc_set_attention_tile_mask_sharded": (_i, [_vp, _vp, _i, _i, _i, _i]),
     "mc_engine_attention_tile_mask": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_d)]),
     "mc_set_attention_tile_mass": (_i, [_vp, _f, _i]),
     "mc_engine_attention_tile_mass": (_i, [_vp, C.POINTER(_f), C.POINTER(_i)]),
@@ -138,6 +139,8 @@ SIGNATURES = {
     "mc_op_attention_tile_predict": (_i, [_vp, _l, _vp, _l, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp]),
     "mc_op_attention_mx8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _vp, _vp]),
     "mc_op_attention_partial": (_i, [_vp, _l, _vp, _l, _l, _vp, _l, _l, _vp, _l, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp]),
+    "mc_op_attention_sparse_partial": (_i, [_vp, _l, _vp, _l, _l, _vp, _l, _l, _vp, _l, _i, _i, _i, _i, _i, _f, _i, _vp, _vp,
+                                            _vp, _i, _i, _i, _i, _vp, _vp]),
     "mc_op_attn_merge": (_i, [_vp, _vp, _i, _vp, _l, _i, _i, _i, _vp]),
     "mc_op_ln_modulate": (_i, [_vp, _l, _vp, _l, _vp, _vp, _i, _f, _vp, _l, _vp, _l, _i, _i, _vp]),
     "mc_op_rmsnorm_rope": (_i, [_vp, _l, _vp, _f, _vp, _i, _i, _i, _vp]),

@@ -48,12 +48,16 @@ struct mc_engine {
   int32_t* mask_order = nullptr;
   int mask_heads = 0, mask_nqt = 0, mask_nkt = 0, mask_dense_layers = 0;
   double mask_density = 0.0;
+  // mc_set_attention_tile_mask_sharded set it: a sequence-parallel engine, mask_nkt = P * Lp / 64 (bit p * Lp / 64 + t = key tile t
+  // of rank p's shard), no order table; the launches of the chain run on attention_sparse_shards.hip
+  bool mask_sharded = false;
   void mask_drop() {
     if (mask_bits) (void)hipFree(mask_bits);
     if (mask_order) (void)hipFree(mask_order);
     mask_bits = nullptr; mask_order = nullptr;
     mask_heads = mask_nqt = mask_nkt = mask_dense_layers = 0;
     mask_density = 0.0;
+    mask_sharded = false;
   }
   // mc_set_attention_tile_mass: the share of the softmax mass the predicted mask keeps (0 = off), the first block it applies to,
   // and what the predictor writes per launch -- the mask words [H][nqt][words] and its pooled rows --, owned here, outside the
@@ -476,7 +480,7 @@ mc_status attend(const mc_engine* e, const bf16_t* Q, long ldq, bf16_t* O, const
 //   otherwise              attend() over the same operands
 // (the four are exclusive: each setter refuses while another is on)
 mc_status tile_mask_fits(const mc_engine* e) {
-  if (e->mask_heads && (e->mask_nqt != e->Lp / 128 || e->mask_nkt != e->Lp / 64))
+  if (e->mask_heads && (e->mask_nqt != e->Lp / 128 || e->mask_nkt != (e->mask_sharded ? e->P : 1) * (e->Lp / 64)))
     return fail(MC_ESTATE, "the attention tile mask was set for %d x %d tiles (a sequence padded to %d rows) and the grid in force pads "
                            "to %d rows: call mc_set_attention_tile_mask again, or with NULL", e->mask_nqt, e->mask_nkt, e->mask_nqt * 128, e->Lp);
   if (e->tile_mass > 0.f && (e->mass_nqt != e->Lp / 128 || e->mass_nkt != e->Lp / 64))
@@ -765,7 +769,8 @@ mc_status mc_set_attention_tile_mask(mc_engine* e, const uint32_t* bits_host, in
   }
   if (e->sp)
     return fail(MC_EINVAL, "mc_set_attention_tile_mask: the engine is sequence parallel (sp_size %d%s) and the tile-sparse kernel "
-                           "has no log-sum-exp to merge key shards with", e->P, e->cfg.sp_phases ? ", sp_phases" : "");
+                           "of this call has no log-sum-exp to merge key shards with: mc_set_attention_tile_mask_sharded takes the mask "
+                           "in the tile space of the shards", e->P, e->cfg.sp_phases ? ", sp_phases" : "");
   if (e->attn_mx8)
     return fail(MC_EINVAL, "mc_set_attention_tile_mask: the engine was created under the option \"attn_mx8\" and the MX fp8 "
                            "self-attention kernel has no mask");
@@ -821,6 +826,54 @@ mc_status mc_set_attention_tile_mask(mc_engine* e, const uint32_t* bits_host, in
   e->mask_bits = bits_dev; e->mask_order = order_dev;
   e->mask_heads = mask_heads; e->mask_nqt = nqt; e->mask_nkt = nkt; e->mask_dense_layers = dense_layers;
   e->mask_density = (double)visited / ((double)mask_heads * vq * vk);
+  return MC_OK;
+}
+mc_status mc_set_attention_tile_mask_sharded(mc_engine* e, const uint32_t* bits_host, int mask_heads, int nqt, int nkt, int dense_layers) {
+  if (!e) return fail(MC_EINVAL, "null engine");
+  if (e->phase_open) return fail(MC_ESTATE, "mc_set_attention_tile_mask_sharded between mc_embed and mc_head");
+  if (!e->sp)
+    return fail(MC_ESTATE, "mc_set_attention_tile_mask_sharded needs a sequence-parallel engine (sp_size > 1 or sp_phases) (one GPU: "
+                           "mc_set_attention_tile_mask)");
+  if (!bits_host) {   // off: earlier forwards may still be reading the copy
+    if (e->mask_heads) HIP_TRY(hipDeviceSynchronize());
+    e->mask_drop();
+    return MC_OK;
+  }
+  if (e->causal_frames || e->tile_mass > 0.f || e->attn_mx8)   // (none of the three can be on on a sequence-parallel engine today)
+    return fail(MC_EINVAL, "mc_set_attention_tile_mask_sharded: causal blocks, the attention tile mass or \"attn_mx8\" is on");
+  const int tpr = e->Lp / 64;   // key tiles per rank
+  if (nqt != e->Lp / 128 || nkt != e->P * tpr)
+    return fail(MC_EINVAL, "mc_set_attention_tile_mask_sharded: %d x %d tiles, rank %d of %d (%d rows padded to %d) has %d x %d", nqt, nkt,
+                e->rank, e->P, e->Lr, e->Lp, e->Lp / 128, e->P * tpr);
+  if (mask_heads != 1 && mask_heads != e->H)
+    return fail(MC_EINVAL, "mc_set_attention_tile_mask_sharded: mask_heads %d must be 1 or num_heads (%d)", mask_heads, e->H);
+  if (dense_layers < 0) return fail(MC_EINVAL, "mc_set_attention_tile_mask_sharded: dense_layers (%d) must be >= 0", dense_layers);
+  // visited valid key tiles per (mask head, query tile), over the shards of all ranks
+  const int words = (nkt + 31) / 32, vq = (e->Lr + 127) / 128, vk = (e->Lr + 63) / 64;
+  long visited = 0;
+  for (int h = 0; h < mask_heads; ++h)
+    for (int qt = 0; qt < vq; ++qt) {
+      const uint32_t* row = bits_host + ((size_t)h * nqt + qt) * words;
+      int c = 0;
+      for (int p = 0; p < e->P; ++p)
+        for (int kt = 0; kt < vk; ++kt) c += (row[(p * tpr + kt) >> 5] >> ((p * tpr + kt) & 31)) & 1;
+      visited += c;
+      if (c == 0)
+        return fail(MC_EINVAL, "mc_set_attention_tile_mask_sharded: query tile %d of mask head %d holds valid rows and sees no key tile "
+                               "with a valid key in any shard", qt, h);
+    }
+  uint32_t* bits_dev = nullptr;
+  const size_t bits_bytes = (size_t)mask_heads * nqt * words * 4;
+  if (hipMalloc((void**)&bits_dev, bits_bytes) != hipSuccess || hipMemcpy(bits_dev, bits_host, bits_bytes, hipMemcpyHostToDevice) != hipSuccess) {
+    if (bits_dev) (void)hipFree(bits_dev);
+    return fail(MC_EHIP, "mc_set_attention_tile_mask_sharded: no device memory for the mask (%zu bytes)", bits_bytes);
+  }
+  if (e->mask_heads) HIP_TRY(hipDeviceSynchronize());   // earlier forwards may still be reading the copy this one replaces
+  e->mask_drop();
+  e->mask_bits = bits_dev; e->mask_sharded = true;
+  e->mask_heads = mask_heads; e->mask_nqt = nqt; e->mask_nkt = nkt; e->mask_dense_layers = dense_layers;
+  e->mask_density = (double)visited / ((double)mask_heads * vq * e->P * vk);
+  e->attn_layer = -2;
   return MC_OK;
 }
 mc_status mc_engine_attention_tile_mask(const mc_engine* e, int* mask_heads, int* nqt, int* nkt, int* dense_layers, double* density) {
@@ -1350,7 +1403,12 @@ mc_status mc_block_pre_q(mc_engine* e, int layer, mc_stream stream_) {
 // from the other ranks); round c >= 0: chunk c of the gathered shards ("kv_gather"[c] = [P][Lp / C][2d]), without this
 // rank's shard when the local launch already covered it.  The first launch of a chain writes "ao" and the log2-sum-exp of
 // the keys it visited ("attn_lse"); every later one merges into both in the kernel epilogue (in place).
-static mc_status sp_attn_launch(mc_engine* e, int layer, int round, hipStream_t s) {
+// mask_layer: the main layer whose dense_layers decides (a VACE block counts as the main layer it feeds).  With a sharded tile
+// mask (mc_set_attention_tile_mask_sharded) and mask_layer >= dense_layers the same chain runs on attention_sparse_shards.hip:
+// the local launch reads the bits of this rank's shard, round c the bits [c lc / 64, ...) of every rank's.
+static bool sp_sparse_layer(const mc_engine* e, int mask_layer) { return e->mask_sharded && mask_layer >= e->mask_dense_layers; }
+static int sp_mask_layer(const mc_engine* e, const Layer& l) { return l.index < e->NL ? l.index : (l.index - e->NL) * e->cfg.vace_stride; }
+static mc_status sp_attn_launch(mc_engine* e, int layer, int mask_layer, int round, hipStream_t s) {
   attn_chain_open(e, layer);
   const int n_rounds = sp_rounds(e);
   bool more;   // does another launch of this chain follow?
@@ -1369,8 +1427,19 @@ static mc_status sp_attn_launch(mc_engine* e, int layer, int round, hipStream_t 
   float* lse = e->buf<float>("attn_lse");
   {
     Prof pr(e, MC_PROF_ATTN_SELF, s);   // measurement hook, see mc_profile_enable
-    MC_TRY(attend(e, e->buf<bf16_t>("qkv"), e->d, e->buf<bf16_t>("ao"), sp_keys(e, round, e->attn_local_done),
-                  e->attn_launches ? lse : nullptr, more ? lse : nullptr, s));
+    const Keys keys = sp_keys(e, round, e->attn_local_done);
+    const float* lse_in = e->attn_launches ? lse : nullptr;
+    if (sp_sparse_layer(e, mask_layer)) {
+      MC_TRY(tile_mask_fits(e));   // (no launch may read past the mask)
+      const int tpr = e->Lp / 64;
+      const mc::AttnParams a = mc::attn_params(e->buf<bf16_t>("qkv"), e->d, e->buf<bf16_t>("ao"), e->d, e->Lp, e->H, keys, mc::kAttnScale,
+                                               lse_in, more ? lse : nullptr);
+      const mc::AttnShardMask m = {e->mask_bits, e->mask_heads, (e->mask_nkt + 31) / 32,
+                                   round < 0 ? e->rank * tpr : round * (sp_chunk_rows(e) / 64), round < 0 ? 0 : tpr, nullptr};
+      HIP_TRY(mc::launch_attention_sparse_shards(a, m, s));
+    } else {
+      MC_TRY(attend(e, e->buf<bf16_t>("qkv"), e->d, e->buf<bf16_t>("ao"), keys, lse_in, more ? lse : nullptr, s));
+    }
   }
   e->attn_launches++;
   if (round < 0) e->attn_local_done = true; else e->attn_rounds_done++;
@@ -1398,7 +1467,7 @@ static mc_status sp_side_stream(mc_engine* e) {
 mc_status mc_block_attn_local(mc_engine* e, int layer, mc_stream stream_) {
   MC_TRY(check_layer_call(e, layer));
   if (!e->sp) return fail(MC_ESTATE, "mc_block_attn_local needs a sequence-parallel engine (sp_size > 1 or sp_phases)");
-  return sp_attn_launch(e, layer, -1, (hipStream_t)stream_);
+  return sp_attn_launch(e, layer, layer, -1, (hipStream_t)stream_);
 }
 
 // Self-attention over round `round` of the gathered shards (rounds in order 0 .. mc_sp_rounds - 1; the caller has made
@@ -1407,7 +1476,7 @@ mc_status mc_block_attn_round(mc_engine* e, int layer, int round, mc_stream stre
   MC_TRY(check_layer_call(e, layer));
   if (!e->sp) return fail(MC_ESTATE, "mc_block_attn_round needs a sequence-parallel engine (sp_size > 1 or sp_phases)");
   if (round < 0) return fail(MC_EINVAL, "round %d", round);
-  return sp_attn_launch(e, layer, round, (hipStream_t)stream_);
+  return sp_attn_launch(e, layer, layer, round, (hipStream_t)stream_);
 }
 
 // Rounds of the K|V all-gather per layer: round c moves rows [c Lp / C, (c + 1) Lp / C) of every rank's "kv_local" into
@@ -1470,7 +1539,7 @@ static mc_status block_post_self(mc_engine* e, const Layer& l, const float* em, 
   } else {
     // whatever the caller has not attended yet (mc_block_attn_local / mc_block_attn_round): the remaining gather rounds
     attn_chain_open(e, layer);
-    while (e->attn_rounds_done < sp_rounds(e)) MC_TRY(sp_attn_launch(e, layer, e->attn_rounds_done, s));
+    while (e->attn_rounds_done < sp_rounds(e)) MC_TRY(sp_attn_launch(e, layer, sp_mask_layer(e, l), e->attn_rounds_done, s));
     e->attn_layer = -2;
   }
   {  // x = x + o(attn) * e[2]
@@ -1720,11 +1789,11 @@ mc_status mc_blocks_sp(mc_engine* e, int layer_begin, int layer_end, int branch,
     if (!overlap)
       for (int c = 0; c < R; ++c) MC_TRY(wait_round(l, c, s));
     MC_TRY(block_pre_q(e, ly, s));
-    if (!partials) {
-      MC_TRY(sp_attn_launch(e, chain_id, -1, s));
+    if (!partials || sp_sparse_layer(e, sp_mask_layer(e, ly))) {   // a sparse layer always merges in place: attn_merge knows no -inf
+      MC_TRY(sp_attn_launch(e, chain_id, sp_mask_layer(e, ly), -1, s));
       for (int c = 0; c < R; ++c) {
         if (overlap) MC_TRY(wait_round(l, c, s));
-        MC_TRY(sp_attn_launch(e, chain_id, c, s));
+        MC_TRY(sp_attn_launch(e, chain_id, sp_mask_layer(e, ly), c, s));
       }
       return MC_OK;
     }

@@ -291,8 +291,8 @@ hipError_t launch_adapter_merge(const bf16_t* base, long ld_base, bf16_t* out, l
 hipError_t launch_widen_f32(const void* src, int src_f32, float* dst, size_t n, hipStream_t stream);
 
 // ---------------------------------------------------------------- attention (attention_v3.hip, attention_v5.hip,
-// attention_mx8.hip, attention_band.hip, attention_sparse.hip, attention_joint.hip; the tile geometry v3, band, sparse and joint
-// share: attention_tile.h)
+// attention_mx8.hip, attention_band.hip, attention_sparse.hip, attention_sparse_shards.hip, attention_joint.hip; the tile
+// geometry v3, band, sparse, sparse_shards and joint share: attention_tile.h)
 struct AttnParams {
   const bf16_t* Q; long ldq;
   const bf16_t* K; long ldk; long k_shard_stride;
@@ -377,6 +377,29 @@ struct AttnTileMask { const uint32_t* bits; int mask_heads; const int32_t* order
 // n_heads, fewer than 2^31 items.
 bool attention_sparse_supports(const AttnParams& p, const AttnTileMask& m);
 hipError_t launch_attention_sparse(const AttnParams& p, const AttnTileMask& m, hipStream_t stream);
+
+// ---------------------------------------------------------------- tile-sparse self-attention over key shards
+// (attention_sparse_shards.hip): the sequence-parallel form -- AttnParams in its FULL form (shards, a skipped shard, lse_in,
+// lse_out) and a slice of a wider mask row.
+// bits: uint32 [mask_heads][Lq_pad / 128][row_words] in device memory, mask_heads 1 or n_heads.  With tps = ceil(shard_valid / 64),
+// query row i of head h sees key j of shard s (s != the skipped one, j < shard_valid) iff bit
+//   bit0 + s * bit_shard_stride + j / 64
+// of row [mask_heads == 1 ? 0 : h][i / 128] is set (bit b is bit b & 31 of word b >> 5).  Only the ranges
+// [bit0 + s * bit_shard_stride, + tps) of the visited shards are read: bits outside them mean nothing to this launch, words
+// outside them are not loaded.  Rows [shard_valid, shard_rows) of a shard and every row of the skipped shard are never counted.
+// lse_out: log2-sum-exp of the scaled scores of the keys seen, AttnParams.lse_out's layout and unit.  lse_in: O holds a
+// normalised result over other keys; both are merged, in place.  A query tile that sees no key in this launch: without lse_in
+// O = exact zeros and lse_out = -inf; with lse_in O is not touched and lse_out = lse_in.  A row whose lse_in is -inf takes this
+// launch's result alone.  No NaN arises from any of these.
+// order: as AttnTileMask's (null: identity; clamped; the result does not depend on it).
+struct AttnShardMask { const uint32_t* bits; int mask_heads; int row_words; int bit0; int bit_shard_stride; const int32_t* order; };
+// attention_shape_ok and its own conditions: Q, K, V, O non-null and 16-byte aligned, every ld >= n_heads * 128, ldo % 8 == 0,
+// 0 <= skip_shard_p1 <= n_shards with a shard left to visit, shard strides >= 0 and % 8 == 0 (when n_shards > 1), the whole K / V
+// span ((n_shards - 1) * stride + shard_rows * ld) and Lq_pad * ldq / ldo within 32-bit byte offsets, bits non-null, bits and
+// order 4-byte aligned, mask_heads 1 or n_heads, row_words >= 1, bit0 >= 0, bit_shard_stride >= 0, every addressed bit below
+// 32 * row_words, both lse arrays 16-byte aligned (null counts), fewer than 2^31 items.
+bool attention_sparse_shards_supports(const AttnParams& p, const AttnShardMask& m);
+hipError_t launch_attention_sparse_shards(const AttnParams& p, const AttnShardMask& m, hipStream_t stream);
 
 // ---------------------------------------------------------------- tile-sparse joint attention (attention_joint.hip)
 // The same bitmap, for a joint text + image sequence (MM-DiT).  With qdense = [q0, q1) in 128-row query tiles and kalways =

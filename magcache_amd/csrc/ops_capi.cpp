@@ -342,6 +342,27 @@ mc_status mc_op_attention_partial(const void* Q, long ldq, const void* K, long l
   return MC_OK;
 }
 
+// tile-sparse self-attention over key shards, with the log-sum-exp (attention_sparse_shards.hip)
+mc_status mc_op_attention_sparse_partial(const void* Q, long ldq, const void* K, long ldk, long kss, const void* V, long ldv, long vss,
+                                         void* O, long ldo, int Lq_pad, int n_heads, int shard_rows, int shard_valid, int n_shards,
+                                         float scale, int skip_shard, float* lse_out, const float* lse_in, const uint32_t* bits,
+                                         int mask_heads, int row_words, int bit0, int bit_shard_stride, const int32_t* order,
+                                         mc_stream s) {
+  const mc::AttnParams a = attn_op(Q, ldq, K, ldk, kss, V, ldv, vss, O, ldo, Lq_pad, n_heads, shard_rows, shard_valid, n_shards, scale,
+                                   skip_shard >= 0 ? skip_shard + 1 : 0, lse_in, lse_out);
+  hipError_t err = mc::launch_attention_sparse_shards(a, mc::AttnShardMask{bits, mask_heads, row_words, bit0, bit_shard_stride, order},
+                                                      (hipStream_t)s);
+  if (err == hipErrorInvalidValue)
+    return fail(MC_EINVAL, "attention_sparse_shards: needs Lq_pad %% 256 == 0, shard_rows %% 64 == 0, 1 <= shard_valid <= shard_rows, leading "
+                           "dimensions %% 8 == 0 and >= n_heads * 128, operands non-null and 16-byte aligned, lse arrays 16-byte aligned, "
+                           "a shard left after skip_shard (%d of %d), shard strides >= 0 and %% 8 == 0, the K / V span within 32-bit byte "
+                           "offsets, a non-null 4-byte aligned tile mask, mask_heads 1 or n_heads (%d), bit0 (%d) and bit_shard_stride "
+                           "(%d) >= 0 and every addressed bit below 32 * row_words (%d)",
+                skip_shard, n_shards, mask_heads, bit0, bit_shard_stride, row_words);
+  HIP_TRY(err);
+  return MC_OK;
+}
+
 mc_status mc_op_attn_merge(const void* const* o_parts, const float* const* lse_parts, int n, void* out, long ldo, int rows,
                            int rows_pad, int d, mc_stream s) {
   if (!o_parts || !lse_parts || !out) return fail(MC_EINVAL, "attn_merge: null argument");

@@ -227,6 +227,21 @@ class Engine(EngineHost):
         words = pack_tile_mask(m)                                       # int32 [mask_heads, nqt, words], host
         check(self.lib.mc_set_attention_tile_mask(self.h, words.data_ptr(), m.shape[0], m.shape[1], m.shape[2], int(dense_layers)))
 
+    def set_sharded_attention_tile_mask(self, mask, dense_layers=0):
+        """The static block mask of a sequence-parallel engine (mc_set_attention_tile_mask_sharded): mask is a bool tensor
+        [mask_heads, Lp / 128, P * Lp / 64] -- this rank's query tiles against the key tiles of every rank's shard, column
+        p * (Lp / 64) + t = key tile t of rank p (sparse_masks.shard_tile_cover builds one); None turns it off.  Every launch of a
+        sparse block's attention chain then visits only its visible tiles.  Raises on an engine that is not sequence parallel."""
+        if mask is None:
+            check(self.lib.mc_set_attention_tile_mask_sharded(self.h, None, 0, 0, 0, 0))
+            return
+        from .sparse_masks import pack_tile_mask
+        m = torch.as_tensor(mask).detach().cpu()
+        if m.dtype != torch.bool or m.dim() != 3:
+            raise ValueError(f"set_sharded_attention_tile_mask: a bool tensor [mask_heads, Lp / 128, P * Lp / 64], got {m.dtype} {tuple(m.shape)}")
+        words = pack_tile_mask(m)                                       # int32 [mask_heads, nqt, words], host
+        check(self.lib.mc_set_attention_tile_mask_sharded(self.h, words.data_ptr(), m.shape[0], m.shape[1], m.shape[2], int(dense_layers)))
+
     @property
     def attention_tile_mask(self):
         """(mask_heads, nqt, nkt, dense_layers, density) of the mask in force, or None"""

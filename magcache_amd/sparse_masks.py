@@ -56,6 +56,29 @@ def tile_cover(vis, L):
     return torch.from_numpy(out)
 
 
+def shard_tile_cover(vis, L, rank, P):
+    """tile_cover in the tile space of a sequence-parallel engine (Engine.set_sharded_attention_tile_mask): rank p holds the
+    tokens [p Lr, (p + 1) Lr), Lr = L / P, as rows 0 .. Lr - 1 of a shard padded to Lp = padded_len(Lr).  Returns bool
+    [Lp / 128, P * Lp / 64] for `rank`: row qt = this rank's query tile qt, column p * (Lp / 64) + t = key tile t of rank p's shard
+    -- tiles are counted per shard, because Lr need not be a multiple of 64.  vis as in tile_cover (indices are global
+    tokens); like tile_cover, for small sizes.  P = 1 is tile_cover."""
+    L, rank, P = int(L), int(rank), int(P)
+    if P < 1 or L % P or not 0 <= rank < P:
+        raise ValueError(f"shard_tile_cover: L {L} must divide into P {P} shards and rank {rank} lie in [0, P)")
+    Lr = L // P
+    Lp = padded_len(Lr)
+    nqt, tpr = Lp // QT, Lp // KT
+    out = np.zeros((nqt, P * tpr), dtype=bool)
+    j = np.arange(L)
+    for qt in range((Lr + QT - 1) // QT):
+        i = rank * Lr + np.arange(qt * QT, min((qt + 1) * QT, Lr))
+        rows = vis(i[:, None], j[None, :]) if callable(vis) else np.asarray(torch.as_tensor(vis)[i[0]:i[-1] + 1].cpu().numpy())
+        cols = np.zeros((P, tpr * KT), dtype=bool)
+        cols[:, :Lr] = np.asarray(rows, dtype=bool).any(0).reshape(P, Lr)
+        out[qt] = cols.reshape(P * tpr, KT).any(1)
+    return torch.from_numpy(out)
+
+
 def joint_tile_mask(image_mask, text_first, txt_len, img_tokens):
     """Lift a mask over the IMAGE tokens to the joint rows of an MM-DiT engine (MMDiTEngine.set_attention_tile_mask).
     image_mask: bool [mask_heads, >= ceil(Li / 128), >= ceil(Li / 64)] over tiles of the Li = img_tokens image tokens counted

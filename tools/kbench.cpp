@@ -1,7 +1,7 @@
 // Torch-free kernel A/B harness for the two MFMA-bound kernels at the Wan2.1-1.3B 480p shapes, through the C ABI.
 //
 //   kbench.bin <what> <rounds> <launches> libA.so [libB.so ...]
-//      what: gemm | attn | attn_mx8 | attn_band | attn_sparse | attn_joint | attn_predict | attn_predict_sparse | calib | all
+//      what: gemm | attn | attn_mx8 | attn_band | attn_sparse | attn_sparse_sp | attn_joint | attn_predict | attn_predict_sparse | calib | all
 //      (attn_joint: the MM-DiT joint shapes, HunyuanVideo 720p and FLUX 1024^2; KBENCH_JOINT picks another)
 //
 // Every library given on the command line is dlopen'ed privately (RTLD_LOCAL), so build variants of
@@ -44,6 +44,8 @@ struct Lib {
   decltype(&mc_op_attention_band) attn_band;      // null in a library older than the frame-block causal kernel (attn_band only)
   decltype(&mc_op_attention_sparse) attn_sparse;  // null in a library older than the tile-sparse kernel (attn_sparse only)
   decltype(&mc_op_attention_tile_predict) predict;  // null in a library older than the tile-mask predictor (attn_predict* only)
+  decltype(&mc_op_attention_partial) attn_partial;                 // the dense chain of attn_sparse_sp
+  decltype(&mc_op_attention_sparse_partial) attn_sparse_partial;   // null in a library older than the sharded tile-sparse kernel
   decltype(&mc_set_option) set_option;
   decltype(&mc_last_error) last_error;
 };
@@ -687,6 +689,134 @@ static void bench_attn_sparse(int Lq_pad, int H, int valid, int rounds, int laun
   for (int c = 0; c < NM; ++c) { CK(hipFree(bits_dev[c])); CK(hipFree(order_dev[c])); }
 }
 
+// The self-attention chain of ONE rank of a sequence-parallel engine at the 1.3B 480p sp 4 geometry: 32760 tokens, 8190 per rank
+// padded to 8192 query rows, 12 heads; the local shard ("kv_local" [8192][k | v]) with lse_out, then one gather round of 4 x 8192
+// keys with this rank's shard skipped, merged in place through the lse.  The dense chain (mc_op_attention_partial of the LAST
+// library given: the parent commit's build when one is named) and library 0's mc_op_attention_sparse_partial chain with all bits
+// set and with the sharded cover of sparse_masks.temporal_decay_tile_mask's rule, interleaved round by round.
+static void bench_attn_sparse_sp(int rounds, int launches) {
+  const Lib &lib = g_libs[0], &base = g_libs.back();
+  if (!lib.attn_sparse_partial || !base.attn_partial) {
+    fprintf(stderr, "no mc_op_attention_sparse_partial (library 0) / mc_op_attention_partial (last library)\n");
+    exit(2);
+  }
+  const int P = 4, rank = 1, H = 12, D = H * 128, L = 32760, Lr = L / P, Lp = 8192, F = 21, tpf = L / F;
+  const int nqt = Lp / 128, tpr = Lp / 64, words = (P * tpr + 31) / 32, vk = (Lr + 63) / 64, vq = (Lr + 127) / 128;
+  typedef std::vector<uint32_t> Bits;   // [nqt][words]
+  auto span = [&](Bits& m, int qt, int k_lo, int k_hi) {   // global keys k_lo .. k_hi (inclusive) -> their tiles in every shard
+    for (int p = 0; p < P; ++p) {
+      const int lo = std::max(k_lo, p * Lr) - p * Lr, hi = std::min(k_hi, (p + 1) * Lr - 1) - p * Lr;
+      for (int kt = lo / 64; lo <= hi && kt <= hi / 64; ++kt) m[(size_t)qt * words + ((p * tpr + kt) >> 5)] |= 1u << ((p * tpr + kt) & 31);
+    }
+  };
+  auto decay_cover = [&](int dense, int sink) {   // sparse_masks.shard_tile_cover of temporal_decay_tile_mask's rule, by intervals
+    Bits m((size_t)nqt * words, 0);
+    for (int qt = 0; qt < vq; ++qt) {
+      const int q0 = rank * Lr + qt * 128, q1 = rank * Lr + std::min(qt * 128 + 127, Lr - 1);
+      for (int fi = q0 / tpf; fi <= q1 / tpf; ++fi) {
+        const int a = std::max(q0, fi * tpf) - fi * tpf, b = std::min(q1, fi * tpf + tpf - 1) - fi * tpf;
+        for (int fj = 0; fj < F; ++fj) {
+          const int d = std::abs(fi - fj);
+          if (d < dense || fj < sink) { span(m, qt, fj * tpf, fj * tpf + tpf - 1); continue; }
+          int s = 1;
+          while ((dense << s) <= d) ++s;
+          const int w = (tpf + (1 << s) - 1) / (1 << s) - 1;
+          span(m, qt, fj * tpf + std::max(a - w, 0), fj * tpf + std::min(b + w, tpf - 1));
+        }
+      }
+    }
+    return m;
+  };
+  struct MaskCase { const char* name; Bits bits; };
+  const std::vector<MaskCase> cases = {{"all bits set", Bits((size_t)nqt * words, 0xffffffffu)}, {"decay 1:1", decay_cover(1, 1)},
+                                       {"decay 2:1", decay_cover(2, 1)}};
+  const int NM = (int)cases.size();
+  std::vector<uint32_t*> bits_dev(NM);
+  std::vector<double> density(NM);
+  for (int c = 0; c < NM; ++c) {
+    double visited = 0;
+    for (int qt = 0; qt < vq; ++qt)
+      for (int p = 0; p < P; ++p)
+        for (int kt = 0; kt < vk; ++kt) visited += (cases[c].bits[(size_t)qt * words + ((p * tpr + kt) >> 5)] >> ((p * tpr + kt) & 31)) & 1;
+    density[c] = visited / ((double)vq * P * vk);
+    CK(hipMalloc(&bits_dev[c], cases[c].bits.size() * 4));
+    CK(hipMemcpy(bits_dev[c], cases[c].bits.data(), cases[c].bits.size() * 4, hipMemcpyHostToDevice));
+  }
+  const size_t nq = (size_t)Lp * D, nkv = (size_t)Lp * 2 * D;
+  uint16_t *Q, *KVl, *KVg, *O, *Ob;
+  float *lse, *lse_b;
+  CK(hipMalloc(&Q, nq * 2)); CK(hipMalloc(&O, nq * 2)); CK(hipMalloc(&Ob, nq * 2));
+  CK(hipMalloc(&KVl, nkv * 2)); CK(hipMalloc(&KVg, P * nkv * 2));
+  CK(hipMalloc(&lse, (size_t)H * Lp * 4)); CK(hipMalloc(&lse_b, (size_t)H * Lp * 4));
+  fill_bf16<<<2048, 256>>>(Q, nq, 11, g_amp);
+  fill_bf16<<<2048, 256>>>(KVg, P * nkv, 12, g_amp);
+  CK(hipMemcpy(KVl, KVg + (size_t)rank * nkv, nkv * 2, hipMemcpyDeviceToDevice));
+  CK(hipDeviceSynchronize());
+  const float scale = 1.0f / std::sqrt(128.0f);
+  const long ld = 2L * D, stride = (long)Lp * ld;
+  auto launch = [&](int kind) {   // 0: the dense chain; 1 .. NM: the sparse chain under mask kind - 1
+    if (kind == 0) {
+      MCL(base, base.attn_partial(Q, D, KVl, ld, 0, KVl + D, ld, 0, O, D, Lp, H, Lp, Lr, 1, scale, -1, lse, nullptr, nullptr));
+      MCL(base, base.attn_partial(Q, D, KVg, ld, stride, KVg + D, ld, stride, O, D, Lp, H, Lp, Lr, P, scale, rank, nullptr, lse, nullptr));
+      return;
+    }
+    const uint32_t* bits = bits_dev[kind - 1];
+    MCL(lib, lib.attn_sparse_partial(Q, D, KVl, ld, 0, KVl + D, ld, 0, Ob, D, Lp, H, Lp, Lr, 1, scale, -1, lse_b, nullptr, bits, 1, words,
+                                     rank * tpr, 0, nullptr, nullptr));
+    MCL(lib, lib.attn_sparse_partial(Q, D, KVg, ld, stride, KVg + D, ld, stride, Ob, D, Lp, H, Lp, Lr, P, scale, rank, nullptr, lse_b, bits, 1,
+                                     words, 0, tpr, nullptr, nullptr));
+  };
+  const int NK = NM + 1;
+  printf("# attn_sparse_sp: rank %d of %d, %d query rows (%d valid), %d heads, local shard + one round of %d x %d keys (own skipped)\n", rank, P,
+         Lp, Lr, H, P, Lp);
+  hipEvent_t a, b;
+  CK(hipEventCreate(&a));
+  CK(hipEventCreate(&b));
+  float ms = 0;
+  CK(hipEventRecord(a, nullptr));
+  do {   // ~1 s warm-up of all of them
+    for (int kind = 0; kind < NK; ++kind) launch(kind);
+    CK(hipEventRecord(b, nullptr));
+    CK(hipEventSynchronize(b));
+    CK(hipEventElapsedTime(&ms, a, b));
+  } while (ms < 1000.f);
+  std::vector<std::vector<double>> t(NK);
+  for (int r = 0; r < rounds; ++r)
+    for (int kind = 0; kind < NK; ++kind) {
+      launch(kind);
+      CK(hipEventRecord(a, nullptr));
+      for (int i = 0; i < launches; ++i) launch(kind);
+      CK(hipEventRecord(b, nullptr));
+      CK(hipEventSynchronize(b));
+      CK(hipEventElapsedTime(&ms, a, b));
+      t[kind].push_back(ms / launches);
+    }
+  std::vector<double> med(NK);
+  for (int kind = 0; kind < NK; ++kind) {
+    std::sort(t[kind].begin(), t[kind].end());
+    med[kind] = t[kind][t[kind].size() / 2];
+  }
+  printf("%-22s median %8.4f ms %8.1f TF | min %8.4f ms\n", "dense chain", med[0], 4.0 * Lr * (double)L * D * 1e-12 / (med[0] * 1e-3), t[0][0]);
+  for (int kind = 1; kind <= NM; ++kind)
+    printf("%-22s median %8.4f ms | min %8.4f ms | x%.3f of dense | density %.4f, ideal %8.4f ms, measured / ideal %.3f\n", cases[kind - 1].name,
+           med[kind], t[kind][0], med[kind] / med[0], density[kind - 1], density[kind - 1] * med[0], med[kind] / (density[kind - 1] * med[0]));
+  printf("break-even density (dense / all bits set, time taken as linear in the density): %.3f\n", med[0] / med[1]);
+  {   // all bits set against the dense chain: the largest element difference over the valid rows
+    launch(0);
+    launch(1);
+    CK(hipDeviceSynchronize());
+    std::vector<uint16_t> ho(nq), hb(nq);
+    CK(hipMemcpy(ho.data(), O, nq * 2, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(hb.data(), Ob, nq * 2, hipMemcpyDeviceToHost));
+    double worst = 0;
+    for (size_t i = 0; i < (size_t)Lr * D; ++i) worst = std::max(worst, (double)std::fabs(bf16_to_f(ho[i]) - bf16_to_f(hb[i])));
+    printf("  all bits set vs the dense chain: max |difference| %.3e\n", worst);
+  }
+  fflush(stdout);
+  for (void* p : {(void*)Q, (void*)KVl, (void*)KVg, (void*)O, (void*)Ob, (void*)lse, (void*)lse_b}) CK(hipFree(p));
+  for (int c = 0; c < NM; ++c) CK(hipFree(bits_dev[c]));
+}
+
 // The tile-mask predictor (library 0) beside the dense launch of the LAST library given (the parent commit's build, to compare
 // with it in one process; library 0's own when it is the only one), all launches interleaved round by round.
 //   with_sparse = false: the predictor alone at mass 0.9 on randn operands (its cost does not depend on the content).
@@ -942,7 +1072,7 @@ static void bench_calib(int M, int D, int rounds, int launches) {
 
 int main(int argc, char** argv) {
   if (argc < 5) {
-    fprintf(stderr, "usage: kbench.bin <gemm|attn|attn_mx8|attn_band|attn_sparse|attn_joint|attn_predict|attn_predict_sparse|attn_keys|calib|all> <rounds> <launches> libA.so [libB.so ...]\n");
+    fprintf(stderr, "usage: kbench.bin <gemm|attn|attn_mx8|attn_band|attn_sparse|attn_sparse_sp|attn_joint|attn_predict|attn_predict_sparse|attn_keys|calib|all> <rounds> <launches> libA.so [libB.so ...]\n");
     return 2;
   }
   if (getenv("KBENCH_AMP")) g_amp = (float)atof(getenv("KBENCH_AMP"));
@@ -964,6 +1094,8 @@ int main(int argc, char** argv) {
     l.attn_band = (decltype(l.attn_band))dlsym(l.h, "mc_op_attention_band");
     l.attn_sparse = (decltype(l.attn_sparse))dlsym(l.h, "mc_op_attention_sparse");
     l.predict = (decltype(l.predict))dlsym(l.h, "mc_op_attention_tile_predict");
+    l.attn_partial = (decltype(l.attn_partial))dlsym(l.h, "mc_op_attention_partial");
+    l.attn_sparse_partial = (decltype(l.attn_sparse_partial))dlsym(l.h, "mc_op_attention_sparse_partial");
     l.set_option = (decltype(l.set_option))dlsym(l.h, "mc_set_option");
     l.last_error = (decltype(l.last_error))dlsym(l.h, "mc_last_error");
     if (!l.gemm || !l.attn || !l.calib || !l.set_option || !l.last_error) {
@@ -996,6 +1128,7 @@ int main(int argc, char** argv) {
   if (what == "attn_mx8") bench_attn_mx8(32768, 12, 32760, rounds, std::max(1, launches / 4));
   if (what == "attn_band") bench_attn_band(32768, 12, 32760, rounds, std::max(1, launches / 4));
   if (what == "attn_sparse") bench_attn_sparse(32768, 12, 32760, rounds, std::max(1, launches / 4));
+  if (what == "attn_sparse_sp") bench_attn_sparse_sp(rounds, std::max(1, launches / 4));
   if (what == "attn_predict") bench_attn_predict(32768, 12, 32760, rounds, std::max(1, launches / 4), false);
   if (what == "attn_predict_sparse") bench_attn_predict(32768, 12, 32760, rounds, std::max(1, launches / 4), true);
   if (what == "attn_joint") {
