@@ -173,7 +173,8 @@ mc_status mc_create(const mc_config* cfg, mc_engine** out);
  * mc_engine_causal_blocks, mc_op_attention_band; the tile-sparse self-attention adds calls only: mc_set_attention_tile_mask,
  * mc_engine_attention_tile_mask, mc_op_attention_sparse; the predicted tile mask adds calls only: mc_set_attention_tile_mass,
  * mc_engine_attention_tile_mass, mc_read_attention_tile_mask, mc_op_attention_tile_predict / _scratch; the sharded tile mask adds calls
- * only: mc_set_attention_tile_mask_sharded, mc_op_attention_sparse_partial; mc_version() names the library's. */
+ * only: mc_set_attention_tile_mask_sharded, mc_op_attention_sparse_partial; the sharded causal blocks add calls only:
+ * mc_set_causal_blocks_sharded, mc_op_attention_band_partial; mc_version() names the library's. */
 mc_status mc_create_sized(const mc_config* cfg, size_t cfg_bytes, mc_engine** out);
 void mc_destroy(mc_engine* e);
 /* 1: this engine's quantised Linears are MXFP4 (it was created under mc_set_option("mx_fp4", 1) with fp8_linear 2 | 3); else 0 */
@@ -193,6 +194,17 @@ int mc_engine_attn_mx8(const mc_engine* e);
  * names which.  mc_engine_causal_blocks reads the two values back (NULL outputs are skipped). */
 mc_status mc_set_causal_blocks(mc_engine* e, int frames_per_block, int window_blocks);
 mc_status mc_engine_causal_blocks(const mc_engine* e, int* frames_per_block, int* window_blocks);
+/* The same band on a SEQUENCE-PARALLEL engine (sp_size > 1 or sp_phases; MC_ESTATE on any other: mc_set_causal_blocks is its call).
+ * The blocks are blocks of the WHOLE sequence: block_tokens = frames_per_block * Hp * Wp of the grid in force counts global tokens,
+ * rank r holds tokens [r Lr, (r + 1) Lr) (Lr: this rank's valid rows), and a block may straddle ranks.  Every launch of the
+ * self-attention chain of every block (VACE blocks included) -- the local shard and each gather round -- then runs on
+ * attention_band_shards.hip under the semantics stated at mc_op_attention_band_partial, always in the chained form (merged in
+ * place by the log-sum-exp, whatever the option "sp_attn_partials" says); a launch whose shards this rank cannot see loads
+ * nothing.  0, 0 turns it off: every launch afterwards is the one an engine makes that never heard of the call.  Between
+ * forwards only (MC_ESTATE between mc_embed and mc_head).  MC_EINVAL: a negative argument, an "attn_mx8" engine, while a sharded
+ * tile mask is set (mc_set_attention_tile_mask_sharded, which in turn is refused while this is on); the error text names which.
+ * mc_engine_causal_blocks reads the two values back. */
+mc_status mc_set_causal_blocks_sharded(mc_engine* e, int frames_per_block, int window_blocks);
 /* Tile-sparse self-attention: one static block mask over (128-row query tile, 64-key tile) of the flattened sequence -- the
  * contract training-free sparse video-DiT methods share (temporal decay, sink + local windows, per-head spatial / temporal
  * heads, sliding tiles).  bits_host: uint32 [mask_heads][nqt][(nkt + 31) / 32] on the HOST, under the semantics stated at
@@ -809,6 +821,28 @@ mc_status mc_op_attention_sparse_partial(const void* Q_dev, long ldq, const void
                                          float* lse_out_dev, const float* lse_in_dev, const uint32_t* bits_dev, int mask_heads,
                                          int row_words, int bit0, int bit_shard_stride, const int32_t* order_dev,
                                          mc_stream stream);
+/* Frame-block causal / windowed self-attention over key shards, with the log-sum-exp (attention_band_shards.hip):
+ * mc_op_attention_partial's arguments and meaning -- n_shards shards of shard_rows rows (multiple of 64), the first shard_valid of
+ * each are keys, skip_shard >= 0 leaves that shard out, lse_out / lse_in as there --, restricted by mc_op_attention_band's band
+ * stated in GLOBAL tokens, so that each rank of a sequence-parallel job, and each launch of its chain, names where its rows stand:
+ *   - query row i stands at global token gq = q_tok0 + min(i, q_valid - 1) (rows >= q_valid behave as the last valid row) and
+ *     belongs to block b = gq / block_tokens;
+ *   - key row j (j < shard_valid) of shard s stands at global token key_tok0 + s * key_tok_stride + j;
+ *   - the row sees the key iff lo(b) <= that token < hi(b), hi(b) = (b + 1) * block_tokens,
+ *     lo(b) = 0 when window_blocks == 0, else max(0, b - window_blocks + 1) * block_tokens;
+ *   - a row that sees no key in this launch: without lse_in, O = 0 exactly and lse_out = -inf; with lse_in, O is not touched
+ *     and lse_out = lse_in.  A row whose lse_in is -inf takes this launch's result alone.  No NaN arises;
+ *   - block_tokens at or above every token is mc_op_attention_partial.
+ * A workgroup loads only the key tiles of the shards its 128 query rows can see: a shard wholly outside their band (every later
+ * rank's under a causal band) costs nothing.  Refused with MC_EINVAL, nothing launched: what mc_op_attention_sparse_partial refuses
+ * of the shape, the operands, the skip, the strides and the span; block_tokens < 1, window_blocks < 0, q_valid outside
+ * 1..Lq_pad, a negative q_tok0, key_tok0 or key_tok_stride, a global token at or beyond 2^31 (with a window: more than
+ * 16383 * 128 query rows). */
+mc_status mc_op_attention_band_partial(const void* Q_dev, long ldq, const void* K_dev, long ldk, long k_shard_stride,
+                                       const void* V_dev, long ldv, long v_shard_stride, void* O_dev, long ldo, int Lq_pad,
+                                       int n_heads, int shard_rows, int shard_valid, int n_shards, float scale, int skip_shard,
+                                       float* lse_out_dev, const float* lse_in_dev, int block_tokens, int window_blocks, int q_tok0,
+                                       int q_valid, int key_tok0, int key_tok_stride, mc_stream stream);
 /* the join of the two-stream attention chain (sequence parallel, sp_attn_partials): out[row, head] = sum_i w_i O_i / sum_i w_i
  * with w_i = 2^(lse_i[head][row] - max_i lse_i) over n (1..9) normalised partial results on disjoint key sets; o_parts / lse_parts
  * are HOST arrays of n device pointers (bf16 [rows][ldo] each / fp32 [d / 128][rows_pad] each, log2 units) */

@@ -52,6 +52,7 @@ SIGNATURES = {
     "mc_engine_attn_mx8": (_i, [_vp]),
     "mc_set_causal_blocks": (_i, [_vp, _i, _i]),
     "mc_engine_causal_blocks": (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
+    "mc_set_causal_blocks_sharded": (_i, [_vp, _i, _i]),
     "mc_set_attention_tile_mask": (_i, [_vp, _vp, _i, _i, _i, _i]),
     "mc_set_attention_tile_mask_sharded": (_i, [_vp, _vp, _i, _i, _i, _i]),
     "mc_engine_attention_tile_mask": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_d)]),
@@ -141,6 +142,8 @@ SIGNATURES = {
     "mc_op_attention_partial": (_i, [_vp, _l, _vp, _l, _l, _vp, _l, _l, _vp, _l, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp]),
     "mc_op_attention_sparse_partial": (_i, [_vp, _l, _vp, _l, _l, _vp, _l, _l, _vp, _l, _i, _i, _i, _i, _i, _f, _i, _vp, _vp,
                                             _vp, _i, _i, _i, _i, _vp, _vp]),
+    "mc_op_attention_band_partial": (_i, [_vp, _l, _vp, _l, _l, _vp, _l, _l, _vp, _l, _i, _i, _i, _i, _i, _f, _i, _vp, _vp,
+                                          _i, _i, _i, _i, _i, _i, _vp]),
     "mc_op_attn_merge": (_i, [_vp, _vp, _i, _vp, _l, _i, _i, _i, _vp]),
     "mc_op_ln_modulate": (_i, [_vp, _l, _vp, _l, _vp, _vp, _i, _f, _vp, _l, _vp, _l, _i, _i, _vp]),
     "mc_op_rmsnorm_rope": (_i, [_vp, _l, _vp, _f, _vp, _i, _i, _i, _vp]),

@@ -752,6 +752,28 @@ mc_status mc_set_causal_blocks(mc_engine* e, int frames_per_block, int window_bl
   e->causal_window = frames_per_block ? window_blocks : 0;
   return MC_OK;
 }
+// the same state on a sequence-parallel engine: sp_attn_launch reads it (attention_band_shards.hip); mc_set_causal_blocks keeps
+// refusing such an engine, so causal_frames != 0 with e->sp set means this call made it so
+mc_status mc_set_causal_blocks_sharded(mc_engine* e, int frames_per_block, int window_blocks) {
+  if (!e) return fail(MC_EINVAL, "null engine");
+  if (frames_per_block < 0 || window_blocks < 0)
+    return fail(MC_EINVAL, "mc_set_causal_blocks_sharded: frames_per_block (%d) and window_blocks (%d) must be >= 0", frames_per_block,
+                window_blocks);
+  if (e->phase_open) return fail(MC_ESTATE, "mc_set_causal_blocks_sharded between mc_embed and mc_head");
+  if (frames_per_block != 0 && e->attn_mx8)   // (asked first: such an engine is never sequence parallel, and this names why)
+    return fail(MC_EINVAL, "mc_set_causal_blocks_sharded: the engine was created under the option \"attn_mx8\" and the MX fp8 "
+                           "self-attention kernel has no mask");
+  if (!e->sp)
+    return fail(MC_ESTATE, "mc_set_causal_blocks_sharded needs a sequence-parallel engine (sp_size > 1 or sp_phases) (one GPU: "
+                           "mc_set_causal_blocks)");
+  if (frames_per_block != 0 && e->mask_heads)
+    return fail(MC_EINVAL, "mc_set_causal_blocks_sharded: a sharded attention tile mask is set (mc_set_attention_tile_mask_sharded); "
+                           "express the causal blocks in the mask, or turn the mask off first");
+  e->causal_frames = frames_per_block;
+  e->causal_window = frames_per_block ? window_blocks : 0;
+  e->attn_layer = -2;   // no chain of the other mode is continued
+  return MC_OK;
+}
 mc_status mc_engine_causal_blocks(const mc_engine* e, int* frames_per_block, int* window_blocks) {
   if (!e) return fail(MC_EINVAL, "null engine");
   if (frames_per_block) *frames_per_block = e->causal_frames;
@@ -839,8 +861,11 @@ mc_status mc_set_attention_tile_mask_sharded(mc_engine* e, const uint32_t* bits_
     e->mask_drop();
     return MC_OK;
   }
-  if (e->causal_frames || e->tile_mass > 0.f || e->attn_mx8)   // (none of the three can be on on a sequence-parallel engine today)
-    return fail(MC_EINVAL, "mc_set_attention_tile_mask_sharded: causal blocks, the attention tile mass or \"attn_mx8\" is on");
+  if (e->causal_frames)
+    return fail(MC_EINVAL, "mc_set_attention_tile_mask_sharded: mc_set_causal_blocks_sharded is on (%d frames per block); express the "
+                           "causal blocks in the mask, or turn them off first", e->causal_frames);
+  if (e->tile_mass > 0.f || e->attn_mx8)   // (neither can be on on a sequence-parallel engine today)
+    return fail(MC_EINVAL, "mc_set_attention_tile_mask_sharded: the attention tile mass or \"attn_mx8\" is on");
   const int tpr = e->Lp / 64;   // key tiles per rank
   if (nqt != e->Lp / 128 || nkt != e->P * tpr)
     return fail(MC_EINVAL, "mc_set_attention_tile_mask_sharded: %d x %d tiles, rank %d of %d (%d rows padded to %d) has %d x %d", nqt, nkt,
@@ -1406,7 +1431,10 @@ mc_status mc_block_pre_q(mc_engine* e, int layer, mc_stream stream_) {
 // mask_layer: the main layer whose dense_layers decides (a VACE block counts as the main layer it feeds).  With a sharded tile
 // mask (mc_set_attention_tile_mask_sharded) and mask_layer >= dense_layers the same chain runs on attention_sparse_shards.hip:
 // the local launch reads the bits of this rank's shard, round c the bits [c lc / 64, ...) of every rank's.
+// With sharded causal blocks (mc_set_causal_blocks_sharded) every layer's chain runs on attention_band_shards.hip, the band in
+// global tokens: this rank's queries stand at rank * Lr, the local shard's keys too, round c's at c * Lp / C of every rank.
 static bool sp_sparse_layer(const mc_engine* e, int mask_layer) { return e->mask_sharded && mask_layer >= e->mask_dense_layers; }
+static bool sp_in_place_layer(const mc_engine* e, int mask_layer) { return e->causal_frames || sp_sparse_layer(e, mask_layer); }
 static int sp_mask_layer(const mc_engine* e, const Layer& l) { return l.index < e->NL ? l.index : (l.index - e->NL) * e->cfg.vace_stride; }
 static mc_status sp_attn_launch(mc_engine* e, int layer, int mask_layer, int round, hipStream_t s) {
   attn_chain_open(e, layer);
@@ -1429,7 +1457,14 @@ static mc_status sp_attn_launch(mc_engine* e, int layer, int mask_layer, int rou
     Prof pr(e, MC_PROF_ATTN_SELF, s);   // measurement hook, see mc_profile_enable
     const Keys keys = sp_keys(e, round, e->attn_local_done);
     const float* lse_in = e->attn_launches ? lse : nullptr;
-    if (sp_sparse_layer(e, mask_layer)) {
+    if (e->causal_frames) {
+      const long block_tokens = (long)e->causal_frames * (e->cfg.latent_h / 2) * (e->cfg.latent_w / 2);
+      const mc::AttnParams a = mc::attn_params(e->buf<bf16_t>("qkv"), e->d, e->buf<bf16_t>("ao"), e->d, e->Lp, e->H, keys, mc::kAttnScale,
+                                               lse_in, more ? lse : nullptr);
+      const mc::AttnBandShards b = {(int)std::min<long>(block_tokens, (long)e->P * e->Lp), e->causal_window,   // >= every token: plain
+                                    e->rank * e->Lr, e->Lr, round < 0 ? e->rank * e->Lr : round * sp_chunk_rows(e), round < 0 ? 0 : e->Lr};
+      HIP_TRY(mc::launch_attention_band_shards(a, b, s));
+    } else if (sp_sparse_layer(e, mask_layer)) {
       MC_TRY(tile_mask_fits(e));   // (no launch may read past the mask)
       const int tpr = e->Lp / 64;
       const mc::AttnParams a = mc::attn_params(e->buf<bf16_t>("qkv"), e->d, e->buf<bf16_t>("ao"), e->d, e->Lp, e->H, keys, mc::kAttnScale,
@@ -1789,7 +1824,7 @@ mc_status mc_blocks_sp(mc_engine* e, int layer_begin, int layer_end, int branch,
     if (!overlap)
       for (int c = 0; c < R; ++c) MC_TRY(wait_round(l, c, s));
     MC_TRY(block_pre_q(e, ly, s));
-    if (!partials || sp_sparse_layer(e, sp_mask_layer(e, ly))) {   // a sparse layer always merges in place: attn_merge knows no -inf
+    if (!partials || sp_in_place_layer(e, sp_mask_layer(e, ly))) {   // a sparse or causal layer always merges in place: attn_merge knows no -inf
       MC_TRY(sp_attn_launch(e, chain_id, sp_mask_layer(e, ly), -1, s));
       for (int c = 0; c < R; ++c) {
         if (overlap) MC_TRY(wait_round(l, c, s));

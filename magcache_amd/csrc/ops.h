@@ -401,6 +401,26 @@ struct AttnShardMask { const uint32_t* bits; int mask_heads; int row_words; int 
 bool attention_sparse_shards_supports(const AttnParams& p, const AttnShardMask& m);
 hipError_t launch_attention_sparse_shards(const AttnParams& p, const AttnShardMask& m, hipStream_t stream);
 
+// ---------------------------------------------------------------- frame-block causal / windowed self-attention over key shards
+// (attention_band_shards.hip): the sequence-parallel form of the band -- AttnParams in its FULL form and the band in GLOBAL
+// tokens.  Query row i stands at global token gq = q_tok0 + min(i, q_valid - 1), in block b = gq / block_tokens.  It sees key row
+// j < shard_valid of shard s (s not the skipped one) iff lo(b) <= key_tok0 + s * key_tok_stride + j < hi(b), with
+// hi(b) = (b + 1) block_tokens and lo(b) = window_blocks ? max(0, b - window_blocks + 1) block_tokens : 0.  Rows
+// [shard_valid, shard_rows) of a shard and every row of the skipped shard are never counted.  lse_out, lse_in and a row that
+// sees no key in this launch: as stated at AttnShardMask, per ROW (no lse_in: zeros and -inf; lse_in: O untouched, lse handed
+// on; an lse_in of -inf: this launch's result alone).  No NaN arises from any of these.
+struct AttnBandShards {
+  int block_tokens, window_blocks;   // as AttnBand, in GLOBAL tokens
+  int q_tok0, q_valid;               // global token of query row 0; valid query rows (rows >= q_valid behave as row q_valid - 1)
+  int key_tok0, key_tok_stride;      // global token of key row 0 of shard 0; global tokens between row 0 of shard s and of shard s + 1
+};
+// attention_shape_ok and the pointer / alignment / ld / skip / stride / 32-bit-span / lse-alignment conditions of
+// attention_sparse_shards_supports; its own: block_tokens >= 1, window_blocks >= 0, 1 <= q_valid <= Lq_pad, q_tok0, key_tok0 and
+// key_tok_stride >= 0, every global token (the last valid query row, the last key of the last shard) below 2^31, fewer than 2^31
+// items and, with a window, at most 16383 query tiles of 128 rows.
+bool attention_band_shards_supports(const AttnParams& p, const AttnBandShards& b);
+hipError_t launch_attention_band_shards(const AttnParams& p, const AttnBandShards& b, hipStream_t stream);
+
 // ---------------------------------------------------------------- tile-sparse joint attention (attention_joint.hip)
 // The same bitmap, for a joint text + image sequence (MM-DiT).  With qdense = [q0, q1) in 128-row query tiles and kalways =
 // [k0, k1) in 64-key tiles, query row i of head h sees key j iff j < shard_valid and at least one of: i / 128 in qdense, j / 64

@@ -363,6 +363,26 @@ mc_status mc_op_attention_sparse_partial(const void* Q, long ldq, const void* K,
   return MC_OK;
 }
 
+// frame-block causal / windowed self-attention over key shards, with the log-sum-exp (attention_band_shards.hip)
+mc_status mc_op_attention_band_partial(const void* Q, long ldq, const void* K, long ldk, long kss, const void* V, long ldv, long vss,
+                                       void* O, long ldo, int Lq_pad, int n_heads, int shard_rows, int shard_valid, int n_shards,
+                                       float scale, int skip_shard, float* lse_out, const float* lse_in, int block_tokens,
+                                       int window_blocks, int q_tok0, int q_valid, int key_tok0, int key_tok_stride, mc_stream s) {
+  const mc::AttnParams a = attn_op(Q, ldq, K, ldk, kss, V, ldv, vss, O, ldo, Lq_pad, n_heads, shard_rows, shard_valid, n_shards, scale,
+                                   skip_shard >= 0 ? skip_shard + 1 : 0, lse_in, lse_out);
+  hipError_t err = mc::launch_attention_band_shards(a, mc::AttnBandShards{block_tokens, window_blocks, q_tok0, q_valid, key_tok0, key_tok_stride},
+                                                    (hipStream_t)s);
+  if (err == hipErrorInvalidValue)
+    return fail(MC_EINVAL, "attention_band_shards: needs Lq_pad %% 256 == 0, shard_rows %% 64 == 0, 1 <= shard_valid <= shard_rows, leading "
+                           "dimensions %% 8 == 0 and >= n_heads * 128, operands non-null and 16-byte aligned, lse arrays 16-byte aligned, "
+                           "a shard left after skip_shard (%d of %d), shard strides >= 0 and %% 8 == 0, the K / V span within 32-bit byte "
+                           "offsets, block_tokens (%d) >= 1, window_blocks (%d) >= 0, 1 <= q_valid (%d) <= Lq_pad, q_tok0 (%d), key_tok0 (%d) "
+                           "and key_tok_stride (%d) >= 0 and every global token below 2^31",
+                skip_shard, n_shards, block_tokens, window_blocks, q_valid, q_tok0, key_tok0, key_tok_stride);
+  HIP_TRY(err);
+  return MC_OK;
+}
+
 mc_status mc_op_attn_merge(const void* const* o_parts, const float* const* lse_parts, int n, void* out, long ldo, int rows,
                            int rows_pad, int d, mc_stream s) {
   if (!o_parts || !lse_parts || !out) return fail(MC_EINVAL, "attn_merge: null argument");

@@ -202,6 +202,13 @@ class Engine(EngineHost):
         launch.  Refused on a sharded engine and on an attn_mx8 engine."""
         check(self.lib.mc_set_causal_blocks(self.h, int(frames_per_block), int(window_blocks)))
 
+    def set_sharded_causal_blocks(self, frames_per_block, window_blocks=0):
+        """The same mask on a sequence-parallel engine (mc_set_causal_blocks_sharded): the blocks are blocks of the whole
+        sequence, whichever rank holds their tokens, and every launch of a block's attention chain loads only the key tiles
+        this rank's rows can see.  0 turns it off.  Raises on an engine that is not sequence parallel, on an attn_mx8 engine
+        and while a sharded tile mask is set."""
+        check(self.lib.mc_set_causal_blocks_sharded(self.h, int(frames_per_block), int(window_blocks)))
+
     @property
     def causal_blocks(self):
         """(frames_per_block, window_blocks) in force; (0, 0) = plain attention"""

@@ -123,7 +123,8 @@ class WanModelHIP(LoraModel):
         what Wan2.2 TI2V's `mask * t` needs.
         attn_mx8: self-attention on the opt-in MX fp8 kernel (Engine(..., attn_mx8=True)); self.attn_mx8 is what the engine latched.
         causal_block_frames (>= 1): self-attention block-causal over blocks of that many latent frames, causal_window_blocks
-        (>= 1) only over the last so many blocks (Engine.set_causal_blocks): set once here, kept across set_geometry
+        (>= 1) only over the last so many blocks (Engine.set_causal_blocks; on a sequence-parallel engine
+        Engine.set_sharded_causal_blocks): set once here, kept across set_geometry
         (dynamic_geometry) because the engine counts the block in frames.  MagCache, CFG pairs and per-frame timesteps need
         no change.  wan22.make_experts passes both keywords through.
         attention_tile_mask: tile-sparse self-attention (Engine.set_attention_tile_mask) for the blocks >= sparse_dense_layers --
@@ -151,7 +152,8 @@ class WanModelHIP(LoraModel):
                                        sp_rank=sp_rank, sp_size=sp_size, sp_phases=sp_phases, attn_mx8=attn_mx8)
         self.attn_mx8 = getattr(self.engine, "attn_mx8", False)     # (an engine passed in may predate the option)
         if causal_block_frames or causal_window_blocks:
-            self.engine.set_causal_blocks(causal_block_frames, causal_window_blocks)
+            sharded = getattr(self.engine, "sharded", False)     # a sequence-parallel engine: the band in global tokens
+            (self.engine.set_sharded_causal_blocks if sharded else self.engine.set_causal_blocks)(causal_block_frames, causal_window_blocks)
         self._tile_mask, self._sparse_dense_layers = None, 0
         if attention_tile_mask is not None:
             self.set_attention_tile_mask(attention_tile_mask, sparse_dense_layers)

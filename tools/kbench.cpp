@@ -1,7 +1,7 @@
 // Torch-free kernel A/B harness for the two MFMA-bound kernels at the Wan2.1-1.3B 480p shapes, through the C ABI.
 //
 //   kbench.bin <what> <rounds> <launches> libA.so [libB.so ...]
-//      what: gemm | attn | attn_mx8 | attn_band | attn_sparse | attn_sparse_sp | attn_joint | attn_predict | attn_predict_sparse | calib | all
+//      what: gemm | attn | attn_mx8 | attn_band | attn_sparse | attn_sparse_sp | attn_band_sp | attn_joint | attn_predict | attn_predict_sparse | calib | all
 //      (attn_joint: the MM-DiT joint shapes, HunyuanVideo 720p and FLUX 1024^2; KBENCH_JOINT picks another)
 //
 // Every library given on the command line is dlopen'ed privately (RTLD_LOCAL), so build variants of
@@ -46,6 +46,7 @@ struct Lib {
   decltype(&mc_op_attention_tile_predict) predict;  // null in a library older than the tile-mask predictor (attn_predict* only)
   decltype(&mc_op_attention_partial) attn_partial;                 // the dense chain of attn_sparse_sp
   decltype(&mc_op_attention_sparse_partial) attn_sparse_partial;   // null in a library older than the sharded tile-sparse kernel
+  decltype(&mc_op_attention_band_partial) attn_band_partial;       // null in a library older than the sharded band kernel (attn_band_sp only)
   decltype(&mc_set_option) set_option;
   decltype(&mc_last_error) last_error;
 };
@@ -817,6 +818,142 @@ static void bench_attn_sparse_sp(int rounds, int launches) {
   for (int c = 0; c < NM; ++c) CK(hipFree(bits_dev[c]));
 }
 
+// The self-attention chain of EVERY rank of a sequence-parallel engine under sharded causal blocks, at the 1.3B 480p sp 4
+// geometry with 4 gather rounds: 32760 tokens, 8190 per rank padded to 8192 query rows, 12 heads; the local shard with lse_out,
+// then rounds c = 0 .. 3 of 4 x 2048 rows (2046 valid in the last) with this rank's shard skipped, merged in place through the
+// lse -- the launches and arguments of sp_attn_launch.  The dense chain (mc_op_attention_partial of the LAST library given; it
+// does not depend on the rank) and library 0's mc_op_attention_band_partial chain per (rank, band), interleaved round by round.
+// The visited-tile fraction is the kernel's own walk (item's first row's lo .. last row's hi per shard) counted on the host.
+static void bench_attn_band_sp(int rounds, int launches) {
+  const Lib &lib = g_libs[0], &base = g_libs.back();
+  if (!lib.attn_band_partial || !base.attn_partial) {
+    fprintf(stderr, "no mc_op_attention_band_partial (library 0) / mc_op_attention_partial (last library)\n");
+    exit(2);
+  }
+  const int P = 4, C = 4, H = 12, D = H * 128, L = 32760, Lr = L / P, Lp = 8192, Lc = Lp / C, F = 21, tpf = L / F, vq = (Lr + 127) / 128;
+  struct BandCase { const char* name; int frames, window; };
+  const std::vector<BandCase> cases = {{"causal 21 blocks", 1, 0}, {"causal 7 blocks", 3, 0}, {"causal 3 blocks", 7, 0}, {"21 blocks window 3", 1, 3}};
+  const int NB = (int)cases.size();
+  auto round_valid = [&](int c) { return std::max(0, std::min(Lc, Lr - c * Lc)); };
+  auto tiles = [&](long glo, long ghi, long key0, int valid) {   // visited tiles of one shard: BandShards::tiles
+    const long a = std::min<long>(std::max<long>(glo - key0, 0), valid), b = std::min<long>(std::max<long>(ghi - key0, 0), valid);
+    return b > a ? (int)((b - 1) / 64 - a / 64 + 1) : 0;
+  };
+  auto fraction = [&](int rank, const BandCase& bc) {
+    const long bt = (long)bc.frames * tpf;
+    double visited = 0, dense = 0;
+    for (int qt = 0; qt < vq; ++qt) {
+      const long b0 = ((long)rank * Lr + std::min(qt * 128, Lr - 1)) / bt, b1 = ((long)rank * Lr + std::min(qt * 128 + 127, Lr - 1)) / bt;
+      const long glo = bc.window ? std::max(0l, b0 - bc.window + 1) * bt : 0, ghi = (b1 + 1) * bt;
+      visited += tiles(glo, ghi, (long)rank * Lr, Lr);
+      dense += (Lr + 63) / 64;
+      for (int c = 0; c < C; ++c)
+        for (int p = 0; p < P; ++p)
+          if (p != rank) {
+            visited += tiles(glo, ghi, (long)c * Lc + (long)p * Lr, round_valid(c));
+            dense += (round_valid(c) + 63) / 64;
+          }
+    }
+    return visited / dense;
+  };
+  const size_t nq = (size_t)Lp * D, nkv = (size_t)Lp * 2 * D;
+  uint16_t *Q, *KVl, *KVg, *O, *Ob;
+  float *lse, *lse_b;
+  CK(hipMalloc(&Q, nq * 2)); CK(hipMalloc(&O, nq * 2)); CK(hipMalloc(&Ob, nq * 2));
+  CK(hipMalloc(&KVl, nkv * 2)); CK(hipMalloc(&KVg, P * nkv * 2));   // "kv_gather": [C][P][Lc][k | v]
+  CK(hipMalloc(&lse, (size_t)H * Lp * 4)); CK(hipMalloc(&lse_b, (size_t)H * Lp * 4));
+  fill_bf16<<<2048, 256>>>(Q, nq, 11, g_amp);
+  fill_bf16<<<2048, 256>>>(KVg, P * nkv, 12, g_amp);
+  fill_bf16<<<2048, 256>>>(KVl, nkv, 13, g_amp);
+  CK(hipDeviceSynchronize());
+  const float scale = 1.0f / std::sqrt(128.0f);
+  const long ld = 2L * D, stride = (long)Lc * ld;
+  auto launch = [&](int kind) {   // 0: the dense chain (as rank 1); 1 + rank * NB + band: the band chain
+    if (kind == 0) {
+      MCL(base, base.attn_partial(Q, D, KVl, ld, 0, KVl + D, ld, 0, O, D, Lp, H, Lp, Lr, 1, scale, -1, lse, nullptr, nullptr));
+      for (int c = 0; c < C; ++c) {
+        const uint16_t* kv = KVg + (size_t)c * P * Lc * ld;
+        MCL(base, base.attn_partial(Q, D, kv, ld, stride, kv + D, ld, stride, O, D, Lp, H, Lc, round_valid(c), P, scale, 1,
+                                    c + 1 < C ? lse : nullptr, lse, nullptr));
+      }
+      return;
+    }
+    const int rank = (kind - 1) / NB;
+    const BandCase& bc = cases[(kind - 1) % NB];
+    const int bt = bc.frames * tpf;
+    MCL(lib, lib.attn_band_partial(Q, D, KVl, ld, 0, KVl + D, ld, 0, Ob, D, Lp, H, Lp, Lr, 1, scale, -1, lse_b, nullptr, bt, bc.window,
+                                   rank * Lr, Lr, rank * Lr, 0, nullptr));
+    for (int c = 0; c < C; ++c) {
+      const uint16_t* kv = KVg + (size_t)c * P * Lc * ld;
+      MCL(lib, lib.attn_band_partial(Q, D, kv, ld, stride, kv + D, ld, stride, Ob, D, Lp, H, Lc, round_valid(c), P, scale, rank,
+                                     c + 1 < C ? lse_b : nullptr, lse_b, bt, bc.window, rank * Lr, Lr, c * Lc, Lr, nullptr));
+    }
+  };
+  const int NK = 1 + P * NB;
+  printf("# attn_band_sp: %d ranks, %d query rows (%d valid) each, %d heads, local shard + %d rounds of %d x %d rows (own skipped)\n", P, Lp,
+         Lr, H, C, P, Lc);
+  hipEvent_t a, b;
+  CK(hipEventCreate(&a));
+  CK(hipEventCreate(&b));
+  float ms = 0;
+  CK(hipEventRecord(a, nullptr));
+  do {   // ~1 s warm-up of all of them
+    for (int kind = 0; kind < NK; ++kind) launch(kind);
+    CK(hipEventRecord(b, nullptr));
+    CK(hipEventSynchronize(b));
+    CK(hipEventElapsedTime(&ms, a, b));
+  } while (ms < 1000.f);
+  std::vector<std::vector<double>> t(NK);
+  for (int r = 0; r < rounds; ++r)
+    for (int kind = 0; kind < NK; ++kind) {
+      launch(kind);
+      CK(hipEventRecord(a, nullptr));
+      for (int i = 0; i < launches; ++i) launch(kind);
+      CK(hipEventRecord(b, nullptr));
+      CK(hipEventSynchronize(b));
+      CK(hipEventElapsedTime(&ms, a, b));
+      t[kind].push_back(ms / launches);
+    }
+  std::vector<double> med(NK);
+  for (int kind = 0; kind < NK; ++kind) {
+    std::sort(t[kind].begin(), t[kind].end());
+    med[kind] = t[kind][t[kind].size() / 2];
+  }
+  printf("%-22s median %8.4f ms %8.1f TF | min %8.4f ms\n", "dense chain", med[0], 4.0 * Lr * (double)L * D * 1e-12 / (med[0] * 1e-3), t[0][0]);
+  for (int bi = 0; bi < NB; ++bi) {
+    double worst = 0, sum = 0;
+    for (int rank = 0; rank < P; ++rank) {
+      const int kind = 1 + rank * NB + bi;
+      const double f = fraction(rank, cases[bi]);
+      printf("%-20s rank %d median %8.4f ms | min %8.4f ms | x%.3f of dense | visited %.4f, ideal %8.4f ms, measured / ideal %.3f\n",
+             cases[bi].name, rank, med[kind], t[kind][0], med[kind] / med[0], f, f * med[0], med[kind] / (f * med[0]));
+      worst = std::max(worst, med[kind]);
+      sum += med[kind];
+    }
+    printf("%-20s slowest rank %8.4f ms = x%.3f of dense, x%.3f of the ranks' mean (the imbalance of the contiguous split)\n", cases[bi].name,
+           worst, worst / med[0], worst * P / sum);
+  }
+  {   // one block of everything against the dense chain: the largest element difference over the valid rows
+    const int bt = L;
+    MCL(lib, lib.attn_band_partial(Q, D, KVl, ld, 0, KVl + D, ld, 0, Ob, D, Lp, H, Lp, Lr, 1, scale, -1, lse_b, nullptr, bt, 0, Lr, Lr, Lr, 0, nullptr));
+    for (int c = 0; c < C; ++c) {
+      const uint16_t* kv = KVg + (size_t)c * P * Lc * ld;
+      MCL(lib, lib.attn_band_partial(Q, D, kv, ld, stride, kv + D, ld, stride, Ob, D, Lp, H, Lc, round_valid(c), P, scale, 1,
+                                     c + 1 < C ? lse_b : nullptr, lse_b, bt, 0, Lr, Lr, c * Lc, Lr, nullptr));
+    }
+    launch(0);
+    CK(hipDeviceSynchronize());
+    std::vector<uint16_t> ho(nq), hb(nq);
+    CK(hipMemcpy(ho.data(), O, nq * 2, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(hb.data(), Ob, nq * 2, hipMemcpyDeviceToHost));
+    double worst = 0;
+    for (size_t i = 0; i < (size_t)Lr * D; ++i) worst = std::max(worst, (double)std::fabs(bf16_to_f(ho[i]) - bf16_to_f(hb[i])));
+    printf("  one block (rank 1) vs the dense chain: max |difference| %.3e\n", worst);
+  }
+  fflush(stdout);
+  for (void* p : {(void*)Q, (void*)KVl, (void*)KVg, (void*)O, (void*)Ob, (void*)lse, (void*)lse_b}) CK(hipFree(p));
+}
+
 // The tile-mask predictor (library 0) beside the dense launch of the LAST library given (the parent commit's build, to compare
 // with it in one process; library 0's own when it is the only one), all launches interleaved round by round.
 //   with_sparse = false: the predictor alone at mass 0.9 on randn operands (its cost does not depend on the content).
@@ -1072,7 +1209,7 @@ static void bench_calib(int M, int D, int rounds, int launches) {
 
 int main(int argc, char** argv) {
   if (argc < 5) {
-    fprintf(stderr, "usage: kbench.bin <gemm|attn|attn_mx8|attn_band|attn_sparse|attn_sparse_sp|attn_joint|attn_predict|attn_predict_sparse|attn_keys|calib|all> <rounds> <launches> libA.so [libB.so ...]\n");
+    fprintf(stderr, "usage: kbench.bin <gemm|attn|attn_mx8|attn_band|attn_sparse|attn_sparse_sp|attn_band_sp|attn_joint|attn_predict|attn_predict_sparse|attn_keys|calib|all> <rounds> <launches> libA.so [libB.so ...]\n");
     return 2;
   }
   if (getenv("KBENCH_AMP")) g_amp = (float)atof(getenv("KBENCH_AMP"));
@@ -1096,6 +1233,7 @@ int main(int argc, char** argv) {
     l.predict = (decltype(l.predict))dlsym(l.h, "mc_op_attention_tile_predict");
     l.attn_partial = (decltype(l.attn_partial))dlsym(l.h, "mc_op_attention_partial");
     l.attn_sparse_partial = (decltype(l.attn_sparse_partial))dlsym(l.h, "mc_op_attention_sparse_partial");
+    l.attn_band_partial = (decltype(l.attn_band_partial))dlsym(l.h, "mc_op_attention_band_partial");
     l.set_option = (decltype(l.set_option))dlsym(l.h, "mc_set_option");
     l.last_error = (decltype(l.last_error))dlsym(l.h, "mc_last_error");
     if (!l.gemm || !l.attn || !l.calib || !l.set_option || !l.last_error) {
@@ -1129,6 +1267,7 @@ int main(int argc, char** argv) {
   if (what == "attn_band") bench_attn_band(32768, 12, 32760, rounds, std::max(1, launches / 4));
   if (what == "attn_sparse") bench_attn_sparse(32768, 12, 32760, rounds, std::max(1, launches / 4));
   if (what == "attn_sparse_sp") bench_attn_sparse_sp(rounds, std::max(1, launches / 4));
+  if (what == "attn_band_sp") bench_attn_band_sp(rounds, std::max(1, launches / 4));
   if (what == "attn_predict") bench_attn_predict(32768, 12, 32760, rounds, std::max(1, launches / 4), false);
   if (what == "attn_predict_sparse") bench_attn_predict(32768, 12, 32760, rounds, std::max(1, launches / 4), true);
   if (what == "attn_joint") {
